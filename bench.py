@@ -65,6 +65,9 @@ def parse_args():
     ap.add_argument("--rehearse", action="store_true",
                     help="N > 1 on ONE GPU: every rank takes device (local rank mod device count) and the process group is gloo (RCCL refuses two ranks on "
                          "one device); the hand-over keeps the grouped form the RCCL run takes.  A rehearsal of the N > 1 control flow, not a measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last picture of the last timed step returned as DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB in all: a fixed, seeded sample of the larger arrays)")
     ap.add_argument("--dry-launch", action="store_true",
                     help="launcher check without a GPU: start the ranks (gloo), verify the world size, hand one dummy boundary picture round the ring")
     return ap.parse_args()
@@ -219,6 +222,63 @@ def cpu_baseline(wl, budget_s=25.0):
                       "stage seconds per picture: %s" % (what, sum(secs_tot.values()), {k: round(v / reps * scale, 4) for k, v in secs_tot.items()})}
 
 
+DUMP_BUDGET_BYTES = 60 * 10 ** 6          # sample bytes: with the .npy headers the files stay under 64 MB
+
+
+def dump_outputs(out, path):
+    """--dump-outputs: the arrays one picture of the timed path hands its caller (Workload.run_gpu's `out`), one DIR/<name>.npy each.  Record buffers
+    (SEARCH_BEST, FRAC_RESULT) are split into one array per field; the prediction is cut to the part the one-pass form keeps (`pred_valid`, as
+    tests/test_gpu_workload.py compares it).  Integers of at most 16 bits are stored as float32, wider ones as float64 (both exact).  An array over its
+    share of DUMP_BUDGET_BYTES is stored as a sample: a fixed set of flat indices drawn from a generator seeded by the array's name and size."""
+    import zlib
+    import numpy as np
+    from vvcsoftware_vtm_amd import ops
+    arrays = {}
+
+    def add(name, t):
+        if t is None:
+            return
+        if isinstance(t, (list, tuple)):
+            for i, x in enumerate(t):
+                add("%s_%d" % (name, i), x)
+            return
+        a = t.detach().cpu().numpy()
+        rec = ops.SEARCH_BEST if name.startswith("me_best_") else ops.FRAC_RESULT if name == "frac" else None
+        if rec is not None:
+            a = a.view(rec)
+            for f in rec.names:
+                arrays["%s_%s" % (name, f)] = a[f]
+            return
+        arrays[name] = a
+
+    for k in sorted(out):
+        if k in ("pred", "pred_valid"):
+            continue
+        add(k, out[k])
+    if out.get("pred_valid") is None:
+        add("pred", out["pred"])
+    else:
+        th, tw = out["pred_valid"]
+        add("pred_0", out["pred"][0][:th, :tw])
+    os.makedirs(path, exist_ok=True)
+    dts = {name: (np.float32 if a.dtype.itemsize <= 2 else np.float64) for name, a in arrays.items()}
+    total = 0
+    # smallest first: an array that fits its share is stored whole and leaves the rest of that share to the larger ones
+    order = sorted(arrays, key=lambda k: (arrays[k].size * np.dtype(dts[k]).itemsize, k))
+    for i, name in enumerate(order):
+        a, dt = arrays[name], dts[name]
+        a = np.ascontiguousarray(a).reshape(-1) if a.ndim else a.reshape(1)
+        n = (DUMP_BUDGET_BYTES - total) // (len(order) - i) // np.dtype(dt).itemsize
+        if a.size > n:
+            rng = np.random.default_rng(zlib.crc32(("%s:%d" % (name, a.size)).encode()))
+            a = a[np.sort(rng.choice(a.size, n, replace=False))]
+        v = a.astype(dt)
+        np.save(os.path.join(path, name + ".npy"), v)
+        total += v.nbytes
+    assert total <= DUMP_BUDGET_BYTES
+    return len(arrays), total
+
+
 def dry_launch(args):
     """Launcher check on CPU (gloo): every rank joins, the world size equals --gpus, one dummy boundary picture goes round the ring."""
     import torch
@@ -256,6 +316,8 @@ def dry_launch(args):
 
 def main():
     args = parse_args()
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args))                      # nothing GPU-related has been imported or called at this point
     if args.dry_launch:
@@ -422,6 +484,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     timed_groups = dict(timer.ev)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(out, args.dump_outputs)                 # what the last timed picture computed, before any later leg reuses its buffers
 
     # ---- the same K steps once more WITH the input stream (reported beside `value`, never as `value`: the contract's figure has the inputs resident)
     dt_up = None
