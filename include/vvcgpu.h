@@ -62,17 +62,18 @@ int vvcgpu_stream_sync(void* stream);
 /* Library-internal per-stream resources (work lists, packed search blocks, counters) are created on the first call that needs them and kept
  * for later calls on the same (device, stream).  A host that creates streams per thread / job calls vvcgpu_stream_release(stream) before it
  * destroys a stream: the call waits for the stream's queued work and frees what the library holds for it (any number of streams may come and
- * go; the stream's slot is found whichever device is current).  vvcgpu_shutdown() does the same for every stream of every device (e.g. before
- * unloading the library).  Both return VVCGPU_OK when there was nothing to free and VVCGPU_E_DEVICE when a device could not be reached (what
- * could not be freed is kept, not leaked).  The scratch of a stream grows geometrically; a buffer it has outgrown is freed as soon as the work
- * queued before the growth has completed.  One host thread drives a stream at a time (per-thread streams for concurrent callers). */
+ * go; the stream's slot is found whichever device is current).  vvcgpu_shutdown() does the same for every stream of every device and also
+ * releases the table images below (e.g. before unloading the library); whatever is needed afterwards is created again on demand.  Both return
+ * VVCGPU_OK when there was nothing to free and VVCGPU_E_DEVICE when a device could not be reached (what could not be freed is kept, not leaked).
+ * The scratch of a stream grows geometrically; a buffer it has outgrown is freed once the work queued up to the end of the call that outgrew it
+ * has completed.  One host thread drives a stream at a time (per-thread streams for concurrent callers). */
 int vvcgpu_stream_release(void* stream);
 int vvcgpu_shutdown(void);
 /* Per device (and bit depth) the library keeps a few constant table images in device memory: the transform matrices (TrQuant.cpp:72-84, Rom.cpp:245-299)
  * as int32 and as the f16 image of the matrix-core kernels, the Toeplitz tap tables of the matrix-core interpolation (InterpolationFilter.cpp:59-138).
  * They are built by the FIRST call that needs them -- on the NULL stream, with a device synchronisation, under a library mutex: that call must not run
  * inside a stream capture and briefly stalls other threads' streams.  vvcgpu_warmup(bit_depth) builds them all for the current device at a time the host
- * chooses (start-up), after which no entry point synchronises the device.  Optional; idempotent. */
+ * chooses (start-up), after which no entry point synchronises the device until vvcgpu_shutdown() has released them.  Optional; idempotent. */
 int vvcgpu_warmup(int bit_depth);
 
 /* ---- A1: ALF classification  (AdaptiveLoopFilter::deriveClassification, AdaptiveLoopFilter.cpp:274-463;

@@ -112,6 +112,99 @@ def test_many_short_lived_streams():
     assert np.array_equal(out.cpu().numpy(), want)
 
 
+def test_me_batch_scratch_grows_inside_the_chain():
+    """vvcgpu_me_batch claims the TZ search's and the refinement's workspace from ONE scratch scope.  On one fresh stream: a small call, then a large
+    one -- its first claims fit the stream's buffer, a later claim moves the stream to a larger buffer while the earlier claims stay in use (the
+    outgrown buffer is retired when the call ends) -- then a small one again.  Each equals the same call on a stream of its own."""
+    from vvcsoftware_vtm_amd import ops, capi
+    rng = np.random.default_rng(77)
+    W, H, M, bd, w, h = 512, 320, 160, 10, 16, 16
+    org, ref_ = cases.tz_planes(rng, W, H, M, bd, motion=(3, 2))
+    cfg = cases.tz_cfg(W, H, M, 9.5, search_range=32)
+    dorg, dref = dev(org), dev(ref_)
+    lists = [cases.tz_pus(rng, n, W, H, M, [(w, h)], flags_choices=(0, 1), spread=8) for n in (64, 6000, 100)]
+    torch.cuda.synchronize()
+
+    def run(pus, s):
+        with torch.cuda.stream(s):
+            best, frac = ops.me_batch(dorg, dref, ops.struct_to_device(pus), len(pus), w, h, cfg, bd, use_hadamard=True)
+            s.synchronize()
+            return best.cpu().numpy(), frac.cpu().numpy()
+
+    shared = torch.cuda.Stream()
+    got = [run(pus, shared) for pus in lists]
+    capi.call("vvcgpu_stream_release", C.c_void_p(shared.cuda_stream))
+    for pus, (gb, gf) in zip(lists, got):
+        own = torch.cuda.Stream()
+        wb, wf = run(pus, own)
+        capi.call("vvcgpu_stream_release", C.c_void_p(own.cuda_stream))
+        assert np.array_equal(gb, wb) and np.array_equal(gf, wf), len(pus)
+
+
+def test_table_images_come_back_after_shutdown():
+    """vvcgpu_shutdown releases the per-device table images as well; every user builds its image again on demand: the matrix-core motion
+    compensation, the fractional refinement, the forward transform of a long list (chain launch: f16 image + golden tables) and the residual chain
+    of shape runs give the same results as before the shutdown."""
+    from vvcsoftware_vtm_amd import ops, capi
+    rng = np.random.default_rng(11)
+    bd, mx, M = 10, 1023, 16
+    W, H = 256, 128
+    ref = cases.rand_plane(rng, H + 2 * M, W + 2 * M, bd, "smooth")
+    org = np.ascontiguousarray(np.clip(ref[M + 1:M + 1 + H, M + 2:M + 2 + W].astype(np.int32) + rng.integers(-6, 7, (H, W)), 0, mx).astype(np.int16))
+    dref, dorg = dev(ref), dev(org)
+    # motion compensation, 16x16 luma PUs (the matrix-core kernel's shape)
+    gx, gy = [a.reshape(-1) for a in np.meshgrid(np.arange(0, W, 16), np.arange(0, H, 16))]
+    mc = np.zeros(gx.size, ops.MC_DESC)
+    mc["ref0_off"] = mc["ref1_off"] = (gy + M) * (W + 2 * M) + gx + M
+    mc["dst_off"] = gy * W + gx
+    mc["ref0_stride"] = mc["ref1_stride"] = W + 2 * M
+    mc["dst_stride"], mc["w"], mc["h"], mc["is_luma"], mc["bi"] = W, 16, 16, 1, 1
+    mc["frac_x0"], mc["frac_y1"] = 4, 8
+    dmc = ops.struct_to_device(mc)
+    # fractional refinement, 16x16 blocks with the Hadamard cost
+    fb = np.zeros(gx.size, ops.FRAC_BLK)
+    mvx, mvy = rng.integers(-3, 4, gx.size), rng.integers(-3, 4, gx.size)
+    fb["org_x"], fb["org_y"], fb["ref_x"], fb["ref_y"], fb["mv_x"], fb["mv_y"] = gx, gy, M + gx + mvx, M + gy + mvy, mvx, mvy
+    dfb = ops.struct_to_device(fb)
+    mv = ops.MvCost(17.0, 3, -2, 0, 0)
+    # forward transform of 256 16x16 TUs, then 16384 4x4 TUs, over a 512 x 640 residual
+    resi = rng.integers(-300, 300, (640, 512)).astype(np.int16)
+    tr = [(y * 512 + x, 0, 512, 16, 16, 0, 0, 0, 0) for y in range(0, 128, 16) for x in range(0, 512, 16)]
+    tr += [(y * 512 + x, 0, 512, 4, 4, 1, 1, 0, 0) for y in range(128, 640, 4) for x in range(0, 512, 4)]
+    tr = np.array(tr, dtype=ops.TR_DESC)
+    tr["coeff_off"] = np.concatenate([[0], np.cumsum(tr["w"].astype(np.int64) * tr["h"])[:-1]])
+    dtr, dresi = ops.struct_to_device(tr), dev(resi)
+    assert len(tr) >= 16384
+    # residual chain of shape runs: 16x16 TUs, then 8x8 TUs
+    tus = [(x, y, 16) for y in range(0, H // 2, 16) for x in range(0, W, 16)] + [(x, y, 8) for y in range(H // 2, H, 8) for x in range(0, W, 8)]
+    rc = np.zeros(len(tus), ops.RC_DESC)
+    for i, (x, y, s) in enumerate(tus):
+        rc[i] = (y * W + x, y * W + x, y * W + x, 0, W, W, W, s, s, 0, 0, 0, 0, 32, (0, 0))
+    rc["level_off"] = np.concatenate([[0], np.cumsum(rc["w"].astype(np.int64) * rc["h"])[:-1]])
+    runs = [(16, 16, sum(t[2] == 16 for t in tus)), (8, 8, sum(t[2] == 8 for t in tus))]
+    drc = ops.struct_to_device(rc)
+    dpred = dev(np.ascontiguousarray(np.clip(org + rng.integers(-25, 26, org.shape), 0, mx).astype(np.int16)))
+
+    def run_all():
+        out = torch.zeros((H, W), dtype=torch.int16, device="cuda")
+        ops.mc_batch(dref, dref, out, dmc, len(mc), bd, (0, mx))
+        frac = ops.frac_refine(dorg, dref, dfb, len(fb), 16, 16, bd, mv, True, (0, mx))
+        coeff = torch.zeros(int(tr["coeff_off"][-1]) + 16, dtype=torch.int32, device="cuda")
+        ops.tr_fwd_batch(dresi, coeff, dtr, len(tr), bd)
+        rec = dpred.clone()
+        level = torch.zeros(int(rc["level_off"][-1]) + 64, dtype=torch.int32, device="cuda")
+        asum = ops.resi_chain_runs_batch(dorg, dpred, rec, level, drc, len(rc), runs, bd, (0, mx))
+        torch.cuda.synchronize()
+        return [t.cpu().numpy() for t in (out, frac, coeff, rec, level, asum)]
+
+    before = run_all()
+    assert capi.lib().vvcgpu_shutdown() == 0, capi.lib().vvcgpu_last_error()
+    after = run_all()
+    for name, a, b in zip(("mc", "frac", "tr_fwd", "rec", "level", "abs_sum"), before, after):
+        assert np.array_equal(a, b), name
+    assert np.any(before[0] != 0) and np.any(before[2] != 0) and np.any(before[4] != 0)
+
+
 def test_out_of_contract_descriptors_give_the_sentinel():
     """descriptors live in device memory, so the library cannot validate them on the host: the fused predict-and-distort kernels skip a descriptor whose
     shape does not fit their LDS tile and answer the documented sentinel ~0 (include/vvcgpu.h) instead of overrunning LDS; the valid neighbours of the

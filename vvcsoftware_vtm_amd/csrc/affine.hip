@@ -305,9 +305,6 @@ __global__ __launch_bounds__(256) void affine_iter_small_kernel(const Pel* __res
 
 }  // namespace
 
-extern "C" __attribute__((visibility("hidden"))) int vvcgpu_mc_batch_impl(const vvc_pel* ref0_base, const vvc_pel* ref1_base, vvc_pel* dst_base, const vvcgpu_mc_desc* descs, int n, int bit_depth,
-                                    int clp_min, int clp_max, void* stream, bool skip_fast, bool sub44);       // interp.hip (not part of the ABI)
-
 extern "C" {
 
 int vvcgpu_affine_sobel_batch(int vertical, const vvc_pel* pred_base, int32_t* deriv_base, const vvcgpu_afg_desc* descs, int n, void* stream)
@@ -359,7 +356,8 @@ int vvcgpu_affine_pred_batch(const vvc_pel* ref0_base, const vvc_pel* ref1_base,
                                               stream);
   if (rc != VVCGPU_OK) return rc;
   // luma: every descriptor is a 4x4 block -- no fast-kernel launch, the packed 4x4 variant of the generic kernel; chroma (2x2): the plain one, no fast-kernel launch either
-  return vvcgpu_mc_batch_impl(ref0_base, ref1_base ? ref1_base : ref0_base, dst_base, subblock_ws, n_subblocks, bit_depth, clp_min, clp_max, stream, true,
+  VvcScratch sc((hipStream_t)stream);
+  return vvcgpu_mc_batch_impl(ref0_base, ref1_base ? ref1_base : ref0_base, dst_base, subblock_ws, n_subblocks, bit_depth, clp_min, clp_max, stream, sc, true,
                               comp == 0);
 }
 
@@ -375,11 +373,12 @@ int vvcgpu_affine_me_iter_batch(const vvc_pel* org_base, const vvc_pel* ref_base
   VVC_CHECK_ARG(dist_kind == 0 || dist_kind == 1, "affine_me_iter_batch: dist_kind %d (0 SAD, 1 Hadamard)", dist_kind);
   VVC_CHECK_ARG(pic_w > 0 && pic_h > 0 && max_cu_w > 0 && max_cu_h > 0 && ref_stride > 0, "affine_me_iter_batch: geometry");
   hipStream_t st = (hipStream_t)stream;
+  VvcScratch sc(st);
   // sub-block vectors -> sub-block prediction (the entry points a caller would chain itself) -> everything that reads the prediction, fused
   hipLaunchKernelGGL(affine_subblock_descs_kernel, dim3(n), dim3(256), 0, st, reinterpret_cast<const vvcgpu_affine_pu*>(items), (int)sizeof(vvcgpu_affine_iter),
                      n, 0, pic_w, pic_h, max_cu_w, max_cu_h, ref_origin_x, ref_origin_y, ref_stride, ref_stride, subblock_ws);
   VVC_LAUNCH_CHECK();
-  const int rc = vvcgpu_mc_batch_impl(ref_base, ref_base, pred_base, subblock_ws, n_subblocks, bit_depth, clp_min, clp_max, stream, true, true);   // 4x4 luma only
+  const int rc = vvcgpu_mc_batch_impl(ref_base, ref_base, pred_base, subblock_ws, n_subblocks, bit_depth, clp_min, clp_max, stream, sc, true, true);   // 4x4 luma only
   if (rc != VVCGPU_OK) return rc;
   // every PU is served by exactly one of the two: by size, which only the device knows
   hipLaunchKernelGGL(affine_iter_small_kernel, dim3(cdiv(n, 4)), dim3(256), 0, st, org_base, pred_base, items, n, dist_kind,

@@ -5,21 +5,36 @@
 #include <stdio.h>
 #include <string.h>
 #include <stdlib.h>
+#include <vector>
 #include "vvcgpu.h"
 
 typedef int16_t Pel;
 typedef int32_t TCoeff;
 
 void vvcgpu_set_error(const char* fmt, ...);
-// Library-internal device scratch, cached per (device, stream): work on one stream is ordered, so the buffer of the previous
-// call on that stream is free again when the next call's kernels start.  Grow-only; returns nullptr (error text set) on failure.
-// ONE call of an entry point may take each REGION once: an entry point that sizes its own workspace uses VVC_SCRATCH_ENTRY (vvcgpu_scratch), a
-// launch helper that other entry points call with their workspace still live (vvcgpu_frac_refine_launch under vvcgpu_me_batch,
-// vvcgpu_mc_batch_impl under the affine entry points) uses VVC_SCRATCH_HELPER -- two requests for the same region on one call path alias.
-enum { VVC_SCRATCH_ENTRY = 0, VVC_SCRATCH_HELPER = 1, VVC_SCRATCH_IOTA = 2, VVC_SCRATCH_REGIONS = 3 };
+// The device workspace of ONE call of an entry point, opened at its top (lib.hip): take<T>(count) returns `count` T, aligned to `align` bytes, that no
+// other claim of the scope overlaps (nullptr, error text set, on failure).  Helpers claim from their caller's scope.  The memory is the stream's cached
+// buffer: work on one stream is ordered, so the previous call's claims are free again when this call's kernels start.
+class VvcScratch
+{
+public:
+  explicit VvcScratch(hipStream_t stream) : stream_(stream) {}
+  ~VvcScratch();                                                              // retires the buffers this call outgrew (lib.hip)
+  VvcScratch(const VvcScratch&) = delete; VvcScratch& operator=(const VvcScratch&) = delete;
+  template <class T> T* take(size_t count, size_t align = 64) { return static_cast<T*>(take_bytes(count * sizeof(T), align)); }
+private:
+  void* take_bytes(size_t bytes, size_t align);
+  hipStream_t stream_;
+  int device_ = -1;                                                           // looked up by the first claim
+  size_t used_ = 0;                                                           // end of the last claim in the stream's buffer
+  std::vector<void*> outgrown_;
+};
 int* vvcgpu_iota(hipStream_t stream, int n);                                 // device array 0, 1, .. of at least n ints, persistent per stream (lib.hip)
-void* vvcgpu_scratch(hipStream_t stream, size_t bytes);                      // region VVC_SCRATCH_ENTRY
-void* vvcgpu_scratch_region(hipStream_t stream, int region, size_t bytes);
+// Per-device constant images (lib.hip): image `key` of the current device, built by its first user -- build(dst, arg) into `bytes` of new device memory
+// (bytes 0: none, a symbol upload) on the null stream, then a device synchronisation -- and released by vvcgpu_shutdown.  Returns VVCGPU_OK (*image: the
+// memory, if image is not null) or an error code with the text set.
+enum { VVC_IMAGE_TR_TABLES, VVC_IMAGE_TR_F16, VVC_IMAGE_MC, VVC_IMAGE_FRAC = VVC_IMAGE_MC + 3, VVC_IMAGE_KEYS = VVC_IMAGE_FRAC + 3 };   // MC, FRAC: + bit depth - 8
+int vvcgpu_device_image(int key, size_t bytes, int (*build)(void* dst, const void* arg), const void* arg, void** image);
 // The ONE behaviour switch of the library (read per call): VVCGPU_NO_MFMA=1 keeps the interpolation filters, the Hadamard refinement and the
 // transforms off the matrix cores (the vector-pipe bodies that otherwise serve flagged PUs / TUs take everything) -- tests/test_gpu_no_mfma.py runs the
 // parity cases of those bodies under it.  Every other environment variable the library reads is a measurement aid (VVCGPU_*_DIAG: cycle stamps to
@@ -36,6 +51,11 @@ void vvcgpu_counters_failed(hipStream_t stream);       // a launch that took a c
 int vvcgpu_frac_refine_launch(const vvc_pel* org, int org_stride, const vvc_pel* ref, int ref_stride, const vvcgpu_frac_blk* blocks, int nblocks,
                               int w, int h, int bit_depth, int clp_min, int clp_max, int use_hadamard, const vvcgpu_mvcost* mvcost_host,
                               const int* preds, vvcgpu_frac_result* results, void* stream);
+// the motion compensation behind vvcgpu_mc_batch / vvcgpu_mc_picture_batch and the affine entry points (interp.hip); it claims its work list from
+// the caller's scope.  skip_fast: the caller knows that no descriptor is one of the fast kernel's shapes (affine sub-blocks): its launch is left out
+// -- 65 k workgroups that only look at their descriptors and leave cost 80 us for the 518 k sub-blocks of a 4K picture
+int vvcgpu_mc_batch_impl(const vvc_pel* ref0_base, const vvc_pel* ref1_base, vvc_pel* dst_base, const vvcgpu_mc_desc* descs, int n, int bit_depth,
+                         int clp_min, int clp_max, void* stream, VvcScratch& sc, bool skip_fast, bool sub44, bool serve_in_kernel = false);
 
 // Raster stage of whole-PU TZ searches as its own launch (tzsearch.hip -> dist.hip): one record per PU, written on the device.  An active
 // PU's raster is the nx x ny grid of step 5 whose position (0, 0) is the motion vector (x0, y0); blocks[] holds the block's origin in the

@@ -1521,7 +1521,8 @@ int vvcgpu_dist_batch(int kind, const vvc_pel* org_base, const vvc_pel* cur_base
   VVC_CHECK_ARG(org_base && cur_base && descs && out, "dist_batch: null pointer");
   if (bit_depth > 10) { vvcgpu_set_error("dist_batch: bit depth %d > 10 is outside the precondition", bit_depth); return VVCGPU_E_UNSUPPORTED; }
   hipStream_t st = (hipStream_t)stream;
-  int* heavyList = static_cast<int*>(vvcgpu_scratch(st, sizeof(int) * (size_t)n));
+  VvcScratch sc(st);
+  int* heavyList = sc.take<int>(n);
   if (!heavyList) return VVCGPU_E_DEVICE;
   int cur = 0;
   int* counters = vvcgpu_counters(st, &cur);                                  // zeroed counter for this call; the kernel clears the other set
@@ -1551,6 +1552,7 @@ int vvcgpu_sad_search(const vvc_pel* org, int org_stride, const vvc_pel* ref, in
   VVC_CHECK_ARG(nx > 0 && ny > 0 && sx > 0 && sy > 0, "sad_search: bad position grid");
   VVC_CHECK_ARG((best == nullptr) == (mvcost_host == nullptr), "sad_search: best and mvcost must be given together");
   hipStream_t st0 = (hipStream_t)stream;
+  VvcScratch sc(st0);
   if (sx == 1 && sy == 1 && nx == 9 && ny == 9 && sub_shift == 1 && (w & 15) == 0 && (h & 15) == 0 && w <= 64 && h <= 64 &&
       (ref_stride & 3) == 0 && (!best || (mvcost_host->lambda >= 0.0 && mvcost_host->lambda < 1.0e9)))
   {
@@ -1622,7 +1624,7 @@ int vvcgpu_sad_search(const vvc_pel* org, int org_stride, const vvc_pel* ref, in
       const int threads = 64 * units;                                     // one wave per unit (<= 16: rps <= 24, nbg <= 8)
       const int total = ngroups * nstrips;
       const size_t packedDw = (size_t)nblocks * 2 * hsR * 8;
-      unsigned* packed = static_cast<unsigned*>(vvcgpu_scratch(st0, packedDw * sizeof(unsigned)));
+      unsigned* packed = sc.take<unsigned>(packedDw);
       if (!packed) return VVCGPU_E_DEVICE;
       hipLaunchKernelGGL(r5c_pack_org_kernel, dim3((unsigned)(((size_t)nblocks * hsR * (w >> 4) + 255) / 256)), dim3(256), 0, st0, org, org_stride, blocks, nblocks,
                          w, hsR, sub_shift, packed, gq ? 1 : 0, reinterpret_cast<unsigned long long*>(best));
@@ -1699,7 +1701,7 @@ int vvcgpu_sad_search(const vvc_pel* org, int org_stride, const vvc_pel* ref, in
         const int threadsQ = itemsQ * splitQ * 64;
         const int totalQ = nblocks * nstripsQ;
         const size_t packedDwQ = (size_t)nblocks * 2 * hsR * (w >> 1);
-        unsigned* packedQ = static_cast<unsigned*>(vvcgpu_scratch(st0, packedDwQ * sizeof(unsigned)));
+        unsigned* packedQ = sc.take<unsigned>(packedDwQ);
         if (!packedQ) return VVCGPU_E_DEVICE;
         hipLaunchKernelGGL(r5c_pack_org_kernel, dim3((unsigned)(((size_t)nblocks * hsR * (w >> 4) + 255) / 256)), dim3(256), 0, st0, org, org_stride, blocks, nblocks,
                            w, hsR, sub_shift, packedQ, 1, reinterpret_cast<unsigned long long*>(best));
@@ -1730,7 +1732,7 @@ int vvcgpu_sad_search(const vvc_pel* org, int org_stride, const vvc_pel* ref, in
       const int threads = split == 2 ? items * 2 * 64 : (items >= 8 ? 512 : items * 64);
       const int total = nblocks * nstrips;
       const size_t packedDw = (size_t)nblocks * 2 * hsR * (w >> 1);
-      unsigned* packed = static_cast<unsigned*>(vvcgpu_scratch(st0, packedDw * sizeof(unsigned)));
+      unsigned* packed = sc.take<unsigned>(packedDw);
       if (!packed) return VVCGPU_E_DEVICE;
       hipLaunchKernelGGL(r5c_pack_org_kernel, dim3((unsigned)(((size_t)nblocks * hsR * (w >> 4) + 255) / 256)), dim3(256), 0, st0, org, org_stride, blocks, nblocks,
                          w, hsR, sub_shift, packed, 0, reinterpret_cast<unsigned long long*>(best));

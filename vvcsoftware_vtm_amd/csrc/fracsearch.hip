@@ -12,7 +12,6 @@
 // (tile row per lane, vertical butterflies with wave shuffles).  Nothing but the 32-byte result leaves the CU.
 #include "common.h"
 #include "mfma_tr.h"
-#include <mutex>
 
 namespace {
 
@@ -1076,26 +1075,17 @@ __global__ __launch_bounds__(64 * WV, WV == 16 ? 1 : WPS) void frac16m_kernel(co
 }
 
 // TA / TB images per device and bit depth, built on first use
+int fm_build(void* dst, const void* bd)
+{
+  const int b = *static_cast<const int*>(bd);
+  hipLaunchKernelGGL(fm_build_tables_kernel, dim3(cdiv(FM_TAB_HALVES, 256)), dim3(256), 0, (hipStream_t)0, static_cast<_Float16*>(dst), 6 + (14 - b > 2 ? 14 - b : 2));
+  VVC_LAUNCH_CHECK();
+  return VVCGPU_OK;
+}
 const _Float16* fm_image(int bd)
 {
-  static std::mutex mtx;
-  static _Float16* images[64][3] = { { nullptr } };
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) { vvcgpu_set_error("frac image: device index"); return nullptr; }
-  std::lock_guard<std::mutex> lock(mtx);
-  _Float16*& slot = images[dev][bd - 8];
-  if (!slot)
-  {
-    void* p = nullptr;
-    hipError_t e = hipMalloc(&p, FM_TAB_HALVES * sizeof(_Float16));
-    if (e != hipSuccess) { (void)hipGetLastError(); vvcgpu_set_error("frac image: hipMalloc failed: %s", hipGetErrorString(e)); return nullptr; }
-    hipLaunchKernelGGL(fm_build_tables_kernel, dim3(cdiv(FM_TAB_HALVES, 256)), dim3(256), 0, (hipStream_t)0, static_cast<_Float16*>(p), 6 + (14 - bd > 2 ? 14 - bd : 2));
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipDeviceSynchronize();         // other streams may use the image right after this call returns
-    if (e != hipSuccess) { (void)hipFree(p); vvcgpu_set_error("building the fractional-search table image failed: %s", hipGetErrorString(e)); return nullptr; }
-    slot = static_cast<_Float16*>(p);
-  }
-  return slot;
+  void* p = nullptr;
+  return vvcgpu_device_image(VVC_IMAGE_FRAC + bd - 8, FM_TAB_HALVES * sizeof(_Float16), fm_build, &bd, &p) == VVCGPU_OK ? static_cast<const _Float16*>(p) : nullptr;
 }
 }  // namespace
 

@@ -15,7 +15,6 @@
 #include "common.h"
 #include "dist_dev.h"
 #include "mfma_tr.h"
-#include <mutex>
 
 // the generic MC scan loads bytes 32..47 of a descriptor as ONE uint4 (dst_stride | w, h | the four phases | is_luma, bi, reserved): the layout is part of
 // the ABI, and the descriptor array must be 16-byte aligned (include/vvcgpu.h)
@@ -996,26 +995,16 @@ __global__ __launch_bounds__(256, 4) void mc_mfma_kernel(const Pel* __restrict__
 }
 
 // the table image of mc_mfma_kernel per device and bit depth
+static int mm_build(void* dst, const void* bd)
+{
+  hipLaunchKernelGGL(mm_build_tables_kernel, dim3(cdiv(MM_ENTRIES * 8, 256)), dim3(256), 0, (hipStream_t)0, static_cast<_Float16*>(dst), *static_cast<const int*>(bd));
+  VVC_LAUNCH_CHECK();
+  return VVCGPU_OK;
+}
 static const _Float16* mm_image(int bd)
 {
-  static std::mutex mtx;
-  static _Float16* images[64][3] = { { nullptr } };
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) { vvcgpu_set_error("mc image: device index"); return nullptr; }
-  std::lock_guard<std::mutex> lock(mtx);
-  _Float16*& slot = images[dev][bd - 8];
-  if (!slot)
-  {
-    void* p = nullptr;
-    hipError_t e = hipMalloc(&p, MM_ENTRIES * 16);
-    if (e != hipSuccess) { (void)hipGetLastError(); vvcgpu_set_error("mc image: hipMalloc failed: %s", hipGetErrorString(e)); return nullptr; }
-    hipLaunchKernelGGL(mm_build_tables_kernel, dim3(cdiv(MM_ENTRIES * 8, 256)), dim3(256), 0, (hipStream_t)0, static_cast<_Float16*>(p), bd);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) { (void)hipFree(p); vvcgpu_set_error("building the motion-compensation table image failed: %s", hipGetErrorString(e)); return nullptr; }
-    slot = static_cast<_Float16*>(p);
-  }
-  return slot;
+  void* p = nullptr;
+  return vvcgpu_device_image(VVC_IMAGE_MC + bd - 8, MM_ENTRIES * 16, mm_build, &bd, &p) == VVCGPU_OK ? static_cast<const _Float16*>(p) : nullptr;
 }
 
 // four 4x4 luma PUs side by side, sixteen lanes each, through the packed code of the fast kernel (N = 8 taps, tile 4, 16 lanes: 11 window rows of
@@ -1495,7 +1484,8 @@ int vvcgpu_if_batch(const vvc_pel* src_base, vvc_pel* dst_base, const vvcgpu_if_
   VVC_CHECK_ARG(src_base && dst_base && descs, "if_batch: null pointer");
   if (bit_depth > 10 || bit_depth < 8) { vvcgpu_set_error("if_batch: bit depth %d outside 8..10", bit_depth); return VVCGPU_E_UNSUPPORTED; }
   hipStream_t st = (hipStream_t)stream;
-  int* heavyList = static_cast<int*>(vvcgpu_scratch(st, sizeof(int) * (size_t)n));
+  VvcScratch sc(st);
+  int* heavyList = sc.take<int>(n);
   if (!heavyList) return VVCGPU_E_DEVICE;
   int cur = 0;
   int* counters = vvcgpu_counters(st, &cur);
@@ -1514,26 +1504,25 @@ int vvcgpu_if_batch(const vvc_pel* src_base, vvc_pel* dst_base, const vvcgpu_if_
   return VVCGPU_OK;
 }
 
-// skip_fast: the caller knows that no descriptor is one of the fast kernel's shapes (affine sub-blocks): its launch is left out -- 65 k workgroups
-// that only look at their descriptors and leave cost 80 us for the 518 k sub-blocks of a 4K picture
-__attribute__((visibility("hidden"))) int vvcgpu_mc_batch_impl(const vvc_pel* ref0_base, const vvc_pel* ref1_base, vvc_pel* dst_base,
-                         const vvcgpu_mc_desc* descs, int n, int bit_depth, int clp_min, int clp_max, void* stream, bool skip_fast, bool sub44, bool serve_in_kernel = false);
-
 int vvcgpu_mc_batch(const vvc_pel* ref0_base, const vvc_pel* ref1_base, vvc_pel* dst_base,
                     const vvcgpu_mc_desc* descs, int n, int bit_depth, int clp_min, int clp_max, void* stream)
 {
-  return vvcgpu_mc_batch_impl(ref0_base, ref1_base, dst_base, descs, n, bit_depth, clp_min, clp_max, stream, false, false);
+  VvcScratch sc((hipStream_t)stream);
+  return vvcgpu_mc_batch_impl(ref0_base, ref1_base, dst_base, descs, n, bit_depth, clp_min, clp_max, stream, sc, false, false);
 }
 // a picture's PU list as an encoder builds it for the common partition (16x16 luma / 8x8 chroma PUs): ONE launch -- what the matrix-core kernel cannot
 // take (other shapes, phases, strides, samples outside the bit depth) is served by the wave that found it behind its walk, through the generic body
 int vvcgpu_mc_picture_batch(const vvc_pel* ref0_base, const vvc_pel* ref1_base, vvc_pel* dst_base,
                             const vvcgpu_mc_desc* descs, int n, int bit_depth, int clp_min, int clp_max, void* stream)
 {
-  return vvcgpu_mc_batch_impl(ref0_base, ref1_base, dst_base, descs, n, bit_depth, clp_min, clp_max, stream, false, false, true);
+  VvcScratch sc((hipStream_t)stream);
+  return vvcgpu_mc_batch_impl(ref0_base, ref1_base, dst_base, descs, n, bit_depth, clp_min, clp_max, stream, sc, false, false, true);
 }
 
-int vvcgpu_mc_batch_impl(const vvc_pel* ref0_base, const vvc_pel* ref1_base, vvc_pel* dst_base,
-                         const vvcgpu_mc_desc* descs, int n, int bit_depth, int clp_min, int clp_max, void* stream, bool skip_fast, bool sub44, bool serve_in_kernel)
+}  // extern "C"
+
+int vvcgpu_mc_batch_impl(const vvc_pel* ref0_base, const vvc_pel* ref1_base, vvc_pel* dst_base, const vvcgpu_mc_desc* descs, int n, int bit_depth,
+                         int clp_min, int clp_max, void* stream, VvcScratch& sc, bool skip_fast, bool sub44, bool serve_in_kernel)
 {
   VVC_CHECK_ARG(n >= 0, "mc_batch: n %d", n);
   if (n == 0) return VVCGPU_OK;
@@ -1548,7 +1537,7 @@ int vvcgpu_mc_batch_impl(const vvc_pel* ref0_base, const vvc_pel* ref1_base, vvc
   {
     const _Float16* image = mm_image(bit_depth);
     if (!image) return VVCGPU_E_DEVICE;
-    int* fl = static_cast<int*>(vvcgpu_scratch_region(st, VVC_SCRATCH_HELPER, (size_t)n * sizeof(int)));
+    int* fl = sc.take<int>(n);
     if (!fl) return VVCGPU_E_DEVICE;
     const int wgL = cdiv(n, 4) < 256 * 4 ? cdiv(n, 4) : 256 * 4;   // persistent: four workgroups per CU
     unsigned long long* diag = nullptr;
@@ -1592,6 +1581,8 @@ int vvcgpu_mc_batch_impl(const vvc_pel* ref0_base, const vvc_pel* ref1_base, vvc
   return VVCGPU_OK;
 }
 
+extern "C" {
+
 int vvcgpu_mc_dist_batch(int kind, const vvc_pel* ref0_base, const vvc_pel* ref1_base, const vvc_pel* org_base, const vvcgpu_mc_desc* descs, int n,
                          int bit_depth, int clp_min, int clp_max, uint64_t* out, void* stream)
 {
@@ -1617,10 +1608,11 @@ int vvcgpu_pelop_batch(int op, const vvc_pel* src0_base, const vvc_pel* src1_bas
   int perWg = n < 8192 ? 1 : 64;                          // long lists: up to 64 descriptors per workgroup, fewer when that would leave compute units without one
   while (perWg > 16 && cdiv(n, perWg) < 4096) perWg >>= 1;
   hipStream_t st = (hipStream_t)stream;
+  VvcScratch sc(st);
   int* heavyList = nullptr; int* counters = nullptr; int cur = 0;
   if (perWg > 1)                                          // long lists: heavy blocks go to a list and a second launch
   {
-    heavyList = static_cast<int*>(vvcgpu_scratch(st, sizeof(int) * (size_t)n));
+    heavyList = sc.take<int>(n);
     if (!heavyList) return VVCGPU_E_DEVICE;
     counters = vvcgpu_counters(st, &cur);
     if (!counters) return VVCGPU_E_DEVICE;

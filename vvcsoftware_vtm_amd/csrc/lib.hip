@@ -16,23 +16,20 @@ void vvcgpu_set_error(const char* fmt, ...)
   va_end(ap);
 }
 
-// ---- per-(device, stream) resources: scratch buffer + two persistent zeroed counter sets.  One table behind one mutex; slots are created on
-// first use, released by vvcgpu_stream_release (a host that makes streams per job calls it before destroying the stream) or all at once by
-// vvcgpu_shutdown.  A buffer that has been outgrown is NOT freed on the spot -- work queued on the stream may still read it, and hipFree is a
-// device-wide synchronisation -- but parked in the slot's retired list and freed with the slot.  Capacity grows geometrically (at least doubling),
-// so a stream whose batches grow slowly re-allocates O(log n) times and the parked buffers sum to less than the live one: a slot never holds more
-// than about four times its largest request.  No entry point synchronises the device or another thread's stream while it holds the table's mutex.
-// (A stream is driven by one host thread at a time: per-thread streams, include/vvcgpu.h.)
-#include <vector>
+// ---- per-(device, stream) resources: scratch buffer (VvcScratch), identity array (vvcgpu_iota), two persistent zeroed counter sets.  One table behind
+// one mutex; slots are created on first use, released by vvcgpu_stream_release (before the host destroys the stream) or all at once by vvcgpu_shutdown.
+// An outgrown buffer is NOT freed on the spot -- queued work may still read it, and hipFree synchronises the device -- but parked behind an event, freed
+// once that has completed (at a later growth) or with the slot.  Capacity at least doubles, so the parked buffers sum to less than the live one.  No
+// entry point allocates, or synchronises anything, while it holds the mutex.  (One host thread drives a stream at a time: include/vvcgpu.h.)
 namespace {
+struct Retired { void* ptr; hipEvent_t done; };
 struct StreamSlot
 {
   int device; hipStream_t stream;
-  void* ptr[VVC_SCRATCH_REGIONS]; size_t cap[VVC_SCRATCH_REGIONS];   // scratch, one buffer per region (common.h)
-  struct Retired { void* ptr; hipEvent_t done; };
-  std::vector<Retired> retired;           // outgrown scratch buffers: freed with the slot
-  int* counters; int cur; bool dirty;     // int[2][16]; dirty: a launch that owned a set failed -- both sets are cleared before the next use
-  void* iotaPtr; int iotaN;               // the identity array of vvcgpu_iota: valid entries [0, iotaN) of the buffer at iotaPtr (region VVC_SCRATCH_IOTA)
+  void* scratch = nullptr; size_t scratchCap = 0;
+  int* iota = nullptr; int iotaN = 0;                       // the identity array 0 .. iotaN - 1
+  std::vector<Retired> retired;                             // outgrown buffers
+  int* counters = nullptr; int cur = 0; bool dirty = false; // int[2][VVC_CTR_INTS]; dirty: a launch that owned a set failed -- both are cleared before the next use
 };
 std::vector<StreamSlot> g_slots;
 std::mutex g_slotMutex;
@@ -42,66 +39,82 @@ StreamSlot* find_slot(int dev, hipStream_t stream, bool create)
   for (auto& s : g_slots)
     if (s.device == dev && s.stream == stream) return &s;
   if (!create) return nullptr;
-  g_slots.push_back(StreamSlot{ dev, stream, {}, {}, {}, nullptr, 0, false, nullptr, 0 });
+  g_slots.push_back(StreamSlot{ dev, stream });
   return &g_slots.back();
 }
 void free_slot(StreamSlot& s)             // the slot is out of the table (or the caller holds the mutex at shutdown), its device is current, its stream is idle
 {
-  for (int r = 0; r < VVC_SCRATCH_REGIONS; r++) if (s.ptr[r]) (void)hipFree(s.ptr[r]);
+  if (s.scratch) (void)hipFree(s.scratch);
+  if (s.iota) (void)hipFree(s.iota);
   for (auto& q : s.retired) { (void)hipFree(q.ptr); if (q.done) (void)hipEventDestroy(q.done); }
   s.retired.clear();
   if (s.counters) (void)hipFree(s.counters);
 }
+
+// a buffer of at least `bytes` that replaces one of `have` bytes: whole MiB, at least doubling -- the request alone when the doubled size does not fit
+void* grow_alloc(size_t bytes, size_t have, size_t* cap, const char* who)
+{
+  const size_t need = (bytes + (1u << 20) - 1) & ~(size_t)((1u << 20) - 1);
+  for (size_t c : { std::max(need, 2 * have), need })
+  {
+    void* p = nullptr;
+    if (hipMalloc(&p, c) == hipSuccess) { *cap = c; return p; }
+    (void)hipGetLastError();                                                // a failed attempt must not surface at the caller's next launch check
+  }
+  vvcgpu_set_error("%s: hipMalloc(%zu) failed", who, need);
+  return nullptr;
 }
 
-void* vvcgpu_scratch(hipStream_t stream, size_t bytes) { return vvcgpu_scratch_region(stream, VVC_SCRATCH_ENTRY, bytes); }
-
-void* vvcgpu_scratch_region(hipStream_t stream, int region, size_t bytes)
+// parks an outgrown buffer of the stream behind an event recorded after the work queued so far; parked buffers whose event has completed are freed
+// here (growth is rare), outside the lock
+void retire(int dev, hipStream_t stream, void* p)
 {
-  if (region < 0 || region >= VVC_SCRATCH_REGIONS) { vvcgpu_set_error("scratch: region %d", region); return nullptr; }
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) { vvcgpu_set_error("hipGetDevice failed"); return nullptr; }
-  {
-    std::lock_guard<std::mutex> lock(g_slotMutex);
-    StreamSlot* slot = find_slot(dev, stream, true);
-    if (slot->cap[region] >= bytes) return slot->ptr[region];               // the hot path: no allocation, no event, no free
-  }
-  // Growth (O(log n) times per stream): allocate OUTSIDE the lock -- hipMalloc / hipFree may synchronise the device, and no other thread's entry
-  // point should wait for that behind the table's mutex.  (A stream is driven by one host thread at a time, so the slot's region does not change
-  // under us; the slot is looked up again because the table may have been re-allocated.)
-  size_t have = 0;
-  { std::lock_guard<std::mutex> lock(g_slotMutex); have = find_slot(dev, stream, true)->cap[region]; }
-  size_t cap = (bytes + (1u << 20) - 1) & ~(size_t)((1u << 20) - 1);
-  if (cap < 2 * have) cap = 2 * have;                                       // geometric growth
-  void* p = nullptr;
-  if (hipMalloc(&p, cap) != hipSuccess)
-  {
-    (void)hipGetLastError();                                                // the failed attempt must not surface at the caller's next launch check
-    cap = (bytes + (1u << 20) - 1) & ~(size_t)((1u << 20) - 1);             // the doubled size did not fit: the request itself
-    if (hipMalloc(&p, cap) != hipSuccess) { (void)hipGetLastError(); vvcgpu_set_error("scratch: hipMalloc(%zu) failed", cap); return nullptr; }
-  }
-  // The outgrown buffer: queued work on the stream may still read it, so it is parked with an event recorded behind that work; parked buffers
-  // whose event has completed are freed HERE, on the (rare) growth path and outside the lock, the rest with the slot (vvcgpu_stream_release /
-  // vvcgpu_shutdown).  Capacities at least double, so the parked buffers of a slot sum to less than its current capacity.
   hipEvent_t ev = nullptr;
   if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess || hipEventRecord(ev, stream) != hipSuccess)
   { (void)hipGetLastError(); if (ev) (void)hipEventDestroy(ev); ev = nullptr; }   // no event: the buffer stays parked until the slot goes
-  std::vector<StreamSlot::Retired> done;
+  std::vector<Retired> done;
   {
     std::lock_guard<std::mutex> lock(g_slotMutex);
     StreamSlot* slot = find_slot(dev, stream, true);
-    for (size_t i = 0; i < slot->retired.size();)
-    {
-      if (slot->retired[i].done && hipEventQuery(slot->retired[i].done) == hipSuccess) { done.push_back(slot->retired[i]); slot->retired.erase(slot->retired.begin() + (ptrdiff_t)i); }
-      else i++;
-    }
+    auto& r = slot->retired;
+    const auto finished = std::partition(r.begin(), r.end(), [](const Retired& q) { return !q.done || hipEventQuery(q.done) != hipSuccess; });
+    done.assign(finished, r.end()); r.erase(finished, r.end());
     (void)hipGetLastError();                                                // hipErrorNotReady of a query is not an error of the caller
-    if (slot->ptr[region]) slot->retired.push_back(StreamSlot::Retired{ slot->ptr[region], ev });
-    else if (ev) { (void)hipEventDestroy(ev); }
-    slot->ptr[region] = p; slot->cap[region] = cap;
+    slot->retired.push_back(Retired{ p, ev });
   }
   for (auto& q : done) { (void)hipFree(q.ptr); (void)hipEventDestroy(q.done); }
-  return p;
+}
+}
+
+// A claim that does not fit moves the stream to a new buffer that holds the whole scope so far (the next call of the same shape fits); the claims
+// already made stay where they are, and the outgrown buffer is retired when the scope closes, behind every launch of the call.
+void* VvcScratch::take_bytes(size_t bytes, size_t align)
+{
+  if (device_ < 0 && hipGetDevice(&device_) != hipSuccess) { device_ = -1; vvcgpu_set_error("hipGetDevice failed"); return nullptr; }
+  const size_t at = (used_ + align - 1) & ~(align - 1), end = at + (bytes ? bytes : 1);
+  size_t have = 0;
+  {
+    std::lock_guard<std::mutex> lock(g_slotMutex);
+    StreamSlot* slot = find_slot(device_, stream_, true);
+    if (slot->scratchCap >= end) { used_ = end; return static_cast<char*>(slot->scratch) + at; }   // the hot path: no allocation, no event, no free
+    have = slot->scratchCap;
+  }
+  size_t cap = 0;
+  void* p = grow_alloc(end, have, &cap, "scratch");
+  if (!p) return nullptr;
+  void* old = nullptr;
+  {
+    std::lock_guard<std::mutex> lock(g_slotMutex);                         // looked up again: the table may have been re-allocated
+    StreamSlot* slot = find_slot(device_, stream_, true);
+    old = slot->scratch; slot->scratch = p; slot->scratchCap = cap;
+  }
+  if (old) outgrown_.push_back(old);
+  used_ = end;
+  return static_cast<char*>(p) + at;
+}
+VvcScratch::~VvcScratch()
+{
+  for (void* p : outgrown_) retire(device_, stream_, p);
 }
 
 // identity array 0, 1, 2, ... of at least n ints, persistent per (device, stream): written by a launch on that stream when it is first needed or has to
@@ -109,24 +122,58 @@ void* vvcgpu_scratch_region(hipStream_t stream, int region, size_t bytes)
 namespace { __global__ void iota_kernel(int* p, int first, int n) { const int i = first + blockIdx.x * 256 + threadIdx.x; if (i < n) p[i] = i; } }
 int* vvcgpu_iota(hipStream_t stream, int n)
 {
-  int* p = static_cast<int*>(vvcgpu_scratch_region(stream, VVC_SCRATCH_IOTA, (size_t)(n > 0 ? n : 1) * sizeof(int)));
-  if (!p) return nullptr;
-  int dev = 0, first = 0, cap = 0;
+  int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess) { vvcgpu_set_error("hipGetDevice failed"); return nullptr; }
+  int* old = nullptr; int have = 0;
   {
     std::lock_guard<std::mutex> lock(g_slotMutex);
     StreamSlot* slot = find_slot(dev, stream, true);
-    if (slot->iotaPtr != p) { slot->iotaPtr = p; slot->iotaN = 0; }
-    first = slot->iotaN;
-    cap = (int)std::min<size_t>(slot->cap[VVC_SCRATCH_IOTA] / sizeof(int), (size_t)0x7FFFFFFF);
-    if (first < n) slot->iotaN = cap;                                     // the whole buffer is filled below
+    if (slot->iotaN >= n) return slot->iota;                                // the hot path
+    old = slot->iota; have = slot->iotaN;
   }
-  if (first < n)
+  size_t cap = 0;
+  int* p = static_cast<int*>(grow_alloc((size_t)n * sizeof(int), (size_t)have * sizeof(int), &cap, "iota"));
+  if (!p) return nullptr;
+  const int valid = (int)std::min<size_t>(cap / sizeof(int), (size_t)0x7FFFFFFF);   // the whole buffer is filled
+  hipLaunchKernelGGL(iota_kernel, dim3((unsigned)((valid + 255) / 256)), dim3(256), 0, stream, p, 0, valid);
+  if (hipGetLastError() != hipSuccess) { (void)hipFree(p); vvcgpu_set_error("iota: kernel launch failed"); return nullptr; }
   {
-    hipLaunchKernelGGL(iota_kernel, dim3((unsigned)((cap - first + 255) / 256)), dim3(256), 0, stream, p, first, cap);
-    if (hipGetLastError() != hipSuccess) { vvcgpu_set_error("iota: kernel launch failed"); return nullptr; }
+    std::lock_guard<std::mutex> lock(g_slotMutex);                         // committed only once the fill is queued
+    StreamSlot* slot = find_slot(dev, stream, true);
+    slot->iota = p; slot->iotaN = valid;
   }
+  if (old) retire(dev, stream, old);                                        // queued work of earlier calls may still read it
   return p;
+}
+
+// ---- per-device constant images (common.h): one registry behind one mutex, held while an image is built
+namespace {
+constexpr int VVC_MAX_DEVICES = 64;
+struct DeviceImage { void* ptr; bool built; };
+DeviceImage g_images[VVC_MAX_DEVICES][VVC_IMAGE_KEYS];
+std::mutex g_imageMutex;
+}
+
+int vvcgpu_device_image(int key, size_t bytes, int (*build)(void* dst, const void* arg), const void* arg, void** image)
+{
+  int dev = 0;
+  VVC_HIP(hipGetDevice(&dev));
+  if (dev < 0 || dev >= VVC_MAX_DEVICES) { vvcgpu_set_error("table image %d: device index %d out of range", key, dev); return VVCGPU_E_DEVICE; }
+  std::lock_guard<std::mutex> lock(g_imageMutex);
+  DeviceImage& img = g_images[dev][key];
+  if (!img.built)
+  {
+    // built on the null stream, then a device synchronisation (not on the caller's stream: that would serialise every other thread's first call
+    // behind a stream of unknown length); the memory is freed again if any step fails
+    void* p = nullptr;
+    if (bytes && hipMalloc(&p, bytes) != hipSuccess) { (void)hipGetLastError(); vvcgpu_set_error("table image %d: hipMalloc(%zu) failed", key, bytes); return VVCGPU_E_DEVICE; }
+    int rc = build(p, arg);
+    if (rc == VVCGPU_OK && hipDeviceSynchronize() != hipSuccess) { vvcgpu_set_error("building table image %d failed: %s", key, hipGetErrorString(hipGetLastError())); rc = VVCGPU_E_DEVICE; }
+    if (rc != VVCGPU_OK) { (void)hipFree(p); return rc; }
+    img = DeviceImage{ p, true };
+  }
+  if (image) *image = img.ptr;
+  return VVCGPU_OK;
 }
 
 // Two persistent work counters per (device, stream), zero when handed out: a launch that needs a zeroed counter takes counter `cur` and clears
@@ -278,7 +325,7 @@ int vvcgpu_stream_release(void* stream)
   const hipError_t e = hipStreamSynchronize((hipStream_t)stream);           // queued work may still read the buffers
   if (e == hipSuccess)
   {
-    StreamSlot taken{ sdev, nullptr, {}, {}, {}, nullptr, 0, false, nullptr, 0 };
+    StreamSlot taken{ sdev, nullptr };
     bool found = false;
     {
       std::lock_guard<std::mutex> lock(g_slotMutex);
@@ -296,16 +343,24 @@ int vvcgpu_shutdown(void)
   int dev0 = 0;
   VVC_HIP(hipGetDevice(&dev0));
   std::lock_guard<std::mutex> lock(g_slotMutex);
-  std::vector<StreamSlot> kept;                                             // slots whose device could not be reached: kept, and reported
-  for (auto& s : g_slots)
+  std::lock_guard<std::mutex> imageLock(g_imageMutex);
+  std::vector<StreamSlot> kept;                                             // what a device that cannot be reached holds is kept, and reported
+  int unreachable = 0;
+  for (int d = 0; d < VVC_MAX_DEVICES; d++)
   {
-    if (hipSetDevice(s.device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) { kept.push_back(s); continue; }
-    free_slot(s);
+    bool holds = false;
+    for (auto& s : g_slots) holds |= s.device == d;
+    for (auto& img : g_images[d]) holds |= img.built;
+    if (!holds) continue;
+    const bool reached = hipSetDevice(d) == hipSuccess && hipDeviceSynchronize() == hipSuccess;
+    unreachable += !reached;
+    for (auto& s : g_slots)
+      if (s.device == d) { if (reached) free_slot(s); else kept.push_back(s); }
+    if (reached) for (auto& img : g_images[d]) { if (img.ptr) (void)hipFree(img.ptr); img = DeviceImage{ nullptr, false }; }
   }
-  const size_t nkept = kept.size();
   g_slots.swap(kept);
   VVC_HIP(hipSetDevice(dev0));
-  if (nkept) { vvcgpu_set_error("shutdown: %zu stream slot(s) on unreachable devices were kept", nkept); return VVCGPU_E_DEVICE; }
+  if (unreachable) { vvcgpu_set_error("shutdown: %d unreachable device(s): their stream slots and table images were kept", unreachable); return VVCGPU_E_DEVICE; }
   return VVCGPU_OK;
 }
 }

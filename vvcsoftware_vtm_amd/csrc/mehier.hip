@@ -542,7 +542,8 @@ int vvcgpu_me_hier_search(const vvc_pel* org, int org_stride, const vvc_pel* ref
   g.winBytes = winRowsMax * MH_PITCH * 4 + MH_MAXSLIDE * 128 + 128;            // + the slack the sliding window runs into
   const size_t smem = (size_t)g.winBytes + MH_MAXSLOTS * 4 * sizeof(unsigned);
   const int nblocks = c.n16x * c.n16y;
-  unsigned* packed = static_cast<unsigned*>(vvcgpu_scratch(st, (size_t)nblocks * g.hs * 16 * sizeof(unsigned)));
+  VvcScratch sc(st);
+  unsigned* packed = sc.take<unsigned>((size_t)nblocks * g.hs * 16);
   if (!packed) return VVCGPU_E_DEVICE;
   hipLaunchKernelGGL(mh_pack_org_kernel, dim3((unsigned)(((size_t)nblocks * g.hs * 4 + 255) / 256)), dim3(256), 0, st, org, org_stride, c.org_x, c.org_y, c.n16x, nblocks, g.hs, c.sub_shift, packed);
   VVC_LAUNCH_CHECK();

@@ -24,7 +24,6 @@
 // of lanes holds a 4x4 coefficient group: sign bit hiding is decided per quad with DPP quad permutes.
 #include "common.h"
 #include "mfma_tr.h"
-#include <mutex>
 
 namespace {
 // Pointer arguments of functions that are NOT inlined arrive as generic pointers: every access through them is a FLAT instruction (both wait counters, no
@@ -2234,36 +2233,18 @@ __global__ __launch_bounds__(256, 3) void rc_chain_kernel(const Pel* __restrict_
 }  // namespace
 
 // f16 LDS image of the matrices (mfma_tr.h): built once per device
+static int mfma_image_build(void* dst, const void* tables)
+{
+  const VvcTrTables& tb = *static_cast<const VvcTrTables*>(tables);
+  VVC_HIP(hipMemset(dst, 0, (size_t)RC_IMG_U4 * 16));                   // row padding
+  hipLaunchKernelGGL(rc_build_tables_kernel, dim3(16), dim3(256), 0, (hipStream_t)0, static_cast<_Float16*>(dst), tb.tr32, tb.tr32t);
+  VVC_LAUNCH_CHECK();
+  return VVCGPU_OK;
+}
 const _Float16* vvcgpu_mfma_image(const VvcTrTables& tb)
 {
-  static std::mutex imageMutex;
-  static _Float16* images[64] = { nullptr };
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) { vvcgpu_set_error("mfma image: device index"); return nullptr; }
-  std::lock_guard<std::mutex> lock(imageMutex);
-  if (!images[dev])
-  {
-    // built on the null stream with blocking calls (not on the caller's stream: that would serialise every other thread's first call behind
-    // a stream of unknown length); the buffer is released again if any step fails
-    void* p = nullptr;
-    hipError_t e = hipMalloc(&p, (size_t)RC_IMG_U4 * 16);
-    if (e != hipSuccess) { vvcgpu_set_error("mfma image: hipMalloc failed: %s", hipGetErrorString(e)); return nullptr; }
-    e = hipMemset(p, 0, (size_t)RC_IMG_U4 * 16);                    // row padding
-    if (e == hipSuccess)
-    {
-      hipLaunchKernelGGL(rc_build_tables_kernel, dim3(16), dim3(256), 0, (hipStream_t)0, static_cast<_Float16*>(p), tb.tr32, tb.tr32t);
-      e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipDeviceSynchronize();     // other streams may use the image right after this call returns
-    if (e != hipSuccess)
-    {
-      (void)hipFree(p);
-      vvcgpu_set_error("building the f16 table image failed: %s", hipGetErrorString(e));
-      return nullptr;
-    }
-    images[dev] = static_cast<_Float16*>(p);
-  }
-  return images[dev];
+  void* p = nullptr;
+  return vvcgpu_device_image(VVC_IMAGE_TR_F16, (size_t)RC_IMG_U4 * 16, mfma_image_build, &tb, &p) == VVCGPU_OK ? static_cast<const _Float16*>(p) : nullptr;
 }
 
 __attribute__((visibility("hidden"))) int vvcgpu_tr_image_build(void)
@@ -2287,13 +2268,11 @@ static int rc_chain_launch(int mode, const vvc_pel* org_base, const vvc_pel* pre
   // scratch: the class lists, (plain transforms) the descriptors as chain descriptors, and per wave of the chain launch two 4096-int buffers for a TU its
   // body cannot take (rc_fallback_call: touched only then)
   constexpr int CHAIN_WGS = 768;
-  const size_t ints = (size_t)RC_NCLS * n;
-  const size_t convOff = (ints * sizeof(int) + 63) & ~(size_t)63;
-  const size_t fbOff = (convOff + (mode == RC_CHAIN ? 0 : (size_t)n * sizeof(RcDesc)) + 63) & ~(size_t)63;
-  int* ws = static_cast<int*>(vvcgpu_scratch(st, fbOff + (size_t)CHAIN_WGS * 4 * 8192 * sizeof(int)));
-  if (!ws) return VVCGPU_E_DEVICE;
-  RcDesc* conv = mode == RC_CHAIN ? nullptr : reinterpret_cast<RcDesc*>(reinterpret_cast<unsigned char*>(ws) + convOff);
-  int* fbScratch = reinterpret_cast<int*>(reinterpret_cast<unsigned char*>(ws) + fbOff);
+  VvcScratch sc(st);
+  int* lists = sc.take<int>((size_t)RC_NCLS * n);
+  RcDesc* conv = mode == RC_CHAIN ? nullptr : sc.take<RcDesc>(n);
+  int* fbScratch = sc.take<int>((size_t)CHAIN_WGS * 4 * 8192);
+  if (!lists || (mode != RC_CHAIN && !conv) || !fbScratch) return VVCGPU_E_DEVICE;
   const RcDesc* descs = mode == RC_CHAIN ? static_cast<const RcDesc*>(descs_raw) : conv;
   // the header lives in the stream's persistent zeroed counters: this call's set is clean, the classifier clears the other set for the next
   // call (no fill launch in front of the chain)
@@ -2301,7 +2280,6 @@ static int rc_chain_launch(int mode, const vvc_pel* org_base, const vvc_pel* pre
   int* counters = vvcgpu_counters(st, &cur);
   if (!counters) return VVCGPU_E_DEVICE;
   int* hdr = counters + VVC_CTR_INTS * cur;
-  int* lists = ws;
   RcBins bins;
   memset(&bins, 0, sizeof bins);
   if (runs)

@@ -18,7 +18,6 @@
 #include "common.h"
 #include "mfma_tr.h"
 #include "tr_tables.inc"
-#include <mutex>
 
 // resichain.hip: the chain's bodies as plain transforms (mode 1 forward, 2 inverse): ONE launch with packed matrix-core tiles for long calls
 int vvcgpu_tr_chain_launch(int mode, const vvc_pel* resi_in, vvc_pel* resi_out, vvc_coef* coeff, const vvcgpu_tr_desc* descs, int n, int bit_depth, void* stream);
@@ -2342,8 +2341,6 @@ __global__ __launch_bounds__(256) void rdoq_kernel(const TCoeff* __restrict__ co
   }
 }
 
-static bool g_tablesUploaded[64] = { false };
-static std::mutex g_tablesMutex;            // the C ABI may be entered from several host threads: one uploads, the others wait
 constexpr int g_smallGrid = 1280;                  // workgroups of the small-TU kernels (swept in round 2)
 
 // diagonal 4x4-grouped coefficient scan (Rom.cpp:357-405): groups of 4x4 (2x2 when a side is 2) visited along the diagonals
@@ -2366,91 +2363,85 @@ static void host_scan_order(int w, int h, uint16_t* out)
     }
 }
 
-static int ensure_tables()
+// the golden tables of the current device: uploaded by the first call that needs them (vvcgpu_device_image, without memory of its own)
+static int upload_tables(void*, const void*)
 {
-  int dev = 0;
-  VVC_HIP(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 64) { vvcgpu_set_error("device index %d out of range", dev); return VVCGPU_E_DEVICE; }
-  std::lock_guard<std::mutex> lock(g_tablesMutex);
-  if (!g_tablesUploaded[dev])
-  {
-    static int t32[3 * 5460], t32t[3 * 5460];
-    for (int t = 0; t < 3; t++)
-      for (int n = 2; n <= 64; n <<= 1)
+  static int t32[3 * 5460], t32t[3 * 5460];
+  for (int t = 0; t < 3; t++)
+    for (int n = 2; n <= 64; n <<= 1)
+    {
+      const int o = t * 5460 + (n * n - 4) / 3;
+      for (int k = 0; k < n; k++)
+        for (int j = 0; j < n; j++) { t32[o + k * n + j] = VVC_TR_TABLES[o + k * n + j]; t32t[o + j * n + k] = VVC_TR_TABLES[o + k * n + j]; }
+    }
+  VVC_HIP(hipMemcpyToSymbol(HIP_SYMBOL(d_tr32), t32, sizeof(t32)));
+  VVC_HIP(hipMemcpyToSymbol(HIP_SYMBOL(d_tr32t), t32t, sizeof(t32t)));
+  static uint16_t scan[15876];
+  int off[36], o = 0;
+  for (int a = 0; a < 6; a++)
+    for (int b = 0; b < 6; b++) { off[a * 6 + b] = o; host_scan_order(2 << a, 2 << b, scan + o); o += (2 << a) * (2 << b); }
+  VVC_HIP(hipMemcpyToSymbol(HIP_SYMBOL(d_scan), scan, sizeof(scan)));
+  VVC_HIP(hipMemcpyToSymbol(HIP_SYMBOL(d_scanOff), off, sizeof(off)));
+  // dependent quantisation: raster -> scan id
+  static uint16_t invs[15876];
+  for (int a = 0; a < 6; a++)
+    for (int b = 0; b < 6; b++)
+    {
+      const int N = (2 << a) * (2 << b), o0 = off[a * 6 + b];
+      for (int i = 0; i < N; i++) invs[o0 + scan[o0 + i]] = (uint16_t)i;
+    }
+  // depquant_kernel keeps the ancestry of a trellis path as 32 two-bit entries: the sub-block a template read goes to (right of / below / below-right of the
+  // sub-block about to be walked) must lie at most 32 sub-blocks back in the scan from the one that just ended.  True for every shape up to 64x64 (30 for 64x64);
+  // checked here so that a larger transform size cannot pass silently.
+  for (int a = 1; a < 6; a++)
+    for (int b = 1; b < 6; b++)
+    {
+      const int W = 2 << a, H = 2 << b, o0 = off[a * 6 + b], wS = W >> 2, hS = H >> 2;
+      for (int n = 0; n + 1 < wS * hS; n++)                     // n: the sub-block about to be walked, n + 1 the one that just ended
       {
-        const int o = t * 5460 + (n * n - 4) / 3;
-        for (int k = 0; k < n; k++)
-          for (int j = 0; j < n; j++) { t32[o + k * n + j] = VVC_TR_TABLES[o + k * n + j]; t32t[o + j * n + k] = VVC_TR_TABLES[o + k * n + j]; }
-      }
-    VVC_HIP(hipMemcpyToSymbol(HIP_SYMBOL(d_tr32), t32, sizeof(t32)));
-    VVC_HIP(hipMemcpyToSymbol(HIP_SYMBOL(d_tr32t), t32t, sizeof(t32t)));
-    static uint16_t scan[15876];
-    int off[36], o = 0;
-    for (int a = 0; a < 6; a++)
-      for (int b = 0; b < 6; b++) { off[a * 6 + b] = o; host_scan_order(2 << a, 2 << b, scan + o); o += (2 << a) * (2 << b); }
-    VVC_HIP(hipMemcpyToSymbol(HIP_SYMBOL(d_scan), scan, sizeof(scan)));
-    VVC_HIP(hipMemcpyToSymbol(HIP_SYMBOL(d_scanOff), off, sizeof(off)));
-    // dependent quantisation: raster -> scan id
-    static uint16_t invs[15876];
-    for (int a = 0; a < 6; a++)
-      for (int b = 0; b < 6; b++)
-      {
-        const int N = (2 << a) * (2 << b), o0 = off[a * 6 + b];
-        for (int i = 0; i < N; i++) invs[o0 + scan[o0 + i]] = (uint16_t)i;
-      }
-    // depquant_kernel keeps the ancestry of a trellis path as 32 two-bit entries: the sub-block a template read goes to (right of / below / below-right of the
-    // sub-block about to be walked) must lie at most 32 sub-blocks back in the scan from the one that just ended.  True for every shape up to 64x64 (30 for 64x64);
-    // checked here so that a larger transform size cannot pass silently.
-    for (int a = 1; a < 6; a++)
-      for (int b = 1; b < 6; b++)
-      {
-        const int W = 2 << a, H = 2 << b, o0 = off[a * 6 + b], wS = W >> 2, hS = H >> 2;
-        for (int n = 0; n + 1 < wS * hS; n++)                     // n: the sub-block about to be walked, n + 1 the one that just ended
-        {
-          const int p = scan[o0 + 16 * n], sx = (p % W) >> 2, sy = (p / W) >> 2;
-          const int cand[3][2] = { { sx + 1, sy }, { sx, sy + 1 }, { sx + 1, sy + 1 } };
-          for (auto& c : cand)
-            if (c[0] < wS && c[1] < hS)
-            {
-              const int j = invs[o0 + (4 * c[1]) * W + 4 * c[0]] >> 4;
-              if (j - (n + 1) - 1 > 31) { vvcgpu_set_error("depquant tables: a template reaches %d sub-blocks back in a %dx%d TU", j - n - 2, W, H); return VVCGPU_E_UNSUPPORTED; }
-            }
-        }
-      }
-    // the shape-only part of the trellis' position records (depquant_kernel, fillRec)
-    static uint4 psel[15876];
-    static uint2 pmisc[15876];
-    for (int a = 0; a < 6; a++)
-      for (int b = 0; b < 6; b++)
-      {
-        const int W = 2 << a, H = 2 << b, N = W * H, o0 = off[a * 6 + b];
-        for (int si = 0; si < N; si++)
-        {
-          const int sn = si > 0 ? si - 1 : 0, p2 = scan[o0 + sn], x2 = p2 % W, y2 = p2 / W, beg = sn & ~15;
-          const int cx[5] = { x2 + 1, x2 + 2, x2 + 1, x2, x2 }, cy[5] = { y2, y2, y2 + 1, y2 + 1, y2 + 2 };
-          unsigned nb = 0, selLo[2] = { 0x0C0C0C0Cu, 0x0C0C0C0Cu }, selHi[2] = { 0x0C0C0C0Cu, 0x0C0C0C0Cu };
-          for (int t = 0; t < 5; t++)
+        const int p = scan[o0 + 16 * n], sx = (p % W) >> 2, sy = (p / W) >> 2;
+        const int cand[3][2] = { { sx + 1, sy }, { sx, sy + 1 }, { sx + 1, sy + 1 } };
+        for (auto& c : cand)
+          if (c[0] < wS && c[1] < hS)
           {
-            const int r = (cx[t] < W && cy[t] < H) ? (int)invs[o0 + cy[t] * W + cx[t]] - beg : 0;
-            const unsigned rel = (r > 0 && r < 16) ? (unsigned)r : 0u, sh = (unsigned)(t & 3) * 8u, m = 0xFFu << sh;
-            nb |= rel << (4 * t);
-            if (rel != 0u && rel < 8u) selLo[t >> 2] = (selLo[t >> 2] & ~m) | (rel << sh);
-            if (rel >= 8u) selHi[t >> 2] = (selHi[t >> 2] & ~m) | ((rel - 8u) << sh);
+            const int j = invs[o0 + (4 * c[1]) * W + 4 * c[0]] >> 4;
+            if (j - (n + 1) - 1 > 31) { vvcgpu_set_error("depquant tables: a template reaches %d sub-blocks back in a %dx%d TU", j - n - 2, W, H); return VVCGPU_E_UNSUPPORTED; }
           }
-          const int diag = x2 + y2;
-          const unsigned sigL = diag < 2 ? 12 : diag < 5 ? 6 : 0, sigC = diag < 2 ? 6 : 0;
-          const unsigned gtxL = diag < 1 ? 16 : diag < 3 ? 11 : diag < 10 ? 6 : 1, gtxC = diag < 1 ? 6 : 1;
-          psel[o0 + si] = make_uint4(selLo[0], selHi[0], selLo[1], selHi[1]);
-          pmisc[o0 + si] = make_uint2(nb | sigL << 20 | gtxL << 24, nb | sigC << 20 | gtxC << 24);
-        }
       }
-    VVC_HIP(hipMemcpyToSymbol(HIP_SYMBOL(d_dqPosSel), psel, sizeof(psel)));
-    VVC_HIP(hipMemcpyToSymbol(HIP_SYMBOL(d_dqPosMisc), pmisc, sizeof(pmisc)));
-    VVC_HIP(hipMemcpyToSymbol(HIP_SYMBOL(d_dqInv), invs, sizeof(invs)));
-    g_tablesUploaded[dev] = true;
-  }
+    }
+  // the shape-only part of the trellis' position records (depquant_kernel, fillRec)
+  static uint4 psel[15876];
+  static uint2 pmisc[15876];
+  for (int a = 0; a < 6; a++)
+    for (int b = 0; b < 6; b++)
+    {
+      const int W = 2 << a, H = 2 << b, N = W * H, o0 = off[a * 6 + b];
+      for (int si = 0; si < N; si++)
+      {
+        const int sn = si > 0 ? si - 1 : 0, p2 = scan[o0 + sn], x2 = p2 % W, y2 = p2 / W, beg = sn & ~15;
+        const int cx[5] = { x2 + 1, x2 + 2, x2 + 1, x2, x2 }, cy[5] = { y2, y2, y2 + 1, y2 + 1, y2 + 2 };
+        unsigned nb = 0, selLo[2] = { 0x0C0C0C0Cu, 0x0C0C0C0Cu }, selHi[2] = { 0x0C0C0C0Cu, 0x0C0C0C0Cu };
+        for (int t = 0; t < 5; t++)
+        {
+          const int r = (cx[t] < W && cy[t] < H) ? (int)invs[o0 + cy[t] * W + cx[t]] - beg : 0;
+          const unsigned rel = (r > 0 && r < 16) ? (unsigned)r : 0u, sh = (unsigned)(t & 3) * 8u, m = 0xFFu << sh;
+          nb |= rel << (4 * t);
+          if (rel != 0u && rel < 8u) selLo[t >> 2] = (selLo[t >> 2] & ~m) | (rel << sh);
+          if (rel >= 8u) selHi[t >> 2] = (selHi[t >> 2] & ~m) | ((rel - 8u) << sh);
+        }
+        const int diag = x2 + y2;
+        const unsigned sigL = diag < 2 ? 12 : diag < 5 ? 6 : 0, sigC = diag < 2 ? 6 : 0;
+        const unsigned gtxL = diag < 1 ? 16 : diag < 3 ? 11 : diag < 10 ? 6 : 1, gtxC = diag < 1 ? 6 : 1;
+        psel[o0 + si] = make_uint4(selLo[0], selHi[0], selLo[1], selHi[1]);
+        pmisc[o0 + si] = make_uint2(nb | sigL << 20 | gtxL << 24, nb | sigC << 20 | gtxC << 24);
+      }
+    }
+  VVC_HIP(hipMemcpyToSymbol(HIP_SYMBOL(d_dqPosSel), psel, sizeof(psel)));
+  VVC_HIP(hipMemcpyToSymbol(HIP_SYMBOL(d_dqPosMisc), pmisc, sizeof(pmisc)));
+  VVC_HIP(hipMemcpyToSymbol(HIP_SYMBOL(d_dqInv), invs, sizeof(invs)));
   return VVCGPU_OK;
 }
+static int ensure_tables() { return vvcgpu_device_image(VVC_IMAGE_TR_TABLES, 0, upload_tables, nullptr, nullptr); }
 
 // VVCGPU_NO_MFMA=1 (common.h) keeps every large TU on the dot2 kernels
 static int tr_use_mfma() { return vvcgpu_no_mfma() ? 0 : 1; }
@@ -2500,16 +2491,18 @@ int vvcgpu_tr_fwd_batch(const vvc_pel* resi_base, vvc_coef* coeff_base, const vv
   if (n >= 16384 && tr_use_mfma()) return vvcgpu_tr_chain_launch(1, resi_base, nullptr, coeff_base, descs, n, bit_depth, stream);
   // long calls: the small TUs are binned on the device as well and the small kernel walks the bin lists (see small_setup)
   const bool ordered = n >= 16384;
-  int* ws = static_cast<int*>(vvcgpu_scratch(st, sizeof(int) * ((ordered ? 6 : 2) * (size_t)n + 2)));   // cached per-stream scratch: the lists of large (and small) TUs
-  if (!ws) return VVCGPU_E_DEVICE;
+  VvcScratch sc(st);
+  int* ws = sc.take<int>(2 + 2 * (size_t)n);                                // two counters, then the lists of dot2 and matrix-core TUs
+  int* smLists = ordered ? sc.take<int>(4 * (size_t)n) : nullptr;           // the bins of the small TUs
+  if (!ws || (ordered && !smLists)) return VVCGPU_E_DEVICE;
   VVC_HIP(hipMemsetAsync(ws, 0, 2 * sizeof(int), st));
-  int* smCnt = nullptr; int* smLists = nullptr; int* nextCnt = nullptr;
+  int* smCnt = nullptr; int* nextCnt = nullptr;
   if (ordered)
   {
     int cur = 0;
     int* counters = vvcgpu_counters(st, &cur);
     if (!counters) return VVCGPU_E_DEVICE;
-    smCnt = counters + VVC_CTR_INTS * cur; nextCnt = counters + VVC_CTR_INTS * (cur ^ 1); smLists = ws + 2 + 2 * (size_t)n;
+    smCnt = counters + VVC_CTR_INTS * cur; nextCnt = counters + VVC_CTR_INTS * (cur ^ 1);
   }
   const int nb = cdiv(n, SM_DESCS), nl = cdiv(n, 4);
   hipLaunchKernelGGL(tr_collect_large_kernel, dim3(cdiv(n, 1024)), dim3(1024), 0, st, descs, n, ws, tr_use_mfma(), smCnt, smLists, nextCnt);
@@ -2540,16 +2533,18 @@ int vvcgpu_tr_inv_batch(const vvc_coef* coeff_base, vvc_pel* resi_base, const vv
   if (n >= 16384 && n < 65536 && tr_use_mfma()) return vvcgpu_tr_chain_launch(2, nullptr, resi_base, const_cast<vvc_coef*>(coeff_base), descs, n, bit_depth, stream);
   // long calls: the small TUs are binned on the device as well and the small kernel walks the bin lists (see small_setup)
   const bool ordered = n >= 16384;
-  int* ws = static_cast<int*>(vvcgpu_scratch(st, sizeof(int) * ((ordered ? 6 : 2) * (size_t)n + 2)));   // cached per-stream scratch: the lists of large (and small) TUs
-  if (!ws) return VVCGPU_E_DEVICE;
+  VvcScratch sc(st);
+  int* ws = sc.take<int>(2 + 2 * (size_t)n);                                // two counters, then the lists of dot2 and matrix-core TUs
+  int* smLists = ordered ? sc.take<int>(4 * (size_t)n) : nullptr;           // the bins of the small TUs
+  if (!ws || (ordered && !smLists)) return VVCGPU_E_DEVICE;
   VVC_HIP(hipMemsetAsync(ws, 0, 2 * sizeof(int), st));
-  int* smCnt = nullptr; int* smLists = nullptr; int* nextCnt = nullptr;
+  int* smCnt = nullptr; int* nextCnt = nullptr;
   if (ordered)
   {
     int cur = 0;
     int* counters = vvcgpu_counters(st, &cur);
     if (!counters) return VVCGPU_E_DEVICE;
-    smCnt = counters + VVC_CTR_INTS * cur; nextCnt = counters + VVC_CTR_INTS * (cur ^ 1); smLists = ws + 2 + 2 * (size_t)n;
+    smCnt = counters + VVC_CTR_INTS * cur; nextCnt = counters + VVC_CTR_INTS * (cur ^ 1);
   }
   const int nb = cdiv(n, SM_DESCS), nl = cdiv(n, 4);
   hipLaunchKernelGGL(tr_collect_large_kernel, dim3(cdiv(n, 1024)), dim3(1024), 0, st, descs, n, ws, tr_use_mfma(), smCnt, smLists, nextCnt);
@@ -2584,7 +2579,8 @@ int vvcgpu_dequant_tr_inv_batch(const vvc_coef* level_base, vvc_pel* resi_base, 
   const bool ordered = n >= 16384;                                           // shorter calls: the extra launch (~15 us) costs more than the order gains
   if (ordered)
   {
-    int* lists = static_cast<int*>(vvcgpu_scratch(st, (size_t)DQC_NCLS * n * sizeof(int)));
+    VvcScratch sc(st);
+    int* lists = sc.take<int>((size_t)DQC_NCLS * n);
     if (!lists) return VVCGPU_E_DEVICE;
     int cur = 0;
     int* counters = vvcgpu_counters(st, &cur);
@@ -2614,7 +2610,8 @@ int vvcgpu_quant_batch(const vvc_coef* coeff_base, vvc_coef* level_base, const v
   const int rt = ensure_tables();
   if (rt) return rt;
   hipStream_t st = (hipStream_t)stream;
-  int* list = static_cast<int*>(vvcgpu_scratch(st, ((size_t)n + 1) * sizeof(int)));
+  VvcScratch sc(st);
+  int* list = sc.take<int>((size_t)n + 1);
   if (!list) return VVCGPU_E_DEVICE;
   VVC_HIP(hipMemsetAsync(list, 0, sizeof(int), st));
   hipLaunchKernelGGL(quant_small_kernel, dim3(cdiv(n, 16)), dim3(256), 0, st, coeff_base, level_base, descs, n, bit_depth, abs_sum, list);

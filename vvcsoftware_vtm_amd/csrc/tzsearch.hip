@@ -643,11 +643,9 @@ __global__ __launch_bounds__(256) void tz_to_frac_kernel(const vvcgpu_tz_pu* __r
 
 }  // namespace
 
-extern "C" {
-
-int vvcgpu_tz_search_batch(const vvc_pel* org, int org_stride, const vvc_pel* ref, int ref_stride,
-                           const vvcgpu_tz_pu* pus, int n, const vvcgpu_tz_cfg* cfg_host,
-                           vvcgpu_search_best* results, void* stream)
+// the body of vvcgpu_tz_search_batch, claiming from the caller's scope (vvcgpu_me_batch: one scope for the whole chain)
+static int tz_search(const vvc_pel* org, int org_stride, const vvc_pel* ref, int ref_stride, const vvcgpu_tz_pu* pus, int n,
+                     const vvcgpu_tz_cfg* cfg_host, vvcgpu_search_best* results, void* stream, VvcScratch& sc)
 {
   VVC_CHECK_ARG(n >= 0, "tz_search_batch: n %d", n);
   if (n == 0) return VVCGPU_OK;
@@ -691,15 +689,12 @@ int vvcgpu_tz_search_batch(const vvc_pel* org, int org_stride, const vvc_pel* re
   if (c.uniform_pu != 0 && (uw == 16 || uw == 32 || uw == 64) && (uh == 16 || uh == 32 || uh == 64) && gridMax <= 40 &&
       (org_stride & 1) == 0 && (ref_stride & 7) == 0 && ((uintptr_t)org & 3) == 0 && ((uintptr_t)ref & 15) == 0)
   {
-    const size_t packedDw = (size_t)n * 2 * (uh >> 1) * (uw >> 1);
-    const size_t bytes = (size_t)n * (sizeof(TzSave) + sizeof(vvcgpu_search_blk) + sizeof(VvcRasterPer) + sizeof(vvcgpu_search_best)) + packedDw * 4 + 256;
-    unsigned char* ws = static_cast<unsigned char*>(vvcgpu_scratch(st, bytes));
-    if (!ws) return VVCGPU_E_DEVICE;
-    TzSave* save = reinterpret_cast<TzSave*>(ws);
-    vvcgpu_search_best* rbest = reinterpret_cast<vvcgpu_search_best*>(save + n);
-    VvcRasterPer* rper = reinterpret_cast<VvcRasterPer*>(rbest + n);
-    vvcgpu_search_blk* rblk = reinterpret_cast<vvcgpu_search_blk*>(rper + n);
-    unsigned* packed = reinterpret_cast<unsigned*>((reinterpret_cast<uintptr_t>(rblk + n) + 63) & ~(uintptr_t)63);
+    TzSave* save = sc.take<TzSave>(n);
+    vvcgpu_search_best* rbest = sc.take<vvcgpu_search_best>(n);
+    VvcRasterPer* rper = sc.take<VvcRasterPer>(n);
+    vvcgpu_search_blk* rblk = sc.take<vvcgpu_search_blk>(n);
+    unsigned* packed = sc.take<unsigned>((size_t)n * 2 * (uh >> 1) * (uw >> 1));
+    if (!save || !rbest || !rper || !rblk || !packed) return VVCGPU_E_DEVICE;
     launch(1, save, rblk, rper, nullptr);
     VVC_LAUNCH_CHECK();
     vvcgpu_mvcost mv;
@@ -715,6 +710,16 @@ int vvcgpu_tz_search_batch(const vvc_pel* org, int org_stride, const vvc_pel* re
   return VVCGPU_OK;
 }
 
+extern "C" {
+
+int vvcgpu_tz_search_batch(const vvc_pel* org, int org_stride, const vvc_pel* ref, int ref_stride,
+                           const vvcgpu_tz_pu* pus, int n, const vvcgpu_tz_cfg* cfg_host,
+                           vvcgpu_search_best* results, void* stream)
+{
+  VvcScratch sc((hipStream_t)stream);
+  return tz_search(org, org_stride, ref, ref_stride, pus, n, cfg_host, results, stream, sc);
+}
+
 int vvcgpu_me_batch(const vvc_pel* org, int org_stride, const vvc_pel* ref, int ref_stride, const vvcgpu_tz_pu* pus, int n, int w, int h,
                     const vvcgpu_tz_cfg* cfg_host, int bit_depth, int clp_min, int clp_max, int use_hadamard,
                     vvcgpu_search_best* int_results, vvcgpu_frac_result* frac_results, void* stream)
@@ -724,13 +729,13 @@ int vvcgpu_me_batch(const vvc_pel* org, int org_stride, const vvc_pel* ref, int 
   VVC_CHECK_ARG(cfg_host && int_results && frac_results, "me_batch: null pointer");
   vvcgpu_tz_cfg cfgu = *cfg_host;
   if (cfgu.uniform_pu == 0 && (w == 16 || w == 32 || w == 64) && (h == 16 || h == 32 || h == 64)) cfgu.uniform_pu = (h << 16) | w;   // the chain's PUs are w x h
-  int rc = vvcgpu_tz_search_batch(org, org_stride, ref, ref_stride, pus, n, &cfgu, int_results, stream);
-  if (rc != VVCGPU_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
-  unsigned char* scratch = static_cast<unsigned char*>(vvcgpu_scratch(st, (size_t)n * (sizeof(vvcgpu_frac_blk) + 2 * sizeof(int))));
-  if (!scratch) return VVCGPU_E_DEVICE;
-  vvcgpu_frac_blk* blk = reinterpret_cast<vvcgpu_frac_blk*>(scratch);
-  int* preds = reinterpret_cast<int*>(scratch + (size_t)n * sizeof(vvcgpu_frac_blk));
+  VvcScratch sc(st);
+  int rc = tz_search(org, org_stride, ref, ref_stride, pus, n, &cfgu, int_results, stream, sc);
+  if (rc != VVCGPU_OK) return rc;
+  vvcgpu_frac_blk* blk = sc.take<vvcgpu_frac_blk>(n);
+  int* preds = sc.take<int>(2 * (size_t)n);
+  if (!blk || !preds) return VVCGPU_E_DEVICE;
   hipLaunchKernelGGL(tz_to_frac_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, pus, int_results, n, blk, preds);
   VVC_LAUNCH_CHECK();
   vvcgpu_mvcost mv;
