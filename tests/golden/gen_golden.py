@@ -11,9 +11,10 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
+sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import cases  # noqa: E402
-from oraclelib import ref, p, SAO_DTYPE  # noqa: E402
+from oraclelib import ref, p  # noqa: E402
 
 R = ref()
 R.vtmref_dist.restype = C.c_uint64

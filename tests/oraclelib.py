@@ -3,18 +3,9 @@ oracle/_ref/libvtmref.so (the compiled reference).  Test infrastructure only."""
 import ctypes as C
 import os
 import subprocess
-import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ORACLE_DIR = os.path.join(ROOT, "oracle")
-
-
-class SaoCtu(C.Structure):
-    _fields_ = [("type", C.c_int8), ("avail", C.c_uint8), ("offset", C.c_int16 * 32)]
-
-
-SAO_DTYPE = np.dtype([("type", "i1"), ("avail", "u1"), ("offset", "<i2", (32,))])
-assert SAO_DTYPE.itemsize == C.sizeof(SaoCtu) == 66
 
 _oracle = None
 _ref = None

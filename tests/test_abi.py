@@ -2,9 +2,14 @@
 include/vvcgpu.h declares (no compute calls -- there is no GPU here)."""
 import ctypes as C
 import os
+import re
+import shlex
 import subprocess
 
-from vvcsoftware_vtm_amd import capi
+import numpy as np
+import pytest
+
+from vvcsoftware_vtm_amd import abi, capi
 
 
 def _ensure_built():
@@ -45,20 +50,126 @@ def test_version_and_error_text():
 
 
 def test_struct_layouts_match_python_bindings():
-    """numpy / ctypes mirrors used by the host code have exactly the C sizes (no GPU needed; torch is imported lazily)."""
+    """numpy / ctypes mirrors used by the host code have exactly the sizes the built library reports (no GPU needed)."""
     _ensure_built()
-    import numpy as np
-    from vvcsoftware_vtm_amd import ops
     lib = capi.lib()
-    want = {0: ops.SAO_DTYPE.itemsize, 1: C.sizeof(ops.DeblockCfg), 2: ops.DIST_DESC.itemsize, 3: ops.SEARCH_BLK.itemsize,
-            4: C.sizeof(ops.MvCost), 5: ops.SEARCH_BEST.itemsize, 6: ops.IF_DESC.itemsize, 7: ops.MC_DESC.itemsize,
-            8: ops.PELOP_DESC.itemsize, 9: C.sizeof(ops.PelopCfg), 10: ops.TR_DESC.itemsize, 13: ops.DQTR_DESC.itemsize, 14: ops.AFG_DESC.itemsize, 15: ops.AFE_DESC.itemsize,
-            11: ops.FRAC_BLK.itemsize, 12: ops.FRAC_RESULT.itemsize, 16: ops.TZ_PU.itemsize, 17: ops.TZ_CFG.itemsize, 18: ops.INTRA_DESC.itemsize,
-            19: ops.CCLM_DESC.itemsize, 20: ops.INTRA_FILL_DESC.itemsize, 21: ops.IMV_PU.itemsize, 22: ops.IMV_RESULT.itemsize, 23: ops.QUANT_DESC.itemsize, 24: ops.DQ_RATES.itemsize, 25: ops.DEPQUANT_DESC.itemsize,
-            26: ops.RDOQ_RATES.itemsize, 27: ops.RDOQ_DESC.itemsize, 28: ops.INTRA_SATD_DESC.itemsize, 29: ops.AFFINE_ITER.itemsize}
+    want = {0: abi.SAO_DTYPE.itemsize, 1: C.sizeof(abi.DeblockCfg), 2: abi.DIST_DESC.itemsize, 3: abi.SEARCH_BLK.itemsize,
+            4: C.sizeof(abi.MvCost), 5: abi.SEARCH_BEST.itemsize, 6: abi.IF_DESC.itemsize, 7: abi.MC_DESC.itemsize,
+            8: abi.PELOP_DESC.itemsize, 9: C.sizeof(abi.PelopCfg), 10: abi.TR_DESC.itemsize, 13: abi.DQTR_DESC.itemsize, 14: abi.AFG_DESC.itemsize, 15: abi.AFE_DESC.itemsize,
+            11: abi.FRAC_BLK.itemsize, 12: abi.FRAC_RESULT.itemsize, 16: abi.TZ_PU.itemsize, 17: abi.TZ_CFG.itemsize, 18: abi.INTRA_DESC.itemsize,
+            19: abi.CCLM_DESC.itemsize, 20: abi.INTRA_FILL_DESC.itemsize, 21: abi.IMV_PU.itemsize, 22: abi.IMV_RESULT.itemsize, 23: abi.QUANT_DESC.itemsize, 24: abi.DQ_RATES.itemsize, 25: abi.DEPQUANT_DESC.itemsize,
+            26: abi.RDOQ_RATES.itemsize, 27: abi.RDOQ_DESC.itemsize, 28: abi.INTRA_SATD_DESC.itemsize, 29: abi.AFFINE_ITER.itemsize, 30: C.sizeof(abi.MeHierCfg)}
     for k, v in want.items():
         assert lib.vvcgpu_sizeof(k) == v, (k, lib.vvcgpu_sizeof(k), v)
     assert lib.vvcgpu_sizeof(99) == -1
+
+
+# every typedef struct of include/vvcgpu.h -> its mirrors in vvcsoftware_vtm_amd.abi
+MIRRORS = {
+    "vvcgpu_sao_ctu": ["SAO_DTYPE", "SaoCtu"], "vvcgpu_deblock_cfg": ["DeblockCfg"], "vvcgpu_planes": ["Planes"],
+    "vvcgpu_dist_desc": ["DIST_DESC"], "vvcgpu_search_blk": ["SEARCH_BLK"], "vvcgpu_search_best": ["SEARCH_BEST"], "vvcgpu_mvcost": ["MvCost"],
+    "vvcgpu_me_hier_cfg": ["MeHierCfg"], "vvcgpu_tz_pu": ["TZ_PU"], "vvcgpu_tz_cfg": ["TZ_CFG"], "vvcgpu_imv_pu": ["IMV_PU"],
+    "vvcgpu_imv_result": ["IMV_RESULT"], "vvcgpu_frac_blk": ["FRAC_BLK"], "vvcgpu_frac_result": ["FRAC_RESULT"],
+    "vvcgpu_intra_desc": ["INTRA_DESC"], "vvcgpu_intra_satd_desc": ["INTRA_SATD_DESC"], "vvcgpu_cclm_desc": ["CCLM_DESC"],
+    "vvcgpu_intra_fill_desc": ["INTRA_FILL_DESC"], "vvcgpu_quant_desc": ["QUANT_DESC"], "vvcgpu_dq_rates": ["DQ_RATES"],
+    "vvcgpu_depquant_desc": ["DEPQUANT_DESC"], "vvcgpu_rdoq_rates": ["RDOQ_RATES"], "vvcgpu_rdoq_desc": ["RDOQ_DESC"],
+    "vvcgpu_if_desc": ["IF_DESC"], "vvcgpu_mc_desc": ["MC_DESC"], "vvcgpu_pelop_desc": ["PELOP_DESC"], "vvcgpu_pelop_cfg": ["PelopCfg"],
+    "vvcgpu_tr_desc": ["TR_DESC"], "vvcgpu_dqtr_desc": ["DQTR_DESC"], "vvcgpu_resi_chain_desc": ["RC_DESC"], "vvcgpu_rdpcm_desc": ["RDPCM_DESC"],
+    "vvcgpu_afg_desc": ["AFG_DESC"], "vvcgpu_afe_desc": ["AFE_DESC"], "vvcgpu_affine_pu": ["AFFINE_PU"], "vvcgpu_affine_iter": ["AFFINE_ITER"],
+}
+# mirror fields named differently from their C member
+RENAMED = {("MvCost", "lambda_"): "lambda", ("TZ_CFG", "reserved"): "uniform_pu"}
+# mirror fields that name the tail padding of the C struct (no C member)
+TAIL_PADDING = {("RDPCM_DESC", "pad")}
+
+
+def _mirror_fields(m, prefix=""):
+    """[(name, offset, size)] of a dtype's or Structure's fields; the fields of a nested record follow it as "outer.inner"."""
+    if isinstance(m, np.dtype):
+        out = []
+        for name in m.names:
+            dt, off = m.fields[name][:2]
+            out.append((prefix + name, off, dt.itemsize))
+            if dt.names:
+                out += [(n, off + o, sz) for n, o, sz in _mirror_fields(dt, prefix + name + ".")]
+        return out
+    return [(prefix + f[0], getattr(m, f[0]).offset, getattr(m, f[0]).size) for f in m._fields_]
+
+
+def _mirror_size(m):
+    return m.itemsize if isinstance(m, np.dtype) else C.sizeof(m)
+
+
+def test_struct_mirrors_match_header_field_by_field(tmp_path):
+    """the C compiler's sizeof / offsetof of include/vvcgpu.h == every mirror in abi, per struct and per field"""
+    hdr = re.sub(r"/\*.*?\*/", "", open(capi.HEADER).read(), flags=re.S)
+    assert sorted(re.findall(r"typedef\s+struct\s+(vvcgpu_\w+)", hdr)) == sorted(MIRRORS)
+    mirrors = {(cname, name): getattr(abi, name) for cname, names in MIRRORS.items() for name in names}
+    fields = {key: _mirror_fields(m) for key, m in mirrors.items()}
+    seen = {(name, f) for (_, name), fs in fields.items() for f, _, _ in fs}
+    assert set(RENAMED) <= seen and TAIL_PADDING <= seen
+
+    members = sorted({(cname, RENAMED.get((name, f), f)) for (cname, name), fs in fields.items() for f, _, _ in fs if (name, f) not in TAIL_PADDING})
+    src = tmp_path / "layout.c"
+    src.write_text("#include <stddef.h>\n#include <stdio.h>\n#include \"vvcgpu.h\"\nint main(void)\n{\n"
+                   + "".join('  printf("%%s %%zu\\n", "%s", sizeof(%s));\n' % (c, c) for c in MIRRORS)
+                   + "".join('  printf("%%s %%s %%zu %%zu\\n", "%s", "%s", offsetof(%s, %s), sizeof(((%s*)0)->%s));\n' % (c, f, c, f, c, f) for c, f in members)
+                   + "  return 0;\n}\n")
+    exe = tmp_path / "layout"
+    cc = shlex.split(os.environ.get("CC", "cc"))
+    r = subprocess.run(cc + ["-I", os.path.dirname(capi.HEADER), str(src), "-o", str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    c_size, c_member = {}, {}
+    for line in subprocess.check_output([str(exe)], text=True).splitlines():
+        w = line.split()
+        if len(w) == 2:
+            c_size[w[0]] = int(w[1])
+        else:
+            c_member[(w[0], w[1])] = (int(w[2]), int(w[3]))
+
+    bad = []
+    for (cname, name), fs in fields.items():
+        size = _mirror_size(mirrors[(cname, name)])
+        if size != c_size[cname]:
+            bad.append("%s: sizeof %d, %s: %d" % (name, size, cname, c_size[cname]))
+        for f, off, sz in fs:
+            if (name, f) in TAIL_PADDING:
+                if off < max(o + s for g, o, s in fs if g != f) or off + sz != size:
+                    bad.append("%s.%s (padding) at %d + %d is not the tail of %d bytes" % (name, f, off, sz, size))
+                continue
+            cm = RENAMED.get((name, f), f)
+            if (off, sz) != c_member[(cname, cm)]:
+                bad.append("%s.%s at %d + %d, %s.%s at %d + %d" % ((name, f, off, sz, cname, cm) + c_member[(cname, cm)]))
+    assert not bad, "\n".join(bad)
+
+
+def test_every_declared_function_has_a_signature(tmp_path, monkeypatch):
+    _ensure_built()
+    lib = capi.lib()
+    protos = capi.prototypes()
+    assert len(protos) == len(capi.declared_symbols()) >= 60
+    for name, (restype, argtypes) in protos.items():
+        fn = getattr(lib, name)
+        assert fn.restype is restype and fn.argtypes == argtypes, name
+    assert protos["vvcgpu_version"] == (C.c_int, ())
+    assert protos["vvcgpu_last_error"][0] is C.c_char_p and protos["vvcgpu_tr_matrix_host"][0] is C.c_void_p
+    assert protos["vvcgpu_depquant_workspace_bytes"] == (C.c_size_t, (C.c_size_t, C.c_int))
+    assert protos["vvcgpu_malloc"][1] == (C.c_void_p, C.c_size_t)                                           # void**
+    assert protos["vvcgpu_me_hier_search"][1][6:8] == (C.c_void_p, C.c_void_p)                             # vvcgpu_search_best* const*
+    assert protos["vvcgpu_imv_refine_batch"][1][7:9] == (C.c_int, C.c_double)
+    # a value of the wrong type or a wrong argument count is refused before the call
+    with pytest.raises(C.ArgumentError):
+        lib.vvcgpu_sizeof(1.5)
+    with pytest.raises(TypeError):
+        lib.vvcgpu_sizeof()
+    with pytest.raises(TypeError):
+        capi.call("vvcgpu_sizeof", 1, 2)
+    # a C type without a ctypes mapping is an error, not a guess
+    hdr = tmp_path / "vvcgpu.h"
+    hdr.write_text("int vvcgpu_version(void);\nint vvcgpu_scale(float s);\n")
+    monkeypatch.setattr(capi, "HEADER", str(hdr))
+    with pytest.raises(capi.VvcGpuError, match="vvcgpu_scale parameter 1"):
+        capi.prototypes()
 
 
 def test_next_row_entry_points_validate_arguments_without_a_device():

@@ -9,22 +9,9 @@ import torch
 
 import cases
 from oraclelib import oracle, p
+from vvcsoftware_vtm_amd.abi import DQTR_DESC, PELOP_DESC, QUANT_DESC, TR_DESC, PelopCfg
 
 pytestmark = pytest.mark.gpu
-
-TR_DESC = np.dtype([("resi_off", "<i8"), ("coeff_off", "<i8"), ("resi_stride", "<i4"), ("w", "<i2"), ("h", "<i2"),
-                    ("tr_hor", "i1"), ("tr_ver", "i1"), ("reserved", "<i2"), ("reserved2", "<i4")])
-QUANT_DESC = np.dtype([("coeff_off", "<i8"), ("level_off", "<i8"), ("w", "<i2"), ("h", "<i2"), ("intra_slice", "i1"), ("sign_hiding", "i1"),
-                       ("reserved", "<i2"), ("qp", "<i4"), ("reserved2", "<i4")])
-DQTR_DESC = np.dtype([("resi_off", "<i8"), ("level_off", "<i8"), ("resi_stride", "<i4"), ("w", "<i2"), ("h", "<i2"),
-                      ("tr_hor", "i1"), ("tr_ver", "i1"), ("dep_quant", "i1"), ("reserved", "i1"), ("qp", "<i4")])
-PELOP_DESC = np.dtype([("src0_off", "<i8"), ("src1_off", "<i8"), ("dst_off", "<i8"), ("src0_stride", "<i4"),
-                       ("src1_stride", "<i4"), ("dst_stride", "<i4"), ("w", "<i2"), ("h", "<i2")])
-
-
-class PelopCfg(C.Structure):
-    _fields_ = [("scale", C.c_int32), ("shift", C.c_int32), ("offset", C.c_int32), ("clip", C.c_int32),
-                ("clp_min", C.c_int32), ("clp_max", C.c_int32)]
 
 
 def oracle_chain(org, pred, tus, bd, W):

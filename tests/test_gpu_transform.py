@@ -222,12 +222,11 @@ def test_shipped_tables_match_golden():
     import os
     from vvcsoftware_vtm_amd import capi
     lib = capi.lib()
-    lib.vvcgpu_tr_matrix_host.restype = C.POINTER(C.c_int16)
     g = np.load(os.path.join(os.path.dirname(__file__), "golden", "tr_tables.npz"))
     for t, nm in enumerate(["DCT2", "DCT8", "DST7"]):
         for lg in range(1, 7):
             N = 1 << lg
-            a = np.ctypeslib.as_array(lib.vvcgpu_tr_matrix_host(t, N), shape=(N * N,)).reshape(N, N)
+            a = np.ctypeslib.as_array(C.cast(lib.vvcgpu_tr_matrix_host(t, N), C.POINTER(C.c_int16)), shape=(N * N,)).reshape(N, N)
             assert np.array_equal(a, g["%s_%d" % (nm, N)])
 
 

@@ -1,0 +1,126 @@
+"""Python mirrors of the structs in include/vvcgpu.h: one numpy dtype (records built in arrays) or ctypes Structure (one record passed by
+pointer from the host) per struct, both where both are used.  Field names, order and types follow the header;
+tests/test_abi.py compares every field's offset and size with the C compiler's.
+
+numpy and ctypes only: workload.py and the CPU checkers load this without torch or a GPU."""
+import ctypes as C
+
+import numpy as np
+
+# ---- in-loop filters ------------------------------------------------------------------------------------------
+SAO_DTYPE = np.dtype([("type", "i1"), ("avail", "u1"), ("offset", "<i2", (32,))])
+
+
+class SaoCtu(C.Structure):
+    """vvcgpu_sao_ctu"""
+    _fields_ = [("type", C.c_int8), ("avail", C.c_uint8), ("offset", C.c_int16 * 32)]
+
+
+class DeblockCfg(C.Structure):
+    """vvcgpu_deblock_cfg"""
+    _fields_ = [("bit_depth_luma", C.c_int32), ("bit_depth_chroma", C.c_int32),
+                ("beta_offset_div2", C.c_int32), ("tc_offset_div2", C.c_int32),
+                ("cb_qp_offset", C.c_int32), ("cr_qp_offset", C.c_int32),
+                ("clp_min", C.c_int32 * 3), ("clp_max", C.c_int32 * 3)]
+
+
+class Planes(C.Structure):
+    """vvcgpu_planes"""
+    _fields_ = [("p", C.c_void_p * 3), ("stride", C.c_int32 * 3)]
+
+
+# ---- block distortion and integer motion search -------------------------------------------------------------------
+DIST_DESC = np.dtype([("org_off", "<i8"), ("cur_off", "<i8"), ("org_stride", "<i4"), ("cur_stride", "<i4"),
+                      ("w", "<i2"), ("h", "<i2"), ("sub_shift", "<i2"), ("reserved", "<i2")])
+SEARCH_BLK = np.dtype([("org_x", "<i4"), ("org_y", "<i4"), ("ref_x", "<i4"), ("ref_y", "<i4")])
+SEARCH_BEST = np.dtype([("x", "<i4"), ("y", "<i4"), ("cost", "<u8"), ("sad", "<u8")])
+
+
+class MvCost(C.Structure):
+    """vvcgpu_mvcost"""
+    _fields_ = [("lambda_", C.c_double), ("pred_hor", C.c_int32), ("pred_ver", C.c_int32),
+                ("cost_scale", C.c_int32), ("imv_shift", C.c_int32)]
+
+
+class MeHierCfg(C.Structure):
+    """vvcgpu_me_hier_cfg"""
+    _fields_ = [("org_x", C.c_int32), ("org_y", C.c_int32), ("ref_x", C.c_int32), ("ref_y", C.c_int32), ("n16x", C.c_int32), ("n16y", C.c_int32),
+                ("sub_shift", C.c_int32), ("raster_range", C.c_int32), ("raster_step", C.c_int32), ("dense_range", C.c_int32)]
+
+
+TZ_PU = np.dtype([("org_x", "<i4"), ("org_y", "<i4"), ("ref_x", "<i4"), ("ref_y", "<i4"), ("start_x", "<i4"), ("start_y", "<i4"),
+                  ("pred2_x", "<i4"), ("pred2_y", "<i4"), ("pos_x", "<i4"), ("pos_y", "<i4"), ("pred_hor", "<i4"), ("pred_ver", "<i4"),
+                  ("w", "<i2"), ("h", "<i2"), ("sub_shift", "<i2"), ("flags", "<i2"), ("reserved", "<i4", (2,))])
+TZ_CFG = np.dtype([("lambda", "<f8"), ("cost_scale", "<i4"), ("imv_shift", "<i4"), ("search_range", "<i4"), ("first_search_stop", "<i4"),
+                   ("pic_w", "<i4"), ("pic_h", "<i4"), ("max_cu_w", "<i4"), ("max_cu_h", "<i4"),
+                   ("ref_x0", "<i4"), ("ref_y0", "<i4"), ("ref_x1", "<i4"), ("ref_y1", "<i4"), ("wg_per_pu", "<i4"), ("reserved", "<i4")])   # "reserved" = vvcgpu_tz_cfg.uniform_pu (the field keeps its name: the golden fixtures store this dtype)
+TZ_PRED2, TZ_EXTENDED, TZ_FAST = 1, 2, 4          # TZ_PU.flags
+
+IMV_PU = np.dtype([("org_x", "<i4"), ("org_y", "<i4"), ("ref_x", "<i4"), ("ref_y", "<i4"), ("mv_x", "<i4"), ("mv_y", "<i4"),
+                   ("cand_x", "<i4", (2,)), ("cand_y", "<i4", (2,)), ("pos_x", "<i4"), ("pos_y", "<i4"), ("idx_cost", "<u4", (2,)), ("bits", "<u4"),
+                   ("w", "<i2"), ("h", "<i2"), ("num_cand", "i1"), ("mvp_idx", "i1"), ("reserved", "<i2"), ("reserved2", "<i4")])
+IMV_RESULT = np.dtype([("mv_x", "<i4"), ("mv_y", "<i4"), ("mvp_idx", "<i4"), ("bits", "<u4"), ("cost", "<u8")])
+
+# ---- fractional refinement --------------------------------------------------------------------------------------------
+FRAC_BLK = np.dtype([("org_x", "<i4"), ("org_y", "<i4"), ("ref_x", "<i4"), ("ref_y", "<i4"), ("mv_x", "<i4"), ("mv_y", "<i4")])
+FRAC_RESULT = np.dtype([("half_x", "<i4"), ("half_y", "<i4"), ("qter_x", "<i4"), ("qter_y", "<i4"), ("cost_half", "<u8"), ("cost", "<u8")])
+
+# ---- intra prediction -----------------------------------------------------------------------------------------------------
+INTRA_DESC = np.dtype([("ref_off", "<i8"), ("dst_off", "<i8"), ("dst_stride", "<i4"), ("w", "<i2"), ("h", "<i2"), ("mode", "i1"),
+                       ("filter_refs", "i1"), ("reserved", "<i2"), ("reserved2", "<i4")])
+INTRA_SATD_DESC = np.dtype([("ref_off", "<i8"), ("org_off", "<i8"), ("org_stride", "<i4"), ("w", "<i2"), ("h", "<i2"), ("mode", "i1"),
+                            ("filter_refs", "i1"), ("reserved", "<i2"), ("reserved2", "<i4")])
+CCLM_DESC = np.dtype([("luma_off", "<i8"), ("nb_off", "<i8"), ("dst_off", "<i8"), ("luma_stride", "<i4"), ("dst_stride", "<i4"), ("w", "<i2"),
+                      ("h", "<i2"), ("above_avail", "i1"), ("left_avail", "i1"), ("reserved", "<i2"), ("reserved2", "<i4", (2,))])
+INTRA_FILL_DESC = np.dtype([("rec_off", "<i8"), ("flags_off", "<i8"), ("ref_off", "<i8"), ("rec_stride", "<i4"), ("w", "<i2"), ("h", "<i2"),
+                            ("unit_w", "i1"), ("unit_h", "i1"), ("reserved", "<i2"), ("reserved2", "<i4")])
+
+# ---- quantisers ---------------------------------------------------------------------------------------------------------------
+QUANT_DESC = np.dtype([("coeff_off", "<i8"), ("level_off", "<i8"), ("w", "<i2"), ("h", "<i2"), ("intra_slice", "i1"), ("sign_hiding", "i1"),
+                       ("reserved", "<i2"), ("qp", "<i4"), ("reserved2", "<i4")])
+DQ_RATES = np.dtype([("last_x", "<i4", (64,)), ("last_y", "<i4", (64,)), ("sig_sbb", "<i4", (2, 2)), ("sig", "<i4", (3, 18, 2)), ("gtx", "<i4", (21, 7))])
+DEPQUANT_DESC = np.dtype([("coeff_off", "<i8"), ("level_off", "<i8"), ("lambda", "<f8"), ("qp", "<i4"), ("rates_idx", "<i4"), ("w", "<i2"), ("h", "<i2"),
+                          ("luma", "i1"), ("reserved", "i1", (3,))])
+RDOQ_RATES = np.dtype([("sig", "<i4", (18, 2)), ("par", "<i4", (21, 2)), ("gt1", "<i4", (21, 2)), ("gt2", "<i4", (21, 2)), ("sig_group", "<i4", (2, 2)),
+                       ("last_x", "<i4", (14,)), ("last_y", "<i4", (14,)), ("cbf", "<i4", (2,))])
+RDOQ_DESC = np.dtype([("coeff_off", "<i8"), ("level_off", "<i8"), ("lambda", "<f8"), ("qp", "<i4"), ("rates_idx", "<i4"), ("w", "<i2"), ("h", "<i2"),
+                      ("luma", "i1"), ("sign_hiding", "i1"), ("reserved", "i1", (2,))])
+
+# ---- interpolation, motion compensation, PelBuffer ops --------------------------------------------------------------------
+IF_DESC = np.dtype([("src_off", "<i8"), ("dst_off", "<i8"), ("src_stride", "<i4"), ("dst_stride", "<i4"),
+                    ("w", "<i2"), ("h", "<i2"), ("taps", "i1"), ("is_vertical", "i1"), ("is_first", "i1"),
+                    ("is_last", "i1"), ("coeff", "<i2", (8,)), ("reserved", "<i2", (4,))])
+MC_DESC = np.dtype([("ref0_off", "<i8"), ("ref1_off", "<i8"), ("dst_off", "<i8"), ("ref0_stride", "<i4"),
+                    ("ref1_stride", "<i4"), ("dst_stride", "<i4"), ("w", "<i2"), ("h", "<i2"), ("frac_x0", "i1"),
+                    ("frac_y0", "i1"), ("frac_x1", "i1"), ("frac_y1", "i1"), ("is_luma", "i1"), ("bi", "i1"),
+                    ("reserved", "<i2")])
+PELOP_DESC = np.dtype([("src0_off", "<i8"), ("src1_off", "<i8"), ("dst_off", "<i8"), ("src0_stride", "<i4"),
+                       ("src1_stride", "<i4"), ("dst_stride", "<i4"), ("w", "<i2"), ("h", "<i2")])
+
+
+class PelopCfg(C.Structure):
+    """vvcgpu_pelop_cfg"""
+    _fields_ = [("scale", C.c_int32), ("shift", C.c_int32), ("offset", C.c_int32), ("clip", C.c_int32),
+                ("clp_min", C.c_int32), ("clp_max", C.c_int32)]
+
+
+# ---- transforms and the residual chain -------------------------------------------------------------------------------------
+TR_DESC = np.dtype([("resi_off", "<i8"), ("coeff_off", "<i8"), ("resi_stride", "<i4"), ("w", "<i2"), ("h", "<i2"),
+                    ("tr_hor", "i1"), ("tr_ver", "i1"), ("reserved", "<i2"), ("reserved2", "<i4")])
+DCT2, DCT8, DST7, TSKIP = 0, 1, 2, 3              # tr_hor / tr_ver
+DQTR_DESC = np.dtype([("resi_off", "<i8"), ("level_off", "<i8"), ("resi_stride", "<i4"), ("w", "<i2"), ("h", "<i2"),
+                      ("tr_hor", "i1"), ("tr_ver", "i1"), ("dep_quant", "i1"), ("reserved", "i1"), ("qp", "<i4")])
+RC_DESC = np.dtype([("org_off", "<i8"), ("pred_off", "<i8"), ("rec_off", "<i8"), ("level_off", "<i8"), ("org_stride", "<i4"), ("pred_stride", "<i4"),
+                    ("rec_stride", "<i4"), ("w", "<i2"), ("h", "<i2"), ("tr_hor", "i1"), ("tr_ver", "i1"), ("intra_slice", "i1"), ("sign_hiding", "i1"),
+                    ("qp", "<i4"), ("reserved", "<i4", (2,))])
+RDPCM_DESC = np.dtype([("resi_off", "<i8"), ("coeff_off", "<i8"), ("resi_stride", "<i4"), ("w", "<i2"), ("h", "<i2"), ("mode", "i1"), ("lossless", "i1"),
+                       ("rotate", "i1"), ("intra_slice", "i1"), ("qp", "<i4"), ("reserved", "<i4"), ("pad", "<i4")])    # "pad": the C struct's tail padding
+
+# ---- affine motion --------------------------------------------------------------------------------------------------------------
+AFG_DESC = np.dtype([("pred_off", "<i8"), ("deriv_off", "<i8"), ("pred_stride", "<i4"), ("deriv_stride", "<i4"), ("w", "<i2"), ("h", "<i2"),
+                     ("reserved", "<i4")])
+AFE_DESC = np.dtype([("resi_off", "<i8"), ("deriv_off", "<i8"), ("deriv_stride", "<i4"), ("w", "<i2"), ("h", "<i2"), ("six_param", "<i4"),
+                     ("reserved", "<i4")])
+AFFINE_PU = np.dtype([("pos_x", "<i4"), ("pos_y", "<i4"), ("w", "<i2"), ("h", "<i2"), ("six_param", "<i2"), ("bi", "<i2"), ("mv", "<i4", (2, 3, 2)),
+                      ("dst_off", "<i8"), ("dst_stride", "<i4"), ("first_desc", "<i4")])
+AFFINE_ITER = np.dtype([("pu", AFFINE_PU), ("org_off", "<i8"), ("org_stride", "<i4"), ("reserved", "<i4")])

@@ -1,4 +1,7 @@
-"""ctypes binding of include/vvcgpu.h.  Fails loudly when the HIP library is missing or a call fails."""
+"""ctypes binding of include/vvcgpu.h.  Fails loudly when the HIP library is missing or a call fails.
+
+Every function gets its argtypes / restype from its prototype in the header, so a value of the wrong type is refused by
+ctypes instead of reaching the library as garbage.  The struct mirrors are in `abi`."""
 import ctypes as C
 import os
 import re
@@ -10,21 +13,41 @@ HEADER = os.path.join(ROOT, "include", "vvcgpu.h")
 
 _lib = None
 
+# C type of a parameter / a return value -> ctypes type; any pointer is c_void_p, except the error text
+_PARAM = {"int": C.c_int, "size_t": C.c_size_t, "double": C.c_double}
+_RESULT = {"int": C.c_int, "size_t": C.c_size_t, "const char*": C.c_char_p}
+
 
 class VvcGpuError(RuntimeError):
     pass
 
 
-class SaoCtu(C.Structure):
-    """vvcgpu_sao_ctu"""
-    _fields_ = [("type", C.c_int8), ("avail", C.c_uint8), ("offset", C.c_int16 * 32)]
+def _ctype(decl, table, where):
+    if decl in table:
+        return table[decl]
+    if decl.endswith("*"):
+        return C.c_void_p
+    raise VvcGpuError("%s: %s: type '%s' has no ctypes mapping" % (HEADER, where, decl))
+
+
+def prototypes():
+    """{name: (restype, argtypes)} of every function include/vvcgpu.h declares"""
+    txt = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    txt = re.sub(r"^\s*#.*$", "", txt, flags=re.M)
+    out = {}
+    for ret, name, params in re.findall(r"([\w\s*]+?)\b(vvcgpu_\w+)\s*\(([^()]*)\)\s*;", txt):
+        args = []
+        for i, prm in enumerate(params.split(",") if params.strip() != "void" else []):
+            prm = " ".join(prm.split())
+            m = re.fullmatch(r"(?:const )?(\w+) \w+", prm)
+            args.append(C.c_void_p if "*" in prm else _ctype(m.group(1) if m else prm, _PARAM, "%s parameter %d" % (name, i + 1)))
+        out[name] = (_ctype(" ".join(ret.split()).replace(" *", "*"), _RESULT, name + " result"), tuple(args))
+    return out
 
 
 def declared_symbols():
     """Every function name include/vvcgpu.h declares (used by the ABI test)."""
-    txt = open(HEADER).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(vvcgpu_[a-z0-9_]+)\s*\(", txt)))
+    return sorted(prototypes())
 
 
 def lib():
@@ -34,8 +57,11 @@ def lib():
             raise VvcGpuError(
                 "HIP library %s is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(there is no CPU fallback)" % LIB_PATH)
-        _lib = C.CDLL(LIB_PATH)
-        _lib.vvcgpu_last_error.restype = C.c_char_p
+        dll = C.CDLL(LIB_PATH)
+        for name, (restype, argtypes) in prototypes().items():
+            fn = getattr(dll, name)
+            fn.restype, fn.argtypes = restype, argtypes
+        _lib = dll
     return _lib
 
 
@@ -46,6 +72,8 @@ def check(rc, what=""):
 
 def call(name, *args):
     fn = getattr(lib(), name)
+    if len(args) != len(fn.argtypes):                     # ctypes itself lets extra arguments through
+        raise TypeError("%s takes %d arguments (%d given)" % (name, len(fn.argtypes), len(args)))
     check(fn(*args), name)
 
 

@@ -7,6 +7,11 @@ import numpy as np
 import torch
 
 from . import capi
+# the struct mirrors live in abi; bench.py, the tests and the tools read them as ops.<NAME>
+from .abi import (AFE_DESC, AFFINE_ITER, AFFINE_PU, AFG_DESC, CCLM_DESC, DEPQUANT_DESC, DIST_DESC, DQ_RATES, DQTR_DESC, FRAC_BLK,  # noqa: F401
+                  FRAC_RESULT, IF_DESC, IMV_PU, IMV_RESULT, INTRA_DESC, INTRA_FILL_DESC, INTRA_SATD_DESC, MC_DESC, PELOP_DESC, QUANT_DESC, RC_DESC,
+                  RDOQ_DESC, RDOQ_RATES, RDPCM_DESC, SAO_DTYPE, SEARCH_BEST, SEARCH_BLK, TR_DESC, TZ_CFG, TZ_PU, DeblockCfg, MeHierCfg, MvCost,
+                  PelopCfg, Planes)
 
 
 def _stream():
@@ -50,9 +55,6 @@ def alf_filter_chroma(src, dst, ctu_c, coeff, ctu_enable=None, clp=(0, 1023)):
 
 
 # ---- SAO (SampleAdaptiveOffset.cpp) -------------------------------------------------------------
-SAO_DTYPE = np.dtype([("type", "i1"), ("avail", "u1"), ("offset", "<i2", (32,))])
-
-
 def sao_params_to_device(params, device="cuda"):
     """params: numpy structured array of SAO_DTYPE (one per CTU, raster order)."""
     assert params.dtype == SAO_DTYPE
@@ -69,14 +71,6 @@ def sao_apply(src, dst, ctu_w, ctu_h, bit_depth, params_dev, clp=(0, 1023)):
 
 
 # ---- Deblocking (LoopFilter.cpp) ----------------------------------------------------------------
-class DeblockCfg(C.Structure):
-    """vvcgpu_deblock_cfg"""
-    _fields_ = [("bit_depth_luma", C.c_int32), ("bit_depth_chroma", C.c_int32),
-                ("beta_offset_div2", C.c_int32), ("tc_offset_div2", C.c_int32),
-                ("cb_qp_offset", C.c_int32), ("cr_qp_offset", C.c_int32),
-                ("clp_min", C.c_int32 * 3), ("clp_max", C.c_int32 * 3)]
-
-
 def deblock_cfg(bd=10, beta_off=0, tc_off=0, cb_off=0, cr_off=0):
     mx = (1 << bd) - 1
     return DeblockCfg(bd, bd, beta_off, tc_off, cb_off, cr_off, (C.c_int32 * 3)(0, 0, 0), (C.c_int32 * 3)(mx, mx, mx))
@@ -123,17 +117,7 @@ def alf_stats(org, rec, ctu, cls, filter_type):
 
 
 # ---- block distortion (RdCost) ---------------------------------------------------------------------
-DIST_DESC = np.dtype([("org_off", "<i8"), ("cur_off", "<i8"), ("org_stride", "<i4"), ("cur_stride", "<i4"),
-                      ("w", "<i2"), ("h", "<i2"), ("sub_shift", "<i2"), ("reserved", "<i2")])
-SEARCH_BLK = np.dtype([("org_x", "<i4"), ("org_y", "<i4"), ("ref_x", "<i4"), ("ref_y", "<i4")])
-SEARCH_BEST = np.dtype([("x", "<i4"), ("y", "<i4"), ("cost", "<u8"), ("sad", "<u8")])
 SAD, HAD, SSE, MRSAD, MRHAD = 0, 1, 2, 3, 4
-
-
-class MvCost(C.Structure):
-    """vvcgpu_mvcost"""
-    _fields_ = [("lambda_", C.c_double), ("pred_hor", C.c_int32), ("pred_ver", C.c_int32),
-                ("cost_scale", C.c_int32), ("imv_shift", C.c_int32)]
 
 
 def struct_to_device(arr, device="cuda"):
@@ -166,11 +150,6 @@ def sad_search(org, ref, blocks_dev, nblocks, w, h, sub_shift, dx0, dy0, nx, ny,
     return sad, best
 
 
-class MeHierCfg(C.Structure):
-    _fields_ = [("org_x", C.c_int32), ("org_y", C.c_int32), ("ref_x", C.c_int32), ("ref_y", C.c_int32), ("n16x", C.c_int32), ("n16y", C.c_int32),
-                ("sub_shift", C.c_int32), ("raster_range", C.c_int32), ("raster_step", C.c_int32), ("dense_range", C.c_int32)]
-
-
 def me_hier_search(org, ref, org_xy, ref_xy, n16x, n16y, sub_shift, raster_range, dense_range, mvcost, raster_step=5):
     """D1 + D5 hierarchical form (vvcgpu_me_hier_search): the step-5 raster and the +-dense_range grid of every 16x16 / 32x32 / 64x64 block of the grid
     in one launch.  Returns (raster, dense): two lists of three SEARCH_BEST uint8 tensors (16, 32, 64; None where the grid has no block of the size,
@@ -187,16 +166,6 @@ def me_hier_search(org, ref, org_xy, ref_xy, n16x, n16y, sub_shift, raster_range
 
 
 # ---- N2: integer TZ search of whole PUs (InterSearch::xTZSearch) ---------------------------------------------
-TZ_PU = np.dtype([("org_x", "<i4"), ("org_y", "<i4"), ("ref_x", "<i4"), ("ref_y", "<i4"), ("start_x", "<i4"), ("start_y", "<i4"),
-                  ("pred2_x", "<i4"), ("pred2_y", "<i4"), ("pos_x", "<i4"), ("pos_y", "<i4"), ("pred_hor", "<i4"), ("pred_ver", "<i4"),
-                  ("w", "<i2"), ("h", "<i2"), ("sub_shift", "<i2"), ("flags", "<i2"), ("reserved", "<i4", (2,))])
-TZ_CFG = np.dtype([("lambda", "<f8"), ("cost_scale", "<i4"), ("imv_shift", "<i4"), ("search_range", "<i4"), ("first_search_stop", "<i4"),
-                   ("pic_w", "<i4"), ("pic_h", "<i4"), ("max_cu_w", "<i4"), ("max_cu_h", "<i4"),
-                   ("ref_x0", "<i4"), ("ref_y0", "<i4"), ("ref_x1", "<i4"), ("ref_y1", "<i4"), ("wg_per_pu", "<i4"), ("reserved", "<i4")])   # "reserved" = vvcgpu_tz_cfg.uniform_pu (the field keeps its name: the golden fixtures store this dtype)
-assert TZ_PU.itemsize == 64 and TZ_CFG.itemsize == 64
-TZ_PRED2, TZ_EXTENDED, TZ_FAST = 1, 2, 4
-
-
 def tz_search_batch(org, ref, pus_dev, n, cfg):
     """N2: xTZSearch for n PUs (one wavefront each).  org/ref: 2-D int16 planes (ref = the whole padded reference plane,
     PU positions in plane coordinates); pus_dev: TZ_PU records on the device; cfg: one-element TZ_CFG numpy record (host).
@@ -245,20 +214,10 @@ def picture_hash(method, plane, bit_depth):
 
 
 # ---- N4 intra sample prediction ----------------------------------------------------------------------------
-INTRA_DESC = np.dtype([("ref_off", "<i8"), ("dst_off", "<i8"), ("dst_stride", "<i4"), ("w", "<i2"), ("h", "<i2"), ("mode", "i1"),
-                       ("filter_refs", "i1"), ("reserved", "<i2"), ("reserved2", "<i4")])
-assert INTRA_DESC.itemsize == 32
-
-
 def intra_ref_lengths(w, h):
     t, l = C.c_int(), C.c_int()
     capi.call("vvcgpu_intra_ref_lengths", w, h, C.byref(t), C.byref(l))
     return t.value, l.value
-
-
-INTRA_SATD_DESC = np.dtype([("ref_off", "<i8"), ("org_off", "<i8"), ("org_stride", "<i4"), ("w", "<i2"), ("h", "<i2"), ("mode", "i1"),
-                            ("filter_refs", "i1"), ("reserved", "<i2"), ("reserved2", "<i4")])
-assert INTRA_SATD_DESC.itemsize == 32
 
 
 def intra_satd_batch(refs_base, org_base, descs_dev, n, clp=(0, 1023)):
@@ -273,32 +232,15 @@ def intra_pred_batch(refs_base, dst_base, descs_dev, n, clp=(0, 1023)):
     capi.call("vvcgpu_intra_pred_batch", capi.ptr(refs_base), capi.ptr(dst_base), capi.ptr(descs_dev), n, clp[0], clp[1], _stream())
 
 
-CCLM_DESC = np.dtype([("luma_off", "<i8"), ("nb_off", "<i8"), ("dst_off", "<i8"), ("luma_stride", "<i4"), ("dst_stride", "<i4"), ("w", "<i2"),
-                      ("h", "<i2"), ("above_avail", "i1"), ("left_avail", "i1"), ("reserved", "<i2"), ("reserved2", "<i4", (2,))])
-assert CCLM_DESC.itemsize == 48
-
-
 def cclm_pred_batch(luma_base, nb_base, dst_base, descs_dev, n, bd_luma=10, bd_chroma=10, clp=(0, 1023)):
     """N4: CCLM chroma prediction (xGetLumaRecPixels + xGetLMParameters + predIntraChromaLM) for n chroma blocks."""
     capi.call("vvcgpu_cclm_pred_batch", capi.ptr(luma_base), capi.ptr(nb_base), capi.ptr(dst_base), capi.ptr(descs_dev), n, bd_luma, bd_chroma,
               clp[0], clp[1], _stream())
 
 
-INTRA_FILL_DESC = np.dtype([("rec_off", "<i8"), ("flags_off", "<i8"), ("ref_off", "<i8"), ("rec_stride", "<i4"), ("w", "<i2"), ("h", "<i2"),
-                            ("unit_w", "i1"), ("unit_h", "i1"), ("reserved", "<i2"), ("reserved2", "<i4")])
-assert INTRA_FILL_DESC.itemsize == 40
-
-
 def intra_fill_refs_batch(rec_base, flags_base, refs_base, descs_dev, n, bit_depth=10):
     """N4: xFillReferenceSamples for n blocks: reconstruction + unit availability flags -> packed reference samples."""
     capi.call("vvcgpu_intra_fill_refs_batch", capi.ptr(rec_base), capi.ptr(flags_base), capi.ptr(refs_base), capi.ptr(descs_dev), n, bit_depth, _stream())
-
-
-IMV_PU = np.dtype([("org_x", "<i4"), ("org_y", "<i4"), ("ref_x", "<i4"), ("ref_y", "<i4"), ("mv_x", "<i4"), ("mv_y", "<i4"),
-                   ("cand_x", "<i4", (2,)), ("cand_y", "<i4", (2,)), ("pos_x", "<i4"), ("pos_y", "<i4"), ("idx_cost", "<u4", (2,)), ("bits", "<u4"),
-                   ("w", "<i2"), ("h", "<i2"), ("num_cand", "i1"), ("mvp_idx", "i1"), ("reserved", "<i2"), ("reserved2", "<i4")])
-IMV_RESULT = np.dtype([("mv_x", "<i4"), ("mv_y", "<i4"), ("mvp_idx", "<i4"), ("bits", "<u4"), ("cost", "<u8")])
-assert IMV_PU.itemsize == 72 and IMV_RESULT.itemsize == 24
 
 
 def imv_refine_batch(org, ref, pus_dev, n, cfg, use_hadamard=True, weight=1.0):
@@ -313,11 +255,6 @@ def imv_refine_batch(org, ref, pus_dev, n, cfg, use_hadamard=True, weight=1.0):
     return out
 
 
-QUANT_DESC = np.dtype([("coeff_off", "<i8"), ("level_off", "<i8"), ("w", "<i2"), ("h", "<i2"), ("intra_slice", "i1"), ("sign_hiding", "i1"),
-                       ("reserved", "<i2"), ("qp", "<i4"), ("reserved2", "<i4")])
-assert QUANT_DESC.itemsize == 32
-
-
 def quant_batch(coeff_base, level_base, descs_dev, n, bit_depth=10):
     """N1 forward: Quant::quant without RDOQ (+ sign bit hiding) for n TUs -> abs-sum int32 tensor [n] (bits as uint32)."""
     out = torch.zeros(n, dtype=torch.int32, device=coeff_base.device)
@@ -325,17 +262,9 @@ def quant_batch(coeff_base, level_base, descs_dev, n, bit_depth=10):
     return out
 
 
-DQ_RATES = np.dtype([("last_x", "<i4", (64,)), ("last_y", "<i4", (64,)), ("sig_sbb", "<i4", (2, 2)), ("sig", "<i4", (3, 18, 2)), ("gtx", "<i4", (21, 7))])
-DEPQUANT_DESC = np.dtype([("coeff_off", "<i8"), ("level_off", "<i8"), ("lambda", "<f8"), ("qp", "<i4"), ("rates_idx", "<i4"), ("w", "<i2"), ("h", "<i2"),
-                          ("luma", "i1"), ("reserved", "i1", (3,))])
-assert DEPQUANT_DESC.itemsize == 40 and DQ_RATES.itemsize == 4 * (128 + 4 + 108 + 147)
-
-
 def depquant_batch(coeff_base, level_base, descs_dev, n, rates_dev, total_coeffs, bit_depth=10):
     """N1: dependent-quantisation trellis (DQIntern::DepQuant::quant) for n TUs -> abs-sum int32 tensor [n] (bits as uint32)."""
-    lib = capi.lib()
-    lib.vvcgpu_depquant_workspace_bytes.restype = C.c_size_t
-    nbytes = int(lib.vvcgpu_depquant_workspace_bytes(C.c_size_t(total_coeffs), n))
+    nbytes = capi.lib().vvcgpu_depquant_workspace_bytes(total_coeffs, n)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=coeff_base.device)
     out = torch.zeros(n, dtype=torch.int32, device=coeff_base.device)
     capi.call("vvcgpu_depquant_batch", capi.ptr(coeff_base), capi.ptr(level_base), capi.ptr(descs_dev), n, capi.ptr(rates_dev), bit_depth,
@@ -343,18 +272,9 @@ def depquant_batch(coeff_base, level_base, descs_dev, n, rates_dev, total_coeffs
     return out
 
 
-RDOQ_RATES = np.dtype([("sig", "<i4", (18, 2)), ("par", "<i4", (21, 2)), ("gt1", "<i4", (21, 2)), ("gt2", "<i4", (21, 2)), ("sig_group", "<i4", (2, 2)),
-                       ("last_x", "<i4", (14,)), ("last_y", "<i4", (14,)), ("cbf", "<i4", (2,))])
-RDOQ_DESC = np.dtype([("coeff_off", "<i8"), ("level_off", "<i8"), ("lambda", "<f8"), ("qp", "<i4"), ("rates_idx", "<i4"), ("w", "<i2"), ("h", "<i2"),
-                      ("luma", "i1"), ("sign_hiding", "i1"), ("reserved", "i1", (2,))])
-assert RDOQ_DESC.itemsize == 40 and RDOQ_RATES.itemsize == 784
-
-
 def rdoq_batch(coeff_base, level_base, descs_dev, n, rates_dev, total_coeffs, bit_depth=10):
     """N1: rate-distortion optimised quantiser (QuantRDOQ::xRateDistOptQuant) for n TUs -> abs-sum int32 tensor [n] (bits as uint32)."""
-    lib = capi.lib()
-    lib.vvcgpu_rdoq_workspace_bytes.restype = C.c_size_t
-    nbytes = int(lib.vvcgpu_rdoq_workspace_bytes(C.c_size_t(total_coeffs), n))
+    nbytes = capi.lib().vvcgpu_rdoq_workspace_bytes(total_coeffs, n)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=coeff_base.device)
     out = torch.zeros(n, dtype=torch.int32, device=coeff_base.device)
     capi.call("vvcgpu_rdoq_batch", capi.ptr(coeff_base), capi.ptr(level_base), capi.ptr(descs_dev), n, capi.ptr(rates_dev), bit_depth,
@@ -363,23 +283,6 @@ def rdoq_batch(coeff_base, level_base, descs_dev, n, rates_dev, total_coeffs, bi
 
 
 # ---- interpolation / MC / PelBuffer ops -------------------------------------------------------------
-IF_DESC = np.dtype([("src_off", "<i8"), ("dst_off", "<i8"), ("src_stride", "<i4"), ("dst_stride", "<i4"),
-                    ("w", "<i2"), ("h", "<i2"), ("taps", "i1"), ("is_vertical", "i1"), ("is_first", "i1"),
-                    ("is_last", "i1"), ("coeff", "<i2", (8,)), ("reserved", "<i2", (4,))])
-MC_DESC = np.dtype([("ref0_off", "<i8"), ("ref1_off", "<i8"), ("dst_off", "<i8"), ("ref0_stride", "<i4"),
-                    ("ref1_stride", "<i4"), ("dst_stride", "<i4"), ("w", "<i2"), ("h", "<i2"), ("frac_x0", "i1"),
-                    ("frac_y0", "i1"), ("frac_x1", "i1"), ("frac_y1", "i1"), ("is_luma", "i1"), ("bi", "i1"),
-                    ("reserved", "<i2")])
-PELOP_DESC = np.dtype([("src0_off", "<i8"), ("src1_off", "<i8"), ("dst_off", "<i8"), ("src0_stride", "<i4"),
-                       ("src1_stride", "<i4"), ("dst_stride", "<i4"), ("w", "<i2"), ("h", "<i2")])
-assert IF_DESC.itemsize == 56 and MC_DESC.itemsize == 48 and PELOP_DESC.itemsize == 40
-
-
-class PelopCfg(C.Structure):
-    _fields_ = [("scale", C.c_int32), ("shift", C.c_int32), ("offset", C.c_int32), ("clip", C.c_int32),
-                ("clp_min", C.c_int32), ("clp_max", C.c_int32)]
-
-
 def if_batch(src_base, dst_base, descs_dev, n, bit_depth=10, clp=(0, 1023)):
     capi.call("vvcgpu_if_batch", capi.ptr(src_base), capi.ptr(dst_base), capi.ptr(descs_dev), n, bit_depth, clp[0], clp[1], _stream())
 
@@ -410,12 +313,6 @@ def pelop_batch(op, src0_base, src1_base, dst_base, descs_dev, n, cfg):
 
 
 # ---- transforms (TrQuant) ----------------------------------------------------------------------------
-TR_DESC = np.dtype([("resi_off", "<i8"), ("coeff_off", "<i8"), ("resi_stride", "<i4"), ("w", "<i2"), ("h", "<i2"),
-                    ("tr_hor", "i1"), ("tr_ver", "i1"), ("reserved", "<i2"), ("reserved2", "<i4")])
-assert TR_DESC.itemsize == 32
-DCT2, DCT8, DST7, TSKIP = 0, 1, 2, 3
-
-
 def tr_fwd_batch(resi_base, coeff_base, descs_dev, n, bit_depth=10):
     capi.call("vvcgpu_tr_fwd_batch", capi.ptr(resi_base), capi.ptr(coeff_base), capi.ptr(descs_dev), n, bit_depth, _stream())
 
@@ -425,17 +322,6 @@ def tr_inv_batch(coeff_base, resi_base, descs_dev, n, bit_depth=10):
 
 
 # ---- fused fractional refinement (InterSearch::xPatternSearchFracDIF) ---------------------------------------
-FRAC_BLK = np.dtype([("org_x", "<i4"), ("org_y", "<i4"), ("ref_x", "<i4"), ("ref_y", "<i4"), ("mv_x", "<i4"), ("mv_y", "<i4")])
-FRAC_RESULT = np.dtype([("half_x", "<i4"), ("half_y", "<i4"), ("qter_x", "<i4"), ("qter_y", "<i4"), ("cost_half", "<u8"), ("cost", "<u8")])
-
-
-AFG_DESC = np.dtype([("pred_off", "<i8"), ("deriv_off", "<i8"), ("pred_stride", "<i4"), ("deriv_stride", "<i4"), ("w", "<i2"), ("h", "<i2"),
-                     ("reserved", "<i4")])
-AFE_DESC = np.dtype([("resi_off", "<i8"), ("deriv_off", "<i8"), ("deriv_stride", "<i4"), ("w", "<i2"), ("h", "<i2"), ("six_param", "<i4"),
-                     ("reserved", "<i4")])
-assert AFG_DESC.itemsize == 32 and AFE_DESC.itemsize == 32
-
-
 def affine_sobel_batch(vertical, pred_base, deriv_base, descs_dev, n):
     """N3: Sobel derivative planes of prediction blocks (table slots m_HorizontalSobelFilter / m_VerticalSobelFilter)."""
     capi.call("vvcgpu_affine_sobel_batch", int(vertical), capi.ptr(pred_base), capi.ptr(deriv_base), capi.ptr(descs_dev), n, _stream())
@@ -447,11 +333,6 @@ def affine_equal_coeff_batch(resi_base, gx_base, gy_base, descs_dev, n):
     capi.call("vvcgpu_affine_equal_coeff_batch", capi.ptr(resi_base), capi.ptr(gx_base), capi.ptr(gy_base), capi.ptr(descs_dev), n,
               capi.ptr(out), _stream())
     return out
-
-
-DQTR_DESC = np.dtype([("resi_off", "<i8"), ("level_off", "<i8"), ("resi_stride", "<i4"), ("w", "<i2"), ("h", "<i2"),
-                      ("tr_hor", "i1"), ("tr_ver", "i1"), ("dep_quant", "i1"), ("reserved", "i1"), ("qp", "<i4")])
-assert DQTR_DESC.itemsize == 32
 
 
 def dequant_tr_inv_batch(level_base, resi_base, descs_dev, n, bit_depth, coeff_out=None):
@@ -472,12 +353,6 @@ def frac_refine(org, ref, blocks_dev, nblocks, w, h, bit_depth, mvcost, use_hada
 
 
 # ---- fused residual chain (InterSearch::xEstimateInterResidualQT per TU) ------------------------------------
-RC_DESC = np.dtype([("org_off", "<i8"), ("pred_off", "<i8"), ("rec_off", "<i8"), ("level_off", "<i8"), ("org_stride", "<i4"), ("pred_stride", "<i4"),
-                    ("rec_stride", "<i4"), ("w", "<i2"), ("h", "<i2"), ("tr_hor", "i1"), ("tr_ver", "i1"), ("intra_slice", "i1"), ("sign_hiding", "i1"),
-                    ("qp", "<i4"), ("reserved", "<i4", (2,))])
-assert RC_DESC.itemsize == 64
-
-
 def resi_chain_batch(org_base, pred_base, rec_base, level_base, descs_dev, n, bit_depth=10, clp=(0, 1023)):
     """subtract -> forward transform -> Quant::quant -> Quant::dequant -> inverse transform -> reconstruction of n TUs in one pass.
     Returns the abs-sum int32 tensor [n] (bits as uint32; 0xFFFFFFFF marks a TU outside the entry point's preconditions)."""
@@ -497,11 +372,6 @@ def resi_chain_runs_batch(org_base, pred_base, rec_base, level_base, descs_dev, 
 
 
 # ---- picture-level forms of the in-loop entry points (three planes, one launch each) ------------------------
-class Planes(C.Structure):
-    """vvcgpu_planes"""
-    _fields_ = [("p", C.c_void_p * 3), ("stride", C.c_int32 * 3)]
-
-
 def planes(ts):
     """three 2-D int16 CUDA tensors (Y, Cb, Cr) -> vvcgpu_planes"""
     pl = Planes()
@@ -567,16 +437,6 @@ def alf_classify_stats_picture(org, rec, ctu, bit_depth):
 
 
 # ---- T3 residual DPCM, I3 affine sub-block vectors -------------------------------------------------------------
-RDPCM_DESC = np.dtype([("resi_off", "<i8"), ("coeff_off", "<i8"), ("resi_stride", "<i4"), ("w", "<i2"), ("h", "<i2"), ("mode", "i1"), ("lossless", "i1"),
-                       ("rotate", "i1"), ("intra_slice", "i1"), ("qp", "<i4"), ("reserved", "<i4"), ("pad", "<i4")])
-AFFINE_PU = np.dtype([("pos_x", "<i4"), ("pos_y", "<i4"), ("w", "<i2"), ("h", "<i2"), ("six_param", "<i2"), ("bi", "<i2"), ("mv", "<i4", (2, 3, 2)),
-                      ("dst_off", "<i8"), ("dst_stride", "<i4"), ("first_desc", "<i4")])
-MC_DESC = np.dtype([("ref0_off", "<i8"), ("ref1_off", "<i8"), ("dst_off", "<i8"), ("ref0_stride", "<i4"), ("ref1_stride", "<i4"), ("dst_stride", "<i4"),
-                    ("w", "<i2"), ("h", "<i2"), ("frac_x0", "i1"), ("frac_y0", "i1"), ("frac_x1", "i1"), ("frac_y1", "i1"), ("is_luma", "i1"), ("bi", "i1"),
-                    ("reserved", "<i2")])
-assert RDPCM_DESC.itemsize == 40 and AFFINE_PU.itemsize == 80 and MC_DESC.itemsize == 48
-
-
 def rdpcm_fwd_batch(resi_base, coeff_base, descs_dev, n, bit_depth=10):
     """TrQuant::applyForwardRDPCM for n TUs -> abs-sum int32 tensor [n] (bits as uint32)"""
     out = torch.zeros(n, dtype=torch.int32, device=resi_base.device)
@@ -587,10 +447,6 @@ def rdpcm_fwd_batch(resi_base, coeff_base, descs_dev, n, bit_depth=10):
 def rdpcm_inv_batch(resi_base, descs_dev, n):
     """TrQuant::invRdpcmNxN, in place"""
     capi.call("vvcgpu_rdpcm_inv_batch", capi.ptr(resi_base), capi.ptr(descs_dev), n, _stream())
-
-
-AFFINE_ITER = np.dtype([("pu", AFFINE_PU), ("org_off", "<i8"), ("org_stride", "<i4"), ("reserved", "<i4")])
-assert AFFINE_ITER.itemsize == 96
 
 
 def affine_me_iter_batch(org_base, ref_base, pred_base, items_dev, n, n_subblocks, dist_kind, pic_w, pic_h, ref_origin, ref_stride,

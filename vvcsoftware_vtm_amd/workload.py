@@ -26,57 +26,12 @@ import ctypes as C
 import numpy as np
 
 from . import synth
+from .abi import (DEPQUANT_DESC, DQ_RATES, DQTR_DESC, FRAC_BLK, FRAC_RESULT, MC_DESC, PELOP_DESC, QUANT_DESC, RC_DESC, SAO_DTYPE,  # noqa: F401
+                  SEARCH_BEST, SEARCH_BLK, TR_DESC, DeblockCfg, MvCost, PelopCfg)
 
 MARGIN = 144          # reference picture margin (maxCUWidth + 16, Picture.cpp:737-742)
 CTU = 128
 STAGES = ["me", "frac", "mc", "resi", "dbk", "sao", "alf"]
-
-DIST_DESC = np.dtype([("org_off", "<i8"), ("cur_off", "<i8"), ("org_stride", "<i4"), ("cur_stride", "<i4"),
-                      ("w", "<i2"), ("h", "<i2"), ("sub_shift", "<i2"), ("reserved", "<i2")])
-SEARCH_BLK = np.dtype([("org_x", "<i4"), ("org_y", "<i4"), ("ref_x", "<i4"), ("ref_y", "<i4")])
-SEARCH_BEST = np.dtype([("x", "<i4"), ("y", "<i4"), ("cost", "<u8"), ("sad", "<u8")])
-MC_DESC = np.dtype([("ref0_off", "<i8"), ("ref1_off", "<i8"), ("dst_off", "<i8"), ("ref0_stride", "<i4"),
-                    ("ref1_stride", "<i4"), ("dst_stride", "<i4"), ("w", "<i2"), ("h", "<i2"), ("frac_x0", "i1"),
-                    ("frac_y0", "i1"), ("frac_x1", "i1"), ("frac_y1", "i1"), ("is_luma", "i1"), ("bi", "i1"),
-                    ("reserved", "<i2")])
-PELOP_DESC = np.dtype([("src0_off", "<i8"), ("src1_off", "<i8"), ("dst_off", "<i8"), ("src0_stride", "<i4"),
-                       ("src1_stride", "<i4"), ("dst_stride", "<i4"), ("w", "<i2"), ("h", "<i2")])
-TR_DESC = np.dtype([("resi_off", "<i8"), ("coeff_off", "<i8"), ("resi_stride", "<i4"), ("w", "<i2"), ("h", "<i2"),
-                    ("tr_hor", "i1"), ("tr_ver", "i1"), ("reserved", "<i2"), ("reserved2", "<i4")])
-SAO_DTYPE = np.dtype([("type", "i1"), ("avail", "u1"), ("offset", "<i2", (32,))])
-FRAC_BLK = np.dtype([("org_x", "<i4"), ("org_y", "<i4"), ("ref_x", "<i4"), ("ref_y", "<i4"), ("mv_x", "<i4"), ("mv_y", "<i4")])
-FRAC_RESULT = np.dtype([("half_x", "<i4"), ("half_y", "<i4"), ("qter_x", "<i4"), ("qter_y", "<i4"), ("cost_half", "<u8"), ("cost", "<u8")])
-
-
-QUANT_DESC = np.dtype([("coeff_off", "<i8"), ("level_off", "<i8"), ("w", "<i2"), ("h", "<i2"), ("intra_slice", "i1"), ("sign_hiding", "i1"),
-                       ("reserved", "<i2"), ("qp", "<i4"), ("reserved2", "<i4")])
-DQTR_DESC = np.dtype([("resi_off", "<i8"), ("level_off", "<i8"), ("resi_stride", "<i4"), ("w", "<i2"), ("h", "<i2"),
-                      ("tr_hor", "i1"), ("tr_ver", "i1"), ("dep_quant", "i1"), ("reserved", "i1"), ("qp", "<i4")])
-RC_DESC = np.dtype([("org_off", "<i8"), ("pred_off", "<i8"), ("rec_off", "<i8"), ("level_off", "<i8"), ("org_stride", "<i4"), ("pred_stride", "<i4"),
-                    ("rec_stride", "<i4"), ("w", "<i2"), ("h", "<i2"), ("tr_hor", "i1"), ("tr_ver", "i1"), ("intra_slice", "i1"), ("sign_hiding", "i1"),
-                    ("qp", "<i4"), ("reserved", "<i4", (2,))])
-DQ_RATES = np.dtype([("last_x", "<i4", (64,)), ("last_y", "<i4", (64,)), ("sig_sbb", "<i4", (2, 2)), ("sig", "<i4", (3, 18, 2)), ("gtx", "<i4", (21, 7))])
-DEPQUANT_DESC = np.dtype([("coeff_off", "<i8"), ("level_off", "<i8"), ("lambda", "<f8"), ("qp", "<i4"), ("rates_idx", "<i4"), ("w", "<i2"), ("h", "<i2"),
-                          ("luma", "i1"), ("reserved", "i1", (3,))])
-assert QUANT_DESC.itemsize == 32 and DQTR_DESC.itemsize == 32 and RC_DESC.itemsize == 64 and DEPQUANT_DESC.itemsize == 40
-
-
-class MvCost(C.Structure):
-    _fields_ = [("lambda_", C.c_double), ("pred_hor", C.c_int32), ("pred_ver", C.c_int32),
-                ("cost_scale", C.c_int32), ("imv_shift", C.c_int32)]
-
-
-class PelopCfg(C.Structure):
-    _fields_ = [("scale", C.c_int32), ("shift", C.c_int32), ("offset", C.c_int32), ("clip", C.c_int32),
-                ("clp_min", C.c_int32), ("clp_max", C.c_int32)]
-
-
-class DeblockCfg(C.Structure):
-    _fields_ = [("bit_depth_luma", C.c_int32), ("bit_depth_chroma", C.c_int32),
-                ("beta_offset_div2", C.c_int32), ("tc_offset_div2", C.c_int32),
-                ("cb_qp_offset", C.c_int32), ("cr_qp_offset", C.c_int32),
-                ("clp_min", C.c_int32 * 3), ("clp_max", C.c_int32 * 3)]
-
 
 def _plane_offsets(sizes):
     """start (in samples) of each plane when the planes of one picture share an allocation: starts rounded up to 64 samples;
@@ -488,8 +443,6 @@ class Workload:
             on_input_set(st["rot"], st)
         out = {}
         bd, mx = self.bd, self.mx
-        cfg_mv = ops.MvCost(self.mvcost.lambda_, self.mvcost.pred_hor, self.mvcost.pred_ver, self.mvcost.cost_scale, self.mvcost.imv_shift)
-        fmv = ops.MvCost(self.frac_mvcost.lambda_, self.frac_mvcost.pred_hor, self.frac_mvcost.pred_ver, 0, 0)
         main = torch.cuda.current_stream()
         if overlap and "streams" not in st:
             st["streams"] = [torch.cuda.Stream() for _ in range(3)]
@@ -522,7 +475,7 @@ class Workload:
                 # xPatternSearch and the raster stage of xTZSearch keep only the best candidate
                 # (InterSearch.cpp:1887-1935, 1979-2000): no SAD surface
                 sad, best = ops.sad_search(st["org"][0], st["ref0"][0], st["me_blk"][s], self.me[s].size, s, s, 1,
-                                           dx0, dy0, nx, ny, sx, sy, cfg_mv, want_sad=False)
+                                           dx0, dy0, nx, ny, sx, sy, self.mvcost, want_sad=False)
             out["me_sad_%d_%d" % (s, nx)] = sad
             out["me_best_%d_%d" % (s, nx)] = best
 
@@ -531,13 +484,13 @@ class Workload:
 
         def frac():
             with T("frac/frac_refine_16x16"):
-                out["frac"] = ops.frac_refine(st["org"][0], st["ref0"][0], st["frac_blk"], self.frac.size, 16, 16, bd, fmv, True, (0, mx))
+                out["frac"] = ops.frac_refine(st["org"][0], st["ref0"][0], st["frac_blk"], self.frac.size, 16, 16, bd, self.frac_mvcost, True, (0, mx))
 
         if self.hier_me:
             # ---- me, hierarchical: ONE launch answers the six searches (InterSearch.cpp:2159-2169 raster, :1886-1935 +-4) on the main stream, alone;
             # the fractional refinement follows on a side stream
             with T("me/hier_search"):
-                rb, db = ops.me_hier_search(st["org"][0], st["ref0"][0], (0, 0), (MARGIN, MARGIN), self.w // 16, self.h // 16, 1, self.raster_range, 4, cfg_mv)
+                rb, db = ops.me_hier_search(st["org"][0], st["ref0"][0], (0, 0), (MARGIN, MARGIN), self.w // 16, self.h // 16, 1, self.raster_range, 4, self.mvcost)
             for k, s in enumerate((16, 32, 64)):
                 out["me_sad_%d_%d" % (s, raster[2])] = out["me_sad_%d_%d" % (s, dense[2])] = None
                 out["me_best_%d_%d" % (s, dense[2])] = db[k]
