@@ -43,7 +43,7 @@ int         vvcgpu_set_device(int device);
 /* sizeof() of the parameter structs, for binding self-checks: 0 sao_ctu, 1 deblock_cfg, 2 dist_desc, 3 search_blk,
  * 4 mvcost, 5 search_best, 6 if_desc, 7 mc_desc, 8 pelop_desc, 9 pelop_cfg, 10 tr_desc, 11 frac_blk, 12 frac_result,
  * 13 dqtr_desc, 14 afg_desc, 15 afe_desc, 16 tz_pu, 17 tz_cfg, 18 intra_desc, 19 cclm_desc, 20 intra_fill_desc, 21 imv_pu, 22 imv_result, 23 quant_desc,
- * 24 dq_rates, 25 depquant_desc, 26 rdoq_rates, 27 rdoq_desc, 28 intra_satd_desc, 29 affine_iter, 30 me_hier_cfg; -1 for unknown ids.          */
+ * 24 dq_rates, 25 depquant_desc, 26 rdoq_rates, 27 rdoq_desc, 28 intra_satd_desc, 29 affine_iter, 30 me_hier_cfg, 31 wp_param; -1 for unknown ids. */
 int         vvcgpu_sizeof(int struct_id);
 
 /* ---- device memory helpers for host-side callers (the reference keeps pictures in host memory; the shim stages them).
@@ -311,6 +311,27 @@ int vvcgpu_mc_picture_batch(const vvc_pel* ref0_base, const vvc_pel* ref1_base, 
  * vvcgpu_affine_me_iter_batch (w, h outside 1..128).  The descriptor array of vvcgpu_mc_batch / vvcgpu_mc_dist_batch is 16-byte aligned.       */
 int vvcgpu_mc_dist_batch(int kind, const vvc_pel* ref0_base, const vvc_pel* ref1_base, const vvc_pel* org_base, const vvcgpu_mc_desc* descs, int n,
                          int bit_depth, int clp_min, int clp_max, uint64_t* out, void* stream);
+/* Explicit weighted prediction of a slice's PUs (InterPrediction::xPredInterBi / motionCompensation, InterPrediction.cpp:418-477, 762-800, with
+ * WeightPrediction::addWeightUni / addWeightBi, WeightPrediction.cpp:46-60, 157-300): the prediction of vvcgpu_mc_picture_batch (ONE launch, the same
+ * matrix-core / generic split) with the weighted epilogue in place of rndRes / addAvg.  P = the 14-bit intermediate that bi = 2 stores
+ * ((src << headRoom) - 8192 at full-sample positions, not clipped); shiftNum = max(2, 14 - bit_depth), S = shift + shiftNum, clip to [clp_min, clp_max]:
+ *   bi = 0, w0 != 1 << shift   clip(((w0 (P0 + 8192) + (1 << (S - 1))) >> S) + offset)
+ *   bi = 0, w0 == 1 << shift   clip((((P0 + 8192) + (1 << (shiftNum - 1))) >> shiftNum) + offset)
+ *   bi = 1                     clip((w0 (P0 + 8192) + w1 (P1 + 8192) + (1 << (S - 1)) + (offset << (S - 1))) >> S)
+ * Descriptors as vvcgpu_mc_batch EXCEPT: bi = 0 is weighted uni-prediction from ref0 (a PU predicted from list 1 only is passed as ref0 with list 1's
+ * entry), bi = 1 weighted bi-prediction, and `reserved` is the index of the PU's entry in wp.  wp: device memory, 16-byte aligned, n_wp (1..32767)
+ * entries, typically built once per slice from its (refIdx pair, component) combinations.  Like the sentinel of vvcgpu_mc_dist_batch, a descriptor
+ * outside the contract is skipped and its dst left untouched: bi outside 0..1, reserved outside [0, n_wp), w or h outside 1..128, or an entry
+ * outside the range a WPScalingParam takes (|w0| <= 255, |w1| <= 255 for bi = 1, 0 <= shift <= 8, |offset| <= 2^(bit_depth + 1)).  n == 0 is a
+ * no-op; null pointers (ref1_base may be null for a list without bi = 1), n_wp outside 1..32767 and descriptor or table arrays that are not
+ * 16-byte aligned return VVCGPU_E_ARG, a bit depth outside 8..10 VVCGPU_E_UNSUPPORTED, before any device work. */
+typedef struct {                      /* WPScalingParam fields AFTER WeightPrediction::getWpScaling (WeightPrediction.cpp:77-156)       */
+  int32_t w0, w1;                     /* .w of list 0 / list 1 (w1 unused when bi == 0)                                                    */
+  int32_t offset;                     /* .offset: uni = iOffset * (1 << (bd - 8)); bi = o0 + o1                                            */
+  int32_t shift;                      /* .shift:  uni = log2WeightDenom;            bi = log2WeightDenom + 1;  sizeof == 16               */
+} vvcgpu_wp_param;
+int vvcgpu_mc_wp_batch(const vvc_pel* ref0_base, const vvc_pel* ref1_base, vvc_pel* dst_base, const vvcgpu_mc_desc* descs, int n,
+                       const vvcgpu_wp_param* wp, int n_wp, int bit_depth, int clp_min, int clp_max, void* stream);
 
 /* ---- B1-B4: PelBuffer element-wise operations, batched  (g_pelBufOP table, Buffer.h:57-73: addAvg4/8, reco4/8,
  *          linTf4/8; cores Buffer.cpp:50-94; plus AreaBuf::subtract Buffer.h:321-339, removeHighFreq :389-416,

@@ -94,6 +94,8 @@ MC_DESC = np.dtype([("ref0_off", "<i8"), ("ref1_off", "<i8"), ("dst_off", "<i8")
                     ("ref1_stride", "<i4"), ("dst_stride", "<i4"), ("w", "<i2"), ("h", "<i2"), ("frac_x0", "i1"),
                     ("frac_y0", "i1"), ("frac_x1", "i1"), ("frac_y1", "i1"), ("is_luma", "i1"), ("bi", "i1"),
                     ("reserved", "<i2")])
+# vvcgpu_wp_param: one entry of the weight table of vvcgpu_mc_wp_batch (WPScalingParam after WeightPrediction::getWpScaling)
+WP_PARAM = np.dtype([("w0", "<i4"), ("w1", "<i4"), ("offset", "<i4"), ("shift", "<i4")])
 PELOP_DESC = np.dtype([("src0_off", "<i8"), ("src1_off", "<i8"), ("dst_off", "<i8"), ("src0_stride", "<i4"),
                        ("src1_stride", "<i4"), ("dst_stride", "<i4"), ("w", "<i2"), ("h", "<i2")])
 

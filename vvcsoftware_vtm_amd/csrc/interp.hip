@@ -58,6 +58,42 @@ __device__ __forceinline__ int if_copy(int s, bool isFirst, bool isLast, int bd,
   return clip3(cmin, cmax, (short)((s + IF_INTERNAL_OFFS + (1 << (shift - 1))) >> shift));
 }
 
+// explicit weighted prediction (vvcgpu_mc_wp_batch): the epilogue that replaces rndRes / addAvg, on P = the 14-bit intermediate of xPredInterBlk with
+// rndRes = false (what bi = 2 stores).  WeightPrediction::addWeightBi / addWeightUni and their weightBidir / weightUnidir / noWeightUnidir cores
+// (WeightPrediction.cpp:46-60, 157-300).  Integer arithmetic throughout: |P + 8192| < 2^16 (P is a Pel), |w| <= 255, |offset| <= 2^11 and shift <= 8
+// keep every term and the bi sum below 2^31.  offset << (S - 1) of the reference is an arithmetic shift (gcc) also for a negative offset: a product here.
+__device__ __forceinline__ int wp_apply(int p0, int p1, bool bi, const vvcgpu_wp_param& e, int shiftNum, int cmin, int cmax)
+{
+  const int S = e.shift + shiftNum;
+  int v;
+  if (bi) v = (e.w0 * (p0 + IF_INTERNAL_OFFS) + e.w1 * (p1 + IF_INTERNAL_OFFS) + (1 << (S - 1)) + e.offset * (1 << (S - 1))) >> S;
+  else if (e.w0 != 1 << e.shift) v = ((e.w0 * (p0 + IF_INTERNAL_OFFS) + (1 << (S - 1))) >> S) + e.offset;
+  else v = ((p0 + IF_INTERNAL_OFFS + (1 << (shiftNum - 1))) >> shiftNum) + e.offset;
+  return clip3(cmin, cmax, v);
+}
+// the range a WPScalingParam can take after getWpScaling (log2WeightDenom <= 7, weights and offsets of the slice header scaled to the bit depth)
+// -- outside it the descriptor is skipped
+__device__ __forceinline__ bool wp_valid(const vvcgpu_wp_param& e, bool bi, int bd)
+{
+  return e.w0 >= -255 && e.w0 <= 255 && (!bi || (e.w1 >= -255 && e.w1 <= 255)) && e.shift >= 0 && e.shift <= 8 && e.offset >= -(2 << bd) && e.offset <= (2 << bd);
+}
+// a table entry as four scalars (the index is wave-uniform wherever this is called)
+__device__ __forceinline__ vvcgpu_wp_param wp_load(const vvcgpu_wp_param* __restrict__ wp, int i)
+{
+  const int4 q = *reinterpret_cast<const int4*>(wp + i);
+  vvcgpu_wp_param e;
+  e.w0 = q.x; e.w1 = q.y; e.offset = q.z; e.shift = q.w;
+  return e;
+}
+// a descriptor vvcgpu_mc_wp_batch skips, from bytes 32..47 (dst_stride | w, h | phases | is_luma, bi, reserved = table index): bi outside 0..1, index outside
+// [0, nWp), w or h outside 1..128, a table entry outside wp_valid
+__device__ __forceinline__ bool wp_skip(const uint4& q2, const vvcgpu_wp_param* __restrict__ wp, int nWp, int bd)
+{
+  const int w = (short)(q2.y & 0xFFFFu), h = (short)(q2.y >> 16), bi = (signed char)((q2.w >> 8) & 0xFFu), ix = (short)(q2.w >> 16);
+  if (bi < 0 || bi > 1 || ix < 0 || ix >= nWp || w < 1 || w > 128 || h < 1 || h > 128) return true;
+  return !wp_valid(wp_load(wp, ix), bi == 1, bd);
+}
+
 // ------------------------------------------------------------------------------------------------ I1
 // four samples of a row in ONE 8-byte access whatever the address (blocks start at any sample: 2-byte alignment).  gfx950 under HSA runs with
 // unaligned global access enabled and the compiler knows it: a load / store through a 2-byte-aligned type is one global_load / store_dwordx2.  (Until
@@ -341,9 +377,10 @@ __device__ __forceinline__ void mc_stage(const vvcgpu_mc_desc& d, bool active, c
   st.bad = bad;
 }
 
-template <int N, int S, int G>
+// WPF: the weighted epilogue (wp_apply) with entry e on the unrounded intermediates of both lists
+template <int N, int S, int G, bool WPF = false>
 __device__ __forceinline__ void mc_tile_dot2(const vvcgpu_mc_desc& d, bool active, const McStaged<N, S, G>& st, Pel* __restrict__ dstBase, int bd, int cmin, int cmax,
-                                             int gl, unsigned* win, short* tmpT, short* outL)
+                                             int gl, unsigned* win, short* tmpT, short* outL, const vvcgpu_wp_param* e = nullptr)
 {
   constexpr int half = N / 2 - 1, NR = S + N - 1, WD = McStaged<N, S, G>::WD;                              // dwords per window row (even: 8-byte reads)
   constexpr int TP = 2 * WD;                                             // tmpT pitch in samples
@@ -351,7 +388,7 @@ __device__ __forceinline__ void mc_tile_dot2(const vvcgpu_mc_desc& d, bool activ
   constexpr int HITEMS = NR * NG, VITEMS = S * NG, LOADS = NR * WD;
   if (!active) return;                                                    // (the wave barriers below only order this wave's own LDS accesses)
   const int hr = max(2, IF_INTERNAL_PREC - bd);
-  const bool rndRes = d.bi == 0;
+  const bool rndRes = WPF ? false : d.bi == 0;
   const int nRef = d.bi == 1 ? 2 : 1;
   const auto& ld = st.ld;
   const auto& phase = st.phase;
@@ -455,7 +492,8 @@ __device__ __forceinline__ void mc_tile_dot2(const vvcgpu_mc_desc& d, bool activ
     for (int j = 0; j < 4; j++)
     {
       int v = pred[0][j];
-      if (d.bi == 1) v = clip3(cmin, cmax, (pred[0][j] + pred[1][j] + offset) >> shiftNum);
+      if (WPF) v = wp_apply(pred[0][j], pred[1][j], d.bi == 1, *e, shiftNum - 1, cmin, cmax);
+      else if (d.bi == 1) v = clip3(cmin, cmax, (pred[0][j] + pred[1][j] + offset) >> shiftNum);
       outL[(4 * yg + j) * S + x] = (short)v;
     }
   }
@@ -569,6 +607,7 @@ struct MmK                                                   // lane constants o
   mm_h2 pmin, pmax, pmin0, pmaxF;                            // packed clip bounds (+ 1024): the caller's range; the bit depth's range (a uni-predictive full-sample copy is NOT clipped: filterCopy, isFirst == isLast)
   int perm;                                                  // ds_bpermute address: lane (row & 15) + 16 chunk <- lane 4 (row & 15) + chunk
   int* genCount;                                             // PUs left to the generic kernel behind this one (it leaves at once when there are none)
+  int cmin, cmax;                                            // the caller's clip range (the weighted tail: mm_tail_wp)
 };
 
 // pass-1 result registers -> limb operand (kind: 0 every row real; 1 luma rows 16..31; 2 chroma rows 0..15); hclip (per lane): the rounded horizontal-only
@@ -618,6 +657,18 @@ __device__ __forceinline__ uint2 mm_tail(const MmK& K, const float (&f0)[4], con
   uint2 o;
   o.x = __builtin_bit_cast(unsigned, q0) & 0x03FF03FFu;
   o.y = __builtin_bit_cast(unsigned, q1) & 0x03FF03FFu;
+  return o;
+}
+// the weighted tail (vvcgpu_mc_wp_batch): f0 / f1 are the unrounded intermediates of the two lists (exact f32 integers, |P| < 2^15: the conversion is exact),
+// wp_apply in integers -- the products w (P + 8192) of a bi sum may reach 2^24, beyond what an f32 sum keeps exact
+__device__ __forceinline__ uint2 mm_tail_wp(const MmK& K, const float (&f0)[4], const float (&f1)[4], bool bi, const vvcgpu_wp_param& e)
+{
+  int v[4];
+#pragma unroll
+  for (int j = 0; j < 4; j++) v[j] = wp_apply((int)f0[j], (int)f1[j], bi, e, K.hr, K.cmin, K.cmax);
+  uint2 o;
+  o.x = ((unsigned)v[0] & 0xFFFFu) | ((unsigned)v[1] << 16);
+  o.y = ((unsigned)v[2] & 0xFFFFu) | ((unsigned)v[3] << 16);
   return o;
 }
 struct __attribute__((packed, aligned(2))) MmQuad { uint2 v; };
@@ -674,11 +725,13 @@ __device__ __forceinline__ void mm_luma_win(const MmK& K, const MmRaw& raw, MmWi
       W.w[rf][ch] = __builtin_bit_cast(h8, u);
     }
 }
+// WPF: both lists unrounded (the bi form of the second stage), the weighted tail with entry e
+template <bool WPF = false>
 __device__ __forceinline__ void mm_luma(const MmK& K, const vvcgpu_mc_desc& d, const MmWin& W, const Pel* __restrict__ ref0Base, const Pel* __restrict__ ref1Base,
-                                        Pel* __restrict__ dstBase, int* __restrict__ flags, int idx)
+                                        Pel* __restrict__ dstBase, int* __restrict__ flags, int idx, const vvcgpu_wp_param* e = nullptr)
 {
   const int nRef = d.bi == 1 ? 2 : 1;
-  const bool hOnly = d.bi == 0 && d.frac_y0 == 0 && d.frac_x0 != 0;
+  const bool hOnly = !WPF && d.bi == 0 && d.frac_y0 == 0 && d.frac_x0 != 0;
   float fr[2][4] = { { 0.f, 0.f, 0.f, 0.f }, { 0.f, 0.f, 0.f, 0.f } };
 #pragma unroll
   for (int rf = 0; rf < 2; rf++)
@@ -699,14 +752,16 @@ __device__ __forceinline__ void mm_luma(const MmK& K, const vvcgpu_mc_desc& d, c
     f4 acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(p0, tb0, f4{ 0.f, 0.f, 0.f, 0.f }, 0, 0, 0);
     acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(p1, tb1, acc, 0, 0, 0);
     // second-stage rounding of this list: bi acc >> 6; uni (acc + offset) >> (6 + headroom); rounded horizontal-only: the pass-2 copy, acc / 64
-    const float sc = (d.bi == 1 || hOnly) ? K.scBi1 : K.scUni1, of = (d.bi == 1 || hOnly) ? 0.f : K.ofUni1;
+    const float sc = (WPF || d.bi == 1 || hOnly) ? K.scBi1 : K.scUni1, of = (WPF || d.bi == 1 || hOnly) ? 0.f : K.ofUni1;
 #pragma unroll
     for (int j = 0; j < 4; j++) fr[rf][j] = floorf(__builtin_fmaf(acc[j], sc, of));
   }
   const bool isBad = __ballot(W.bad != 0) != 0ull;           // a reference sample outside the bit depth: the generic kernel takes the PU
   if (K.lane == 0) { flags[idx] = isBad; if (isBad) atomicAdd(K.genCount, 1); }
   if (isBad) return;
-  const uint2 o = mm_tail(K, fr[0], fr[1], d.bi == 1 ? 1.f : 0.f, d.bi == 1 ? K.scBi2 : 1.f, d.bi == 1 ? K.ofBi2 : 1024.f, d.bi == 0 && (d.frac_x0 | d.frac_y0) == 0);
+  uint2 o;
+  if constexpr (WPF) o = mm_tail_wp(K, fr[0], fr[1], d.bi == 1, *e);
+  else o = mm_tail(K, fr[0], fr[1], d.bi == 1 ? 1.f : 0.f, d.bi == 1 ? K.scBi2 : 1.f, d.bi == 1 ? K.ofBi2 : 1024.f, d.bi == 0 && (d.frac_x0 | d.frac_y0) == 0);
   Pel* dp = dstBase + d.dst_off + (ptrdiff_t)K.c16 * d.dst_stride + 4 * K.g;                 // lane (c16, g): row c16, columns 4 g .. 4 g + 3
   reinterpret_cast<MmQuad*>(dp)->v = o;
 }
@@ -753,14 +808,17 @@ __device__ __forceinline__ void mm_chroma_win(const MmK& K, const MmRaw& raw, Mm
   W.w[1][0] = mm_window(K, raw.w[1][0], (K.g & 1) == 1, false, W.bad);
   W.dstLo = raw.dstLo; W.dstHi = raw.dstHi; W.ds = raw.ds; W.frac = raw.frac; W.flg = raw.flg;
 }
-__device__ __forceinline__ void mm_chroma(const MmK& K, const MmWin& raw, int iA, int iB, Pel* __restrict__ dstBase, int* __restrict__ flags)
+// WPF: as mm_luma; a lane's table entry is its OUTPUT PU's (the index rides in the high half of raw.flg), both entries read as scalars
+template <bool WPF = false>
+__device__ __forceinline__ void mm_chroma(const MmK& K, const MmWin& raw, int iA, int iB, Pel* __restrict__ dstBase, int* __restrict__ flags,
+                                          const vvcgpu_wp_param* __restrict__ wp = nullptr)
 {
   const bool hasB = iB >= 0;
   // the lane's OUTPUT PU (by c16 >> 3)
   const int bi = (int)(signed char)((raw.flg >> 8) & 0xFFu);
   const int fx0 = (int)(signed char)(raw.frac & 0xFFu) >> 2, fy0 = (int)(signed char)((raw.frac >> 8) & 0xFFu) >> 2;
   const int fx1 = (int)(signed char)((raw.frac >> 16) & 0xFFu) >> 2, fy1 = (int)(signed char)((raw.frac >> 24) & 0xFFu) >> 2;
-  const bool hOnly = bi == 0 && fy0 == 0 && fx0 != 0;
+  const bool hOnly = !WPF && bi == 0 && fy0 == 0 && fx0 != 0;
   const bool anyH = __ballot(hOnly) != 0ull;
   const int nRef = __ballot(bi == 1) != 0ull ? 2 : 1;
   const bool mineCols = (K.g >> 1) == (K.c16 >> 3) && (K.c16 < 8 || hasB);      // pass 1: this lane's table row is non-zero only in the k range of ITS PU
@@ -779,7 +837,7 @@ __device__ __forceinline__ void mm_chroma(const MmK& K, const MmWin& raw, int iA
     const float magic = hO ? K.magicH : K.magicN;
     const h8 p0 = anyH ? mm_limbs<true>(K, a0, magic, 2, hO) : mm_limbs<false>(K, a0, magic, 2, false);
     const f4 acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(p0, tb, f4{ 0.f, 0.f, 0.f, 0.f }, 0, 0, 0);
-    const float sc = (bi == 1 || hO) ? K.scBi1 : K.scUni1, of = (bi == 1 || hO) ? 0.f : K.ofUni1;
+    const float sc = (WPF || bi == 1 || hO) ? K.scBi1 : K.scUni1, of = (WPF || bi == 1 || hO) ? 0.f : K.ofUni1;
 #pragma unroll
     for (int j = 0; j < 4; j++) fr[rf][j] = floorf(__builtin_fmaf(acc[j], sc, of));
   }
@@ -788,7 +846,14 @@ __device__ __forceinline__ void mm_chroma(const MmK& K, const MmWin& raw, int iA
   // other PU's, whose table entries for it are zero (0 x NaN) -- both PUs of the pair go to the generic kernel
   const bool badA = badLanes != 0ull, badB = hasB && badLanes != 0ull;
   if (K.lane == 0) { flags[iA] = badA; if (hasB) flags[iB] = badB; if (badA) atomicAdd(K.genCount, 1 + (badB ? 1 : 0)); }
-  const uint2 o = mm_tail(K, fr[0], fr[1], bi == 1 ? 1.f : 0.f, bi == 1 ? K.scBi2 : 1.f, bi == 1 ? K.ofBi2 : 1024.f, bi == 0 && (fx0 | fy0) == 0);
+  uint2 o;
+  if constexpr (WPF)
+  {
+    const int ix = (int)(short)(raw.flg >> 16);                 // lane 0 writes PU A, lane 8 PU B (A again when there is none)
+    const vvcgpu_wp_param eA = wp_load(wp, __builtin_amdgcn_readlane(ix, 0)), eB = wp_load(wp, __builtin_amdgcn_readlane(ix, 8));
+    o = mm_tail_wp(K, fr[0], fr[1], bi == 1, K.c16 >= 8 ? eB : eA);
+  }
+  else o = mm_tail(K, fr[0], fr[1], bi == 1 ? 1.f : 0.f, bi == 1 ? K.scBi2 : 1.f, bi == 1 ? K.ofBi2 : 1024.f, bi == 0 && (fx0 | fy0) == 0);
   // lane (c16, g): row c16 & 7 of PU c16 >> 3, columns 4 (g & 1) ..; real when g >> 1 == c16 >> 3
   const bool outB = K.c16 >= 8;
   if ((K.g >> 1) == (K.c16 >> 3) && (outB ? (hasB && !badB) : !badA))
@@ -818,180 +883,44 @@ __device__ __forceinline__ int mm_kind_of(const uint4& q)   // bytes 32..47 of a
 // mc_batch_kernel behind this kernel cost 4.9 us per 4K picture for an empty list).  The second pass is a REAL call that takes everything it needs from
 // a record in LDS: values kept alive for it across the walks cost the walks' loops spilled registers (190 instead of 49 us).  Defined below mc_generic_pu.
 struct MmServe { const Pel* ref0Base; const Pel* ref1Base; Pel* dstBase; const vvcgpu_mc_desc* descs; const int* flags; int n, bd, cmin, cmax, w0, W, luma; };
-__device__ __forceinline__ void mm_second_pass(const MmServe* sv, short* gen, unsigned* genT);
+struct MmServeWp : MmServe { const vvcgpu_wp_param* wp; int nWp, allGen; };             // vvcgpu_mc_wp_batch: the weight table (mm_wp_kind)
+template <bool WPF> __device__ __forceinline__ void mm_second_pass(const MmServe* sv, short* gen, unsigned* genT);
 __device__ __noinline__ void mm_serve_one(const MmServe* sv, int li, short* gen, unsigned* genT);
+__device__ __noinline__ void mm_serve_one_wp(const MmServeWp* sv, int li, short* gen, unsigned* genT);
+// vvcgpu_mc_wp_batch: the kind of mm_kind_of / the stride check, MM_SKIP for a descriptor the call skips (wp_skip: neither a walk's shape, 1 / 2, nor the
+// generic body's, <= 0); allGen (VVCGPU_NO_MFMA): every PU to the generic body
+constexpr int MM_SKIP = 3;
+__device__ __forceinline__ int mm_wp_kind(int k, const uint4& q2, const vvcgpu_wp_param* __restrict__ wp, int nWp, int bd, int allGen)
+{
+  if (wp_skip(q2, wp, nWp, bd)) return MM_SKIP;
+  return allGen && k > 0 ? 0 : k;
+}
 constexpr int MM_GEN_SHORTS = 23 * 24 + 23 * 16;                               // WR x WP + WR x ST (declared below)
 
+// The matrix-core kernels (their body: mc_mfma_body.inc).  WPF (mc_mfma_wp_kernel, vvcgpu_mc_wp_batch): the same walks and passes with the weighted
+// epilogue; descriptors the call skips (mm_wp_kind MM_SKIP) are neither taken nor served.
 template <int KIND_T>
 __global__ __launch_bounds__(256, 4) void mc_mfma_kernel(const Pel* __restrict__ ref0Base, const Pel* __restrict__ ref1Base, Pel* __restrict__ dstBase,
                                                                          const vvcgpu_mc_desc* __restrict__ descs, int n, int bd, int cmin, int cmax,
                                                                          const _Float16* __restrict__ image, int* __restrict__ flags, unsigned long long* __restrict__ diag,
                                                                          int* __restrict__ genCount, int* __restrict__ nextCounters, int serve)
 {
-  if (blockIdx.x == 0 && threadIdx.x < VVC_CTR_INTS) nextCounters[threadIdx.x] = 0;       // the counter set of the NEXT call on this stream (vvcgpu_counters)
-  // KIND_T 0: ONE launch, workgroups alternate between the two shapes (both kinds of waves on every CU at the same time)
-  const int KIND = KIND_T ? KIND_T : 1 + ((int)blockIdx.x & 1);
-  const int T0 = KIND == 1 ? MM_TAL : MM_TAC, T1 = KIND == 1 ? MM_TAC : MM_ENTRIES;          // this kind's table entries
-  __shared__ __align__(16) _Float16 tabL[(KIND_T == 2 ? MM_ENTRIES - MM_TAC : MM_TAC - MM_TAL) * 8];
-  __shared__ __align__(16) short genS[4][MM_GEN_SHORTS];                     // the generic body's window / intermediate, per wave
-  __shared__ __align__(16) unsigned genT[4][MC_LDS_DW];                      // ... and its packed-form tile
-  __shared__ MmServe serveS;
-  __shared__ int anyGenS[4];                                 // serve: per wave, what its walk left to the generic body (the count lands here instead of in genCount)
-  for (int i = threadIdx.x; i < T1 - T0; i += 256) reinterpret_cast<uint4*>(tabL)[i] = reinterpret_cast<const uint4*>(image)[T0 + i];
-  if (threadIdx.x < 4) anyGenS[threadIdx.x] = 0;
-  MmK K;                                                     // (the barrier behind the table copy follows the lane constants and the serve record)
-  K.genCount = serve ? &anyGenS[threadIdx.x >> 6] : genCount;
-  K.tabS = tabL - T0 * 8;                                    // (indexed with the image's entry numbers)
-  K.lane = threadIdx.x & 63; K.c16 = K.lane & 15; K.g = K.lane >> 4;
-  const int g = K.g;
-  const int hr = max(2, IF_INTERNAL_PREC - bd), S = 1 << (IF_FILTER_PREC - hr);
-  K.hr = hr;
-  K.rangeMask = (unsigned)((1 << bd) - 1) * 0x10001u;
-  K.uLo = (unsigned)(16384 + cmin) * 0x10001u; K.uHi = (unsigned)(16384 + cmax) * 0x10001u;
-  // limb masks / exponent patterns of a pass-1 result by row-chunk kind: 0 every row real; 1 luma rows 16..31 (lane group 2: the constants 1.0, 1024.0;
-  // 3: nothing); 2 chroma rows 0..15 (lane group 3: the constants)
-  K.m7[0] = 0x007F007Fu; K.m8[0] = 0x00FF00FFu; K.orX[0] = 0x64006400u;
-  asm("" : "+v"(K.m7[0]), "+v"(K.m8[0]), "+v"(K.orX[0]));   // held in vector registers (v_and_or_b32 takes no literal)
-  K.orR[0] = K.orX[0];
-  K.m7[1] = g < 2 ? 0x007F007Fu : 0u; K.m8[1] = g < 2 ? 0x00FF00FFu : 0u; K.orX[1] = g < 2 ? 0x64006400u : g == 2 ? 0x64003C00u : 0u; K.orR[1] = g < 2 ? 0x64006400u : 0u;
-  K.m7[2] = g < 3 ? 0x007F007Fu : 0u; K.m8[2] = g < 3 ? 0x00FF00FFu : 0u; K.orX[2] = g < 3 ? 0x64006400u : 0x64003C00u; K.orR[2] = g < 3 ? 0x64006400u : 0u;
-  K.magicN = 8388608.f * (float)S; K.magicH = 536870912.f;
-  K.cinN = 8192.f * (float)S - 65536.f - 0.5f * (float)(S - 1); K.cinH = 983040.5f;     // start values of a luma pass-1 sum (the chroma tables carry theirs)
-  K.perm = (4 * K.c16 + K.g) * 4;
-  K.pmin = mm_h2{ (_Float16)(short)(1024 + cmin), (_Float16)(short)(1024 + cmin) }; K.pmax = mm_h2{ (_Float16)(short)(1024 + cmax), (_Float16)(short)(1024 + cmax) };
-  K.pmin0 = mm_h2{ (_Float16)1024.f, (_Float16)1024.f }; K.pmaxF = mm_h2{ (_Float16)(short)(1023 + (1 << bd)), (_Float16)(short)(1023 + (1 << bd)) };
-  // second-stage rounding as fma + floor (exact: f32 integers below 2^24 times powers of two)
-  K.scBi1 = 1.f / 64.f; K.scUni1 = 1.f / (float)(64 << hr); K.ofUni1 = (float)((1 << (5 + hr)) + (IF_INTERNAL_OFFS << 6)) * K.scUni1;
-  K.scBi2 = 1.f / (float)(2 << hr); K.ofBi2 = (float)((1 << hr) + 2 * IF_INTERNAL_OFFS) * K.scBi2 + 1024.f;
-
-  const int nb = KIND_T ? (int)gridDim.x : (KIND == 1 ? ((int)gridDim.x + 1) >> 1 : (int)gridDim.x >> 1), bi_ = KIND_T ? (int)blockIdx.x : (int)blockIdx.x >> 1;
-  // XCD-aware walk (workgroups are dealt round-robin over the 8 XCDs, each with its own L2): at every step the waves of ONE XCD hold one contiguous
-  // run of W / 8 descriptors, so the window lines that neighbouring PUs share are fetched from the fabric by one L2 (speed only)
-  const int W = nb * 4, perX = W >> 3;
-  const int w = (nb & 7) ? bi_ * 4 + __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6)
-                         : (bi_ & 7) * perX + (bi_ >> 3) * 4 + __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
-  if (serve && threadIdx.x == 0) serveS = MmServe{ ref0Base, ref1Base, dstBase, descs, flags, n, bd, cmin, cmax, w, W, KIND == 1 ? 1 : 0 };     // (w of wave 0; read behind the walks)
-  __syncthreads();
-  // The wave's descriptors w + j W are classified 64 at a time, one per LANE (one gather load and a ballot; a descriptor-by-descriptor walk on the scalar
-  // unit -- one per CU, shared by its 20 waves -- bound the kernel: 400 scalar instructions per PU); the walk over the set bits is a few scalar operations.
-  // Three steps are in flight (in-kernel stamps, VVCGPU_MC_DIAG: with the descriptor read inside the step that requests the samples, 1400 of a step's
-  // 5500 cycles were that read's latency): the descriptor of step k + 2 is being read, the samples of step k + 1 are requested, step k is computed.
-  MmRaw raw;
-  bool pend = false;
-  if (KIND == 1)
-  {
-    vvcgpu_mc_desc dP = descs[0];
-    int iP = 0, dstep = 0;
-    for (int j0 = 0; w + (long long)j0 * W < n; j0 += 64)
-    {
-      const long long iL = w + (long long)(j0 + K.lane) * W;
-      int k = 0;
-      if (iL < n)
-      {
-        const uint4 q1 = reinterpret_cast<const uint4*>(descs + iL)[1], q2 = reinterpret_cast<const uint4*>(descs + iL)[2];
-        k = mm_kind_of(q2);
-        const int bi = (int)(signed char)((q2.w >> 8) & 0xFFu);
-        if (k == 1 && ((q1.z | (bi == 1 ? q1.w : 0u)) & 7u)) k = -1;           // aligned 16-byte words need rows that keep their alignment (ref strides: bytes 24..31)
-        if (k < 0) flags[iL] = 1;                            // a fast SHAPE these kernels do not take: the generic kernel's
-      }
-      {
-        const unsigned long long gm = __ballot(iL < n && k <= 0);             // every other shape, and the fast shapes left above: the generic kernel's work
-        if (gm != 0ull && K.lane == 0) atomicAdd(K.genCount, (int)__popcll(gm));
-      }
-      unsigned long long mine = __ballot(k == 1);
-      auto nextIdx = [&]() -> int { if (mine == 0ull) return -1; const int j = (int)__builtin_ctzll(mine); mine &= mine - 1ull; return w + (j0 + j) * W; };
-      // A step's descriptor is wave-uniform, but it is read with VECTOR loads (every lane the same address) a step ahead and moved to scalar registers
-      // when its step begins: scalar loads return out of order, so with one in flight every LDS wait of the step (operand permutes, table reads) is an
-      // lgkmcnt(0) that also waits for the descriptor -- ~2000 of a step's 5000 cycles (VVCGPU_MC_DIAG stamps).
-      auto descLoad = [&](int i, uint4 (&v)[3]) { const uint4* q = reinterpret_cast<const uint4*>(descs + i); v[0] = q[0]; v[1] = q[1]; v[2] = q[2]; };
-      auto descScalar = [&](const uint4 (&v)[3]) -> vvcgpu_mc_desc
-      {
-        unsigned u[12] = { v[0].x, v[0].y, v[0].z, v[0].w, v[1].x, v[1].y, v[1].z, v[1].w, v[2].x, v[2].y, v[2].z, v[2].w };
-#pragma unroll
-        for (int t = 0; t < 12; t++) u[t] = (unsigned)__builtin_amdgcn_readfirstlane((int)u[t]);
-        vvcgpu_mc_desc d;
-        d.ref0_off = (long long)(((unsigned long long)u[1] << 32) | u[0]); d.ref1_off = (long long)(((unsigned long long)u[3] << 32) | u[2]);
-        d.dst_off = (long long)(((unsigned long long)u[5] << 32) | u[4]);
-        d.ref0_stride = (int)u[6]; d.ref1_stride = (int)u[7]; d.dst_stride = (int)u[8];
-        d.w = (short)(u[9] & 0xFFFFu); d.h = (short)(u[9] >> 16);
-        d.frac_x0 = (signed char)(u[10] & 0xFFu); d.frac_y0 = (signed char)((u[10] >> 8) & 0xFFu); d.frac_x1 = (signed char)((u[10] >> 16) & 0xFFu); d.frac_y1 = (signed char)(u[10] >> 24);
-        d.is_luma = (signed char)(u[11] & 0xFFu); d.bi = (signed char)((u[11] >> 8) & 0xFFu); d.reserved = 0;
-        return d;
-      };
-      int iA = nextIdx();
-      if (iA < 0) continue;
-      uint4 dv[3];
-      descLoad(iA, dv);
-      while (iA >= 0)
-      {
-        const vvcgpu_mc_desc dA = descScalar(dv);
-        const int iB = nextIdx();
-        descLoad(iB >= 0 ? iB : iA, dv);                     // the next step's descriptor: a whole step ahead
-        if (pend)
-        {
-          // VVCGPU_MC_DIAG (measurement aid): core-clock stamps of one wave's steps: step start, samples arrived + operands, next samples requested, done
-          const bool st = diag && bi_ == (nb >> 1) && (threadIdx.x >> 6) == 0 && dstep < 12;
-          if (st && K.lane == 0) diag[dstep * 4 + 0] = __builtin_amdgcn_s_memtime();
-          MmWin Wn;
-          mm_luma_win(K, raw, Wn);                           // the previous PU's samples have arrived: operands; the loaded registers are free
-          if (st && K.lane == 0) { asm volatile("" :: "v"(Wn.w[0][0]), "v"(Wn.w[1][1])); diag[dstep * 4 + 1] = __builtin_amdgcn_s_memtime(); }
-          mm_fetch_luma(K, dA, ref0Base, ref1Base, raw);     // this PU's samples travel behind the previous PU's products
-          if (st && K.lane == 0) diag[dstep * 4 + 2] = __builtin_amdgcn_s_memtime();
-          mm_luma(K, dP, Wn, ref0Base, ref1Base, dstBase, flags, iP);
-          if (st && K.lane == 0) diag[dstep * 4 + 3] = __builtin_amdgcn_s_memtime();
-          dstep++;
-        }
-        else mm_fetch_luma(K, dA, ref0Base, ref1Base, raw);
-        dP = dA; iP = iA; pend = true;
-        iA = iB;
-      }
-    }
-    if (pend) { MmWin Wn; mm_luma_win(K, raw, Wn); mm_luma(K, dP, Wn, ref0Base, ref1Base, dstBase, flags, iP); }
-    if (serve && anyGenS[(int)threadIdx.x >> 6] != 0) mm_second_pass(&serveS, genS[(int)threadIdx.x >> 6], genT[(int)threadIdx.x >> 6]);
-  }
-  else
-  {
-    const int units = (n + 1) >> 1;
-    int iAP = -1, iBP = -1;
-    for (int j0 = 0; w + (long long)j0 * W < units; j0 += 64)
-    {
-      const long long uL = w + (long long)(j0 + K.lane) * W;
-      int iAv = -1, iBv = -1;
-      if (uL < units)
-      {
-        const int k0 = mm_kind_of(reinterpret_cast<const uint4*>(descs + 2 * uL)[2]);
-        const int k1 = 2 * uL + 1 < n ? mm_kind_of(reinterpret_cast<const uint4*>(descs + 2 * uL + 1)[2]) : 0;
-        iAv = k0 == 2 ? (int)(2 * uL) : k1 == 2 ? (int)(2 * uL + 1) : -1;
-        iBv = (k0 == 2 && k1 == 2) ? (int)(2 * uL + 1) : -1;
-      }
-      unsigned long long mine = __ballot(iAv >= 0);
-      auto nextJ = [&]() -> int { if (mine == 0ull) return -1; const int j = (int)__builtin_ctzll(mine); mine &= mine - 1ull; return j; };
-      int jA = nextJ();
-      if (jA < 0) continue;
-      int iA = __builtin_amdgcn_readlane(iAv, jA), iB = __builtin_amdgcn_readlane(iBv, jA);
-      MmCDesc cA;
-      mm_chroma_desc(K, descs, iA, iB, cA);
-      while (jA >= 0)
-      {
-        const int jN = nextJ();
-        const int iAN = __builtin_amdgcn_readlane(iAv, jN >= 0 ? jN : jA), iBN = __builtin_amdgcn_readlane(iBv, jN >= 0 ? jN : jA);
-        MmCDesc cN;
-        mm_chroma_desc(K, descs, iAN, iBN, cN);              // the descriptor fields of the step after this one (vector loads, consumed next iteration)
-        if (pend)
-        {
-          MmWin Wn;
-          mm_chroma_win(K, raw, Wn);
-          mm_fetch_chroma(K, cA, ref0Base, ref1Base, raw);
-          mm_chroma(K, Wn, iAP, iBP, dstBase, flags);
-        }
-        else mm_fetch_chroma(K, cA, ref0Base, ref1Base, raw);
-        iAP = iA; iBP = iB; pend = true;
-        jA = jN; iA = iAN; iB = iBN; cA = cN;
-      }
-    }
-    if (pend) { MmWin Wn; mm_chroma_win(K, raw, Wn); mm_chroma(K, Wn, iAP, iBP, dstBase, flags); }
-    if (serve && anyGenS[(int)threadIdx.x >> 6] != 0) mm_second_pass(&serveS, genS[(int)threadIdx.x >> 6], genT[(int)threadIdx.x >> 6]);
-  }
+  constexpr bool WPF = false;
+  const vvcgpu_wp_param* const wp = nullptr;
+  const int nWp = 0, allGen = 0;
+#include "mc_mfma_body.inc"
+}
+// vvcgpu_mc_wp_batch: ONE launch, the picture form (both shapes, the generic body served behind the walks) with the weighted epilogue
+__global__ __launch_bounds__(256, 4) void mc_mfma_wp_kernel(const Pel* __restrict__ ref0Base, const Pel* __restrict__ ref1Base, Pel* __restrict__ dstBase,
+                                                            const vvcgpu_mc_desc* __restrict__ descs, int n, int bd, int cmin, int cmax,
+                                                            const _Float16* __restrict__ image, int* __restrict__ flags, int* __restrict__ nextCounters,
+                                                            const vvcgpu_wp_param* __restrict__ wp, int nWp, int allGen)
+{
+  constexpr bool WPF = true;
+  constexpr int KIND_T = 0, serve = 1;
+  unsigned long long* const diag = nullptr;
+  int* const genCount = nullptr;
+#include "mc_mfma_body.inc"
 }
 
 // the table image of mc_mfma_kernel per device and bit depth
@@ -1053,11 +982,13 @@ __device__ __forceinline__ unsigned long long mc_luma4x4_chunk(unsigned long lon
 
 // One PU through the generic body: tiles of the packed form where the PU is a grid of them, else (or when a sample leaves the bit depth) sample by sample.
 // ONE wave; win / tmp / tileL: that wave's LDS (WR x WP, WR x ST shorts, MC_LDS_DW dwords); DIST: the prediction goes to predT (pitch d.w) instead of dst.
-// TAG separates the copies by caller: a function that is not inlined takes the loosest register budget of the kernels that call it.
+// TAG separates the copies by caller: a function that is not inlined takes the loosest register budget of the kernels that call it.  WPF: the weighted
+// epilogue with entry e (vvcgpu_mc_wp_batch): both lists unrounded, then wp_apply.
 #define MC_WAVE_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup"); } while (0)
-template <bool DIST, int TAG>
+template <bool DIST, int TAG, bool WPF = false>
 __device__ __forceinline__ void mc_generic_pu(const vvcgpu_mc_desc& d, const Pel* __restrict__ ref0Base, const Pel* __restrict__ ref1Base, Pel* __restrict__ dstBase,
-                                              int bd, int cmin, int cmax, int lane, short* win, short* tmp, unsigned* tileL, short* predT)
+                                              int bd, int cmin, int cmax, int lane, short* win, short* tmp, unsigned* tileL, short* predT,
+                                              const vvcgpu_wp_param* e = nullptr)
 {
   // descriptors live in device memory, the host cannot validate them: a shape outside the contract (the prediction tile of the fused form is
   // 128 x 128, bi is 0 or 1 there) is skipped with the sentinel ~0 as its distortion instead of overrunning LDS (wave-uniform)
@@ -1079,7 +1010,7 @@ __device__ __forceinline__ void mc_generic_pu(const vvcgpu_mc_desc& d, const Pel
         McStaged<8, 16, 64> st;
         mc_stage<8, 16, 64>(q, true, ref0Base, ref1Base, lane, st, bd);
         if (__builtin_amdgcn_ballot_w64(st.bad != 0u) != 0ull) { outsideDepth = true; break; }
-        mc_tile_dot2<8, 16, 64>(q, true, st, dstBase, bd, cmin, cmax, lane, L, reinterpret_cast<short*>(L + 23 * 12), reinterpret_cast<short*>(L + 23 * 12 + 16 * 12));
+        mc_tile_dot2<8, 16, 64, WPF>(q, true, st, dstBase, bd, cmin, cmax, lane, L, reinterpret_cast<short*>(L + 23 * 12), reinterpret_cast<short*>(L + 23 * 12 + 16 * 12), e);
       }
     }
     else
@@ -1093,13 +1024,13 @@ __device__ __forceinline__ void mc_generic_pu(const vvcgpu_mc_desc& d, const Pel
         McStaged<4, 8, 32> st;
         mc_stage<4, 8, 32>(q, on, ref0Base, ref1Base, lane & 31, st, bd);
         if (__builtin_amdgcn_ballot_w64(st.bad != 0u) != 0ull) { outsideDepth = true; break; }
-        mc_tile_dot2<4, 8, 32>(q, on, st, dstBase, bd, cmin, cmax, lane & 31, Lh, reinterpret_cast<short*>(Lh + 11 * 6), reinterpret_cast<short*>(Lh + 11 * 6 + 8 * 6));
+        mc_tile_dot2<4, 8, 32, WPF>(q, on, st, dstBase, bd, cmin, cmax, lane & 31, Lh, reinterpret_cast<short*>(Lh + 11 * 6), reinterpret_cast<short*>(Lh + 11 * 6 + 8 * 6), e);
       }
     }
     if (!outsideDepth) return;
   }
   const int N = d.is_luma ? 8 : 4, half = N / 2 - 1;
-  const bool rndRes = d.bi == 0;
+  const bool rndRes = WPF ? false : d.bi == 0;
   const int nRef = d.bi == 1 ? 2 : 1;
 
   for (int sy = 0; sy < d.h; sy += ST)
@@ -1108,6 +1039,7 @@ __device__ __forceinline__ void mc_generic_pu(const vvcgpu_mc_desc& d, const Pel
       const int tw = min(ST, d.w - sx), th = min(ST, d.h - sy);
       const int npx = tw * th;
       int pred[2][4];
+      if (WPF) { pred[1][0] = pred[1][1] = pred[1][2] = pred[1][3] = 0; }      // (uni: the second list's operand of wp_apply is not read)
 #pragma unroll
       for (int r = 0; r < 2; r++)
       {
@@ -1190,7 +1122,8 @@ __device__ __forceinline__ void mc_generic_pu(const vvcgpu_mc_desc& d, const Pel
         {
           const int y = p / tw, x = p - y * tw;
           int v = pred[0][j];
-          if (d.bi == 1) v = clip3(cmin, cmax, (pred[0][j] + pred[1][j] + offset) >> shiftNum);
+          if (WPF) v = wp_apply(pred[0][j], pred[1][j], d.bi == 1, *e, shiftNum - 1, cmin, cmax);
+          else if (d.bi == 1) v = clip3(cmin, cmax, (pred[0][j] + pred[1][j] + offset) >> shiftNum);
           dst[(size_t)y * dstStride + x] = (short)v;
         }
       }
@@ -1206,6 +1139,15 @@ __device__ __noinline__ void mm_serve_one(const MmServe* sv, int li, short* gen,
   const vvcgpu_mc_desc d = S.descs[li];
   mc_generic_pu<false, 1>(d, S.ref0Base, S.ref1Base, S.dstBase, S.bd, S.cmin, S.cmax, (int)threadIdx.x & 63, gen, gen + WR * WP, genT, nullptr);
 }
+__device__ __noinline__ void mm_serve_one_wp(const MmServeWp* sv, int li, short* gen, unsigned* genT)
+{
+  const MmServeWp S = *sv;
+  const vvcgpu_mc_desc d = S.descs[li];
+  const vvcgpu_wp_param e = wp_load(S.wp, d.reserved);
+  mc_generic_pu<false, 2, true>(d, S.ref0Base, S.ref1Base, S.dstBase, S.bd, S.cmin, S.cmax, (int)threadIdx.x & 63, gen, gen + WR * WP, genT, nullptr,
+                                &e);
+}
+template <bool WPF>
 __device__ __forceinline__ void mm_second_pass(const MmServe* sv, short* gen, unsigned* genT)
 {
   // flags[] was written by this wave in its walk: its stores are complete behind the wait (vector stores write through to the L2), and the loads below are
@@ -1214,7 +1156,8 @@ __device__ __forceinline__ void mm_second_pass(const MmServe* sv, short* gen, un
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
   const MmServe S = *sv;
   const int lane = (int)threadIdx.x & 63, w = S.w0 + ((int)threadIdx.x >> 6);
-  auto serve = [&](int li) { mm_serve_one(sv, li, gen, genT); };
+  const MmServeWp* svW = static_cast<const MmServeWp*>(sv);            // (WPF only)
+  auto serve = [&](int li) { if constexpr (WPF) mm_serve_one_wp(svW, li, gen, genT); else mm_serve_one(sv, li, gen, genT); };
   if (S.luma)
   {
     // what this wave's descriptors leave to the generic body: every shape that is not a fast one (luma or chroma), the fast shapes the walk rejected
@@ -1229,6 +1172,7 @@ __device__ __forceinline__ void mm_second_pass(const MmServe* sv, short* gen, un
         int k = mm_kind_of(q2);
         const int bi = (int)(signed char)((q2.w >> 8) & 0xFFu);
         if (k == 1 && ((q1.z | (bi == 1 ? q1.w : 0u)) & 7u)) k = -1;
+        if constexpr (WPF) k = mm_wp_kind(k, q2, svW->wp, svW->nWp, S.bd, svW->allGen);
         gen1 = k <= 0 || (k == 1 && __hip_atomic_load(S.flags + iL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0);
       }
       unsigned long long todo = __ballot(gen1);
@@ -1250,8 +1194,10 @@ __device__ __forceinline__ void mm_second_pass(const MmServe* sv, short* gen, un
       int g0 = -1, g1 = -1;
       if (uL < units)
       {
-        const int k0 = mm_kind_of(reinterpret_cast<const uint4*>(S.descs + 2 * uL)[2]);
-        const int k1 = 2 * uL + 1 < S.n ? mm_kind_of(reinterpret_cast<const uint4*>(S.descs + 2 * uL + 1)[2]) : 0;
+        const uint4* q0 = reinterpret_cast<const uint4*>(S.descs + 2 * uL) + 2;
+        const int k0 = WPF ? mm_wp_kind(mm_kind_of(*q0), *q0, svW->wp, svW->nWp, S.bd, svW->allGen) : mm_kind_of(reinterpret_cast<const uint4*>(S.descs + 2 * uL)[2]);
+        const int k1 = 2 * uL + 1 < S.n ? (WPF ? mm_wp_kind(mm_kind_of(q0[3]), q0[3], svW->wp, svW->nWp, S.bd, svW->allGen)
+                                                : mm_kind_of(reinterpret_cast<const uint4*>(S.descs + 2 * uL + 1)[2])) : 0;
         if (k0 == 2 && __hip_atomic_load(S.flags + 2 * uL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) g0 = (int)(2 * uL);
         if (k1 == 2 && __hip_atomic_load(S.flags + 2 * uL + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) g1 = (int)(2 * uL + 1);
       }
@@ -1517,6 +1463,32 @@ int vvcgpu_mc_picture_batch(const vvc_pel* ref0_base, const vvc_pel* ref1_base, 
 {
   VvcScratch sc((hipStream_t)stream);
   return vvcgpu_mc_batch_impl(ref0_base, ref1_base, dst_base, descs, n, bit_depth, clp_min, clp_max, stream, sc, false, false, true);
+}
+// explicit weighted prediction: the launch of vvcgpu_mc_picture_batch with the weighted epilogue (mc_mfma_wp_kernel); reserved = index into wp
+int vvcgpu_mc_wp_batch(const vvc_pel* ref0_base, const vvc_pel* ref1_base, vvc_pel* dst_base, const vvcgpu_mc_desc* descs, int n,
+                       const vvcgpu_wp_param* wp, int n_wp, int bit_depth, int clp_min, int clp_max, void* stream)
+{
+  VVC_CHECK_ARG(n >= 0, "mc_wp_batch: n %d", n);
+  if (n == 0) return VVCGPU_OK;
+  VVC_CHECK_ARG(ref0_base && dst_base && descs && wp, "mc_wp_batch: null pointer");
+  VVC_CHECK_ARG(n_wp >= 1 && n_wp <= 32767, "mc_wp_batch: n_wp %d outside 1..32767", n_wp);
+  VVC_CHECK_ARG(((uintptr_t)descs & 15) == 0, "mc_wp_batch: descriptor array must be 16-byte aligned");
+  VVC_CHECK_ARG(((uintptr_t)wp & 15) == 0, "mc_wp_batch: weight table must be 16-byte aligned");
+  if (bit_depth > 10 || bit_depth < 8) { vvcgpu_set_error("mc_wp_batch: bit depth %d outside 8..10", bit_depth); return VVCGPU_E_UNSUPPORTED; }
+  hipStream_t st = (hipStream_t)stream;
+  const _Float16* image = mm_image(bit_depth);
+  if (!image) return VVCGPU_E_DEVICE;
+  VvcScratch sc(st);
+  int* fl = sc.take<int>(n);
+  if (!fl) return VVCGPU_E_DEVICE;
+  int cur = 0;
+  int* counters = vvcgpu_counters(st, &cur);
+  if (!counters) return VVCGPU_E_DEVICE;
+  const int wgL = cdiv(n, 4) < 256 * 4 ? cdiv(n, 4) : 256 * 4;           // as vvcgpu_mc_batch_impl: persistent, four workgroups per CU, an even count
+  hipLaunchKernelGGL(mc_mfma_wp_kernel, dim3(wgL < 2 ? 2 : (wgL & ~1)), dim3(256), 0, st, ref0_base, ref1_base ? ref1_base : ref0_base, dst_base, descs, n,
+                     bit_depth, clp_min, clp_max, image, fl, counters + VVC_CTR_INTS * (cur ^ 1), wp, n_wp, vvcgpu_no_mfma());
+  VVC_LAUNCH_CHECK_COUNTERS(st);
+  return VVCGPU_OK;
 }
 
 }  // extern "C"

@@ -291,6 +291,7 @@ int vvcgpu_sizeof(int id)
   case 28: return (int)sizeof(vvcgpu_intra_satd_desc);
   case 29: return (int)sizeof(vvcgpu_affine_iter);
   case 30: return (int)sizeof(vvcgpu_me_hier_cfg);
+  case 31: return (int)sizeof(vvcgpu_wp_param);
   default: return -1;
   }
 }

@@ -11,7 +11,7 @@ from . import capi
 from .abi import (AFE_DESC, AFFINE_ITER, AFFINE_PU, AFG_DESC, CCLM_DESC, DEPQUANT_DESC, DIST_DESC, DQ_RATES, DQTR_DESC, FRAC_BLK,  # noqa: F401
                   FRAC_RESULT, IF_DESC, IMV_PU, IMV_RESULT, INTRA_DESC, INTRA_FILL_DESC, INTRA_SATD_DESC, MC_DESC, PELOP_DESC, QUANT_DESC, RC_DESC,
                   RDOQ_DESC, RDOQ_RATES, RDPCM_DESC, SAO_DTYPE, SEARCH_BEST, SEARCH_BLK, TR_DESC, TZ_CFG, TZ_PU, DeblockCfg, MeHierCfg, MvCost,
-                  PelopCfg, Planes)
+                  PelopCfg, Planes, WP_PARAM)
 
 
 def _stream():
@@ -296,6 +296,23 @@ def mc_picture_batch(ref0_base, ref1_base, dst_base, descs_dev, n, bit_depth=10,
     """mc_batch for a picture's list of (mostly) 16x16 luma / 8x8 chroma PUs: one launch (vvcgpu_mc_picture_batch)"""
     capi.call("vvcgpu_mc_picture_batch", capi.ptr(ref0_base), capi.ptr(ref1_base), capi.ptr(dst_base), capi.ptr(descs_dev), n,
               bit_depth, clp[0], clp[1], _stream())
+
+
+def mc_wp_batch(ref0_base, ref1_base, dst_base, descs_dev, n, wp_dev, n_wp, bit_depth=10, clp=(0, 1023)):
+    """explicit weighted prediction of a picture's PUs (vvcgpu_mc_wp_batch): descriptors as mc_picture_batch, bi = 0 weighted uni- / 1 weighted
+    bi-prediction, reserved = index into wp_dev (a device copy of a WP_PARAM array with n_wp entries, see wp_param)"""
+    capi.call("vvcgpu_mc_wp_batch", capi.ptr(ref0_base), capi.ptr(ref1_base), capi.ptr(dst_base), capi.ptr(descs_dev), n, capi.ptr(wp_dev), n_wp,
+              bit_depth, clp[0], clp[1], _stream())
+
+
+def wp_param(bit_depth, log2_denom, weight0, offset0, weight1=None, offset1=None, high_precision_offsets=False):
+    """one WP_PARAM record (w0, w1, offset, shift) from the slice header's values of ONE component, as WeightPrediction::getWpScaling derives it
+    (WeightPrediction.cpp:77-156): uni-prediction when weight1 is None (a list-1-only PU passes list 1's values as weight0 / offset0), else
+    bi-prediction.  Offsets are scaled to the bit depth unless the range extension's high-precision offsets are on."""
+    sc = 1 if high_precision_offsets else 1 << (bit_depth - 8)
+    if weight1 is None:
+        return (weight0, 0, offset0 * sc, log2_denom)
+    return (weight0, weight1, offset0 * sc + offset1 * sc, log2_denom + 1)
 
 
 def mc_dist_batch(kind, ref0_base, ref1_base, org_base, descs_dev, n, bit_depth=10, clp=(0, 1023)):
