@@ -93,7 +93,8 @@ int vvcgpu_alf_classify(const vvc_pel* src, int src_stride, int width, int heigh
  * coeff_host: luma: 25 classes x 13 int16 (m_coeffFinal layout, MAX_NUM_ALF_LUMA_COEFF = 13);
  *             chroma: 7 int16.
  * ctu_enable: device array, one byte per CTU in raster order (Picture::getAlfCtuEnableFlag); CTUs with 0
- *             are left untouched in dst.  NULL = all enabled.
+ *             receive the unfiltered src samples, so dst is a complete picture (the reference's dst already
+ *             holds them).  NULL = all enabled.
  * For chroma pass the chroma plane, its width/height and ctu_size = luma CTU size >> 1.          */
 int vvcgpu_alf_filter_luma(const vvc_pel* src, int src_stride, vvc_pel* dst, int dst_stride,
                            int width, int height, int ctu_size, const uint16_t* cls,

@@ -49,6 +49,45 @@ def sao_params(rng, w, h, cw, ch, full_avail=True, types=None):
     return prm
 
 
+# offsets at the edges of the strip form's packed ranges (6-bit EO table, 16-bit sample pairs) and at the int16 extremes
+SAO_EDGE_OFFSETS = np.array([-32768, -32767, -33, -32, -31, 30, 31, 32, 32766, 32767], np.int16)
+
+
+def sao_picture_params(rng, w, h, ctu, mode, full_avail=False):
+    """vvcgpu_sao_ctu arrays of the three planes of a 4:2:0 picture (luma w x h, luma CTU ctu).  mode:
+      'type<t>'  every CTU of type t (-1..4), offsets drawn per CTU in -31..31 (all 32 entries: BO with every band random)
+      'band4'    BO as a decoder binding builds it: four consecutive bands (modulo 32) from a random start, zeros elsewhere
+      'mixed'    random types, a quarter of the CTUs with offsets outside the packed EO range
+      'edge_eo' / 'edge_bo'   EO / BO types with every offset drawn from SAO_EDGE_OFFSETS"""
+    out = []
+    for c in range(3):
+        pw, ph, cs = (w, h, ctu) if c == 0 else (w // 2, h // 2, ctu // 2)
+        if mode.startswith("type"):
+            prm = sao_params(rng, pw, ph, cs, cs, full_avail, types=[int(mode[4:])])
+        elif mode == "band4":
+            prm = sao_params(rng, pw, ph, cs, cs, full_avail, types=[4])
+            prm["offset"] = 0
+            for r in prm:
+                r["offset"][(int(rng.integers(0, 32)) + np.arange(4)) % 32] = rng.integers(-31, 32, 4)
+        elif mode == "mixed":
+            prm = sao_params(rng, pw, ph, cs, cs, full_avail, types=[-1, 0, 1, 2, 3, 4])
+            big = rng.random(prm.size) < 0.25
+            prm["offset"][big] = rng.integers(-300, 301, (int(big.sum()), 32))
+        elif mode in ("edge_eo", "edge_bo"):
+            prm = sao_params(rng, pw, ph, cs, cs, full_avail, types=[0, 1, 2, 3] if mode == "edge_eo" else [4])
+            prm["offset"] = rng.choice(SAO_EDGE_OFFSETS, prm["offset"].shape)
+        else:
+            raise ValueError(mode)
+        out.append(prm)
+    return out
+
+
+def ctu_enables(rng, w, h, ctu, p=0.6):
+    """one random ALF enable byte per CTU (raster order)"""
+    nx, ny = n_ctus(w, h, ctu)
+    return (rng.random(nx * ny) < p).astype(np.uint8)
+
+
 def deblock_maps(rng, w, h, mode="cu"):
     """Edge/BS/QP maps per 4x4 luma unit (see include/vvcgpu.h).  mode 'cu': a seeded quadtree CU grid with
     intra/inter blocks and cbf-like BS; mode 'random': arbitrary map bytes (stress: off-grid edges, flags)."""

@@ -38,6 +38,8 @@ CLIPS = [
     # 1920x1080, 9 pictures of the hierarchical-B cfg: the decoder leg of M3 (tools/m3_decoder_time.py) -- ~8 minutes of encoding
     ("rab_1920x1080_10b_q32", "@tests/golden/bitstreams/test_randomaccess.cfg", 1920, 1080, 10, 9, 32, 20261031),
     ("ldprdoq_208x120_10b_q32", "@tests/golden/bitstreams/test_lowdelay.cfg", 208, 120, 10, 2, 32, 20261010, 1, ["--DepQuant=0", "--SignHideFlag=1"]),
+    # 64x64 CTUs: the picture-level SAO / ALF entry points of the drop-in binding with 32x32 chroma CTUs (several CTUs per SAO strip tile)
+    ("ldpctu64_208x120_10b_q32", "@tests/golden/bitstreams/test_lowdelay.cfg", 208, 120, 10, 3, 32, 20261013, 1, ["--CTUSize=64"]),
 ]
 
 

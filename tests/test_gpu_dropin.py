@@ -71,7 +71,8 @@ def test_decoder_fallthrough_matches(tmp_path):
 
 
 @needs_ref
-@pytest.mark.parametrize("name", ["ldp_208x120_10b_q27", "ai_416x240_8b_q37own", "ldpfs_208x120_10b_q32", "ldpcrc_208x120_10b_q32", "aisum_208x120_8b_q37", "ldprdoq_208x120_10b_q32", "rab_208x120_10b_q32"])
+@pytest.mark.parametrize("name", ["ldp_208x120_10b_q27", "ai_416x240_8b_q37own", "ldpfs_208x120_10b_q32", "ldpcrc_208x120_10b_q32", "aisum_208x120_8b_q37", "ldprdoq_208x120_10b_q32", "rab_208x120_10b_q32",
+                                  "ldpctu64_208x120_10b_q32"])
 def test_encoder_with_gpu_inloop_is_bitstream_exact(tmp_path, name):
     """the reference ENCODER with deblocking, the SAO statistics (getStatistics) and the ALF covariances
     (deriveStatsForFiltering), the per-CTU SAO offsetting (offsetCTU) and the three ALF table slots computed on the GPU inside its loop: every SAO / ALF decision and therefore the bitstream must be
@@ -93,7 +94,11 @@ def test_encoder_with_gpu_inloop_is_bitstream_exact(tmp_path, name):
     line = [l for l in r.stderr.splitlines() if "[vvcgpu shim]" in l]
     assert line, r.stderr[-1000:]
     calls = [int(x) for x in line[-1].replace(",", " ").split() if x.isdigit()]
-    assert calls[0] >= m["frames"] and calls[3] >= m["frames"] and calls[4] >= m["frames"], line[-1]
+    assert calls[0] >= m["frames"] and calls[3] >= m["frames"], line[-1]
+    # the binding serves the ALF covariances with vvcgpu_alf_stats, whose chroma CTUs are multiples of 64: at CTU 64 the reference computes them
+    ctu = int(next((a.split("=")[1] for a in m.get("extra", []) if a.startswith("--CTUSize=")), 128))
+    if ctu % 128 == 0:
+        assert calls[4] >= m["frames"], line[-1]
     # per-CTU SAO offsetCTU, and the ALF table slots (m_filter5x5Blk / m_filter7x7Blk / m_deriveClassificationBlk) installed
     # where the reference installs its SIMD functions
     assert calls[5] > 0 and calls[7] > 0, line[-1]

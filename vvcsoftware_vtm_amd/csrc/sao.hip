@@ -205,7 +205,7 @@ __global__ __launch_bounds__(256) void sao_apply_picture_kernel(SaoApply3 p)
 // steps with the second step's rows in flight; a row is loaded once (the row above / below a band once more: SS_RB + 2 loads for SS_RB rows), the left / right
 // neighbour samples of a lane come from the neighbouring LANE (DPP wave shift; the two edge lanes of the tile load theirs), and the arithmetic
 // works on sample pairs (v_pk_*_i16: sign = clamp(c - n, -1, 1), the five offsets as a byte table of v_perm_b32): two load instructions and
-// ~70 vector instructions per row of eight samples.  The SAO type is a per-lane value (a chroma tile spans two CTUs): the row bodies branch on it.  Results identical to the form above (tests/test_gpu_inloop.py, the workload tests).
+// ~70 vector instructions per row of eight samples.  The SAO type is a per-lane value (a tile of a small CTU spans several CTUs): the row bodies branch on it.  Results identical to the form above (tests/test_gpu_inloop.py, the workload tests).
 // ---------------------------------------------------------------------------------------------------
 #ifndef SS_RB_D
 #define SS_RB_D 8
@@ -230,6 +230,7 @@ __device__ __forceinline__ unsigned ss_pk_sign(unsigned a, unsigned b)
   return r;
 }
 __device__ __forceinline__ unsigned ss_pk_add(unsigned a, unsigned b) { unsigned r; asm("v_pk_add_i16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+__device__ __forceinline__ unsigned ss_pk_add_sat(unsigned a, unsigned b) { unsigned r; asm("v_pk_add_i16 %0, %1, %2 clamp" : "=v"(r) : "v"(a), "v"(b)); return r; }   // signed saturation
 __device__ __forceinline__ unsigned ss_pk_max(unsigned a, unsigned b) { unsigned r; asm("v_pk_max_i16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 __device__ __forceinline__ unsigned ss_pk_min(unsigned a, unsigned b) { unsigned r; asm("v_pk_min_i16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 __device__ __forceinline__ unsigned ss_pk_sub32(unsigned a) { unsigned r; asm("v_pk_sub_i16 %0, %1, 32 op_sel_hi:[1,0]" : "=v"(r) : "v"(a)); return r; }
@@ -343,7 +344,8 @@ __device__ __forceinline__ void ss_eo_row(const SsLane& L, const SsEo& E, const 
   ss_store(L, y, o);
 }
 // band offset: offset[sample >> boShift] per sample.  TAB: the offsets of the wave's CTU as a table in LDS (the uniform walk: a look-up in memory behind
-// the previous row's store would wait for that store as well -- loads and stores share one counter), else read through the parameter record
+// the previous row's store would wait for that store as well -- loads and stores share one counter), else read through the parameter record.
+// The two adds saturate: a sample plus an offset near +32767 (the ABI takes any int16) ends at the upper clip bound, as in int arithmetic
 template <bool TAB>
 __device__ __forceinline__ void ss_bo_row(const SsLane& L, const int16_t* __restrict__ off, const unsigned short* tab, int boShift, const SsRow& mid, int y)
 {
@@ -354,7 +356,7 @@ __device__ __forceinline__ void ss_bo_row(const SsLane& L, const int16_t* __rest
     const unsigned c = mid.v[j];
     const unsigned b0 = (c & 0xFFFFu) >> boShift, b1 = c >> (16 + boShift);
     const unsigned tb = TAB ? (unsigned)tab[b0 & 31u] | (unsigned)tab[b1 & 31u] << 16 : (unsigned)(unsigned short)off[b0] | (unsigned)(unsigned short)off[b1] << 16;
-    o[j] = ss_pk_sub32(ss_pk_min(ss_pk_max(ss_pk_add(ss_pk_add(c, tb), 0x00200020u), L.lo32), L.hi32));
+    o[j] = ss_pk_sub32(ss_pk_min(ss_pk_max(ss_pk_add_sat(ss_pk_add_sat(c, tb), 0x00200020u), L.lo32), L.hi32));
   }
   ss_store(L, y, o);
 }
@@ -403,8 +405,8 @@ __global__ __launch_bounds__(64) void sao_apply_strip_kernel(SaoStrip3 p)
   L.ex = L.isL ? max(L.gx - 1, 0) : L.isR ? min(L.gx + 8, a.w - 1) : L.gxc;
   SsRaw A0;
   ss_load(L, L.y0 - 1, A0);                                                    // the first rows travel while the CTU's parameters are read
-  const int cx = L.gxc / a.ctuW, cy = min(L.y0, a.h - 1) / a.ctuH;
-  const vvcgpu_sao_ctu* prm = a.params + cy * a.wCtu + cx;
+  const int cx = L.gxc / a.ctuW, cy = min(L.y0, a.h - 1) / a.ctuH, ci = cy * a.wCtu + cx;
+  const vvcgpu_sao_ctu* prm = a.params + ci;
   L.x0 = cx * a.ctuW; L.x1 = min(L.x0 + a.ctuW, a.w); L.cy0 = cy * a.ctuH; L.cy1 = min(L.cy0 + a.ctuH, a.h);
   L.avail = prm->avail;
   L.lo32 = (unsigned)(p.clpMin + 32) * 0x10001u; L.hi32 = (unsigned)(p.clpMax + 32) * 0x10001u;
@@ -417,9 +419,11 @@ __global__ __launch_bounds__(64) void sao_apply_strip_kernel(SaoStrip3 p)
   ss_walk(L, A0, [&](const SsRow&, const SsRow& mid, const SsRow& dn, int y, bool) { unsigned o[4] = { mid.v[0], mid.v[1], mid.v[2], mid.v[3] ^ (dn.l & dn.r & 0u) }; ss_store(L, y, o); });
   return;
 #endif
-  // The tile of a plane is at most one CTU wide (host), so the type is wave-uniform wherever the CTU is at least as tall as the tile: one walk with
-  // the type's row body.  A wave that sees several types, or offsets outside the byte table, takes the general walk: loads and lane shifts are common
-  // code that every lane executes, only the row bodies branch on the lane's type (a shift inside a divergent branch would read lanes switched off there).
+  // A plane CTU of 64 or 128 samples holds whole tiles (host), so the type is wave-uniform: one walk with the type's row body.  Other CTU sizes put
+  // several CTUs into a tile (luma 32, chroma 32 / 16 / 8: 4 to 16 CTUs in a 32 x 128 tile).  Waves whose lanes see one type still take the uniform
+  // walk for EO (its offsets stay per lane), band offset only when every lane is in ONE CTU, because its look-up table is built once per wave.  A wave that sees
+  // several types, or EO offsets outside the byte table, takes the general walk: loads and lane shifts are common code that every lane executes,
+  // only the row bodies branch on the lane's type (a shift inside a divergent branch would read lanes switched off there).
   SsEo E;
   E.fits = true; E.tLo = E.tHi = 0u; E.aL = E.aR = E.bL = E.bR = E.aIn = E.bIn = 0;
   E.mI[0] = E.mI[1] = E.mI[2] = E.mI[3] = 0u; E.off[0] = E.off[1] = E.off[2] = E.off[3] = E.off[4] = 0;
@@ -431,9 +435,9 @@ __global__ __launch_bounds__(64) void sao_apply_strip_kernel(SaoStrip3 p)
   case 3: ss_eo_setup<1, -1>(L, prm, E); break;
   default: break;
   }
-  const int t0 = __builtin_amdgcn_readfirstlane(type);
+  const int t0 = __builtin_amdgcn_readfirstlane(type), ci0 = __builtin_amdgcn_readfirstlane(ci);
   const bool fullBand = !L.live || L.yEnd == L.y0 + SS_RB;                     // (a band cut by the picture's last row ends its CTU on another row than its last: general walk)
-  if (__all(type == t0 && E.fits && fullBand))
+  if (__all(type == t0 && E.fits && fullBand && (t0 != 4 || ci == ci0)))
   {
     if (t0 == 0)      ss_walk(L, A0, [&](const SsRow& u, const SsRow& m, const SsRow& d, int y, bool er) { ss_eo_row<-1, 0, true>(L, E, u, m, d, y, er); });
     else if (t0 == 1) ss_walk(L, A0, [&](const SsRow& u, const SsRow& m, const SsRow& d, int y, bool er) { ss_eo_row<0, -1, true>(L, E, u, m, d, y, er); });
@@ -442,7 +446,7 @@ __global__ __launch_bounds__(64) void sao_apply_strip_kernel(SaoStrip3 p)
     else if (t0 == 4)
     {
       __shared__ unsigned short boTab[32];
-      if (lane < 32) boTab[lane] = (unsigned short)prm->offset[lane];
+      if (lane < 32) boTab[lane] = (unsigned short)a.params[ci0].offset[lane];        // the wave's one CTU
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
       ss_walk(L, A0, [&](const SsRow&, const SsRow& m, const SsRow&, int y, bool) { ss_bo_row<true>(L, prm->offset, boTab, p.boShift, m, y); });
     }
