@@ -13,7 +13,11 @@ value = pictures all ranks processed / max-over-ranks time.  This is NOT Encoder
 outside the path (M1 must never be presented as encoder fps).
 
 `python bench.py --gpus N` without a torch.distributed environment starts the N ranks itself (torch.distributed.run, before
-anything touches a GPU).  Prints ONE JSON line on rank 0."""
+anything touches a GPU).  Prints ONE JSON line on rank 0.
+
+A plain run does what the headline needs and nothing more: set-up, warm-up, the timed steps, --dump-outputs, the result line.
+`--full` adds everything else the line has carried: picture hashes, the input-stream and with-depquant legs, the per-launch-group
+table and roofline (an untimed serial pass of their own), the CPU baseline and the real-shape block."""
 import argparse
 import ctypes as C
 import hashlib
@@ -51,6 +55,9 @@ def parse_args():
     ap.add_argument("--width", type=int, default=3840)
     ap.add_argument("--height", type=int, default=2160)
     ap.add_argument("--qp", type=int, default=32, help="base QP of the workload (BASELINE configs[2] sweeps 22 / 27 / 32 / 37): quantiser, de-quantiser, motion lambda and deblocking QP field follow it")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run and report the legs beside the headline (picture hashes, input stream, with_depquant, "
+                         "launch-group table and roofline, cpu_baseline, kernels_real_mix); the --no-* options below skip single ones of them")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-real-mix", action="store_true", help="skip the real-shape block (kernels_real_mix)")
     ap.add_argument("--serial", action="store_true", help="one stream, stage order: the default since round 4 (kept as a flag for older command lines)")
@@ -384,12 +391,12 @@ def main():
     timer = Timer()
     overlap = bool(args.overlap) and not args.serial
 
-    # ---- picture 0 on a fresh state: the md5 the 4K parity test pins (tests/golden/bench_md5.json), then one serial, bracketed
+    # ---- picture 0 on a fresh state (--full: the md5 the 4K parity test pins, tests/golden/bench_md5.json), then one serial, bracketed
     # picture to find the dominant launch group (in the timed region only THAT group carries HIP events: an event pair per
     # launch group would put ~40 markers into every picture)
     state, out = wl.run_gpu(None, None, overlap=overlap)
     torch.cuda.synchronize()
-    first_md5 = shard.picture_hash(out["final"])
+    first_md5 = shard.picture_hash(out["final"]) if args.full else None
     timer.on = True
     state, out = wl.run_gpu(state, timer, overlap=False)
     torch.cuda.synchronize()
@@ -486,6 +493,46 @@ def main():
     timed_groups = dict(timer.ev)
     if args.dump_outputs and rank == 0:
         dump_outputs(out, args.dump_outputs)                 # what the last timed picture computed, before any later leg reuses its buffers
+
+    # ---- the headline: what the timed steps alone give.  A plain run prints it and ends here; --full adds the legs below to the same line
+    pictures = args.steps * pps * world
+    ms_pic = dt / (args.steps * pps) * 1e3
+    head = {
+        "metric": BASELINE_METRIC + " [M1: hot-path pictures/s of the kernels behind the call sites, NOT EncoderApp fps]",
+        "value": pictures / dt,
+        "unit": "frames/s",
+        "n_gpus": world,
+        "rehearsal": bool(args.rehearse),
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": dt / args.steps * 1e3,
+        "timed_s": dt,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "int16",
+        "data": "synthetic",
+        "full": bool(args.full),
+        "config": {"workload": "hot-path canonical per-picture workload (SURVEY 8(d) M1: ME SAD searches 16/32/64 +-4 & raster +-96 (one hierarchical launch, every SAD once), fused half/quarter refinement 16x16 (9+9 SATD), "
+                               "bi-pred MC 16x16 (PUs without residual stored straight into the reconstruction), residual+fwd transform+quantiser (Quant::quant, sign hiding)+dequant+inv transform+reco "
+                               "(TUs handed over grouped by shape: vvcgpu_resi_chain_runs_batch), deblock, SAO stats+apply, ALF classify+stats+filter) "
+                               "on %dx%d 10-bit 4:2:0 (BASELINE configs[3] picture format; configs[1] is the same workload at 1920x1080), planes resident in HBM; "
+                               "step = one intra period of %d pictures + hand-over of the last reconstructed picture as the next chunk's reference; "
+                               "NOT EncoderApp fps (RDO control loop out of scope)" % (args.width, args.height, pps),
+                   "width": args.width, "height": args.height, "bit_depth": bd, "qp": args.qp, "pictures_per_step": pps, "ms_per_picture": ms_pic,
+                   "schedule": ("serial: one HIP stream, stage order (every kernel alone on the device: event-timed durations are kernel times)" if not overlap else
+                                "overlap: reconstruction chain on the main stream, searches / refinement / statistics on three side streams "
+                                "(their real dependencies only); the integer search is the first launch of a picture, alone on the main stream"),
+                   "parallelism": "one chunk stream per GPU (intra-period sharding), one point-to-point boundary picture per step; no data-path collective"},
+        "input_rotation": {"sets": rotate, "MB_per_set": round((sum(int(p_.size) for p_ in wl.org) + sum(int(p_.size) for p_ in wl.ref0_pad)) * 2 / 1e6, 1),
+                           "what": "original + first reference picture cycle through this many resident copies (beyond the 256 MB memory-side cache from 5 sets on)"},
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(head))
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     # ---- the same K steps once more WITH the input stream (reported beside `value`, never as `value`: the contract's figure has the inputs resident)
     dt_up = None
@@ -631,9 +678,7 @@ def main():
         per_kernel[k] = e
 
     if rank == 0:
-        pictures = args.steps * pps * world
         dk = per_kernel[dom]
-        ms_pic = dt / (args.steps * pps) * 1e3
         uniq_total = sum(v for st_ in uniq.values() for v in st_.values() if isinstance(v, (int, float)))
         # roofline{}: ONE bound, and frac against THAT bound's peak, never above 1.
         #   a search launch: bound "valu" -- useful (non-redundant) v_sad_u16 wave-instructions of the launch / its HIP-event duration against the
@@ -665,35 +710,9 @@ def main():
             roofline = dict(common, bound="hbm", achieved=ach, peak=HBM_PEAK_GBS, unit="GB/s", frac=ach / HBM_PEAK_GBS,
                             note="achieved = bytes the launch must touch once / HIP-event duration of the launch group on its stream; traffic = counter bytes of the "
                                  "committed profile (FETCH by request size + WRITE_SIZE)")
-        res = {
-            "metric": BASELINE_METRIC + " [M1: hot-path pictures/s of the kernels behind the call sites, NOT EncoderApp fps]",
-            "value": pictures / dt,
-            "unit": "frames/s",
-            "n_gpus": world,
-            "rehearsal": bool(args.rehearse),
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": dt / args.steps * 1e3,
-            "timed_s": dt,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "int16",
-            "data": "synthetic",
-            "config": {"workload": "hot-path canonical per-picture workload (SURVEY 8(d) M1: ME SAD searches 16/32/64 +-4 & raster +-96 (one hierarchical launch, every SAD once), fused half/quarter refinement 16x16 (9+9 SATD), "
-                                   "bi-pred MC 16x16 (PUs without residual stored straight into the reconstruction), residual+fwd transform+quantiser (Quant::quant, sign hiding)+dequant+inv transform+reco "
-                                   "(TUs handed over grouped by shape: vvcgpu_resi_chain_runs_batch), deblock, SAO stats+apply, ALF classify+stats+filter) "
-                                   "on %dx%d 10-bit 4:2:0 (BASELINE configs[3] picture format; configs[1] is the same workload at 1920x1080), planes resident in HBM; "
-                                   "step = one intra period of %d pictures + hand-over of the last reconstructed picture as the next chunk's reference; "
-                                   "NOT EncoderApp fps (RDO control loop out of scope)" % (args.width, args.height, pps),
-                       "width": args.width, "height": args.height, "bit_depth": bd, "qp": args.qp, "pictures_per_step": pps, "ms_per_picture": ms_pic,
-                       "schedule": ("serial: one HIP stream, stage order (every kernel alone on the device: event-timed durations are kernel times)" if not overlap else
-                                    "overlap: reconstruction chain on the main stream, searches / refinement / statistics on three side streams "
-                                    "(their real dependencies only); the integer search is the first launch of a picture, alone on the main stream"),
-                       "parallelism": "one chunk stream per GPU (intra-period sharding), one point-to-point boundary picture per step; no data-path collective"},
+        res = dict(head)
+        res.update({
             "roofline": roofline,
-            "input_rotation": {"sets": rotate, "MB_per_set": round((sum(int(p_.size) for p_ in wl.org) + sum(int(p_.size) for p_ in wl.ref0_pad)) * 2 / 1e6, 1),
-                               "what": "original + first reference picture cycle through this many resident copies (beyond the 256 MB memory-side cache from 5 sets on)"},
             "input_stream": (None if dt_up is None else {
                 "value": pictures / dt_up, "unit": "frames/s", "ms_per_picture": dt_up / (args.steps * pps) * 1e3, "timed_s": dt_up,
                 "upload_MB_per_picture": round(up["bytes"] / 1e6, 2), "side_info_MB_per_picture": round(up["side_bytes"] / 1e6, 2),
@@ -709,7 +728,7 @@ def main():
             "kernel_launches": profile_launches(),
             "lib_digest": lib_digest(),
             "encoder_fps_m3": "see profiles/*_m3_encoder.txt (reference encoder with and without the library, measured separately; never this line's value)",
-        }
+        })
         if world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(wl)
         if world == 1 and not args.no_real_mix:

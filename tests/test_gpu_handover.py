@@ -152,12 +152,12 @@ def test_handover_two_ranks_device_tensors_gloo():
 def test_bench_two_ranks_rehearsal():
     """`bench.py --gpus 2 --rehearse`: the whole N = 2 control flow of the bench on the one GPU of a test box (gloo instead of RCCL, both ranks on
     device 0): launcher, rank / world checks, chunk steps with the grouped hand-over installed in front of the first motion compensation, barriers,
-    max-over-ranks time, hash gather, input-stream leg -- one JSON line from rank 0.  Not a measurement (gloo stages device tensors through the host)."""
+    max-over-ranks time, hash gather, input-stream leg (--full) -- one JSON line from rank 0.  Not a measurement (gloo stages device tensors through the host)."""
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rehearse", "--steps", "1", "--warmup", "1", "--pictures-per-step", "2",
-                        "--width", "1920", "--height", "1080", "--rotate", "2", "--no-cpu-baseline", "--no-real-mix"],
+                        "--width", "1920", "--height", "1080", "--rotate", "2", "--full", "--no-cpu-baseline", "--no-real-mix"],
                        capture_output=True, text=True, env=env, timeout=400)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

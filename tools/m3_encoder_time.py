@@ -12,7 +12,8 @@ for: f = share of encoder time inside the hot path (gprof split of the reference
 the batched kernels (bench.py: GPU pictures/s over the reference's SIMD kernels on one host core).
 
 This is a test/measurement tool: it runs the compiled reference, which is not part of the product path.
-usage: python tools/m3_encoder_time.py [--projection-only] [bench.json] > profiles/rNN_m3_encoder.txt"""
+usage: python tools/m3_encoder_time.py [--projection-only] [bench.json] > profiles/rNN_m3_encoder.txt
+(bench.json: the line of `bench.py --full`, which carries cpu_baseline)"""
 import hashlib
 import json
 import os

@@ -16,7 +16,6 @@ python3 profiles/summarize.py gpurun_out $TAG > gpurun_out/summarize.log 2>&1 &&
 python3 profiles/summarize_pmc.py gpurun_out $TAG >> gpurun_out/summarize.log 2>&1 &&
 python3 tools/mfma_vs_dot2.py > profiles/${TAG}_mfma_vs_dot2.txt 2> gpurun_out/mfma_vs_dot2.err &&
 python3 tools/shape_mix_time.py 8388608 2> gpurun_out/shape_mix.err | grep -v amdgpu.ids > profiles/${TAG}_shape_mix.txt &&
-python3 bench.py --steps 10 --warmup 3 > gpurun_out/${TAG}_bench_n1.json 2> gpurun_out/bench.err
+python3 bench.py --full --steps 10 --warmup 3 > profiles/${TAG}_bench_n1.json
 mkdir -p gpurun_out/profiles_out && cp profiles/${TAG}_* gpurun_out/profiles_out/ 2>/dev/null
-cp gpurun_out/${TAG}_bench_n1.json gpurun_out/profiles_out/ 2>/dev/null
-tail -c 600 gpurun_out/${TAG}_bench_n1.json
+tail -c 600 profiles/${TAG}_bench_n1.json
