@@ -66,7 +66,14 @@ int vvcgpu_stream_sync(void* stream);
  * releases the table images below (e.g. before unloading the library); whatever is needed afterwards is created again on demand.  Both return
  * VVCGPU_OK when there was nothing to free and VVCGPU_E_DEVICE when a device could not be reached (what could not be freed is kept, not leaked).
  * The scratch of a stream grows geometrically; a buffer it has outgrown is freed once the work queued up to the end of the call that outgrew it
- * has completed.  One host thread drives a stream at a time (per-thread streams for concurrent callers). */
+ * has completed.
+ * Threads: the entry points are re-entrant; calls on DIFFERENT streams may run at the same time from different host threads (the first calls included,
+ * which create the slots and build the table images below), and so may vvcgpu_stream_release of different streams.  ONE host thread drives a stream at a
+ * time (per-thread streams for concurrent callers), and that includes its release: no thread is inside an entry point on a stream while another
+ * releases it.  Once vvcgpu_stream_release(stream) has returned the library holds nothing for that handle: any thread may drive it from then on (a
+ * runtime that hands out streams from a pool may give the handle to another thread), its resources are created anew.  vvcgpu_shutdown() is called while
+ * no other thread is inside the library.  vvcgpu_last_error() is per thread: a refused call of one thread never shows in another's text.
+ * (tests/test_gpu_threads.py runs this contract with 4 and 8 threads against the oracle.) */
 int vvcgpu_stream_release(void* stream);
 int vvcgpu_shutdown(void);
 /* Per device (and bit depth) the library keeps a few constant table images in device memory: the transform matrices (TrQuant.cpp:72-84, Rom.cpp:245-299)

@@ -235,6 +235,95 @@ def test_bench_workload_4k_matches_oracle():
         _cmp_pred(k + "#handover", g2, c2[k]) if k == "pred" else _cmp(k + "#handover", g2[k], c2[k])
 
 
+def _golden_md5(key):
+    import json
+    import os
+    return json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "bench_md5.json")))[key]
+
+
+def _cpu_md5(planes):
+    import hashlib
+    h = hashlib.md5()
+    for p in planes:
+        h.update(np.ascontiguousarray(p).tobytes())
+    return h.hexdigest()
+
+
+def _bench_workload_matches_oracle(width, height, key):
+    """bench.py's object at width x height in its overlapped schedule against the checker (the compiled reference where oracle/_ref exists, its
+    arg-min re-derived from the SAD surfaces; else the scalar port): every output run_cpu returns, and the pinned md5 of `final`.
+    Returns the checker's seconds per stage."""
+    from vvcsoftware_vtm_amd import shard
+    from vvcsoftware_vtm_amd.workload import Workload
+    wl = Workload(width, height, 10, seed=20261003)
+    _, gout = wl.run_gpu(None, None, overlap=True)
+    torch.cuda.synchronize()
+    md5 = shard.picture_hash(gout["final"])
+    if ref_available():
+        cout, secs = run_cpu(wl, (oracle(), ref()), "reference")
+        for s in sorted(wl.me):
+            for grid in wl.me_grids:
+                k = "%d_%d" % (s, grid[2])
+                cout["me_best_" + k] = best_from_surface(cout["me_sad_" + k], grid, wl.mvcost)
+    else:
+        cout, secs = run_cpu(wl, oracle(), "port")
+    print("checker seconds at %dx%d (%s):" % (width, height, "reference" if ref_available() else "port"), {k: round(v, 1) for k, v in secs.items()})
+    checked = []
+    for k in cout:
+        if k.startswith("me_sad_"):
+            continue                                  # the searches return the best candidate only (me_best_*)
+        _cmp_pred(k, gout, cout[k]) if k == "pred" else _cmp(k, gout[k], cout[k])
+        checked.append(k)
+    for k in ["me_best_%d_%d" % (s, n) for s in (16, 32, 64) for n in (9, 39)] + ["frac", "coef", "abs_sum", "final", "sao_stats", "alf_stats7", "alf_stats5", "alf_stats_c", "cls", "pred"]:
+        assert k in checked, k
+    assert md5 == _cpu_md5(cout["final"])
+    assert md5 == _golden_md5(key)
+    print("bench first-picture md5 at %dx%d" % (width, height), md5)
+    return secs
+
+
+def test_bench_workload_1080p_matches_oracle():
+    """The object `bench.py --width 1920 --height 1080` times -- Workload(1920, 1080, 10, seed=20261003), bench defaults throughout -- in the
+    overlapped schedule against the checker at full size, as test_bench_workload_4k_matches_oracle does at 3840x2160.  1080 = 8 x 128 + 56: a
+    ragged bottom CTU row (partial CTUs in deblocking / SAO / ALF, partial ME super-blocks), and with 15 x 9 = 135 CTUs the ALF takes its
+    two-launch form for pictures under 320 CTUs.  Every stage runs on the previous stage's output, so this is the stages composed, not one by one.
+    The pinned md5 is the checker's (tests/golden/bench_md5.json: compiled reference == scalar port)."""
+    _bench_workload_matches_oracle(1920, 1080, "1920x1080_10bit_seed20261003_qp32_first_picture_final_md5")
+
+
+def test_bench_workload_8k_matches_oracle():
+    """The same at 7680x4320 (4320 = 33 x 128 + 96: the ragged bottom row again, at 60 x 34 CTUs), bench defaults throughout: three block sizes,
+    the +-4 and +-96 grids.  One checker step on the host of the MI355X machine: the scalar port 53 s (ME 40 s, fractional refinement 7 s, ALF 4 s;
+    the whole test 57 s), the compiled reference 7 s (ME 2.5 s, ALF 3.3 s; the whole test 11 - 15 s); about 2.6 GB of host memory.  A slower host
+    has been seen to take 130 s for the port's step (ME 99 s): a time limit of 600 s for this test alone leaves a wide margin."""
+    _bench_workload_matches_oracle(7680, 4320, "7680x4320_10bit_seed20261003_qp32_first_picture_final_md5")
+
+
+@pytest.mark.parametrize("width,height", [(3840, 2160), (1920, 1080)])
+def test_bench_depquant_leg_4k_md5_matches_oracle(width, height):
+    """bench.py's `with_depquant` leg at the size it runs -- Workload(width, height, 10, seed=20261003, depquant=True), serial schedule -- against
+    the checker: levels, abs sums, reconstruction after the in-loop chain and the ALF classes, as the 416x240 leg test compares them; the md5 of
+    `final` pinned under its own key (bench.py --full prints it as with_depquant.last_picture_md5).  bench prints the LAST picture's md5: a second
+    step on the resident state must give the same.  1920x1080 is the leg on the ragged picture (partial CTUs and the trellis together)."""
+    from vvcsoftware_vtm_amd import shard
+    from vvcsoftware_vtm_amd.workload import Workload
+    wl = Workload(width, height, 10, seed=20261003, depquant=True)
+    assert wl.depquant and not wl.fused_resi and int(wl.dqtr["dep_quant"].min()) == 1
+    st, gout = wl.run_gpu(None, None, overlap=False)
+    torch.cuda.synchronize()
+    md5 = shard.picture_hash(gout["final"])
+    cout, secs = run_cpu(wl, (oracle(), ref()), "reference") if ref_available() else run_cpu(wl, oracle(), "port")
+    print("checker seconds at %dx%d, depquant leg:" % (width, height), {k: round(v, 1) for k, v in secs.items()})
+    for k in ("abs_sum", "coef", "final", "cls"):
+        _cmp(k, gout[k], cout[k])
+    assert md5 == _cpu_md5(cout["final"])
+    assert md5 == _golden_md5("%dx%d_10bit_seed20261003_qp32_depquant_final_md5" % (width, height))
+    st, gout2 = wl.run_gpu(st, None, overlap=False)
+    torch.cuda.synchronize()
+    assert shard.picture_hash(gout2["final"]) == md5, "second step on the resident state"
+    print("with_depquant md5 at %dx%d" % (width, height), md5)
+
+
 def test_fused_residual_chain_equals_separate_entry_points():
     """vvcgpu_resi_chain_batch inside the workload (default) against the five separate entry points it replaces, on the same step"""
     from vvcsoftware_vtm_amd.workload import Workload

@@ -20,7 +20,12 @@ void vvcgpu_set_error(const char* fmt, ...)
 // one mutex; slots are created on first use, released by vvcgpu_stream_release (before the host destroys the stream) or all at once by vvcgpu_shutdown.
 // An outgrown buffer is NOT freed on the spot -- queued work may still read it, and hipFree synchronises the device -- but parked behind an event, freed
 // once that has completed (at a later growth) or with the slot.  Capacity at least doubles, so the parked buffers sum to less than the live one.  No
-// entry point allocates, or synchronises anything, while it holds the mutex.  (One host thread drives a stream at a time: include/vvcgpu.h.)
+// entry point allocates, frees, queues work or synchronises anything while it holds the mutex (hipEventQuery in retire() does not wait); the one
+// exception is vvcgpu_shutdown, which holds both mutexes for its whole length on purpose.  One host thread drives a stream at a time
+// (include/vvcgpu.h): between two lookups of one call nobody else creates, changes or releases THAT stream's slot -- which is why retire(),
+// vvcgpu_iota and vvcgpu_counters may drop the lock, allocate, and look the slot up again (with create = true: the second lookup finds the slot
+// of the first, possibly at another address, since other threads' slots come and go and the vector re-allocates; a pointer into g_slots is never kept
+// across an unlock).  tests/test_gpu_threads.py runs this with 4 and 8 threads.
 namespace {
 struct Retired { void* ptr; hipEvent_t done; };
 struct StreamSlot
@@ -185,23 +190,40 @@ int* vvcgpu_counters(hipStream_t stream, int* cur)
 {
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess) { vvcgpu_set_error("hipGetDevice failed"); return nullptr; }
-  std::lock_guard<std::mutex> lock(g_slotMutex);
-  StreamSlot* slot = find_slot(dev, stream, true);
-  if (!slot->counters)
+  constexpr size_t bytes = 2 * VVC_CTR_INTS * sizeof(int);
+  int* have = nullptr; bool clear = false;
   {
-    void* p = nullptr;
-    if (hipMalloc(&p, 2 * VVC_CTR_INTS * sizeof(int)) != hipSuccess) { vvcgpu_set_error("counters: hipMalloc failed"); return nullptr; }
-    if (hipMemset(p, 0, 2 * VVC_CTR_INTS * sizeof(int)) != hipSuccess) { (void)hipFree(p); vvcgpu_set_error("counters: hipMemset failed"); return nullptr; }
-    slot->counters = static_cast<int*>(p); slot->cur = 0; slot->dirty = false;
+    std::lock_guard<std::mutex> lock(g_slotMutex);
+    StreamSlot* slot = find_slot(dev, stream, true);
+    if ((have = slot->counters) != nullptr)                                 // the hot path
+    {
+      clear = slot->dirty;
+      if (clear) { slot->dirty = false; slot->cur = 0; }
+      *cur = slot->cur;
+      slot->cur ^= 1;
+    }
   }
-  if (slot->dirty)
+  if (have)
   {
-    if (hipMemsetAsync(slot->counters, 0, 2 * VVC_CTR_INTS * sizeof(int), stream) != hipSuccess) { vvcgpu_set_error("counters: hipMemsetAsync failed"); return nullptr; }
-    slot->dirty = false; slot->cur = 0;
+    // the clearing is queued outside the lock, on the caller's stream: in front of the caller's kernels, behind the failed call's
+    if (clear && hipMemsetAsync(have, 0, bytes, stream) != hipSuccess) { (void)hipGetLastError(); vvcgpu_counters_failed(stream); vvcgpu_set_error("counters: hipMemsetAsync failed"); return nullptr; }
+    return have;
   }
-  *cur = slot->cur;
-  slot->cur ^= 1;
-  return slot->counters;
+  // first use on this stream: allocated and zeroed outside the lock.  The zeroing goes onto the CALLER's stream, so it is ordered in front of the first
+  // kernel that reads the sets whatever kind of stream that is (a non-blocking stream does not wait for the null stream).
+  void* p = nullptr;
+  if (hipMalloc(&p, bytes) != hipSuccess) { (void)hipGetLastError(); vvcgpu_set_error("counters: hipMalloc failed"); return nullptr; }
+  if (hipMemsetAsync(p, 0, bytes, stream) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(p); vvcgpu_set_error("counters: hipMemsetAsync failed"); return nullptr; }
+  {
+    std::lock_guard<std::mutex> lock(g_slotMutex);                         // looked up again: the table may have been re-allocated
+    StreamSlot* slot = find_slot(dev, stream, true);
+    if (!slot->counters) { slot->counters = static_cast<int*>(p); slot->cur = 0; slot->dirty = false; p = nullptr; }
+    have = slot->counters;
+    *cur = slot->cur;
+    slot->cur ^= 1;
+  }
+  if (p) (void)hipFree(p);                                                  // only if a second thread drove the stream meanwhile (outside the contract): its sets stay
+  return have;
 }
 void vvcgpu_counters_failed(hipStream_t stream)
 {
