@@ -43,7 +43,8 @@ int         vvcgpu_set_device(int device);
 /* sizeof() of the parameter structs, for binding self-checks: 0 sao_ctu, 1 deblock_cfg, 2 dist_desc, 3 search_blk,
  * 4 mvcost, 5 search_best, 6 if_desc, 7 mc_desc, 8 pelop_desc, 9 pelop_cfg, 10 tr_desc, 11 frac_blk, 12 frac_result,
  * 13 dqtr_desc, 14 afg_desc, 15 afe_desc, 16 tz_pu, 17 tz_cfg, 18 intra_desc, 19 cclm_desc, 20 intra_fill_desc, 21 imv_pu, 22 imv_result, 23 quant_desc,
- * 24 dq_rates, 25 depquant_desc, 26 rdoq_rates, 27 rdoq_desc, 28 intra_satd_desc, 29 affine_iter, 30 me_hier_cfg, 31 wp_param; -1 for unknown ids. */
+ * 24 dq_rates, 25 depquant_desc, 26 rdoq_rates, 27 rdoq_desc, 28 intra_satd_desc, 29 affine_iter, 30 me_hier_cfg, 31 wp_param,
+ * 32 wp_sad_cand, 33 tile_stats; -1 for unknown ids. */
 int         vvcgpu_sizeof(int struct_id);
 
 /* ---- device memory helpers for host-side callers (the reference keeps pictures in host memory; the shim stages them).
@@ -827,6 +828,72 @@ int vvcgpu_imv_refine_batch(const vvc_pel* org, int org_stride, const vvc_pel* r
 int vvcgpu_me_batch(const vvc_pel* org, int org_stride, const vvc_pel* ref, int ref_stride, const vvcgpu_tz_pu* pus, int n, int w, int h,
                     const vvcgpu_tz_cfg* cfg_host, int bit_depth, int clp_min, int clp_max, int use_hadamard,
                     vvcgpu_search_best* int_results, vvcgpu_frac_result* frac_results, void* stream);
+
+/* ---- encoder picture analysis: the per-picture scalars the reference computes OUTSIDE its CTU loop, from planes already in HBM --------------
+ * (the same reason vvcgpu_picture_hash exists: a 4K 10-bit picture is 24.9 MB, its download costs more than its whole hot path).  Every device
+ * result is an INTEGER, bit-exact with the reference; where the reference goes on in double, the *_host helpers below finish the integers with the
+ * reference's operations in the reference's order (no floating-point sum is formed on the device).  Picture forms take vvcgpu_planes (Y, Cb, Cr;
+ * 4:2:0, chroma at half size) and n_planes in {1, 3} (1: only p[0] / stride[0] are read, at width x height -- a chroma plane may be passed that way).
+ * Precondition of every entry: samples within the bit depth (0 .. 2^bd - 1, bd 8..10).  Null pointers and bad sizes return VVCGPU_E_ARG, a bit depth
+ * outside 8..10 VVCGPU_E_UNSUPPORTED, before any device work.  Base pointers and strides are free: 16-byte row loads where both allow, sample-wise
+ * loads otherwise (views into padded pictures, odd strides).  Each entry is at most one zeroing launch and one kernel; none synchronises.
+ *
+ * vvcgpu_tile_stats_picture: per plane, the plane is cut into tile x tile tiles (tile / 2 for the chroma planes of n_planes = 3), raster order, partial
+ *   tiles at the right and at the bottom: ceil(w / t) * ceil(h / t) records per plane, written to out_y / out_cb / out_cr (the chroma outputs may be
+ *   null for n_planes = 1).  Per tile:
+ *     sa_act  sum |f| of the high-pass filter  f = 12 c - 2 (l + r + u + d) - (the four diagonal neighbours)  over the tile's samples EXCEPT those on the
+ *             plane's outer row or column; neighbours are read across tile borders;
+ *     sum     sum of the samples of the whole tile;
+ *     ss_err  sum (org - rec)^2 over the whole tile; 0 when rec_or_null is null.
+ *   tile: a multiple of 4 (n_planes = 1) or of 8 (n_planes = 3) up to 128.  Two reference computations are this definition:
+ *   (a) perceptual QP adaptation per CTU (EncSlice.cpp:1405-1448, filterAndCalculateAverageEnergies :156-184): with tile = CTU size, the interior of the
+ *       reference's fltArea (the CTU grown by one sample and clipped to the picture, whose own border row and column the filter skips) is exactly the
+ *       CTU's samples minus the picture's outer row and column, so sa_act is the reference's saAct of that CTU and its sample count is
+ *       (iFltWidth - 2) * (iFltHeight - 2); m_iOffsetCtu = (sum + (n >> 1)) / n with n the CTU's clipped area.  The whole-plane activity of
+ *       applyQPAdaptationChroma (:219, luma and both chroma planes) is the integer sum of a plane's sa_act, the luma mean of :237-244 the sum of its sum fields.
+ *   (b) WPSNR (EncGOP.cpp:2661-2717, calcWeightedSquaredError): with tile = B, the block size of :2741-2742 (vvcgpu_wpsnr_block_size_host), xAct, yAct,
+ *       wAct and hAct select the same samples, ss_err is ssErr and sa_act is saAct; org is the ORIGINAL (the reference passes it as its pic1).  One tile
+ *       size per call, halved for chroma: when the chroma B is not half the luma B (the table of a plane's own B: 3840x2160 128 / 64, 1920x1080 64 / 32,
+ *       416x240 16 / 8, 64x64 4 / none), call per plane with n_planes = 1.
+ * vvcgpu_picture_sse: sum (a - b)^2 per plane, out3[0..2] (the planes beyond n_planes: 0) -- xFindDistortionPlane without WPSNR (EncGOP.cpp:2812-2825)
+ *   and its fall-back for planes too small for WPSNR (:2746-2760).  No filter reads.
+ * vvcgpu_wpsnr_block_size_host: B of :2741-2742 in the reference's types from the PLANE's own width and height and its chroma shift (0 luma, 1 chroma of
+ *   4:2:0); 0 when the reference falls back to the plain SSE (B < 4).
+ * vvcgpu_wpsnr_finish_host: :2762-2794 from the tile records of one plane (tile = that plane's B, host copy): wmse += ss_err * pow(msAct^2, -0.5) in raster
+ *   order with the lower limit of :2709, the GLOBAL_AVERAGING scaling by picture size, uint64(wmse * pow(sumAct, 0.5) + 0.5).  VVCGPU_E_ARG for a plane
+ *   whose B is 0.
+ *
+ * vvcgpu_picture_histogram: xCalcHistogram (WeightPredAnalysis.cpp:79-99, values clamped into [0, 2^bd)) of every plane: hist[c * 2^bd + v], uint32,
+ *   3 * 2^bd entries (planes beyond n_planes: 0).
+ * vvcgpu_wp_acdc_host: xCalcACDCParamSlice (:267-297) of one plane from its histogram (host copy, 2^bd entries, n_samples = width * height of the plane):
+ *   orgDC = sum v * h[v]; orgNormDC and *dc with the roundings of :280, 296 (fixed_shift: RExt__PREDICTION_WEIGHTING_ANALYSIS_DC_PRECISION with
+ *   high-precision offsets, else 0); *ac = sum h[v] * |v - orgNormDC|.  One device pass for the reference's two dependent ones; exact because the samples
+ *   are within the bit depth (the histogram's clamp changes nothing).
+ * vvcgpu_wp_sad_batch: the weighted SADs of ONE (original plane, reference plane) pair for n_cand (0..16; 0: a no-op) candidates in one pass over the two
+ *   planes; out: n_cand int64 on the device.  flags bit 0: high-precision offsets; bit 1: the clipped form.  Unclipped: xCalcSADvalueWP (:653-682) =
+ *   the unclipped branch of xCalcSADvalueWPOptionalClip (:718-733); clipped: :699-717.  Accumulation in 64 bits as the reference.  Candidates are
+ *   accepted within log2_denom 0..7, |weight| <= 1024, offset -32768..32767 (else VVCGPU_E_ARG): every term then fits 32 bits.  Covers the four SADs
+ *   per (list, reference, component) of xUpdatingWPParameters (:513-545) and the pairs of xSelectWP (:620-630).
+ *   xSearchHistogram / xCalcHistDistortion (:102-219) are NOT offered: the reference's loop reads one element past its vectors (i <= numElements, :110),
+ *   so there is nothing defined to be exact against.
+ *
+ * vvcgpu_intra_cost_ctus: rate control's intra cost (EncSlice::calCostSliceI, EncSlice.cpp:1163-1204): per CTU in raster order
+ *   m_costIntra = (sumHad + offset) >> shift with shift = bit_depth - 8, offset = shift ? 1 << (shift - 1) : 0 (:1172-1173) and sumHad the sum over the
+ *   whole 8 x 8 blocks inside the clipped CTU (EncCu::updateCtuDataISlice, EncCu.cpp:468-485) of the 8 x 8 Hadamard of the original samples without its DC
+ *   term, (s + 2) >> 2 (xCalcHADs8x8_ISlice :374-466).  cost: ceil(width / ctu) * ceil(height / ctu) int32; the picture's total is the host's sum.
+ *   ctu_size: 16, 32, 64 or 128.                                                                                                                  */
+typedef struct { uint64_t sa_act, sum, ss_err; } vvcgpu_tile_stats;                     /* sizeof == 24 */
+typedef struct { int32_t log2_denom, weight, offset, flags; } vvcgpu_wp_sad_cand;        /* sizeof == 16 */
+int vvcgpu_tile_stats_picture(const vvcgpu_planes* org, const vvcgpu_planes* rec_or_null, int width, int height, int tile, int n_planes,
+                              vvcgpu_tile_stats* out_y, vvcgpu_tile_stats* out_cb, vvcgpu_tile_stats* out_cr, void* stream);
+int vvcgpu_picture_sse(const vvcgpu_planes* a, const vvcgpu_planes* b, int width, int height, int n_planes, uint64_t* out3, void* stream);
+int vvcgpu_wpsnr_block_size_host(int plane_w, int plane_h, int chroma_shift, int* block_size);
+int vvcgpu_wpsnr_finish_host(const vvcgpu_tile_stats* tiles_host, int plane_w, int plane_h, int chroma_shift, int bit_depth, uint64_t* ssd);
+int vvcgpu_picture_histogram(const vvcgpu_planes* pic, int width, int height, int n_planes, int bit_depth, uint32_t* hist, void* stream);
+int vvcgpu_wp_acdc_host(const uint32_t* hist_host, int bit_depth, int n_samples, int fixed_shift, int64_t* dc, int64_t* ac);
+int vvcgpu_wp_sad_batch(const vvc_pel* org, int org_stride, const vvc_pel* ref, int ref_stride, int w, int h, int bit_depth,
+                        const vvcgpu_wp_sad_cand* cands_host, int n_cand, int64_t* out, void* stream);
+int vvcgpu_intra_cost_ctus(const vvc_pel* org_y, int stride, int width, int height, int ctu_size, int bit_depth, int32_t* cost, void* stream);
 
 #ifdef __cplusplus
 }

@@ -126,3 +126,9 @@ AFE_DESC = np.dtype([("resi_off", "<i8"), ("deriv_off", "<i8"), ("deriv_stride",
 AFFINE_PU = np.dtype([("pos_x", "<i4"), ("pos_y", "<i4"), ("w", "<i2"), ("h", "<i2"), ("six_param", "<i2"), ("bi", "<i2"), ("mv", "<i4", (2, 3, 2)),
                       ("dst_off", "<i8"), ("dst_stride", "<i4"), ("first_desc", "<i4")])
 AFFINE_ITER = np.dtype([("pu", AFFINE_PU), ("org_off", "<i8"), ("org_stride", "<i4"), ("reserved", "<i4")])
+
+# ---- encoder picture analysis ---------------------------------------------------------------------------------------------------------------------
+# vvcgpu_tile_stats: one tile of vvcgpu_tile_stats_picture; vvcgpu_wp_sad_cand: one candidate of vvcgpu_wp_sad_batch (flags: WP_SAD_*)
+TILE_STATS = np.dtype([("sa_act", "<u8"), ("sum", "<u8"), ("ss_err", "<u8")])
+WP_SAD_CAND = np.dtype([("log2_denom", "<i4"), ("weight", "<i4"), ("offset", "<i4"), ("flags", "<i4")])
+WP_SAD_HIGH_PRECISION, WP_SAD_CLIPPED = 1, 2

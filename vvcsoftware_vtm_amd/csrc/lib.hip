@@ -314,6 +314,8 @@ int vvcgpu_sizeof(int id)
   case 29: return (int)sizeof(vvcgpu_affine_iter);
   case 30: return (int)sizeof(vvcgpu_me_hier_cfg);
   case 31: return (int)sizeof(vvcgpu_wp_param);
+  case 32: return (int)sizeof(vvcgpu_wp_sad_cand);
+  case 33: return (int)sizeof(vvcgpu_tile_stats);
   default: return -1;
   }
 }

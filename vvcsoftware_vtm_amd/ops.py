@@ -11,7 +11,7 @@ from . import capi
 from .abi import (AFE_DESC, AFFINE_ITER, AFFINE_PU, AFG_DESC, CCLM_DESC, DEPQUANT_DESC, DIST_DESC, DQ_RATES, DQTR_DESC, FRAC_BLK,  # noqa: F401
                   FRAC_RESULT, IF_DESC, IMV_PU, IMV_RESULT, INTRA_DESC, INTRA_FILL_DESC, INTRA_SATD_DESC, MC_DESC, PELOP_DESC, QUANT_DESC, RC_DESC,
                   RDOQ_DESC, RDOQ_RATES, RDPCM_DESC, SAO_DTYPE, SEARCH_BEST, SEARCH_BLK, TR_DESC, TZ_CFG, TZ_PU, DeblockCfg, MeHierCfg, MvCost,
-                  PelopCfg, Planes, WP_PARAM)
+                  PelopCfg, Planes, WP_PARAM, TILE_STATS, WP_SAD_CAND, WP_SAD_HIGH_PRECISION, WP_SAD_CLIPPED)
 
 
 def _stream():
@@ -493,3 +493,93 @@ def affine_subblock_descs(pus_dev, n, n_descs, comp, pic_w, pic_h, ref_origin, r
     capi.call("vvcgpu_affine_subblock_descs", capi.ptr(pus_dev), n, comp, pic_w, pic_h, max_cu, max_cu, ref_origin[0], ref_origin[1], ref0_stride,
               ref1_stride, capi.ptr(out), _stream())
     return out
+
+
+# ---- encoder picture analysis (PSNR / WPSNR, QPA activity, weighted-prediction statistics, rate control's intra cost) ----------------------------
+def _planes_n(ts):
+    """1 or 3 planes (a 2-D tensor or a sequence of them) -> (vvcgpu_planes, n_planes, width, height)"""
+    ts = [ts] if torch.is_tensor(ts) else list(ts)
+    assert len(ts) in (1, 3), "1 or 3 planes"
+    return planes(ts), len(ts), ts[0].shape[1], ts[0].shape[0]
+
+
+def tile_stats_picture(org, rec, tile):
+    """per plane an int64 tensor (tiles_y, tiles_x, 3) holding sa_act, sum, ss_err (uint64 bit patterns) of its tile x tile tiles (tile / 2 for the chroma
+    planes of a 3-plane call); rec may be None (ss_err = 0)"""
+    po, n, w, h = _planes_n(org)
+    pr = _planes_n(rec)[0] if rec is not None else None
+    dev = (org if torch.is_tensor(org) else org[0]).device
+    outs = []
+    for c in range(n):
+        t = tile >> 1 if c else tile
+        pw, ph = (w >> 1, h >> 1) if c else (w, h)
+        outs.append(torch.empty((-(-ph // t), -(-pw // t), 3), dtype=torch.int64, device=dev))
+    capi.call("vvcgpu_tile_stats_picture", C.byref(po), C.byref(pr) if pr is not None else None, w, h, tile, n, capi.ptr(outs[0]),
+              capi.ptr(outs[1]) if n == 3 else None, capi.ptr(outs[2]) if n == 3 else None, _stream())
+    return outs
+
+
+def picture_sse(a, b):
+    """sum (a - b)^2 per plane -> int64 tensor (3,) on the device"""
+    pa, n, w, h = _planes_n(a)
+    pb = _planes_n(b)[0]
+    out = torch.empty(3, dtype=torch.int64, device=(a if torch.is_tensor(a) else a[0]).device)
+    capi.call("vvcgpu_picture_sse", C.byref(pa), C.byref(pb), w, h, n, capi.ptr(out), _stream())
+    return out
+
+
+def picture_histogram(pic, bit_depth):
+    """xCalcHistogram of every plane -> int32 tensor (3, 2^bd) on the device"""
+    pp, n, w, h = _planes_n(pic)
+    out = torch.empty((3, 1 << bit_depth), dtype=torch.int32, device=(pic if torch.is_tensor(pic) else pic[0]).device)
+    capi.call("vvcgpu_picture_histogram", C.byref(pp), w, h, n, bit_depth, capi.ptr(out), _stream())
+    return out
+
+
+def wp_sad_cands(cands):
+    """[(log2_denom, weight, offset, flags)] -> WP_SAD_CAND array"""
+    return np.array([tuple(c) for c in cands], dtype=WP_SAD_CAND)
+
+
+def wp_sad_batch(org, ref, bit_depth, cands):
+    """weighted SADs of one (original, reference) plane pair for up to 16 candidates (WP_SAD_CAND array or tuples) -> int64 tensor (n_cand,)"""
+    po, so, w, h = _plane(org, "org")
+    pr, sr, wr, hr = _plane(ref, "ref")
+    assert (w, h) == (wr, hr)
+    cands = np.ascontiguousarray(cands if isinstance(cands, np.ndarray) else wp_sad_cands(cands))
+    assert cands.dtype == WP_SAD_CAND
+    out = torch.empty(len(cands), dtype=torch.int64, device=org.device)
+    capi.call("vvcgpu_wp_sad_batch", po, so, pr, sr, w, h, bit_depth, cands.ctypes.data_as(C.c_void_p), len(cands), capi.ptr(out), _stream())
+    return out
+
+
+def intra_cost_ctus(org_y, ctu_size, bit_depth):
+    """m_costIntra of every CTU -> int32 tensor (ctus_y, ctus_x)"""
+    p, st, w, h = _plane(org_y, "org_y")
+    out = torch.empty((-(-h // ctu_size), -(-w // ctu_size)), dtype=torch.int32, device=org_y.device)
+    capi.call("vvcgpu_intra_cost_ctus", p, st, w, h, ctu_size, bit_depth, capi.ptr(out), _stream())
+    return out
+
+
+def wpsnr_block_size(plane_w, plane_h, chroma_shift):
+    """the WPSNR block size of a plane (0: the reference takes the plain SSE)"""
+    b = C.c_int()
+    capi.call("vvcgpu_wpsnr_block_size_host", plane_w, plane_h, chroma_shift, C.byref(b))
+    return b.value
+
+
+def wpsnr_finish(tiles, plane_w, plane_h, chroma_shift, bit_depth):
+    """tiles: the plane's tile statistics at its own block size (host array, TILE_STATS records or (.., 3) 64-bit integers) -> the reference's weighted SSD"""
+    t = np.ascontiguousarray(np.asarray(tiles)).view(np.uint64).reshape(-1)
+    ssd = C.c_uint64()
+    capi.call("vvcgpu_wpsnr_finish_host", t.ctypes.data_as(C.c_void_p), plane_w, plane_h, chroma_shift, bit_depth, C.byref(ssd))
+    return ssd.value
+
+
+def wp_acdc(hist, bit_depth, n_samples, fixed_shift=0):
+    """(iDC, iAC) of xCalcACDCParamSlice from one plane's histogram (host array of 2^bd counts)"""
+    hh = np.ascontiguousarray(np.asarray(hist).astype(np.uint32))
+    assert hh.size == 1 << bit_depth
+    dc, ac = C.c_int64(), C.c_int64()
+    capi.call("vvcgpu_wp_acdc_host", hh.ctypes.data_as(C.c_void_p), bit_depth, n_samples, fixed_shift, C.byref(dc), C.byref(ac))
+    return dc.value, ac.value
