@@ -119,7 +119,7 @@ def test_resi_chain_rectangles_and_chroma_shapes():
     org = cases.rand_plane(rng, H, W, bd, "smooth")
     pred = np.clip(org + rng.integers(-40, 41, org.shape), 0, 1023).astype(np.int16)
     shapes = [(64, 32), (32, 64), (16, 32), (32, 16), (64, 16), (8, 16), (16, 8), (4, 16), (4, 64), (64, 4), (16, 4), (4, 8), (8, 4), (2, 8), (8, 2), (2, 2), (16, 64), (32, 8), (2, 32)]
-    tus = tile(W, H, shapes, rng, [27, 32, 37], bd)
+    tus = tile(W, H, shapes, rng, [27, 32, 37, 22, 24, 29], bd)                 # every qp % 6
     lv, asum, rec, coffs = oracle_chain(org, pred, tus, bd, W)
     glv, gsum, grec = gpu_chain(org, pred, tus, bd, W, coffs)
     assert np.array_equal(gsum, asum)
@@ -139,7 +139,7 @@ def test_resi_chain_packed_tiles(bd, content):
     pred = cases.rand_plane(rng, H, W, bd, "smooth" if content != "extreme" else "extreme")
     if content == "smooth":
         pred = np.clip(org + rng.integers(-9, 10, org.shape), 0, (1 << bd) - 1).astype(np.int16)
-    tus = tile(W, H, [(16, 8), (8, 16), (16, 4), (4, 16), (16, 16), (8, 8), (32, 8), (8, 32), (32, 4), (4, 32), (64, 8), (8, 64), (64, 4), (4, 64)], rng, [22, 27, 32, 37, 45], bd)
+    tus = tile(W, H, [(16, 8), (8, 16), (16, 4), (4, 16), (16, 16), (8, 8), (32, 8), (8, 32), (32, 4), (4, 32), (64, 8), (8, 64), (64, 4), (4, 64)], rng, [22, 27, 30, 32, 35, 37, 45], bd)   # every qp % 6
     keep = rng.random(len(tus)) > 0.07                       # odd counts per class, tiles whose TUs are not neighbours in the picture
     tus = [t for t, k in zip(tus, keep) if k]
     order = rng.permutation(len(tus))

@@ -46,7 +46,11 @@ def main():
     print("%-60s %5s %5s %6s %7s %8s" % ("kernel", "vgpr", "agpr", "spill", "LDS", "scratch"))
     for r in rows:
         nm = subprocess.run(["c++filt", r["name"]], capture_output=True, text=True).stdout.strip()
-        nm = re.sub(r"\(.*", "", nm).replace("(anonymous namespace)::", "")
+        nm = re.sub(r"\(.*|^void ", "", nm.replace("(anonymous namespace)::", ""))     # the namespace first: its "(" is not the argument list
+        m = re.match(r"_ZN12_GLOBAL__N_1(\d+)", nm)                              # c++filt gave up (a _Float16 parameter): the name and its integer template arguments
+        if m:
+            end = m.end() + int(m.group(1))
+            nm = nm[m.end():end] + "".join("<%s>" % ", ".join(re.findall(r"L[ib](\d+)E", t)) for t in re.findall(r"^I((?:L[ib]\d+E)+)E", nm[end:]))
         if flt in nm:
             print("%-60s %5s %5s %6s %7s %8s" % (nm[:60], r.get("vgpr_count"), r.get("agpr_count"), r.get("vgpr_spill_count"), r.get("group_segment_fixed_size"),
                                                 r.get("private_segment_fixed_size")))

@@ -43,7 +43,7 @@ int vvcgpu_no_mfma(void);
 // eager construction of the per-device table images (vvcgpu_warmup, lib.hip): each returns VVCGPU_OK or an error code with the text set
 int vvcgpu_mc_image_build(int bit_depth);          // interp.hip
 int vvcgpu_frac_image_build(int bit_depth);        // fracsearch.hip
-int vvcgpu_tr_image_build(void);                   // resichain.hip (transform tables + f16 image)
+int vvcgpu_tr_image_build(void);                   // resichain.hip (the tables of transform.hip + f16 image)
 int vvcgpu_cu_count(void);                         // compute units of the current device (queried once per device; 256 if the query fails)
 constexpr int VVC_CTR_INTS = 32;                       // ints per counter set of vvcgpu_counters
 int* vvcgpu_counters(hipStream_t stream, int* cur);     // two persistent zeroed work counters per (device, stream), see lib.hip
@@ -67,8 +67,10 @@ int vvcgpu_raster_per_block_launch(const vvc_pel* org, int org_stride, const vvc
                                    const vvcgpu_mvcost* mvcost_host, vvcgpu_search_best* best, unsigned* packed_workspace, hipStream_t stream);
 
 // device addresses (current device) of the transform matrices as int32 (tr32[type][size] row-major T[k][n] at type * 5460 + (n n - 4) / 3, tr32t its
-// transpose), of the raster position -> scan index tables (dqInv + scanOff[(log2 w - 1) * 6 + log2 h - 1]); uploaded on first use (transform.hip)
-struct VvcTrTables { const int* tr32; const int* tr32t; const unsigned short* dqInv; const int* scanOff; };
+// transpose), of the coefficient scans and their inverse, raster position -> scan index (scan / dqInv + scanOff[(log2 w - 1) * 6 + log2 h - 1]) and of the
+// shape-only part of the trellis' position records (dqPosSel, dqPosMisc: same offsets).  Defined and uploaded, on first use, in transform.hip alone; device
+// code is compiled per source, so the kernels of every other source (resichain.hip, quant.hip, depquant.hip, rdoq.hip) take this struct as an argument.
+struct VvcTrTables { const int* tr32; const int* tr32t; const unsigned short* scan; const unsigned short* dqInv; const int* scanOff; const uint4* dqPosSel; const uint2* dqPosMisc; };
 int vvcgpu_tr_tables(VvcTrTables* out);
 
 #define VVC_CHECK_ARG(cond, ...)                                   \
@@ -121,6 +123,7 @@ static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
 __device__ __forceinline__ int clip3(int lo, int hi, int v) { return min(max(v, lo), hi); }
 __device__ __forceinline__ int sgn(int v) { return (v > 0) - (v < 0); }
+__device__ __forceinline__ int ilog2(int v) { return 31 - __clz(v); }
 
 // 8 Pels = 16 bytes, the coalescing sweet spot for int16 planes (guide G13)
 typedef short pel8 __attribute__((ext_vector_type(8)));

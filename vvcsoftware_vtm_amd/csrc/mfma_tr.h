@@ -34,6 +34,7 @@ __device__ __forceinline__ int rc_tab_off(int type, int n, int transposed)
 }
 // the image (built once per device in global memory, resichain.hip) as a device pointer; nullptr + error text on failure
 const _Float16* vvcgpu_mfma_image(const VvcTrTables& tb);
+int vvcgpu_tr_images(VvcTrTables* tb, const _Float16** image);            // the tables and that image; VVCGPU_OK or an error code with the text set
 
 // copies the matrices a TU size needs: sizes 16 / 32: the T and T^T copies of that size for the three types; 64: the DCT-II pair
 template <int N>

@@ -5,25 +5,19 @@
 // The forward form is a closed loop: every sample's delta is taken against the RECONSTRUCTED running sum, so a line (a column for vertical, a row
 // for horizontal DPCM) is a serial chain; the lines of a TU and the TUs of a batch are independent: one wave per TU, one lane per line.
 #include "common.h"
+#include "quant_dev.h"
 
 namespace {
 
-__device__ __forceinline__ int ilog2(int v) { return 31 - __clz(v); }
-
-struct TsQ { int transformShift, qBits, scale, invScale, rightShift, inMin, inMax; long long add; };
+struct TsQ { int transformShift; VqFwd f; VqInv i; };
 
 __device__ __forceinline__ TsQ ts_params(int w, int h, int qp, int bd, bool halfRound, bool intraSlice)
 {
+  // the transform-skip quantiser of the reference applies no sqrt-2 correction (:942, :1000); add: evaluated in 64 bits, stored as int there (:945): fits
   TsQ q;
-  const int per = qp / 6, rem = qp - 6 * per;
-  q.transformShift = 15 - bd - ((ilog2(w) + ilog2(h)) >> 1);                // getTransformShift, maxLog2TrDynamicRange 15 (ChromaFormat.h:117-120)
-  q.qBits = 14 + per + q.transformShift;                                    // QUANT_SHIFT + per + shift (:942)
-  q.scale = rem == 0 ? 26214 : rem == 1 ? 23302 : rem == 2 ? 20560 : rem == 3 ? 18396 : rem == 4 ? 16384 : 14564;
-  q.add = (long long)(halfRound ? 256 : (intraSlice ? 171 : 85)) << (q.qBits - 9);       // (:945; evaluated in 64 bits, stored as int there: fits)
-  q.invScale = rem == 0 ? 40 : rem == 1 ? 45 : rem == 2 ? 51 : rem == 3 ? 57 : rem == 4 ? 64 : 72;
-  q.rightShift = 6 - (q.transformShift + per);                              // IQUANT_SHIFT - (shift + per) (:1003)
-  const int targetBits = min(16, 32 + q.rightShift - 7);                    // (:1050)
-  q.inMin = -(1 << (targetBits - 1)); q.inMax = (1 << (targetBits - 1)) - 1;
+  q.transformShift = vq_transform_shift(bd, ilog2(w), ilog2(h));
+  q.f = vq_fwd(qp, q.transformShift, false, halfRound ? 256 : vq_round9(intraSlice));
+  q.i = vq_inv(qp, q.transformShift, false);
   return q;
 }
 // transformSkipQuantOneSample (:947-975)
@@ -31,17 +25,17 @@ __device__ __forceinline__ int ts_quant_one(const TsQ& q, int resiDiff)
 {
   const int tc = q.transformShift >= 0 ? resiDiff << q.transformShift : (resiDiff + (1 << (-q.transformShift - 1))) >> -q.transformShift;
   const int sign = tc < 0 ? -1 : 1;
-  const long long tmp = (long long)abs(tc) * q.scale;
-  const int lv = (int)((tmp + (int)q.add) >> q.qBits) * sign;
+  const long long tmp = (long long)abs(tc) * q.f.scale;
+  const int lv = (int)((tmp + (int)q.f.add) >> q.f.qBits) * sign;
   return min(max(lv, -32768), 32767);
 }
 // invTrSkipDeQuantOneSample (:1046-1090): Intermediate_Int is `int` (TypeDef.h:374): the products wrap in 32 bits like the reference's
 __device__ __forceinline__ short ts_dequant_one(const TsQ& q, int level)
 {
-  const int c = min(max(level, q.inMin), q.inMax);
+  const int c = min(max(level, q.i.inMin), q.i.inMax);
   int v;
-  if (q.rightShift > 0) v = (int)((unsigned)(c * q.invScale) + (1u << (q.rightShift - 1))) >> q.rightShift;
-  else v = (int)((unsigned)(c * q.invScale) << -q.rightShift);
+  if (q.i.rightShift > 0) v = (int)((unsigned)(c * q.i.scale) + (1u << (q.i.rightShift - 1))) >> q.i.rightShift;
+  else v = (int)((unsigned)(c * q.i.scale) << -q.i.rightShift);
   v = min(max(v, -32768), 32767);
   if (q.transformShift >= 0) return (short)((v + (q.transformShift == 0 ? 0 : 1 << (q.transformShift - 1))) >> q.transformShift);
   return (short)(v << -q.transformShift);

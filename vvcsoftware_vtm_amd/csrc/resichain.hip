@@ -24,6 +24,7 @@
 // of lanes holds a 4x4 coefficient group: sign bit hiding is decided per quad with DPP quad permutes.
 #include "common.h"
 #include "mfma_tr.h"
+#include "quant_dev.h"
 
 namespace {
 // Pointer arguments of functions that are NOT inlined arrive as generic pointers: every access through them is a FLAT instruction (both wait counters, no
@@ -38,7 +39,6 @@ namespace {
 
 typedef vvcgpu_resi_chain_desc RcDesc;
 
-__device__ __forceinline__ int ilog2(int v) { return 31 - __clz(v); }
 #define RC_WAVE_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); } while (0)
 
 // ---- work lists (device): hdr[0 .. RC_NCLS) = counts of the classes, hdr[RC_FB] = count of the fall-back list
@@ -170,31 +170,24 @@ __global__ __launch_bounds__(1024) void rc_classify_kernel(const void* __restric
 }
 
 // ---------------------------------------------------------------------------------------------------
-// Quantiser / de-quantiser of one TU (flat scaling lists)
+// Quantiser / de-quantiser of one TU (flat scaling lists), filled from quant_dev.h
 struct RcQ
 {
   unsigned mul;                       // quantiser scale * (181 for 2:1 shapes)
   int qBits, qBits8;
   long long add;
-  int dqScale, rightShift, inMin, inMax;
+  VqInv dq;
   bool sbh;
 };
 __device__ __forceinline__ RcQ rc_qparams(int w, int h, int qp, int bd, int intraSlice, int signHiding)
 {
   RcQ q;
-  const int lw = ilog2(w), lh = ilog2(h), per = qp / 6, rem = qp - 6 * per;
-  const int transformShift = 15 - bd - ((lw + lh) >> 1);
-  const bool sqrt2 = ((lw + lh) & 1) != 0;
-  const int scale = rem == 0 ? 26214 : rem == 1 ? 23302 : rem == 2 ? 20560 : rem == 3 ? 18396 : rem == 4 ? 16384 : 14564;
-  q.mul = (unsigned)scale * (sqrt2 ? 181u : 1u);
-  q.qBits = 14 + per + transformShift + (sqrt2 ? 7 : 0);
-  q.qBits8 = q.qBits - 8;
-  q.add = (long long)(intraSlice ? 171 : 85) << (q.qBits - 9);
-  const int invq = rem == 0 ? 40 : rem == 1 ? 45 : rem == 2 ? 51 : rem == 3 ? 57 : rem == 4 ? 64 : 72;
-  q.dqScale = invq * (sqrt2 ? 181 : 1);
-  q.rightShift = (sqrt2 ? 8 : 0) + (6 - (transformShift + per));
-  const int targetBits = min(16, 32 + q.rightShift - 7);
-  q.inMin = -(1 << (targetBits - 1)); q.inMax = (1 << (targetBits - 1)) - 1;
+  const int lw = ilog2(w), lh = ilog2(h), transformShift = vq_transform_shift(bd, lw, lh);
+  const bool sqrt2 = vq_sqrt2(lw, lh);
+  const VqFwd f = vq_fwd(qp, transformShift, sqrt2, vq_round9(intraSlice));
+  q.mul = (unsigned)f.scale * (unsigned)f.whScale;
+  q.qBits = f.qBits; q.qBits8 = f.qBits8; q.add = f.add;
+  q.dq = vq_inv(qp, transformShift, sqrt2);
   q.sbh = signHiding && w >= 4 && h >= 4;
   return q;
 }
@@ -208,12 +201,7 @@ __device__ __forceinline__ int rc_quant_one(const RcQ& q, int c, int& deltaU, in
   deltaU = (int)((long long)(tmp - ((unsigned long long)(unsigned)mag << q.qBits)) >> q.qBits8);
   return min(max(c < 0 ? -mag : mag, -32768), 32767);
 }
-__device__ __forceinline__ int rc_dequant_one(const RcQ& q, int lv)
-{
-  const long long c = min(max(lv, q.inMin), q.inMax);
-  const long long v = q.rightShift > 0 ? (c * q.dqScale + (1ll << (q.rightShift - 1))) >> q.rightShift : (c * q.dqScale) << -q.rightShift;
-  return (int)min(max(v, -32768ll), 32767ll);
-}
+__device__ __forceinline__ int rc_dequant_one(const RcQ& q, int lv) { return vq_dequant_one(q.dq, lv); }
 
 __device__ __forceinline__ unsigned quad_or(unsigned v)
 {
@@ -253,7 +241,7 @@ __device__ __forceinline__ bool rc_cg_nonzero(const int (&lv)[4])
   return quad_or((unsigned)((lv[0] | lv[1] | lv[2] | lv[3]) != 0)) != 0u;
 }
 
-// Sign bit hiding of one coefficient group (xSignBitHidingHDQ, Quant.cpp:142-273; logic as quant_tu in transform.hip, which is pinned against
+// Sign bit hiding of one coefficient group (xSignBitHidingHDQ, Quant.cpp:142-273; logic as quant_tu in quant.hip, which is pinned against
 // the reference): the lane holds rows 0..3 of column x = lane & 3 of the group; cf = coefficients, du = the quantiser's deltaU.
 __device__ __forceinline__ void rc_sbh_quad(int (&lv)[4], const int (&du)[4], const int (&cf)[4], bool isLast, int lane)
 {
@@ -2247,12 +2235,18 @@ const _Float16* vvcgpu_mfma_image(const VvcTrTables& tb)
   return vvcgpu_device_image(VVC_IMAGE_TR_F16, (size_t)RC_IMG_U4 * 16, mfma_image_build, &tb, &p) == VVCGPU_OK ? static_cast<const _Float16*>(p) : nullptr;
 }
 
+// the tables of the current device (transform.hip) and the f16 image built from them, each made by its first user
+__attribute__((visibility("hidden"))) int vvcgpu_tr_images(VvcTrTables* tb, const _Float16** image)
+{
+  const int rt = vvcgpu_tr_tables(tb);
+  if (rt) return rt;
+  *image = vvcgpu_mfma_image(*tb);
+  return *image ? VVCGPU_OK : VVCGPU_E_DEVICE;
+}
 __attribute__((visibility("hidden"))) int vvcgpu_tr_image_build(void)
 {
-  VvcTrTables tb;
-  const int rt = vvcgpu_tr_tables(&tb);
-  if (rt) return rt;
-  return vvcgpu_mfma_image(tb) ? VVCGPU_OK : VVCGPU_E_DEVICE;
+  VvcTrTables tb; const _Float16* image = nullptr;
+  return vvcgpu_tr_images(&tb, &image);
 }
 
 // the classify / chain / generic launches behind vvcgpu_resi_chain_batch (mode RC_CHAIN) and, for long calls, behind vvcgpu_tr_fwd_batch /
@@ -2260,11 +2254,9 @@ __attribute__((visibility("hidden"))) int vvcgpu_tr_image_build(void)
 static int rc_chain_launch(int mode, const vvc_pel* org_base, const vvc_pel* pred_base, vvc_pel* rec_base, vvc_coef* level_base, const void* descs_raw, int n,
                            int bit_depth, int clp_min, int clp_max, uint32_t* abs_sum, hipStream_t st, const RcBins* runs = nullptr)
 {
-  VvcTrTables tb;
-  const int rt = vvcgpu_tr_tables(&tb);
+  VvcTrTables tb; const _Float16* image = nullptr;
+  const int rt = vvcgpu_tr_images(&tb, &image);
   if (rt) return rt;
-  const _Float16* image = vvcgpu_mfma_image(tb);
-  if (!image) return VVCGPU_E_DEVICE;
   // scratch: the class lists, (plain transforms) the descriptors as chain descriptors, and per wave of the chain launch two 4096-int buffers for a TU its
   // body cannot take (rc_fallback_call: touched only then)
   constexpr int CHAIN_WGS = 768;

@@ -1,4 +1,7 @@
-// transform.hip -- 2-D separable integer transforms (T1 forward, T2 inverse, T3 transform skip) for gfx950.
+// transform.hip -- 2-D separable integer transforms (T1 forward, T2 inverse, T3 transform skip) for gfx950; the de-quantiser fused in front of the inverse
+// transform (vvcgpu_dequant_tr_inv_batch: it reuses the lane-group tables, the int16 matrix loader and the inverse bodies below); and the ONE definition and
+// upload of the device tables (transform matrices, coefficient scans, the trellis' position records), whose addresses vvcgpu_tr_tables hands to the kernels
+// of the other sources.  The quantisers live in quant.hip, depquant.hip and rdoq.hip, their shared arithmetic in quant_dev.h.
 //
 // Reference behaviour reproduced (bit-exact): xTrMxN_EMT / xITrMxN_EMT (CommonLib/TrQuant.cpp:138-310) with the 1-D
 // stages of TrQuant_EMT.cpp expressed as integer matrix products with the reference's own tables (tr_tables.inc, dumped
@@ -17,6 +20,7 @@
 //     each lane group reading the rows of its own TU's transform types (same-address reads broadcast).
 #include "common.h"
 #include "mfma_tr.h"
+#include "quant_dev.h"
 #include "tr_tables.inc"
 
 // resichain.hip: the chain's bodies as plain transforms (mode 1 forward, 2 inverse): ONE launch with packed matrix-core tiles for long calls
@@ -31,7 +35,6 @@ __device__ int d_tr32t[3 * 5460];
 
 __device__ __forceinline__ const int* tr32(int type, int n)  { return d_tr32  + type * 5460 + (n * n - 4) / 3; }
 __device__ __forceinline__ const int* tr32t(int type, int n) { return d_tr32t + type * 5460 + (n * n - 4) / 3; }
-__device__ __forceinline__ int ilog2(int v) { return 31 - __clz(v); }
 
 constexpr int MAXN = 64;
 // address-space-qualified views: behind a real call a plain pointer is a FLAT pointer -- every LDS access becomes a flat_load / flat_store that the
@@ -42,8 +45,6 @@ typedef __attribute__((address_space(1))) int GlbInt;
 typedef __attribute__((address_space(1))) short GlbPel;
 
 typedef short short2v __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ bool is_large_tu(const vvcgpu_tr_desc& d) { return d.tr_hor != 3 && (d.w > 16 || d.h > 16); }
 
 // ---------------------------------------------------------------------------------------------------
 // Small TUs (w, h <= 16) and transform skip: 64 descriptors per 256-thread workgroup, binned in LDS.
@@ -165,8 +166,8 @@ __global__ __launch_bounds__(256) void tr_fwd_small_kernel(const Pel* __restrict
   {
     const vvcgpu_tr_desc& d = sh.d[sh.list[0][q]];
     const int w = d.w, h = d.h, lw = ilog2(w), lh = ilog2(h);
-    int shift = 15 - bd - ((lw + lh) >> 1), scale = 1;
-    if ((lw + lh) & 1) { shift -= 8; scale = 181; }
+    int shift = vq_transform_shift(bd, lw, lh), scale = 1;
+    if (vq_sqrt2(lw, lh)) { shift -= 8; scale = 181; }
     const Pel* resi = resiBase + d.resi_off;
     TCoeff* coeff = coeffBase + d.coeff_off;
     for (int i = tid; i < w * h; i += 256)
@@ -249,8 +250,8 @@ __global__ __launch_bounds__(256) void tr_inv_small_kernel(const TCoeff* __restr
   {
     const vvcgpu_tr_desc& d = sh.d[sh.list[0][q]];
     const int w = d.w, h = d.h, lw = ilog2(w), lh = ilog2(h);
-    int shift = 15 - bd - ((lw + lh) >> 1), scale = 1;
-    if ((lw + lh) & 1) { shift += 7; scale = 181; }
+    int shift = vq_transform_shift(bd, lw, lh), scale = 1;
+    if (vq_sqrt2(lw, lh)) { shift += 7; scale = 181; }
     const TCoeff* coeff = coeffBase + d.coeff_off;
     Pel* resi = resiBase + d.resi_off;
     for (int i = tid; i < w * h; i += 256)
@@ -755,70 +756,48 @@ __global__ __launch_bounds__(1024) void tr_collect_large_kernel(const vvcgpu_tr_
 }
 
 // ---------------------------------------------------------------------------------------------------
-// N1: de-quantisation in front of the inverse transform (vvcgpu_dequant_tr_inv_batch).
-//   Quant::dequant (Quant.cpp:277-428, flat scaling): an element-wise map.
-//   Dependent quantisation (DepQuant.cpp:708-785): the reconstruction level of a coefficient depends on a 4-state
-//   machine driven by the parities of the levels before it in (reverse) scan order.  The transition of one level is a
-//   map {0..3} -> {0..3} (8 bits); maps compose associatively, so a wave walks the scan in 64 contiguous chunks: every lane
-//   composes the maps of its chunk, an inclusive wave scan of the composed maps gives each lane its entry state, and a
-//   second walk reconstructs the levels.  (Zero levels above the last significant one keep state 0, so the walk can
-//   start at the end of the scan instead of searching the last level as the reference does.)
+// The scan tables: defined and uploaded here only (upload_tables); the kernels of the other sources get their addresses as arguments (vvcgpu_tr_tables).
 __device__ unsigned short d_scan[15876];            // diagonal 4x4-grouped scans of all W x H in 2..64, [log2 w - 1][log2 h - 1]
 __device__ int d_scanOff[36];
-
-__device__ __forceinline__ unsigned dq_compose(unsigned first, unsigned then)     // map applied first, then the second one
-{
-  unsigned r = 0;
-#pragma unroll
-  for (int s = 0; s < 4; s++) r |= ((then >> (2 * ((first >> (2 * s)) & 3))) & 3) << (2 * s);
-  return r;
-}
+__device__ unsigned short d_dqInv[15876];           // raster position -> scan id, same layout as d_scan
+// What a position record of the trellis (TqRec, depquant.hip) holds that depends on the TU's SHAPE only, per scan id si, for the
+// position AFTER si in the walk (scan id max(si - 1, 0)): the byte selectors of its five template neighbours inside the sub-block
+// and the word (neighbour positions 5 x 4 bits | sigOff << 20 | gtxOff << 24) for luma (.x) and chroma (.y).
+__device__ uint4 d_dqPosSel[15876];
+__device__ uint2 d_dqPosMisc[15876];
 
 // ---------------------------------------------------------------------------------------------------
-// N1 in ONE launch: de-quantiser and inverse transform of a TU in the same wave, the de-quantised coefficients in LDS (the separate form above
+// N1: de-quantisation in front of the inverse transform (vvcgpu_dequant_tr_inv_batch).
+//   Quant::dequant (Quant.cpp:277-428, flat scaling): an element-wise map (vq_dequant_one, quant_dev.h).
+//   Dependent quantisation (DepQuant.cpp:708-785): the reconstruction level of a coefficient depends on a 4-state
+//   machine driven by the parities of the levels before it in (reverse) scan order (dq_group below).
+
+// ---------------------------------------------------------------------------------------------------
+// N1 in ONE launch: de-quantiser and inverse transform of a TU in the same wave, the de-quantised coefficients in LDS (a separate form
 // wrote them to a workspace in HBM and read them back in a second and third launch).  A workgroup takes `per` consecutive descriptors and serves
 // them in phases: transform skip and the lane-group sizes (<= 16), then the matrix-core shapes, then the remaining large shapes; the tables of
 // the phases share one LDS region and are reloaded only when a workgroup's phase changes (homogeneous batches: never).
 struct DqP
 {
-  int dep, rightShift, shift;
-  long long scale, inMin, inMax, invQScale, add;
+  int dep, shift;
+  VqInv flat;                                                // the scalar de-quantiser (dep == 0)
+  long long invQScale, add;                                  // dependent quantisation: scale and shift of qp + 1 with one more bit (DepQuant.cpp:758-759)
 };
 __device__ __forceinline__ DqP dq_params(const vvcgpu_dqtr_desc& d, int bd, int lw, int lh)
 {
   DqP q;
-  const int transformShift = 15 - bd - ((lw + lh) >> 1);
-  const bool sqrt2 = ((lw + lh) & 1) != 0;
+  const int transformShift = vq_transform_shift(bd, lw, lh);
+  const bool sqrt2 = vq_sqrt2(lw, lh);
   q.dep = d.dep_quant;
-  {
-    const int per = d.qp / 6, rem = d.qp - 6 * per;
-    q.rightShift = (sqrt2 ? 8 : 0) + (6 - (transformShift + per));
-    const int invq = rem == 0 ? 40 : rem == 1 ? 45 : rem == 2 ? 51 : rem == 3 ? 57 : rem == 4 ? 64 : 72;
-    q.scale = (long long)invq * (sqrt2 ? 181 : 1);
-    const int targetBits = min(16, 32 + q.rightShift - 7);
-    q.inMin = -(1ll << (targetBits - 1)); q.inMax = (1ll << (targetBits - 1)) - 1;
-  }
-  {
-    const int qpDQ = d.qp + 1, qpPer = qpDQ / 6, qpRem = qpDQ - 6 * qpPer;
-    int shift = 6 + 1 - qpPer - transformShift + (sqrt2 ? 8 : 0);
-    const int invq = qpRem == 0 ? 40 : qpRem == 1 ? 45 : qpRem == 2 ? 51 : qpRem == 3 ? 57 : qpRem == 4 ? 64 : 72;
-    long long s = (long long)invq * (sqrt2 ? 181 : 1);
-    if (shift < 0) { s <<= -shift; shift = 0; }
-    q.invQScale = s; q.shift = shift; q.add = (1ll << shift) >> 1;
-  }
+  q.flat = vq_inv(d.qp, transformShift, sqrt2);
+  const VqInv dep = vq_inv(d.qp + 1, transformShift, sqrt2);
+  int shift = dep.rightShift + 1;
+  long long s = dep.scale;
+  if (shift < 0) { s <<= -shift; shift = 0; }
+  q.invQScale = s; q.shift = shift; q.add = (1ll << shift) >> 1;
   return q;
 }
-__device__ __forceinline__ int dq_scalar(const DqP& q, int lv)
-{
-  const long long c = min(max((long long)lv, q.inMin), q.inMax);
-  const long long v = q.rightShift > 0 ? (c * q.scale + (1ll << (q.rightShift - 1))) >> q.rightShift : (c * q.scale) << -q.rightShift;
-  return (int)min(max(v, -(1ll << 15)), (1ll << 15) - 1);
-}
 
-// De-quantises one TU with a group of L lanes (L = 4, 8, 16: L TUs ... 64 / L TUs side by side in the wave; L = 64: the whole wave).  lig = lane
-// index inside the group; act = the group has a TU (all lanes of the wave must call: the scan uses shuffles).  The levels of the kept region
-// (x < wj, y < hj) are first staged in `stage` (LDS, row pitch wj); levels outside it (64-wide / 64-high TUs only) are read from memory.
-// `sink(pos, x, y, v)` receives every de-quantised coefficient (pos = raster index y w + x), each exactly once.
 // position of a scan index without the table (host_scan_order below is the definition): coefficient groups of g x g (g = 4, or 2 when a side is 2)
 // in up-right diagonal order over the gw x gh grid, the same order inside a group.  dq_cg: group index -> (gy << 8 | gx).
 __device__ __forceinline__ int dq_cg(int c, int gw, int gh)
@@ -876,7 +855,7 @@ __device__ __forceinline__ void dq_group(const vvcgpu_dqtr_desc& d, const TCoeff
       const int y = pos >> lw, x = pos & (w - 1);
       const bool in = x < wj && y < hj;
       const int lv = in ? stage[y * wj + x] : level[pos];
-      sink(pos, x, y, dq_scalar(q, lv));
+      sink(pos, x, y, vq_dequant_one(q.flat, lv));
     }
   }
   const bool dep = act && q.dep;
@@ -1034,8 +1013,8 @@ __device__ __noinline__ void dq_ts_tu(const vvcgpu_dqtr_desc& d, const TCoeff* _
                                       int bd, int lane, int* coefW)
 {
   const int lw = ilog2(d.w), lh = ilog2(d.h);
-  int shift = 15 - bd - ((lw + lh) >> 1), scale = 1;
-  if ((lw + lh) & 1) { shift += 7; scale = 181; }
+  int shift = vq_transform_shift(bd, lw, lh), scale = 1;
+  if (vq_sqrt2(lw, lh)) { shift += 7; scale = 181; }
   GlbPel* resi = (GlbPel*)(resiBase + d.resi_off);
   GlbInt* out = coeffOut ? (GlbInt*)(coeffOut + d.level_off) : nullptr;
   const int stride = d.resi_stride;
@@ -1236,1111 +1215,6 @@ __global__ __launch_bounds__(256, 2) void dqtr_fused_kernel(const TCoeff* __rest
   }
 }
 
-// ---- forward scalar quantisation without RDOQ: Quant::quant (Quant.cpp:721-834) + xSignBitHidingHDQ (:142-273) ---------------
-// Without sign hiding the map is element-wise.  With it, the coefficient groups (16 coefficients in scan order) are independent
-// once the TU's abs-sum and its last group with a level are known: pass 1 finds both, pass 2 decides every group's adjustment.
-struct QuantParams { int qBits, qBits8, scale, whScale; long long add; };
-
-__device__ __forceinline__ int quant_one(const QuantParams& q, int c, int& deltaU)
-{
-  const long long tmp = (long long)abs(c) * q.scale * q.whScale;
-  const int mag = (int)((tmp + q.add) >> q.qBits);
-  deltaU = (int)((tmp - ((long long)mag << q.qBits)) >> q.qBits8);
-  return mag;
-}
-
-// TUs of up to 256 coefficients are handled by 16 lanes each, four side by side in a wavefront (a step = one coefficient group of
-// each; most of a picture's TUs are small, so this fills the lanes and shares the set-up); larger TUs take the whole wavefront
-// (four coefficient groups per step).
-template <bool LARGE>
-__device__ __forceinline__ void quant_tu(const TCoeff* __restrict__ coeffBase, TCoeff* __restrict__ levelBase, const vvcgpu_quant_desc& d, bool live,
-                                         int ti, int bd, unsigned* __restrict__ absSumOut, int lane)
-{
-  constexpr int LPT = LARGE ? 64 : 16;
-  const int k = lane & 15, slot = lane >> 4, tl = lane & (LPT - 1);
-  const int w = d.w, h = d.h, cnt = live ? w * h : 0, lw = ilog2(w), lh = ilog2(h);
-  const TCoeff* coef = coeffBase + d.coeff_off;
-  TCoeff* level = levelBase + d.level_off;
-  QuantParams q;
-  {
-    const int per = d.qp / 6, rem = d.qp - 6 * per;
-    int transformShift = 15 - bd - ((lw + lh) >> 1);
-    q.whScale = 1;
-    if ((lw + lh) & 1) { transformShift += 7; q.whScale = 181; }
-    q.qBits = 14 + per + transformShift; q.qBits8 = q.qBits - 8;
-    q.scale = rem == 0 ? 26214 : rem == 1 ? 23302 : rem == 2 ? 20560 : rem == 3 ? 18396 : rem == 4 ? 16384 : 14564;
-    q.add = (long long)(d.intra_slice ? 171 : 85) << (q.qBits - 9);
-  }
-  const bool sbh = d.sign_hiding && w >= 4 && h >= 4;
-  const unsigned short* scan = d_scan + d_scanOff[(lw - 1) * 6 + (lh - 1)];
-  int maxCnt = cnt;                                         // the wavefront runs as many steps as its largest TU needs
-#pragma unroll
-  for (int m = LPT; m < 64; m <<= 1) maxCnt = max(maxCnt, __shfl_xor(maxCnt, m));
-  if (maxCnt == 0) return;
-  int sum = 0;
-  if (!sbh || !live)
-  {
-    // element-wise (sign hiding off): levels are final
-    for (int s0 = 0; s0 < maxCnt; s0 += LPT)
-    {
-      const int si = s0 + tl;
-      if (si < cnt && !sbh)
-      {
-        int du; const int c = coef[si];
-        const int mag = quant_one(q, c, du);
-        sum += mag;
-        level[si] = min(max(c < 0 ? -mag : mag, -32768), 32767);
-      }
-    }
-  }
-  // Sign hiding, ONE pass from the end of the scan: the first coefficient group met with a level is the reference's "last" group
-  // (:183-186), every other group searches all 16 positions.  The reference hides only if uiAbsSum >= 2; a group that qualifies
-  // (last - first >= 4) has two levels, so the test can only fail when the 32-bit sum wrapped -- handled after the loop.
-  // 16 lanes per coefficient group; the sequential search for the cheapest parity fix (:196-262, the highest scan position wins
-  // ties) is a 16-lane min over (cost, -position).
-  bool foundLast = false, fixedAny = false;
-  const int steps = (maxCnt + LPT - 1) / LPT;
-  for (int st = steps - 1; st >= 0; st--)
-  {
-    const int si = st * LPT + tl;
-    const bool in = sbh && live && si < cnt;
-    const int pos = in ? scan[si] : 0;
-    const int c = in ? coef[pos] : 0;
-    int du;
-    const int mag = quant_one(q, c, du);
-    sum += in ? mag : 0;
-    int lv = min(max(c < 0 ? -mag : mag, -32768), 32767);
-    const unsigned long long nzAll = __ballot(lv != 0);
-    const unsigned nz = (unsigned)((nzAll >> (16 * slot)) & 0xFFFFull);
-    // is this lane's group the last one with a level?  no earlier-met (= later in scan order) group of this TU had one
-    bool isLast;
-    if (LARGE)
-    {
-      const unsigned long long higher = slot == 3 ? 0ull : (nzAll >> (16 * (slot + 1)));
-      isLast = !foundLast && nz != 0 && higher == 0ull;
-      foundLast = foundLast || nzAll != 0ull;
-    }
-    else { isLast = !foundLast && nz != 0; foundLast = foundLast || nz != 0; }
-    const int first = nz ? __ffs((int)nz) - 1 : 16, last = nz ? 31 - __clz((int)nz) : -1;
-    int ssum = lv;
-#pragma unroll
-    for (int m = 1; m < 16; m <<= 1) ssum += __shfl_xor(ssum, m);
-    const int firstLv = __shfl(lv, (lane & 48) + (first & 15));
-    const unsigned signbit = firstLv > 0 ? 0u : 1u;
-    const bool fix = last - first >= 4 && signbit != (unsigned)(ssum & 1);
-    const int start = isLast ? last : 15;
-    const int TMAX = 0x7fffffff;
-    int cost = TMAX, change = 0;
-    if (k <= start)
-    {
-      if (lv != 0)
-      {
-        if (du > 0) { cost = -du; change = 1; }
-        else if (!(k == first && abs(lv) == 1)) { cost = du; change = -1; }
-      }
-      else if (k < first) { if ((c >= 0 ? 0u : 1u) == signbit) { cost = -du; change = 1; } }
-      else { cost = -du; change = 1; }
-    }
-    long long key = ((long long)cost << 5) + (15 - k);
-#pragma unroll
-    for (int m = 1; m < 16; m <<= 1) { const long long o = __shfl_xor(key, m); key = min(key, o); }
-    if (fix && k == 15 - (int)(key & 31))
-    {
-      if (lv == 32767 || lv == -32768) change = -1;
-      lv += c >= 0 ? change : -change;
-    }
-    fixedAny = fixedAny || (fix && in);
-    if (in) level[pos] = lv;
-  }
-#pragma unroll
-  for (int m = 1; m < LPT; m <<= 1) sum += __shfl_xor(sum, m);
-  if (live && tl == 0) absSumOut[ti] = (unsigned)sum;
-  // uiAbsSum is a 32-bit int in the reference: if it wrapped below 2 no hiding happened there -- rewrite the plain levels
-  if (sbh && live && sum < 2 && __ballot(fixedAny) != 0ull)
-    for (int s0 = 0; s0 < cnt; s0 += LPT)
-    {
-      const int si = s0 + tl;
-      if (si < cnt) { int du; const int c = coef[si]; const int mag = quant_one(q, c, du); level[si] = min(max(c < 0 ? -mag : mag, -32768), 32767); }
-    }
-}
-
-// two launches: the first takes the small TUs (four per wavefront) and lists the large ones; the second walks that list, one large
-// TU per wavefront at a time (a persistent grid: no empty workgroups for the many small TUs of a picture)
-__global__ __launch_bounds__(256) void quant_small_kernel(const TCoeff* __restrict__ coeffBase, TCoeff* __restrict__ levelBase,
-                                                          const vvcgpu_quant_desc* __restrict__ descs, int n, int bd, unsigned* __restrict__ absSumOut,
-                                                          int* __restrict__ largeList)
-{
-  const int lane = threadIdx.x & 63;
-  const int ti = (blockIdx.x * 4 + (threadIdx.x >> 6)) * 4 + (lane >> 4);
-  const vvcgpu_quant_desc d = descs[ti < n ? ti : n - 1];
-  const bool large = (int)d.w * d.h > 256;
-  if (ti < n && large && (lane & 15) == 0) largeList[1 + atomicAdd(&largeList[0], 1)] = ti;
-  const bool live = ti < n && !large;
-  if (__ballot(live) == 0ull) return;
-  quant_tu<false>(coeffBase, levelBase, d, live, ti, bd, absSumOut, lane);
-}
-
-__global__ __launch_bounds__(256) void quant_large_kernel(const TCoeff* __restrict__ coeffBase, TCoeff* __restrict__ levelBase,
-                                                          const vvcgpu_quant_desc* __restrict__ descs, int bd, unsigned* __restrict__ absSumOut,
-                                                          const int* __restrict__ largeList)
-{
-  const int lane = threadIdx.x & 63;
-  const int count = largeList[0], waves = gridDim.x * 4;
-  for (int i = blockIdx.x * 4 + (threadIdx.x >> 6); i < count; i += waves)
-  {
-    const int ti = largeList[1 + i];
-    const vvcgpu_quant_desc d = descs[ti];
-    quant_tu<true>(coeffBase, levelBase, d, true, ti, bd, absSumOut, lane);
-  }
-}
-
-// ---- dependent-quantisation trellis: DQIntern::DepQuant::quant (DepQuant.cpp:1323-1391) ---------------------------------------
-// The trellis is a sequential walk down the scan with four states; TUs are independent.  FOUR LANES own one TU, lane k carries
-// trellis state k (its previous-position state and its skip state live in the lane's registers), sixteen TUs share a wavefront.
-// Per scan position: every lane prices the transitions LEAVING its state (two quantisation candidates + zero), the three 64-bit
-// costs entering decision k are gathered with quad shuffles in the reference's comparison order (:1222-1249, strict '<'), the
-// winner's template context (16 abs levels + 16 context seeds = 12 dwords) is pulled from the source lane, and the new rates are
-// looked up in the caller's rate tables.  Decisions (absLevel << 4 | prevId + 2) go to the workspace for the back-trace; the
-// per-state sub-block memory of CommonCtx (:828-858) lives in the workspace as well and is touched only at sub-block ends.
-__device__ unsigned short d_dqInv[15876];           // raster position -> scan id, same layout as d_scan
-// What a position record holds that depends on the TU's SHAPE only (built on the host with the scan tables), per scan id si, for the
-// position AFTER si in the walk (scan id max(si - 1, 0)): the byte selectors of its five template neighbours inside the sub-block
-// (DqRec below) and the word (neighbour positions 5 x 4 bits | sigOff << 20 | gtxOff << 24) for luma (.x) and chroma (.y).
-__device__ uint4 d_dqPosSel[15876];
-__device__ uint2 d_dqPosMisc[15876];
-
-// Small per-lane tables are ext-vector VALUES, not arrays: element selects then stay register selects (with arrays LLVM rewrites a
-// select of loads into a load through a selected address, which pins the whole state struct in scratch memory).
-typedef unsigned dq_u4 __attribute__((ext_vector_type(4)));
-typedef unsigned dq_u8 __attribute__((ext_vector_type(8)));
-typedef int dq_i8 __attribute__((ext_vector_type(8)));
-typedef long long dq_l4 __attribute__((ext_vector_type(4)));
-typedef int dq_i4 __attribute__((ext_vector_type(4)));
-
-struct DqState
-{
-  long long rdCost;
-  dq_u4 lev;                          // 16 abs levels of the current sub-block (bytes)
-  dq_u4 aux;                          // per level min(4 - (v & 1), v) | (v != 0) << 5: what it adds to sumAbs1 and sumNum of a template
-  int numSigSbb, refSbbCtxId;         // refSbbCtxId also names the LDS slot with the 16 template-context seeds of the sub-block (-1: all zero)
-  int sbb0, sbb1, sig0, sig1;
-  int gc;                             // row of the greater-than-x rate table (coefficient bit sums [0..6])
-  int goRice;
-};
-
-// member-wise copy: a whole-struct assignment also copies the padding through scratch memory
-__device__ __forceinline__ void dq_copy(DqState& d, const DqState& s)
-{
-  d.rdCost = s.rdCost; d.lev = s.lev; d.aux = s.aux; d.numSigSbb = s.numSigSbb; d.refSbbCtxId = s.refSbbCtxId;
-  d.sbb0 = s.sbb0; d.sbb1 = s.sbb1; d.sig0 = s.sig0; d.sig1 = s.sig1; d.gc = s.gc; d.goRice = s.goRice;
-}
-__device__ __forceinline__ unsigned dq_get_byte(const dq_u4 a, int j)
-{
-  const int d = j >> 2;
-  const unsigned v = d == 0 ? a[0] : d == 1 ? a[1] : d == 2 ? a[2] : a[3];
-  return (v >> ((j & 3) * 8)) & 0xFFu;
-}
-__device__ __forceinline__ void dq_set_byte(dq_u4& a, int j, unsigned val)
-{
-  const int d = j >> 2, sh = (j & 3) * 8;
-#pragma unroll
-  for (int i = 0; i < 4; i++) { const unsigned m = i == d ? 0xFFu << sh : 0u; a[i] = (a[i] & ~m) | ((val << sh) & m); }   // no conditional store: keeps the array in registers
-}
-__device__ __forceinline__ unsigned dq_get_u16(const dq_u8 c, int j)
-{
-  const int d = j >> 1;
-  unsigned v = c[0];
-#pragma unroll
-  for (int i = 1; i < 8; i++) v = d == i ? c[i] : v;
-  return (v >> ((j & 1) * 16)) & 0xFFFFu;
-}
-typedef const __attribute__((address_space(3))) vvcgpu_dq_rates* DqLdsRates;
-__device__ __forceinline__ int dq_level_bits(DqLdsRates rt, int gc, int goRice, unsigned level)       // State::getLevelBits :909-931
-{
-  const unsigned idx = level < 5 ? level : 5 + ((level - 5) & 1);
-  const int bits = rt->gtx[gc][idx];
-  if (level < 5) return bits;
-  // escape part; the prefix loop of :924-929 ends at length = floor(log2(value - thres + 2^goRice))
-  const unsigned value = (level - 5) >> 1;
-  const unsigned range = goRice == 0 ? 6u : goRice == 1 ? 5u : goRice == 2 ? 6u : 3u;              // g_auiGoRiceRange
-  const unsigned thres = range << goRice;
-  const unsigned length = 31u - (unsigned)__clz((int)(value - thres + (1u << goRice)));
-  const unsigned esc = value < thres ? (value >> goRice) + 1 + goRice : range + 1 + (length << 1) - goRice;
-  return bits + (int)(esc << 15);
-}
-__device__ __forceinline__ long long dq_shfl64(long long v, int src) { return __shfl(v, src); }
-// quad permutation with a compile-time pattern (v_mov_b32 dpp quad_perm): no LDS round trip on the cost chain
-template <int CTRL>
-__device__ __forceinline__ long long dq_quad64(long long v)
-{
-  const unsigned lo = (unsigned)__builtin_amdgcn_mov_dpp((int)(unsigned)v, CTRL, 0xF, 0xF, true);
-  const unsigned hi = (unsigned)__builtin_amdgcn_mov_dpp((int)(unsigned)((unsigned long long)v >> 32), CTRL, 0xF, 0xF, true);
-  return (long long)(((unsigned long long)hi << 32) | lo);
-}
-
-template <int CTRL>
-__device__ __forceinline__ unsigned dq_quad32(unsigned v) { return (unsigned)__builtin_amdgcn_mov_dpp((int)v, CTRL, 0xF, 0xF, true); }
-
-// the diagonal scan inside a 4x4 sub-block: scan index of in-block position y * 4 + x, and its inverse (4 bits each)
-constexpr unsigned long long dq_pack_scan4(bool inverse)
-{
-  unsigned long long kof = 0, posof = 0; int k = 0;
-  for (int d = 0; d < 7; d++)
-    for (int y = (d < 3 ? d : 3); y >= 0; y--)
-    {
-      const int x = d - y;
-      if (x > 3) continue;
-      kof |= (unsigned long long)k << (4 * (y * 4 + x)); posof |= (unsigned long long)(y * 4 + x) << (4 * k); k++;
-    }
-  return inverse ? posof : kof;
-}
-constexpr unsigned long long DQ_KOFPOS = dq_pack_scan4(false), DQ_POSOFK = dq_pack_scan4(true);
-
-// What a trellis step needs that does not depend on the trellis state, per scan position: the four quantisation candidates of
-// Quantizer::preQuantCoeff (:786-808), the two "start here" costs (checkRdCostStart :1196-1213: candidate 0 / 2 + last-position bits +
-// level bits in the start context), and for the position AFTER it the in-sub-block template neighbours (:139-168) and its context offsets.
-// The quad fills the sixteen records of a sub-block when the walk enters it (four positions per lane) instead of every lane repeating
-// the same arithmetic at every step: ~250 of a step's ~735 instructions were this.
-struct DqRec
-{
-  long long dist[4];                  // pqData.deltaDist by slot (qIdx & 3)
-  unsigned short ab[4];               // pqData.absLevel by slot
-  long long start[2];                 // decision 0 / decision 2
-  unsigned misc;                      // neighbour positions 5 x 4 bits | sigOff << 20 | gtxOff << 24
-  // v_perm_b32 selectors that pick the five neighbours out of the sixteen level bytes: group A = neighbours 0..3, group B = neighbour 4;
-  // Lo reads bytes 0..7, Hi bytes 8..15, selector 12 (= constant zero) where the neighbour is in the other half or does not exist
-  unsigned selLoA, selHiA, selLoB, selHiB, pad;
-};
-static_assert(sizeof(DqRec) == 80, "DqRec");
-constexpr int DQ_REC_N = 8;                                               // positions filled at a time (half a sub-block)
-constexpr int DQ_SEED_BYTES = 5 * 32;                                     // per TU: the seeds of context slots 0..3 + an all-zero slot
-constexpr int DQ_LDS_BYTES = 64 * (DQ_REC_N * (int)sizeof(DqRec) + DQ_SEED_BYTES);   // 64 quads per workgroup
-constexpr int DQ_RT_SLOTS = 16;
-
-__global__ __launch_bounds__(256) void depquant_kernel(const TCoeff* __restrict__ coeffBase, TCoeff* __restrict__ levelBase,
-                                                       const vvcgpu_depquant_desc* __restrict__ descs, int n,
-                                                       const vvcgpu_dq_rates* __restrict__ ratesBase, int bd, unsigned* __restrict__ absSumOut,
-                                                       unsigned* __restrict__ wsDec, unsigned char* __restrict__ wsCtx)
-{
-  const int lane = threadIdx.x & 63, k = lane & 3, qbase = lane & ~3;
-  const int ti = (blockIdx.x * 4 + (threadIdx.x >> 6)) * 16 + (lane >> 2);
-  const bool live = ti < n;
-  const vvcgpu_depquant_desc d = descs[live ? ti : n - 1];
-  const int w = d.w, h = d.h, N = w * h, lw = ilog2(w), lh = ilog2(h);
-  const int widthInSbb = w >> 2, heightInSbb = h >> 2, numSbb = N >> 4;
-  const bool luma = d.luma != 0;
-  const TCoeff* coef = coeffBase + d.coeff_off;
-  TCoeff* level = levelBase + d.level_off;
-  const int tabOff = d_scanOff[(lw - 1) * 6 + (lh - 1)];
-  const unsigned short* scan = d_scan + tabOff;
-  const unsigned short* inv = d_dqInv + tabOff;
-  const uint4* posSel = d_dqPosSel + tabOff;
-  const uint2* posMisc = d_dqPosMisc + tabOff;
-  unsigned* dec = wsDec + (size_t)d.coeff_off * 4;                         // [scanIdx][4]
-  // CommonCtx's per-state sub-block memory (:828-858) as a pool of 16-byte blocks [sub-block in scan order][context slot]: the levels of a
-  // sub-block as the state that took slot k at its end left them (the first 4 N of the 8 N bytes a TU has in the workspace)
-  unsigned char* ctxMem = wsCtx + (size_t)d.coeff_off * 8;
-
-  // Quantizer::initQuantBlock :647-706 (the same IEEE double arithmetic)
-  int qShift, maxQIdx, thresLast, distShift;
-  long long qAdd, qScale, distAdd, distStepAdd, distOrgFact;
-  {
-    const int qpDQ = d.qp + 1, qpPer = qpDQ / 6, qpRem = qpDQ - 6 * qpPer;
-    const bool sqrt2 = ((lw + lh) & 1) != 0;
-    const int transformShift = 15 - bd - ((lw + lh) >> 1);
-    const int qs = qpRem == 0 ? 26214 : qpRem == 1 ? 23302 : qpRem == 2 ? 20560 : qpRem == 3 ? 18396 : qpRem == 4 ? 16384 : 14564;
-    qShift = 14 - 1 + qpPer + transformShift;
-    qAdd = -((3ll << qShift) >> 1);
-    const int invShift = 6 + 1 - qpPer - transformShift + (sqrt2 ? 8 : 0);
-    qScale = sqrt2 ? (qs * 181) >> 7 : qs;
-    const unsigned qIdxBD = min(16u, (unsigned)(32 + invShift - 6 - 1));
-    maxQIdx = (1 << (qIdxBD - 1)) - 4;
-    thresLast = (int)((3ll << qShift) / (4 * qScale));
-    const int nomDShift = 15 - 2 * transformShift + qShift;
-    const double qScale2 = (double)((long long)qs * qs);
-    const double nomDistFactor = nomDShift < 0 ? 1.0 / ((double)(1ll << (-nomDShift)) * qScale2 * d.lambda) : (double)(1ll << nomDShift) / (qScale2 * d.lambda);
-    const long long pow2dfShift = (long long)(nomDistFactor * qScale2) + 1;
-    int dfShift = 0;
-    while ((1ull << dfShift) < (unsigned long long)pow2dfShift && dfShift < 63) dfShift++;
-    distShift = 62 + qShift - 2 * 15 - dfShift;
-    distAdd = (1ll << distShift) >> 1;
-    distStepAdd = (long long)(nomDistFactor * (double)(1ll << (distShift + qShift)) + .5);
-    distOrgFact = (long long)(nomDistFactor * (double)(1ll << (distShift + 1)) + .5);
-  }
-
-  // first tested position :1337-1349 (four lanes split the search), levels start as zero
-  int first = -1;
-  if (live)
-  {
-    for (int i = k; i < N; i += 4) level[i] = 0;
-    // (sixteen positions a round per quad, the loads of a round independent of each other: the search of a 64x64 TU with a zeroed-out
-    // high-frequency region walks ~2000 positions whose coefficients come from memory)
-    for (int i = N - 1 - k; i >= 0 && first < 0; i -= 16)
-    {
-      int a[4];
-#pragma unroll
-      for (int u = 0; u < 4; u++) a[u] = abs(coef[scan[max(i - 4 * u, 0)]]);
-#pragma unroll
-      for (int u = 3; u >= 0; u--) if (i - 4 * u >= 0 && a[u] > thresLast) first = i - 4 * u;
-    }
-  }
-  first = max(first, __shfl_xor(first, 1));
-  first = max(first, __shfl_xor(first, 2));
-  if (live && first < 0 && k == 0) absSumOut[ti] = 0;
-
-  // LDS: per quad the position records and the template seeds of its four context slots; per workgroup the rate tables.  The tables
-  // are looked up on the critical path of every step, so the walk only ever reads them from LDS: up to DQ_RT_SLOTS distinct tables of
-  // the workgroup's 64 TUs are staged per pass, TUs whose table found no slot walk in the next pass (one pass unless a caller
-  // mixes more than sixteen tables inside 64 consecutive TUs).
-  extern __shared__ __align__(16) unsigned char dqSmem[];
-  DqRec* const recTu = reinterpret_cast<DqRec*>(dqSmem) + (threadIdx.x >> 2) * DQ_REC_N;
-  unsigned* const seedTu = reinterpret_cast<unsigned*>(dqSmem + 64 * DQ_REC_N * sizeof(DqRec)) + (threadIdx.x >> 2) * (DQ_SEED_BYTES / 4);
-  __shared__ vvcgpu_dq_rates rtCache[DQ_RT_SLOTS];
-  __shared__ int rtSlot[DQ_RT_SLOTS];
-  __shared__ int rtPending;
-#pragma unroll
-  for (int i = 0; i < DQ_SEED_BYTES / 4 / 4; i++) seedTu[k * (DQ_SEED_BYTES / 4 / 4) + i] = 0u;
-
-  auto walk = [&](const bool run, DqLdsRates rt)
-  {
-  int maxFirst = run ? first : -1;
-#pragma unroll
-  for (int m = 4; m < 64; m <<= 1) maxFirst = max(maxFirst, __shfl_xor(maxFirst, m));
-  maxFirst = __builtin_amdgcn_readfirstlane(maxFirst);                    // the walk's position is the same in every lane: keep it (and what
-  if (maxFirst < 0) return;                                               // derives from it) in scalar registers
-
-  const int sigSet = max(k - 1, 0);                                       // RateEstimator::sigFlagBits(stateId) :282-285
-  DqState P, S;                                                           // previous-position state k, skip state k
-  {
-    P.rdCost = 0x7FFFFFFFFFFFFFFFll >> 1; P.numSigSbb = 0; P.refSbbCtxId = -1; P.goRice = 0; P.sbb0 = P.sbb1 = 0;
-    P.sig0 = rt->sig[sigSet][0][0]; P.sig1 = rt->sig[sigSet][0][1];
-    P.lev = dq_u4{ 0, 0, 0, 0 }; P.aux = dq_u4{ 0, 0, 0, 0 }; P.gc = 0;
-    dq_copy(S, P);
-  }
-  DqState P0; dq_copy(P0, P);
-  // The level history of a state (CommonCtx::update copies `setCpSize` bytes of it from the parent state at every sub-block end, :1104-1130)
-  // is never copied here: a block of the pool is written once, and a context slot carries the ANCESTRY of its path -- which slot its
-  // ancestor took at the end of each of the last 32 sub-blocks, two bits each, youngest in the low bits, and how many of them exist
-  // (a path that starts inside a sub-block has none: the reference zeroes its history).  The farthest block a template reads lies 30
-  // sub-blocks back (64x64).  Like the flags below, the pair lives in the lane whose number is the slot's.  The copy was 30 x 64 lines
-  // of 16 bytes per wavefront and sub-block end for 64x64 TUs, a twentieth of their walk.
-  unsigned long long ancCur = 0; int ancLen = 0;
-  dq_u8 Fcur;                                                             // coded-sub-block flags (bit per sub-block) of context slot k, current half
-#pragma unroll
-  for (int i = 0; i < 8; i++) Fcur[i] = 0;
-  long long finalCost = 0;
-
-  auto fillRec = [&](int si, int p, int coefAbs, const uint4 sel, const unsigned misc)
-  {
-    const int x = p & (w - 1), y = p >> lw;
-    // Quantizer::preQuantCoeff :786-808
-    dq_l4 pqDist = { 0, 0, 0, 0 }; dq_i4 pqAbs = { 0, 0, 0, 0 };
-    {
-      const long long scaledOrg = (long long)coefAbs * qScale;
-      int qIdx = max(1, min(maxQIdx, (int)((scaledOrg + qAdd) >> qShift)));
-      long long scaledAdd = qIdx * distStepAdd - scaledOrg * distOrgFact;
-#pragma unroll
-      for (int i = 0; i < 4; i++)
-      {
-        const int slot = qIdx & 3;
-        const long long dd = (scaledAdd * qIdx + distAdd) >> distShift;
-        const int al = (++qIdx) >> 1;
-#pragma unroll
-        for (int t = 0; t < 4; t++) { pqDist[t] = t == slot ? dd : pqDist[t]; pqAbs[t] = t == slot ? al : pqAbs[t]; }
-        scaledAdd += distStepAdd;
-      }
-    }
-    const int lastOffset = rt->last_x[x] + rt->last_y[y];
-    DqRec* r = recTu + (si & (DQ_REC_N - 1));
-    r->selLoA = sel.x; r->selHiA = sel.y; r->selLoB = sel.z; r->selHiB = sel.w;       // the shape-only part: straight from the table
-#pragma unroll
-    for (int t = 0; t < 4; t++) r->dist[t] = pqDist[t];
-    *reinterpret_cast<uint2*>(r->ab) = make_uint2((unsigned)pqAbs[0] | (unsigned)pqAbs[1] << 16, (unsigned)pqAbs[2] | (unsigned)pqAbs[3] << 16);
-    r->start[0] = pqDist[0] + lastOffset + dq_level_bits(rt, 0, 0, (unsigned)pqAbs[0]);
-    r->start[1] = pqDist[2] + lastOffset + dq_level_bits(rt, 0, 0, (unsigned)pqAbs[2]);
-    r->misc = misc;
-  };
-  // transitions leaving state k: state 0: pq0 -> dec0, pq2 -> dec2; state 1: pq2 -> dec0, pq0 -> dec2; state 2: pq3 -> dec1, pq1 -> dec3;
-  // state 3: pq1 -> dec1, pq3 -> dec3; the zero transition goes to dec0 / dec2 / dec1 / dec3  (:1229-1240)
-  const int lowIdx = k == 0 ? 0 : k == 1 ? 2 : k == 2 ? 3 : 1, highIdx = lowIdx ^ 2;
-  struct DqRecRegs { long long dl, dh, start; uint2 ab; unsigned misc; uint4 sel; };
-  auto loadRec = [&](int inside)
-  {
-    const DqRec* r = recTu + inside;
-    DqRecRegs v;
-    v.dl = r->dist[lowIdx]; v.dh = r->dist[highIdx]; v.start = r->start[k >> 1];
-    v.ab = *reinterpret_cast<const uint2*>(r->ab); v.misc = r->misc;
-    v.sel = make_uint4(r->selLoA, r->selHiA, r->selLoB, r->selHiB);
-    return v;
-  };
-  auto abOf = [](uint2 ab, int t) { return (int)(((t < 2 ? ab.x : ab.y) >> ((t & 1) * 16)) & 0xFFFFu); };
-  DqRecRegs R, Rn;
-  int pfPos[2] = { 0, 0 }, pfAbs[2] = { 0, 0 };
-  uint4 pfSel[2] = { make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0) }; unsigned pfMisc[2] = { 0, 0 };
-  auto prefetch = [&](int beg)
-  {
-#pragma unroll
-    for (int j = 0; j < 2; j++)
-    {
-      const int si = beg + k + 4 * j;
-      pfPos[j] = scan[si]; const int c = coef[pfPos[j]]; pfAbs[j] = abs(c);
-      pfSel[j] = posSel[si]; const uint2 m = posMisc[si]; pfMisc[j] = (luma ? m.x : m.y) | (c < 0 ? 0x80000000u : 0u);   // bit 31: the coefficient's sign
-    }
-  };
-  Rn.dl = Rn.dh = Rn.start = 0; Rn.ab = make_uint2(0, 0); Rn.misc = 0; Rn.sel = make_uint4(0, 0, 0, 0);
-
-  for (int scanIdx = maxFirst; scanIdx >= 0; scanIdx--)
-  {
-    const bool act = run && scanIdx <= first;                             // quad-uniform
-    const int sIdx = scanIdx;                                             // inactive quads compute on valid indices and discard
-    const int insidePos = sIdx & 15;
-    const bool eosbb = insidePos == 0, sosbb = insidePos == 15;
-    const bool socsbb = sosbb && sIdx > 16 && sIdx < N - 1;
-    const bool eocsbb = eosbb && sIdx > 0 && sIdx < N - 16;
-    const int spt = socsbb ? 1 : (eocsbb ? 2 : 0);
-    const int nxt = max(sIdx - 1, 0);
-    // a quad that is not active yet (scanIdx > first) computes along and its state is whatever that leaves: it starts from the
-    // initial state at its first tested position (instead of guarding every state copy of every step)
-    if (scanIdx == first)
-    {
-      dq_copy(P, P0); dq_copy(S, P0); ancCur = 0; ancLen = 0;
-#pragma unroll
-      for (int i = 0; i < 8; i++) Fcur[i] = 0;
-    }
-    const int recPos = sIdx & (DQ_REC_N - 1);
-    if (recPos == DQ_REC_N - 1 || scanIdx == maxFirst)                    // wave-uniform: the walk enters a group of positions
-    {
-      const int beg = sIdx & ~(DQ_REC_N - 1);
-      static_assert(DQ_REC_N == 8, "two records per lane");
-      if (scanIdx == maxFirst) prefetch(beg);
-#pragma unroll
-      for (int j = 0; j < 2; j++) fillRec(beg + k + 4 * j, pfPos[j], pfAbs[j], pfSel[j], pfMisc[j]);
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
-      R = loadRec(recPos);
-      // the coefficients of the NEXT group are the one stream of a TU that comes from HBM: requested here (with the shape part of its
-      // records), used eight steps later
-      prefetch(max(beg - DQ_REC_N, 0));
-    }
-    else R = Rn;
-    if (recPos != 0) Rn = loadRec(recPos - 1);                            // the next step's record is in flight during this one
-
-    const long long INF = 0x7FFFFFFFFFFFFFFFll;
-    long long cLow, cHigh, cZero = INF;
-    {
-      // checkRdCostNonZero / checkRdCostZero by scan-position type (:1133-1177) as selects (the three-way branch diverges inside a wavefront):
-      // the significance bits count unless the sub-block's coded flag is inferred (its end with nothing significant so far: no zero either),
-      // the coded-flag bits at its start
-      const bool zeroOk = !(spt == 2 && P.numSigSbb == 0);
-      const int sb = spt == 1 ? P.sbb1 : 0;
-      const int extra1 = (zeroOk ? P.sig1 : 0) + sb, extra0 = (zeroOk ? P.sig0 : 0) + sb;
-      cLow = P.rdCost + R.dl + dq_level_bits(rt, P.gc, P.goRice, (unsigned)abOf(R.ab, lowIdx)) + extra1;
-      cHigh = P.rdCost + R.dh + dq_level_bits(rt, P.gc, P.goRice, (unsigned)abOf(R.ab, highIdx)) + extra1;
-      if (zeroOk) cZero = P.rdCost + extra0;
-    }
-    // decision k: sources a = 0 / 2, b = a + 1; k < 2 takes their "low" transitions, k >= 2 the "high" ones.  The source lanes are a fixed
-    // pattern of the quad: lanes (0, 1, 2, 3) read a = (0, 2, 0, 2) and b = (1, 3, 1, 3)
-    const int a = (k & 1) * 2, b = a + 1;
-    const long long aLow = dq_quad64<0x88>(cLow), aHigh = dq_quad64<0x88>(cHigh), aZero = dq_quad64<0x88>(cZero);
-    const long long bLow = dq_quad64<0xDD>(cLow), bHigh = dq_quad64<0xDD>(cHigh), bZero = dq_quad64<0xDD>(cZero);
-    long long dCost = INF >> 2; int dAbs = -1, dPrev = -2;
-    {
-      // pq index of the transition a -> k and b -> k
-      const int ia = k == 0 ? 0 : k == 2 ? 2 : k == 1 ? 3 : 1, ib = ia ^ 2;
-      const int absA = abOf(R.ab, ia), absB = abOf(R.ab, ib);
-      // comparison order (strict '<'): k < 2: a, a's zero, b; k >= 2: a, b, b's zero -- as selects, the two orders share one code path
-      const bool lo = k < 2;
-      const long long cA = lo ? aLow : aHigh, cB = lo ? bLow : bHigh;
-      const long long c2 = lo ? aZero : cB, c3 = lo ? cB : bZero;
-      const int abs2 = lo ? 0 : absB, prev2 = lo ? a : b, abs3 = lo ? absB : 0;
-      if (cA < dCost) { dCost = cA; dAbs = absA; dPrev = a; }
-      if (c2 < dCost) { dCost = c2; dAbs = abs2; dPrev = prev2; }
-      if (c3 < dCost) { dCost = c3; dAbs = abs3; dPrev = b; }
-      if (spt == 2) { const long long c = S.rdCost + S.sbb0; if (c < dCost) { dCost = c; dAbs = 0; dPrev = 4 + k; } }          // checkRdCostSkipSbb
-      if ((k & 1) == 0 && R.start < dCost) { dCost = R.start; dAbs = abOf(R.ab, k); dPrev = -1; }                     // checkRdCostStart (decisions 0, 2)
-    }
-    // (with the coefficient's sign in bit 31: the back-trace then reads nothing but the decisions -- the coefficients of a picture do not stay in L2)
-    if (act) dec[(size_t)sIdx * 4 + k] = ((unsigned)max(dAbs, 0) << 4) | (unsigned)(dPrev + 2) | (R.misc & 0x80000000u);
-    if (scanIdx == 0) finalCost = dCost;
-
-    // ---- state update (:1259-1318); every lane pulls its winner's context from the source lane
-    DqState C; dq_copy(C, P);                                              // becomes the new previous state
-    if (sIdx > 0)
-    {
-      const int sigOff = (int)((R.misc >> 20) & 15u), gtxOff = (int)((R.misc >> 24) & 31u);
-      const int nextInside = nxt & 15;
-      // source of the copied context: lane dPrev (0..3), own skip state (4 + k) or nothing
-      const int srcLane = qbase + (dPrev >= 0 && dPrev < 4 ? dPrev : k);
-      dq_u4 lv = { 0, 0, 0, 0 }, ax = { 0, 0, 0, 0 }; int sNum, sRef, sSbb0, sSbb1;
-#pragma unroll
-      for (int i = 0; i < 4; i++) lv[i] = (unsigned)__shfl((int)P.lev[i], srcLane);
-      if (!eosbb)
-#pragma unroll
-        for (int i = 0; i < 4; i++) ax[i] = (unsigned)__shfl((int)P.aux[i], srcLane);
-      sNum = __shfl(P.numSigSbb, srcLane); sRef = __shfl(P.refSbbCtxId, srcLane);
-      sSbb0 = __shfl(P.sbb0, srcLane); sSbb1 = __shfl(P.sbb1, srcLane);
-      if (dPrev >= 4) { sNum = S.numSigSbb; sRef = S.refSbbCtxId;
-#pragma unroll
-        for (int i = 0; i < 4; i++) lv[i] = S.lev[i]; }
-      // sub-block flags of the inherited context slot: a register pull from the lane that owns the slot (slot id = lane in the quad);
-      // done by the whole quad (the branch below diverges inside a quad)
-      dq_u8 nf = { 0, 0, 0, 0, 0, 0, 0, 0 };
-      unsigned long long nAnc = 0; int nLen = 0;
-      if (eosbb)
-      {
-        const int pr = dPrev >= 0 ? sRef : -1;
-#pragma unroll
-        for (int i = 0; i < 8; i++) { const unsigned v = (unsigned)__shfl((int)Fcur[i], qbase + max(pr, 0)); nf[i] = pr >= 0 ? v : 0u; }
-        const unsigned long long pa = (unsigned long long)dq_shfl64((long long)ancCur, qbase + max(pr, 0));
-        const int pl = __shfl(ancLen, qbase + max(pr, 0));
-        nAnc = pr >= 0 ? (pa << 2) | (unsigned long long)pr : 0ull; nLen = pr >= 0 ? min(pl + 1, 32) : 0;
-      }
-      C.rdCost = dCost;
-      if (dPrev > -2)
-      {
-        int sumAbs, sumAbs1, sumNum;
-        if (!eosbb)                                                        // State::updateState :1004-1068
-        {
-          if (dPrev >= 0) { C.numSigSbb = sNum + (dAbs != 0); C.refSbbCtxId = sRef; C.sbb0 = sSbb0; C.sbb1 = sSbb1;
-#pragma unroll
-            for (int i = 0; i < 4; i++) { C.lev[i] = lv[i]; C.aux[i] = ax[i]; } }
-          else { C.numSigSbb = 1; C.refSbbCtxId = -1;
-#pragma unroll
-            for (int i = 0; i < 4; i++) { C.lev[i] = 0; C.aux[i] = 0; } }
-          const unsigned lvNew = (unsigned)min(255, dAbs);
-          dq_set_byte(C.lev, insidePos, lvNew);
-          dq_set_byte(C.aux, insidePos, min(4u - (lvNew & 1u), lvNew) | (lvNew != 0u ? 32u : 0u));
-          // the seeds of a sub-block belong to the context slot that was current when the walk entered it; every state that descends
-          // from it reads the same sixteen values (slot 4 = zeros: a path that started inside the sub-block)
-          const unsigned tinit = reinterpret_cast<const unsigned short*>(seedTu)[(C.refSbbCtxId < 0 ? 4 : C.refSbbCtxId) * 16 + nextInside];
-          sumAbs = (int)(tinit >> 8); sumAbs1 = (int)((tinit >> 3) & 31); sumNum = (int)(tinit & 7);
-          // the five template neighbours inside the sub-block: four byte permutes pick them out of the sixteen levels (and out of their
-          // sumAbs1 / sumNum contributions), v_sad_u8 against zero adds the picked bytes up
-          {
-            const unsigned nA = __builtin_amdgcn_perm(C.lev[1], C.lev[0], R.sel.x) | __builtin_amdgcn_perm(C.lev[3], C.lev[2], R.sel.y);
-            const unsigned nB = __builtin_amdgcn_perm(C.lev[1], C.lev[0], R.sel.z) | __builtin_amdgcn_perm(C.lev[3], C.lev[2], R.sel.w);
-            const unsigned xA = __builtin_amdgcn_perm(C.aux[1], C.aux[0], R.sel.x) | __builtin_amdgcn_perm(C.aux[3], C.aux[2], R.sel.y);
-            const unsigned xB = __builtin_amdgcn_perm(C.aux[1], C.aux[0], R.sel.z) | __builtin_amdgcn_perm(C.aux[3], C.aux[2], R.sel.w);
-            sumAbs = (int)__builtin_amdgcn_sad_u8(nB, 0u, __builtin_amdgcn_sad_u8(nA, 0u, (unsigned)sumAbs));
-            const unsigned sx = __builtin_amdgcn_sad_u8(xB, 0u, __builtin_amdgcn_sad_u8(xA, 0u, 0u));
-            sumAbs1 += (int)(sx & 31u); sumNum += (int)(sx >> 5);
-          }
-        }
-        else                                                               // State::updateStateEOS :1071-1102 + CommonCtx::update :1104-1164
-        {
-          if (dPrev >= 0) { C.numSigSbb = sNum + (dAbs != 0);
-#pragma unroll
-            for (int i = 0; i < 4; i++) C.lev[i] = lv[i]; }
-          else { C.numSigSbb = 1;
-#pragma unroll
-            for (int i = 0; i < 4; i++) C.lev[i] = 0; }
-          dq_set_byte(C.lev, insidePos, (unsigned)min(255, dAbs));
-          const int sbbId = sIdx >> 4;
-          if (act) *reinterpret_cast<uint4*>(ctxMem + (size_t)(sbbId * 4 + k) * 16) = make_uint4(C.lev[0], C.lev[1], C.lev[2], C.lev[3]);
-          const int pos = scan[sIdx], px = pos & (w - 1), py = pos >> lw, nxtPos = scan[nxt], nx = nxtPos & (w - 1), ny = nxtPos >> lw;
-          {
-            const int sbbPos = (py >> 2) * widthInSbb + (px >> 2);
-#pragma unroll
-            for (int i = 0; i < 8; i++) { const unsigned m = i == (sbbPos >> 5) ? 1u << (sbbPos & 31) : 0u; nf[i] = (nf[i] & ~m) | (C.numSigSbb != 0 ? m : 0u); }
-          }
-          const int nsx = nx >> 2, nsy = ny >> 2, nsp = nsy * widthInSbb + nsx;
-          const int right = nsx < widthInSbb - 1 ? nsp + 1 : 0, below = nsy < heightInSbb - 1 ? nsp + widthInSbb : 0;
-          unsigned fr = nf[0], fb = nf[0];
-#pragma unroll
-          for (int i = 1; i < 8; i++) { fr = (right >> 5) == i ? nf[i] : fr; fb = (below >> 5) == i ? nf[i] : fb; }
-          const int sigNSbb = ((right && ((fr >> (right & 31)) & 1u)) || (below && ((fb >> (below & 31)) & 1u))) ? 1 : 0;
-#pragma unroll
-          for (int i = 0; i < 8; i++) Fcur[i] = nf[i];
-          ancCur = nAnc; ancLen = nLen;
-          C.numSigSbb = 0; C.refSbbCtxId = k;
-          C.sbb0 = rt->sig_sbb[sigNSbb][0]; C.sbb1 = rt->sig_sbb[sigNSbb][1];
-          // template seeds of the sixteen positions of the next sub-block from the levels outside it (:1131-1160).  Every template
-          // neighbour outside a 4x4 sub-block lies in the sub-block to its right, below it or below-right of it, whose sixteen levels
-          // are sixteen consecutive bytes of the history (scan order): three 16-byte loads and compile-time byte picks replace eighty
-          // dependent byte loads behind eighty table look-ups (13.6 us per sub-block end, a fifth of the kernel).
-          dq_u8 cti = { 0, 0, 0, 0, 0, 0, 0, 0 };
-          if (act)
-          {
-            const int bx = nsx * 4, by = nsy * 4;
-            const bool hasR = nsx + 1 < widthInSbb, hasB = nsy + 1 < heightInSbb;
-            // read from the blocks of this state's ancestors (the sub-block that just ended: its levels are still in C.lev)
-            const uint4 own = make_uint4(C.lev[0], C.lev[1], C.lev[2], C.lev[3]), zero4 = make_uint4(0, 0, 0, 0);
-            // (loads from addresses that are always valid, the choice made on the VALUES: a choice between a loaded value and `own` / zero
-            // becomes a load through a selected address, i.e. `own` goes to scratch memory and the three loads wait for each other)
-            auto sbbLevels = [&](bool exists, int rasterPos)
-            {
-              const int j = inv[exists ? rasterPos : 0] >> 4, back = j - sbbId - 1;      // back = 0: the parent's sub-block
-              const unsigned slot = (unsigned)(nAnc >> (2 * min(max(back, 0), 31))) & 3u;
-              const uint4 hv = *reinterpret_cast<const uint4*>(ctxMem + (size_t)(j * 4 + (int)slot) * 16);
-              const bool fromHist = exists && back >= 0 && back < nLen, fromOwn = exists && j == sbbId;
-              uint4 r;
-              r.x = fromHist ? hv.x : fromOwn ? own.x : 0u; r.y = fromHist ? hv.y : fromOwn ? own.y : 0u;
-              r.z = fromHist ? hv.z : fromOwn ? own.z : 0u; r.w = fromHist ? hv.w : fromOwn ? own.w : 0u;
-              return r;
-            };
-            const uint4 LR = sbbLevels(hasR, by * w + bx + 4), LB = sbbLevels(hasB, (by + 4) * w + bx), LD = sbbLevels(hasR && hasB, (by + 4) * w + bx + 4);
-            auto pick = [](const uint4& v, int j) { const unsigned q = j < 4 ? v.x : j < 8 ? v.y : j < 12 ? v.z : v.w; return (q >> ((j & 3) * 8)) & 0xFFu; };
-            // contribution of one neighbour level to (sumNum | sumAbs1 << 3 | sumAbs << 8): at most five are added, the fields do not carry
-            auto cv = [](unsigned v) { return (v != 0u ? 1u : 0u) + (min(4u - (v & 1u), v) << 3) + (v << 8); };
-            unsigned cR[4][2], cB[2][4];
-#pragma unroll
-            for (int y = 0; y < 4; y++)
-#pragma unroll
-              for (int x = 0; x < 2; x++) cR[y][x] = cv(pick(LR, (int)((DQ_KOFPOS >> (4 * (y * 4 + x))) & 15)));
-#pragma unroll
-            for (int y = 0; y < 2; y++)
-#pragma unroll
-              for (int x = 0; x < 4; x++) cB[y][x] = cv(pick(LB, (int)((DQ_KOFPOS >> (4 * (y * 4 + x))) & 15)));
-            const unsigned cD = cv(pick(LD, (int)(DQ_KOFPOS & 15)));
-#pragma unroll
-            for (int i = 0; i < 16; i++)
-            {
-              const int pi = (int)((DQ_POSOFK >> (4 * i)) & 15), x = pi & 3, y = pi >> 2;
-              const int dx[5] = { 1, 2, 1, 0, 0 }, dy[5] = { 0, 0, 1, 1, 2 };
-              unsigned sum = 0;
-#pragma unroll
-              for (int t = 0; t < 5; t++)
-              {
-                const int X = x + dx[t], Y = y + dy[t];
-                if (X > 3 && Y > 3) sum += cD; else if (X > 3) sum += cR[Y][X - 4]; else if (Y > 3) sum += cB[Y - 4][X];
-              }
-              const unsigned seed = (sum & 0xFFu) | (min(127u, sum >> 8) << 8);
-              cti[i >> 1] |= seed << ((i & 1) * 16);
-            }
-            *reinterpret_cast<uint4*>(seedTu + k * 8) = make_uint4(cti[0], cti[1], cti[2], cti[3]);
-            *reinterpret_cast<uint4*>(seedTu + k * 8 + 4) = make_uint4(cti[4], cti[5], cti[6], cti[7]);
-          }
-#pragma unroll
-          for (int i = 0; i < 4; i++) { C.lev[i] = 0; C.aux[i] = 0; }
-          const unsigned tinit = dq_get_u16(cti, nextInside);
-          sumNum = (int)(tinit & 7); sumAbs1 = (int)((tinit >> 3) & 31); sumAbs = (int)(tinit >> 8);
-        }
-        const int sumGt1 = sumAbs1 - sumNum;
-        sumAbs -= sumNum;
-        const int sc = sigOff + min(sumAbs1, 5), gc = gtxOff + min(sumGt1, 4);
-        C.sig0 = rt->sig[sigSet][sc][0]; C.sig1 = rt->sig[sigSet][sc][1];
-        C.gc = gc;
-        const int ga = min(sumAbs, 31);
-        C.goRice = ga < 12 ? 0 : ga < 25 ? 1 : 2;                          // g_auiGoRicePars
-      }
-      if (eosbb) { __threadfence_block(); }
-    }
-    if (socsbb) dq_copy(S, P);                                             // swap( m_prevStates, m_skipStates ) :1314-1317
-    dq_copy(P, C);
-  }
-
-  // ---- best final state and back-trace :1368-1390.  Decisions 4..7 are implicit: at a sub-block end they are a copy of decisions
-  // 0..3 (:1269), elsewhere { level 0, same skip id } (startDec :1218).  The chain through the decisions is serial, the loads are not: the
-  // quad takes eight scan positions a round, lane j loads the four decisions of positions base + j and base + 4 + j (16 bytes each, the coefficient's sign in bit 31) and
-  // their raster positions -- one round ahead --, the chain then runs over quad broadcasts in registers (every lane alike) and lane j writes the
-  // level of its position.  (With lane 0 alone every position was a dependent load from memory: ~0.5 ms of a 64x64 TU's 3.1 ms.)
-  long long c1 = dq_shfl64(finalCost, qbase + 1), c2 = dq_shfl64(finalCost, qbase + 2), c3 = dq_shfl64(finalCost, qbase + 3);
-  const long long c0 = dq_shfl64(finalCost, qbase);
-  if (!run) return;
-  int prevId = -2; long long minCost = 0;
-  if (c0 < minCost) { prevId = 0; minCost = c0; }
-  if (c1 < minCost) { prevId = 1; minCost = c1; }
-  if (c2 < minCost) { prevId = 2; minCost = c2; }
-  if (c3 < minCost) { prevId = 3; minCost = c3; }
-  unsigned absSum = 0;
-  __threadfence_block();                                                   // the decisions were stored by the four lanes
-  const uint4* dec4 = reinterpret_cast<const uint4*>(dec);
-  // (eight positions a round, two per lane: the chain over eight positions takes about as long as the loads of the next eight)
-  uint4 dv[2]; int pos[2];
-#pragma unroll
-  for (int u = 0; u < 2; u++) { const int i = min(4 * u + k, N - 1); dv[u] = dec4[i]; pos[u] = scan[i]; }
-  for (int base = 0; prevId >= 0; base += 8)
-  {
-    uint4 dn[2]; int posn[2];
-#pragma unroll
-    for (int u = 0; u < 2; u++) { const int i = min(base + 8 + 4 * u + k, N - 1); dn[u] = dec4[i]; posn[u] = scan[i]; }
-#pragma unroll
-    for (int u = 0; u < 2; u++)
-    {
-      int myAl = 0; bool mine = false, myNeg = false;
-      // a link of the chain: every lane picks the decision of the current state out of ITS position's four (two selects on the bits of
-      // the state: nested conditionals became branches), lane j's pick is the one that counts
-      auto pick = [&]()
-      {
-        const bool b0 = (prevId & 1) != 0, b1 = (prevId & 2) != 0;
-        const unsigned lo = b0 ? dv[u].y : dv[u].x, hi = b0 ? dv[u].w : dv[u].z;
-        return b1 ? hi : lo;
-      };
-      auto link = [&](int j, unsigned v)
-      {
-        const bool on = prevId >= 0, keep = prevId >= 4 && ((base + 4 * u + j) & 15) != 0;
-        const int al = keep ? 0 : (int)((v >> 4) & 0x7FFFFFFu), nextPrev = keep ? prevId : (int)(v & 15) - 2;
-        if (on && j == k) { myAl = al; mine = true; myNeg = (v >> 31) != 0u; }
-        absSum += on ? (unsigned)al : 0u; prevId = on ? nextPrev : prevId;
-      };
-      link(0, dq_quad32<0x00>(pick()));                                    // quad_perm [j, j, j, j]: lane j of the quad to all four
-      link(1, dq_quad32<0x55>(pick()));
-      link(2, dq_quad32<0xAA>(pick()));
-      link(3, dq_quad32<0xFF>(pick()));
-      if (mine) level[pos[u]] = myNeg ? -myAl : myAl;
-    }
-#pragma unroll
-    for (int u = 0; u < 2; u++) { dv[u] = dn[u]; pos[u] = posn[u]; }
-  }
-  if (k != 0) return;
-  absSumOut[ti] = absSum;
-  };
-
-  bool done = !(live && first >= 0);
-  for (;;)
-  {
-    if (threadIdx.x < DQ_RT_SLOTS) rtSlot[threadIdx.x] = -1;
-    if (threadIdx.x == 0) rtPending = 0;
-    __syncthreads();
-    int mySlot = -1;
-    if (!done && k == 0)
-    {
-      for (int t = 0; t < DQ_RT_SLOTS && mySlot < 0; t++)
-      {
-        const int sl = (d.rates_idx + t) & (DQ_RT_SLOTS - 1);
-        const int old = atomicCAS(&rtSlot[sl], -1, d.rates_idx);
-        if (old == -1 || old == d.rates_idx) mySlot = sl;
-      }
-      if (mySlot < 0) rtPending = 1;
-    }
-    mySlot = __shfl(mySlot, qbase);
-    __syncthreads();
-    const bool more = rtPending != 0;
-    for (int sl = 0; sl < DQ_RT_SLOTS; sl++)
-      if (rtSlot[sl] >= 0)
-      {
-        const int* src = reinterpret_cast<const int*>(ratesBase + rtSlot[sl]);
-        int* dst = reinterpret_cast<int*>(&rtCache[sl]);
-        for (int i = threadIdx.x; i < (int)(sizeof(vvcgpu_dq_rates) / 4); i += 256) dst[i] = src[i];
-      }
-    __syncthreads();
-    const bool run = !done && mySlot >= 0;
-    walk(run, (DqLdsRates)&rtCache[max(mySlot, 0)]);
-    done = done || run;
-    if (!more) break;
-    __syncthreads();
-  }
-}
-
-// ---- N1: rate-distortion optimised quantiser (QuantRDOQ::xRateDistOptQuant, QuantRDOQ.cpp:694-1409) -------------------------
-// Sixteen lanes per TU, lane k = position k of the current 4x4 coefficient group.  What the reference does one coefficient at a
-// time splits into: per-coefficient quantities (parallel), the level decisions (each reads the five template neighbours: the
-// anti-diagonals of a group are independent, so seven steps decide sixteen levels; neighbours inside the group travel by lane
-// shuffles, those in earlier groups are read back from the level buffer), and the running cost sums, which are IEEE double
-// additions in scan order and therefore stay a serial chain (evaluated by every lane of the team alike, operands by shuffle).
-// All double arithmetic is written in the reference's order with contraction off.
-#pragma clang fp contract(off)
-
-constexpr unsigned long long rdoq_pack_kofpos()
-{
-  // lane (scan index inside a 4x4 group) of in-group position y * 4 + x, from the diagonal scan
-  unsigned long long v = 0; int k = 0;
-  for (int d = 0; d < 7; d++)
-    for (int y = (d < 3 ? d : 3); y >= 0; y--)
-    {
-      const int x = d - y;
-      if (x > 3) continue;
-      v |= (unsigned long long)k << (4 * (y * 4 + x)); k++;
-    }
-  return v;
-}
-constexpr unsigned long long RDOQ_KOFPOS = rdoq_pack_kofpos();
-
-struct RdoqBits { int par0, par1, gt10, gt11, gt20, gt21; };
-
-__device__ __forceinline__ int rdoq_ic_rate(unsigned a, const RdoqBits& b, int rice)              // xGetICRate :235-313
-{
-  if (a == 0) return 0;
-  int rate = 32768;
-  if (a >= 5)
-  {
-    unsigned symbol = (a - 5) >> 1;
-    const int thr = rice == 1 ? 5 : 6;                                                              // g_auiGoRiceRange[0..2]
-    if (symbol < (unsigned)(thr << rice)) rate += (int)((symbol >> rice) + 1 + rice) << 15;
-    else
-    {
-      // the escape loop (:279-286) ends at length = floor(log2(symbol' + 2^rice)), symbol' = symbol - (thr << rice)
-      const int length = 31 - __clz((int)(symbol - (unsigned)(thr << rice) + (1u << rice)));
-      rate += (thr + length + 1 - rice + length) << 15;
-    }
-    rate += (((a - 1) & 1) ? b.par1 : b.par0) + b.gt11 + b.gt21;
-  }
-  else if (a == 1) rate += b.par0 + b.gt10;
-  else if (a == 2) rate += b.par1 + b.gt10;
-  else if (a == 3) rate += b.par0 + b.gt11 + b.gt20;
-  else rate += b.par1 + b.gt11 + b.gt20;
-  return rate;
-}
-
-__device__ __forceinline__ double rdoq_shfl(double v, int src) { return __shfl(v, src); }
-
-__global__ __launch_bounds__(256) void rdoq_kernel(const TCoeff* __restrict__ coeffBase, TCoeff* __restrict__ levelBase,
-                                                   const vvcgpu_rdoq_desc* __restrict__ descs, int n, const vvcgpu_rdoq_rates* __restrict__ rates,
-                                                   int bd, unsigned* __restrict__ absSumOut, double* __restrict__ wsD, int* __restrict__ wsI,
-                                                   double* __restrict__ wsCG, unsigned char* __restrict__ wsSG, size_t c)
-{
-  const int ti = (int)((blockIdx.x * 256u + threadIdx.x) >> 4), k = threadIdx.x & 15, tb = threadIdx.x & 48;
-  if (ti >= n) return;                                                                              // whole teams leave
-  const vvcgpu_rdoq_desc d = descs[ti];
-  const int w = d.w, h = d.h, lw = ilog2(w), lh = ilog2(h), numCG = (w * h) >> 4, wig = w >> 2, hig = h >> 2;
-  const unsigned short* scan = d_scan + d_scanOff[(lw - 1) * 6 + (lh - 1)];
-  const TCoeff* src = coeffBase + d.coeff_off;
-  TCoeff* dst = levelBase + d.level_off;
-  const vvcgpu_rdoq_rates* rt = rates + d.rates_idx;
-  const double lambda = d.lambda;
-  const bool luma = d.luma != 0;
-  const int per = d.qp / 6, rem = d.qp - 6 * per;
-  const int transformShift = 15 - bd - ((lw + lh) >> 1);
-  const bool sqrt2 = ((lw + lh) & 1) != 0;
-  const int qBits = 14 + per + transformShift;
-  const int qs = rem == 0 ? 26214 : rem == 1 ? 23302 : rem == 2 ? 20560 : rem == 3 ? 18396 : rem == 4 ? 16384 : 14564;     // g_quantScales
-  const int quantCoef = sqrt2 ? (qs * 181) >> 7 : qs;
-  const double errScale = ldexp(1.0, 15 - 2 * transformShift + (sqrt2 ? 1 : 0)) / quantCoef / quantCoef;                  // xGetErrScaleCoeff :482-506
-  const int half = 1 << (qBits - 1);
-  // workspace, indexed by coeff_off + scan position (coeff_off is a multiple of 16: the sixteen lanes write one line)
-  double* wCoeff = wsD + d.coeff_off; double* wSig = wsD + c + d.coeff_off; double* wCoeff0 = wsD + 2 * c + d.coeff_off;
-  int* wUp = wsI + d.coeff_off; int* wDown = wsI + c + d.coeff_off; int* wSigDelta = wsI + 2 * c + d.coeff_off; int* wDeltaU = wsI + 3 * c + d.coeff_off;
-  double* wCG = wsCG + (d.coeff_off >> 4);
-  unsigned char* wSG = wsSG + (d.coeff_off >> 4);
-
-  double blockUncoded = 0, baseCost = 0;
-  int cgLastScanPos = -1, lastScanPos = -1;
-  for (int subSet = numCG - 1; subSet >= 0; subSet--)
-  {
-    const int sp = (subSet << 4) + k, pos = scan[sp], x = pos & (w - 1), y = pos >> lw, x4 = x & 3, y4 = y & 3, diag4 = x4 + y4;
-    const int cgX = x >> 2, cgY = y >> 2, cgPos = cgY * wig + cgX;
-    const int sigRight = cgX + 1 < wig ? wSG[cgPos + 1] : 0, sigLower = cgY + 1 < hig ? wSG[cgPos + wig] : 0;
-    const int sg0 = rt->sig_group[sigRight | sigLower][0], sg1 = rt->sig_group[sigRight | sigLower][1];
-    // ---- per coefficient :830-843
-    const long long tmpLevel = (long long)abs(src[pos]) * quantCoef;
-    const int levelDouble = (int)min(tmpLevel, (long long)0x7FFFFFFF - half);
-    const unsigned maxAbs = min(32767u, (unsigned)((levelDouble + half) >> qBits));
-    const double err0 = (double)levelDouble;
-    const double cost0 = err0 * err0 * errScale;
-    if (lastScanPos < 0)
-    {
-      const unsigned m = (unsigned)(__ballot(maxAbs > 0) >> tb) & 0xFFFFu;
-      if (m) { lastScanPos = (subSet << 4) + 31 - __clz((int)m); cgLastScanPos = subSet; }
-    }
-    const bool inRange = lastScanPos >= 0 && sp <= lastScanPos, isLast = sp == lastScanPos;
-    // ---- template neighbours (x+1,y) (x+2,y) (x+1,y+1) (x,y+1) (x,y+2): validity as nested at ContextModelling.h:144-164
-    const bool v0 = x < w - 1, v1 = x < w - 2, v2 = v0 && y < h - 1, v3 = y < h - 1, v4 = y < h - 2;
-    const bool in0 = x4 < 3, in1 = x4 < 2, in2 = x4 < 3 && y4 < 3, in3 = y4 < 3, in4 = y4 < 2;
-    int nb0 = (v0 && !in0) ? dst[pos + 1] : 0, nb1 = (v1 && !in1) ? dst[pos + 2] : 0, nb2 = (v2 && !in2) ? dst[pos + w + 1] : 0,
-        nb3 = (v3 && !in3) ? dst[pos + w] : 0, nb4 = (v4 && !in4) ? dst[pos + 2 * w] : 0;
-    const int p4 = y4 * 4 + x4;
-    const int l0 = tb + (int)((RDOQ_KOFPOS >> (4 * ((p4 + 1) & 15))) & 15), l1 = tb + (int)((RDOQ_KOFPOS >> (4 * ((p4 + 2) & 15))) & 15),
-              l2 = tb + (int)((RDOQ_KOFPOS >> (4 * ((p4 + 5) & 15))) & 15), l3 = tb + (int)((RDOQ_KOFPOS >> (4 * ((p4 + 4) & 15))) & 15),
-              l4 = tb + (int)((RDOQ_KOFPOS >> (4 * ((p4 + 8) & 15))) & 15);
-    int level = 0, incUp = 0, incDown = 0, sigDelta = 0, deltaU = 0;
-    double costCoeff = 0, costSig = 0;
-    for (int dg = 6; dg >= 0; dg--)
-    {
-      const int t0 = __shfl(level, l0), t1 = __shfl(level, l1), t2 = __shfl(level, l2), t3 = __shfl(level, l3), t4 = __shfl(level, l4);
-      if (diag4 == dg && inRange)
-      {
-        int sumAbs = 0, numPos = 0, sumGo = 0;
-        auto upd = [&](bool valid, int a) { if (valid) { sumAbs += min(4 - (a & 1), a); numPos += a != 0; sumGo += a - (a != 0); } };
-        upd(v0, in0 ? t0 : nb0); upd(v1, in1 ? t1 : nb1); upd(v2, in2 ? t2 : nb2); upd(v3, in3 ? t3 : nb3); upd(v4, in4 ? t4 : nb4);
-        int ctxSig = 0, ofs = 0;
-        if (!isLast)
-        {
-          const int diag = x + y;
-          ctxSig = min(sumAbs, 5) + (diag < 2 ? 6 : 0) + ((luma && diag < 5) ? 6 : 0);
-          ofs = min(sumAbs - numPos, 4) + 1 + (diag == 0 ? (luma ? 15 : 5) : (luma ? (diag < 3 ? 10 : (diag < 10 ? 5 : 0)) : 0));
-        }
-        const int sm = min(sumGo, 31), rice = sm < 12 ? 0 : sm < 25 ? 1 : 2;                       // g_auiGoRicePars
-        const RdoqBits b = { rt->par[ofs][0], rt->par[ofs][1], rt->gt1[ofs][0], rt->gt1[ofs][1], rt->gt2[ofs][0], rt->gt2[ofs][1] };
-        const int sig0 = rt->sig[ctxSig][0], sig1 = rt->sig[ctxSig][1];
-        // xGetCodedLevel :107-162
-        double codedCost; unsigned best = 0; bool done = false;
-        if (!isLast && maxAbs < 3)
-        {
-          costSig = lambda * sig0;
-          codedCost = cost0 + costSig;
-          done = maxAbs == 0;
-        }
-        else codedCost = 1.7976931348623157e308;
-        if (!done)
-        {
-          const double currSig = isLast ? 0.0 : lambda * sig1;
-          const int minAbs = maxAbs > 1 ? (int)maxAbs - 1 : 1;
-          for (int a = (int)maxAbs; a >= minAbs; a--)
-          {
-            const double err = (double)(levelDouble - (int)((unsigned)a << qBits));
-            double cost = err * err * errScale + lambda * rdoq_ic_rate((unsigned)a, b, rice);
-            cost += currSig;
-            if (cost < codedCost) { best = (unsigned)a; codedCost = cost; costSig = currSig; }
-          }
-        }
-        costCoeff = codedCost;
-        if (!isLast) sigDelta = sig1 - sig0;
-        deltaU = (levelDouble - (int)(best << qBits)) >> (qBits - 8);
-        if (best > 0)
-        {
-          const int now = rdoq_ic_rate(best, b, rice);
-          incUp = rdoq_ic_rate(best + 1, b, rice) - now;
-          incDown = rdoq_ic_rate(best - 1, b, rice) - now;
-        }
-        else incUp = b.par0 + b.gt10;
-        level = (int)best;
-      }
-    }
-    // ---- the running sums of the group, scan order fifteen down to zero :1023-1041
-    double sigCost = 0, sigCost0 = 0, codedLevelAndDist = 0, uncodedDist = 0; int nnzBeforePos0 = 0;
-    const unsigned nzMask = (unsigned)(__ballot(level != 0) >> tb) & 0xFFFFu;
-    for (int kk = 15; kk >= 0; kk--)
-    {
-      const double cc = rdoq_shfl(costCoeff, tb + kk), c0 = rdoq_shfl(cost0, tb + kk), cs = rdoq_shfl(costSig, tb + kk);
-      blockUncoded += c0;
-      baseCost += (lastScanPos >= 0 && (subSet << 4) + kk <= lastScanPos) ? cc : c0;
-      sigCost += cs;
-      if (kk == 0) sigCost0 = cs;
-      if ((nzMask >> kk) & 1u) { codedLevelAndDist += cc - cs; uncodedDist += c0; if (kk != 0) nnzBeforePos0++; }
-    }
-    bool sigGroup = nzMask != 0;
-    double cgSig = 0;
-    if (cgLastScanPos >= 0)
-    {
-      if (subSet)
-      {
-        if (!sigGroup)
-        {
-          baseCost += lambda * sg0 - sigCost;
-          cgSig = lambda * sg0;
-        }
-        else if (subSet < cgLastScanPos)
-        {
-          if (nnzBeforePos0 == 0) { baseCost -= sigCost0; sigCost -= sigCost0; }
-          double costZeroCG = baseCost;
-          baseCost += lambda * sg1;
-          costZeroCG += lambda * sg0;
-          cgSig = lambda * sg1;
-          costZeroCG += uncodedDist;
-          costZeroCG -= codedLevelAndDist;
-          costZeroCG -= sigCost;
-          if (costZeroCG < baseCost)
-          {
-            sigGroup = false;
-            baseCost = costZeroCG;
-            cgSig = lambda * sg0;
-            if (level) { level = 0; costCoeff = cost0; costSig = 0; }
-          }
-        }
-      }
-      else sigGroup = true;
-    }
-    dst[pos] = level;
-    wCoeff[sp] = costCoeff; wSig[sp] = costSig; wCoeff0[sp] = cost0;
-    wUp[sp] = incUp; wDown[sp] = incDown; wSigDelta[sp] = sigDelta; wDeltaU[sp] = deltaU;
-    if (k == 0) { wSG[cgPos] = sigGroup ? 1 : 0; wCG[subSet] = cgSig; }
-    __threadfence_block();                                                 // levels and group flags are read by other lanes of the team later
-  }
-  if (lastScanPos < 0) { if (k == 0) absSumOut[ti] = 0; return; }
-
-  // ---- last position :1127-1262 (serial chain on the base cost; ends at the first level above one)
-  double bestCost = blockUncoded + lambda * rt->cbf[0];
-  baseCost += lambda * rt->cbf[1];
-  int bestLastIdxP1 = 0;
-  bool foundLast = false;
-  for (int cg = cgLastScanPos; cg >= 0 && !foundLast; cg--)
-  {
-    baseCost -= wCG[cg];
-    const int sp = (cg << 4) + k, pos = scan[sp], px = pos & (w - 1), py = pos >> lw;
-    if (!wSG[(py >> 2) * wig + (px >> 2)]) continue;
-    const int lvl = dst[pos];
-    const double cc = wCoeff[sp], cs = wSig[sp], c0 = wCoeff0[sp];
-    const int gx = px < 4 ? px : (2 * (31 - __clz(px))) + ((px >> (30 - __clz(px))) & 1), gy = py < 4 ? py : (2 * (31 - __clz(py))) + ((py >> (30 - __clz(py))) & 1);   // g_uiGroupIdx
-    double rl = rt->last_x[gx] + rt->last_y[gy];                                    // xGetRateLast :407-421
-    if (gx > 3) rl += 32768.0 * ((gx - 2) >> 1);
-    if (gy > 3) rl += 32768.0 * ((gy - 2) >> 1);
-    const double costLast = lambda * rl;
-    for (int kk = 15; kk >= 0; kk--)
-    {
-      const int l = __shfl(lvl, tb + kk);
-      const double cck = rdoq_shfl(cc, tb + kk), csk = rdoq_shfl(cs, tb + kk), c0k = rdoq_shfl(c0, tb + kk), clk = rdoq_shfl(costLast, tb + kk);
-      if ((cg << 4) + kk > lastScanPos) continue;
-      if (l)
-      {
-        const double total = baseCost + clk - csk;
-        if (total < bestCost) { bestLastIdxP1 = (cg << 4) + kk + 1; bestCost = total; }
-        if (l > 1) { foundLast = true; break; }
-        baseCost -= cck;
-        baseCost += c0k;
-      }
-      else baseCost -= csk;
-    }
-  }
-
-  // ---- signs, the positions beyond the chosen last one, the sum of levels :1263-1276
-  unsigned absSum = 0;
-  for (int cg = 0; cg <= cgLastScanPos; cg++)
-  {
-    const int sp = (cg << 4) + k, pos = scan[sp];
-    const int lvl = sp < bestLastIdxP1 ? dst[pos] : 0;
-    absSum += (unsigned)lvl;
-    dst[pos] = src[pos] < 0 ? -lvl : lvl;
-  }
-  for (int m = 1; m < 16; m <<= 1) absSum += (unsigned)__shfl_xor((int)absSum, m);
-  if (k == 0) absSumOut[ti] = absSum;
-
-  // ---- sign bit hiding :1278-1406: every group on its own; lane = candidate position
-  if (!d.sign_hiding || (int)absSum < 2) return;
-  const double inv = rem == 0 ? 40.0 : rem == 1 ? 45.0 : rem == 2 ? 51.0 : rem == 3 ? 57.0 : rem == 4 ? 64.0 : 72.0;               // g_invQuantScales
-  const long long rdFactor = (long long)(inv * inv * (1 << (2 * per)) / lambda / 16 / 1 + 0.5);
-  int lastCG = -1;
-  for (int subSet = cgLastScanPos; subSet >= 0; subSet--)
-  {
-    const int sp = (subSet << 4) + k, pos = scan[sp];
-    const int lvl = dst[pos];
-    const unsigned m = (unsigned)(__ballot(lvl != 0) >> tb) & 0xFFFFu;
-    const int lastNZ = m ? 31 - __clz((int)m) : -1, firstNZ = m ? __ffs((int)m) - 1 : 16;
-    int sum = lvl;
-    for (int s = 1; s < 16; s <<= 1) sum += __shfl_xor(sum, s);
-    if (lastNZ >= 0 && lastCG == -1) lastCG = 1;
-    if (lastNZ - firstNZ >= 4)
-    {
-      const unsigned signbit = __shfl(lvl, tb + firstNZ) > 0 ? 0u : 1u;
-      if (signbit != (unsigned)(sum & 1))
-      {
-        const long long MAXC = 0x7FFFFFFFFFFFFFFFll;
-        long long curCost = MAXC; int curChange = 0;
-        if (k <= (lastCG == 1 ? lastNZ : 15))
-        {
-          const int dU = wDeltaU[sp], up = wUp[sp], down = wDown[sp], sd = wSigDelta[sp];
-          if (lvl != 0)
-          {
-            const long long costUp = rdFactor * (-dU) + up;
-            long long costDown = rdFactor * dU + down - (abs(lvl) == 1 ? sd : 0);
-            if (lastCG == 1 && lastNZ == k && abs(lvl) == 1) costDown -= 4 << 15;
-            if (costUp < costDown) { curCost = costUp; curChange = 1; }
-            else { curChange = -1; curCost = (k == firstNZ && abs(lvl) == 1) ? MAXC : costDown; }
-          }
-          else
-          {
-            curCost = rdFactor * (-(long long)abs(dU)) + (1 << 15) + up + sd;
-            curChange = 1;
-            if (k < firstNZ && (src[pos] >= 0 ? 0u : 1u) != signbit) curCost = MAXC;
-          }
-        }
-        // minimum cost; among equals the position visited first (the highest) stays
-        long long bc = curCost; int bk = k;
-        for (int s = 1; s < 16; s <<= 1)
-        {
-          const long long oc = __shfl_xor(bc, s); const int ok = __shfl_xor(bk, s);
-          if (oc < bc || (oc == bc && ok > bk)) { bc = oc; bk = ok; }
-        }
-        if (bk == k && bc != MAXC)
-        {
-          int change = curChange;
-          if (lvl == 32767 || lvl == -32768) change = -1;
-          dst[pos] = src[pos] >= 0 ? lvl + change : lvl - change;
-        }
-      }
-    }
-    if (lastCG == 1) lastCG = 0;
-  }
-}
-
 constexpr int g_smallGrid = 1280;                  // workgroups of the small-TU kernels (swept in round 2)
 
 // diagonal 4x4-grouped coefficient scan (Rom.cpp:357-405): groups of 4x4 (2x2 when a side is 2) visited along the diagonals
@@ -2441,32 +1315,65 @@ static int upload_tables(void*, const void*)
   VVC_HIP(hipMemcpyToSymbol(HIP_SYMBOL(d_dqInv), invs, sizeof(invs)));
   return VVCGPU_OK;
 }
-static int ensure_tables() { return vvcgpu_device_image(VVC_IMAGE_TR_TABLES, 0, upload_tables, nullptr, nullptr); }
-
 // VVCGPU_NO_MFMA=1 (common.h) keeps every large TU on the dot2 kernels
 static int tr_use_mfma() { return vvcgpu_no_mfma() ? 0 : 1; }
 
-static int check_descs_args(const void* a, const void* b, const void* d, int n, int bd, const char* who)
+// argument checks of the three entries below.  *empty: the call has no descriptors and is done (VVCGPU_OK)
+static int check_descs_args(const void* a, const void* b, const void* d, int n, int bd, const char* who, bool* empty)
 {
+  *empty = n == 0;
   VVC_CHECK_ARG(n >= 0, "%s: n %d", who, n);
-  if (n == 0) return 1;
+  if (n == 0) return VVCGPU_OK;
   VVC_CHECK_ARG(a && b && d, "%s: null pointer", who);
   if (bd < 8 || bd > 10) { vvcgpu_set_error("%s: bit depth %d outside 8..10", who, bd); return VVCGPU_E_UNSUPPORTED; }
   return VVCGPU_OK;
 }
 
+// A plain transform call as lists on the device and three kernels that walk them: in -> out is residual -> coefficients (forward) or the reverse
+template <class In, class Out, class SmallK, class MfmaK, class LargeK>
+static int tr_launch_lists(SmallK smallK, MfmaK mfmaK, LargeK largeK, const In* in, Out* out, const vvcgpu_tr_desc* descs, int n, int bit_depth,
+                           const _Float16* image, hipStream_t st)
+{
+  // long calls: the small TUs are binned on the device as well and the small kernel walks the bin lists (see small_setup)
+  const bool ordered = n >= 16384;
+  VvcScratch sc(st);
+  int* ws = sc.take<int>(2 + 2 * (size_t)n);                                // two counters, then the lists of dot2 and matrix-core TUs
+  int* smLists = ordered ? sc.take<int>(4 * (size_t)n) : nullptr;           // the bins of the small TUs
+  if (!ws || (ordered && !smLists)) return VVCGPU_E_DEVICE;
+  VVC_HIP(hipMemsetAsync(ws, 0, 2 * sizeof(int), st));
+  int* smCnt = nullptr; int* nextCnt = nullptr;
+  if (ordered)
+  {
+    int cur = 0;
+    int* counters = vvcgpu_counters(st, &cur);
+    if (!counters) return VVCGPU_E_DEVICE;
+    smCnt = counters + VVC_CTR_INTS * cur; nextCnt = counters + VVC_CTR_INTS * (cur ^ 1);
+  }
+  const int nb = cdiv(n, SM_DESCS), nl = cdiv(n, 4);
+  hipLaunchKernelGGL(tr_collect_large_kernel, dim3(cdiv(n, 1024)), dim3(1024), 0, st, descs, n, ws, tr_use_mfma(), smCnt, smLists, nextCnt);
+  hipLaunchKernelGGL(smallK, dim3(nb < g_smallGrid ? nb : g_smallGrid), dim3(256), 0, st, in, out, descs, n, bit_depth, tr_use_mfma(), smCnt, smLists);
+  hipLaunchKernelGGL(mfmaK, dim3(nl < 768 ? nl : 768), dim3(256), 0, st, in, out, descs, ws, ws + 2 + n, ws + 1, bit_depth, image);
+  hipLaunchKernelGGL(largeK, dim3(nl < 768 ? nl : 768), dim3(256), 0, st, in, out, descs, ws + 1, bit_depth);
+  if (ordered) VVC_LAUNCH_CHECK_COUNTERS(st);
+  VVC_LAUNCH_CHECK();
+  return VVCGPU_OK;
+}
+
 }  // namespace
 
-// device addresses of the golden tables on the current device, for the kernels of other translation units (resichain.hip)
+// device addresses of the tables on the current device, for the kernels of the other sources (resichain.hip, quant.hip, depquant.hip, rdoq.hip)
 int vvcgpu_tr_tables(VvcTrTables* out)
 {
-  const int rt = ensure_tables();
+  const int rt = vvcgpu_device_image(VVC_IMAGE_TR_TABLES, 0, upload_tables, nullptr, nullptr);     // uploaded by the first call that needs them
   if (rt) return rt;
   void* p = nullptr;
   VVC_HIP(hipGetSymbolAddress(&p, HIP_SYMBOL(d_tr32)));      out->tr32 = static_cast<const int*>(p);
   VVC_HIP(hipGetSymbolAddress(&p, HIP_SYMBOL(d_tr32t)));     out->tr32t = static_cast<const int*>(p);
+  VVC_HIP(hipGetSymbolAddress(&p, HIP_SYMBOL(d_scan)));      out->scan = static_cast<const unsigned short*>(p);
   VVC_HIP(hipGetSymbolAddress(&p, HIP_SYMBOL(d_dqInv)));     out->dqInv = static_cast<const unsigned short*>(p);
   VVC_HIP(hipGetSymbolAddress(&p, HIP_SYMBOL(d_scanOff)));   out->scanOff = static_cast<const int*>(p);
+  VVC_HIP(hipGetSymbolAddress(&p, HIP_SYMBOL(d_dqPosSel)));  out->dqPosSel = static_cast<const uint4*>(p);
+  VVC_HIP(hipGetSymbolAddress(&p, HIP_SYMBOL(d_dqPosMisc))); out->dqPosMisc = static_cast<const uint2*>(p);
   return VVCGPU_OK;
 }
 
@@ -2475,102 +1382,47 @@ extern "C" {
 int vvcgpu_tr_fwd_batch(const vvc_pel* resi_base, vvc_coef* coeff_base, const vvcgpu_tr_desc* descs, int n,
                         int bit_depth, void* stream)
 {
-  const int rc = check_descs_args(resi_base, coeff_base, descs, n, bit_depth, "tr_fwd_batch");
-  if (rc) return rc > 0 ? VVCGPU_OK : rc;
-  const int rt = ensure_tables();
-  if (rt) return rt;
-  hipStream_t st = (hipStream_t)stream;
-  VvcTrTables tb;
-  const int rtb = vvcgpu_tr_tables(&tb);
-  if (rtb) return rtb;
-  const _Float16* image = vvcgpu_mfma_image(tb);
-  if (!image) return VVCGPU_E_DEVICE;
+  bool empty;
+  const int rc = check_descs_args(resi_base, coeff_base, descs, n, bit_depth, "tr_fwd_batch", &empty);
+  if (rc || empty) return rc;
+  VvcTrTables tb; const _Float16* image = nullptr;
+  const int ri = vvcgpu_tr_images(&tb, &image);                               // the tables (uploaded by the first call) and the f16 image of the matrix-core kernels
+  if (ri) return ri;
   // long calls: ONE launch of the residual chain's bodies in forward-only mode (packed matrix-core tiles for TUs with a 4- / 8-point side, lane groups
   // for 8x8 and smaller) instead of the small / matrix-core / dot2 kernels in a row -- on a real encoder's call mix those three were each bound by
   // their own per-wave latency (profiles/r04_shape_mix.txt)
   if (n >= 16384 && tr_use_mfma()) return vvcgpu_tr_chain_launch(1, resi_base, nullptr, coeff_base, descs, n, bit_depth, stream);
-  // long calls: the small TUs are binned on the device as well and the small kernel walks the bin lists (see small_setup)
-  const bool ordered = n >= 16384;
-  VvcScratch sc(st);
-  int* ws = sc.take<int>(2 + 2 * (size_t)n);                                // two counters, then the lists of dot2 and matrix-core TUs
-  int* smLists = ordered ? sc.take<int>(4 * (size_t)n) : nullptr;           // the bins of the small TUs
-  if (!ws || (ordered && !smLists)) return VVCGPU_E_DEVICE;
-  VVC_HIP(hipMemsetAsync(ws, 0, 2 * sizeof(int), st));
-  int* smCnt = nullptr; int* nextCnt = nullptr;
-  if (ordered)
-  {
-    int cur = 0;
-    int* counters = vvcgpu_counters(st, &cur);
-    if (!counters) return VVCGPU_E_DEVICE;
-    smCnt = counters + VVC_CTR_INTS * cur; nextCnt = counters + VVC_CTR_INTS * (cur ^ 1);
-  }
-  const int nb = cdiv(n, SM_DESCS), nl = cdiv(n, 4);
-  hipLaunchKernelGGL(tr_collect_large_kernel, dim3(cdiv(n, 1024)), dim3(1024), 0, st, descs, n, ws, tr_use_mfma(), smCnt, smLists, nextCnt);
-  hipLaunchKernelGGL(tr_fwd_small_kernel, dim3(nb < g_smallGrid ? nb : g_smallGrid), dim3(256), 0, st, resi_base, coeff_base, descs, n, bit_depth, tr_use_mfma(), smCnt, smLists);
-  hipLaunchKernelGGL(tr_fwd_mfma_kernel, dim3(nl < 768 ? nl : 768), dim3(256), 0, st, resi_base, coeff_base, descs, ws, ws + 2 + n, ws + 1, bit_depth, image);
-  hipLaunchKernelGGL(tr_fwd_large_kernel, dim3(nl < 768 ? nl : 768), dim3(256), 0, st, resi_base, coeff_base, descs, ws + 1, bit_depth);
-  if (ordered) VVC_LAUNCH_CHECK_COUNTERS(st);
-  VVC_LAUNCH_CHECK();
-  return VVCGPU_OK;
+  return tr_launch_lists(tr_fwd_small_kernel, tr_fwd_mfma_kernel, tr_fwd_large_kernel, resi_base, coeff_base, descs, n, bit_depth, image, (hipStream_t)stream);
 }
 
 int vvcgpu_tr_inv_batch(const vvc_coef* coeff_base, vvc_pel* resi_base, const vvcgpu_tr_desc* descs, int n,
                         int bit_depth, void* stream)
 {
-  const int rc = check_descs_args(coeff_base, resi_base, descs, n, bit_depth, "tr_inv_batch");
-  if (rc) return rc > 0 ? VVCGPU_OK : rc;
-  const int rt = ensure_tables();
-  if (rt) return rt;
-  hipStream_t st = (hipStream_t)stream;
-  VvcTrTables tb;
-  const int rtb = vvcgpu_tr_tables(&tb);
-  if (rtb) return rtb;
-  const _Float16* image = vvcgpu_mfma_image(tb);
-  if (!image) return VVCGPU_E_DEVICE;
+  bool empty;
+  const int rc = check_descs_args(coeff_base, resi_base, descs, n, bit_depth, "tr_inv_batch", &empty);
+  if (rc || empty) return rc;
+  VvcTrTables tb; const _Float16* image = nullptr;
+  const int ri = vvcgpu_tr_images(&tb, &image);                               // the tables (uploaded by the first call) and the f16 image of the matrix-core kernels
+  if (ri) return ri;
   // long calls: the residual chain's bodies in inverse-only mode (see vvcgpu_tr_fwd_batch)
   // (measured on the real call mix: 0.048 vs 0.054 ms at 35 k TUs, 0.126 vs 0.089 at 141 k -- there the three kernels' own latencies are amortised and their
   // lane-group forms run at five waves per SIMD against the chain kernel's three)
   if (n >= 16384 && n < 65536 && tr_use_mfma()) return vvcgpu_tr_chain_launch(2, nullptr, resi_base, const_cast<vvc_coef*>(coeff_base), descs, n, bit_depth, stream);
-  // long calls: the small TUs are binned on the device as well and the small kernel walks the bin lists (see small_setup)
-  const bool ordered = n >= 16384;
-  VvcScratch sc(st);
-  int* ws = sc.take<int>(2 + 2 * (size_t)n);                                // two counters, then the lists of dot2 and matrix-core TUs
-  int* smLists = ordered ? sc.take<int>(4 * (size_t)n) : nullptr;           // the bins of the small TUs
-  if (!ws || (ordered && !smLists)) return VVCGPU_E_DEVICE;
-  VVC_HIP(hipMemsetAsync(ws, 0, 2 * sizeof(int), st));
-  int* smCnt = nullptr; int* nextCnt = nullptr;
-  if (ordered)
-  {
-    int cur = 0;
-    int* counters = vvcgpu_counters(st, &cur);
-    if (!counters) return VVCGPU_E_DEVICE;
-    smCnt = counters + VVC_CTR_INTS * cur; nextCnt = counters + VVC_CTR_INTS * (cur ^ 1);
-  }
-  const int nb = cdiv(n, SM_DESCS), nl = cdiv(n, 4);
-  hipLaunchKernelGGL(tr_collect_large_kernel, dim3(cdiv(n, 1024)), dim3(1024), 0, st, descs, n, ws, tr_use_mfma(), smCnt, smLists, nextCnt);
-  hipLaunchKernelGGL(tr_inv_small_kernel, dim3(nb < g_smallGrid ? nb : g_smallGrid), dim3(256), 0, st, coeff_base, resi_base, descs, n, bit_depth, tr_use_mfma(), smCnt, smLists);
-  hipLaunchKernelGGL(tr_inv_mfma_kernel, dim3(nl < 768 ? nl : 768), dim3(256), 0, st, coeff_base, resi_base, descs, ws, ws + 2 + n, ws + 1, bit_depth, image);
-  hipLaunchKernelGGL(tr_inv_large_kernel, dim3(nl < 768 ? nl : 768), dim3(256), 0, st, coeff_base, resi_base, descs, ws + 1, bit_depth);
-  if (ordered) VVC_LAUNCH_CHECK_COUNTERS(st);
-  VVC_LAUNCH_CHECK();
-  return VVCGPU_OK;
+  return tr_launch_lists(tr_inv_small_kernel, tr_inv_mfma_kernel, tr_inv_large_kernel, coeff_base, resi_base, descs, n, bit_depth, image, (hipStream_t)stream);
 }
 
 int vvcgpu_dequant_tr_inv_batch(const vvc_coef* level_base, vvc_pel* resi_base, const vvcgpu_dqtr_desc* descs, int n,
                                 int bit_depth, vvc_coef* coeff_out, void* stream)
 {
   static_assert(sizeof(vvcgpu_dqtr_desc) == sizeof(vvcgpu_tr_desc), "descriptor layouts must stay interchangeable");
-  const int rc = check_descs_args(level_base, resi_base, descs, n, bit_depth, "dequant_tr_inv_batch");
-  if (rc) return rc > 0 ? VVCGPU_OK : rc;
+  bool empty;
+  const int rc = check_descs_args(level_base, resi_base, descs, n, bit_depth, "dequant_tr_inv_batch", &empty);
+  if (rc || empty) return rc;
   VVC_CHECK_ARG(coeff_out != level_base, "dequant_tr_inv_batch: coeff_out must not alias the levels");
-  const int rt = ensure_tables();
-  if (rt) return rt;
   hipStream_t st = (hipStream_t)stream;
-  VvcTrTables tb;
-  const int rtb = vvcgpu_tr_tables(&tb);
-  if (rtb) return rtb;
-  const _Float16* image = vvcgpu_mfma_image(tb);
-  if (!image) return VVCGPU_E_DEVICE;
+  VvcTrTables tb; const _Float16* image = nullptr;
+  const int ri = vvcgpu_tr_images(&tb, &image);                               // the tables (uploaded by the first call) and the f16 image of the matrix-core kernels
+  if (ri) return ri;
   // descriptors per workgroup: 64 when the batch is long (lane-group TUs need many per wave), fewer when that would leave compute units idle
   int per = SM_DESCS;
   while (per > 4 && cdiv(n, per) < 1024) per >>= 1;
@@ -2596,91 +1448,6 @@ int vvcgpu_dequant_tr_inv_batch(const vvc_coef* level_base, vvc_pel* resi_base, 
   }
   hipLaunchKernelGGL(dqtr_fused_kernel, dim3(nb < 512 ? nb : 512), dim3(256), 0, st, level_base, resi_base, descs, n, per, bit_depth, coeff_out, image,
                      tr_use_mfma(), nullptr, nullptr);
-  VVC_LAUNCH_CHECK();
-  return VVCGPU_OK;
-}
-
-int vvcgpu_quant_batch(const vvc_coef* coeff_base, vvc_coef* level_base, const vvcgpu_quant_desc* descs, int n, int bit_depth, uint32_t* abs_sum,
-                       void* stream)
-{
-  VVC_CHECK_ARG(n >= 0, "quant_batch: n %d", n);
-  if (n == 0) return VVCGPU_OK;
-  VVC_CHECK_ARG(coeff_base && level_base && descs && abs_sum, "quant_batch: null pointer");
-  VVC_CHECK_ARG(bit_depth >= 8 && bit_depth <= 10, "quant_batch: bit depth %d outside 8..10", bit_depth);
-  const int rt = ensure_tables();
-  if (rt) return rt;
-  hipStream_t st = (hipStream_t)stream;
-  VvcScratch sc(st);
-  int* list = sc.take<int>((size_t)n + 1);
-  if (!list) return VVCGPU_E_DEVICE;
-  VVC_HIP(hipMemsetAsync(list, 0, sizeof(int), st));
-  hipLaunchKernelGGL(quant_small_kernel, dim3(cdiv(n, 16)), dim3(256), 0, st, coeff_base, level_base, descs, n, bit_depth, abs_sum, list);
-  const int nl = cdiv(n, 4);
-  hipLaunchKernelGGL(quant_large_kernel, dim3(nl < 512 ? nl : 512), dim3(256), 0, st, coeff_base, level_base, descs, bit_depth, abs_sum, list);
-  VVC_LAUNCH_CHECK();
-  return VVCGPU_OK;
-}
-
-size_t vvcgpu_depquant_workspace_bytes(size_t total_coeffs, int n)
-{
-  (void)n;
-  const size_t c = (total_coeffs + 15) & ~(size_t)15;
-  return c * 16 + c * 8 + 256;                             // decisions (4 x u32 per position) + 8 level histories per TU
-}
-
-int vvcgpu_depquant_batch(const vvc_coef* coeff_base, vvc_coef* level_base, const vvcgpu_depquant_desc* descs, int n,
-                          const vvcgpu_dq_rates* rates, int bit_depth, uint32_t* abs_sum, size_t total_coeffs, void* ws, size_t ws_bytes,
-                          void* stream)
-{
-  VVC_CHECK_ARG(n >= 0, "depquant_batch: n %d", n);
-  if (n == 0) return VVCGPU_OK;
-  VVC_CHECK_ARG(coeff_base && level_base && descs && rates && abs_sum && ws, "depquant_batch: null pointer");
-  VVC_CHECK_ARG(bit_depth >= 8 && bit_depth <= 10, "depquant_batch: bit depth %d outside 8..10", bit_depth);
-  VVC_CHECK_ARG(total_coeffs >= 16 && ws_bytes >= vvcgpu_depquant_workspace_bytes(total_coeffs, n) && (reinterpret_cast<uintptr_t>(ws) & 15) == 0,
-                "depquant_batch: workspace of %zu bytes for %zu coefficients is too small (need %zu) or unaligned", ws_bytes, total_coeffs,
-                vvcgpu_depquant_workspace_bytes(total_coeffs, n));
-  const int rt = ensure_tables();
-  if (rt) return rt;
-  // the workspace is split as vvcgpu_depquant_workspace_bytes lays it out: c * 16 bytes of decisions, then the level histories
-  const size_t c = (total_coeffs + 15) & ~(size_t)15;
-  unsigned* dec = static_cast<unsigned*>(ws);
-  unsigned char* ctx = static_cast<unsigned char*>(ws) + c * 16;
-  VVC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(depquant_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, DQ_LDS_BYTES));
-  hipLaunchKernelGGL(depquant_kernel, dim3(cdiv(n, 64)), dim3(256), DQ_LDS_BYTES, (hipStream_t)stream, coeff_base, level_base, descs, n, rates, bit_depth,
-                     abs_sum, dec, ctx);
-  VVC_LAUNCH_CHECK();
-  return VVCGPU_OK;
-}
-
-size_t vvcgpu_rdoq_workspace_bytes(size_t total_coeffs, int n)
-{
-  (void)n;
-  const size_t c = (total_coeffs + 15) & ~(size_t)15;
-  return c * 24 + c * 16 + (c >> 4) * 8 + (c >> 4) + 256;  // three cost arrays, four rate-delta arrays, per group: flag cost + flag
-}
-
-int vvcgpu_rdoq_batch(const vvc_coef* coeff_base, vvc_coef* level_base, const vvcgpu_rdoq_desc* descs, int n,
-                      const vvcgpu_rdoq_rates* rates, int bit_depth, uint32_t* abs_sum, size_t total_coeffs, void* ws, size_t ws_bytes,
-                      void* stream)
-{
-  VVC_CHECK_ARG(n >= 0, "rdoq_batch: n %d", n);
-  if (n == 0) return VVCGPU_OK;
-  VVC_CHECK_ARG(coeff_base && level_base && descs && rates && abs_sum && ws, "rdoq_batch: null pointer");
-  VVC_CHECK_ARG(bit_depth >= 8 && bit_depth <= 10, "rdoq_batch: bit depth %d outside 8..10", bit_depth);
-  VVC_CHECK_ARG(total_coeffs >= 16 && ws_bytes >= vvcgpu_rdoq_workspace_bytes(total_coeffs, n) && (reinterpret_cast<uintptr_t>(ws) & 15) == 0,
-                "rdoq_batch: workspace of %zu bytes for %zu coefficients is too small (need %zu) or unaligned", ws_bytes, total_coeffs,
-                vvcgpu_rdoq_workspace_bytes(total_coeffs, n));
-  const int rt = ensure_tables();
-  if (rt) return rt;
-  const size_t c = (total_coeffs + 15) & ~(size_t)15;
-  unsigned char* base = static_cast<unsigned char*>(ws);
-  double* wsD = reinterpret_cast<double*>(base);
-  int* wsI = reinterpret_cast<int*>(base + c * 24);
-  double* wsCG = reinterpret_cast<double*>(base + c * 40);
-  unsigned char* wsSG = base + c * 40 + (c >> 4) * 8;
-  // (a group flag is always written before a left / upper neighbour group reads it: the workspace needs no clearing)
-  hipLaunchKernelGGL(rdoq_kernel, dim3(cdiv(n, 16)), dim3(256), 0, (hipStream_t)stream, coeff_base, level_base, descs, n, rates, bit_depth,
-                     abs_sum, wsD, wsI, wsCG, wsSG, c);
   VVC_LAUNCH_CHECK();
   return VVCGPU_OK;
 }
