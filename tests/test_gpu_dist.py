@@ -176,7 +176,7 @@ def test_sad_search_tie_rule():
 
 @pytest.mark.parametrize("h,ss,nx,ny,content", [(16, 1, 39, 39, "smooth"), (16, 1, 39, 39, "flat"), (16, 1, 39, 39, "ties"), (16, 0, 20, 13, "ties"), (16, 0, 17, 9, "smooth"), (8, 0, 40, 5, "extreme"),
                                                (32, 2, 7, 30, "smooth"), (16, 1, 1, 1, "smooth"),
-                                               # lambda x bits beyond 2^29 / 2^30: the quad group form hands over to the pair group form, that one to the per-block form
+                                               # lambda x bits beyond 2^29: the quad group form hands over to the per-block quad form (5e6, and 2e7 beyond the former pair group form's 2^30)
                                                (16, 1, 39, 39, "ties-lambda5e6"), (16, 1, 39, 39, "flat-lambda2e7")])
 def test_sad_search_group_runs(h, ss, nx, ny, content):
     """16-wide blocks on a 5-stride raster take the GROUP kernel (one staged window per run of horizontal neighbours, up to 8 blocks):

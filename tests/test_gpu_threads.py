@@ -307,7 +307,7 @@ def _depquant_job():
 
 
 def _tz_job():
-    """vvcgpu_tz_search_batch: scratch claimed in tzsearch.hip (raster records) and, through it, in dist.hip"""
+    """vvcgpu_tz_search_batch: scratch claimed in tzsearch.hip (raster records) and, through it, in sadsearch.hip"""
     ops = _ops()
     rng = np.random.default_rng(10096)
     W, H, M, bd, n = 320, 256, 160, 10, 300

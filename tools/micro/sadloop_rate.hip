@@ -1,4 +1,4 @@
-// micro-test: what one SIMD sustains on the raster kernels' stage body (csrc/raster7.hip, csrc/dist.hip quad form) -- per stage 8 ds_read_b64 of a
+// micro-test: what one SIMD sustains on the raster kernels' stage body (csrc/raster7.hip, csrc/sadsearch.hip quad form) -- per stage 8 ds_read_b64 of a
 // window span + one 64-byte scalar load of the packed original row + 32 v_sad_u16 (four accumulators) + 2 v_bfi_b32, software-pipelined one
 // stage ahead -- with 4 waves per SIMD (one 1024-thread workgroup per CU, all 256 CUs busy).  Variants switch parts off:
 //   bit 0: no LDS reads   bit 1: no scalar load   bit 2: accumulators interleaved (no 8-deep dependent chains)   bit 3: VGPR original (no SGPR operand)

@@ -57,7 +57,7 @@ int vvcgpu_frac_refine_launch(const vvc_pel* org, int org_stride, const vvc_pel*
 int vvcgpu_mc_batch_impl(const vvc_pel* ref0_base, const vvc_pel* ref1_base, vvc_pel* dst_base, const vvcgpu_mc_desc* descs, int n, int bit_depth,
                          int clp_min, int clp_max, void* stream, VvcScratch& sc, bool skip_fast, bool sub44, bool serve_in_kernel = false);
 
-// Raster stage of whole-PU TZ searches as its own launch (tzsearch.hip -> dist.hip): one record per PU, written on the device.  An active
+// Raster stage of whole-PU TZ searches as its own launch (tzsearch.hip -> sadsearch.hip): one record per PU, written on the device.  An active
 // PU's raster is the nx x ny grid of step 5 whose position (0, 0) is the motion vector (x0, y0); blocks[] holds the block's origin in the
 // original and the reference position of the ZERO vector (as in vvcgpu_sad_search); the best candidate comes back as the packed
 // key (cost << 24 | j * nx + i) in best[].cost (all-ones: no candidate).  Every PU of the launch is w x h with row sub-sampling sub_shift.
@@ -80,6 +80,14 @@ int vvcgpu_tr_tables(VvcTrTables* out);
   do { hipError_t e_ = (call); if (e_ != hipSuccess) {                                       \
          vvcgpu_set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
          return VVCGPU_E_DEVICE; } } while (0)
+
+// A kernel may use more than 48 KB of dynamic LDS only after this has been allowed for it: VVC_HIP(vvc_allow_lds(kernel, bytes)) in front of the launch
+// (host-only and idempotent, so it is simply repeated per call; nothing to do up to 48 KB)
+template <class K> static inline hipError_t vvc_allow_lds(K kernel, size_t bytes)
+{
+  if (bytes <= 48 * 1024) return hipSuccess;
+  return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+}
 
 #define VVC_LAUNCH_CHECK()                                                                    \
   do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) {                            \

@@ -634,7 +634,7 @@ int vvcgpu_depquant_batch(const vvc_coef* coeff_base, vvc_coef* level_base, cons
   const size_t c = (total_coeffs + 15) & ~(size_t)15;
   unsigned* dec = static_cast<unsigned*>(ws);
   unsigned char* ctx = static_cast<unsigned char*>(ws) + c * 16;
-  VVC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(depquant_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, TQ_LDS_BYTES));
+  VVC_HIP(vvc_allow_lds(depquant_kernel, TQ_LDS_BYTES));
   hipLaunchKernelGGL(depquant_kernel, dim3(cdiv(n, 64)), dim3(256), TQ_LDS_BYTES, (hipStream_t)stream, coeff_base, level_base, descs, n, rates, bit_depth,
                      abs_sum, dec, ctx, tb);
   VVC_LAUNCH_CHECK();

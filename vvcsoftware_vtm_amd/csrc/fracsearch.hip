@@ -1145,8 +1145,7 @@ int vvcgpu_frac_refine_launch(const vvc_pel* org, int org_stride, const vvc_pel*
     VVC_LAUNCH_CHECK();
     return VVCGPU_OK;
   }
-  if (smem > 64 * 1024)
-    VVC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(frac_refine_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+  VVC_HIP(vvc_allow_lds(frac_refine_kernel, smem));
   hipLaunchKernelGGL(frac_refine_kernel, dim3(cdiv(nblocks, groups)), dim3(256), smem, st, org, org_stride, ref, ref_stride, blocks,
                      nblocks, w, h, bit_depth, clp_min, clp_max, use_hadamard, *mvcost_host, preds, groups, (int)groupBytes, results);
   VVC_LAUNCH_CHECK();

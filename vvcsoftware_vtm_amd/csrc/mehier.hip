@@ -58,7 +58,7 @@ struct MhGeom
   unsigned magicNq, magicDl;                           // ceil(65536 / n): v / n == (v * magic) >> 16 for the slot indices (< 448, n <= 10)
 };
 
-// original rows packed per 16x16 block: [block][sampled row][even 8 dwords | odd 8 dwords], biased; layouts as r5c_pack_org_kernel (dist.hip).
+// original rows packed per 16x16 block: [block][sampled row][even 8 dwords | odd 8 dwords], biased; layouts as r5c_pack_org_kernel (sadsearch.hip).
 // Packed by a launch of its own in front of the search (7.5 us per 4K picture).  Round 6 measured the search kernel packing the rows of its super-blocks
 // ITSELF (first super-block of a run by every thread, the rest by the four waves without a second-round unit, read back by explicit scalar loads): exact,
 // and 6 us faster when the entry is timed alone in a loop (178 against 185 us) -- but 220 against 192 + 7.5 us inside the picture's workload, where the rows come
@@ -547,7 +547,7 @@ int vvcgpu_me_hier_search(const vvc_pel* org, int org_stride, const vvc_pel* ref
   if (!packed) return VVCGPU_E_DEVICE;
   hipLaunchKernelGGL(mh_pack_org_kernel, dim3((unsigned)(((size_t)nblocks * g.hs * 4 + 255) / 256)), dim3(256), 0, st, org, org_stride, c.org_x, c.org_y, c.n16x, nblocks, g.hs, c.sub_shift, packed);
   VVC_LAUNCH_CHECK();
-  VVC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(me_hier_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+  VVC_HIP(vvc_allow_lds(me_hier_kernel, smem));
   unsigned long long* diag = nullptr;
 #ifdef MH_DIAG
   const bool wantDiag = getenv("VVCGPU_MH_DIAG") != nullptr;                 // measurement aid (tools/mehier_time.py, a -DMH_DIAG build): phase stamps of one workgroup

@@ -1,6 +1,6 @@
-// raster_dev.h -- device pieces shared by the step-5 raster search kernels of dist.hip and the hierarchical search of mehier.hip:
+// raster_dev.h -- device pieces shared by the step-5 raster search kernels of sadsearch.hip and the hierarchical search of mehier.hip:
 // wave minima, the LDS window fill, and the QUAD SAD loop (a lane owns four consecutive raster columns; the org rows are wave-uniform scalar
-// operands from a packed copy of the block).  See the kernel comments in dist.hip for the measurements behind these forms.
+// operands from a packed copy of the block).  See the kernel comments in sadsearch.hip for the measurements behind these forms.
 #pragma once
 #include "common.h"
 

@@ -1222,8 +1222,7 @@ int vvcgpu_sao_stats(const vvc_pel* org, int org_stride, const vvc_pel* rec, int
   const size_t tileBytes = packed ? (((size_t)((SAO_PK_THREADS / ctu_w) * SAO_PK_ROWS + 6) * (ctu_w + 2) * 2) + 15) & ~(size_t)15
                                   : (((size_t)(ctu_h + 2) * (ctu_w + 2) * 2) + 15) & ~(size_t)15;
   const size_t smem = tileBytes + 16 * 32 * 8 + 40 * 4;
-  if (smem > 48 * 1024)
-    VVC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(sao_stats_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+  VVC_HIP(vvc_allow_lds(sao_stats_kernel, smem));
   hipLaunchKernelGGL(sao_stats_kernel, dim3(wCtu, hCtu), dim3(nthreads), smem, (hipStream_t)stream, org, org_stride, rec,
                      rec_stride, width, height, ctu_w, ctu_h, wCtu, bit_depth - 5, avail, skip_lines_r, skip_lines_b,
                      reinterpret_cast<long long*>(out));
@@ -1294,8 +1293,7 @@ int vvcgpu_sao_stats_picture(const vvcgpu_planes* org, const vvcgpu_planes* rec,
   }
   tileBytes = (tileBytes + 15) & ~(size_t)15;
   const size_t smem = tileBytes + 16 * 32 * 8 + 40 * 4;
-  if (smem > 48 * 1024)
-    VVC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(sao_stats_picture_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+  VVC_HIP(vvc_allow_lds(sao_stats_picture_kernel, smem));
   p.total = end; p.xcd = vvc_xcd_on();
   hipLaunchKernelGGL(sao_stats_picture_kernel, dim3(vvc_xcd_grid2(p.a[0].wgEnd, end, p.xcd)), dim3(nthreads), smem, (hipStream_t)stream, p);
   VVC_LAUNCH_CHECK();
@@ -1340,7 +1338,7 @@ static int alf_stats_picture_impl(const vvcgpu_planes* org, const vvcgpu_planes*
     a.out7 = o7; a.out5 = reinterpret_cast<unsigned long long*>(out5); a.outC[0] = ocb; a.outC[1] = ocr;
     auto launch = [&](auto kernel, int ldsBytes) -> int
     {
-      VVC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, ldsBytes));
+      VVC_HIP(vvc_allow_lds(kernel, ldsBytes));
       hipLaunchKernelGGL(kernel, dim3(vvc_xcd_grid(nCtu, a.xcd)), dim3(ACT), ldsBytes, st, a);
       return VVCGPU_OK;
     };

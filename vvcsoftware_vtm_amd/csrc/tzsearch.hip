@@ -682,7 +682,7 @@ static int tz_search(const vvc_pel* org, int org_stride, const vvc_pel* ref, int
       hipLaunchKernelGGL(tz_search_kernel<1>, dim3((n + 3) / 4), dim3(256), (size_t)ldsDwords * 4, st, org, org_stride, ref, ref_stride, pus, n, c, results, ldsDwords, phase, save, rblk, rper, rbest);
   };
   // Split form (cfg.uniform_pu = h << 16 | w: the caller states that EVERY PU of the batch is w x h with 2:1 row sub-sampling): the raster stage,
-  // 86 % of the probes of a search that enters it, runs as the quad raster kernel of dist.hip between two launches of the state machine --
+  // 86 % of the probes of a search that enters it, runs as the quad raster kernel of sadsearch.hip between two launches of the state machine --
   // the in-kernel raster round works one wavefront per PU at ~8 % of the v_sad_u16 issue rate, the raster kernel at ~60 %.
   const int uw = c.uniform_pu & 0xFFFF, uh = (c.uniform_pu >> 16) & 0xFFFF;
   const int gridMax = (2 * c.search_range) / 5 + 1;
