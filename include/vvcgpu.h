@@ -44,7 +44,7 @@ int         vvcgpu_set_device(int device);
  * 4 mvcost, 5 search_best, 6 if_desc, 7 mc_desc, 8 pelop_desc, 9 pelop_cfg, 10 tr_desc, 11 frac_blk, 12 frac_result,
  * 13 dqtr_desc, 14 afg_desc, 15 afe_desc, 16 tz_pu, 17 tz_cfg, 18 intra_desc, 19 cclm_desc, 20 intra_fill_desc, 21 imv_pu, 22 imv_result, 23 quant_desc,
  * 24 dq_rates, 25 depquant_desc, 26 rdoq_rates, 27 rdoq_desc, 28 intra_satd_desc, 29 affine_iter, 30 me_hier_cfg, 31 wp_param,
- * 32 wp_sad_cand, 33 tile_stats; -1 for unknown ids. */
+ * 32 wp_sad_cand, 33 tile_stats, 34 affine_me_item, 35 affine_me_cfg, 36 affine_me_result, 37 affine_me_step; -1 for unknown ids. */
 int         vvcgpu_sizeof(int struct_id);
 
 /* ---- device memory helpers for host-side callers (the reference keeps pictures in host memory; the shim stages them).
@@ -546,7 +546,8 @@ int vvcgpu_affine_equal_coeff_batch(const vvc_pel* resi_base, const int32_t* der
  * caller's "2 org - other prediction" block, as in the reference.  pu.first_desc: index of the PU's first sub-block in subblock_ws (n_subblocks
  * entries = sum of (w / 4) (h / 4), device memory the call may overwrite).  coeff_out: n x 7 x 7 int64 as vvcgpu_affine_equal_coeff_batch;
  * dist_out (may be NULL): n x uint64, dist_kind 0 SAD / 1 Hadamard (what xAffineMotionEstimation's cost uses) of org against the prediction.
- * The caller solves the 4 x 4 / 6 x 6 system and updates the vectors on the host (double arithmetic, InterSearch.cpp:3536-3600).                    */
+ * The caller solves the 4 x 4 / 6 x 6 system and updates the vectors on the host (double arithmetic, InterSearch.cpp:3536-3600);
+ * vvcgpu_affine_me_batch below runs the whole loop on the device.                                                                                 */
 typedef struct vvcgpu_affine_iter {
   vvcgpu_affine_pu pu;
   int64_t org_off;                      /* elements from org_base */
@@ -556,6 +557,50 @@ int vvcgpu_affine_me_iter_batch(const vvc_pel* org_base, const vvc_pel* ref_base
                                 int n_subblocks, vvcgpu_mc_desc* subblock_ws, int dist_kind, int pic_w, int pic_h, int max_cu_w, int max_cu_h,
                                 int ref_origin_x, int ref_origin_y, int ref_stride, int bit_depth, int clp_min, int clp_max, int64_t* coeff_out,
                                 uint64_t* dist_out, void* stream);
+
+/* The WHOLE affine gradient search of a PU against one reference picture (InterSearch::xAffineMotionEstimation, InterSearch.cpp:3286-3743; solveEqual
+ * :3102-3179; clipMv Mv.cpp:64-80; Mv::roundMV2SignalPrecision Mv.h:242-247; RdCost::getBitsOfVectorWithPredictor / getCost RdCost.h:172-199) for a list
+ * of independent searches in ONE launch with no host synchronisation inside: the owner of a PU (a wavefront up to 1024 samples, a workgroup above)
+ * carries it from the start vectors through every iteration -- sub-block vectors, 4x4 sub-block prediction (kept in LDS, never written out), error,
+ * Sobel and equation sums, the 4 x 4 / 6 x 6 solve in IEEE double arithmetic (the double -> int conversions give what x86 cvttsd2si gives: truncation,
+ * 0x80000000 for NaN or out of range), vector update, Hadamard cost, vector bits, keep-if-strictly-better -- to the reference's termination rule.
+ * Every result is the one the reference computes.  Start (:3362-3415): the start vectors are clipped, predicted and costed as step 0.
+ * items, results, trace: device memory.  The library cannot validate device-resident items on the host: an item outside the contract (a side outside
+ * 16..128 or no multiple of 4, pu.bi != 0) is skipped and gets cost = ~0 (UINT64_MAX), steps = 0 and zero vectors / bits (the sentinel convention of
+ * vvcgpu_mc_dist_batch).  n == 0 is a no-op; null pointers (trace may be NULL), non-positive picture / CTU sizes or ref_stride, clp_min > clp_max and a
+ * lambda outside [0, 2^20) return VVCGPU_E_ARG, a bit depth outside 8..10 VVCGPU_E_UNSUPPORTED, before any device work.  Reference samples: the
+ * contract of vvcgpu_affine_me_iter_batch (sub-block vectors are clipped to the picture + 8 samples / - CTU - 8 samples; the 8-tap window reaches 4
+ * samples further, so a margin of max_cu + 12 readable samples around the picture serves every search).                                          */
+#define VVCGPU_AFFINE_ME_MAX_STEPS 8    /* the start vectors + at most 7 iterations */
+typedef struct {                        /* one (PU, reference picture) search               sizeof == 128 */
+  vvcgpu_affine_pu pu;    /* pos_x/pos_y = pu.cu->lumaPos(), w, h (16..128, multiples of 4), six_param = cu->affineType; bi must be 0;
+                             mv[0][k] = acMv[k] on entry in 1/16 sample units (after Mv::setHighPrec); mv[1], dst_off, dst_stride, first_desc: 0 */
+  int64_t  org_off;       /* elements from org_base; for a bi-predictive search the caller's "2 org - other prediction" block, any int16 */
+  int32_t  org_stride;
+  int32_t  half_weight;   /* bBi: cost weight 0.5 and the shorter iteration limits */
+  int32_t  mvp[3][2];     /* acMvPred[k] in 1/16 units (setHighPrec applied by the caller; exact for a low-precision predictor) */
+  uint32_t bits;          /* ruiBits on entry */
+  int32_t  reserved;
+} vvcgpu_affine_me_item;
+typedef struct {                        /* host struct                                      sizeof == 64 */
+  double  lambda;         /* RdCost::m_motionLambda */
+  int32_t pic_w, pic_h, max_cu_w, max_cu_h;        /* clipMv, sub-block vector clip */
+  int32_t ref_origin_x, ref_origin_y, ref_stride;  /* as vvcgpu_affine_me_iter_batch */
+  int32_t bit_depth, clp_min, clp_max;
+  int32_t affine_type;    /* sps.getSpsNext().getUseAffineType(): iteration limits 3/4 (6-param), 3/5 (4-param) for bi/uni; 0: 5/7 */
+  int32_t reserved[3];
+} vvcgpu_affine_me_cfg;
+typedef struct {                        /* sizeof == 40 */
+  int32_t  mv[3][2];      /* acMv on return (1/16 units); mv[2] of a 4-parameter search = the input, untouched */
+  uint32_t bits;          /* ruiBits on return */
+  uint32_t steps;         /* predictions evaluated: 1 + iterations that reached the second xPredAffineBlk */
+  uint64_t cost;          /* ruiCost */
+} vvcgpu_affine_me_result;
+typedef struct { int32_t mv[3][2]; uint64_t cost; } vvcgpu_affine_me_step;   /* sizeof == 32 */
+/* trace (may be NULL): n x VVCGPU_AFFINE_ME_MAX_STEPS entries, entry s of a search = the vectors and the cost of its evaluated prediction s, unused
+ * entries zero. */
+int vvcgpu_affine_me_batch(const vvc_pel* org_base, const vvc_pel* ref_base, const vvcgpu_affine_me_item* items, int n,
+                           const vvcgpu_affine_me_cfg* cfg_host, vvcgpu_affine_me_result* results, vvcgpu_affine_me_step* trace, void* stream);
 
 /* ---- N2 ("next" row): integer-sample TZ search of whole PUs, on the device  (InterSearch::xTZSearch,
  *          EncoderLib/InterSearch.cpp:1971-2252, with xTZSearchHelp :249-343, xTZ2PointSearch :349-374,

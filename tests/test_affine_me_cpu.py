@@ -1,0 +1,139 @@
+"""CPU checks of the whole-PU affine motion search (vvcgpu_affine_me_batch): the tests' restatement of InterSearch::xAffineMotionEstimation
+(tests/affine_me_cases.py) against the compiled reference's own results (tests/golden/affine_me.npz), the x86 double -> int conversion it emulates,
+the four structs' layout against the header, and the host-side argument checks (no device is touched)."""
+import ctypes as C
+import os
+import shlex
+import subprocess
+
+import numpy as np
+import pytest
+
+import affine_me_cases as amc
+from vvcsoftware_vtm_amd import abi, capi
+
+G = os.path.join(os.path.dirname(__file__), "golden")
+W, H = 256, 128
+
+
+def _lib():
+    if not os.path.exists(capi.LIB_PATH):
+        import __graft_entry__ as g
+        g.build()
+    return capi.lib()
+
+
+@pytest.mark.parametrize("bd", [10, 8])
+def test_restatement_equals_reference_golden(bd):
+    """every search of the fixture: vectors, bits and cost of the restatement == the reference's xAffineMotionEstimation; the fixture holds the
+    cases the device tests rely on (both models, both weights under both iteration-limit rules, early stops, full runs, a best that is not the
+    last step, a flat PU, the listed sizes)"""
+    g = np.load(os.path.join(G, "affine_me.npz"))
+    k = "bd%d_" % bd
+    items, ats, want = g[k + "items"], g[k + "affine_type"], g[k + "want"]
+    assert len(items) >= 30
+    refp = amc.pad(g[k + "ref"])
+    seen = set()
+    for at in (1, 0):
+        idx = np.nonzero(ats == at)[0]
+        res, trace = amc.search_all(g[k + "org"], refp, amc.make_cfg(float(g[k + "lambda"]), W, H, bd, at), items[idx])
+        for j, i in enumerate(idx):
+            assert np.array_equal(res[j]["mv"], want[i]["mv"]) and res[j]["bits"] == want[i]["bits"] and res[j]["cost"] == want[i]["cost"], (i, res[j], want[i])
+            assert res[j]["steps"] == want[i]["steps"]
+            n, six, hw = int(res[j]["steps"]), bool(items[i]["pu"]["six_param"]), bool(items[i]["half_weight"])
+            seen.add((six, hw, at))
+            seen.add((int(items[i]["pu"]["w"]), int(items[i]["pu"]["h"])))
+            if n == 1 + amc.iter_limit(six, hw, at):
+                seen.add("limit")
+            if 1 < n < 1 + amc.iter_limit(six, hw, at):
+                seen.add("early")
+            if n > 1 and trace[j][n - 1]["cost"] != res[j]["cost"]:
+                seen.add("best is not last")
+            assert (trace[j][n:]["cost"] == 0).all() and (trace[j][n:]["mv"] == 0).all()
+    assert {(s, h, a) for s in (False, True) for h in (False, True) for a in (0, 1)} <= seen
+    assert {"limit", "early", "best is not last", (16, 16), (32, 32), (64, 16), (16, 64), (64, 32), (128, 128), (16, 128), (128, 16)} <= seen
+    assert (want["steps"] == 1).any()
+
+
+def test_double_to_int_conversion_is_the_x86_one():
+    nan = float("nan")
+    assert amc.cvttsd2si(nan) == amc.cvttsd2si(1e300) == amc.cvttsd2si(-1e300) == amc.cvttsd2si(float("inf")) == -(1 << 31)
+    assert amc.cvttsd2si(2147483647.9) == 2147483647 and amc.cvttsd2si(2147483648.0) == -(1 << 31)
+    assert amc.cvttsd2si(-2147483648.9) == -(1 << 31) and amc.cvttsd2si(-2147483649.0) == -(1 << 31)
+    assert amc.cvttsd2si(0.999) == 0 and amc.cvttsd2si(-0.999) == 0 and amc.cvttsd2si(-7.5) == -7
+    # the quantiser (int)(d * 4 + SIGN(d) * 0.5) << 2: NaN and out-of-range values wrap to 0, +-0.124999 stays 0, +-0.125 is one quarter sample
+    for d in (nan, 1e300, -1e300):
+        assert amc.delta_of(d) == 0
+    assert amc.delta_of(0.124999) == 0 and amc.delta_of(-0.124999) == 0
+    assert amc.delta_of(0.125) == 4 and amc.delta_of(-0.125) == -4 and amc.delta_of(0.0) == 0 and amc.delta_of(-0.0) == 0
+    assert amc.delta_of(3.0) == 48 and amc.delta_of(-2.6) == -40
+    # 2^29 quarter samples wrap in the shift as in C
+    assert amc.delta_of(float(1 << 27)) == amc.wrap32((1 << 29) << 2) == -(1 << 31)
+
+
+def test_solver_takes_the_zero_pivot_exits():
+    z = amc.deltas(np.zeros((7, 7), np.int64), 16, 16, False)
+    assert z == [[0, 0], [0, 0], [0, 0]]
+    m = np.zeros((7, 7), np.int64)
+    m[1:5, 0:5] = [[4, 0, 0, 0, 8], [0, 2, 0, 0, 2], [0, 0, 1, 0, 3], [0, 0, 0, 8, 16]]
+    assert amc.deltas(m, 16, 16, False) == [[32, 48], [32 + 16 * 16, 48 - 2 * 16 * 16], [0, 0]]
+    m[4, 3] = 0                                              # the last pivot: every parameter stays 0
+    assert amc.deltas(m, 16, 16, False) == [[0, 0], [0, 0], [0, 0]]
+
+
+MIRRORS = {"vvcgpu_affine_me_item": (34, abi.AFFINE_ME_ITEM, 128), "vvcgpu_affine_me_cfg": (35, abi.AffineMeCfg, 64),
+           "vvcgpu_affine_me_result": (36, abi.AFFINE_ME_RESULT, 40), "vvcgpu_affine_me_step": (37, abi.AFFINE_ME_STEP, 32)}
+
+
+def _fields(m):
+    if isinstance(m, np.dtype):
+        return [(n, m.fields[n][1], m.fields[n][0].itemsize) for n in m.names]
+    return [("lambda" if f[0] == "lambda_" else f[0], getattr(m, f[0]).offset, getattr(m, f[0]).size) for f in m._fields_]
+
+
+def test_struct_mirrors_match_the_header(tmp_path):
+    lib = _lib()
+    lines = []
+    for cname, (sid, m, size) in MIRRORS.items():
+        assert lib.vvcgpu_sizeof(sid) == size == (m.itemsize if isinstance(m, np.dtype) else C.sizeof(m)), cname
+        lines.append('  printf("%%s . %%zu %%zu\\n", "%s", (size_t)0, sizeof(%s));\n' % (cname, cname))
+        lines += ['  printf("%%s %%s %%zu %%zu\\n", "%s", "%s", offsetof(%s, %s), sizeof(((%s*)0)->%s));\n' % (cname, f, cname, f, cname, f)
+                  for f, _, _ in _fields(m)]
+    src = tmp_path / "afm.c"
+    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "vvcgpu.h"\nint main(void)\n{\n' + "".join(lines) + "  return 0;\n}\n")
+    exe = tmp_path / "afm"
+    r = subprocess.run(shlex.split(os.environ.get("CC", "cc")) + ["-I", os.path.dirname(capi.HEADER), str(src), "-o", str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    got = {}
+    for line in subprocess.check_output([str(exe)], text=True).splitlines():
+        c, f, off, sz = line.split()
+        got[(c, f)] = (int(off), int(sz))
+    for cname, (sid, m, size) in MIRRORS.items():
+        assert got[(cname, ".")] == (0, size)
+        for f, off, sz in _fields(m):
+            assert got[(cname, f)] == (off, sz), (cname, f)
+    assert abi.AFFINE_ME_MAX_STEPS == 8 and "#define VVCGPU_AFFINE_ME_MAX_STEPS 8" in open(capi.HEADER).read()
+
+
+def test_argument_checks_need_no_device():
+    lib = _lib()
+    P = C.c_void_p(4096)                     # never dereferenced: every check below fails before device work
+    good = amc.make_cfg(30.0, 256, 128, 10, 1)
+    call = lambda *a: lib.vvcgpu_affine_me_batch(*a)
+    assert call(None, None, None, 0, None, None, None, None) == 0                                    # n == 0: a no-op
+    assert call(P, P, P, -1, C.byref(good), P, P, None) == -1 and b"affine_me_batch" in lib.vvcgpu_last_error()
+    for k in (0, 1, 2, 4, 5):                                                                          # org, ref, items, cfg, results (trace may be null)
+        a = [P, P, P, 3, C.byref(good), P, None, None]
+        a[k] = None
+        assert call(*a) == -1 and b"affine_me_batch: null" in lib.vvcgpu_last_error(), k
+    for field, v in (("pic_w", 0), ("pic_h", -4), ("max_cu_w", 0), ("max_cu_h", 0), ("ref_stride", 0)):
+        c = amc.make_cfg(30.0, 256, 128, 10, 1)
+        setattr(c, field, v)
+        assert call(P, P, P, 3, C.byref(c), P, None, None) == -1 and b"affine_me_batch: geometry" in lib.vvcgpu_last_error(), field
+    c = amc.make_cfg(30.0, 256, 128, 10, 1)
+    c.clp_min, c.clp_max = 5, 4
+    assert call(P, P, P, 3, C.byref(c), P, None, None) == -1 and b"clip" in lib.vvcgpu_last_error()
+    for lam in (-1.0, float("nan"), 2.0 ** 20):
+        assert call(P, P, P, 3, C.byref(amc.make_cfg(lam, 256, 128, 10, 1)), P, None, None) == -1 and b"lambda" in lib.vvcgpu_last_error()
+    for bd in (7, 11):
+        assert call(P, P, P, 3, C.byref(amc.make_cfg(30.0, 256, 128, bd, 1)), P, None, None) == -3 and b"bit depth" in lib.vvcgpu_last_error()

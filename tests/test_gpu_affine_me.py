@@ -1,0 +1,119 @@
+"""vvcgpu_affine_me_batch on the device: whole affine motion searches (InterSearch::xAffineMotionEstimation) in one launch, against the compiled
+reference's results (tests/golden/affine_me.npz) and, step by step, against the tests' restatement (tests/affine_me_cases.py, pinned to the
+reference by tests/test_affine_me_cpu.py)."""
+import functools
+import os
+import threading
+
+import numpy as np
+import pytest
+import torch
+
+import affine_me_cases as amc
+from vvcsoftware_vtm_amd import abi
+
+pytestmark = pytest.mark.gpu
+G = os.path.join(os.path.dirname(__file__), "golden")
+W, H = 256, 128
+
+# (w, h, six_param, half_weight): wave-form PUs (up to 1024 samples; 32x32 is the last) and workgroup-form PUs (64x32 is the first) mixed; sides
+# that are no power of two; both models and both weights
+SIZES = [(32, 32, 0, 0), (64, 32, 1, 0), (16, 16, 1, 1), (128, 64, 0, 1), (16, 24, 1, 0), (64, 16, 0, 0), (16, 64, 1, 0), (128, 128, 1, 0),
+         (32, 16, 0, 1), (48, 32, 0, 0), (16, 128, 0, 0), (128, 16, 1, 1), (64, 64, 0, 0), (20, 20, 1, 0), (32, 64, 1, 1), (64, 32, 0, 1),
+         (32, 32, 1, 1), (16, 16, 0, 0), (24, 48, 0, 0), (128, 32, 0, 0), (32, 128, 1, 0), (40, 24, 1, 0), (16, 32, 0, 1), (64, 16, 1, 1),
+         (32, 32, 0, 0), (64, 64, 1, 1), (16, 16, 1, 0), (36, 28, 0, 0), (64, 32, 1, 0), (32, 16, 1, 0), (16, 64, 0, 1), (128, 128, 0, 1),
+         (32, 32, 1, 0), (16, 20, 0, 0), (96, 32, 1, 0), (16, 16, 0, 1), (64, 48, 0, 0)]
+
+
+def dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def run(org, refp, cfg, items, want_trace=True):
+    from vvcsoftware_vtm_amd import ops
+    res, trace = ops.affine_me_batch(dev(org), dev(refp), ops.struct_to_device(items), len(items), cfg, want_trace)
+    torch.cuda.synchronize()
+    res = res.cpu().numpy().view(abi.AFFINE_ME_RESULT)
+    return res, (trace.cpu().numpy().view(abi.AFFINE_ME_STEP).reshape(len(items), abi.AFFINE_ME_MAX_STEPS) if want_trace else None)
+
+
+@functools.lru_cache(maxsize=None)
+def fresh(n, affine_type):
+    """seeded inputs and the restatement's answer, computed once: n searches in shuffled order"""
+    order = np.random.default_rng(n).permutation(len(SIZES))[:n]
+    org, refp, cfg, items = amc.fresh_set(900 + n, 10 if n != 5 else 8, [SIZES[i] for i in order], affine_type)
+    res, trace = amc.search_all(org, refp, cfg, items)
+    return org, refp, cfg, items, res, trace
+
+
+@pytest.mark.parametrize("bd", [10, 8])
+def test_results_equal_the_reference_golden(bd):
+    g = np.load(os.path.join(G, "affine_me.npz"))
+    k = "bd%d_" % bd
+    items, ats, want = g[k + "items"], g[k + "affine_type"], g[k + "want"]
+    refp = amc.pad(g[k + "ref"])
+    for at in (1, 0):
+        idx = np.nonzero(ats == at)[0]
+        res, _ = run(g[k + "org"], refp, amc.make_cfg(float(g[k + "lambda"]), W, H, bd, at), items[idx])
+        for j, i in enumerate(idx):
+            assert res[j].tobytes() == want[i].tobytes(), (bd, at, i, res[j], want[i])
+
+
+@pytest.mark.parametrize("n,affine_type", [(1, 1), (5, 0), (37, 1)])
+def test_results_and_trace_equal_the_restatement(n, affine_type):
+    org, refp, cfg, items, want, want_trace = fresh(n, affine_type)
+    if n == 37:
+        px = items["pu"]["w"].astype(int) * items["pu"]["h"]
+        assert (px <= 1024).any() and (px > 1024).any() and (px == 1024).any() and (px == 2048).any()
+        assert (want["steps"] > 2).sum() >= n // 3                                            # the searches move
+    res, trace = run(org, refp, cfg, items)
+    for i in range(n):
+        assert np.array_equal(trace[i], want_trace[i]), (i, items[i]["pu"], trace[i], want_trace[i])
+        assert res[i].tobytes() == want[i].tobytes(), (i, res[i], want[i])
+
+
+def test_null_trace_gives_the_same_results():
+    org, refp, cfg, items, want, _ = fresh(37, 1)
+    res, trace = run(org, refp, cfg, items, want_trace=False)
+    assert trace is None and np.array_equal(res, want)
+
+
+def test_items_outside_the_contract_get_the_sentinel():
+    org, refp, cfg, items, want, want_trace = fresh(5, 0)
+    items = items.copy()
+    items[1]["pu"]["w"] = 12                     # below 16
+    items[2]["pu"]["h"] = 132                    # above 128
+    items[3]["pu"]["bi"] = 1
+    items[4]["pu"]["w"] = 18                     # no multiple of 4
+    res, trace = run(org, refp, cfg, items)
+    assert res[0].tobytes() == want[0].tobytes() and np.array_equal(trace[0], want_trace[0])
+    for i in range(1, 5):
+        assert res[i]["cost"] == np.uint64(0xFFFFFFFFFFFFFFFF) and res[i]["steps"] == 0 and res[i]["bits"] == 0 and (res[i]["mv"] == 0).all(), i
+        assert (trace[i]["cost"] == 0).all() and (trace[i]["mv"] == 0).all()
+
+
+def test_two_streams_from_two_host_threads():
+    from vvcsoftware_vtm_amd import ops
+    org, refp, cfg, items, want, want_trace = fresh(37, 1)
+    d_org, d_ref, d_items = dev(org), dev(refp), ops.struct_to_device(items)
+    torch.cuda.synchronize()
+    out, errs = [None, None], []
+
+    def work(k):
+        try:
+            s = torch.cuda.Stream()
+            with torch.cuda.stream(s):
+                for _ in range(3):
+                    res, trace = ops.affine_me_batch(d_org, d_ref, d_items, len(items), cfg)
+                s.synchronize()
+            out[k] = (res.cpu().numpy().view(abi.AFFINE_ME_RESULT), trace.cpu().numpy().view(abi.AFFINE_ME_STEP).reshape(len(items), -1))
+        except Exception as e:                    # noqa: BLE001
+            errs.append(e)
+    ts = [threading.Thread(target=work, args=(k,)) for k in range(2)]
+    for t in ts:
+        t.start()
+    for t in ts:
+        t.join()
+    assert not errs, errs
+    for k in range(2):
+        assert np.array_equal(out[k][0], want) and np.array_equal(out[k][1], want_trace), k

@@ -126,6 +126,20 @@ AFE_DESC = np.dtype([("resi_off", "<i8"), ("deriv_off", "<i8"), ("deriv_stride",
 AFFINE_PU = np.dtype([("pos_x", "<i4"), ("pos_y", "<i4"), ("w", "<i2"), ("h", "<i2"), ("six_param", "<i2"), ("bi", "<i2"), ("mv", "<i4", (2, 3, 2)),
                       ("dst_off", "<i8"), ("dst_stride", "<i4"), ("first_desc", "<i4")])
 AFFINE_ITER = np.dtype([("pu", AFFINE_PU), ("org_off", "<i8"), ("org_stride", "<i4"), ("reserved", "<i4")])
+# vvcgpu_affine_me_batch: one (PU, reference picture) search, its result and one step of its trace
+AFFINE_ME_MAX_STEPS = 8
+AFFINE_ME_ITEM = np.dtype([("pu", AFFINE_PU), ("org_off", "<i8"), ("org_stride", "<i4"), ("half_weight", "<i4"), ("mvp", "<i4", (3, 2)), ("bits", "<u4"),
+                           ("reserved", "<i4")])
+AFFINE_ME_RESULT = np.dtype([("mv", "<i4", (3, 2)), ("bits", "<u4"), ("steps", "<u4"), ("cost", "<u8")])
+AFFINE_ME_STEP = np.dtype([("mv", "<i4", (3, 2)), ("cost", "<u8")])
+
+
+class AffineMeCfg(C.Structure):
+    """vvcgpu_affine_me_cfg"""
+    _fields_ = [("lambda_", C.c_double), ("pic_w", C.c_int32), ("pic_h", C.c_int32), ("max_cu_w", C.c_int32), ("max_cu_h", C.c_int32),
+                ("ref_origin_x", C.c_int32), ("ref_origin_y", C.c_int32), ("ref_stride", C.c_int32), ("bit_depth", C.c_int32), ("clp_min", C.c_int32),
+                ("clp_max", C.c_int32), ("affine_type", C.c_int32), ("reserved", C.c_int32 * 3)]
+
 
 # ---- encoder picture analysis ---------------------------------------------------------------------------------------------------------------------
 # vvcgpu_tile_stats: one tile of vvcgpu_tile_stats_picture; vvcgpu_wp_sad_cand: one candidate of vvcgpu_wp_sad_batch (flags: WP_SAD_*)

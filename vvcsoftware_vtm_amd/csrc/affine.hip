@@ -9,6 +9,7 @@
 // share of the block with the <= 6 x 7 sums in 64-bit registers, then one transposed wave reduction (63 shuffles for all sums).
 #include "common.h"
 #include "dist_dev.h"
+#include "afi_dev.h"
 
 namespace {
 
@@ -54,27 +55,6 @@ __device__ __forceinline__ void eq_accumulate(const Pel* __restrict__ resi, cons
       acc[col][P] += ((long long)iC[col] * r) << 3;
     }
   }
-}
-
-// Sum M = 64 (or 32) per-lane values over the wavefront with a halving butterfly: at every step a lane keeps one half of its
-// values and hands the other half to its partner, so 63 (31 + 1) shuffles replace 6 per value; lane L ends with the total of value L.
-template <int M>
-__device__ __forceinline__ long long wave_transpose_sum(long long (&v)[M], int lane)
-{
-  static_assert(M == 64 || M == 32, "M");
-#pragma unroll
-  for (int s = M / 2, len = M; s > 0; s >>= 1, len >>= 1)
-  {
-    const bool up = (lane & s) != 0;
-#pragma unroll
-    for (int i = 0; i < len / 2; i++)
-    {
-      const long long keep = up ? v[i + len / 2] : v[i], send = up ? v[i] : v[i + len / 2];
-      v[i] = keep + __shfl_xor(send, s);
-    }
-  }
-  if (M == 32) v[0] += __shfl_xor(v[0], 32);
-  return v[0];
 }
 
 // one wavefront per PU: every lane accumulates its samples, one transposed reduction, lanes 0 .. P (P + 1) - 1 hold the sums
@@ -169,81 +149,6 @@ __global__ __launch_bounds__(256) void affine_subblock_descs_kernel(const vvcgpu
 // both Sobel planes and the normal-equation sums in ONE pass over the PU, plus the distortion of the prediction the next cost check needs.
 // One workgroup per PU: the prediction is staged in LDS once; a sample's two derivatives come from the same eight neighbours (nearest interior
 // position, as affine_sobel_kernel), no derivative plane and no residue plane is written.
-constexpr int AFI_MAX = 128, AFI_WAVE_MAX = 1024;          // PUs of up to AFI_WAVE_MAX samples are served by one wavefront each, larger ones by a workgroup
-typedef const __attribute__((address_space(3))) Pel* AfiLdsPel;
-
-// NT = 64: the wavefront owns the PU; NT = 256: the four wavefronts of the workgroup share it and their sums meet in `red`
-template <int P, int NT>
-__device__ __forceinline__ void afi_equations(const vvcgpu_affine_iter& d, const Pel* __restrict__ org, const Pel* predL, int w, int h, long long* out,
-                                              long long (*red)[64], int tid)
-{
-  const int lane = tid & 63, wave = tid >> 6;
-  long long acc[P][P + 1];
-#pragma unroll
-  for (int c = 0; c < P; c++)
-#pragma unroll
-    for (int r = 0; r <= P; r++) acc[c][r] = 0;
-  for (int i = tid; i < w * h; i += NT)
-  {
-    const int j = i / w, k = i - j * w;
-    const int yy = min(max(j, 1), h - 2), xx = min(max(k, 1), w - 2);
-    const Pel* c = predL + yy * w + xx;
-    const int x = c[1 - w] - c[-1 - w] + (c[1] << 1) - (c[-1] << 1) + c[1 + w] - c[-1 + w];
-    const int y = c[w - 1] - c[-w - 1] + (c[w] << 1) - (c[-w] << 1) + c[w + 1] - c[-w + 1];
-    int iC[P];
-    if (P == 4) { iC[0] = x; iC[1] = k * x + j * y; iC[2] = y; iC[3] = j * x - k * y; }
-    else        { iC[0] = x; iC[1] = k * x; iC[2] = y; iC[3] = k * y; iC[4] = j * x; iC[5] = j * y; }
-    const long long r = (long long)(Pel)((int)org[(size_t)j * d.org_stride + k] - (int)predL[j * w + k]);      // the error block is a Pel block
-#pragma unroll
-    for (int col = 0; col < P; col++)
-    {
-#pragma unroll
-      for (int row = 0; row < P; row++) acc[col][row] += (long long)iC[col] * iC[row];
-      acc[col][P] += ((long long)iC[col] * r) << 3;
-    }
-  }
-  constexpr int M = P == 6 ? 64 : 32;
-  long long v[M];
-#pragma unroll
-  for (int i = 0; i < M; i++) v[i] = i < P * (P + 1) ? acc[i / (P + 1)][i % (P + 1)] : 0;
-  const long long total = wave_transpose_sum<M>(v, lane);       // lane L: this wave's sum of value L
-  const int row7 = lane / 7, col7 = lane - row7 * 7;
-  const bool used = row7 >= 1 && row7 <= P && col7 <= P;
-  const int src = used ? (row7 - 1) * (P + 1) + col7 : 0;
-  if (NT == 64)
-  {
-    const long long val = __shfl(total, src & 63);
-    if (lane < 49) out[lane] = used ? val : 0;
-  }
-  else
-  {
-    red[wave][lane] = total;
-    __syncthreads();
-    if (tid < 49) out[tid] = used ? red[0][src] + red[1][src] + red[2][src] + red[3][src] : 0;
-  }
-}
-
-// distortion of rows [r0, r1) x 16 of the PU against the prediction in LDS, by one wavefront
-__device__ __forceinline__ unsigned long long afi_dist(const vvcgpu_affine_iter& d, const Pel* __restrict__ org, const Pel* predL, int w, int h,
-                                                       int distKind, int band0, int bandStep, int lane)
-{
-  // bands of sixteen rows: every Hadamard tile of an affine PU (both sides >= 16) is at most sixteen rows high, the tile shape is the whole PU's
-  unsigned long long sum = 0;
-  for (int b = band0; b * 16 < h; b += bandStep)
-  {
-    const Pel* o = org + (size_t)b * 16 * d.org_stride;
-    AfiLdsPel c = (AfiLdsPel)predL + b * 16 * w;
-    if (distKind == 1) sum += satd_block<64, AfiLdsPel>(o, d.org_stride, c, w, w, 16, lane, 0, h);
-    else
-    {
-      unsigned s = 0;
-      for (int i = lane; i < 16 * w; i += 64) { const int j = i / w, k = i - j * w; s += (unsigned)abs((int)o[(size_t)j * d.org_stride + k] - (int)c[j * w + k]); }
-      sum += wave_sum_u64(s);
-    }
-  }
-  return sum;
-}
-
 // PUs of more than AFI_WAVE_MAX samples: one workgroup each (the others leave at once)
 __global__ __launch_bounds__(256) void affine_iter_kernel(const Pel* __restrict__ orgBase, const Pel* __restrict__ predBase,
                                                           const vvcgpu_affine_iter* __restrict__ items, int n, int distKind,

@@ -1,0 +1,166 @@
+// afi_dev.h -- device functions of the affine gradient search shared by the per-iteration entry (affine.hip) and the whole-PU search
+// (affine_me.hip): the transposed wave reduction, the error / Sobel / normal-equation pass and the distortion over a prediction held in LDS.
+// Reference behaviour: AffineGradientSearch.cpp:66-174, InterSearch.cpp:3446-3534 (see affine.hip).
+#pragma once
+#include "common.h"
+#include "dist_dev.h"
+
+// Sum M = 64 (or 32) per-lane values over the wavefront with a halving butterfly: at every step a lane keeps one half of its
+// values and hands the other half to its partner, so 63 (31 + 1) shuffles replace 6 per value; lane L ends with the total of value L.
+template <int M>
+__device__ __forceinline__ long long wave_transpose_sum(long long (&v)[M], int lane)
+{
+  static_assert(M == 64 || M == 32, "M");
+#pragma unroll
+  for (int s = M / 2, len = M; s > 0; s >>= 1, len >>= 1)
+  {
+    const bool up = (lane & s) != 0;
+#pragma unroll
+    for (int i = 0; i < len / 2; i++)
+    {
+      const long long keep = up ? v[i + len / 2] : v[i], send = up ? v[i] : v[i + len / 2];
+      v[i] = keep + __shfl_xor(send, s);
+    }
+  }
+  if (M == 32) v[0] += __shfl_xor(v[0], 32);
+  return v[0];
+}
+
+constexpr int AFI_MAX = 128, AFI_WAVE_MAX = 1024;          // PUs of up to AFI_WAVE_MAX samples are served by one wavefront each, larger ones by a workgroup
+typedef const __attribute__((address_space(3))) Pel* AfiLdsPel;
+
+// NT = 64: the wavefront owns the PU; NT = 256: the four wavefronts of the workgroup share it and their sums meet in `red`
+// this lane's share of the P x (P + 1) sums
+template <int P, int NT>
+__device__ __forceinline__ void afi_accumulate(const vvcgpu_affine_iter& d, const Pel* __restrict__ org, const Pel* predL, int w, int h,
+                                               long long (&acc)[P][P + 1], int tid)
+{
+#pragma unroll
+  for (int c = 0; c < P; c++)
+#pragma unroll
+    for (int r = 0; r <= P; r++) acc[c][r] = 0;
+  for (int i = tid; i < w * h; i += NT)
+  {
+    const int j = i / w, k = i - j * w;
+    const int yy = min(max(j, 1), h - 2), xx = min(max(k, 1), w - 2);
+    const Pel* c = predL + yy * w + xx;
+    const int x = c[1 - w] - c[-1 - w] + (c[1] << 1) - (c[-1] << 1) + c[1 + w] - c[-1 + w];
+    const int y = c[w - 1] - c[-w - 1] + (c[w] << 1) - (c[-w] << 1) + c[w + 1] - c[-w + 1];
+    int iC[P];
+    if (P == 4) { iC[0] = x; iC[1] = k * x + j * y; iC[2] = y; iC[3] = j * x - k * y; }
+    else        { iC[0] = x; iC[1] = k * x; iC[2] = y; iC[3] = k * y; iC[4] = j * x; iC[5] = j * y; }
+    const long long r = (long long)(Pel)((int)org[(size_t)j * d.org_stride + k] - (int)predL[j * w + k]);      // the error block is a Pel block
+#pragma unroll
+    for (int col = 0; col < P; col++)
+    {
+#pragma unroll
+      for (int row = 0; row < P; row++) acc[col][row] += (long long)iC[col] * iC[row];
+      acc[col][P] += ((long long)iC[col] * r) << 3;
+    }
+  }
+}
+
+// total: lane L holds this wave's sum of value L = acc[L / (P + 1)][L % (P + 1)]; -> out[7][7] (the wave's, or the workgroup's through `red`)
+template <int P, int NT>
+__device__ __forceinline__ void afi_publish(long long total, long long* out, long long (*red)[64], int tid)
+{
+  const int lane = tid & 63, wave = tid >> 6;
+  const int row7 = lane / 7, col7 = lane - row7 * 7;
+  const bool used = row7 >= 1 && row7 <= P && col7 <= P;
+  const int src = used ? (row7 - 1) * (P + 1) + col7 : 0;
+  if (NT == 64)
+  {
+    const long long val = __shfl(total, src & 63);
+    if (lane < 49) out[lane] = used ? val : 0;
+  }
+  else
+  {
+    red[wave][lane] = total;
+    __syncthreads();
+    if (tid < 49) out[tid] = used ? red[0][src] + red[1][src] + red[2][src] + red[3][src] : 0;
+  }
+}
+
+template <int P, int NT>
+__device__ __forceinline__ void afi_equations(const vvcgpu_affine_iter& d, const Pel* __restrict__ org, const Pel* predL, int w, int h, long long* out,
+                                              long long (*red)[64], int tid)
+{
+  long long acc[P][P + 1];
+  afi_accumulate<P, NT>(d, org, predL, w, h, acc, tid);
+  constexpr int M = P == 6 ? 64 : 32;
+  long long v[M];
+#pragma unroll
+  for (int i = 0; i < M; i++) v[i] = i < P * (P + 1) ? acc[i / (P + 1)][i % (P + 1)] : 0;
+  const long long total = wave_transpose_sum<M>(v, tid & 63);   // lane L: this wave's sum of value L
+  afi_publish<P, NT>(total, out, red, tid);
+}
+
+// The halving butterfly of wave_transpose_sum, one stage per instantiation: every index is a constant, so v stays in registers (the loops of
+// wave_transpose_sum are not unrolled by the compiler and its v[] lives in scratch memory).  v[0] of lane L ends as the sum of value L % LEN over
+// the LEN lanes that share L / LEN.
+template <int LEN>
+__device__ __forceinline__ void afi_fold(long long (&v)[LEN], int lane)
+{
+  if constexpr (LEN > 1)
+  {
+    constexpr int s = LEN / 2;
+    const bool up = (lane & s) != 0;
+    long long u[s];
+#pragma unroll
+    for (int i = 0; i < s; i++)
+    {
+      const long long keep = up ? v[i + s] : v[i], send = up ? v[i] : v[i + s];
+      u[i] = keep + __shfl_xor(send, s);
+    }
+    afi_fold<s>(u, lane);
+    v[0] = u[0];
+  }
+}
+
+// afi_equations with the reduction in registers only, 32 values at a time (at most 32 + 16 for the 42 sums of the 6-parameter model: 64 registers
+// instead of 128, 49 shuffles instead of 63); integer sums, so the result is the same whatever the order
+template <int P, int NT>
+__device__ __forceinline__ void afi_equations_regs(const vvcgpu_affine_iter& d, const Pel* __restrict__ org, const Pel* predL, int w, int h,
+                                                   long long* out, long long (*red)[64], int tid)
+{
+  const int lane = tid & 63;
+  long long acc[P][P + 1];
+  afi_accumulate<P, NT>(d, org, predL, w, h, acc, tid);
+  long long a[32];
+#pragma unroll
+  for (int i = 0; i < 32; i++) a[i] = i < P * (P + 1) ? acc[i / (P + 1)][i % (P + 1)] : 0;
+  afi_fold<32>(a, lane);
+  long long total = a[0] + __shfl_xor(a[0], 32);                // lane L: value L % 32
+  if constexpr (P * (P + 1) > 32)
+  {
+    long long b[16];
+#pragma unroll
+    for (int i = 0; i < 16; i++) b[i] = 32 + i < P * (P + 1) ? acc[(32 + i) / (P + 1)][(32 + i) % (P + 1)] : 0;
+    afi_fold<16>(b, lane);
+    long long tb = b[0] + __shfl_xor(b[0], 16);
+    tb += __shfl_xor(tb, 32);                                    // lane L: value 32 + L % 16
+    if (lane >= 32) total = tb;                                  // lanes 32 .. 47: value L
+  }
+  afi_publish<P, NT>(total, out, red, tid);
+}
+
+// distortion of rows [r0, r1) x 16 of the PU against the prediction in LDS, by one wavefront
+__device__ __forceinline__ unsigned long long afi_dist(const vvcgpu_affine_iter& d, const Pel* __restrict__ org, const Pel* predL, int w, int h,
+                                                       int distKind, int band0, int bandStep, int lane)
+{
+  // bands of sixteen rows: every Hadamard tile of an affine PU (both sides >= 16) is at most sixteen rows high, the tile shape is the whole PU's
+  unsigned long long sum = 0;
+  for (int b = band0; b * 16 < h; b += bandStep)
+  {
+    const Pel* o = org + (size_t)b * 16 * d.org_stride;
+    AfiLdsPel c = (AfiLdsPel)predL + b * 16 * w;
+    if (distKind == 1) sum += satd_block<64, AfiLdsPel>(o, d.org_stride, c, w, w, 16, lane, 0, h);
+    else
+    {
+      unsigned s = 0;
+      for (int i = lane; i < 16 * w; i += 64) { const int j = i / w, k = i - j * w; s += (unsigned)abs((int)o[(size_t)j * d.org_stride + k] - (int)c[j * w + k]); }
+      sum += wave_sum_u64(s);
+    }
+  }
+  return sum;
+}

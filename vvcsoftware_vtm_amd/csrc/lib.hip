@@ -316,6 +316,10 @@ int vvcgpu_sizeof(int id)
   case 31: return (int)sizeof(vvcgpu_wp_param);
   case 32: return (int)sizeof(vvcgpu_wp_sad_cand);
   case 33: return (int)sizeof(vvcgpu_tile_stats);
+  case 34: return (int)sizeof(vvcgpu_affine_me_item);
+  case 35: return (int)sizeof(vvcgpu_affine_me_cfg);
+  case 36: return (int)sizeof(vvcgpu_affine_me_result);
+  case 37: return (int)sizeof(vvcgpu_affine_me_step);
   default: return -1;
   }
 }

@@ -8,10 +8,10 @@ import torch
 
 from . import capi
 # the struct mirrors live in abi; bench.py, the tests and the tools read them as ops.<NAME>
-from .abi import (AFE_DESC, AFFINE_ITER, AFFINE_PU, AFG_DESC, CCLM_DESC, DEPQUANT_DESC, DIST_DESC, DQ_RATES, DQTR_DESC, FRAC_BLK,  # noqa: F401
+from .abi import (AFE_DESC, AFFINE_ITER, AFFINE_ME_ITEM, AFFINE_ME_MAX_STEPS, AFFINE_ME_RESULT, AFFINE_ME_STEP, AFFINE_PU, AFG_DESC, CCLM_DESC, DEPQUANT_DESC, DIST_DESC, DQ_RATES, DQTR_DESC, FRAC_BLK,  # noqa: F401
                   FRAC_RESULT, IF_DESC, IMV_PU, IMV_RESULT, INTRA_DESC, INTRA_FILL_DESC, INTRA_SATD_DESC, MC_DESC, PELOP_DESC, QUANT_DESC, RC_DESC,
                   RDOQ_DESC, RDOQ_RATES, RDPCM_DESC, SAO_DTYPE, SEARCH_BEST, SEARCH_BLK, TR_DESC, TZ_CFG, TZ_PU, DeblockCfg, MeHierCfg, MvCost,
-                  PelopCfg, Planes, WP_PARAM, TILE_STATS, WP_SAD_CAND, WP_SAD_HIGH_PRECISION, WP_SAD_CLIPPED)
+                  PelopCfg, Planes, AffineMeCfg, WP_PARAM, TILE_STATS, WP_SAD_CAND, WP_SAD_HIGH_PRECISION, WP_SAD_CLIPPED)
 
 
 def _stream():
@@ -477,6 +477,22 @@ def affine_me_iter_batch(org_base, ref_base, pred_base, items_dev, n, n_subblock
               capi.ptr(ws), dist_kind, pic_w, pic_h, max_cu, max_cu, ref_origin[0], ref_origin[1], ref_stride, bit_depth, clp[0], clp[1],
               capi.ptr(coeff), capi.ptr(dist) if want_dist else None, _stream())
     return coeff, dist
+
+
+def affine_me_cfg(lambda_, pic_w, pic_h, ref_origin, ref_stride, bit_depth=10, clp=(0, 1023), affine_type=1, max_cu=128):
+    """vvcgpu_affine_me_cfg of one (slice, reference picture): motion lambda, picture / CTU size, the reference plane's margin and stride"""
+    return AffineMeCfg(lambda_, pic_w, pic_h, max_cu, max_cu, ref_origin[0], ref_origin[1], ref_stride, bit_depth, clp[0], clp[1], affine_type)
+
+
+def affine_me_batch(org_base, ref_base, items_dev, n, cfg, want_trace=True):
+    """xAffineMotionEstimation for n independent (PU, reference picture) searches in one launch: items_dev = AFFINE_ME_ITEM records on the device,
+    cfg = affine_me_cfg(...).  -> (AFFINE_ME_RESULT records, AFFINE_ME_STEP records [n x AFFINE_ME_MAX_STEPS] or None), uint8 tensors"""
+    assert isinstance(cfg, AffineMeCfg)
+    res = torch.empty(n * AFFINE_ME_RESULT.itemsize, dtype=torch.uint8, device=org_base.device)
+    trace = torch.empty(n * AFFINE_ME_MAX_STEPS * AFFINE_ME_STEP.itemsize, dtype=torch.uint8, device=org_base.device) if want_trace else None
+    capi.call("vvcgpu_affine_me_batch", capi.ptr(org_base), capi.ptr(ref_base), capi.ptr(items_dev), n, C.byref(cfg), capi.ptr(res),
+              capi.ptr(trace) if want_trace else None, _stream())
+    return res, trace
 
 
 def affine_pred_batch(ref0_base, ref1_base, dst_base, pus_dev, n, n_subblocks, comp, pic_w, pic_h, ref_origin, ref0_stride, ref1_stride,
