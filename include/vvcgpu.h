@@ -509,6 +509,29 @@ int vvcgpu_alf_stats_picture(const vvcgpu_planes* org, const vvcgpu_planes* rec,
  * where a classifier launch of its own is the faster form -- run exactly these two).  */
 int vvcgpu_alf_classify_stats_picture(const vvcgpu_planes* org, const vvcgpu_planes* rec, int width, int height, int ctu_size, int bit_depth,
                                       uint16_t* cls_out, int64_t* out7, int64_t* out5, int64_t* out_cb, int64_t* out_cr, void* stream);
+/* ---- what EncAdaptiveLoopFilter::alfEncoder (EncAdaptiveLoopFilter.cpp:333-461) reads of the per-CTU records, so that they never leave the device:
+ * the frame sums (48 KB per set) and two doubles per CTU are all a binding downloads per decision round.
+ * vvcgpu_alf_frame_stats = getFrameStat (:1303-1315): frame_out[class][val] (+)= the sum over the CTUs whose enable byte is not 0.
+ *   ctu_stats: device array n_ctu x n_classes x n_vals exactly as the statistics entries above write it; n_classes 25 or 1, n_vals 183 or 57.
+ *   enable: device array, one byte per CTU (the array vvcgpu_alf_filter_picture takes), NULL = every CTU is on; a disabled CTU's record is not read.
+ *   frame_out: device array n_classes x n_vals; accumulate == 0 overwrites it, != 0 adds to it -- the chroma frame record of getFrameStats
+ *   (:1285-1301) is the Cb call followed by the Cr call with accumulate = 1 (:1298-1299).
+ *   Arithmetic is int64 (integer atomics: the result does not depend on scheduling).  As for vvcgpu_alf_stats this equals the reference's double
+ *   accumulation as long as every sum stays below 2^53 in magnitude: then int64 is exact and order-independent.
+ *   n_ctu == 0 returns VVCGPU_OK and writes nothing.                                                                                              */
+int vvcgpu_alf_frame_stats(const int64_t* ctu_stats, int n_ctu, int n_classes, int n_vals, const uint8_t* enable, int accumulate,
+                           int64_t* frame_out, void* stream);
+/* vvcgpu_alf_ctu_dist = the two per-CTU distortions of deriveCtbAlfEnableFlags (:272-331): dist_out[i][0] = getUnfilteredDistortion(cov, numClasses)
+ *   (:618-626, the sum of pixAcc in class order), dist_out[i][1] = getFilteredDistortion (:628-639): calcErrorForCoeffs (:1157-1174) of every class
+ *   record under the quantised filter its class is assigned, summed in class order.  Both are the reference's doubles BIT FOR BIT: IEEE double
+ *   arithmetic in the reference's order, no contraction.
+ *   filter_type 0: N = 7, 1: N = 13 (a class record is N*N + N + 1 values); coeff_set_host: n_filters x N quantised coefficients (m_filterCoeffSet),
+ *   1 <= n_filters <= 25; filter_idx_host: n_classes entries in 0 .. n_filters - 1 (the row of m_filterIndices in use; NULL with n_classes == 1 =
+ *   filter 0); coeff_bits: m_NUM_BITS (10 in the reference; 2..16), factor = 1 << (coeff_bits - 1).  Both host tables travel in the kernel argument:
+ *   no copy, no synchronisation.  dist_out: device array n_ctu x 2 doubles.
+ *   Precondition: every record value is below 2^53 in magnitude, so that its conversion to double is exact.                                     */
+int vvcgpu_alf_ctu_dist(const int64_t* ctu_stats, int n_ctu, int n_classes, int filter_type, const int32_t* coeff_set_host, int n_filters,
+                        const int16_t* filter_idx_host, int coeff_bits, double* dist_out, void* stream);
 /* The coefficient scan the library replays (host copy, out[scanIdx] = raster position; w, h in 2..64 powers of two). */
 int vvcgpu_scan_order_host(int w, int h, uint16_t* out);
 /* ---- N3 ("next" row): affine gradient search kernels  (AffineGradientSearch table slots m_HorizontalSobelFilter /

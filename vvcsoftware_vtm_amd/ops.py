@@ -453,6 +453,35 @@ def alf_classify_stats_picture(org, rec, ctu, bit_depth):
     return cls, a7, a5, ac
 
 
+def alf_frame_stats(ctu_stats, enable=None, out=None, accumulate=False):
+    """getFrameStat on the device: ctu_stats int64 (nCtu, nClasses, nVals) as the statistics entries return it, enable uint8 (nCtu,) or None (all on)
+    -> int64 (nClasses, nVals); with `out` and accumulate the sum is added to it (chroma: Cb, then Cr with accumulate)"""
+    n, ncls, nv = ctu_stats.shape
+    assert ctu_stats.dtype == torch.int64 and ctu_stats.is_contiguous()
+    assert enable is None or (enable.dtype == torch.uint8 and enable.numel() == n and enable.is_contiguous())
+    if out is None:
+        assert not accumulate, "accumulate needs the record to add to"
+        out = torch.empty((ncls, nv), dtype=torch.int64, device=ctu_stats.device)
+    assert out.dtype == torch.int64 and out.numel() == ncls * nv and out.is_contiguous()
+    capi.call("vvcgpu_alf_frame_stats", capi.ptr(ctu_stats), n, ncls, nv, capi.ptr(enable), 1 if accumulate else 0, capi.ptr(out), _stream())
+    return out
+
+
+def alf_ctu_dist(ctu_stats, coeff_set, filter_idx=None, coeff_bits=10):
+    """per CTU (getUnfilteredDistortion, getFilteredDistortion) of deriveCtbAlfEnableFlags -> float64 (nCtu, 2), the reference's doubles bit for bit.
+    coeff_set: (nFilters, N) quantised coefficients, filter_idx: per class the filter in use (None with one class: filter 0)"""
+    n, ncls, nv = ctu_stats.shape
+    assert ctu_stats.dtype == torch.int64 and ctu_stats.is_contiguous() and nv in (57, 183)
+    N = 13 if nv == 183 else 7
+    cs = np.ascontiguousarray(coeff_set, dtype=np.int32).reshape(-1, N)
+    fi = None if filter_idx is None else np.ascontiguousarray(filter_idx, dtype=np.int16).reshape(-1)
+    assert fi is None or fi.size == ncls
+    out = torch.empty((n, 2), dtype=torch.float64, device=ctu_stats.device)
+    capi.call("vvcgpu_alf_ctu_dist", capi.ptr(ctu_stats), n, ncls, 1 if N == 13 else 0, C.c_void_p(cs.ctypes.data), cs.shape[0],
+              None if fi is None else C.c_void_p(fi.ctypes.data), coeff_bits, capi.ptr(out), _stream())
+    return out
+
+
 # ---- T3 residual DPCM, I3 affine sub-block vectors -------------------------------------------------------------
 def rdpcm_fwd_batch(resi_base, coeff_base, descs_dev, n, bit_depth=10):
     """TrQuant::applyForwardRDPCM for n TUs -> abs-sum int32 tensor [n] (bits as uint32)"""
