@@ -44,7 +44,8 @@ int         vvcgpu_set_device(int device);
  * 4 mvcost, 5 search_best, 6 if_desc, 7 mc_desc, 8 pelop_desc, 9 pelop_cfg, 10 tr_desc, 11 frac_blk, 12 frac_result,
  * 13 dqtr_desc, 14 afg_desc, 15 afe_desc, 16 tz_pu, 17 tz_cfg, 18 intra_desc, 19 cclm_desc, 20 intra_fill_desc, 21 imv_pu, 22 imv_result, 23 quant_desc,
  * 24 dq_rates, 25 depquant_desc, 26 rdoq_rates, 27 rdoq_desc, 28 intra_satd_desc, 29 affine_iter, 30 me_hier_cfg, 31 wp_param,
- * 32 wp_sad_cand, 33 tile_stats, 34 affine_me_item, 35 affine_me_cfg, 36 affine_me_result, 37 affine_me_step; -1 for unknown ids. */
+ * 32 wp_sad_cand, 33 tile_stats, 34 affine_me_item, 35 affine_me_cfg, 36 affine_me_result, 37 affine_me_step,
+ * 38 bipred_me_ref, 39 bipred_me_item, 40 bipred_me_cfg, 41 bipred_me_result, 42 bipred_me_step; -1 for unknown ids. */
 int         vvcgpu_sizeof(int struct_id);
 
 /* ---- device memory helpers for host-side callers (the reference keeps pictures in host memory; the shim stages them).
@@ -624,6 +625,108 @@ typedef struct { int32_t mv[3][2]; uint64_t cost; } vvcgpu_affine_me_step;   /* 
  * entries zero. */
 int vvcgpu_affine_me_batch(const vvc_pel* org_base, const vvc_pel* ref_base, const vvcgpu_affine_me_item* items, int n,
                            const vvcgpu_affine_me_cfg* cfg_host, vvcgpu_affine_me_result* results, vvcgpu_affine_me_step* trace, void* stream);
+
+/* The WHOLE bi-predictive refinement of a PU (the loop of InterSearch::predInterSearch, InterSearch.cpp:1058-1164, with every
+ * xMotionEstimation(..., bBi = true) :1668-1816 and xCheckBestMVP :1537-1603 inside it) for a list of independent PUs in ONE launch with no host
+ * synchronisation inside.  The owner of a PU (a wavefront up to 1024 samples, a workgroup above) carries it through every dependent step; per iteration
+ * and reference index, in the reference's order:
+ *   other prediction  luma motionCompensation of the other list's current vector (xPredInterUni: clipMv, 8-tap DCTIF, rounded and clipped -- the uni
+ *                     form of vvcgpu_mc_batch), formed when the iteration starts (the reference forms it at :1077-1084 and again after each accepted
+ *                     improvement, :1130-1138; an iteration only ever reads the prediction of the OTHER list's current vector, so both give the same);
+ *   search key        2 org - otherPred, clipped when clip_for_bipred_me (Buffer.h:389-416; op 4 of vvcgpu_pelop_batch); it lives in LDS;
+ *   xSetSearchRange   (:1820-1854) around the entry vector cMvTemp[list][ref]: clipMv, +-bipred_search_range, clipMv of both corners, divideByPowerOf2;
+ *   xPatternSearch    (:1887-1941) SAD with the item's sub_shift, vector cost at scale 2 against cMvPredBi[list][ref], y outer, x inner, strict '<';
+ *   xPatternSearchFracDIF   half then quarter stage, Hadamard when use_hadamard: exactly vvcgpu_frac_refine;
+ *   cost              vector (int << 2) + (half << 1) + qter; uiMvBits at scale 0; ruiBits += uiMvBits;
+ *                     ruiCost = (uint64)(floor(0.5 ((double)cost - (double)getCost(uiMvBits))) + (double)getCost(ruiBits)), getCost(b) = (uint64)(lambda b);
+ *   xCheckBestMVP     over the candidates of that (list, ref); then keep-if-strictly-better against uiCostBi (:1119-1139), which starts at UINT64_MAX.
+ * After a pass without change (:1142-1163) the two closing xCheckBestMVP calls are made when uiCostBi <= uiCost[0] && uiCostBi <= uiCost[1].  The
+ * reference hands them amvp[eRefPicList] -- the candidate set last copied for the list of the CURRENT iteration, not that of the list being checked --
+ * and so does this.  An item on which the reference's own CHECK in xCheckBestMVP throws ("Invalid MV prediction candidate") is outside the contract:
+ * the device ignores the CHECK, does not fault, and the result is unspecified.
+ * Loop control (host cfg): num_iter 4 or 1 (iNumIter); pick_list_by_cost (FASTINTERSEARCH_MODE1/2, :1062-1072); mvd_l1_zero: list 1 is fixed and list 0
+ * searched -- the caller has done :1009-1023 and passes ref_idx[1] = bestBiPRefIdxL1, that record's mvp_idx = bestBiPMvpL1 and mv[1] = the candidate;
+ * the device derives uiMotBits[1] by :1024-1036 and forms the list-1 prediction like any other.  Not served: imv != 0, weighted prediction, composite
+ * reference.
+ * Reference planes: up to 16 luma planes of one stride; ref_planes[i] points to sample (0, 0) of picture i inside its padded allocation.  Readable
+ * margin (a stated margin, as vvcgpu_affine_me_batch): vectors are clipped to the picture + 8 / - CTU - 8 samples, the block, the +-1 sample of the
+ * refinement and the 8 taps reach further: max_cu + 12 readable samples around the picture on every side serve every search.
+ * items, results, trace: device memory.  Items cannot be validated on the host: an item outside the contract (a side not in {4, 8, 16, 32, 64, 128} or
+ * larger than the CTU or than cfg.max_pu_w / max_pu_h, a PU not inside the picture, sub_shift outside 0..1 or h >> sub_shift == 0, n_ref outside 1..4,
+ * ref_idx outside the list, a plane index outside [0, n_planes), num_cand outside 1..2, mvp_idx outside the candidates, org_stride <= 0) is skipped and
+ * gets cost = ~0 (UINT64_MAX) with everything else zero (the sentinel of vvcgpu_affine_me_batch); its trace entries are zero.  n == 0 is a no-op;
+ * null pointers (trace may be NULL), n < 0, geometry, clp_min > clp_max, lambda outside [0, 2^20), bipred_search_range outside 1..8, num_iter other
+ * than 1 or 4, n_planes outside 1..16 and max_pu sides that are no served side return VVCGPU_E_ARG, a bit depth outside 8..10 VVCGPU_E_UNSUPPORTED,
+ * before any device work. */
+#define VVCGPU_BIPRED_ME_MAX_STEPS  16  /* num_iter 4 x at most 4 reference indices */
+#define VVCGPU_BIPRED_ME_MAX_REFS   4
+#define VVCGPU_BIPRED_ME_MAX_PLANES 16
+typedef struct {                        /* one (list, reference index) of a PU                sizeof == 32 */
+  int32_t plane;          /* index into cfg.ref_planes */
+  int32_t mv[2];          /* cMvTemp[list][ref] on entry (quarter units): the uni-predictive result for this reference */
+  int32_t mv_cand[2][2];  /* aacAMVPInfo[list][ref].mvCand[0..1] */
+  int16_t num_cand;       /* .numCand: 1..2 */
+  int16_t mvp_idx;        /* aaiMvpIdx[list][ref]; cMvPred[list][ref] = mv_cand[mvp_idx] */
+} vvcgpu_bipred_me_ref;
+typedef struct {                        /* one PU                                             sizeof == 360 */
+  int32_t  pos_x, pos_y;  /* pu.cu->lumaPos() == the PU's position */
+  int16_t  w, h;          /* 4, 8, 16, 32, 64 or 128 each */
+  int16_t  sub_shift;     /* DistParam::subShift of the integer search: 0 or 1 */
+  int16_t  reserved0;
+  int64_t  org_off;       /* elements from org_base */
+  int32_t  org_stride;
+  int32_t  n_ref[2];      /* getNumRefIdx(list): 1..4 */
+  int32_t  ref_idx[2];    /* iRefIdx[list]: the uni-predictive choice */
+  int32_t  mv[2][2];      /* cMv[list] (quarter units) */
+  int32_t  reserved1;
+  uint64_t cost[2];       /* uiCost[0..1] */
+  uint32_t bits[2];       /* uiBits[0..1] */
+  uint32_t mb_bits[3];    /* uiMbBits[0..2] */
+  int32_t  reserved2;
+  vvcgpu_bipred_me_ref ref[2][VVCGPU_BIPRED_ME_MAX_REFS];
+} vvcgpu_bipred_me_item;
+typedef struct {                        /* host struct                                        sizeof == 224 */
+  double  lambda;         /* RdCost::m_motionLambda */
+  const vvc_pel* ref_planes[VVCGPU_BIPRED_ME_MAX_PLANES];   /* device pointers; entries from n_planes on are ignored */
+  int32_t n_planes, ref_stride;
+  int32_t pic_w, pic_h, max_cu_w, max_cu_h;                 /* clipMv */
+  int32_t bit_depth, clp_min, clp_max;
+  int32_t num_iter;             /* iNumIter: 4 or 1 */
+  int32_t pick_list_by_cost;    /* FASTINTERSEARCH_MODE1/2: the list of every iteration is the one with the larger uni cost (:1062-1072) */
+  int32_t mvd_l1_zero;          /* slice.getMvdL1ZeroFlag() */
+  int32_t bipred_search_range;  /* m_bipredSearchRange: 1..8 */
+  int32_t clip_for_bipred_me;   /* getClipForBiPredMeEnabled() */
+  int32_t use_hadamard;         /* getUseHADME() (no lossless CUs) */
+  uint32_t mvp_idx_cost[3];     /* m_auiMVPIdxCost[0..2][AMVP_MAX_NUM_CANDS] */
+  int32_t max_pu_w, max_pu_h;   /* the caller states that no item is wider / higher (0: 128): LDS per owner is sized by it, so that small PUs keep many
+                                   owners per compute unit; an item beyond it is skipped */
+  int32_t reserved[2];
+} vvcgpu_bipred_me_cfg;
+typedef struct {                        /* sizeof == 80 */
+  int32_t  mv[2][2];      /* cMvBi[0..1] */
+  int32_t  ref_idx[2];    /* iRefIdxBi[0..1] */
+  int32_t  mvp_idx[2];    /* aaiMvpIdxBi[list][iRefIdxBi[list]] */
+  int32_t  mvp[2][2];     /* cMvPredBi[list][iRefIdxBi[list]] */
+  uint32_t bits;          /* uiBits[2] */
+  uint32_t mot_bits[2];   /* uiMotBits[0..1] */
+  uint32_t me_calls;      /* xMotionEstimation calls made */
+  uint32_t closing;       /* 1: the closing xCheckBestMVP calls ran */
+  uint32_t reserved;
+  uint64_t cost;          /* uiCostBi; ~0 with everything else zero: item skipped */
+} vvcgpu_bipred_me_result;
+typedef struct {                        /* one xMotionEstimation + xCheckBestMVP              sizeof == 48 */
+  int32_t  list, ref;
+  int32_t  int_mv[2];     /* the integer vector xPatternSearch found */
+  int32_t  mv[2];         /* cMvTemp[list][ref] after the refinement (quarter units) */
+  uint32_t bits;          /* uiBitsTemp after xCheckBestMVP */
+  int32_t  mvp_idx;       /* aaiMvpIdxBi[list][ref] after xCheckBestMVP */
+  int32_t  accepted;      /* uiCostTemp < uiCostBi */
+  int32_t  reserved;
+  uint64_t cost;          /* uiCostTemp after xCheckBestMVP */
+} vvcgpu_bipred_me_step;
+/* trace (may be NULL): n x VVCGPU_BIPRED_ME_MAX_STEPS entries, entry s of an item = its s-th xMotionEstimation call, unused entries zero. */
+int vvcgpu_bipred_me_batch(const vvc_pel* org_base, const vvcgpu_bipred_me_item* items, int n, const vvcgpu_bipred_me_cfg* cfg_host,
+                           vvcgpu_bipred_me_result* results, vvcgpu_bipred_me_step* trace, void* stream);
 
 /* ---- N2 ("next" row): integer-sample TZ search of whole PUs, on the device  (InterSearch::xTZSearch,
  *          EncoderLib/InterSearch.cpp:1971-2252, with xTZSearchHelp :249-343, xTZ2PointSearch :349-374,

@@ -1,0 +1,318 @@
+"""The bi-predictive refinement loop of InterSearch::predInterSearch (InterSearch.cpp:1058-1164) restated for the tests of vvcgpu_bipred_me_batch:
+the pixel steps of every xMotionEstimation(bBi = true) (:1668-1816) go through the CPU restatement (orc_mc_batch, orc_pelop_batch op 4, orc_sad_search,
+orc_frac_refine, orc_mvcost, orc_expgolomb_bits); xSetSearchRange (:1820-1854), the cost in IEEE doubles (:1805), xCheckBestMVP (:1537-1603) and the
+loop control are written here.  tests/golden/bipred_me.npz pins it to the compiled reference (tests/test_bipred_me_cpu.py).  Also the builders of the
+test inputs (planes, items) that the generator, the tests and tools/bipred_me_time.py share.  numpy only."""
+import ctypes
+import math
+
+import numpy as np
+
+from oraclelib import oracle, p
+from vvcsoftware_vtm_amd import abi
+
+MARGIN = 144                # samples of edge padding around a reference plane: CTU 128 + 8 (vector clip) + 4 (filter taps) + 1 (refinement), rounded up
+MAX_STEPS = abi.BIPRED_ME_MAX_STEPS
+U64_MAX = 0xFFFFFFFFFFFFFFFF
+SIDES = (4, 8, 16, 32, 64, 128)
+
+
+class RefThrows(Exception):
+    """the reference's CHECK in xCheckBestMVP (:1552) fails: the item is outside the contract"""
+
+
+def cfg_dict(lambda_, pic_w, pic_h, bit_depth, num_iter=4, pick_list_by_cost=0, mvd_l1_zero=0, search_range=4, clip_key=1, use_hadamard=1,
+             mvp_idx_cost=(1, 1, 0), max_cu=128):
+    """the host cfg as plain values (the device tests turn it into ops.bipred_me_cfg with the planes' addresses)"""
+    return dict(lambda_=float(lambda_), pic_w=pic_w, pic_h=pic_h, max_cu=max_cu, bit_depth=bit_depth, clp_min=0, clp_max=(1 << bit_depth) - 1,
+                num_iter=num_iter, pick_list_by_cost=int(pick_list_by_cost), mvd_l1_zero=int(mvd_l1_zero), search_range=search_range,
+                clip_key=int(clip_key), use_hadamard=int(use_hadamard), mvp_idx_cost=tuple(mvp_idx_cost))
+
+
+def clip_mv(v, pos, pic, max_cu):
+    """clipMv of one component of a quarter-unit vector (Mv.cpp:64-80)"""
+    return min((pic + 8 - pos - 1) << 2, max((-max_cu - 8 - pos + 1) << 2, v))
+
+
+def ref_bits(n_ref, r):
+    """the reference index bits of :1101-1108"""
+    return (r + 1 - (1 if r == n_ref - 1 else 0)) if n_ref > 1 else 0
+
+
+def item_ok(it, c, n_planes):
+    w, h = int(it["w"]), int(it["h"])
+    if w not in SIDES or h not in SIDES or w > c["max_cu"] or h > c["max_cu"]:
+        return False
+    if not (0 <= int(it["pos_x"]) <= c["pic_w"] - w and 0 <= int(it["pos_y"]) <= c["pic_h"] - h):
+        return False
+    if int(it["sub_shift"]) not in (0, 1) or (h >> int(it["sub_shift"])) == 0 or int(it["org_stride"]) <= 0:
+        return False
+    for l in range(2):
+        n = int(it["n_ref"][l])
+        if not 1 <= n <= abi.BIPRED_ME_MAX_REFS or not 0 <= int(it["ref_idx"][l]) < n:
+            return False
+        for r in range(n):
+            a = it["ref"][l][r]
+            if not 0 <= int(a["plane"]) < n_planes or not 1 <= int(a["num_cand"]) <= 2 or not 0 <= int(a["mvp_idx"]) < int(a["num_cand"]):
+                return False
+    return True
+
+
+class Searcher:
+    """one (org plane, padded reference planes [n][H + 2 M][W + 2 M], cfg): search(item) -> (result record, trace records)"""
+
+    def __init__(self, org, planes_pad, cfg, margin=MARGIN):
+        self.org, self.planes, self.c, self.m = np.ascontiguousarray(org), np.ascontiguousarray(planes_pad), cfg, margin
+        self.rs = self.planes.shape[2]
+        self.o = oracle()
+        self.o.orc_expgolomb_bits.restype = ctypes.c_uint32
+        self.o.orc_mvcost.restype = ctypes.c_uint64
+
+    # ---- scalar pieces
+    def mv_bits(self, pred, scale, x, y):
+        return self.o.orc_expgolomb_bits((x << scale) - int(pred[0])) + self.o.orc_expgolomb_bits((y << scale) - int(pred[1]))
+
+    def get_cost(self, bits):
+        return int(self.c["lambda_"] * bits)
+
+    def check_best_mvp(self, a, mv, pred, idx, bits, cost, strict=False):
+        """xCheckBestMVP with the candidate set `a` (a BIPRED_ME_REF record) -> (pred, idx, bits, cost)"""
+        cand = [[int(v) for v in a["mv_cand"][k]] for k in range(2)]
+        if strict and cand[idx] != list(pred):
+            raise RefThrows()
+        if int(a["num_cand"]) < 2:
+            return pred, idx, bits, cost
+        mic = self.c["mvp_idx_cost"]
+        org_bits = self.mv_bits(pred, 0, mv[0], mv[1]) + mic[idx]
+        best_bits, best_idx = org_bits, idx
+        for i in range(2):
+            if i == idx:
+                continue
+            b = self.mv_bits(cand[i], 0, mv[0], mv[1]) + mic[i]
+            if b < best_bits:
+                best_bits, best_idx = b, i
+        if best_idx != idx:
+            nb = bits - org_bits + best_bits
+            cost = ((cost - self.get_cost(bits)) + self.get_cost(nb)) & U64_MAX
+            pred, idx, bits = cand[best_idx], best_idx, nb
+        return list(pred), idx, bits, cost
+
+    # ---- pixel steps
+    def predict(self, it, plane, mv):
+        """luma motionCompensation (uni): clipMv, xPredInterBlk"""
+        c, w, h, px, py = self.c, int(it["w"]), int(it["h"]), int(it["pos_x"]), int(it["pos_y"])
+        mx, my = clip_mv(mv[0], px, c["pic_w"], c["max_cu"]), clip_mv(mv[1], py, c["pic_h"], c["max_cu"])
+        d = np.zeros(1, abi.MC_DESC)
+        d[0]["ref0_off"] = (self.m + py + (my >> 2)) * self.rs + self.m + px + (mx >> 2)
+        d[0]["ref0_stride"], d[0]["dst_stride"], d[0]["w"], d[0]["h"] = self.rs, w, w, h
+        d[0]["frac_x0"], d[0]["frac_y0"], d[0]["is_luma"] = (mx & 3) << 2, (my & 3) << 2, 1
+        pred = np.zeros(w * h, np.int16)
+        self.o.orc_mc_batch(p(self.planes[plane]), p(self.planes[plane]), p(pred), p(d), 1, c["bit_depth"], c["clp_min"], c["clp_max"])
+        return pred
+
+    def key(self, it, other_pred):
+        """2 org - otherPred (removeHighFreq)"""
+        c, w, h = self.c, int(it["w"]), int(it["h"])
+        d = np.zeros(1, abi.PELOP_DESC)
+        d[0]["src0_off"], d[0]["src0_stride"], d[0]["src1_stride"], d[0]["dst_stride"], d[0]["w"], d[0]["h"] = int(it["org_off"]), int(it["org_stride"]), w, w, w, h
+        out = np.zeros(w * h, np.int16)
+        pc = abi.PelopCfg(0, 0, 0, c["clip_key"], c["clp_min"], c["clp_max"])
+        self.o.orc_pelop_batch(4, p(self.org), p(other_pred), p(out), p(d), 1, ctypes.byref(pc))
+        return out
+
+    def motion_estimation(self, it, plane, key, entry, pred, bits):
+        """xMotionEstimation(bBi = true) -> (integer vector, vector, bits, cost)"""
+        c, w, h, px, py, R = self.c, int(it["w"]), int(it["h"]), int(it["pos_x"]), int(it["pos_y"]), self.c["search_range"]
+        lim = ((px, c["pic_w"]), (py, c["pic_h"]))
+        ctr = [clip_mv(entry[k], lim[k][0], lim[k][1], c["max_cu"]) for k in range(2)]
+        tl = [(clip_mv(ctr[k] - (R << 2), lim[k][0], lim[k][1], c["max_cu"]) + 2) >> 2 for k in range(2)]       # divideByPowerOf2 rounds (ME_ENABLE_ROUNDING_OF_MVS)
+        br = [(clip_mv(ctr[k] + (R << 2), lim[k][0], lim[k][1], c["max_cu"]) + 2) >> 2 for k in range(2)]
+        ref = self.planes[plane]
+        blk = np.array([(0, 0, self.m + px, self.m + py)], dtype=abi.SEARCH_BLK)
+        mc = abi.MvCost(c["lambda_"], int(pred[0]), int(pred[1]), 2, 0)
+        best = np.zeros(1, abi.SEARCH_BEST)
+        self.o.orc_sad_search(p(key), w, p(ref), self.rs, p(blk), 1, w, h, int(it["sub_shift"]), tl[0], tl[1], br[0] - tl[0] + 1, br[1] - tl[1] + 1, 1, 1,
+                              None, ctypes.byref(mc), p(best))
+        ix, iy = int(best[0]["x"]), int(best[0]["y"])
+        fb = np.array([(0, 0, self.m + px + ix, self.m + py + iy, ix, iy)], dtype=abi.FRAC_BLK)
+        fr = np.zeros(1, abi.FRAC_RESULT)
+        mc0 = abi.MvCost(c["lambda_"], int(pred[0]), int(pred[1]), 0, 0)
+        self.o.orc_frac_refine(p(key), w, p(ref), self.rs, p(fb), 1, w, h, c["bit_depth"], c["clp_min"], c["clp_max"], c["use_hadamard"], ctypes.byref(mc0), p(fr))
+        mv = [(ix << 2) + (int(fr[0]["half_x"]) << 1) + int(fr[0]["qter_x"]), (iy << 2) + (int(fr[0]["half_y"]) << 1) + int(fr[0]["qter_y"])]
+        mv_bits = self.mv_bits(pred, 0, mv[0], mv[1])
+        bits += mv_bits
+        cost = int(math.floor(0.5 * (float(int(fr[0]["cost"])) - float(self.get_cost(mv_bits)))) + float(self.get_cost(bits)))
+        return [ix, iy], mv, bits, cost
+
+    # ---- the loop
+    def search(self, it, strict=False, facts=None):
+        """strict: raise RefThrows where the reference's CHECK would (the generator and the CPU tests; the device ignores the CHECK).  facts (a set):
+        receives "mvp_switch", "nonzero_ref_accepted", "closing_changes_bits" when they happen"""
+        facts = set() if facts is None else facts
+        c = self.c
+        res, trace = np.zeros(1, abi.BIPRED_ME_RESULT), np.zeros(MAX_STEPS, abi.BIPRED_ME_STEP)
+        if not item_ok(it, c, len(self.planes)):
+            res["cost"] = np.uint64(U64_MAX)
+            return res[0], trace
+        n_ref = [int(v) for v in it["n_ref"]]
+        rec = it["ref"]
+        mv_temp = [[[int(v) for v in rec[l][r]["mv"]] for r in range(4)] for l in range(2)]
+        mvp_idx = [[int(rec[l][r]["mvp_idx"]) & 1 for r in range(4)] for l in range(2)]
+        mv_pred = [[[int(v) for v in rec[l][r]["mv_cand"][mvp_idx[l][r]]] for r in range(4)] for l in range(2)]
+        mv_bi = [[int(v) for v in it["mv"][l]] for l in range(2)]
+        ref_bi = [int(v) for v in it["ref_idx"]]
+        uni_cost = [int(v) for v in it["cost"]]
+        mb = [int(v) for v in it["mb_bits"]]
+        mot = [(int(it["bits"][0]) - mb[0]) & 0xFFFFFFFF, 0]
+        if c["mvd_l1_zero"]:
+            mot[1] = mb[1] + ref_bits(n_ref[1], ref_bi[1]) + c["mvp_idx_cost"][mvp_idx[1][ref_bi[1]]]
+        else:
+            mot[1] = (int(it["bits"][1]) - mb[1]) & 0xFFFFFFFF
+        bits2 = (mb[2] + mot[0] + mot[1]) & 0xFFFFFFFF
+        cost_bi, calls, closing = U64_MAX, 0, 0
+        for it_no in range(c["num_iter"]):
+            lst = it_no % 2
+            if c["pick_list_by_cost"]:
+                lst = 1 if uni_cost[0] <= uni_cost[1] else 0
+            elif it_no == 0:
+                lst = 0
+            if c["mvd_l1_zero"]:
+                lst = 0
+            oth = 1 - lst
+            key = self.key(it, self.predict(it, int(rec[oth][ref_bi[oth]]["plane"]), mv_bi[oth]))
+            changed = False
+            for r in range(n_ref[lst]):
+                bits_t = (mb[2] + mot[oth] + ref_bits(n_ref[lst], r) + c["mvp_idx_cost"][mvp_idx[lst][r]]) & 0xFFFFFFFF
+                imv, mv, bits_t, cost_t = self.motion_estimation(it, int(rec[lst][r]["plane"]), key, mv_temp[lst][r], mv_pred[lst][r], bits_t)
+                bits_t &= 0xFFFFFFFF
+                mv_temp[lst][r] = mv
+                before = mvp_idx[lst][r]
+                mv_pred[lst][r], mvp_idx[lst][r], bits_t, cost_t = self.check_best_mvp(rec[lst][r], mv, mv_pred[lst][r], mvp_idx[lst][r], bits_t, cost_t, strict)
+                if mvp_idx[lst][r] != before:
+                    facts.add("mvp_switch")
+                accepted = cost_t < cost_bi
+                trace[calls] = (lst, r, imv, mv, bits_t, mvp_idx[lst][r], int(accepted), 0, cost_t)
+                calls += 1
+                if accepted:
+                    changed = True
+                    if r > 0:
+                        facts.add("nonzero_ref_accepted")
+                    mv_bi[lst], ref_bi[lst], cost_bi = list(mv), r, cost_t
+                    mot[lst] = (bits_t - mb[2] - mot[oth]) & 0xFFFFFFFF
+                    bits2 = bits_t
+            if not changed:
+                if cost_bi <= uni_cost[0] and cost_bi <= uni_cost[1]:
+                    closing, bits_before = 1, bits2
+                    # amvp[eRefPicList] (:1148, :1156): the set last copied for the list of THIS iteration
+                    a = rec[0][ref_bi[0]] if lst == 0 else rec[1][n_ref[1] - 1]
+                    r0 = ref_bi[0]
+                    mv_pred[0][r0], mvp_idx[0][r0], bits2, cost_bi = self.check_best_mvp(a, mv_bi[0], mv_pred[0][r0], mvp_idx[0][r0], bits2, cost_bi, strict)
+                    if not c["mvd_l1_zero"]:
+                        a = rec[0][ref_bi[0]] if lst == 0 else rec[1][ref_bi[1]]
+                        r1 = ref_bi[1]
+                        mv_pred[1][r1], mvp_idx[1][r1], bits2, cost_bi = self.check_best_mvp(a, mv_bi[1], mv_pred[1][r1], mvp_idx[1][r1], bits2, cost_bi, strict)
+                    if bits2 != bits_before:
+                        facts.add("closing_changes_bits")
+                break
+        res[0] = (mv_bi, ref_bi, [mvp_idx[l][ref_bi[l]] for l in range(2)], [mv_pred[l][ref_bi[l]] for l in range(2)], bits2 & 0xFFFFFFFF, mot, calls, closing, 0, cost_bi)
+        return res[0], trace
+
+
+def search_all(org, planes_pad, cfg, items, strict=False):
+    s = Searcher(org, planes_pad, cfg)
+    res, trace = np.zeros(len(items), abi.BIPRED_ME_RESULT), np.zeros((len(items), MAX_STEPS), abi.BIPRED_ME_STEP)
+    for i, it in enumerate(items):
+        res[i], trace[i] = s.search(it, strict)
+    return res, trace
+
+
+# ---- inputs ------------------------------------------------------------------------------------------------------------------------------------
+def texture(rng, h, w, bd, phase=0.0):
+    """smooth texture plus noise: gradients everywhere, so that the searches move"""
+    y, x = np.mgrid[0:h, 0:w].astype(np.float64)
+    x, y = x + phase, y - 0.6 * phase
+    mx = (1 << bd) - 1
+    a = 0.5 + 0.22 * np.sin(x / 9.0 + y / 23.0) + 0.18 * np.cos(y / 7.0 - x / 31.0) + 0.08 * np.sin((x + 2 * y) / 3.5)
+    a = a * mx + rng.normal(0, mx / 200.0, (h, w))
+    return np.clip(np.rint(a), 0, mx).astype(np.int16)
+
+
+def pad(planes, margin=MARGIN):
+    """[n][H][W] -> [n][H + 2 M][W + 2 M], edges replicated"""
+    return np.ascontiguousarray(np.pad(planes, ((0, 0), (margin, margin), (margin, margin)), mode="edge"))
+
+
+def ref_record(plane, mv, cands, mvp_idx=0):
+    a = np.zeros(1, abi.BIPRED_ME_REF)
+    cands = [list(c) for c in cands]
+    a[0]["plane"], a[0]["mv"], a[0]["num_cand"], a[0]["mvp_idx"] = plane, mv, len(cands), mvp_idx
+    a[0]["mv_cand"] = (cands + cands)[:2]
+    return a[0]
+
+
+def item(px, py, w, h, sub_shift, org_off, org_stride, refs, ref_idx, cost, bits, mb_bits=(2, 2, 4), mv=None):
+    """refs = ([records of list 0], [records of list 1]); mv: cMv[0..1] (default: the chosen records' entry vectors)"""
+    it = np.zeros(1, abi.BIPRED_ME_ITEM)
+    it[0]["pos_x"], it[0]["pos_y"], it[0]["w"], it[0]["h"], it[0]["sub_shift"] = px, py, w, h, sub_shift
+    it[0]["org_off"], it[0]["org_stride"] = org_off, org_stride
+    for l in range(2):
+        it[0]["n_ref"][l] = len(refs[l])
+        for r, a in enumerate(refs[l][:abi.BIPRED_ME_MAX_REFS]):
+            it[0]["ref"][l][r] = a
+        it[0]["ref_idx"][l] = ref_idx[l]
+        it[0]["mv"][l] = mv[l] if mv is not None else refs[l][ref_idx[l]]["mv"]
+    it[0]["cost"], it[0]["bits"], it[0]["mb_bits"] = cost, bits, mb_bits
+    return it[0]
+
+
+def sub_shift_of(w, h, fast):
+    """DistParam::subShift of subShiftMode 2 (RdCost.cpp:277-283), which FASTINTERSEARCH_MODE1/3 select"""
+    return 1 if fast and h > 8 and w <= 64 else 0
+
+
+def fresh_set(seed, bd, shapes, pic=(256, 128), n_planes=4, n_ref=(2, 2), fast=False, far=0, single=None, **cfgkw):
+    """seeded inputs for the device tests: -> (org plane, padded planes, cfg dict, items); one PU per entry of `shapes` = (w, h).  The planes are
+    shifted copies of one texture, the original is their mean plus noise, so bi-prediction pays and the refinements move.  Every (list, reference) of
+    an item shares its two candidates, so that the closing checks stay inside the contract; single = (x, y): that one candidate everywhere instead."""
+    rng = np.random.default_rng(seed)
+    W, H = pic
+    planes = np.stack([texture(rng, H, W, bd, 1.5 * k) for k in range(n_planes)])
+    org = np.clip(planes.astype(np.int32).mean(axis=0) + rng.integers(-6, 7, (H, W)), 0, (1 << bd) - 1).astype(np.int16)
+    cfg = cfg_dict(4.0 + (seed % 5) * 9.25, W, H, bd, **cfgkw)
+    items = np.zeros(len(shapes), abi.BIPRED_ME_ITEM)
+    for i, (w, h) in enumerate(shapes):
+        px, py = int(rng.integers(0, (W - w) // 4 + 1)) * 4, int(rng.integers(0, (H - h) // 4 + 1)) * 4
+        base = rng.integers(-24, 25, 2) + far * rng.integers(-1, 2, 2)
+        cands = [list(base + rng.integers(-6, 7, 2)), list(base + rng.integers(-6, 7, 2))] if single is None else [list(single)]
+        refs = []
+        for l in range(2):
+            refs.append([ref_record(int(rng.integers(0, n_planes)), list(base + rng.integers(-10, 11, 2)), cands, int(rng.integers(0, len(cands)))) for _ in range(n_ref[l])])
+        ri = [int(rng.integers(0, n_ref[0])), int(rng.integers(0, n_ref[1]))]
+        sad = w * h * (3 << (bd - 8))
+        cost = [int(sad * rng.uniform(0.6, 1.6)), int(sad * rng.uniform(0.6, 1.6))]
+        items[i] = item(px, py, w, h, sub_shift_of(w, h, fast), py * W + px, W, refs, ri, cost, [int(rng.integers(8, 30)), int(rng.integers(8, 30))])
+    return org, pad(planes), cfg, items
+
+
+def passes(trace_row, calls):
+    """iterations of the loop an item ran (:1058): a new pass starts where the list changes or the reference index does not rise"""
+    n = 0
+    for k in range(int(calls)):
+        if k == 0 or trace_row[k]["list"] != trace_row[k - 1]["list"] or trace_row[k]["ref"] <= trace_row[k - 1]["ref"]:
+            n += 1
+    return n
+
+
+# ---- the golden file ------------------------------------------------------------------------------------------------------------------------------
+GOLDEN_FLAGS = ("num_iter", "pick_list_by_cost", "mvd_l1_zero", "search_range", "clip_key", "use_hadamard")
+
+
+def golden_groups(g, bd, pic=(256, 128)):
+    """tests/golden/bipred_me.npz -> [(cfg dict, item indices)] of one bit depth: the items of a group share the loop-control flags"""
+    k = "bd%d_" % bd
+    out = []
+    for gi, flags in enumerate(g[k + "flags"]):
+        cfg = cfg_dict(float(g[k + "lambda"]), pic[0], pic[1], bd, mvp_idx_cost=tuple(int(v) for v in g[k + "mvp_idx_cost"]),
+                       **{f: int(v) for f, v in zip(GOLDEN_FLAGS, flags)})
+        out.append((cfg, np.nonzero(g[k + "group"] == gi)[0]))
+    return out

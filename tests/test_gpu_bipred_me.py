@@ -1,0 +1,169 @@
+"""vvcgpu_bipred_me_batch on the device: whole bi-predictive refinements (the loop of InterSearch::predInterSearch, InterSearch.cpp:1058-1164) in one
+launch, against the compiled reference's results (tests/golden/bipred_me.npz) and, call by call, against the tests' restatement
+(tests/bipred_me_cases.py, pinned to the reference by tests/test_bipred_me_cpu.py)."""
+import functools
+import itertools
+import os
+import threading
+
+import numpy as np
+import pytest
+import torch
+
+import bipred_me_cases as bc
+from vvcsoftware_vtm_amd import abi
+
+pytestmark = pytest.mark.gpu
+G = os.path.join(os.path.dirname(__file__), "golden")
+W, H = 256, 128
+PAIRS = list(itertools.product(bc.SIDES, bc.SIDES))          # every served (w, h); 32x32 is the last wave-owned square, 64x32 / 32x64 the first workgroup-owned
+
+
+def dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def device_cfg(cfg, planes_dev, max_pu=(0, 0)):
+    from vvcsoftware_vtm_amd import ops
+    m = bc.MARGIN
+    return ops.bipred_me_cfg(cfg["lambda_"], [planes_dev[i] for i in range(planes_dev.shape[0])], (m, m), cfg["pic_w"], cfg["pic_h"], cfg["bit_depth"],
+                             (cfg["clp_min"], cfg["clp_max"]), cfg["num_iter"], cfg["pick_list_by_cost"], cfg["mvd_l1_zero"], cfg["search_range"],
+                             cfg["clip_key"], cfg["use_hadamard"], cfg["mvp_idx_cost"], cfg["max_cu"], max_pu)
+
+
+def run(org, planes, cfg, items, want_trace=True, max_pu=(0, 0)):
+    from vvcsoftware_vtm_amd import ops
+    d_planes = dev(planes)
+    res, trace = ops.bipred_me_batch(dev(org), ops.struct_to_device(items), len(items), device_cfg(cfg, d_planes, max_pu), want_trace)
+    torch.cuda.synchronize()
+    res = res.cpu().numpy().view(abi.BIPRED_ME_RESULT)
+    return res, (trace.cpu().numpy().view(abi.BIPRED_ME_STEP).reshape(len(items), abi.BIPRED_ME_MAX_STEPS) if want_trace else None)
+
+
+def shapes_of(n):
+    """n shapes: every served side pair once when n allows it, the rest small; shuffled, so that wave- and workgroup-owned PUs alternate"""
+    rng = np.random.default_rng(n)
+    small = [(16, 16), (8, 8), (4, 4), (8, 4), (4, 8), (16, 8), (32, 32), (32, 16), (64, 32), (8, 16), (64, 8), (4, 16)]
+    if n >= 100:
+        shapes = PAIRS + [small[int(i)] for i in rng.integers(0, len(small), n - len(PAIRS))]
+    else:
+        shapes = [PAIRS[int(i)] for i in rng.choice(len(PAIRS), min(n, len(PAIRS)), replace=False)] + [small[int(i)] for i in rng.integers(0, len(small), max(0, n - len(PAIRS)))]
+    return [shapes[int(i)] for i in rng.permutation(len(shapes))]
+
+
+@functools.lru_cache(maxsize=None)
+def fresh(n):
+    """seeded inputs and the restatement's answer, computed once"""
+    kw = {1: dict(n_ref=(1, 1)), 2: dict(n_ref=(4, 2), search_range=2, use_hadamard=0, fast=True), 63: dict(n_ref=(2, 2), clip_key=0),
+          64: dict(n_ref=(2, 1), fast=True), 65: dict(n_ref=(1, 2), num_iter=1, pick_list_by_cost=1), 300: dict(n_ref=(2, 2), search_range=4)}[n]
+    org, planes, cfg, items = bc.fresh_set(700 + n, 8 if n in (2, 65) else 10, shapes_of(n), **kw)
+    res, trace = bc.search_all(org, planes, cfg, items)
+    return org, planes, cfg, items, res, trace
+
+
+@pytest.mark.parametrize("bd", [10, 8])
+def test_results_and_trace_equal_the_reference_golden(bd):
+    g = np.load(os.path.join(G, "bipred_me.npz"))
+    k = "bd%d_" % bd
+    planes = bc.pad(g[k + "planes"])
+    items, want, want_trace = g[k + "items"], g[k + "want"], g[k + "trace"]
+    for cfg, idx in bc.golden_groups(g, bd):
+        res, trace = run(g[k + "org"], planes, cfg, items[idx])
+        for j, i in enumerate(idx):
+            assert np.array_equal(trace[j], want_trace[i]), (bd, i, trace[j], want_trace[i])
+            assert res[j].tobytes() == want[i].tobytes(), (bd, i, res[j], want[i])
+
+
+@pytest.mark.parametrize("n", [1, 2, 63, 64, 65, 300])
+def test_results_and_trace_equal_the_restatement(n):
+    org, planes, cfg, items, want, want_trace = fresh(n)
+    if n == 300:
+        px = items["w"].astype(int) * items["h"]
+        assert set(zip(items["w"].tolist(), items["h"].tolist())) == set(PAIRS)
+        assert ((px[:-1] <= 1024) & (px[1:] > 1024)).any() and ((px[:-1] > 1024) & (px[1:] <= 1024)).any()     # the two owner kinds side by side
+        # passes of the loop: the first always accepts (uiCostBi starts at the maximum), so an item stops in iIter 1, 2 or 3 or runs all four;
+        # stops in iIter 1 (the earliest) next to full runs
+        ps = np.array([bc.passes(want_trace[i], want[i]["me_calls"]) for i in range(n)])
+        assert set(ps.tolist()) == {2, 3, 4}
+        assert ((ps[:-1] == 2) & (ps[1:] == 4)).any() or ((ps[:-1] == 4) & (ps[1:] == 2)).any()
+    res, trace = run(org, planes, cfg, items)
+    for i in range(n):
+        assert np.array_equal(trace[i], want_trace[i]), (i, items[i]["w"], items[i]["h"], trace[i], want_trace[i])
+        assert res[i].tobytes() == want[i].tobytes(), (i, res[i], want[i])
+
+
+def test_max_pu_hint_gives_the_same_results_and_skips_what_exceeds_it():
+    org, planes, cfg, items, want, want_trace = fresh(64)
+    res, trace = run(org, planes, cfg, items, max_pu=(32, 16))
+    big = (items["w"] > 32) | (items["h"] > 16)
+    assert big.any() and (~big).any()
+    assert (res[big]["cost"] == np.uint64(bc.U64_MAX)).all() and (res[big]["me_calls"] == 0).all()
+    assert np.array_equal(res[~big], want[~big]) and np.array_equal(trace[~big], want_trace[~big])
+
+
+def test_null_trace_gives_the_same_results():
+    org, planes, cfg, items, want, _ = fresh(63)
+    res, trace = run(org, planes, cfg, items, want_trace=False)
+    assert trace is None and np.array_equal(res, want)
+
+
+def test_items_outside_the_contract_get_the_sentinel():
+    org, planes, cfg, items, want, want_trace = fresh(63)
+    items = items[:10].copy()
+    items[1]["w"] = 12                           # no served side
+    items[2]["h"] = 256                          # above 128
+    items[3]["n_ref"][0] = 5
+    items[4]["n_ref"][1] = 0
+    items[5]["ref"][0][0]["plane"] = planes.shape[0]
+    items[6]["ref"][1][0]["num_cand"] = 3
+    items[7]["ref"][0][0]["num_cand"] = 0
+    items[8]["pos_x"] = W - int(items[8]["w"]) + 4   # not inside the picture
+    res, trace = run(org, planes, cfg, items)
+    for i in (0, 9):
+        assert res[i].tobytes() == want[i].tobytes() and np.array_equal(trace[i], want_trace[i]), i
+    zero = np.zeros(1, abi.BIPRED_ME_RESULT)
+    zero["cost"] = np.uint64(bc.U64_MAX)
+    for i in range(1, 9):
+        assert res[i].tobytes() == zero[0].tobytes(), (i, res[i])
+        assert trace[i].tobytes() == bytes(trace[i].nbytes), i
+
+
+def test_two_streams_from_two_host_threads():
+    from vvcsoftware_vtm_amd import ops
+    org, planes, cfg, items, want, want_trace = fresh(63)
+    d_org, d_planes, d_items = dev(org), dev(planes), ops.struct_to_device(items)
+    dcfg = device_cfg(cfg, d_planes)
+    torch.cuda.synchronize()
+    out, errs = [None, None], []
+
+    def work(k):
+        try:
+            s = torch.cuda.Stream()
+            with torch.cuda.stream(s):
+                for _ in range(3):
+                    res, trace = ops.bipred_me_batch(d_org, d_items, len(items), dcfg)
+                s.synchronize()
+            out[k] = (res.cpu().numpy().view(abi.BIPRED_ME_RESULT), trace.cpu().numpy().view(abi.BIPRED_ME_STEP).reshape(len(items), -1))
+        except Exception as e:                    # noqa: BLE001
+            errs.append(e)
+    ts = [threading.Thread(target=work, args=(k,)) for k in range(2)]
+    for t in ts:
+        t.start()
+    for t in ts:
+        t.join()
+    assert not errs, errs
+    for k in range(2):
+        assert np.array_equal(out[k][0], want) and np.array_equal(out[k][1], want_trace), k
+
+
+def test_entry_equals_the_chained_form_of_the_existing_entries():
+    """a consistency supplement, not evidence: mc_batch -> pelop -> sad_search -> frac_refine per iteration with host decisions between
+    (tests/bipred_me_chain.py) ends where the one-launch entry ends"""
+    import bipred_me_chain
+    shapes = [(16, 16), (8, 8), (32, 16), (64, 64), (16, 16), (4, 8), (128, 32), (16, 16), (8, 8), (32, 32), (16, 64)]
+    org, planes, cfg, items = bc.fresh_set(41, 10, shapes, n_ref=(2, 2), single=(4, -8))
+    res, _ = run(org, planes, cfg, items)
+    got, launches = bipred_me_chain.chained(dev(org), dev(planes), cfg, items, bc.MARGIN)
+    assert launches > 4 * len(set(shapes))
+    for f in ("mv", "ref_idx", "mvp", "bits", "mot_bits", "me_calls", "closing", "cost"):
+        assert np.array_equal(got[f], res[f]), (f, got[f], res[f])

@@ -320,6 +320,11 @@ int vvcgpu_sizeof(int id)
   case 35: return (int)sizeof(vvcgpu_affine_me_cfg);
   case 36: return (int)sizeof(vvcgpu_affine_me_result);
   case 37: return (int)sizeof(vvcgpu_affine_me_step);
+  case 38: return (int)sizeof(vvcgpu_bipred_me_ref);
+  case 39: return (int)sizeof(vvcgpu_bipred_me_item);
+  case 40: return (int)sizeof(vvcgpu_bipred_me_cfg);
+  case 41: return (int)sizeof(vvcgpu_bipred_me_result);
+  case 42: return (int)sizeof(vvcgpu_bipred_me_step);
   default: return -1;
   }
 }
