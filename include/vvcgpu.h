@@ -45,7 +45,8 @@ int         vvcgpu_set_device(int device);
  * 13 dqtr_desc, 14 afg_desc, 15 afe_desc, 16 tz_pu, 17 tz_cfg, 18 intra_desc, 19 cclm_desc, 20 intra_fill_desc, 21 imv_pu, 22 imv_result, 23 quant_desc,
  * 24 dq_rates, 25 depquant_desc, 26 rdoq_rates, 27 rdoq_desc, 28 intra_satd_desc, 29 affine_iter, 30 me_hier_cfg, 31 wp_param,
  * 32 wp_sad_cand, 33 tile_stats, 34 affine_me_item, 35 affine_me_cfg, 36 affine_me_result, 37 affine_me_step,
- * 38 bipred_me_ref, 39 bipred_me_item, 40 bipred_me_cfg, 41 bipred_me_result, 42 bipred_me_step; -1 for unknown ids. */
+ * 38 bipred_me_ref, 39 bipred_me_item, 40 bipred_me_cfg, 41 bipred_me_result, 42 bipred_me_step, 44 affine_bipred_ref, 45 affine_bipred_item,
+ * 46 affine_bipred_cfg, 47 affine_bipred_result, 48 affine_bipred_step; -1 for unknown ids (43 is not assigned and stays unknown). */
 int         vvcgpu_sizeof(int struct_id);
 
 /* ---- device memory helpers for host-side callers (the reference keeps pictures in host memory; the shim stages them).
@@ -727,6 +728,104 @@ typedef struct {                        /* one xMotionEstimation + xCheckBestMVP
 /* trace (may be NULL): n x VVCGPU_BIPRED_ME_MAX_STEPS entries, entry s of an item = its s-th xMotionEstimation call, unused entries zero. */
 int vvcgpu_bipred_me_batch(const vvc_pel* org_base, const vvcgpu_bipred_me_item* items, int n, const vvcgpu_bipred_me_cfg* cfg_host,
                            vvcgpu_bipred_me_result* results, vvcgpu_bipred_me_step* trace, void* stream);
+
+/* The WHOLE affine bi-predictive search of a PU (the bi-predictive part of InterSearch::xPredAffineInterSearch, InterSearch.cpp:2823-2997, with every
+ * xAffineMotionEstimation(..., bBi = true) :3286-3743 and xCheckBestAffineMVP :3181-3284 inside it) for a list of independent PUs in ONE launch with
+ * no host synchronisation inside.  The owner of a PU (a wavefront up to 1024 samples, a workgroup above) carries it through every dependent step; per
+ * iteration and reference index, in the reference's order:
+ *   set-up            (:2831-2882) uiMotBits, uiBits[2]; with mvd_l1_zero list 1 is fixed: the caller passes ref_idx[1] = bestBiPRefIdxL1 and that record's
+ *                     mvp_idx = bestBiPMvpL1, the device sets cMvBi[1] = cMvTemp[1][ref] = cMvPredBi[1][ref] = that candidate (:2847-2853) and derives
+ *                     uiMotBits[1] by :2864-2874;
+ *   list              (:2895-2928) iIter % 2, list 0 first; pick_list_by_cost: the list with the larger uni cost; mvd_l1_zero: list 0;
+ *   other prediction  luma motionCompensation of an affine PU (InterPrediction::xPredInterUni, InterPrediction.cpp:377-407): the control-point vectors
+ *                     PU::setAllAffineMv leaves in the corners of the motion buffer (UnitTools.cpp:2319-2330), no clipMv of them, xPredAffineBlk
+ *                     (:550-722) with bi = false, rounded and clipped -- of the other list's current cMvBi at iRefIdxBi, formed when the iteration
+ *                     starts (the reference forms it at :2913-2920 and again after each acceptance, :2970-2977; an iteration only ever reads the
+ *                     prediction of the OTHER list, so both give the same);
+ *   search key        2 org - otherPred, clipped when clip_for_bipred_me (Buffer.h:389-416; op 4 of vvcgpu_pelop_batch); it lives in LDS;
+ *   per reference     skipped when only_ref says so (:2936-2941); the bits of :2944-2953; xAffineMotionEstimation(bBi = true) from cMvTemp[list][ref]
+ *                     against cMvPredBi[list][ref] -- what vvcgpu_affine_me_batch does for an item with half_weight = 1, the original being the key;
+ *                     xCheckBestAffineMVP over the candidates of that (list, ref): nothing when num_cand < 2, the second-predictor rule for vectors 1
+ *                     and 2, uint32 bits, wrapping uint64 cost; then keep-if-strictly-better against uiCostBi (:2960-2978), which starts at UINT64_MAX.
+ * After a pass without change (:2981-2995) the two closing xCheckBestAffineMVP calls are made when uiCostBi <= uiCost[0] && uiCostBi <= uiCost[1]; each
+ * gets the candidate set of the list it checks (unlike the translational loop).  All vectors are in 1/16 sample units (after Mv::setHighPrec; the
+ * convention of vvcgpu_affine_me_item.mvp).  Not served: the uni-predictive stage (:2651-2814; one vvcgpu_affine_me_batch call plus host decisions),
+ * the final mode choice (:3017-3099; host), weighted prediction.
+ * Reference planes and readable margin: as vvcgpu_bipred_me_batch -- ref_planes[i] points to sample (0, 0) of picture i inside its padded allocation;
+ * sub-block vectors are clipped to the picture + 8 / - CTU - 8 samples and the 8 taps reach 4 further: max_cu + 12 readable samples around the picture
+ * on every side serve every search.
+ * items, results, trace: device memory.  Items cannot be validated on the host: an item outside the contract (a side not in {16, 32, 64, 128} or larger
+ * than the CTU or than cfg.max_pu_w / max_pu_h, a PU not inside the picture, n_ref outside 1..4, ref_idx outside the list, only_ref outside -1 ..
+ * n_ref - 1, a plane index outside [0, n_planes), num_cand outside 1..2, mvp_idx outside the candidates, org_stride <= 0) is skipped and gets
+ * cost = ~0 (UINT64_MAX) with everything else zero; its trace entries are zero; it reads no sample.  n == 0 is a no-op; null pointers (trace may be
+ * NULL), n < 0, geometry, clp_min > clp_max, lambda outside [0, 2^20), num_iter other than 1 or 4, n_planes outside 1..16 and max_pu sides that are
+ * no served side return VVCGPU_E_ARG, a bit depth outside 8..10 VVCGPU_E_UNSUPPORTED, before any device work. */
+#define VVCGPU_AFFINE_BIPRED_MAX_STEPS 16  /* num_iter 4 x at most 4 reference indices */
+#define VVCGPU_AFFINE_BIPRED_MAX_REFS 4
+typedef struct {                        /* one (list, reference index) of a PU                sizeof == 80 */
+  int32_t plane;             /* index into cfg.ref_planes */
+  int32_t mv[3][2];          /* cMvTemp[list][ref] on entry: the uni-predictive affine result for this reference */
+  int32_t mv_cand[2][3][2];  /* aacAffineAMVPInfo[list][ref]: mvCandLT / RT / LB of candidates 0 and 1 */
+  int16_t num_cand;          /* .numCand: 1..2 */
+  int16_t mvp_idx;           /* aaiMvpIdx[list][ref]; cMvPred[list][ref] = mv_cand[mvp_idx] */
+} vvcgpu_affine_bipred_ref;
+typedef struct {                        /* one PU                                             sizeof == 784 */
+  int32_t  pos_x, pos_y;     /* pu.cu->lumaPos() */
+  int16_t  w, h;             /* 16, 32, 64 or 128 each */
+  int16_t  six_param;        /* cu->affineType */
+  int16_t  reserved0;
+  int64_t  org_off;          /* elements from org_base */
+  int32_t  org_stride;
+  int32_t  n_ref[2];         /* getNumRefIdx(list): 1..4 */
+  int32_t  ref_idx[2];       /* iRefIdx[list] */
+  int32_t  mv[2][3][2];      /* aacMv[list] */
+  int32_t  reserved1;
+  uint64_t cost[2];          /* uiCost[0..1] */
+  uint32_t bits[2];          /* uiBits[0..1] */
+  uint32_t mb_bits[3];       /* uiMbBits[0..2] */
+  int32_t  only_ref[2];      /* refIdx4Para[list] of a 6-parameter PU: -1 every index, r >= 0 only index r (< n_ref[list]) is searched (:2936-2941) */
+  int32_t  reserved2;
+  vvcgpu_affine_bipred_ref ref[2][VVCGPU_AFFINE_BIPRED_MAX_REFS];
+} vvcgpu_affine_bipred_item;
+typedef struct {                        /* host struct                                        sizeof == 224 */
+  double  lambda;            /* RdCost::m_motionLambda */
+  const vvc_pel* ref_planes[16];   /* device pointers; entries from n_planes on are ignored */
+  int32_t n_planes, ref_stride;
+  int32_t pic_w, pic_h, max_cu_w, max_cu_h;                 /* clipMv, sub-block vector clip */
+  int32_t bit_depth, clp_min, clp_max;
+  int32_t num_iter;             /* iNumIter: 4 or 1 */
+  int32_t pick_list_by_cost;    /* FASTINTERSEARCH_MODE1/2 (:2896-2906) */
+  int32_t mvd_l1_zero;          /* slice.getMvdL1ZeroFlag() */
+  int32_t clip_for_bipred_me;   /* getClipForBiPredMeEnabled() */
+  int32_t affine_type;          /* sps.getSpsNext().getUseAffineType(): iteration limit 3 per search; 0: 5 (as vvcgpu_affine_me_cfg) */
+  uint32_t mvp_idx_cost[3];     /* m_auiMVPIdxCost[0..2][AMVP_MAX_NUM_CANDS] */
+  int32_t max_pu_w, max_pu_h;   /* the caller states that no item is wider / higher (0: 128): LDS per owner is sized by it; an item beyond it is skipped */
+  int32_t reserved[3];
+} vvcgpu_affine_bipred_cfg;
+typedef struct {                        /* sizeof == 144 */
+  int32_t  mv[2][3][2];      /* cMvBi[0..1] */
+  int32_t  ref_idx[2];       /* iRefIdxBi[0..1] */
+  int32_t  mvp_idx[2];       /* aaiMvpIdxBi[list][iRefIdxBi[list]] */
+  int32_t  mvp[2][3][2];     /* cMvPredBi[list][iRefIdxBi[list]] */
+  uint32_t bits;             /* uiBits[2] */
+  uint32_t mot_bits[2];      /* uiMotBits[0..1] */
+  uint32_t me_calls;         /* xAffineMotionEstimation calls made */
+  uint32_t closing;          /* 1: the closing xCheckBestAffineMVP calls ran */
+  uint32_t reserved;
+  uint64_t cost;             /* uiCostBi; ~0 with everything else zero: item skipped */
+} vvcgpu_affine_bipred_result;
+typedef struct {                        /* one xAffineMotionEstimation + xCheckBestAffineMVP  sizeof == 56 */
+  int32_t  list, ref;
+  int32_t  mv[3][2];         /* cMvTemp[list][ref] after the search */
+  uint32_t steps;            /* predictions evaluated, as vvcgpu_affine_me_result.steps */
+  uint32_t bits;             /* uiBitsTemp after xCheckBestAffineMVP */
+  int32_t  mvp_idx;          /* aaiMvpIdxBi[list][ref] after xCheckBestAffineMVP */
+  int32_t  accepted;         /* uiCostTemp < uiCostBi */
+  uint64_t cost;             /* uiCostTemp after xCheckBestAffineMVP */
+} vvcgpu_affine_bipred_step;
+/* trace (may be NULL): n x VVCGPU_AFFINE_BIPRED_MAX_STEPS entries, entry s of an item = its s-th xAffineMotionEstimation call, unused entries zero. */
+int vvcgpu_affine_bipred_me_batch(const vvc_pel* org_base, const vvcgpu_affine_bipred_item* items, int n, const vvcgpu_affine_bipred_cfg* cfg_host,
+                                  vvcgpu_affine_bipred_result* results, vvcgpu_affine_bipred_step* trace, void* stream);
 
 /* ---- N2 ("next" row): integer-sample TZ search of whole PUs, on the device  (InterSearch::xTZSearch,
  *          EncoderLib/InterSearch.cpp:1971-2252, with xTZSearchHelp :249-343, xTZ2PointSearch :349-374,

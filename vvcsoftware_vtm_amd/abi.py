@@ -163,6 +163,28 @@ class BipredMeCfg(C.Structure):
                 ("max_pu_w", C.c_int32), ("max_pu_h", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
+# vvcgpu_affine_bipred_me_batch: one (list, reference index) record, one PU, its result and one step of its trace
+AFFINE_BIPRED_MAX_STEPS, AFFINE_BIPRED_MAX_REFS = 16, 4
+AFFINE_BIPRED_REF = np.dtype([("plane", "<i4"), ("mv", "<i4", (3, 2)), ("mv_cand", "<i4", (2, 3, 2)), ("num_cand", "<i2"), ("mvp_idx", "<i2")])
+AFFINE_BIPRED_ITEM = np.dtype([("pos_x", "<i4"), ("pos_y", "<i4"), ("w", "<i2"), ("h", "<i2"), ("six_param", "<i2"), ("reserved0", "<i2"), ("org_off", "<i8"),
+                               ("org_stride", "<i4"), ("n_ref", "<i4", (2,)), ("ref_idx", "<i4", (2,)), ("mv", "<i4", (2, 3, 2)), ("reserved1", "<i4"),
+                               ("cost", "<u8", (2,)), ("bits", "<u4", (2,)), ("mb_bits", "<u4", (3,)), ("only_ref", "<i4", (2,)), ("reserved2", "<i4"),
+                               ("ref", AFFINE_BIPRED_REF, (2, AFFINE_BIPRED_MAX_REFS))])
+AFFINE_BIPRED_RESULT = np.dtype([("mv", "<i4", (2, 3, 2)), ("ref_idx", "<i4", (2,)), ("mvp_idx", "<i4", (2,)), ("mvp", "<i4", (2, 3, 2)), ("bits", "<u4"),
+                                 ("mot_bits", "<u4", (2,)), ("me_calls", "<u4"), ("closing", "<u4"), ("reserved", "<u4"), ("cost", "<u8")])
+AFFINE_BIPRED_STEP = np.dtype([("list", "<i4"), ("ref", "<i4"), ("mv", "<i4", (3, 2)), ("steps", "<u4"), ("bits", "<u4"), ("mvp_idx", "<i4"),
+                               ("accepted", "<i4"), ("cost", "<u8")])
+
+
+class AffineBipredCfg(C.Structure):
+    """vvcgpu_affine_bipred_cfg"""
+    _fields_ = [("lambda_", C.c_double), ("ref_planes", C.c_void_p * 16), ("n_planes", C.c_int32), ("ref_stride", C.c_int32),
+                ("pic_w", C.c_int32), ("pic_h", C.c_int32), ("max_cu_w", C.c_int32), ("max_cu_h", C.c_int32), ("bit_depth", C.c_int32),
+                ("clp_min", C.c_int32), ("clp_max", C.c_int32), ("num_iter", C.c_int32), ("pick_list_by_cost", C.c_int32), ("mvd_l1_zero", C.c_int32),
+                ("clip_for_bipred_me", C.c_int32), ("affine_type", C.c_int32), ("mvp_idx_cost", C.c_uint32 * 3),
+                ("max_pu_w", C.c_int32), ("max_pu_h", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
 # ---- encoder picture analysis ---------------------------------------------------------------------------------------------------------------------
 # vvcgpu_tile_stats: one tile of vvcgpu_tile_stats_picture; vvcgpu_wp_sad_cand: one candidate of vvcgpu_wp_sad_batch (flags: WP_SAD_*)
 TILE_STATS = np.dtype([("sa_act", "<u8"), ("sum", "<u8"), ("ss_err", "<u8")])

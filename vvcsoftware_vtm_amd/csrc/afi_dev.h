@@ -30,9 +30,9 @@ constexpr int AFI_MAX = 128, AFI_WAVE_MAX = 1024;          // PUs of up to AFI_W
 typedef const __attribute__((address_space(3))) Pel* AfiLdsPel;
 
 // NT = 64: the wavefront owns the PU; NT = 256: the four wavefronts of the workgroup share it and their sums meet in `red`
-// this lane's share of the P x (P + 1) sums
-template <int P, int NT>
-__device__ __forceinline__ void afi_accumulate(const vvcgpu_affine_iter& d, const Pel* __restrict__ org, const Pel* predL, int w, int h,
+// this lane's share of the P x (P + 1) sums; OrgPtr: the original's pointer type (plain: global memory; AfiLdsPel: a block the caller keeps in LDS)
+template <int P, int NT, class OrgPtr = const Pel*>
+__device__ __forceinline__ void afi_accumulate(const vvcgpu_affine_iter& d, OrgPtr __restrict__ org, const Pel* predL, int w, int h,
                                                long long (&acc)[P][P + 1], int tid)
 {
 #pragma unroll
@@ -119,13 +119,13 @@ __device__ __forceinline__ void afi_fold(long long (&v)[LEN], int lane)
 
 // afi_equations with the reduction in registers only, 32 values at a time (at most 32 + 16 for the 42 sums of the 6-parameter model: 64 registers
 // instead of 128, 49 shuffles instead of 63); integer sums, so the result is the same whatever the order
-template <int P, int NT>
-__device__ __forceinline__ void afi_equations_regs(const vvcgpu_affine_iter& d, const Pel* __restrict__ org, const Pel* predL, int w, int h,
+template <int P, int NT, class OrgPtr = const Pel*>
+__device__ __forceinline__ void afi_equations_regs(const vvcgpu_affine_iter& d, OrgPtr __restrict__ org, const Pel* predL, int w, int h,
                                                    long long* out, long long (*red)[64], int tid)
 {
   const int lane = tid & 63;
   long long acc[P][P + 1];
-  afi_accumulate<P, NT>(d, org, predL, w, h, acc, tid);
+  afi_accumulate<P, NT, OrgPtr>(d, org, predL, w, h, acc, tid);
   long long a[32];
 #pragma unroll
   for (int i = 0; i < 32; i++) a[i] = i < P * (P + 1) ? acc[i / (P + 1)][i % (P + 1)] : 0;
@@ -145,16 +145,17 @@ __device__ __forceinline__ void afi_equations_regs(const vvcgpu_affine_iter& d, 
 }
 
 // distortion of rows [r0, r1) x 16 of the PU against the prediction in LDS, by one wavefront
-__device__ __forceinline__ unsigned long long afi_dist(const vvcgpu_affine_iter& d, const Pel* __restrict__ org, const Pel* predL, int w, int h,
+template <class OrgPtr = const Pel*>
+__device__ __forceinline__ unsigned long long afi_dist(const vvcgpu_affine_iter& d, OrgPtr __restrict__ org, const Pel* predL, int w, int h,
                                                        int distKind, int band0, int bandStep, int lane)
 {
   // bands of sixteen rows: every Hadamard tile of an affine PU (both sides >= 16) is at most sixteen rows high, the tile shape is the whole PU's
   unsigned long long sum = 0;
   for (int b = band0; b * 16 < h; b += bandStep)
   {
-    const Pel* o = org + (size_t)b * 16 * d.org_stride;
+    OrgPtr o = org + (size_t)b * 16 * d.org_stride;
     AfiLdsPel c = (AfiLdsPel)predL + b * 16 * w;
-    if (distKind == 1) sum += satd_block<64, AfiLdsPel>(o, d.org_stride, c, w, w, 16, lane, 0, h);
+    if (distKind == 1) sum += satd_block<64, AfiLdsPel, OrgPtr>(o, d.org_stride, c, w, w, 16, lane, 0, h);
     else
     {
       unsigned s = 0;

@@ -325,6 +325,11 @@ int vvcgpu_sizeof(int id)
   case 40: return (int)sizeof(vvcgpu_bipred_me_cfg);
   case 41: return (int)sizeof(vvcgpu_bipred_me_result);
   case 42: return (int)sizeof(vvcgpu_bipred_me_step);
+  case 44: return (int)sizeof(vvcgpu_affine_bipred_ref);
+  case 45: return (int)sizeof(vvcgpu_affine_bipred_item);
+  case 46: return (int)sizeof(vvcgpu_affine_bipred_cfg);
+  case 47: return (int)sizeof(vvcgpu_affine_bipred_result);
+  case 48: return (int)sizeof(vvcgpu_affine_bipred_step);
   default: return -1;
   }
 }

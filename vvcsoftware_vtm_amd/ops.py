@@ -12,7 +12,8 @@ from .abi import (AFE_DESC, AFFINE_ITER, AFFINE_ME_ITEM, AFFINE_ME_MAX_STEPS, AF
                   FRAC_RESULT, IF_DESC, IMV_PU, IMV_RESULT, INTRA_DESC, INTRA_FILL_DESC, INTRA_SATD_DESC, MC_DESC, PELOP_DESC, QUANT_DESC, RC_DESC,
                   RDOQ_DESC, RDOQ_RATES, RDPCM_DESC, SAO_DTYPE, SEARCH_BEST, SEARCH_BLK, TR_DESC, TZ_CFG, TZ_PU, DeblockCfg, MeHierCfg, MvCost,
                   PelopCfg, Planes, AffineMeCfg, BipredMeCfg, BIPRED_ME_ITEM, BIPRED_ME_MAX_PLANES, BIPRED_ME_MAX_REFS, BIPRED_ME_MAX_STEPS, BIPRED_ME_REF,
-                  BIPRED_ME_RESULT, BIPRED_ME_STEP, WP_PARAM, TILE_STATS, WP_SAD_CAND, WP_SAD_HIGH_PRECISION, WP_SAD_CLIPPED)
+                  BIPRED_ME_RESULT, BIPRED_ME_STEP, AffineBipredCfg, AFFINE_BIPRED_ITEM, AFFINE_BIPRED_MAX_REFS, AFFINE_BIPRED_MAX_STEPS,
+                  AFFINE_BIPRED_REF, AFFINE_BIPRED_RESULT, AFFINE_BIPRED_STEP, WP_PARAM, TILE_STATS, WP_SAD_CAND, WP_SAD_HIGH_PRECISION, WP_SAD_CLIPPED)
 
 
 def _stream():
@@ -553,6 +554,38 @@ def bipred_me_batch(org_base, items_dev, n, cfg, want_trace=True):
     res = torch.empty(n * BIPRED_ME_RESULT.itemsize, dtype=torch.uint8, device=org_base.device)
     trace = torch.empty(n * BIPRED_ME_MAX_STEPS * BIPRED_ME_STEP.itemsize, dtype=torch.uint8, device=org_base.device) if want_trace else None
     capi.call("vvcgpu_bipred_me_batch", capi.ptr(org_base), capi.ptr(items_dev), n, C.byref(cfg), capi.ptr(res),
+              capi.ptr(trace) if want_trace else None, _stream())
+    return res, trace
+
+
+def affine_bipred_cfg(lambda_, ref_planes, ref_origin, pic_w, pic_h, bit_depth=10, clp=(0, 1023), num_iter=4, pick_list_by_cost=False, mvd_l1_zero=False,
+                      clip_key=True, affine_type=1, mvp_idx_cost=(1, 1, 0), max_cu=128, max_pu=(0, 0)):
+    """vvcgpu_affine_bipred_cfg of one slice.  ref_planes: the PADDED reference luma planes (2-D int16 CUDA tensors of one stride; keep them alive while
+    calls that use the cfg run); ref_origin = (x, y) of picture sample (0, 0) inside each of them"""
+    cfg = AffineBipredCfg()
+    cfg.lambda_ = lambda_
+    assert 1 <= len(ref_planes) <= 16
+    for i, t in enumerate(ref_planes):
+        ptr, stride, _, _ = _plane(t, "ref_planes[%d]" % i)
+        assert stride == ref_planes[0].stride(0), "reference planes of one stride"
+        cfg.ref_planes[i] = ptr.value + 2 * (ref_origin[1] * stride + ref_origin[0])
+    cfg.n_planes, cfg.ref_stride = len(ref_planes), ref_planes[0].stride(0)
+    cfg.pic_w, cfg.pic_h, cfg.max_cu_w, cfg.max_cu_h = pic_w, pic_h, max_cu, max_cu
+    cfg.bit_depth, cfg.clp_min, cfg.clp_max = bit_depth, clp[0], clp[1]
+    cfg.num_iter, cfg.pick_list_by_cost, cfg.mvd_l1_zero = num_iter, int(pick_list_by_cost), int(mvd_l1_zero)
+    cfg.clip_for_bipred_me, cfg.affine_type = int(clip_key), int(affine_type)
+    cfg.mvp_idx_cost[:] = mvp_idx_cost
+    cfg.max_pu_w, cfg.max_pu_h = max_pu
+    return cfg
+
+
+def affine_bipred_me_batch(org_base, items_dev, n, cfg, want_trace=True):
+    """The bi-predictive part of xPredAffineInterSearch for n independent PUs in one launch: items_dev = AFFINE_BIPRED_ITEM records on the device,
+    cfg = affine_bipred_cfg(...).  -> (AFFINE_BIPRED_RESULT records, AFFINE_BIPRED_STEP records [n x AFFINE_BIPRED_MAX_STEPS] or None), uint8 tensors"""
+    assert isinstance(cfg, AffineBipredCfg)
+    res = torch.empty(n * AFFINE_BIPRED_RESULT.itemsize, dtype=torch.uint8, device=org_base.device)
+    trace = torch.empty(n * AFFINE_BIPRED_MAX_STEPS * AFFINE_BIPRED_STEP.itemsize, dtype=torch.uint8, device=org_base.device) if want_trace else None
+    capi.call("vvcgpu_affine_bipred_me_batch", capi.ptr(org_base), capi.ptr(items_dev), n, C.byref(cfg), capi.ptr(res),
               capi.ptr(trace) if want_trace else None, _stream())
     return res, trace
 
