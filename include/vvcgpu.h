@@ -46,7 +46,8 @@ int         vvcgpu_set_device(int device);
  * 24 dq_rates, 25 depquant_desc, 26 rdoq_rates, 27 rdoq_desc, 28 intra_satd_desc, 29 affine_iter, 30 me_hier_cfg, 31 wp_param,
  * 32 wp_sad_cand, 33 tile_stats, 34 affine_me_item, 35 affine_me_cfg, 36 affine_me_result, 37 affine_me_step,
  * 38 bipred_me_ref, 39 bipred_me_item, 40 bipred_me_cfg, 41 bipred_me_result, 42 bipred_me_step, 44 affine_bipred_ref, 45 affine_bipred_item,
- * 46 affine_bipred_cfg, 47 affine_bipred_result, 48 affine_bipred_step; -1 for unknown ids (43 is not assigned and stays unknown). */
+ * 46 affine_bipred_cfg, 47 affine_bipred_result, 48 affine_bipred_step, 50 unipred_me_ref, 51 unipred_me_item, 52 unipred_me_cfg,
+ * 53 unipred_me_search, 54 unipred_me_result; -1 for unknown ids (43 and 49 are not assigned and stay unknown). */
 int         vvcgpu_sizeof(int struct_id);
 
 /* ---- device memory helpers for host-side callers (the reference keeps pictures in host memory; the shim stages them).
@@ -826,6 +827,111 @@ typedef struct {                        /* one xAffineMotionEstimation + xCheckB
 /* trace (may be NULL): n x VVCGPU_AFFINE_BIPRED_MAX_STEPS entries, entry s of an item = its s-th xAffineMotionEstimation call, unused entries zero. */
 int vvcgpu_affine_bipred_me_batch(const vvc_pel* org_base, const vvcgpu_affine_bipred_item* items, int n, const vvcgpu_affine_bipred_cfg* cfg_host,
                                   vvcgpu_affine_bipred_result* results, vvcgpu_affine_bipred_step* trace, void* stream);
+
+/* The WHOLE uni-predictive stage of the translational inter search of a PU (the loop of InterSearch::predInterSearch, InterSearch.cpp:877-964, with
+ * xEstimateMvPredAMVP :1443-1483 / xGetTemplateCost :1606-1642, xMotionEstimation(bBi = false) :1668-1816 and xCheckBestMVP :1537-1603 inside it) for
+ * a list of independent PUs of mixed sizes, with no host synchronisation inside: two launches on the stream.  The first gives every (PU, list, reference
+ * index) search an owner of its own (a wavefront up to 1024 samples, a workgroup above), the second makes the per-PU decisions.  Results are bit-exact,
+ * the double arithmetic of the costs included.  Per PU and per (list, reference index), in the reference's order:
+ *   bits              uiBitsTemp = mb_bits[list] + the reference-index bits of :883-890 (cfg.n_ref[list]);
+ *   xEstimateMvPredAMVP   with the caller's candidates (bFilled = true; PU::fillMvpCand stays on the host): per candidate clipMv, luma xPredInterBlk
+ *                     (uni, rounded and clipped: the uni form of vvcgpu_mc_batch), full SAD (no row sub-sampling) + getCost(mvp_idx_cost[i]); the best by
+ *                     uiBestCost > uiTmpCost in candidate order; its cost is biPDistTemp;
+ *   :896-901          bestBiPDist / bestBiPMvpL1 / bestBiPRefIdxL1 when cfg.mvd_l1_zero (list 1, strict '<');
+ *   xMotionEstimation (bBi = false), diamond searches only.  Normal path: rcMv = rcMvPred, xTZSearch under the contract of vvcgpu_tz_search_batch
+ *                     (cost scale 2; VVCGPU_TZ_EXTENDED per item = MESEARCH_DIAMOND_ENHANCED; the 2Nx2N predictor m_integerMv2Nx2N[list][ref] per
+ *                     (list, reference) when VVCGPU_UNIPRED_PRED2), xPatternSearchFracDIF under the contract of vvcgpu_frac_refine (Hadamard when
+ *                     use_hadamard), then :1795-1805: vector (int << 2) + (half << 1) + qter, uiMvBits at scale 0, ruiBits += uiMvBits,
+ *                     ruiCost = (uint64)(floor((double)cost - (double)getCost(uiMvBits)) + (double)getCost(ruiBits)), getCost(b) = (uint64)(lambda b).
+ *                     Cached-start path (:1759-1766; VVCGPU_UNIPRED_CACHED: the block cache holds an integer vector for this (list, reference)): the
+ *                     search starts from that vector with the fast settings, not the extended ones, and without the 2Nx2N predictor.  The search range
+ *                     is cfg.search_range[list][ref] (m_aaiAdaptSR);
+ *   xCheckBestMVP     over that (list, reference)'s candidates;
+ *   list-1 shortcut   with cfg.fast_me_gen_b_low_delay and cfg.list1_to_list0[ref] >= 0 a list-1 reference takes list 0's vector instead of searching
+ *                     and corrects the cost as :909-921 do (uint64 subtraction, then addition), then xCheckBestMVP;
+ *   :944-962          keep-if-strictly-better per list, and the "valid list 1" record (list-1 references with list1_to_list0 < 0).
+ * Not served: imv != 0, weighted prediction, composite reference, MESEARCH_FULL and MESEARCH_SELECTIVE, affine.
+ * bipred_items_out (may be NULL): n complete vvcgpu_bipred_me_item records, exactly what vvcgpu_bipred_me_batch asks of its caller -- n_ref, planes,
+ * cMvTemp, candidates and aaiMvpIdx per (list, reference), iRefIdx, cMv, uiCost, uiBits, mb_bits -- with the mvd_l1_zero preparation of :1009-1023 and
+ * :1038 done when cfg.mvd_l1_zero (ref_idx[1] = bestBiPRefIdxL1, that record's mvp_idx = bestBiPMvpL1, its mv and mv[1] = that candidate), so that
+ * the buffer can be handed to vvcgpu_bipred_me_batch on the same stream as it is.  On a P slice (n_ref[1] == 0) the records carry n_ref[1] = 0, which
+ * the bi-predictive entry skips.
+ * Reference planes: up to 16 luma planes of one stride; ref_planes[i] points to sample (0, 0) of picture i inside its padded allocation.  Readable
+ * margin (a stated margin, as vvcgpu_bipred_me_batch): max_cu + 16 readable samples around the picture on every side.  Vectors are clipped to the picture
+ * + 8 / - CTU - 8 samples, and the block, the +-1 sample of the refinement and the 8 taps reach max_cu + 12 samples; the zero-neighbourhood rounds of the
+ * extended TZ search probe up to search_range / 2 around the zero vector whatever the clipped range is: a probe whose block would leave the picture by
+ * more than max_cu + 14 samples is clamped to that rectangle (a wrong SAD where the reference would read its own margin, never a fault).  Reference
+ * rows are read as aligned dwords; reference and original samples of the integer search must be non-negative (picture samples).
+ * items, results, bipred_items_out: device memory.  Items cannot be validated on the host: an item outside the contract (a side not in {4, 8, 16, 32,
+ * 64, 128} or larger than the CTU or than cfg.max_pu_w / max_pu_h, a PU not inside the picture, sub_shift outside 0..1 or h >> sub_shift == 0,
+ * org_stride <= 0, tz_flags other than 0 or VVCGPU_TZ_EXTENDED, and for a (list, reference) of the slice num_cand outside 1..2 or flags outside 0..3) is
+ * skipped: it reads no sample, its result has cost[0] = cost[1] = ~0 (UINT64_MAX) with everything else zero, its out-item is all zero.  n == 0 is a
+ * no-op; null pointers (bipred_items_out may be NULL), n < 0, geometry, clp_min > clp_max, lambda outside [0, 2^20), n_planes outside 1..16, n_ref[0]
+ * outside 1..4, n_ref[1] outside 0..4, a ref_plane outside [0, n_planes), a search_range outside 1..256, a list1_to_list0 outside [-1, n_ref[0]) and
+ * max_pu sides that are no served side return VVCGPU_E_ARG, a bit depth outside 8..10 VVCGPU_E_UNSUPPORTED, before any device work. */
+#define VVCGPU_UNIPRED_ME_MAX_REFS   4
+#define VVCGPU_UNIPRED_ME_MAX_PLANES 16
+enum { VVCGPU_UNIPRED_PRED2 = 1, VVCGPU_UNIPRED_CACHED = 2 };
+typedef struct {                        /* one (list, reference index) of a PU                sizeof == 40 */
+  int32_t mv_cand[2][2];  /* amvp.mvCand[0..1] (quarter units) */
+  int32_t pred2[2];       /* m_integerMv2Nx2N[list][ref] (integer units), used when VVCGPU_UNIPRED_PRED2 */
+  int32_t cached_mv[2];   /* the block cache's integer vector (integer units), used when VVCGPU_UNIPRED_CACHED */
+  int16_t num_cand;       /* amvp.numCand: 1..2 */
+  int16_t flags;          /* VVCGPU_UNIPRED_* */
+  int32_t reserved;
+} vvcgpu_unipred_me_ref;
+typedef struct {                        /* one PU                                             sizeof == 360 */
+  int32_t  pos_x, pos_y;  /* pu.cu->lumaPos() == the PU's position */
+  int16_t  w, h;          /* 4, 8, 16, 32, 64 or 128 each */
+  int16_t  sub_shift;     /* DistParam::subShift of the integer search: 0 or 1 */
+  int16_t  tz_flags;      /* 0 or VVCGPU_TZ_EXTENDED (normal path) */
+  int64_t  org_off;       /* elements from org_base */
+  int32_t  org_stride;
+  uint32_t mb_bits[3];    /* uiMbBits[0..2] */
+  vvcgpu_unipred_me_ref ref[2][VVCGPU_UNIPRED_ME_MAX_REFS];
+} vvcgpu_unipred_me_item;
+typedef struct {                        /* host struct                                        sizeof == 304 */
+  double  lambda;         /* RdCost::m_motionLambda */
+  const vvc_pel* ref_planes[VVCGPU_UNIPRED_ME_MAX_PLANES];  /* device pointers; entries from n_planes on are ignored */
+  int32_t n_planes, ref_stride;
+  int32_t pic_w, pic_h, max_cu_w, max_cu_h;                 /* clipMv */
+  int32_t bit_depth, clp_min, clp_max;
+  int32_t n_ref[2];                                         /* slice.getNumRefIdx(list): 1..4, list 1 also 0 (P slice) */
+  int32_t ref_plane[2][VVCGPU_UNIPRED_ME_MAX_REFS];         /* index into ref_planes of (list, reference index) */
+  int32_t search_range[2][VVCGPU_UNIPRED_ME_MAX_REFS];      /* m_aaiAdaptSR[list][ref]: 1..256 */
+  int32_t list1_to_list0[VVCGPU_UNIPRED_ME_MAX_REFS];       /* slice.getList1IdxToList0Idx(ref): -1 or a list-0 reference index */
+  int32_t fast_me_gen_b_low_delay;  /* getFastMEForGenBLowDelayEnabled() */
+  int32_t mvd_l1_zero;              /* slice.getMvdL1ZeroFlag() */
+  int32_t first_search_stop;        /* getFastMEAssumingSmootherMVEnabled() */
+  int32_t use_hadamard;             /* getUseHADME() (no lossless CUs) */
+  uint32_t mvp_idx_cost[3];         /* m_auiMVPIdxCost[0..2][AMVP_MAX_NUM_CANDS] */
+  int32_t max_pu_w, max_pu_h;       /* as in vvcgpu_bipred_me_cfg: no item is wider / higher (0: 128); an item beyond it is skipped */
+  int32_t reserved[2];
+} vvcgpu_unipred_me_cfg;
+typedef struct {                        /* one (list, reference index) of a result            sizeof == 48 */
+  int32_t  mv[2];         /* cMvTemp[list][ref] (quarter units) */
+  int32_t  int_mv[2];     /* the integer vector xTZSearch found: what m_integerMv2Nx2N / the block cache are updated with (zero where the list-1
+                             shortcut took list 0's vector) */
+  int32_t  mvp_idx;       /* aaiMvpIdx[list][ref] after xCheckBestMVP */
+  uint32_t bits;          /* uiBitsTemp after xCheckBestMVP */
+  uint64_t cost;          /* uiCostTemp after xCheckBestMVP */
+  uint64_t tmpl_cost[2];  /* xGetTemplateCost of candidate 0..1 (0 beyond num_cand) */
+} vvcgpu_unipred_me_search;
+typedef struct {                        /* one PU                                             sizeof == 472 */
+  vvcgpu_unipred_me_search s[2][VVCGPU_UNIPRED_ME_MAX_REFS];   /* entries beyond cfg.n_ref[list] are zero */
+  int32_t  ref_idx[2];    /* iRefIdx[0..1] */
+  int32_t  mv[2][2];      /* cMv[0..1] */
+  uint64_t cost[2];       /* uiCost[0..1]; both ~0 with everything else zero: item skipped.  cost[1] = ~0 on a P slice */
+  uint32_t bits[2];       /* uiBits[0..1] (0 for a list without references) */
+  int32_t  best_bip_ref_idx_l1, best_bip_mvp_l1;   /* bestBiPRefIdxL1, bestBiPMvpL1 (0 unless mvd_l1_zero) */
+  uint64_t best_bip_dist; /* bestBiPDist (~0 unless mvd_l1_zero set it) */
+  int32_t  valid_l1_ref_idx;   /* refIdxValidList1 */
+  int32_t  valid_l1_mv[2];     /* mvValidList1 */
+  uint32_t valid_l1_bits;      /* bitsValidList1 (0xFFFFFFFF: no valid list-1 reference) */
+  uint64_t valid_l1_cost;      /* costValidList1 (~0: no valid list-1 reference) */
+} vvcgpu_unipred_me_result;
+int vvcgpu_unipred_me_batch(const vvc_pel* org_base, const vvcgpu_unipred_me_item* items, int n, const vvcgpu_unipred_me_cfg* cfg_host,
+                            vvcgpu_unipred_me_result* results, vvcgpu_bipred_me_item* bipred_items_out, void* stream);
 
 /* ---- N2 ("next" row): integer-sample TZ search of whole PUs, on the device  (InterSearch::xTZSearch,
  *          EncoderLib/InterSearch.cpp:1971-2252, with xTZSearchHelp :249-343, xTZ2PointSearch :349-374,

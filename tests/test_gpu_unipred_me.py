@@ -1,0 +1,212 @@
+"""vvcgpu_unipred_me_batch on the device: the uni-predictive stage of InterSearch::predInterSearch (InterSearch.cpp:877-964) for lists of PUs, against the
+compiled reference's results (tests/golden/unipred_me.npz) and the tests' restatement (tests/unipred_me_cases.py, pinned to the reference by
+tests/test_unipred_me_cpu.py), and handed on to vvcgpu_bipred_me_batch from device memory."""
+import functools
+import os
+import threading
+
+import numpy as np
+import pytest
+import torch
+
+import bipred_me_cases as bc
+import unipred_me_cases as uc
+from vvcsoftware_vtm_amd import abi
+
+pytestmark = pytest.mark.gpu
+G = os.path.join(os.path.dirname(__file__), "golden")
+W, H = 256, 128
+PAIRS = uc.all_shapes()
+
+
+def dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def device_cfg(cfg, planes_dev, max_pu=None):
+    from vvcsoftware_vtm_amd import ops
+    m = uc.MARGIN
+    return ops.unipred_me_cfg(cfg["lambda_"], [planes_dev[i] for i in range(planes_dev.shape[0])], (m, m), cfg["pic_w"], cfg["pic_h"], cfg["n_ref"],
+                              cfg["ref_plane"], cfg["search_range"], cfg["bit_depth"], (cfg["clp_min"], cfg["clp_max"]), cfg["list1_to_list0"],
+                              cfg["fast_me_gen_b_low_delay"], cfg["mvd_l1_zero"], cfg["first_search_stop"], cfg["use_hadamard"], cfg["mvp_idx_cost"],
+                              cfg["max_cu"], cfg["max_pu"] if max_pu is None else max_pu)
+
+
+def run(org, planes, cfg, items, want_items=True, max_pu=None):
+    from vvcsoftware_vtm_amd import ops
+    d_planes = dev(planes)
+    res, out = ops.unipred_me_batch(dev(org), ops.struct_to_device(items), len(items), device_cfg(cfg, d_planes, max_pu), want_items)
+    torch.cuda.synchronize()
+    return res.cpu().numpy().view(abi.UNIPRED_ME_RESULT), (out.cpu().numpy().view(abi.BIPRED_ME_ITEM) if want_items else None)
+
+
+def same(got, want, items, what):
+    for i in range(len(want)):
+        assert got[i].tobytes() == want[i].tobytes(), (what, i, int(items[i]["w"]), int(items[i]["h"]), got[i], want[i])
+
+
+KW = {1: dict(n_ref=(1, 1), search_range=8),
+      2: dict(n_ref=(4, 2), use_hadamard=0, fast=True, list1_to_list0=(0, -1, -1, -1), fast_me_gen_b_low_delay=1, far=300),
+      63: dict(n_ref=(2, 2), mvd_l1_zero=1),
+      64: dict(n_ref=(2, 1), fast=True, first_search_stop=1, search_range=((8, 32, 8, 8), (32, 8, 8, 8))),
+      65: dict(n_ref=(1, 2), list1_to_list0=(0, 0, -1, -1), fast_me_gen_b_low_delay=1, mvd_l1_zero=1, search_range=8),
+      300: dict(n_ref=(2, 2), list1_to_list0=(-1, 1, -1, -1), fast_me_gen_b_low_delay=1)}
+
+
+@functools.lru_cache(maxsize=None)
+def fresh(n, search_range=None):
+    """seeded inputs and the restatement's answer, computed once"""
+    kw = dict(KW[n])
+    if search_range is not None:
+        kw["search_range"] = search_range
+    rng = np.random.default_rng(n)
+    shapes = uc.alternating_shapes(n, rng) if n == 300 else [PAIRS[int(i)] for i in rng.permutation(len(PAIRS))[:min(n, len(PAIRS))]] + \
+        [(16, 16), (8, 8), (32, 32), (64, 64), (4, 8), (16, 4), (64, 16), (8, 32)] * ((max(0, n - len(PAIRS)) + 7) // 8)
+    org, planes, cfg, items = uc.fresh_set(900 + n, 8 if n in (2, 65) else 10, shapes[:n], **kw)
+    facts = set()
+    res, out = uc.search_all(org, planes, cfg, items, facts)
+    return org, planes, cfg, items, res, out, facts
+
+
+@pytest.mark.parametrize("bd", [10, 8])
+def test_results_and_out_items_equal_the_reference_golden(bd):
+    g = np.load(os.path.join(G, "unipred_me.npz"))
+    k = "bd%d_" % bd
+    planes = uc.pad(g[k + "planes"])
+    items, want, want_out = g[k + "items"], g[k + "want"], g[k + "out"]
+    for cfg, idx in uc.golden_groups(g, bd):
+        res, out = run(g[k + "org"], planes, cfg, items[idx])
+        same(res, want[idx], items[idx], "result")
+        same(out, want_out[idx], items[idx], "out-item")
+
+
+@pytest.mark.parametrize("n", [1, 2, 63, 64, 65, 300])
+def test_results_and_out_items_equal_the_restatement(n):
+    for sr in ((32, 8) if n == 300 else (None,)):
+        org, planes, cfg, items, want, want_out, facts = fresh(n, sr)
+        if n == 300:
+            px = items["w"].astype(int) * items["h"]
+            assert set(zip(items["w"].tolist(), items["h"].tolist())) == set(PAIRS)
+            assert ((px[0::2] <= uc.WAVE_MAX).all() and (px[1::2] > uc.WAVE_MAX).all())         # the two owner kinds alternate
+            assert {"shortcut", "searched_l1", "mvp_switch", "no_raster"} <= facts and (sr != 32 or "raster" in facts), facts
+        res, out = run(org, planes, cfg, items)
+        same(res, want, items, "result")
+        same(out, want_out, items, "out-item")
+
+
+@pytest.mark.parametrize("mvd_l1_zero", [0, 1])
+def test_out_items_go_straight_into_the_bipredictive_entry(mvd_l1_zero):
+    """vvcgpu_unipred_me_batch, then vvcgpu_bipred_me_batch on the same stream with the first call's out-items as they lie in device memory: the outcome
+    is that of the bi-predictive restatement on the uni-predictive restatement's items"""
+    from vvcsoftware_vtm_amd import ops
+    shapes = [(16, 16), (8, 8), (32, 16), (64, 64), (4, 8), (128, 32), (8, 4), (32, 32), (16, 64), (64, 128), (128, 128), (4, 4)]
+    org, planes, cfg, items = uc.fresh_set(77 + mvd_l1_zero, 10, shapes, n_ref=(2, 2), mvd_l1_zero=mvd_l1_zero, search_range=16)
+    want, want_items = uc.search_all(org, planes, cfg, items)
+    bcfg = bc.cfg_dict(cfg["lambda_"], W, H, 10, mvd_l1_zero=mvd_l1_zero, mvp_idx_cost=cfg["mvp_idx_cost"])
+    want_bi, want_trace = bc.search_all(org, planes, bcfg, want_items)
+    assert (want_bi["cost"] != np.uint64(bc.U64_MAX)).all() and (want_bi["me_calls"] >= 2).all()
+    d_org, d_planes, m = dev(org), dev(planes), uc.MARGIN
+    dbcfg = ops.bipred_me_cfg(bcfg["lambda_"], [d_planes[i] for i in range(d_planes.shape[0])], (m, m), W, H, 10, (0, 1023), bcfg["num_iter"], bcfg["pick_list_by_cost"],
+                              mvd_l1_zero, bcfg["search_range"], bcfg["clip_key"], bcfg["use_hadamard"], bcfg["mvp_idx_cost"], bcfg["max_cu"])
+    s = torch.cuda.Stream()
+    with torch.cuda.stream(s):
+        res, out = ops.unipred_me_batch(d_org, ops.struct_to_device(items), len(items), device_cfg(cfg, d_planes))
+        bi, trace = ops.bipred_me_batch(d_org, out, len(items), dbcfg)
+    s.synchronize()
+    same(res.cpu().numpy().view(abi.UNIPRED_ME_RESULT), want, items, "result")
+    same(bi.cpu().numpy().view(abi.BIPRED_ME_RESULT), want_bi, items, "bi-predictive result")
+    assert np.array_equal(trace.cpu().numpy().view(abi.BIPRED_ME_STEP).reshape(len(items), -1), want_trace)
+
+
+def test_null_out_items_give_the_same_results():
+    org, planes, cfg, items, want, _, _ = fresh(63)
+    res, out = run(org, planes, cfg, items, want_items=False)
+    assert out is None
+    same(res, want, items, "result")
+
+
+def test_p_slice_leaves_list_1_untouched():
+    org, planes, cfg, items = uc.fresh_set(5, 10, PAIRS[::3], n_ref=(2, 0), search_range=8)
+    want, want_out = uc.search_all(org, planes, cfg, items)
+    for want_items in (True, False):
+        res, out = run(org, planes, cfg, items, want_items=want_items)
+        same(res, want, items, "result")
+        assert (res["cost"][:, 1] == np.uint64(uc.U64_MAX)).all() and (res["cost"][:, 0] != np.uint64(uc.U64_MAX)).all()
+        assert res["s"][:, 1].tobytes() == bytes(res["s"][:, 1].nbytes) and (res["valid_l1_cost"] == np.uint64(uc.U64_MAX)).all()
+        if want_items:
+            same(out, want_out, items, "out-item")
+            assert (out["n_ref"][:, 1] == 0).all()
+
+
+def test_max_pu_hint_gives_the_same_results_and_skips_what_exceeds_it():
+    org, planes, cfg, items, want, want_out, _ = fresh(64)
+    res, out = run(org, planes, cfg, items, max_pu=(32, 16))
+    big = (items["w"] > 32) | (items["h"] > 16)
+    assert big.any() and (~big).any()
+    assert (res[big]["cost"] == np.uint64(uc.U64_MAX)).all() and out[big].tobytes() == bytes(out[big].nbytes)
+    assert np.array_equal(res[~big], want[~big]) and np.array_equal(out[~big], want_out[~big])
+
+
+def test_items_outside_the_contract_get_the_sentinel():
+    org, planes, cfg, items, want, want_out, _ = fresh(63)
+    items = items[:12].copy()
+    items[1]["w"] = 12                           # no served side
+    items[2]["h"] = 256                          # above 128
+    items[3]["tz_flags"] = abi.TZ_FAST           # the fast settings belong to the cached-start path
+    items[4]["sub_shift"] = 2
+    items[5]["ref"][0][1]["flags"] = 4
+    items[6]["ref"][1][0]["num_cand"] = 3
+    items[7]["ref"][0][0]["num_cand"] = 0
+    items[8]["pos_x"] = W - int(items[8]["w"]) + 4   # not inside the picture
+    items[9]["org_stride"] = 0
+    items[10]["pos_y"] = -4
+    res, out = run(org, planes, cfg, items)
+    for i in (0, 11):
+        assert res[i].tobytes() == want[i].tobytes() and out[i].tobytes() == want_out[i].tobytes(), i
+    zero = np.zeros(1, abi.UNIPRED_ME_RESULT)
+    zero["cost"] = np.uint64(uc.U64_MAX)
+    for i in range(1, 11):
+        assert res[i].tobytes() == zero[0].tobytes(), (i, res[i])
+        assert out[i].tobytes() == bytes(out[i].nbytes), i
+
+
+def test_two_streams_from_two_host_threads():
+    from vvcsoftware_vtm_amd import ops
+    org, planes, cfg, items, want, want_out, _ = fresh(63)
+    d_org, d_planes, d_items = dev(org), dev(planes), ops.struct_to_device(items)
+    dcfg = device_cfg(cfg, d_planes)
+    torch.cuda.synchronize()
+    got, errs = [None, None], []
+
+    def work(k):
+        try:
+            s = torch.cuda.Stream()
+            with torch.cuda.stream(s):
+                for _ in range(3):
+                    res, out = ops.unipred_me_batch(d_org, d_items, len(items), dcfg)
+                s.synchronize()
+            got[k] = (res.cpu().numpy().view(abi.UNIPRED_ME_RESULT), out.cpu().numpy().view(abi.BIPRED_ME_ITEM))
+        except Exception as e:                    # noqa: BLE001
+            errs.append(e)
+    ts = [threading.Thread(target=work, args=(k,)) for k in range(2)]
+    for t in ts:
+        t.start()
+    for t in ts:
+        t.join()
+    assert not errs, errs
+    for k in range(2):
+        assert np.array_equal(got[k][0], want) and np.array_equal(got[k][1], want_out), k
+
+
+def test_entry_ends_where_the_chain_of_the_existing_entries_ends():
+    """a consistency supplement, not evidence: vvcgpu_mc_dist_batch -> host -> vvcgpu_me_batch per (shape, list, reference) -> host
+    (tests/unipred_me_chain.py) ends where the entry ends"""
+    import unipred_me_chain
+    shapes = [(16, 16), (8, 8), (32, 16), (64, 64), (16, 16), (4, 8), (128, 32), (16, 16), (8, 8), (32, 32), (16, 64)]
+    org, planes, cfg, items = uc.fresh_set(41, 10, shapes, n_ref=(2, 2), list1_to_list0=(-1, 0, -1, -1), fast_me_gen_b_low_delay=1, mvd_l1_zero=1, fast=True,
+                                           search_range=((32, 8, 8, 8), (32, 8, 8, 8)))
+    res, _ = run(org, planes, cfg, items)
+    got, calls = unipred_me_chain.chained(dev(org), dev(planes), cfg, items, uc.MARGIN)
+    assert calls > 3 * len(set(shapes))
+    for f in res.dtype.names:
+        assert np.array_equal(got[f], res[f]), (f, got[f], res[f])

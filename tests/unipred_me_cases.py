@@ -1,0 +1,308 @@
+"""The uni-predictive loop of InterSearch::predInterSearch (InterSearch.cpp:877-964) restated for the tests of vvcgpu_unipred_me_batch: the pixel
+steps go through the CPU restatement -- xGetTemplateCost (:1606-1642) = orc_mc_batch + orc_dist_batch (SAD), xTZSearch = orc_tz_search,
+xPatternSearchFracDIF = orc_frac_refine, vector bits = orc_expgolomb_bits -- and xEstimateMvPredAMVP's choice (:1443-1483), the two paths of
+xMotionEstimation(bBi = false) (:1668-1816), the cost in IEEE doubles (:1805), xCheckBestMVP (:1537-1603, bipred_me_cases), the list-1 shortcut
+(:905-922), the bookkeeping of :896-901 / :944-962 and the out-item for vvcgpu_bipred_me_batch (:1009-1023, :1038) are written here from the
+reference's text.  Also the builders of the test inputs that the tests and tools/unipred_me_time.py share.  numpy only."""
+import ctypes
+import math
+
+import numpy as np
+
+import bipred_me_cases as bc
+from bipred_me_cases import MARGIN, SIDES, U64_MAX, clip_mv, pad, ref_bits, sub_shift_of, texture  # noqa: F401  (re-exported)
+from oraclelib import oracle, p
+from vvcsoftware_vtm_amd import abi
+
+MAX_REFS = abi.UNIPRED_ME_MAX_REFS
+U32_MAX = 0xFFFFFFFF
+WAVE_MAX = 1024             # samples a wavefront owns (unipredme.hip)
+CLAMP = 14                  # TZ probes are clamped to max_cu + CLAMP samples around the picture (include/vvcgpu.h)
+
+
+def cfg_dict(lambda_, pic_w, pic_h, bit_depth, n_ref=(2, 2), ref_plane=((0, 1, 2, 3), (1, 0, 3, 2)), search_range=32, list1_to_list0=(-1, -1, -1, -1),
+             fast_me_gen_b_low_delay=0, mvd_l1_zero=0, first_search_stop=0, use_hadamard=1, mvp_idx_cost=(1, 1, 0), max_cu=128, max_pu=(0, 0)):
+    """the host cfg as plain values (the device tests turn it into ops.unipred_me_cfg with the planes' addresses); search_range: one value or [2][4]"""
+    if isinstance(search_range, int):
+        search_range = ((search_range,) * MAX_REFS,) * 2
+    return dict(lambda_=float(lambda_), pic_w=pic_w, pic_h=pic_h, max_cu=max_cu, bit_depth=bit_depth, clp_min=0, clp_max=(1 << bit_depth) - 1,
+                n_ref=tuple(n_ref), ref_plane=tuple(tuple(v) for v in ref_plane), search_range=tuple(tuple(v) for v in search_range),
+                list1_to_list0=tuple(list1_to_list0), fast_me_gen_b_low_delay=int(fast_me_gen_b_low_delay), mvd_l1_zero=int(mvd_l1_zero),
+                first_search_stop=int(first_search_stop), use_hadamard=int(use_hadamard), mvp_idx_cost=tuple(mvp_idx_cost), max_pu=tuple(max_pu))
+
+
+def shortcut(c, lst, r):
+    return lst == 1 and c["fast_me_gen_b_low_delay"] and c["list1_to_list0"][r] >= 0
+
+
+def item_ok(it, c):
+    w, h = int(it["w"]), int(it["h"])
+    mw, mh = (c["max_pu"][0] or 128), (c["max_pu"][1] or 128)
+    if w not in SIDES or h not in SIDES or w > c["max_cu"] or h > c["max_cu"] or w > mw or h > mh:
+        return False
+    if not (0 <= int(it["pos_x"]) <= c["pic_w"] - w and 0 <= int(it["pos_y"]) <= c["pic_h"] - h):
+        return False
+    if int(it["sub_shift"]) not in (0, 1) or (h >> int(it["sub_shift"])) == 0 or int(it["org_stride"]) <= 0:
+        return False
+    if int(it["tz_flags"]) & ~abi.TZ_EXTENDED:
+        return False
+    for l in range(2):
+        for r in range(c["n_ref"][l]):
+            a = it["ref"][l][r]
+            if not 1 <= int(a["num_cand"]) <= 2 or not 0 <= int(a["flags"]) <= 3:
+                return False
+    return True
+
+
+class Searcher:
+    """one (org plane, padded reference planes [n][H + 2 M][W + 2 M], cfg): search(item) -> (result record, out-item record)"""
+
+    def __init__(self, org, planes_pad, cfg, margin=MARGIN):
+        self.org, self.planes, self.c, self.m = np.ascontiguousarray(org), np.ascontiguousarray(planes_pad), cfg, margin
+        self.rs = self.planes.shape[2]
+        self.o = oracle()
+        self.o.orc_expgolomb_bits.restype = ctypes.c_uint32
+        self.b = bc.Searcher(org, planes_pad, dict(cfg, search_range=4, clip_key=1, num_iter=4, pick_list_by_cost=0), margin)    # mv_bits, get_cost, check_best_mvp, predict
+
+    def template_cost(self, it, plane, cand, idx):
+        """xGetTemplateCost: clipMv, xPredInterBlk, full SAD, + getCost(m_auiMVPIdxCost[idx][AMVP_MAX_NUM_CANDS])"""
+        w, h = int(it["w"]), int(it["h"])
+        pred = self.b.predict(it, plane, cand)
+        d = np.zeros(1, abi.DIST_DESC)
+        d[0]["org_off"], d[0]["org_stride"], d[0]["cur_stride"], d[0]["w"], d[0]["h"] = int(it["org_off"]), int(it["org_stride"]), w, w, h
+        out = np.zeros(1, np.uint64)
+        self.o.orc_dist_batch(0, p(self.org), p(pred), p(d), 1, p(out))
+        return int(out[0]) + self.b.get_cost(self.c["mvp_idx_cost"][idx])
+
+    def motion_estimation(self, it, lst, r, pred, bits, facts):
+        """xMotionEstimation(bBi = false) -> (integer vector, vector, bits, cost)"""
+        c, w, h, px, py, m = self.c, int(it["w"]), int(it["h"]), int(it["pos_x"]), int(it["pos_y"]), self.m
+        a = it["ref"][lst][r]
+        plane = self.planes[c["ref_plane"][lst][r]]
+        oy, ox = divmod(int(it["org_off"]), int(it["org_stride"]))
+        cached = bool(int(a["flags"]) & abi.UNIPRED_CACHED)
+        pu = np.zeros(1, abi.TZ_PU)
+        pu[0]["org_x"], pu[0]["org_y"], pu[0]["ref_x"], pu[0]["ref_y"] = ox, oy, m + px, m + py
+        if cached:                                               # :1759-1766: the cached vector, fast settings, no 2Nx2N predictor
+            pu[0]["start_x"], pu[0]["start_y"], pu[0]["flags"] = int(a["cached_mv"][0]) << 2, int(a["cached_mv"][1]) << 2, abi.TZ_FAST
+        else:                                                    # :1767-1786
+            pu[0]["start_x"], pu[0]["start_y"] = pred
+            pu[0]["flags"] = (int(it["tz_flags"]) & abi.TZ_EXTENDED) | (abi.TZ_PRED2 if int(a["flags"]) & abi.UNIPRED_PRED2 else 0)
+        pu[0]["pred2_x"], pu[0]["pred2_y"] = a["pred2"]
+        pu[0]["pos_x"], pu[0]["pos_y"], pu[0]["pred_hor"], pu[0]["pred_ver"] = px, py, pred[0], pred[1]
+        pu[0]["w"], pu[0]["h"], pu[0]["sub_shift"] = w, h, int(it["sub_shift"])
+        tc = np.zeros(1, abi.TZ_CFG)
+        tc[0]["lambda"], tc[0]["cost_scale"], tc[0]["search_range"], tc[0]["first_search_stop"] = c["lambda_"], 2, c["search_range"][lst][r], c["first_search_stop"]
+        tc[0]["pic_w"], tc[0]["pic_h"], tc[0]["max_cu_w"], tc[0]["max_cu_h"] = c["pic_w"], c["pic_h"], c["max_cu"], c["max_cu"]
+        e = c["max_cu"] + CLAMP
+        tc[0]["ref_x0"], tc[0]["ref_y0"], tc[0]["ref_x1"], tc[0]["ref_y1"] = m - e, m - e, m + c["pic_w"] + e, m + c["pic_h"] + e
+        best = np.zeros(1, abi.SEARCH_BEST)
+        self.o.orc_tz_search(p(self.org), int(it["org_stride"]), p(plane), self.rs, p(pu), 1, p(tc), p(best))
+        if facts is not None:
+            st = np.zeros(3, np.uint64)
+            self.o.orc_tz_stats(p(st))
+            facts.add("raster" if int(st[2]) else "no_raster")
+        ix, iy = int(best[0]["x"]), int(best[0]["y"])
+        fb = np.array([(ox, oy, m + px + ix, m + py + iy, ix, iy)], dtype=abi.FRAC_BLK)
+        fr = np.zeros(1, abi.FRAC_RESULT)
+        mc0 = abi.MvCost(c["lambda_"], int(pred[0]), int(pred[1]), 0, 0)
+        self.o.orc_frac_refine(p(self.org), int(it["org_stride"]), p(plane), self.rs, p(fb), 1, w, h, c["bit_depth"], c["clp_min"], c["clp_max"], c["use_hadamard"],
+                               ctypes.byref(mc0), p(fr))
+        mv = [(ix << 2) + (int(fr[0]["half_x"]) << 1) + int(fr[0]["qter_x"]), (iy << 2) + (int(fr[0]["half_y"]) << 1) + int(fr[0]["qter_y"])]
+        mv_bits = self.b.mv_bits(pred, 0, mv[0], mv[1])
+        bits = (bits + mv_bits) & U32_MAX
+        cost = int(math.floor(1.0 * (float(int(fr[0]["cost"])) - float(self.b.get_cost(mv_bits)))) + float(self.b.get_cost(bits)))
+        return [ix, iy], mv, bits, cost
+
+    def search(self, it, facts=None):
+        """facts (a set): receives "raster", "no_raster", "mvp_switch", "shortcut", "searched_l1", "best_ref_nonzero", "bip_ref_nonzero", "clip_binds" """
+        c = self.c
+        res, out = np.zeros(1, abi.UNIPRED_ME_RESULT), np.zeros(1, abi.BIPRED_ME_ITEM)
+        if not item_ok(it, c):
+            res[0]["cost"] = U64_MAX
+            return res[0], out[0]
+        n_ref, mic, mb = c["n_ref"], c["mvp_idx_cost"], [int(v) for v in it["mb_bits"]]
+        ui_cost, ui_bits, ref_idx, c_mv = [U64_MAX, U64_MAX], [0, 0], [0, 0], [[0, 0], [0, 0]]
+        cost_l0, bits_l0 = [0] * MAX_REFS, [0] * MAX_REFS
+        best_bip_dist, best_bip_mvp, best_bip_ref = U64_MAX, 0, 0
+        cost_valid, bits_valid, mv_valid, ref_valid = U64_MAX, U32_MAX, [0, 0], 0
+        mv_temp = [[[0, 0] for _ in range(MAX_REFS)] for _ in range(2)]
+        mvp_idx = [[0] * MAX_REFS for _ in range(2)]
+        for lst in range(2):
+            for r in range(n_ref[lst]):
+                a = it["ref"][lst][r]
+                cand = [[int(v) for v in a["mv_cand"][k]] for k in range(2)]
+                bits = mb[lst] + ref_bits(n_ref[lst], r)
+                # xEstimateMvPredAMVP, bFilled
+                best_cost, idx, tmpl = U64_MAX, 0, [0, 0]
+                for i in range(int(a["num_cand"])):
+                    tmpl[i] = self.template_cost(it, c["ref_plane"][lst][r], cand[i], i)
+                    if facts is not None and (clip_mv(cand[i][0], int(it["pos_x"]), c["pic_w"], c["max_cu"]) != cand[i][0] or
+                                              clip_mv(cand[i][1], int(it["pos_y"]), c["pic_h"], c["max_cu"]) != cand[i][1]):
+                        facts.add("clip_binds")
+                    if best_cost > tmpl[i]:
+                        best_cost, idx = tmpl[i], i
+                pred, bip_dist = cand[idx], best_cost
+                if c["mvd_l1_zero"] and lst == 1 and bip_dist < best_bip_dist:
+                    best_bip_dist, best_bip_mvp, best_bip_ref = bip_dist, idx, r
+                bits += mic[idx]
+                imv = [0, 0]
+                if shortcut(c, lst, r):
+                    k = c["list1_to_list0"][r]
+                    mv = list(mv_temp[0][k])
+                    cost = (cost_l0[k] - self.b.get_cost(bits_l0[k])) & U64_MAX
+                    bits = (bits + self.b.mv_bits(pred, 0, mv[0], mv[1])) & U32_MAX
+                    cost = (cost + self.b.get_cost(bits)) & U64_MAX
+                    if facts is not None:
+                        facts.add("shortcut")
+                else:
+                    imv, mv, bits, cost = self.motion_estimation(it, lst, r, pred, bits, facts)
+                    if facts is not None and lst == 1:
+                        facts.add("searched_l1")
+                mv_temp[lst][r] = mv
+                before = idx
+                pred, idx, bits, cost = self.b.check_best_mvp(dict(mv_cand=cand, num_cand=int(a["num_cand"])), mv, pred, idx, bits, cost)
+                if facts is not None and idx != before:
+                    facts.add("mvp_switch")
+                mvp_idx[lst][r] = idx
+                res[0]["s"][lst][r] = (mv, imv, idx, bits, cost, tmpl)
+                if lst == 0:
+                    cost_l0[r], bits_l0[r] = cost, bits
+                if cost < ui_cost[lst]:
+                    ui_cost[lst], ui_bits[lst], c_mv[lst], ref_idx[lst] = cost, bits, list(mv), r
+                if lst == 1 and cost < cost_valid and c["list1_to_list0"][r] < 0:
+                    cost_valid, bits_valid, mv_valid, ref_valid = cost, bits, list(mv), r
+        if facts is not None:
+            if max(ref_idx) > 0:
+                facts.add("best_ref_nonzero")
+            if c["mvd_l1_zero"] and best_bip_ref > 0:
+                facts.add("bip_ref_nonzero")
+        res[0]["ref_idx"], res[0]["mv"], res[0]["cost"], res[0]["bits"] = ref_idx, c_mv, ui_cost, ui_bits
+        res[0]["best_bip_ref_idx_l1"], res[0]["best_bip_mvp_l1"], res[0]["best_bip_dist"] = best_bip_ref, best_bip_mvp, best_bip_dist
+        res[0]["valid_l1_ref_idx"], res[0]["valid_l1_mv"], res[0]["valid_l1_bits"], res[0]["valid_l1_cost"] = ref_valid, mv_valid, bits_valid, cost_valid
+        # what vvcgpu_bipred_me_batch asks of its caller
+        o = out[0]
+        for f in ("pos_x", "pos_y", "w", "h", "sub_shift", "org_off", "org_stride", "mb_bits"):
+            o[f] = it[f]
+        o["n_ref"], o["ref_idx"], o["mv"], o["cost"], o["bits"] = n_ref, ref_idx, c_mv, ui_cost, ui_bits
+        for lst in range(2):
+            for r in range(n_ref[lst]):
+                a, q = it["ref"][lst][r], o["ref"][lst][r]
+                q["plane"], q["mv"], q["mv_cand"], q["num_cand"], q["mvp_idx"] = c["ref_plane"][lst][r], mv_temp[lst][r], a["mv_cand"], a["num_cand"], mvp_idx[lst][r]
+        if c["mvd_l1_zero"] and n_ref[1] > 0:                     # :1009-1023, :1038
+            q = o["ref"][1][best_bip_ref]
+            q["mvp_idx"] = best_bip_mvp
+            q["mv"] = q["mv_cand"][best_bip_mvp]
+            o["mv"][1], o["ref_idx"][1] = q["mv"], best_bip_ref
+        return res[0], out[0]
+
+
+def search_all(org, planes_pad, cfg, items, facts=None):
+    s = Searcher(org, planes_pad, cfg)
+    res, out = np.zeros(len(items), abi.UNIPRED_ME_RESULT), np.zeros(len(items), abi.BIPRED_ME_ITEM)
+    for i, it in enumerate(items):
+        res[i], out[i] = s.search(it, facts)
+    return res, out
+
+
+# ---- inputs ------------------------------------------------------------------------------------------------------------------------------------
+def item(px, py, w, h, sub_shift, org_off, org_stride, refs, tz_flags=0, mb_bits=(2, 2, 4)):
+    """refs = ([records of list 0], [records of list 1]), each (candidates, flags, pred2, cached_mv)"""
+    it = np.zeros(1, abi.UNIPRED_ME_ITEM)
+    it[0]["pos_x"], it[0]["pos_y"], it[0]["w"], it[0]["h"], it[0]["sub_shift"], it[0]["tz_flags"] = px, py, w, h, sub_shift, tz_flags
+    it[0]["org_off"], it[0]["org_stride"], it[0]["mb_bits"] = org_off, org_stride, mb_bits
+    for l in range(2):
+        for r, (cands, flags, pred2, cached) in enumerate(refs[l][:MAX_REFS]):
+            a = it[0]["ref"][l][r]
+            cands = [list(v) for v in cands]
+            a["mv_cand"], a["num_cand"], a["flags"], a["pred2"], a["cached_mv"] = (cands + cands)[:2], len(cands), flags, pred2, cached
+    return it[0]
+
+
+def fresh_set(seed, bd, shapes, pic=(256, 128), n_planes=4, fast=False, far=0, flat=False, ext=None, corners=False, **cfgkw):
+    """seeded inputs: -> (org plane, padded planes, cfg dict, items); one PU per entry of `shapes` = (w, h).  The planes are shifted copies of one
+    texture, the original is one of them displaced plus noise, so the searches move.  Per (list, reference) one or two candidates around the PU's
+    true motion (far: displaced by multiples of it, so that clipMv binds at the picture's corners), the 2Nx2N predictor and the cached start vector
+    on a seeded subset.  ext: the extended settings for every item (None: seeded per item); corners: the PUs sit in the picture's corners"""
+    rng = np.random.default_rng(seed)
+    W, H = pic
+    planes = np.stack([texture(rng, H, W, bd, 1.5 * k) for k in range(n_planes)])
+    if flat:
+        org = np.full((H, W), 1 << (bd - 1), np.int16)
+    else:
+        sh = np.roll(planes[0], (3, -5), axis=(0, 1)).astype(np.int32)
+        org = np.clip(sh + rng.integers(-6, 7, (H, W)), 0, (1 << bd) - 1).astype(np.int16)
+    cfg = cfg_dict(4.0 + (seed % 5) * 9.25, W, H, bd, **cfgkw)
+    items = np.zeros(len(shapes), abi.UNIPRED_ME_ITEM)
+    for i, (w, h) in enumerate(shapes):
+        if corners:
+            px, py = (0, W - w)[i & 1], (0, H - h)[(i >> 1) & 1]
+        else:
+            px, py = int(rng.integers(0, (W - w) // 4 + 1)) * 4, int(rng.integers(0, (H - h) // 4 + 1)) * 4
+        refs = []
+        for l in range(2):
+            recs = []
+            for _ in range(MAX_REFS):
+                base = np.array([20, -12]) + rng.integers(-24, 25, 2) + far * rng.integers(-1, 2, 2)
+                cands = [list(base + rng.integers(-9, 10, 2)) for _ in range(int(rng.integers(1, 3)))]
+                flags = int(rng.choice([0, 0, abi.UNIPRED_PRED2, abi.UNIPRED_CACHED]))
+                recs.append((cands, flags, list(rng.integers(-12, 13, 2)), list(rng.integers(-10, 11, 2))))
+            refs.append(recs)
+        e = int(rng.integers(0, 2)) if ext is None else int(ext)
+        items[i] = item(px, py, w, h, sub_shift_of(w, h, fast), py * W + px, W, refs, abi.TZ_EXTENDED * e, [int(v) for v in rng.integers(1, 6, 3)])
+    return org, pad(planes), cfg, items
+
+
+def all_shapes():
+    return [(w, h) for w in SIDES for h in SIDES]
+
+
+def alternating_shapes(n, rng):
+    """n shapes in which wave-owned (<= WAVE_MAX samples) and workgroup-owned PUs alternate and every side pair occurs (n >= 72)"""
+    small = [s for s in all_shapes() if s[0] * s[1] <= WAVE_MAX]
+    large = [s for s in all_shapes() if s[0] * s[1] > WAVE_MAX]
+    out = []
+    for i in range(n):
+        pool = small if i % 2 == 0 else large
+        out.append(pool[(i // 2) % len(pool)])
+    return out
+
+
+# ---- the golden file ------------------------------------------------------------------------------------------------------------------------------
+GOLDEN_FLAGS = ("fast_me_gen_b_low_delay", "mvd_l1_zero", "first_search_stop", "use_hadamard")
+GOLDEN_NEED = {("shape", w, h) for w in SIDES for h in SIDES} | {("n_ref", 1), ("n_ref", 2), ("n_ref", 4), "p_slice", ("range", 8), ("range", 32), "raster",
+                                                               "no_raster", "flat", "mvp_switch", "shortcut_mixed", "bip_ref_nonzero", "best_ref_nonzero",
+                                                               "clip_binds"} | \
+    {(f, v) for f in ("pred2", "ext", "sub_shift", "hadamard", "first_search_stop") for v in (0, 1)} | {("num_cand", 1), ("num_cand", 2)}
+
+
+def golden_groups(g, bd, pic=(256, 128)):
+    """tests/golden/unipred_me.npz -> [(cfg dict, item indices)] of one bit depth: the items of a group share the slice-level settings"""
+    k = "bd%d_" % bd
+    out = []
+    for gi in range(len(g[k + "g_n_ref"])):
+        cfg = cfg_dict(float(g[k + "lambda"]), pic[0], pic[1], bd, n_ref=[int(v) for v in g[k + "g_n_ref"][gi]], ref_plane=g[k + "g_ref_plane"][gi].tolist(),
+                       search_range=g[k + "g_search_range"][gi].tolist(), list1_to_list0=[int(v) for v in g[k + "g_list1_to_list0"][gi]],
+                       mvp_idx_cost=tuple(int(v) for v in g[k + "mvp_idx_cost"]), **{f: int(v) for f, v in zip(GOLDEN_FLAGS, g[k + "g_flags"][gi])})
+        out.append((cfg, np.nonzero(g[k + "group"] == gi)[0]))
+    return out
+
+
+def golden_facts(org, cfg, it, facts):
+    """what an item of the golden set covers, beyond the facts its search reported"""
+    w, h, px, py = int(it["w"]), int(it["h"]), int(it["pos_x"]), int(it["pos_y"])
+    out = {("shape", w, h), ("n_ref", cfg["n_ref"][0]), ("ext", 1 if int(it["tz_flags"]) & abi.TZ_EXTENDED else 0), ("sub_shift", int(it["sub_shift"])),
+           ("hadamard", cfg["use_hadamard"]), ("first_search_stop", cfg["first_search_stop"])}
+    out.add(("n_ref", cfg["n_ref"][1]) if cfg["n_ref"][1] else "p_slice")
+    for l in range(2):
+        for r in range(cfg["n_ref"][l]):
+            a = it["ref"][l][r]
+            out.add(("num_cand", int(a["num_cand"])))
+            if not shortcut(cfg, l, r):
+                out |= {("range", cfg["search_range"][l][r]), ("pred2", 1 if int(a["flags"]) & abi.UNIPRED_PRED2 else 0)}
+    if {"shortcut", "searched_l1"} <= facts:
+        out.add("shortcut_mixed")
+    blk = org[py:py + h, px:px + w]
+    if blk.min() == blk.max():
+        out.add("flat")
+    return out

@@ -1,0 +1,184 @@
+"""The uni-predictive stage as a caller had to build it before vvcgpu_unipred_me_batch existed: one vvcgpu_mc_dist_batch for the template costs of every
+candidate -> download, predictor choice on the host -> per (PU shape, list, reference index) one vvcgpu_me_batch (one reference plane and one PU size
+per call) -> download, vector bits, cost, xCheckBestMVP, the list-1 shortcut and keep-if-better on the host.  Used by the consistency test of
+tests/test_gpu_unipred_me.py and by tools/unipred_me_time.py.  Host decisions are vectorised numpy."""
+import time
+
+import numpy as np
+import torch
+
+from vvcsoftware_vtm_amd import abi, ops
+
+U64 = np.uint64
+CLAMP = 14
+
+
+def eg_bits(v):
+    """xGetExpGolombNumberOfBits (RdCost.h:172-184), vectorised"""
+    v = v.astype(np.int64)
+    t = np.where(v <= 0, ((-v) << 1) + 1, v << 1)
+    ln = np.ones_like(t)
+    while (t > 128).any():
+        big = t > 128
+        ln += 14 * big
+        t = np.where(big, t >> 7, t)
+    return ln + 2 * np.floor(np.log2(t)).astype(np.int64)
+
+
+def mv_bits(pred, mv):
+    return eg_bits(mv[:, 0] - pred[:, 0]) + eg_bits(mv[:, 1] - pred[:, 1])
+
+
+class Chain:
+    def __init__(self, org_dev, planes_dev, cfg, items, margin):
+        self.org, self.planes, self.c, self.items, self.m = org_dev, planes_dev, cfg, items, margin
+        self.n = len(items)
+        self.rs = planes_dev.shape[2]
+        self.plane_sz = planes_dev.shape[1] * planes_dev.shape[2]
+        self.searches = [(l, r) for l in range(2) for r in range(cfg["n_ref"][l])]
+        self.launches = 0
+        self.device_s = self.host_s = 0.0
+
+    def get_cost(self, bits):
+        return (self.c["lambda_"] * bits.astype(np.float64)).astype(U64)
+
+    def clip(self, v, pos, pic):
+        return np.minimum((pic + 8 - pos - 1) << 2, np.maximum((-self.c["max_cu"] - 8 - pos + 1) << 2, v))
+
+    def shortcut(self, l, r):
+        return l == 1 and self.c["fast_me_gen_b_low_delay"] and self.c["list1_to_list0"][r] >= 0
+
+    def template_costs(self):
+        """xGetTemplateCost of every candidate of every (item, list, reference): one launch -> [n][searches][2] (second column of single-candidate sets: 0)"""
+        it, c, m, n = self.items, self.c, self.m, self.n
+        px, py = it["pos_x"].astype(np.int64), it["pos_y"].astype(np.int64)
+        d = np.zeros((n, len(self.searches), 2), abi.MC_DESC)
+        for s, (l, r) in enumerate(self.searches):
+            for k in range(2):
+                mx = self.clip(it["ref"]["mv_cand"][:, l, r, k, 0].astype(np.int64), px, c["pic_w"])
+                my = self.clip(it["ref"]["mv_cand"][:, l, r, k, 1].astype(np.int64), py, c["pic_h"])
+                e = d[:, s, k]
+                e["ref0_off"] = c["ref_plane"][l][r] * self.plane_sz + (m + py + (my >> 2)) * self.rs + m + px + (mx >> 2)
+                e["ref0_stride"], e["dst_off"], e["dst_stride"], e["w"], e["h"] = self.rs, it["org_off"], it["org_stride"], it["w"], it["h"]
+                e["frac_x0"], e["frac_y0"], e["is_luma"] = (mx & 3) << 2, (my & 3) << 2, 1
+        t0 = time.perf_counter()
+        out = ops.mc_dist_batch(0, self.planes, self.planes, self.org, ops.struct_to_device(d.reshape(-1)), d.size, c["bit_depth"], (c["clp_min"], c["clp_max"]))
+        sad = out.cpu().numpy().astype(U64).reshape(n, len(self.searches), 2)
+        self.device_s += time.perf_counter() - t0
+        self.launches += 1
+        return sad
+
+    def run(self):
+        """-> UNIPRED_ME_RESULT records"""
+        it, c, m, n = self.items, self.c, self.m, self.n
+        ar = np.arange(n)
+        mic = np.array(c["mvp_idx_cost"], np.int64)
+        sad = self.template_costs()
+        t0 = time.perf_counter()
+        res = np.zeros(n, abi.UNIPRED_ME_RESULT)
+        st = {}
+        for s, (l, r) in enumerate(self.searches):
+            nc = it["ref"]["num_cand"][:, l, r].astype(np.int64)
+            tmpl = sad[:, s] + self.get_cost(mic[:2])[None, :]
+            tmpl[nc < 2, 1] = 0
+            idx = ((nc > 1) & (tmpl[:, 0] > tmpl[:, 1])).astype(np.int64)
+            pred = it["ref"]["mv_cand"][ar, l, r, idx].astype(np.int64)
+            bits = it["mb_bits"][:, l].astype(np.int64) + (r + 1 - (1 if r == c["n_ref"][l] - 1 else 0) if c["n_ref"][l] > 1 else 0) + mic[idx]
+            st[(l, r)] = dict(tmpl=tmpl, amvp=idx.copy(), idx=idx, pred=pred, bits=bits)
+        # one vvcgpu_me_batch per (shape, list, reference): the calls are independent, so they are all issued before the one download
+        self.host_s += time.perf_counter() - t0
+        shape_key = it["w"].astype(np.int64) * 1000 + it["h"]
+        e = c["max_cu"] + CLAMP
+        pending = []
+        oy, ox = np.divmod(it["org_off"].astype(np.int64), it["org_stride"].astype(np.int64))
+        for (l, r) in self.searches:
+            if self.shortcut(l, r):
+                continue
+            a, q = it["ref"][:, l, r], st[(l, r)]
+            cached = (a["flags"] & abi.UNIPRED_CACHED) != 0
+            pu = np.zeros(n, abi.TZ_PU)
+            pu["org_x"], pu["org_y"], pu["ref_x"], pu["ref_y"] = ox, oy, m + it["pos_x"], m + it["pos_y"]
+            pu["start_x"] = np.where(cached, a["cached_mv"][:, 0].astype(np.int64) << 2, q["pred"][:, 0])
+            pu["start_y"] = np.where(cached, a["cached_mv"][:, 1].astype(np.int64) << 2, q["pred"][:, 1])
+            pu["pred2_x"], pu["pred2_y"], pu["pos_x"], pu["pos_y"] = a["pred2"][:, 0], a["pred2"][:, 1], it["pos_x"], it["pos_y"]
+            pu["pred_hor"], pu["pred_ver"], pu["w"], pu["h"], pu["sub_shift"] = q["pred"][:, 0], q["pred"][:, 1], it["w"], it["h"], it["sub_shift"]
+            pu["flags"] = np.where(cached, abi.TZ_FAST, (it["tz_flags"] & abi.TZ_EXTENDED) | np.where(a["flags"] & abi.UNIPRED_PRED2, abi.TZ_PRED2, 0))
+            tc = np.zeros(1, abi.TZ_CFG)
+            tc[0]["lambda"], tc[0]["cost_scale"], tc[0]["search_range"], tc[0]["first_search_stop"] = c["lambda_"], 2, c["search_range"][l][r], c["first_search_stop"]
+            tc[0]["pic_w"], tc[0]["pic_h"], tc[0]["max_cu_w"], tc[0]["max_cu_h"] = c["pic_w"], c["pic_h"], c["max_cu"], c["max_cu"]
+            tc[0]["ref_x0"], tc[0]["ref_y0"], tc[0]["ref_x1"], tc[0]["ref_y1"] = m - e, m - e, m + c["pic_w"] + e, m + c["pic_h"] + e
+            plane = self.planes[c["ref_plane"][l][r]]
+            for key in np.unique(shape_key):
+                sel = np.nonzero(shape_key == key)[0]
+                w, h = int(key) // 1000, int(key) % 1000
+                tc[0]["wg_per_pu"] = 1 if w * h > 1024 else 0
+                d_pu = ops.struct_to_device(pu[sel])
+                t0 = time.perf_counter()
+                best, frac = ops.me_batch(self.org, plane, d_pu, len(sel), w, h, tc, c["bit_depth"], bool(c["use_hadamard"]))
+                self.device_s += time.perf_counter() - t0
+                self.launches += 1
+                pending.append((l, r, sel, best, frac))
+        t0 = time.perf_counter()
+        torch.cuda.synchronize()
+        got = [(l, r, sel, best.cpu().numpy().view(abi.SEARCH_BEST), frac.cpu().numpy().view(abi.FRAC_RESULT)) for l, r, sel, best, frac in pending]
+        self.device_s += time.perf_counter() - t0
+        t0 = time.perf_counter()
+        for (l, r) in self.searches:
+            q = st[(l, r)]
+            q["imv"], q["mv"], q["cost"] = np.zeros((n, 2), np.int64), np.zeros((n, 2), np.int64), np.zeros(n, U64)
+        for l, r, sel, best, frac in got:
+            q = st[(l, r)]
+            q["imv"][sel, 0], q["imv"][sel, 1] = best["x"], best["y"]
+            q["mv"][sel, 0] = (best["x"].astype(np.int64) << 2) + (frac["half_x"].astype(np.int64) << 1) + frac["qter_x"]
+            q["mv"][sel, 1] = (best["y"].astype(np.int64) << 2) + (frac["half_y"].astype(np.int64) << 1) + frac["qter_y"]
+            q["cost"][sel] = frac["cost"]
+        ui_cost, ui_bits = np.full((n, 2), U64(0xFFFFFFFFFFFFFFFF)), np.zeros((n, 2), np.int64)
+        ref_idx, c_mv = np.zeros((n, 2), np.int64), np.zeros((n, 2, 2), np.int64)
+        bip_dist, bip_mvp, bip_ref = np.full(n, U64(0xFFFFFFFFFFFFFFFF)), np.zeros(n, np.int64), np.zeros(n, np.int64)
+        v_cost, v_bits, v_mv, v_ref = np.full(n, U64(0xFFFFFFFFFFFFFFFF)), np.full(n, 0xFFFFFFFF, np.int64), np.zeros((n, 2), np.int64), np.zeros(n, np.int64)
+        for (l, r) in self.searches:
+            q = st[(l, r)]
+            if c["mvd_l1_zero"] and l == 1:
+                d = q["tmpl"][ar, q["amvp"]]
+                better = d < bip_dist
+                bip_dist, bip_mvp, bip_ref = np.where(better, d, bip_dist), np.where(better, q["amvp"], bip_mvp), np.where(better, r, bip_ref)
+            if self.shortcut(l, r):
+                z = st[(0, c["list1_to_list0"][r])]
+                q["mv"] = z["mv"].copy()
+                cost = z["cost"] - self.get_cost(z["bits"])
+                q["bits"] = q["bits"] + mv_bits(q["pred"], q["mv"])
+                q["cost"] = cost + self.get_cost(q["bits"])
+            else:
+                mb = mv_bits(q["pred"], q["mv"])
+                q["bits"] = q["bits"] + mb
+                q["cost"] = (np.floor(1.0 * (q["cost"].astype(np.float64) - self.get_cost(mb).astype(np.float64))) + self.get_cost(q["bits"]).astype(np.float64)).astype(U64)
+            # xCheckBestMVP
+            cand, nc = it["ref"]["mv_cand"][:, l, r].astype(np.int64), it["ref"]["num_cand"][:, l, r]
+            oth = 1 - q["idx"]
+            org_bits = mv_bits(q["pred"], q["mv"]) + mic[q["idx"]]
+            b = mv_bits(cand[ar, oth], q["mv"]) + mic[oth]
+            sw = (nc > 1) & (b < org_bits)
+            nb = q["bits"] - org_bits + b
+            ncost = (q["cost"] - self.get_cost(q["bits"])) + self.get_cost(nb)
+            q["idx"], q["bits"], q["cost"] = np.where(sw, oth, q["idx"]), np.where(sw, nb, q["bits"]), np.where(sw, ncost, q["cost"])
+            rs = res["s"][:, l, r]
+            rs["mv"], rs["int_mv"], rs["mvp_idx"], rs["bits"], rs["cost"], rs["tmpl_cost"] = q["mv"], q["imv"], q["idx"], q["bits"], q["cost"], q["tmpl"]
+            better = q["cost"] < ui_cost[:, l]
+            ui_cost[:, l], ui_bits[:, l], ref_idx[:, l] = np.where(better, q["cost"], ui_cost[:, l]), np.where(better, q["bits"], ui_bits[:, l]), np.where(better, r, ref_idx[:, l])
+            c_mv[:, l] = np.where(better[:, None], q["mv"], c_mv[:, l])
+            if l == 1 and c["list1_to_list0"][r] < 0:
+                better = q["cost"] < v_cost
+                v_cost, v_bits, v_ref = np.where(better, q["cost"], v_cost), np.where(better, q["bits"], v_bits), np.where(better, r, v_ref)
+                v_mv = np.where(better[:, None], q["mv"], v_mv)
+        res["ref_idx"], res["mv"], res["cost"], res["bits"] = ref_idx, c_mv, ui_cost, ui_bits
+        res["best_bip_ref_idx_l1"], res["best_bip_mvp_l1"], res["best_bip_dist"] = bip_ref, bip_mvp, bip_dist
+        res["valid_l1_ref_idx"], res["valid_l1_mv"], res["valid_l1_bits"], res["valid_l1_cost"] = v_ref, v_mv, v_bits, v_cost
+        self.host_s += time.perf_counter() - t0
+        return res
+
+
+def chained(org_dev, planes_dev, cfg, items, margin):
+    """-> (UNIPRED_ME_RESULT records, entry calls made)"""
+    ch = Chain(org_dev, planes_dev, cfg, items, margin)
+    res = ch.run()
+    return res, ch.launches

@@ -163,6 +163,29 @@ class BipredMeCfg(C.Structure):
                 ("max_pu_w", C.c_int32), ("max_pu_h", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
+# vvcgpu_unipred_me_batch: one (list, reference index) of an item, one PU, one (list, reference index) of a result, the result of a PU
+UNIPRED_ME_MAX_REFS, UNIPRED_ME_MAX_PLANES = 4, 16
+UNIPRED_PRED2, UNIPRED_CACHED = 1, 2              # UNIPRED_ME_REF.flags
+UNIPRED_ME_REF = np.dtype([("mv_cand", "<i4", (2, 2)), ("pred2", "<i4", (2,)), ("cached_mv", "<i4", (2,)), ("num_cand", "<i2"), ("flags", "<i2"),
+                           ("reserved", "<i4")])
+UNIPRED_ME_ITEM = np.dtype([("pos_x", "<i4"), ("pos_y", "<i4"), ("w", "<i2"), ("h", "<i2"), ("sub_shift", "<i2"), ("tz_flags", "<i2"), ("org_off", "<i8"),
+                            ("org_stride", "<i4"), ("mb_bits", "<u4", (3,)), ("ref", UNIPRED_ME_REF, (2, UNIPRED_ME_MAX_REFS))])
+UNIPRED_ME_SEARCH = np.dtype([("mv", "<i4", (2,)), ("int_mv", "<i4", (2,)), ("mvp_idx", "<i4"), ("bits", "<u4"), ("cost", "<u8"), ("tmpl_cost", "<u8", (2,))])
+UNIPRED_ME_RESULT = np.dtype([("s", UNIPRED_ME_SEARCH, (2, UNIPRED_ME_MAX_REFS)), ("ref_idx", "<i4", (2,)), ("mv", "<i4", (2, 2)), ("cost", "<u8", (2,)),
+                              ("bits", "<u4", (2,)), ("best_bip_ref_idx_l1", "<i4"), ("best_bip_mvp_l1", "<i4"), ("best_bip_dist", "<u8"),
+                              ("valid_l1_ref_idx", "<i4"), ("valid_l1_mv", "<i4", (2,)), ("valid_l1_bits", "<u4"), ("valid_l1_cost", "<u8")])
+
+
+class UnipredMeCfg(C.Structure):
+    """vvcgpu_unipred_me_cfg"""
+    _fields_ = [("lambda_", C.c_double), ("ref_planes", C.c_void_p * UNIPRED_ME_MAX_PLANES), ("n_planes", C.c_int32), ("ref_stride", C.c_int32),
+                ("pic_w", C.c_int32), ("pic_h", C.c_int32), ("max_cu_w", C.c_int32), ("max_cu_h", C.c_int32), ("bit_depth", C.c_int32),
+                ("clp_min", C.c_int32), ("clp_max", C.c_int32), ("n_ref", C.c_int32 * 2), ("ref_plane", (C.c_int32 * UNIPRED_ME_MAX_REFS) * 2),
+                ("search_range", (C.c_int32 * UNIPRED_ME_MAX_REFS) * 2), ("list1_to_list0", C.c_int32 * UNIPRED_ME_MAX_REFS),
+                ("fast_me_gen_b_low_delay", C.c_int32), ("mvd_l1_zero", C.c_int32), ("first_search_stop", C.c_int32), ("use_hadamard", C.c_int32),
+                ("mvp_idx_cost", C.c_uint32 * 3), ("max_pu_w", C.c_int32), ("max_pu_h", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
 # vvcgpu_affine_bipred_me_batch: one (list, reference index) record, one PU, its result and one step of its trace
 AFFINE_BIPRED_MAX_STEPS, AFFINE_BIPRED_MAX_REFS = 16, 4
 AFFINE_BIPRED_REF = np.dtype([("plane", "<i4"), ("mv", "<i4", (3, 2)), ("mv_cand", "<i4", (2, 3, 2)), ("num_cand", "<i2"), ("mvp_idx", "<i2")])

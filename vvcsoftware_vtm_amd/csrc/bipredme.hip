@@ -2,9 +2,9 @@
 //
 // Reference behaviour reproduced (bit-exact, the double arithmetic of the cost included): the loop of InterSearch::predInterSearch
 // (EncoderLib/InterSearch.cpp:1058-1164) with xMotionEstimation(bBi = true) (:1668-1816): removeHighFreq (Buffer.h:389-416), xSetSearchRange (:1820-1854),
-// xPatternSearch (:1887-1941), xPatternSearchFracDIF (:2503-2552; frac_dev.h), and xCheckBestMVP (:1537-1603); motionCompensation -> xPredInterUni ->
+// xPatternSearch (:1887-1941), xPatternSearchFracDIF (:2503-2552; frac_dev.h), and xCheckBestMVP (:1537-1603; me_dev.h); motionCompensation -> xPredInterUni ->
 // xPredInterBlk (CommonLib/InterPrediction.cpp:480-547) with InterpolationFilter::filter / filterCopy (InterpolationFilter.cpp:205-379), clipMv
-// (Mv.cpp:64-80), Mv::divideByPowerOf2 (Mv.h:142-151, ME_ENABLE_ROUNDING_OF_MVS), RdCost::getBitsOfVectorWithPredictor / getCost (RdCost.h:172-199).
+// (Mv.cpp:64-80) -- the prediction body is me_pred_uni of me_dev.h --, Mv::divideByPowerOf2 (Mv.h:142-151, ME_ENABLE_ROUNDING_OF_MVS), RdCost::getBitsOfVectorWithPredictor / getCost (RdCost.h:172-199).
 //
 // Design: the owner of a PU -- one wavefront up to BP_WAVE_MAX samples, the workgroup's four above -- carries it through every iteration, the grid
 // split being that of affine_me.hip (cdiv(n, 4) workgroups of four wavefront owners, then n workgroup owners; an item is served by exactly one of the
@@ -17,6 +17,7 @@
 // scalar state; the per-(list, reference) state that is indexed dynamically (cMvTemp, aaiMvpIdxBi, cMvPredBi) lives in LDS.
 #include "common.h"
 #include "frac_dev.h"
+#include "me_dev.h"
 
 namespace {
 
@@ -34,13 +35,6 @@ inline __host__ __device__ int bp_work_shorts(int w, int h, int range)
 }
 inline __host__ __device__ int bp_lds_bytes(int w, int h, int range) { return BP_HDR + 2 * (bp_r8(w * h) + bp_work_shorts(w, h, range)); }
 
-// NT = 64: the wavefront owns the PU; NT = 256: the workgroup does (every wavefront follows the same, uniform, control flow)
-template <int NT> __device__ __forceinline__ void bp_sync()
-{
-  if (NT == 256) __syncthreads();
-  else { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }
-}
-
 struct BpLds
 {
   FracLds F;                      // F.cost: bytes 0..511, F.sel: 512..543; F.org = the key; F.win / F.hpl / F.pred = the work area
@@ -50,81 +44,21 @@ struct BpLds
   short* work;
 };
 
-struct BpPu
-{
-  const Pel* org; int os;
-  int w, h, lgW, posX, posY, subShift;
-  int horMin, horMax, verMin, verMax;          // clipMv, quarter units
-};
-
-__device__ __forceinline__ unsigned bp_mvbits(int predH, int predV, int scale, int x, int y) { return eg_bits((x << scale) - predH) + eg_bits((y << scale) - predV); }
-__device__ __forceinline__ unsigned long long bp_getcost(double lambda, unsigned bits) { return (unsigned long long)(lambda * (double)bits); }
-
-// motionCompensation (luma, uni) of the quarter-unit vector (mvX, mvY) against `ref` (sample (0, 0) of the picture), and the key from it:
+// motionCompensation (luma, uni; me_dev.h) of the quarter-unit vector (mvX, mvY) against `ref` (sample (0, 0) of the picture), and the key from it:
 // key = 2 org - pred, clipped when cfg.clip_for_bipred_me.  tmp: w x (h + 7) shorts.
 template <int NT>
-__device__ __forceinline__ void bp_key(const BpPu& u, const vvcgpu_bipred_me_cfg& c, const Pel* __restrict__ ref, int mvX, int mvY, short* key, short* tmp, int tid)
+__device__ __forceinline__ void bp_key(const MePu& u, const vvcgpu_bipred_me_cfg& c, const Pel* __restrict__ ref, int mvX, int mvY, short* key, short* tmp, int tid)
 {
-  mvX = min(u.horMax, max(u.horMin, mvX));
-  mvY = min(u.verMax, max(u.verMin, mvY));
-  const int xFrac = (mvX & 3) << 2, yFrac = (mvY & 3) << 2, w = u.w, h = u.h, rs = c.ref_stride;
-  const Pel* blk = ref + (ptrdiff_t)(u.posY + (mvY >> 2)) * rs + u.posX + (mvX >> 2);
-  const short* fx = c_lumaF[xFrac];
-  const short* fy = c_lumaF[yFrac];
-  const int headRoom = 14 - c.bit_depth;                                 // IF_INTERNAL_PREC - bit depth (8..10)
-  const int sh1 = 6 - headRoom, off1 = -(OFFS << sh1);                   // first of two passes
-  const int sh2 = 6 + headRoom, off2 = (1 << (sh2 - 1)) + (OFFS << 6);   // second of two passes
-  const bool both = xFrac != 0 && yFrac != 0;
-  if (both)
+  me_pred_uni<NT>(u, ref, c.ref_stride, c.bit_depth, c.clp_min, c.clp_max, mvX, mvY, tmp, tid, [&](int i, int y, int x, int v)
   {
-    for (int i = tid; i < w * (h + 7); i += NT)
-    {
-      const int r = i >> u.lgW, x = i & (w - 1);
-      const Pel* p = blk + (ptrdiff_t)(r - 3) * rs + x - 3;
-      int sum = 0;
-#pragma unroll
-      for (int k = 0; k < 8; k++) sum += (int)p[k] * fx[k];
-      tmp[i] = (short)((sum + off1) >> sh1);
-    }
-  }
-  bp_sync<NT>();
-  for (int i = tid; i < w * h; i += NT)
-  {
-    const int y = i >> u.lgW, x = i & (w - 1);
-    int v;
-    if (both)
-    {
-      int sum = 0;
-#pragma unroll
-      for (int k = 0; k < 8; k++) sum += (int)tmp[i + k * w] * fy[k];
-      v = clip3(c.clp_min, c.clp_max, (int)(short)((sum + off2) >> sh2));
-    }
-    else if (yFrac != 0)
-    {
-      const Pel* p = blk + (ptrdiff_t)(y - 3) * rs + x;
-      int sum = 0;
-#pragma unroll
-      for (int k = 0; k < 8; k++) sum += (int)p[(ptrdiff_t)k * rs] * fy[k];
-      v = clip3(c.clp_min, c.clp_max, (int)(short)((sum + 32) >> 6));
-    }
-    else if (xFrac != 0)
-    {
-      const Pel* p = blk + (ptrdiff_t)y * rs + x - 3;
-      int sum = 0;
-#pragma unroll
-      for (int k = 0; k < 8; k++) sum += (int)p[k] * fx[k];
-      v = clip3(c.clp_min, c.clp_max, (int)(short)((sum + 32) >> 6));
-    }
-    else v = blk[(ptrdiff_t)y * rs + x];                                 // filterCopy, first and last: no clip
     const int k2 = 2 * (int)u.org[(ptrdiff_t)y * u.os + x] - v;
     key[i] = (short)(c.clip_for_bipred_me ? clip3(c.clp_min, c.clp_max, k2) : k2);
-  }
-  bp_sync<NT>();
+  });
 }
 
 // xPatternSearch over [left, left + nx) x [top, top + ny) (integer vectors); sw = the window (pitch swp), its sample (0, 0) = the block at (left, top)
 template <int NT>
-__device__ __forceinline__ void bp_int_search(const BpPu& u, const BpLds& L, const short* sw, int swp, int left, int top, int nx, int ny, double lambda,
+__device__ __forceinline__ void bp_int_search(const MePu& u, const BpLds& L, const short* sw, int swp, int left, int top, int nx, int ny, double lambda,
                                               int predH, int predV, int tid, int& bx, int& by)
 {
   const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), nw = NT >> 6;
@@ -149,7 +83,7 @@ __device__ __forceinline__ void bp_int_search(const BpPu& u, const BpLds& L, con
     for (int o = 1; o < S; o <<= 1) sum += __shfl_xor(sum, o);
     if (act)
     {
-      const unsigned long long cost = (unsigned long long)(sum << u.subShift) + bp_getcost(lambda, bp_mvbits(predH, predV, 2, left + i, top + j));
+      const unsigned long long cost = (unsigned long long)(sum << u.subShift) + me_getcost(lambda, me_mvbits(predH, predV, 2, left + i, top + j));
       if (cost < bestC) { bestC = cost; bestP = (unsigned)p; }
     }
   }
@@ -178,36 +112,11 @@ __device__ __forceinline__ void bp_int_search(const BpPu& u, const BpLds& L, con
   bx = left + (int)bestP - j * nx; by = top + j;
 }
 
-// xCheckBestMVP (:1537-1603) with the candidate set `a`; the reference's CHECK (mv_cand[mvpIdx] == pred) is the caller's contract
-__device__ __forceinline__ void bp_check_best_mvp(const vvcgpu_bipred_me_ref& a, const vvcgpu_bipred_me_cfg& c, int mvX, int mvY, int& predX, int& predY, int& mvpIdx,
-                                                  unsigned& bits, unsigned long long& cost)
-{
-  if (a.num_cand < 2) return;
-  const int orgBits = (int)(bp_mvbits(predX, predY, 0, mvX, mvY) + c.mvp_idx_cost[mvpIdx]);
-  int bestBits = orgBits, bestIdx = mvpIdx;
-  for (int i = 0; i < 2; i++)
-  {
-    if (i == mvpIdx) continue;
-    const int b = (int)(bp_mvbits(a.mv_cand[i][0], a.mv_cand[i][1], 0, mvX, mvY) + c.mvp_idx_cost[i]);
-    if (b < bestBits) { bestBits = b; bestIdx = i; }
-  }
-  if (bestIdx != mvpIdx)
-  {
-    predX = a.mv_cand[bestIdx][0]; predY = a.mv_cand[bestIdx][1];
-    mvpIdx = bestIdx;
-    const unsigned orgB = bits;
-    bits = orgB - (unsigned)orgBits + (unsigned)bestBits;
-    cost = (cost - bp_getcost(c.lambda, orgB)) + bp_getcost(c.lambda, bits);
-  }
-}
-
-__device__ __forceinline__ unsigned bp_ref_bits(int nRef, int r) { return nRef > 1 ? (unsigned)(r + 1 - (r == nRef - 1 ? 1 : 0)) : 0u; }
-
 template <int NT>
 __device__ __forceinline__ void bp_search(const vvcgpu_bipred_me_item* __restrict__ itp, const vvcgpu_bipred_me_cfg& c, const Pel* __restrict__ orgBase,
                                           const BpLds& L, vvcgpu_bipred_me_result* res, vvcgpu_bipred_me_step* trace, int tid)
 {
-  BpPu u;
+  MePu u;
   u.w = itp->w; u.h = itp->h; u.lgW = ilog2(u.w); u.posX = itp->pos_x; u.posY = itp->pos_y; u.subShift = itp->sub_shift;
   u.org = orgBase + itp->org_off; u.os = itp->org_stride;
   u.horMax = (c.pic_w + 8 - u.posX - 1) << 2; u.horMin = (-c.max_cu_w - 8 - u.posX + 1) << 2;
@@ -224,13 +133,13 @@ __device__ __forceinline__ void bp_search(const vvcgpu_bipred_me_item* __restric
     int* s = L.st + tid * BP_ST;
     s[0] = a.mv[0]; s[1] = a.mv[1]; s[2] = k; s[3] = a.mv_cand[k][0]; s[4] = a.mv_cand[k][1];
   }
-  bp_sync<NT>();
+  me_sync<NT>();
 
   int mvBi[2][2] = { { itp->mv[0][0], itp->mv[0][1] }, { itp->mv[1][0], itp->mv[1][1] } };
   int refBi[2] = { itp->ref_idx[0], itp->ref_idx[1] };
   unsigned motBits[2];
   motBits[0] = itp->bits[0] - itp->mb_bits[0];
-  if (c.mvd_l1_zero) motBits[1] = itp->mb_bits[1] + bp_ref_bits(nRef[1], refBi[1]) + c.mvp_idx_cost[L.st[(4 + refBi[1]) * BP_ST + 2]];     // :1024-1036
+  if (c.mvd_l1_zero) motBits[1] = itp->mb_bits[1] + me_ref_bits(nRef[1], refBi[1]) + c.mvp_idx_cost[L.st[(4 + refBi[1]) * BP_ST + 2]];     // :1024-1036
   else motBits[1] = itp->bits[1] - itp->mb_bits[1];
   unsigned bits2 = mbBits2 + motBits[0] + motBits[1];
   unsigned long long costBi = ~0ull;
@@ -251,7 +160,7 @@ __device__ __forceinline__ void bp_search(const vvcgpu_bipred_me_item* __restric
       const vvcgpu_bipred_me_ref& a = itp->ref[list][r];
       int* s = L.st + (list * 4 + r) * BP_ST;
       int mvpIdx = s[2], predX = s[3], predY = s[4];
-      unsigned bitsT = mbBits2 + motBits[other] + bp_ref_bits(nRef[list], r) + c.mvp_idx_cost[mvpIdx];
+      unsigned bitsT = mbBits2 + motBits[other] + me_ref_bits(nRef[list], r) + c.mvp_idx_cost[mvpIdx];
       const Pel* ref = c.ref_planes[a.plane] + (ptrdiff_t)u.posY * c.ref_stride + u.posX;
       // xSetSearchRange around cMvTemp[list][r]
       const int cx = min(u.horMax, max(u.horMin, s[0])), cy = min(u.verMax, max(u.verMin, s[1]));
@@ -259,15 +168,15 @@ __device__ __forceinline__ void bp_search(const vvcgpu_bipred_me_item* __restric
       const int top = (min(u.verMax, max(u.verMin, cy - (R << 2))) + 2) >> 2, bottom = (min(u.verMax, max(u.verMin, cy + (R << 2))) + 2) >> 2;
       const int nx = right - left + 1, ny = bottom - top + 1;              // 1 .. 2 R + 1 each
       const int swp = w + nx - 1, swr = h + ny - 1;
-      bp_sync<NT>();                                                      // the work area's last readers are done
+      me_sync<NT>();                                                      // the work area's last readers are done
       {
         const Pel* r0 = ref + (ptrdiff_t)top * c.ref_stride + left;
         for (int i = tid; i < swp * swr; i += NT) { const int y = i / swp, x = i - y * swp; L.work[i] = r0[(ptrdiff_t)y * c.ref_stride + x]; }
       }
-      bp_sync<NT>();
+      me_sync<NT>();
       int ix, iy;
       bp_int_search<NT>(u, L, L.work, swp, left, top, nx, ny, c.lambda, predX, predY, tid, ix, iy);
-      bp_sync<NT>();
+      me_sync<NT>();
       // xPatternSearchFracDIF around (ix, iy)
       const int wp = w + 10;
       {
@@ -277,13 +186,13 @@ __device__ __forceinline__ void bp_search(const vvcgpu_bipred_me_item* __restric
       vvcgpu_mvcost mc;
       mc.lambda = c.lambda; mc.pred_hor = predX; mc.pred_ver = predY; mc.cost_scale = 0; mc.imv_shift = 0;
       frac_refine_pu(L.F, w, h, wp, c.bit_depth, c.clp_min, c.clp_max, c.use_hadamard, mc, ix, iy, true, tid, NT, L.fres);
-      bp_sync<NT>();
+      me_sync<NT>();
       const int mvX = (ix << 2) + (L.fres->half_x << 1) + L.fres->qter_x, mvY = (iy << 2) + (L.fres->half_y << 1) + L.fres->qter_y;
-      const unsigned mvBits = bp_mvbits(predX, predY, 0, mvX, mvY);
+      const unsigned mvBits = me_mvbits(predX, predY, 0, mvX, mvY);
       bitsT += mvBits;
-      unsigned long long costT = (unsigned long long)(floor(0.5 * ((double)L.fres->cost - (double)bp_getcost(c.lambda, mvBits))) + (double)bp_getcost(c.lambda, bitsT));
-      bp_check_best_mvp(a, c, mvX, mvY, predX, predY, mvpIdx, bitsT, costT);
-      bp_sync<NT>();                                                      // every lane has read st and fres
+      unsigned long long costT = (unsigned long long)(floor(0.5 * ((double)L.fres->cost - (double)me_getcost(c.lambda, mvBits))) + (double)me_getcost(c.lambda, bitsT));
+      me_check_best_mvp(a.mv_cand, a.num_cand, c.mvp_idx_cost, c.lambda, mvX, mvY, predX, predY, mvpIdx, bitsT, costT);
+      me_sync<NT>();                                                      // every lane has read st and fres
       if (tid == 0) { s[0] = mvX; s[1] = mvY; s[2] = mvpIdx; s[3] = predX; s[4] = predY; }
       const bool accepted = costT < costBi;
       if (trace && tid == 0)
@@ -303,7 +212,7 @@ __device__ __forceinline__ void bp_search(const vvcgpu_bipred_me_item* __restric
         bits2 = bitsT;
       }
     }
-    bp_sync<NT>();
+    me_sync<NT>();
     if (!changed)
     {
       if (costBi <= uniCost[0] && costBi <= uniCost[1])
@@ -314,20 +223,20 @@ __device__ __forceinline__ void bp_search(const vvcgpu_bipred_me_item* __restric
           const vvcgpu_bipred_me_ref& a = list == 0 ? itp->ref[0][refBi[0]] : itp->ref[1][nRef[1] - 1];
           int* s = L.st + refBi[0] * BP_ST;
           int mvpIdx = s[2], predX = s[3], predY = s[4];
-          bp_check_best_mvp(a, c, mvBi[0][0], mvBi[0][1], predX, predY, mvpIdx, bits2, costBi);
-          bp_sync<NT>();
+          me_check_best_mvp(a.mv_cand, a.num_cand, c.mvp_idx_cost, c.lambda, mvBi[0][0], mvBi[0][1], predX, predY, mvpIdx, bits2, costBi);
+          me_sync<NT>();
           if (tid == 0) { s[2] = mvpIdx; s[3] = predX; s[4] = predY; }
-          bp_sync<NT>();
+          me_sync<NT>();
         }
         if (!c.mvd_l1_zero)
         {
           const vvcgpu_bipred_me_ref& a = list == 0 ? itp->ref[0][refBi[0]] : itp->ref[1][refBi[1]];
           int* s = L.st + (4 + refBi[1]) * BP_ST;
           int mvpIdx = s[2], predX = s[3], predY = s[4];
-          bp_check_best_mvp(a, c, mvBi[1][0], mvBi[1][1], predX, predY, mvpIdx, bits2, costBi);
-          bp_sync<NT>();
+          me_check_best_mvp(a.mv_cand, a.num_cand, c.mvp_idx_cost, c.lambda, mvBi[1][0], mvBi[1][1], predX, predY, mvpIdx, bits2, costBi);
+          me_sync<NT>();
           if (tid == 0) { s[2] = mvpIdx; s[3] = predX; s[4] = predY; }
-          bp_sync<NT>();
+          me_sync<NT>();
         }
       }
       break;

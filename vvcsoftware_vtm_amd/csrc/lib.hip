@@ -330,6 +330,11 @@ int vvcgpu_sizeof(int id)
   case 46: return (int)sizeof(vvcgpu_affine_bipred_cfg);
   case 47: return (int)sizeof(vvcgpu_affine_bipred_result);
   case 48: return (int)sizeof(vvcgpu_affine_bipred_step);
+  case 50: return (int)sizeof(vvcgpu_unipred_me_ref);
+  case 51: return (int)sizeof(vvcgpu_unipred_me_item);
+  case 52: return (int)sizeof(vvcgpu_unipred_me_cfg);
+  case 53: return (int)sizeof(vvcgpu_unipred_me_search);
+  case 54: return (int)sizeof(vvcgpu_unipred_me_result);
   default: return -1;
   }
 }
