@@ -47,7 +47,8 @@ int         vvcgpu_set_device(int device);
  * 32 wp_sad_cand, 33 tile_stats, 34 affine_me_item, 35 affine_me_cfg, 36 affine_me_result, 37 affine_me_step,
  * 38 bipred_me_ref, 39 bipred_me_item, 40 bipred_me_cfg, 41 bipred_me_result, 42 bipred_me_step, 44 affine_bipred_ref, 45 affine_bipred_item,
  * 46 affine_bipred_cfg, 47 affine_bipred_result, 48 affine_bipred_step, 50 unipred_me_ref, 51 unipred_me_item, 52 unipred_me_cfg,
- * 53 unipred_me_search, 54 unipred_me_result; -1 for unknown ids (43 and 49 are not assigned and stay unknown). */
+ * 53 unipred_me_search, 54 unipred_me_result, 56 affine_unipred_ref, 57 affine_unipred_item, 58 affine_unipred_cfg, 59 affine_unipred_search,
+ * 60 affine_unipred_result; -1 for unknown ids (43, 49 and 55 are not assigned and stay unknown). */
 int         vvcgpu_sizeof(int struct_id);
 
 /* ---- device memory helpers for host-side callers (the reference keeps pictures in host memory; the shim stages them).
@@ -750,8 +751,8 @@ int vvcgpu_bipred_me_batch(const vvc_pel* org_base, const vvcgpu_bipred_me_item*
  *                     and 2, uint32 bits, wrapping uint64 cost; then keep-if-strictly-better against uiCostBi (:2960-2978), which starts at UINT64_MAX.
  * After a pass without change (:2981-2995) the two closing xCheckBestAffineMVP calls are made when uiCostBi <= uiCost[0] && uiCostBi <= uiCost[1]; each
  * gets the candidate set of the list it checks (unlike the translational loop).  All vectors are in 1/16 sample units (after Mv::setHighPrec; the
- * convention of vvcgpu_affine_me_item.mvp).  Not served: the uni-predictive stage (:2651-2814; one vvcgpu_affine_me_batch call plus host decisions),
- * the final mode choice (:3017-3099; host), weighted prediction.
+ * convention of vvcgpu_affine_me_item.mvp).  The uni-predictive stage (:2651-2814) is vvcgpu_affine_unipred_me_batch, whose out-items are this
+ * entry's items.  Not served: the final mode choice (:3017-3099; host), weighted prediction.
  * Reference planes and readable margin: as vvcgpu_bipred_me_batch -- ref_planes[i] points to sample (0, 0) of picture i inside its padded allocation;
  * sub-block vectors are clipped to the picture + 8 / - CTU - 8 samples and the 8 taps reach 4 further: max_cu + 12 readable samples around the picture
  * on every side serve every search.
@@ -932,6 +933,115 @@ typedef struct {                        /* one PU                               
 } vvcgpu_unipred_me_result;
 int vvcgpu_unipred_me_batch(const vvc_pel* org_base, const vvcgpu_unipred_me_item* items, int n, const vvcgpu_unipred_me_cfg* cfg_host,
                             vvcgpu_unipred_me_result* results, vvcgpu_bipred_me_item* bipred_items_out, void* stream);
+
+/* The WHOLE uni-predictive stage of the affine inter search of a PU (the uni-predictive part of InterSearch::xPredAffineInterSearch,
+ * InterSearch.cpp:2651-2814, with xEstimateAffineAMVP :3745-3794 / xGetAffineTemplateCost :1645-1665, xAffineMotionEstimation(bBi = false) :3286-3743
+ * and xCheckBestAffineMVP :3181-3284 inside it) for a list of independent PUs of mixed sizes and mixed 4- / 6-parameter type, with no host
+ * synchronisation inside: two launches on the stream.  The first gives every (PU, list, reference index) search an owner of its own (a wavefront up to
+ * 1024 samples, a workgroup above), the second makes the per-PU decisions.  Results are bit-exact, the double arithmetic of the costs included.  All
+ * vectors are in 1/16 sample units, after Mv::setHighPrec (the convention of vvcgpu_affine_me_item.mvp and of vvcgpu_affine_bipred_me_batch): the
+ * reference holds hevcMv as quarter-sample vectors and mvAffine4Para, the output of an earlier xAffineMotionEstimation, as 1/16-sample ones;
+ * xPredAffineBlk and xAffineMotionEstimation raise what they get to 1/16 sample (InterPrediction.cpp:579-581, InterSearch.cpp:3327-3329), and
+ * :2700-2706 work on the raw components of mvFour, which are 1/16-sample values, so hevc_mv = hevcMv << 2 and mv4 = mvAffine4Para as they are give
+ * what the reference computes.  Per PU and per (list, reference index), in the reference's order:
+ *   bits              uiBitsTemp = mb_bits[list] + the reference-index bits of :2658-2666 (cfg.n_ref[list]);
+ *   xEstimateAffineAMVP   with the caller's candidates (PU::fillAffineMvpCand stays on the host): per candidate xGetAffineTemplateCost -- luma
+ *                     xPredAffineBlk with bi = false on the candidate's three vectors as they are (no clipMv of them), rounded and clipped, full SAD
+ *                     against the original + getCost(mvp_idx_cost[i]); the best by uiBestCost > uiTmpCost in candidate order; its cost is biPDistTemp;
+ *   :2673-2677        a 6-parameter PU whose only_ref[list] (refIdx4Para) differs from this index stops here: only aaiMvpIdx and the candidate set are
+ *                     kept, cMvTemp stays zero; this happens before the bestBiP* update;
+ *   start vectors     (:2681-2727) the template cost of hevc_mv used for all three control points, with the chosen index's cost; for a 6-parameter PU
+ *                     also that of the inherited 4-parameter result mvFour: mv4[0..1] and mvFour[2] by :2700-2706 ((mv4[0] << 7) -+ ((mv4[1] - mv4[0])
+ *                     swapped << (7 + log2 h - log2 w)), >> 7, roundMV2SignalPrecision), taken on strict '<'; the search starts from that vector when
+ *                     its cost is < biPDistTemp, otherwise from the predictor;
+ *   :2730-2735        bestBiPDist / bestBiPMvpL1 / bestBiPRefIdxL1 when cfg.mvd_l1_zero (list 1, strict '<');
+ *   search            (:2738-2783) bits += mvp_idx_cost[mvp_idx]; then xAffineMotionEstimation(bBi = false) -- exactly what vvcgpu_affine_me_batch does
+ *                     for an item with half_weight = 0 -- or the list-1 shortcut: with cfg.fast_me_gen_b_low_delay, list1_to_list0[ref] >= 0 and, for a
+ *                     6-parameter PU, list1_to_list0[ref] == only_ref[0], a list-1 reference copies list 0's vectors, subtracts getCost(bits) of list 0
+ *                     (uint64), adds the vector bits of :2753-2770 (second-predictor rule for vectors 1 and 2) and adds getCost again;
+ *   xCheckBestAffineMVP   over that (list, reference)'s candidates;
+ *   :2788-2812        the uiCostTempL0 / uiBitsTempL0 record, keep-if-strictly-better per list, and the "valid list 1" record.
+ * Not served: weighted prediction (the bi branch of xGetAffineTemplateCost), composite reference.  Affine AMVP derivation and the final mode choice
+ * (:3017-3099) stay on the host.
+ * bipred_items_out (may be NULL): n complete vvcgpu_affine_bipred_item records, exactly what vvcgpu_affine_bipred_me_batch asks of its caller --
+ * geometry, n_ref, planes, cMvTemp, candidates and aaiMvpIdx per (list, reference), iRefIdx, aacMv, uiCost, uiBits, mb_bits, only_ref -- with the
+ * mvd_l1_zero preparation of :2840-2853 done when cfg.mvd_l1_zero (ref_idx[1] = bestBiPRefIdxL1, that record's mvp_idx = bestBiPMvpL1, its mv and
+ * mv[1] = that candidate), so that the buffer can be handed to vvcgpu_affine_bipred_me_batch on the same stream as it is.  On a P slice
+ * (n_ref[1] == 0) the records carry n_ref[1] = 0, which the bi-predictive entry skips.
+ * Reference planes and readable margin: as vvcgpu_affine_bipred_me_batch -- ref_planes[i] points to sample (0, 0) of picture i inside its padded
+ * allocation; sub-block vectors are clipped to the picture + 8 / - CTU - 8 samples and the 8 taps reach 4 further: max_cu + 12 readable samples around
+ * the picture on every side serve every prediction of every search.
+ * items, results, bipred_items_out: device memory.  Items cannot be validated on the host: an item outside the contract (a side not in {16, 32, 64,
+ * 128} or larger than the CTU or than cfg.max_pu_w / max_pu_h, a PU not inside the picture, org_stride <= 0, only_ref[l] outside -1 .. n_ref[l] - 1 for
+ * a list that has references, num_cand outside 1..2 for a (list, reference) of the slice) is skipped: it reads no sample, its result has cost[0] =
+ * cost[1] = ~0 (UINT64_MAX) with everything else zero, its out-item is all zero.  n == 0 is a no-op; null pointers (bipred_items_out may be NULL),
+ * n < 0, geometry, clp_min > clp_max, lambda outside [0, 2^20), n_planes outside 1..16, n_ref[0] outside 1..4, n_ref[1] outside 0..4, a ref_plane
+ * outside [0, n_planes), a list1_to_list0 outside [-1, n_ref[0]) and max_pu sides that are no served side return VVCGPU_E_ARG, a bit depth outside
+ * 8..10 VVCGPU_E_UNSUPPORTED, before any device work. */
+#define VVCGPU_AFFINE_UNIPRED_MAX_REFS 4
+typedef struct {                        /* one (list, reference index) of a PU                sizeof == 80 */
+  int32_t mv_cand[2][3][2];  /* affiAMVPInfo: mvCandLT / RT / LB of candidates 0 and 1 */
+  int32_t hevc_mv[2];        /* hevcMv[list][ref] << 2: the translational result */
+  int32_t mv4[2][2];         /* mvAffine4Para[list][ref][0..1]: read for a 6-parameter PU */
+  int16_t num_cand;          /* .numCand: 1..2 */
+  int16_t reserved0;
+  int32_t reserved1;
+} vvcgpu_affine_unipred_ref;
+typedef struct {                        /* one PU                                             sizeof == 688 */
+  int32_t  pos_x, pos_y;     /* pu.cu->lumaPos() */
+  int16_t  w, h;             /* 16, 32, 64 or 128 each */
+  int16_t  six_param;        /* cu->affineType */
+  int16_t  reserved0;
+  int64_t  org_off;          /* elements from org_base */
+  int32_t  org_stride;
+  uint32_t mb_bits[3];       /* uiMbBits[0..2] */
+  int32_t  only_ref[2];      /* refIdx4Para[list]: a 6-parameter PU searches only this index of the list (-1: none); copied to the out-item */
+  vvcgpu_affine_unipred_ref ref[2][VVCGPU_AFFINE_UNIPRED_MAX_REFS];
+} vvcgpu_affine_unipred_item;
+typedef struct {                        /* host struct                                        sizeof == 264 */
+  double  lambda;            /* RdCost::m_motionLambda */
+  const vvc_pel* ref_planes[16];   /* device pointers; entries from n_planes on are ignored */
+  int32_t n_planes, ref_stride;
+  int32_t pic_w, pic_h, max_cu_w, max_cu_h;                 /* clipMv, sub-block vector clip */
+  int32_t bit_depth, clp_min, clp_max;
+  int32_t n_ref[2];                                         /* slice.getNumRefIdx(list): 1..4, list 1 also 0 (P slice) */
+  int32_t ref_plane[2][VVCGPU_AFFINE_UNIPRED_MAX_REFS];     /* index into ref_planes of (list, reference index) */
+  int32_t list1_to_list0[VVCGPU_AFFINE_UNIPRED_MAX_REFS];   /* slice.getList1IdxToList0Idx(ref): -1 or a list-0 reference index */
+  int32_t fast_me_gen_b_low_delay;  /* getFastMEForGenBLowDelayEnabled() */
+  int32_t mvd_l1_zero;              /* slice.getMvdL1ZeroFlag() */
+  int32_t affine_type;              /* sps.getSpsNext().getUseAffineType(): iteration limit 4 (6-param) / 5 (4-param); 0: 7 (as vvcgpu_affine_me_cfg) */
+  uint32_t mvp_idx_cost[3];         /* m_auiMVPIdxCost[0..2][AMVP_MAX_NUM_CANDS] */
+  int32_t max_pu_w, max_pu_h;       /* as in vvcgpu_affine_bipred_cfg: no item is wider / higher (0: 128); an item beyond it is skipped */
+  int32_t reserved;
+} vvcgpu_affine_unipred_cfg;
+typedef struct {                        /* one (list, reference index) of a result            sizeof == 88 */
+  int32_t  mv[3][2];         /* cMvTemp[list][ref]: what the caller stores as mvAffine4Para (zero where skipped by only_ref) */
+  int32_t  mvp_idx;          /* aaiMvpIdx[list][ref] after xCheckBestAffineMVP */
+  uint32_t bits;             /* uiBitsTemp after xCheckBestAffineMVP (0 where skipped) */
+  uint64_t cost;             /* uiCostTemp after xCheckBestAffineMVP (0 where skipped) */
+  uint64_t tmpl_cost[2];     /* xGetAffineTemplateCost of candidate 0..1 (0 beyond num_cand) */
+  uint64_t start_cost;       /* template cost of the translational start; 0 unless searched == 1 */
+  uint64_t inherit_cost;     /* template cost of the inherited 4-parameter start; 0 unless searched == 1 of a 6-parameter PU */
+  int32_t  start;            /* 0 the predictor, 1 the translational vector, 2 the inherited vectors; 0 unless searched == 1 */
+  uint32_t steps;            /* as vvcgpu_affine_me_result.steps; 0 where nothing was searched */
+  int32_t  searched;         /* 0 skipped by only_ref, 1 searched, 2 the list-1 shortcut */
+  int32_t  reserved;
+} vvcgpu_affine_unipred_search;
+typedef struct {                        /* one PU                                             sizeof == 840 */
+  vvcgpu_affine_unipred_search s[2][VVCGPU_AFFINE_UNIPRED_MAX_REFS];   /* entries beyond cfg.n_ref[list] are zero */
+  int32_t  ref_idx[2];       /* iRefIdx[0..1] */
+  int32_t  mv[2][3][2];      /* aacMv[0..1] */
+  uint64_t cost[2];          /* uiCost[0..1]; both ~0 with everything else zero: item skipped.  cost[1] = ~0 on a P slice */
+  uint32_t bits[2];          /* uiBits[0..1] (0 for a list in which nothing was searched) */
+  int32_t  best_bip_ref_idx_l1, best_bip_mvp_l1;   /* bestBiPRefIdxL1, bestBiPMvpL1 (0 unless mvd_l1_zero) */
+  uint64_t best_bip_dist;    /* bestBiPDist (~0 unless mvd_l1_zero set it) */
+  int32_t  valid_l1_ref_idx;    /* refIdxValidList1 */
+  int32_t  valid_l1_mv[3][2];   /* mvValidList1 */
+  uint32_t valid_l1_bits;       /* bitsValidList1 (0xFFFFFFFF: no valid list-1 reference) */
+  uint64_t valid_l1_cost;       /* costValidList1 (~0: no valid list-1 reference) */
+} vvcgpu_affine_unipred_result;
+int vvcgpu_affine_unipred_me_batch(const vvc_pel* org_base, const vvcgpu_affine_unipred_item* items, int n, const vvcgpu_affine_unipred_cfg* cfg_host,
+                                   vvcgpu_affine_unipred_result* results, vvcgpu_affine_bipred_item* bipred_items_out, void* stream);
 
 /* ---- N2 ("next" row): integer-sample TZ search of whole PUs, on the device  (InterSearch::xTZSearch,
  *          EncoderLib/InterSearch.cpp:1971-2252, with xTZSearchHelp :249-343, xTZ2PointSearch :349-374,

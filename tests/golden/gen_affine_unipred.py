@@ -1,0 +1,290 @@
+"""Generates tests/golden/affine_unipred.npz: whole affine uni-predictive stages (the uni-predictive part of InterSearch::xPredAffineInterSearch,
+InterSearch.cpp:2651-2814, with the loop of xEstimateAffineAMVP :3765-3784) whose every step is the COMPILED REFERENCE's.  Build machine only (needs
+the reference tree and oracle/_ref/libvtmref.so, i.e. a build() where the reference exists):  python tests/golden/gen_affine_unipred.py
+
+xPredAffineInterSearch itself needs the affine AMVP derivation and the mode control around it, which is no modest scaffold; so
+gen_affine_unipred_driver.cpp -- compiled here against the reference's headers (the include set of oracle/Makefile's CXXFLAGS_REF,
+-fno-access-control) and linked with libvtmref.so -- exposes the reference's own xGetAffineTemplateCost, xAffineMotionEstimation(bBi = false),
+xCheckBestAffineMVP, Mv::roundMV2SignalPrecision and the RdCost vector bits on a real Picture / Slice / PU scaffold, and ref_loop() below drives them
+with the loop control of :2651-2814 and :3765-3784, written here from the reference's text.  The tests' restatement (tests/affine_unipred_cases.py)
+has its own writing of that loop control over the CPU restatement's pixel steps; the generator asserts that it reproduces every stored result and
+every out-item.  So the arithmetic of every step is the compiled reference's, and the loop control is pinned by two independent drivings of it.
+
+Precision flags: ref_loop hands the driver Mv objects as the reference has them at :2683-2706 -- the candidates 1/16-sample (PU::fillAffineMvpCand),
+hevcMv quarter-sample (hevc_mv >> 2, flag off), mvAffine4Para 1/16-sample (the flag xAffineMotionEstimation's output carries, which the driver
+reports and this file asserts) -- and the raw components of mvFour go into :2700-2706 as they are.  The stored results, all in 1/16 units, are
+what the restatement computes from hevc_mv = hevcMv << 2 and mv4 = mvAffine4Para unchanged: that is the outcome the header states.
+
+Nothing of the reference is copied; only the resulting data is stored.  The `steps` of a search (which xAffineMotionEstimation does not return) are
+the restatement's, stored after everything else agreed.  xCheckBestAffineMVP has no CHECK, so every generated item is stored."""
+import ctypes as C
+import os
+import subprocess
+import sys
+import tempfile
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(os.path.dirname(HERE))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(HERE))
+
+import affine_unipred_cases as uc  # noqa: E402
+from oraclelib import p  # noqa: E402
+from vvcsoftware_vtm_amd import abi  # noqa: E402
+
+REF = os.environ.get("REF", "/root/reference")
+W, H = 256, 128
+N_PLANES = 4
+FLAT = (192, 64, 64, 64)             # x, y, w, h of the flat patch of the original
+MVP_IDX_COST = (1, 1, 0)
+U64, U32 = (1 << 64) - 1, (1 << 32) - 1
+#          fast_me_gen_b_low_delay, mvd_l1_zero, affine_type | n_ref | list1_to_list0
+GROUPS = [((0, 0, 1), (2, 2), (-1, -1, -1, -1)),       # plain B
+          ((1, 0, 1), (2, 3), (0, -1, 1, -1)),         # the shortcut with a mixed list1_to_list0
+          ((1, 1, 1), (2, 3), (-1, 1, -1, -1)),        # mvd_l1_zero
+          ((0, 0, 1), (4, 0), (-1, -1, -1, -1)),       # P slice
+          ((0, 0, 0), (1, 2), (-1, -1, -1, -1))]       # affine_type 0
+REF_PLANE = ((0, 1, 2, 3), (1, 0, 3, 2))
+
+
+def driver():
+    src = os.path.join(REF, "source", "Lib")
+    inc = ["-I" + os.path.join(src, d) for d in ("", "CommonLib", "CommonLib/x86", "libmd5", "EncoderLib", "DecoderLib", "Utilities")]
+    refdir = os.path.join(ROOT, "oracle", "_ref")
+    out = os.path.join(tempfile.mkdtemp(), "libauref.so")
+    subprocess.check_call(["g++", "-std=c++11", "-O2", "-fPIC", "-shared", "-msse4.1", "-w", "-DNDEBUG", "-fno-access-control"] + inc +
+                          [os.path.join(HERE, "gen_affine_unipred_driver.cpp"), "-o", out, "-L" + refdir, "-lvtmref", "-Wl,-rpath," + refdir])
+    D = C.CDLL(out)
+    D.auref_template_cost.restype = C.c_uint64
+    D.auref_get_cost.restype = C.c_uint64
+    D.auref_vector_bits.restype = C.c_uint
+    return D
+
+
+_KEEP = []                           # the arrays whose addresses a driver call of the current item received
+
+
+def i32(v):
+    _KEEP.append(np.ascontiguousarray(np.asarray(v, np.int32).reshape(-1)))
+    return _KEEP[-1]
+
+
+def ref_loop(D, org, it, flags, n_ref, l1to0):
+    """:2651-2814 (and :2840-2853 for the out-item) over the driver's primitives -> (result record without `steps`, out-item record)"""
+    del _KEEP[:]
+    fast, mvd_l1_zero = flags[0], flags[1]
+    px, py, w, h, six = int(it["pos_x"]), int(it["pos_y"]), int(it["w"]), int(it["h"]), int(it["six_param"])
+    blk, os_ = org.reshape(-1)[int(it["org_off"]):], int(it["org_stride"])
+    D.auref_set_lists(n_ref[0], p(i32(REF_PLANE[0])), n_ref[1], p(i32(REF_PLANE[1])))
+    mvNum = 3 if six else 2
+    refIdx4Para = [int(v) for v in it["only_ref"]]
+    uiMbBits = [int(v) for v in it["mb_bits"]]
+    zero3 = [[0, 0], [0, 0], [0, 0]]
+    cMvTemp = [[[list(v) for v in zero3] for _ in range(4)] for _ in range(2)]
+    cMvPred = [[None] * 4 for _ in range(2)]
+    aaiMvpIdx = [[0] * 4 for _ in range(2)]
+    uiCost, uiBits, iRefIdx, aacMv = [U64, U64], [0, 0], [0, 0], [zero3, zero3]
+    uiCostTempL0, uiBitsTempL0 = [U64] * 4, [0] * 4
+    bestBiPDist, bestBiPMvpL1, bestBiPRefIdxL1 = U64, 0, 0
+    costValidList1, bitsValidList1, mvValidList1, refIdxValidList1 = U64, U32, zero3, 0
+    res = np.zeros(1, abi.AFFINE_UNIPRED_RESULT)
+
+    def template_cost(lst, r, mv, hp, idx):
+        return int(D.auref_template_cost(p(blk), os_, px, py, w, h, six, lst, r, p(i32(mv)), hp, idx))
+
+    def bits_of(mv, pred):
+        """:2753-2770 through RdCost and Mv of the reference"""
+        return sum(int(D.auref_vector_bits(p(i32(mv[i])), 1, p(i32(pred[i])), 1, int(i != 0), p(i32(mv[0])), p(i32(pred[0])))) for i in range(mvNum))
+
+    for iRefList in range(2):
+        for iRefIdxTemp in range(n_ref[iRefList]):
+            a = it["ref"][iRefList][iRefIdxTemp]
+            cand = [uc.vec3(a["mv_cand"][k]) for k in range(2)]
+            uiBitsTemp = uiMbBits[iRefList]
+            if n_ref[iRefList] > 1:
+                uiBitsTemp += iRefIdxTemp + 1
+                if iRefIdxTemp == n_ref[iRefList] - 1:
+                    uiBitsTemp -= 1
+            # xEstimateAffineAMVP :3765-3784
+            uiBestCost, iBestIdx, biPDistTemp, tmpl = U64, 0, None, [0, 0]
+            for i in range(int(a["num_cand"])):
+                uiTmpCost = tmpl[i] = template_cost(iRefList, iRefIdxTemp, cand[i], 1, i)
+                if uiBestCost > uiTmpCost:
+                    uiBestCost, iBestIdx, biPDistTemp = uiTmpCost, i, uiTmpCost
+            cMvPred[iRefList][iRefIdxTemp] = [list(v) for v in cand[iBestIdx]]
+            aaiMvpIdx[iRefList][iRefIdxTemp] = iBestIdx
+            rec = res[0]["s"][iRefList][iRefIdxTemp]
+            rec["mvp_idx"], rec["tmpl_cost"] = iBestIdx, tmpl
+            if six and refIdx4Para[iRefList] != iRefIdxTemp:
+                continue
+            take_l0 = bool(fast) and iRefList == 1 and l1to0[iRefIdxTemp] >= 0 and (not six or l1to0[iRefIdxTemp] == refIdx4Para[0])
+            start_cost = inherit_cost = sel = 0
+            if not take_l0:                                                      # what :2681-2727 compute is overwritten at :2749 otherwise
+                hevc_q = [int(a["hevc_mv"][0]) >> 2, int(a["hevc_mv"][1]) >> 2]   # hevcMv as the reference holds it: quarter sample, flag off
+                assert [v << 2 for v in hevc_q] == [int(v) for v in a["hevc_mv"]]
+                mvHevc, hevc_hp, sel = [hevc_q] * 3, 0, 1
+                uiCandCost = start_cost = template_cost(iRefList, iRefIdxTemp, mvHevc, 0, aaiMvpIdx[iRefList][iRefIdxTemp])
+                assert start_cost == template_cost(iRefList, iRefIdxTemp, [[v << 2 for v in hevc_q]] * 3, 1, aaiMvpIdx[iRefList][iRefIdxTemp])
+                if six:
+                    mvFour = [[int(v) for v in a["mv4"][0]], [int(v) for v in a["mv4"][1]], None]      # 1/16 sample, flag on
+                    shift = 7
+                    sh2 = shift + (h.bit_length() - 1) - (w.bit_length() - 1)
+                    vx2 = ((mvFour[0][0] << shift) - ((mvFour[1][1] - mvFour[0][1]) << sh2)) >> shift
+                    vy2 = ((mvFour[0][1] << shift) + ((mvFour[1][0] - mvFour[0][0]) << sh2)) >> shift
+                    hv = np.zeros(2, np.int32)
+                    D.auref_round_mv(vx2, vy2, 1, p(hv))
+                    mvFour[2] = [int(hv[0]), int(hv[1])]
+                    uiCandCostInherit = inherit_cost = template_cost(iRefList, iRefIdxTemp, mvFour, 1, aaiMvpIdx[iRefList][iRefIdxTemp])
+                    if uiCandCostInherit < uiCandCost:
+                        uiCandCost, mvHevc, hevc_hp, sel = uiCandCostInherit, mvFour, 1, 2
+                if uiCandCost < biPDistTemp:
+                    start, start_hp = mvHevc, hevc_hp
+                else:
+                    start, start_hp, sel = cMvPred[iRefList][iRefIdxTemp], 1, 0
+            if mvd_l1_zero and iRefList == 1 and biPDistTemp < bestBiPDist:
+                bestBiPDist, bestBiPMvpL1, bestBiPRefIdxL1 = biPDistTemp, aaiMvpIdx[iRefList][iRefIdxTemp], iRefIdxTemp
+            uiBitsTemp += MVP_IDX_COST[aaiMvpIdx[iRefList][iRefIdxTemp]]
+            if take_l0:
+                k = l1to0[iRefIdxTemp]
+                cMvTemp[1][iRefIdxTemp] = [list(v) for v in cMvTemp[0][k]]
+                uiCostTemp = (uiCostTempL0[k] - int(D.auref_get_cost(uiBitsTempL0[k]))) & U64
+                uiBitsTemp = (uiBitsTemp + bits_of(cMvTemp[1][iRefIdxTemp], cMvPred[iRefList][iRefIdxTemp])) & U32
+                uiCostTemp = (uiCostTemp + int(D.auref_get_cost(uiBitsTemp))) & U64
+            else:
+                mv, bits, cost, hp_out = i32(start).copy(), C.c_uint(uiBitsTemp & U32), C.c_uint64(0), C.c_int(0)
+                D.auref_me(p(blk), os_, px, py, w, h, six, iRefList, iRefIdxTemp, p(i32(cMvPred[iRefList][iRefIdxTemp])), 1, p(mv), start_hp, C.byref(bits),
+                           C.byref(cost), C.byref(hp_out))
+                assert hp_out.value == 1                                         # what becomes mvAffine4Para carries the high-precision flag
+                cMvTemp[iRefList][iRefIdxTemp], uiBitsTemp, uiCostTemp = uc.vec3(mv.reshape(3, 2)), bits.value, cost.value
+            pr, ix, b, c = i32(cMvPred[iRefList][iRefIdxTemp]).copy(), C.c_int(aaiMvpIdx[iRefList][iRefIdxTemp]), C.c_uint(uiBitsTemp), C.c_uint64(uiCostTemp)
+            D.auref_check_best_mvp(six, iRefList, p(i32(cMvTemp[iRefList][iRefIdxTemp])), 1, p(pr), C.byref(ix), p(i32(a["mv_cand"])), 1, int(a["num_cand"]),
+                                   C.byref(b), C.byref(c))
+            cMvPred[iRefList][iRefIdxTemp], aaiMvpIdx[iRefList][iRefIdxTemp], uiBitsTemp, uiCostTemp = uc.vec3(pr.reshape(3, 2)), ix.value, b.value, c.value
+            res[0]["s"][iRefList][iRefIdxTemp] = (cMvTemp[iRefList][iRefIdxTemp], ix.value, uiBitsTemp, uiCostTemp, tmpl, start_cost, inherit_cost, sel, 0,
+                                                  2 if take_l0 else 1, 0)
+            if iRefList == 0:
+                uiCostTempL0[iRefIdxTemp], uiBitsTempL0[iRefIdxTemp] = uiCostTemp, uiBitsTemp
+            if uiCostTemp < uiCost[iRefList]:
+                uiCost[iRefList], uiBits[iRefList] = uiCostTemp, uiBitsTemp
+                aacMv[iRefList], iRefIdx[iRefList] = [list(v) for v in cMvTemp[iRefList][iRefIdxTemp]], iRefIdxTemp
+            if iRefList == 1 and uiCostTemp < costValidList1 and l1to0[iRefIdxTemp] < 0:
+                costValidList1, bitsValidList1 = uiCostTemp, uiBitsTemp
+                mvValidList1, refIdxValidList1 = [list(v) for v in cMvTemp[iRefList][iRefIdxTemp]], iRefIdxTemp
+    r0 = res[0]
+    r0["ref_idx"], r0["mv"], r0["cost"], r0["bits"] = iRefIdx, aacMv, uiCost, uiBits
+    r0["best_bip_ref_idx_l1"], r0["best_bip_mvp_l1"], r0["best_bip_dist"] = bestBiPRefIdxL1, bestBiPMvpL1, bestBiPDist
+    r0["valid_l1_ref_idx"], r0["valid_l1_mv"], r0["valid_l1_bits"], r0["valid_l1_cost"] = refIdxValidList1, mvValidList1, bitsValidList1, costValidList1
+    # the item of the bi-predictive stage: what :2823-2853 start from
+    out = np.zeros(1, abi.AFFINE_BIPRED_ITEM)
+    o = out[0]
+    o["pos_x"], o["pos_y"], o["w"], o["h"], o["six_param"], o["org_off"], o["org_stride"] = px, py, w, h, six, it["org_off"], os_
+    o["n_ref"], o["ref_idx"], o["mv"], o["cost"], o["bits"], o["mb_bits"], o["only_ref"] = n_ref, iRefIdx, aacMv, uiCost, uiBits, uiMbBits, refIdx4Para
+    for l in range(2):
+        for r in range(n_ref[l]):
+            q = o["ref"][l][r]
+            q["plane"], q["mv"], q["mv_cand"], q["num_cand"], q["mvp_idx"] = REF_PLANE[l][r], cMvTemp[l][r], it["ref"][l][r]["mv_cand"], it["ref"][l][r]["num_cand"], aaiMvpIdx[l][r]
+    if mvd_l1_zero and n_ref[1] > 0:
+        q = o["ref"][1][bestBiPRefIdxL1]
+        pcMvTemp = uc.vec3(q["mv_cand"][bestBiPMvpL1])
+        q["mvp_idx"], q["mv"] = bestBiPMvpL1, pcMvTemp
+        o["mv"][1], o["ref_idx"][1] = pcMvTemp, bestBiPRefIdxL1
+    return res[0], out[0]
+
+
+def build_items(rng, painter, org, n_ref):
+    """the items of one group: every shape as a 4- and a 6-parameter PU on a warped patch, single-candidate and identical-candidate PUs, corner PUs
+    with far-out vectors, and PUs on the flat patch"""
+    items = []
+    fx, fy, _, _ = FLAT
+
+    def add(w, h, six, px=None, py=None, far=0, cands=None, painted=True):
+        if px is None:
+            px = int(rng.integers(0, (W - 64 - w) // 4 + 1)) * 4 if w <= W - 64 else 0          # the flat patch stays as it is
+            py = int(rng.integers(0, (H - h) // 4 + 1)) * 4
+        it, truth = uc.random_item(rng, W, H, w, h, six, n_ref, px, py, far, cands)
+        if painted:
+            l = int(rng.integers(0, 2)) if n_ref[1] else 0
+            uc.paint(org, painter, it, REF_PLANE[l][int(rng.integers(0, n_ref[l]))], truth, rng)
+        items.append(it)
+    for (w, h) in uc.SHAPES:
+        for six in (0, 1):
+            add(w, h, six)
+    for k in range(4):
+        add(16, 16, k & 1, cands=1 + (k >> 1))
+    for k in range(4):                                                                    # the picture's corners, vectors far outside
+        w, h = [(16, 16), (32, 32)][k & 1]
+        add(w, h, k >> 1, (0, W - w)[k & 1], (0, H - h)[k >> 1], far=300, painted=False)
+    for six in (0, 1):
+        add(16 << six, 16, six, fx + 16, fy + 16, painted=False)
+    return np.array(items, dtype=abi.AFFINE_UNIPRED_ITEM)
+
+
+def build_set(D, bd, rng):
+    mx = (1 << bd) - 1
+    lam = 37.5 if bd == 10 else 11.25
+    planes, org = uc.make_planes(rng, N_PLANES, W, H, bd)
+    fx, fy, fw, fh = FLAT
+    org[fy:fy + fh, fx:fx + fw] = mx // 3 + 7                                        # flat original on flat references: zero gradients, a singular system
+    for k in range(N_PLANES):
+        planes[k, fy:fy + fh, fx:fx + fw] = mx // 3 + 7 + 3 * k
+    painter = uc.Searcher(org, uc.pad(planes), uc.cfg_dict(lam, W, H, bd))
+    groups = [build_items(rng, painter, org, n_ref) for _, n_ref, _ in GROUPS]       # the items paint the original: all items first
+    org = np.ascontiguousarray(org)
+    cost = np.array(MVP_IDX_COST, np.uint32)
+    items, group, want, out = [], [], [], []
+    for gi, ((flags, n_ref, l1to0), its) in enumerate(zip(GROUPS, groups)):
+        D.auref_open(p(planes), N_PLANES, W, H, bd, C.c_double(lam), flags[2], p(cost))
+        for it in its:
+            r, o = ref_loop(D, org, it, flags, n_ref, l1to0)
+            items.append(it); group.append(gi); want.append(r); out.append(o)
+    generated = sum(len(g) for g in groups)
+    assert len(items) == generated                                                   # nothing is dropped
+    return (planes, org, np.array(items, dtype=abi.AFFINE_UNIPRED_ITEM), np.array(group, np.int32), lam, np.array(want, dtype=abi.AFFINE_UNIPRED_RESULT),
+            np.array(out, dtype=abi.AFFINE_BIPRED_ITEM), generated)
+
+
+def check_set(bd, planes, org, items, group, lam, want, out):
+    """the restatement reproduces every reference result and out-item (and supplies `steps`); the set holds the cases the tests rely on"""
+    pp = uc.pad(planes)
+    seen = set()
+    for gi, (flags, n_ref, l1to0) in enumerate(GROUPS):
+        cfg = uc.cfg_dict(lam, W, H, bd, n_ref=n_ref, ref_plane=REF_PLANE, list1_to_list0=l1to0, mvp_idx_cost=MVP_IDX_COST, **dict(zip(uc.GOLDEN_FLAGS, flags)))
+        s = uc.Searcher(org, pp, cfg)
+        for i in np.nonzero(group == gi)[0]:
+            f = set()
+            res, o = s.search(items[i], f)
+            got = res.copy()
+            got["s"]["steps"] = 0
+            assert got.tobytes() == want[i].tobytes(), (bd, i, got, want[i])
+            assert o.tobytes() == out[i].tobytes(), (bd, i, o, out[i])
+            want[i] = res
+            seen |= f | uc.golden_facts(org, cfg, items[i], res, f)
+    assert uc.GOLDEN_NEED <= seen, (bd, uc.GOLDEN_NEED - seen)
+    return seen
+
+
+def main():
+    D = driver()
+    data = {}
+    for bd in (10, 8):
+        rng = np.random.default_rng(int(os.environ.get("SEED", "7301")) + bd)
+        planes, org, items, group, lam, want, out, generated = build_set(D, bd, rng)
+        check_set(bd, planes, org, items, group, lam, want, out)
+        k = "bd%d_" % bd
+        data.update({k + "planes": planes, k + "org": org, k + "items": items, k + "group": group, k + "lambda": np.float64(lam),
+                     k + "g_flags": np.array([g[0] for g in GROUPS], np.int32), k + "g_n_ref": np.array([g[1] for g in GROUPS], np.int32),
+                     k + "g_ref_plane": np.array([REF_PLANE] * len(GROUPS), np.int32), k + "g_list1_to_list0": np.array([g[2] for g in GROUPS], np.int32),
+                     k + "mvp_idx_cost": np.array(MVP_IDX_COST, np.uint32), k + "want": want, k + "out": out, k + "generated": np.int32(generated)})
+        sr = want["s"]["searched"]
+        print("bit depth %d: %d items, searches %d, shortcuts %d, skipped %d, starts %s" % (bd, len(items), int((sr == 1).sum()), int((sr == 2).sum()),
+              int((sr == 0).sum()), np.bincount(want["s"]["start"][sr == 1], minlength=3)))
+    path = os.path.join(HERE, "affine_unipred.npz")
+    np.savez_compressed(path, **data)
+    print("wrote", path, os.path.getsize(path), "bytes")
+    assert os.path.getsize(path) <= 500 * 1024                                   # about 500 KB at the most, like its siblings
+
+
+if __name__ == "__main__":
+    main()

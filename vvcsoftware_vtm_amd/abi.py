@@ -208,6 +208,30 @@ class AffineBipredCfg(C.Structure):
                 ("max_pu_w", C.c_int32), ("max_pu_h", C.c_int32), ("reserved", C.c_int32 * 3)]
 
 
+# vvcgpu_affine_unipred_me_batch: one (list, reference index) of an item, one PU, one (list, reference index) of a result, the result of a PU
+AFFINE_UNIPRED_MAX_REFS = 4
+AFFINE_UNIPRED_REF = np.dtype([("mv_cand", "<i4", (2, 3, 2)), ("hevc_mv", "<i4", (2,)), ("mv4", "<i4", (2, 2)), ("num_cand", "<i2"), ("reserved0", "<i2"),
+                               ("reserved1", "<i4")])
+AFFINE_UNIPRED_ITEM = np.dtype([("pos_x", "<i4"), ("pos_y", "<i4"), ("w", "<i2"), ("h", "<i2"), ("six_param", "<i2"), ("reserved0", "<i2"), ("org_off", "<i8"),
+                                ("org_stride", "<i4"), ("mb_bits", "<u4", (3,)), ("only_ref", "<i4", (2,)),
+                                ("ref", AFFINE_UNIPRED_REF, (2, AFFINE_UNIPRED_MAX_REFS))])
+AFFINE_UNIPRED_SEARCH = np.dtype([("mv", "<i4", (3, 2)), ("mvp_idx", "<i4"), ("bits", "<u4"), ("cost", "<u8"), ("tmpl_cost", "<u8", (2,)), ("start_cost", "<u8"),
+                                  ("inherit_cost", "<u8"), ("start", "<i4"), ("steps", "<u4"), ("searched", "<i4"), ("reserved", "<i4")])
+AFFINE_UNIPRED_RESULT = np.dtype([("s", AFFINE_UNIPRED_SEARCH, (2, AFFINE_UNIPRED_MAX_REFS)), ("ref_idx", "<i4", (2,)), ("mv", "<i4", (2, 3, 2)),
+                                  ("cost", "<u8", (2,)), ("bits", "<u4", (2,)), ("best_bip_ref_idx_l1", "<i4"), ("best_bip_mvp_l1", "<i4"),
+                                  ("best_bip_dist", "<u8"), ("valid_l1_ref_idx", "<i4"), ("valid_l1_mv", "<i4", (3, 2)), ("valid_l1_bits", "<u4"),
+                                  ("valid_l1_cost", "<u8")])
+
+
+class AffineUnipredCfg(C.Structure):
+    """vvcgpu_affine_unipred_cfg"""
+    _fields_ = [("lambda_", C.c_double), ("ref_planes", C.c_void_p * 16), ("n_planes", C.c_int32), ("ref_stride", C.c_int32),
+                ("pic_w", C.c_int32), ("pic_h", C.c_int32), ("max_cu_w", C.c_int32), ("max_cu_h", C.c_int32), ("bit_depth", C.c_int32),
+                ("clp_min", C.c_int32), ("clp_max", C.c_int32), ("n_ref", C.c_int32 * 2), ("ref_plane", (C.c_int32 * AFFINE_UNIPRED_MAX_REFS) * 2),
+                ("list1_to_list0", C.c_int32 * AFFINE_UNIPRED_MAX_REFS), ("fast_me_gen_b_low_delay", C.c_int32), ("mvd_l1_zero", C.c_int32),
+                ("affine_type", C.c_int32), ("mvp_idx_cost", C.c_uint32 * 3), ("max_pu_w", C.c_int32), ("max_pu_h", C.c_int32), ("reserved", C.c_int32)]
+
+
 # ---- encoder picture analysis ---------------------------------------------------------------------------------------------------------------------
 # vvcgpu_tile_stats: one tile of vvcgpu_tile_stats_picture; vvcgpu_wp_sad_cand: one candidate of vvcgpu_wp_sad_batch (flags: WP_SAD_*)
 TILE_STATS = np.dtype([("sa_act", "<u8"), ("sum", "<u8"), ("ss_err", "<u8")])

@@ -50,35 +50,13 @@ __device__ __forceinline__ AbpLds abp_lds(unsigned char* base, int wave, int pix
   return L;
 }
 
-__device__ __forceinline__ unsigned long long abp_getcost(double lambda, unsigned bits) { return (unsigned long long)(lambda * (double)bits); }
 __device__ __forceinline__ unsigned abp_ref_bits(int nRef, int r) { return nRef > 1 ? (unsigned)(r + 1 - (r == nRef - 1 ? 1 : 0)) : 0u; }
 
-// xCheckBestAffineMVP (:3181-3284) with the candidate set `a`: the vector bits (second-predictor rule for vectors 1 and 2) against the current
-// predictors and against the other candidate; on a switch the predictors, the index, the bits (uint32) and the cost (wrapping uint64) follow
+// xCheckBestAffineMVP (afm_dev.h) with the candidate set of the record `a`
 __device__ __forceinline__ void abp_check_best_mvp(const vvcgpu_affine_bipred_ref& a, const vvcgpu_affine_bipred_cfg& c, int nmv, const int (&mv)[3][2],
                                                    int (&pred)[3][2], int& mvpIdx, unsigned& bits, unsigned long long& cost)
 {
-  if (a.num_cand < 2) return;
-  const int orgBits = (int)(afm_bits(0u, pred, nmv, mv) + c.mvp_idx_cost[mvpIdx]);
-  int bestBits = orgBits, bestIdx = mvpIdx;
-  for (int i = 0; i < 2; i++)
-  {
-    if (i == mvpIdx) continue;
-    int cand[3][2];
-#pragma unroll
-    for (int k = 0; k < 3; k++) { cand[k][0] = a.mv_cand[i][k][0]; cand[k][1] = a.mv_cand[i][k][1]; }
-    const int b = (int)(afm_bits(0u, cand, nmv, mv) + c.mvp_idx_cost[i]);
-    if (b < bestBits) { bestBits = b; bestIdx = i; }
-  }
-  if (bestIdx != mvpIdx)
-  {
-#pragma unroll
-    for (int k = 0; k < 3; k++) { pred[k][0] = a.mv_cand[bestIdx][k][0]; pred[k][1] = a.mv_cand[bestIdx][k][1]; }
-    mvpIdx = bestIdx;
-    const unsigned orgB = bits;
-    bits = orgB - (unsigned)orgBits + (unsigned)bestBits;
-    cost = (cost - abp_getcost(c.lambda, orgB)) + abp_getcost(c.lambda, bits);
-  }
+  afm_check_best_mvp(a.mv_cand, a.num_cand, c.mvp_idx_cost, c.lambda, nmv, mv, pred, mvpIdx, bits, cost);
 }
 
 template <int NT>

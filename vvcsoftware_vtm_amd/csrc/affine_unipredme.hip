@@ -1,0 +1,357 @@
+// affine_unipredme.hip -- the whole uni-predictive stage of the affine inter search of a PU (vvcgpu_affine_unipred_me_batch) for gfx950.
+//
+// Reference behaviour reproduced (bit-exact, the double arithmetic of the costs included): the uni-predictive part of
+// InterSearch::xPredAffineInterSearch (EncoderLib/InterSearch.cpp:2651-2814) with xEstimateAffineAMVP (:3745-3794, the caller's candidates) /
+// xGetAffineTemplateCost (:1645-1665, bi = false), the start vectors of :2681-2727 with the 4-to-6-parameter inheritance of :2700-2706,
+// xAffineMotionEstimation (bBi = false, :3286-3743; afm_dev.h), xCheckBestAffineMVP (:3181-3284; afm_dev.h), the list-1 shortcut (:2740-2774), the
+// records of :2788-2812 and the mvd_l1_zero preparation of the bi-predictive stage (:2840-2853) for the out-items.
+//
+// Design: the shape of unipredme.hip.  The (list, reference index) searches of a PU depend on each other only through the list-1 shortcut and the
+// final comparisons, and one gradient search is a chain of dependent predictions, so the unit of ownership is the SEARCH: launch 1 gives each of the
+// n x (n_ref[0] + n_ref[1]) searches an owner -- one wavefront up to AFI_WAVE_MAX samples, the workgroup's four above, the grid split of
+// affine_bipredme.hip.  The owner forms every template-cost prediction (each candidate, the translational start, the inherited start) in the
+// prediction tile of afm_dev.h and reduces its SAD against the original straight from that tile (nothing is written out), chooses the start vectors,
+// runs the gradient search of afm_dev.h unchanged and xCheckBestAffineMVP, and writes its record into the PU's result.  A search that takes list 0's
+// vectors, or that a 6-parameter PU skips, only chooses its predictor.  Launch 2, one lane per PU, walks the records in the reference's order: the
+// list-1 shortcut with its xCheckBestAffineMVP, bestBiP*, keep-if-strictly-better, the valid-list-1 record, the out-item for
+// vvcgpu_affine_bipred_me_batch, and everything a skipped item gets.  Control flow is uniform per owner.  Dynamic LDS, sized on the host from
+// cfg.max_pu_w / max_pu_h.
+#include "common.h"
+#include "afm_dev.h"
+
+namespace {
+
+constexpr int AUP_OFF_TMP = 400;                                                              // behind the 49 equation sums
+constexpr int AUP_TMP_BYTES = 4 * AFM_TMP * 2;                                                // one wavefront's first-pass rows
+constexpr int AUP_HDR_WAVE = (AUP_OFF_TMP + AUP_TMP_BYTES + 15) & ~15;                        // 752: bytes in front of a wavefront owner's tile
+constexpr int AUP_OFF_RED = AUP_OFF_TMP + 4 * AUP_TMP_BYTES;                                  // 1808: the workgroup owner's partial sums
+constexpr int AUP_OFF_DIST = AUP_OFF_RED + 4 * 64 * 8;                                        // 3856
+constexpr int AUP_HDR_GROUP = (AUP_OFF_DIST + 4 * 8 + 15) & ~15;                              // 3888
+static_assert(AUP_OFF_RED % 8 == 0 && AUP_OFF_DIST % 8 == 0, "alignment");
+
+template <int NT>
+__device__ __forceinline__ AfmLds aup_lds(unsigned char* base, int wave)
+{
+  AfmLds L;
+  L.eq = reinterpret_cast<long long*>(base);
+  L.tmpW = reinterpret_cast<short*>(base + AUP_OFF_TMP) + (NT == 256 ? wave * 4 * AFM_TMP : 0);
+  L.red = reinterpret_cast<long long (*)[64]>(base + AUP_OFF_RED);            // NT = 256 only
+  L.distW = reinterpret_cast<unsigned long long*>(base + AUP_OFF_DIST);       // NT = 256 only
+  L.predL = reinterpret_cast<Pel*>(base + (NT == 256 ? AUP_HDR_GROUP : AUP_HDR_WAVE));
+  return L;
+}
+
+inline __host__ __device__ bool aup_side_ok(int v) { return v == 16 || v == 32 || v == 64 || v == 128; }
+
+__device__ __forceinline__ bool aup_item_ok(const vvcgpu_affine_unipred_item& it, const vvcgpu_affine_unipred_cfg& c)
+{
+  const int w = it.w, h = it.h;
+  if (!aup_side_ok(w) || !aup_side_ok(h) || w > c.max_cu_w || h > c.max_cu_h || w > c.max_pu_w || h > c.max_pu_h) return false;
+  if (it.pos_x < 0 || it.pos_y < 0 || it.pos_x > c.pic_w - w || it.pos_y > c.pic_h - h || it.org_stride <= 0) return false;
+  for (int l = 0; l < 2; l++)
+  {
+    if (c.n_ref[l] > 0 && (it.only_ref[l] < -1 || it.only_ref[l] >= c.n_ref[l])) return false;
+    for (int r = 0; r < c.n_ref[l]; r++)
+      if (it.ref[l][r].num_cand < 1 || it.ref[l][r].num_cand > 2) return false;
+  }
+  return true;
+}
+
+__device__ __forceinline__ unsigned aup_ref_bits(int nRef, int r) { return nRef > 1 ? (unsigned)(r + 1 - (r == nRef - 1 ? 1 : 0)) : 0u; }
+// :2673: a 6-parameter PU searches only the reference index its 4-parameter search chose
+__device__ __forceinline__ bool aup_skipped(const vvcgpu_affine_unipred_item& it, int list, int r) { return it.six_param != 0 && it.only_ref[list] != r; }
+// :2740-2746
+__device__ __forceinline__ bool aup_shortcut(const vvcgpu_affine_unipred_item& it, const vvcgpu_affine_unipred_cfg& c, int list, int r)
+{
+  return list == 1 && c.fast_me_gen_b_low_delay && c.list1_to_list0[r] >= 0 && (it.six_param == 0 || c.list1_to_list0[r] == it.only_ref[0]);
+}
+// Mv::roundMV2SignalPrecision of a 1/16-unit component (Mv.h:242-257)
+__device__ __forceinline__ int aup_round_signal(int v) { return (v >= 0 ? (v + 2) >> 2 : -((-v + 2) >> 2)) * 4; }
+
+// xGetAffineTemplateCost without its getCost term: xPredAffineBlk of `mv` into the tile, the SAD against the original from the tile
+template <int NT>
+__device__ __forceinline__ unsigned long long aup_template_sad(const AfmPu& u, const Pel* __restrict__ org, const int (&mv)[3][2], const AfmLds& L, int tid)
+{
+  afm_predict<NT>(u, mv, L.predL, L.tmpW, tid);
+  afm_sync<NT>();
+  const int lgW = ilog2(u.w), pixels = u.w * u.h;
+  unsigned sad = 0;
+  for (int i = tid; i < pixels; i += NT) sad += (unsigned)abs((int)org[(ptrdiff_t)(i >> lgW) * u.os + (i & (u.w - 1))] - (int)L.predL[i]);
+  unsigned long long s = sad;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  if (NT == 256)
+  {
+    if ((tid & 63) == 0) L.distW[tid >> 6] = s;
+    __syncthreads();
+    s = L.distW[0] + L.distW[1] + L.distW[2] + L.distW[3];
+    __syncthreads();                                                     // distW and the tile are written again by the next prediction
+  }
+  else afm_sync<64>();
+  return s;
+}
+
+// one (list, reference index) search of a PU by NT lanes
+template <int NT>
+__device__ __forceinline__ void aup_search(const vvcgpu_affine_unipred_item* __restrict__ itp, const vvcgpu_affine_unipred_cfg& c, const Pel* __restrict__ orgBase,
+                                           const AfmLds& L, int list, int r, vvcgpu_affine_unipred_search* out, int tid)
+{
+  AfmPu u;
+  const bool six = itp->six_param != 0;
+  afm_set_pu(u, itp->pos_x, itp->pos_y, itp->w, itp->h, six, c.pic_w, c.pic_h, c.max_cu_w, c.max_cu_h, c.bit_depth, c.clp_min, c.clp_max);
+  u.os = itp->org_stride; u.rs = c.ref_stride;
+  u.ref = c.ref_planes[c.ref_plane[list][r]] + (ptrdiff_t)u.posY * c.ref_stride + u.posX;
+  const Pel* org = orgBase + itp->org_off;
+  const vvcgpu_affine_unipred_ref& a = itp->ref[list][r];
+
+  const bool skipped = aup_skipped(*itp, list, r), shortcut = !skipped && aup_shortcut(*itp, c, list, r);
+  int four[3][2];                                                        // :2696-2706: the inherited 4-parameter result of a 6-parameter PU
+  four[0][0] = a.mv4[0][0]; four[0][1] = a.mv4[0][1]; four[1][0] = a.mv4[1][0]; four[1][1] = a.mv4[1][1];
+  {
+    const int sh = 7 + ilog2(u.h) - ilog2(u.w);                          // 4..10
+    const int vx2 = (int)(((unsigned)four[0][0] << 7) - ((unsigned)(four[1][1] - four[0][1]) << sh)) >> 7;
+    const int vy2 = (int)(((unsigned)four[0][1] << 7) + ((unsigned)(four[1][0] - four[0][0]) << sh)) >> 7;
+    four[2][0] = aup_round_signal(vx2); four[2][1] = aup_round_signal(vy2);
+  }
+
+  // the template costs, one prediction after the other through one body: candidate 0, candidate 1 (xEstimateAffineAMVP: the best by '>' in
+  // candidate order), then for a search the translational result (:2681-2692) and, for a 6-parameter PU, the inherited result (:2693-2717)
+  unsigned long long tm0 = 0, tm1 = 0, startCost = 0, inheritCost = 0, biPDist = ~0ull;
+  int mvpIdx = 0;
+  const int nT = (skipped || shortcut) ? 2 : (six ? 4 : 3);
+#pragma unroll 1
+  for (int t = 0; t < nT; t++)
+  {
+    if (t == 1 && a.num_cand < 2) continue;
+    int tv[3][2];
+#pragma unroll
+    for (int k = 0; k < 3; k++)
+#pragma unroll
+      for (int d = 0; d < 2; d++) tv[k][d] = t < 2 ? a.mv_cand[t][k][d] : t == 2 ? a.hevc_mv[d] : four[k][d];
+    const unsigned long long v = aup_template_sad<NT>(u, org, tv, L, tid) + afm_getcost(c.lambda, c.mvp_idx_cost[t < 2 ? t : mvpIdx]);
+    if (t < 2)
+    {
+      if (t == 0) tm0 = v; else tm1 = v;
+      if (biPDist > v) { biPDist = v; mvpIdx = t; }
+    }
+    else if (t == 2) startCost = v;
+    else inheritCost = v;
+  }
+  vvcgpu_affine_unipred_search o;
+  memset(&o, 0, sizeof(o));
+  o.tmpl_cost[0] = tm0; o.tmpl_cost[1] = tm1; o.mvp_idx = mvpIdx;
+  if (skipped)                                                           // :2673-2677: the predictor choice is all that is kept
+  {
+    if (tid == 0) *out = o;
+    return;
+  }
+  unsigned bits = itp->mb_bits[list] + aup_ref_bits(c.n_ref[list], r) + c.mvp_idx_cost[mvpIdx];
+  if (shortcut)                                                          // list 0's vectors: the decision step finishes this record
+  {
+    o.bits = bits; o.searched = 2;
+    if (tid == 0) *out = o;
+    return;
+  }
+
+  // :2709-2727: the inherited vectors on strict '<', then that start when its cost is < biPDistTemp, otherwise the predictor
+  const bool inherit = six && inheritCost < startCost;
+  const int sel = (inherit ? inheritCost : startCost) < biPDist ? (inherit ? 2 : 1) : 0;
+  o.start_cost = startCost; o.inherit_cost = inheritCost; o.start = sel;
+  int pred[3][2], start[3][2];
+#pragma unroll
+  for (int k = 0; k < 3; k++)
+#pragma unroll
+    for (int d = 0; d < 2; d++)
+    {
+      pred[k][d] = a.mv_cand[mvpIdx][k][d];
+      start[k][d] = sel == 0 ? pred[k][d] : sel == 1 ? a.hevc_mv[d] : four[k][d];
+    }
+
+  int mv[3][2];
+  unsigned steps;
+  unsigned long long cost;
+  afm_search_body<NT, const Pel*>(u, org, c.lambda, false, c.affine_type, bits, pred, start, L, nullptr, tid, mv, bits, cost, steps);
+  afm_check_best_mvp(a.mv_cand, a.num_cand, c.mvp_idx_cost, c.lambda, u.nmv, mv, pred, mvpIdx, bits, cost);
+  if (tid == 0)
+  {
+#pragma unroll
+    for (int k = 0; k < 3; k++) { o.mv[k][0] = mv[k][0]; o.mv[k][1] = mv[k][1]; }
+    o.mvp_idx = mvpIdx; o.bits = bits; o.cost = cost; o.steps = steps; o.searched = 1;
+    *out = o;
+  }
+}
+
+__global__ __launch_bounds__(256) void affine_unipred_search_kernel(const Pel* __restrict__ orgBase, const vvcgpu_affine_unipred_item* __restrict__ items, int n,
+                                                                    const vvcgpu_affine_unipred_cfg c, int waveBytes,
+                                                                    vvcgpu_affine_unipred_result* __restrict__ results)
+{
+  extern __shared__ __align__(16) unsigned char smem[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // uniform for the compiler too
+  const int S = c.n_ref[0] + c.n_ref[1], total = n * S, nWaveGroups = (total + 3) >> 2;
+  const bool waveOwner = (int)blockIdx.x < nWaveGroups;
+  const int o = waveOwner ? (int)blockIdx.x * 4 + wave : (int)blockIdx.x - nWaveGroups;     // search o = search k of PU b
+  if (o >= total) return;
+  const int b = o / S, k = o - b * S, list = k >= c.n_ref[0] ? 1 : 0, r = list ? k - c.n_ref[0] : k;
+  const vvcgpu_affine_unipred_item* it = items + b;
+  if (!aup_item_ok(*it, c)) return;                                      // the decision step writes the sentinel
+  if ((it->w * it->h <= AFI_WAVE_MAX) != waveOwner) return;              // the other kind of owner serves this item
+  if (waveOwner) aup_search<64>(it, c, orgBase, aup_lds<64>(smem + (size_t)wave * waveBytes, 0), list, r, &results[b].s[list][r], lane);
+  else aup_search<256>(it, c, orgBase, aup_lds<256>(smem, wave), list, r, &results[b].s[list][r], tid);
+}
+
+// per PU: the records of its searches in the reference's order (:2651-2814) -> the result and the out-item
+__global__ __launch_bounds__(256) void affine_unipred_decide_kernel(const vvcgpu_affine_unipred_item* __restrict__ items, int n, const vvcgpu_affine_unipred_cfg c,
+                                                                    vvcgpu_affine_unipred_result* __restrict__ results,
+                                                                    vvcgpu_affine_bipred_item* __restrict__ outItems)
+{
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= n) return;
+  const vvcgpu_affine_unipred_item& it = items[b];
+  vvcgpu_affine_unipred_result* R = results + b;
+  if (!aup_item_ok(it, c))
+  {
+    unsigned long long* z = reinterpret_cast<unsigned long long*>(R);
+    for (unsigned i = 0; i < sizeof(*R) / 8; i++) z[i] = 0;
+    R->cost[0] = R->cost[1] = ~0ull;
+    if (outItems)
+    {
+      z = reinterpret_cast<unsigned long long*>(outItems + b);
+      for (unsigned i = 0; i < sizeof(*outItems) / 8; i++) z[i] = 0;
+    }
+    return;
+  }
+  const int nmv = it.six_param ? 3 : 2;
+  unsigned long long uiCost[2] = { ~0ull, ~0ull }, bestBiPDist = ~0ull, costValid = ~0ull;
+  unsigned uiBits[2] = { 0u, 0u }, bitsValid = 0xFFFFFFFFu;
+  int refIdx[2] = { 0, 0 }, bestBiPRef = 0, bestBiPMvp = 0, refValid = 0;
+  bool found[2] = { false, false }, foundValid = false;
+  for (int list = 0; list < 2; list++)
+    for (int r = 0; r < VVCGPU_AFFINE_UNIPRED_MAX_REFS; r++)
+    {
+      vvcgpu_affine_unipred_search s;
+      if (r >= c.n_ref[list]) { memset(&s, 0, sizeof(s)); R->s[list][r] = s; continue; }
+      s = R->s[list][r];
+      if (s.searched == 0) continue;                                     // :2673-2677, before the bestBiP* update
+      const vvcgpu_affine_unipred_ref& a = it.ref[list][r];
+      const int amvpIdx = (a.num_cand > 1 && s.tmpl_cost[0] > s.tmpl_cost[1]) ? 1 : 0;       // xEstimateAffineAMVP's choice
+      if (c.mvd_l1_zero && list == 1 && s.tmpl_cost[amvpIdx] < bestBiPDist) { bestBiPDist = s.tmpl_cost[amvpIdx]; bestBiPMvp = amvpIdx; bestBiPRef = r; }
+      if (s.searched == 2)                                               // :2747-2774, then xCheckBestAffineMVP
+      {
+        const vvcgpu_affine_unipred_search& s0 = R->s[0][c.list1_to_list0[r]];
+        int mvpIdx = s.mvp_idx, pred[3][2], mv[3][2];
+#pragma unroll
+        for (int k = 0; k < 3; k++) { pred[k][0] = a.mv_cand[mvpIdx][k][0]; pred[k][1] = a.mv_cand[mvpIdx][k][1]; mv[k][0] = s0.mv[k][0]; mv[k][1] = s0.mv[k][1]; }
+        unsigned long long cost = s0.cost;
+        cost -= afm_getcost(c.lambda, s0.bits);
+        unsigned bits = afm_bits(s.bits, pred, nmv, mv);
+        cost += afm_getcost(c.lambda, bits);
+        afm_check_best_mvp(a.mv_cand, a.num_cand, c.mvp_idx_cost, c.lambda, nmv, mv, pred, mvpIdx, bits, cost);
+#pragma unroll
+        for (int k = 0; k < 3; k++) { s.mv[k][0] = mv[k][0]; s.mv[k][1] = mv[k][1]; }
+        s.mvp_idx = mvpIdx; s.bits = bits; s.cost = cost;
+        R->s[list][r] = s;
+      }
+      if (s.cost < uiCost[list]) { uiCost[list] = s.cost; uiBits[list] = s.bits; refIdx[list] = r; found[list] = true; }
+      if (list == 1 && s.cost < costValid && c.list1_to_list0[r] < 0) { costValid = s.cost; bitsValid = s.bits; refValid = r; foundValid = true; }
+    }
+  for (int l = 0; l < 2; l++)
+  {
+    R->ref_idx[l] = refIdx[l]; R->cost[l] = uiCost[l]; R->bits[l] = uiBits[l];
+    for (int k = 0; k < 3; k++) { R->mv[l][k][0] = found[l] ? R->s[l][refIdx[l]].mv[k][0] : 0; R->mv[l][k][1] = found[l] ? R->s[l][refIdx[l]].mv[k][1] : 0; }
+  }
+  R->best_bip_ref_idx_l1 = bestBiPRef; R->best_bip_mvp_l1 = bestBiPMvp; R->best_bip_dist = bestBiPDist;
+  R->valid_l1_ref_idx = refValid; R->valid_l1_bits = bitsValid; R->valid_l1_cost = costValid;
+  for (int k = 0; k < 3; k++) { R->valid_l1_mv[k][0] = foundValid ? R->s[1][refValid].mv[k][0] : 0; R->valid_l1_mv[k][1] = foundValid ? R->s[1][refValid].mv[k][1] : 0; }
+  if (!outItems) return;
+
+  vvcgpu_affine_bipred_item* o = outItems + b;                           // every byte of the record is written
+  o->pos_x = it.pos_x; o->pos_y = it.pos_y; o->w = it.w; o->h = it.h; o->six_param = it.six_param; o->reserved0 = 0;
+  o->org_off = it.org_off; o->org_stride = it.org_stride; o->reserved1 = 0; o->reserved2 = 0;
+  for (int i = 0; i < 3; i++) o->mb_bits[i] = it.mb_bits[i];
+  for (int l = 0; l < 2; l++)
+  {
+    o->n_ref[l] = c.n_ref[l]; o->ref_idx[l] = refIdx[l]; o->cost[l] = uiCost[l]; o->bits[l] = uiBits[l]; o->only_ref[l] = it.only_ref[l];
+    for (int k = 0; k < 3; k++) { o->mv[l][k][0] = R->mv[l][k][0]; o->mv[l][k][1] = R->mv[l][k][1]; }
+    for (int r = 0; r < VVCGPU_AFFINE_BIPRED_MAX_REFS; r++)
+    {
+      vvcgpu_affine_bipred_ref q;
+      memset(&q, 0, sizeof(q));
+      if (r < c.n_ref[l])
+      {
+        const vvcgpu_affine_unipred_ref& a = it.ref[l][r];
+        q.plane = c.ref_plane[l][r]; q.num_cand = a.num_cand; q.mvp_idx = (int16_t)R->s[l][r].mvp_idx;
+        for (int k = 0; k < 3; k++)
+        {
+          q.mv[k][0] = R->s[l][r].mv[k][0]; q.mv[k][1] = R->s[l][r].mv[k][1];
+          for (int i = 0; i < 2; i++) { q.mv_cand[i][k][0] = a.mv_cand[i][k][0]; q.mv_cand[i][k][1] = a.mv_cand[i][k][1]; }
+        }
+        if (c.mvd_l1_zero && l == 1 && r == bestBiPRef)                  // :2840-2853
+        {
+          q.mvp_idx = (int16_t)bestBiPMvp;
+          for (int k = 0; k < 3; k++)
+          {
+            q.mv[k][0] = a.mv_cand[bestBiPMvp][k][0]; q.mv[k][1] = a.mv_cand[bestBiPMvp][k][1];
+            o->mv[1][k][0] = q.mv[k][0]; o->mv[1][k][1] = q.mv[k][1];
+          }
+          o->ref_idx[1] = bestBiPRef;
+        }
+      }
+      o->ref[l][r] = q;
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" int vvcgpu_affine_unipred_me_batch(const vvc_pel* org_base, const vvcgpu_affine_unipred_item* items, int n, const vvcgpu_affine_unipred_cfg* cfg_host,
+                                              vvcgpu_affine_unipred_result* results, vvcgpu_affine_bipred_item* bipred_items_out, void* stream)
+{
+  VVC_CHECK_ARG(n >= 0, "affine_unipred_me_batch: n %d", n);
+  if (n == 0) return VVCGPU_OK;
+  VVC_CHECK_ARG(org_base && items && cfg_host && results, "affine_unipred_me_batch: null pointer");
+  vvcgpu_affine_unipred_cfg c = *cfg_host;
+  VVC_CHECK_ARG(c.n_planes >= 1 && c.n_planes <= 16, "affine_unipred_me_batch: n_planes %d outside 1..16", c.n_planes);
+  for (int i = 0; i < c.n_planes; i++) VVC_CHECK_ARG(c.ref_planes[i], "affine_unipred_me_batch: null pointer (ref_planes[%d])", i);
+  VVC_CHECK_ARG(c.pic_w > 0 && c.pic_h > 0 && c.max_cu_w > 0 && c.max_cu_h > 0 && c.ref_stride > 0,
+                "affine_unipred_me_batch: geometry (picture %d x %d, CTU %d x %d, ref_stride %d)", c.pic_w, c.pic_h, c.max_cu_w, c.max_cu_h, c.ref_stride);
+  VVC_CHECK_ARG(c.pic_w <= 65536 && c.pic_h <= 65536 && c.max_cu_w <= 256 && c.max_cu_h <= 256, "affine_unipred_me_batch: geometry (picture %d x %d, CTU %d x %d)",
+                c.pic_w, c.pic_h, c.max_cu_w, c.max_cu_h);
+  VVC_CHECK_ARG(c.clp_min <= c.clp_max && c.clp_min >= -32768 && c.clp_max <= 32767, "affine_unipred_me_batch: clip range %d..%d", c.clp_min, c.clp_max);
+  VVC_CHECK_ARG(c.lambda >= 0.0 && c.lambda < 1048576.0, "affine_unipred_me_batch: lambda out of range");
+  VVC_CHECK_ARG(c.n_ref[0] >= 1 && c.n_ref[0] <= VVCGPU_AFFINE_UNIPRED_MAX_REFS && c.n_ref[1] >= 0 && c.n_ref[1] <= VVCGPU_AFFINE_UNIPRED_MAX_REFS,
+                "affine_unipred_me_batch: n_ref %d, %d (list 0: 1..4, list 1: 0..4)", c.n_ref[0], c.n_ref[1]);
+  for (int l = 0; l < 2; l++)
+    for (int r = 0; r < c.n_ref[l]; r++)
+      VVC_CHECK_ARG(c.ref_plane[l][r] >= 0 && c.ref_plane[l][r] < c.n_planes, "affine_unipred_me_batch: ref_plane[%d][%d] %d outside [0, %d)", l, r, c.ref_plane[l][r],
+                    c.n_planes);
+  for (int r = 0; r < c.n_ref[1]; r++)
+    VVC_CHECK_ARG(c.list1_to_list0[r] >= -1 && c.list1_to_list0[r] < c.n_ref[0], "affine_unipred_me_batch: list1_to_list0[%d] %d outside [-1, %d)", r, c.list1_to_list0[r],
+                  c.n_ref[0]);
+  if (c.max_pu_w == 0) c.max_pu_w = 128;
+  if (c.max_pu_h == 0) c.max_pu_h = 128;
+  VVC_CHECK_ARG(aup_side_ok(c.max_pu_w) && aup_side_ok(c.max_pu_h), "affine_unipred_me_batch: max_pu %d x %d (sides 16, 32, 64, 128, or 0)", c.max_pu_w, c.max_pu_h);
+  if (c.bit_depth > 10 || c.bit_depth < 8) { vvcgpu_set_error("affine_unipred_me_batch: bit depth %d outside 8..10", c.bit_depth); return VVCGPU_E_UNSUPPORTED; }
+  const int S = c.n_ref[0] + c.n_ref[1];
+  VVC_CHECK_ARG(n < (1 << 27) / S, "affine_unipred_me_batch: n %d", n);
+  for (int i = c.n_planes; i < 16; i++) c.ref_planes[i] = nullptr;
+  // LDS of an owner: its header and the tile of the largest served shape within max_pu that the owner kind takes
+  int wavePix = 0, groupPix = 0;
+  for (int w = 16; w <= c.max_pu_w; w <<= 1)
+    for (int h = 16; h <= c.max_pu_h; h <<= 1)
+    {
+      int& dst = w * h <= AFI_WAVE_MAX ? wavePix : groupPix;
+      if (w * h > dst) dst = w * h;
+    }
+  const int waveBytes = AUP_HDR_WAVE + 2 * wavePix;
+  const int groupBytes = groupPix ? AUP_HDR_GROUP + 2 * groupPix : 0;
+  const size_t lds = (size_t)(4 * waveBytes > groupBytes ? 4 * waveBytes : groupBytes);
+  const int total = n * S;
+  hipStream_t st = (hipStream_t)stream;
+  VVC_HIP(vvc_allow_lds(affine_unipred_search_kernel, lds));
+  const int groupOwners = groupPix ? total : 0;                          // no served item is workgroup-owned when max_pu says so
+  hipLaunchKernelGGL(affine_unipred_search_kernel, dim3(cdiv(total, 4) + groupOwners), dim3(256), lds, st, org_base, items, n, c, waveBytes, results);
+  VVC_LAUNCH_CHECK();
+  hipLaunchKernelGGL(affine_unipred_decide_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, items, n, c, results, bipred_items_out);
+  VVC_LAUNCH_CHECK();
+  return VVCGPU_OK;
+}

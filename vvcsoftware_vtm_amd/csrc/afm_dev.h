@@ -1,6 +1,6 @@
-// afm_dev.h -- device functions of the whole affine gradient search shared by vvcgpu_affine_me_batch (affine_me.hip) and the affine bi-predictive
-// search (affine_bipredme.hip): the 4x4 sub-block prediction into an LDS tile, the vector bits, the Hadamard distortion, the solve and the search
-// body.  Reference behaviour: see affine_me.hip.  The original of a search is read through OrgPtr: a plain pointer (global memory) or AfiLdsPel (the
+// afm_dev.h -- device functions of the whole affine gradient search shared by vvcgpu_affine_me_batch (affine_me.hip), the affine bi-predictive
+// search (affine_bipredme.hip) and the affine uni-predictive stage (affine_unipredme.hip): the 4x4 sub-block prediction into an LDS tile, the
+// vector bits, xCheckBestAffineMVP, the Hadamard distortion, the solve and the search body.  Reference behaviour: see affine_me.hip.  The original of a search is read through OrgPtr: a plain pointer (global memory) or AfiLdsPel (the
 // bi-predictive search key, which lives in LDS) -- a template parameter, so no sample pays a run-time choice.
 #pragma once
 #include "common.h"
@@ -235,6 +235,38 @@ __device__ __forceinline__ unsigned afm_bits(unsigned bits, const int (&mvp)[3][
     bits += expgolomb_bits((mv[i][0] >> 2) - (px >> 2)) + expgolomb_bits((mv[i][1] >> 2) - (py >> 2));
   }
   return bits;
+}
+
+// getCost (RdCost.h:172-199)
+__device__ __forceinline__ unsigned long long afm_getcost(double lambda, unsigned bits) { return (unsigned long long)(lambda * (double)bits); }
+
+// xCheckBestAffineMVP (:3181-3284) with the candidate set `cand` of `numCand` candidates: the vector bits (second-predictor rule for vectors 1 and 2)
+// against the current predictors and against the other candidate; on a switch the predictors, the index, the bits (uint32) and the cost (wrapping
+// uint64) follow
+__device__ __forceinline__ void afm_check_best_mvp(const int32_t (&cand)[2][3][2], int numCand, const uint32_t (&mvpIdxCost)[3], double lambda, int nmv,
+                                                   const int (&mv)[3][2], int (&pred)[3][2], int& mvpIdx, unsigned& bits, unsigned long long& cost)
+{
+  if (numCand < 2) return;
+  const int orgBits = (int)(afm_bits(0u, pred, nmv, mv) + mvpIdxCost[mvpIdx]);
+  int bestBits = orgBits, bestIdx = mvpIdx;
+  for (int i = 0; i < 2; i++)
+  {
+    if (i == mvpIdx) continue;
+    int cd[3][2];
+#pragma unroll
+    for (int k = 0; k < 3; k++) { cd[k][0] = cand[i][k][0]; cd[k][1] = cand[i][k][1]; }
+    const int b = (int)(afm_bits(0u, cd, nmv, mv) + mvpIdxCost[i]);
+    if (b < bestBits) { bestBits = b; bestIdx = i; }
+  }
+  if (bestIdx != mvpIdx)
+  {
+#pragma unroll
+    for (int k = 0; k < 3; k++) { pred[k][0] = cand[bestIdx][k][0]; pred[k][1] = cand[bestIdx][k][1]; }
+    mvpIdx = bestIdx;
+    const unsigned orgB = bits;
+    bits = orgB - (unsigned)orgBits + (unsigned)bestBits;
+    cost = (cost - afm_getcost(lambda, orgB)) + afm_getcost(lambda, bits);
+  }
 }
 
 struct AfmLds

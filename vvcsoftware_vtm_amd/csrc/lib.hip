@@ -335,6 +335,11 @@ int vvcgpu_sizeof(int id)
   case 52: return (int)sizeof(vvcgpu_unipred_me_cfg);
   case 53: return (int)sizeof(vvcgpu_unipred_me_search);
   case 54: return (int)sizeof(vvcgpu_unipred_me_result);
+  case 56: return (int)sizeof(vvcgpu_affine_unipred_ref);
+  case 57: return (int)sizeof(vvcgpu_affine_unipred_item);
+  case 58: return (int)sizeof(vvcgpu_affine_unipred_cfg);
+  case 59: return (int)sizeof(vvcgpu_affine_unipred_search);
+  case 60: return (int)sizeof(vvcgpu_affine_unipred_result);
   default: return -1;
   }
 }

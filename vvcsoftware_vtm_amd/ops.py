@@ -13,8 +13,8 @@ from .abi import (AFE_DESC, AFFINE_ITER, AFFINE_ME_ITEM, AFFINE_ME_MAX_STEPS, AF
                   RDOQ_DESC, RDOQ_RATES, RDPCM_DESC, SAO_DTYPE, SEARCH_BEST, SEARCH_BLK, TR_DESC, TZ_CFG, TZ_PU, DeblockCfg, MeHierCfg, MvCost,
                   PelopCfg, Planes, AffineMeCfg, BipredMeCfg, BIPRED_ME_ITEM, BIPRED_ME_MAX_PLANES, BIPRED_ME_MAX_REFS, BIPRED_ME_MAX_STEPS, BIPRED_ME_REF,
                   BIPRED_ME_RESULT, BIPRED_ME_STEP, AffineBipredCfg, AFFINE_BIPRED_ITEM, AFFINE_BIPRED_MAX_REFS, AFFINE_BIPRED_MAX_STEPS,
-                  AFFINE_BIPRED_REF, AFFINE_BIPRED_RESULT, AFFINE_BIPRED_STEP, UnipredMeCfg, UNIPRED_ME_MAX_PLANES, UNIPRED_ME_MAX_REFS,
-                  UNIPRED_ME_RESULT, WP_PARAM, TILE_STATS, WP_SAD_CAND, WP_SAD_HIGH_PRECISION, WP_SAD_CLIPPED)
+                  AFFINE_BIPRED_REF, AFFINE_BIPRED_RESULT, AFFINE_BIPRED_STEP, AffineUnipredCfg, AFFINE_UNIPRED_MAX_REFS, AFFINE_UNIPRED_RESULT,
+                  UnipredMeCfg, UNIPRED_ME_MAX_PLANES, UNIPRED_ME_MAX_REFS, UNIPRED_ME_RESULT, WP_PARAM, TILE_STATS, WP_SAD_CAND, WP_SAD_HIGH_PRECISION, WP_SAD_CLIPPED)
 
 
 def _stream():
@@ -628,6 +628,44 @@ def affine_bipred_me_batch(org_base, items_dev, n, cfg, want_trace=True):
     capi.call("vvcgpu_affine_bipred_me_batch", capi.ptr(org_base), capi.ptr(items_dev), n, C.byref(cfg), capi.ptr(res),
               capi.ptr(trace) if want_trace else None, _stream())
     return res, trace
+
+
+def affine_unipred_cfg(lambda_, ref_planes, ref_origin, pic_w, pic_h, n_ref, ref_plane, bit_depth=10, clp=(0, 1023), list1_to_list0=(-1, -1, -1, -1),
+                       fast_me_gen_b_low_delay=False, mvd_l1_zero=False, affine_type=1, mvp_idx_cost=(1, 1, 0), max_cu=128, max_pu=(0, 0)):
+    """vvcgpu_affine_unipred_cfg of one slice.  ref_planes: the PADDED reference luma planes (2-D int16 CUDA tensors of one stride; keep them alive while
+    calls that use the cfg run); ref_origin = (x, y) of picture sample (0, 0) inside each of them; n_ref = (list 0, list 1) reference counts,
+    ref_plane = per list the plane index of every reference index"""
+    cfg = AffineUnipredCfg()
+    cfg.lambda_ = lambda_
+    assert 1 <= len(ref_planes) <= 16
+    for i, t in enumerate(ref_planes):
+        ptr, stride, _, _ = _plane(t, "ref_planes[%d]" % i)
+        assert stride == ref_planes[0].stride(0), "reference planes of one stride"
+        cfg.ref_planes[i] = ptr.value + 2 * (ref_origin[1] * stride + ref_origin[0])
+    cfg.n_planes, cfg.ref_stride = len(ref_planes), ref_planes[0].stride(0)
+    cfg.pic_w, cfg.pic_h, cfg.max_cu_w, cfg.max_cu_h = pic_w, pic_h, max_cu, max_cu
+    cfg.bit_depth, cfg.clp_min, cfg.clp_max = bit_depth, clp[0], clp[1]
+    cfg.n_ref[:] = n_ref
+    for l in range(2):
+        for r in range(min(n_ref[l], AFFINE_UNIPRED_MAX_REFS)):
+            cfg.ref_plane[l][r] = ref_plane[l][r]
+    cfg.list1_to_list0[:] = (tuple(list1_to_list0) + (-1,) * AFFINE_UNIPRED_MAX_REFS)[:AFFINE_UNIPRED_MAX_REFS]
+    cfg.fast_me_gen_b_low_delay, cfg.mvd_l1_zero, cfg.affine_type = int(fast_me_gen_b_low_delay), int(mvd_l1_zero), int(affine_type)
+    cfg.mvp_idx_cost[:] = mvp_idx_cost
+    cfg.max_pu_w, cfg.max_pu_h = max_pu
+    return cfg
+
+
+def affine_unipred_me_batch(org_base, items_dev, n, cfg, want_bipred_items=True):
+    """The uni-predictive stage of xPredAffineInterSearch for n independent PUs, two launches and no host synchronisation: items_dev =
+    AFFINE_UNIPRED_ITEM records on the device, cfg = affine_unipred_cfg(...).  -> (AFFINE_UNIPRED_RESULT records, AFFINE_BIPRED_ITEM records ready for
+    affine_bipred_me_batch or None), uint8 tensors"""
+    assert isinstance(cfg, AffineUnipredCfg)
+    res = torch.empty(n * AFFINE_UNIPRED_RESULT.itemsize, dtype=torch.uint8, device=org_base.device)
+    out = torch.empty(n * AFFINE_BIPRED_ITEM.itemsize, dtype=torch.uint8, device=org_base.device) if want_bipred_items else None
+    capi.call("vvcgpu_affine_unipred_me_batch", capi.ptr(org_base), capi.ptr(items_dev), n, C.byref(cfg), capi.ptr(res),
+              capi.ptr(out) if want_bipred_items else None, _stream())
+    return res, out
 
 
 def affine_pred_batch(ref0_base, ref1_base, dst_base, pus_dev, n, n_subblocks, comp, pic_w, pic_h, ref_origin, ref0_stride, ref1_stride,
