@@ -6,28 +6,24 @@
 // PU::setAllAffineMv leaves in the corners of the motion buffer (UnitTools.cpp:2319-2330; no clipMv of them), xPredAffineBlk (:550-722) with
 // bi = false; PelBuf::removeHighFreq (Buffer.h:389-416); RdCost::getBitsOfVectorWithPredictor / getCost (RdCost.h:172-199).
 //
-// Design: the owner model of affine_me.hip and bipredme.hip -- cdiv(n, 4) workgroups of four wavefront owners (PUs up to AFI_WAVE_MAX samples), then n
-// workgroup owners; an item is served by exactly one of the two, by its size; no work list, no atomics.  The owner carries its PU through every
-// iteration.  Per owner LDS holds two Pel tiles: the prediction tile of the search (afm_dev.h) and the search key.  What an iteration needs of the
-// lists' predictions is only the OTHER list's, and only to form the key 2 org - otherPred: it is formed in the prediction tile when the iteration starts
-// (the reference forms it at :2913-2920 and again after each acceptance, :2970-2977, which the iteration never reads) and turned into the key in the
-// second tile; every search of the iteration then reads the key where afm_dev.h's passes read an original, through an LDS-qualified pointer.  Dynamic
-// LDS, sized on the host from cfg.max_pu_w / max_pu_h.  Control flow is uniform per owner: every lane computes the same scalar state; the
-// per-(list, reference) state that is indexed dynamically (cMvTemp, aaiMvpIdxBi, cMvPredBi) lives in LDS.
+// Design: the owner of a PU -- one wavefront up to AFI_WAVE_MAX samples, the workgroup's four above -- carries it through every iteration (the owner
+// model: owner_dev.h and docs/KERNELS.md, "Owners of the whole-PU entries").  Per owner LDS holds two Pel tiles: the prediction tile of the search
+// (afm_dev.h) and the search key.  What an iteration needs of the lists' predictions is only the OTHER list's, and only to form the key 2 org -
+// otherPred: it is formed in the prediction tile when the iteration starts (the reference forms it at :2913-2920 and again after each acceptance,
+// :2970-2977, which the iteration never reads) and turned into the key in the second tile; every search of the iteration then reads the key where
+// afm_dev.h's passes read an original, through an LDS-qualified pointer.  Dynamic LDS, sized on the host from cfg.max_pu_w / max_pu_h.  Control flow
+// is uniform per owner: every lane computes the same scalar state; the per-(list, reference) state that is indexed dynamically (cMvTemp, aaiMvpIdxBi,
+// cMvPredBi) lives in LDS.
 #include "common.h"
 #include "afm_dev.h"
+#include "pu_entry_host.h"
 
 namespace {
 
 constexpr int ABP_ST = 13;                 // ints of state per (list, reference): cMvTemp[3][2], aaiMvpIdxBi, cMvPredBi[3][2]
-constexpr int ABP_OFF_ST = 400;            // behind the 49 equation sums
-constexpr int ABP_OFF_TMP = ABP_OFF_ST + 2 * VVCGPU_AFFINE_BIPRED_MAX_REFS * ABP_ST * 4;      // 816
-constexpr int ABP_TMP_BYTES = 4 * AFM_TMP * 2;                                                   // one wavefront's first-pass rows
-constexpr int ABP_HDR_WAVE = (ABP_OFF_TMP + ABP_TMP_BYTES + 15) & ~15;                           // 1168: bytes in front of a wavefront owner's tiles
-constexpr int ABP_OFF_RED = ABP_OFF_TMP + 4 * ABP_TMP_BYTES;                                     // 2224: the workgroup owner's partial sums
-constexpr int ABP_OFF_DIST = ABP_OFF_RED + 4 * 64 * 8;                                           // 4272
-constexpr int ABP_HDR_GROUP = (ABP_OFF_DIST + 4 * 8 + 15) & ~15;                                 // 4304
-static_assert(ABP_OFF_RED % 8 == 0 && ABP_OFF_DIST % 8 == 0, "alignment");
+constexpr int ABP_ST_BYTES = 2 * VVCGPU_AFFINE_BIPRED_MAX_REFS * ABP_ST * 4;
+typedef AfmHdr<ABP_ST_BYTES> AbpHdr;       // the header of afm_dev.h with the state block behind the equation sums
+static_assert(AbpHdr::WAVE == 1168 && AbpHdr::GROUP == 4304, "header sizes");
 
 struct AbpLds
 {
@@ -40,17 +36,11 @@ template <int NT>
 __device__ __forceinline__ AbpLds abp_lds(unsigned char* base, int wave, int pixels)
 {
   AbpLds L;
-  L.A.eq = reinterpret_cast<long long*>(base);
-  L.st = reinterpret_cast<int*>(base + ABP_OFF_ST);
-  L.A.tmpW = reinterpret_cast<short*>(base + ABP_OFF_TMP) + (NT == 256 ? wave * 4 * AFM_TMP : 0);
-  L.A.red = reinterpret_cast<long long (*)[64]>(base + ABP_OFF_RED);          // NT = 256 only
-  L.A.distW = reinterpret_cast<unsigned long long*>(base + ABP_OFF_DIST);     // NT = 256 only
-  L.A.predL = reinterpret_cast<Pel*>(base + (NT == 256 ? ABP_HDR_GROUP : ABP_HDR_WAVE));
+  L.A = afm_lds<NT, ABP_ST_BYTES>(base, wave);
+  L.st = reinterpret_cast<int*>(base + AFM_OFF_STATE);
   L.key = L.A.predL + pixels;
   return L;
 }
-
-__device__ __forceinline__ unsigned abp_ref_bits(int nRef, int r) { return nRef > 1 ? (unsigned)(r + 1 - (r == nRef - 1 ? 1 : 0)) : 0u; }
 
 // xCheckBestAffineMVP (afm_dev.h) with the candidate set of the record `a`
 __device__ __forceinline__ void abp_check_best_mvp(const vvcgpu_affine_bipred_ref& a, const vvcgpu_affine_bipred_cfg& c, int nmv, const int (&mv)[3][2],
@@ -90,7 +80,7 @@ __device__ __forceinline__ void abp_search(const vvcgpu_affine_bipred_item* __re
     }
     s[6] = k;
   }
-  afm_sync<NT>();
+  owner_sync<NT>();
 
   int mvBi[2][3][2];
 #pragma unroll
@@ -104,7 +94,7 @@ __device__ __forceinline__ void abp_search(const vvcgpu_affine_bipred_item* __re
     }
   unsigned motBits[2];
   motBits[0] = itp->bits[0] - itp->mb_bits[0];
-  if (c.mvd_l1_zero) motBits[1] = itp->mb_bits[1] + abp_ref_bits(nRef[1], refBi[1]) + c.mvp_idx_cost[L.st[(4 + refBi[1]) * ABP_ST + 6]];       // :2864-2874
+  if (c.mvd_l1_zero) motBits[1] = itp->mb_bits[1] + pu_ref_bits(nRef[1], refBi[1]) + c.mvp_idx_cost[L.st[(4 + refBi[1]) * ABP_ST + 6]];        // :2864-2874
   else motBits[1] = itp->bits[1] - itp->mb_bits[1];
   unsigned bits2 = mbBits2 + motBits[0] + motBits[1];
   unsigned long long costBi = ~0ull;
@@ -120,14 +110,14 @@ __device__ __forceinline__ void abp_search(const vvcgpu_affine_bipred_item* __re
     // the other list's prediction into the first tile, the key from it into the second
     u.ref = c.ref_planes[itp->ref[other][refBi[other]].plane] + puOff;
     afm_predict<NT>(u, mvBi[other], L.A.predL, L.A.tmpW, tid);
-    afm_sync<NT>();
+    owner_sync<NT>();
     for (int i = tid; i < pixels; i += NT)
     {
       const int y = i / u.w, x = i - y * u.w;
       const int k2 = 2 * (int)org[(ptrdiff_t)y * os + x] - (int)L.A.predL[i];
       L.key[i] = (Pel)(c.clip_for_bipred_me ? clip3(c.clp_min, c.clp_max, k2) : k2);
     }
-    afm_sync<NT>();
+    owner_sync<NT>();
 
     bool changed = false;
     for (int r = 0; r < nRef[list]; r++)
@@ -139,13 +129,13 @@ __device__ __forceinline__ void abp_search(const vvcgpu_affine_bipred_item* __re
 #pragma unroll
       for (int i = 0; i < 3; i++) { start[i][0] = s[2 * i]; start[i][1] = s[2 * i + 1]; pred[i][0] = s[7 + 2 * i]; pred[i][1] = s[8 + 2 * i]; }
       int mvpIdx = s[6];
-      unsigned bitsT = mbBits2 + motBits[other] + abp_ref_bits(nRef[list], r) + c.mvp_idx_cost[mvpIdx];     // :2944-2953
+      unsigned bitsT = mbBits2 + motBits[other] + pu_ref_bits(nRef[list], r) + c.mvp_idx_cost[mvpIdx];      // :2944-2953
       u.ref = c.ref_planes[a.plane] + puOff;
       unsigned steps;
       unsigned long long costT;
       afm_search_body<NT, AfiLdsPel>(u, (AfiLdsPel)L.key, c.lambda, true, c.affine_type, bitsT, pred, start, L.A, nullptr, tid, mv, bitsT, costT, steps);
       abp_check_best_mvp(a, c, u.nmv, mv, pred, mvpIdx, bitsT, costT);
-      afm_sync<NT>();                                                      // every lane has read st
+      owner_sync<NT>();                                                    // every lane has read st
       if (tid == 0)
       {
 #pragma unroll
@@ -173,7 +163,7 @@ __device__ __forceinline__ void abp_search(const vvcgpu_affine_bipred_item* __re
         motBits[list] = bitsT - mbBits2 - motBits[other];
         bits2 = bitsT;
       }
-      afm_sync<NT>();                                                      // st is written before anyone reads it again
+      owner_sync<NT>();                                                    // st is written before anyone reads it again
     }
     if (!changed)
     {
@@ -188,14 +178,14 @@ __device__ __forceinline__ void abp_search(const vvcgpu_affine_bipred_item* __re
           for (int i = 0; i < 3; i++) { pred[i][0] = s[7 + 2 * i]; pred[i][1] = s[8 + 2 * i]; }
           int mvpIdx = s[6];
           abp_check_best_mvp(itp->ref[l][refBi[l]], c, u.nmv, mvBi[l], pred, mvpIdx, bits2, costBi);
-          afm_sync<NT>();
+          owner_sync<NT>();
           if (tid == 0)
           {
 #pragma unroll
             for (int i = 0; i < 3; i++) { s[7 + 2 * i] = pred[i][0]; s[8 + 2 * i] = pred[i][1]; }
             s[6] = mvpIdx;
           }
-          afm_sync<NT>();
+          owner_sync<NT>();
         }
       }
       break;
@@ -218,21 +208,14 @@ __device__ __forceinline__ void abp_search(const vvcgpu_affine_bipred_item* __re
     o.bits = bits2; o.me_calls = calls; o.closing = closing; o.reserved = 0; o.cost = costBi;
     *res = o;
     if (trace)
-      for (unsigned k = calls; k < VVCGPU_AFFINE_BIPRED_MAX_STEPS; k++)
-      {
-        vvcgpu_affine_bipred_step t;
-        memset(&t, 0, sizeof(t));
-        trace[k] = t;
-      }
+      for (unsigned k = calls; k < VVCGPU_AFFINE_BIPRED_MAX_STEPS; k++) zero_record(trace + k);
   }
 }
-
-inline __host__ __device__ bool abp_side_ok(int v) { return v == 16 || v == 32 || v == 64 || v == 128; }
 
 __device__ __forceinline__ bool abp_item_ok(const vvcgpu_affine_bipred_item& it, const vvcgpu_affine_bipred_cfg& c)
 {
   const int w = it.w, h = it.h;
-  if (!abp_side_ok(w) || !abp_side_ok(h) || w > c.max_cu_w || h > c.max_cu_h || w > c.max_pu_w || h > c.max_pu_h) return false;
+  if (!pu_side_affine_ok(w) || !pu_side_affine_ok(h) || w > c.max_cu_w || h > c.max_cu_h || w > c.max_pu_w || h > c.max_pu_h) return false;
   if (it.pos_x < 0 || it.pos_y < 0 || it.pos_x > c.pic_w - w || it.pos_y > c.pic_h - h || it.org_stride <= 0) return false;
   for (int l = 0; l < 2; l++)
   {
@@ -254,40 +237,25 @@ __global__ __launch_bounds__(256) void affine_bipred_me_kernel(const Pel* __rest
 {
   extern __shared__ __align__(16) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // uniform for the compiler too
-  const int nWaveGroups = (n + 3) >> 2;
-  if ((int)blockIdx.x < nWaveGroups)
-  {
-    const int b = blockIdx.x * 4 + wave;                                 // wavefront owners
-    if (b >= n) return;
-    const vvcgpu_affine_bipred_item* it = items + b;
-    if (!abp_item_ok(*it, c) || it->w * it->h > AFI_WAVE_MAX) return;    // the workgroup owner of this item answers
-    abp_search<64>(it, c, orgBase, abp_lds<64>(smem + (size_t)wave * waveBytes, 0, it->w * it->h), results + b,
-                   trace ? trace + (size_t)b * VVCGPU_AFFINE_BIPRED_MAX_STEPS : nullptr, lane);
-    return;
-  }
-  const int b = blockIdx.x - nWaveGroups;                                // workgroup owners
-  if (b >= n) return;
+  const OwnerSlot o = owner_slot(n, wave);
+  if (o.leave) return;
+  const int b = o.unit;
   const vvcgpu_affine_bipred_item* it = items + b;
   vvcgpu_affine_bipred_step* tr = trace ? trace + (size_t)b * VVCGPU_AFFINE_BIPRED_MAX_STEPS : nullptr;
-  if (!abp_item_ok(*it, c))                                              // outside the contract: the sentinel, nothing is read or predicted
+  if (!abp_item_ok(*it, c))                                              // outside the contract: nothing is read or predicted
   {
-    if (tid == 0)
-    {
-      vvcgpu_affine_bipred_result r;
-      memset(&r, 0, sizeof(r));
-      r.cost = ~0ull;
-      results[b] = r;
-    }
-    if (tr && tid < VVCGPU_AFFINE_BIPRED_MAX_STEPS)
-    {
-      vvcgpu_affine_bipred_step s;
-      memset(&s, 0, sizeof(s));
-      tr[tid] = s;
-    }
+    if (!o.waveOwner) owner_write_sentinel(results + b, tr, VVCGPU_AFFINE_BIPRED_MAX_STEPS, tid);
     return;
   }
-  if (it->w * it->h <= AFI_WAVE_MAX) return;
-  abp_search<256>(it, c, orgBase, abp_lds<256>(smem, wave, it->w * it->h), results + b, tr, tid);
+  if ((it->w * it->h <= AFI_WAVE_MAX) != o.waveOwner) return;            // the other kind of owner serves this item
+  if (o.waveOwner) abp_search<64>(it, c, orgBase, abp_lds<64>(smem + (size_t)wave * waveBytes, 0, it->w * it->h), results + b, tr, lane);
+  else abp_search<256>(it, c, orgBase, abp_lds<256>(smem, wave, it->w * it->h), results + b, tr, tid);
+}
+
+// the launch's LDS (cfg checked, max_pu set): an owner's header and two tiles
+PuOwnerLds abp_owner_lds(const vvcgpu_affine_bipred_cfg& c)
+{
+  return pu_owner_lds(16, c.max_pu_w, c.max_pu_h, AFI_WAVE_MAX, [](int w, int h, int nt) { return AbpHdr::bytes(nt, 2 * w * h * (int)sizeof(Pel)); });
 }
 
 }  // namespace
@@ -299,34 +267,13 @@ extern "C" int vvcgpu_affine_bipred_me_batch(const vvc_pel* org_base, const vvcg
   if (n == 0) return VVCGPU_OK;
   VVC_CHECK_ARG(org_base && items && cfg_host && results, "affine_bipred_me_batch: null pointer");
   vvcgpu_affine_bipred_cfg c = *cfg_host;
-  VVC_CHECK_ARG(c.n_planes >= 1 && c.n_planes <= 16, "affine_bipred_me_batch: n_planes %d outside 1..16", c.n_planes);
-  for (int i = 0; i < c.n_planes; i++) VVC_CHECK_ARG(c.ref_planes[i], "affine_bipred_me_batch: null pointer (ref_planes[%d])", i);
-  VVC_CHECK_ARG(c.pic_w > 0 && c.pic_h > 0 && c.max_cu_w > 0 && c.max_cu_h > 0 && c.ref_stride > 0,
-                "affine_bipred_me_batch: geometry (picture %d x %d, CTU %d x %d, ref_stride %d)", c.pic_w, c.pic_h, c.max_cu_w, c.max_cu_h, c.ref_stride);
-  VVC_CHECK_ARG(c.pic_w <= 65536 && c.pic_h <= 65536 && c.max_cu_w <= 256 && c.max_cu_h <= 256, "affine_bipred_me_batch: geometry (picture %d x %d, CTU %d x %d)",
-                c.pic_w, c.pic_h, c.max_cu_w, c.max_cu_h);
-  VVC_CHECK_ARG(c.clp_min <= c.clp_max && c.clp_min >= -32768 && c.clp_max <= 32767, "affine_bipred_me_batch: clip range %d..%d", c.clp_min, c.clp_max);
-  VVC_CHECK_ARG(c.lambda >= 0.0 && c.lambda < 1048576.0, "affine_bipred_me_batch: lambda out of range");
+  if (const int rc = pu_check_frame("affine_bipred_me_batch", c, 16)) return rc;
   VVC_CHECK_ARG(c.num_iter == 1 || c.num_iter == 4, "affine_bipred_me_batch: num_iter %d (4 or 1)", c.num_iter);
-  if (c.max_pu_w == 0) c.max_pu_w = 128;
-  if (c.max_pu_h == 0) c.max_pu_h = 128;
-  VVC_CHECK_ARG(abp_side_ok(c.max_pu_w) && abp_side_ok(c.max_pu_h), "affine_bipred_me_batch: max_pu %d x %d (sides 16, 32, 64, 128, or 0)", c.max_pu_w, c.max_pu_h);
-  if (c.bit_depth > 10 || c.bit_depth < 8) { vvcgpu_set_error("affine_bipred_me_batch: bit depth %d outside 8..10", c.bit_depth); return VVCGPU_E_UNSUPPORTED; }
-  VVC_CHECK_ARG(n < (1 << 28), "affine_bipred_me_batch: n %d", n);
-  for (int i = c.n_planes; i < 16; i++) c.ref_planes[i] = nullptr;
-  // LDS of an owner: its header and two tiles of the largest served shape within max_pu that the owner kind takes
-  int wavePix = 0, groupPix = 0;
-  for (int w = 16; w <= c.max_pu_w; w <<= 1)
-    for (int h = 16; h <= c.max_pu_h; h <<= 1)
-    {
-      int& dst = w * h <= AFI_WAVE_MAX ? wavePix : groupPix;
-      if (w * h > dst) dst = w * h;
-    }
-  const int waveBytes = ABP_HDR_WAVE + 4 * wavePix;
-  const int groupBytes = groupPix ? ABP_HDR_GROUP + 4 * groupPix : 0;
-  const size_t lds = (size_t)(4 * waveBytes > groupBytes ? 4 * waveBytes : groupBytes);
-  VVC_HIP(vvc_allow_lds(affine_bipred_me_kernel, lds));
-  hipLaunchKernelGGL(affine_bipred_me_kernel, dim3(cdiv(n, 4) + n), dim3(256), lds, (hipStream_t)stream, org_base, items, n, c, waveBytes, results, trace);
+  if (const int rc = pu_check_tail("affine_bipred_me_batch", c, n, 1 << 28, pu_side_affine_ok, "16, 32, 64, 128")) return rc;
+  const PuOwnerLds L = abp_owner_lds(c);
+  VVC_HIP(vvc_allow_lds(affine_bipred_me_kernel, L.lds));
+  hipLaunchKernelGGL(affine_bipred_me_kernel, dim3(pu_owner_grid(n, true)), dim3(256), L.lds, (hipStream_t)stream, org_base, items, n, c, L.waveBytes, results,
+                     trace);
   VVC_LAUNCH_CHECK();
   return VVCGPU_OK;
 }

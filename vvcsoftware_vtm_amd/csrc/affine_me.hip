@@ -5,18 +5,18 @@
 // yFrac == 0 / xFrac == 0 branches), InterpolationFilter::filter / filterCopy (InterpolationFilter.cpp:205-379, m_lumaFilter :59-77), clipMv
 // (Mv.cpp:64-80), Mv::roundMV2SignalPrecision (Mv.h:242-257), RdCost::getBitsOfVectorWithPredictor / getCost (RdCost.h:172-199).
 //
-// Design: the owner of a PU -- one wavefront up to AFI_WAVE_MAX samples, the workgroup's four above -- carries it through the whole search.  The grid
-// is cdiv(n, 4) workgroups of four wavefront owners followed by n workgroup owners; each item is served by exactly one of the two, by its size, which
-// only the device knows (the other leaves at once): no work list, no atomics.  The prediction lives in LDS from the first step to the last: sixteen
+// Design: the owner of a PU -- one wavefront up to AFI_WAVE_MAX samples, the workgroup's four above -- carries it through the whole search (the owner
+// model: owner_dev.h and docs/KERNELS.md, "Owners of the whole-PU entries").  The prediction lives in LDS from the first step to the last: sixteen
 // lanes interpolate one 4x4 sub-block (four per wavefront) from its 11x11 window of the reference plane straight into the tile; the error / Sobel /
 // equation pass and the Hadamard distortion (afi_dev.h, shared with the per-iteration entry) read it there; the search body itself is in afm_dev.h,
-// shared with the affine bi-predictive search (affine_bipredme.hip).  The equation sums meet in LDS; every
-// lane of the owner then solves the system and updates the vectors with the same (uniform) values, so nothing is broadcast.
+// shared with the affine bi-predictive and uni-predictive entries.  The equation sums meet in LDS; every lane of the owner then solves the system and
+// updates the vectors with the same (uniform) values, so nothing is broadcast.  This kernel's LDS is static: the tiles of the largest PU.
 #include "common.h"
 #include "dist_dev.h"
 #include "afi_dev.h"
 #include "afm_dev.h"
 #include "raster_dev.h"
+#include "pu_entry_host.h"
 
 namespace {
 
@@ -41,12 +41,7 @@ __device__ __forceinline__ void afm_search(const vvcgpu_affine_me_item& it, cons
     for (int i = 0; i < 3; i++) { res->mv[i][0] = best[i][0]; res->mv[i][1] = best[i][1]; }
     res->bits = bestBits; res->steps = steps; res->cost = bestCost;
     if (trace)
-      for (unsigned s = steps; s < VVCGPU_AFFINE_ME_MAX_STEPS; s++)
-      {
-#pragma unroll
-        for (int i = 0; i < 3; i++) { trace[s].mv[i][0] = 0; trace[s].mv[i][1] = 0; }
-        trace[s].cost = 0;
-      }
+      for (unsigned s = steps; s < VVCGPU_AFFINE_ME_MAX_STEPS; s++) zero_record(trace + s);
   }
 }
 
@@ -66,38 +61,25 @@ __global__ __launch_bounds__(256) void affine_me_kernel(const Pel* __restrict__ 
   __shared__ long long red[4][64];
   __shared__ unsigned long long distW[4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int nWaveGroups = (n + 3) >> 2;
+  const OwnerSlot o = owner_slot(n, wave);                               // wave is a per-lane value here, so each kind of owner keeps its own branch:
+  if (o.leave) return;                                                   // the workgroup's unit stays in scalar registers, and the item with it
   AfmLds L;
   L.tmpW = tmpL[wave]; L.red = red; L.distW = distW;
-  if ((int)blockIdx.x < nWaveGroups)
+  if (o.waveOwner)
   {
-    const int b = blockIdx.x * 4 + wave;                                 // wavefront owners
-    if (b >= n) return;
+    const int b = o.unit;
     const vvcgpu_affine_me_item it = items[b];
     if (!afm_item_ok(it) || it.pu.w * it.pu.h > AFI_WAVE_MAX) return;    // the workgroup owner of this item answers
     L.predL = predL + wave * AFI_WAVE_MAX; L.eq = eqL[wave];
     afm_search<64>(it, c, orgBase, refBase, L, results + b, trace ? trace + (size_t)b * VVCGPU_AFFINE_ME_MAX_STEPS : nullptr, lane);
     return;
   }
-  const int b = blockIdx.x - nWaveGroups;                                // workgroup owners
-  if (b >= n) return;
+  const int b = __builtin_amdgcn_readfirstlane(o.unit);                  // the workgroup's: uniform for the compiler too
   const vvcgpu_affine_me_item it = items[b];
   vvcgpu_affine_me_step* tr = trace ? trace + (size_t)b * VVCGPU_AFFINE_ME_MAX_STEPS : nullptr;
-  if (!afm_item_ok(it))                                                  // outside the contract: the sentinel, nothing is read or predicted
+  if (!afm_item_ok(it))                                                  // outside the contract: nothing is read or predicted
   {
-    if (tid == 0)
-    {
-      vvcgpu_affine_me_result r;
-      memset(&r, 0, sizeof(r));
-      r.cost = ~0ull;
-      results[b] = r;
-    }
-    if (tr && tid < VVCGPU_AFFINE_ME_MAX_STEPS)
-    {
-      vvcgpu_affine_me_step s;
-      memset(&s, 0, sizeof(s));
-      tr[tid] = s;
-    }
+    owner_write_sentinel(results + b, tr, VVCGPU_AFFINE_ME_MAX_STEPS, tid);
     return;
   }
   if (it.pu.w * it.pu.h <= AFI_WAVE_MAX) return;
@@ -114,15 +96,12 @@ extern "C" int vvcgpu_affine_me_batch(const vvc_pel* org_base, const vvc_pel* re
   if (n == 0) return VVCGPU_OK;
   VVC_CHECK_ARG(org_base && ref_base && items && cfg_host && results, "affine_me_batch: null pointer");
   const vvcgpu_affine_me_cfg c = *cfg_host;
-  VVC_CHECK_ARG(c.pic_w > 0 && c.pic_h > 0 && c.max_cu_w > 0 && c.max_cu_h > 0 && c.ref_stride > 0, "affine_me_batch: geometry (picture %d x %d, CTU %d x %d, ref_stride %d)",
-                c.pic_w, c.pic_h, c.max_cu_w, c.max_cu_h, c.ref_stride);
-  VVC_CHECK_ARG(c.pic_w <= 65536 && c.pic_h <= 65536 && c.max_cu_w <= 256 && c.max_cu_h <= 256, "affine_me_batch: geometry (picture %d x %d, CTU %d x %d)", c.pic_w,
-                c.pic_h, c.max_cu_w, c.max_cu_h);
+  if (const int rc = pu_check_geometry("affine_me_batch", c)) return rc;
   VVC_CHECK_ARG(c.clp_min <= c.clp_max, "affine_me_batch: clip range %d..%d", c.clp_min, c.clp_max);
   VVC_CHECK_ARG(c.lambda >= 0.0 && c.lambda < 1048576.0, "affine_me_batch: lambda out of range");
   if (c.bit_depth > 10 || c.bit_depth < 8) { vvcgpu_set_error("affine_me_batch: bit depth %d outside 8..10", c.bit_depth); return VVCGPU_E_UNSUPPORTED; }
   VVC_CHECK_ARG(n < (1 << 28), "affine_me_batch: n %d", n);
-  hipLaunchKernelGGL(affine_me_kernel, dim3(cdiv(n, 4) + n), dim3(256), 0, (hipStream_t)stream, org_base, ref_base, items, n, c, results, trace);
+  hipLaunchKernelGGL(affine_me_kernel, dim3(pu_owner_grid(n, true)), dim3(256), 0, (hipStream_t)stream, org_base, ref_base, items, n, c, results, trace);
   VVC_LAUNCH_CHECK();
   return VVCGPU_OK;
 }

@@ -8,45 +8,27 @@
 //
 // Design: the shape of unipredme.hip.  The (list, reference index) searches of a PU depend on each other only through the list-1 shortcut and the
 // final comparisons, and one gradient search is a chain of dependent predictions, so the unit of ownership is the SEARCH: launch 1 gives each of the
-// n x (n_ref[0] + n_ref[1]) searches an owner -- one wavefront up to AFI_WAVE_MAX samples, the workgroup's four above, the grid split of
-// affine_bipredme.hip.  The owner forms every template-cost prediction (each candidate, the translational start, the inherited start) in the
-// prediction tile of afm_dev.h and reduces its SAD against the original straight from that tile (nothing is written out), chooses the start vectors,
-// runs the gradient search of afm_dev.h unchanged and xCheckBestAffineMVP, and writes its record into the PU's result.  A search that takes list 0's
-// vectors, or that a 6-parameter PU skips, only chooses its predictor.  Launch 2, one lane per PU, walks the records in the reference's order: the
-// list-1 shortcut with its xCheckBestAffineMVP, bestBiP*, keep-if-strictly-better, the valid-list-1 record, the out-item for
+// n x (n_ref[0] + n_ref[1]) searches an owner -- one wavefront up to AFI_WAVE_MAX samples, the workgroup's four above (the owner model: owner_dev.h
+// and docs/KERNELS.md, "Owners of the whole-PU entries").  The owner forms every template-cost prediction (each candidate, the translational start,
+// the inherited start) in the prediction tile of afm_dev.h and reduces its SAD against the original straight from that tile (nothing is written out),
+// chooses the start vectors, runs the gradient search of afm_dev.h unchanged and xCheckBestAffineMVP, and writes its record into the PU's result.  A
+// search that takes list 0's vectors, or that a 6-parameter PU skips, only chooses its predictor.  Launch 2, one lane per PU, walks the records in the
+// reference's order: the list-1 shortcut with its xCheckBestAffineMVP, bestBiP*, keep-if-strictly-better, the valid-list-1 record, the out-item for
 // vvcgpu_affine_bipred_me_batch, and everything a skipped item gets.  Control flow is uniform per owner.  Dynamic LDS, sized on the host from
 // cfg.max_pu_w / max_pu_h.
 #include "common.h"
 #include "afm_dev.h"
+#include "pu_entry_host.h"
 
 namespace {
 
-constexpr int AUP_OFF_TMP = 400;                                                              // behind the 49 equation sums
-constexpr int AUP_TMP_BYTES = 4 * AFM_TMP * 2;                                                // one wavefront's first-pass rows
-constexpr int AUP_HDR_WAVE = (AUP_OFF_TMP + AUP_TMP_BYTES + 15) & ~15;                        // 752: bytes in front of a wavefront owner's tile
-constexpr int AUP_OFF_RED = AUP_OFF_TMP + 4 * AUP_TMP_BYTES;                                  // 1808: the workgroup owner's partial sums
-constexpr int AUP_OFF_DIST = AUP_OFF_RED + 4 * 64 * 8;                                        // 3856
-constexpr int AUP_HDR_GROUP = (AUP_OFF_DIST + 4 * 8 + 15) & ~15;                              // 3888
-static_assert(AUP_OFF_RED % 8 == 0 && AUP_OFF_DIST % 8 == 0, "alignment");
-
-template <int NT>
-__device__ __forceinline__ AfmLds aup_lds(unsigned char* base, int wave)
-{
-  AfmLds L;
-  L.eq = reinterpret_cast<long long*>(base);
-  L.tmpW = reinterpret_cast<short*>(base + AUP_OFF_TMP) + (NT == 256 ? wave * 4 * AFM_TMP : 0);
-  L.red = reinterpret_cast<long long (*)[64]>(base + AUP_OFF_RED);            // NT = 256 only
-  L.distW = reinterpret_cast<unsigned long long*>(base + AUP_OFF_DIST);       // NT = 256 only
-  L.predL = reinterpret_cast<Pel*>(base + (NT == 256 ? AUP_HDR_GROUP : AUP_HDR_WAVE));
-  return L;
-}
-
-inline __host__ __device__ bool aup_side_ok(int v) { return v == 16 || v == 32 || v == 64 || v == 128; }
+typedef AfmHdr<0> AupHdr;                  // the header of afm_dev.h with no state of the entry's own
+static_assert(AupHdr::WAVE == 752 && AupHdr::GROUP == 3888, "header sizes");
 
 __device__ __forceinline__ bool aup_item_ok(const vvcgpu_affine_unipred_item& it, const vvcgpu_affine_unipred_cfg& c)
 {
   const int w = it.w, h = it.h;
-  if (!aup_side_ok(w) || !aup_side_ok(h) || w > c.max_cu_w || h > c.max_cu_h || w > c.max_pu_w || h > c.max_pu_h) return false;
+  if (!pu_side_affine_ok(w) || !pu_side_affine_ok(h) || w > c.max_cu_w || h > c.max_cu_h || w > c.max_pu_w || h > c.max_pu_h) return false;
   if (it.pos_x < 0 || it.pos_y < 0 || it.pos_x > c.pic_w - w || it.pos_y > c.pic_h - h || it.org_stride <= 0) return false;
   for (int l = 0; l < 2; l++)
   {
@@ -57,7 +39,6 @@ __device__ __forceinline__ bool aup_item_ok(const vvcgpu_affine_unipred_item& it
   return true;
 }
 
-__device__ __forceinline__ unsigned aup_ref_bits(int nRef, int r) { return nRef > 1 ? (unsigned)(r + 1 - (r == nRef - 1 ? 1 : 0)) : 0u; }
 // :2673: a 6-parameter PU searches only the reference index its 4-parameter search chose
 __device__ __forceinline__ bool aup_skipped(const vvcgpu_affine_unipred_item& it, int list, int r) { return it.six_param != 0 && it.only_ref[list] != r; }
 // :2740-2746
@@ -73,21 +54,12 @@ template <int NT>
 __device__ __forceinline__ unsigned long long aup_template_sad(const AfmPu& u, const Pel* __restrict__ org, const int (&mv)[3][2], const AfmLds& L, int tid)
 {
   afm_predict<NT>(u, mv, L.predL, L.tmpW, tid);
-  afm_sync<NT>();
+  owner_sync<NT>();
   const int lgW = ilog2(u.w), pixels = u.w * u.h;
   unsigned sad = 0;
   for (int i = tid; i < pixels; i += NT) sad += (unsigned)abs((int)org[(ptrdiff_t)(i >> lgW) * u.os + (i & (u.w - 1))] - (int)L.predL[i]);
-  unsigned long long s = sad;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-  if (NT == 256)
-  {
-    if ((tid & 63) == 0) L.distW[tid >> 6] = s;
-    __syncthreads();
-    s = L.distW[0] + L.distW[1] + L.distW[2] + L.distW[3];
-    __syncthreads();                                                     // distW and the tile are written again by the next prediction
-  }
-  else afm_sync<64>();
+  const unsigned long long s = owner_sum<NT>(sad, L.distW, tid);
+  if (NT == 64) owner_sync<64>();                                        // the tile is written again by the next prediction (NT = 256: the sum's barriers)
   return s;
 }
 
@@ -128,7 +100,7 @@ __device__ __forceinline__ void aup_search(const vvcgpu_affine_unipred_item* __r
     for (int k = 0; k < 3; k++)
 #pragma unroll
       for (int d = 0; d < 2; d++) tv[k][d] = t < 2 ? a.mv_cand[t][k][d] : t == 2 ? a.hevc_mv[d] : four[k][d];
-    const unsigned long long v = aup_template_sad<NT>(u, org, tv, L, tid) + afm_getcost(c.lambda, c.mvp_idx_cost[t < 2 ? t : mvpIdx]);
+    const unsigned long long v = aup_template_sad<NT>(u, org, tv, L, tid) + pu_getcost(c.lambda, c.mvp_idx_cost[t < 2 ? t : mvpIdx]);
     if (t < 2)
     {
       if (t == 0) tm0 = v; else tm1 = v;
@@ -145,7 +117,7 @@ __device__ __forceinline__ void aup_search(const vvcgpu_affine_unipred_item* __r
     if (tid == 0) *out = o;
     return;
   }
-  unsigned bits = itp->mb_bits[list] + aup_ref_bits(c.n_ref[list], r) + c.mvp_idx_cost[mvpIdx];
+  unsigned bits = itp->mb_bits[list] + pu_ref_bits(c.n_ref[list], r) + c.mvp_idx_cost[mvpIdx];
   if (shortcut)                                                          // list 0's vectors: the decision step finishes this record
   {
     o.bits = bits; o.searched = 2;
@@ -187,16 +159,15 @@ __global__ __launch_bounds__(256) void affine_unipred_search_kernel(const Pel* _
 {
   extern __shared__ __align__(16) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // uniform for the compiler too
-  const int S = c.n_ref[0] + c.n_ref[1], total = n * S, nWaveGroups = (total + 3) >> 2;
-  const bool waveOwner = (int)blockIdx.x < nWaveGroups;
-  const int o = waveOwner ? (int)blockIdx.x * 4 + wave : (int)blockIdx.x - nWaveGroups;     // search o = search k of PU b
-  if (o >= total) return;
-  const int b = o / S, k = o - b * S, list = k >= c.n_ref[0] ? 1 : 0, r = list ? k - c.n_ref[0] : k;
+  const int S = c.n_ref[0] + c.n_ref[1];
+  const OwnerSlot o = owner_slot(n * S, wave);                          // unit = search k of PU b
+  if (o.leave) return;
+  const int b = o.unit / S, k = o.unit - b * S, list = k >= c.n_ref[0] ? 1 : 0, r = list ? k - c.n_ref[0] : k;
   const vvcgpu_affine_unipred_item* it = items + b;
   if (!aup_item_ok(*it, c)) return;                                      // the decision step writes the sentinel
-  if ((it->w * it->h <= AFI_WAVE_MAX) != waveOwner) return;              // the other kind of owner serves this item
-  if (waveOwner) aup_search<64>(it, c, orgBase, aup_lds<64>(smem + (size_t)wave * waveBytes, 0), list, r, &results[b].s[list][r], lane);
-  else aup_search<256>(it, c, orgBase, aup_lds<256>(smem, wave), list, r, &results[b].s[list][r], tid);
+  if ((it->w * it->h <= AFI_WAVE_MAX) != o.waveOwner) return;              // the other kind of owner serves this item
+  if (o.waveOwner) aup_search<64>(it, c, orgBase, afm_lds<64, 0>(smem + (size_t)wave * waveBytes, 0), list, r, &results[b].s[list][r], lane);
+  else aup_search<256>(it, c, orgBase, afm_lds<256, 0>(smem, wave), list, r, &results[b].s[list][r], tid);
 }
 
 // per PU: the records of its searches in the reference's order (:2651-2814) -> the result and the out-item
@@ -210,14 +181,9 @@ __global__ __launch_bounds__(256) void affine_unipred_decide_kernel(const vvcgpu
   vvcgpu_affine_unipred_result* R = results + b;
   if (!aup_item_ok(it, c))
   {
-    unsigned long long* z = reinterpret_cast<unsigned long long*>(R);
-    for (unsigned i = 0; i < sizeof(*R) / 8; i++) z[i] = 0;
+    zero_record(R);
     R->cost[0] = R->cost[1] = ~0ull;
-    if (outItems)
-    {
-      z = reinterpret_cast<unsigned long long*>(outItems + b);
-      for (unsigned i = 0; i < sizeof(*outItems) / 8; i++) z[i] = 0;
-    }
+    if (outItems) zero_record(outItems + b);
     return;
   }
   const int nmv = it.six_param ? 3 : 2;
@@ -229,7 +195,7 @@ __global__ __launch_bounds__(256) void affine_unipred_decide_kernel(const vvcgpu
     for (int r = 0; r < VVCGPU_AFFINE_UNIPRED_MAX_REFS; r++)
     {
       vvcgpu_affine_unipred_search s;
-      if (r >= c.n_ref[list]) { memset(&s, 0, sizeof(s)); R->s[list][r] = s; continue; }
+      if (r >= c.n_ref[list]) { zero_record(&R->s[list][r]); continue; }
       s = R->s[list][r];
       if (s.searched == 0) continue;                                     // :2673-2677, before the bestBiP* update
       const vvcgpu_affine_unipred_ref& a = it.ref[list][r];
@@ -242,9 +208,9 @@ __global__ __launch_bounds__(256) void affine_unipred_decide_kernel(const vvcgpu
 #pragma unroll
         for (int k = 0; k < 3; k++) { pred[k][0] = a.mv_cand[mvpIdx][k][0]; pred[k][1] = a.mv_cand[mvpIdx][k][1]; mv[k][0] = s0.mv[k][0]; mv[k][1] = s0.mv[k][1]; }
         unsigned long long cost = s0.cost;
-        cost -= afm_getcost(c.lambda, s0.bits);
+        cost -= pu_getcost(c.lambda, s0.bits);
         unsigned bits = afm_bits(s.bits, pred, nmv, mv);
-        cost += afm_getcost(c.lambda, bits);
+        cost += pu_getcost(c.lambda, bits);
         afm_check_best_mvp(a.mv_cand, a.num_cand, c.mvp_idx_cost, c.lambda, nmv, mv, pred, mvpIdx, bits, cost);
 #pragma unroll
         for (int k = 0; k < 3; k++) { s.mv[k][0] = mv[k][0]; s.mv[k][1] = mv[k][1]; }
@@ -301,6 +267,12 @@ __global__ __launch_bounds__(256) void affine_unipred_decide_kernel(const vvcgpu
   }
 }
 
+// the launch's LDS (cfg checked, max_pu set): an owner's header and its tile
+PuOwnerLds aup_owner_lds(const vvcgpu_affine_unipred_cfg& c)
+{
+  return pu_owner_lds(16, c.max_pu_w, c.max_pu_h, AFI_WAVE_MAX, [](int w, int h, int nt) { return AupHdr::bytes(nt, w * h * (int)sizeof(Pel)); });
+}
+
 }  // namespace
 
 extern "C" int vvcgpu_affine_unipred_me_batch(const vvc_pel* org_base, const vvcgpu_affine_unipred_item* items, int n, const vvcgpu_affine_unipred_cfg* cfg_host,
@@ -310,46 +282,15 @@ extern "C" int vvcgpu_affine_unipred_me_batch(const vvc_pel* org_base, const vvc
   if (n == 0) return VVCGPU_OK;
   VVC_CHECK_ARG(org_base && items && cfg_host && results, "affine_unipred_me_batch: null pointer");
   vvcgpu_affine_unipred_cfg c = *cfg_host;
-  VVC_CHECK_ARG(c.n_planes >= 1 && c.n_planes <= 16, "affine_unipred_me_batch: n_planes %d outside 1..16", c.n_planes);
-  for (int i = 0; i < c.n_planes; i++) VVC_CHECK_ARG(c.ref_planes[i], "affine_unipred_me_batch: null pointer (ref_planes[%d])", i);
-  VVC_CHECK_ARG(c.pic_w > 0 && c.pic_h > 0 && c.max_cu_w > 0 && c.max_cu_h > 0 && c.ref_stride > 0,
-                "affine_unipred_me_batch: geometry (picture %d x %d, CTU %d x %d, ref_stride %d)", c.pic_w, c.pic_h, c.max_cu_w, c.max_cu_h, c.ref_stride);
-  VVC_CHECK_ARG(c.pic_w <= 65536 && c.pic_h <= 65536 && c.max_cu_w <= 256 && c.max_cu_h <= 256, "affine_unipred_me_batch: geometry (picture %d x %d, CTU %d x %d)",
-                c.pic_w, c.pic_h, c.max_cu_w, c.max_cu_h);
-  VVC_CHECK_ARG(c.clp_min <= c.clp_max && c.clp_min >= -32768 && c.clp_max <= 32767, "affine_unipred_me_batch: clip range %d..%d", c.clp_min, c.clp_max);
-  VVC_CHECK_ARG(c.lambda >= 0.0 && c.lambda < 1048576.0, "affine_unipred_me_batch: lambda out of range");
-  VVC_CHECK_ARG(c.n_ref[0] >= 1 && c.n_ref[0] <= VVCGPU_AFFINE_UNIPRED_MAX_REFS && c.n_ref[1] >= 0 && c.n_ref[1] <= VVCGPU_AFFINE_UNIPRED_MAX_REFS,
-                "affine_unipred_me_batch: n_ref %d, %d (list 0: 1..4, list 1: 0..4)", c.n_ref[0], c.n_ref[1]);
-  for (int l = 0; l < 2; l++)
-    for (int r = 0; r < c.n_ref[l]; r++)
-      VVC_CHECK_ARG(c.ref_plane[l][r] >= 0 && c.ref_plane[l][r] < c.n_planes, "affine_unipred_me_batch: ref_plane[%d][%d] %d outside [0, %d)", l, r, c.ref_plane[l][r],
-                    c.n_planes);
-  for (int r = 0; r < c.n_ref[1]; r++)
-    VVC_CHECK_ARG(c.list1_to_list0[r] >= -1 && c.list1_to_list0[r] < c.n_ref[0], "affine_unipred_me_batch: list1_to_list0[%d] %d outside [-1, %d)", r, c.list1_to_list0[r],
-                  c.n_ref[0]);
-  if (c.max_pu_w == 0) c.max_pu_w = 128;
-  if (c.max_pu_h == 0) c.max_pu_h = 128;
-  VVC_CHECK_ARG(aup_side_ok(c.max_pu_w) && aup_side_ok(c.max_pu_h), "affine_unipred_me_batch: max_pu %d x %d (sides 16, 32, 64, 128, or 0)", c.max_pu_w, c.max_pu_h);
-  if (c.bit_depth > 10 || c.bit_depth < 8) { vvcgpu_set_error("affine_unipred_me_batch: bit depth %d outside 8..10", c.bit_depth); return VVCGPU_E_UNSUPPORTED; }
+  if (const int rc = pu_check_frame("affine_unipred_me_batch", c, 16)) return rc;
+  if (const int rc = pu_check_lists("affine_unipred_me_batch", c, VVCGPU_AFFINE_UNIPRED_MAX_REFS, [](int, int) { return VVCGPU_OK; })) return rc;
   const int S = c.n_ref[0] + c.n_ref[1];
-  VVC_CHECK_ARG(n < (1 << 27) / S, "affine_unipred_me_batch: n %d", n);
-  for (int i = c.n_planes; i < 16; i++) c.ref_planes[i] = nullptr;
-  // LDS of an owner: its header and the tile of the largest served shape within max_pu that the owner kind takes
-  int wavePix = 0, groupPix = 0;
-  for (int w = 16; w <= c.max_pu_w; w <<= 1)
-    for (int h = 16; h <= c.max_pu_h; h <<= 1)
-    {
-      int& dst = w * h <= AFI_WAVE_MAX ? wavePix : groupPix;
-      if (w * h > dst) dst = w * h;
-    }
-  const int waveBytes = AUP_HDR_WAVE + 2 * wavePix;
-  const int groupBytes = groupPix ? AUP_HDR_GROUP + 2 * groupPix : 0;
-  const size_t lds = (size_t)(4 * waveBytes > groupBytes ? 4 * waveBytes : groupBytes);
+  if (const int rc = pu_check_tail("affine_unipred_me_batch", c, n, (1 << 27) / S, pu_side_affine_ok, "16, 32, 64, 128")) return rc;
+  const PuOwnerLds L = aup_owner_lds(c);
   const int total = n * S;
   hipStream_t st = (hipStream_t)stream;
-  VVC_HIP(vvc_allow_lds(affine_unipred_search_kernel, lds));
-  const int groupOwners = groupPix ? total : 0;                          // no served item is workgroup-owned when max_pu says so
-  hipLaunchKernelGGL(affine_unipred_search_kernel, dim3(cdiv(total, 4) + groupOwners), dim3(256), lds, st, org_base, items, n, c, waveBytes, results);
+  VVC_HIP(vvc_allow_lds(affine_unipred_search_kernel, L.lds));
+  hipLaunchKernelGGL(affine_unipred_search_kernel, dim3(pu_owner_grid(total, L.groupBytes != 0)), dim3(256), L.lds, st, org_base, items, n, c, L.waveBytes, results);
   VVC_LAUNCH_CHECK();
   hipLaunchKernelGGL(affine_unipred_decide_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, items, n, c, results, bipred_items_out);
   VVC_LAUNCH_CHECK();

@@ -1,12 +1,15 @@
 // afm_dev.h -- device functions of the whole affine gradient search shared by vvcgpu_affine_me_batch (affine_me.hip), the affine bi-predictive
 // search (affine_bipredme.hip) and the affine uni-predictive stage (affine_unipredme.hip): the 4x4 sub-block prediction into an LDS tile, the
-// vector bits, xCheckBestAffineMVP, the Hadamard distortion, the solve and the search body.  Reference behaviour: see affine_me.hip.  The original of a search is read through OrgPtr: a plain pointer (global memory) or AfiLdsPel (the
-// bi-predictive search key, which lives in LDS) -- a template parameter, so no sample pays a run-time choice.
+// vector bits, xCheckBestAffineMVP, the Hadamard distortion, the solve, the search body, and the dynamic-LDS layout of an owner (afm_lds).  The owner
+// model (split, barrier, sum, reference-index bits, getCost) is owner_dev.h's.  Reference behaviour: see affine_me.hip.  The original of a search is
+// read through OrgPtr: a plain pointer (global memory) or AfiLdsPel (the bi-predictive search key, which lives in LDS) -- a template parameter, so no
+// sample pays a run-time choice.
 #pragma once
 #include "common.h"
 #include "dist_dev.h"
 #include "afi_dev.h"
 #include "raster_dev.h"
+#include "owner_dev.h"
 
 namespace {
 
@@ -17,13 +20,6 @@ __constant__ short kAfmLuma[16][8] = {                        // m_lumaFilter, 1
   {  0, 1,  -5, 17, 58, -10,  4, -1 }, {  0, 1,  -4, 13, 60,  -8,  3, -1 }, {  0, 1,  -3,  8, 62,  -5,  2, -1 }, {  0, 1,  -2,  4, 63,  -3,  1,  0 } };
 
 constexpr int AFM_TMP = 11 * 4;            // first-pass rows of one 4x4 sub-block (8 taps: 11 rows) x 4 columns
-
-// NT = 64: the wavefront owns the PU; NT = 256: the workgroup does (every wavefront follows the same, uniform, control flow)
-template <int NT> __device__ __forceinline__ void afm_sync()
-{
-  if (NT == 256) __syncthreads();
-  else { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }
-}
 
 // (int)double as x86 cvttsd2si gives it: truncation; the "integer indefinite" 0x80000000 for NaN and for values outside int (v_cvt_i32_f64 saturates)
 __device__ __forceinline__ int afm_cvtt(double d) { return (d >= -2147483648.0 && d < 2147483648.0) ? (int)d : (int)0x80000000u; }
@@ -186,7 +182,7 @@ __device__ __forceinline__ void afm_predict(const AfmPu& u, const int (&mv)[3][2
         }
       }
     }
-    afm_sync<64>();
+    owner_sync<64>();
     if (act)
     {
       int v;
@@ -219,7 +215,7 @@ __device__ __forceinline__ void afm_predict(const AfmPu& u, const int (&mv)[3][2
       }
       predL[(hq + r) * w + wq + cc] = (Pel)v;
     }
-    afm_sync<64>();                                                     // the next round overwrites tmp
+    owner_sync<64>();                                                   // the next round overwrites tmp
   }
 }
 
@@ -236,9 +232,6 @@ __device__ __forceinline__ unsigned afm_bits(unsigned bits, const int (&mvp)[3][
   }
   return bits;
 }
-
-// getCost (RdCost.h:172-199)
-__device__ __forceinline__ unsigned long long afm_getcost(double lambda, unsigned bits) { return (unsigned long long)(lambda * (double)bits); }
 
 // xCheckBestAffineMVP (:3181-3284) with the candidate set `cand` of `numCand` candidates: the vector bits (second-predictor rule for vectors 1 and 2)
 // against the current predictors and against the other candidate; on a switch the predictors, the index, the bits (uint32) and the cost (wrapping
@@ -265,7 +258,7 @@ __device__ __forceinline__ void afm_check_best_mvp(const int32_t (&cand)[2][3][2
     mvpIdx = bestIdx;
     const unsigned orgB = bits;
     bits = orgB - (unsigned)orgBits + (unsigned)bestBits;
-    cost = (cost - afm_getcost(lambda, orgB)) + afm_getcost(lambda, bits);
+    cost = (cost - pu_getcost(lambda, orgB)) + pu_getcost(lambda, bits);
   }
 }
 
@@ -278,6 +271,34 @@ struct AfmLds
   unsigned long long* distW;  // NT = 256: the wavefronts' distortions
 };
 
+// The header in front of an owner's tiles in dynamic LDS: eq | EXTRA bytes of the entry's own state (at AFM_OFF_STATE) | tmp | red | dist.  A wavefront
+// owner's header ends behind its one tmp block (WAVE bytes); the workgroup owner's holds four of them, red and dist (GROUP bytes).
+constexpr int AFM_OFF_STATE = 400;                       // behind the 49 equation sums
+constexpr int AFM_TMP_BYTES = 4 * AFM_TMP * 2;           // one wavefront's first-pass rows
+template <int EXTRA> struct AfmHdr
+{
+  static constexpr int TMP = AFM_OFF_STATE + EXTRA;
+  static constexpr int WAVE = (TMP + AFM_TMP_BYTES + 15) & ~15;
+  static constexpr int RED = TMP + 4 * AFM_TMP_BYTES;
+  static constexpr int DIST = RED + 4 * 64 * 8;
+  static constexpr int GROUP = (DIST + 4 * 8 + 15) & ~15;
+  static_assert(EXTRA % 8 == 0 && RED % 8 == 0 && DIST % 8 == 0, "alignment");
+  static int bytes(int nt, int tileBytes) { return (nt == 64 ? WAVE : GROUP) + tileBytes; }      // host: an owner's LDS with its tiles
+};
+
+template <int NT, int EXTRA>
+__device__ __forceinline__ AfmLds afm_lds(unsigned char* base, int wave)
+{
+  typedef AfmHdr<EXTRA> H;
+  AfmLds L;
+  L.eq = reinterpret_cast<long long*>(base);
+  L.tmpW = reinterpret_cast<short*>(base + H::TMP) + (NT == 256 ? wave * 4 * AFM_TMP : 0);
+  L.red = reinterpret_cast<long long (*)[64]>(base + H::RED);                 // NT = 256 only
+  L.distW = reinterpret_cast<unsigned long long*>(base + H::DIST);            // NT = 256 only
+  L.predL = reinterpret_cast<Pel*>(base + (NT == 256 ? H::GROUP : H::WAVE));
+  return L;
+}
+
 template <int NT, class OrgPtr>
 __device__ __forceinline__ unsigned long long afm_dist(const AfmPu& u, OrgPtr org, const AfmLds& L, int tid)
 {
@@ -287,12 +308,7 @@ __device__ __forceinline__ unsigned long long afm_dist(const AfmPu& u, OrgPtr or
   unsigned long long sum;
   if ((u.h & 15) == 0) sum = afi_dist<OrgPtr>(d, org, L.predL, u.w, u.h, 1, NT == 256 ? wave : 0, NT == 256 ? 4 : 1, lane);
   else sum = (NT == 64 || wave == 0) ? satd_block<64, AfiLdsPel, OrgPtr>(org, u.os, (AfiLdsPel)L.predL, u.w, u.w, u.h, lane) : 0ull;   // no bands of sixteen rows
-  if (NT == 64) return sum;
-  if (lane == 0) L.distW[wave] = sum;
-  __syncthreads();
-  sum = L.distW[0] + L.distW[1] + L.distW[2] + L.distW[3];
-  __syncthreads();                                                       // distW is written again by the next step
-  return sum;
+  return owner_sum_waves<NT>(sum, L.distW, tid);                         // afi_dist and satd_block return a wavefront's sum in each of its lanes
 }
 
 // xAffineMotionEstimation from the vectors `start` against the predictors `mvp` with ruiBits = bits0 on entry: the start vectors are clipped,
@@ -315,7 +331,7 @@ __device__ __forceinline__ void afm_search_body(const AfmPu& u, OrgPtr org, doub
     if (i < u.nmv) { cur[i][0] = min(u.horMax, max(u.horMin, cur[i][0])); cur[i][1] = min(u.verMax, max(u.verMin, cur[i][1])); }
 
   afm_predict<NT>(u, cur, L.predL, L.tmpW, tid);
-  afm_sync<NT>();
+  owner_sync<NT>();
   unsigned long long had = afm_dist<NT, OrgPtr>(u, org, L, tid);
   bestBits = afm_bits(bits0, mvp, u.nmv, cur);
   bestCost = (unsigned long long)(floor(weight * (double)had) + (double)(unsigned long long)(lambda * bestBits));
@@ -335,7 +351,7 @@ __device__ __forceinline__ void afm_search_body(const AfmPu& u, OrgPtr org, doub
   {
     if (u.six) afi_equations_regs<6, NT, OrgPtr>(d, org, L.predL, u.w, u.h, L.eq, L.red, tid);
     else       afi_equations_regs<4, NT, OrgPtr>(d, org, L.predL, u.w, u.h, L.eq, L.red, tid);
-    afm_sync<NT>();
+    owner_sync<NT>();
     int delta[3][2];
     if (u.six) afm_deltas<6>(L.eq, u.w, u.h, delta);
     else       afm_deltas<4>(L.eq, u.w, u.h, delta);
@@ -357,9 +373,9 @@ __device__ __forceinline__ void afm_search_body(const AfmPu& u, OrgPtr org, doub
         cur[i][k] = k == 0 ? min(u.horMax, max(u.horMin, v)) : min(u.verMax, max(u.verMin, v));
       }
     }
-    afm_sync<NT>();                                                      // every lane has read eq and the tile before they are overwritten
+    owner_sync<NT>();                                                    // every lane has read eq and the tile before they are overwritten
     afm_predict<NT>(u, cur, L.predL, L.tmpW, tid);
-    afm_sync<NT>();
+    owner_sync<NT>();
     had = afm_dist<NT, OrgPtr>(u, org, L, tid);
     const unsigned bits = afm_bits(bits0, mvp, u.nmv, cur);
     const unsigned long long cost = (unsigned long long)(floor(weight * (double)had) + (double)(unsigned long long)(lambda * bits));

@@ -6,18 +6,19 @@
 // xPredInterBlk (CommonLib/InterPrediction.cpp:480-547) with InterpolationFilter::filter / filterCopy (InterpolationFilter.cpp:205-379), clipMv
 // (Mv.cpp:64-80) -- the prediction body is me_pred_uni of me_dev.h --, Mv::divideByPowerOf2 (Mv.h:142-151, ME_ENABLE_ROUNDING_OF_MVS), RdCost::getBitsOfVectorWithPredictor / getCost (RdCost.h:172-199).
 //
-// Design: the owner of a PU -- one wavefront up to BP_WAVE_MAX samples, the workgroup's four above -- carries it through every iteration, the grid
-// split being that of affine_me.hip (cdiv(n, 4) workgroups of four wavefront owners, then n workgroup owners; an item is served by exactly one of the
-// two, by its size).  What an iteration needs of the lists' predictions is only the OTHER list's, and only to form the search key 2 org - otherPred,
-// so the prediction goes from the interpolation straight into the key and is never stored: per owner LDS holds the key (w x h), and a work area that is
-// in turn the first-pass plane of the interpolation, the reference window of the integer search (block + range each way) and the window, first-stage
-// plane and candidate block of the fractional refinement.  Dynamic LDS, sized on the host from cfg.max_pu_w / max_pu_h.  The integer search gives
-// every position to a group of 1..64 lanes (a quarter of the block's sampled pixels each at most), so that no sum crosses a wavefront; the arg-min keeps
-// (cost, scan index) pairs, which is the strict '<' of the y-outer, x-inner scan.  Control flow is uniform per owner: every lane computes the same
-// scalar state; the per-(list, reference) state that is indexed dynamically (cMvTemp, aaiMvpIdxBi, cMvPredBi) lives in LDS.
+// Design: the owner of a PU -- one wavefront up to BP_WAVE_MAX samples, the workgroup's four above -- carries it through every iteration (the owner
+// model: owner_dev.h and docs/KERNELS.md, "Owners of the whole-PU entries").  What an iteration needs of the lists' predictions is only the OTHER
+// list's, and only to form the search key 2 org - otherPred, so the prediction goes from the interpolation straight into the key and is never stored:
+// per owner LDS holds the key (w x h), and a work area that is in turn the first-pass plane of the interpolation, the reference window of the integer
+// search (block + range each way) and the window, first-stage plane and candidate block of the fractional refinement.  Dynamic LDS, sized on the host
+// from cfg.max_pu_w / max_pu_h.  The integer search gives every position to a group of 1..64 lanes (a quarter of the block's sampled pixels each at
+// most), so that no sum crosses a wavefront; the arg-min keeps (cost, scan index) pairs, which is the strict '<' of the y-outer, x-inner scan.
+//  Control flow is uniform per owner: every lane computes the same scalar state; the per-(list, reference) state that is indexed dynamically
+// (cMvTemp, aaiMvpIdxBi, cMvPredBi) lives in LDS.
 #include "common.h"
 #include "frac_dev.h"
 #include "me_dev.h"
+#include "pu_entry_host.h"
 
 namespace {
 
@@ -25,24 +26,21 @@ constexpr int BP_WAVE_MAX = 1024;          // samples a wavefront owns
 constexpr int BP_HDR = 1024;               // bytes in front of an owner's key: see BpLds
 constexpr int BP_ST = 5;                   // ints of state per (list, reference): cMvTemp (2), aaiMvpIdxBi, cMvPredBi (2)
 
-inline __host__ __device__ int bp_r8(int v) { return (v + 7) & ~7; }
 // shorts of the work area: the fractional refinement's three buffers, or the search window
 inline __host__ __device__ int bp_work_shorts(int w, int h, int range)
 {
-  const int frac = bp_r8((w + 10) * (h + 9)) + bp_r8(w * (h + 8)) + bp_r8(w * h);
-  const int srch = bp_r8((w + 2 * range) * (h + 2 * range));
+  const int frac = frac_work_shorts(w, h), srch = frac_r8((w + 2 * range) * (h + 2 * range));
   return frac > srch ? frac : srch;
 }
-inline __host__ __device__ int bp_lds_bytes(int w, int h, int range) { return BP_HDR + 2 * (bp_r8(w * h) + bp_work_shorts(w, h, range)); }
+inline __host__ __device__ int bp_lds_bytes(int w, int h, int range) { return BP_HDR + 2 * (frac_r8(w * h) + bp_work_shorts(w, h, range)); }
 
-struct BpLds
+struct BpLds : FracOwnerLds       // frac_dev.h: bytes 0..575 of the header; F.org = the key
 {
-  FracLds F;                      // F.cost: bytes 0..511, F.sel: 512..543; F.org = the key; F.win / F.hpl / F.pred = the work area
-  vvcgpu_frac_result* fres;       // bytes 544..575
   int* st;                        // bytes 576..735: [2][4][BP_ST]
   unsigned long long* sb;         // bytes 736..799: the wavefronts' best (cost, scan index << 32 | sad) of the integer search
-  short* work;
 };
+constexpr int BP_OFF_SB = FRAC_HDR + 2 * VVCGPU_BIPRED_ME_MAX_REFS * BP_ST * 4;
+static_assert(BP_OFF_SB == 736 && BP_OFF_SB % 8 == 0 && BP_OFF_SB + 4 * 2 * 8 <= BP_HDR && BP_HDR % 16 == 0, "header layout");
 
 // motionCompensation (luma, uni; me_dev.h) of the quarter-unit vector (mvX, mvY) against `ref` (sample (0, 0) of the picture), and the key from it:
 // key = 2 org - pred, clipped when cfg.clip_for_bipred_me.  tmp: w x (h + 7) shorts.
@@ -83,7 +81,7 @@ __device__ __forceinline__ void bp_int_search(const MePu& u, const BpLds& L, con
     for (int o = 1; o < S; o <<= 1) sum += __shfl_xor(sum, o);
     if (act)
     {
-      const unsigned long long cost = (unsigned long long)(sum << u.subShift) + me_getcost(lambda, me_mvbits(predH, predV, 2, left + i, top + j));
+      const unsigned long long cost = (unsigned long long)(sum << u.subShift) + pu_getcost(lambda, me_mvbits(predH, predV, 2, left + i, top + j));
       if (cost < bestC) { bestC = cost; bestP = (unsigned)p; }
     }
   }
@@ -133,13 +131,13 @@ __device__ __forceinline__ void bp_search(const vvcgpu_bipred_me_item* __restric
     int* s = L.st + tid * BP_ST;
     s[0] = a.mv[0]; s[1] = a.mv[1]; s[2] = k; s[3] = a.mv_cand[k][0]; s[4] = a.mv_cand[k][1];
   }
-  me_sync<NT>();
+  owner_sync<NT>();
 
   int mvBi[2][2] = { { itp->mv[0][0], itp->mv[0][1] }, { itp->mv[1][0], itp->mv[1][1] } };
   int refBi[2] = { itp->ref_idx[0], itp->ref_idx[1] };
   unsigned motBits[2];
   motBits[0] = itp->bits[0] - itp->mb_bits[0];
-  if (c.mvd_l1_zero) motBits[1] = itp->mb_bits[1] + me_ref_bits(nRef[1], refBi[1]) + c.mvp_idx_cost[L.st[(4 + refBi[1]) * BP_ST + 2]];     // :1024-1036
+  if (c.mvd_l1_zero) motBits[1] = itp->mb_bits[1] + pu_ref_bits(nRef[1], refBi[1]) + c.mvp_idx_cost[L.st[(4 + refBi[1]) * BP_ST + 2]];     // :1024-1036
   else motBits[1] = itp->bits[1] - itp->mb_bits[1];
   unsigned bits2 = mbBits2 + motBits[0] + motBits[1];
   unsigned long long costBi = ~0ull;
@@ -160,7 +158,7 @@ __device__ __forceinline__ void bp_search(const vvcgpu_bipred_me_item* __restric
       const vvcgpu_bipred_me_ref& a = itp->ref[list][r];
       int* s = L.st + (list * 4 + r) * BP_ST;
       int mvpIdx = s[2], predX = s[3], predY = s[4];
-      unsigned bitsT = mbBits2 + motBits[other] + me_ref_bits(nRef[list], r) + c.mvp_idx_cost[mvpIdx];
+      unsigned bitsT = mbBits2 + motBits[other] + pu_ref_bits(nRef[list], r) + c.mvp_idx_cost[mvpIdx];
       const Pel* ref = c.ref_planes[a.plane] + (ptrdiff_t)u.posY * c.ref_stride + u.posX;
       // xSetSearchRange around cMvTemp[list][r]
       const int cx = min(u.horMax, max(u.horMin, s[0])), cy = min(u.verMax, max(u.verMin, s[1]));
@@ -168,15 +166,15 @@ __device__ __forceinline__ void bp_search(const vvcgpu_bipred_me_item* __restric
       const int top = (min(u.verMax, max(u.verMin, cy - (R << 2))) + 2) >> 2, bottom = (min(u.verMax, max(u.verMin, cy + (R << 2))) + 2) >> 2;
       const int nx = right - left + 1, ny = bottom - top + 1;              // 1 .. 2 R + 1 each
       const int swp = w + nx - 1, swr = h + ny - 1;
-      me_sync<NT>();                                                      // the work area's last readers are done
+      owner_sync<NT>();                                                   // the work area's last readers are done
       {
         const Pel* r0 = ref + (ptrdiff_t)top * c.ref_stride + left;
         for (int i = tid; i < swp * swr; i += NT) { const int y = i / swp, x = i - y * swp; L.work[i] = r0[(ptrdiff_t)y * c.ref_stride + x]; }
       }
-      me_sync<NT>();
+      owner_sync<NT>();
       int ix, iy;
       bp_int_search<NT>(u, L, L.work, swp, left, top, nx, ny, c.lambda, predX, predY, tid, ix, iy);
-      me_sync<NT>();
+      owner_sync<NT>();
       // xPatternSearchFracDIF around (ix, iy)
       const int wp = w + 10;
       {
@@ -186,13 +184,13 @@ __device__ __forceinline__ void bp_search(const vvcgpu_bipred_me_item* __restric
       vvcgpu_mvcost mc;
       mc.lambda = c.lambda; mc.pred_hor = predX; mc.pred_ver = predY; mc.cost_scale = 0; mc.imv_shift = 0;
       frac_refine_pu(L.F, w, h, wp, c.bit_depth, c.clp_min, c.clp_max, c.use_hadamard, mc, ix, iy, true, tid, NT, L.fres);
-      me_sync<NT>();
+      owner_sync<NT>();
       const int mvX = (ix << 2) + (L.fres->half_x << 1) + L.fres->qter_x, mvY = (iy << 2) + (L.fres->half_y << 1) + L.fres->qter_y;
       const unsigned mvBits = me_mvbits(predX, predY, 0, mvX, mvY);
       bitsT += mvBits;
-      unsigned long long costT = (unsigned long long)(floor(0.5 * ((double)L.fres->cost - (double)me_getcost(c.lambda, mvBits))) + (double)me_getcost(c.lambda, bitsT));
+      unsigned long long costT = (unsigned long long)(floor(0.5 * ((double)L.fres->cost - (double)pu_getcost(c.lambda, mvBits))) + (double)pu_getcost(c.lambda, bitsT));
       me_check_best_mvp(a.mv_cand, a.num_cand, c.mvp_idx_cost, c.lambda, mvX, mvY, predX, predY, mvpIdx, bitsT, costT);
-      me_sync<NT>();                                                      // every lane has read st and fres
+      owner_sync<NT>();                                                   // every lane has read st and fres
       if (tid == 0) { s[0] = mvX; s[1] = mvY; s[2] = mvpIdx; s[3] = predX; s[4] = predY; }
       const bool accepted = costT < costBi;
       if (trace && tid == 0)
@@ -212,7 +210,7 @@ __device__ __forceinline__ void bp_search(const vvcgpu_bipred_me_item* __restric
         bits2 = bitsT;
       }
     }
-    me_sync<NT>();
+    owner_sync<NT>();
     if (!changed)
     {
       if (costBi <= uniCost[0] && costBi <= uniCost[1])
@@ -224,9 +222,9 @@ __device__ __forceinline__ void bp_search(const vvcgpu_bipred_me_item* __restric
           int* s = L.st + refBi[0] * BP_ST;
           int mvpIdx = s[2], predX = s[3], predY = s[4];
           me_check_best_mvp(a.mv_cand, a.num_cand, c.mvp_idx_cost, c.lambda, mvBi[0][0], mvBi[0][1], predX, predY, mvpIdx, bits2, costBi);
-          me_sync<NT>();
+          owner_sync<NT>();
           if (tid == 0) { s[2] = mvpIdx; s[3] = predX; s[4] = predY; }
-          me_sync<NT>();
+          owner_sync<NT>();
         }
         if (!c.mvd_l1_zero)
         {
@@ -234,9 +232,9 @@ __device__ __forceinline__ void bp_search(const vvcgpu_bipred_me_item* __restric
           int* s = L.st + (4 + refBi[1]) * BP_ST;
           int mvpIdx = s[2], predX = s[3], predY = s[4];
           me_check_best_mvp(a.mv_cand, a.num_cand, c.mvp_idx_cost, c.lambda, mvBi[1][0], mvBi[1][1], predX, predY, mvpIdx, bits2, costBi);
-          me_sync<NT>();
+          owner_sync<NT>();
           if (tid == 0) { s[2] = mvpIdx; s[3] = predX; s[4] = predY; }
-          me_sync<NT>();
+          owner_sync<NT>();
         }
       }
       break;
@@ -255,21 +253,14 @@ __device__ __forceinline__ void bp_search(const vvcgpu_bipred_me_item* __restric
     o.bits = bits2; o.me_calls = calls; o.closing = closing; o.reserved = 0; o.cost = costBi;
     *res = o;
     if (trace)
-      for (unsigned k = calls; k < VVCGPU_BIPRED_ME_MAX_STEPS; k++)
-      {
-        vvcgpu_bipred_me_step t;
-        memset(&t, 0, sizeof(t));
-        trace[k] = t;
-      }
+      for (unsigned k = calls; k < VVCGPU_BIPRED_ME_MAX_STEPS; k++) zero_record(trace + k);
   }
 }
-
-__device__ __forceinline__ bool bp_side_ok(int v) { return v >= 4 && v <= 128 && (v & (v - 1)) == 0; }
 
 __device__ __forceinline__ bool bp_item_ok(const vvcgpu_bipred_me_item& it, const vvcgpu_bipred_me_cfg& c)
 {
   const int w = it.w, h = it.h;
-  if (!bp_side_ok(w) || !bp_side_ok(h) || w > c.max_cu_w || h > c.max_cu_h || w > c.max_pu_w || h > c.max_pu_h) return false;
+  if (!pu_side_pow2_ok(w) || !pu_side_pow2_ok(h) || w > c.max_cu_w || h > c.max_cu_h || w > c.max_pu_w || h > c.max_pu_h) return false;
   if (it.pos_x < 0 || it.pos_y < 0 || it.pos_x > c.pic_w - w || it.pos_y > c.pic_h - h) return false;
   if (it.sub_shift < 0 || it.sub_shift > 1 || (h >> it.sub_shift) == 0 || it.org_stride <= 0) return false;
   for (int l = 0; l < 2; l++)
@@ -288,16 +279,9 @@ __device__ __forceinline__ bool bp_item_ok(const vvcgpu_bipred_me_item& it, cons
 __device__ __forceinline__ BpLds bp_lds(unsigned char* base, int w, int h)
 {
   BpLds L;
-  L.F.cost = reinterpret_cast<unsigned long long*>(base);
-  L.F.sel = reinterpret_cast<int*>(base + 512);
-  L.fres = reinterpret_cast<vvcgpu_frac_result*>(base + 544);
-  L.st = reinterpret_cast<int*>(base + 576);
-  L.sb = reinterpret_cast<unsigned long long*>(base + 736);
-  L.F.org = reinterpret_cast<short*>(base + BP_HDR);
-  L.work = L.F.org + bp_r8(w * h);
-  L.F.win = L.work;
-  L.F.hpl = L.F.win + bp_r8((w + 10) * (h + 9));
-  L.F.pred = L.F.hpl + bp_r8(w * (h + 8));
+  frac_owner_lds(L, base, BP_HDR, w, h);
+  L.st = reinterpret_cast<int*>(base + FRAC_HDR);
+  L.sb = reinterpret_cast<unsigned long long*>(base + BP_OFF_SB);
   return L;
 }
 
@@ -307,43 +291,26 @@ __global__ __launch_bounds__(256) void bipred_me_kernel(const Pel* __restrict__ 
 {
   extern __shared__ __align__(16) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // uniform for the compiler too: item fields and loop state in scalar registers
-  const int nWaveGroups = (n + 3) >> 2;
-  if ((int)blockIdx.x < nWaveGroups)
-  {
-    const int b = blockIdx.x * 4 + wave;                                 // wavefront owners
-    if (b >= n) return;
-    const vvcgpu_bipred_me_item* it = items + b;
-    if (!bp_item_ok(*it, c) || it->w * it->h > BP_WAVE_MAX) return;      // the workgroup owner of this item answers
-    bp_search<64>(it, c, orgBase, bp_lds(smem + (size_t)wave * waveBytes, it->w, it->h), results + b,
-                  trace ? trace + (size_t)b * VVCGPU_BIPRED_ME_MAX_STEPS : nullptr, lane);
-    return;
-  }
-  const int b = blockIdx.x - nWaveGroups;                                // workgroup owners
-  if (b >= n) return;
+  const OwnerSlot o = owner_slot(n, wave);
+  if (o.leave) return;
+  const int b = o.unit;
   const vvcgpu_bipred_me_item* it = items + b;
   vvcgpu_bipred_me_step* tr = trace ? trace + (size_t)b * VVCGPU_BIPRED_ME_MAX_STEPS : nullptr;
-  if (!bp_item_ok(*it, c))                                               // outside the contract: the sentinel, nothing is read or predicted
+  if (!bp_item_ok(*it, c))                                               // outside the contract: nothing is read or predicted
   {
-    if (tid == 0)
-    {
-      vvcgpu_bipred_me_result r;
-      memset(&r, 0, sizeof(r));
-      r.cost = ~0ull;
-      results[b] = r;
-    }
-    if (tr && tid < VVCGPU_BIPRED_ME_MAX_STEPS)
-    {
-      vvcgpu_bipred_me_step s;
-      memset(&s, 0, sizeof(s));
-      tr[tid] = s;
-    }
+    if (!o.waveOwner) owner_write_sentinel(results + b, tr, VVCGPU_BIPRED_ME_MAX_STEPS, tid);
     return;
   }
-  if (it->w * it->h <= BP_WAVE_MAX) return;
-  bp_search<256>(it, c, orgBase, bp_lds(smem, it->w, it->h), results + b, tr, tid);
+  if ((it->w * it->h <= BP_WAVE_MAX) != o.waveOwner) return;             // the other kind of owner serves this item
+  if (o.waveOwner) bp_search<64>(it, c, orgBase, bp_lds(smem + (size_t)wave * waveBytes, it->w, it->h), results + b, tr, lane);
+  else bp_search<256>(it, c, orgBase, bp_lds(smem, it->w, it->h), results + b, tr, tid);
 }
 
-bool bp_host_side_ok(int v) { return v >= 4 && v <= 128 && (v & (v - 1)) == 0; }
+// the launch's LDS (cfg checked, max_pu set)
+PuOwnerLds bp_owner_lds(const vvcgpu_bipred_me_cfg& c)
+{
+  return pu_owner_lds(4, c.max_pu_w, c.max_pu_h, BP_WAVE_MAX, [&](int w, int h, int) { return bp_lds_bytes(w, h, c.bipred_search_range); });
+}
 
 }  // namespace
 
@@ -354,35 +321,13 @@ extern "C" int vvcgpu_bipred_me_batch(const vvc_pel* org_base, const vvcgpu_bipr
   if (n == 0) return VVCGPU_OK;
   VVC_CHECK_ARG(org_base && items && cfg_host && results, "bipred_me_batch: null pointer");
   vvcgpu_bipred_me_cfg c = *cfg_host;
-  VVC_CHECK_ARG(c.n_planes >= 1 && c.n_planes <= VVCGPU_BIPRED_ME_MAX_PLANES, "bipred_me_batch: n_planes %d outside 1..%d", c.n_planes, VVCGPU_BIPRED_ME_MAX_PLANES);
-  for (int i = 0; i < c.n_planes; i++) VVC_CHECK_ARG(c.ref_planes[i], "bipred_me_batch: null pointer (ref_planes[%d])", i);
-  VVC_CHECK_ARG(c.pic_w > 0 && c.pic_h > 0 && c.max_cu_w > 0 && c.max_cu_h > 0 && c.ref_stride > 0, "bipred_me_batch: geometry (picture %d x %d, CTU %d x %d, ref_stride %d)",
-                c.pic_w, c.pic_h, c.max_cu_w, c.max_cu_h, c.ref_stride);
-  VVC_CHECK_ARG(c.pic_w <= 65536 && c.pic_h <= 65536 && c.max_cu_w <= 256 && c.max_cu_h <= 256, "bipred_me_batch: geometry (picture %d x %d, CTU %d x %d)", c.pic_w,
-                c.pic_h, c.max_cu_w, c.max_cu_h);
-  VVC_CHECK_ARG(c.clp_min <= c.clp_max && c.clp_min >= -32768 && c.clp_max <= 32767, "bipred_me_batch: clip range %d..%d", c.clp_min, c.clp_max);
-  VVC_CHECK_ARG(c.lambda >= 0.0 && c.lambda < 1048576.0, "bipred_me_batch: lambda out of range");
+  if (const int rc = pu_check_frame("bipred_me_batch", c, VVCGPU_BIPRED_ME_MAX_PLANES)) return rc;
   VVC_CHECK_ARG(c.bipred_search_range >= 1 && c.bipred_search_range <= 8, "bipred_me_batch: bipred_search_range %d outside 1..8", c.bipred_search_range);
   VVC_CHECK_ARG(c.num_iter == 1 || c.num_iter == 4, "bipred_me_batch: num_iter %d (4 or 1)", c.num_iter);
-  if (c.max_pu_w == 0) c.max_pu_w = 128;
-  if (c.max_pu_h == 0) c.max_pu_h = 128;
-  VVC_CHECK_ARG(bp_host_side_ok(c.max_pu_w) && bp_host_side_ok(c.max_pu_h), "bipred_me_batch: max_pu %d x %d (sides 4, 8, .. 128, or 0)", c.max_pu_w, c.max_pu_h);
-  if (c.bit_depth > 10 || c.bit_depth < 8) { vvcgpu_set_error("bipred_me_batch: bit depth %d outside 8..10", c.bit_depth); return VVCGPU_E_UNSUPPORTED; }
-  VVC_CHECK_ARG(n < (1 << 28), "bipred_me_batch: n %d", n);
-  for (int i = c.n_planes; i < VVCGPU_BIPRED_ME_MAX_PLANES; i++) c.ref_planes[i] = nullptr;
-  // LDS of an owner: the largest need among the served shapes within max_pu that the owner kind takes
-  int waveBytes = 0, groupBytes = 0;
-  for (int w = 4; w <= c.max_pu_w; w <<= 1)
-    for (int h = 4; h <= c.max_pu_h; h <<= 1)
-    {
-      const int bytes = bp_lds_bytes(w, h, c.bipred_search_range);
-      int& dst = w * h <= BP_WAVE_MAX ? waveBytes : groupBytes;
-      if (bytes > dst) dst = bytes;
-    }
-  waveBytes = (waveBytes + 15) & ~15;
-  const size_t lds = (size_t)(4 * waveBytes > groupBytes ? 4 * waveBytes : groupBytes);
-  VVC_HIP(vvc_allow_lds(bipred_me_kernel, lds));
-  hipLaunchKernelGGL(bipred_me_kernel, dim3(cdiv(n, 4) + n), dim3(256), lds, (hipStream_t)stream, org_base, items, n, c, waveBytes, results, trace);
+  if (const int rc = pu_check_tail("bipred_me_batch", c, n, 1 << 28, pu_side_pow2_ok, "4, 8, .. 128")) return rc;
+  const PuOwnerLds L = bp_owner_lds(c);
+  VVC_HIP(vvc_allow_lds(bipred_me_kernel, L.lds));
+  hipLaunchKernelGGL(bipred_me_kernel, dim3(pu_owner_grid(n, true)), dim3(256), L.lds, (hipStream_t)stream, org_base, items, n, c, L.waveBytes, results, trace);
   VVC_LAUNCH_CHECK();
   return VVCGPU_OK;
 }

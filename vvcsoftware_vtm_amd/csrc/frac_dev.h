@@ -1,5 +1,6 @@
 // frac_dev.h -- the fractional-sample refinement of one PU whose original block and reference window are in LDS: the device body shared by
-// vvcgpu_frac_refine's general kernel (fracsearch.hip) and the bi-predictive refinement loop (bipredme.hip).
+// vvcgpu_frac_refine's general kernel (fracsearch.hip) and the translational whole-PU entries (bipredme.hip, unipredme.hip), and the LDS carve of
+// those entries' owners (frac_owner_lds).
 //
 // Reference behaviour reproduced (bit-exact): InterSearch::xPatternSearchFracDIF (EncoderLib/InterSearch.cpp:2503-2552): xExtDIFUpSamplingH
 // (:3813-3869), xPatternRefinement (:634-689, candidate order s_acMvRefineH/Q :59-83, strict '<'), xExtDIFUpSamplingQ (:3882-4093); distortion =
@@ -118,6 +119,37 @@ __device__ __forceinline__ unsigned long long dist_lds(const short* org, const s
 #define GROUP_SYNC() do { if (nw == 1) { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); } else __syncthreads(); } while (0)
 
 struct FracLds { short* org; short* win; short* hpl; short* pred; unsigned long long* cost; int* sel; };
+
+// The LDS of an owner of a translational whole-PU entry: a header, the first FRAC_HDR bytes of which are laid out here (the entry's own fields follow
+// up to its header size), then the w x h block F.org, then the work area: F.win | F.hpl | F.pred, or whatever else the entry keeps there in turn.
+constexpr int FRAC_OFF_SEL = 512;          // F.cost: bytes 0..511
+constexpr int FRAC_OFF_RES = 544;          // F.sel: bytes 512..543
+constexpr int FRAC_HDR = 576;              // fres: bytes 544..575
+static_assert(52 * 8 <= FRAC_OFF_SEL && FRAC_OFF_SEL + 2 * 4 <= FRAC_OFF_RES && FRAC_OFF_RES + sizeof(vvcgpu_frac_result) <= FRAC_HDR, "header fields overlap");
+
+inline __host__ __device__ int frac_r8(int v) { return (v + 7) & ~7; }
+// shorts of the fractional refinement's three buffers in the work area
+inline __host__ __device__ int frac_work_shorts(int w, int h) { return frac_r8((w + 10) * (h + 9)) + frac_r8(w * (h + 8)) + frac_r8(w * h); }
+
+struct FracOwnerLds
+{
+  FracLds F;
+  vvcgpu_frac_result* fres;
+  short* work;
+};
+
+// base: the owner's LDS; orgOff: the entry's header size (F.org starts there)
+__device__ __forceinline__ void frac_owner_lds(FracOwnerLds& L, unsigned char* base, int orgOff, int w, int h)
+{
+  L.F.cost = reinterpret_cast<unsigned long long*>(base);
+  L.F.sel = reinterpret_cast<int*>(base + FRAC_OFF_SEL);
+  L.fres = reinterpret_cast<vvcgpu_frac_result*>(base + FRAC_OFF_RES);
+  L.F.org = reinterpret_cast<short*>(base + orgOff);
+  L.work = L.F.org + frac_r8(w * h);
+  L.F.win = L.work;
+  L.F.hpl = L.F.win + frac_r8((w + 10) * (h + 9));
+  L.F.pred = L.F.hpl + frac_r8(w * (h + 8));
+}
 
 // One PU by `gsz` lanes (64: a wavefront, GROUP_SYNC is a wave barrier; 256: the workgroup, every wavefront of which makes the same calls).
 // L.org = the w x h original (pitch w), L.win = reference rows -4 .. h+4, columns -4 .. w+4 around the integer position (pitch wp = w + 10); L.hpl

@@ -1,5 +1,6 @@
-// me_dev.h -- pieces of the translational inter search that the whole-PU entries share (bipredme.hip, unipredme.hip): the owner's barrier, the vector
-// and reference-index bits, the luma uni prediction of a PU handed to the caller sample by sample, and xCheckBestMVP.
+// me_dev.h -- pieces of the translational inter search that the whole-PU entries share (bipredme.hip, unipredme.hip): the vector bits, the luma uni
+// prediction of a PU handed to the caller sample by sample, and xCheckBestMVP.  The owner model (split, barrier, sum, reference-index bits, getCost)
+// is owner_dev.h's; the owner's LDS header and work area are frac_dev.h's.
 //
 // Reference behaviour reproduced (bit-exact): motionCompensation -> xPredInterUni -> xPredInterBlk (CommonLib/InterPrediction.cpp:480-547) with
 // InterpolationFilter::filter / filterCopy (InterpolationFilter.cpp:205-379), clipMv (Mv.cpp:64-80), RdCost::getBitsOfVectorWithPredictor / getCost
@@ -7,15 +8,9 @@
 #pragma once
 #include "common.h"
 #include "frac_dev.h"
+#include "owner_dev.h"
 
 namespace {
-
-// NT = 64: the wavefront owns the PU; NT = 256: the workgroup does (every wavefront follows the same, uniform, control flow)
-template <int NT> __device__ __forceinline__ void me_sync()
-{
-  if (NT == 256) __syncthreads();
-  else { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }
-}
 
 struct MePu
 {
@@ -25,8 +20,6 @@ struct MePu
 };
 
 __device__ __forceinline__ unsigned me_mvbits(int predH, int predV, int scale, int x, int y) { return eg_bits((x << scale) - predH) + eg_bits((y << scale) - predV); }
-__device__ __forceinline__ unsigned long long me_getcost(double lambda, unsigned bits) { return (unsigned long long)(lambda * (double)bits); }
-__device__ __forceinline__ unsigned me_ref_bits(int nRef, int r) { return nRef > 1 ? (unsigned)(r + 1 - (r == nRef - 1 ? 1 : 0)) : 0u; }
 
 // motionCompensation (luma, uni, rounded and clipped) of the quarter-unit vector (mvX, mvY), clipMv applied, against `ref` (sample (0, 0) of the
 // picture, pitch rs): emit(i, y, x, v) receives sample i = y * w + x of the prediction, each exactly once, from the lane that computed it.
@@ -57,7 +50,7 @@ __device__ __forceinline__ void me_pred_uni(const MePu& u, const Pel* __restrict
       tmp[i] = (short)((sum + off1) >> sh1);
     }
   }
-  me_sync<NT>();
+  owner_sync<NT>();
   for (int i = tid; i < w * h; i += NT)
   {
     const int y = i >> u.lgW, x = i & (w - 1);
@@ -88,7 +81,7 @@ __device__ __forceinline__ void me_pred_uni(const MePu& u, const Pel* __restrict
     else v = blk[(ptrdiff_t)y * rs + x];                                 // filterCopy, first and last: no clip
     emit(i, y, x, v);
   }
-  me_sync<NT>();
+  owner_sync<NT>();
 }
 
 // xCheckBestMVP (:1537-1603) over the candidates cand[0 .. numCand); the reference's CHECK (cand[mvpIdx] == pred) is the caller's contract
@@ -110,7 +103,7 @@ __device__ __forceinline__ void me_check_best_mvp(const int32_t (*cand)[2], int 
     mvpIdx = bestIdx;
     const unsigned orgB = bits;
     bits = orgB - (unsigned)orgBits + (unsigned)bestBits;
-    cost = (cost - me_getcost(lambda, orgB)) + me_getcost(lambda, bits);
+    cost = (cost - pu_getcost(lambda, orgB)) + pu_getcost(lambda, bits);
   }
 }
 

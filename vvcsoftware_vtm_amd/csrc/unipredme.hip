@@ -7,7 +7,8 @@
 //
 // Design: the (list, reference index) searches of a PU depend on each other only through the list-1 shortcut and the final comparisons, and one TZ
 // search is a chain of about 20 dependent rounds, so the unit of ownership is the SEARCH: launch 1 gives each of the n x (n_ref[0] + n_ref[1])
-// searches an owner -- one wavefront up to UP_WAVE_MAX samples, the workgroup's four above, the grid split of bipredme.hip -- which chooses the AMVP
+// searches an owner -- one wavefront up to UP_WAVE_MAX samples, the workgroup's four above (the owner model: owner_dev.h and docs/KERNELS.md, "Owners
+// of the whole-PU entries") -- which chooses the AMVP
 // predictor (prediction of each candidate straight into its SAD against the original in LDS, never stored), runs the TZ state machine as a team
 // (the sub-sampled original as packed pairs in the work area), the fractional refinement (window, first-stage plane and candidate block in the same
 // work area) and xCheckBestMVP, and writes its record into the PU's result.  A list-1 reference that takes list 0's vector only chooses its
@@ -17,6 +18,7 @@
 #include "frac_dev.h"
 #include "me_dev.h"
 #include "tz_dev.h"
+#include "pu_entry_host.h"
 
 namespace {
 
@@ -24,48 +26,35 @@ constexpr int UP_WAVE_MAX = 1024;                       // samples a wavefront o
 constexpr int UP_SEG = 64 * TZ_SEG_REGS + 4;            // dwords of one wavefront's raster chunk
 constexpr int UP_HDR = 1024;                            // bytes in front of the raster chunks: see up_lds
 
-inline __host__ __device__ int up_r8(int v) { return (v + 7) & ~7; }
 inline __host__ __device__ int up_hdr_bytes(int nt) { return UP_HDR + (nt >> 6) * UP_SEG * 4; }
-// shorts of the work area: the fractional refinement's three buffers (the first pass of a prediction, w x (h + 7), and the packed original of the
-// integer search, at most w x h, are smaller)
-inline __host__ __device__ int up_work_shorts(int w, int h) { return up_r8((w + 10) * (h + 9)) + up_r8(w * (h + 8)) + up_r8(w * h); }
-inline __host__ __device__ int up_lds_bytes(int w, int h, int nt) { return up_hdr_bytes(nt) + 2 * (up_r8(w * h) + up_work_shorts(w, h)); }
+// the work area holds the fractional refinement's three buffers (the first pass of a prediction, w x (h + 7), and the packed original of the integer
+// search, at most w x h, are smaller)
+inline __host__ __device__ int up_lds_bytes(int w, int h, int nt) { return up_hdr_bytes(nt) + 2 * (frac_r8(w * h) + frac_work_shorts(w, h)); }
 
-struct UpLds
+struct UpLds : FracOwnerLds       // frac_dev.h: bytes 0..575 of the header; F.org = the original
 {
-  FracLds F;                      // F.cost: bytes 0..511, F.sel: 512..543; F.org = the original; F.win / F.hpl / F.pred = the work area
-  vvcgpu_frac_result* fres;       // bytes 544..575
   unsigned long long* keyL;       // bytes 576..607: the wavefronts' keys of a TZ round
   int* negL;                      // bytes 608..623
   unsigned long long* part;       // bytes 640..671: the wavefronts' partial SADs of a candidate's prediction
   unsigned* seg;                  // UP_HDR ..: one raster chunk per wavefront
-  short* work;
 };
+static_assert(FRAC_HDR == 576 && 640 + 4 * 8 <= UP_HDR && UP_HDR % 16 == 0, "header layout");
 
 template <int NT> __device__ __forceinline__ UpLds up_lds(unsigned char* base, int w, int h)
 {
   UpLds L;
-  L.F.cost = reinterpret_cast<unsigned long long*>(base);
-  L.F.sel = reinterpret_cast<int*>(base + 512);
-  L.fres = reinterpret_cast<vvcgpu_frac_result*>(base + 544);
-  L.keyL = reinterpret_cast<unsigned long long*>(base + 576);
+  frac_owner_lds(L, base, up_hdr_bytes(NT), w, h);
+  L.keyL = reinterpret_cast<unsigned long long*>(base + FRAC_HDR);
   L.negL = reinterpret_cast<int*>(base + 608);
   L.part = reinterpret_cast<unsigned long long*>(base + 640);
   L.seg = reinterpret_cast<unsigned*>(base + UP_HDR);
-  L.F.org = reinterpret_cast<short*>(base + up_hdr_bytes(NT));
-  L.work = L.F.org + up_r8(w * h);
-  L.F.win = L.work;
-  L.F.hpl = L.F.win + up_r8((w + 10) * (h + 9));
-  L.F.pred = L.F.hpl + up_r8(w * (h + 8));
   return L;
 }
-
-__device__ __forceinline__ bool up_side_ok(int v) { return v >= 4 && v <= 128 && (v & (v - 1)) == 0; }
 
 __device__ __forceinline__ bool up_item_ok(const vvcgpu_unipred_me_item& it, const vvcgpu_unipred_me_cfg& c)
 {
   const int w = it.w, h = it.h;
-  if (!up_side_ok(w) || !up_side_ok(h) || w > c.max_cu_w || h > c.max_cu_h || w > c.max_pu_w || h > c.max_pu_h) return false;
+  if (!pu_side_pow2_ok(w) || !pu_side_pow2_ok(h) || w > c.max_cu_w || h > c.max_cu_h || w > c.max_pu_w || h > c.max_pu_h) return false;
   if (it.pos_x < 0 || it.pos_y < 0 || it.pos_x > c.pic_w - w || it.pos_y > c.pic_h - h) return false;
   if (it.sub_shift < 0 || it.sub_shift > 1 || (h >> it.sub_shift) == 0 || it.org_stride <= 0) return false;
   if ((it.tz_flags & ~VVCGPU_TZ_EXTENDED) != 0) return false;
@@ -97,7 +86,7 @@ __device__ __forceinline__ void up_search(const vvcgpu_unipred_me_item* __restri
   const Pel* plane = c.ref_planes[c.ref_plane[list][r]];
 
   for (int i = tid; i < w * h; i += NT) L.F.org[i] = u.org[(ptrdiff_t)(i >> u.lgW) * u.os + (i & (w - 1))];
-  me_sync<NT>();
+  owner_sync<NT>();
 
   // xEstimateMvPredAMVP (bFilled): template cost of every candidate, the best by '>' in candidate order
   unsigned long long tmpl[2] = { 0ull, 0ull }, bestTmpl = ~0ull;
@@ -109,21 +98,11 @@ __device__ __forceinline__ void up_search(const vvcgpu_unipred_me_item* __restri
     unsigned sad = 0;
     me_pred_uni<NT>(u, plane, c.ref_stride, c.bit_depth, c.clp_min, c.clp_max, a.mv_cand[i][0], a.mv_cand[i][1], L.work, tid,
                     [&](int k, int, int, int v) { sad += (unsigned)abs((int)L.F.org[k] - v); });
-    unsigned long long s = sad;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    if (NT == 256)
-    {
-      if (lane == 0) L.part[wave] = s;
-      __syncthreads();
-      s = L.part[0] + L.part[1] + L.part[2] + L.part[3];
-      __syncthreads();                                                   // part is written again by the next candidate
-    }
-    tmpl[i] = s + me_getcost(c.lambda, c.mvp_idx_cost[i]);
+    tmpl[i] = owner_sum<NT>(sad, L.part, tid) + pu_getcost(c.lambda, c.mvp_idx_cost[i]);
     if (bestTmpl > tmpl[i]) { bestTmpl = tmpl[i]; mvpIdx = i; }
   }
   int predX = a.mv_cand[mvpIdx][0], predY = a.mv_cand[mvpIdx][1];
-  unsigned bits = itp->mb_bits[list] + me_ref_bits(c.n_ref[list], r) + c.mvp_idx_cost[mvpIdx];
+  unsigned bits = itp->mb_bits[list] + pu_ref_bits(c.n_ref[list], r) + c.mvp_idx_cost[mvpIdx];
 
   if (up_shortcut(c, list, r))                                           // list 0's vector: the decision step finishes this record
   {
@@ -159,7 +138,7 @@ __device__ __forceinline__ void up_search(const vvcgpu_unipred_me_item* __restri
                      a.pred2[0], a.pred2[1], false, [](const TzRound&, const TzRange&, int) { return false; });
     ix = s.bestX; iy = s.bestY;
   }
-  me_sync<NT>();                                                         // the packed original's last readers are done
+  owner_sync<NT>();                                                      // the packed original's last readers are done
 
   // xPatternSearchFracDIF around (ix, iy)
   const int wp = w + 10;
@@ -170,11 +149,11 @@ __device__ __forceinline__ void up_search(const vvcgpu_unipred_me_item* __restri
   vvcgpu_mvcost mc;
   mc.lambda = c.lambda; mc.pred_hor = predX; mc.pred_ver = predY; mc.cost_scale = 0; mc.imv_shift = 0;
   frac_refine_pu(L.F, w, h, wp, c.bit_depth, c.clp_min, c.clp_max, c.use_hadamard, mc, ix, iy, true, tid, NT, L.fres);
-  me_sync<NT>();
+  owner_sync<NT>();
   const int mvX = (ix << 2) + (L.fres->half_x << 1) + L.fres->qter_x, mvY = (iy << 2) + (L.fres->half_y << 1) + L.fres->qter_y;
   const unsigned mvBits = me_mvbits(predX, predY, 0, mvX, mvY);
   bits += mvBits;
-  unsigned long long cost = (unsigned long long)(floor(1.0 * ((double)L.fres->cost - (double)me_getcost(c.lambda, mvBits))) + (double)me_getcost(c.lambda, bits));
+  unsigned long long cost = (unsigned long long)(floor(1.0 * ((double)L.fres->cost - (double)pu_getcost(c.lambda, mvBits))) + (double)pu_getcost(c.lambda, bits));
   me_check_best_mvp(a.mv_cand, a.num_cand, c.mvp_idx_cost, c.lambda, mvX, mvY, predX, predY, mvpIdx, bits, cost);
   if (tid == 0)
   {
@@ -190,15 +169,14 @@ __global__ __launch_bounds__(256) void unipred_search_kernel(const Pel* __restri
 {
   extern __shared__ __align__(16) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int S = c.n_ref[0] + c.n_ref[1], total = n * S, nWaveGroups = (total + 3) >> 2;
-  const bool waveOwner = (int)blockIdx.x < nWaveGroups;
-  const int o = waveOwner ? (int)blockIdx.x * 4 + wave : (int)blockIdx.x - nWaveGroups;     // search o = search k of PU b
-  if (o >= total) return;
-  const int b = o / S, k = o - b * S, list = k >= c.n_ref[0] ? 1 : 0, r = list ? k - c.n_ref[0] : k;
+  const int S = c.n_ref[0] + c.n_ref[1];
+  const OwnerSlot o = owner_slot(n * S, wave);                          // unit = search k of PU b
+  if (o.leave) return;
+  const int b = o.unit / S, k = o.unit - b * S, list = k >= c.n_ref[0] ? 1 : 0, r = list ? k - c.n_ref[0] : k;
   const vvcgpu_unipred_me_item* it = items + b;
   if (!up_item_ok(*it, c)) return;                                       // the decision step writes the sentinel
-  if ((it->w * it->h <= UP_WAVE_MAX) != waveOwner) return;               // the other kind of owner serves this item
-  if (waveOwner) up_search<64>(it, c, orgBase, smem + (size_t)wave * waveBytes, list, r, &results[b].s[list][r], lane);
+  if ((it->w * it->h <= UP_WAVE_MAX) != o.waveOwner) return;               // the other kind of owner serves this item
+  if (o.waveOwner) up_search<64>(it, c, orgBase, smem + (size_t)wave * waveBytes, list, r, &results[b].s[list][r], lane);
   else up_search<256>(it, c, orgBase, smem, list, r, &results[b].s[list][r], tid);
 }
 
@@ -237,9 +215,9 @@ __global__ __launch_bounds__(256) void unipred_decide_kernel(const vvcgpu_unipre
         int mvpIdx = s.mvp_idx, predX = a.mv_cand[mvpIdx][0], predY = a.mv_cand[mvpIdx][1];
         s.mv[0] = R->s[0][k].mv[0]; s.mv[1] = R->s[0][k].mv[1];
         unsigned long long cost = costL0[k];
-        cost -= me_getcost(c.lambda, bitsL0[k]);
+        cost -= pu_getcost(c.lambda, bitsL0[k]);
         unsigned bits = s.bits + me_mvbits(predX, predY, 0, s.mv[0], s.mv[1]);
-        cost += me_getcost(c.lambda, bits);
+        cost += pu_getcost(c.lambda, bits);
         me_check_best_mvp(a.mv_cand, a.num_cand, c.mvp_idx_cost, c.lambda, s.mv[0], s.mv[1], predX, predY, mvpIdx, bits, cost);
         s.mvp_idx = mvpIdx; s.bits = bits; s.cost = cost;
         R->s[list][r] = s;
@@ -279,7 +257,8 @@ __global__ __launch_bounds__(256) void unipred_decide_kernel(const vvcgpu_unipre
   outItems[b] = o;
 }
 
-bool up_host_side_ok(int v) { return v >= 4 && v <= 128 && (v & (v - 1)) == 0; }
+// the launch's LDS (cfg checked, max_pu set)
+PuOwnerLds up_owner_lds(const vvcgpu_unipred_me_cfg& c) { return pu_owner_lds(4, c.max_pu_w, c.max_pu_h, UP_WAVE_MAX, up_lds_bytes); }
 
 }  // namespace
 
@@ -290,47 +269,19 @@ extern "C" int vvcgpu_unipred_me_batch(const vvc_pel* org_base, const vvcgpu_uni
   if (n == 0) return VVCGPU_OK;
   VVC_CHECK_ARG(org_base && items && cfg_host && results, "unipred_me_batch: null pointer");
   vvcgpu_unipred_me_cfg c = *cfg_host;
-  VVC_CHECK_ARG(c.n_planes >= 1 && c.n_planes <= VVCGPU_UNIPRED_ME_MAX_PLANES, "unipred_me_batch: n_planes %d outside 1..%d", c.n_planes, VVCGPU_UNIPRED_ME_MAX_PLANES);
-  for (int i = 0; i < c.n_planes; i++) VVC_CHECK_ARG(c.ref_planes[i], "unipred_me_batch: null pointer (ref_planes[%d])", i);
-  VVC_CHECK_ARG(c.pic_w > 0 && c.pic_h > 0 && c.max_cu_w > 0 && c.max_cu_h > 0 && c.ref_stride > 0, "unipred_me_batch: geometry (picture %d x %d, CTU %d x %d, ref_stride %d)",
-                c.pic_w, c.pic_h, c.max_cu_w, c.max_cu_h, c.ref_stride);
-  VVC_CHECK_ARG(c.pic_w <= 65536 && c.pic_h <= 65536 && c.max_cu_w <= 256 && c.max_cu_h <= 256, "unipred_me_batch: geometry (picture %d x %d, CTU %d x %d)", c.pic_w,
-                c.pic_h, c.max_cu_w, c.max_cu_h);
-  VVC_CHECK_ARG(c.clp_min <= c.clp_max && c.clp_min >= -32768 && c.clp_max <= 32767, "unipred_me_batch: clip range %d..%d", c.clp_min, c.clp_max);
-  VVC_CHECK_ARG(c.lambda >= 0.0 && c.lambda < 1048576.0, "unipred_me_batch: lambda out of range");
-  VVC_CHECK_ARG(c.n_ref[0] >= 1 && c.n_ref[0] <= VVCGPU_UNIPRED_ME_MAX_REFS && c.n_ref[1] >= 0 && c.n_ref[1] <= VVCGPU_UNIPRED_ME_MAX_REFS,
-                "unipred_me_batch: n_ref %d, %d (list 0: 1..4, list 1: 0..4)", c.n_ref[0], c.n_ref[1]);
-  for (int l = 0; l < 2; l++)
-    for (int r = 0; r < c.n_ref[l]; r++)
-    {
-      VVC_CHECK_ARG(c.ref_plane[l][r] >= 0 && c.ref_plane[l][r] < c.n_planes, "unipred_me_batch: ref_plane[%d][%d] %d outside [0, %d)", l, r, c.ref_plane[l][r], c.n_planes);
-      VVC_CHECK_ARG(c.search_range[l][r] >= 1 && c.search_range[l][r] <= 256, "unipred_me_batch: search_range[%d][%d] %d outside 1..256", l, r, c.search_range[l][r]);
-    }
-  for (int r = 0; r < c.n_ref[1]; r++)
-    VVC_CHECK_ARG(c.list1_to_list0[r] >= -1 && c.list1_to_list0[r] < c.n_ref[0], "unipred_me_batch: list1_to_list0[%d] %d outside [-1, %d)", r, c.list1_to_list0[r], c.n_ref[0]);
-  if (c.max_pu_w == 0) c.max_pu_w = 128;
-  if (c.max_pu_h == 0) c.max_pu_h = 128;
-  VVC_CHECK_ARG(up_host_side_ok(c.max_pu_w) && up_host_side_ok(c.max_pu_h), "unipred_me_batch: max_pu %d x %d (sides 4, 8, .. 128, or 0)", c.max_pu_w, c.max_pu_h);
-  if (c.bit_depth > 10 || c.bit_depth < 8) { vvcgpu_set_error("unipred_me_batch: bit depth %d outside 8..10", c.bit_depth); return VVCGPU_E_UNSUPPORTED; }
-  VVC_CHECK_ARG(n < (1 << 27), "unipred_me_batch: n %d", n);
-  for (int i = c.n_planes; i < VVCGPU_UNIPRED_ME_MAX_PLANES; i++) c.ref_planes[i] = nullptr;
-  // LDS of an owner: the largest need among the served shapes within max_pu that the owner kind takes
-  int waveBytes = 0, groupBytes = 0;
-  for (int w = 4; w <= c.max_pu_w; w <<= 1)
-    for (int h = 4; h <= c.max_pu_h; h <<= 1)
-    {
-      const bool wv = w * h <= UP_WAVE_MAX;
-      const int bytes = up_lds_bytes(w, h, wv ? 64 : 256);
-      int& dst = wv ? waveBytes : groupBytes;
-      if (bytes > dst) dst = bytes;
-    }
-  waveBytes = (waveBytes + 15) & ~15;
-  const size_t lds = (size_t)(4 * waveBytes > groupBytes ? 4 * waveBytes : groupBytes);
+  if (const int rc = pu_check_frame("unipred_me_batch", c, VVCGPU_UNIPRED_ME_MAX_PLANES)) return rc;
+  const auto searchRangeOk = [&](int l, int r)
+  {
+    VVC_CHECK_ARG(c.search_range[l][r] >= 1 && c.search_range[l][r] <= 256, "unipred_me_batch: search_range[%d][%d] %d outside 1..256", l, r, c.search_range[l][r]);
+    return VVCGPU_OK;
+  };
+  if (const int rc = pu_check_lists("unipred_me_batch", c, VVCGPU_UNIPRED_ME_MAX_REFS, searchRangeOk)) return rc;
+  if (const int rc = pu_check_tail("unipred_me_batch", c, n, 1 << 27, pu_side_pow2_ok, "4, 8, .. 128")) return rc;
+  const PuOwnerLds L = up_owner_lds(c);
   const int total = n * (c.n_ref[0] + c.n_ref[1]);
   hipStream_t st = (hipStream_t)stream;
-  VVC_HIP(vvc_allow_lds(unipred_search_kernel, lds));
-  const int groupOwners = c.max_pu_w * c.max_pu_h > UP_WAVE_MAX ? total : 0;      // no served item is workgroup-owned when max_pu says so
-  hipLaunchKernelGGL(unipred_search_kernel, dim3(cdiv(total, 4) + groupOwners), dim3(256), lds, st, org_base, items, n, c, waveBytes, results);
+  VVC_HIP(vvc_allow_lds(unipred_search_kernel, L.lds));
+  hipLaunchKernelGGL(unipred_search_kernel, dim3(pu_owner_grid(total, L.groupBytes != 0)), dim3(256), L.lds, st, org_base, items, n, c, L.waveBytes, results);
   VVC_LAUNCH_CHECK();
   hipLaunchKernelGGL(unipred_decide_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, items, n, c, results, bipred_items_out);
   VVC_LAUNCH_CHECK();
