@@ -15,6 +15,8 @@ ap.add_argument("--width", type=int, default=3840)
 ap.add_argument("--height", type=int, default=2160)
 ap.add_argument("--reps", type=int, default=3)
 ap.add_argument("--only", default="")
+ap.add_argument("--rotate", type=int, default=int(os.environ.get("ROTATE", "1")),
+                help="input sets the pictures cycle through (bench.py: 12; default: ROTATE of the environment, else 1: every picture reads the same addresses)")
 a = ap.parse_args()
 wl = Workload(a.width, a.height, 10)
 
@@ -44,7 +46,7 @@ class Span:
 st = None
 t = Timer()
 for i in range(a.reps + 1):
-    st, out = wl.run_gpu(st, t)
+    st, out = wl.run_gpu(st, t, rotate=a.rotate)
 torch.cuda.synchronize()
 for k, v in t.ev.items():
     if a.only in k:

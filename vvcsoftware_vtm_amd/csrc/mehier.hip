@@ -21,6 +21,10 @@
 //     first columns of the row below) and are requested one super-block ahead; tables and lane descriptors are set up once per workgroup.
 //   * The SAD loop is the QUAD form of the strip kernels (raster_dev.h): a lane owns four consecutive raster columns (0 / 5 / 10 / 15 samples
 //     into one span of LDS), the original rows are wave-uniform scalar operands from a packed copy (even + odd-shifted layout per chunk-row).
+//     The packed rows are written by the launch in front (mh_pack_org_kernel) and L2 keeps nothing across a launch boundary, so the first scalar load of
+//     every 128-byte line would go to the memory side -- with a look-ahead of one stage, and all four waves of a SIMD (same quadrant) waiting for the same
+//     row.  One wave therefore TOUCHES the lines of the run's next super-block with plain vector loads while the current one is searched (mh_touch.h: four
+//     contiguous runs, 64 / 128 lines), and the first super-block of a run its own lines in front of its window fill.
 //   * A unit of work = (32x32 quadrant, 64 flattened (raster row, column quad) slots): the wave walks the quadrant's four 16x16 sub-blocks one
 //     after the other with the SAME lane -> position map, so the 32x32 SAD of a lane's four positions is a register sum; the 64x64 SAD meets in
 //     an LDS surface (one ds_add_u32 per position and quadrant).  39 x 10 quads = 390 slots = 7 slot waves x 4 quadrants = 28 units = two rounds of
@@ -34,6 +38,7 @@
 //     reads beyond what the per-size searches of the existing blocks read.
 #include "common.h"
 #include "raster_dev.h"
+#include "mh_touch.h"
 
 namespace {
 
@@ -291,6 +296,21 @@ __device__ __forceinline__ void mh_unit(const unsigned* orgPacked, const MhGeom&
   }
 }
 
+// One wave touches every 128-byte line of a super-block's packed original rows (mh_touch.h: at most 128 lines, two per lane) with plain vector loads, so that
+// the lines sit in the XCD's L2 when the units' scalar loads ask for them.  The form of pf[]: loads into zeroed registers, consumed by the caller later.
+__device__ __forceinline__ void mh_touch_lines(const unsigned* orgPacked, const MhTouch& t, int lane, unsigned (&v)[2])
+{
+  const unsigned char* p = reinterpret_cast<const unsigned char*>(orgPacked);
+#pragma unroll
+  for (int j = 0; j < 2; j++)
+  {
+    const unsigned long long o = mh_touch_line(t, lane + 64 * j);
+    v[j] = 0u;
+    if (o != ~0ull) v[j] = *reinterpret_cast<const unsigned*>(p + o);
+  }
+}
+constexpr int MH_TOUCH_WAVE = 15;                      // one of the four waves without a second-round unit
+
 __global__ __launch_bounds__(1024) void me_hier_kernel(const unsigned* orgPacked, const Pel* __restrict__ ref, int rs, MhGeom g, vvcgpu_mvcost mv,
                                                        vvcgpu_search_best* __restrict__ r16, vvcgpu_search_best* __restrict__ r32, vvcgpu_search_best* __restrict__ r64,
                                                        vvcgpu_search_best* __restrict__ d16, vvcgpu_search_best* __restrict__ d32, vvcgpu_search_best* __restrict__ d64,
@@ -312,7 +332,6 @@ __global__ __launch_bounds__(1024) void me_hier_kernel(const unsigned* orgPacked
   __shared__ vvcgpu_search_best* outPtr[6];
   __shared__ vvcgpu_mvcost mvL;
   const int tid = threadIdx.x, lane = tid & 63;
-  const int chunk = (g.total + 7) >> 3;                                          // XCD-aware order: every XCD gets a contiguous run of super-blocks
   // what does not depend on the super-block, once per workgroup: the rate tables, the spans of the +-D grid, and (below) what every lane of a
   // slot wave works on -- the window of every super-block starts at the same offset from a 16-byte boundary (64 columns / 64 rows of an 8-sample
   // aligned stride apart)
@@ -351,21 +370,22 @@ __global__ __launch_bounds__(1024) void me_hier_kernel(const unsigned* orgPacked
       if (u < 4 * nsw) mh_lane(sw * 64 + lane, g, T, off, nq, nslots, ndl, LU[r]);
     }
   }
-  // persistent: workgroup b walks a contiguous run of super-blocks of its XCD's chunk -- a workgroup owns a CU (150 KB of LDS), and a new workgroup per
+  // persistent, XCD-aware order (mh_touch.h: mh_run_of): workgroup b walks a contiguous run of super-blocks of its XCD's chunk -- a workgroup owns a CU (150 KB of LDS), and a new workgroup per
   // super-block pays the dispatch of sixteen waves and the argument loads with nothing else running on the CU.  SLIDING WINDOW: the next super-block of
   // a run is the right-hand neighbour, whose window shares 190 of its 254 columns; LDS is addressed linearly, so the shared columns stay where they are
   // when every address moves on by 32 dwords (64 samples), and the 64 new columns of a row land behind its old end: in the row padding and in the
   // first -- now dead -- 64 columns of the row below (the last row runs into 1 KB of slack).  A slide loads 8 of 33 quads per row.
-  const int perX = (int)(gridDim.x >> 3), runLen = (chunk + perX - 1) / perX, kk0 = (int)(blockIdx.x >> 3) * runLen;
+  const MhRun run = mh_run_of(g.total, (int)gridDim.x, (int)blockIdx.x);
+  const int kk0 = run.kk0;
   int slide = 0, pfQ0 = 0;
   bool pfHave = false;
   uint4 pf[2];
+  unsigned tch[2] = { 0u, 0u };                                                  // the touch of the next super-block's packed original rows (below)
   // (row, column) of the run's super-blocks: one division per run, then a step to the right with wrap (the items of a run are consecutive)
-  int sbyRun = ((int)(blockIdx.x & 7) * chunk + kk0) / g.nsbx, sbxRun = ((int)(blockIdx.x & 7) * chunk + kk0) - sbyRun * g.nsbx;
-  for (int kk = kk0; kk < kk0 + runLen && kk < chunk; kk++)
+  int sbyRun = (run.chunk0 + kk0) / g.nsbx, sbxRun = (run.chunk0 + kk0) - sbyRun * g.nsbx;
+  for (int kk = kk0; mh_run_has(run, kk, g.total); kk++)
   {
-  const int item = (int)(blockIdx.x & 7) * chunk + kk;
-  if (item >= g.total) break;
+  const int item = run.chunk0 + kk;
   const int sby = sbyRun, sbx = sbxRun;
   if (++sbxRun == g.nsbx) { sbxRun = 0; sbyRun++; }
   const int nsubx = min(4, g.n16x - 4 * sbx), nsuby = min(4, g.n16y - 4 * sby);
@@ -389,6 +409,7 @@ __global__ __launch_bounds__(1024) void me_hier_kernel(const unsigned* orgPacked
   const int rsQ = rs >> 3;
   // the quads (row, q) of a slide that this thread moves: items tid and tid + 1024 of nNew x winRows
   auto slideItem = [&](int it, int q0, int& row, int& q) { row = it >> 3; q = q0 + (it & 7); };     // (a slide is always 8 quads per row: both windows full width)
+  asm volatile("" :: "v"(tch[0]), "v"(tch[1]));                                  // the touch requested a super-block ago ends here: nothing is done with the values
   if (pfHave)                                                                    // requested while the previous super-block was searched
   {
     slide++;
@@ -410,11 +431,17 @@ __global__ __launch_bounds__(1024) void me_hier_kernel(const unsigned* orgPacked
   else
   {
     slide = 0;
+    // the first super-block of a run: nobody touched its packed original rows a super-block ago.  Its own lines, in front of the window's requests,
+    // whose latency covers them
+    unsigned own[2] = { 0u, 0u };
+    if (wave == MH_TOUCH_WAVE && kk == kk0) mh_touch_lines(orgPacked, mh_touch_range(g.n16x, g.n16y, g.hs, sbx, sby, item, g.total), lane, own);
     fill_window_cols<9>(refL, reinterpret_cast<const uint4*>(ref + (winOff - off)), rs >> 3, winRows, MH_PITCH, nQuads, tid, (int)blockDim.x);
+    asm volatile("" :: "v"(own[0]), "v"(own[1]));
   }
   // the right-hand neighbour's new columns, if it is the next super-block of this run: two 16-byte loads per thread, in flight during the search
   pfHave = false;
-  if (kk + 1 < kk0 + runLen && kk + 1 < chunk && item + 1 < g.total && sbx + 1 < g.nsbx && slide < MH_MAXSLIDE)      // wave-uniform
+  const bool hasNext = mh_run_has(run, kk + 1, g.total);                          // wave-uniform
+  if (hasNext && sbx + 1 < g.nsbx && slide < MH_MAXSLIDE)
   {
     const int nsubxN = min(4, g.n16x - 4 * (sbx + 1)), nQuadsN = (((g.nR - 1) * 5 + 16 * nsubxN - 1 + off) >> 3) + 1;
     pfQ0 = nQuads - 8;
@@ -443,6 +470,13 @@ __global__ __launch_bounds__(1024) void me_hier_kernel(const unsigned* orgPacked
   // LDS-only barrier: __syncthreads() also waits for vmcnt(0), i.e. for the neighbour's columns that were requested just above.  The first super-block
   // of the run: its original rows are packed here by every thread (behind the window's requests), and the barrier is the full one (stores complete)
   asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+  // The packed original rows of the run's next super-block, whether the window slides to it or not (a run that wraps to the next row of super-blocks
+  // profits too).  mh_pack_org_kernel wrote them in the launch before, L2 does not keep lines across a launch boundary, and the units ask for a row only
+  // one stage (~500 cycles) before they sum it -- all four waves of a SIMD the same row at the same moment: a first touch that goes to the memory side
+  // stalls the SIMD.  Touched here, a super-block (~22 us) ahead, the lines are in L2 when the scalar loads arrive.  (Behind the barrier: in front of it the
+  // touching wave's address arithmetic kept the fifteen others waiting -- window staged after 2.5 k instead of 2.1 k cycles; this wave has no second-round unit.)
+  tch[0] = tch[1] = 0u;
+  if (wave == MH_TOUCH_WAVE && hasNext) mh_touch_lines(orgPacked, mh_touch_range(g.n16x, g.n16y, g.hs, sbxRun, sbyRun, item + 1, g.total), lane, tch);
   if (stamp && tid == 0) diag[1] = __builtin_amdgcn_s_memtime();
   if (diag && stampK >= 0 && tid == 0) diag[40 + 1 * 4 + stampK] = __builtin_amdgcn_s_memtime();
 
