@@ -8,12 +8,13 @@ import ctypes
 import numpy as np
 
 import affine_me_cases as amc
+import pu_search_kit as kit
 from oraclelib import oracle, p
+from pu_search_kit import U64_MAX, pad, planes_and_mean_org, ref_bits, vec3
 from vvcsoftware_vtm_amd import abi
 
 MARGIN = amc.MARGIN         # samples of edge padding around a reference plane: CTU 128 + 8 (vector clip) + 4 (filter taps), rounded up
 MAX_STEPS = abi.AFFINE_BIPRED_MAX_STEPS
-U64_MAX = 0xFFFFFFFFFFFFFFFF
 U32 = 0xFFFFFFFF
 SIDES = (16, 32, 64, 128)
 
@@ -23,11 +24,6 @@ def cfg_dict(lambda_, pic_w, pic_h, bit_depth, num_iter=4, pick_list_by_cost=0, 
     return dict(lambda_=float(lambda_), pic_w=pic_w, pic_h=pic_h, max_cu=max_cu, bit_depth=bit_depth, clp_min=0, clp_max=(1 << bit_depth) - 1,
                 num_iter=num_iter, pick_list_by_cost=int(pick_list_by_cost), mvd_l1_zero=int(mvd_l1_zero), clip_key=int(clip_key),
                 affine_type=int(affine_type), mvp_idx_cost=tuple(mvp_idx_cost))
-
-
-def ref_bits(n_ref, r):
-    """the reference index bits of :2945-2952"""
-    return (r + 1 - (1 if r == n_ref - 1 else 0)) if n_ref > 1 else 0
 
 
 def item_ok(it, c, n_planes, max_pu=(128, 128)):
@@ -45,10 +41,6 @@ def item_ok(it, c, n_planes, max_pu=(128, 128)):
             if not 0 <= int(a["plane"]) < n_planes or not 1 <= int(a["num_cand"]) <= 2 or not 0 <= int(a["mvp_idx"]) < int(a["num_cand"]):
                 return False
     return True
-
-
-def vec3(a):
-    return [[int(a[k][0]), int(a[k][1])] for k in range(3)]
 
 
 class Searcher:
@@ -208,37 +200,7 @@ def search_all(org, planes_pad, cfg, items, max_pu=(128, 128)):
     return res, trace
 
 
-def passes(trace_row, calls):
-    """iterations of the loop an item ran (:2892): a new pass starts where the list changes or the reference index does not rise"""
-    n = 0
-    for k in range(int(calls)):
-        if k == 0 or trace_row[k]["list"] != trace_row[k - 1]["list"] or trace_row[k]["ref"] <= trace_row[k - 1]["ref"]:
-            n += 1
-    return n
-
-
 # ---- inputs ------------------------------------------------------------------------------------------------------------------------------------
-def pad(planes, margin=MARGIN):
-    """[n][H][W] -> [n][H + 2 M][W + 2 M], edges replicated"""
-    return np.ascontiguousarray(np.pad(planes, ((0, 0), (margin, margin), (margin, margin)), mode="edge"))
-
-
-def make_planes(rng, n_planes, W, H, bd):
-    """shifted copies of one texture (each with its own noise) and an original that is their mean plus noise: bi-prediction pays, the searches move"""
-    planes = np.stack([texture(rng, H, W, bd, 1.5 * k) for k in range(n_planes)])
-    org = np.clip(planes.astype(np.int32).mean(axis=0) + rng.integers(-6, 7, (H, W)), 0, (1 << bd) - 1).astype(np.int16)
-    return planes, org
-
-
-def texture(rng, h, w, bd, phase=0.0):
-    y, x = np.mgrid[0:h, 0:w].astype(np.float64)
-    x, y = x + phase, y - 0.6 * phase
-    mx = (1 << bd) - 1
-    a = 0.5 + 0.22 * np.sin(x / 9.0 + y / 23.0) + 0.18 * np.cos(y / 7.0 - x / 31.0) + 0.08 * np.sin((x + 2 * y) / 3.5)
-    a = a * mx + rng.normal(0, mx / 200.0, (h, w))
-    return np.clip(np.rint(a), 0, mx).astype(np.int16)
-
-
 def ref_record(plane, mv, cands, mvp_idx=0):
     """cands: one or two candidates of three vectors each"""
     a = np.zeros(1, abi.AFFINE_BIPRED_REF)
@@ -299,7 +261,7 @@ def fresh_set(seed, bd, shapes, pic=(256, 128), n_planes=4, n_ref=(2, 2), painte
     `painted` of the PUs sits on the mean of its own two predictions (later PUs may paint over earlier ones: still valid searches)"""
     rng = np.random.default_rng(seed)
     W, H = pic
-    planes, org = make_planes(rng, n_planes, W, H, bd)
+    planes, org = planes_and_mean_org(rng, n_planes, W, H, bd)
     cfg = cfg_dict(4.0 + (seed % 5) * 9.25, W, H, bd, **cfgkw)
     planes = pad(planes)
     s = Searcher(org, planes, cfg)
@@ -318,10 +280,4 @@ GOLDEN_FLAGS = ("num_iter", "pick_list_by_cost", "mvd_l1_zero", "clip_key", "aff
 
 def golden_groups(g, bd, pic=(256, 128)):
     """tests/golden/affine_bipred.npz -> [(cfg dict, item indices)] of one bit depth: the items of a group share the loop-control flags"""
-    k = "bd%d_" % bd
-    out = []
-    for gi, flags in enumerate(g[k + "flags"]):
-        cfg = cfg_dict(float(g[k + "lambda"]), pic[0], pic[1], bd, mvp_idx_cost=tuple(int(v) for v in g[k + "mvp_idx_cost"]),
-                       **{f: int(v) for f, v in zip(GOLDEN_FLAGS, flags)})
-        out.append((cfg, np.nonzero(g[k + "group"] == gi)[0]))
-    return out
+    return kit.golden_groups(g, bd, cfg_dict, GOLDEN_FLAGS, pic)

@@ -6,25 +6,10 @@ pick_list_by_cost and mvd_l1_zero.  Host decisions are vectorised numpy."""
 import numpy as np
 import torch
 
-from bipred_me_chain import eg_bits
+from pu_search_kit import U64_MAX, get_cost, vec_bits
 from vvcsoftware_vtm_amd import abi, ops
 
-U64_MAX = 0xFFFFFFFFFFFFFFFF
 U32 = 0xFFFFFFFF
-
-
-def get_cost(lam, bits):
-    return (lam * bits.astype(np.float64)).astype(np.uint64)
-
-
-def vec_bits(pred, nmv, mv):
-    """[m] bits of mv [m][3][2] against pred [m][3][2]; vectors 1 and 2 against pred[i] + (mv[0] - pred[0]); vector 2 only where nmv == 3"""
-    b = np.zeros(len(mv), np.int64)
-    for i in range(3):
-        p = pred[:, i] + (mv[:, 0] - pred[:, 0] if i else 0)
-        bi = eg_bits((mv[:, i, 0] >> 2) - (p[:, 0] >> 2)) + eg_bits((mv[:, i, 1] >> 2) - (p[:, 1] >> 2))
-        b += np.where(i < nmv, bi, 0)
-    return b
 
 
 class Chain:

@@ -5,16 +5,20 @@ here in IEEE doubles, the x86 double -> int conversion included.  tests/golden/a
 (tests/test_affine_me_cpu.py).  Also the builders of the test inputs (planes, warped originals, items) that the generator, the tests and
 tools/affine_me_time.py share.  numpy only."""
 import ctypes
+import functools
 import math
 
 import numpy as np
 
+import pu_search_kit as kit
 from oraclelib import oracle, p
+from pu_search_kit import pad, round_signal, texture
 from vvcsoftware_vtm_amd import abi
 
-MARGIN = 144                # samples of edge padding around a reference plane: CTU 128 + 8 (vector clip) + 4 (filter taps), rounded up
+MARGIN = kit.MARGIN         # samples of edge padding around a reference plane: CTU 128 + 8 (vector clip) + 4 (filter taps), rounded up
 MAX_STEPS = abi.AFFINE_ME_MAX_STEPS
 INT_MIN = -(1 << 31)
+clip_mv = functools.partial(kit.clip_mv, shift=4)          # clipMv of one component of a 1/16-unit vector
 
 
 def cvttsd2si(d):
@@ -84,17 +88,6 @@ def deltas(coeff, w, h, six):
     if six:
         out[2] = [delta_of(d[4]), delta_of(d[5])]
     return out
-
-
-def clip_mv(v, pos, pic, max_cu):
-    """clipMv of one component of a 1/16-unit vector (Mv.cpp:64-80)"""
-    return min((pic + 8 - pos - 1) << 4, max((-max_cu - 8 - pos + 1) << 4, v))
-
-
-def round_signal(v):
-    """Mv::roundMV2SignalPrecision of a 1/16-unit component: to quarter sample and back"""
-    q = (v + 2) >> 2 if v >= 0 else -((-v + 2) >> 2)
-    return q * 4
 
 
 def iter_limit(six, half_weight, affine_type):
@@ -210,19 +203,6 @@ def search_all(org, ref_pad, cfg, items):
 def make_cfg(lambda_, pic_w, pic_h, bit_depth, affine_type, ref_stride=None, margin=MARGIN):
     return abi.AffineMeCfg(lambda_, pic_w, pic_h, 128, 128, margin, margin, ref_stride if ref_stride else pic_w + 2 * margin, bit_depth, 0,
                            (1 << bit_depth) - 1, affine_type)
-
-
-def texture(rng, h, w, bd):
-    """smooth texture plus noise: gradients everywhere, so that the searches move"""
-    y, x = np.mgrid[0:h, 0:w].astype(np.float64)
-    mx = (1 << bd) - 1
-    a = 0.5 + 0.22 * np.sin(x / 9.0 + y / 23.0) + 0.18 * np.cos(y / 7.0 - x / 31.0) + 0.08 * np.sin((x + 2 * y) / 3.5)
-    a = a * mx + rng.normal(0, mx / 200.0, (h, w))
-    return np.clip(np.rint(a), 0, mx).astype(np.int16)
-
-
-def pad(plane, margin=MARGIN):
-    return np.ascontiguousarray(np.pad(plane, margin, mode="edge"))
 
 
 def item(px, py, w, h, six, mv, org_off, org_stride, half_weight=0, mvp=None, bits=0):

@@ -7,15 +7,10 @@ decisions are vectorised numpy."""
 import numpy as np
 import torch
 
-from affine_bipred_chain import get_cost, vec_bits
+from pu_search_kit import U64_MAX, get_cost, round_signal, vec_bits
 from vvcsoftware_vtm_amd import abi, ops
 
-U64_MAX = 0xFFFFFFFFFFFFFFFF
 U32 = 0xFFFFFFFF
-
-
-def round_signal(v):
-    return np.where(v >= 0, (v + 2) >> 2, -((-v + 2) >> 2)) * 4
 
 
 def check_best_mvp(c, nmv, cands, num_cand, mv, pred, mvp_idx, bits, cost):

@@ -8,12 +8,13 @@ import math
 
 import numpy as np
 
+import pu_search_kit as kit
 from oraclelib import oracle, p
+from pu_search_kit import U64_MAX, clip_mv, pad, planes_and_mean_org, ref_bits, sub_shift_of
 from vvcsoftware_vtm_amd import abi
 
-MARGIN = 144                # samples of edge padding around a reference plane: CTU 128 + 8 (vector clip) + 4 (filter taps) + 1 (refinement), rounded up
+MARGIN = kit.MARGIN         # samples of edge padding around a reference plane: CTU 128 + 8 (vector clip) + 4 (filter taps) + 1 (refinement), rounded up
 MAX_STEPS = abi.BIPRED_ME_MAX_STEPS
-U64_MAX = 0xFFFFFFFFFFFFFFFF
 SIDES = (4, 8, 16, 32, 64, 128)
 
 
@@ -27,16 +28,6 @@ def cfg_dict(lambda_, pic_w, pic_h, bit_depth, num_iter=4, pick_list_by_cost=0, 
     return dict(lambda_=float(lambda_), pic_w=pic_w, pic_h=pic_h, max_cu=max_cu, bit_depth=bit_depth, clp_min=0, clp_max=(1 << bit_depth) - 1,
                 num_iter=num_iter, pick_list_by_cost=int(pick_list_by_cost), mvd_l1_zero=int(mvd_l1_zero), search_range=search_range,
                 clip_key=int(clip_key), use_hadamard=int(use_hadamard), mvp_idx_cost=tuple(mvp_idx_cost))
-
-
-def clip_mv(v, pos, pic, max_cu):
-    """clipMv of one component of a quarter-unit vector (Mv.cpp:64-80)"""
-    return min((pic + 8 - pos - 1) << 2, max((-max_cu - 8 - pos + 1) << 2, v))
-
-
-def ref_bits(n_ref, r):
-    """the reference index bits of :1101-1108"""
-    return (r + 1 - (1 if r == n_ref - 1 else 0)) if n_ref > 1 else 0
 
 
 def item_ok(it, c, n_planes):
@@ -227,21 +218,6 @@ def search_all(org, planes_pad, cfg, items, strict=False):
 
 
 # ---- inputs ------------------------------------------------------------------------------------------------------------------------------------
-def texture(rng, h, w, bd, phase=0.0):
-    """smooth texture plus noise: gradients everywhere, so that the searches move"""
-    y, x = np.mgrid[0:h, 0:w].astype(np.float64)
-    x, y = x + phase, y - 0.6 * phase
-    mx = (1 << bd) - 1
-    a = 0.5 + 0.22 * np.sin(x / 9.0 + y / 23.0) + 0.18 * np.cos(y / 7.0 - x / 31.0) + 0.08 * np.sin((x + 2 * y) / 3.5)
-    a = a * mx + rng.normal(0, mx / 200.0, (h, w))
-    return np.clip(np.rint(a), 0, mx).astype(np.int16)
-
-
-def pad(planes, margin=MARGIN):
-    """[n][H][W] -> [n][H + 2 M][W + 2 M], edges replicated"""
-    return np.ascontiguousarray(np.pad(planes, ((0, 0), (margin, margin), (margin, margin)), mode="edge"))
-
-
 def ref_record(plane, mv, cands, mvp_idx=0):
     a = np.zeros(1, abi.BIPRED_ME_REF)
     cands = [list(c) for c in cands]
@@ -265,19 +241,13 @@ def item(px, py, w, h, sub_shift, org_off, org_stride, refs, ref_idx, cost, bits
     return it[0]
 
 
-def sub_shift_of(w, h, fast):
-    """DistParam::subShift of subShiftMode 2 (RdCost.cpp:277-283), which FASTINTERSEARCH_MODE1/3 select"""
-    return 1 if fast and h > 8 and w <= 64 else 0
-
-
 def fresh_set(seed, bd, shapes, pic=(256, 128), n_planes=4, n_ref=(2, 2), fast=False, far=0, single=None, **cfgkw):
     """seeded inputs for the device tests: -> (org plane, padded planes, cfg dict, items); one PU per entry of `shapes` = (w, h).  The planes are
     shifted copies of one texture, the original is their mean plus noise, so bi-prediction pays and the refinements move.  Every (list, reference) of
     an item shares its two candidates, so that the closing checks stay inside the contract; single = (x, y): that one candidate everywhere instead."""
     rng = np.random.default_rng(seed)
     W, H = pic
-    planes = np.stack([texture(rng, H, W, bd, 1.5 * k) for k in range(n_planes)])
-    org = np.clip(planes.astype(np.int32).mean(axis=0) + rng.integers(-6, 7, (H, W)), 0, (1 << bd) - 1).astype(np.int16)
+    planes, org = planes_and_mean_org(rng, n_planes, W, H, bd)
     cfg = cfg_dict(4.0 + (seed % 5) * 9.25, W, H, bd, **cfgkw)
     items = np.zeros(len(shapes), abi.BIPRED_ME_ITEM)
     for i, (w, h) in enumerate(shapes):
@@ -294,25 +264,10 @@ def fresh_set(seed, bd, shapes, pic=(256, 128), n_planes=4, n_ref=(2, 2), fast=F
     return org, pad(planes), cfg, items
 
 
-def passes(trace_row, calls):
-    """iterations of the loop an item ran (:1058): a new pass starts where the list changes or the reference index does not rise"""
-    n = 0
-    for k in range(int(calls)):
-        if k == 0 or trace_row[k]["list"] != trace_row[k - 1]["list"] or trace_row[k]["ref"] <= trace_row[k - 1]["ref"]:
-            n += 1
-    return n
-
-
 # ---- the golden file ------------------------------------------------------------------------------------------------------------------------------
 GOLDEN_FLAGS = ("num_iter", "pick_list_by_cost", "mvd_l1_zero", "search_range", "clip_key", "use_hadamard")
 
 
 def golden_groups(g, bd, pic=(256, 128)):
     """tests/golden/bipred_me.npz -> [(cfg dict, item indices)] of one bit depth: the items of a group share the loop-control flags"""
-    k = "bd%d_" % bd
-    out = []
-    for gi, flags in enumerate(g[k + "flags"]):
-        cfg = cfg_dict(float(g[k + "lambda"]), pic[0], pic[1], bd, mvp_idx_cost=tuple(int(v) for v in g[k + "mvp_idx_cost"]),
-                       **{f: int(v) for f, v in zip(GOLDEN_FLAGS, flags)})
-        out.append((cfg, np.nonzero(g[k + "group"] == gi)[0]))
-    return out
+    return kit.golden_groups(g, bd, cfg_dict, GOLDEN_FLAGS, pic)

@@ -7,25 +7,14 @@ pick_list_by_cost and no mvd_l1_zero; calls are grouped by (shape, plane).  Host
 import numpy as np
 import torch
 
+import pu_search_kit as kit
+from pu_search_kit import U64_MAX, eg_bits
 from vvcsoftware_vtm_amd import abi, ops
-
-U64_MAX = 0xFFFFFFFFFFFFFFFF
-
-
-def eg_bits(v):
-    """xGetExpGolombNumberOfBits (RdCost.h:172-184), vectorised"""
-    v = v.astype(np.int64)
-    t = np.where(v <= 0, ((-v) << 1) + 1, v << 1)
-    ln = np.ones_like(t)
-    while (t > 128).any():
-        big = t > 128
-        ln += 14 * big
-        t = np.where(big, t >> 7, t)
-    return ln + 2 * np.floor(np.log2(t)).astype(np.int64)
 
 
 def get_cost(lam, bits):
-    return (lam * bits.astype(np.float64)).astype(np.uint64).astype(np.int64)
+    return kit.get_cost(lam, bits).astype(np.int64)                          # this chain keeps its costs signed
+
 
 
 class Chain:

@@ -22,6 +22,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(HERE))
 
 import affine_me_cases as amc  # noqa: E402
+import pu_search_kit as kit  # noqa: E402
 from oraclelib import p  # noqa: E402
 from vvcsoftware_vtm_amd import abi  # noqa: E402
 
@@ -42,7 +43,7 @@ def driver():
 
 
 def plane(rng, bd):
-    a = amc.texture(rng, H, W, bd)
+    a = kit.texture(rng, H, W, bd)
     x0, y0, w, h = STRIPES
     a[y0:y0 + h, x0:x0 + w] = ((np.arange(w) % 7) * ((1 << bd) // 9) + (1 << bd) // 8).astype(np.int16)[None, :]
     a[y0:y0 + h, x0 + w:] = (1 << bd) // 3
@@ -140,7 +141,7 @@ def build_set(D, bd, rng):
 
 def check_set(bd, ref, atlas, items, ats, lam, want, tags):
     """the restatement reproduces every reference result; with its step counts: the set holds the cases the tests rely on"""
-    refp = amc.pad(ref)
+    refp = kit.pad(ref)
     steps, facts = np.zeros(len(items), np.uint32), set()
     for at in (1, 0):
         cfg = amc.make_cfg(lam, W, H, bd, at)

@@ -31,6 +31,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(HERE))
 
 import affine_unipred_cases as uc  # noqa: E402
+import pu_search_kit as kit  # noqa: E402
 from oraclelib import p  # noqa: E402
 from vvcsoftware_vtm_amd import abi  # noqa: E402
 
@@ -101,7 +102,7 @@ def ref_loop(D, org, it, flags, n_ref, l1to0):
     for iRefList in range(2):
         for iRefIdxTemp in range(n_ref[iRefList]):
             a = it["ref"][iRefList][iRefIdxTemp]
-            cand = [uc.vec3(a["mv_cand"][k]) for k in range(2)]
+            cand = [kit.vec3(a["mv_cand"][k]) for k in range(2)]
             uiBitsTemp = uiMbBits[iRefList]
             if n_ref[iRefList] > 1:
                 uiBitsTemp += iRefIdxTemp + 1
@@ -157,11 +158,11 @@ def ref_loop(D, org, it, flags, n_ref, l1to0):
                 D.auref_me(p(blk), os_, px, py, w, h, six, iRefList, iRefIdxTemp, p(i32(cMvPred[iRefList][iRefIdxTemp])), 1, p(mv), start_hp, C.byref(bits),
                            C.byref(cost), C.byref(hp_out))
                 assert hp_out.value == 1                                         # what becomes mvAffine4Para carries the high-precision flag
-                cMvTemp[iRefList][iRefIdxTemp], uiBitsTemp, uiCostTemp = uc.vec3(mv.reshape(3, 2)), bits.value, cost.value
+                cMvTemp[iRefList][iRefIdxTemp], uiBitsTemp, uiCostTemp = kit.vec3(mv.reshape(3, 2)), bits.value, cost.value
             pr, ix, b, c = i32(cMvPred[iRefList][iRefIdxTemp]).copy(), C.c_int(aaiMvpIdx[iRefList][iRefIdxTemp]), C.c_uint(uiBitsTemp), C.c_uint64(uiCostTemp)
             D.auref_check_best_mvp(six, iRefList, p(i32(cMvTemp[iRefList][iRefIdxTemp])), 1, p(pr), C.byref(ix), p(i32(a["mv_cand"])), 1, int(a["num_cand"]),
                                    C.byref(b), C.byref(c))
-            cMvPred[iRefList][iRefIdxTemp], aaiMvpIdx[iRefList][iRefIdxTemp], uiBitsTemp, uiCostTemp = uc.vec3(pr.reshape(3, 2)), ix.value, b.value, c.value
+            cMvPred[iRefList][iRefIdxTemp], aaiMvpIdx[iRefList][iRefIdxTemp], uiBitsTemp, uiCostTemp = kit.vec3(pr.reshape(3, 2)), ix.value, b.value, c.value
             res[0]["s"][iRefList][iRefIdxTemp] = (cMvTemp[iRefList][iRefIdxTemp], ix.value, uiBitsTemp, uiCostTemp, tmpl, start_cost, inherit_cost, sel, 0,
                                                   2 if take_l0 else 1, 0)
             if iRefList == 0:
@@ -187,7 +188,7 @@ def ref_loop(D, org, it, flags, n_ref, l1to0):
             q["plane"], q["mv"], q["mv_cand"], q["num_cand"], q["mvp_idx"] = REF_PLANE[l][r], cMvTemp[l][r], it["ref"][l][r]["mv_cand"], it["ref"][l][r]["num_cand"], aaiMvpIdx[l][r]
     if mvd_l1_zero and n_ref[1] > 0:
         q = o["ref"][1][bestBiPRefIdxL1]
-        pcMvTemp = uc.vec3(q["mv_cand"][bestBiPMvpL1])
+        pcMvTemp = kit.vec3(q["mv_cand"][bestBiPMvpL1])
         q["mvp_idx"], q["mv"] = bestBiPMvpL1, pcMvTemp
         o["mv"][1], o["ref_idx"][1] = pcMvTemp, bestBiPRefIdxL1
     return res[0], out[0]
@@ -224,12 +225,12 @@ def build_items(rng, painter, org, n_ref):
 def build_set(D, bd, rng):
     mx = (1 << bd) - 1
     lam = 37.5 if bd == 10 else 11.25
-    planes, org = uc.make_planes(rng, N_PLANES, W, H, bd)
+    planes, org = kit.planes_and_first_org(rng, N_PLANES, W, H, bd)
     fx, fy, fw, fh = FLAT
     org[fy:fy + fh, fx:fx + fw] = mx // 3 + 7                                        # flat original on flat references: zero gradients, a singular system
     for k in range(N_PLANES):
         planes[k, fy:fy + fh, fx:fx + fw] = mx // 3 + 7 + 3 * k
-    painter = uc.Searcher(org, uc.pad(planes), uc.cfg_dict(lam, W, H, bd))
+    painter = uc.Searcher(org, kit.pad(planes), uc.cfg_dict(lam, W, H, bd))
     groups = [build_items(rng, painter, org, n_ref) for _, n_ref, _ in GROUPS]       # the items paint the original: all items first
     org = np.ascontiguousarray(org)
     cost = np.array(MVP_IDX_COST, np.uint32)
@@ -247,7 +248,7 @@ def build_set(D, bd, rng):
 
 def check_set(bd, planes, org, items, group, lam, want, out):
     """the restatement reproduces every reference result and out-item (and supplies `steps`); the set holds the cases the tests rely on"""
-    pp = uc.pad(planes)
+    pp = kit.pad(planes)
     seen = set()
     for gi, (flags, n_ref, l1to0) in enumerate(GROUPS):
         cfg = uc.cfg_dict(lam, W, H, bd, n_ref=n_ref, ref_plane=REF_PLANE, list1_to_list0=l1to0, mvp_idx_cost=MVP_IDX_COST, **dict(zip(uc.GOLDEN_FLAGS, flags)))

@@ -27,6 +27,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(HERE))
 
 import bipred_me_cases as bc  # noqa: E402
+import pu_search_kit as kit  # noqa: E402
 from oraclelib import p  # noqa: E402
 from vvcsoftware_vtm_amd import abi  # noqa: E402
 
@@ -170,7 +171,7 @@ def build_items(rng, planes, org, bd, flags, fast, n_ref):
     def add(tag, px, py, w, h, refs, cost_scale=(0.6, 1.6), org_off=None, ref_idx=None):
         ri = ref_idx if ref_idx is not None else [int(rng.integers(0, n_ref[0])), int(rng.integers(0, n_ref[1]))]
         cost = [int(w * h * sad0 * rng.uniform(*cost_scale)), int(w * h * sad0 * rng.uniform(*cost_scale))]
-        items.append(bc.item(px, py, w, h, bc.sub_shift_of(w, h, fast), py * W + px if org_off is None else org_off, W, refs, ri, cost,
+        items.append(bc.item(px, py, w, h, kit.sub_shift_of(w, h, fast), py * W + px if org_off is None else org_off, W, refs, ri, cost,
                              [int(rng.integers(8, 30)), int(rng.integers(8, 30))]))
         tags.append(tag)
 
@@ -234,7 +235,7 @@ def build_items(rng, planes, org, bd, flags, fast, n_ref):
 def build_set(D, bd, rng):
     mx = (1 << bd) - 1
     lam = 37.5 if bd == 10 else 11.25
-    planes = np.stack([bc.texture(rng, H, W, bd, 1.5 * k) for k in range(N_PLANES)])
+    planes = np.stack([kit.texture(rng, H, W, bd, 1.5 * k) for k in range(N_PLANES)])
     org = np.clip(planes.astype(np.int32).mean(axis=0) + rng.integers(-5, 6, (H, W)), 0, mx).astype(np.int16)
     fx, fy, fw, fh = FLAT
     org[fy:fy + fh, fx:fx + fw] = mx // 3 + 7
@@ -261,7 +262,7 @@ def build_set(D, bd, rng):
 
 def check_set(bd, planes, org, items, group, lam, want, trace, tags, facts):
     """the restatement reproduces every reference result and trace entry (and supplies the integer vectors); the set holds the cases the tests rely on"""
-    pp = bc.pad(planes)
+    pp = kit.pad(planes)
     for gi, (flags, fast, n_ref) in enumerate(GROUPS):
         cfg = bc.cfg_dict(lam, W, H, bd, mvp_idx_cost=MVP_IDX_COST, **dict(zip(bc.GOLDEN_FLAGS, flags)))
         s = bc.Searcher(org, pp, cfg)
@@ -277,7 +278,7 @@ def check_set(bd, planes, org, items, group, lam, want, trace, tags, facts):
             w, h = int(it["w"]), int(it["h"])
             facts |= {("shape", w, h), ("n_ref", int(it["n_ref"][0])), ("n_ref", int(it["n_ref"][1])), ("range", flags[3]), ("num_iter", flags[0]),
                       ("pick", flags[1]), ("mvd_l1_zero", flags[2]), ("clip_key", flags[4]), ("hadamard", flags[5]), ("sub_shift", int(it["sub_shift"])),
-                      ("passes", bc.passes(tr, n)), ("closing", int(res["closing"]))}
+                      ("passes", kit.passes(tr, n)), ("closing", int(res["closing"]))}
             if tags[i] == "corner":
                 # clipMv binds on the vector (the first integer vector is the clipped entry's neighbourhood, far from the entry) and on the range
                 e = it["ref"][int(tr[0]["list"])][int(tr[0]["ref"])]["mv"]
@@ -307,7 +308,7 @@ def main():
                     k + "lambda": np.float64(lam), k + "mvp_idx_cost": np.array(MVP_IDX_COST, np.uint32), k + "want": want, k + "trace": trace,
                     k + "dropped": np.int32(dropped), k + "generated": np.int32(generated)})
         total += len(items)
-        ps = [bc.passes(trace[i], want[i]["me_calls"]) for i in range(len(items))]
+        ps = [kit.passes(trace[i], want[i]["me_calls"]) for i in range(len(items))]
         print("bit depth %d: %d items kept of %d (the reference throws on %d), passes %s, closing %d" % (bd, len(items), generated, dropped, np.bincount(ps), int(want["closing"].sum())))
     path = os.path.join(HERE, "bipred_me.npz")
     np.savez_compressed(path, **out)

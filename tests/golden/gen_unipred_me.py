@@ -29,6 +29,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(HERE))
 
 import unipred_me_cases as uc  # noqa: E402
+import pu_search_kit as kit  # noqa: E402
 from oraclelib import p  # noqa: E402
 from vvcsoftware_vtm_amd import abi  # noqa: E402
 
@@ -170,7 +171,7 @@ def build_items(rng, grp, gi):
         return out
 
     def add(px, py, w, h, refs):
-        items.append(uc.item(px, py, w, h, uc.sub_shift_of(w, h, grp["fast"]), py * W + px, W, refs, abi.TZ_EXTENDED * grp["ext"], [int(v) for v in rng.integers(1, 6, 3)]))
+        items.append(uc.item(px, py, w, h, kit.sub_shift_of(w, h, grp["fast"]), py * W + px, W, refs, abi.TZ_EXTENDED * grp["ext"], [int(v) for v in rng.integers(1, 6, 3)]))
 
     shapes = uc.all_shapes()
     pick = shapes if grp["shapes"] >= len(shapes) else [shapes[(5 * gi + 2 * k) % len(shapes)] for k in range(grp["shapes"])]
@@ -191,7 +192,7 @@ def build_items(rng, grp, gi):
 def build_set(D, bd, rng):
     mx = (1 << bd) - 1
     lam = 37.5 if bd == 10 else 11.25
-    planes = np.stack([uc.texture(rng, H, W, bd, 1.5 * k) for k in range(N_PLANES)])
+    planes = np.stack([kit.texture(rng, H, W, bd, 1.5 * k) for k in range(N_PLANES)])
     org = np.clip(np.roll(planes[0], (3, -5), axis=(0, 1)).astype(np.int32) + rng.integers(-5, 6, (H, W)), 0, mx).astype(np.int16)
     fx, fy, fw, fh = FLAT
     org[fy:fy + fh, fx:fx + fw] = mx // 3 + 7
@@ -218,7 +219,7 @@ def build_set(D, bd, rng):
 
 def check_set(bd, planes, org, items, group, lam, want, outs):
     """the restatement reproduces every reference result and out-item; the set holds the cases the tests rely on"""
-    pp = uc.pad(planes)
+    pp = kit.pad(planes)
     seen = set()
     for gi, grp in enumerate(GROUPS):
         cfg = group_cfg(grp, lam, bd)

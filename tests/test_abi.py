@@ -1,5 +1,6 @@
 """CPU-side checks of the drop-in boundary: the C-ABI library loads and exports every symbol that
-include/vvcgpu.h declares (no compute calls -- there is no GPU here)."""
+include/vvcgpu.h declares, and every struct of the header has a mirror in vvcsoftware_vtm_amd.abi with the C compiler's
+layout (no compute calls -- there is no GPU here)."""
 import ctypes as C
 import os
 import re
@@ -49,6 +50,18 @@ def test_version_and_error_text():
     assert rc == -1 and b"alias" in lib.vvcgpu_last_error()
 
 
+# vvcgpu_sizeof id -> (mirror, its size written out): the structs from vvcgpu_wp_param on
+SIZED = {31: ("WP_PARAM", 16), 32: ("WP_SAD_CAND", 16), 33: ("TILE_STATS", 24),
+         34: ("AFFINE_ME_ITEM", 128), 35: ("AffineMeCfg", 64), 36: ("AFFINE_ME_RESULT", 40), 37: ("AFFINE_ME_STEP", 32),
+         38: ("BIPRED_ME_REF", 32), 39: ("BIPRED_ME_ITEM", 360), 40: ("BipredMeCfg", 224), 41: ("BIPRED_ME_RESULT", 80), 42: ("BIPRED_ME_STEP", 48),
+         44: ("AFFINE_BIPRED_REF", 80), 45: ("AFFINE_BIPRED_ITEM", 784), 46: ("AffineBipredCfg", 224), 47: ("AFFINE_BIPRED_RESULT", 144),
+         48: ("AFFINE_BIPRED_STEP", 56),
+         50: ("UNIPRED_ME_REF", 40), 51: ("UNIPRED_ME_ITEM", 360), 52: ("UnipredMeCfg", 304), 53: ("UNIPRED_ME_SEARCH", 48), 54: ("UNIPRED_ME_RESULT", 472),
+         56: ("AFFINE_UNIPRED_REF", 80), 57: ("AFFINE_UNIPRED_ITEM", 688), 58: ("AffineUnipredCfg", 264), 59: ("AFFINE_UNIPRED_SEARCH", 88),
+         60: ("AFFINE_UNIPRED_RESULT", 840)}
+UNUSED_IDS = (43, 49, 55, 61)
+
+
 def test_struct_layouts_match_python_bindings():
     """numpy / ctypes mirrors used by the host code have exactly the sizes the built library reports (no GPU needed)."""
     _ensure_built()
@@ -61,7 +74,27 @@ def test_struct_layouts_match_python_bindings():
             26: abi.RDOQ_RATES.itemsize, 27: abi.RDOQ_DESC.itemsize, 28: abi.INTRA_SATD_DESC.itemsize, 29: abi.AFFINE_ITER.itemsize, 30: C.sizeof(abi.MeHierCfg)}
     for k, v in want.items():
         assert lib.vvcgpu_sizeof(k) == v, (k, lib.vvcgpu_sizeof(k), v)
-    assert lib.vvcgpu_sizeof(99) == -1
+    for k, (name, size) in SIZED.items():
+        assert lib.vvcgpu_sizeof(k) == size == _mirror_size(getattr(abi, name)), (k, name, lib.vvcgpu_sizeof(k), size)
+    assert sorted(want) + sorted(SIZED) == [k for k in range(61) if k not in UNUSED_IDS]
+    for k in UNUSED_IDS + (99,):
+        assert lib.vvcgpu_sizeof(k) == -1, k
+    assert all(size % 8 == 0 for k, (_, size) in SIZED.items() if 56 <= k <= 60)             # the affine uni-predictive records pack into arrays of 8-byte members
+    assert abi.AFFINE_BIPRED_ITEM.itemsize == 784                                              # the out-items of the affine uni-predictive entry
+
+
+def test_header_constants_match_python_bindings():
+    """the array bounds, flag values and stated sizes of the PU search entries in include/vvcgpu.h == abi's"""
+    hdr = " ".join(open(capi.HEADER).read().split())
+    for name in ("AFFINE_ME_MAX_STEPS", "BIPRED_ME_MAX_STEPS", "BIPRED_ME_MAX_REFS", "BIPRED_ME_MAX_PLANES", "AFFINE_BIPRED_MAX_STEPS", "AFFINE_BIPRED_MAX_REFS",
+                 "UNIPRED_ME_MAX_REFS", "UNIPRED_ME_MAX_PLANES", "AFFINE_UNIPRED_MAX_REFS"):
+        assert "#define VVCGPU_%s %d " % (name, getattr(abi, name)) in hdr, name
+    assert abi.AFFINE_ME_MAX_STEPS == 8
+    assert "VVCGPU_UNIPRED_PRED2 = %d, VVCGPU_UNIPRED_CACHED = %d" % (abi.UNIPRED_PRED2, abi.UNIPRED_CACHED) in hdr
+    assert "sizeof == 784" in hdr and "sizeof == 688" in hdr and "sizeof == 840" in hdr
+    # the out-items of the uni-predictive entries are the bi-predictive entries' items
+    assert abi.BIPRED_ME_MAX_REFS == abi.UNIPRED_ME_MAX_REFS and abi.BIPRED_ME_MAX_PLANES == abi.UNIPRED_ME_MAX_PLANES
+    assert abi.AFFINE_BIPRED_MAX_REFS == abi.AFFINE_UNIPRED_MAX_REFS
 
 
 # every typedef struct of include/vvcgpu.h -> its mirrors in vvcsoftware_vtm_amd.abi
@@ -76,15 +109,28 @@ MIRRORS = {
     "vvcgpu_if_desc": ["IF_DESC"], "vvcgpu_mc_desc": ["MC_DESC"], "vvcgpu_pelop_desc": ["PELOP_DESC"], "vvcgpu_pelop_cfg": ["PelopCfg"],
     "vvcgpu_tr_desc": ["TR_DESC"], "vvcgpu_dqtr_desc": ["DQTR_DESC"], "vvcgpu_resi_chain_desc": ["RC_DESC"], "vvcgpu_rdpcm_desc": ["RDPCM_DESC"],
     "vvcgpu_afg_desc": ["AFG_DESC"], "vvcgpu_afe_desc": ["AFE_DESC"], "vvcgpu_affine_pu": ["AFFINE_PU"], "vvcgpu_affine_iter": ["AFFINE_ITER"],
+    "vvcgpu_wp_param": ["WP_PARAM"], "vvcgpu_tile_stats": ["TILE_STATS"], "vvcgpu_wp_sad_cand": ["WP_SAD_CAND"],
+    "vvcgpu_affine_me_item": ["AFFINE_ME_ITEM"], "vvcgpu_affine_me_cfg": ["AffineMeCfg"], "vvcgpu_affine_me_result": ["AFFINE_ME_RESULT"],
+    "vvcgpu_affine_me_step": ["AFFINE_ME_STEP"],
+    "vvcgpu_bipred_me_ref": ["BIPRED_ME_REF"], "vvcgpu_bipred_me_item": ["BIPRED_ME_ITEM"], "vvcgpu_bipred_me_cfg": ["BipredMeCfg"],
+    "vvcgpu_bipred_me_result": ["BIPRED_ME_RESULT"], "vvcgpu_bipred_me_step": ["BIPRED_ME_STEP"],
+    "vvcgpu_affine_bipred_ref": ["AFFINE_BIPRED_REF"], "vvcgpu_affine_bipred_item": ["AFFINE_BIPRED_ITEM"], "vvcgpu_affine_bipred_cfg": ["AffineBipredCfg"],
+    "vvcgpu_affine_bipred_result": ["AFFINE_BIPRED_RESULT"], "vvcgpu_affine_bipred_step": ["AFFINE_BIPRED_STEP"],
+    "vvcgpu_unipred_me_ref": ["UNIPRED_ME_REF"], "vvcgpu_unipred_me_item": ["UNIPRED_ME_ITEM"], "vvcgpu_unipred_me_cfg": ["UnipredMeCfg"],
+    "vvcgpu_unipred_me_search": ["UNIPRED_ME_SEARCH"], "vvcgpu_unipred_me_result": ["UNIPRED_ME_RESULT"],
+    "vvcgpu_affine_unipred_ref": ["AFFINE_UNIPRED_REF"], "vvcgpu_affine_unipred_item": ["AFFINE_UNIPRED_ITEM"], "vvcgpu_affine_unipred_cfg": ["AffineUnipredCfg"],
+    "vvcgpu_affine_unipred_search": ["AFFINE_UNIPRED_SEARCH"], "vvcgpu_affine_unipred_result": ["AFFINE_UNIPRED_RESULT"],
 }
 # mirror fields named differently from their C member
 RENAMED = {("MvCost", "lambda_"): "lambda", ("TZ_CFG", "reserved"): "uniform_pu"}
+RENAMED.update({(name, "lambda_"): "lambda" for name in ("AffineMeCfg", "BipredMeCfg", "UnipredMeCfg", "AffineBipredCfg", "AffineUnipredCfg")})
 # mirror fields that name the tail padding of the C struct (no C member)
 TAIL_PADDING = {("RDPCM_DESC", "pad")}
 
 
 def _mirror_fields(m, prefix=""):
-    """[(name, offset, size)] of a dtype's or Structure's fields; the fields of a nested record follow it as "outer.inner"."""
+    """[(name, offset, size)] of a dtype's or Structure's fields; the fields of a nested record follow it as "outer.inner".  An array of nested
+    records (dt.names is None, the records are in dt.subdtype) stays one field: its struct is checked as the typedef it is"""
     if isinstance(m, np.dtype):
         out = []
         for name in m.names:
@@ -103,7 +149,8 @@ def _mirror_size(m):
 def test_struct_mirrors_match_header_field_by_field(tmp_path):
     """the C compiler's sizeof / offsetof of include/vvcgpu.h == every mirror in abi, per struct and per field"""
     hdr = re.sub(r"/\*.*?\*/", "", open(capi.HEADER).read(), flags=re.S)
-    assert sorted(re.findall(r"typedef\s+struct\s+(vvcgpu_\w+)", hdr)) == sorted(MIRRORS)
+    names = re.findall(r"typedef\s+struct\s*(?:vvcgpu_\w+)?\s*\{[^{}]*\}\s*(vvcgpu_\w+)\s*;", hdr)          # tagged or anonymous: the closing name
+    assert sorted(names) == sorted(MIRRORS) and len(names) >= 62
     mirrors = {(cname, name): getattr(abi, name) for cname, names in MIRRORS.items() for name in names}
     fields = {key: _mirror_fields(m) for key, m in mirrors.items()}
     seen = {(name, f) for (_, name), fs in fields.items() for f, _, _ in fs}

@@ -1,16 +1,15 @@
 """CPU checks of the whole-PU affine motion search (vvcgpu_affine_me_batch): the tests' restatement of InterSearch::xAffineMotionEstimation
 (tests/affine_me_cases.py) against the compiled reference's own results (tests/golden/affine_me.npz), the x86 double -> int conversion it emulates,
-the four structs' layout against the header, and the host-side argument checks (no device is touched)."""
+and the host-side argument checks (no device is touched).  The structs' layout: tests/test_abi.py."""
 import ctypes as C
 import os
-import shlex
-import subprocess
 
 import numpy as np
 import pytest
 
 import affine_me_cases as amc
-from vvcsoftware_vtm_amd import abi, capi
+import pu_search_kit as kit
+from vvcsoftware_vtm_amd import capi
 
 G = os.path.join(os.path.dirname(__file__), "golden")
 W, H = 256, 128
@@ -32,7 +31,7 @@ def test_restatement_equals_reference_golden(bd):
     k = "bd%d_" % bd
     items, ats, want = g[k + "items"], g[k + "affine_type"], g[k + "want"]
     assert len(items) >= 30
-    refp = amc.pad(g[k + "ref"])
+    refp = kit.pad(g[k + "ref"])
     seen = set()
     for at in (1, 0):
         idx = np.nonzero(ats == at)[0]
@@ -79,40 +78,6 @@ def test_solver_takes_the_zero_pivot_exits():
     assert amc.deltas(m, 16, 16, False) == [[32, 48], [32 + 16 * 16, 48 - 2 * 16 * 16], [0, 0]]
     m[4, 3] = 0                                              # the last pivot: every parameter stays 0
     assert amc.deltas(m, 16, 16, False) == [[0, 0], [0, 0], [0, 0]]
-
-
-MIRRORS = {"vvcgpu_affine_me_item": (34, abi.AFFINE_ME_ITEM, 128), "vvcgpu_affine_me_cfg": (35, abi.AffineMeCfg, 64),
-           "vvcgpu_affine_me_result": (36, abi.AFFINE_ME_RESULT, 40), "vvcgpu_affine_me_step": (37, abi.AFFINE_ME_STEP, 32)}
-
-
-def _fields(m):
-    if isinstance(m, np.dtype):
-        return [(n, m.fields[n][1], m.fields[n][0].itemsize) for n in m.names]
-    return [("lambda" if f[0] == "lambda_" else f[0], getattr(m, f[0]).offset, getattr(m, f[0]).size) for f in m._fields_]
-
-
-def test_struct_mirrors_match_the_header(tmp_path):
-    lib = _lib()
-    lines = []
-    for cname, (sid, m, size) in MIRRORS.items():
-        assert lib.vvcgpu_sizeof(sid) == size == (m.itemsize if isinstance(m, np.dtype) else C.sizeof(m)), cname
-        lines.append('  printf("%%s . %%zu %%zu\\n", "%s", (size_t)0, sizeof(%s));\n' % (cname, cname))
-        lines += ['  printf("%%s %%s %%zu %%zu\\n", "%s", "%s", offsetof(%s, %s), sizeof(((%s*)0)->%s));\n' % (cname, f, cname, f, cname, f)
-                  for f, _, _ in _fields(m)]
-    src = tmp_path / "afm.c"
-    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "vvcgpu.h"\nint main(void)\n{\n' + "".join(lines) + "  return 0;\n}\n")
-    exe = tmp_path / "afm"
-    r = subprocess.run(shlex.split(os.environ.get("CC", "cc")) + ["-I", os.path.dirname(capi.HEADER), str(src), "-o", str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    got = {}
-    for line in subprocess.check_output([str(exe)], text=True).splitlines():
-        c, f, off, sz = line.split()
-        got[(c, f)] = (int(off), int(sz))
-    for cname, (sid, m, size) in MIRRORS.items():
-        assert got[(cname, ".")] == (0, size)
-        for f, off, sz in _fields(m):
-            assert got[(cname, f)] == (off, sz), (cname, f)
-    assert abi.AFFINE_ME_MAX_STEPS == 8 and "#define VVCGPU_AFFINE_ME_MAX_STEPS 8" in open(capi.HEADER).read()
 
 
 def test_argument_checks_need_no_device():

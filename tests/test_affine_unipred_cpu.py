@@ -1,16 +1,15 @@
 """CPU checks of the affine uni-predictive stage (vvcgpu_affine_unipred_me_batch): the tests' restatement of the uni-predictive part of
 InterSearch::xPredAffineInterSearch (tests/affine_unipred_cases.py) against the results the compiled reference's own xGetAffineTemplateCost /
-xAffineMotionEstimation / xCheckBestAffineMVP gave (tests/golden/affine_unipred.npz), the five structs' layout against the header, the exported
-symbol, and the host-side argument checks (no device is touched)."""
+xAffineMotionEstimation / xCheckBestAffineMVP gave (tests/golden/affine_unipred.npz), the exported symbol, and the host-side
+argument checks (no device is touched).  The structs' layout: tests/test_abi.py."""
 import ctypes as C
 import os
-import shlex
-import subprocess
 
 import numpy as np
 import pytest
 
 import affine_unipred_cases as uc
+import pu_search_kit as kit
 from vvcsoftware_vtm_amd import abi, capi
 
 G = os.path.join(os.path.dirname(__file__), "golden")
@@ -32,7 +31,7 @@ def test_restatement_equals_reference_golden(bd):
     k = "bd%d_" % bd
     items, want, want_out = g[k + "items"], g[k + "want"], g[k + "out"]
     assert len(items) >= 100 and len(items) == int(g[k + "generated"]) == len(want) == len(want_out)
-    planes = uc.pad(g[k + "planes"])
+    planes = kit.pad(g[k + "planes"])
     assert planes.shape[1:] == (H + 2 * uc.MARGIN, W + 2 * uc.MARGIN)
     groups = uc.golden_groups(g, bd)
     assert sorted(int(i) for _, idx in groups for i in idx) == list(range(len(items)))
@@ -60,51 +59,11 @@ def test_the_inheritance_shifts_by_the_shape():
     assert uc.inherited([[-4, 4], [-9, 1]], 32, 64) == [[-4, 4], [-9, 1], [4, -8]]
 
 
-MIRRORS = {"vvcgpu_affine_unipred_ref": (56, abi.AFFINE_UNIPRED_REF, 80), "vvcgpu_affine_unipred_item": (57, abi.AFFINE_UNIPRED_ITEM, 688),
-           "vvcgpu_affine_unipred_cfg": (58, abi.AffineUnipredCfg, 264), "vvcgpu_affine_unipred_search": (59, abi.AFFINE_UNIPRED_SEARCH, 88),
-           "vvcgpu_affine_unipred_result": (60, abi.AFFINE_UNIPRED_RESULT, 840)}
-
-
-def _fields(m):
-    if isinstance(m, np.dtype):
-        return [(n, m.fields[n][1], m.fields[n][0].itemsize) for n in m.names]
-    return [("lambda" if f[0] == "lambda_" else f[0], getattr(m, f[0]).offset, getattr(m, f[0]).size) for f in m._fields_]
-
-
 def test_the_entry_is_exported_and_declared():
     lib = _lib()
     assert "vvcgpu_affine_unipred_me_batch" in capi.declared_symbols() and hasattr(lib, "vvcgpu_affine_unipred_me_batch")
     restype, argtypes = capi.prototypes()["vvcgpu_affine_unipred_me_batch"]
     assert restype is C.c_int and argtypes == (C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
-
-
-def test_struct_mirrors_match_the_header(tmp_path):
-    lib = _lib()
-    lines = []
-    for cname, (sid, m, size) in MIRRORS.items():
-        assert size % 8 == 0 and lib.vvcgpu_sizeof(sid) == size == (m.itemsize if isinstance(m, np.dtype) else C.sizeof(m)), cname
-        lines.append('  printf("%%s . %%zu %%zu\\n", "%s", (size_t)0, sizeof(%s));\n' % (cname, cname))
-        lines += ['  printf("%%s %%s %%zu %%zu\\n", "%s", "%s", offsetof(%s, %s), sizeof(((%s*)0)->%s));\n' % (cname, f, cname, f, cname, f)
-                  for f, _, _ in _fields(m)]
-    src = tmp_path / "aup.c"
-    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "vvcgpu.h"\nint main(void)\n{\n' + "".join(lines) + "  return 0;\n}\n")
-    exe = tmp_path / "aup"
-    r = subprocess.run(shlex.split(os.environ.get("CC", "cc")) + ["-I", os.path.dirname(capi.HEADER), str(src), "-o", str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    got = {}
-    for line in subprocess.check_output([str(exe)], text=True).splitlines():
-        c, f, off, sz = line.split()
-        got[(c, f)] = (int(off), int(sz))
-    for cname, (sid, m, size) in MIRRORS.items():
-        assert got[(cname, ".")] == (0, size)
-        for f, off, sz in _fields(m):
-            assert got[(cname, f)] == (off, sz), (cname, f)
-    hdr = " ".join(open(capi.HEADER).read().split())
-    assert "#define VVCGPU_AFFINE_UNIPRED_MAX_REFS %d" % abi.AFFINE_UNIPRED_MAX_REFS in hdr
-    assert "sizeof == 688" in hdr and "sizeof == 840" in hdr
-    assert lib.vvcgpu_sizeof(43) == -1 and lib.vvcgpu_sizeof(49) == -1 and lib.vvcgpu_sizeof(55) == -1 and lib.vvcgpu_sizeof(61) == -1
-    # the out-items are the affine bi-predictive entry's items
-    assert abi.AFFINE_BIPRED_MAX_REFS == abi.AFFINE_UNIPRED_MAX_REFS and abi.AFFINE_BIPRED_ITEM.itemsize == 784
 
 
 def _cfg(**kw):

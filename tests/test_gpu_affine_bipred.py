@@ -4,13 +4,12 @@ tests' restatement (tests/affine_bipred_cases.py, pinned to the reference by tes
 import functools
 import itertools
 import os
-import threading
 
 import numpy as np
 import pytest
-import torch
 
 import affine_bipred_cases as ac
+import pu_search_kit as kit
 from vvcsoftware_vtm_amd import abi
 
 pytestmark = pytest.mark.gpu
@@ -19,25 +18,22 @@ W, H = 256, 128
 PAIRS = list(itertools.product(ac.SIDES, ac.SIDES))          # every served (w, h); up to 1024 samples a wavefront owns the PU, above the workgroup
 
 
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+# ops.affine_bipred_cfg's parameters between pic_h and max_cu, as keys of ac.cfg_dict
+CFG_FIELDS = ("bit_depth", "clp", "num_iter", "pick_list_by_cost", "mvd_l1_zero", "clip_key", "affine_type", "mvp_idx_cost")
 
 
 def device_cfg(cfg, planes_dev, max_pu=(0, 0)):
     from vvcsoftware_vtm_amd import ops
-    m = ac.MARGIN
-    return ops.affine_bipred_cfg(cfg["lambda_"], [planes_dev[i] for i in range(planes_dev.shape[0])], (m, m), cfg["pic_w"], cfg["pic_h"], cfg["bit_depth"],
-                                 (cfg["clp_min"], cfg["clp_max"]), cfg["num_iter"], cfg["pick_list_by_cost"], cfg["mvd_l1_zero"], cfg["clip_key"],
-                                 cfg["affine_type"], cfg["mvp_idx_cost"], cfg["max_cu"], max_pu)
+    return kit.device_cfg(ops.affine_bipred_cfg, cfg, planes_dev, ac.MARGIN, CFG_FIELDS, max_pu)
+
+
+def decode(res, trace):
+    return kit.download(res, abi.AFFINE_BIPRED_RESULT), kit.download(trace, abi.AFFINE_BIPRED_STEP, (-1, abi.AFFINE_BIPRED_MAX_STEPS))
 
 
 def run(org, planes, cfg, items, want_trace=True, max_pu=(0, 0)):
     from vvcsoftware_vtm_amd import ops
-    d_planes = dev(planes)
-    res, trace = ops.affine_bipred_me_batch(dev(org), ops.struct_to_device(items), len(items), device_cfg(cfg, d_planes, max_pu), want_trace)
-    torch.cuda.synchronize()
-    res = res.cpu().numpy().view(abi.AFFINE_BIPRED_RESULT)
-    return res, (trace.cpu().numpy().view(abi.AFFINE_BIPRED_STEP).reshape(len(items), abi.AFFINE_BIPRED_MAX_STEPS) if want_trace else None)
+    return kit.run(ops.affine_bipred_me_batch, lambda d: device_cfg(cfg, d, max_pu), org, planes, items, want_trace, decode)
 
 
 def shapes_of(n):
@@ -65,7 +61,7 @@ def fresh(n):
 def test_results_and_trace_equal_the_reference_golden(bd):
     g = np.load(os.path.join(G, "affine_bipred.npz"))
     k = "bd%d_" % bd
-    planes = ac.pad(g[k + "planes"])
+    planes = kit.pad(g[k + "planes"])
     items, want, want_trace = g[k + "items"], g[k + "want"], g[k + "trace"]
     for cfg, idx in ac.golden_groups(g, bd):
         res, trace = run(g[k + "org"], planes, cfg, items[idx])
@@ -83,7 +79,7 @@ def test_results_and_trace_equal_the_restatement(n):
         assert (items["n_ref"] == 2).all()
         assert ((px[:-1] <= 1024) & (px[1:] > 1024)).any() and ((px[:-1] > 1024) & (px[1:] <= 1024)).any()     # the two owner kinds side by side
         # passes of the loop: the first always accepts (uiCostBi starts at the maximum), so an item stops in pass 2, 3 or 4 (or runs all four)
-        ps = np.array([ac.passes(want_trace[i], want[i]["me_calls"]) for i in range(n)])
+        ps = np.array([kit.passes(want_trace[i], want[i]["me_calls"]) for i in range(n)])
         assert set(ps.tolist()) == {2, 3, 4}
         stopped = [int(ps[i]) for i in range(n) if not want_trace[i][int(want[i]["me_calls"]) - 1]["accepted"]]
         assert {2, 3, 4} <= set(stopped)                                                                       # stops in pass 2, 3 and 4
@@ -98,7 +94,7 @@ def test_max_pu_hint_gives_the_same_results_and_skips_what_exceeds_it():
     res, trace = run(org, planes, cfg, items, max_pu=(64, 32))
     big = (items["w"] > 64) | (items["h"] > 32)
     assert big.any() and (~big).any() and (items["w"][~big].astype(int) * items["h"][~big] > 1024).any()
-    assert (res[big]["cost"] == np.uint64(ac.U64_MAX)).all() and (res[big]["me_calls"] == 0).all()
+    assert (res[big]["cost"] == np.uint64(kit.U64_MAX)).all() and (res[big]["me_calls"] == 0).all()
     assert trace[big].tobytes() == bytes(trace[big].nbytes)
     assert np.array_equal(res[~big], want[~big]) and np.array_equal(trace[~big], want_trace[~big])
 
@@ -129,19 +125,13 @@ def test_items_outside_the_contract_get_the_sentinel():
     items[14]["only_ref"][1] = -2
     bad = list(range(1, 15))
     res, trace = run(org, planes, cfg, items)
-    for i in (0, 15):
-        assert res[i].tobytes() == want[i].tobytes() and np.array_equal(trace[i], want_trace[i]), i
-    zero = np.zeros(1, abi.AFFINE_BIPRED_RESULT)
-    zero["cost"] = np.uint64(ac.U64_MAX)
-    for i in bad:
-        assert res[i].tobytes() == zero[0].tobytes(), (i, res[i])
-        assert trace[i].tobytes() == bytes(trace[i].nbytes), i
+    kit.sentinel_check(res, trace, (0, 15), bad, want, want_trace, abi.AFFINE_BIPRED_RESULT)
     # a side beyond the CTU: the same list under a CTU of 64
     cfg64 = dict(cfg, max_cu=64)
     sub = fresh(96)[3][:16]
     w64, t64 = ac.search_all(org, planes, cfg64, sub)
     beyond = (sub["w"] > 64) | (sub["h"] > 64)
-    assert beyond.any() and (~beyond).any() and (w64[beyond]["cost"] == np.uint64(ac.U64_MAX)).all()
+    assert beyond.any() and (~beyond).any() and (w64[beyond]["cost"] == np.uint64(kit.U64_MAX)).all()
     res, trace = run(org, planes, cfg64, sub)
     assert np.array_equal(res, w64) and np.array_equal(trace, t64)
 
@@ -149,29 +139,9 @@ def test_items_outside_the_contract_get_the_sentinel():
 def test_two_streams_from_two_host_threads():
     from vvcsoftware_vtm_amd import ops
     org, planes, cfg, items, want, want_trace = fresh(96)
-    d_org, d_planes, d_items = dev(org), dev(planes), ops.struct_to_device(items)
+    d_org, d_planes, d_items = kit.dev(org), kit.dev(planes), ops.struct_to_device(items)
     dcfg = device_cfg(cfg, d_planes)
-    torch.cuda.synchronize()
-    out, errs = [None, None], []
-
-    def work(k):
-        try:
-            s = torch.cuda.Stream()
-            with torch.cuda.stream(s):
-                for _ in range(3):
-                    res, trace = ops.affine_bipred_me_batch(d_org, d_items, len(items), dcfg)
-                s.synchronize()
-            out[k] = (res.cpu().numpy().view(abi.AFFINE_BIPRED_RESULT), trace.cpu().numpy().view(abi.AFFINE_BIPRED_STEP).reshape(len(items), -1))
-        except Exception as e:                    # noqa: BLE001
-            errs.append(e)
-    ts = [threading.Thread(target=work, args=(k,)) for k in range(2)]
-    for t in ts:
-        t.start()
-    for t in ts:
-        t.join()
-    assert not errs, errs
-    for k in range(2):
-        assert np.array_equal(out[k][0], want) and np.array_equal(out[k][1], want_trace), k
+    kit.two_streams(lambda: ops.affine_bipred_me_batch(d_org, d_items, len(items), dcfg), decode, (want, want_trace))
 
 
 def test_entry_equals_the_chained_form_of_the_existing_entries():
@@ -181,7 +151,7 @@ def test_entry_equals_the_chained_form_of_the_existing_entries():
     shapes = [(16, 16, 0), (32, 32, 1), (64, 32, 0), (16, 16, 1), (128, 128, 0), (32, 64, 1), (16, 128, 0), (16, 16, 0), (128, 16, 1), (32, 32, 0)]
     org, planes, cfg, items = ac.fresh_set(43, 10, shapes, n_ref=(2, 2))
     res, _ = run(org, planes, cfg, items)
-    got, launches = affine_bipred_chain.chained(dev(org), dev(planes), cfg, items, ac.MARGIN)
+    got, launches = affine_bipred_chain.chained(kit.dev(org), kit.dev(planes), cfg, items, ac.MARGIN)
     assert launches > 8
     for f in ("mv", "ref_idx", "mvp_idx", "mvp", "bits", "mot_bits", "me_calls", "closing", "cost"):
         assert np.array_equal(got[f], res[f]), (f, got[f], res[f])

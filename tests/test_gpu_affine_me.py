@@ -3,13 +3,13 @@ reference's results (tests/golden/affine_me.npz) and, step by step, against the 
 reference by tests/test_affine_me_cpu.py)."""
 import functools
 import os
-import threading
 
 import numpy as np
 import pytest
 import torch
 
 import affine_me_cases as amc
+import pu_search_kit as kit
 from vvcsoftware_vtm_amd import abi
 
 pytestmark = pytest.mark.gpu
@@ -25,16 +25,16 @@ SIZES = [(32, 32, 0, 0), (64, 32, 1, 0), (16, 16, 1, 1), (128, 64, 0, 1), (16, 2
          (32, 32, 1, 0), (16, 20, 0, 0), (96, 32, 1, 0), (16, 16, 0, 1), (64, 48, 0, 0)]
 
 
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+def decode(res, trace):
+    return kit.download(res, abi.AFFINE_ME_RESULT), kit.download(trace, abi.AFFINE_ME_STEP, (-1, abi.AFFINE_ME_MAX_STEPS))
 
 
 def run(org, refp, cfg, items, want_trace=True):
+    """this entry takes its one reference plane as an argument, not in its cfg"""
     from vvcsoftware_vtm_amd import ops
-    res, trace = ops.affine_me_batch(dev(org), dev(refp), ops.struct_to_device(items), len(items), cfg, want_trace)
+    out = ops.affine_me_batch(kit.dev(org), kit.dev(refp), ops.struct_to_device(items), len(items), cfg, want_trace)
     torch.cuda.synchronize()
-    res = res.cpu().numpy().view(abi.AFFINE_ME_RESULT)
-    return res, (trace.cpu().numpy().view(abi.AFFINE_ME_STEP).reshape(len(items), abi.AFFINE_ME_MAX_STEPS) if want_trace else None)
+    return decode(*out)
 
 
 @functools.lru_cache(maxsize=None)
@@ -51,7 +51,7 @@ def test_results_equal_the_reference_golden(bd):
     g = np.load(os.path.join(G, "affine_me.npz"))
     k = "bd%d_" % bd
     items, ats, want = g[k + "items"], g[k + "affine_type"], g[k + "want"]
-    refp = amc.pad(g[k + "ref"])
+    refp = kit.pad(g[k + "ref"])
     for at in (1, 0):
         idx = np.nonzero(ats == at)[0]
         res, _ = run(g[k + "org"], refp, amc.make_cfg(float(g[k + "lambda"]), W, H, bd, at), items[idx])
@@ -95,25 +95,5 @@ def test_items_outside_the_contract_get_the_sentinel():
 def test_two_streams_from_two_host_threads():
     from vvcsoftware_vtm_amd import ops
     org, refp, cfg, items, want, want_trace = fresh(37, 1)
-    d_org, d_ref, d_items = dev(org), dev(refp), ops.struct_to_device(items)
-    torch.cuda.synchronize()
-    out, errs = [None, None], []
-
-    def work(k):
-        try:
-            s = torch.cuda.Stream()
-            with torch.cuda.stream(s):
-                for _ in range(3):
-                    res, trace = ops.affine_me_batch(d_org, d_ref, d_items, len(items), cfg)
-                s.synchronize()
-            out[k] = (res.cpu().numpy().view(abi.AFFINE_ME_RESULT), trace.cpu().numpy().view(abi.AFFINE_ME_STEP).reshape(len(items), -1))
-        except Exception as e:                    # noqa: BLE001
-            errs.append(e)
-    ts = [threading.Thread(target=work, args=(k,)) for k in range(2)]
-    for t in ts:
-        t.start()
-    for t in ts:
-        t.join()
-    assert not errs, errs
-    for k in range(2):
-        assert np.array_equal(out[k][0], want) and np.array_equal(out[k][1], want_trace), k
+    d_org, d_ref, d_items = kit.dev(org), kit.dev(refp), ops.struct_to_device(items)
+    kit.two_streams(lambda: ops.affine_me_batch(d_org, d_ref, d_items, len(items), cfg), decode, (want, want_trace))

@@ -4,13 +4,12 @@ launch, against the compiled reference's results (tests/golden/bipred_me.npz) an
 import functools
 import itertools
 import os
-import threading
 
 import numpy as np
 import pytest
-import torch
 
 import bipred_me_cases as bc
+import pu_search_kit as kit
 from vvcsoftware_vtm_amd import abi
 
 pytestmark = pytest.mark.gpu
@@ -19,25 +18,22 @@ W, H = 256, 128
 PAIRS = list(itertools.product(bc.SIDES, bc.SIDES))          # every served (w, h); 32x32 is the last wave-owned square, 64x32 / 32x64 the first workgroup-owned
 
 
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+# ops.bipred_me_cfg's parameters between pic_h and max_cu, as keys of bc.cfg_dict
+CFG_FIELDS = ("bit_depth", "clp", "num_iter", "pick_list_by_cost", "mvd_l1_zero", "search_range", "clip_key", "use_hadamard", "mvp_idx_cost")
 
 
 def device_cfg(cfg, planes_dev, max_pu=(0, 0)):
     from vvcsoftware_vtm_amd import ops
-    m = bc.MARGIN
-    return ops.bipred_me_cfg(cfg["lambda_"], [planes_dev[i] for i in range(planes_dev.shape[0])], (m, m), cfg["pic_w"], cfg["pic_h"], cfg["bit_depth"],
-                             (cfg["clp_min"], cfg["clp_max"]), cfg["num_iter"], cfg["pick_list_by_cost"], cfg["mvd_l1_zero"], cfg["search_range"],
-                             cfg["clip_key"], cfg["use_hadamard"], cfg["mvp_idx_cost"], cfg["max_cu"], max_pu)
+    return kit.device_cfg(ops.bipred_me_cfg, cfg, planes_dev, bc.MARGIN, CFG_FIELDS, max_pu)
+
+
+def decode(res, trace):
+    return kit.download(res, abi.BIPRED_ME_RESULT), kit.download(trace, abi.BIPRED_ME_STEP, (-1, abi.BIPRED_ME_MAX_STEPS))
 
 
 def run(org, planes, cfg, items, want_trace=True, max_pu=(0, 0)):
     from vvcsoftware_vtm_amd import ops
-    d_planes = dev(planes)
-    res, trace = ops.bipred_me_batch(dev(org), ops.struct_to_device(items), len(items), device_cfg(cfg, d_planes, max_pu), want_trace)
-    torch.cuda.synchronize()
-    res = res.cpu().numpy().view(abi.BIPRED_ME_RESULT)
-    return res, (trace.cpu().numpy().view(abi.BIPRED_ME_STEP).reshape(len(items), abi.BIPRED_ME_MAX_STEPS) if want_trace else None)
+    return kit.run(ops.bipred_me_batch, lambda d: device_cfg(cfg, d, max_pu), org, planes, items, want_trace, decode)
 
 
 def shapes_of(n):
@@ -65,7 +61,7 @@ def fresh(n):
 def test_results_and_trace_equal_the_reference_golden(bd):
     g = np.load(os.path.join(G, "bipred_me.npz"))
     k = "bd%d_" % bd
-    planes = bc.pad(g[k + "planes"])
+    planes = kit.pad(g[k + "planes"])
     items, want, want_trace = g[k + "items"], g[k + "want"], g[k + "trace"]
     for cfg, idx in bc.golden_groups(g, bd):
         res, trace = run(g[k + "org"], planes, cfg, items[idx])
@@ -83,7 +79,7 @@ def test_results_and_trace_equal_the_restatement(n):
         assert ((px[:-1] <= 1024) & (px[1:] > 1024)).any() and ((px[:-1] > 1024) & (px[1:] <= 1024)).any()     # the two owner kinds side by side
         # passes of the loop: the first always accepts (uiCostBi starts at the maximum), so an item stops in iIter 1, 2 or 3 or runs all four;
         # stops in iIter 1 (the earliest) next to full runs
-        ps = np.array([bc.passes(want_trace[i], want[i]["me_calls"]) for i in range(n)])
+        ps = np.array([kit.passes(want_trace[i], want[i]["me_calls"]) for i in range(n)])
         assert set(ps.tolist()) == {2, 3, 4}
         assert ((ps[:-1] == 2) & (ps[1:] == 4)).any() or ((ps[:-1] == 4) & (ps[1:] == 2)).any()
     res, trace = run(org, planes, cfg, items)
@@ -97,7 +93,7 @@ def test_max_pu_hint_gives_the_same_results_and_skips_what_exceeds_it():
     res, trace = run(org, planes, cfg, items, max_pu=(32, 16))
     big = (items["w"] > 32) | (items["h"] > 16)
     assert big.any() and (~big).any()
-    assert (res[big]["cost"] == np.uint64(bc.U64_MAX)).all() and (res[big]["me_calls"] == 0).all()
+    assert (res[big]["cost"] == np.uint64(kit.U64_MAX)).all() and (res[big]["me_calls"] == 0).all()
     assert np.array_equal(res[~big], want[~big]) and np.array_equal(trace[~big], want_trace[~big])
 
 
@@ -119,41 +115,15 @@ def test_items_outside_the_contract_get_the_sentinel():
     items[7]["ref"][0][0]["num_cand"] = 0
     items[8]["pos_x"] = W - int(items[8]["w"]) + 4   # not inside the picture
     res, trace = run(org, planes, cfg, items)
-    for i in (0, 9):
-        assert res[i].tobytes() == want[i].tobytes() and np.array_equal(trace[i], want_trace[i]), i
-    zero = np.zeros(1, abi.BIPRED_ME_RESULT)
-    zero["cost"] = np.uint64(bc.U64_MAX)
-    for i in range(1, 9):
-        assert res[i].tobytes() == zero[0].tobytes(), (i, res[i])
-        assert trace[i].tobytes() == bytes(trace[i].nbytes), i
+    kit.sentinel_check(res, trace, (0, 9), range(1, 9), want, want_trace, abi.BIPRED_ME_RESULT)
 
 
 def test_two_streams_from_two_host_threads():
     from vvcsoftware_vtm_amd import ops
     org, planes, cfg, items, want, want_trace = fresh(63)
-    d_org, d_planes, d_items = dev(org), dev(planes), ops.struct_to_device(items)
+    d_org, d_planes, d_items = kit.dev(org), kit.dev(planes), ops.struct_to_device(items)
     dcfg = device_cfg(cfg, d_planes)
-    torch.cuda.synchronize()
-    out, errs = [None, None], []
-
-    def work(k):
-        try:
-            s = torch.cuda.Stream()
-            with torch.cuda.stream(s):
-                for _ in range(3):
-                    res, trace = ops.bipred_me_batch(d_org, d_items, len(items), dcfg)
-                s.synchronize()
-            out[k] = (res.cpu().numpy().view(abi.BIPRED_ME_RESULT), trace.cpu().numpy().view(abi.BIPRED_ME_STEP).reshape(len(items), -1))
-        except Exception as e:                    # noqa: BLE001
-            errs.append(e)
-    ts = [threading.Thread(target=work, args=(k,)) for k in range(2)]
-    for t in ts:
-        t.start()
-    for t in ts:
-        t.join()
-    assert not errs, errs
-    for k in range(2):
-        assert np.array_equal(out[k][0], want) and np.array_equal(out[k][1], want_trace), k
+    kit.two_streams(lambda: ops.bipred_me_batch(d_org, d_items, len(items), dcfg), decode, (want, want_trace))
 
 
 def test_entry_equals_the_chained_form_of_the_existing_entries():
@@ -163,7 +133,7 @@ def test_entry_equals_the_chained_form_of_the_existing_entries():
     shapes = [(16, 16), (8, 8), (32, 16), (64, 64), (16, 16), (4, 8), (128, 32), (16, 16), (8, 8), (32, 32), (16, 64)]
     org, planes, cfg, items = bc.fresh_set(41, 10, shapes, n_ref=(2, 2), single=(4, -8))
     res, _ = run(org, planes, cfg, items)
-    got, launches = bipred_me_chain.chained(dev(org), dev(planes), cfg, items, bc.MARGIN)
+    got, launches = bipred_me_chain.chained(kit.dev(org), kit.dev(planes), cfg, items, bc.MARGIN)
     assert launches > 4 * len(set(shapes))
     for f in ("mv", "ref_idx", "mvp", "bits", "mot_bits", "me_calls", "closing", "cost"):
         assert np.array_equal(got[f], res[f]), (f, got[f], res[f])

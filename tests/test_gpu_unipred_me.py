@@ -3,13 +3,13 @@ compiled reference's results (tests/golden/unipred_me.npz) and the tests' restat
 tests/test_unipred_me_cpu.py), and handed on to vvcgpu_bipred_me_batch from device memory."""
 import functools
 import os
-import threading
 
 import numpy as np
 import pytest
 import torch
 
 import bipred_me_cases as bc
+import pu_search_kit as kit
 import unipred_me_cases as uc
 from vvcsoftware_vtm_amd import abi
 
@@ -19,25 +19,23 @@ W, H = 256, 128
 PAIRS = uc.all_shapes()
 
 
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+# ops.unipred_me_cfg's parameters between pic_h and max_cu, as keys of uc.cfg_dict
+CFG_FIELDS = ("n_ref", "ref_plane", "search_range", "bit_depth", "clp", "list1_to_list0", "fast_me_gen_b_low_delay", "mvd_l1_zero", "first_search_stop",
+              "use_hadamard", "mvp_idx_cost")
 
 
 def device_cfg(cfg, planes_dev, max_pu=None):
     from vvcsoftware_vtm_amd import ops
-    m = uc.MARGIN
-    return ops.unipred_me_cfg(cfg["lambda_"], [planes_dev[i] for i in range(planes_dev.shape[0])], (m, m), cfg["pic_w"], cfg["pic_h"], cfg["n_ref"],
-                              cfg["ref_plane"], cfg["search_range"], cfg["bit_depth"], (cfg["clp_min"], cfg["clp_max"]), cfg["list1_to_list0"],
-                              cfg["fast_me_gen_b_low_delay"], cfg["mvd_l1_zero"], cfg["first_search_stop"], cfg["use_hadamard"], cfg["mvp_idx_cost"],
-                              cfg["max_cu"], cfg["max_pu"] if max_pu is None else max_pu)
+    return kit.device_cfg(ops.unipred_me_cfg, cfg, planes_dev, uc.MARGIN, CFG_FIELDS, cfg["max_pu"] if max_pu is None else max_pu)
+
+
+def decode(res, out):
+    return kit.download(res, abi.UNIPRED_ME_RESULT), kit.download(out, abi.BIPRED_ME_ITEM)
 
 
 def run(org, planes, cfg, items, want_items=True, max_pu=None):
     from vvcsoftware_vtm_amd import ops
-    d_planes = dev(planes)
-    res, out = ops.unipred_me_batch(dev(org), ops.struct_to_device(items), len(items), device_cfg(cfg, d_planes, max_pu), want_items)
-    torch.cuda.synchronize()
-    return res.cpu().numpy().view(abi.UNIPRED_ME_RESULT), (out.cpu().numpy().view(abi.BIPRED_ME_ITEM) if want_items else None)
+    return kit.run(ops.unipred_me_batch, lambda d: device_cfg(cfg, d, max_pu), org, planes, items, want_items, decode)
 
 
 def same(got, want, items, what):
@@ -72,7 +70,7 @@ def fresh(n, search_range=None):
 def test_results_and_out_items_equal_the_reference_golden(bd):
     g = np.load(os.path.join(G, "unipred_me.npz"))
     k = "bd%d_" % bd
-    planes = uc.pad(g[k + "planes"])
+    planes = kit.pad(g[k + "planes"])
     items, want, want_out = g[k + "items"], g[k + "want"], g[k + "out"]
     for cfg, idx in uc.golden_groups(g, bd):
         res, out = run(g[k + "org"], planes, cfg, items[idx])
@@ -104,8 +102,8 @@ def test_out_items_go_straight_into_the_bipredictive_entry(mvd_l1_zero):
     want, want_items = uc.search_all(org, planes, cfg, items)
     bcfg = bc.cfg_dict(cfg["lambda_"], W, H, 10, mvd_l1_zero=mvd_l1_zero, mvp_idx_cost=cfg["mvp_idx_cost"])
     want_bi, want_trace = bc.search_all(org, planes, bcfg, want_items)
-    assert (want_bi["cost"] != np.uint64(bc.U64_MAX)).all() and (want_bi["me_calls"] >= 2).all()
-    d_org, d_planes, m = dev(org), dev(planes), uc.MARGIN
+    assert (want_bi["cost"] != np.uint64(kit.U64_MAX)).all() and (want_bi["me_calls"] >= 2).all()
+    d_org, d_planes, m = kit.dev(org), kit.dev(planes), uc.MARGIN
     dbcfg = ops.bipred_me_cfg(bcfg["lambda_"], [d_planes[i] for i in range(d_planes.shape[0])], (m, m), W, H, 10, (0, 1023), bcfg["num_iter"], bcfg["pick_list_by_cost"],
                               mvd_l1_zero, bcfg["search_range"], bcfg["clip_key"], bcfg["use_hadamard"], bcfg["mvp_idx_cost"], bcfg["max_cu"])
     s = torch.cuda.Stream()
@@ -131,8 +129,8 @@ def test_p_slice_leaves_list_1_untouched():
     for want_items in (True, False):
         res, out = run(org, planes, cfg, items, want_items=want_items)
         same(res, want, items, "result")
-        assert (res["cost"][:, 1] == np.uint64(uc.U64_MAX)).all() and (res["cost"][:, 0] != np.uint64(uc.U64_MAX)).all()
-        assert res["s"][:, 1].tobytes() == bytes(res["s"][:, 1].nbytes) and (res["valid_l1_cost"] == np.uint64(uc.U64_MAX)).all()
+        assert (res["cost"][:, 1] == np.uint64(kit.U64_MAX)).all() and (res["cost"][:, 0] != np.uint64(kit.U64_MAX)).all()
+        assert res["s"][:, 1].tobytes() == bytes(res["s"][:, 1].nbytes) and (res["valid_l1_cost"] == np.uint64(kit.U64_MAX)).all()
         if want_items:
             same(out, want_out, items, "out-item")
             assert (out["n_ref"][:, 1] == 0).all()
@@ -143,7 +141,7 @@ def test_max_pu_hint_gives_the_same_results_and_skips_what_exceeds_it():
     res, out = run(org, planes, cfg, items, max_pu=(32, 16))
     big = (items["w"] > 32) | (items["h"] > 16)
     assert big.any() and (~big).any()
-    assert (res[big]["cost"] == np.uint64(uc.U64_MAX)).all() and out[big].tobytes() == bytes(out[big].nbytes)
+    assert (res[big]["cost"] == np.uint64(kit.U64_MAX)).all() and out[big].tobytes() == bytes(out[big].nbytes)
     assert np.array_equal(res[~big], want[~big]) and np.array_equal(out[~big], want_out[~big])
 
 
@@ -161,41 +159,15 @@ def test_items_outside_the_contract_get_the_sentinel():
     items[9]["org_stride"] = 0
     items[10]["pos_y"] = -4
     res, out = run(org, planes, cfg, items)
-    for i in (0, 11):
-        assert res[i].tobytes() == want[i].tobytes() and out[i].tobytes() == want_out[i].tobytes(), i
-    zero = np.zeros(1, abi.UNIPRED_ME_RESULT)
-    zero["cost"] = np.uint64(uc.U64_MAX)
-    for i in range(1, 11):
-        assert res[i].tobytes() == zero[0].tobytes(), (i, res[i])
-        assert out[i].tobytes() == bytes(out[i].nbytes), i
+    kit.sentinel_check(res, out, (0, 11), range(1, 11), want, want_out, abi.UNIPRED_ME_RESULT)
 
 
 def test_two_streams_from_two_host_threads():
     from vvcsoftware_vtm_amd import ops
     org, planes, cfg, items, want, want_out, _ = fresh(63)
-    d_org, d_planes, d_items = dev(org), dev(planes), ops.struct_to_device(items)
+    d_org, d_planes, d_items = kit.dev(org), kit.dev(planes), ops.struct_to_device(items)
     dcfg = device_cfg(cfg, d_planes)
-    torch.cuda.synchronize()
-    got, errs = [None, None], []
-
-    def work(k):
-        try:
-            s = torch.cuda.Stream()
-            with torch.cuda.stream(s):
-                for _ in range(3):
-                    res, out = ops.unipred_me_batch(d_org, d_items, len(items), dcfg)
-                s.synchronize()
-            got[k] = (res.cpu().numpy().view(abi.UNIPRED_ME_RESULT), out.cpu().numpy().view(abi.BIPRED_ME_ITEM))
-        except Exception as e:                    # noqa: BLE001
-            errs.append(e)
-    ts = [threading.Thread(target=work, args=(k,)) for k in range(2)]
-    for t in ts:
-        t.start()
-    for t in ts:
-        t.join()
-    assert not errs, errs
-    for k in range(2):
-        assert np.array_equal(got[k][0], want) and np.array_equal(got[k][1], want_out), k
+    kit.two_streams(lambda: ops.unipred_me_batch(d_org, d_items, len(items), dcfg), decode, (want, want_out))
 
 
 def test_entry_ends_where_the_chain_of_the_existing_entries_ends():
@@ -206,7 +178,7 @@ def test_entry_ends_where_the_chain_of_the_existing_entries_ends():
     org, planes, cfg, items = uc.fresh_set(41, 10, shapes, n_ref=(2, 2), list1_to_list0=(-1, 0, -1, -1), fast_me_gen_b_low_delay=1, mvd_l1_zero=1, fast=True,
                                            search_range=((32, 8, 8, 8), (32, 8, 8, 8)))
     res, _ = run(org, planes, cfg, items)
-    got, calls = unipred_me_chain.chained(dev(org), dev(planes), cfg, items, uc.MARGIN)
+    got, calls = unipred_me_chain.chained(kit.dev(org), kit.dev(planes), cfg, items, uc.MARGIN)
     assert calls > 3 * len(set(shapes))
     for f in res.dtype.names:
         assert np.array_equal(got[f], res[f]), (f, got[f], res[f])

@@ -1,15 +1,13 @@
-"""CPU checks of explicit weighted prediction (vvcgpu_mc_wp_batch): the host-side argument checks (no device is touched), the table entry's layout, and
-the tests' restatement of the weighted epilogue against the reference's own addWeightUni / addWeightBi (tests/golden/wp.npz)."""
+"""CPU checks of explicit weighted prediction (vvcgpu_mc_wp_batch): the host-side argument checks (no device is touched) and the tests' restatement of
+the weighted epilogue against the reference's own addWeightUni / addWeightBi (tests/golden/wp.npz).  The table entry's layout: tests/test_abi.py."""
 import ctypes as C
 import os
-import shlex
-import subprocess
 
 import numpy as np
 
 import wp_cases
 from oraclelib import oracle
-from vvcsoftware_vtm_amd import abi, capi
+from vvcsoftware_vtm_amd import capi
 
 G = os.path.join(os.path.dirname(__file__), "golden")
 
@@ -37,21 +35,6 @@ def test_wp_argument_checks_need_no_device():
     assert call(P, P, P, P, 4, C.c_void_p(4096 + 4), 1, 10, 0, 1023, None) == -1 and b"aligned" in lib.vvcgpu_last_error()
     for bd in (7, 11, 12):
         assert call(P, P, P, P, 4, P, 1, bd, 0, 1023, None) == -3 and b"bit depth" in lib.vvcgpu_last_error()
-
-
-def test_wp_param_layout(tmp_path):
-    lib = _lib()
-    assert lib.vvcgpu_sizeof(31) == abi.WP_PARAM.itemsize == 16
-    src = tmp_path / "wp.c"
-    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "vvcgpu.h"\nint main(void)\n{\n'
-                   + "".join('  printf("%%s %%zu %%zu\\n", "%s", offsetof(vvcgpu_wp_param, %s), sizeof(((vvcgpu_wp_param*)0)->%s));\n' % (f, f, f)
-                             for f in abi.WP_PARAM.names) + "  return 0;\n}\n")
-    exe = tmp_path / "wp"
-    r = subprocess.run(shlex.split(os.environ.get("CC", "cc")) + ["-I", os.path.dirname(capi.HEADER), str(src), "-o", str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    for line in subprocess.check_output([str(exe)], text=True).splitlines():
-        f, off, sz = line.split()
-        assert (int(off), int(sz)) == (abi.WP_PARAM.fields[f][1], abi.WP_PARAM.fields[f][0].itemsize), f
 
 
 def test_wp_param_helper_restates_get_wp_scaling():

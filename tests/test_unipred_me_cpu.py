@@ -1,16 +1,15 @@
 """CPU checks of the uni-predictive stage (vvcgpu_unipred_me_batch): the tests' restatement of the uni-predictive loop of InterSearch::predInterSearch
 (tests/unipred_me_cases.py) against the results the compiled reference's own xEstimateMvPredAMVP / xMotionEstimation / xCheckBestMVP gave
-(tests/golden/unipred_me.npz), the five structs' layout against the header, the exported symbol, and the host-side argument checks (no device is
-touched)."""
+(tests/golden/unipred_me.npz), the exported symbol, and the host-side argument checks (no device is touched).  The structs' layout:
+tests/test_abi.py."""
 import ctypes as C
 import os
-import shlex
-import subprocess
 
 import numpy as np
 import pytest
 
 import unipred_me_cases as uc
+import pu_search_kit as kit
 from vvcsoftware_vtm_amd import abi, capi
 
 G = os.path.join(os.path.dirname(__file__), "golden")
@@ -32,7 +31,7 @@ def test_restatement_equals_reference_golden(bd):
     k = "bd%d_" % bd
     items, want, want_out = g[k + "items"], g[k + "want"], g[k + "out"]
     assert len(items) >= 100 and int(g[k + "dropped"]) * 4 <= int(g[k + "generated"]) and len(items) + int(g[k + "dropped"]) == int(g[k + "generated"])
-    planes = uc.pad(g[k + "planes"])
+    planes = kit.pad(g[k + "planes"])
     assert planes.shape[1:] == (H + 2 * uc.MARGIN, W + 2 * uc.MARGIN)
     seen = set()
     for cfg, idx in uc.golden_groups(g, bd):
@@ -72,52 +71,11 @@ def test_the_cached_start_path_takes_the_fast_settings_from_the_cached_vector():
     assert differ == len(items)
 
 
-MIRRORS = {"vvcgpu_unipred_me_ref": (50, abi.UNIPRED_ME_REF, 40), "vvcgpu_unipred_me_item": (51, abi.UNIPRED_ME_ITEM, 360),
-           "vvcgpu_unipred_me_cfg": (52, abi.UnipredMeCfg, 304), "vvcgpu_unipred_me_search": (53, abi.UNIPRED_ME_SEARCH, 48),
-           "vvcgpu_unipred_me_result": (54, abi.UNIPRED_ME_RESULT, 472)}
-
-
-def _fields(m):
-    if isinstance(m, np.dtype):
-        return [(n, m.fields[n][1], m.fields[n][0].itemsize) for n in m.names]
-    return [("lambda" if f[0] == "lambda_" else f[0], getattr(m, f[0]).offset, getattr(m, f[0]).size) for f in m._fields_]
-
-
 def test_the_entry_is_exported_and_declared():
     lib = _lib()
     assert "vvcgpu_unipred_me_batch" in capi.declared_symbols() and hasattr(lib, "vvcgpu_unipred_me_batch")
     restype, argtypes = capi.prototypes()["vvcgpu_unipred_me_batch"]
     assert restype is C.c_int and argtypes == (C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
-
-
-def test_struct_mirrors_match_the_header(tmp_path):
-    lib = _lib()
-    lines = []
-    for cname, (sid, m, size) in MIRRORS.items():
-        assert lib.vvcgpu_sizeof(sid) == size == (m.itemsize if isinstance(m, np.dtype) else C.sizeof(m)), cname
-        lines.append('  printf("%%s . %%zu %%zu\\n", "%s", (size_t)0, sizeof(%s));\n' % (cname, cname))
-        lines += ['  printf("%%s %%s %%zu %%zu\\n", "%s", "%s", offsetof(%s, %s), sizeof(((%s*)0)->%s));\n' % (cname, f, cname, f, cname, f)
-                  for f, _, _ in _fields(m)]
-    src = tmp_path / "upm.c"
-    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "vvcgpu.h"\nint main(void)\n{\n' + "".join(lines) + "  return 0;\n}\n")
-    exe = tmp_path / "upm"
-    r = subprocess.run(shlex.split(os.environ.get("CC", "cc")) + ["-I", os.path.dirname(capi.HEADER), str(src), "-o", str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    got = {}
-    for line in subprocess.check_output([str(exe)], text=True).splitlines():
-        c, f, off, sz = line.split()
-        got[(c, f)] = (int(off), int(sz))
-    for cname, (sid, m, size) in MIRRORS.items():
-        assert got[(cname, ".")] == (0, size)
-        for f, off, sz in _fields(m):
-            assert got[(cname, f)] == (off, sz), (cname, f)
-    hdr = " ".join(open(capi.HEADER).read().split())
-    for name, v in (("MAX_REFS", abi.UNIPRED_ME_MAX_REFS), ("MAX_PLANES", abi.UNIPRED_ME_MAX_PLANES)):
-        assert "#define VVCGPU_UNIPRED_ME_%s %d" % (name, v) in hdr, name
-    assert "VVCGPU_UNIPRED_PRED2 = %d, VVCGPU_UNIPRED_CACHED = %d" % (abi.UNIPRED_PRED2, abi.UNIPRED_CACHED) in hdr
-    assert lib.vvcgpu_sizeof(43) == -1 and lib.vvcgpu_sizeof(49) == -1 and lib.vvcgpu_sizeof(55) == -1
-    # the out-items are the bi-predictive entry's items
-    assert abi.BIPRED_ME_MAX_REFS == abi.UNIPRED_ME_MAX_REFS and abi.BIPRED_ME_MAX_PLANES == abi.UNIPRED_ME_MAX_PLANES
 
 
 def _cfg(**kw):

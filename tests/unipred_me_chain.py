@@ -7,22 +7,11 @@ import time
 import numpy as np
 import torch
 
+from pu_search_kit import eg_bits, get_cost
 from vvcsoftware_vtm_amd import abi, ops
 
 U64 = np.uint64
 CLAMP = 14
-
-
-def eg_bits(v):
-    """xGetExpGolombNumberOfBits (RdCost.h:172-184), vectorised"""
-    v = v.astype(np.int64)
-    t = np.where(v <= 0, ((-v) << 1) + 1, v << 1)
-    ln = np.ones_like(t)
-    while (t > 128).any():
-        big = t > 128
-        ln += 14 * big
-        t = np.where(big, t >> 7, t)
-    return ln + 2 * np.floor(np.log2(t)).astype(np.int64)
 
 
 def mv_bits(pred, mv):
@@ -40,7 +29,7 @@ class Chain:
         self.device_s = self.host_s = 0.0
 
     def get_cost(self, bits):
-        return (self.c["lambda_"] * bits.astype(np.float64)).astype(U64)
+        return get_cost(self.c["lambda_"], bits)
 
     def clip(self, v, pos, pic):
         return np.minimum((pic + 8 - pos - 1) << 2, np.maximum((-self.c["max_cu"] - 8 - pos + 1) << 2, v))

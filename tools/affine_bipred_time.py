@@ -22,6 +22,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import affine_bipred_cases as ac  # noqa: E402
+import pu_search_kit as kit  # noqa: E402
 import affine_bipred_chain  # noqa: E402
 from vvcsoftware_vtm_amd import abi, ops  # noqa: E402
 
@@ -57,19 +58,9 @@ def build_items(side):
     return items
 
 
-def events(fn):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    a.record()
-    out = fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b), out
-
-
 def main():
-    planes, org = ac.make_planes(rng, N_PLANES, W, H, BD)
-    d_org, d_planes = torch.from_numpy(org).cuda(), torch.from_numpy(ac.pad(planes)).cuda()
+    planes, org = kit.planes_and_mean_org(rng, N_PLANES, W, H, BD)
+    d_org, d_planes = torch.from_numpy(org).cuda(), torch.from_numpy(kit.pad(planes)).cuda()
     cfg = ac.cfg_dict(LAMBDA, W, H, BD, mvp_idx_cost=(1, 1, 0))
     print("list       PUs   ME calls  chain launches   chain ms (min..max)     one launch ms (min..max)   kernel ms   chain / one launch")
     for side in (16, 64):
@@ -89,15 +80,9 @@ def main():
         got, launches = chain()
         for f in ("mv", "ref_idx", "mvp_idx", "mvp", "bits", "mot_bits", "me_calls", "closing", "cost"):
             assert np.array_equal(got[f], res[f]), (side, f)
-        for _ in range(WARMUP - 1):
-            one_call()
-            chain()
-        ta, tb = [], []
-        for _ in range(RUNS):
-            ta.append(events(chain)[0])
-            tb.append(events(one_call)[0])
+        ta, tb = kit.times_of_alternating((chain, one_call), WARMUP - 1, RUNS)              # the comparison above was the first warm-up run
         d_items = ops.struct_to_device(items)
-        tk = sorted(events(lambda: ops.affine_bipred_me_batch(d_org, d_items, n, dcfg, want_trace=False))[0] for _ in range(RUNS))[RUNS // 2]
+        tk = sorted(kit.events(lambda: ops.affine_bipred_me_batch(d_org, d_items, n, dcfg, want_trace=False))[0] for _ in range(RUNS))[RUNS // 2]
         a, b = float(np.median(ta)), float(np.median(tb))
         print("%-7s %6d  %9d  %14d   %8.2f (%.2f..%.2f)   %8.2f (%.2f..%.2f)   %9.2f   %8.2f" %
               ("%dx%d" % (side, side), n, int(res["me_calls"].sum()), launches, a, min(ta), max(ta), b, min(tb), max(tb), tk, a / b), flush=True)

@@ -14,7 +14,10 @@ import time
 import numpy as np
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+from pu_search_kit import eg_bits  # noqa: E402
 from vvcsoftware_vtm_amd import abi, ops  # noqa: E402
 
 W, H, bd, M = 3840, 2160, 10, 144
@@ -28,18 +31,6 @@ def texture(h, w):
     y, x = np.mgrid[0:h, 0:w].astype(np.float32)
     a = 0.5 + 0.22 * np.sin(x / 9.0 + y / 23.0) + 0.18 * np.cos(y / 7.0 - x / 31.0) + 0.08 * np.sin((x + 2 * y) / 3.5)
     return np.clip(np.rint(a * 1023 + rng.normal(0, 5.0, (h, w))), 0, 1023).astype(np.int16)
-
-
-def eg_bits(v):
-    """xGetExpGolombNumberOfBits (RdCost.h:180-192), vectorised"""
-    v = v.astype(np.int64)
-    t = np.where(v <= 0, ((-v) << 1) + 1, v << 1)
-    ln = np.ones_like(t)
-    while (t > 128).any():
-        big = t > 128
-        ln += 14 * big
-        t = np.where(big, t >> 7, t)
-    return ln + 2 * np.floor(np.log2(t)).astype(np.int64)
 
 
 def quant(d):

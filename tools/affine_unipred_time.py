@@ -23,6 +23,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import affine_unipred_cases as uc  # noqa: E402
+import pu_search_kit as kit  # noqa: E402
 import affine_unipred_chain  # noqa: E402
 from vvcsoftware_vtm_amd import abi, ops  # noqa: E402
 
@@ -54,19 +55,9 @@ def build_items(side):
     return items
 
 
-def events(fn):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    a.record()
-    out = fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b), out
-
-
 def main():
-    planes, org = uc.make_planes(rng, N_PLANES, W, H, BD)
-    d_org, d_planes = torch.from_numpy(org).cuda(), torch.from_numpy(uc.pad(planes)).cuda()
+    planes, org = kit.planes_and_first_org(rng, N_PLANES, W, H, BD)
+    d_org, d_planes = torch.from_numpy(org).cuda(), torch.from_numpy(kit.pad(planes)).cuda()
     cfg = uc.cfg_dict(LAMBDA, W, H, BD, n_ref=N_REF, ref_plane=REF_PLANE)
     pl = [d_planes[i] for i in range(N_PLANES)]
     print("list       PUs  searches  (a) launches   (a) chain ms (min..max)    (b) entry ms (min..max)   (b) kernels ms   (c) entry + bi ms (min..max)   (a) / (b)")
@@ -96,18 +87,10 @@ def main():
         for f in res.dtype.names:
             assert np.array_equal(got[f], res[f]), (side, f)
         r2, bi = entry_bi()
-        assert np.array_equal(r2, res) and (bi["cost"] != np.uint64(uc.U64_MAX)).all()
-        for _ in range(WARMUP - 1):
-            chain()
-            entry()
-            entry_bi()
-        ta, tb, tc = [], [], []
-        for _ in range(RUNS):
-            ta.append(events(chain)[0])
-            tb.append(events(entry)[0])
-            tc.append(events(entry_bi)[0])
+        assert np.array_equal(r2, res) and (bi["cost"] != np.uint64(kit.U64_MAX)).all()
+        ta, tb, tc = kit.times_of_alternating((chain, entry, entry_bi), WARMUP - 1, RUNS)   # the comparison above was the first warm-up run
         d_items = ops.struct_to_device(items)
-        tk = sorted(events(lambda: ops.affine_unipred_me_batch(d_org, d_items, n, dcfg, want_bipred_items=False))[0] for _ in range(RUNS))[RUNS // 2]
+        tk = sorted(kit.events(lambda: ops.affine_unipred_me_batch(d_org, d_items, n, dcfg, want_bipred_items=False))[0] for _ in range(RUNS))[RUNS // 2]
         a, b, c = float(np.median(ta)), float(np.median(tb)), float(np.median(tc))
         print("%-7s %6d  %8d  %12d   %9.2f (%.2f..%.2f)   %9.2f (%.2f..%.2f)   %14.2f   %9.2f (%.2f..%.2f)   %9.2f" %
               ("%dx%d" % (side, side), n, int((res["s"]["searched"] == 1).sum()), launches, a, min(ta), max(ta), b, min(tb), max(tb), tk, c, min(tc), max(tc), a / b),

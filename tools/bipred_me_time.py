@@ -21,6 +21,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import bipred_me_cases as bc  # noqa: E402
+import pu_search_kit as kit  # noqa: E402
 import bipred_me_chain  # noqa: E402
 from vvcsoftware_vtm_amd import abi, ops, shape_mix  # noqa: E402
 
@@ -42,20 +43,10 @@ def build_items(shapes, pos):
     return items
 
 
-def events(fn):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    a.record()
-    out = fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b), out
-
-
 def main():
-    planes = np.stack([bc.texture(rng, H, W, BD, 1.5 * k) for k in range(N_PLANES)])
+    planes = np.stack([kit.texture(rng, H, W, BD, 1.5 * k) for k in range(N_PLANES)])
     org = np.clip(planes.astype(np.int32).mean(axis=0) + rng.integers(-6, 7, (H, W)), 0, 1023).astype(np.int16)
-    d_org, d_planes = torch.from_numpy(org).cuda(), torch.from_numpy(bc.pad(planes)).cuda()
+    d_org, d_planes = torch.from_numpy(org).cuda(), torch.from_numpy(kit.pad(planes)).cuda()
     cfg = bc.cfg_dict(LAMBDA, W, H, BD, mvp_idx_cost=(1, 1, 0))
     hist, _ = shape_mix.load_trace()
     sig = shape_mix.signatures(hist, "pelop", lambda w, h, a, b, c: a == 0 and w in bc.SIDES and h in bc.SIDES)
@@ -81,15 +72,9 @@ def main():
         got, launches = chain()
         for f in ("mv", "ref_idx", "bits", "mot_bits", "me_calls", "closing", "cost"):
             assert np.array_equal(got[f], res[f]), (name, f)
-        for _ in range(WARMUP - 1):
-            one_call()
-            chain()
-        ta, tb = [], []
-        for _ in range(RUNS):
-            ta.append(events(chain)[0])
-            tb.append(events(one_call)[0])
+        ta, tb = kit.times_of_alternating((chain, one_call), WARMUP - 1, RUNS)              # the comparison above was the first warm-up run
         d_items = ops.struct_to_device(items)
-        tk = sorted(events(lambda: ops.bipred_me_batch(d_org, d_items, n, dcfg, want_trace=False))[0] for _ in range(RUNS))[RUNS // 2]
+        tk = sorted(kit.events(lambda: ops.bipred_me_batch(d_org, d_items, n, dcfg, want_trace=False))[0] for _ in range(RUNS))[RUNS // 2]
         a, b = float(np.median(ta)), float(np.median(tb))
         print("%-10s %6d  %9d  %14d   %8.2f (%.2f..%.2f)   %8.2f (%.2f..%.2f)   %9.2f   %8.2f" %
               (name, n, int(res["me_calls"].sum()), launches, a, min(ta), max(ta), b, min(tb), max(tb), tk, a / b))

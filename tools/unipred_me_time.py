@@ -22,6 +22,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import unipred_me_cases as uc  # noqa: E402
+import pu_search_kit as kit  # noqa: E402
 import unipred_me_chain  # noqa: E402
 from vvcsoftware_vtm_amd import abi, ops, shape_mix  # noqa: E402
 
@@ -49,20 +50,10 @@ def build_items(shapes, pos):
     return items
 
 
-def events(fn):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    a.record()
-    out = fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b), out
-
-
 def main():
-    planes = np.stack([uc.texture(rng, H, W, BD, 1.5 * k) for k in range(N_PLANES)])
+    planes = np.stack([kit.texture(rng, H, W, BD, 1.5 * k) for k in range(N_PLANES)])
     org = np.clip(np.roll(planes[0], (3, -5), axis=(0, 1)).astype(np.int32) + rng.integers(-6, 7, (H, W)), 0, 1023).astype(np.int16)
-    d_org, d_planes = torch.from_numpy(org).cuda(), torch.from_numpy(uc.pad(planes)).cuda()
+    d_org, d_planes = torch.from_numpy(org).cuda(), torch.from_numpy(kit.pad(planes)).cuda()
     cfg = uc.cfg_dict(LAMBDA, W, H, BD, n_ref=N_REF, search_range=RANGE)
     hist, _ = shape_mix.load_trace()
     sig = shape_mix.signatures(hist, "pelop", lambda w, h, a, b, c: a == 0 and w in uc.SIDES and h in uc.SIDES)
@@ -98,22 +89,13 @@ def main():
         for f in res.dtype.names:
             assert np.array_equal(got[f], res[f]), (name, f)
         bi = entry_bipred()
-        assert (bi["cost"] != np.uint64(uc.U64_MAX)).all()
-        for _ in range(WARMUP - 1):
-            entry()
-            chain()
-            entry_bipred()
-        del host[:]
-        ta, tb, tc = [], [], []
-        for _ in range(RUNS):
-            ta.append(events(chain)[0])
-            tb.append(events(entry)[0])
-            tc.append(events(entry_bipred)[0])
+        assert (bi["cost"] != np.uint64(kit.U64_MAX)).all()
+        ta, tb, tc = kit.times_of_alternating((chain, entry, entry_bipred), WARMUP - 1, RUNS)   # the comparison above was the first warm-up run
         d_items = ops.struct_to_device(items)
-        tk = sorted(events(lambda: ops.unipred_me_batch(d_org, d_items, n, dcfg, want_bipred_items=False))[0] for _ in range(RUNS))[RUNS // 2]
+        tk = sorted(kit.events(lambda: ops.unipred_me_batch(d_org, d_items, n, dcfg, want_bipred_items=False))[0] for _ in range(RUNS))[RUNS // 2]
         a, b, c = float(np.median(ta)), float(np.median(tb)), float(np.median(tc))
         print("%-10s %6d  %6d  %11d   %8.2f (%.2f..%.2f)   %10.2f   %8.2f (%.2f..%.2f)   %11.2f   %8.2f (%.2f..%.2f)   %10.2f" %
-              (name, n, len(set(shapes)), calls, a, min(ta), max(ta), float(np.median(host)), b, min(tb), max(tb), tk, c, min(tc), max(tc), a / b))
+              (name, n, len(set(shapes)), calls, a, min(ta), max(ta), float(np.median(host[-RUNS:])), b, min(tb), max(tb), tk, c, min(tc), max(tc), a / b))
 
 
 if __name__ == "__main__":

@@ -527,13 +527,10 @@ def affine_me_batch(org_base, ref_base, items_dev, n, cfg, want_trace=True):
     return res, trace
 
 
-def bipred_me_cfg(lambda_, ref_planes, ref_origin, pic_w, pic_h, bit_depth=10, clp=(0, 1023), num_iter=4, pick_list_by_cost=False, mvd_l1_zero=False,
-                  search_range=4, clip_key=True, use_hadamard=True, mvp_idx_cost=(1, 1, 0), max_cu=128, max_pu=(0, 0)):
-    """vvcgpu_bipred_me_cfg of one slice.  ref_planes: the PADDED reference luma planes (2-D int16 CUDA tensors of one stride; keep them alive while
-    calls that use the cfg run); ref_origin = (x, y) of picture sample (0, 0) inside each of them"""
-    cfg = BipredMeCfg()
+def _pu_frame(cfg, lambda_, ref_planes, ref_origin, pic_w, pic_h, bit_depth, clp, max_cu, mvp_idx_cost, max_pu):
+    """the fields every whole-PU search cfg begins and ends with (pu_entry_host.h checks them as one frame)"""
     cfg.lambda_ = lambda_
-    assert 1 <= len(ref_planes) <= BIPRED_ME_MAX_PLANES
+    assert 1 <= len(ref_planes) <= len(cfg.ref_planes)                   # the entry's MAX_PLANES
     for i, t in enumerate(ref_planes):
         ptr, stride, _, _ = _plane(t, "ref_planes[%d]" % i)
         assert stride == ref_planes[0].stride(0), "reference planes of one stride"
@@ -541,10 +538,28 @@ def bipred_me_cfg(lambda_, ref_planes, ref_origin, pic_w, pic_h, bit_depth=10, c
     cfg.n_planes, cfg.ref_stride = len(ref_planes), ref_planes[0].stride(0)
     cfg.pic_w, cfg.pic_h, cfg.max_cu_w, cfg.max_cu_h = pic_w, pic_h, max_cu, max_cu
     cfg.bit_depth, cfg.clp_min, cfg.clp_max = bit_depth, clp[0], clp[1]
-    cfg.num_iter, cfg.pick_list_by_cost, cfg.mvd_l1_zero = num_iter, int(pick_list_by_cost), int(mvd_l1_zero)
-    cfg.bipred_search_range, cfg.clip_for_bipred_me, cfg.use_hadamard = search_range, int(clip_key), int(use_hadamard)
     cfg.mvp_idx_cost[:] = mvp_idx_cost
     cfg.max_pu_w, cfg.max_pu_h = max_pu
+    return cfg
+
+
+def _unipred_refs(cfg, n_ref, ref_plane, list1_to_list0):
+    """the reference lists of a uni-predictive cfg: counts, the plane of every reference index, list 1's twins in list 0"""
+    max_refs = len(cfg.list1_to_list0)                                   # the entry's MAX_REFS
+    cfg.n_ref[:] = n_ref
+    for l in range(2):
+        for r in range(min(n_ref[l], max_refs)):
+            cfg.ref_plane[l][r] = ref_plane[l][r]
+    cfg.list1_to_list0[:] = (tuple(list1_to_list0) + (-1,) * max_refs)[:max_refs]
+
+
+def bipred_me_cfg(lambda_, ref_planes, ref_origin, pic_w, pic_h, bit_depth=10, clp=(0, 1023), num_iter=4, pick_list_by_cost=False, mvd_l1_zero=False,
+                  search_range=4, clip_key=True, use_hadamard=True, mvp_idx_cost=(1, 1, 0), max_cu=128, max_pu=(0, 0)):
+    """vvcgpu_bipred_me_cfg of one slice.  ref_planes: the PADDED reference luma planes (2-D int16 CUDA tensors of one stride; keep them alive while
+    calls that use the cfg run); ref_origin = (x, y) of picture sample (0, 0) inside each of them"""
+    cfg = _pu_frame(BipredMeCfg(), lambda_, ref_planes, ref_origin, pic_w, pic_h, bit_depth, clp, max_cu, mvp_idx_cost, max_pu)
+    cfg.num_iter, cfg.pick_list_by_cost, cfg.mvd_l1_zero = num_iter, int(pick_list_by_cost), int(mvd_l1_zero)
+    cfg.bipred_search_range, cfg.clip_for_bipred_me, cfg.use_hadamard = search_range, int(clip_key), int(use_hadamard)
     return cfg
 
 
@@ -565,25 +580,13 @@ def unipred_me_cfg(lambda_, ref_planes, ref_origin, pic_w, pic_h, n_ref, ref_pla
     """vvcgpu_unipred_me_cfg of one slice.  ref_planes: the PADDED reference luma planes (2-D int16 CUDA tensors of one stride; keep them alive while
     calls that use the cfg run); ref_origin = (x, y) of picture sample (0, 0) inside each of them; n_ref = (list 0, list 1) reference counts, ref_plane
     and search_range = per list the plane index / m_aaiAdaptSR of every reference index"""
-    cfg = UnipredMeCfg()
-    cfg.lambda_ = lambda_
-    assert 1 <= len(ref_planes) <= UNIPRED_ME_MAX_PLANES
-    for i, t in enumerate(ref_planes):
-        ptr, stride, _, _ = _plane(t, "ref_planes[%d]" % i)
-        assert stride == ref_planes[0].stride(0), "reference planes of one stride"
-        cfg.ref_planes[i] = ptr.value + 2 * (ref_origin[1] * stride + ref_origin[0])
-    cfg.n_planes, cfg.ref_stride = len(ref_planes), ref_planes[0].stride(0)
-    cfg.pic_w, cfg.pic_h, cfg.max_cu_w, cfg.max_cu_h = pic_w, pic_h, max_cu, max_cu
-    cfg.bit_depth, cfg.clp_min, cfg.clp_max = bit_depth, clp[0], clp[1]
-    cfg.n_ref[:] = n_ref
+    cfg = _pu_frame(UnipredMeCfg(), lambda_, ref_planes, ref_origin, pic_w, pic_h, bit_depth, clp, max_cu, mvp_idx_cost, max_pu)
+    _unipred_refs(cfg, n_ref, ref_plane, list1_to_list0)
     for l in range(2):
         for r in range(min(n_ref[l], UNIPRED_ME_MAX_REFS)):
-            cfg.ref_plane[l][r], cfg.search_range[l][r] = ref_plane[l][r], search_range[l][r]
-    cfg.list1_to_list0[:] = (tuple(list1_to_list0) + (-1,) * UNIPRED_ME_MAX_REFS)[:UNIPRED_ME_MAX_REFS]
+            cfg.search_range[l][r] = search_range[l][r]
     cfg.fast_me_gen_b_low_delay, cfg.mvd_l1_zero = int(fast_me_gen_b_low_delay), int(mvd_l1_zero)
     cfg.first_search_stop, cfg.use_hadamard = int(first_search_stop), int(use_hadamard)
-    cfg.mvp_idx_cost[:] = mvp_idx_cost
-    cfg.max_pu_w, cfg.max_pu_h = max_pu
     return cfg
 
 
@@ -602,20 +605,9 @@ def affine_bipred_cfg(lambda_, ref_planes, ref_origin, pic_w, pic_h, bit_depth=1
                       clip_key=True, affine_type=1, mvp_idx_cost=(1, 1, 0), max_cu=128, max_pu=(0, 0)):
     """vvcgpu_affine_bipred_cfg of one slice.  ref_planes: the PADDED reference luma planes (2-D int16 CUDA tensors of one stride; keep them alive while
     calls that use the cfg run); ref_origin = (x, y) of picture sample (0, 0) inside each of them"""
-    cfg = AffineBipredCfg()
-    cfg.lambda_ = lambda_
-    assert 1 <= len(ref_planes) <= 16
-    for i, t in enumerate(ref_planes):
-        ptr, stride, _, _ = _plane(t, "ref_planes[%d]" % i)
-        assert stride == ref_planes[0].stride(0), "reference planes of one stride"
-        cfg.ref_planes[i] = ptr.value + 2 * (ref_origin[1] * stride + ref_origin[0])
-    cfg.n_planes, cfg.ref_stride = len(ref_planes), ref_planes[0].stride(0)
-    cfg.pic_w, cfg.pic_h, cfg.max_cu_w, cfg.max_cu_h = pic_w, pic_h, max_cu, max_cu
-    cfg.bit_depth, cfg.clp_min, cfg.clp_max = bit_depth, clp[0], clp[1]
+    cfg = _pu_frame(AffineBipredCfg(), lambda_, ref_planes, ref_origin, pic_w, pic_h, bit_depth, clp, max_cu, mvp_idx_cost, max_pu)
     cfg.num_iter, cfg.pick_list_by_cost, cfg.mvd_l1_zero = num_iter, int(pick_list_by_cost), int(mvd_l1_zero)
     cfg.clip_for_bipred_me, cfg.affine_type = int(clip_key), int(affine_type)
-    cfg.mvp_idx_cost[:] = mvp_idx_cost
-    cfg.max_pu_w, cfg.max_pu_h = max_pu
     return cfg
 
 
@@ -635,24 +627,9 @@ def affine_unipred_cfg(lambda_, ref_planes, ref_origin, pic_w, pic_h, n_ref, ref
     """vvcgpu_affine_unipred_cfg of one slice.  ref_planes: the PADDED reference luma planes (2-D int16 CUDA tensors of one stride; keep them alive while
     calls that use the cfg run); ref_origin = (x, y) of picture sample (0, 0) inside each of them; n_ref = (list 0, list 1) reference counts,
     ref_plane = per list the plane index of every reference index"""
-    cfg = AffineUnipredCfg()
-    cfg.lambda_ = lambda_
-    assert 1 <= len(ref_planes) <= 16
-    for i, t in enumerate(ref_planes):
-        ptr, stride, _, _ = _plane(t, "ref_planes[%d]" % i)
-        assert stride == ref_planes[0].stride(0), "reference planes of one stride"
-        cfg.ref_planes[i] = ptr.value + 2 * (ref_origin[1] * stride + ref_origin[0])
-    cfg.n_planes, cfg.ref_stride = len(ref_planes), ref_planes[0].stride(0)
-    cfg.pic_w, cfg.pic_h, cfg.max_cu_w, cfg.max_cu_h = pic_w, pic_h, max_cu, max_cu
-    cfg.bit_depth, cfg.clp_min, cfg.clp_max = bit_depth, clp[0], clp[1]
-    cfg.n_ref[:] = n_ref
-    for l in range(2):
-        for r in range(min(n_ref[l], AFFINE_UNIPRED_MAX_REFS)):
-            cfg.ref_plane[l][r] = ref_plane[l][r]
-    cfg.list1_to_list0[:] = (tuple(list1_to_list0) + (-1,) * AFFINE_UNIPRED_MAX_REFS)[:AFFINE_UNIPRED_MAX_REFS]
+    cfg = _pu_frame(AffineUnipredCfg(), lambda_, ref_planes, ref_origin, pic_w, pic_h, bit_depth, clp, max_cu, mvp_idx_cost, max_pu)
+    _unipred_refs(cfg, n_ref, ref_plane, list1_to_list0)
     cfg.fast_me_gen_b_low_delay, cfg.mvd_l1_zero, cfg.affine_type = int(fast_me_gen_b_low_delay), int(mvd_l1_zero), int(affine_type)
-    cfg.mvp_idx_cost[:] = mvp_idx_cost
-    cfg.max_pu_w, cfg.max_pu_h = max_pu
     return cfg
 
 
