@@ -649,8 +649,18 @@ int vvcgpu_affine_me_batch(const vvc_pel* org_base, const vvc_pel* ref_base, con
  * the device ignores the CHECK, does not fault, and the result is unspecified.
  * Loop control (host cfg): num_iter 4 or 1 (iNumIter); pick_list_by_cost (FASTINTERSEARCH_MODE1/2, :1062-1072); mvd_l1_zero: list 1 is fixed and list 0
  * searched -- the caller has done :1009-1023 and passes ref_idx[1] = bestBiPRefIdxL1, that record's mvp_idx = bestBiPMvpL1 and mv[1] = the candidate;
- * the device derives uiMotBits[1] by :1024-1036 and forms the list-1 prediction like any other.  Not served: imv != 0, weighted prediction, composite
- * reference.
+ * the device derives uiMotBits[1] by :1024-1036 and forms the list-1 prediction like any other.  Not served: weighted prediction, composite reference.
+ * AMVR passes (cfg.imv = cu.imv of every PU of the call, 1: integer-sample, 2: four-sample vectors; the encoder runs one pass per value,
+ * EncCu::xCheckRDCostInterIMV): with imvShift = imv << 1, xPatternSearch takes its vector bits with >> imvShift (:1913); xPatternSearchIntRefine
+ * (:2408-2500) replaces xPatternSearchFracDIF and the cost line: the integer vector and its 8 neighbours at 1 << imvShift quarter units, each against
+ * every candidate i < num_cand at test_i = testPos (1 << imvShift) + roundMV(mv - cand_i, imvShift) + cand_i, the full block at clipMv(test_i) >> 2 (no
+ * interpolation, no row sub-sampling), SATD when use_hadamard else SAD, (uint64)(0.5 d) + getCost(vector bits), strict '<' in the reference's visiting
+ * order; the step's vector, predictor index, predictor, bits (the vector bits counted twice, :2494-2497) and cost are as the refinement leaves them;
+ * xCheckBestMVP returns at once (:1543-1546), per step and in the closing calls (result.closing still reports that the condition of :1142-1163 held).
+ * Contract of an AMVR pass: every candidate vector of every (list, reference) is a multiple of 1 << imvShift quarter units (PU::fillMvpCand rounds
+ * them), and item.mv / ref[][].mv on entry are results of a pass with the same imv, hence aligned.  The reference's own CHECKs (:2437-2438: integer-sample
+ * differences to BOTH candidates) throw otherwise; an item that breaks this is outside the contract like one that fails the CHECK of xCheckBestMVP: no
+ * fault, result unspecified.  With num_cand == 1 candidate 1 is not read.  cfg.imv == 0 is the quarter-sample pass described above, bit for bit.
  * Reference planes: up to 16 luma planes of one stride; ref_planes[i] points to sample (0, 0) of picture i inside its padded allocation.  Readable
  * margin (a stated margin, as vvcgpu_affine_me_batch): vectors are clipped to the picture + 8 / - CTU - 8 samples, the block, the +-1 sample of the
  * refinement and the 8 taps reach further: max_cu + 12 readable samples around the picture on every side serve every search.
@@ -659,7 +669,7 @@ int vvcgpu_affine_me_batch(const vvc_pel* org_base, const vvc_pel* ref_base, con
  * ref_idx outside the list, a plane index outside [0, n_planes), num_cand outside 1..2, mvp_idx outside the candidates, org_stride <= 0) is skipped and
  * gets cost = ~0 (UINT64_MAX) with everything else zero (the sentinel of vvcgpu_affine_me_batch); its trace entries are zero.  n == 0 is a no-op;
  * null pointers (trace may be NULL), n < 0, geometry, clp_min > clp_max, lambda outside [0, 2^20), bipred_search_range outside 1..8, num_iter other
- * than 1 or 4, n_planes outside 1..16 and max_pu sides that are no served side return VVCGPU_E_ARG, a bit depth outside 8..10 VVCGPU_E_UNSUPPORTED,
+ * than 1 or 4, imv outside 0..2, n_planes outside 1..16 and max_pu sides that are no served side return VVCGPU_E_ARG, a bit depth outside 8..10 VVCGPU_E_UNSUPPORTED,
  * before any device work. */
 #define VVCGPU_BIPRED_ME_MAX_STEPS  16  /* num_iter 4 x at most 4 reference indices */
 #define VVCGPU_BIPRED_ME_MAX_REFS   4
@@ -703,7 +713,8 @@ typedef struct {                        /* host struct                          
   uint32_t mvp_idx_cost[3];     /* m_auiMVPIdxCost[0..2][AMVP_MAX_NUM_CANDS] */
   int32_t max_pu_w, max_pu_h;   /* the caller states that no item is wider / higher (0: 128): LDS per owner is sized by it, so that small PUs keep many
                                    owners per compute unit; an item beyond it is skipped */
-  int32_t reserved[2];
+  int32_t imv;                  /* cu.imv of every PU of the call: 0 (quarter-sample), 1 (integer-sample) or 2 (four-sample vectors) */
+  int32_t reserved;
 } vvcgpu_bipred_me_cfg;
 typedef struct {                        /* sizeof == 80 */
   int32_t  mv[2][2];      /* cMvBi[0..1] */
@@ -851,7 +862,16 @@ int vvcgpu_affine_bipred_me_batch(const vvc_pel* org_base, const vvcgpu_affine_b
  *   list-1 shortcut   with cfg.fast_me_gen_b_low_delay and cfg.list1_to_list0[ref] >= 0 a list-1 reference takes list 0's vector instead of searching
  *                     and corrects the cost as :909-921 do (uint64 subtraction, then addition), then xCheckBestMVP;
  *   :944-962          keep-if-strictly-better per list, and the "valid list 1" record (list-1 references with list1_to_list0 < 0).
- * Not served: imv != 0, weighted prediction, composite reference, MESEARCH_FULL and MESEARCH_SELECTIVE, affine.
+ * AMVR passes (cfg.imv = cu.imv of every PU of the call, 1: integer-sample, 2: four-sample vectors; the encoder runs one pass per value,
+ * EncCu::xCheckRDCostInterIMV): with imvShift = imv << 1, xTZSearch takes its vector cost with imvShift on both paths (vvcgpu_tz_cfg.imv_shift);
+ * xPatternSearchIntRefine (:2408-2500) replaces xPatternSearchFracDIF and :1795-1805, as described for vvcgpu_bipred_me_batch with weight 1.0 on the
+ * original; xCheckBestMVP returns at once (:1543-1546); the list-1 shortcut takes its vector bits with >> imvShift (:916).  mv is the refined vector,
+ * int_mv still the xTZSearch result, mvp_idx / bits / cost as the refinement leaves them, and the out-items carry that mvp_idx; bestBiP* still come from
+ * the template costs and the mvd_l1_zero preparation is unchanged.  The affine search is skipped by the encoder when imv != 0 (:969).  Contract of an
+ * AMVR pass: every candidate vector of every (list, reference) is a multiple of 1 << imvShift quarter units (PU::fillMvpCand rounds them); the
+ * reference's own CHECKs (:2437-2438) throw otherwise, and an item that breaks this is outside the contract: no fault, result unspecified.  With
+ * num_cand == 1 candidate 1 is not read.  cfg.imv == 0 is the quarter-sample pass described above, bit for bit.
+ * Not served: weighted prediction, composite reference, MESEARCH_FULL and MESEARCH_SELECTIVE, affine.
  * bipred_items_out (may be NULL): n complete vvcgpu_bipred_me_item records, exactly what vvcgpu_bipred_me_batch asks of its caller -- n_ref, planes,
  * cMvTemp, candidates and aaiMvpIdx per (list, reference), iRefIdx, cMv, uiCost, uiBits, mb_bits -- with the mvd_l1_zero preparation of :1009-1023 and
  * :1038 done when cfg.mvd_l1_zero (ref_idx[1] = bestBiPRefIdxL1, that record's mvp_idx = bestBiPMvpL1, its mv and mv[1] = that candidate), so that
@@ -868,7 +888,7 @@ int vvcgpu_affine_bipred_me_batch(const vvc_pel* org_base, const vvcgpu_affine_b
  * org_stride <= 0, tz_flags other than 0 or VVCGPU_TZ_EXTENDED, and for a (list, reference) of the slice num_cand outside 1..2 or flags outside 0..3) is
  * skipped: it reads no sample, its result has cost[0] = cost[1] = ~0 (UINT64_MAX) with everything else zero, its out-item is all zero.  n == 0 is a
  * no-op; null pointers (bipred_items_out may be NULL), n < 0, geometry, clp_min > clp_max, lambda outside [0, 2^20), n_planes outside 1..16, n_ref[0]
- * outside 1..4, n_ref[1] outside 0..4, a ref_plane outside [0, n_planes), a search_range outside 1..256, a list1_to_list0 outside [-1, n_ref[0]) and
+ * outside 1..4, n_ref[1] outside 0..4, a ref_plane outside [0, n_planes), a search_range outside 1..256, a list1_to_list0 outside [-1, n_ref[0]), imv outside 0..2 and
  * max_pu sides that are no served side return VVCGPU_E_ARG, a bit depth outside 8..10 VVCGPU_E_UNSUPPORTED, before any device work. */
 #define VVCGPU_UNIPRED_ME_MAX_REFS   4
 #define VVCGPU_UNIPRED_ME_MAX_PLANES 16
@@ -907,7 +927,8 @@ typedef struct {                        /* host struct                          
   int32_t use_hadamard;             /* getUseHADME() (no lossless CUs) */
   uint32_t mvp_idx_cost[3];         /* m_auiMVPIdxCost[0..2][AMVP_MAX_NUM_CANDS] */
   int32_t max_pu_w, max_pu_h;       /* as in vvcgpu_bipred_me_cfg: no item is wider / higher (0: 128); an item beyond it is skipped */
-  int32_t reserved[2];
+  int32_t imv;                      /* cu.imv of every PU of the call: 0 (quarter-sample), 1 (integer-sample) or 2 (four-sample vectors) */
+  int32_t reserved;
 } vvcgpu_unipred_me_cfg;
 typedef struct {                        /* one (list, reference index) of a result            sizeof == 48 */
   int32_t  mv[2];         /* cMvTemp[list][ref] (quarter units) */

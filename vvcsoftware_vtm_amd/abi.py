@@ -160,7 +160,7 @@ class BipredMeCfg(C.Structure):
                 ("pic_w", C.c_int32), ("pic_h", C.c_int32), ("max_cu_w", C.c_int32), ("max_cu_h", C.c_int32), ("bit_depth", C.c_int32),
                 ("clp_min", C.c_int32), ("clp_max", C.c_int32), ("num_iter", C.c_int32), ("pick_list_by_cost", C.c_int32), ("mvd_l1_zero", C.c_int32),
                 ("bipred_search_range", C.c_int32), ("clip_for_bipred_me", C.c_int32), ("use_hadamard", C.c_int32), ("mvp_idx_cost", C.c_uint32 * 3),
-                ("max_pu_w", C.c_int32), ("max_pu_h", C.c_int32), ("reserved", C.c_int32 * 2)]
+                ("max_pu_w", C.c_int32), ("max_pu_h", C.c_int32), ("imv", C.c_int32), ("reserved", C.c_int32)]
 
 
 # vvcgpu_unipred_me_batch: one (list, reference index) of an item, one PU, one (list, reference index) of a result, the result of a PU
@@ -183,7 +183,7 @@ class UnipredMeCfg(C.Structure):
                 ("clp_min", C.c_int32), ("clp_max", C.c_int32), ("n_ref", C.c_int32 * 2), ("ref_plane", (C.c_int32 * UNIPRED_ME_MAX_REFS) * 2),
                 ("search_range", (C.c_int32 * UNIPRED_ME_MAX_REFS) * 2), ("list1_to_list0", C.c_int32 * UNIPRED_ME_MAX_REFS),
                 ("fast_me_gen_b_low_delay", C.c_int32), ("mvd_l1_zero", C.c_int32), ("first_search_stop", C.c_int32), ("use_hadamard", C.c_int32),
-                ("mvp_idx_cost", C.c_uint32 * 3), ("max_pu_w", C.c_int32), ("max_pu_h", C.c_int32), ("reserved", C.c_int32 * 2)]
+                ("mvp_idx_cost", C.c_uint32 * 3), ("max_pu_w", C.c_int32), ("max_pu_h", C.c_int32), ("imv", C.c_int32), ("reserved", C.c_int32)]
 
 
 # vvcgpu_affine_bipred_me_batch: one (list, reference index) record, one PU, its result and one step of its trace

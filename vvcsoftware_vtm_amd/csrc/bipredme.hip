@@ -15,6 +15,9 @@
 // most), so that no sum crosses a wavefront; the arg-min keeps (cost, scan index) pairs, which is the strict '<' of the y-outer, x-inner scan.
 //  Control flow is uniform per owner: every lane computes the same scalar state; the per-(list, reference) state that is indexed dynamically
 // (cMvTemp, aaiMvpIdxBi, cMvPredBi) lives in LDS.
+// AMVR passes (cfg.imv = 1, 2; their own instantiation of the kernel, chosen by the host): xPatternSearch takes its vector bits with >> imvShift
+// (:1913), xPatternSearchIntRefine (:2408-2500; me_imv_refine of me_dev.h) with half weight on the key replaces the fractional refinement and its
+// cost, and no xCheckBestMVP runs (:1543-1546).
 #include "common.h"
 #include "frac_dev.h"
 #include "me_dev.h"
@@ -54,10 +57,11 @@ __device__ __forceinline__ void bp_key(const MePu& u, const vvcgpu_bipred_me_cfg
   });
 }
 
-// xPatternSearch over [left, left + nx) x [top, top + ny) (integer vectors); sw = the window (pitch swp), its sample (0, 0) = the block at (left, top)
+// xPatternSearch over [left, left + nx) x [top, top + ny) (integer vectors), the vector bits taken with >> sh (imvShift, :1913); sw = the window
+// (pitch swp), its sample (0, 0) = the block at (left, top)
 template <int NT>
 __device__ __forceinline__ void bp_int_search(const MePu& u, const BpLds& L, const short* sw, int swp, int left, int top, int nx, int ny, double lambda,
-                                              int predH, int predV, int tid, int& bx, int& by)
+                                              int predH, int predV, int sh, int tid, int& bx, int& by)
 {
   const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), nw = NT >> 6;
   const int hs = u.h >> u.subShift, n = u.w * hs;                         // sampled pixels: a power of two
@@ -81,7 +85,7 @@ __device__ __forceinline__ void bp_int_search(const MePu& u, const BpLds& L, con
     for (int o = 1; o < S; o <<= 1) sum += __shfl_xor(sum, o);
     if (act)
     {
-      const unsigned long long cost = (unsigned long long)(sum << u.subShift) + pu_getcost(lambda, me_mvbits(predH, predV, 2, left + i, top + j));
+      const unsigned long long cost = (unsigned long long)(sum << u.subShift) + pu_getcost(lambda, me_mvbits_imv(predH, predV, 2, sh, left + i, top + j));
       if (cost < bestC) { bestC = cost; bestP = (unsigned)p; }
     }
   }
@@ -110,7 +114,8 @@ __device__ __forceinline__ void bp_int_search(const MePu& u, const BpLds& L, con
   bx = left + (int)bestP - j * nx; by = top + j;
 }
 
-template <int NT>
+// IMV: an AMVR pass (cfg.imv != 0): xPatternSearchIntRefine for the fractional step, no xCheckBestMVP
+template <int NT, bool IMV>
 __device__ __forceinline__ void bp_search(const vvcgpu_bipred_me_item* __restrict__ itp, const vvcgpu_bipred_me_cfg& c, const Pel* __restrict__ orgBase,
                                           const BpLds& L, vvcgpu_bipred_me_result* res, vvcgpu_bipred_me_step* trace, int tid)
 {
@@ -119,7 +124,7 @@ __device__ __forceinline__ void bp_search(const vvcgpu_bipred_me_item* __restric
   u.org = orgBase + itp->org_off; u.os = itp->org_stride;
   u.horMax = (c.pic_w + 8 - u.posX - 1) << 2; u.horMin = (-c.max_cu_w - 8 - u.posX + 1) << 2;
   u.verMax = (c.pic_h + 8 - u.posY - 1) << 2; u.verMin = (-c.max_cu_h - 8 - u.posY + 1) << 2;
-  const int w = u.w, h = u.h, R = c.bipred_search_range;
+  const int w = u.w, h = u.h, R = c.bipred_search_range, sh = IMV ? c.imv << 1 : 0;
   const int nRef[2] = { itp->n_ref[0], itp->n_ref[1] };
   const unsigned long long uniCost[2] = { itp->cost[0], itp->cost[1] };
   const unsigned mbBits2 = itp->mb_bits[2];
@@ -173,23 +178,30 @@ __device__ __forceinline__ void bp_search(const vvcgpu_bipred_me_item* __restric
       }
       owner_sync<NT>();
       int ix, iy;
-      bp_int_search<NT>(u, L, L.work, swp, left, top, nx, ny, c.lambda, predX, predY, tid, ix, iy);
+      bp_int_search<NT>(u, L, L.work, swp, left, top, nx, ny, c.lambda, predX, predY, sh, tid, ix, iy);
       owner_sync<NT>();
-      // xPatternSearchFracDIF around (ix, iy)
-      const int wp = w + 10;
+      int mvX, mvY;
+      unsigned long long costT;
+      if (IMV)                                                            // xPatternSearchIntRefine around (ix, iy), half weight on the key
+        me_imv_refine<NT>(u, L.F.org, c.ref_planes[a.plane], c.ref_stride, c.use_hadamard, 0.5, c.lambda, sh, a.mv_cand, a.num_cand, c.mvp_idx_cost,
+                          reinterpret_cast<unsigned long long*>(L.work), ix, iy, mvX, mvY, predX, predY, mvpIdx, bitsT, costT, tid);
+      else                                                                // xPatternSearchFracDIF around (ix, iy)
       {
-        const Pel* r0 = ref + (ptrdiff_t)(iy - 4) * c.ref_stride + ix - 4;
-        for (int i = tid; i < (w + 9) * (h + 9); i += NT) { const int y = i / (w + 9), x = i - y * (w + 9); L.F.win[y * wp + x] = r0[(ptrdiff_t)y * c.ref_stride + x]; }
+        const int wp = w + 10;
+        {
+          const Pel* r0 = ref + (ptrdiff_t)(iy - 4) * c.ref_stride + ix - 4;
+          for (int i = tid; i < (w + 9) * (h + 9); i += NT) { const int y = i / (w + 9), x = i - y * (w + 9); L.F.win[y * wp + x] = r0[(ptrdiff_t)y * c.ref_stride + x]; }
+        }
+        vvcgpu_mvcost mc;
+        mc.lambda = c.lambda; mc.pred_hor = predX; mc.pred_ver = predY; mc.cost_scale = 0; mc.imv_shift = 0;
+        frac_refine_pu(L.F, w, h, wp, c.bit_depth, c.clp_min, c.clp_max, c.use_hadamard, mc, ix, iy, true, tid, NT, L.fres);
+        owner_sync<NT>();
+        mvX = (ix << 2) + (L.fres->half_x << 1) + L.fres->qter_x; mvY = (iy << 2) + (L.fres->half_y << 1) + L.fres->qter_y;
+        const unsigned mvBits = me_mvbits(predX, predY, 0, mvX, mvY);
+        bitsT += mvBits;
+        costT = (unsigned long long)(floor(0.5 * ((double)L.fres->cost - (double)pu_getcost(c.lambda, mvBits))) + (double)pu_getcost(c.lambda, bitsT));
+        me_check_best_mvp(a.mv_cand, a.num_cand, c.mvp_idx_cost, c.lambda, mvX, mvY, predX, predY, mvpIdx, bitsT, costT);
       }
-      vvcgpu_mvcost mc;
-      mc.lambda = c.lambda; mc.pred_hor = predX; mc.pred_ver = predY; mc.cost_scale = 0; mc.imv_shift = 0;
-      frac_refine_pu(L.F, w, h, wp, c.bit_depth, c.clp_min, c.clp_max, c.use_hadamard, mc, ix, iy, true, tid, NT, L.fres);
-      owner_sync<NT>();
-      const int mvX = (ix << 2) + (L.fres->half_x << 1) + L.fres->qter_x, mvY = (iy << 2) + (L.fres->half_y << 1) + L.fres->qter_y;
-      const unsigned mvBits = me_mvbits(predX, predY, 0, mvX, mvY);
-      bitsT += mvBits;
-      unsigned long long costT = (unsigned long long)(floor(0.5 * ((double)L.fres->cost - (double)pu_getcost(c.lambda, mvBits))) + (double)pu_getcost(c.lambda, bitsT));
-      me_check_best_mvp(a.mv_cand, a.num_cand, c.mvp_idx_cost, c.lambda, mvX, mvY, predX, predY, mvpIdx, bitsT, costT);
       owner_sync<NT>();                                                   // every lane has read st and fres
       if (tid == 0) { s[0] = mvX; s[1] = mvY; s[2] = mvpIdx; s[3] = predX; s[4] = predY; }
       const bool accepted = costT < costBi;
@@ -217,6 +229,7 @@ __device__ __forceinline__ void bp_search(const vvcgpu_bipred_me_item* __restric
       {
         closing = 1;
         // amvp[eRefPicList]: list 0's is the set just copied for iRefIdxBi[0]; list 1's is, at the first check, the one the loop above copied last
+        if (!IMV)                                                         // an AMVR pass: xCheckBestMVP returns at once (:1543-1546)
         {
           const vvcgpu_bipred_me_ref& a = list == 0 ? itp->ref[0][refBi[0]] : itp->ref[1][nRef[1] - 1];
           int* s = L.st + refBi[0] * BP_ST;
@@ -226,7 +239,7 @@ __device__ __forceinline__ void bp_search(const vvcgpu_bipred_me_item* __restric
           if (tid == 0) { s[2] = mvpIdx; s[3] = predX; s[4] = predY; }
           owner_sync<NT>();
         }
-        if (!c.mvd_l1_zero)
+        if (!IMV && !c.mvd_l1_zero)
         {
           const vvcgpu_bipred_me_ref& a = list == 0 ? itp->ref[0][refBi[0]] : itp->ref[1][refBi[1]];
           int* s = L.st + (4 + refBi[1]) * BP_ST;
@@ -285,6 +298,7 @@ __device__ __forceinline__ BpLds bp_lds(unsigned char* base, int w, int h)
   return L;
 }
 
+template <bool IMV>
 __global__ __launch_bounds__(256) void bipred_me_kernel(const Pel* __restrict__ orgBase, const vvcgpu_bipred_me_item* __restrict__ items, int n,
                                                         const vvcgpu_bipred_me_cfg c, int waveBytes, vvcgpu_bipred_me_result* __restrict__ results,
                                                         vvcgpu_bipred_me_step* __restrict__ trace)
@@ -302,8 +316,8 @@ __global__ __launch_bounds__(256) void bipred_me_kernel(const Pel* __restrict__ 
     return;
   }
   if ((it->w * it->h <= BP_WAVE_MAX) != o.waveOwner) return;             // the other kind of owner serves this item
-  if (o.waveOwner) bp_search<64>(it, c, orgBase, bp_lds(smem + (size_t)wave * waveBytes, it->w, it->h), results + b, tr, lane);
-  else bp_search<256>(it, c, orgBase, bp_lds(smem, it->w, it->h), results + b, tr, tid);
+  if (o.waveOwner) bp_search<64, IMV>(it, c, orgBase, bp_lds(smem + (size_t)wave * waveBytes, it->w, it->h), results + b, tr, lane);
+  else bp_search<256, IMV>(it, c, orgBase, bp_lds(smem, it->w, it->h), results + b, tr, tid);
 }
 
 // the launch's LDS (cfg checked, max_pu set)
@@ -324,10 +338,12 @@ extern "C" int vvcgpu_bipred_me_batch(const vvc_pel* org_base, const vvcgpu_bipr
   if (const int rc = pu_check_frame("bipred_me_batch", c, VVCGPU_BIPRED_ME_MAX_PLANES)) return rc;
   VVC_CHECK_ARG(c.bipred_search_range >= 1 && c.bipred_search_range <= 8, "bipred_me_batch: bipred_search_range %d outside 1..8", c.bipred_search_range);
   VVC_CHECK_ARG(c.num_iter == 1 || c.num_iter == 4, "bipred_me_batch: num_iter %d (4 or 1)", c.num_iter);
+  if (const int rc = pu_check_imv("bipred_me_batch", c)) return rc;
   if (const int rc = pu_check_tail("bipred_me_batch", c, n, 1 << 28, pu_side_pow2_ok, "4, 8, .. 128")) return rc;
   const PuOwnerLds L = bp_owner_lds(c);
-  VVC_HIP(vvc_allow_lds(bipred_me_kernel, L.lds));
-  hipLaunchKernelGGL(bipred_me_kernel, dim3(pu_owner_grid(n, true)), dim3(256), L.lds, (hipStream_t)stream, org_base, items, n, c, L.waveBytes, results, trace);
+  const auto kernel = c.imv ? bipred_me_kernel<true> : bipred_me_kernel<false>;
+  VVC_HIP(vvc_allow_lds(kernel, L.lds));
+  hipLaunchKernelGGL(kernel, dim3(pu_owner_grid(n, true)), dim3(256), L.lds, (hipStream_t)stream, org_base, items, n, c, L.waveBytes, results, trace);
   VVC_LAUNCH_CHECK();
   return VVCGPU_OK;
 }

@@ -26,6 +26,13 @@ template <class Cfg> int pu_check_frame(const char* name, const Cfg& c, int maxP
   return VVCGPU_OK;
 }
 
+// cfg.imv of the translational entries: cu.imv of the pass
+template <class Cfg> int pu_check_imv(const char* name, const Cfg& c)
+{
+  VVC_CHECK_ARG(c.imv >= 0 && c.imv <= 2, "%s: imv %d outside 0..2", name, c.imv);
+  return VVCGPU_OK;
+}
+
 // the reference lists of the uni-predictive entries; perRef(l, r): what else the entry checks of (list, reference index), in its place in the order
 template <class Cfg, class PerRef> int pu_check_lists(const char* name, const Cfg& c, int maxRefs, PerRef perRef)
 {

@@ -14,6 +14,9 @@
 // work area) and xCheckBestMVP, and writes its record into the PU's result.  A list-1 reference that takes list 0's vector only chooses its
 // predictor.  Launch 2, one lane per PU, walks the records in the reference's order: the list-1 shortcut, bestBiP*, keep-if-strictly-better, the
 // valid-list-1 record, the out-item for vvcgpu_bipred_me_batch, and everything a skipped item gets.  Control flow is uniform per owner.
+// AMVR passes (cfg.imv = 1, 2; its own instantiation of launch 1, chosen by the host): imvShift = imv << 1 in the TZ cost, xPatternSearchIntRefine
+// (:2408-2500; me_imv_refine of me_dev.h) for the fractional refinement and its cost, no xCheckBestMVP (:1543-1546), the shortcut's vector bits with
+// >> imvShift (:916).
 #include "common.h"
 #include "frac_dev.h"
 #include "me_dev.h"
@@ -70,7 +73,7 @@ __device__ __forceinline__ bool up_item_ok(const vvcgpu_unipred_me_item& it, con
 __device__ __forceinline__ bool up_shortcut(const vvcgpu_unipred_me_cfg& c, int list, int r) { return list == 1 && c.fast_me_gen_b_low_delay && c.list1_to_list0[r] >= 0; }
 
 // one (list, reference index) search of a PU by NT lanes
-template <int NT>
+template <int NT, bool IMV>
 __device__ __forceinline__ void up_search(const vvcgpu_unipred_me_item* __restrict__ itp, const vvcgpu_unipred_me_cfg& c, const Pel* __restrict__ orgBase,
                                           unsigned char* base, int list, int r, vvcgpu_unipred_me_search* out, int tid)
 {
@@ -123,7 +126,7 @@ __device__ __forceinline__ void up_search(const vvcgpu_unipred_me_item* __restri
     s.w = w; s.h = h; s.subShift = u.subShift; s.refX = u.posX; s.refY = u.posY;
     s.rx0 = -(c.max_cu_w + 14); s.ry0 = -(c.max_cu_h + 14); s.rx1 = c.pic_w + c.max_cu_w + 14 - w; s.ry1 = c.pic_h + c.max_cu_h + 14 - h;
     s.horMax = u.horMax; s.horMin = u.horMin; s.verMax = u.verMax; s.verMin = u.verMin;
-    s.lambda = c.lambda; s.predHor = predX; s.predVer = predY; s.costScale = 2; s.imvShift = 0;
+    s.lambda = c.lambda; s.predHor = predX; s.predVer = predY; s.costScale = 2; s.imvShift = IMV ? c.imv << 1 : 0;
     s.tl = tid;
     int LX = 1; while (4 * LX < w) LX <<= 1;
     s.LX = LX;
@@ -140,21 +143,28 @@ __device__ __forceinline__ void up_search(const vvcgpu_unipred_me_item* __restri
   }
   owner_sync<NT>();                                                      // the packed original's last readers are done
 
-  // xPatternSearchFracDIF around (ix, iy)
-  const int wp = w + 10;
+  int mvX, mvY;
+  unsigned long long cost;
+  if (IMV)                                                               // xPatternSearchIntRefine around (ix, iy); no xCheckBestMVP (:1543-1546)
+    me_imv_refine<NT>(u, L.F.org, plane, c.ref_stride, c.use_hadamard, 1.0, c.lambda, c.imv << 1, a.mv_cand, a.num_cand, c.mvp_idx_cost,
+                      reinterpret_cast<unsigned long long*>(L.work), ix, iy, mvX, mvY, predX, predY, mvpIdx, bits, cost, tid);
+  else                                                                   // xPatternSearchFracDIF around (ix, iy)
   {
-    const Pel* r0 = plane + (ptrdiff_t)(u.posY + iy - 4) * c.ref_stride + u.posX + ix - 4;
-    for (int i = tid; i < (w + 9) * (h + 9); i += NT) { const int y = i / (w + 9), x = i - y * (w + 9); L.F.win[y * wp + x] = r0[(ptrdiff_t)y * c.ref_stride + x]; }
+    const int wp = w + 10;
+    {
+      const Pel* r0 = plane + (ptrdiff_t)(u.posY + iy - 4) * c.ref_stride + u.posX + ix - 4;
+      for (int i = tid; i < (w + 9) * (h + 9); i += NT) { const int y = i / (w + 9), x = i - y * (w + 9); L.F.win[y * wp + x] = r0[(ptrdiff_t)y * c.ref_stride + x]; }
+    }
+    vvcgpu_mvcost mc;
+    mc.lambda = c.lambda; mc.pred_hor = predX; mc.pred_ver = predY; mc.cost_scale = 0; mc.imv_shift = 0;
+    frac_refine_pu(L.F, w, h, wp, c.bit_depth, c.clp_min, c.clp_max, c.use_hadamard, mc, ix, iy, true, tid, NT, L.fres);
+    owner_sync<NT>();
+    mvX = (ix << 2) + (L.fres->half_x << 1) + L.fres->qter_x; mvY = (iy << 2) + (L.fres->half_y << 1) + L.fres->qter_y;
+    const unsigned mvBits = me_mvbits(predX, predY, 0, mvX, mvY);
+    bits += mvBits;
+    cost = (unsigned long long)(floor(1.0 * ((double)L.fres->cost - (double)pu_getcost(c.lambda, mvBits))) + (double)pu_getcost(c.lambda, bits));
+    me_check_best_mvp(a.mv_cand, a.num_cand, c.mvp_idx_cost, c.lambda, mvX, mvY, predX, predY, mvpIdx, bits, cost);
   }
-  vvcgpu_mvcost mc;
-  mc.lambda = c.lambda; mc.pred_hor = predX; mc.pred_ver = predY; mc.cost_scale = 0; mc.imv_shift = 0;
-  frac_refine_pu(L.F, w, h, wp, c.bit_depth, c.clp_min, c.clp_max, c.use_hadamard, mc, ix, iy, true, tid, NT, L.fres);
-  owner_sync<NT>();
-  const int mvX = (ix << 2) + (L.fres->half_x << 1) + L.fres->qter_x, mvY = (iy << 2) + (L.fres->half_y << 1) + L.fres->qter_y;
-  const unsigned mvBits = me_mvbits(predX, predY, 0, mvX, mvY);
-  bits += mvBits;
-  unsigned long long cost = (unsigned long long)(floor(1.0 * ((double)L.fres->cost - (double)pu_getcost(c.lambda, mvBits))) + (double)pu_getcost(c.lambda, bits));
-  me_check_best_mvp(a.mv_cand, a.num_cand, c.mvp_idx_cost, c.lambda, mvX, mvY, predX, predY, mvpIdx, bits, cost);
   if (tid == 0)
   {
     vvcgpu_unipred_me_search o;
@@ -164,6 +174,8 @@ __device__ __forceinline__ void up_search(const vvcgpu_unipred_me_item* __restri
   }
 }
 
+// IMV: an AMVR pass (cfg.imv != 0); its own instantiation, so that the quarter-sample pass keeps its registers
+template <bool IMV>
 __global__ __launch_bounds__(256) void unipred_search_kernel(const Pel* __restrict__ orgBase, const vvcgpu_unipred_me_item* __restrict__ items, int n,
                                                              const vvcgpu_unipred_me_cfg c, int waveBytes, vvcgpu_unipred_me_result* __restrict__ results)
 {
@@ -176,8 +188,8 @@ __global__ __launch_bounds__(256) void unipred_search_kernel(const Pel* __restri
   const vvcgpu_unipred_me_item* it = items + b;
   if (!up_item_ok(*it, c)) return;                                       // the decision step writes the sentinel
   if ((it->w * it->h <= UP_WAVE_MAX) != o.waveOwner) return;               // the other kind of owner serves this item
-  if (o.waveOwner) up_search<64>(it, c, orgBase, smem + (size_t)wave * waveBytes, list, r, &results[b].s[list][r], lane);
-  else up_search<256>(it, c, orgBase, smem, list, r, &results[b].s[list][r], tid);
+  if (o.waveOwner) up_search<64, IMV>(it, c, orgBase, smem + (size_t)wave * waveBytes, list, r, &results[b].s[list][r], lane);
+  else up_search<256, IMV>(it, c, orgBase, smem, list, r, &results[b].s[list][r], tid);
 }
 
 // per PU: the records of its searches in the reference's order (:877-964) -> the result and the out-item
@@ -216,9 +228,9 @@ __global__ __launch_bounds__(256) void unipred_decide_kernel(const vvcgpu_unipre
         s.mv[0] = R->s[0][k].mv[0]; s.mv[1] = R->s[0][k].mv[1];
         unsigned long long cost = costL0[k];
         cost -= pu_getcost(c.lambda, bitsL0[k]);
-        unsigned bits = s.bits + me_mvbits(predX, predY, 0, s.mv[0], s.mv[1]);
+        unsigned bits = s.bits + me_mvbits_imv(predX, predY, 0, c.imv << 1, s.mv[0], s.mv[1]);
         cost += pu_getcost(c.lambda, bits);
-        me_check_best_mvp(a.mv_cand, a.num_cand, c.mvp_idx_cost, c.lambda, s.mv[0], s.mv[1], predX, predY, mvpIdx, bits, cost);
+        if (c.imv == 0) me_check_best_mvp(a.mv_cand, a.num_cand, c.mvp_idx_cost, c.lambda, s.mv[0], s.mv[1], predX, predY, mvpIdx, bits, cost);
         s.mvp_idx = mvpIdx; s.bits = bits; s.cost = cost;
         R->s[list][r] = s;
       }
@@ -276,12 +288,14 @@ extern "C" int vvcgpu_unipred_me_batch(const vvc_pel* org_base, const vvcgpu_uni
     return VVCGPU_OK;
   };
   if (const int rc = pu_check_lists("unipred_me_batch", c, VVCGPU_UNIPRED_ME_MAX_REFS, searchRangeOk)) return rc;
+  if (const int rc = pu_check_imv("unipred_me_batch", c)) return rc;
   if (const int rc = pu_check_tail("unipred_me_batch", c, n, 1 << 27, pu_side_pow2_ok, "4, 8, .. 128")) return rc;
   const PuOwnerLds L = up_owner_lds(c);
   const int total = n * (c.n_ref[0] + c.n_ref[1]);
   hipStream_t st = (hipStream_t)stream;
-  VVC_HIP(vvc_allow_lds(unipred_search_kernel, L.lds));
-  hipLaunchKernelGGL(unipred_search_kernel, dim3(pu_owner_grid(total, L.groupBytes != 0)), dim3(256), L.lds, st, org_base, items, n, c, L.waveBytes, results);
+  const auto search = c.imv ? unipred_search_kernel<true> : unipred_search_kernel<false>;
+  VVC_HIP(vvc_allow_lds(search, L.lds));
+  hipLaunchKernelGGL(search, dim3(pu_owner_grid(total, L.groupBytes != 0)), dim3(256), L.lds, st, org_base, items, n, c, L.waveBytes, results);
   VVC_LAUNCH_CHECK();
   hipLaunchKernelGGL(unipred_decide_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, items, n, c, results, bipred_items_out);
   VVC_LAUNCH_CHECK();

@@ -554,12 +554,12 @@ def _unipred_refs(cfg, n_ref, ref_plane, list1_to_list0):
 
 
 def bipred_me_cfg(lambda_, ref_planes, ref_origin, pic_w, pic_h, bit_depth=10, clp=(0, 1023), num_iter=4, pick_list_by_cost=False, mvd_l1_zero=False,
-                  search_range=4, clip_key=True, use_hadamard=True, mvp_idx_cost=(1, 1, 0), max_cu=128, max_pu=(0, 0)):
-    """vvcgpu_bipred_me_cfg of one slice.  ref_planes: the PADDED reference luma planes (2-D int16 CUDA tensors of one stride; keep them alive while
+                  search_range=4, clip_key=True, use_hadamard=True, mvp_idx_cost=(1, 1, 0), max_cu=128, max_pu=(0, 0), imv=0):
+    """vvcgpu_bipred_me_cfg of one slice (imv: cu.imv of the pass, 0..2).  ref_planes: the PADDED reference luma planes (2-D int16 CUDA tensors of one stride; keep them alive while
     calls that use the cfg run); ref_origin = (x, y) of picture sample (0, 0) inside each of them"""
     cfg = _pu_frame(BipredMeCfg(), lambda_, ref_planes, ref_origin, pic_w, pic_h, bit_depth, clp, max_cu, mvp_idx_cost, max_pu)
     cfg.num_iter, cfg.pick_list_by_cost, cfg.mvd_l1_zero = num_iter, int(pick_list_by_cost), int(mvd_l1_zero)
-    cfg.bipred_search_range, cfg.clip_for_bipred_me, cfg.use_hadamard = search_range, int(clip_key), int(use_hadamard)
+    cfg.bipred_search_range, cfg.clip_for_bipred_me, cfg.use_hadamard, cfg.imv = search_range, int(clip_key), int(use_hadamard), imv
     return cfg
 
 
@@ -576,8 +576,8 @@ def bipred_me_batch(org_base, items_dev, n, cfg, want_trace=True):
 
 def unipred_me_cfg(lambda_, ref_planes, ref_origin, pic_w, pic_h, n_ref, ref_plane, search_range, bit_depth=10, clp=(0, 1023), list1_to_list0=(-1, -1, -1, -1),
                    fast_me_gen_b_low_delay=False, mvd_l1_zero=False, first_search_stop=False, use_hadamard=True, mvp_idx_cost=(1, 1, 0), max_cu=128,
-                   max_pu=(0, 0)):
-    """vvcgpu_unipred_me_cfg of one slice.  ref_planes: the PADDED reference luma planes (2-D int16 CUDA tensors of one stride; keep them alive while
+                   max_pu=(0, 0), imv=0):
+    """vvcgpu_unipred_me_cfg of one slice (imv: cu.imv of the pass, 0..2).  ref_planes: the PADDED reference luma planes (2-D int16 CUDA tensors of one stride; keep them alive while
     calls that use the cfg run); ref_origin = (x, y) of picture sample (0, 0) inside each of them; n_ref = (list 0, list 1) reference counts, ref_plane
     and search_range = per list the plane index / m_aaiAdaptSR of every reference index"""
     cfg = _pu_frame(UnipredMeCfg(), lambda_, ref_planes, ref_origin, pic_w, pic_h, bit_depth, clp, max_cu, mvp_idx_cost, max_pu)
@@ -586,7 +586,7 @@ def unipred_me_cfg(lambda_, ref_planes, ref_origin, pic_w, pic_h, n_ref, ref_pla
         for r in range(min(n_ref[l], UNIPRED_ME_MAX_REFS)):
             cfg.search_range[l][r] = search_range[l][r]
     cfg.fast_me_gen_b_low_delay, cfg.mvd_l1_zero = int(fast_me_gen_b_low_delay), int(mvd_l1_zero)
-    cfg.first_search_stop, cfg.use_hadamard = int(first_search_stop), int(use_hadamard)
+    cfg.first_search_stop, cfg.use_hadamard, cfg.imv = int(first_search_stop), int(use_hadamard), imv
     return cfg
 
 
