@@ -1064,6 +1064,60 @@ typedef struct {                        /* one PU                               
 int vvcgpu_affine_unipred_me_batch(const vvc_pel* org_base, const vvcgpu_affine_unipred_item* items, int n, const vvcgpu_affine_unipred_cfg* cfg_host,
                                    vvcgpu_affine_unipred_result* results, vvcgpu_affine_bipred_item* bipred_items_out, void* stream);
 
+/* ---- the merge candidate pass of a CU, on the device  (EncCu::xCheckRDCostMerge2Nx2N, first pass, EncoderLib/EncCu.cpp:1537-1612: per merge candidate
+ *          InterPrediction::motionCompensation of all components into acMergeBuffer[] -- xSubPuMC, CommonLib/InterPrediction.cpp:265-345, for an ATMVP
+ *          candidate --, the Hadamard (lossless: SAD) distFunc of the luma prediction, cost = (double)sad + (double)bits * sqrtLambda, updateCandList
+ *          (CommonLib/UnitTools.h:190-223) into RdModeList and the MRG_FAST_RATIO cut) -----------------------------------------------------------
+ * One call serves the pass for n_pu independent PUs: two launches on the caller's stream, no host synchronisation inside, every output bit for bit
+ * the reference's, the doubles included.  It is built from the two descriptor types of vvcgpu_mc_batch and vvcgpu_dist_batch and plain index arrays.
+ * Every array is device memory; descriptor arrays are 16-byte aligned.
+ *   pu_cand_first[n_pu + 1]   PU p owns candidates pu_cand_first[p] .. pu_cand_first[p + 1] - 1 in merge order: candidate k of the PU is uiMergeCand = k;
+ *                             their number is mergeCtx.numValidMergeCand, 1..7
+ *   cand_dist[n_comp c + comp]  the DistParam / getDistPart pair of candidate c and component comp (0 Y, 1 Cb, 2 Cr); n_comp is 1 (luma only) or 3.
+ *                             org_off / org_stride address the original block in org_base, cur_off / cur_stride the candidate's prediction block of the
+ *                             component in pred_base (the caller's layout of m_acMergeBuffer[c]); w, h its size, sub_shift 0.  Luma sides are 4, 8, .. 128;
+ *                             a chroma block is no larger than the luma block; cur_stride >= w
+ *   cand_mc_first[n_cand + 1]   candidate c is predicted by mc_descs[cand_mc_first[c] .. cand_mc_first[c + 1] - 1]: descriptors as vvcgpu_mc_batch takes
+ *                             them (bi 0 or 1, the vector clipped and split into integer offset and phase by the caller -- 1/16 luma, 1/32 chroma, so
+ *                             high-precision merge vectors are served; a list-1-only candidate is passed as ref0), EXCEPT that `reserved` is the component
+ *                             (0, 1, 2) and dst_off / dst_stride address pred_base.  A MRG_TYPE_DEFAULT_N candidate is one descriptor per component, an
+ *                             ATMVP candidate (MRG_TYPE_SUBPU_ATMVP) one per sub-block (1 << getSubPuMvpSubblkLog2Size() luma samples: chroma blocks go
+ *                             down to 2x2) per component; xSubPuMC joins neighbours of equal motion before it predicts, which changes no sample, so the
+ *                             caller need not.  Within a candidate every descriptor's destination rectangle lies inside the cur block of its component,
+ *                             with dst_stride == cur_stride, and together the rectangles of a component tile that block
+ *   max_num_merge_cand        slice.getMaxNumMergeCand(), 1..7;  use_hadamard: !lossless (:1564), 0 = full SAD without row sub-sampling;
+ *   sqrt_lambda               getMotionLambda(), in [0, 2^20)
+ *   pred_base                 may be NULL: a cost-only call, nothing is written and the offsets still place the blocks;  sse_out may be NULL
+ * Outputs:
+ *   dist_out[c]               what vvcgpu_mc_batch of the luma run followed by vvcgpu_dist_batch(kind = use_hadamard ? 1 : 0) on cand_dist[n_comp c] returns
+ *   sse_out[n_comp c + comp]  what vvcgpu_dist_batch(kind 2) returns for the component: the DF_SSE of the no-residual leg of the second pass
+ *                             (InterSearch.cpp:4762-4790); the chroma distortion weight stays on the host, as for vvcgpu_dist_batch
+ *   cost_out[c]               (double)dist + (double)bits * sqrt_lambda with bits = k + 1 - (k == max_num_merge_cand - 1) (:1594-1599): a product, then
+ *                             a sum, no fused multiply-add
+ *   rd_list_out[8 p]          uiNumMrgSATDCand after :1605-1612;  rd_list_out[8 p + 1 + i] = RdModeList[i] for i < min(NUM_MRG_SATD_CAND, count), -1
+ *                             beyond (entries 5..7 are always -1).  updateCandList is followed literally with uiFastCandNum = 4 (strict '<': of two equal
+ *                             costs the earlier candidate stays ahead).  With fewer than four candidates the reference's pruning loop indexes its cost
+ *                             list beyond its size; the entry stops at the list's size there: uiNumMrgSATDCand starts from min(4, count)
+ *   the predictions           of every component of every candidate, in pred_base (unless NULL): the samples vvcgpu_mc_batch writes for the descriptors
+ * Reads of reference samples are exactly those vvcgpu_mc_batch states.
+ * Descriptors cannot be validated on the host.  A candidate is SKIPPED -- it writes no sample, its dist_out and sse_out are ~0 -- if its run is empty or
+ * leaves [0, n_mc); if one of its descriptors has w or h outside 1..128, bi outside 0..1, `reserved` outside [0, n_comp) or a phase outside the filter
+ * table (0..15 luma, 0..31 chroma); if a destination rectangle leaves its cur block (or dst_stride differs from cur_stride); if its luma block has a
+ * side outside {4, 8, .. 128}, or a chroma block is empty, larger than the luma block or wider than its cur_stride.  A PU is skipped -- its rd_list_out
+ * row is all -1 -- if it has a skipped candidate (then the cost_out of all its candidates is +infinity), fewer than 1 or more than 7 candidates, or a
+ * candidate range that leaves [0, n_cand) (then no cost_out is written for it).  A PU outside the contract is never a fault.
+ * VVCGPU_E_ARG before any device work: a null pointer (ref1_base, pred_base and sse_out may be null), a negative count, n_comp outside {1, 3},
+ * max_num_merge_cand outside 1..7, clp_min > clp_max, sqrt_lambda negative, not finite or >= 2^20, a descriptor array that is not 16-byte aligned;
+ * VVCGPU_E_UNSUPPORTED: a bit depth outside 8..10.  n_pu == 0 is a no-op.
+ * Not served, i.e. the caller's: PU::getInterMergeCandidates, clipMv, xCheckIdenticalMotion (a bi candidate of identical motion is handed over as a
+ * uni-predictive one), the bestIsSkip gate and the second pass; weighted prediction; the single affine merge candidate, which has no SATD pass in
+ * this reference (:1722-1803).                                                                                                                      */
+int vvcgpu_merge_cand_batch(const vvc_pel* ref0_base, const vvc_pel* ref1_base, const vvc_pel* org_base, vvc_pel* pred_base,
+                            const vvcgpu_mc_desc* mc_descs, int n_mc, const int32_t* cand_mc_first,
+                            const vvcgpu_dist_desc* cand_dist, int n_cand, int n_comp, const int32_t* pu_cand_first, int n_pu,
+                            int max_num_merge_cand, int use_hadamard, double sqrt_lambda, int bit_depth, int clp_min, int clp_max,
+                            uint64_t* dist_out, uint64_t* sse_out, double* cost_out, int32_t* rd_list_out, void* stream);
+
 /* ---- N2 ("next" row): integer-sample TZ search of whole PUs, on the device  (InterSearch::xTZSearch,
  *          EncoderLib/InterSearch.cpp:1971-2252, with xTZSearchHelp :249-343, xTZ2PointSearch :349-374,
  *          xTZ8PointDiamondSearch :431-632, xSetSearchRange :1820-1883, clipMv CommonLib/Mv.cpp:64-80) -----------------

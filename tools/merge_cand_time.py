@@ -1,0 +1,158 @@
+#!/usr/bin/env python3
+"""The merge candidate pass (first pass of EncCu::xCheckRDCostMerge2Nx2N, EncCu.cpp:1537-1612), seven candidates per PU in all three components of a
+4:2:0 10-bit 3840x2160 picture, four reference pictures, one of the seven an ATMVP candidate with 4x4 sub-blocks (where the PU is at least 8x8):
+  4K      every 16x16 PU of the picture (32 400 PUs, 226 800 candidates);
+  mix     about 8 000 PUs at random positions whose shapes follow the committed call trace (tests/golden/trace_ragop16_416x240_10b_q32.npz: the
+          shapes of its pelop calls, sides 4..128, powers of two).
+Candidates: uni-predictive from either list or bi-predictive, quarter- or 1/16-sample vectors around the motion the original was made with.
+  (a) the chained form (tests/merge_cand_chain.py), built from entries the library already had: vvcgpu_mc_batch of every descriptor, vvcgpu_dist_batch
+      (Hadamard) of the luma blocks, vvcgpu_dist_batch (SSE) of all blocks, download, costs / lists / cut on the host (vectorised numpy);
+  (b) vvcgpu_merge_cand_batch and the download of its four outputs;
+  (c) (b) as a cost-only call (pred_base and sse_out NULL).
+The results of (a) and (b) are compared before anything is timed.  Times: device events around a whole run on the stream (for (a) that includes the
+host's part: it is what the caller waits for), 3 warm-up runs, then the median and the spread of 7 runs, (a), (b) and (c) alternating.  The device time
+of (b)'s two launches alone is given too."""
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import merge_cand_cases as mcc  # noqa: E402
+import merge_cand_chain as chain  # noqa: E402
+import pu_search_kit as kit  # noqa: E402
+from vvcsoftware_vtm_amd import abi, shape_mix  # noqa: E402
+
+W, H, BD = 3840, 2160, 10
+SQRT_LAMBDA, MAX_NUM, N_CAND, ATMVP_AT, SUB = 27.375, 7, 7, 2, 4
+WARMUP, RUNS = 3, 7
+rng = np.random.default_rng(31)
+
+
+def block_descs(fr, comp, bx, by, bw, bh, cux, cuy, pres, pic, mv, prec, dst_off, dst_stride):
+    """merge_cand_cases._block_desc on arrays: blocks (bx, by, bw, bh) of CUs at (cux, cuy); pres / pic [n][2], mv [n][2][2], prec [n]"""
+    s = 1 if comp else 0
+    n = len(bx)
+    e = np.zeros(n, abi.MC_DESC)
+    only1 = pres[:, 1] & ~pres[:, 0]                                       # a list-1-only block is handed over as ref0
+    for r in range(2):
+        src = np.where(only1, 1, r) if r == 0 else np.full(n, 1)
+        rows = np.arange(n)
+        p_, m = pic[rows, src], mv[rows, src].astype(np.int64)
+        lo = np.stack([(-mcc.MAX_CU - 8 - cux + 1) << prec, (-mcc.MAX_CU - 8 - cuy + 1) << prec], 1)
+        hi = np.stack([(fr.w + 8 - cux - 1) << prec, (fr.h + 8 - cuy - 1) << prec], 1)
+        m = np.minimum(hi, np.maximum(lo, m))
+        sh = (prec + s)[:, None]
+        whole, frac = m >> sh, (m & ((1 << sh) - 1)) << (4 - prec)[:, None]
+        off = np.array(fr.plane_off)[p_, comp] + (fr.margin[comp] + (by >> s) + whole[:, 1]) * fr.stride[comp] + fr.margin[comp] + (bx >> s) + whole[:, 0]
+        use = pres[:, 0] | pres[:, 1] if r == 0 else pres[:, 0] & pres[:, 1]
+        e["ref%d_off" % r], e["ref%d_stride" % r] = np.where(use, off, 0), np.where(use, fr.stride[comp], 0)
+        e["frac_x%d" % r], e["frac_y%d" % r] = np.where(use, frac[:, 0], 0), np.where(use, frac[:, 1], 0)
+    e["dst_off"], e["dst_stride"], e["w"], e["h"] = dst_off, dst_stride, bw >> s, bh >> s
+    e["is_luma"], e["bi"], e["reserved"] = 0 if comp else 1, pres[:, 0] & pres[:, 1], comp
+    return e
+
+
+def motion(n, prec=None):
+    """n blocks' (pres [n][2], pic [n][2], mv [n][2][2], prec [n]) around the true motion: list 0 / list 1 / both, never the same picture in both"""
+    kind = rng.integers(0, 3, n)
+    pres = np.stack([kind != 1, kind != 0], 1)
+    p0 = rng.integers(0, 2, n) * 2                                         # pictures 0 and 2 carry the original's motion (merge_cand_cases.derived_frame)
+    pic = np.stack([p0, 2 - p0], 1)
+    prec = rng.choice([2, 4], n) if prec is None else prec
+    true = np.where((pic == 0)[..., None], np.array([3, -2]), np.array([-4, 3]))          # samples
+    mv = (true << prec[:, None, None]) + rng.integers(-6, 7, (n, 2, 2))
+    return pres, pic, mv, prec
+
+
+def build(fr, px, py, w, h):
+    n = len(px)
+    atm = (np.arange(N_CAND)[None, :] == ATMVP_AT) & ((w >= 8) & (h >= 8))[:, None]          # [n][7]
+    nsub = np.where(atm, (w // SUB * (h // SUB))[:, None], 1)
+    count = (3 * nsub).reshape(-1)
+    n_cand = n * N_CAND
+    first = np.concatenate([[0], np.cumsum(count)]).astype(np.int64)
+    rep = lambda a: np.repeat(a, N_CAND)
+    cw, ch, cx, cy = rep(w), rep(h), rep(px), rep(py)
+    size = cw * ch
+    pos = np.concatenate([[0], np.cumsum(size * 3 // 2)]).astype(np.int64)
+    cur_off = np.stack([pos[:-1], pos[:-1] + size, pos[:-1] + size + size // 4], 1)      # [n_cand][3]
+    cur_stride = np.stack([cw, cw // 2, cw // 2], 1)
+    cand_dist = np.zeros((n_cand, 3), abi.DIST_DESC)
+    for comp in range(3):
+        s = 1 if comp else 0
+        d = cand_dist[:, comp]
+        d["org_off"] = fr.org_off[comp] + (cy >> s) * fr.org_stride[comp] + (cx >> s)
+        d["cur_off"], d["org_stride"], d["cur_stride"], d["w"], d["h"] = cur_off[:, comp], fr.org_stride[comp], cur_stride[:, comp], cw >> s, ch >> s
+    mc = np.zeros(int(first[-1]), abi.MC_DESC)
+    # the default candidates: one descriptor per component
+    dflt = np.nonzero(~atm.reshape(-1))[0]
+    pres, pic, mv, prec = motion(len(dflt))
+    for comp in range(3):
+        mc[first[dflt] + comp] = block_descs(fr, comp, cx[dflt], cy[dflt], cw[dflt], ch[dflt], cx[dflt], cy[dflt], pres, pic, mv, prec,
+                                             cur_off[dflt, comp], cur_stride[dflt, comp])
+    # the ATMVP candidates: one descriptor per sub-block and component; two sub-blocks of three share the candidate's base motion
+    ac = np.nonzero(atm.reshape(-1))[0]
+    if len(ac):
+        ns = nsub.reshape(-1)[ac]
+        owner = np.repeat(np.arange(len(ac)), ns)
+        k = np.arange(len(owner)) - np.repeat(np.cumsum(ns) - ns, ns)
+        c = ac[owner]
+        nx = cw[c] // SUB
+        sx, sy = (k % nx) * SUB, (k // nx) * SUB
+        bp, bpic, bmv, bprec = motion(len(ac))
+        prec = bprec[owner]
+        op, opic, omv, _ = motion(len(owner), prec)
+        own = rng.integers(0, 3, len(owner)) == 0
+        pres, pic, mv = np.where(own[:, None], op, bp[owner]), np.where(own[:, None], opic, bpic[owner]), np.where(own[:, None, None], omv, bmv[owner])
+        for comp in range(3):
+            s = 1 if comp else 0
+            off = cur_off[c, comp] + (sy >> s) * cur_stride[c, comp] + (sx >> s)
+            mc[first[c] + 3 * k + comp] = block_descs(fr, comp, cx[c] + sx, cy[c] + sy, np.full(len(c), SUB), np.full(len(c), SUB), cx[c], cy[c], pres, pic, mv,
+                                                      prec, off, cur_stride[c, comp])
+    return dict(mc=mc, cand_mc_first=first.astype(np.int32), cand_dist=cand_dist.reshape(-1),
+                pu_cand_first=(np.arange(n + 1) * N_CAND).astype(np.int32), pred_size=int(pos[-1]), n_comp=3)
+
+
+def main():
+    l0, l1 = kit.texture(rng, H, W, BD, 0.0), kit.texture(rng, H, W, BD, 1.5)
+    org = np.clip(np.roll(l0, (2, -3), axis=(0, 1)).astype(np.int32) + rng.integers(-5, 6, (H, W)), 0, 1023).astype(np.int16)
+    fr = mcc.derived_frame(l0, l1, org, BD)
+    hist, _ = shape_mix.load_trace()
+    sig = shape_mix.signatures(hist, "pelop", lambda w, h, a, b, c: a == 0 and w in mcc.SIDES and h in mcc.SIDES)
+    mix = np.array([(int(w), int(h)) for w, h in sig[rng.choice(len(sig), 8000, p=sig[:, 5] / sig[:, 5].sum()), :2]])
+    g = np.array([(x, y) for y in range(0, H, 16) for x in range(0, W, 16)])
+    lists = [("4K 16x16", np.full(len(g), 16), np.full(len(g), 16), g[:, 0], g[:, 1]),
+             ("trace mix", mix[:, 0], mix[:, 1], rng.integers(0, (W - mix[:, 0]) // 4 + 1) * 4, rng.integers(0, (H - mix[:, 1]) // 4 + 1) * 4)]
+    print("list          PUs  candidates  descriptors   chain ms (min..max)   entry ms (min..max)   launches ms   cost-only ms (min..max)   chain / entry")
+    for name, w, h, px, py in lists:
+        L = build(fr, px, py, w, h)
+        D = chain.Device(fr, L)
+        pred_a, pred_b = D.fresh_pred(), D.fresh_pred()
+
+        def entry():
+            return chain.download(chain.run_entry(D, pred_b, MAX_NUM, 1, SQRT_LAMBDA), None)
+
+        def cost_only():
+            return chain.download(chain.run_entry(D, None, MAX_NUM, 1, SQRT_LAMBDA, want_sse=False), None)
+
+        def chained():
+            return chain.run_chain(D, pred_a, MAX_NUM, 1, SQRT_LAMBDA, want_pred=False)
+
+        a, b, c = chained(), entry(), cost_only()
+        for f in ("dist", "sse", "rd_list"):
+            assert np.array_equal(a[f], b[f]), (name, f)
+        assert a["cost"].tobytes() == b["cost"].tobytes() == c["cost"].tobytes() and np.array_equal(b["rd_list"], c["rd_list"]), name
+        assert torch.equal(pred_a, pred_b), name
+        ta, tb, tc = kit.times_of_alternating((chained, entry, cost_only), WARMUP - 1, RUNS)      # the comparison above was the first warm-up run
+        tk = sorted(kit.events(lambda: chain.run_entry(D, pred_b, MAX_NUM, 1, SQRT_LAMBDA))[0] for _ in range(RUNS))[RUNS // 2]
+        ma, mb, mc_ = float(np.median(ta)), float(np.median(tb)), float(np.median(tc))
+        print("%-10s %6d  %10d  %11d   %8.2f (%.2f..%.2f)   %8.2f (%.2f..%.2f)   %11.2f   %8.2f (%.2f..%.2f)   %13.2f" %
+              (name, len(w), D.n_cand, D.n_mc, ma, min(ta), max(ta), mb, min(tb), max(tb), tk, mc_, min(tc), max(tc), ma / mb))
+
+
+if __name__ == "__main__":
+    main()

@@ -327,6 +327,22 @@ def mc_dist_batch(kind, ref0_base, ref1_base, org_base, descs_dev, n, bit_depth=
     return out
 
 
+def merge_cand_batch(ref0_base, ref1_base, org_base, pred_base, mc_descs_dev, n_mc, cand_mc_first, cand_dist_dev, n_cand, n_comp, pu_cand_first, n_pu,
+                     max_num_merge_cand, sqrt_lambda, use_hadamard=True, bit_depth=10, clp=(0, 1023), want_sse=True):
+    """the merge candidate pass of n_pu PUs (vvcgpu_merge_cand_batch): mc_descs_dev / cand_dist_dev are device copies of MC_DESC / DIST_DESC arrays,
+    cand_mc_first [n_cand + 1] and pu_cand_first [n_pu + 1] int32 tensors; pred_base may be None (cost only).  -> (dist int64 [n_cand], sse int64
+    [n_cand][n_comp] or None, cost float64 [n_cand], rd_list int32 [n_pu][8]: uiNumMrgSATDCand, then RdModeList)"""
+    dv = org_base.device
+    dist = torch.empty(n_cand, dtype=torch.int64, device=dv)
+    sse = torch.empty((n_cand, n_comp), dtype=torch.int64, device=dv) if want_sse else None
+    cost = torch.empty(n_cand, dtype=torch.float64, device=dv)
+    rd_list = torch.empty((n_pu, 8), dtype=torch.int32, device=dv)
+    capi.call("vvcgpu_merge_cand_batch", capi.ptr(ref0_base), capi.ptr(ref1_base), capi.ptr(org_base), capi.ptr(pred_base), capi.ptr(mc_descs_dev), n_mc,
+              capi.ptr(cand_mc_first), capi.ptr(cand_dist_dev), n_cand, n_comp, capi.ptr(pu_cand_first), n_pu, max_num_merge_cand, 1 if use_hadamard else 0,
+              float(sqrt_lambda), bit_depth, clp[0], clp[1], capi.ptr(dist), capi.ptr(sse), capi.ptr(cost), capi.ptr(rd_list), _stream())
+    return dist, sse, cost, rd_list
+
+
 def pelop_batch(op, src0_base, src1_base, dst_base, descs_dev, n, cfg):
     capi.call("vvcgpu_pelop_batch", op, capi.ptr(src0_base), capi.ptr(src1_base), capi.ptr(dst_base), capi.ptr(descs_dev), n,
               C.byref(cfg), _stream())
