@@ -228,3 +228,179 @@ def deblock_golden():
         r["post"] = [(r["pre"][c].astype(np.int32) + z["delta%d_%d" % (c, i)]).astype(np.int16) for c in range(3)]
         pics.append(r)
     return pics
+
+
+# ---- inputs at the exactness bounds of the transform, quantiser and statistics kernels ------------------------------------
+TR_NAMES = ("DCT2", "DCT8", "DST7")
+_tr_tables = None
+
+
+def tr_matrix(t, n):
+    """the n-point matrix of transform type t (0 DCT-II, 1 DCT-VIII, 2 DST-VII) of tests/golden/tr_tables.npz, row = frequency"""
+    global _tr_tables
+    if _tr_tables is None:
+        import os
+        _tr_tables = dict(np.load(os.path.join(os.path.dirname(__file__), "golden", "tr_tables.npz")))
+    return _tr_tables["%s_%d" % (TR_NAMES[t], n)].astype(np.int64)
+
+
+def _sgn(v):
+    return np.where(v < 0, -1, 1).astype(np.int64)         # sign(0) counts as +1
+
+
+def tr_aligned_block(w, h, th, tv, k, l, amp, negate=False):
+    """h x w residual whose signs follow row k of the horizontal and row l of the vertical matrix: coefficient (l, k) of the forward transform
+    is the largest a block of |x| <= amp can give, and the first stage's sums for frequency k are amp * (row-sum of |c|) in every row"""
+    b = amp * np.outer(_sgn(tr_matrix(tv, h)[l]), _sgn(tr_matrix(th, w)[k]))
+    return (-b if negate else b).astype(np.int16)
+
+
+_tr_idx = {}
+
+
+def _tr_aligned_idx(t, n):
+    if (t, n) not in _tr_idx:
+        kept = min(n, 32)
+        out = []
+        for i in (0, int(np.abs(tr_matrix(t, n))[:kept].sum(1).argmax()), kept - 1):
+            if i not in out:
+                out.append(i)
+        _tr_idx[(t, n)] = out
+    return _tr_idx[(t, n)]
+
+
+def tr_aligned_set(w, h, th, tv):
+    """(k, l, negate): per dimension index 0, the kept index with the largest row-sum of |c| and the last kept index min(N, 32) - 1, crossed,
+    each with and without negation (equal indices once)"""
+    for k in _tr_aligned_idx(th, w):
+        for l in _tr_aligned_idx(tv, h):
+            for negate in (False, True):
+                yield k, l, negate
+
+
+def tr_aligned_coeffs(w, h, th, tv, x, y, val):
+    """h x w int32 coefficients: (l, k) = val * sign(Th[k][x]) * sign(Tv[l][y]) inside the kept region (k, l < 32), zero outside: every term of
+    output sample (x, y) of the inverse transform has the sign of val"""
+    wj, hj = min(w, 32), min(h, 32)
+    c = np.zeros((h, w), np.int32)
+    c[:hj, :wj] = val * np.outer(_sgn(tr_matrix(tv, h)[:hj, y]), _sgn(tr_matrix(th, w)[:wj, x]))
+    return c
+
+
+def tr_sample_points(w, h):
+    """the four corners and one interior sample"""
+    return [(0, 0), (w - 1, 0), (0, h - 1), (w - 1, h - 1), (w // 2, h // 2 - (1 if h > 2 else 0))]
+
+
+TR_WORST_PAIRS = [(0, 0), (1, 1), (1, 2), (2, 1), (2, 2)]
+TR_SIZES = (2, 4, 8, 16, 32, 64)
+
+
+def tr_pair_allowed(w, h, th, tv):
+    return (th, tv) == (0, 0) or (4 <= w <= 32 and 4 <= h <= 32)
+
+
+def tr_worst_rows():
+    """forward items (w, h, th, tv, k, l, negate, amp, bd): every W x H in 2..64 with DCT-II / DCT-II and every shape in 4..32 with the other four
+    pairs, the patterns of tr_aligned_set, amplitude 1023 at bit depth 10, 255 and 1023 at bit depth 8 (the items of
+    tests/golden/transform_worst.npz)"""
+    rows = []
+    for bd, amps in ((10, (1023,)), (8, (255, 1023))):
+        for amp in amps:
+            for w in TR_SIZES:
+                for h in TR_SIZES:
+                    for (th, tv) in TR_WORST_PAIRS:
+                        if not tr_pair_allowed(w, h, th, tv):
+                            continue
+                        for k, l, negate in tr_aligned_set(w, h, th, tv):
+                            rows.append((w, h, th, tv, k, l, int(negate), amp, bd))
+    return np.array(rows, np.int32)
+
+
+def tr_worst_inv_rows():
+    """inverse items (w, h, th, tv, x, y, val, bd): tr_aligned_coeffs with val in {32767, -32768} at the points of tr_sample_points"""
+    rows = []
+    for bd in (10, 8):
+        for w in TR_SIZES:
+            for h in TR_SIZES:
+                for (th, tv) in TR_WORST_PAIRS:
+                    if not tr_pair_allowed(w, h, th, tv):
+                        continue
+                    for (x, y) in tr_sample_points(w, h):
+                        for val in (32767, -32768):
+                            rows.append((w, h, th, tv, x, y, val, bd))
+    return np.array(rows, np.int32)
+
+
+def chain_bound_case(bd, seed=0):
+    """org / pred planes tiled with tr_aligned_block residuals (pred = 0 or max, org the other, per sign of the pattern) and the TU list
+    (x, y, w, h, tr_hor, tr_ver, qp, intra, sbh) of the fused chain at low QPs: every shape of the chain's classes and of its generic path, QP in
+    {0, 4, 12, 22} + 6 (bd - 8) and QP 0 itself, both slice types, sign hiding on and off, in shuffled order.  The first two 64 x 64 TUs and
+    the first two TUs of every 32 x 32 cell are the DC pattern (plain, negated) at QP 0: at bit depth 10 their level meets the clip of
+    Quant::quant at +32767 / -32768 (bit depth 8, residual +-255: 26111).  -> org, pred, tus, W"""
+    rng = np.random.default_rng(1000 + bd + seed)
+    mx = (1 << bd) - 1
+    shapes = [(64, 64), (32, 32), (16, 16), (8, 8), (4, 4),
+              (64, 32), (32, 64), (16, 32), (32, 16), (64, 16), (8, 16), (16, 8), (4, 16), (4, 64), (64, 4), (16, 4), (4, 8), (8, 4), (2, 8), (8, 2), (2, 2),
+              (16, 64), (32, 8), (2, 32), (8, 32), (32, 4), (4, 32), (64, 8), (8, 64)]
+    qps = sorted({0} | {q + 6 * (bd - 8) for q in (0, 4, 12, 22)})
+    W, H = 640, 384                                          # 60 cells of 64 x 64: every shape twice, the two largest squares once more
+    org = np.zeros((H, W), np.int16)
+    pred = np.zeros((H, W), np.int16)
+    tus = []
+    ci = 0
+    for y0 in range(0, H, 64):
+        for x0 in range(0, W, 64):
+            w, h = shapes[ci % len(shapes)]
+            rnd = ci // len(shapes)
+            ci += 1
+            n = 0
+            for ty in range(0, 64, h):
+                for tx in range(0, 64, w):
+                    th = int(rng.integers(0, 3)) if 4 <= w <= 32 else 0
+                    tv = int(rng.integers(0, 3)) if 4 <= h <= 32 else 0
+                    pats = list(tr_aligned_set(w, h, th, tv))
+                    k, l, negate = pats[(n + ci) % len(pats)]
+                    qp, intra, sbh = int(qps[(n + ci // 3) % len(qps)]), (n >> 1) & 1, (n + ci) & 1
+                    if w == h and w >= 32 and (n < 2 if w == 32 else rnd < 2):
+                        th = tv = k = l = 0
+                        qp, negate = 0, bool(n & 1 if w == 32 else rnd & 1)
+                    b = tr_aligned_block(w, h, th, tv, k, l, mx, negate).astype(np.int32)
+                    org[y0 + ty:y0 + ty + h, x0 + tx:x0 + tx + w] = np.where(b > 0, mx, 0)
+                    pred[y0 + ty:y0 + ty + h, x0 + tx:x0 + tx + w] = np.where(b > 0, 0, mx)
+                    tus.append((x0 + tx, y0 + ty, w, h, th, tv, qp, intra, sbh))
+                    n += 1
+    order = rng.permutation(len(tus))
+    return org, pred, [tus[i] for i in order], W
+
+
+SAO_ONE_CATEGORY_KINDS = ("org_max", "rec_max", "stripes")
+
+
+def sao_one_category_planes(kind, w, h, bd):
+    """(org, rec) with |org - rec| at the full range in every sample: constant planes (max, 0) / (0, max) -- every sample in category 2 of
+    every EO class -- and (max, rec = vertical stripes of period 2 in {0, 1}), which moves everything into the categories 0 and 4 of the
+    horizontal and the diagonal classes"""
+    mx = (1 << bd) - 1
+    org = np.full((h, w), mx if kind != "rec_max" else 0, np.int16)
+    rec = np.full((h, w), mx if kind == "rec_max" else 0, np.int16)
+    if kind == "stripes":
+        rec[:, 1::2] = 1
+    return org, rec
+
+
+ALF_WORST_KINDS = (0, 64, 128, 896, 960, "max", "checker")
+
+
+def alf_worst_planes(kind, w, h, bd):
+    """(org, rec): rec constant at `kind` (64 and 128 make the low limb of a tap-pair sum or of the centre sample -128), org at the opposite
+    extreme; 'checker': rec a checkerboard of {0, max}, org its complement"""
+    mx = (1 << bd) - 1
+    if kind == "checker":
+        yy, xx = np.mgrid[0:h, 0:w]
+        rec = (((xx + yy) & 1) * mx).astype(np.int16)
+        return (mx - rec).astype(np.int16), rec
+    v = mx if kind == "max" else min(int(kind), mx)
+    rec = np.full((h, w), v, np.int16)
+    org = np.full((h, w), 0 if v > mx // 2 else mx, np.int16)
+    return org, rec

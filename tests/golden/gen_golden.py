@@ -202,6 +202,25 @@ def gen_transform():
     save("transform", **out)
 
 
+def gen_transform_worst():
+    """the transforms at their exactness bounds (cases.tr_worst_rows / tr_worst_inv_rows): residuals whose signs follow a basis
+    row at the full amplitude -- at bit depth 8 also at +-1023, where the first stage leaves 16 bits -- and full-scale coefficients aligned with
+    one output sample.  Only the rows and the reference's outputs are stored; the tests rebuild the inputs from the rows."""
+    rows, irows = cases.tr_worst_rows(), cases.tr_worst_inv_rows()
+    coefs, invs = [], []
+    for (w, h, th, tv, k, l, negate, amp, bd) in (tuple(int(v) for v in r) for r in rows):
+        r = np.ascontiguousarray(cases.tr_aligned_block(w, h, th, tv, k, l, amp, bool(negate)))
+        c = np.zeros((h, w), np.int32)
+        R.vtmref_fwd_tr2d(bd, p(r), w, p(c), w, h, th, tv)
+        coefs.append(c.reshape(-1))
+    for (w, h, th, tv, x, y, val, bd) in (tuple(int(v) for v in r) for r in irows):
+        q = np.ascontiguousarray(cases.tr_aligned_coeffs(w, h, th, tv, x, y, val))
+        ri = np.zeros((h, w), np.int16)
+        R.vtmref_inv_tr2d(bd, p(q), p(ri), w, w, h, th, tv)
+        invs.append(ri.reshape(-1))
+    save("transform_worst", rows=rows, coef=np.concatenate(coefs), inv_rows=irows, inv=np.concatenate(invs))
+
+
 def gen_tskip():
     """transform skip through the reference's own TrQuant::xTransformSkip / xITransformSkip (private members, entered by
     oracle/ref_wrap_kernels.h:vtmref_transform_skip): every W x H in 2..64 incl. the sqrt(2)-scaled rectangular shapes."""
@@ -624,6 +643,6 @@ def gen_pelop():
 
 if __name__ == "__main__":
     only = sys.argv[1:]
-    for fn in (gen_alf, gen_sao, gen_dist, gen_interp, gen_transform, gen_tskip, gen_dequant, gen_affine, gen_rdpcm, gen_affine_mv, gen_frac, gen_tzsearch, gen_picture, gen_intra, gen_imv, gen_quant, gen_depquant, gen_rdoq, gen_pelop):
+    for fn in (gen_alf, gen_sao, gen_dist, gen_interp, gen_transform, gen_transform_worst, gen_tskip, gen_dequant, gen_affine, gen_rdpcm, gen_affine_mv, gen_frac, gen_tzsearch, gen_picture, gen_intra, gen_imv, gen_quant, gen_depquant, gen_rdoq, gen_pelop):
         if not only or fn.__name__[4:] in only:
             fn()

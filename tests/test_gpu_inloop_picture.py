@@ -134,6 +134,30 @@ def test_sao_stats_picture(ctu, w, h, bd, use_avail, skips):
         assert_plane(got[i].cpu().numpy(), want, "plane %d" % i)
 
 
+@pytest.mark.parametrize("bd", [8, 10])
+@pytest.mark.parametrize("ctu", [32, 64, 128], ids=["scalar32_16", "packed64_scalar32", "packed128_64"])
+def test_sao_stats_picture_one_category_full_ctu(ctu, bd):
+    """the content of test_gpu_stats.py::test_sao_stats_one_category_full_ctu (|org - rec| = max everywhere, every sample of a CTU in one category or in
+    the two extreme ones) in all three planes; one CTU and 2 x 2 CTUs with a partial last row and column, skip lines on and off, org and rec views with
+    different strides.  The id names the body of the luma / chroma CTUs."""
+    from vvcsoftware_vtm_amd import ops
+    for (w, h) in ((ctu, ctu), (2 * ctu - 8, 2 * ctu - 12)):
+        hw = shapes(w, h)
+        nx, ny = cases.n_ctus(w, h, ctu)
+        for kind in cases.SAO_ONE_CATEGORY_KINDS:
+            pl = [cases.sao_one_category_planes(kind, b, a, bd) for a, b in hw]
+            o = Views(hw, 8, 16, [q[0] for q in pl])
+            r = Views(hw, 3, 7, [q[1] for q in pl])
+            for skips in ((5, 4, 3, 2), (0, 0, 0, 0)):
+                got = ops.sao_stats_picture(o.views, r.views, ctu, bd, None, skips[:2], skips[2:])
+                for i, (a, b) in enumerate(hw):
+                    cs = ctu if i == 0 else ctu // 2
+                    sr, sb = skips[:2] if i == 0 else skips[2:]
+                    want = np.zeros((nx * ny, 5, 2, 32), np.int64)
+                    oracle().orc_sao_stats(p(pl[i][0]), b, p(pl[i][1]), b, b, a, cs, cs, bd, None, sr, sb, p(want))
+                    assert_plane(got[i].cpu().numpy(), want, "%dx%d %s skips %s plane %d" % (w, h, kind, skips, i))
+
+
 # ---- ALF filter ----------------------------------------------------------------------------------------------------------------
 # variants: (content, coefficient amplitude, enables, narrowed clip).  'rand': a different random enable array per plane; 'null': NULL for all
 # three; 'mix': luma and Cr random, Cb NULL
@@ -224,6 +248,54 @@ def run_alf_stats_picture(w, h, ctu, bd, seed):
 @pytest.mark.parametrize("ctu", [64, 128, 256], ids=["ctu_form64", "ctu_form128", "tile_form256"])
 def test_alf_stats_picture(ctu, w, h, bd):
     run_alf_stats_picture(w, h, ctu, bd, [ctu, w, bd])
+
+
+@pytest.mark.parametrize("bd", [8, 10])
+@pytest.mark.parametrize("w,h", [(0, 0), (136, 72)], ids=["one_ctu", "ragged"])
+@pytest.mark.parametrize("ctu", [64, 128], ids=["ctu_form64", "ctu_form128"])
+def test_alf_stats_picture_single_class_worst_limbs(ctu, w, h, bd):
+    """the content of test_gpu_stats.py::test_alf_stats_single_class_worst_limbs through the CTU form (matrix-core Gram products on byte limbs, int32
+    accumulators per class and CTU): every block of a CTU in one class at |org - rec| = max.  vvcgpu_alf_stats_picture with an all-zero class map (and an
+    all-(24 | 3 << 8) one); vvcgpu_alf_classify_stats_picture with the classes it derives itself (constant / checkerboard planes: one class)."""
+    from vvcsoftware_vtm_amd import ops
+    from test_gpu_stats import alf_worst_kinds
+    if w == 0:
+        w = h = ctu
+    hw = shapes(w, h)
+    nx, ny = cases.n_ctus(w, h, ctu)
+    for kind in alf_worst_kinds(bd):
+        pl = [cases.alf_worst_planes(kind, b, a, bd) for a, b in hw]
+        o = Views(hw, 4, 12, [q[0] for q in pl])
+        r = Views(hw, 4, 12, [q[1] for q in pl])
+        org, rec = pl[0]
+        wantc = []
+        for i in (1, 2):
+            a, b = hw[i]
+            wc = np.zeros((nx * ny, 1, 57), np.int64)
+            oracle().orc_alf_stats(p(pl[i][0]), b, p(pl[i][1]), b, b, a, ctu // 2, None, 0, p(wc))
+            wantc.append(wc)
+        own = np.zeros((h // 4, w // 4), np.uint16)
+        oracle().orc_alf_classify(p(rec), w, w, h, bd, p(own))
+        assert len(np.unique(own & 0xFF)) == 1               # the classifier puts such a plane into ONE class (checkerboard: every transposition of it)
+        maps = [("own", own), ("zero", np.zeros_like(own))] + ([("last", np.full_like(own, 24 | (3 << 8)))] if kind in (64, "checker") else [])
+        for name, cls in maps:
+            want7 = np.zeros((nx * ny, 25, 183), np.int64)
+            want5 = np.zeros((nx * ny, 25, 57), np.int64)
+            oracle().orc_alf_stats(p(org), w, p(rec), w, w, h, ctu, p(cls), 1, p(want7))
+            oracle().orc_alf_stats(p(org), w, p(rec), w, w, h, ctu, p(cls), 0, p(want5))
+            if name == "own":
+                gcls, g7, g5, gc = ops.alf_classify_stats_picture(o.views, r.views, ctu, bd)
+                assert_plane(gcls.cpu().numpy().view(np.uint16), cls, "classes")
+            else:
+                g7, g5, gc = ops.alf_stats_picture(o.views, r.views, ctu, torch.from_numpy(cls.view(np.int16)).cuda())
+            what = "%s %s " % (kind, name)
+            assert_plane(g7.cpu().numpy(), want7, what + "luma 7x7")
+            assert_plane(g5.cpu().numpy(), want5, what + "luma 5x5")
+            assert_plane(gc[0].cpu().numpy(), wantc[0], what + "Cb")
+            assert_plane(gc[1].cpu().numpy(), wantc[1], what + "Cr")
+            E = g7.cpu().numpy()[..., :169].reshape(-1, 13, 13)
+            assert np.array_equal(E, E.transpose(0, 2, 1))
+            assert int(g7.cpu().numpy()[..., -1].sum()) == int(((org.astype(np.int64) - rec) ** 2).sum())
 
 
 def test_alf_stats_picture_1080p():

@@ -15,7 +15,8 @@ def test_vector_pipe_bodies_match_the_oracle():
     cases = ["tests/test_gpu_frac.py::test_frac16_every_alignment", "tests/test_gpu_frac.py::test_frac16_hadamard_at_the_int16_bound",
              "tests/test_gpu_interp.py::test_mc_every_phase", "tests/test_gpu_interp.py::test_mc_batch_few_pus",
              "tests/test_gpu_transform.py::test_tr_fwd_inv", "tests/test_gpu_transform.py::test_tr_many_tus_shuffled",
-             "tests/test_gpu_transform.py::test_dequant_tr_inv", "tests/test_gpu_transform.py::test_dequant_tr_inv_long_homogeneous_batches"]
+             "tests/test_gpu_transform.py::test_dequant_tr_inv", "tests/test_gpu_transform.py::test_dequant_tr_inv_long_homogeneous_batches",
+             "tests/test_gpu_transform.py::test_tr_fwd_inv_at_the_exactness_bound", "tests/test_gpu_transform.py::test_dequant_tr_inv_at_the_clip"]
     r = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-m", "gpu", "-p", "no:cacheprovider"] + cases, cwd=ROOT, env=env,
                        capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]

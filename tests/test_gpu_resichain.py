@@ -54,6 +54,32 @@ def gpu_chain(org, pred, tus, bd, W, coffs):
     return dlevel.cpu().numpy(), a.cpu().numpy().view(np.uint32), drec.cpu().numpy()
 
 
+def runs_of(tus):
+    """(w, h, count) of a list grouped by shape"""
+    runs = []
+    for t in tus:
+        if runs and runs[-1][0] == t[2] and runs[-1][1] == t[3]:
+            runs[-1][2] += 1
+        else:
+            runs.append([t[2], t[3], 1])
+    return runs
+
+
+def gpu_chain_runs(org, pred, tus, runs, bd, W, coffs):
+    """vvcgpu_resi_chain_runs_batch on a list grouped by shape"""
+    from vvcsoftware_vtm_amd import ops
+    n = len(tus)
+    d = np.zeros(n, ops.RC_DESC)
+    for i, (x, y, w, h, th, tv, qp, intra, sbh) in enumerate(tus):
+        d[i] = (y * W + x, y * W + x, y * W + x, coffs[i], W, W, W, w, h, th, tv, intra, sbh, qp, (0, 0))
+    dorg, dpred = torch.from_numpy(org).cuda(), torch.from_numpy(pred).cuda()
+    drec = dpred.clone()
+    dlevel = torch.full((int(sum(t[2] * t[3] for t in tus)),), 0x5A5A5A5A, dtype=torch.int32, device="cuda")
+    a = ops.resi_chain_runs_batch(dorg, dpred, drec, dlevel, ops.struct_to_device(d), n, runs, bd, (0, (1 << bd) - 1))
+    torch.cuda.synchronize()
+    return dlevel.cpu().numpy(), a.cpu().numpy().view(np.uint32), drec.cpu().numpy()
+
+
 def tile(W, H, shapes, rng, qps, bd, types_small=True):
     """non-overlapping TUs: the plane is cut into 64x64 cells, each cell tiled with one shape"""
     tus = []
@@ -263,30 +289,17 @@ def test_resi_chain_runs_entry_equals_the_classified_entry(bd, content):
         tus = [t for t, k in zip(tus, keep) if k]
         order = sorted(range(len(tus)), key=lambda i: shapes.index((tus[i][2], tus[i][3])))      # grouped by shape, groups in the caller's order
         tus = [tus[i] for i in order]
-        runs = []
-        for t in tus:
-            if runs and runs[-1][0] == t[2] and runs[-1][1] == t[3]:
-                runs[-1][2] += 1
-            else:
-                runs.append([t[2], t[3], 1])
+        runs = runs_of(tus)
         o2 = org.copy()
         if rnd == 0 and bd == 10:
             for i in rng.choice(len(tus), 9, replace=False):
                 x, y = tus[i][:2]
                 o2[y, x] = -2500
         lv, asum, rec, coffs = oracle_chain(o2, pred, tus, bd, W)
-        n = len(tus)
-        d = np.zeros(n, ops.RC_DESC)
-        for i, (x, y, w, h, th, tv, qp, intra, sbh) in enumerate(tus):
-            d[i] = (y * W + x, y * W + x, y * W + x, coffs[i], W, W, W, w, h, th, tv, intra, sbh, qp, (0, 0))
-        dorg, dpred = torch.from_numpy(o2).cuda(), torch.from_numpy(pred).cuda()
-        drec = dpred.clone()
-        dlevel = torch.full((int(sum(t[2] * t[3] for t in tus)),), 0x5A5A5A5A, dtype=torch.int32, device="cuda")
-        a = ops.resi_chain_runs_batch(dorg, dpred, drec, dlevel, ops.struct_to_device(d), n, runs, bd, (0, (1 << bd) - 1))
-        torch.cuda.synchronize()
-        assert np.array_equal(a.cpu().numpy().view(np.uint32), asum), rnd
-        assert np.array_equal(dlevel.cpu().numpy(), lv), rnd
-        assert np.array_equal(drec.cpu().numpy(), rec), rnd
+        glv, gsum, grec = gpu_chain_runs(o2, pred, tus, runs, bd, W, coffs)
+        assert np.array_equal(gsum, asum), rnd
+        assert np.array_equal(glv, lv), rnd
+        assert np.array_equal(grec, rec), rnd
 
 
 def test_resi_chain_runs_entry_rejects_inconsistent_runs():
@@ -299,3 +312,86 @@ def test_resi_chain_runs_entry_rejects_inconsistent_runs():
     for runs in ([(8, 8, 3)], [(8, 8, 2), (8, 8, 2)], [(8, 3, 4)]):
         with pytest.raises(capi.VvcGpuError):
             ops.resi_chain_runs_batch(t, t, t.clone(), lvl, dd, 4, runs, 10)
+
+
+def assert_chain(got, want, tus, coffs):
+    """levels, abs_sum and reconstruction equal; on a mismatch the message names the TUs"""
+    (glv, gsum, grec), (lv, asum, rec) = got, want
+    bad = [t for i, t in enumerate(tus) if gsum[i] != asum[i] or not np.array_equal(glv[coffs[i]:coffs[i] + t[2] * t[3]], lv[coffs[i]:coffs[i] + t[2] * t[3]])
+           or not np.array_equal(grec[t[1]:t[1] + t[3], t[0]:t[0] + t[2]], rec[t[1]:t[1] + t[3], t[0]:t[0] + t[2]])]
+    assert not bad, (len(bad), bad[:8])
+    assert np.array_equal(gsum, asum) and np.array_equal(glv, lv) and np.array_equal(grec, rec)
+
+
+@pytest.mark.parametrize("bd", [8, 10])
+def test_resi_chain_at_the_exactness_bound(bd):
+    """cases.chain_bound_case: residuals of +-max whose signs follow a basis row, all 29 shapes (co-operative 64 / 32 forms, one-wave matrix-core
+    rectangles, the 16x16 walk, packed tiles, lane groups, the generic launch for the 2-wide ones), QP 0 .. 22 + 6 (bd - 8): first-stage sums of
+    16 760 832 of 2^24 (bit depth 10), limbs at hi = 128, levels clipped to +-32767 / -32768 by the quantiser while abs_sum keeps the unclipped magnitudes,
+    the sign-hiding special case of a level on the clip, the de-quantiser's clip.  Through the classified entry, then (without the shapes with a 2-point side,
+    which make that entry take the classified path) grouped by shape through the runs entry."""
+    org, pred, tus, W = cases.chain_bound_case(bd)
+    lv, asum, rec, coffs = oracle_chain(org, pred, tus, bd, W)
+    assert_chain(gpu_chain(org, pred, tus, bd, W, coffs), (lv, asum, rec), tus, coffs)
+    shapes = sorted({(t[2], t[3]) for t in tus if min(t[2], t[3]) >= 4})
+    grouped = sorted((t for t in tus if min(t[2], t[3]) >= 4), key=lambda t: shapes.index((t[2], t[3])))
+    assert len(shapes) == 25
+    lv, asum, rec, coffs = oracle_chain(org, pred, grouped, bd, W)
+    assert_chain(gpu_chain_runs(org, pred, grouped, runs_of(grouped), bd, W, coffs), (lv, asum, rec), grouped, coffs)
+
+
+def threshold_case(rng, bd=10):
+    """quiet TUs (|org - pred| <= 20), every third (packed tiles, lane groups: TUs that share a tile) or second one with ONE sample whose residual is
+    +-1023 (the last value the matrix-core bodies take), +-1024 (the first they hand over; still an exact f16 value: it shows a TU lost or served twice) or
+    16392 / -16408 (no f16 values, 8 away from the next one: a TU that a missed vote keeps on the matrix cores gets different levels), org outside the bit depth where that needs it:
+    -> org, pred, tus, W, indices of the touched TUs"""
+    mx = (1 << bd) - 1
+    single = [(64, 64), (64, 32), (32, 64), (32, 32), (64, 16), (16, 64), (32, 16), (16, 32), (16, 16)]
+    shared = [(16, 8), (8, 16), (16, 4), (4, 16), (32, 8), (8, 32), (32, 4), (4, 32), (64, 8), (8, 64), (64, 4), (4, 64), (8, 8), (4, 4), (8, 4), (4, 8)]
+    want = []                                                # (w, h, None | (x, y, v))
+    for (w, h) in single + shared:
+        pts = [(0, 0), (w - 1, 0), (0, h - 1), (w - 1, h - 1), (w // 2 - 1, h // 2), (w - 1, h // 2)]
+        pts += [(min(w // 2 + 3, w - 1), 16 * s_ + 5) for s_ in range(h // 16)] if h >= 32 else []      # a sample in every wave's row strip of the co-operative form
+        for pt in pts:
+            for v in (1023, -1023, 1024, -1024, 16392, -16408):
+                want += [(w, h, pt + (v,))] + [(w, h, None)] * (1 if (w, h) in single else 2)
+    want += [(16, 16, (i % 16, (i // 16) % 16, (1024, -1024, 1023, 16392, -16408)[i % 5]) if i % 53 == 0 else None) for i in range(3200)]   # > 4 x 768: the 16x16 walk goes round
+    by_shape = {}
+    for i, (w, h, t) in enumerate(want):
+        by_shape.setdefault((w, h), []).append(i)
+    W = 1024
+    pos = {}
+    cell = 0
+    for (w, h), idx in by_shape.items():                     # 64 x 64 cells, one shape per cell
+        per = (64 // w) * (64 // h)
+        for j, i in enumerate(idx):
+            c = cell + j // per
+            q = j % per
+            pos[i] = ((c % 16) * 64 + (q % (64 // w)) * w, (c // 16) * 64 + (q // (64 // w)) * h)
+        cell += (len(idx) + per - 1) // per
+    H = ((cell + 15) // 16) * 64
+    pred = rng.integers(100, mx - 100, (H, W)).astype(np.int16)
+    org = (pred + rng.integers(-20, 21, (H, W))).astype(np.int16)
+    tus, touched = [], []
+    for i, (w, h, t) in enumerate(want):
+        x0, y0 = pos[i]
+        if t is not None:
+            x, y, v = t
+            org[y0 + y, x0 + x], pred[y0 + y, x0 + x] = {1023: (mx, 0), -1023: (0, mx), 1024: (mx + 1, 0), -1024: (-1, mx), 16392: (16392, 0), -16408: (mx - 16408, mx)}[v]
+            touched.append(i)
+        th = int(rng.integers(0, 3)) if 4 <= w <= 32 else 0
+        tv = int(rng.integers(0, 3)) if 4 <= h <= 32 else 0
+        tus.append((x0, y0, w, h, th, tv, (4, 22, 0)[i % 3] + 6 * (bd - 8), i & 1, (i >> 1) & 1))
+    return org, pred, tus, W, touched
+
+
+def test_resi_chain_single_sample_across_the_threshold():
+    """the range vote of every matrix-core class (co-operative 64 / 32 forms: the flag one wave raises must stop all four; one-wave rectangles; the
+    16x16 walk with more than 4 x 768 TUs, so that it goes round and sets TUs aside), of every packed-tile class and of the lane groups, with the
+    sample on the limit (+-1023: stays) and one past it (+-1024: handed to the generic body on the spot) at lanes of every kind.  The quiet TUs that share a
+    tile, a lane group or a slot with such a TU keep their fast path's results."""
+    rng = np.random.default_rng(1024)
+    org, pred, tus, W, touched = threshold_case(rng)
+    assert len(touched) > 1100 and sum(1 for t in tus if t[2:4] == (16, 16)) > 4 * 768
+    lv, asum, rec, coffs = oracle_chain(org, pred, tus, 10, W)
+    assert_chain(gpu_chain(org, pred, tus, 10, W, coffs), (lv, asum, rec), tus, coffs)

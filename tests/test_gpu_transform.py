@@ -202,6 +202,160 @@ def test_dequant_tr_inv_long_homogeneous_batches():
         assert np.array_equal(gres.cpu().numpy(), wres), (w, h)
 
 
+# ---- at the exactness bounds (the builders of cases.py; tests/test_exactness_bounds_cpu.py asserts that they reach the bounds) ----------
+def layout(items, pad):
+    """TR_DESC rows for blocks [(block h x w, th, tv)] laid out one after the other with row stride w + pad; pad 8 and 0: offsets kept at
+    multiples of 8 samples (16-byte aligned rows: what the matrix-core forward stages of a 32- / 64-wide TU ask for) -> descs, buffer, ncoef"""
+    from vvcsoftware_vtm_amd import ops
+    rows, bufs = [], []
+    roff = coff = 0
+    for (b, th, tv) in items:
+        h, w = b.shape
+        st = w + pad
+        r = np.full((h, st), 77, np.int16)
+        r[:, :w] = b
+        n = h * st + ((-h * st) % 8 if pad in (0, 8) else 0)
+        bufs.append(np.concatenate([r.reshape(-1), np.full(n - h * st, 77, np.int16)]))
+        rows.append((roff, coff, st, w, h, th, tv, 0, 0))
+        roff += n
+        coff += w * h
+    return np.array(rows, dtype=ops.TR_DESC), np.concatenate(bufs), coff
+
+
+def check_fwd(d, resi, ncoef, bd):
+    from vvcsoftware_vtm_amd import ops
+    want = np.full(ncoef, 9, np.int32)
+    oracle().orc_tr_fwd_batch(p(resi), p(want), p(d), len(d), bd)
+    got = torch.full((ncoef,), 9, dtype=torch.int32, device="cuda")
+    ops.tr_fwd_batch(dev(resi), got, ops.struct_to_device(d), len(d), bd)
+    got = got.cpu().numpy()
+    bad = [tuple(r)[2:7] for r in d if not np.array_equal(got[r["coeff_off"]:r["coeff_off"] + r["w"] * r["h"]], want[r["coeff_off"]:r["coeff_off"] + r["w"] * r["h"]])]
+    assert not bad, (len(bad), bad[:8])
+    assert np.array_equal(got, want)
+    return want
+
+
+def check_inv(d, cf, nresi, bd):
+    from vvcsoftware_vtm_amd import ops
+    wres = np.full(nresi, 77, np.int16)
+    oracle().orc_tr_inv_batch(p(cf), p(wres), p(d), len(d), bd)
+    gres = torch.full((nresi,), 77, dtype=torch.int16, device="cuda")
+    ops.tr_inv_batch(dev(cf), gres, ops.struct_to_device(d), len(d), bd)
+    gres = gres.cpu().numpy()
+    bad = []
+    for r in d:
+        idx = int(r["resi_off"]) + np.arange(int(r["h"]))[:, None] * int(r["resi_stride"]) + np.arange(int(r["w"]))[None, :]
+        if not np.array_equal(gres[idx], wres[idx]):
+            bad.append(tuple(r)[2:7])
+    assert not bad, (len(bad), bad[:8])
+    assert np.array_equal(gres, wres)                      # nothing outside the blocks either
+
+
+@pytest.mark.parametrize("bd", [8, 10])
+@pytest.mark.parametrize("pad", [3, 4, 8])
+def test_tr_fwd_inv_at_the_exactness_bound(bd, pad):
+    """residuals whose signs follow a basis row at the full amplitude (bit depth 8: also at +-1023, which the matrix-core predicate admits: the first
+    stage's result then needs 18 bits), every shape x transform pair x pattern of cases.tr_worst_rows in ONE list; inverse of full-scale coefficients
+    aligned with one output sample and of the forward results as they are.  Bodies (short calls: small / matrix-core / dot2 kernels):
+      pad 8  rows 16-byte aligned: tr_fwd_mfma_kernel for every shape with both sides in 16 / 32 / 64 -- the f32 sums of 16 760 832 of 2^24, the limb
+             edge hi = 128, at bit depth 8 the recombination of 2.1454e9 of 2^31; tr_inv_mfma_kernel, and its hand-over to the dot2 list when a
+             coefficient leaves 16 bits (+32768, the forward results of bit depth 8 at +-1023)
+      pad 4  4-byte aligned rows: matrix cores for the 16-wide shapes only, the dot2 kernels' packed 16-bit stages for the others with their
+             fits16 vote into the 32-bit second stage; lane groups of the small kernels for sides <= 8 (and 16 with a short side)
+      pad 3  odd row addresses: the generic first stage of the dot2 kernels, unaligned stores of the matrix-core inverse"""
+    rows = [r for r in cases.tr_worst_rows() if r[8] == bd]
+    items = [(cases.tr_aligned_block(*(int(v) for v in r[:6]), int(r[7]), bool(r[6])), int(r[2]), int(r[3])) for r in rows]
+    d, resi, ncoef = layout(items, pad)
+    want = check_fwd(d, resi, ncoef, bd)
+    check_inv(d, want, resi.size, bd)
+    irows = [r for r in cases.tr_worst_inv_rows() if r[7] == bd]
+    cfs = [cases.tr_aligned_coeffs(*(int(v) for v in r[:7])) for r in irows]
+    d2, buf, ncoef2 = layout([(np.zeros(c.shape, np.int16), int(r[2]), int(r[3])) for c, r in zip(cfs, irows)], pad)
+    check_inv(d2, np.concatenate([c.reshape(-1) for c in cfs]), buf.size, bd)
+
+
+MFMA_SIDES = (16, 32, 64)
+
+
+def vote_points(w, h):
+    """every corner, a sample in front of the vertical middle and one at the right edge: different lanes, registers and 16-row strips"""
+    return [(0, 0), (w - 1, 0), (0, h - 1), (w - 1, h - 1), (w // 2 - 1, h // 2), (w - 1, h // 2)]
+
+
+@pytest.mark.parametrize("pad", [0, 4])
+def test_tr_fallback_vote_at_the_threshold(pad):
+    """the range votes of the matrix-core forms (residual inside +-1023, coefficients inside 16 bits; ballots over the wave) at the value ON the
+    limit and one past it, in one sample of an otherwise quiet TU, at lanes / registers of every kind; untouched neighbours in between in the list
+    must keep their results whichever way their neighbour went.  +-1024 and +32768 / -32769 are still exact on the matrix cores (f16 values, limbs
+    of 8 bits + 1): they show a TU that is lost or served twice on its way to the other kernel.  16392 and -16408 are NO f16 values, 2049 * 256 + 5 and
+    -4099 * 256 - 3 have no exact high limb: a TU that a missed vote keeps on the matrix cores gets different results (the coefficients: where the
+    first inverse stage's clip to 16 bits does not absorb the difference).  pad 0: rows 16-byte aligned (matrix cores for all nine shapes); pad 4: the
+    32- / 64-wide shapes take the dot2 kernels, whose vote is on the first stage's results / the coefficients"""
+    rng = np.random.default_rng(31 + pad)
+    bd = 10
+    items, citems = [], []
+    for w in MFMA_SIDES:
+        for h in MFMA_SIDES:
+            th, tv = ((0, 0), (2, 1))[(w + h) // 16 % 2] if max(w, h) <= 32 else (0, 0)
+            for (x, y) in vote_points(w, h):
+                for v in (1023, -1023, 1024, -1024, 16392, -16408):
+                    b = rng.integers(-20, 21, (h, w)).astype(np.int16)
+                    b[y, x] = v
+                    items += [(b, th, tv), (rng.integers(-20, 21, (h, w)).astype(np.int16), th, tv)]
+            for (x, y) in vote_points(min(w, 32), min(h, 32)):
+                for v in (32767, -32768, 32768, -32769, 2049 * 256 + 5, -4099 * 256 - 3):
+                    c = rng.integers(-20, 21, (h, w)).astype(np.int32)
+                    c[y, x] = v
+                    citems += [(c, th, tv), (rng.integers(-20, 21, (h, w)).astype(np.int32), th, tv)]
+    d, resi, ncoef = layout(items, pad)
+    check_fwd(d, resi, ncoef, bd)
+    d2, buf, _ = layout([(np.zeros(c.shape, np.int16), th, tv) for c, th, tv in citems], pad)
+    check_inv(d2, np.concatenate([c.reshape(-1) for c, _, _ in citems]), buf.size, bd)
+
+
+@pytest.mark.parametrize("bd", [8, 10])
+def test_dequant_tr_inv_at_the_clip(bd):
+    """levels of +-32767 and of a few thousand at QP 0..5 and at the top QP, scalar and dependent quantisation, every shape: the de-quantiser's
+    clip to 16 bits binds (the coefficient output shows it) and the inverse transform starts from +-32768 / 32767 at position 0 and at the last kept
+    position.  dqtr_fused_kernel: lane groups (sides <= 8), the matrix-core inverse (both sides in 16 / 32 / 64), the dot2 stages (the others)"""
+    from vvcsoftware_vtm_amd import ops
+    rows = []
+    lvs = []
+    roff = loff = 0
+    qps = [0, 1, 2, 3, 4, 5, 51 + 6 * (bd - 8)]
+    for w in cases.TR_SIZES:
+        for h in cases.TR_SIZES:
+            for (th, tv) in [(0, 0), (2, 1)]:
+                if not cases.tr_pair_allowed(w, h, th, tv):
+                    continue
+                last = (min(h, 32) - 1) * w + min(w, 32) - 1
+                for (v0, v1) in [(32767, 0), (0, 32767), (-32767, 3000), (2500, -32767), (3000, -2500)]:
+                    for qp in qps:
+                        for dq in (0, 1):
+                            st = w + 4
+                            rows.append((roff, loff, st, w, h, th, tv, dq, 0, qp))
+                            lv = np.zeros(w * h, np.int32)
+                            lv[0] += v0
+                            lv[last] += v1
+                            lvs.append(lv)
+                            roff += h * st
+                            loff += w * h
+    d = np.array(rows, dtype=ops.DQTR_DESC)
+    lv = np.concatenate(lvs)
+    wres = np.full(roff, 11, np.int16)
+    wcoef = np.full(loff, 3, np.int32)
+    oracle().orc_dequant_tr_inv_batch(p(lv), p(wres), p(d), len(d), bd, p(wcoef))
+    assert wcoef.max() == 32767 and wcoef.min() == -32768               # the clip binds
+    gres = torch.full((roff,), 11, dtype=torch.int16, device="cuda")
+    gcoef = torch.full((loff,), 3, dtype=torch.int32, device="cuda")
+    ops.dequant_tr_inv_batch(dev(lv), gres, ops.struct_to_device(d), len(d), bd, gcoef)
+    assert np.array_equal(gcoef.cpu().numpy(), wcoef)
+    assert np.array_equal(gres.cpu().numpy(), wres)
+    gres2 = torch.full((roff,), 11, dtype=torch.int16, device="cuda")
+    ops.dequant_tr_inv_batch(dev(lv), gres2, ops.struct_to_device(d), len(d), bd, None)
+    assert np.array_equal(gres2.cpu().numpy(), wres)
+
+
 def test_scan_order_host_matches_golden():
     import ctypes as C
     import os

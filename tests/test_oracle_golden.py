@@ -127,6 +127,33 @@ def test_transform_golden():
             pos += n
 
 
+def test_transform_worst_golden():
+    """restatement == compiled reference at the exactness bounds of the device transforms (tests/golden/gen_golden.py:gen_transform_worst): residuals
+    aligned with a basis row at the full amplitude, full-scale coefficients aligned with one output sample; the inputs are rebuilt from the rows"""
+    import cases
+    g = dict(load("transform_worst"))                       # (decompressed once)
+    assert np.array_equal(g["rows"], cases.tr_worst_rows()) and np.array_equal(g["inv_rows"], cases.tr_worst_inv_rows())
+    O = oracle()
+    pos = 0
+    for row in g["rows"]:
+        w, h, th, tv, k, l, negate, amp, bd = (int(v) for v in row)
+        r = np.ascontiguousarray(cases.tr_aligned_block(w, h, th, tv, k, l, amp, bool(negate)))
+        c = np.zeros(w * h, np.int32)
+        O.orc_tr_fwd(p(r), w, p(c), w, h, th, tv, bd)
+        assert np.array_equal(c, g["coef"][pos:pos + w * h]), tuple(row)
+        pos += w * h
+    assert pos == g["coef"].size
+    pos = 0
+    for row in g["inv_rows"]:
+        w, h, th, tv, x, y, val, bd = (int(v) for v in row)
+        q = np.ascontiguousarray(cases.tr_aligned_coeffs(w, h, th, tv, x, y, val))
+        ri = np.zeros(w * h, np.int16)
+        O.orc_tr_inv(p(q), p(ri), w, w, h, th, tv, bd)
+        assert np.array_equal(ri, g["inv"][pos:pos + w * h]), tuple(row)
+        pos += w * h
+    assert pos == g["inv"].size
+
+
 def test_transform_skip_golden():
     """T3 pinned: restatement == TrQuant::xTransformSkip / xITransformSkip of the compiled reference."""
     g = load("tskip")

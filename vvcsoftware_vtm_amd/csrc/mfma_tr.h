@@ -5,7 +5,19 @@
 //
 // v_mfma_f32_16x16x32_f16 accumulates in f32, which is exact for integers below 2^24: the matrix entries (|c| <= 362... 90 for DCT-II, all exact
 // f16 values) times operands of at most 11 bits over 64 terms stay below 2^24; 16-bit operands are split into two signed 8-bit limbs
-// (t = 256 hi + lo), one MFMA chain per limb, recombined in int32 with the reference's rounding shift and clipping.  The result tile of one
+// (t = 256 hi + lo), one MFMA chain per limb, recombined in int32 with the reference's rounding shift and clipping.
+// The margins (tests/test_exactness_bounds_cpu.py computes them from the tables, tests/test_gpu_transform.py::test_tr_fwd_inv_at_the_exactness_bound
+// and tests/test_gpu_resichain.py::test_resi_chain_at_the_exactness_bound sit on them):
+//   * first forward stage: the largest row-sum of |c| is 16384 (row 0 of the 64-point DCT-II, 64 x 256), so a row of +-1023 whose signs follow it
+//     sums to 16 760 832 = 2^24 - 16 384;
+//   * its result at bit depth 10 is then 32 736: limbs hi = 128, lo = -32, the one value of hi outside a signed byte (exact in f16 all the same);
+//     a limb chain sums to at most 128 x 16384 = 2^21;
+//   * the range vote admits |x| <= 1023 at EVERY bit depth; at bit depth 8 the first shift is two bits shorter and the result reaches 130 944 --
+//     no 16-bit operand (limbs hi = 512, lo = -128; -511 and -128 for the negated block), but hi is still exact, its chain sums to at most
+//     512 x 16384 = 2^23 < 2^24, and the recombination (hi << 8) + lo of the second stage reaches 2 145 386 496 of 2^31 = 2 147 483 648, the tightest
+//     margin of the family (0.1 %) -- with hi << 8 = 2^31 on the way, which is why rc_join forms it modulo 2^32;
+//   * inverse stages: operands are 16-bit by vote (coefficients) or by clip (first stage), |hi| <= 128 over at most 32 kept terms: below 2^21.
+// The result tile of one
 // stage is the operand of the next WITHOUT leaving the lane: a 16x16 result has its column on the lane and four consecutive rows in registers,
 // the next product sums over that row index, and the k order of an MFMA is free as long as both operands agree -- so the matrix operand is read
 // from LDS in the k order the result registers already have.
@@ -87,6 +99,10 @@ __device__ __forceinline__ void rc_limbs(int v, _Float16& hi, _Float16& lo)
   lo = (_Float16)(short)l;
   hi = (_Float16)(short)((v - l) >> 8);
 }
+
+// 256 hi + lo + rnd of a forward second stage, formed modulo 2^32: at bit depth 8 with |x| = 1023 in a 64-row column (see the margins above) the high
+// chain alone is 512 x 16384 = 2^23 and hi << 8 = 2^31 -- one more than int32 holds -- while the sum with lo (-128 x 16384 there) is 2 145 386 496 again
+__device__ __forceinline__ int rc_join(float hi, float lo, int rnd) { return (int)(((unsigned)(int)hi << 8) + (unsigned)(int)lo + (unsigned)rnd); }
 
 // K-step bookkeeping of a product with inner dimension KD: one 16x16x16 step for KD = 16, KD / 32 steps of 16x16x32 otherwise
 template <int KD> struct RcK { static constexpr int STEPS = KD == 16 ? 1 : KD / 32; };
@@ -218,7 +234,7 @@ __device__ __forceinline__ void mt_fwd2(int (&cf)[(MtShape<W, H>::IT)][(MtShape<
     {
       const f4 hi = rc_mma<H>(a, bh[jt], f4{ 0.f, 0.f, 0.f, 0.f }), lo = rc_mma<H>(a, bl[jt], f4{ 0.f, 0.f, 0.f, 0.f });
 #pragma unroll
-      for (int r = 0; r < 4; r++) cf[it][jt][r] = ((((int)hi[r]) << 8) + (int)lo[r] + (1 << (s2 - 1))) >> s2;
+      for (int r = 0; r < 4; r++) cf[it][jt][r] = rc_join(hi[r], lo[r], 1 << (s2 - 1)) >> s2;
     }
   }
 }

@@ -8,7 +8,9 @@
 // One chain launch (+ a generic launch for what it cannot take) behind the entry point, fed by a device-side classification of the descriptor list:
 //   * both sides in 16 / 32 / 64: ONE WAVE PER TU, all four 1-D stages on the matrix cores.  v_mfma_f32_16x16x32_f16 accumulates in f32, which is
 //     exact for integers below 2^24: the matrix entries (|c| <= 362) and the residual (|x| <= 1023) are exact f16 values and a 64-term row sum
-//     stays below 2^24; the 16-bit intermediates of the later stages are split into two signed 8-bit limbs (t = 256 hi + lo), one MFMA chain per
+//     stays below 2^24 (at most 1023 x 16384 = 16 760 832 = 2^24 - 16 384; the margins of every stage, and of the bit depth 8 case where the first
+//     stage's result leaves 16 bits, are listed in mfma_tr.h; tests/test_gpu_resichain.py::test_resi_chain_at_the_exactness_bound runs the chain on
+//     them); the 16-bit intermediates of the later stages are split into two signed 8-bit limbs (t = 256 hi + lo), one MFMA chain per
 //     limb, recombined in int32 with the reference's rounding shift and clipping.  The result tile of one stage is the operand of the next
 //     WITHOUT leaving the lane: a 16x16 result has its column on the lane and four consecutive rows in registers, the next product sums over
 //     that row index, and the k order of an MFMA is free as long as both operands agree -- so the matrix operand is read from LDS in the
@@ -617,7 +619,7 @@ __device__ __forceinline__ bool rc_tu_coop(const RcDesc& d, const Pel* __restric
         lo = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, *reinterpret_cast<const h8*>(e1l + (16 * jt + c) * P1 + 32 * s + 8 * g), lo, 0, 0, 0);
       }
 #pragma unroll
-      for (int r = 0; r < 4; r++) cf[r] = ((((int)hi[r]) << 8) + (int)lo[r] + (1 << (s2 - 1))) >> s2;
+      for (int r = 0; r < 4; r++) cf[r] = rc_join(hi[r], lo[r], 1 << (s2 - 1)) >> s2;
     }
     const int tid = wv * 64 + lane;
     if (MODE == RC_CHAIN)
@@ -1294,7 +1296,7 @@ __device__ __noinline__ void rc_tile_packed_hl(const RcDesc* __restrict__ descs,
 #pragma unroll
     for (int it = 0; it < 2; it++)
 #pragma unroll
-      for (int r = 0; r < 4; r++) cf[it][r] = ((((int)hi[it][r]) << 8) + (int)lo[it][r] + (1 << (s2 - 1))) >> s2;   // C[vertical frequency 16 it + 4 g + r][horizontal c]
+      for (int r = 0; r < 4; r++) cf[it][r] = rc_join(hi[it][r], lo[it][r], 1 << (s2 - 1)) >> s2;   // C[vertical frequency 16 it + 4 g + r][horizontal c]
   }
   if (mode == RC_FWD)                                                     // forward transform only: the coefficients are the result
   {

@@ -118,6 +118,9 @@ __device__ __forceinline__ void sao_stats_body(const int cx, const int cy, const
   // per (EO class, category) one packed accumulator: count in bits 21.., sum of (d + 1024) below -- one compare, one select, one add
   // per category instead of two selects and two adds.  A thread walks <= 16 rows (host), so even the sum over the 64 lanes of a wave
   // stays inside the fields (sum <= 1024 * 2047 < 2^21, count <= 1024 < 2^11): the wave reduction below works on the packed words.
+  // Margins: 16 rows would give 64 x 16 x 2047 = 2 096 128 = 2^21 - 1024 when every sample of the wave falls into ONE category with d = +max at
+  // bit depth 10; the launch shapes the host chooses (vvcgpu_sao_stats, vvcgpu_sao_stats_picture) give a thread at most 4 rows, i.e. 524 032.
+  // tests/test_gpu_stats.py::test_sao_stats_one_category_full_ctu and its picture twin in tests/test_gpu_inloop_picture.py run exactly that content.
   unsigned acc[4][5];
 #pragma unroll
   for (int t = 0; t < 4; t++)
@@ -756,7 +759,10 @@ typedef int alf_i4 __attribute__((ext_vector_type(4)));
 // to 13 x 13, y = its column 13, pixAcc = entry (13, 13).  Values need 11 bits (+ sign for org - rec), so x = 256 H + L with L = the low byte read
 // as SIGNED (the matrix cores multiply signed bytes) and H = (x + 128) >> 8 in [-4, 8] = the high byte of x + 128: both limbs are byte picks
 // (v_perm_b32), no masks or shifts; four v_mfma_i32_16x16x64_i8 per step of 64 pixels accumulate L L^T, H L^T, L H^T and H H^T exactly in int32
-// (a whole CTU of one class stays below 2^29), and E = 65536 HH + 256 (HL + LH) + LL is formed in 64 bits when a class is finished.
+// (a whole CTU of one class stays below 2^29: L L^T reaches 128 x 128 x 16384 pixels = 2^28 exactly when every pixel of a 128 x 128 CTU falls into one
+// class with L = -128 -- rec = 64 everywhere for the tap pairs, 128 for the centre sample; tests/test_gpu_stats.py::test_alf_stats_single_class_worst_limbs
+// and tests/test_gpu_inloop_picture.py::test_alf_stats_picture_single_class_worst_limbs run it), and E = 65536 HH + 256 (HL + LH) + LL is formed in 64
+// bits when a class is finished.
 //   * the CTU's 4x4 blocks are counting-sorted by class in LDS; a class is padded to whole steps of four blocks;
 //   * lane (c, g) of a step builds variable c for the 16 pixels of block g: two unaligned 4-sample reads per row from the LDS tile (offset of
 //     the tap that the block's transposition puts at coefficient c), one v_pk_add_u16, limb split, byte pack -- the SAME registers are the A
