@@ -1235,6 +1235,49 @@ typedef struct vvcgpu_intra_fill_desc {
 int vvcgpu_intra_fill_refs_batch(const vvc_pel* rec_base, const uint8_t* flags_base, vvc_pel* refs_base, const vvcgpu_intra_fill_desc* descs,
                                  int n, int bit_depth, void* stream);
 
+/* N4, the intra mode pre-selection PASS: what IntraSearch::estIntraPredLumaQT does between initIntraPatternChType and its RD loop
+ * (EncoderLib/IntraSearch.cpp:383-522, 591-618) for n independent luma PUs of mixed sizes, in one launch with no host synchronisation inside.
+ * Per PU: the reference sample gathering (optional; xFillReferenceSamples, CommonLib/IntraPrediction.cpp:807-1004), both reference chains of
+ * initIntraPatternChType(.., true) (xFilterReferenceSamples :1071-1104), round 1 (:405-446: planar, DC and the even angular modes), round 2
+ * (:452-496: mode -1 / +1 of every parent 3..65 of the round-1 list, in list order, under the bSatdChecked guard), the MPM append (:499-522) and the
+ * PBINTRA cut with its early return (:591-618).  Every mode is predicted from the chain that useFilteredIntraRefSamples(.., modeSpecific = true, ..)
+ * selects (:1107-1139: the wide-angle rule, planar iff w h > 32, m_aucIntraFilter with HM_MDIS_AS_IN_JEM = 1), costs
+ * (double)uiSad + (double)bits * sqrt_lambda with the Hadamard distFunc (the product first, then the sum, not fused), and goes through the two
+ * updateCandList calls of :440-442 / :489-490 (CommonLib/UnitTools.h:190-223; strict '<': of two equal costs the earlier visited mode stays ahead).
+ *
+ * pus[p]       org_off, org_stride, w, h (powers of two 4..64) and ref_off: the PU's T + L + 1 packed references in refs_base, laid out as for
+ *              vvcgpu_intra_pred_batch; mode, filter_refs and the reserved fields are ignored.
+ * fill[p]      with rec_base and flags_base, all three or none: exactly what vvcgpu_intra_fill_refs_batch takes, with w, h and ref_off equal to
+ *              pus[p]'s.  The references are gathered first and, unless refs_base is NULL, also written there.  Without fill, refs_base holds them.
+ * pu_ctl       [4 p .. 4 p + 3]: the three MPMs of PU::getIntraMPMs (each 0..66), then numModesForFullRD (1..8; the caller's table lookup, :356-368).
+ * pu_mode_bits [4 p + k]: what xFracModeBitsIntra returns for a mode equal to mpm[k] (the first match, k = 0..2), k = 3: for every other mode
+ *              (CABACWriter::intra_luma_pred_mode, EncoderLib/CABACWriter.cpp:867-935, yields these four values under a fixed ctxStartIntraMode).
+ * pu_inter_had [p]: cs.interHad of the PBINTRA gate; ~0 switches the gate off for the PU, a NULL array for all.  The gate's condition (getUsePbIntraFast,
+ *              the slice type, the part size, the EMT pass) is the caller's; the device compares CandHadList[k] > (double)interHad * 1.1.
+ * flags        VVCGPU_INTRA_CAND_*.  sqrt_lambda: getMotionLambda() / (1 << SCALE_BITS), in [0, 2^20).  bit_depth: 8..10 (else VVCGPU_E_UNSUPPORTED).
+ * satd_out     [67 p + m]: uiSad of every evaluated mode m, ~0 for the others; may be NULL.
+ * list_out     [16 p ..]: [0] the final uiRdModeList.size() (0: the early return of :604-617), [1] the size of uiHadModeList, [2..4] uiHadModeList,
+ *              [5..15] uiRdModeList; -1 beyond each list's size.
+ * cost_out     [12 p ..]: [0..7] CandCostList (numModesForFullRD entries: an appended MPM carries none), [8..10] CandHadList; +infinity elsewhere.
+ *
+ * A PU outside the contract -- a side outside 4..64 (a 128-sample side is not served, as by the other intra entries), fill[p] disagreeing with pus[p]
+ * (or with a unit size below 1, or more than 192 units), an MPM outside 0..66, numModesForFullRD outside 1..8 -- is skipped: nothing is read or
+ * predicted for it, its list_out row is all -1, its cost_out row all +infinity, its satd_out row all ~0.  Offsets cannot be validated.
+ * VVCGPU_E_ARG before any device work: a null required pointer, fill / rec_base / flags_base not all set or all NULL, neither fill nor refs_base,
+ * negative n, unknown flag bits, a bad clip range, sqrt_lambda negative, not finite or >= 2^20, a descriptor array that is not 16-byte aligned.
+ * n == 0 is a no-op.
+ * Not served: lossless DPCM (useDPCMForFirstPassIntraEstimation), INTRA_FULL_SEARCH, the emtUsageFlag == 2 reuse of a saved list (:541-581), chroma,
+ * and the RD loop that follows (:620-).                                                                                                         */
+#define VVCGPU_INTRA_CAND_USE_MPM       1   /* getFastUDIUseMPMEnabled(): the append of :499-522 */
+#define VVCGPU_INTRA_CAND_NO_SMOOTHING  2   /* sps intraSmoothingDisabledFlag: no mode predicts from filtered references */
+int vvcgpu_intra_mode_cand_batch(
+    const vvc_pel* rec_base, const uint8_t* flags_base, const vvcgpu_intra_fill_desc* fill,  /* all three NULL: refs_base holds the references */
+    vvc_pel* refs_base,                        /* read when fill == NULL; with fill: where the gathered references are also written, may be NULL */
+    const vvc_pel* org_base, const vvcgpu_intra_satd_desc* pus, int n,
+    const int32_t* pu_ctl, const uint64_t* pu_mode_bits, const uint64_t* pu_inter_had,       /* pu_inter_had may be NULL */
+    int flags, double sqrt_lambda, int bit_depth, int clp_min, int clp_max,
+    uint64_t* satd_out, int32_t* list_out, double* cost_out, void* stream);                   /* satd_out may be NULL */
+
 /* N4, CCLM: cross-component linear model prediction of a chroma block  (IntraPrediction::xGetLumaRecPixels :1283-1581, the
  * JVET_K0190 branch, + xGetLMParameters :1597-1857 + predIntraChromaLM :390-403).  4:2:0 only.  luma_off: the co-located luma
  * block's top-left sample in the luma RECONSTRUCTION plane (rows -2, -1 are read when above_avail, columns -3 .. -1 when left_avail);

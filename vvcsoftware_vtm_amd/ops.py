@@ -246,6 +246,26 @@ def intra_fill_refs_batch(rec_base, flags_base, refs_base, descs_dev, n, bit_dep
     capi.call("vvcgpu_intra_fill_refs_batch", capi.ptr(rec_base), capi.ptr(flags_base), capi.ptr(refs_base), capi.ptr(descs_dev), n, bit_depth, _stream())
 
 
+INTRA_CAND_USE_MPM, INTRA_CAND_NO_SMOOTHING = 1, 2
+
+
+def intra_mode_cand_batch(org_base, pus_dev, n, pu_ctl, pu_mode_bits, sqrt_lambda, refs_base=None, fill=None, pu_inter_had=None,
+                          flags=INTRA_CAND_USE_MPM, bit_depth=10, clp=(0, 1023), want_satd=True):
+    """the intra mode pre-selection pass of n luma PUs (vvcgpu_intra_mode_cand_batch): pus_dev a device copy of an INTRA_SATD_DESC array, pu_ctl int32
+    [n][4] (three MPMs, numModesForFullRD), pu_mode_bits int64 [n][4], pu_inter_had int64 [n] or None.  fill = (rec_base, flags_base, a device copy
+    of an INTRA_FILL_DESC array) gathers the references first (refs_base, if given, receives them); without fill, refs_base holds them.
+    -> (satd int64 [n][67] or None, lists int32 [n][16], costs float64 [n][12])"""
+    dv = org_base.device
+    satd = torch.empty((n, 67), dtype=torch.int64, device=dv) if want_satd else None
+    lists = torch.empty((n, 16), dtype=torch.int32, device=dv)
+    costs = torch.empty((n, 12), dtype=torch.float64, device=dv)
+    rec, flg, fd = fill if fill is not None else (None, None, None)
+    capi.call("vvcgpu_intra_mode_cand_batch", capi.ptr(rec), capi.ptr(flg), capi.ptr(fd), capi.ptr(refs_base), capi.ptr(org_base), capi.ptr(pus_dev), n,
+              capi.ptr(pu_ctl), capi.ptr(pu_mode_bits), capi.ptr(pu_inter_had), flags, float(sqrt_lambda), bit_depth, clp[0], clp[1], capi.ptr(satd),
+              capi.ptr(lists), capi.ptr(costs), _stream())
+    return satd, lists, costs
+
+
 def imv_refine_batch(org, ref, pus_dev, n, cfg, use_hadamard=True, weight=1.0):
     """N2 (AMVR): xPatternSearchIntRefine for n PUs -> IMV_RESULT records (uint8 tensor)."""
     po, so, _, _ = _plane(org, "org")
