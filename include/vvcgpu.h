@@ -1267,7 +1267,7 @@ int vvcgpu_intra_fill_refs_batch(const vvc_pel* rec_base, const uint8_t* flags_b
  * negative n, unknown flag bits, a bad clip range, sqrt_lambda negative, not finite or >= 2^20, a descriptor array that is not 16-byte aligned.
  * n == 0 is a no-op.
  * Not served: lossless DPCM (useDPCMForFirstPassIntraEstimation), INTRA_FULL_SEARCH, the emtUsageFlag == 2 reuse of a saved list (:541-581), chroma,
- * and the RD loop that follows (:620-).                                                                                                         */
+ * and the RD loop that follows (:620-; its pixel pass: vvcgpu_intra_tu_code_batch).                                                             */
 #define VVCGPU_INTRA_CAND_USE_MPM       1   /* getFastUDIUseMPMEnabled(): the append of :499-522 */
 #define VVCGPU_INTRA_CAND_NO_SMOOTHING  2   /* sps intraSmoothingDisabledFlag: no mode predicts from filtered references */
 int vvcgpu_intra_mode_cand_batch(
@@ -1277,6 +1277,50 @@ int vvcgpu_intra_mode_cand_batch(
     const int32_t* pu_ctl, const uint64_t* pu_mode_bits, const uint64_t* pu_inter_had,       /* pu_inter_had may be NULL */
     int flags, double sqrt_lambda, int bit_depth, int clp_min, int clp_max,
     uint64_t* satd_out, int32_t* list_out, double* cost_out, void* stream);                   /* satd_out may be NULL */
+
+/* N4, the pixel pass of the intra RD loop: what IntraSearch::xIntraCodingTUBlock (EncoderLib/IntraSearch.cpp:1147-1316) does for one surviving mode or
+ * one EMT candidate -- predIntraAng, org - pred, transformNxN, the numSig count (:1257-1280), invTransformNxN, reconstruct, getDistPart(DF_SSE) -- for
+ * n independent luma TUs of mixed sizes, in ONE launch with no host synchronisation inside.  The prediction is formed in LDS and never goes through
+ * device memory; the rate (xGetIntraFracBitsQT) and the cost compare stay with the caller.
+ *
+ * Item i is the pair preds[i] + tus[i] (both device arrays, 16-byte aligned); w, h must agree between the two: powers of two 4..64.
+ * preds[i]     ref_off: the packed references in refs_base, as for vvcgpu_intra_pred_batch.  dst_off / dst_stride are ignored: the prediction's place is
+ *              tus[i].pred_off / pred_stride in pred_base.  mode 0..66 with filter_refs: used as given.  mode VVCGPU_INTRA_TU_FROM_LIST: the mode is
+ *              mode_list[16 row + 5 + slot] with row = tus[i].reserved[0], slot = tus[i].reserved[1] -- mode_list being list_out of
+ *              vvcgpu_intra_mode_cand_batch, consumed where it lies -- when slot < mode_list[16 row], else the item is skipped; the filter decision is
+ *              then the device's (useFilteredIntraRefSamples(.., modeSpecific = true, ..) for luma, CommonLib/IntraPrediction.cpp:1107-1139).
+ *              mode VVCGPU_INTRA_TU_PRED_GIVEN: no prediction, it is read from pred_base (chroma and CCLM through vvcgpu_cclm_pred_batch, the reload of
+ *              default0Save1Load2 == 2).
+ * tus[i]       as for vvcgpu_resi_chain_batch (Quant::quant with rounding 171 / 85 by intra_slice, xSignBitHidingHDQ by sign_hiding, Quant::dequant,
+ *              tr_hor / tr_ver 0..2, the 64-point zero-out, the reconstruction clip), same alignment contract for offsets and strides.  Levels go to
+ *              level_off, the zeroed region included.  reserved[0] / reserved[1]: row and slot of a FROM_LIST item, for this entry only.
+ * flags        VVCGPU_INTRA_TU_*.  bit_depth: 8..10 (else VVCGPU_E_UNSUPPORTED).  clp_min / clp_max: the clip range of prediction and reconstruction.
+ * abs_sum[i]   as vvcgpu_resi_chain_batch's.  num_sig[i]: the number of non-zero levels as stored (what :1262-1274 counts, uncapped; the comparison
+ *              with g_EmtSigNumThr and the early return of :1276 are the caller's, the entry always finishes the item).
+ * dist[i]      xGetSSE(org, rec), what vvcgpu_dist_batch kind 2 returns for the two blocks, from the reconstruction the item has just formed (64-bit
+ *              sums; the chroma distortion weight and DF_SSE_WTD are the caller's).  mode_out[i]: the mode used, -1 for PRED_GIVEN.
+ *
+ * An item is skipped -- abs_sum = num_sig = 0xFFFFFFFF, dist = ~0, mode_out = -1, nothing touched in pred_base / rec_base / level_base -- when it is a
+ * FROM_LIST slot beyond its list (or mode_list is NULL, or the list holds no mode 0..66 there), a side is outside 4..64, the pair disagrees on w / h,
+ * the mode is outside -2..66, tr_hor / tr_ver is outside 0..2, a 64-point side is not DCT-II, or it is PRED_GIVEN without pred_base.
+ * The rec / pred / level regions of different items must not overlap (candidates of one PU go to candidate buffers of their own), nor an item's rec
+ * region its own pred region.  Samples must lie within the bit depth.  Offsets cannot be validated.
+ * VVCGPU_E_ARG before any device work: a null required pointer (pred_base may be NULL when no item is PRED_GIVEN and WRITE_PRED is off; mode_list may
+ * be NULL), negative n, unknown flag bits, a bad clip range, a descriptor array that is not 16-byte aligned.  n == 0 is a no-op.
+ * Not served: transform skip and RDPCM (their own entries), RDOQ and the DepQuant trellis (vvcgpu_rdoq_batch / vvcgpu_depquant_batch; this is the
+ * Quant::quant chain), cross-component prediction, TUs split below the PU (the 64x64 TUs of a 128-sample CU depend on each other's reconstruction),
+ * chroma and CCLM prediction (they come in through PRED_GIVEN), the rate and the cost.                                                            */
+#define VVCGPU_INTRA_TU_PRED_GIVEN  (-1)   /* preds[i].mode: the prediction is read from pred_base */
+#define VVCGPU_INTRA_TU_FROM_LIST   (-2)   /* preds[i].mode: taken from mode_list */
+#define VVCGPU_INTRA_TU_WRITE_PRED    1    /* flags: predicted items also store their prediction at tus[i].pred_off (the "save" of default0Save1Load2 == 1) */
+#define VVCGPU_INTRA_TU_NO_SMOOTHING  2    /* flags: as VVCGPU_INTRA_CAND_NO_SMOOTHING, for FROM_LIST items */
+int vvcgpu_intra_tu_code_batch(
+    const vvc_pel* refs_base, const vvcgpu_intra_desc* preds,
+    const vvc_pel* org_base, vvc_pel* pred_base, vvc_pel* rec_base, vvc_coef* level_base,
+    const vvcgpu_resi_chain_desc* tus, int n,
+    const int32_t* mode_list,
+    int flags, int bit_depth, int clp_min, int clp_max,
+    uint32_t* abs_sum, uint32_t* num_sig, uint64_t* dist, int32_t* mode_out, void* stream);
 
 /* N4, CCLM: cross-component linear model prediction of a chroma block  (IntraPrediction::xGetLumaRecPixels :1283-1581, the
  * JVET_K0190 branch, + xGetLMParameters :1597-1857 + predIntraChromaLM :390-403).  4:2:0 only.  luma_off: the co-located luma

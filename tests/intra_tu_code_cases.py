@@ -1,0 +1,345 @@
+"""The pixel pass of the intra RD loop (IntraSearch::xIntraCodingTUBlock, IntraSearch.cpp:1147-1316) restated for the tests of vvcgpu_intra_tu_code_batch from
+oracle steps that are each pinned to the compiled reference: orc_intra_filter_refs / orc_intra_pred, orc_pelop_batch (subtract), orc_tr_fwd_batch,
+orc_quant_batch, orc_dequant_tr_inv_batch, orc_pelop_batch (reconstruct), orc_dist_batch kind 2; num_sig is counted in numpy; the luma filter rule, the
+list look-up and the planes come from intra_mode_cand_cases.  Also the case builders: items (a PU of an intra_mode_cand_cases.Case + a mode + the TU's
+transform and quantiser parameters) with candidate buffers of their own for prediction, reconstruction and levels, canaries between them.
+numpy only: the generator and the CPU tests load this file without torch."""
+import ctypes as C
+import os
+
+import numpy as np
+
+import intra_mode_cand_cases as imc
+from oraclelib import oracle, p
+from vvcsoftware_vtm_amd import abi
+from vvcsoftware_vtm_amd.abi import DIST_DESC, DQTR_DESC, PELOP_DESC, QUANT_DESC, TR_DESC, PelopCfg
+
+PRED_GIVEN, FROM_LIST = abi.INTRA_TU_PRED_GIVEN, abi.INTRA_TU_FROM_LIST
+WRITE_PRED, NO_SMOOTHING = abi.INTRA_TU_WRITE_PRED, abi.INTRA_TU_NO_SMOOTHING
+U32_MAX, U64_MAX = 0xFFFFFFFF, imc.U64_MAX
+PRED_CANARY, REC_CANARY, LEVEL_CANARY = 0x5A5A, -21846, 0x5A5A5A5A
+EMT_SIG_NUM_THR = 2                                                         # g_EmtSigNumThr (Rom.cpp)
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "intra_tu_code.npz")
+
+# w, h: the TU's sides as tus[i] states them (preds[i] carries the PU's own); row, slot: tus[i].reserved of a FROM_LIST item
+ITEM = np.dtype([("pu", "<i4"), ("mode", "<i4"), ("filt", "<i4"), ("w", "<i4"), ("h", "<i4"), ("tr_hor", "<i4"), ("tr_ver", "<i4"), ("qp", "<i4"),
+                 ("intra", "<i4"), ("sbh", "<i4"), ("row", "<i4"), ("slot", "<i4"), ("pred_off", "<i8"), ("pred_stride", "<i4"), ("rec_off", "<i8"),
+                 ("rec_stride", "<i4"), ("level_off", "<i8")])
+
+
+def max_qp(bd):
+    """the largest QpParam::Qp of the component: 63 (JVET_K0251) plus the bit-depth offset"""
+    return 63 + 6 * (bd - 8)
+
+
+def plain_case(bd, rec, org, blocks, rng=None):
+    """an intra_mode_cand_cases.Case over the two planes with one PU per (x, y, w, h); availability: everything, or random runs with rng"""
+    pus = np.zeros(len(blocks), imc.PU)
+    avail, fo, ro = [], 0, 0
+    for q, (x, y, w, h) in enumerate(blocks):
+        fl = imc.availability(rng, w, h, 0 if rng is None else int(rng.integers(0, 5)))
+        pus[q] = (x, y, w, h, [0, 1, 50], imc.num_modes_of(w, h), [0, 0, 0, 0], U64_MAX, fo, ro)
+        avail.append(fl)
+        fo += fl.size
+        ro += sum(imc.ref_lengths(w, h)) + 1
+    return imc.Case(rec, org, pus, np.concatenate(avail), bd)
+
+
+class TuCase:
+    """base: the planes and PUs (intra_mode_cand_cases.Case); items: ITEM records; pred0: the prediction buffer before the call (canaries, and the given
+    predictions of PRED_GIVEN items)"""
+    def __init__(self, base, items, pred0, rec_size, level_size):
+        self.base, self.items, self.pred0, self.rec_size, self.level_size, self.bd = base, items, pred0, rec_size, level_size, base.bd
+        self._refs = {}
+
+    def refs_of(self, q):
+        if q not in self._refs:
+            self._refs[q] = self.base.refs_of(q)
+        return self._refs[q]
+
+    def refs(self):
+        out = np.zeros(self.base.refs_size, np.int16)
+        for q, u in enumerate(self.base.pus):
+            r = self.refs_of(q)
+            out[int(u["ref_off"]):int(u["ref_off"]) + r.size] = r
+        return out
+
+    def descs(self):
+        """-> (preds: INTRA_DESC array, tus: RC_DESC array)"""
+        it, pus = self.items, self.base.pus[self.items["pu"]]
+        d = np.zeros(len(it), abi.INTRA_DESC)
+        d["ref_off"], d["dst_off"], d["dst_stride"] = pus["ref_off"], -12345, -7                      # dst_off / dst_stride are ignored by the entry
+        d["w"], d["h"], d["mode"], d["filter_refs"] = pus["w"], pus["h"], it["mode"], it["filt"]
+        t = np.zeros(len(it), abi.RC_DESC)
+        t["org_off"], t["org_stride"] = pus["y"].astype(np.int64) * self.base.W + pus["x"], self.base.W
+        for k in ("pred_off", "pred_stride", "rec_off", "rec_stride", "level_off", "w", "h", "tr_hor", "tr_ver", "qp"):
+            t[k] = it[k]
+        t["intra_slice"], t["sign_hiding"] = it["intra"], it["sbh"]
+        t["reserved"][:, 0], t["reserved"][:, 1] = it["row"], it["slot"]
+        return d, t
+
+    def initial(self):
+        """the three output buffers before the call"""
+        return self.pred0.copy(), np.full(self.rec_size, REC_CANARY, np.int16), np.full(self.level_size, LEVEL_CANARY, np.int32)
+
+
+def side_ok(v):
+    return 4 <= v <= 64 and (v & (v - 1)) == 0
+
+
+def resolve(tc, i, flags, mode_list, have_pred=True):
+    """-> (mode, filter) of item i, mode PRED_GIVEN included, or None: skipped"""
+    it = tc.items[i]
+    u = tc.base.pus[int(it["pu"])]
+    w, h, mode = int(it["w"]), int(it["h"]), int(it["mode"])
+    if not (side_ok(w) and side_ok(h) and w == int(u["w"]) and h == int(u["h"]) and FROM_LIST <= mode <= 66):
+        return None
+    if not (0 <= it["tr_hor"] <= 2 and 0 <= it["tr_ver"] <= 2 and (w <= 32 or it["tr_hor"] == 0) and (h <= 32 or it["tr_ver"] == 0)):
+        return None
+    if mode == PRED_GIVEN:
+        return (mode, 0) if have_pred else None
+    if mode == FROM_LIST:
+        row, slot = int(it["row"]), int(it["slot"])
+        if mode_list is None or not (0 <= slot < 11 and row >= 0) or slot >= int(mode_list[row][0]):
+            return None
+        mode = int(mode_list[row][5 + slot])
+        if not 0 <= mode <= 66:
+            return None
+        return mode, int(imc.use_filtered(w, h, mode, flags & NO_SMOOTHING))
+    return mode, int(it["filt"] != 0)
+
+
+def block(buf, off, stride, w, h):
+    """the h x w view of a flat buffer"""
+    return np.lib.stride_tricks.as_strided(buf[off:], (h, w), (stride * buf.itemsize, buf.itemsize))
+
+
+def code_block(org, pred, bd, tr_hor, tr_ver, qp, intra, sbh, clp):
+    """one TU from contiguous h x w original and prediction -> (levels [h][w] int32, abs_sum, rec [h][w] int16, dist) by the oracle's separate steps"""
+    h, w = org.shape
+    o = oracle()
+    org, pred = np.ascontiguousarray(org, np.int16), np.ascontiguousarray(pred, np.int16)
+    band = np.zeros(1, PELOP_DESC); band[0] = (0, 0, 0, w, w, w, w, h)
+    tr = np.zeros(1, TR_DESC); tr[0] = (0, 0, w, w, h, tr_hor, tr_ver, 0, 0)
+    qd = np.zeros(1, QUANT_DESC); qd[0] = (0, 0, w, h, intra, sbh, 0, qp, 0)
+    dq = np.zeros(1, DQTR_DESC); dq[0] = (0, 0, w, w, h, tr_hor, tr_ver, 0, 0, qp)
+    dd = np.zeros(1, DIST_DESC); dd[0] = (0, 0, w, w, w, h, 0, 0)
+    resi, resi2, rec = np.zeros((h, w), np.int16), np.zeros((h, w), np.int16), np.zeros((h, w), np.int16)
+    coef, level, dqc = np.zeros(w * h, np.int32), np.zeros(w * h, np.int32), np.zeros(w * h, np.int32)
+    abs_sum, dist = np.zeros(1, np.uint32), np.zeros(1, np.uint64)
+    o.orc_pelop_batch(3, p(org), p(pred), p(resi), p(band), 1, C.byref(PelopCfg(0, 0, 0, 0, 0, (1 << bd) - 1)))
+    o.orc_tr_fwd_batch(p(resi), p(coef), p(tr), 1, bd)
+    o.orc_quant_batch(p(coef), p(level), p(qd), 1, bd, p(abs_sum))
+    o.orc_dequant_tr_inv_batch(p(level), p(resi2), p(dq), 1, bd, p(dqc))
+    o.orc_pelop_batch(1, p(pred), p(resi2), p(rec), p(band), 1, C.byref(PelopCfg(0, 0, 0, 1, clp[0], clp[1])))
+    o.orc_dist_batch(2, p(org), p(rec), p(dd), 1, p(dist))
+    return level.reshape(h, w), int(abs_sum[0]), rec, int(dist[0])
+
+
+def predict(refs, w, h, mode, filt, clp):
+    src = refs
+    if filt:
+        src = np.zeros_like(refs)
+        oracle().orc_intra_filter_refs(p(refs), p(src), w, h)
+    pred = np.zeros((h, w), np.int16)
+    oracle().orc_intra_pred(p(src), p(pred), w, w, h, mode, clp[0], clp[1])
+    return pred
+
+
+def restate(tc, flags=0, clp=None, mode_list=None, have_pred=True):
+    """the entry over every item -> dict(pred, rec, level: the three buffers after the call; abs_sum, num_sig uint32 [n]; dist uint64 [n]; mode_out)"""
+    clp = clp or (0, (1 << tc.bd) - 1)
+    n = len(tc.items)
+    pred_b, rec_b, level_b = tc.initial()
+    out = dict(pred=pred_b, rec=rec_b, level=level_b, abs_sum=np.full(n, U32_MAX, np.uint32), num_sig=np.full(n, U32_MAX, np.uint32),
+               dist=np.full(n, U64_MAX, np.uint64), mode_out=np.full(n, -1, np.int32))
+    W = tc.base.W
+    for i, it in enumerate(tc.items):
+        r = resolve(tc, i, flags, mode_list, have_pred)
+        if r is None:
+            continue
+        mode, filt = r
+        u = tc.base.pus[int(it["pu"])]
+        w, h = int(it["w"]), int(it["h"])
+        org = tc.base.org[int(u["y"]):int(u["y"]) + h, int(u["x"]):int(u["x"]) + w]
+        if mode == PRED_GIVEN:
+            pred = block(tc.pred0, int(it["pred_off"]), int(it["pred_stride"]), w, h).copy()
+        else:
+            pred = predict(tc.refs_of(int(it["pu"])), w, h, mode, filt, clp)
+            out["mode_out"][i] = mode
+            if flags & WRITE_PRED:
+                block(pred_b, int(it["pred_off"]), int(it["pred_stride"]), w, h)[:] = pred
+        level, abs_sum, rec, dist = code_block(org, pred, tc.bd, int(it["tr_hor"]), int(it["tr_ver"]), int(it["qp"]), int(it["intra"]), int(it["sbh"]), clp)
+        level_b[int(it["level_off"]):int(it["level_off"]) + w * h] = level.reshape(-1)
+        block(rec_b, int(it["rec_off"]), int(it["rec_stride"]), w, h)[:] = rec
+        out["abs_sum"][i], out["num_sig"][i], out["dist"][i] = abs_sum, int(np.count_nonzero(level)), dist
+    return out
+
+
+# ---- builders --------------------------------------------------------------------------------------------------------------------------------------
+def make(base, specs, rng, odd=False, givens=None):
+    """specs: one dict per item with pu and any of mode (default DC), filt, w, h (default the PU's), tr_hor, tr_ver, qp, intra, sbh, row, slot.
+    Every item gets regions of its own in the three buffers with canaries between; odd: odd offsets and strides of the prediction and the
+    reconstruction.  givens: {item: h x w prediction} for PRED_GIVEN items (default: the original plus noise)."""
+    items = np.zeros(len(specs), ITEM)
+    po = ro = 3
+    lo = 4                                                                  # (level regions stay 16-byte aligned, as an encoder's coefficient buffers are)
+    mx = (1 << base.bd) - 1
+    fills = []
+    for i, s in enumerate(specs):
+        u = base.pus[s["pu"]]
+        w, h = int(s.get("w", u["w"])), int(s.get("h", u["h"]))
+        ew, eh = max(1, min(abs(w), 64)), max(1, min(abs(h), 64))            # the room an item gets, whatever its sides claim
+        ps, rs = (ew + 1 + 2 * (i % 3), ew + 3 + 2 * (i % 2)) if odd else (ew, ew + 8 * (i % 2))
+        if odd:
+            po, ro = po | 1, ro | 1
+        items[i] = (s["pu"], s.get("mode", imc.DC), s.get("filt", 0), w, h, s.get("tr_hor", 0), s.get("tr_ver", 0), s.get("qp", 32), s.get("intra", 1),
+                    s.get("sbh", 1), s.get("row", s["pu"]), s.get("slot", 0), po, ps, ro, rs, lo)
+        if items[i]["mode"] == PRED_GIVEN and w == int(u["w"]) and h == int(u["h"]):
+            g = None if givens is None else givens.get(i)
+            if g is None:
+                o = base.org[int(u["y"]):int(u["y"]) + h, int(u["x"]):int(u["x"]) + w].astype(np.int32)
+                g = np.clip(o + rng.integers(-12, 13, (h, w)) * (1 << (base.bd - 8)), 0, mx)
+            fills.append((po, ps, w, h, np.asarray(g, np.int16)))
+        po += eh * ps + 5 + (i % 4)
+        ro += eh * rs + 7 + (i % 3)
+        lo += ew * eh + 4 * (i % 3)
+    pred0 = np.full(po + 8, PRED_CANARY, np.int16)
+    for off, ps, w, h, g in fills:
+        block(pred0, off, ps, w, h)[:] = g
+    return TuCase(base, items, pred0, ro + 8, lo + 8)
+
+
+def fresh_base(rng, bd, shapes, random_avail=True):
+    """planes of intra_mode_cand_cases and one PU per shape, placed outside the flat patch"""
+    rec, org = imc.fresh_planes(rng, bd)
+    return plain_case(bd, rec, org, [imc.place(rng, w, h) + (w, h) for (w, h) in shapes], rng if random_avail else None)
+
+
+def emt_pairs(w, h):
+    """DCT-II, then every DST-VII / DCT-VIII pair where both sides are at most 32"""
+    return [(0, 0)] + ([(a, b) for a in (1, 2) for b in (1, 2)] if w <= 32 and h <= 32 else [])
+
+
+MODES = [0, 1, 2, 18, 34, 50, 66, 3, 7, 11, 21, 29, 33, 45, 57, 65, 61, 5]
+
+
+def shapes_case(bd, seed=None):
+    """every shape, a handful of items each: modes incl. odd and wide-angle ones, both filter decisions, every transform pair, sign hiding and slice type
+    both ways, QPs at both ends of the range and in the middle -> (TuCase, restatement)"""
+    rng = np.random.default_rng(7300 + bd if seed is None else seed)
+    shapes = imc.all_shapes()
+    base = fresh_base(rng, bd, shapes)
+    qps = [0, 22 + 6 * (bd - 8), 27 + 6 * (bd - 8), 32 + 6 * (bd - 8), 17 + 6 * (bd - 8), max_qp(bd)]
+    specs = []
+    k = 0
+    for q, (w, h) in enumerate(shapes):
+        for (th, tv) in emt_pairs(w, h):
+            mode = MODES[k % len(MODES)]
+            if w != h and k % 4 == 1:
+                mode = 3 if w > h else 65                                     # a mode getWideAngle moves
+            specs.append(dict(pu=q, mode=mode, filt=(k // 2) % 2 if k % 5 else int(imc.use_filtered(w, h, mode)), tr_hor=th, tr_ver=tv, qp=qps[k % len(qps)],
+                              intra=k % 2, sbh=(k // 3) % 2))
+            k += 1
+    tc = make(base, specs, rng)
+    want = restate(tc)
+    check_conditions(tc, want)
+    return tc, want
+
+
+def check_conditions(tc, want, from_list=False):
+    """the caps on a random list: at most a quarter of the served items with all-zero levels; at most a quarter of the FROM_LIST slots skipped"""
+    served = want["abs_sum"] != U32_MAX
+    zero = served & (want["num_sig"] == 0)
+    assert zero.sum() * 4 <= served.sum(), (int(zero.sum()), int(served.sum()))
+    if from_list:
+        fl = tc.items["mode"] == FROM_LIST
+        assert (fl & ~served).sum() * 4 <= fl.sum(), (int((fl & ~served).sum()), int(fl.sum()))
+
+
+HANDOVER_SLOTS = 4
+
+
+def handover_case(bd, sqrt_lambda=23.75):
+    """PUs for vvcgpu_intra_mode_cand_batch and, per PU, FROM_LIST items for slots 0 .. HANDOVER_SLOTS - 1 -> (imc case, its restatement, TuCase, restatement);
+    at least one PU's list is empty (PBINTRA cut to 0) and one is full"""
+    rng = np.random.default_rng(7500 + bd)
+    gates = ["off", "uncut", "off", 1, "off", "off", "uncut", 0, "off", "off", "off", 2, "off"]
+    shapes = imc.all_shapes() + [(16, 16), (8, 8), (4, 4), (32, 32), (16, 8)]
+    specs = [(w, h, dict(avail=k % 5, gate=gates[k % len(gates)])) for k, (w, h) in enumerate(shapes)]
+    base = imc.make_case(rng, bd, specs, sqrt_lambda, imc.USE_MPM)
+    cand = imc.restate(base, imc.USE_MPM, sqrt_lambda)
+    sizes = cand["lists"][:, 0]
+    assert (sizes == 0).any() and (sizes >= HANDOVER_SLOTS).any()
+    items = []
+    for q, (w, h, _) in enumerate(specs):
+        pairs = emt_pairs(w, h)
+        for slot in range(HANDOVER_SLOTS):
+            th, tv = pairs[(q + slot) % len(pairs)]
+            items.append(dict(pu=q, mode=FROM_LIST, filt=1 - slot % 2, row=q, slot=slot, tr_hor=th, tr_ver=tv, qp=(22, 27, 32)[(q + slot) % 3] + 6 * (bd - 8),
+                              intra=1, sbh=q % 2))
+    tc = make(base, items, rng)
+    want = restate(tc, mode_list=cand["lists"])
+    check_conditions(tc, want, from_list=True)
+    skipped = want["abs_sum"] == U32_MAX
+    assert skipped.any() and (want["mode_out"][~skipped] >= 0).all()
+    return base, cand, tc, want
+
+
+def explicit_from_lists(tc, lists, flags=0):
+    """the explicit-mode list of a FROM_LIST case, built from downloaded lists: mode and filter decision per item; a slot beyond its list becomes an
+    invalid mode (skipped as well)"""
+    items = tc.items.copy()
+    for i, it in enumerate(items):
+        r = resolve(tc, i, flags, lists)
+        items[i]["mode"], items[i]["filt"] = (67, 0) if r is None else r
+    return TuCase(tc.base, items, tc.pred0, tc.rec_size, tc.level_size)
+
+
+def checker(bd, inverse_pred):
+    """a 64 x 64 PRED_GIVEN item whose original is the full-range checkerboard: against a flat prediction (the residual is +-half the range), or against
+    the opposite checkerboard (+-the full range: the SSE is 64 x 64 x (2^bd - 1)^2, beyond 2^31) -> (TuCase, restatement).  Either residual lies in the
+    band the 64-point transforms zero out."""
+    mx = (1 << bd) - 1
+    yy, xx = np.mgrid[0:imc.H, 0:imc.W]
+    org = (((yy + xx) & 1) * mx).astype(np.int16)
+    base = plain_case(bd, org.copy(), org, [(64, 64, 64, 64)])
+    given = (mx - org[64:128, 64:128]) if inverse_pred else np.full((64, 64), (mx + 1) // 2, np.int16)
+    # (the flat prediction leaves a mean of -1/2: a DC coefficient of 32 in orthonormal terms, below two thirds of the step of QP 45)
+    tc = make(base, [dict(pu=0, mode=PRED_GIVEN, qp=45 + 6 * (bd - 8))], np.random.default_rng(1), givens={0: given})
+    return tc, restate(tc)
+
+
+def bounds_case(bd):
+    """a flat item (abs_sum == 0, dist == 0), an item quantised to zero by its QP with a non-zero residual, and items with num_sig 0, 1, 2, 3 (both sides of
+    g_EmtSigNumThr): PRED_GIVEN items whose prediction differs from the original by a few low-frequency basis patterns -> (TuCase, restatement)"""
+    rng = np.random.default_rng(7700 + bd)
+    mx = (1 << bd) - 1
+    base = fresh_base(rng, bd, [(16, 16)] * 6 + [(8, 8)], random_avail=False)
+    givens, specs = {}, []
+    x = (np.arange(16) + 0.5) / 16
+    waves = [np.ones((16, 16)), np.cos(np.pi * x)[None, :] * np.ones((16, 1)), np.cos(np.pi * x)[:, None] * np.ones((1, 16))]
+    for i in range(4):                                                        # num_sig 0 .. 3: that many basis patterns, each far above the quantiser step
+        u = base.pus[i]
+        o = base.org[int(u["y"]):int(u["y"]) + 16, int(u["x"]):int(u["x"]) + 16].astype(np.float64)
+        o = np.clip(o, 100, mx - 100)
+        base.org[int(u["y"]):int(u["y"]) + 16, int(u["x"]):int(u["x"]) + 16] = o.astype(np.int16)
+        g = base.org[int(u["y"]):int(u["y"]) + 16, int(u["x"]):int(u["x"]) + 16].astype(np.float64)
+        for k in range(i):
+            g = g - 30.0 * waves[k]
+        givens[i] = np.rint(g).astype(np.int16)
+        specs.append(dict(pu=i, mode=PRED_GIVEN, qp=37 + 6 * (bd - 8), sbh=0))
+    u = base.pus[4]                                                           # flat: prediction == original
+    givens[4] = base.org[int(u["y"]):int(u["y"]) + 16, int(u["x"]):int(u["x"]) + 16].copy()
+    specs.append(dict(pu=4, mode=PRED_GIVEN, qp=22 + 6 * (bd - 8)))
+    specs.append(dict(pu=5, mode=PRED_GIVEN, qp=max_qp(bd)))                   # quantised to zero by the QP: the default given prediction is the original plus noise
+    specs.append(dict(pu=6, mode=PRED_GIVEN, qp=max_qp(bd), tr_hor=2, tr_ver=1))
+    tc = make(base, specs, rng, givens=givens)
+    return tc, restate(tc)
+
+
+# ---- the golden file -------------------------------------------------------------------------------------------------------------------------------
+def golden_case(g, bd):
+    k = "bd%d_" % bd
+    base = imc.Case(g[k + "rec"], g[k + "org"], g[k + "pus"].view(imc.PU).reshape(-1), g[k + "avail"], bd)
+    return TuCase(base, g[k + "items"].view(ITEM).reshape(-1), g[k + "pred0"], int(g[k + "rec_size"]), int(g[k + "level_size"])), int(g[k + "flags"])

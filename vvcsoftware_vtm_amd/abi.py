@@ -74,6 +74,9 @@ CCLM_DESC = np.dtype([("luma_off", "<i8"), ("nb_off", "<i8"), ("dst_off", "<i8")
                       ("h", "<i2"), ("above_avail", "i1"), ("left_avail", "i1"), ("reserved", "<i2"), ("reserved2", "<i4", (2,))])
 INTRA_FILL_DESC = np.dtype([("rec_off", "<i8"), ("flags_off", "<i8"), ("ref_off", "<i8"), ("rec_stride", "<i4"), ("w", "<i2"), ("h", "<i2"),
                             ("unit_w", "i1"), ("unit_h", "i1"), ("reserved", "<i2"), ("reserved2", "<i4")])
+# vvcgpu_intra_tu_code_batch: INTRA_DESC.mode values beside 0..66, and the flags
+INTRA_TU_PRED_GIVEN, INTRA_TU_FROM_LIST = -1, -2
+INTRA_TU_WRITE_PRED, INTRA_TU_NO_SMOOTHING = 1, 2
 
 # ---- quantisers ---------------------------------------------------------------------------------------------------------------
 QUANT_DESC = np.dtype([("coeff_off", "<i8"), ("level_off", "<i8"), ("w", "<i2"), ("h", "<i2"), ("intra_slice", "i1"), ("sign_hiding", "i1"),

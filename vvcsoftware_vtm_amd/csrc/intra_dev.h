@@ -1,5 +1,5 @@
-// intra_dev.h -- device functions of the intra sample predictors shared by intra.hip and intracand.hip: the reference-length arithmetic, the staging of
-// the packed reference samples, predIntraAng of one block by a group of lanes, and the reference sample gathering.
+// intra_dev.h -- device functions of the intra sample predictors shared by intra.hip, intracand.hip and intratu.hip: the reference-length arithmetic,
+// the luma filter rule, the staging of the packed reference samples, predIntraAng of one block by a group of lanes, and the reference sample gathering.
 // Reference behaviour: IntraPrediction::predIntraAng CommonLib/IntraPrediction.cpp:251-347, setReferenceArrayLengths :233-249,
 // xFilterReferenceSamples :1071-1104, xFillReferenceSamples :807-1004 (see intra.hip).
 #pragma once
@@ -24,6 +24,24 @@ __device__ __forceinline__ void intra_ref_lengths(int w, int h, int& T, int& L)
   const int ratio = min(2, abs(ilog2(w) - ilog2(h)));
   if (w > h) L += (w >> ratio) - h + ((w + 31) >> 5);
   else if (h > w) T += (h >> ratio) - w + ((h + 31) >> 5);
+}
+
+// useFilteredIntraRefSamples(COMPONENT_Y, pu, modeSpecific = true, pu) :1107-1139 (HM_MDIS_AS_IN_JEM = 1, JVET_K0063_PDPC_SIMP, JVET_K0500_WAIP)
+__device__ __forceinline__ bool intra_use_filtered(int w, int h, int mode, int noSmoothing)
+{
+  if (noSmoothing) return false;
+  const int log2W = ilog2(w), log2H = ilog2(h);
+  if (mode > DC)                                                          // a mode that getWideAngle moves leaves 2..66
+  {
+    const int modeShift = (min(2, abs(log2W - log2H)) << 2) + 2;
+    if ((w > h && mode < 2 + modeShift) || (h > w && mode > VDIA - modeShift)) return true;
+  }
+  if (mode == DC) return false;
+  if (mode == PLANAR) return w * h > 32;
+  const int diff = min(abs(mode - HOR), abs(mode - VER));
+  const int log2Size = (log2W + log2H) >> 1;                             // m_aucIntraFilter[CHANNEL_TYPE_LUMA]: 20, 14, 2, 0, 20 for 4, 8, 16, 32, 64
+  const int thr = log2Size == 2 ? 20 : log2Size == 3 ? 14 : log2Size == 4 ? 2 : log2Size == 5 ? 0 : 20;
+  return diff > thr;
 }
 
 // The packed references of a block (refs[0] = top-left, refs[1 .. T] above, refs[T + 1 .. T + L] left) into the wave's top / left arrays

@@ -66,24 +66,6 @@ struct IcArgs
 
 inline __host__ __device__ bool ic_side_ok(int v) { return v >= 4 && v <= 64 && (v & (v - 1)) == 0; }
 
-// useFilteredIntraRefSamples(COMPONENT_Y, pu, modeSpecific = true, pu) :1107-1139 (HM_MDIS_AS_IN_JEM = 1, JVET_K0063_PDPC_SIMP, JVET_K0500_WAIP)
-__device__ __forceinline__ bool ic_use_filtered(int w, int h, int mode, int noSmoothing)
-{
-  if (noSmoothing) return false;
-  const int log2W = ilog2(w), log2H = ilog2(h);
-  if (mode > DC)                                                          // a mode that getWideAngle moves leaves 2..66
-  {
-    const int modeShift = (min(2, abs(log2W - log2H)) << 2) + 2;
-    if ((w > h && mode < 2 + modeShift) || (h > w && mode > VDIA - modeShift)) return true;
-  }
-  if (mode == DC) return false;
-  if (mode == PLANAR) return w * h > 32;
-  const int diff = min(abs(mode - HOR), abs(mode - VER));
-  const int log2Size = (log2W + log2H) >> 1;                             // m_aucIntraFilter[CHANNEL_TYPE_LUMA]: 20, 14, 2, 0, 20 for 4, 8, 16, 32, 64
-  const int thr = log2Size == 2 ? 20 : log2Size == 3 ? 14 : log2Size == 4 ? 2 : log2Size == 5 ? 0 : 20;
-  return diff > thr;
-}
-
 // updateCandList (UnitTools.h:190-223) on lists in LDS; size: the lists' common size, at most fastNum here
 __device__ __forceinline__ void ic_update_cand_list(int mode, double cost, int* modes, double* costs, int& size, int fastNum)
 {
@@ -109,7 +91,7 @@ template <int G>
 __device__ __forceinline__ void ic_mode(const IcArgs& a, IcState* st, int w, int h, int T, int L, int mode, bool write, const short* refs4, short* mainX,
                                         const short* orgS, short* tile, int lane)
 {
-  const bool filt = ic_use_filtered(w, h, mode, a.noSmoothing);
+  const bool filt = intra_use_filtered(w, h, mode, a.noSmoothing);
   const short* top = refs4 + (filt ? 2 * REF_MAX : 0);
   intra_pred_samples<G>(w, h, mode, T, L, top, top + REF_MAX, mainX, tile, w, a.cmin, a.cmax, lane);
   wave_sync();
@@ -155,7 +137,7 @@ __device__ __forceinline__ void ic_round(const IcArgs& a, IcState* st, int w, in
     for (int k = 0; k < nTodo; k++)
     {
       const int mode = st->todo[k];
-      const short* top = refs4 + (ic_use_filtered(w, h, mode, a.noSmoothing) ? 2 * REF_MAX : 0);
+      const short* top = refs4 + (intra_use_filtered(w, h, mode, a.noSmoothing) ? 2 * REF_MAX : 0);
       intra_pred_samples<64>(w, h, mode, T, L, top, top + REF_MAX, mainBuf + NEG_MAX, tile + y0 * w, w, a.cmin, a.cmax, lane, y0, y0 + bandH);
       wave_sync();
       const unsigned long long sad = satd_block<64, IcLdsPel, IcLdsPel>((IcLdsPel)(orgS + y0 * w), w, (IcLdsPel)(tile + y0 * w), w, w, bandH, lane, 0, h);

@@ -9,7 +9,7 @@ import torch
 from . import capi
 # the struct mirrors live in abi; bench.py, the tests and the tools read them as ops.<NAME>
 from .abi import (AFE_DESC, AFFINE_ITER, AFFINE_ME_ITEM, AFFINE_ME_MAX_STEPS, AFFINE_ME_RESULT, AFFINE_ME_STEP, AFFINE_PU, AFG_DESC, CCLM_DESC, DEPQUANT_DESC, DIST_DESC, DQ_RATES, DQTR_DESC, FRAC_BLK,  # noqa: F401
-                  FRAC_RESULT, IF_DESC, IMV_PU, IMV_RESULT, INTRA_DESC, INTRA_FILL_DESC, INTRA_SATD_DESC, MC_DESC, PELOP_DESC, QUANT_DESC, RC_DESC,
+                  FRAC_RESULT, IF_DESC, IMV_PU, IMV_RESULT, INTRA_DESC, INTRA_FILL_DESC, INTRA_SATD_DESC, INTRA_TU_FROM_LIST, INTRA_TU_NO_SMOOTHING, INTRA_TU_PRED_GIVEN, INTRA_TU_WRITE_PRED, MC_DESC, PELOP_DESC, QUANT_DESC, RC_DESC,
                   RDOQ_DESC, RDOQ_RATES, RDPCM_DESC, SAO_DTYPE, SEARCH_BEST, SEARCH_BLK, TR_DESC, TZ_CFG, TZ_PU, DeblockCfg, MeHierCfg, MvCost,
                   PelopCfg, Planes, AffineMeCfg, BipredMeCfg, BIPRED_ME_ITEM, BIPRED_ME_MAX_PLANES, BIPRED_ME_MAX_REFS, BIPRED_ME_MAX_STEPS, BIPRED_ME_REF,
                   BIPRED_ME_RESULT, BIPRED_ME_STEP, AffineBipredCfg, AFFINE_BIPRED_ITEM, AFFINE_BIPRED_MAX_REFS, AFFINE_BIPRED_MAX_STEPS,
@@ -264,6 +264,22 @@ def intra_mode_cand_batch(org_base, pus_dev, n, pu_ctl, pu_mode_bits, sqrt_lambd
               capi.ptr(pu_ctl), capi.ptr(pu_mode_bits), capi.ptr(pu_inter_had), flags, float(sqrt_lambda), bit_depth, clp[0], clp[1], capi.ptr(satd),
               capi.ptr(lists), capi.ptr(costs), _stream())
     return satd, lists, costs
+
+
+def intra_tu_code_batch(refs_base, preds_dev, org_base, pred_base, rec_base, level_base, tus_dev, n, mode_list=None, flags=0, bit_depth=10, clp=(0, 1023)):
+    """the pixel pass of the intra RD loop for n luma TUs (vvcgpu_intra_tu_code_batch): preds_dev / tus_dev device copies of an INTRA_DESC and an RC_DESC
+    array (item i is the pair), mode_list the lists tensor of intra_mode_cand_batch for INTRA_TU_FROM_LIST items, pred_base None when no item is
+    INTRA_TU_PRED_GIVEN and INTRA_TU_WRITE_PRED is off.
+    -> (abs_sum int32 [n] (bits as uint32), num_sig int32 [n] (bits as uint32), dist int64 [n] (bits as uint64), mode_out int32 [n])"""
+    dv = org_base.device
+    abs_sum = torch.empty(n, dtype=torch.int32, device=dv)                 # every entry is written by the library
+    num_sig = torch.empty(n, dtype=torch.int32, device=dv)
+    dist = torch.empty(n, dtype=torch.int64, device=dv)
+    mode_out = torch.empty(n, dtype=torch.int32, device=dv)
+    capi.call("vvcgpu_intra_tu_code_batch", capi.ptr(refs_base), capi.ptr(preds_dev), capi.ptr(org_base), capi.ptr(pred_base), capi.ptr(rec_base),
+              capi.ptr(level_base), capi.ptr(tus_dev), n, capi.ptr(mode_list), flags, bit_depth, clp[0], clp[1], capi.ptr(abs_sum), capi.ptr(num_sig),
+              capi.ptr(dist), capi.ptr(mode_out), _stream())
+    return abs_sum, num_sig, dist, mode_out
 
 
 def imv_refine_batch(org, ref, pus_dev, n, cfg, use_hadamard=True, weight=1.0):
