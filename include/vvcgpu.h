@@ -48,7 +48,7 @@ int         vvcgpu_set_device(int device);
  * 38 bipred_me_ref, 39 bipred_me_item, 40 bipred_me_cfg, 41 bipred_me_result, 42 bipred_me_step, 44 affine_bipred_ref, 45 affine_bipred_item,
  * 46 affine_bipred_cfg, 47 affine_bipred_result, 48 affine_bipred_step, 50 unipred_me_ref, 51 unipred_me_item, 52 unipred_me_cfg,
  * 53 unipred_me_search, 54 unipred_me_result, 56 affine_unipred_ref, 57 affine_unipred_item, 58 affine_unipred_cfg, 59 affine_unipred_search,
- * 60 affine_unipred_result; -1 for unknown ids (43, 49 and 55 are not assigned and stay unknown). */
+ * 60 affine_unipred_result, 62 intra_chroma_pu; -1 for unknown ids (43, 49, 55 and 61 are not assigned and stay unknown). */
 int         vvcgpu_sizeof(int struct_id);
 
 /* ---- device memory helpers for host-side callers (the reference keeps pictures in host memory; the shim stages them).
@@ -1266,8 +1266,8 @@ int vvcgpu_intra_fill_refs_batch(const vvc_pel* rec_base, const uint8_t* flags_b
  * VVCGPU_E_ARG before any device work: a null required pointer, fill / rec_base / flags_base not all set or all NULL, neither fill nor refs_base,
  * negative n, unknown flag bits, a bad clip range, sqrt_lambda negative, not finite or >= 2^20, a descriptor array that is not 16-byte aligned.
  * n == 0 is a no-op.
- * Not served: lossless DPCM (useDPCMForFirstPassIntraEstimation), INTRA_FULL_SEARCH, the emtUsageFlag == 2 reuse of a saved list (:541-581), chroma,
- * and the RD loop that follows (:620-; its pixel pass: vvcgpu_intra_tu_code_batch).                                                             */
+ * Not served: lossless DPCM (useDPCMForFirstPassIntraEstimation), INTRA_FULL_SEARCH, the emtUsageFlag == 2 reuse of a saved list (:541-581), chroma
+ * (vvcgpu_intra_chroma_code_batch), and the RD loop that follows (:620-; its pixel pass: vvcgpu_intra_tu_code_batch).                                                             */
 #define VVCGPU_INTRA_CAND_USE_MPM       1   /* getFastUDIUseMPMEnabled(): the append of :499-522 */
 #define VVCGPU_INTRA_CAND_NO_SMOOTHING  2   /* sps intraSmoothingDisabledFlag: no mode predicts from filtered references */
 int vvcgpu_intra_mode_cand_batch(
@@ -1309,7 +1309,7 @@ int vvcgpu_intra_mode_cand_batch(
  * be NULL), negative n, unknown flag bits, a bad clip range, a descriptor array that is not 16-byte aligned.  n == 0 is a no-op.
  * Not served: transform skip and RDPCM (their own entries), RDOQ and the DepQuant trellis (vvcgpu_rdoq_batch / vvcgpu_depquant_batch; this is the
  * Quant::quant chain), cross-component prediction, TUs split below the PU (the 64x64 TUs of a 128-sample CU depend on each other's reconstruction),
- * chroma and CCLM prediction (they come in through PRED_GIVEN), the rate and the cost.                                                            */
+ * chroma and CCLM prediction (they come in through PRED_GIVEN; whole chroma PUs: vvcgpu_intra_chroma_code_batch), the rate and the cost.          */
 #define VVCGPU_INTRA_TU_PRED_GIVEN  (-1)   /* preds[i].mode: the prediction is read from pred_base */
 #define VVCGPU_INTRA_TU_FROM_LIST   (-2)   /* preds[i].mode: taken from mode_list */
 #define VVCGPU_INTRA_TU_WRITE_PRED    1    /* flags: predicted items also store their prediction at tus[i].pred_off (the "save" of default0Save1Load2 == 1) */
@@ -1321,6 +1321,68 @@ int vvcgpu_intra_tu_code_batch(
     const int32_t* mode_list,
     int flags, int bit_depth, int clp_min, int clp_max,
     uint32_t* abs_sum, uint32_t* num_sig, uint64_t* dist, int32_t* mode_out, void* stream);
+
+/* N4, the intra chroma mode pass: what the mode loop of IntraSearch::estIntraPredChromaQT (EncoderLib/IntraSearch.cpp:704-852) does in pixels for n
+ * independent chroma PUs of mixed sizes, each one TU per component, 4:2:0, with no host synchronisation inside: per PU up to six candidate modes
+ * (PU::getIntraChromaCandModes, CommonLib/UnitTools.cpp:466-491), each through xRecurIntraChromaCodingQT (:1657-1843) = xIntraCodingTUBlock
+ * (:1147-1316) for Cb and for Cr.  Per PU the references of both components (gathered as by vvcgpu_intra_fill_refs_batch, or given), the two original
+ * blocks and -- when a slot holds the linear model -- the down-sampled luma block (xGetLumaRecPixels, CommonLib/IntraPrediction.cpp:1283-1581) are
+ * staged once; every slot's prediction is formed on the chip (predIntraAng :251-354 from unfiltered references: useFilteredIntraRefSamples :1114 never
+ * filters chroma outside 4:4:4; xGetLMParameters :1597-1857 + predIntraChromaLM :390-403 for LM_CHROMA_IDX, the chroma neighbours being row 0 / column 0
+ * of the references) and goes through the residual chain of vvcgpu_resi_chain_batch (DCT-II both ways, Quant::quant, the 64-point zero-out, the
+ * reconstruction clip) and xGetSSE(org, rec).
+ *
+ * pus[p]       org_off[c] (c = 0 Cb, 1 Cr): the component's original block in org_base, rows org_stride apart.  ref_off[c]: its T + L + 1 packed references
+ *              in refs_base, laid out as for vvcgpu_intra_pred_batch.  luma_off / luma_stride: the co-located luma block in luma_base, the luma
+ *              RECONSTRUCTION, as vvcgpu_cclm_desc's; above_avail / left_avail: as vvcgpu_cclm_desc's (the caller's two flags).  w, h: the chroma block,
+ *              powers of two 2..64.  mode[k], k = 0..5: 0..66 = PU::getFinalIntraMode of the slot (DM resolved by the caller), 67 = LM_CHROMA_IDX,
+ *              -1 = unused (LM disabled, or pruned by the caller).  qp[c]: QpParam::Qp of the component; intra_slice / sign_hiding as vvcgpu_quant_desc.
+ *              cand_off / level_off: the PU's candidate buffers, both multiples of 4: item (k, c) owns the contiguous w x h block at
+ *              cand_off + (2 k + c) w h of pred_base and of cand_rec_base, and at level_off + (2 k + c) w h of level_base.
+ * fill[2 p + c] with rec_base and flags_base, all three or none: exactly what vvcgpu_intra_fill_refs_batch takes (rec_base: the chroma reconstruction), with
+ *              w, h and ref_off equal to the PU's.  The references are gathered once per component and, unless refs_base is NULL, also written there.
+ *              Without fill, refs_base holds them.
+ * runs_host    the PU list is GROUPED BY SHAPE: n_runs triples (w, h, count) as vvcgpu_resi_chain_runs_batch takes them (w, h powers of two 2..64), the
+ *              counts summing to n; a shape appears in at most one run.  The library picks a kernel per shape class on the host (both sides <= 16; a
+ *              side of 32 or 64): at most two launches, all on `stream`.
+ * flags        VVCGPU_INTRA_CHROMA_*.  bit_depth: 8..10, ONE value for luma and chroma (the shipped cfgs have them equal), else VVCGPU_E_UNSUPPORTED.
+ *              clp_min / clp_max: the clip range of prediction and reconstruction.
+ * Outputs per (PU, slot, component), index 12 p + 2 k + c: abs_sum as vvcgpu_resi_chain_batch's; dist = xGetSSE(org, rec) from the reconstruction just
+ * formed, 64-bit; the levels (the zeroed region included) and the reconstruction in the candidate buffers; the prediction too under WRITE_PRED.
+ *
+ * An unused slot has abs_sum = 0xFFFFFFFF and dist = ~0 for both components and nothing touched in the buffers.  So has every slot of a PU outside the
+ * contract: a side outside 2..64 or not a power of two, w x h not its run's, a mode outside -1..67, a slot with 67 and no luma_base, cand_off or level_off not
+ * a multiple of 4, fill[2 p + c] disagreeing with the PU (or with a unit size below 1, or more than 192 units).  Candidate regions of different PUs must
+ * not overlap.  Samples must lie within the bit depth.  Offsets cannot be validated.
+ * VVCGPU_E_ARG before any device work: a null required pointer (pred_base may be NULL without WRITE_PRED, luma_base may be NULL), fill / rec_base /
+ * flags_base not all set or all NULL, neither fill nor refs_base, negative n, n_runs below 1, a run whose shape is not one of the 36 or appears twice, a
+ * negative count, counts not summing to n, unknown flag bits, a bad clip range, a descriptor array that is not 16-byte aligned.  n == 0 is a no-op.
+ * With the caller: getIntraChromaCandModes and the resolution of DM through getFinalIntraMode, isLMCModeEnabled, the rate (xGetIntraFracBitsQT), the cost
+ * compare, the chroma distortion weight and DF_SSE_WTD, the copy of the winner.
+ * Not served: transform-skip candidates (checkTransformSkip: their own entries), cross-component prediction, RDOQ and the DepQuant trellis, 4:2:2 and
+ * 4:4:4, TUs split below the PU.                                                                                                                      */
+#define VVCGPU_INTRA_CHROMA_LM          67   /* mode[k]: LM_CHROMA_IDX */
+#define VVCGPU_INTRA_CHROMA_WRITE_PRED   1   /* flags: every served item also stores its prediction in pred_base */
+struct vvcgpu_intra_chroma_pu {
+  int64_t org_off[2], ref_off[2];       /* samples, relative to org_base / refs_base */
+  int64_t luma_off, cand_off, level_off;
+  int32_t org_stride, luma_stride;
+  int32_t qp[2];
+  int16_t w, h;
+  int8_t  above_avail, left_avail, intra_slice, sign_hiding;
+  int8_t  mode[6];
+  int16_t reserved;
+  int32_t reserved2[2];                 /* sizeof == 96 */
+};
+typedef struct vvcgpu_intra_chroma_pu vvcgpu_intra_chroma_pu;
+int vvcgpu_intra_chroma_code_batch(
+    const vvc_pel* rec_base, const uint8_t* flags_base, const vvcgpu_intra_fill_desc* fill,  /* all three NULL: refs_base holds the references */
+    vvc_pel* refs_base,                        /* read when fill == NULL; with fill: where the gathered references are also written, may be NULL */
+    const vvc_pel* luma_base,                  /* may be NULL: a PU with an LM slot is then skipped */
+    const vvc_pel* org_base, const vvcgpu_intra_chroma_pu* pus, int n, const int32_t* runs_host, int n_runs,
+    vvc_pel* pred_base, vvc_pel* cand_rec_base, vvc_coef* level_base,
+    int flags, int bit_depth, int clp_min, int clp_max,
+    uint32_t* abs_sum, uint64_t* dist, void* stream);
 
 /* N4, CCLM: cross-component linear model prediction of a chroma block  (IntraPrediction::xGetLumaRecPixels :1283-1581, the
  * JVET_K0190 branch, + xGetLMParameters :1597-1857 + predIntraChromaLM :390-403).  4:2:0 only.  luma_off: the co-located luma

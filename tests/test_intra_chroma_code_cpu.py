@@ -1,0 +1,110 @@
+"""vvcgpu_intra_chroma_code_batch without a GPU: the restatement of the pass (tests/intra_chroma_code_cases.py) reproduces the compiled reference's values
+(tests/golden/intra_chroma_code.npz), the golden list meets the conditions its cases are chosen by, the restatement keeps the contract, the bound case is
+beyond a signed 32-bit sum, the struct mirror has the C compiler's layout, and the argument checks that come before any device work answer as the header says."""
+import ctypes as C
+import os
+import shlex
+import subprocess
+
+import numpy as np
+import pytest
+
+import intra_chroma_code_cases as icc
+from vvcsoftware_vtm_amd import abi, capi
+
+
+@pytest.mark.parametrize("bd", [8, 10])
+def test_restatement_reproduces_the_golden_file(bd):
+    g = np.load(icc.GOLDEN)
+    case, flags = icc.golden_case(g, bd)
+    assert flags == icc.WRITE_PRED
+    want = icc.restate(case, flags)
+    for name in ("refs", "pred", "rec", "level", "abs_sum", "dist"):
+        assert np.array_equal(want[name], g["bd%d_want_%s" % (bd, name)]), name
+    icc.conditions(case, want)
+    # an unused slot carries the markers and leaves its regions as they were
+    u = case.pus[-1]
+    k = [int(m) for m in u["mode"]].index(-1)
+    assert (want["abs_sum"][-1, k] == icc.U32_MAX).all() and (want["dist"][-1, k] == icc.U64_MAX).all()
+    co, size = int(u["cand_off"]) + 2 * k * int(u["w"]) * int(u["h"]), 2 * int(u["w"]) * int(u["h"])
+    assert (want["rec"][co:co + size] == icc.REC_CANARY).all() and (want["pred"][co:co + size] == icc.PRED_CANARY).all()
+
+
+def test_golden_file_holds_data_only_and_stays_small():
+    assert os.path.getsize(icc.GOLDEN) <= 400 * 1024
+    g = np.load(icc.GOLDEN, allow_pickle=False)
+    assert all(g[k].dtype.kind in "iu" for k in g.files)
+
+
+def test_contract_of_the_restatement():
+    """what the restatement skips: a PU whose shape is not its run's, a mode outside -1..67, an LM slot without a luma plane, a fill descriptor that
+    disagrees; and a given reference buffer stays as it is"""
+    rng = np.random.default_rng(3)
+    case = icc.make(rng, 10, [dict(w=4, h=4, modes=icc.cand_modes(50, lm=False)), dict(w=8, h=8), dict(w=8, h=8), dict(w=16, h=16)])     # (make groups by shape)
+    full = icc.restate(case)
+    assert (full["abs_sum"] != icc.U32_MAX).sum() == 2 * (6 + 5 + 6 + 6)
+    bad = icc.Case(case.bd, case.luma, case.rec, case.org, case.avail, case.pus.copy(), case.fill.copy(), case.runs, case.refs_size, case.cand_size, case.level_size)
+    bad.pus["w"][1] = 16
+    bad.pus["mode"][2][2] = 68
+    bad.fill["h"][2 * 3 + 1] = 8
+    got = icc.restate(bad)
+    assert (got["abs_sum"][1:] == icc.U32_MAX).all() and np.array_equal(got["abs_sum"][0], full["abs_sum"][0])
+    no_luma = icc.restate(case, have_luma=False)
+    assert (no_luma["abs_sum"][1:] == icc.U32_MAX).all() and np.array_equal(no_luma["abs_sum"][0], full["abs_sum"][0])
+    given = icc.restate(case, gather=False, refs_given=full["refs"])
+    for name in ("refs", "rec", "level", "abs_sum", "dist"):
+        assert np.array_equal(given[name], full[name]), name
+
+
+def test_bound_case_exceeds_a_signed_32_bit_sum():
+    case, want = icc.bound_case(10)
+    assert int(want["dist"][0, 4, 0]) > 1 << 31 and int(want["dist"][0, 4, 1]) > 1 << 31
+    assert (want["abs_sum"][0, [1, 2, 3, 5]] == icc.U32_MAX).all()
+
+
+def test_struct_mirror_matches_the_header(tmp_path):
+    """sizeof / offsetof of vvcgpu_intra_chroma_pu by the C compiler == abi.INTRA_CHROMA_PU, field by field; the library reports the same size"""
+    m = abi.INTRA_CHROMA_PU
+    src = tmp_path / "layout.c"
+    src.write_text("#include <stddef.h>\n#include <stdio.h>\n#include \"vvcgpu.h\"\nint main(void)\n{\n"
+                   '  printf("%zu\\n", sizeof(vvcgpu_intra_chroma_pu));\n'
+                   + "".join('  printf("%%s %%zu %%zu\\n", "%s", offsetof(vvcgpu_intra_chroma_pu, %s), sizeof(((vvcgpu_intra_chroma_pu*)0)->%s));\n' % (f, f, f) for f in m.names)
+                   + '  printf("%d %d\\n", VVCGPU_INTRA_CHROMA_LM, VVCGPU_INTRA_CHROMA_WRITE_PRED);\n  return 0;\n}\n')
+    exe = tmp_path / "layout"
+    cc = shlex.split(os.environ.get("CC", "cc"))
+    r = subprocess.run(cc + ["-I", os.path.dirname(capi.HEADER), str(src), "-o", str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    lines = subprocess.check_output([str(exe)], text=True).splitlines()
+    assert int(lines[0]) == m.itemsize == 96 and m.itemsize % 16 == 0
+    for line, name in zip(lines[1:-1], m.names):
+        f, off, size = line.split()
+        assert (f, int(off), int(size)) == (name, m.fields[name][1], m.fields[name][0].itemsize), line
+    assert lines[-1].split() == [str(abi.INTRA_CHROMA_LM), str(abi.INTRA_CHROMA_WRITE_PRED)]
+    assert capi.lib().vvcgpu_sizeof(62) == 96
+
+
+def call(**kw):
+    """the entry with arguments that pass every check (dummy non-null pointers: no check dereferences one), changed by kw"""
+    runs = np.array(kw.pop("runs", [[8, 8, 3]]), np.int32)
+    a = dict(rec=None, flags_base=None, fill=None, refs=C.c_void_p(64), luma=None, org=C.c_void_p(64), pus=C.c_void_p(64), n=3, n_runs=len(runs), pred=None,
+             cand_rec=C.c_void_p(64), level=C.c_void_p(64), flags=0, bd=10, cmin=0, cmax=1023, abs_sum=C.c_void_p(64), dist=C.c_void_p(64), runs_ptr=runs.ctypes.data_as(C.c_void_p))
+    a.update(kw)
+    return capi.lib().vvcgpu_intra_chroma_code_batch(a["rec"], a["flags_base"], a["fill"], a["refs"], a["luma"], a["org"], a["pus"], a["n"], a["runs_ptr"], a["n_runs"],
+                                                     a["pred"], a["cand_rec"], a["level"], a["flags"], a["bd"], a["cmin"], a["cmax"], a["abs_sum"], a["dist"], None)
+
+
+E_ARG_CASES = [dict(n=-1), dict(org=None), dict(pus=None), dict(cand_rec=None), dict(level=None), dict(abs_sum=None), dict(dist=None), dict(runs_ptr=None),
+               dict(refs=None), dict(fill=C.c_void_p(64)), dict(rec=C.c_void_p(64)), dict(flags_base=C.c_void_p(64), fill=C.c_void_p(64)), dict(flags=2), dict(flags=1),
+               dict(cmin=5, cmax=4), dict(cmax=40000), dict(pus=C.c_void_p(72)), dict(rec=C.c_void_p(64), flags_base=C.c_void_p(64), fill=C.c_void_p(72)),
+               dict(n_runs=0), dict(runs=[[8, 8, 2]]), dict(runs=[[8, 8, 4]]), dict(runs=[[8, 8, -1], [4, 4, 4]]), dict(runs=[[8, 8, 1], [8, 8, 2]]),
+               dict(runs=[[128, 8, 3]]), dict(runs=[[8, 3, 3]]), dict(runs=[[1, 8, 3]])]
+
+
+def test_argument_errors_come_before_any_device_work():
+    lib = capi.lib()
+    for kw in E_ARG_CASES:
+        assert call(**dict(kw)) == -1, kw
+        assert b"intra_chroma_code_batch" in lib.vvcgpu_last_error(), kw
+    for bd in (7, 11, 12):
+        assert call(bd=bd) == -3, bd
+    assert call(n=0) == 0 and call(n=0, org=None, pus=None, runs_ptr=None) == 0

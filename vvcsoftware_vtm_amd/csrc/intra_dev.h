@@ -1,7 +1,8 @@
-// intra_dev.h -- device functions of the intra sample predictors shared by intra.hip, intracand.hip and intratu.hip: the reference-length arithmetic,
-// the luma filter rule, the staging of the packed reference samples, predIntraAng of one block by a group of lanes, and the reference sample gathering.
+// intra_dev.h -- device functions of the intra sample predictors shared by intra.hip, intracand.hip, intratu.hip and intrachroma.hip: the reference-length
+// arithmetic, the luma filter rule, the staging of the packed reference samples, predIntraAng of one block by a group of lanes (sides 2..64: chroma's
+// 2-sample sides run the same code), the reference sample gathering, and the cross-component linear model (luma down-sampling, parameters).
 // Reference behaviour: IntraPrediction::predIntraAng CommonLib/IntraPrediction.cpp:251-347, setReferenceArrayLengths :233-249,
-// xFilterReferenceSamples :1071-1104, xFillReferenceSamples :807-1004 (see intra.hip).
+// xFilterReferenceSamples :1071-1104, xFillReferenceSamples :807-1004, xGetLumaRecPixels :1283-1581, xGetLMParameters :1597-1857 (see intra.hip).
 #pragma once
 #include "common.h"
 
@@ -240,6 +241,85 @@ __device__ __forceinline__ void intra_fill_refs_block(const Pel* __restrict__ re
       else v = rec[-rs + (s - leftUnits - 1) * uw + o];
     }
     refs[i] = (Pel)v;
+  }
+}
+
+// ---- CCLM (JVET_K0190): xGetLumaRecPixels :1283-1581 + xGetLMParameters :1597-1857 -------------------------------------------------------------------
+__device__ __forceinline__ int floor_log2(unsigned x) { return 31 - __clz((int)x); }     // x > 0
+
+// one down-sampled luma sample at p (the co-located luma position of a chroma sample; rs: luma stride): [1 2 1; 1 2 1] / 8, or the two-sample form of
+// the first column when the left neighbour is not available (:1381-1395, :1455-1469, :1505-1560)
+__device__ __forceinline__ int cclm_down(const Pel* p, int rs, bool two)
+{
+  return two ? (p[0] + p[rs] + 1) >> 1 : (p[0] * 2 + p[-1] + p[1] + p[rs] * 2 + p[rs - 1] + p[rs + 1] + 4) >> 3;
+}
+
+// xGetLMParameters of one w x h chroma block by one wave: lumaAbove(idx) / lumaLeft(idx) return the down-sampled luma neighbour above column idx / left
+// of row idx, nbAbove / nbLeft hold the reconstructed chroma neighbours of the component.  -> a, bb, shift of the model (a * s >> shift) + bb.
+template <class LA, class LL>
+__device__ __forceinline__ void cclm_params(int w, int h, bool aboveAvail, bool leftAvail, LA lumaAbove, LL lumaLeft, const Pel* nbAbove, const Pel* nbLeft,
+                                            int bdLuma, int bdChroma, int lane, int& a, int& bb, int& shift)
+{
+  a = 0; bb = 1 << (bdChroma - 1); shift = 0;
+  if (aboveAvail || leftAvail)
+  {
+    int x = 0, y = 0, xx = 0, xy = 0, countShift = 0;
+    const int minDim = (leftAvail && aboveAvail) ? min(w, h) : (leftAvail ? h : w);
+    const int lgMin = floor_log2((unsigned)minDim);
+    if (aboveAvail)
+    {
+      for (int j = lane; j < minDim; j += 64)
+      {
+        const int idx = (j * w) >> lgMin;
+        const int s = lumaAbove(idx), c = nbAbove[idx];
+        x += s; y += c; xx += s * s; xy += s * c;
+      }
+      countShift = lgMin;
+    }
+    if (leftAvail)
+    {
+      for (int i = lane; i < minDim; i += 64)
+      {
+        const int idx = (i * h) >> lgMin;
+        const int s = lumaLeft(idx), c = nbLeft[idx];
+        x += s; y += c; xx += s * s; xy += s * c;
+      }
+      countShift += aboveAvail ? 1 : lgMin;
+    }
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) { x += __shfl_xor(x, m); y += __shfl_xor(y, m); xx += __shfl_xor(xx, m); xy += __shfl_xor(xy, m); }
+    const int tempShift = bdChroma + countShift - 15;
+    if (tempShift > 0)
+    {
+      const int r = 1 << (tempShift - 1);
+      x = (x + r) >> tempShift; y = (y + r) >> tempShift; xx = (xx + r) >> tempShift; xy = (xy + r) >> tempShift;
+      countShift -= tempShift;
+    }
+    const int avgX = x >> countShift, avgY = y >> countShift;
+    const int rErrX = x & ((1 << countShift) - 1), rErrY = y & ((1 << countShift) - 1);
+    const int iB = 7;
+    shift = 13 - iB;
+    if (countShift == 0) { a = 0; bb = 1 << (bdChroma - 1); shift = 0; }
+    else
+    {
+      const int a1 = xy - ((avgX * avgY) << countShift) - avgX * rErrY - avgY * rErrX;
+      const int a2 = xx - ((avgX * avgX) << countShift) - 2 * avgX * rErrX;
+      int sA1 = a1 == 0 ? 0 : floor_log2((unsigned)abs(a1)) - (bdChroma - 2);
+      int sA2 = a2 == 0 ? 0 : floor_log2((unsigned)abs(a2)) - 5;
+      sA1 = max(sA1, 0); sA2 = max(sA2, 0);
+      const int sA = sA2 + (bdChroma + 4) - shift - sA1;
+      const int a2s = a2 >> sA2, a1s = a1 >> sA1;
+      if (a2s >= 32) a = (int)((unsigned)a1s * (unsigned)(((1 << (bdLuma + 4)) + a2s / 2) / a2s));     // m_auShiftLM[a2s - 32]
+      else a = 0;
+      if (sA < 0) a = (int)((unsigned)a << -sA); else a = a >> sA;
+      a = min(max(a, -(1 << (15 - iB))), (1 << (15 - iB)) - 1);
+      a = a * (1 << iB);
+      int nn = 0;
+      if (a != 0) nn = (short)(floor_log2((unsigned)(abs(a) + ((a < 0 ? -1 : 1) - 1) / 2)) - 5);
+      shift = (shift + iB) - nn;
+      a = a >> nn;
+      bb = avgY - ((a * avgX) >> shift);
+    }
   }
 }
 

@@ -340,6 +340,7 @@ int vvcgpu_sizeof(int id)
   case 58: return (int)sizeof(vvcgpu_affine_unipred_cfg);
   case 59: return (int)sizeof(vvcgpu_affine_unipred_search);
   case 60: return (int)sizeof(vvcgpu_affine_unipred_result);
+  case 62: return (int)sizeof(vvcgpu_intra_chroma_pu);
   default: return -1;
   }
 }

@@ -9,7 +9,7 @@ import torch
 from . import capi
 # the struct mirrors live in abi; bench.py, the tests and the tools read them as ops.<NAME>
 from .abi import (AFE_DESC, AFFINE_ITER, AFFINE_ME_ITEM, AFFINE_ME_MAX_STEPS, AFFINE_ME_RESULT, AFFINE_ME_STEP, AFFINE_PU, AFG_DESC, CCLM_DESC, DEPQUANT_DESC, DIST_DESC, DQ_RATES, DQTR_DESC, FRAC_BLK,  # noqa: F401
-                  FRAC_RESULT, IF_DESC, IMV_PU, IMV_RESULT, INTRA_DESC, INTRA_FILL_DESC, INTRA_SATD_DESC, INTRA_TU_FROM_LIST, INTRA_TU_NO_SMOOTHING, INTRA_TU_PRED_GIVEN, INTRA_TU_WRITE_PRED, MC_DESC, PELOP_DESC, QUANT_DESC, RC_DESC,
+                  FRAC_RESULT, IF_DESC, IMV_PU, IMV_RESULT, INTRA_DESC, INTRA_FILL_DESC, INTRA_SATD_DESC, INTRA_CHROMA_LM, INTRA_CHROMA_PU, INTRA_CHROMA_WRITE_PRED, INTRA_TU_FROM_LIST, INTRA_TU_NO_SMOOTHING, INTRA_TU_PRED_GIVEN, INTRA_TU_WRITE_PRED, MC_DESC, PELOP_DESC, QUANT_DESC, RC_DESC,
                   RDOQ_DESC, RDOQ_RATES, RDPCM_DESC, SAO_DTYPE, SEARCH_BEST, SEARCH_BLK, TR_DESC, TZ_CFG, TZ_PU, DeblockCfg, MeHierCfg, MvCost,
                   PelopCfg, Planes, AffineMeCfg, BipredMeCfg, BIPRED_ME_ITEM, BIPRED_ME_MAX_PLANES, BIPRED_ME_MAX_REFS, BIPRED_ME_MAX_STEPS, BIPRED_ME_REF,
                   BIPRED_ME_RESULT, BIPRED_ME_STEP, AffineBipredCfg, AFFINE_BIPRED_ITEM, AFFINE_BIPRED_MAX_REFS, AFFINE_BIPRED_MAX_STEPS,
@@ -280,6 +280,23 @@ def intra_tu_code_batch(refs_base, preds_dev, org_base, pred_base, rec_base, lev
               capi.ptr(level_base), capi.ptr(tus_dev), n, capi.ptr(mode_list), flags, bit_depth, clp[0], clp[1], capi.ptr(abs_sum), capi.ptr(num_sig),
               capi.ptr(dist), capi.ptr(mode_out), _stream())
     return abs_sum, num_sig, dist, mode_out
+
+
+def intra_chroma_code_batch(org_base, pus_dev, n, runs, cand_rec_base, level_base, refs_base=None, fill=None, luma_base=None, pred_base=None, flags=0,
+                            bit_depth=10, clp=(0, 1023)):
+    """the intra chroma mode pass of n chroma PUs grouped by shape (vvcgpu_intra_chroma_code_batch): pus_dev a device copy of an INTRA_CHROMA_PU array, runs
+    the (w, h, count) triples of the list.  fill = (rec_base, flags_base, a device copy of an INTRA_FILL_DESC array, two per PU) gathers the references
+    first (refs_base, if given, receives them); without fill, refs_base holds them.  luma_base: the luma reconstruction, for PUs with an LM slot.
+    -> (abs_sum int32 [n][6][2] (bits as uint32), dist int64 [n][6][2] (bits as uint64))"""
+    dv = org_base.device
+    abs_sum = torch.empty((n, 6, 2), dtype=torch.int32, device=dv)         # every entry is written by the library
+    dist = torch.empty((n, 6, 2), dtype=torch.int64, device=dv)
+    r = np.ascontiguousarray(np.asarray(runs, np.int32).reshape(-1, 3))
+    rec, flg, fd = fill if fill is not None else (None, None, None)
+    capi.call("vvcgpu_intra_chroma_code_batch", capi.ptr(rec), capi.ptr(flg), capi.ptr(fd), capi.ptr(refs_base), capi.ptr(luma_base), capi.ptr(org_base),
+              capi.ptr(pus_dev), n, r.ctypes.data_as(C.c_void_p), len(r), capi.ptr(pred_base), capi.ptr(cand_rec_base), capi.ptr(level_base), flags,
+              bit_depth, clp[0], clp[1], capi.ptr(abs_sum), capi.ptr(dist), _stream())
+    return abs_sum, dist
 
 
 def imv_refine_batch(org, ref, pus_dev, n, cfg, use_hadamard=True, weight=1.0):
