@@ -48,7 +48,7 @@ int         vvcgpu_set_device(int device);
  * 38 bipred_me_ref, 39 bipred_me_item, 40 bipred_me_cfg, 41 bipred_me_result, 42 bipred_me_step, 44 affine_bipred_ref, 45 affine_bipred_item,
  * 46 affine_bipred_cfg, 47 affine_bipred_result, 48 affine_bipred_step, 50 unipred_me_ref, 51 unipred_me_item, 52 unipred_me_cfg,
  * 53 unipred_me_search, 54 unipred_me_result, 56 affine_unipred_ref, 57 affine_unipred_item, 58 affine_unipred_cfg, 59 affine_unipred_search,
- * 60 affine_unipred_result, 62 intra_chroma_pu; -1 for unknown ids (43, 49, 55 and 61 are not assigned and stay unknown). */
+ * 60 affine_unipred_result, 62 intra_chroma_pu, 63 inter_resi_item; -1 for unknown ids (43, 49, 55 and 61 are not assigned and stay unknown). */
 int         vvcgpu_sizeof(int struct_id);
 
 /* ---- device memory helpers for host-side callers (the reference keeps pictures in host memory; the shim stages them).
@@ -1117,6 +1117,76 @@ int vvcgpu_merge_cand_batch(const vvc_pel* ref0_base, const vvc_pel* ref1_base, 
                             const vvcgpu_dist_desc* cand_dist, int n_cand, int n_comp, const int32_t* pu_cand_first, int n_pu,
                             int max_num_merge_cand, int use_hadamard, double sqrt_lambda, int bit_depth, int clp_min, int clp_max,
                             uint64_t* dist_out, uint64_t* sse_out, double* cost_out, int32_t* rd_list_out, void* stream);
+
+/* ---- the inter residual pixel pass  (InterSearch::encodeResAndCalcRdInterCU, EncoderLib/InterSearch.cpp:4752-4909, with the "check full" part of
+ *          xEstimateInterResidualQT :4254-4634; reached from xCheckRDCostMerge2Nx2N's second pass and from xEncodeInterResidual after predInterSearch) ----
+ * One call serves n independent transform blocks -- an item is a (TU, component) pair of an inter CU, sides powers of two 2..64: a 4:2:0 CU is three
+ * items, a 128-sample CU its four 64x64 luma TUs and its 32x32 chroma TUs as items of their own (for inter CUs they do not depend on each other) -- in
+ * ONE launch on the caller's stream, no host synchronisation inside.  Per item
+ *   orgResi   = org - pred, formed once (cs.getResiBuf().copyFrom(org); subtract(pred), :4816-4822);
+ *   zero_dist = xGetSSE(0, orgResi) = sum orgResi^2: nonCoeffDist of :4424, the CU's zeroDistortion and the skip leg's distortion (the prediction is
+ *               already clipped);
+ *   and for each of the up to VVCGPU_INTER_RESI_SLOTS transform candidates tr[k] of the TU
+ *   transformNxN :4409 (xT TrQuant.cpp:694-739 or xTransformSkip :1112-1163, Quant::quant Quant.cpp:721-834 with rounding 171 / 85 by intra_slice and
+ *               xSignBitHidingHDQ :142-273 by sign_hiding), invTransformNxN :4497 (Quant::dequant :277-428, xIT :743-791 or xITransformSkip :795-847);
+ *   dist_resi = xGetSSE(orgResi, resi') on the UNCLIPPED resi': currCompDist of :4504 -- the loop decides in the residual domain ("previously unclipped
+ *               reconstruction values were used", :4882), and rec - pred is not resi' wherever the clip bites;
+ *   dist_rec  = xGetSSE(org, clip(pred + resi')): the CU's finalDistortion term (:4880-4900).
+ * orgResi, the coefficients and the de-quantised coefficients never go through device memory; the original and the prediction of an item are read once
+ * for all its slots.
+ *
+ * items[i]     org_off / org_stride: the original block in org_base.  pred_off / pred_stride: the prediction block in pred_base -- the output of
+ *              vvcgpu_mc_batch, or a merge candidate's block.  list_row >= 0 (a LIST item): the prediction is that of merge candidate
+ *              c = rd_list[8 list_row + 1 + list_slot] at pred_off + c pred_cand_pitch, rd_list being rd_list_out of vvcgpu_merge_cand_batch, consumed
+ *              where it lies (same stream, no download); the item is served when 0 <= list_slot < rd_list[8 list_row] and 0 <= c <= 6, else skipped.
+ *              list_row < 0: pred_off as given.  w, h: powers of two 2..64.  qp: QpParam::Qp of the component; intra_slice / sign_hiding as
+ *              vvcgpu_quant_desc.  tr[k], k = 0..5: -1 unused; tr_hor + 3 tr_ver with 0 DCT-II, 1 DCT-VIII, 2 DST-VII (0 = DCT-II both ways; 4, 5, 7, 8 the
+ *              four pairs of g_aiTrSubsetInter under cu.emtFlag); VVCGPU_INTER_RESI_TS transform skip.  Transform skip is served on blocks with BOTH
+ *              SIDES <= 4 (Log2MaxTransformSkipBlockSize 2, the shipped cfgs' value; 2-wide chroma blocks included), on no larger block.
+ *              cand_off / level_off, both multiples of 4: slot k owns the w h contiguous samples at cand_off + k w h of resi_base (and of rec_base) and
+ *              the w h levels at level_off + k w h of level_base.
+ * flags        VVCGPU_INTER_RESI_*.  bit_depth 8..10 (else VVCGPU_E_UNSUPPORTED).  clp_min / clp_max: the clip range of the reconstruction.
+ * Outputs per (item, slot), index 6 i + k: abs_sum as vvcgpu_resi_chain_batch's; dist_resi and dist_rec, each what vvcgpu_dist_batch kind 2 returns for
+ * the two blocks (64-bit sums; one squared term stays below 2^31: |orgResi - resi'| <= 1023 + 32768).  Per item: zero_dist[i].  The levels (the zeroed
+ * region of a 64-point side included) and resi' go to the slot's candidate buffers, the reconstruction to rec_base only under
+ * VVCGPU_INTER_RESI_WRITE_REC (rec_base may be NULL otherwise).
+ * A slot whose levels are all zero is still finished: resi' is stored as zeros, dist_resi == zero_dist, dist_rec == xGetSSE(org, clip(pred)); the
+ * reference takes its else branch at :4521, the host does the same from abs_sum == 0.
+ *
+ * A skipped item or slot has abs_sum = 0xFFFFFFFF and both distortions ~0, a skipped item zero_dist = ~0 as well; nothing is touched in the three
+ * buffers.  An ITEM is skipped when a side is outside 2..64 or not a power of two, when it is a list item and rd_list is NULL or the slot or the
+ * candidate is out of range, when cand_off or level_off is not a multiple of 4.  A SLOT is skipped when it is -1, its code is outside -1..9, it puts a
+ * transform other than DCT-II on a 64-point side or DCT-VIII / DST-VII on a side of 2, or it is a transform-skip slot on a block with a side above 4.
+ * Candidate regions of different items must not overlap.  Samples must lie within the bit depth.  Offsets cannot be validated; an item outside the
+ * contract is never a fault.
+ * VVCGPU_E_ARG before any device work: a null required pointer (rd_list may be NULL; rec_base may be NULL without WRITE_REC), negative n, unknown flag
+ * bits, a bad clip range, an item array that is not 16-byte aligned.  n == 0 is a no-op.
+ * With the caller: every CABAC rate (cbf_comp, residual_coding, rqt_root_cbf, xGetSymbolFracBitsInter), the cost compares and the forced-null rule
+ * (:4531-4568), the root-cbf decision (:4853) and the copy of the winner, the chroma distortion weight and DF_SSE_WTD.
+ * Not served: cross-component prediction, RDPCM and lossless (range extensions, off in the shipped cfgs), RDOQ and the DepQuant trellis
+ * (vvcgpu_rdoq_batch / vvcgpu_depquant_batch; this is the Quant::quant chain, as in every fused entry).                                              */
+#define VVCGPU_INTER_RESI_SLOTS      6
+#define VVCGPU_INTER_RESI_TS         9     /* tr[k]: transform skip */
+#define VVCGPU_INTER_RESI_WRITE_REC  1     /* flags: every served slot also stores clip(pred + resi') in rec_base */
+struct vvcgpu_inter_resi_item {
+  int64_t org_off, pred_off;               /* samples from org_base / pred_base */
+  int64_t pred_cand_pitch;                 /* list items: samples between the blocks of successive merge candidates of this component in pred_base */
+  int64_t cand_off, level_off;             /* slot k: w h samples at cand_off + k w h of resi_base (and rec_base), w h levels at level_off + k w h */
+  int32_t org_stride, pred_stride;
+  int32_t qp;                              /* QpParam::Qp of the component */
+  int32_t list_row;                        /* < 0: pred_off as given; >= 0: a row of rd_list */
+  int16_t w, h;
+  int8_t  list_slot, intra_slice, sign_hiding, reserved;
+  int8_t  tr[VVCGPU_INTER_RESI_SLOTS];     /* -1 unused; tr_hor + 3 tr_ver (each 0 DCT-II, 1 DCT-VIII, 2 DST-VII); 9 transform skip */
+  int8_t  reserved1[2];
+  int32_t reserved2[2];                    /* sizeof == 80 */
+};
+typedef struct vvcgpu_inter_resi_item vvcgpu_inter_resi_item;
+int vvcgpu_inter_resi_code_batch(const vvc_pel* org_base, const vvc_pel* pred_base, const vvcgpu_inter_resi_item* items, int n,
+                                 const int32_t* rd_list,                 /* rd_list_out of vvcgpu_merge_cand_batch, may be NULL */
+                                 vvc_pel* resi_base, vvc_pel* rec_base, vvc_coef* level_base,
+                                 int flags, int bit_depth, int clp_min, int clp_max,
+                                 uint32_t* abs_sum, uint64_t* dist_resi, uint64_t* dist_rec, uint64_t* zero_dist, void* stream);
 
 /* ---- N2 ("next" row): integer-sample TZ search of whole PUs, on the device  (InterSearch::xTZSearch,
  *          EncoderLib/InterSearch.cpp:1971-2252, with xTZSearchHelp :249-343, xTZ2PointSearch :349-374,

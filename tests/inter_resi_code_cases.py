@@ -1,0 +1,415 @@
+"""The inter residual pixel pass (InterSearch::encodeResAndCalcRdInterCU, InterSearch.cpp:4752-4909, with the "check full" part of xEstimateInterResidualQT,
+:4254-4634) restated for the tests of vvcgpu_inter_resi_code_batch from oracle steps that are each pinned to the compiled reference: orc_pelop_batch
+(subtract), orc_tr_fwd_batch (tr_hor = 3: transform skip), orc_quant_batch, orc_dequant_tr_inv_batch, orc_pelop_batch (reconstruct), orc_dist_batch kind 2 on
+residual blocks and on a zero block.  The slot rules, the list look-up and the skip markers are written here from the entry's contract.  Also the case
+builders: items with candidate buffers of their own for resi', reconstruction and levels, canaries between them, and rd_list rows.
+numpy only: the generator and the CPU tests load this file without torch."""
+import ctypes as C
+import os
+
+import numpy as np
+
+from oraclelib import oracle, p
+from vvcsoftware_vtm_amd import abi
+from vvcsoftware_vtm_amd.abi import DIST_DESC, DQTR_DESC, PELOP_DESC, QUANT_DESC, TR_DESC, PelopCfg
+
+ITEM = abi.INTER_RESI_ITEM
+SLOTS, TS, WRITE_REC = abi.INTER_RESI_SLOTS, abi.INTER_RESI_TS, abi.INTER_RESI_WRITE_REC
+U32_MAX, U64_MAX = 0xFFFFFFFF, 0xFFFFFFFFFFFFFFFF
+RESI_CANARY, REC_CANARY, LEVEL_CANARY = 0x5A5A, -21846, 0x5A5A5A5A
+PRED_GUARD = -5
+SIDES = (2, 4, 8, 16, 32, 64)
+EMT = (4, 5, 7, 8)                                                          # tr_hor + 3 tr_ver of the four pairs of g_aiTrSubsetInter: {DCT-VIII, DST-VII}^2
+W, H = 256, 192                                                             # the original plane of the seeded cases
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "inter_resi_code.npz")
+
+
+def all_shapes():
+    return [(w, h) for w in SIDES for h in SIDES]
+
+
+def max_qp(bd):
+    """the largest QpParam::Qp of the component: 63 (JVET_K0251) plus the bit-depth offset"""
+    return 63 + 6 * (bd - 8)
+
+
+def side_ok(v):
+    return 2 <= v <= 64 and (v & (v - 1)) == 0
+
+
+def slot_served(w, h, code):
+    """is transform candidate `code` of a w x h block served?"""
+    if code == TS:
+        return w <= 4 and h <= 4
+    if not 0 <= code < 9:
+        return False
+    th, tv = code % 3, code // 3
+    return (th == 0 or 2 < w <= 32) and (tv == 0 or 2 < h <= 32)
+
+
+class Case:
+    """org, pred: the two flat sample buffers; items: ITEM records; cand_size / level_size: samples of resi_base (and rec_base) / levels of level_base"""
+    def __init__(self, bd, org, pred, items, cand_size, level_size):
+        self.bd, self.org, self.pred, self.items, self.cand_size, self.level_size = bd, org, pred, items, int(cand_size), int(level_size)
+
+    def initial(self):
+        """the three output buffers before the call"""
+        return (np.full(self.cand_size, RESI_CANARY, np.int16), np.full(self.cand_size, REC_CANARY, np.int16),
+                np.full(self.level_size, LEVEL_CANARY, np.int32))
+
+
+def block(buf, off, stride, w, h):
+    """the h x w view of a flat buffer"""
+    return np.lib.stride_tricks.as_strided(buf[off:], (h, w), (stride * buf.itemsize, buf.itemsize))
+
+
+def pred_offset(it, rd_list):
+    """-> the prediction's offset in pred_base, or None: the item is skipped"""
+    w, h = int(it["w"]), int(it["h"])
+    if not (side_ok(w) and side_ok(h)) or int(it["cand_off"]) % 4 or int(it["level_off"]) % 4:
+        return None
+    off = int(it["pred_off"])
+    row, slot = int(it["list_row"]), int(it["list_slot"])
+    if row >= 0:
+        if rd_list is None or not 0 <= slot < 7 or slot >= int(rd_list[row][0]):
+            return None
+        c = int(rd_list[row][1 + slot])
+        if not 0 <= c <= 6:
+            return None
+        off += c * int(it["pred_cand_pitch"])
+    return off
+
+
+def sse(a, b):
+    """orc_dist_batch kind 2 of two contiguous h x w int16 blocks"""
+    h, w = a.shape
+    dd = np.zeros(1, DIST_DESC); dd[0] = (0, 0, w, w, w, h, 0, 0)
+    out = np.zeros(1, np.uint64)
+    oracle().orc_dist_batch(2, p(a), p(b), p(dd), 1, p(out))
+    return int(out[0])
+
+
+def subtract(org, pred, bd):
+    h, w = org.shape
+    band = np.zeros(1, PELOP_DESC); band[0] = (0, 0, 0, w, w, w, w, h)
+    resi = np.zeros((h, w), np.int16)
+    oracle().orc_pelop_batch(3, p(org), p(pred), p(resi), p(band), 1, C.byref(PelopCfg(0, 0, 0, 0, 0, (1 << bd) - 1)))
+    return resi
+
+
+def reconstruct(pred, resi, clp):
+    h, w = pred.shape
+    band = np.zeros(1, PELOP_DESC); band[0] = (0, 0, 0, w, w, w, w, h)
+    rec = np.zeros((h, w), np.int16)
+    oracle().orc_pelop_batch(1, p(pred), p(resi), p(rec), p(band), 1, C.byref(PelopCfg(0, 0, 0, 1, clp[0], clp[1])))
+    return rec
+
+
+def code_slot(resi, bd, code, qp, intra, sbh):
+    """transformNxN + invTransformNxN of one contiguous h x w residual -> (levels [h][w] int32, abs_sum, resi' [h][w] int16)"""
+    h, w = resi.shape
+    th, tv = (3, 0) if code == TS else (code % 3, code // 3)
+    o = oracle()
+    tr = np.zeros(1, TR_DESC); tr[0] = (0, 0, w, w, h, th, tv, 0, 0)
+    qd = np.zeros(1, QUANT_DESC); qd[0] = (0, 0, w, h, intra, sbh, 0, qp, 0)
+    dq = np.zeros(1, DQTR_DESC); dq[0] = (0, 0, w, w, h, th, tv, 0, 0, qp)
+    resi2 = np.zeros((h, w), np.int16)
+    coef, level, dqc = np.zeros(w * h, np.int32), np.zeros(w * h, np.int32), np.zeros(w * h, np.int32)
+    abs_sum = np.zeros(1, np.uint32)
+    o.orc_tr_fwd_batch(p(resi), p(coef), p(tr), 1, bd)
+    o.orc_quant_batch(p(coef), p(level), p(qd), 1, bd, p(abs_sum))
+    o.orc_dequant_tr_inv_batch(p(level), p(resi2), p(dq), 1, bd, p(dqc))
+    return level.reshape(h, w), int(abs_sum[0]), resi2
+
+
+def restate(case, flags=0, clp=None, rd_list=None):
+    """the entry over every item -> dict(resi, rec, level: the three buffers after the call; abs_sum uint32 [n][6]; dist_resi, dist_rec uint64 [n][6];
+    zero_dist uint64 [n]; clip_bites bool [n][6]: the clip changed a sample of the slot's reconstruction)"""
+    bd = case.bd
+    clp = clp or (0, (1 << bd) - 1)
+    n = len(case.items)
+    resi_b, rec_b, level_b = case.initial()
+    out = dict(resi=resi_b, rec=rec_b, level=level_b, abs_sum=np.full((n, SLOTS), U32_MAX, np.uint32), dist_resi=np.full((n, SLOTS), U64_MAX, np.uint64),
+               dist_rec=np.full((n, SLOTS), U64_MAX, np.uint64), zero_dist=np.full(n, U64_MAX, np.uint64), clip_bites=np.zeros((n, SLOTS), bool))
+    for i, it in enumerate(case.items):
+        poff = pred_offset(it, rd_list)
+        if poff is None:
+            continue
+        w, h = int(it["w"]), int(it["h"])
+        org = np.ascontiguousarray(block(case.org, int(it["org_off"]), int(it["org_stride"]), w, h))
+        pred = np.ascontiguousarray(block(case.pred, poff, int(it["pred_stride"]), w, h))
+        org_resi = subtract(org, pred, bd)
+        out["zero_dist"][i] = sse(org_resi, np.zeros((h, w), np.int16))
+        for k in range(SLOTS):
+            code = int(it["tr"][k])
+            if not slot_served(w, h, code):
+                continue
+            level, abs_sum, resi2 = code_slot(org_resi, bd, code, int(it["qp"]), int(it["intra_slice"]), int(it["sign_hiding"]))
+            rec = reconstruct(pred, resi2, clp)
+            co, lo = int(it["cand_off"]) + k * w * h, int(it["level_off"]) + k * w * h
+            resi_b[co:co + w * h] = resi2.reshape(-1)
+            level_b[lo:lo + w * h] = level.reshape(-1)
+            if flags & WRITE_REC:
+                rec_b[co:co + w * h] = rec.reshape(-1)
+            out["abs_sum"][i, k], out["dist_resi"][i, k], out["dist_rec"][i, k] = abs_sum, sse(org_resi, resi2), sse(org, rec)
+            out["clip_bites"][i, k] = not np.array_equal(rec.astype(np.int32), pred.astype(np.int32) + resi2)
+    return out
+
+
+def check_conditions(case, want, random_list=False, handover=False):
+    """the caps on the inputs, asserted on the restatement alone: in a random list at most a quarter of the served slots are all-zero and the clip
+    changes dist_rec in at least a tenth of them; in a hand-over list at most a quarter of the list items are skipped"""
+    served = want["abs_sum"] != U32_MAX
+    if random_list:
+        zero = served & (want["abs_sum"] == 0)
+        assert zero.sum() * 4 <= served.sum(), (int(zero.sum()), int(served.sum()))
+        bites = served & (want["dist_rec"] != want["dist_resi"])
+        assert bites.sum() * 10 >= served.sum(), (int(bites.sum()), int(served.sum()))
+    if handover:
+        li = case.items["list_row"] >= 0
+        skipped = li & (want["zero_dist"] == U64_MAX)
+        assert li.any() and skipped.sum() * 4 <= li.sum(), (int(skipped.sum()), int(li.sum()))
+
+
+# ---- builders --------------------------------------------------------------------------------------------------------------------------------------
+def fresh_plane(rng, bd):
+    """the original: a texture in the middle of the range, a dark band on the left and a bright band on the right whose samples crowd the range ends
+    (there the clip of the reconstruction bites)"""
+    mx = (1 << bd) - 1
+    s = 1 << (bd - 8)
+    yy, xx = np.mgrid[0:H, 0:W]
+    org = 128 * s + 60 * s * np.sin(xx / 9.0) * np.cos(yy / 7.0) + rng.integers(-8 * s, 8 * s + 1, (H, W))
+    org[:, :W // 3] = rng.integers(-30 * s, 31 * s, (H, W // 3))
+    org[:, W - W // 3:] = mx - rng.integers(-30 * s, 31 * s, (H, W // 3))
+    return np.clip(org, 0, mx).astype(np.int16)
+
+
+def place(rng, w, h, band=None):
+    """an odd-aligned position of a w x h block; band 0 / 1 / 2: inside the dark / middle / bright third"""
+    band = int(rng.integers(0, 3)) if band is None else band
+    x0, x1 = ((0, W // 3), (W // 3, W - W // 3), (W - W // 3, W))[band]
+    return int(rng.integers(x0, x1 - w + 1)), int(rng.integers(0, H - h + 1))
+
+
+def noisy_pred(rng, org_block, bd, amp=20):
+    mx = (1 << bd) - 1
+    return np.clip(org_block.astype(np.int32) + rng.integers(-amp, amp + 1, org_block.shape) * (1 << (bd - 8)), 0, mx).astype(np.int16)
+
+
+def make(bd, plane, specs, rng, pred_extra=None):
+    """specs: one dict per item with x, y, w, h and any of pred (h x w; default the original plus noise), tr (up to six codes, default [0]), qp, intra, sbh,
+    list_row, list_slot, pred_off, pred_stride, pred_cand_pitch (list items address pred_extra, a buffer placed in front of the items' own predictions),
+    cand_misalign / level_misalign (an offset that is no multiple of 4).  Every item gets regions of its own in the buffers with canaries between."""
+    items = np.zeros(len(specs), ITEM)
+    front = 0 if pred_extra is None else len(pred_extra)
+    po, co, lo = front + 3, 8, 4
+    fills = []
+    ph, pw = plane.shape
+    for i, s in enumerate(specs):
+        w, h = int(s["w"]), int(s["h"])
+        ew, eh = max(1, min(abs(w), 64)), max(1, min(abs(h), 64))            # the room an item gets, whatever its sides claim
+        ps = ew + 1 + 2 * (i % 3)
+        po |= 1
+        tr = list(s.get("tr", [0])) + [-1] * SLOTS
+        it = items[i]
+        it["org_off"], it["org_stride"] = int(s["y"]) * pw + int(s["x"]), pw
+        it["pred_off"], it["pred_stride"], it["pred_cand_pitch"] = s.get("pred_off", po), s.get("pred_stride", ps), s.get("pred_cand_pitch", 0)
+        it["cand_off"], it["level_off"] = co + s.get("cand_misalign", 0), lo + s.get("level_misalign", 0)
+        it["qp"], it["list_row"], it["list_slot"] = s.get("qp", 32 + 6 * (bd - 8)), s.get("list_row", -1), s.get("list_slot", 0)
+        it["w"], it["h"], it["intra_slice"], it["sign_hiding"], it["tr"] = w, h, s.get("intra", 0), s.get("sbh", 1), tr[:SLOTS]
+        if "pred_off" not in s:
+            g = s.get("pred")
+            if g is None:
+                g = plane[int(s["y"]):int(s["y"]) + eh, int(s["x"]):int(s["x"]) + ew]
+                g = noisy_pred(rng, g, bd) if g.shape == (eh, ew) else np.zeros((eh, ew), np.int16)   # (an item whose sides are not a block's: never read)
+            fills.append((po, ps, ew, eh, np.asarray(g, np.int16)))
+            po += eh * ps + 5 + (i % 4)
+        co += SLOTS * ew * eh + 4 * (1 + i % 3)
+        lo += SLOTS * ew * eh + 4 * (i % 3)
+    pred = np.full(po + 8, PRED_GUARD, np.int16)
+    if pred_extra is not None:
+        pred[:front] = pred_extra
+    for off, ps, w, h, g in fills:
+        block(pred, off, ps, w, h)[:] = g[:h, :w]
+    return Case(bd, np.ascontiguousarray(plane.reshape(-1)), pred, items, co + 8, lo + 8)
+
+
+def shapes_case(bd):
+    """every shape with one DCT-II slot at an odd picture position"""
+    rng = np.random.default_rng(9100 + bd)
+    plane = fresh_plane(rng, bd)
+    specs = []
+    for k, (w, h) in enumerate(all_shapes()):
+        x, y = place(rng, w, h)
+        specs.append(dict(x=x | 1 if x + w < W else x, y=y, w=w, h=h, qp=(22, 27, 32, 37)[k % 4] + 6 * (bd - 8), intra=k % 2, sbh=(k // 2) % 2))
+    case = make(bd, plane, specs, rng)
+    assert (case.items["org_off"] % 2 == 1).sum() > len(specs) // 2
+    return case, restate(case)
+
+
+SKIP_KINDS = ("w3", "w128", "h0", "list_null_row", "list_slot_high", "list_cand_bad", "cand_misalign", "level_misalign")
+
+
+def random_rd_rows():
+    """rd_list rows for the list items of the random list: full, a single survivor, empty, a row with an out-of-range candidate"""
+    return np.array([[4, 2, 0, 5, 1, -1, -1, -1], [1, 3, -1, -1, -1, -1, -1, -1], [0, -1, -1, -1, -1, -1, -1, -1], [2, 9, 6, -1, -1, -1, -1, -1]], np.int32)
+
+
+def random_case(bd, n=300):
+    """mixed shapes, 1..6 slots with unused slots in the middle, EMT and transform-skip slots (served and not), list items, skipped items of every kind
+    interleaved; two thirds of the blocks lie in the bands at the range ends -> (Case, rd_list rows, restatement)"""
+    rng = np.random.default_rng(9300 + bd)
+    plane = fresh_plane(rng, bd)
+    rows = random_rd_rows()
+    shapes = all_shapes()
+    # the candidates' predictions of the list items: seven 8 x 8 blocks, 80 samples apart, of the original block at (8, 8) plus noise
+    extra = np.full(7 * 80 + 8, PRED_GUARD, np.int16)
+    for c in range(7):
+        extra[c * 80:c * 80 + 64] = noisy_pred(rng, plane[8:16, 8:16], bd).reshape(-1)
+    specs = []
+    for i in range(n):
+        w, h = shapes[(i * 7 + i // 36) % len(shapes)]
+        x, y = place(rng, w, h, band=(0, 2, 1)[i % 3])
+        ns = int(rng.integers(1, 7))
+        tr = []
+        for k in range(ns):
+            r = int(rng.integers(0, 10))
+            tr.append(0 if r < 3 else TS if r == 3 else -1 if r == 4 and k < ns - 1 else int(rng.choice(EMT)) if r < 9 else int(rng.choice([1, 2, 3, 6, 10, -2, 100])))
+        if tr[0] == -1 or not any(slot_served(w, h, c) for c in tr):
+            tr[0] = 0
+        s = dict(x=x, y=y, w=w, h=h, tr=tr, qp=int(rng.integers(20, 36)) + 6 * (bd - 8), intra=int(rng.integers(0, 2)), sbh=int(rng.integers(0, 2)))
+        if i % 9 == 4:                                                        # a list item: the 8 x 8 block at (8, 8) against a candidate of `extra`
+            s.update(x=8, y=8, w=8, h=8, list_row=(i // 9) % 2, list_slot=(i // 18) % 4, pred_off=0, pred_stride=8, pred_cand_pitch=80)
+        if i % 11 == 7:
+            kind = SKIP_KINDS[(i // 11) % len(SKIP_KINDS)]
+            if kind == "w3": s["w"] = 3
+            elif kind == "w128": s["w"] = 128
+            elif kind == "h0": s["h"] = 0
+            elif kind == "cand_misalign": s["cand_misalign"] = 2
+            elif kind == "level_misalign": s["level_misalign"] = 1
+            else:
+                s.update(x=8, y=8, w=8, h=8, pred_off=0, pred_stride=8, pred_cand_pitch=80,
+                         list_row=dict(list_null_row=2, list_slot_high=1, list_cand_bad=3)[kind], list_slot=dict(list_null_row=0, list_slot_high=1, list_cand_bad=0)[kind])
+        specs.append(s)
+    case = make(bd, plane, specs, rng, pred_extra=extra)
+    want = restate(case, rd_list=rows)
+    check_conditions(case, want, random_list=True)
+    skipped = want["zero_dist"] == U64_MAX
+    assert skipped.sum() >= len(SKIP_KINDS) and (~skipped).sum() > 250
+    served = want["abs_sum"] != U32_MAX
+    assert ((case.items["tr"] == TS) & served).any() and ((case.items["tr"] == TS) & ~served).any() and (np.isin(case.items["tr"], EMT) & served).any()
+    return case, rows, want
+
+
+def zero_case(bd):
+    """all-zero slots: the largest QP on a small residual, every shape class of the kernel (lane-strided, matrix-core, transform skip)"""
+    rng = np.random.default_rng(9500 + bd)
+    plane = fresh_plane(rng, bd)
+    specs = []
+    for (w, h) in [(4, 4), (8, 8), (2, 4), (16, 16), (32, 8), (64, 64), (32, 32), (4, 16)]:
+        x, y = place(rng, w, h, band=1)
+        pred = np.clip(plane[y:y + h, x:x + w].astype(np.int32) + rng.integers(-1, 2, (h, w)), 0, (1 << bd) - 1)
+        specs.append(dict(x=x, y=y, w=w, h=h, pred=pred, qp=max_qp(bd), tr=[0, TS, 8] if w <= 4 and h <= 4 else [0, 4] if max(w, h) <= 32 else [0]))
+    case = make(bd, plane, specs, rng)
+    return case, restate(case)
+
+
+def flat_case(bd, value, shapes=((64, 64), (32, 32), (16, 16), (8, 8), (4, 4), (2, 2))):
+    """a flat residual of `value` (+-1023 at bit depth 10: original and prediction at opposite range ends) at the smallest QP of the chain's contract and
+    at the largest, on 64 x 64 .. 2 x 2"""
+    mx = (1 << bd) - 1
+    plane = np.full((H, W), mx if value > 0 else 0, np.int16)
+    specs = []
+    for k, (w, h) in enumerate(shapes):
+        for qp in (0, max_qp(bd)):
+            specs.append(dict(x=3 + 66 * (k % 3), y=1 + 66 * (k // 3), w=w, h=h, pred=np.full((h, w), mx - abs(value) if value > 0 else abs(value), np.int16), qp=qp,
+                              tr=[0, TS] if w <= 4 else [0]))
+    case = make(bd, plane, specs, np.random.default_rng(1))
+    return case, restate(case)
+
+
+def checker_case(bd):
+    """64 x 64, 4 x 4 and 2 x 2: original and prediction as opposite 0 / max checkerboards, in both phases: zero_dist of the 64 x 64 block at bit depth 10
+    is 64 x 64 x 1023^2 = 4 286 582 784, beyond 2^31"""
+    mx = (1 << bd) - 1
+    yy, xx = np.mgrid[0:H, 0:W]
+    plane = (((yy + xx) & 1) * mx).astype(np.int16)
+    specs = []
+    for (w, h) in [(64, 64), (4, 4), (2, 2)]:
+        for phase in (0, 1):                                                  # an even / odd column: the two phases of the board
+            pred = (mx - plane[0:h, phase:phase + w]).astype(np.int16)
+            specs.append(dict(x=phase, y=0, w=w, h=h, pred=pred, qp=37 + 6 * (bd - 8), tr=[0, TS] if w <= 4 else [0]))
+    case = make(bd, plane, specs, np.random.default_rng(2))
+    want = restate(case)
+    assert int(want["zero_dist"][0]) == 64 * 64 * mx * mx
+    return case, want
+
+
+def clip_case(bd):
+    """predictions AT the clip bounds with an original just inside: resi' overshoots and the clip bites, dist_rec != dist_resi"""
+    rng = np.random.default_rng(9700 + bd)
+    mx = (1 << bd) - 1
+    plane = fresh_plane(rng, bd)
+    specs = []
+    for k, (w, h) in enumerate([(4, 4), (8, 8), (16, 16), (32, 32), (64, 64), (8, 4), (2, 2), (16, 4)]):
+        x, y = place(rng, w, h, band=0 if k % 2 else 2)
+        pred = np.full((h, w), 0 if k % 2 else mx, np.int16)
+        specs.append(dict(x=x, y=y, w=w, h=h, pred=pred, qp=27 + 6 * (bd - 8), tr=[0, TS] if w <= 4 and h <= 4 else [0]))
+    case = make(bd, plane, specs, rng)
+    want = restate(case)
+    served = want["abs_sum"] != U32_MAX
+    assert (want["dist_rec"][served] != want["dist_resi"][served]).sum() * 2 >= served.sum() and want["clip_bites"].any()
+    return case, want
+
+
+# ---- the hand-over from vvcgpu_merge_cand_batch -----------------------------------------------------------------------------------------------------
+HANDOVER_SLOTS = 4
+HANDOVER_MAX_NUM, HANDOVER_LAM = 6, 11.375
+
+
+def handover_case(bd):
+    """a small PU list for vvcgpu_merge_cand_batch whose rows have 0 (a skipped PU: all -1), 1 and 4 survivors, and per PU and component list items for slots
+    0 .. 3 -> (frame, layout, merge restatement, Case over the merge restatement's prediction buffer, restatement)"""
+    import merge_cand_cases as mcc
+    rng = np.random.default_rng(9900 + bd)
+    fr = mcc.derived_frame(*mcc.fresh_planes(rng, bd), bd)
+    far = lambda j: mcc.default_cand((1, 41 + 9 * j, -35 - 2 * j), None)   # a poor match (another texture); every one about as poor
+    pus = []
+    for q, (w, h) in enumerate([(16, 16), (8, 8), (32, 16), (4, 8), (64, 64), (8, 32), (16, 4), (32, 32), (16, 8), (8, 8), (64, 32), (16, 16)]):
+        px, py = mcc.place(rng, w, h)
+        if q == 5:                                                            # the true motion (the original is the first picture moved by (3, -2)) far ahead of the others: a single survivor
+            px, py = 40, 40                                                   # (away from the edges, where the moved picture wraps)
+            cands = [far(0), mcc.default_cand((0, 12, -8), None), far(1), far(2)]
+        elif q == 9:                                                          # a PU outside the contract (eight candidates): its row is all -1
+            cands = [far(j) for j in range(8)]
+        else:                                                                 # candidates about as poor as each other: four survivors
+            cands = [far(j) for j in range(5 + q % 2)]
+        pus.append((px, py, w, h, cands))
+    L = mcc.layout(fr, pus, 3, pad_of=lambda c: 2)
+    mwant = mcc.restate(fr, L, HANDOVER_MAX_NUM, 1, HANDOVER_LAM)
+    mwant["rd_list"][9] = -1                                                  # (the entry's rule for a PU with more than seven candidates)
+    sizes = mwant["rd_list"][:, 0]
+    assert (sizes == 4).any() and (sizes == 1).any() and (sizes <= 0).any(), sizes
+    specs = []
+    for q, (px, py, w, h, cands) in enumerate(pus):
+        c0 = int(L["pu_cand_first"][q])
+        for comp in range(3):
+            d0, d1 = L["cand_dist"][3 * c0 + comp], L["cand_dist"][3 * (c0 + 1) + comp]
+            s = 1 if comp else 0
+            for slot in range(HANDOVER_SLOTS):
+                specs.append(dict(x=0, y=0, w=w >> s, h=h >> s, list_row=q, list_slot=slot, pred_off=int(d0["cur_off"]), pred_stride=int(d0["cur_stride"]),
+                                  pred_cand_pitch=int(d1["cur_off"]) - int(d0["cur_off"]), qp=(22, 27, 32)[(q + slot) % 3] + 6 * (bd - 8), sbh=q % 2,
+                                  tr=[0, int(EMT[(q + slot) % 4])] if comp == 0 else [0], org_off=int(d0["org_off"]), org_stride=int(d0["org_stride"])))
+    case = make(bd, np.zeros((1, 1), np.int16), specs, rng, pred_extra=mwant["pred"])
+    for it, s in zip(case.items, specs):
+        it["org_off"], it["org_stride"] = s["org_off"], s["org_stride"]
+    case.org = fr.org
+    want = restate(case, rd_list=mwant["rd_list"])
+    check_conditions(case, want, handover=True)
+    return fr, L, mwant, case, want
+
+
+# ---- the golden file -------------------------------------------------------------------------------------------------------------------------------
+def golden_case(g, bd):
+    k = "bd%d_" % bd
+    return Case(bd, g[k + "org"], g[k + "pred"], g[k + "items"].view(ITEM).reshape(-1), int(g[k + "cand_size"]), int(g[k + "level_size"]))

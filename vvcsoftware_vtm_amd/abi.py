@@ -126,6 +126,12 @@ RC_DESC = np.dtype([("org_off", "<i8"), ("pred_off", "<i8"), ("rec_off", "<i8"),
                     ("qp", "<i4"), ("reserved", "<i4", (2,))])
 RDPCM_DESC = np.dtype([("resi_off", "<i8"), ("coeff_off", "<i8"), ("resi_stride", "<i4"), ("w", "<i2"), ("h", "<i2"), ("mode", "i1"), ("lossless", "i1"),
                        ("rotate", "i1"), ("intra_slice", "i1"), ("qp", "<i4"), ("reserved", "<i4"), ("pad", "<i4")])    # "pad": the C struct's tail padding
+# vvcgpu_inter_resi_code_batch: one transform block of an inter CU (vvcgpu_inter_resi_item), its slot count, the transform-skip code and the flag
+INTER_RESI_ITEM = np.dtype([("org_off", "<i8"), ("pred_off", "<i8"), ("pred_cand_pitch", "<i8"), ("cand_off", "<i8"), ("level_off", "<i8"),
+                            ("org_stride", "<i4"), ("pred_stride", "<i4"), ("qp", "<i4"), ("list_row", "<i4"), ("w", "<i2"), ("h", "<i2"),
+                            ("list_slot", "i1"), ("intra_slice", "i1"), ("sign_hiding", "i1"), ("reserved", "i1"), ("tr", "i1", (6,)),
+                            ("reserved1", "i1", (2,)), ("reserved2", "<i4", (2,))])
+INTER_RESI_SLOTS, INTER_RESI_TS, INTER_RESI_WRITE_REC = 6, 9, 1
 
 # ---- affine motion --------------------------------------------------------------------------------------------------------------
 AFG_DESC = np.dtype([("pred_off", "<i8"), ("deriv_off", "<i8"), ("pred_stride", "<i4"), ("deriv_stride", "<i4"), ("w", "<i2"), ("h", "<i2"),

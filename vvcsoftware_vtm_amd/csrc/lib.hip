@@ -341,6 +341,7 @@ int vvcgpu_sizeof(int id)
   case 59: return (int)sizeof(vvcgpu_affine_unipred_search);
   case 60: return (int)sizeof(vvcgpu_affine_unipred_result);
   case 62: return (int)sizeof(vvcgpu_intra_chroma_pu);
+  case 63: return (int)sizeof(vvcgpu_inter_resi_item);
   default: return -1;
   }
 }

@@ -163,8 +163,7 @@ __global__ __launch_bounds__(1024) void rc_classify_kernel(const void* __restric
 // Matrix-core path (stages and the LDS matrix image: mfma_tr.h).  The image is built ONCE per device in global memory (rc_build_tables_kernel)
 // and copied by every workgroup with 16-byte loads.  Behind the f16 matrices (RC_TAB_HALVES halves) the image carries the 4- / 8-point matrices
 // as int32 for the lane-group bodies (RcSmallTab), so that a workgroup's whole table set is ONE run of 16-byte loads.
-struct RcSmallTab { int t[3][16 + 64]; int tt[3][16 + 64]; };       // per type: size 4 at 0, size 8 at 16; tt = transposes
-static_assert(sizeof(RcSmallTab) % 16 == 0, "copied with 16-byte loads");
+// (struct RcSmallTab: resichain_dev.h)
 constexpr int RC_IMG_U4 = RC_TAB_HALVES / 8 + (int)sizeof(RcSmallTab) / 16;       // 16-byte words of the image
 __global__ __launch_bounds__(256) void rc_build_tables_kernel(_Float16* __restrict__ tab, const int* __restrict__ tr32, const int* __restrict__ tr32t)
 {
@@ -1145,340 +1144,7 @@ __global__ __launch_bounds__(256, 3) void rc_generic_kernel(const Pel* __restric
   }
 }
 
-// ---------------------------------------------------------------------------------------------------
-// (multiplies: 24-bit, full rate -- operands are at most 18-bit intermediates and 8-bit matrix entries; the 32-bit v_mul_lo_u32 is a quarter-rate instruction)
-// 4 x 4 and 8 x 8: lane groups of S lanes per TU, G = 64 / S TUs per wave.  Forward: lane = row (stage 1), transposed through LDS, lane = column
-// (stage 2, quantiser, de-quantiser, vertical inverse stage), transposed back, lane = row (horizontal inverse stage + reconstruction: the
-// prediction row is still in the lane's registers).
-template <int S, int MODE>
-__device__ __noinline__ void rc_small_group(const RcDesc* __restrict__ descs, const int* __restrict__ list, int cnt, int item,
-                                               const Pel* __restrict__ orgBase, const Pel* __restrict__ predBase, Pel* __restrict__ recBase,
-                                               TCoeff* __restrict__ levelBase, unsigned* __restrict__ absSumOut, int bd, int clpMin, int clpMax,
-                                               const RcSmallTab& tabs, int* tmpL, int lane)
-{
-  constexpr int mode = MODE;
-  RC_IS_LDS(tmpL);
-
-  constexpr int G = 64 / S, LS = S == 4 ? 2 : 3, TO = S == 4 ? 0 : 16;
-  typedef short pelS __attribute__((ext_vector_type(S)));
-  const int tg = lane / S, li = lane % S;
-  const int k = item * G + tg;
-  const bool act = k < cnt;
-  const int ti = list[act ? k : 0];
-  const RcDesc d = descs[ti];
-  int* tt = tmpL + tg * (S * (S + 1));
-  const int* Th = tabs.t[d.tr_hor] + TO;
-  const int* Tv = tabs.t[d.tr_ver] + TO;
-  const int* ThT = tabs.tt[d.tr_hor] + TO;
-  const int* TvT = tabs.tt[d.tr_ver] + TO;
-  // stage F1: lane = row li
-  pelS p;
-#pragma unroll
-  for (int jj = 0; jj < S; jj++) p[jj] = 0;
-  const int s1 = LS + bd + 6 - 15 + 2, s2 = LS + 6 + 2;
-  int cq[S];                                                              // the inverse stages' input: column li
-  TCoeff* level = levelBase + d.level_off;
-  if (mode != RC_INV)
-  {
-  const pelS o = *reinterpret_cast<const pelS*>(orgBase + d.org_off + (size_t)li * d.org_stride);
-  if (mode == RC_CHAIN) p = *reinterpret_cast<const pelS*>(predBase + d.pred_off + (size_t)li * d.pred_stride);
-  {
-    int x[S];
-#pragma unroll
-    for (int j = 0; j < S; j++) x[j] = (int)o[j] - (int)p[j];
-#pragma unroll
-    for (int j = 0; j < S; j++)
-    {
-      int sum = 0;
-#pragma unroll
-      for (int kk = 0; kk < S; kk++) sum += __mul24(x[kk], Th[j * S + kk]);
-      tt[j * (S + 1) + li] = (sum + (1 << (s1 - 1))) >> s1;
-    }
-  }
-  RC_WAVE_SYNC();
-  // stage F2: lane = column li (horizontal frequency), registers = rows
-  int cf[S];
-  {
-    int t[S];
-#pragma unroll
-    for (int r = 0; r < S; r++) t[r] = tt[li * (S + 1) + r];
-#pragma unroll
-    for (int j = 0; j < S; j++)
-    {
-      int sum = 0;
-#pragma unroll
-      for (int r = 0; r < S; r++) sum += __mul24(t[r], Tv[j * S + r]);
-      cf[j] = (sum + (1 << (s2 - 1))) >> s2;
-    }
-  }
-  RC_WAVE_SYNC();
-  if (mode == RC_FWD)                                                     // forward transform only: the coefficients are the result
-  {
-    if (act)
-    {
-#pragma unroll
-      for (int j = 0; j < S; j++) level[j * S + li] = cf[j];
-    }
-    return;
-  }
-  // quantiser (coefficient groups: rows 4 R .. 4 R + 3 x the lane's aligned quad)
-  const RcQ q = rc_qparams(S, S, d.qp, bd, d.intra_slice, d.sign_hiding);
-  int lv[S], du[S], sum = 0;
-#pragma unroll
-  for (int j = 0; j < S; j++) { int mag; lv[j] = rc_quant_one(q, cf[j], du[j], mag); sum += mag; }
-#pragma unroll
-  for (int m = 1; m < S; m <<= 1) sum += __shfl_xor(sum, m);
-  if (act && li == 0) absSumOut[ti] = (unsigned)sum;
-  if (q.sbh)
-  {
-    // coefficient-group scan index inside the TU: 4x4: one group; 8x8: (cx, cy) -> 2 cx + cy (diagonal scan of the 2 x 2 group grid)
-    int lastCg = -1;
-#pragma unroll
-    for (int R = 0; R < S / 4; R++)
-    {
-      int l4[4] = { lv[4 * R], lv[4 * R + 1], lv[4 * R + 2], lv[4 * R + 3] };
-      if (rc_cg_nonzero(l4)) lastCg = max(lastCg, 2 * (li >> 2) + R);
-    }
-    if (S == 8) lastCg = max(lastCg, __shfl_xor(lastCg, 4));
-#pragma unroll
-    for (int R = 0; R < S / 4; R++)
-    {
-      int l4[4] = { lv[4 * R], lv[4 * R + 1], lv[4 * R + 2], lv[4 * R + 3] };
-      const int d4[4] = { du[4 * R], du[4 * R + 1], du[4 * R + 2], du[4 * R + 3] };
-      const int c4[4] = { cf[4 * R], cf[4 * R + 1], cf[4 * R + 2], cf[4 * R + 3] };
-      rc_sbh_quad(l4, d4, c4, 2 * (li >> 2) + R == lastCg, lane);
-#pragma unroll
-      for (int r = 0; r < 4; r++) lv[4 * R + r] = l4[r];
-    }
-  }
-  if (act)
-  {
-#pragma unroll
-    for (int j = 0; j < S; j++) level[j * S + li] = lv[j];
-  }
-#pragma unroll
-  for (int j = 0; j < S; j++) cq[j] = rc_dequant_one(q, lv[j]);
-  }
-  else
-  {
-#pragma unroll
-    for (int j = 0; j < S; j++) cq[j] = act ? level[j * S + li] : 0;      // any 32-bit coefficient: exact 32-bit multiplies below
-  }
-  // stage I1 (vertical): y[r] = clip(sum_k Cq[k] Tv[k][r]); written transposed: tt[r][column li]
-  {
-    bool fits24 = true;                                                   // 24-bit multiplies when every coefficient of the wave allows it (always, for de-quantiser output)
-    if (mode != RC_CHAIN)
-    {
-#pragma unroll
-      for (int kk = 0; kk < S; kk++) fits24 = fits24 && cq[kk] >= -(1 << 23) && cq[kk] < (1 << 23);
-    }
-    const bool narrow = mode == RC_CHAIN || __builtin_amdgcn_ballot_w64(!fits24) == 0ull;
-#pragma unroll
-    for (int r = 0; r < S; r++)
-    {
-      int acc = 0;
-      if (narrow)
-      {
-#pragma unroll
-        for (int kk = 0; kk < S; kk++) acc += __mul24(cq[kk], TvT[r * S + kk]);
-      }
-      else
-      {
-#pragma unroll
-        for (int kk = 0; kk < S; kk++) acc += cq[kk] * TvT[r * S + kk];
-      }
-      tt[r * (S + 1) + li] = clip3(-(1 << 15), (1 << 15) - 1, (acc + 256) >> 9);
-    }
-  }
-  RC_WAVE_SYNC();
-  // stage I2 (horizontal): lane = row li
-  const int s2i = (6 + 15 - 1) - bd + 2;
-  {
-    int y[S];
-#pragma unroll
-    for (int i = 0; i < S; i++) y[i] = tt[li * (S + 1) + i];
-    pelS out;
-#pragma unroll
-    for (int x = 0; x < S; x++)
-    {
-      int acc = 0;
-#pragma unroll
-      for (int i = 0; i < S; i++) acc += __mul24(y[i], ThT[x * S + i]);
-      const int resi = (short)clip3(-(1 << 15), (1 << 15) - 1, (acc + (1 << (s2i - 1))) >> s2i);
-      out[x] = mode == RC_CHAIN ? (short)clip3(clpMin, clpMax, (int)p[x] + resi) : (short)resi;
-    }
-    if (act) *reinterpret_cast<pelS*>(recBase + d.rec_off + (size_t)li * d.rec_stride) = out;
-  }
-  RC_WAVE_SYNC();
-}
-
-// 8 x 4 and 4 x 8 (the most frequent rectangles of a real encode: tests/golden/trace_*.npz): the same scheme with 8 lanes per TU -- lane = row
-// in the horizontal stages (H rows), lane = column in the vertical stages and the quantiser (W columns; the other lanes of the group idle there).
-// The TU has two coefficient groups side by side (8 x 4) or one above the other (4 x 8): the group's scan index is its position.
-template <int W, int H, int MODE>
-__device__ __noinline__ void rc_rect_group(const RcDesc* __restrict__ descs, const int* __restrict__ list, int cnt, int item,
-                                              const Pel* __restrict__ orgBase, const Pel* __restrict__ predBase, Pel* __restrict__ recBase,
-                                              TCoeff* __restrict__ levelBase, unsigned* __restrict__ absSumOut, int bd, int clpMin, int clpMax,
-                                              const RcSmallTab& tabs, int* tmpL, int lane)
-{
-  constexpr int mode = MODE;
-
-  constexpr int L = 8, G = 64 / L, LW = W == 4 ? 2 : 3, LH = H == 4 ? 2 : 3, TOW = W == 4 ? 0 : 16, TOH = H == 4 ? 0 : 16;
-  typedef short pelW __attribute__((ext_vector_type(W)));
-  const int tg = lane / L, li = lane % L;
-  const int k = item * G + tg;
-  const bool act = k < cnt;
-  const int ti = list[act ? k : 0];
-  const RcDesc d = descs[ti];
-  int* tt = tmpL + tg * (L * (L + 1));
-  const int* Th = tabs.t[d.tr_hor] + TOW;
-  const int* Tv = tabs.t[d.tr_ver] + TOH;
-  const int* ThT = tabs.tt[d.tr_hor] + TOW;
-  const int* TvT = tabs.tt[d.tr_ver] + TOH;
-  const bool isRow = li < H, isCol = li < W;
-  const int rr = isRow ? li : 0;
-  // stage F1: lane = row
-  pelW p;
-#pragma unroll
-  for (int jj = 0; jj < W; jj++) p[jj] = 0;
-  const int s1 = LW + bd + 6 - 15 + 2, s2 = LH + 6 + 2;
-  int cq[H];                                                              // the inverse stages' input: column li
-  TCoeff* level = levelBase + d.level_off;
-  if (mode != RC_INV)
-  {
-  const pelW o = *reinterpret_cast<const pelW*>(orgBase + d.org_off + (size_t)rr * d.org_stride);
-  if (mode == RC_CHAIN) p = *reinterpret_cast<const pelW*>(predBase + d.pred_off + (size_t)rr * d.pred_stride);
-  if (isRow)
-  {
-    int x[W];
-#pragma unroll
-    for (int j = 0; j < W; j++) x[j] = (int)o[j] - (int)p[j];
-#pragma unroll
-    for (int j = 0; j < W; j++)
-    {
-      int sum = 0;
-#pragma unroll
-      for (int kk = 0; kk < W; kk++) sum += __mul24(x[kk], Th[j * W + kk]);
-      tt[j * (L + 1) + li] = (sum + (1 << (s1 - 1))) >> s1;
-    }
-  }
-  RC_WAVE_SYNC();
-  // stage F2: lane = column (horizontal frequency), registers = rows
-  int cf[H];
-  {
-    int t[H];
-#pragma unroll
-    for (int r = 0; r < H; r++) t[r] = isCol ? tt[li * (L + 1) + r] : 0;
-#pragma unroll
-    for (int j = 0; j < H; j++)
-    {
-      int sum = 0;
-#pragma unroll
-      for (int r = 0; r < H; r++) sum += __mul24(t[r], Tv[j * H + r]);
-      cf[j] = (sum + (1 << (s2 - 1))) >> s2;
-    }
-  }
-  RC_WAVE_SYNC();
-  if (mode == RC_FWD)                                                     // forward transform only: the coefficients are the result
-  {
-    if (act && isCol)
-    {
-#pragma unroll
-      for (int j = 0; j < H; j++) level[j * W + li] = cf[j];
-    }
-    return;
-  }
-  // quantiser (coefficient groups: rows 4 R .. 4 R + 3 x the lane's aligned quad); idle lanes carry zeros
-  const RcQ q = rc_qparams(W, H, d.qp, bd, d.intra_slice, d.sign_hiding);
-  int lv[H], du[H], sum = 0;
-#pragma unroll
-  for (int j = 0; j < H; j++) { int mag; lv[j] = rc_quant_one(q, cf[j], du[j], mag); sum += mag; }
-#pragma unroll
-  for (int m = 1; m < L; m <<= 1) sum += __shfl_xor(sum, m);
-  if (act && li == 0) absSumOut[ti] = (unsigned)sum;
-  if (q.sbh)
-  {
-    int lastCg = -1;
-#pragma unroll
-    for (int R = 0; R < H / 4; R++)
-    {
-      int l4[4] = { lv[4 * R], lv[4 * R + 1], lv[4 * R + 2], lv[4 * R + 3] };
-      if (rc_cg_nonzero(l4)) lastCg = max(lastCg, (W == 8 ? (li >> 2) : 0) + R);
-    }
-    lastCg = max(lastCg, __shfl_xor(lastCg, 4));
-#pragma unroll
-    for (int R = 0; R < H / 4; R++)
-    {
-      int l4[4] = { lv[4 * R], lv[4 * R + 1], lv[4 * R + 2], lv[4 * R + 3] };
-      const int d4[4] = { du[4 * R], du[4 * R + 1], du[4 * R + 2], du[4 * R + 3] };
-      const int c4[4] = { cf[4 * R], cf[4 * R + 1], cf[4 * R + 2], cf[4 * R + 3] };
-      rc_sbh_quad(l4, d4, c4, (W == 8 ? (li >> 2) : 0) + R == lastCg, lane);
-#pragma unroll
-      for (int r = 0; r < 4; r++) lv[4 * R + r] = l4[r];
-    }
-  }
-  if (act && isCol)
-  {
-#pragma unroll
-    for (int j = 0; j < H; j++) level[j * W + li] = lv[j];
-  }
-#pragma unroll
-  for (int j = 0; j < H; j++) cq[j] = rc_dequant_one(q, lv[j]);
-  }
-  else
-  {
-#pragma unroll
-    for (int j = 0; j < H; j++) cq[j] = (act && isCol) ? level[j * W + li] : 0;   // any 32-bit coefficient: exact 32-bit multiplies below
-  }
-  // stage I1 (vertical), written transposed: tt[r][column]
-  bool fits24 = true;
-  if (mode != RC_CHAIN)
-  {
-#pragma unroll
-    for (int kk = 0; kk < H; kk++) fits24 = fits24 && cq[kk] >= -(1 << 23) && cq[kk] < (1 << 23);
-  }
-  const bool narrow = mode == RC_CHAIN || __builtin_amdgcn_ballot_w64(!fits24) == 0ull;
-  if (isCol)
-  {
-#pragma unroll
-    for (int r = 0; r < H; r++)
-    {
-      int acc = 0;
-      if (narrow)
-      {
-#pragma unroll
-        for (int kk = 0; kk < H; kk++) acc += __mul24(cq[kk], TvT[r * H + kk]);
-      }
-      else
-      {
-#pragma unroll
-        for (int kk = 0; kk < H; kk++) acc += cq[kk] * TvT[r * H + kk];
-      }
-      tt[r * (L + 1) + li] = clip3(-(1 << 15), (1 << 15) - 1, (acc + 256) >> 9);
-    }
-  }
-  RC_WAVE_SYNC();
-  // stage I2 (horizontal): lane = row
-  const int s2i = (6 + 15 - 1) - bd + 2;
-  if (isRow)
-  {
-    int y[W];
-#pragma unroll
-    for (int i = 0; i < W; i++) y[i] = tt[li * (L + 1) + i];
-    pelW out;
-#pragma unroll
-    for (int x = 0; x < W; x++)
-    {
-      int acc = 0;
-#pragma unroll
-      for (int i = 0; i < W; i++) acc += __mul24(y[i], ThT[x * W + i]);
-      const int resi = (short)clip3(-(1 << 15), (1 << 15) - 1, (acc + (1 << (s2i - 1))) >> s2i);
-      out[x] = mode == RC_CHAIN ? (short)clip3(clpMin, clpMax, (int)p[x] + resi) : (short)resi;
-    }
-    if (act) *reinterpret_cast<pelW*>(recBase + d.rec_off + (size_t)li * d.rec_stride) = out;
-  }
-  RC_WAVE_SYNC();
-}
+// (the lane-group bodies rc_small_group and rc_rect_group: resichain_dev.h -- interresi.hip runs them as well)
 
 // All five size classes in ONE launch.  Each class alone is bound by the latency of a TU, not by throughput (405 64x64 TUs are 405 waves:
 // 20 us; 6480 16x16 TUs: 14 us; ...), and kernels on one stream run one after the other (82 us for the five launches at 4K).  Here a workgroup
