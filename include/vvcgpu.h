@@ -1163,8 +1163,8 @@ int vvcgpu_merge_cand_batch(const vvc_pel* ref0_base, const vvc_pel* ref1_base, 
  * bits, a bad clip range, an item array that is not 16-byte aligned.  n == 0 is a no-op.
  * With the caller: every CABAC rate (cbf_comp, residual_coding, rqt_root_cbf, xGetSymbolFracBitsInter), the cost compares and the forced-null rule
  * (:4531-4568), the root-cbf decision (:4853) and the copy of the winner, the chroma distortion weight and DF_SSE_WTD.
- * Not served: cross-component prediction, RDPCM and lossless (range extensions, off in the shipped cfgs), RDOQ and the DepQuant trellis
- * (vvcgpu_rdoq_batch / vvcgpu_depquant_batch; this is the Quant::quant chain, as in every fused entry).                                              */
+ * Not served: cross-component prediction, RDPCM and lossless (range extensions, off in the shipped cfgs), RDOQ (vvcgpu_rdoq_batch; this is the
+ * Quant::quant chain, as in every fused entry).  The DepQuant trellis is vvcgpu_inter_resi_code_dq_batch's, below.                                 */
 #define VVCGPU_INTER_RESI_SLOTS      6
 #define VVCGPU_INTER_RESI_TS         9     /* tr[k]: transform skip */
 #define VVCGPU_INTER_RESI_WRITE_REC  1     /* flags: every served slot also stores clip(pred + resi') in rec_base */
@@ -1187,6 +1187,53 @@ int vvcgpu_inter_resi_code_batch(const vvc_pel* org_base, const vvc_pel* pred_ba
                                  vvc_pel* resi_base, vvc_pel* rec_base, vvc_coef* level_base,
                                  int flags, int bit_depth, int clp_min, int clp_max,
                                  uint32_t* abs_sum, uint64_t* dist_resi, uint64_t* dist_rec, uint64_t* zero_dist, void* stream);
+
+/* ---- the inter residual pixel pass with the quantiser of the shipped cfgs (DepQuant 1) ----
+ * vvcgpu_inter_resi_code_batch as above -- the same items, the same list look-up through rd_list, the same outputs at the same indices, the same skip
+ * markers -- with what transformNxN (InterSearch.cpp:4409) and invTransformNxN (:4497) do under slice->getDepQuantEnabledFlag():
+ *   the quantiser is DQIntern::DepQuant::quant (CommonLib/DepQuant.cpp:1323-1387), the trellis of vvcgpu_depquant_batch, its early return when no
+ *               coefficient exceeds getLastThreshold() included (abs_sum 0, all levels zero);
+ *   the de-quantiser is DQIntern::Quantizer::dequantBlock (:708-785), the dep_quant = 1 path of vvcgpu_dequant_tr_inv_batch.
+ * intra_slice and sign_hiding of the item are IGNORED: the trellis has no rounding offset, and sign bit hiding is off with dependent quantisation
+ * (JVET_K0072).  orgResi, zero_dist, dist_resi on the unclipped resi', dist_rec and the all-zero rule are those of vvcgpu_inter_resi_code_batch.
+ * At most three launches on the caller's stream (forward transforms, trellis, de-quantiser + inverse transforms + distortions), no host
+ * synchronisation inside; validity and the list look-up are decided on the device, so the call can be submitted behind vvcgpu_merge_cand_batch
+ * without a download.
+ *
+ * dq[i]        parallel to items[i]: lambda = Quant::m_dLambda of the component (> 0), rates_idx and luma as in vvcgpu_depquant_desc.
+ * rates        n_rates tables (vvcgpu_dq_rates), in device memory; shim/vtm_rates.h (vtmref_dq_rates_from_ctx) shows how the reference fills one.
+ * quantiser    VVCGPU_INTER_RESI_Q_DEPQUANT, the one served value; any other returns VVCGPU_E_UNSUPPORTED before any device work.
+ * level_extent the extent of level_base, in levels, that the items address (at least 16).
+ * ws           device workspace of vvcgpu_inter_resi_code_dq_workspace_bytes(level_extent, n) bytes, 16-byte aligned: the coefficients, the trellis
+ *              decisions and level histories -- all indexed by the slot's level offset -- and per slot a trellis record and a work-list entry.  It may hold anything on
+ *              entry; nothing in it survives the call by contract.
+ * Served: sides 4..64, DCT-II and the four inter-EMT pairs (DCT-II only on a 64-point side), bit depth 8..10.
+ * An ITEM is skipped, beside the rules above, when a side is 2, when level_off is negative or not a multiple of 16 (the trellis workspace is indexed by
+ * it), when rates_idx is outside [0, n_rates) or lambda is not above zero.  A SLOT is skipped, beside the rules above, when it is a transform-skip slot
+ * or its levels do not lie inside level_extent.
+ * VVCGPU_E_ARG before any device work: the cases of vvcgpu_inter_resi_code_batch, a null dq, rates or ws, n_rates < 1, level_extent < 16, a workspace
+ * that is too small or not 16-byte aligned, a dq array that is not 8-byte aligned.  n == 0 is a no-op.
+ * With the caller: as for vvcgpu_inter_resi_code_batch, and the rate tables (one per component and TU size class, refreshed when the CABAC contexts move).
+ * Not served: blocks with a side of 2 and transform skip (vvcgpu_depquant_batch serves neither: the binding keeps them on the host), RDOQ,
+ * cross-component prediction, RDPCM and lossless.                                                                                                  */
+#define VVCGPU_INTER_RESI_Q_DEPQUANT 1     /* quantiser: DQIntern::DepQuant::quant */
+struct vvcgpu_inter_resi_dq {
+  double  lambda;                          /* Quant::m_dLambda of the component */
+  int32_t rates_idx;                       /* index into the rates array */
+  int8_t  luma;
+  int8_t  reserved[3];                     /* sizeof == 16 */
+};
+typedef struct vvcgpu_inter_resi_dq vvcgpu_inter_resi_dq;
+struct vvcgpu_dq_rates;                    /* the rate tables of the trellis, defined with vvcgpu_depquant_batch below */
+size_t vvcgpu_inter_resi_code_dq_workspace_bytes(size_t level_extent, int n);
+int vvcgpu_inter_resi_code_dq_batch(const vvc_pel* org_base, const vvc_pel* pred_base, const vvcgpu_inter_resi_item* items,
+                                    const vvcgpu_inter_resi_dq* dq, int n,
+                                    const int32_t* rd_list,              /* rd_list_out of vvcgpu_merge_cand_batch, may be NULL */
+                                    const struct vvcgpu_dq_rates* rates, int n_rates, int quantiser,
+                                    vvc_pel* resi_base, vvc_pel* rec_base, vvc_coef* level_base, size_t level_extent,
+                                    int flags, int bit_depth, int clp_min, int clp_max,
+                                    uint32_t* abs_sum, uint64_t* dist_resi, uint64_t* dist_rec, uint64_t* zero_dist,
+                                    void* ws, size_t ws_bytes, void* stream);
 
 /* ---- N2 ("next" row): integer-sample TZ search of whole PUs, on the device  (InterSearch::xTZSearch,
  *          EncoderLib/InterSearch.cpp:1971-2252, with xTZSearchHelp :249-343, xTZ2PointSearch :349-374,

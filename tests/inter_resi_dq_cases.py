@@ -1,0 +1,342 @@
+"""The inter residual pixel pass under DepQuant 1 restated for the tests of vvcgpu_inter_resi_code_dq_batch from oracle steps that are each pinned to the
+compiled reference: orc_pelop_batch (subtract), orc_tr_fwd_batch, orc_depquant (DQIntern::DepQuant::quant), orc_dequant_tr_inv_batch with dep_quant = 1
+(DQIntern::Quantizer::dequantBlock + the inverse transform), orc_pelop_batch (reconstruct), orc_dist_batch kind 2.  The item and slot rules, the list look-up
+and the skip markers are written here from the entry's contract.  Planes, predictions, canaries and the hand-over are those of the sibling's cases
+(tests/inter_resi_code_cases.py); this file adds the record beside each item (lambda, rate table, luma), level offsets in multiples of 16 and the rate tables.
+numpy only: the generator and the CPU tests load this file without torch."""
+import ctypes as C
+import os
+
+import numpy as np
+
+import inter_resi_code_cases as irc
+from oraclelib import oracle, p
+from vvcsoftware_vtm_amd import abi
+from vvcsoftware_vtm_amd.abi import DQTR_DESC, TR_DESC
+
+ITEM, DQ, RATES = abi.INTER_RESI_ITEM, abi.INTER_RESI_DQ, abi.DQ_RATES
+SLOTS, TS, WRITE_REC, Q_DEPQUANT = abi.INTER_RESI_SLOTS, abi.INTER_RESI_TS, abi.INTER_RESI_WRITE_REC, abi.INTER_RESI_Q_DEPQUANT
+U32_MAX, U64_MAX = irc.U32_MAX, irc.U64_MAX
+SIDES = (4, 8, 16, 32, 64)
+EMT = irc.EMT
+HERE = os.path.dirname(os.path.abspath(__file__))
+GOLDEN = os.path.join(HERE, "golden", "inter_resi_dq.npz")
+
+
+def all_shapes():
+    return [(w, h) for w in SIDES for h in SIDES]
+
+
+def side_ok(v):
+    return 4 <= v <= 64 and (v & (v - 1)) == 0
+
+
+def slot_served(w, h, code):
+    if not 0 <= code < 9:
+        return False
+    th, tv = code % 3, code // 3
+    return (th == 0 or w <= 32) and (tv == 0 or h <= 32)
+
+
+def shared_rates(count=8):
+    """rate tables for the seeded cases: the first tables of tests/golden/depquant.npz (any table is a valid input of the trellis for any shape)"""
+    g = np.load(os.path.join(HERE, "golden", "depquant.npz"))
+    return np.ascontiguousarray(g["rates"][:count]).view(RATES).reshape(-1)
+
+
+class Case(irc.Case):
+    """the sibling's case + dq: one INTER_RESI_DQ record per item; rates: the DQ_RATES array"""
+    def __init__(self, base, dq, rates):
+        irc.Case.__init__(self, base.bd, base.org, base.pred, base.items, base.cand_size, base.level_size)
+        self.dq, self.rates = dq, rates
+
+
+def item_pred_offset(case, i, rd_list):
+    """-> the prediction's offset of item i, or None: the item is skipped"""
+    it, q = case.items[i], case.dq[i]
+    w, h, lo = int(it["w"]), int(it["h"]), int(it["level_off"])
+    if not (side_ok(w) and side_ok(h)) or lo < 0 or lo % 16 or not 0 <= int(q["rates_idx"]) < len(case.rates) or not float(q["lambda"]) > 0:
+        return None
+    return irc.pred_offset(it, rd_list)
+
+
+def code_slot(resi, bd, code, qp, lam, luma, rates_row):
+    """transformNxN + invTransformNxN of one contiguous h x w residual under DepQuant -> (levels [h][w] int32, abs_sum, resi' [h][w] int16)"""
+    h, w = resi.shape
+    th, tv = code % 3, code // 3
+    o = oracle()
+    o.orc_depquant.restype = C.c_uint32
+    tr = np.zeros(1, TR_DESC); tr[0] = (0, 0, w, w, h, th, tv, 0, 0)
+    dq = np.zeros(1, DQTR_DESC); dq[0] = (0, 0, w, w, h, th, tv, 1, 0, qp)
+    resi2 = np.zeros((h, w), np.int16)
+    coef, level, dqc = np.zeros(w * h, np.int32), np.zeros(w * h, np.int32), np.zeros(w * h, np.int32)
+    o.orc_tr_fwd_batch(p(resi), p(coef), p(tr), 1, bd)
+    abs_sum = o.orc_depquant(p(coef), p(level), w, h, luma, bd, qp, C.c_double(lam), p(rates_row))
+    o.orc_dequant_tr_inv_batch(p(level), p(resi2), p(dq), 1, bd, p(dqc))
+    return level.reshape(h, w), int(abs_sum), resi2
+
+
+def restate(case, flags=0, clp=None, rd_list=None):
+    """the entry over every item -> the dict of the sibling's restate"""
+    bd = case.bd
+    clp = clp or (0, (1 << bd) - 1)
+    n = len(case.items)
+    resi_b, rec_b, level_b = case.initial()
+    out = dict(resi=resi_b, rec=rec_b, level=level_b, abs_sum=np.full((n, SLOTS), U32_MAX, np.uint32), dist_resi=np.full((n, SLOTS), U64_MAX, np.uint64),
+               dist_rec=np.full((n, SLOTS), U64_MAX, np.uint64), zero_dist=np.full(n, U64_MAX, np.uint64))
+    for i, it in enumerate(case.items):
+        poff = item_pred_offset(case, i, rd_list)
+        if poff is None:
+            continue
+        q = case.dq[i]
+        w, h = int(it["w"]), int(it["h"])
+        org = np.ascontiguousarray(irc.block(case.org, int(it["org_off"]), int(it["org_stride"]), w, h))
+        pred = np.ascontiguousarray(irc.block(case.pred, poff, int(it["pred_stride"]), w, h))
+        org_resi = irc.subtract(org, pred, bd)
+        out["zero_dist"][i] = irc.sse(org_resi, np.zeros((h, w), np.int16))
+        for k in range(SLOTS):
+            code = int(it["tr"][k])
+            co, lo = int(it["cand_off"]) + k * w * h, int(it["level_off"]) + k * w * h
+            if not slot_served(w, h, code) or lo + w * h > case.level_size:
+                continue
+            level, abs_sum, resi2 = code_slot(org_resi, bd, code, int(it["qp"]), float(q["lambda"]), int(q["luma"]), case.rates[int(q["rates_idx"]):])
+            rec = irc.reconstruct(pred, resi2, clp)
+            resi_b[co:co + w * h] = resi2.reshape(-1)
+            level_b[lo:lo + w * h] = level.reshape(-1)
+            if flags & WRITE_REC:
+                rec_b[co:co + w * h] = rec.reshape(-1)
+            out["abs_sum"][i, k], out["dist_resi"][i, k], out["dist_rec"][i, k] = abs_sum, irc.sse(org_resi, resi2), irc.sse(org, rec)
+    return out
+
+
+# ---- builders --------------------------------------------------------------------------------------------------------------------------------------
+def make(bd, plane, specs, rng, rates=None, pred_extra=None):
+    """the sibling's make() with level offsets in multiples of 16 and a dq record per item.  specs may carry lam, luma, rates_idx (defaults: a lambda that
+    follows the QP -- 0.57 * 2^((qp8 - 12) / 3) of the 8-bit QP, the encoder's order of magnitude --, luma, table i mod len(rates)) and level_misalign"""
+    rates = shared_rates() if rates is None else rates
+    base = irc.make(bd, plane, [{k: v for k, v in s.items() if k != "level_misalign"} for s in specs], rng, pred_extra=pred_extra)
+    dq = np.zeros(len(specs), DQ)
+    lo = 16
+    for i, s in enumerate(specs):
+        ew, eh = max(1, min(abs(int(s["w"])), 64)), max(1, min(abs(int(s["h"])), 64))
+        base.items[i]["level_off"] = lo + s.get("level_misalign", 0)
+        lo += (SLOTS * ew * eh + 16 * (i % 3) + 15) // 16 * 16
+        qp8 = int(base.items[i]["qp"]) - 6 * (bd - 8)
+        dq[i]["lambda"], dq[i]["rates_idx"], dq[i]["luma"] = s.get("lam", 0.57 * 2.0 ** ((qp8 - 12) / 3.0)), s.get("rates_idx", i % len(rates)), s.get("luma", 1)
+    base.level_size = lo + 16
+    return Case(base, dq, rates)
+
+
+def shapes_case(bd):
+    """every shape with one DCT-II slot at an odd picture position and an odd prediction stride"""
+    rng = np.random.default_rng(9100 + bd)
+    plane = irc.fresh_plane(rng, bd)
+    specs = []
+    for k, (w, h) in enumerate(all_shapes()):
+        x, y = irc.place(rng, w, h)
+        specs.append(dict(x=x | 1 if x + w < irc.W else x, y=y, w=w, h=h, qp=(22, 27, 32, 37)[k % 4] + 6 * (bd - 8), luma=k % 2))
+    case = make(bd, plane, specs, rng)
+    assert (case.items["org_off"] % 2 == 1).sum() > len(specs) // 2 and (case.items["pred_stride"] % 2 == 1).all()
+    return case, restate(case)
+
+
+SKIP_KINDS = ("w2", "h2", "w3", "w128", "level_misalign4", "level_misalign8", "cand_misalign", "list_null_row", "list_slot_high", "list_cand_bad", "rates_high",
+              "rates_negative", "lambda_zero")
+
+
+def random_case(bd, n=300):
+    """mixed shapes, 1..6 slots with unused slots in the middle, EMT slots, transform-skip slots and codes out of range (skipped), list items, skipped items of
+    every kind interleaved -> (Case, rd_list rows, restatement)"""
+    rng = np.random.default_rng(9300 + bd)
+    plane = irc.fresh_plane(rng, bd)
+    rows = irc.random_rd_rows()
+    shapes = all_shapes()
+    extra = np.full(7 * 80 + 8, irc.PRED_GUARD, np.int16)
+    for c in range(7):
+        extra[c * 80:c * 80 + 64] = irc.noisy_pred(rng, plane[8:16, 8:16], bd).reshape(-1)
+    specs = []
+    for i in range(n):
+        w, h = shapes[(i * 7 + i // 25) % len(shapes)]
+        x, y = irc.place(rng, w, h, band=(0, 2, 1)[i % 3])
+        ns = int(rng.integers(1, 7))
+        tr = []
+        for k in range(ns):
+            r = int(rng.integers(0, 10))
+            tr.append(0 if r < 3 else TS if r == 3 else -1 if r == 4 and k < ns - 1 else int(rng.choice(EMT)) if r < 9 else int(rng.choice([1, 2, 3, 6, 10, -2, 100])))
+        if not any(slot_served(w, h, c) for c in tr):
+            tr[0] = 0
+        s = dict(x=x, y=y, w=w, h=h, tr=tr, qp=int(rng.integers(20, 36)) + 6 * (bd - 8), luma=int(rng.integers(0, 2)), lam=float(rng.uniform(5, 400)))
+        li = dict(x=8, y=8, w=8, h=8, pred_off=0, pred_stride=8, pred_cand_pitch=80)
+        if i % 9 == 4:
+            s.update(li, list_row=(i // 9) % 2, list_slot=(i // 18) % 4)
+        if i % 11 == 7:
+            kind = SKIP_KINDS[(i // 11) % len(SKIP_KINDS)]
+            if kind == "w2": s["w"] = 2
+            elif kind == "h2": s["h"] = 2
+            elif kind == "w3": s["w"] = 3
+            elif kind == "w128": s["w"] = 128
+            elif kind == "level_misalign4": s["level_misalign"] = 4
+            elif kind == "level_misalign8": s["level_misalign"] = 8
+            elif kind == "cand_misalign": s["cand_misalign"] = 2
+            elif kind == "rates_high": s["rates_idx"] = 8
+            elif kind == "rates_negative": s["rates_idx"] = -1
+            elif kind == "lambda_zero": s["lam"] = 0.0
+            else:
+                s.update(li, list_row=dict(list_null_row=2, list_slot_high=1, list_cand_bad=3)[kind], list_slot=dict(list_null_row=0, list_slot_high=1, list_cand_bad=0)[kind])
+        specs.append(s)
+    case = make(bd, plane, specs, rng, pred_extra=extra)
+    want = restate(case, rd_list=rows)
+    skipped = want["zero_dist"] == U64_MAX
+    assert skipped.sum() >= len(SKIP_KINDS) and (~skipped).sum() > 250
+    served = want["abs_sum"] != U32_MAX
+    assert ((case.items["tr"] == TS) & ~served).any() and not ((case.items["tr"] == TS) & served).any() and (np.isin(case.items["tr"], EMT) & served).any()
+    assert (served & (want["abs_sum"] > 0)).sum() * 3 >= served.sum()
+    return case, rows, want
+
+
+def count_case(served_slots, bd=10):
+    """small items whose served slots add up to `served_slots` (the trellis packs sixteen records into a wavefront, 64 into a workgroup); unused and
+    transform-skip slots between them"""
+    rng = np.random.default_rng(9400 + served_slots)
+    plane = irc.fresh_plane(rng, bd)
+    specs, left, i = [], served_slots, 0
+    while left > 0 or not specs:
+        w, h = ((4, 4), (8, 8), (8, 4), (16, 8), (4, 16))[i % 5]
+        k = min(left, 1 + i % 5)
+        tr = [(0, 4, 5, 7, 8)[j] for j in range(k)]
+        if i % 2:
+            tr = tr[:1] + [-1] + tr[1:]
+        if len(tr) < SLOTS and i % 3 == 0:
+            tr.append(TS)
+        x, y = irc.place(rng, w, h)
+        specs.append(dict(x=x, y=y, w=w, h=h, tr=tr if tr else [-1], qp=27 + 6 * (bd - 8)))
+        left -= k
+        i += 1
+    case = make(bd, plane, specs, rng)
+    want = restate(case)
+    assert (want["abs_sum"] != U32_MAX).sum() == served_slots
+    return case, want
+
+
+def all_skipped_case(bd=10):
+    rng = np.random.default_rng(9450)
+    plane = irc.fresh_plane(rng, bd)
+    specs = [dict(x=1, y=1, w=2, h=8), dict(x=1, y=1, w=8, h=8, level_misalign=4), dict(x=1, y=1, w=8, h=8, tr=[TS, 9, -1]), dict(x=1, y=1, w=16, h=2),
+             dict(x=1, y=1, w=8, h=8, rates_idx=99), dict(x=1, y=1, w=8, h=8, list_row=0, list_slot=0, pred_off=0, pred_stride=8, pred_cand_pitch=0)]
+    case = make(bd, plane, specs, rng)
+    want = restate(case)
+    assert (want["abs_sum"] == U32_MAX).all() and (want["zero_dist"] == U64_MAX).sum() == 5      # (the transform-skip item is served, none of its slots)
+    return case, want
+
+
+def workspace_cases(bd=10):
+    """two lists for one workspace: the first holds 64x64, 64x16 and 16x64 items (zeroed high-frequency regions), the second other shapes at the same offsets"""
+    out = []
+    for j, shapes in enumerate([[(64, 64), (64, 16), (16, 64), (32, 32), (8, 8), (64, 64)], [(16, 16), (32, 64), (64, 32), (8, 32), (4, 4), (64, 8), (32, 32)]]):
+        rng = np.random.default_rng(9480 + j)
+        plane = irc.fresh_plane(rng, bd)
+        specs = []
+        for k, (w, h) in enumerate(shapes):
+            x, y = irc.place(rng, w, h)
+            specs.append(dict(x=x, y=y, w=w, h=h, qp=(22, 27)[k % 2] + 6 * (bd - 8), tr=[0] + ([4, 8] if max(w, h) <= 32 else [])))
+        case = make(bd, plane, specs, rng)
+        out.append((case, restate(case)))
+    return out
+
+
+def last_threshold(w, h, qp, bd):
+    """Quantizer::initQuantBlock's m_thresLast (DepQuant.cpp:647-706): no coefficient above it -> DepQuant::quant returns at once"""
+    lw, lh = w.bit_length() - 1, h.bit_length() - 1
+    qp_dq = qp + 1
+    per, rem = divmod(qp_dq, 6)
+    qs = (26214, 23302, 20560, 18396, 16384, 14564)[rem]
+    q_scale = (qs * 181) >> 7 if (lw + lh) & 1 else qs
+    q_shift = 14 + per + (15 - bd - ((lw + lh) >> 1)) - 1
+    return (3 << q_shift) // (4 * q_scale)
+
+
+def forward(resi, bd, code=0):
+    h, w = resi.shape
+    tr = np.zeros(1, TR_DESC); tr[0] = (0, 0, w, w, h, code % 3, code // 3, 0, 0)
+    coef = np.zeros(w * h, np.int32)
+    oracle().orc_tr_fwd_batch(p(np.ascontiguousarray(resi)), p(coef), p(tr), 1, bd)
+    return coef
+
+
+def zero_case(bd):
+    """all-zero slots: pred == org, and a flat residual that is the largest whose coefficients stay at or under the trellis' last threshold (one more and
+    the DC coefficient exceeds it); every shape class"""
+    rng = np.random.default_rng(9500 + bd)
+    plane = irc.fresh_plane(rng, bd)
+    specs = []
+    for (w, h) in [(4, 4), (8, 8), (16, 16), (32, 8), (64, 64), (32, 32), (4, 16), (64, 16)]:
+        x, y = irc.place(rng, w, h, band=1)
+        org = plane[y:y + h, x:x + w].astype(np.int32)
+        under = lambda v, qp: np.abs(forward(np.full((h, w), v, np.int16), bd)).max() <= last_threshold(w, h, qp, bd)
+        # the largest QP at which the largest flat residual under the threshold is small (the threshold grows with the transform shift of the shape)
+        qp = next(q for q in range(irc.max_qp(bd), 0, -6) if under(1, q) and not under(39, q))
+        v = max(v for v in range(1, 40) if under(v, qp))
+        assert not under(v + 1, qp) and org.min() >= v
+        specs.append(dict(x=x, y=y, w=w, h=h, pred=org, qp=qp, tr=[0, 4] if max(w, h) <= 32 else [0]))
+        specs.append(dict(x=x, y=y, w=w, h=h, pred=org - v, qp=qp, tr=[0]))
+    case = make(bd, plane, specs, rng)
+    want = restate(case, WRITE_REC)
+    served = want["abs_sum"] != U32_MAX
+    assert served.sum() >= 20 and (want["abs_sum"][served] == 0).all() and (want["zero_dist"][1::2] > 0).all()
+    return case, want
+
+
+def clip_case(bd):
+    """predictions AT the clip bounds with an original just inside: resi' overshoots and the clip bites, dist_rec != dist_resi"""
+    rng = np.random.default_rng(9700 + bd)
+    mx = (1 << bd) - 1
+    plane = irc.fresh_plane(rng, bd)
+    specs = []
+    for k, (w, h) in enumerate([(4, 4), (8, 8), (16, 16), (32, 32), (64, 64), (8, 4), (16, 4), (64, 32)]):
+        x, y = irc.place(rng, w, h, band=0 if k % 2 else 2)
+        specs.append(dict(x=x, y=y, w=w, h=h, pred=np.full((h, w), 0 if k % 2 else mx, np.int16), qp=27 + 6 * (bd - 8), lam=30.0))
+    case = make(bd, plane, specs, rng)
+    want = restate(case)
+    served = want["abs_sum"] != U32_MAX
+    assert (want["dist_rec"][served] != want["dist_resi"][served]).sum() * 2 >= served.sum()
+    return case, want
+
+
+def chain_case(bd=10):
+    """every shape, DCT-II and the EMT pairs where the sides allow them, given predictions only: what the eight-launch chain serves"""
+    rng = np.random.default_rng(77)
+    plane = irc.fresh_plane(rng, bd)
+    specs = []
+    for k, (w, h) in enumerate(all_shapes()):
+        x, y = irc.place(rng, w, h)
+        specs.append(dict(x=x, y=y, w=w, h=h, qp=(22, 27, 32, 37)[k % 4] + 6 * (bd - 8), luma=k % 2, tr=[0] + (list(EMT) if w <= 32 and h <= 32 else [])))
+    return make(bd, plane, specs, rng)
+
+
+HANDOVER_SLOTS = irc.HANDOVER_SLOTS
+
+
+def handover_case(bd):
+    """the sibling's hand-over list (vvcgpu_merge_cand_batch rows with 0, 1 and 4 survivors; list items for slots 0 .. 3 per PU and component); chroma
+    blocks with a side of 2 are skipped items here -> (frame, layout, merge restatement, Case, restatement)"""
+    fr, L, mwant, base, _ = irc.handover_case(bd)
+    dq = np.zeros(len(base.items), DQ)
+    lo = 16
+    for i, it in enumerate(base.items):
+        it["level_off"] = lo
+        lo += (SLOTS * int(it["w"]) * int(it["h"]) + 15) // 16 * 16 + 16 * (i % 2)
+        qp8 = int(it["qp"]) - 6 * (bd - 8)
+        dq[i] = (0.57 * 2.0 ** ((qp8 - 12) / 3.0), i % 8, 1 if i % 12 < 4 else 0, (0, 0, 0))
+    base.level_size = lo + 16
+    case = Case(base, dq, shared_rates())
+    want = restate(case, WRITE_REC, rd_list=mwant["rd_list"])
+    li = case.items["list_row"] >= 0
+    assert li.all() and ((want["zero_dist"] != U64_MAX) & li).sum() * 2 >= li.sum()
+    return fr, L, mwant, case, want
+
+
+# ---- the golden file -------------------------------------------------------------------------------------------------------------------------------
+def golden_case(g, bd):
+    k = "bd%d_" % bd
+    base = irc.Case(bd, g[k + "org"], g[k + "pred"], g[k + "items"].view(ITEM).reshape(-1), int(g[k + "cand_size"]), int(g[k + "level_size"]))
+    return Case(base, g[k + "dq"].view(DQ).reshape(-1), g[k + "rates"].view(RATES).reshape(-1))

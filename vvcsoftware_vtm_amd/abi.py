@@ -132,6 +132,9 @@ INTER_RESI_ITEM = np.dtype([("org_off", "<i8"), ("pred_off", "<i8"), ("pred_cand
                             ("list_slot", "i1"), ("intra_slice", "i1"), ("sign_hiding", "i1"), ("reserved", "i1"), ("tr", "i1", (6,)),
                             ("reserved1", "i1", (2,)), ("reserved2", "<i4", (2,))])
 INTER_RESI_SLOTS, INTER_RESI_TS, INTER_RESI_WRITE_REC = 6, 9, 1
+# vvcgpu_inter_resi_code_dq_batch: the record beside an item (vvcgpu_inter_resi_dq) and the served value of `quantiser`
+INTER_RESI_DQ = np.dtype([("lambda", "<f8"), ("rates_idx", "<i4"), ("luma", "i1"), ("reserved", "i1", (3,))])
+INTER_RESI_Q_DEPQUANT = 1
 
 # ---- affine motion --------------------------------------------------------------------------------------------------------------
 AFG_DESC = np.dtype([("pred_off", "<i8"), ("deriv_off", "<i8"), ("pred_stride", "<i4"), ("deriv_stride", "<i4"), ("w", "<i2"), ("h", "<i2"),

@@ -1,0 +1,461 @@
+// interresidq.hip -- vvcgpu_inter_resi_code_dq_batch: the pixel pass of the inter residual RD loop (interresi.hip) with the quantiser of the shipped
+// configurations, the dependent-quantisation trellis, in three launches on the caller's stream.
+//
+// Reference behaviour reproduced (bit-exact):
+//   InterSearch::encodeResAndCalcRdInterCU / xEstimateInterResidualQT "check full"                EncoderLib/InterSearch.cpp:4752-4909, :4254-4634 (see interresi.hip)
+//   transformNxN :4409 under slice->getDepQuantEnabledFlag(): xT (TrQuant.cpp:694-739), DQIntern::DepQuant::quant   CommonLib/DepQuant.cpp:1323-1387
+//   invTransformNxN :4497: DQIntern::Quantizer::dequantBlock :708-785, xIT (TrQuant.cpp:743-791)
+//
+// Design (docs/KERNELS.md, "The inter residual pass with DepQuant"):
+//   front    persistent workgroups of eight wavefronts, a wavefront per item: validity and the rd_list look-up, orgResi = org - pred staged once in the
+//            wavefront's LDS tile, zero_dist, per served slot the forward transform (the RC_FWD bodies of resichain_dev.h) into the coefficient workspace
+//            -- the zeroed region of a 64-point side written as zeros: the trellis reads all w h coefficients -- and the slot's trellis record, whose
+//            index 6 i + k it appends to the work list (one atomic add per wavefront on a counter of vvcgpu_counters).  A skipped item or slot gets its
+//            markers here and no list entry.
+//   trellis  tq_trellis<true> (depquant_dev.h: depquant_kernel's body with a work list) over the listed records: four lanes per TU, sixteen TUs per wavefront; levels and abs_sum of the served
+//            slots.  The grid is sized for 6 n records; workgroups behind the list's end leave at once.
+//   back     the same wavefront-per-item walk: orgResi and the prediction re-formed in the tile; per served slot the dependent de-quantiser (the
+//            GF(2)-linear state replay, as dq_group of transform.hip) into the coefficient workspace, the inverse transform (RC_INV bodies), resi'
+//            unclipped to the candidate buffer, both distortions and the reconstruction as interresi.hip's.  A slot with abs_sum == 0 stores zeros.
+#include "common.h"
+#include "depquant_dev.h"
+#include "dist_dev.h"
+#include "mfma_tr.h"
+#include "quant_dev.h"
+#include "resichain_dev.h"
+
+static_assert(sizeof(vvcgpu_inter_resi_item) == 80 && sizeof(vvcgpu_inter_resi_dq) == 16 && sizeof(vvcgpu_depquant_desc) == 40, "descriptor layouts");
+
+namespace {
+
+typedef vvcgpu_inter_resi_item IrItem;
+typedef vvcgpu_inter_resi_dq IrDq;
+constexpr int IQ_SLOTS = VVCGPU_INTER_RESI_SLOTS;
+constexpr int IQ_WAVES = 8, IQ_THREADS = 64 * IQ_WAVES;
+constexpr int IQ_TILE = 64 * 64;                                          // samples of a wavefront's tile (interresi.hip: orgResi, the prediction, resi')
+constexpr int IQ_TAB_BYTES = RC_TAB_HALVES * 2;                           // the f16 matrices of the matrix-core bodies
+constexpr int IQ_WAVE_BYTES = IQ_TILE * 2 + IQ_SLOTS * (int)sizeof(vvcgpu_resi_chain_desc);      // the tile, a chain descriptor per slot
+constexpr int IQ_LDS_BYTES = IQ_TAB_BYTES + IQ_WAVES * IQ_WAVE_BYTES;
+static_assert(IQ_TAB_BYTES % 16 == 0 && IQ_WAVE_BYTES % 16 == 0 && IQ_LDS_BYTES <= 160 * 1024, "LDS budget");
+constexpr int IQ_LIST_INTS = 8, IQ_LIST_MAX = 7;                          // a row of rd_list_out of vvcgpu_merge_cand_batch: [0] count, [1 .. 7] RdModeList
+constexpr size_t IQ_WS_SLACK = 4096 * sizeof(TCoeff) + 256;               // a quad of the trellis that walks along with a larger TU of its wavefront reads up to 4095 coefficients past its own
+
+struct IqArgs
+{
+  const Pel* org; const Pel* pred; const IrItem* items; const IrDq* dq; const int* rdList; Pel* resi; Pel* rec; TCoeff* level;
+  unsigned* absSum; unsigned long long* distResi; unsigned long long* distRec; unsigned long long* zeroDist; int* fbScratch; const _Float16* image;
+  TCoeff* coef; vvcgpu_depquant_desc* recs; int* list; int* count; int* nextCounters; long long levelExtent;
+  int n, nRates, writeRec, bd, cmin, cmax;
+};
+
+inline __host__ __device__ bool iq_side_ok(int v) { return v >= 4 && v <= 64 && (v & (v - 1)) == 0; }
+
+__device__ __forceinline__ void iq_wave_sync() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }
+// stores of the wavefront to global memory, read back by other lanes of it
+__device__ __forceinline__ void iq_global_sync()
+{
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+}
+
+// is the item served, and where is its prediction?  (the rules of interresi.hip; here also: no side of 2, level_off a multiple of 16 -- the trellis
+// workspace is indexed by it --, a rate table inside the array, a lambda above zero)
+__device__ __forceinline__ bool iq_item_ok(const IqArgs& a, const IrItem& t, const IrDq& q, long long& predOff)
+{
+  predOff = t.pred_off;
+  bool ok = iq_side_ok(t.w) && iq_side_ok(t.h) && (t.cand_off & 3) == 0 && (t.level_off & 15) == 0 && t.level_off >= 0
+            && q.rates_idx >= 0 && q.rates_idx < a.nRates && q.lambda > 0.0;
+  if (ok && t.list_row >= 0)
+  {
+    const int slot = t.list_slot;
+    ok = a.rdList != nullptr && slot >= 0 && slot < IQ_LIST_MAX;
+    if (ok) ok = slot < a.rdList[IQ_LIST_INTS * (size_t)t.list_row];
+    if (ok)
+    {
+      const int c = a.rdList[IQ_LIST_INTS * (size_t)t.list_row + 1 + slot];
+      ok = c >= 0 && c < IQ_LIST_MAX;
+      predOff += (long long)c * t.pred_cand_pitch;
+    }
+  }
+  return ok;
+}
+// the served slots of a served item: DCT-II and the DCT-VIII / DST-VII pairs on sides up to 32, the slot's levels inside level_extent
+__device__ __forceinline__ unsigned iq_served_mask(const IqArgs& a, const IrItem& t)
+{
+  const int w = t.w, h = t.h, samples = w * h;
+  unsigned long long trBits;
+  __builtin_memcpy(&trBits, t.tr, 8);
+  unsigned mask = 0u;
+#pragma unroll
+  for (int k = 0; k < IQ_SLOTS; k++)
+  {
+    const int code = (int)(signed char)(trBits >> (8 * k));
+    const int th = code % 3, tv = code / 3;
+    if (code >= 0 && code < 9 && (th == 0 || w <= 32) && (tv == 0 || h <= 32) && t.level_off + (long long)(k + 1) * samples <= a.levelExtent) mask |= 1u << k;
+  }
+  return mask;
+}
+__device__ __forceinline__ int iq_code(const IrItem& t, int k)
+{
+  unsigned long long trBits;
+  __builtin_memcpy(&trBits, t.tr, 8);
+  return (int)(signed char)(trBits >> (8 * k));
+}
+
+// orgResi = org - pred into the tile (and the prediction into predT, if there is room for it) -> sum orgResi^2 over the wavefront
+__device__ __forceinline__ unsigned long long iq_stage(const IrItem& t, const Pel* __restrict__ org, const Pel* __restrict__ predG, short* resiT, short* predT, int lane)
+{
+  const int w = t.w, samples = w * t.h, lw = ilog2(w);
+  unsigned long long zd = 0ull;
+  for (int e0 = lane; e0 < samples; e0 += 256)                             // four loads of each plane in flight
+  {
+    int ov[4], pv[4];
+#pragma unroll
+    for (int u = 0; u < 4; u++)
+    {
+      const int e = e0 + 64 * u, r = e >> lw, x = e & (w - 1);
+      ov[u] = pv[u] = 0;
+      if (e < samples) { pv[u] = predG[(ptrdiff_t)r * t.pred_stride + x]; ov[u] = org[(ptrdiff_t)r * t.org_stride + x]; }
+    }
+#pragma unroll
+    for (int u = 0; u < 4; u++)
+    {
+      const int e = e0 + 64 * u, df = ov[u] - pv[u];
+      if (e < samples)
+      {
+        resiT[e] = (short)df;
+        if (predT) predT[e] = (short)pv[u];
+      }
+      const unsigned ad = (unsigned)abs(df);
+      zd += (unsigned long long)(ad * ad);
+    }
+  }
+  return group_sum_u64<64>(zd);
+}
+
+// the chain descriptor of slot k for the transform bodies: the residual in the tile, the coefficients at the slot's place in the workspace
+__device__ __forceinline__ RcDesc iq_desc(const IrItem& t, int k, long long recOff)
+{
+  const int code = iq_code(t, k), samples = t.w * t.h;
+  RcDesc u;
+  u.org_off = 0; u.pred_off = 0; u.rec_off = recOff; u.level_off = t.level_off + (long long)k * samples;
+  u.org_stride = t.w; u.pred_stride = t.w; u.rec_stride = t.w; u.w = t.w; u.h = t.h;
+  u.tr_hor = (int8_t)(code % 3); u.tr_ver = (int8_t)(code / 3); u.intra_slice = 0; u.sign_hiding = 0; u.qp = t.qp;
+  u.reserved[0] = 0; u.reserved[1] = 0;
+  return u;
+}
+
+// the transform bodies as real calls (the descriptor and the tile are the wavefront's, in LDS)
+template <int W, int H, int MODE>
+__device__ __noinline__ bool iq_tu_mfma_call(const RcDesc* dS, const Pel* tile, Pel* __restrict__ outBase, TCoeff* __restrict__ coefBase, int bd, const _Float16* tab,
+                                             const unsigned short* __restrict__ dqInv, const int* __restrict__ scanOff, int lane)
+{
+  RC_IS_LDS(dS); RC_IS_LDS(tile); RC_IS_LDS(tab);
+  return rc_tu_mfma<W, H, MODE>(*dS, tile, tile, outBase, coefBase, nullptr, 0, bd, 0, 0, tab, dqInv, scanOff, lane);
+}
+template <int MODE>
+__device__ __noinline__ void iq_tu_generic_call(const RcDesc* dS, const Pel* tile, Pel* __restrict__ outBase, TCoeff* __restrict__ coefBase, int bd,
+                                                const int* __restrict__ tr32, const unsigned short* __restrict__ dqInv, const int* __restrict__ scanOff,
+                                                int* bufA, int* bufB, int lane)
+{
+  rc_tu_generic<MODE>(*dS, tile, tile, outBase, coefBase, nullptr, 0, bd, 0, 0, tr32, dqInv, scanOff, bufA, bufB, lane, nullptr);
+}
+// one slot through the forward (MODE RC_FWD: tile -> coefficients) or the inverse transform (RC_INV: coefficients -> outBase + rec_off)
+template <int MODE>
+__device__ __forceinline__ void iq_transform(const RcDesc* dS, short* resiT, Pel* outBase, TCoeff* coefBase, int bd, const _Float16* tab, const VvcTrTables& tb,
+                                             int* fbScr, int lane)
+{
+  const int w = dS->w, h = dS->h;
+  if (w <= 8 || h <= 8)                                                   // at most 512 samples: the integer body, its two buffers behind them in the tile
+  {
+    iq_tu_generic_call<MODE>(dS, resiT, outBase, coefBase, bd, tb.tr32, tb.dqInv, tb.scanOff, reinterpret_cast<int*>(resiT + 1024), reinterpret_cast<int*>(resiT + 2048), lane);
+    return;
+  }
+  bool done = true;
+#define IQ_MF(W_, H_) case ((W_) << 8) | (H_): done = iq_tu_mfma_call<W_, H_, MODE>(dS, resiT, outBase, coefBase, bd, tab, tb.dqInv, tb.scanOff, lane); break;
+  switch ((w << 8) | h)
+  {
+  IQ_MF(16, 16) IQ_MF(16, 32) IQ_MF(16, 64) IQ_MF(32, 16) IQ_MF(32, 32) IQ_MF(32, 64) IQ_MF(64, 16) IQ_MF(64, 32) IQ_MF(64, 64)
+  default: break;
+  }
+#undef IQ_MF
+  if (!done)                                                              // samples outside the bit depth (out of contract): exact all the same
+    iq_tu_generic_call<MODE>(dS, resiT, outBase, coefBase, bd, tb.tr32, tb.dqInv, tb.scanOff, fbScr, fbScr + 4096, lane);
+}
+
+__device__ __forceinline__ _Float16* iq_load_tables(unsigned char* smem, const _Float16* image, int tid)
+{
+  _Float16* const tab = reinterpret_cast<_Float16*>(smem);
+  const uint4* src = reinterpret_cast<const uint4*>(image);
+  for (int i = tid; i < IQ_TAB_BYTES / 16; i += IQ_THREADS) reinterpret_cast<uint4*>(tab)[i] = src[i];
+  __syncthreads();                                                        // the only workgroup barrier: below every wavefront walks its own items
+  return tab;
+}
+
+// ---------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(IQ_THREADS, 1) void inter_resi_dq_front_kernel(const IqArgs a, const VvcTrTables tb)
+{
+  extern __shared__ __align__(16) unsigned char smem[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const _Float16* const tab = iq_load_tables(smem, a.image, tid);
+  unsigned char* const mine = smem + IQ_TAB_BYTES + (size_t)wave * IQ_WAVE_BYTES;
+  short* const resiT = reinterpret_cast<short*>(mine);
+  RcDesc* const dS = reinterpret_cast<RcDesc*>(resiT + IQ_TILE);
+  int* const fbScr = a.fbScratch + ((size_t)blockIdx.x * IQ_WAVES + wave) * 8192;
+  if (blockIdx.x == 0 && tid < VVC_CTR_INTS) a.nextCounters[tid] = 0;    // the counter set of the NEXT call on this stream (vvcgpu_counters)
+
+  // the wavefront's run in the trellis' work list: its served slots are counted first, a lane per item, so that the counter sees one atomic add per
+  // wavefront (one per item, 94 000 on one address for the 4K list, took 0.9 ms)
+  const int first = (int)blockIdx.x * IQ_WAVES + wave, step = (int)gridDim.x * IQ_WAVES;
+  int listAt = 0;
+  {
+    int cnt = 0;
+    for (int item = first + lane * step; item < a.n; item += 64 * step)
+    {
+      const IrItem t = a.items[item];
+      long long predOff;
+      if (iq_item_ok(a, t, a.dq[item], predOff)) cnt += __popc(iq_served_mask(a, t));
+    }
+    cnt = wave_sum_i32(cnt);
+    if (cnt && lane == 0) listAt = atomicAdd(a.count, cnt);
+    listAt = __builtin_amdgcn_readfirstlane(listAt);
+  }
+
+  for (int item = first; item < a.n; item += step)
+  {
+    const IrItem t = a.items[item];
+    const IrDq q = a.dq[item];
+    long long predOff;
+    const bool ok = iq_item_ok(a, t, q, predOff);
+    const unsigned servedMask = ok ? iq_served_mask(a, t) : 0u;
+    if (lane < IQ_SLOTS)                                                  // the slot's trellis record and list entry; the markers of a skipped slot
+    {
+      const size_t out = IQ_SLOTS * (size_t)item + lane;
+      if ((servedMask >> lane) & 1u)
+      {
+        vvcgpu_depquant_desc r;
+        r.coeff_off = r.level_off = t.level_off + (long long)lane * t.w * t.h;
+        r.lambda = q.lambda; r.qp = t.qp; r.rates_idx = q.rates_idx; r.w = t.w; r.h = t.h; r.luma = q.luma;
+        r.reserved[0] = r.reserved[1] = r.reserved[2] = 0;
+        a.recs[out] = r;
+        a.list[listAt + __popc(servedMask & ((1u << lane) - 1u))] = (int)out;
+      }
+      else { a.absSum[out] = 0xFFFFFFFFu; a.distResi[out] = ~0ull; a.distRec[out] = ~0ull; }
+    }
+    listAt += __popc(servedMask);
+    if (!ok)
+    {
+      if (lane == 0) a.zeroDist[item] = ~0ull;
+      continue;
+    }
+    const unsigned long long zd = iq_stage(t, a.org + t.org_off, a.pred + predOff, resiT, nullptr, lane);
+    if (lane == 0) a.zeroDist[item] = zd;
+    if (lane < IQ_SLOTS && ((servedMask >> lane) & 1u)) dS[lane] = iq_desc(t, lane, 0);
+    iq_wave_sync();
+    for (int k = 0; k < IQ_SLOTS; k++)
+    {
+      if (!((servedMask >> k) & 1u)) continue;
+      iq_transform<RC_FWD>(dS + k, resiT, nullptr, a.coef, a.bd, tab, tb, fbScr, lane);
+      iq_wave_sync();
+    }
+    iq_wave_sync();                                                       // the tile and the descriptors are free again
+  }
+}
+
+__global__ __launch_bounds__(256) void inter_resi_dq_trellis_kernel(const TCoeff* __restrict__ coeffBase, TCoeff* __restrict__ levelBase,
+                                                                    const vvcgpu_depquant_desc* __restrict__ descs, const int* __restrict__ list,
+                                                                    const int* __restrict__ count,
+                                                                    const vvcgpu_dq_rates* __restrict__ ratesBase, int bd, unsigned* __restrict__ absSumOut,
+                                                                    unsigned* __restrict__ wsDec, unsigned char* __restrict__ wsCtx, VvcTrTables tb)
+{
+  const int n = *count;                                                   // the served slots of the call, counted by the front
+  if ((int)blockIdx.x * 64 >= n) return;
+  tq_trellis<true>(coeffBase, levelBase, descs, list, n, ratesBase, bd, absSumOut, wsDec, wsCtx, tb);
+}
+
+// DQIntern::Quantizer::dequantBlock (DepQuant.cpp:708-785) of one TU by the wavefront: levels -> coefficients, both w x h with row pitch w.  The 4-state
+// machine is linear over GF(2) (transform.hip, dq_group): with steps counted from the END of the scan, the state bit that enters the reconstruction of
+// step t is the xor of the level parities of the earlier steps of the other step parity.  A lane takes a run of consecutive steps, folds its parities by
+// step parity, a ballot gives the prefix over the lanes in front of it, a second pass reconstructs.
+__device__ __forceinline__ void iq_dequant(const TCoeff* __restrict__ level, TCoeff* __restrict__ coef, int w, int h, int qp, int bd,
+                                           const unsigned short* __restrict__ scan, int lane)
+{
+  const int lw = ilog2(w), lh = ilog2(h), cnt = w * h;
+  const VqInv dep = vq_inv(qp + 1, vq_transform_shift(bd, lw, lh), vq_sqrt2(lw, lh));      // scale and shift of qp + 1 with one more bit (:758-759)
+  int shift = dep.rightShift + 1;
+  long long scale = dep.scale;
+  if (shift < 0) { scale <<= -shift; shift = 0; }
+  const long long add = (1ll << shift) >> 1;
+  const int C = cnt >= 64 ? cnt >> 6 : 1, t0 = lane * C, t1 = min(t0 + C, cnt);
+  int a0 = 0, a1 = 0;
+  for (int t = t0; t < t1; t++)
+  {
+    const int lv = level[scan[cnt - 1 - t]];
+    if (t & 1) a1 ^= lv; else a0 ^= lv;
+  }
+  const unsigned long long B0 = __builtin_amdgcn_ballot_w64((a0 & 1) != 0), B1 = __builtin_amdgcn_ballot_w64((a1 & 1) != 0);
+  const unsigned long long below = (1ull << lane) - 1ull;
+  int x0 = (int)__popcll(B0 & below) & 1, x1 = (int)__popcll(B1 & below) & 1;
+  for (int t = t0; t < t1; t++)
+  {
+    const int pos = scan[cnt - 1 - t], lv = level[pos], hi = (t & 1) ? x0 : x1;
+    int v = 0;
+    if (lv != 0)
+    {
+      const int qIdx = 2 * lv + (lv > 0 ? -hi : hi);
+      v = (int)min(max(((long long)qIdx * scale + add) >> shift, -(1ll << 15)), (1ll << 15) - 1);
+    }
+    coef[pos] = v;
+    if (t & 1) x1 ^= lv & 1; else x0 ^= lv & 1;
+  }
+}
+
+__global__ __launch_bounds__(IQ_THREADS, 1) void inter_resi_dq_back_kernel(const IqArgs a, const VvcTrTables tb)
+{
+  extern __shared__ __align__(16) unsigned char smem[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const _Float16* const tab = iq_load_tables(smem, a.image, tid);
+  unsigned char* const mine = smem + IQ_TAB_BYTES + (size_t)wave * IQ_WAVE_BYTES;
+  short* const resiT = reinterpret_cast<short*>(mine);
+  RcDesc* const dS = reinterpret_cast<RcDesc*>(resiT + IQ_TILE);
+  int* const fbScr = a.fbScratch + ((size_t)blockIdx.x * IQ_WAVES + wave) * 8192;
+
+  for (int item = (int)blockIdx.x * IQ_WAVES + wave; item < a.n; item += (int)gridDim.x * IQ_WAVES)
+  {
+    const IrItem t = a.items[item];
+    const IrDq q = a.dq[item];
+    long long predOff;
+    if (!iq_item_ok(a, t, q, predOff)) continue;                          // (the front wrote the markers)
+    const unsigned servedMask = iq_served_mask(a, t);
+    if (!servedMask) continue;
+    const int w = t.w, h = t.h, lw = ilog2(w), samples = w * h;
+    // the tile as interresi.hip lays it out: orgResi at 0; behind it the prediction and -- up to 1024 samples -- the place where the body leaves resi'
+    // (`back`); a shape with a side of at most 8 also has the integer body's two buffers there.  64 x 64 fills the tile: its prediction is read again,
+    // and 2048 samples and more return resi' through the candidate buffer.
+    const bool narrow = w <= 8 || h <= 8;
+    short* const predT = samples > 2048 ? nullptr : resiT + (narrow ? 512 : samples <= 1024 ? 1024 : 2048);
+    short* const backT = narrow ? resiT + 3072 : samples <= 1024 ? resiT + 2048 : nullptr;
+    const Pel* const predG = a.pred + predOff;
+    iq_stage(t, a.org + t.org_off, predG, resiT, predT, lane);
+    if (lane < IQ_SLOTS && ((servedMask >> lane) & 1u)) dS[lane] = iq_desc(t, lane, backT ? 0 : t.cand_off + (long long)lane * samples);
+    iq_wave_sync();
+
+    const unsigned short* const scan = tb.scan + tb.scanOff[(lw - 1) * 6 + (ilog2(h) - 1)];
+    Pel* const outBase = backT ? backT : a.resi;
+    for (int k = 0; k < IQ_SLOTS; k++)
+    {
+      if (!((servedMask >> k) & 1u)) continue;
+      const size_t out = IQ_SLOTS * (size_t)item + k;
+      const long long candOff = t.cand_off + (long long)k * samples, levelOff = t.level_off + (long long)k * samples;
+      Pel* const rs = a.resi + candOff;
+      if (a.absSum[out] == 0u)                                            // all levels zero: resi' is stored as zeros
+      {
+        for (int e = lane; e < samples; e += 64) { if (backT) backT[e] = 0; else rs[e] = 0; }
+      }
+      else
+      {
+        iq_dequant(a.level + levelOff, a.coef + levelOff, w, h, t.qp, a.bd, scan, lane);
+        iq_global_sync();
+        iq_transform<RC_INV>(dS + k, resiT, outBase, a.coef, a.bd, tab, tb, fbScr, lane);
+      }
+      if (backT) iq_wave_sync(); else iq_global_sync();
+      // xGetSSE(orgResi, resi') and xGetSSE(org, clip(pred + resi')) from resi' where the body left it; resi' (from `back`) and the reconstruction go
+      // to the candidate buffers on the way
+      Pel* const rec = a.writeRec ? a.rec + candOff : nullptr;
+      unsigned long long dr = 0ull, dc = 0ull;                            // 64 x 64 x 1023^2 is beyond 2^31
+      for (int e = lane; e < samples; e += 64)
+      {
+        int r2;
+        if (backT) { r2 = backT[e]; rs[e] = (short)r2; }
+        else r2 = rs[e];
+        const int o = resiT[e], pv = predT ? (int)predT[e] : (int)predG[(ptrdiff_t)(e >> lw) * t.pred_stride + (e & (w - 1))];
+        const int rc = clip3(a.cmin, a.cmax, pv + r2);
+        const unsigned d1 = (unsigned)abs(o - r2), d2 = (unsigned)abs(o + pv - rc);
+        dr += (unsigned long long)(d1 * d1);
+        dc += (unsigned long long)(d2 * d2);
+        if (rec) rec[e] = (short)rc;
+      }
+      dr = group_sum_u64<64>(dr);
+      dc = group_sum_u64<64>(dc);
+      if (lane == 0) { a.distResi[out] = dr; a.distRec[out] = dc; }
+      iq_wave_sync();                                                     // `back` and the integer body's buffers are free again
+    }
+    iq_wave_sync();                                                       // the tile and the descriptors are free again
+  }
+}
+
+inline size_t iq_extent16(size_t level_extent) { return (level_extent + 15) & ~(size_t)15; }
+
+}  // namespace
+
+extern "C" {
+
+size_t vvcgpu_inter_resi_code_dq_workspace_bytes(size_t level_extent, int n)
+{
+  const size_t c = iq_extent16(level_extent);
+  // the coefficients, the trellis decisions and level histories (all indexed by the slot's level offset), per slot a trellis record and a list entry
+  return c * sizeof(TCoeff) + tq_dec_bytes(c) + tq_ctx_bytes(c) + (size_t)(n > 0 ? n : 0) * IQ_SLOTS * (sizeof(vvcgpu_depquant_desc) + sizeof(int)) + IQ_WS_SLACK;
+}
+
+int vvcgpu_inter_resi_code_dq_batch(const vvc_pel* org_base, const vvc_pel* pred_base, const vvcgpu_inter_resi_item* items, const vvcgpu_inter_resi_dq* dq,
+                                    int n, const int32_t* rd_list, const vvcgpu_dq_rates* rates, int n_rates, int quantiser,
+                                    vvc_pel* resi_base, vvc_pel* rec_base, vvc_coef* level_base, size_t level_extent,
+                                    int flags, int bit_depth, int clp_min, int clp_max,
+                                    uint32_t* abs_sum, uint64_t* dist_resi, uint64_t* dist_rec, uint64_t* zero_dist, void* ws, size_t ws_bytes, void* stream)
+{
+  const char* name = "inter_resi_code_dq_batch";
+  VVC_CHECK_ARG(n >= 0, "%s: n %d", name, n);
+  if (n == 0) return VVCGPU_OK;
+  VVC_CHECK_ARG(org_base && pred_base && items && dq && rates && resi_base && level_base && abs_sum && dist_resi && dist_rec && zero_dist && ws,
+                "%s: null pointer", name);
+  VVC_CHECK_ARG((flags & ~VVCGPU_INTER_RESI_WRITE_REC) == 0, "%s: unknown flags 0x%x", name, flags);
+  VVC_CHECK_ARG(rec_base || !(flags & VVCGPU_INTER_RESI_WRITE_REC), "%s: null pointer (rec_base with VVCGPU_INTER_RESI_WRITE_REC)", name);
+  VVC_CHECK_ARG(clp_min <= clp_max && clp_min >= -32768 && clp_max <= 32767, "%s: clip range %d..%d", name, clp_min, clp_max);
+  VVC_CHECK_ARG(((uintptr_t)items & 15) == 0 && ((uintptr_t)dq & 7) == 0, "%s: item array must be 16-byte, dq array 8-byte aligned", name);
+  VVC_CHECK_ARG(n_rates > 0, "%s: n_rates %d", name, n_rates);
+  VVC_CHECK_ARG(level_extent >= 16 && level_extent < ((size_t)1 << 40), "%s: level_extent %zu", name, level_extent);
+  VVC_CHECK_ARG(ws_bytes >= vvcgpu_inter_resi_code_dq_workspace_bytes(level_extent, n) && ((uintptr_t)ws & 15) == 0,
+                "%s: workspace of %zu bytes for a level extent of %zu and %d items is too small (need %zu) or unaligned", name, ws_bytes, level_extent, n,
+                vvcgpu_inter_resi_code_dq_workspace_bytes(level_extent, n));
+  if (quantiser != VVCGPU_INTER_RESI_Q_DEPQUANT) { vvcgpu_set_error("%s: quantiser %d is not served", name, quantiser); return VVCGPU_E_UNSUPPORTED; }
+  if (bit_depth > 10 || bit_depth < 8) { vvcgpu_set_error("%s: bit depth %d outside 8..10", name, bit_depth); return VVCGPU_E_UNSUPPORTED; }
+  hipStream_t st = (hipStream_t)stream;
+  VvcTrTables tb; const _Float16* image = nullptr;
+  const int rt = vvcgpu_tr_images(&tb, &image);
+  if (rt) return rt;
+  const int cap = vvcgpu_cu_count(), wgs = cdiv(n, IQ_WAVES) < cap ? cdiv(n, IQ_WAVES) : cap;
+  VVC_HIP(vvc_allow_lds(inter_resi_dq_front_kernel, IQ_LDS_BYTES));
+  VVC_HIP(vvc_allow_lds(inter_resi_dq_back_kernel, IQ_LDS_BYTES));
+  VVC_HIP(vvc_allow_lds(inter_resi_dq_trellis_kernel, TQ_LDS_BYTES));
+  int cur = 0;
+  int* counters = vvcgpu_counters(st, &cur);                              // the list's length: zero on entry, the front clears the other set
+  if (!counters) return VVCGPU_E_DEVICE;
+  VvcScratch sc(st);
+  int* fbScratch = sc.take<int>((size_t)wgs * IQ_WAVES * 8192);           // per wavefront two 4096-int buffers, touched only for an item outside the matrix-core range
+  if (!fbScratch) { vvcgpu_counters_failed(st); return VVCGPU_E_DEVICE; }
+  // the workspace as vvcgpu_inter_resi_code_dq_workspace_bytes lays it out
+  const size_t c = iq_extent16(level_extent);
+  unsigned char* const w8 = static_cast<unsigned char*>(ws);
+  TCoeff* coef = reinterpret_cast<TCoeff*>(w8);
+  unsigned* dec = reinterpret_cast<unsigned*>(w8 + c * sizeof(TCoeff));
+  unsigned char* ctx = w8 + c * sizeof(TCoeff) + tq_dec_bytes(c);
+  vvcgpu_depquant_desc* recs = reinterpret_cast<vvcgpu_depquant_desc*>(w8 + c * sizeof(TCoeff) + tq_dec_bytes(c) + tq_ctx_bytes(c));
+  IqArgs a;
+  a.org = org_base; a.pred = pred_base; a.items = items; a.dq = dq; a.rdList = rd_list; a.resi = resi_base; a.rec = rec_base; a.level = level_base;
+  a.absSum = abs_sum; a.distResi = reinterpret_cast<unsigned long long*>(dist_resi); a.distRec = reinterpret_cast<unsigned long long*>(dist_rec);
+  a.zeroDist = reinterpret_cast<unsigned long long*>(zero_dist); a.fbScratch = fbScratch; a.image = image;
+  a.coef = coef; a.recs = recs; a.list = reinterpret_cast<int*>(recs + (size_t)n * IQ_SLOTS);
+  a.count = counters + VVC_CTR_INTS * cur; a.nextCounters = counters + VVC_CTR_INTS * (cur ^ 1); a.levelExtent = (long long)level_extent;
+  a.n = n; a.nRates = n_rates; a.writeRec = (flags & VVCGPU_INTER_RESI_WRITE_REC) ? 1 : 0; a.bd = bit_depth; a.cmin = clp_min; a.cmax = clp_max;
+  hipLaunchKernelGGL(inter_resi_dq_front_kernel, dim3(wgs), dim3(IQ_THREADS), IQ_LDS_BYTES, st, a, tb);
+  VVC_LAUNCH_CHECK_COUNTERS(st);
+  hipLaunchKernelGGL(inter_resi_dq_trellis_kernel, dim3(cdiv(n * IQ_SLOTS, 64)), dim3(256), TQ_LDS_BYTES, st, coef, level_base, recs, a.list, a.count, rates, bit_depth,
+                     abs_sum, dec, ctx, tb);
+  VVC_LAUNCH_CHECK_COUNTERS(st);
+  hipLaunchKernelGGL(inter_resi_dq_back_kernel, dim3(wgs), dim3(IQ_THREADS), IQ_LDS_BYTES, st, a, tb);
+  VVC_LAUNCH_CHECK();
+  return VVCGPU_OK;
+}
+
+}  // extern "C"

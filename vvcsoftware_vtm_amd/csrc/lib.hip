@@ -342,6 +342,7 @@ int vvcgpu_sizeof(int id)
   case 60: return (int)sizeof(vvcgpu_affine_unipred_result);
   case 62: return (int)sizeof(vvcgpu_intra_chroma_pu);
   case 63: return (int)sizeof(vvcgpu_inter_resi_item);
+  case 65: return (int)sizeof(vvcgpu_inter_resi_dq);
   default: return -1;
   }
 }
