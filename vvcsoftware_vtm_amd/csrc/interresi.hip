@@ -17,24 +17,18 @@
 // distortions from it while it copies it (and the reconstruction, under VVCGPU_INTER_RESI_WRITE_REC) to the candidate buffers; larger blocks
 // read resi' back from the candidate buffer while it is in the caches.
 #include "common.h"
-#include "dist_dev.h"
+#include "interresi_dev.h"
 #include "mfma_tr.h"
 #include "quant_dev.h"
-#include "resichain_dev.h"
 
 static_assert(sizeof(vvcgpu_inter_resi_item) == 80 && sizeof(vvcgpu_resi_chain_desc) == 64, "descriptor layouts");
 
 namespace {
 
-typedef vvcgpu_inter_resi_item IrItem;
-constexpr int IR_SLOTS = VVCGPU_INTER_RESI_SLOTS;
-constexpr int IR_WAVES = 8, IR_THREADS = 64 * IR_WAVES;
-constexpr int IR_TILE = 64 * 64;                                          // samples of a wavefront's tile: orgResi, the prediction, resi' (see the kernel)
 constexpr int IR_TAB_BYTES = RC_TAB_HALVES * 2 + (int)sizeof(RcSmallTab); // the f16 matrices, then the 4- and 8-point matrices of the lane-group bodies
 constexpr int IR_WAVE_BYTES = IR_TILE * 2 + IR_SLOTS * (int)sizeof(vvcgpu_resi_chain_desc) + 32;   // the tile, a chain descriptor per slot, the slot list
 constexpr int IR_LDS_BYTES = IR_TAB_BYTES + IR_WAVES * IR_WAVE_BYTES;     // 110 144 bytes: one workgroup of eight wavefronts per compute unit
 static_assert(IR_TAB_BYTES % 16 == 0 && IR_WAVE_BYTES % 16 == 0 && IR_LDS_BYTES <= 160 * 1024, "LDS budget");
-constexpr int IR_LIST_INTS = 8, IR_LIST_MAX = 7;                          // a row of rd_list_out of vvcgpu_merge_cand_batch: [0] count, [1 .. 7] RdModeList
 
 struct IrArgs
 {
@@ -44,8 +38,6 @@ struct IrArgs
 };
 
 inline __host__ __device__ bool ir_side_ok(int v) { return v >= 2 && v <= 64 && (v & (v - 1)) == 0; }
-
-__device__ __forceinline__ void ir_wave_sync() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }
 
 // the matrix-core body of one shape as a real call (the descriptor and the residual tile are the wavefront's, in LDS)
 template <int W, int H>
@@ -82,7 +74,7 @@ __global__ __launch_bounds__(IR_THREADS, 1) void inter_resi_code_kernel(const Ir
   RcDesc* const dS = reinterpret_cast<RcDesc*>(resiT + IR_TILE);          // dS[k]: slot k
   int* const lst = reinterpret_cast<int*>(dS + IR_SLOTS);                 // the slots that run in lane groups
   const RcSmallTab* const tabs = reinterpret_cast<const RcSmallTab*>(smem + RC_TAB_HALVES * 2);
-  int* const fbScr = a.fbScratch + ((size_t)blockIdx.x * IR_WAVES + wave) * 8192;
+  int* const fbScr = a.fbScratch + ((size_t)blockIdx.x * IR_WAVES + wave) * IR_FB_INTS;
 
   const int first = (int)blockIdx.x * IR_WAVES + wave, step = (int)gridDim.x * IR_WAVES;
   IrItem tNext = a.items[first < a.n ? first : 0];
@@ -93,62 +85,23 @@ __global__ __launch_bounds__(IR_THREADS, 1) void inter_resi_code_kernel(const Ir
     const int w = t.w, h = t.h;
     long long predOff = t.pred_off;
     bool ok = ir_side_ok(w) && ir_side_ok(h) && (t.cand_off & 3) == 0 && (t.level_off & 3) == 0;
-    if (ok && t.list_row >= 0)
-    {
-      const int slot = t.list_slot;
-      ok = a.rdList != nullptr && slot >= 0 && slot < IR_LIST_MAX;
-      if (ok) ok = slot < a.rdList[IR_LIST_INTS * (size_t)t.list_row];
-      if (ok)
-      {
-        const int c = a.rdList[IR_LIST_INTS * (size_t)t.list_row + 1 + slot];
-        ok = c >= 0 && c < IR_LIST_MAX;
-        predOff += (long long)c * t.pred_cand_pitch;
-      }
-    }
+    // (the guard is ir_list_pred's own, repeated: without it the kernel compiles to other code, 520 instructions less -- docs/MEASUREMENTS.md)
+    if (ok && t.list_row >= 0) ok = ir_list_pred(ok, a.rdList, t, predOff);
     if (!ok)                                                              // skipped: the markers, nothing else
     {
       if (lane < IR_SLOTS) { a.absSum[IR_SLOTS * (size_t)item + lane] = 0xFFFFFFFFu; a.distResi[IR_SLOTS * (size_t)item + lane] = ~0ull; a.distRec[IR_SLOTS * (size_t)item + lane] = ~0ull; }
       if (lane == 0) a.zeroDist[item] = ~0ull;
       continue;
     }
-    const int lw = ilog2(w), samples = w * h;
-    // the wavefront's tile: orgResi at 0; behind it the prediction and -- up to 1024 samples -- the place where the body leaves resi' (`back`), so that
-    // resi' returns through LDS instead of through a store, a fence and a load.  A shape with a side of at most 8 (at most 512 samples) also has the
-    // integer body's two buffers there.  64 x 64 fills the tile: its prediction is read again behind the body, and 2048 samples and more return
-    // resi' through the candidate buffer.
+    const int samples = w * h;
     const bool narrow = w <= 8 || h <= 8;
-    short* const predT = samples > 2048 ? nullptr : resiT + (narrow ? 512 : samples <= 1024 ? 1024 : 2048);
-    short* const backT = narrow ? resiT + 3072 : samples <= 1024 ? resiT + 2048 : nullptr;
+    short* const predT = ir_tile_pred(resiT, narrow, samples);
+    short* const backT = ir_tile_back(resiT, narrow, samples);
     const Pel* const predG = a.pred + predOff;
 
     // ---- orgResi and the prediction into the tile, zero_dist
     {
-      const Pel* org = a.org + t.org_off;
-      unsigned long long zd = 0ull;
-      for (int e0 = lane; e0 < samples; e0 += 256)                         // four loads of each plane in flight: the item waits for one round trip per 256 samples
-      {
-        int ov[4], pv[4];
-#pragma unroll
-        for (int u = 0; u < 4; u++)
-        {
-          const int e = e0 + 64 * u, r = e >> lw, x = e & (w - 1);
-          ov[u] = pv[u] = 0;
-          if (e < samples) { pv[u] = predG[(ptrdiff_t)r * t.pred_stride + x]; ov[u] = org[(ptrdiff_t)r * t.org_stride + x]; }
-        }
-#pragma unroll
-        for (int u = 0; u < 4; u++)
-        {
-          const int e = e0 + 64 * u, df = ov[u] - pv[u];
-          if (e < samples)
-          {
-            resiT[e] = (short)df;
-            if (predT) predT[e] = (short)pv[u];
-          }
-          const unsigned ad = (unsigned)abs(df);
-          zd += (unsigned long long)(ad * ad);
-        }
-      }
-      zd = group_sum_u64<64>(zd);
+      const unsigned long long zd = ir_stage(t, a.org + t.org_off, predG, resiT, predT, lane);
       if (lane == 0) a.zeroDist[item] = zd;
     }
 
@@ -189,31 +142,8 @@ __global__ __launch_bounds__(IR_THREADS, 1) void inter_resi_code_kernel(const Ir
     }
     ir_wave_sync();
 
-    // xGetSSE(orgResi, resi') and xGetSSE(org, clip(pred + resi')) of slot k from resi' where the body left it; resi' (from `back`) and the
-    // reconstruction go to the candidate buffers on the way
-    auto finish = [&](int k, const short* backK)
-    {
-      const size_t out = IR_SLOTS * (size_t)item + k;
-      const long long candOff = t.cand_off + (long long)k * samples;
-      Pel* rs = a.resi + candOff;
-      Pel* rec = a.writeRec ? a.rec + candOff : nullptr;
-      unsigned long long dr = 0ull, dc = 0ull;                            // 64 x 64 x 1023^2 is beyond 2^31
-      for (int e = lane; e < samples; e += 64)
-      {
-        int r2;
-        if (backK) { r2 = backK[e]; rs[e] = (short)r2; }
-        else r2 = rs[e];
-        const int o = resiT[e], pv = predT ? (int)predT[e] : (int)predG[(ptrdiff_t)(e >> lw) * t.pred_stride + (e & (w - 1))];
-        const int rc = clip3(a.cmin, a.cmax, pv + r2);
-        const unsigned d1 = (unsigned)abs(o - r2), d2 = (unsigned)abs(o + pv - rc);
-        dr += (unsigned long long)(d1 * d1);
-        dc += (unsigned long long)(d2 * d2);
-        if (rec) rec[e] = (short)rc;
-      }
-      dr = group_sum_u64<64>(dr);
-      dc = group_sum_u64<64>(dc);
-      if (lane == 0) { a.distResi[out] = dr; a.distRec[out] = dc; }
-    };
+    // the closing loop of slot k of this item, resi' in backK (null: in the slot's candidate buffer)
+    auto finish = [&](int k, const short* backK) { ir_finish(a, t, item, k, resiT, predT, predG, backK, lane); };
 
     // ---- the residual chain, in the residual domain
     unsigned* const absSumItem = a.absSum + IR_SLOTS * (size_t)item;
@@ -247,13 +177,7 @@ __global__ __launch_bounds__(IR_THREADS, 1) void inter_resi_code_kernel(const Ir
 #undef IR_MF
       if (!done)                                                          // samples outside the bit depth (out of contract): exact all the same
         ir_tu_generic_call(dS + k, resiT, outBase, a.level, absSumItem + k, a.bd, tb.tr32, tb.dqInv, tb.scanOff, fbScr, fbScr + 4096, lane);
-      if (backT) ir_wave_sync();
-      else
-      {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-      }
+      if (backT) ir_wave_sync(); else ir_global_sync();
       finish(k, backT);
       ir_wave_sync();                                                     // `back` is free again
     }
@@ -269,21 +193,18 @@ extern "C" int vvcgpu_inter_resi_code_batch(const vvc_pel* org_base, const vvc_p
                                             uint32_t* abs_sum, uint64_t* dist_resi, uint64_t* dist_rec, uint64_t* zero_dist, void* stream)
 {
   const char* name = "inter_resi_code_batch";
-  VVC_CHECK_ARG(n >= 0, "%s: n %d", name, n);
+  const bool pointers = org_base && pred_base && items && resi_base && level_base && abs_sum && dist_resi && dist_rec && zero_dist;
+  if (const int rc = ir_check_frame(name, n, pointers, flags, rec_base, clp_min, clp_max)) return rc;
   if (n == 0) return VVCGPU_OK;
-  VVC_CHECK_ARG(org_base && pred_base && items && resi_base && level_base && abs_sum && dist_resi && dist_rec && zero_dist, "%s: null pointer", name);
-  VVC_CHECK_ARG((flags & ~VVCGPU_INTER_RESI_WRITE_REC) == 0, "%s: unknown flags 0x%x", name, flags);
-  VVC_CHECK_ARG(rec_base || !(flags & VVCGPU_INTER_RESI_WRITE_REC), "%s: null pointer (rec_base with VVCGPU_INTER_RESI_WRITE_REC)", name);
-  VVC_CHECK_ARG(clp_min <= clp_max && clp_min >= -32768 && clp_max <= 32767, "%s: clip range %d..%d", name, clp_min, clp_max);
   VVC_CHECK_ARG(((uintptr_t)items & 15) == 0, "%s: item array must be 16-byte aligned", name);
-  if (bit_depth > 10 || bit_depth < 8) { vvcgpu_set_error("%s: bit depth %d outside 8..10", name, bit_depth); return VVCGPU_E_UNSUPPORTED; }
+  if (const int rc = ir_check_bit_depth(name, bit_depth)) return rc;
   hipStream_t st = (hipStream_t)stream;
   VvcTrTables tb; const _Float16* image = nullptr;
   const int rt = vvcgpu_tr_images(&tb, &image);
   if (rt) return rt;
-  const int cap = vvcgpu_cu_count(), wgs = cdiv(n, IR_WAVES) < cap ? cdiv(n, IR_WAVES) : cap;
+  const int wgs = ir_workgroups(n);
   VvcScratch sc(st);
-  int* fbScratch = sc.take<int>((size_t)wgs * IR_WAVES * 8192);           // per wavefront two 4096-int buffers, touched only for an item outside the matrix-core range
+  int* fbScratch = ir_fb_scratch(sc, wgs);
   if (!fbScratch) return VVCGPU_E_DEVICE;
   IrArgs a;
   a.org = org_base; a.pred = pred_base; a.items = items; a.rdList = rd_list; a.resi = resi_base; a.rec = rec_base; a.level = level_base;

@@ -12,32 +12,26 @@
 //            -- the zeroed region of a 64-point side written as zeros: the trellis reads all w h coefficients -- and the slot's trellis record, whose
 //            index 6 i + k it appends to the work list (one atomic add per wavefront on a counter of vvcgpu_counters).  A skipped item or slot gets its
 //            markers here and no list entry.
-//   trellis  tq_trellis<true> (depquant_dev.h: depquant_kernel's body with a work list) over the listed records: four lanes per TU, sixteen TUs per wavefront; levels and abs_sum of the served
-//            slots.  The grid is sized for 6 n records; workgroups behind the list's end leave at once.
+//   trellis  the trellis of depquant_dev.h (depquant_body.inc, the body it shares with depquant_kernel, here with the work list in front of the
+//            descriptors) over the listed records: four lanes per TU, sixteen TUs per wavefront; levels and abs_sum of the served slots.  The grid is sized for 6 n records; workgroups behind the list's end leave at once.
 //   back     the same wavefront-per-item walk: orgResi and the prediction re-formed in the tile; per served slot the dependent de-quantiser (the
 //            GF(2)-linear state replay, as dq_group of transform.hip) into the coefficient workspace, the inverse transform (RC_INV bodies), resi'
 //            unclipped to the candidate buffer, both distortions and the reconstruction as interresi.hip's.  A slot with abs_sum == 0 stores zeros.
 #include "common.h"
 #include "depquant_dev.h"
-#include "dist_dev.h"
+#include "interresi_dev.h"
 #include "mfma_tr.h"
 #include "quant_dev.h"
-#include "resichain_dev.h"
 
 static_assert(sizeof(vvcgpu_inter_resi_item) == 80 && sizeof(vvcgpu_inter_resi_dq) == 16 && sizeof(vvcgpu_depquant_desc) == 40, "descriptor layouts");
 
 namespace {
 
-typedef vvcgpu_inter_resi_item IrItem;
 typedef vvcgpu_inter_resi_dq IrDq;
-constexpr int IQ_SLOTS = VVCGPU_INTER_RESI_SLOTS;
-constexpr int IQ_WAVES = 8, IQ_THREADS = 64 * IQ_WAVES;
-constexpr int IQ_TILE = 64 * 64;                                          // samples of a wavefront's tile (interresi.hip: orgResi, the prediction, resi')
 constexpr int IQ_TAB_BYTES = RC_TAB_HALVES * 2;                           // the f16 matrices of the matrix-core bodies
-constexpr int IQ_WAVE_BYTES = IQ_TILE * 2 + IQ_SLOTS * (int)sizeof(vvcgpu_resi_chain_desc);      // the tile, a chain descriptor per slot
-constexpr int IQ_LDS_BYTES = IQ_TAB_BYTES + IQ_WAVES * IQ_WAVE_BYTES;
+constexpr int IQ_WAVE_BYTES = IR_TILE * 2 + IR_SLOTS * (int)sizeof(vvcgpu_resi_chain_desc);      // the tile, a chain descriptor per slot
+constexpr int IQ_LDS_BYTES = IQ_TAB_BYTES + IR_WAVES * IQ_WAVE_BYTES;
 static_assert(IQ_TAB_BYTES % 16 == 0 && IQ_WAVE_BYTES % 16 == 0 && IQ_LDS_BYTES <= 160 * 1024, "LDS budget");
-constexpr int IQ_LIST_INTS = 8, IQ_LIST_MAX = 7;                          // a row of rd_list_out of vvcgpu_merge_cand_batch: [0] count, [1 .. 7] RdModeList
 constexpr size_t IQ_WS_SLACK = 4096 * sizeof(TCoeff) + 256;               // a quad of the trellis that walks along with a larger TU of its wavefront reads up to 4095 coefficients past its own
 
 struct IqArgs
@@ -50,15 +44,6 @@ struct IqArgs
 
 inline __host__ __device__ bool iq_side_ok(int v) { return v >= 4 && v <= 64 && (v & (v - 1)) == 0; }
 
-__device__ __forceinline__ void iq_wave_sync() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }
-// stores of the wavefront to global memory, read back by other lanes of it
-__device__ __forceinline__ void iq_global_sync()
-{
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-}
-
 // is the item served, and where is its prediction?  (the rules of interresi.hip; here also: no side of 2, level_off a multiple of 16 -- the trellis
 // workspace is indexed by it --, a rate table inside the array, a lambda above zero)
 __device__ __forceinline__ bool iq_item_ok(const IqArgs& a, const IrItem& t, const IrDq& q, long long& predOff)
@@ -66,19 +51,7 @@ __device__ __forceinline__ bool iq_item_ok(const IqArgs& a, const IrItem& t, con
   predOff = t.pred_off;
   bool ok = iq_side_ok(t.w) && iq_side_ok(t.h) && (t.cand_off & 3) == 0 && (t.level_off & 15) == 0 && t.level_off >= 0
             && q.rates_idx >= 0 && q.rates_idx < a.nRates && q.lambda > 0.0;
-  if (ok && t.list_row >= 0)
-  {
-    const int slot = t.list_slot;
-    ok = a.rdList != nullptr && slot >= 0 && slot < IQ_LIST_MAX;
-    if (ok) ok = slot < a.rdList[IQ_LIST_INTS * (size_t)t.list_row];
-    if (ok)
-    {
-      const int c = a.rdList[IQ_LIST_INTS * (size_t)t.list_row + 1 + slot];
-      ok = c >= 0 && c < IQ_LIST_MAX;
-      predOff += (long long)c * t.pred_cand_pitch;
-    }
-  }
-  return ok;
+  return ir_list_pred(ok, a.rdList, t, predOff);
 }
 // the served slots of a served item: DCT-II and the DCT-VIII / DST-VII pairs on sides up to 32, the slot's levels inside level_extent
 __device__ __forceinline__ unsigned iq_served_mask(const IqArgs& a, const IrItem& t)
@@ -88,7 +61,7 @@ __device__ __forceinline__ unsigned iq_served_mask(const IqArgs& a, const IrItem
   __builtin_memcpy(&trBits, t.tr, 8);
   unsigned mask = 0u;
 #pragma unroll
-  for (int k = 0; k < IQ_SLOTS; k++)
+  for (int k = 0; k < IR_SLOTS; k++)
   {
     const int code = (int)(signed char)(trBits >> (8 * k));
     const int th = code % 3, tv = code / 3;
@@ -101,37 +74,6 @@ __device__ __forceinline__ int iq_code(const IrItem& t, int k)
   unsigned long long trBits;
   __builtin_memcpy(&trBits, t.tr, 8);
   return (int)(signed char)(trBits >> (8 * k));
-}
-
-// orgResi = org - pred into the tile (and the prediction into predT, if there is room for it) -> sum orgResi^2 over the wavefront
-__device__ __forceinline__ unsigned long long iq_stage(const IrItem& t, const Pel* __restrict__ org, const Pel* __restrict__ predG, short* resiT, short* predT, int lane)
-{
-  const int w = t.w, samples = w * t.h, lw = ilog2(w);
-  unsigned long long zd = 0ull;
-  for (int e0 = lane; e0 < samples; e0 += 256)                             // four loads of each plane in flight
-  {
-    int ov[4], pv[4];
-#pragma unroll
-    for (int u = 0; u < 4; u++)
-    {
-      const int e = e0 + 64 * u, r = e >> lw, x = e & (w - 1);
-      ov[u] = pv[u] = 0;
-      if (e < samples) { pv[u] = predG[(ptrdiff_t)r * t.pred_stride + x]; ov[u] = org[(ptrdiff_t)r * t.org_stride + x]; }
-    }
-#pragma unroll
-    for (int u = 0; u < 4; u++)
-    {
-      const int e = e0 + 64 * u, df = ov[u] - pv[u];
-      if (e < samples)
-      {
-        resiT[e] = (short)df;
-        if (predT) predT[e] = (short)pv[u];
-      }
-      const unsigned ad = (unsigned)abs(df);
-      zd += (unsigned long long)(ad * ad);
-    }
-  }
-  return group_sum_u64<64>(zd);
 }
 
 // the chain descriptor of slot k for the transform bodies: the residual in the tile, the coefficients at the slot's place in the workspace
@@ -188,26 +130,26 @@ __device__ __forceinline__ _Float16* iq_load_tables(unsigned char* smem, const _
 {
   _Float16* const tab = reinterpret_cast<_Float16*>(smem);
   const uint4* src = reinterpret_cast<const uint4*>(image);
-  for (int i = tid; i < IQ_TAB_BYTES / 16; i += IQ_THREADS) reinterpret_cast<uint4*>(tab)[i] = src[i];
+  for (int i = tid; i < IQ_TAB_BYTES / 16; i += IR_THREADS) reinterpret_cast<uint4*>(tab)[i] = src[i];
   __syncthreads();                                                        // the only workgroup barrier: below every wavefront walks its own items
   return tab;
 }
 
 // ---------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(IQ_THREADS, 1) void inter_resi_dq_front_kernel(const IqArgs a, const VvcTrTables tb)
+__global__ __launch_bounds__(IR_THREADS, 1) void inter_resi_dq_front_kernel(const IqArgs a, const VvcTrTables tb)
 {
   extern __shared__ __align__(16) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const _Float16* const tab = iq_load_tables(smem, a.image, tid);
   unsigned char* const mine = smem + IQ_TAB_BYTES + (size_t)wave * IQ_WAVE_BYTES;
   short* const resiT = reinterpret_cast<short*>(mine);
-  RcDesc* const dS = reinterpret_cast<RcDesc*>(resiT + IQ_TILE);
-  int* const fbScr = a.fbScratch + ((size_t)blockIdx.x * IQ_WAVES + wave) * 8192;
+  RcDesc* const dS = reinterpret_cast<RcDesc*>(resiT + IR_TILE);
+  int* const fbScr = a.fbScratch + ((size_t)blockIdx.x * IR_WAVES + wave) * IR_FB_INTS;
   if (blockIdx.x == 0 && tid < VVC_CTR_INTS) a.nextCounters[tid] = 0;    // the counter set of the NEXT call on this stream (vvcgpu_counters)
 
   // the wavefront's run in the trellis' work list: its served slots are counted first, a lane per item, so that the counter sees one atomic add per
   // wavefront (one per item, 94 000 on one address for the 4K list, took 0.9 ms)
-  const int first = (int)blockIdx.x * IQ_WAVES + wave, step = (int)gridDim.x * IQ_WAVES;
+  const int first = (int)blockIdx.x * IR_WAVES + wave, step = (int)gridDim.x * IR_WAVES;
   int listAt = 0;
   {
     int cnt = 0;
@@ -229,9 +171,9 @@ __global__ __launch_bounds__(IQ_THREADS, 1) void inter_resi_dq_front_kernel(cons
     long long predOff;
     const bool ok = iq_item_ok(a, t, q, predOff);
     const unsigned servedMask = ok ? iq_served_mask(a, t) : 0u;
-    if (lane < IQ_SLOTS)                                                  // the slot's trellis record and list entry; the markers of a skipped slot
+    if (lane < IR_SLOTS)                                                  // the slot's trellis record and list entry; the markers of a skipped slot
     {
-      const size_t out = IQ_SLOTS * (size_t)item + lane;
+      const size_t out = IR_SLOTS * (size_t)item + lane;
       if ((servedMask >> lane) & 1u)
       {
         vvcgpu_depquant_desc r;
@@ -249,20 +191,31 @@ __global__ __launch_bounds__(IQ_THREADS, 1) void inter_resi_dq_front_kernel(cons
       if (lane == 0) a.zeroDist[item] = ~0ull;
       continue;
     }
-    const unsigned long long zd = iq_stage(t, a.org + t.org_off, a.pred + predOff, resiT, nullptr, lane);
+    const unsigned long long zd = ir_stage(t, a.org + t.org_off, a.pred + predOff, resiT, nullptr, lane);
     if (lane == 0) a.zeroDist[item] = zd;
-    if (lane < IQ_SLOTS && ((servedMask >> lane) & 1u)) dS[lane] = iq_desc(t, lane, 0);
-    iq_wave_sync();
-    for (int k = 0; k < IQ_SLOTS; k++)
+    if (lane < IR_SLOTS && ((servedMask >> lane) & 1u)) dS[lane] = iq_desc(t, lane, 0);
+    ir_wave_sync();
+    for (int k = 0; k < IR_SLOTS; k++)
     {
       if (!((servedMask >> k) & 1u)) continue;
       iq_transform<RC_FWD>(dS + k, resiT, nullptr, a.coef, a.bd, tab, tb, fbScr, lane);
-      iq_wave_sync();
+      ir_wave_sync();
     }
-    iq_wave_sync();                                                       // the tile and the descriptors are free again
+    ir_wave_sync();                                                       // the tile and the descriptors are free again
   }
 }
 
+// the trellis over the work list: work item ti is descriptor list[ti].  (The body behind the kernel's early exit is a function of its own, and LISTED
+// its template parameter, because the kernel's instruction stream is then what it was when the body was tq_trellis<true> of depquant_dev.h; included
+// in the kernel itself it comes out five instructions shorter and unmeasured.)
+template <bool LISTED>
+__device__ __forceinline__ void iq_trellis(const TCoeff* __restrict__ coeffBase, TCoeff* __restrict__ levelBase,
+                                           const vvcgpu_depquant_desc* __restrict__ descs, const int* __restrict__ list, int n,
+                                           const vvcgpu_dq_rates* __restrict__ ratesBase, int bd, unsigned* __restrict__ absSumOut,
+                                           unsigned* __restrict__ wsDec, unsigned char* __restrict__ wsCtx, VvcTrTables tb)
+{
+#include "depquant_body.inc"
+}
 __global__ __launch_bounds__(256) void inter_resi_dq_trellis_kernel(const TCoeff* __restrict__ coeffBase, TCoeff* __restrict__ levelBase,
                                                                     const vvcgpu_depquant_desc* __restrict__ descs, const int* __restrict__ list,
                                                                     const int* __restrict__ count,
@@ -271,7 +224,7 @@ __global__ __launch_bounds__(256) void inter_resi_dq_trellis_kernel(const TCoeff
 {
   const int n = *count;                                                   // the served slots of the call, counted by the front
   if ((int)blockIdx.x * 64 >= n) return;
-  tq_trellis<true>(coeffBase, levelBase, descs, list, n, ratesBase, bd, absSumOut, wsDec, wsCtx, tb);
+  iq_trellis<true>(coeffBase, levelBase, descs, list, n, ratesBase, bd, absSumOut, wsDec, wsCtx, tb);
 }
 
 // DQIntern::Quantizer::dequantBlock (DepQuant.cpp:708-785) of one TU by the wavefront: levels -> coefficients, both w x h with row pitch w.  The 4-state
@@ -311,17 +264,17 @@ __device__ __forceinline__ void iq_dequant(const TCoeff* __restrict__ level, TCo
   }
 }
 
-__global__ __launch_bounds__(IQ_THREADS, 1) void inter_resi_dq_back_kernel(const IqArgs a, const VvcTrTables tb)
+__global__ __launch_bounds__(IR_THREADS, 1) void inter_resi_dq_back_kernel(const IqArgs a, const VvcTrTables tb)
 {
   extern __shared__ __align__(16) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const _Float16* const tab = iq_load_tables(smem, a.image, tid);
   unsigned char* const mine = smem + IQ_TAB_BYTES + (size_t)wave * IQ_WAVE_BYTES;
   short* const resiT = reinterpret_cast<short*>(mine);
-  RcDesc* const dS = reinterpret_cast<RcDesc*>(resiT + IQ_TILE);
-  int* const fbScr = a.fbScratch + ((size_t)blockIdx.x * IQ_WAVES + wave) * 8192;
+  RcDesc* const dS = reinterpret_cast<RcDesc*>(resiT + IR_TILE);
+  int* const fbScr = a.fbScratch + ((size_t)blockIdx.x * IR_WAVES + wave) * IR_FB_INTS;
 
-  for (int item = (int)blockIdx.x * IQ_WAVES + wave; item < a.n; item += (int)gridDim.x * IQ_WAVES)
+  for (int item = (int)blockIdx.x * IR_WAVES + wave; item < a.n; item += (int)gridDim.x * IR_WAVES)
   {
     const IrItem t = a.items[item];
     const IrDq q = a.dq[item];
@@ -330,23 +283,22 @@ __global__ __launch_bounds__(IQ_THREADS, 1) void inter_resi_dq_back_kernel(const
     const unsigned servedMask = iq_served_mask(a, t);
     if (!servedMask) continue;
     const int w = t.w, h = t.h, lw = ilog2(w), samples = w * h;
-    // the tile as interresi.hip lays it out: orgResi at 0; behind it the prediction and -- up to 1024 samples -- the place where the body leaves resi'
-    // (`back`); a shape with a side of at most 8 also has the integer body's two buffers there.  64 x 64 fills the tile: its prediction is read again,
-    // and 2048 samples and more return resi' through the candidate buffer.
     const bool narrow = w <= 8 || h <= 8;
-    short* const predT = samples > 2048 ? nullptr : resiT + (narrow ? 512 : samples <= 1024 ? 1024 : 2048);
-    short* const backT = narrow ? resiT + 3072 : samples <= 1024 ? resiT + 2048 : nullptr;
+    short* const predT = ir_tile_pred(resiT, narrow, samples);
+    short* const backT = ir_tile_back(resiT, narrow, samples);
     const Pel* const predG = a.pred + predOff;
-    iq_stage(t, a.org + t.org_off, predG, resiT, predT, lane);
-    if (lane < IQ_SLOTS && ((servedMask >> lane) & 1u)) dS[lane] = iq_desc(t, lane, backT ? 0 : t.cand_off + (long long)lane * samples);
-    iq_wave_sync();
+    ir_stage(t, a.org + t.org_off, predG, resiT, predT, lane);
+    if (lane < IR_SLOTS && ((servedMask >> lane) & 1u)) dS[lane] = iq_desc(t, lane, backT ? 0 : t.cand_off + (long long)lane * samples);
+    ir_wave_sync();
 
     const unsigned short* const scan = tb.scan + tb.scanOff[(lw - 1) * 6 + (ilog2(h) - 1)];
     Pel* const outBase = backT ? backT : a.resi;
-    for (int k = 0; k < IQ_SLOTS; k++)
+    // the closing loop of slot k of this item, as in inter_resi_code_kernel
+    auto finish = [&](int k, const short* backK) { ir_finish(a, t, item, k, resiT, predT, predG, backK, lane); };
+    for (int k = 0; k < IR_SLOTS; k++)
     {
       if (!((servedMask >> k) & 1u)) continue;
-      const size_t out = IQ_SLOTS * (size_t)item + k;
+      const size_t out = IR_SLOTS * (size_t)item + k;
       const long long candOff = t.cand_off + (long long)k * samples, levelOff = t.level_off + (long long)k * samples;
       Pel* const rs = a.resi + candOff;
       if (a.absSum[out] == 0u)                                            // all levels zero: resi' is stored as zeros
@@ -356,32 +308,14 @@ __global__ __launch_bounds__(IQ_THREADS, 1) void inter_resi_dq_back_kernel(const
       else
       {
         iq_dequant(a.level + levelOff, a.coef + levelOff, w, h, t.qp, a.bd, scan, lane);
-        iq_global_sync();
+        ir_global_sync();
         iq_transform<RC_INV>(dS + k, resiT, outBase, a.coef, a.bd, tab, tb, fbScr, lane);
       }
-      if (backT) iq_wave_sync(); else iq_global_sync();
-      // xGetSSE(orgResi, resi') and xGetSSE(org, clip(pred + resi')) from resi' where the body left it; resi' (from `back`) and the reconstruction go
-      // to the candidate buffers on the way
-      Pel* const rec = a.writeRec ? a.rec + candOff : nullptr;
-      unsigned long long dr = 0ull, dc = 0ull;                            // 64 x 64 x 1023^2 is beyond 2^31
-      for (int e = lane; e < samples; e += 64)
-      {
-        int r2;
-        if (backT) { r2 = backT[e]; rs[e] = (short)r2; }
-        else r2 = rs[e];
-        const int o = resiT[e], pv = predT ? (int)predT[e] : (int)predG[(ptrdiff_t)(e >> lw) * t.pred_stride + (e & (w - 1))];
-        const int rc = clip3(a.cmin, a.cmax, pv + r2);
-        const unsigned d1 = (unsigned)abs(o - r2), d2 = (unsigned)abs(o + pv - rc);
-        dr += (unsigned long long)(d1 * d1);
-        dc += (unsigned long long)(d2 * d2);
-        if (rec) rec[e] = (short)rc;
-      }
-      dr = group_sum_u64<64>(dr);
-      dc = group_sum_u64<64>(dc);
-      if (lane == 0) { a.distResi[out] = dr; a.distRec[out] = dc; }
-      iq_wave_sync();                                                     // `back` and the integer body's buffers are free again
+      if (backT) ir_wave_sync(); else ir_global_sync();
+      finish(k, backT);
+      ir_wave_sync();                                                     // `back` and the integer body's buffers are free again
     }
-    iq_wave_sync();                                                       // the tile and the descriptors are free again
+    ir_wave_sync();                                                       // the tile and the descriptors are free again
   }
 }
 
@@ -395,7 +329,7 @@ size_t vvcgpu_inter_resi_code_dq_workspace_bytes(size_t level_extent, int n)
 {
   const size_t c = iq_extent16(level_extent);
   // the coefficients, the trellis decisions and level histories (all indexed by the slot's level offset), per slot a trellis record and a list entry
-  return c * sizeof(TCoeff) + tq_dec_bytes(c) + tq_ctx_bytes(c) + (size_t)(n > 0 ? n : 0) * IQ_SLOTS * (sizeof(vvcgpu_depquant_desc) + sizeof(int)) + IQ_WS_SLACK;
+  return c * sizeof(TCoeff) + tq_dec_bytes(c) + tq_ctx_bytes(c) + (size_t)(n > 0 ? n : 0) * IR_SLOTS * (sizeof(vvcgpu_depquant_desc) + sizeof(int)) + IQ_WS_SLACK;
 }
 
 int vvcgpu_inter_resi_code_dq_batch(const vvc_pel* org_base, const vvc_pel* pred_base, const vvcgpu_inter_resi_item* items, const vvcgpu_inter_resi_dq* dq,
@@ -405,13 +339,9 @@ int vvcgpu_inter_resi_code_dq_batch(const vvc_pel* org_base, const vvc_pel* pred
                                     uint32_t* abs_sum, uint64_t* dist_resi, uint64_t* dist_rec, uint64_t* zero_dist, void* ws, size_t ws_bytes, void* stream)
 {
   const char* name = "inter_resi_code_dq_batch";
-  VVC_CHECK_ARG(n >= 0, "%s: n %d", name, n);
+  const bool pointers = org_base && pred_base && items && dq && rates && resi_base && level_base && abs_sum && dist_resi && dist_rec && zero_dist && ws;
+  if (const int rc = ir_check_frame(name, n, pointers, flags, rec_base, clp_min, clp_max)) return rc;
   if (n == 0) return VVCGPU_OK;
-  VVC_CHECK_ARG(org_base && pred_base && items && dq && rates && resi_base && level_base && abs_sum && dist_resi && dist_rec && zero_dist && ws,
-                "%s: null pointer", name);
-  VVC_CHECK_ARG((flags & ~VVCGPU_INTER_RESI_WRITE_REC) == 0, "%s: unknown flags 0x%x", name, flags);
-  VVC_CHECK_ARG(rec_base || !(flags & VVCGPU_INTER_RESI_WRITE_REC), "%s: null pointer (rec_base with VVCGPU_INTER_RESI_WRITE_REC)", name);
-  VVC_CHECK_ARG(clp_min <= clp_max && clp_min >= -32768 && clp_max <= 32767, "%s: clip range %d..%d", name, clp_min, clp_max);
   VVC_CHECK_ARG(((uintptr_t)items & 15) == 0 && ((uintptr_t)dq & 7) == 0, "%s: item array must be 16-byte, dq array 8-byte aligned", name);
   VVC_CHECK_ARG(n_rates > 0, "%s: n_rates %d", name, n_rates);
   VVC_CHECK_ARG(level_extent >= 16 && level_extent < ((size_t)1 << 40), "%s: level_extent %zu", name, level_extent);
@@ -419,12 +349,12 @@ int vvcgpu_inter_resi_code_dq_batch(const vvc_pel* org_base, const vvc_pel* pred
                 "%s: workspace of %zu bytes for a level extent of %zu and %d items is too small (need %zu) or unaligned", name, ws_bytes, level_extent, n,
                 vvcgpu_inter_resi_code_dq_workspace_bytes(level_extent, n));
   if (quantiser != VVCGPU_INTER_RESI_Q_DEPQUANT) { vvcgpu_set_error("%s: quantiser %d is not served", name, quantiser); return VVCGPU_E_UNSUPPORTED; }
-  if (bit_depth > 10 || bit_depth < 8) { vvcgpu_set_error("%s: bit depth %d outside 8..10", name, bit_depth); return VVCGPU_E_UNSUPPORTED; }
+  if (const int rc = ir_check_bit_depth(name, bit_depth)) return rc;
   hipStream_t st = (hipStream_t)stream;
   VvcTrTables tb; const _Float16* image = nullptr;
   const int rt = vvcgpu_tr_images(&tb, &image);
   if (rt) return rt;
-  const int cap = vvcgpu_cu_count(), wgs = cdiv(n, IQ_WAVES) < cap ? cdiv(n, IQ_WAVES) : cap;
+  const int wgs = ir_workgroups(n);
   VVC_HIP(vvc_allow_lds(inter_resi_dq_front_kernel, IQ_LDS_BYTES));
   VVC_HIP(vvc_allow_lds(inter_resi_dq_back_kernel, IQ_LDS_BYTES));
   VVC_HIP(vvc_allow_lds(inter_resi_dq_trellis_kernel, TQ_LDS_BYTES));
@@ -432,7 +362,7 @@ int vvcgpu_inter_resi_code_dq_batch(const vvc_pel* org_base, const vvc_pel* pred
   int* counters = vvcgpu_counters(st, &cur);                              // the list's length: zero on entry, the front clears the other set
   if (!counters) return VVCGPU_E_DEVICE;
   VvcScratch sc(st);
-  int* fbScratch = sc.take<int>((size_t)wgs * IQ_WAVES * 8192);           // per wavefront two 4096-int buffers, touched only for an item outside the matrix-core range
+  int* fbScratch = ir_fb_scratch(sc, wgs);
   if (!fbScratch) { vvcgpu_counters_failed(st); return VVCGPU_E_DEVICE; }
   // the workspace as vvcgpu_inter_resi_code_dq_workspace_bytes lays it out
   const size_t c = iq_extent16(level_extent);
@@ -445,15 +375,15 @@ int vvcgpu_inter_resi_code_dq_batch(const vvc_pel* org_base, const vvc_pel* pred
   a.org = org_base; a.pred = pred_base; a.items = items; a.dq = dq; a.rdList = rd_list; a.resi = resi_base; a.rec = rec_base; a.level = level_base;
   a.absSum = abs_sum; a.distResi = reinterpret_cast<unsigned long long*>(dist_resi); a.distRec = reinterpret_cast<unsigned long long*>(dist_rec);
   a.zeroDist = reinterpret_cast<unsigned long long*>(zero_dist); a.fbScratch = fbScratch; a.image = image;
-  a.coef = coef; a.recs = recs; a.list = reinterpret_cast<int*>(recs + (size_t)n * IQ_SLOTS);
+  a.coef = coef; a.recs = recs; a.list = reinterpret_cast<int*>(recs + (size_t)n * IR_SLOTS);
   a.count = counters + VVC_CTR_INTS * cur; a.nextCounters = counters + VVC_CTR_INTS * (cur ^ 1); a.levelExtent = (long long)level_extent;
   a.n = n; a.nRates = n_rates; a.writeRec = (flags & VVCGPU_INTER_RESI_WRITE_REC) ? 1 : 0; a.bd = bit_depth; a.cmin = clp_min; a.cmax = clp_max;
-  hipLaunchKernelGGL(inter_resi_dq_front_kernel, dim3(wgs), dim3(IQ_THREADS), IQ_LDS_BYTES, st, a, tb);
+  hipLaunchKernelGGL(inter_resi_dq_front_kernel, dim3(wgs), dim3(IR_THREADS), IQ_LDS_BYTES, st, a, tb);
   VVC_LAUNCH_CHECK_COUNTERS(st);
-  hipLaunchKernelGGL(inter_resi_dq_trellis_kernel, dim3(cdiv(n * IQ_SLOTS, 64)), dim3(256), TQ_LDS_BYTES, st, coef, level_base, recs, a.list, a.count, rates, bit_depth,
+  hipLaunchKernelGGL(inter_resi_dq_trellis_kernel, dim3(cdiv(n * IR_SLOTS, 64)), dim3(256), TQ_LDS_BYTES, st, coef, level_base, recs, a.list, a.count, rates, bit_depth,
                      abs_sum, dec, ctx, tb);
   VVC_LAUNCH_CHECK_COUNTERS(st);
-  hipLaunchKernelGGL(inter_resi_dq_back_kernel, dim3(wgs), dim3(IQ_THREADS), IQ_LDS_BYTES, st, a, tb);
+  hipLaunchKernelGGL(inter_resi_dq_back_kernel, dim3(wgs), dim3(IR_THREADS), IQ_LDS_BYTES, st, a, tb);
   VVC_LAUNCH_CHECK();
   return VVCGPU_OK;
 }
