@@ -26,6 +26,20 @@ int ilog2r(int v) { int l = 0; while ((1 << l) < v) l++; return l; }
 
 struct Bits2 { int b[2]; };
 
+// Which branches a run of orc_rdoq took: counted per thread, read and cleared by orc_rdoq_events.  The tests use them to prove that their inputs
+// reach what they are meant to reach (tests/test_rdoq_cases_cpu.py); nothing here feeds back into the results.
+enum RdoqEvent
+{
+  EV_LEVEL_CAPPED,                                                               // maxAbs cut to 32767
+  EV_CG_EMPTY, EV_CG_NNZ_BEFORE_POS0_ZERO, EV_CG_ZEROED,                         // group below the last one: no level / only position 0 / zeroed by the cost test
+  EV_LAST_KEPT, EV_LAST_TRUNCATED, EV_LAST_ZERO, EV_LAST_WALK_ENDED_GT1,         // the chosen last position; the walk ended by a level > 1
+  EV_SBH_NEW, EV_SBH_NEW_BEFORE_FIRST, EV_SBH_UP, EV_SBH_DOWN, EV_SBH_DOWN_TO_ZERO, EV_SBH_BONUS_CHOSEN, EV_SBH_FORCED_AT_CAP, EV_SBH_REFUSED_BY_SIGN,
+  EV_ESCAPE_RICE0, EV_ESCAPE_RICE1, EV_ESCAPE_RICE2, EV_RICE0, EV_RICE1, EV_RICE2,
+  EV_COUNT
+};
+thread_local uint32_t g_events[EV_COUNT];
+inline void ev(int e) { g_events[e]++; }
+
 int icRate(unsigned absLevel, const int* par, const int* gt1, const int* gt2, int rice)      // xGetICRate :235-313
 {
   int rate = 32768;
@@ -36,6 +50,7 @@ int icRate(unsigned absLevel, const int* par, const int* gt1, const int* gt2, in
     if (symbol < (unsigned)(threshold << rice)) { length = symbol >> rice; rate += (length + 1 + rice) << 15; }
     else
     {
+      ev(EV_ESCAPE_RICE0 + rice);
       length = rice; symbol -= threshold << rice;
       while (symbol >= (1u << length)) symbol -= 1u << (length++);
       rate += (threshold + length + 1 - rice + length) << 15;
@@ -51,6 +66,12 @@ int icRate(unsigned absLevel, const int* par, const int* gt1, const int* gt2, in
 }
 
 }  // namespace
+
+// out[22], in the order of RdoqEvent (tests/rdoq_cases.py names them): the events of this thread's orc_rdoq calls since the last read
+ORC_API void orc_rdoq_events(uint32_t* out)
+{
+  for (int i = 0; i < EV_COUNT; i++) { out[i] = g_events[i]; g_events[i] = 0; }
+}
 
 ORC_API uint32_t orc_rdoq(const TCoeff* src, TCoeff* dst, int w, int h, int luma, int bd, int qp, double lambda, int signHiding,
                           const vvcgpu_rdoq_rates* rt)
@@ -97,6 +118,7 @@ ORC_API uint32_t orc_rdoq(const TCoeff* src, TCoeff* dst, int w, int h, int luma
       const int64_t tmpLevel = (int64_t)std::abs(src[pos]) * quantCoef;
       const int levelDouble = (int)std::min<int64_t>(tmpLevel, (int64_t)std::numeric_limits<int>::max() - (1 << (qBits - 1)));
       unsigned maxAbs = std::min<unsigned>((unsigned)entMax, (unsigned)((levelDouble + (1 << (qBits - 1))) >> qBits));
+      if ((unsigned)((levelDouble + (1 << (qBits - 1))) >> qBits) > (unsigned)entMax) ev(EV_LEVEL_CAPPED);
       const double err0 = (double)levelDouble;
       costCoeff0[sp] = err0 * err0 * errScale;
       blockUncoded += costCoeff0[sp];
@@ -115,6 +137,7 @@ ORC_API uint32_t orc_rdoq(const TCoeff* src, TCoeff* dst, int w, int h, int luma
         }
         // at the last position sigCtxIdAbs has never been called: the template state is still -1 and the offset 0 (ContextModelling.h:175-184)
         const int rice = kGoRicePars[std::min(sumGo, 31)];
+        ev(EV_RICE0 + rice);
         const int* par = rt->par[ofs]; const int* gt1 = rt->gt1[ofs]; const int* gt2 = rt->gt2[ofs];
         const int* sig = rt->sig[ctxSig];
         // xGetCodedLevel :107-162
@@ -169,12 +192,13 @@ ORC_API uint32_t orc_rdoq(const TCoeff* src, TCoeff* dst, int w, int h, int luma
       {
         if (!sigGroup[cgPos])
         {
+          ev(EV_CG_EMPTY);
           baseCost += lambda * sgBits[0] - sigCost;
           costCGSig[subSet] = lambda * sgBits[0];
         }
         else if (subSet < cgLastScanPos)
         {
-          if (nnzBeforePos0 == 0) { baseCost -= sigCost0; sigCost -= sigCost0; }
+          if (nnzBeforePos0 == 0) { ev(EV_CG_NNZ_BEFORE_POS0_ZERO); baseCost -= sigCost0; sigCost -= sigCost0; }
           double costZeroCG = baseCost;
           baseCost += lambda * sgBits[1];
           costZeroCG += lambda * sgBits[0];
@@ -184,6 +208,7 @@ ORC_API uint32_t orc_rdoq(const TCoeff* src, TCoeff* dst, int w, int h, int luma
           costZeroCG -= sigCost;
           if (costZeroCG < baseCost)
           {
+            ev(EV_CG_ZEROED);
             sigGroup[cgPos] = 0;
             baseCost = costZeroCG;
             costCGSig[subSet] = lambda * sgBits[0];
@@ -224,13 +249,14 @@ ORC_API uint32_t orc_rdoq(const TCoeff* src, TCoeff* dst, int w, int h, int luma
         const double costLast = lambda * c;
         const double total = baseCost + costLast - costSig[sp];
         if (total < bestCost) { bestLastIdxP1 = sp + 1; bestCost = total; }
-        if (dst[pos] > 1) { foundLast = true; break; }
+        if (dst[pos] > 1) { ev(EV_LAST_WALK_ENDED_GT1); foundLast = true; break; }
         baseCost -= costCoeff[sp];
         baseCost += costCoeff0[sp];
       }
       else baseCost -= costSig[sp];
     }
   }
+  ev(bestLastIdxP1 == 0 ? EV_LAST_ZERO : bestLastIdxP1 <= lastScanPos ? EV_LAST_TRUNCATED : EV_LAST_KEPT);
   uint32_t absSum = 0;
   for (int sp = 0; sp < bestLastIdxP1; sp++)
   {
@@ -261,7 +287,7 @@ ORC_API uint32_t orc_rdoq(const TCoeff* src, TCoeff* dst, int w, int h, int luma
         if (signbit != (unsigned)(sum & 1))
         {
           int64_t minCostInc = std::numeric_limits<int64_t>::max(), curCost = std::numeric_limits<int64_t>::max();
-          int minPos = -1, finalChange = 0, curChange = 0;
+          int minPos = -1, minK = -1, finalChange = 0, curChange = 0;
           for (k = (lastCG == 1 ? lastNZ : 15); k >= 0; --k)
           {
             const int pos = (int)scan[k + subPos];
@@ -284,12 +310,19 @@ ORC_API uint32_t orc_rdoq(const TCoeff* src, TCoeff* dst, int w, int h, int luma
               if (k < firstNZ)
               {
                 const unsigned thisSign = src[pos] >= 0 ? 0 : 1;
-                if (thisSign != signbit) curCost = std::numeric_limits<int64_t>::max();
+                if (thisSign != signbit) { ev(EV_SBH_REFUSED_BY_SIGN); curCost = std::numeric_limits<int64_t>::max(); }
               }
             }
-            if (curCost < minCostInc) { minCostInc = curCost; finalChange = curChange; minPos = pos; }
+            if (curCost < minCostInc) { minCostInc = curCost; finalChange = curChange; minPos = pos; minK = k; }
           }
-          if (dst[minPos] == entMax || dst[minPos] == entMin) finalChange = -1;
+          if (dst[minPos] == entMax || dst[minPos] == entMin) { if (finalChange != -1) ev(EV_SBH_FORCED_AT_CAP); finalChange = -1; }
+          if (dst[minPos] == 0) { ev(EV_SBH_NEW); if (minK < firstNZ) ev(EV_SBH_NEW_BEFORE_FIRST); }
+          else if (finalChange > 0) ev(EV_SBH_UP);
+          else
+          {
+            ev(EV_SBH_DOWN);
+            if (std::abs(dst[minPos]) == 1) { ev(EV_SBH_DOWN_TO_ZERO); if (lastCG == 1 && minK == lastNZ) ev(EV_SBH_BONUS_CHOSEN); }
+          }
           if (src[minPos] >= 0) dst[minPos] += finalChange; else dst[minPos] -= finalChange;
         }
       }
