@@ -1168,7 +1168,7 @@ int vvcgpu_merge_cand_batch(const vvc_pel* ref0_base, const vvc_pel* ref1_base, 
 #define VVCGPU_INTER_RESI_SLOTS      6
 #define VVCGPU_INTER_RESI_TS         9     /* tr[k]: transform skip */
 #define VVCGPU_INTER_RESI_WRITE_REC  1     /* flags: every served slot also stores clip(pred + resi') in rec_base */
-struct vvcgpu_inter_resi_item {
+typedef struct vvcgpu_inter_resi_item {
   int64_t org_off, pred_off;               /* samples from org_base / pred_base */
   int64_t pred_cand_pitch;                 /* list items: samples between the blocks of successive merge candidates of this component in pred_base */
   int64_t cand_off, level_off;             /* slot k: w h samples at cand_off + k w h of resi_base (and rec_base), w h levels at level_off + k w h */
@@ -1180,8 +1180,7 @@ struct vvcgpu_inter_resi_item {
   int8_t  tr[VVCGPU_INTER_RESI_SLOTS];     /* -1 unused; tr_hor + 3 tr_ver (each 0 DCT-II, 1 DCT-VIII, 2 DST-VII); 9 transform skip */
   int8_t  reserved1[2];
   int32_t reserved2[2];                    /* sizeof == 80 */
-};
-typedef struct vvcgpu_inter_resi_item vvcgpu_inter_resi_item;
+} vvcgpu_inter_resi_item;
 int vvcgpu_inter_resi_code_batch(const vvc_pel* org_base, const vvc_pel* pred_base, const vvcgpu_inter_resi_item* items, int n,
                                  const int32_t* rd_list,                 /* rd_list_out of vvcgpu_merge_cand_batch, may be NULL */
                                  vvc_pel* resi_base, vvc_pel* rec_base, vvc_coef* level_base,
@@ -1217,13 +1216,12 @@ int vvcgpu_inter_resi_code_batch(const vvc_pel* org_base, const vvc_pel* pred_ba
  * Not served: blocks with a side of 2 and transform skip (vvcgpu_depquant_batch serves neither: the binding keeps them on the host), RDOQ,
  * cross-component prediction, RDPCM and lossless.                                                                                                  */
 #define VVCGPU_INTER_RESI_Q_DEPQUANT 1     /* quantiser: DQIntern::DepQuant::quant */
-struct vvcgpu_inter_resi_dq {
+typedef struct vvcgpu_inter_resi_dq {
   double  lambda;                          /* Quant::m_dLambda of the component */
   int32_t rates_idx;                       /* index into the rates array */
   int8_t  luma;
   int8_t  reserved[3];                     /* sizeof == 16 */
-};
-typedef struct vvcgpu_inter_resi_dq vvcgpu_inter_resi_dq;
+} vvcgpu_inter_resi_dq;
 struct vvcgpu_dq_rates;                    /* the rate tables of the trellis, defined with vvcgpu_depquant_batch below */
 size_t vvcgpu_inter_resi_code_dq_workspace_bytes(size_t level_extent, int n);
 int vvcgpu_inter_resi_code_dq_batch(const vvc_pel* org_base, const vvc_pel* pred_base, const vvcgpu_inter_resi_item* items,
@@ -1480,7 +1478,7 @@ int vvcgpu_intra_tu_code_batch(
  * 4:4:4, TUs split below the PU.                                                                                                                      */
 #define VVCGPU_INTRA_CHROMA_LM          67   /* mode[k]: LM_CHROMA_IDX */
 #define VVCGPU_INTRA_CHROMA_WRITE_PRED   1   /* flags: every served item also stores its prediction in pred_base */
-struct vvcgpu_intra_chroma_pu {
+typedef struct vvcgpu_intra_chroma_pu {
   int64_t org_off[2], ref_off[2];       /* samples, relative to org_base / refs_base */
   int64_t luma_off, cand_off, level_off;
   int32_t org_stride, luma_stride;
@@ -1490,8 +1488,7 @@ struct vvcgpu_intra_chroma_pu {
   int8_t  mode[6];
   int16_t reserved;
   int32_t reserved2[2];                 /* sizeof == 96 */
-};
-typedef struct vvcgpu_intra_chroma_pu vvcgpu_intra_chroma_pu;
+} vvcgpu_intra_chroma_pu;
 int vvcgpu_intra_chroma_code_batch(
     const vvc_pel* rec_base, const uint8_t* flags_base, const vvcgpu_intra_fill_desc* fill,  /* all three NULL: refs_base holds the references */
     vvc_pel* refs_base,                        /* read when fill == NULL; with fill: where the gathered references are also written, may be NULL */

@@ -1,6 +1,6 @@
 """Generates tests/golden/inter_resi_code.npz: items of the inter residual pixel pass (InterSearch::encodeResAndCalcRdInterCU, InterSearch.cpp:4752-4909, with
 the "check full" part of xEstimateInterResidualQT, :4254-4634) whose every stored result comes from the COMPILED REFERENCE's own functions, through the
-wrappers oracle/_ref/libvtmref.so exports: vtmref_pelop_area (AreaBuf::subtract), vtmref_tr_fwd_batch (xTrMxN_EMT; tr_hor = 3: xTransformSkip),
+wrappers oracle/_ref/libvtmref.so exports, as the chain steps of tests/rd_pass_kit.py call them: vtmref_pelop_area (AreaBuf::subtract), vtmref_tr_fwd_batch (xTrMxN_EMT; tr_hor = 3: xTransformSkip),
 vtmref_quant_batch (Quant::quant), vtmref_dequant_tr_inv_batch (Quant::dequant + xITrMxN_EMT or xITransformSkip), vtmref_pelop (PelBufferOps reco) and
 vtmref_dist (RdCost::xGetSSE, on residual blocks and against a zero block as well).  Build machine only (needs oracle/_ref/libvtmref.so, i.e. a build()
 where the reference exists):
@@ -9,7 +9,6 @@ where the reference exists):
 The tests' restatement (tests/inter_resi_code_cases.py) goes through the CPU restatement's steps; the generator asserts that it reproduces every stored value.
 Nothing of the reference is copied; only the data is stored.  Inputs of the cases, not results of the reference: the planes, the predictions, the
 transform candidates and the quantiser parameters."""
-import ctypes as C
 import os
 import sys
 
@@ -21,8 +20,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(HERE))
 
 import inter_resi_code_cases as irc  # noqa: E402
-from oraclelib import p, ref  # noqa: E402
-from vvcsoftware_vtm_amd.abi import DQTR_DESC, QUANT_DESC, TR_DESC  # noqa: E402
+import rd_pass_kit as kit  # noqa: E402
 
 ROWS_H = 96                                                                  # rows of the original plane the file stores
 
@@ -51,33 +49,22 @@ def ref_item(R, case, i, clp):
     w, h, bd = int(it["w"]), int(it["h"]), case.bd
     org = np.ascontiguousarray(irc.block(case.org, int(it["org_off"]), int(it["org_stride"]), w, h))
     pred = np.ascontiguousarray(irc.block(case.pred, int(it["pred_off"]), int(it["pred_stride"]), w, h))
-    resi, zero = np.zeros((h, w), np.int16), np.zeros((h, w), np.int16)
-    R.vtmref_pelop_area(3, p(org), w, p(pred), w, p(resi), w, w, h, 0, bd, clp[0], clp[1])
-    zero_dist = int(R.vtmref_dist(2, 1, p(zero), w, p(resi), w, w, h, bd, 0))
+    resi = kit.subtract(org, pred, bd, R)
+    zero_dist = kit.sse(np.zeros((h, w), np.int16), resi, bd, R)
     slots = []
     for k in range(irc.SLOTS):
         code = int(it["tr"][k])
         if code < 0:
             continue
         th, tv = (3, 0) if code == irc.TS else (code % 3, code // 3)
-        resi2, rec = np.zeros((h, w), np.int16), np.zeros((h, w), np.int16)
-        coef, level, dqc = np.zeros(w * h, np.int32), np.zeros(w * h, np.int32), np.zeros(w * h, np.int32)
-        abs_sum = np.zeros(1, np.uint32)
-        tr = np.zeros(1, TR_DESC); tr[0] = (0, 0, w, w, h, th, tv, 0, 0)
-        qd = np.zeros(1, QUANT_DESC); qd[0] = (0, 0, w, h, it["intra_slice"], it["sign_hiding"], 0, it["qp"], 0)
-        dq = np.zeros(1, DQTR_DESC); dq[0] = (0, 0, w, w, h, th, tv, 0, 0, it["qp"])
-        assert R.vtmref_tr_fwd_batch(p(resi), p(coef), p(tr), 1, bd) == 0
-        assert R.vtmref_quant_batch(p(coef), p(level), p(qd), 1, bd, p(abs_sum)) == 0
-        assert R.vtmref_dequant_tr_inv_batch(p(level), p(resi2), p(dq), 1, bd, p(dqc)) == 0
-        R.vtmref_pelop(1, 1, p(pred), w, p(resi2), w, p(rec), w, w, h, 0, 0, 0, 1, bd, clp[0], clp[1])
-        slots.append((k, level, int(abs_sum[0]), resi2, rec, int(R.vtmref_dist(2, 1, p(resi), w, p(resi2), w, w, h, bd, 0)),
-                      int(R.vtmref_dist(2, 1, p(org), w, p(rec), w, w, h, bd, 0))))
+        level, abs_sum, resi2 = kit.code_resi(resi, bd, th, tv, int(it["qp"]), int(it["intra_slice"]), int(it["sign_hiding"]), R)
+        rec = kit.reconstruct(pred, resi2, clp, bd, R)
+        slots.append((k, level, abs_sum, resi2, rec, kit.sse(resi, resi2, bd, R), kit.sse(org, rec, bd, R)))
     return zero_dist, slots
 
 
 def main():
-    R = ref()
-    R.vtmref_dist.restype = C.c_uint64
+    R = kit.reference()
     out = {}
     for bd in (8, 10):
         rng = np.random.default_rng(8800 + bd)
@@ -103,9 +90,7 @@ def main():
                 co, lo = int(it["cand_off"]) + k * sz, int(it["level_off"]) + k * sz
                 resi_b[co:co + sz], rec_b[co:co + sz], level_b[lo:lo + sz] = resi2.reshape(-1), rec.reshape(-1), level
                 abs_sum[i, k], dist_resi[i, k], dist_rec[i, k] = asum, dr, dc
-        for k, v in (("resi", resi_b), ("rec", rec_b), ("level", level_b), ("abs_sum", abs_sum), ("dist_resi", dist_resi), ("dist_rec", dist_rec),
-                     ("zero_dist", zero_dist)):
-            assert np.array_equal(want[k], v), (bd, k)                       # the restatement reproduces every stored value
+        kit.check_restatement(want, dict(resi=resi_b, rec=rec_b, level=level_b, abs_sum=abs_sum, dist_resi=dist_resi, dist_rec=dist_rec, zero_dist=zero_dist), bd)
         k = "bd%d_" % bd
         out.update({k + "org": case.org, k + "pred": case.pred, k + "items": case.items.view(np.uint8), k + "cand_size": np.int64(case.cand_size),
                     k + "level_size": np.int64(case.level_size), k + "flags": np.int32(flags), k + "want_resi": resi_b, k + "want_rec": rec_b,
@@ -114,10 +99,7 @@ def main():
         served = abs_sum != irc.U32_MAX
         print("bit depth %d: %d items, %d slots, %d all-zero, the clip bites in %d" % (bd, n, served.sum(), (served & (abs_sum == 0)).sum(),
                                                                                     (served & (dist_rec != dist_resi)).sum()))
-    path = os.path.join(HERE, "inter_resi_code.npz")
-    np.savez_compressed(path, **out)
-    print("wrote", path, os.path.getsize(path), "bytes")
-    assert os.path.getsize(path) <= 400 * 1024
+    kit.save_golden(os.path.join(HERE, "inter_resi_code.npz"), out)
 
 
 if __name__ == "__main__":

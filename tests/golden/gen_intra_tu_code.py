@@ -1,6 +1,6 @@
 """Generates tests/golden/intra_tu_code.npz: items of the intra RD loop's pixel pass (IntraSearch::xIntraCodingTUBlock, IntraSearch.cpp:1147-1316) whose every
 stored value comes from the COMPILED REFERENCE's own functions, through the wrappers oracle/_ref/libvtmref.so exports: vtmref_intra_pred (predIntraAng with
-xFilterReferenceSamples in front), vtmref_pelop_area (AreaBuf::subtract), vtmref_tr_fwd_batch (xTrMxN_EMT), vtmref_quant_batch (Quant::quant),
+xFilterReferenceSamples in front) and, as the chain steps of tests/rd_pass_kit.py call them, vtmref_pelop_area (AreaBuf::subtract), vtmref_tr_fwd_batch (xTrMxN_EMT), vtmref_quant_batch (Quant::quant),
 vtmref_dequant_tr_inv_batch (Quant::dequant + xITrMxN_EMT), vtmref_pelop (PelBufferOps reco) and vtmref_dist (RdCost::xGetSSE).  Build machine only (needs
 oracle/_ref/libvtmref.so, i.e. a build() where the reference exists):
     python tests/golden/gen_intra_tu_code.py
@@ -9,7 +9,6 @@ The tests' restatement (tests/intra_tu_code_cases.py) goes through the CPU resta
 Nothing of the reference is copied; only the data is stored.  Inputs of the cases, not results of the reference: the modes, the filter decisions of the
 explicit items, the transform pairs and quantiser parameters, and the packed references (gathered by orc_intra_fill_refs, which tests/golden/intra_fill.npz
 checks against the reference's own calls)."""
-import ctypes as C
 import os
 import sys
 
@@ -22,8 +21,8 @@ sys.path.insert(0, os.path.dirname(HERE))
 
 import intra_mode_cand_cases as imc  # noqa: E402
 import intra_tu_code_cases as itc  # noqa: E402
-from oraclelib import p, ref  # noqa: E402
-from vvcsoftware_vtm_amd.abi import DQTR_DESC, QUANT_DESC, TR_DESC  # noqa: E402
+import rd_pass_kit as kit  # noqa: E402
+from oraclelib import p  # noqa: E402
 
 # the reference pairs DCT-II only with DCT-II (g_aiTrSubsetInter holds DCT-VIII and DST-VII)
 # (w, h, mode, filter_refs (None: the luma rule), tr_hor, tr_ver, qp - 6 (bd - 8), intra_slice, sign_hiding); mode -1: a given prediction
@@ -49,24 +48,13 @@ def ref_item(R, tc, i, clp):
     else:
         pred = np.zeros((h, w), np.int16)
         assert R.vtmref_intra_pred(p(tc.refs_of(int(it["pu"]))), p(pred), w, w, h, mode, clp[0], clp[1], bd, int(it["filt"]), None) == 0
-    resi, resi2, rec = np.zeros((h, w), np.int16), np.zeros((h, w), np.int16), np.zeros((h, w), np.int16)
-    coef, level, dqc = np.zeros(w * h, np.int32), np.zeros(w * h, np.int32), np.zeros(w * h, np.int32)
-    abs_sum = np.zeros(1, np.uint32)
-    tr = np.zeros(1, TR_DESC); tr[0] = (0, 0, w, w, h, it["tr_hor"], it["tr_ver"], 0, 0)
-    qd = np.zeros(1, QUANT_DESC); qd[0] = (0, 0, w, h, it["intra"], it["sbh"], 0, it["qp"], 0)
-    dq = np.zeros(1, DQTR_DESC); dq[0] = (0, 0, w, w, h, it["tr_hor"], it["tr_ver"], 0, 0, it["qp"])
-    R.vtmref_pelop_area(3, p(org), w, p(pred), w, p(resi), w, w, h, 0, bd, clp[0], clp[1])
-    assert R.vtmref_tr_fwd_batch(p(resi), p(coef), p(tr), 1, bd) == 0
-    assert R.vtmref_quant_batch(p(coef), p(level), p(qd), 1, bd, p(abs_sum)) == 0
-    assert R.vtmref_dequant_tr_inv_batch(p(level), p(resi2), p(dq), 1, bd, p(dqc)) == 0
-    R.vtmref_pelop(1, 1, p(pred), w, p(resi2), w, p(rec), w, w, h, 0, 0, 0, 1, bd, clp[0], clp[1])
-    dist = R.vtmref_dist(2, 1, p(org), w, p(rec), w, w, h, bd, 0)
-    return pred, level, int(abs_sum[0]), rec, int(dist)
+    level, abs_sum, resi2 = kit.code_resi(kit.subtract(org, pred, bd, R), bd, int(it["tr_hor"]), int(it["tr_ver"]), int(it["qp"]), int(it["intra"]), int(it["sbh"]), R)
+    rec = kit.reconstruct(pred, resi2, clp, bd, R)
+    return pred, level, abs_sum, rec, kit.sse(org, rec, bd, R)
 
 
 def main():
-    R = ref()
-    R.vtmref_dist.restype = C.c_uint64
+    R = kit.reference()
     out = {}
     for bd in (8, 10):
         rng = np.random.default_rng(8600 + bd)
@@ -90,8 +78,7 @@ def main():
             itc.block(pred_b, int(it["pred_off"]), int(it["pred_stride"]), w, h)[:] = pred
             itc.block(rec_b, int(it["rec_off"]), int(it["rec_stride"]), w, h)[:] = rec
             level_b[int(it["level_off"]):int(it["level_off"]) + w * h] = level
-        for k, v in (("pred", pred_b), ("rec", rec_b), ("level", level_b), ("abs_sum", abs_sum), ("num_sig", num_sig), ("dist", dist)):
-            assert np.array_equal(want[k], v), (bd, k)                       # the restatement reproduces every stored value
+        kit.check_restatement(want, dict(pred=pred_b, rec=rec_b, level=level_b, abs_sum=abs_sum, num_sig=num_sig, dist=dist), bd)
         itc.check_conditions(tc, want)
         k = "bd%d_" % bd
         out.update({k + "rec": base.rec, k + "org": base.org, k + "pus": base.pus.view(np.uint8), k + "avail": base.avail, k + "items": tc.items.view(np.uint8),
@@ -99,10 +86,7 @@ def main():
                     k + "want_pred": pred_b, k + "want_rec": rec_b, k + "want_level": level_b, k + "want_abs_sum": abs_sum, k + "want_num_sig": num_sig,
                     k + "want_dist": dist})
         print("bit depth %d: %d items, num_sig %s" % (bd, n, [int(v) for v in num_sig]))
-    path = os.path.join(HERE, "intra_tu_code.npz")
-    np.savez_compressed(path, **out)
-    print("wrote", path, os.path.getsize(path), "bytes")
-    assert os.path.getsize(path) <= 400 * 1024
+    kit.save_golden(os.path.join(HERE, "intra_tu_code.npz"), out)
 
 
 if __name__ == "__main__":

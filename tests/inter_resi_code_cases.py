@@ -1,22 +1,20 @@
 """The inter residual pixel pass (InterSearch::encodeResAndCalcRdInterCU, InterSearch.cpp:4752-4909, with the "check full" part of xEstimateInterResidualQT,
-:4254-4634) restated for the tests of vvcgpu_inter_resi_code_batch from oracle steps that are each pinned to the compiled reference: orc_pelop_batch
-(subtract), orc_tr_fwd_batch (tr_hor = 3: transform skip), orc_quant_batch, orc_dequant_tr_inv_batch, orc_pelop_batch (reconstruct), orc_dist_batch kind 2 on
+:4254-4634) restated for the tests of vvcgpu_inter_resi_code_batch from the chain steps of tests/rd_pass_kit.py, oracle steps that are each pinned to the
+compiled reference: subtract, forward transform (tr_hor = 3: transform skip), quantise, de-quantise with inverse transform, reconstruct, and SSE on
 residual blocks and on a zero block.  The slot rules, the list look-up and the skip markers are written here from the entry's contract.  Also the case
 builders: items with candidate buffers of their own for resi', reconstruction and levels, canaries between them, and rd_list rows.
 numpy only: the generator and the CPU tests load this file without torch."""
-import ctypes as C
 import os
 
 import numpy as np
 
-from oraclelib import oracle, p
+import rd_pass_kit as kit
 from vvcsoftware_vtm_amd import abi
-from vvcsoftware_vtm_amd.abi import DIST_DESC, DQTR_DESC, PELOP_DESC, QUANT_DESC, TR_DESC, PelopCfg
 
 ITEM = abi.INTER_RESI_ITEM
 SLOTS, TS, WRITE_REC = abi.INTER_RESI_SLOTS, abi.INTER_RESI_TS, abi.INTER_RESI_WRITE_REC
-U32_MAX, U64_MAX = 0xFFFFFFFF, 0xFFFFFFFFFFFFFFFF
-RESI_CANARY, REC_CANARY, LEVEL_CANARY = 0x5A5A, -21846, 0x5A5A5A5A
+U32_MAX, U64_MAX, max_qp, block = kit.U32_MAX, kit.U64_MAX, kit.max_qp, kit.block
+RESI_CANARY, REC_CANARY, LEVEL_CANARY = kit.RESI_CANARY, kit.REC_CANARY, kit.LEVEL_CANARY
 PRED_GUARD = -5
 SIDES = (2, 4, 8, 16, 32, 64)
 EMT = (4, 5, 7, 8)                                                          # tr_hor + 3 tr_ver of the four pairs of g_aiTrSubsetInter: {DCT-VIII, DST-VII}^2
@@ -26,15 +24,6 @@ GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "int
 
 def all_shapes():
     return [(w, h) for w in SIDES for h in SIDES]
-
-
-def max_qp(bd):
-    """the largest QpParam::Qp of the component: 63 (JVET_K0251) plus the bit-depth offset"""
-    return 63 + 6 * (bd - 8)
-
-
-def side_ok(v):
-    return 2 <= v <= 64 and (v & (v - 1)) == 0
 
 
 def slot_served(w, h, code):
@@ -58,15 +47,10 @@ class Case:
                 np.full(self.level_size, LEVEL_CANARY, np.int32))
 
 
-def block(buf, off, stride, w, h):
-    """the h x w view of a flat buffer"""
-    return np.lib.stride_tricks.as_strided(buf[off:], (h, w), (stride * buf.itemsize, buf.itemsize))
-
-
 def pred_offset(it, rd_list):
     """-> the prediction's offset in pred_base, or None: the item is skipped"""
     w, h = int(it["w"]), int(it["h"])
-    if not (side_ok(w) and side_ok(h)) or int(it["cand_off"]) % 4 or int(it["level_off"]) % 4:
+    if not (kit.side_ok(w, 2) and kit.side_ok(h, 2)) or int(it["cand_off"]) % 4 or int(it["level_off"]) % 4:
         return None
     off = int(it["pred_off"])
     row, slot = int(it["list_row"]), int(it["list_slot"])
@@ -80,46 +64,11 @@ def pred_offset(it, rd_list):
     return off
 
 
-def sse(a, b):
-    """orc_dist_batch kind 2 of two contiguous h x w int16 blocks"""
-    h, w = a.shape
-    dd = np.zeros(1, DIST_DESC); dd[0] = (0, 0, w, w, w, h, 0, 0)
-    out = np.zeros(1, np.uint64)
-    oracle().orc_dist_batch(2, p(a), p(b), p(dd), 1, p(out))
-    return int(out[0])
-
-
-def subtract(org, pred, bd):
-    h, w = org.shape
-    band = np.zeros(1, PELOP_DESC); band[0] = (0, 0, 0, w, w, w, w, h)
-    resi = np.zeros((h, w), np.int16)
-    oracle().orc_pelop_batch(3, p(org), p(pred), p(resi), p(band), 1, C.byref(PelopCfg(0, 0, 0, 0, 0, (1 << bd) - 1)))
-    return resi
-
-
-def reconstruct(pred, resi, clp):
-    h, w = pred.shape
-    band = np.zeros(1, PELOP_DESC); band[0] = (0, 0, 0, w, w, w, w, h)
-    rec = np.zeros((h, w), np.int16)
-    oracle().orc_pelop_batch(1, p(pred), p(resi), p(rec), p(band), 1, C.byref(PelopCfg(0, 0, 0, 1, clp[0], clp[1])))
-    return rec
-
-
 def code_slot(resi, bd, code, qp, intra, sbh):
     """transformNxN + invTransformNxN of one contiguous h x w residual -> (levels [h][w] int32, abs_sum, resi' [h][w] int16)"""
-    h, w = resi.shape
     th, tv = (3, 0) if code == TS else (code % 3, code // 3)
-    o = oracle()
-    tr = np.zeros(1, TR_DESC); tr[0] = (0, 0, w, w, h, th, tv, 0, 0)
-    qd = np.zeros(1, QUANT_DESC); qd[0] = (0, 0, w, h, intra, sbh, 0, qp, 0)
-    dq = np.zeros(1, DQTR_DESC); dq[0] = (0, 0, w, w, h, th, tv, 0, 0, qp)
-    resi2 = np.zeros((h, w), np.int16)
-    coef, level, dqc = np.zeros(w * h, np.int32), np.zeros(w * h, np.int32), np.zeros(w * h, np.int32)
-    abs_sum = np.zeros(1, np.uint32)
-    o.orc_tr_fwd_batch(p(resi), p(coef), p(tr), 1, bd)
-    o.orc_quant_batch(p(coef), p(level), p(qd), 1, bd, p(abs_sum))
-    o.orc_dequant_tr_inv_batch(p(level), p(resi2), p(dq), 1, bd, p(dqc))
-    return level.reshape(h, w), int(abs_sum[0]), resi2
+    level, abs_sum, resi2 = kit.code_resi(resi, bd, th, tv, qp, intra, sbh)
+    return level.reshape(resi.shape), abs_sum, resi2
 
 
 def restate(case, flags=0, clp=None, rd_list=None):
@@ -138,20 +87,20 @@ def restate(case, flags=0, clp=None, rd_list=None):
         w, h = int(it["w"]), int(it["h"])
         org = np.ascontiguousarray(block(case.org, int(it["org_off"]), int(it["org_stride"]), w, h))
         pred = np.ascontiguousarray(block(case.pred, poff, int(it["pred_stride"]), w, h))
-        org_resi = subtract(org, pred, bd)
-        out["zero_dist"][i] = sse(org_resi, np.zeros((h, w), np.int16))
+        org_resi = kit.subtract(org, pred, bd)
+        out["zero_dist"][i] = kit.sse(org_resi, np.zeros((h, w), np.int16))
         for k in range(SLOTS):
             code = int(it["tr"][k])
             if not slot_served(w, h, code):
                 continue
             level, abs_sum, resi2 = code_slot(org_resi, bd, code, int(it["qp"]), int(it["intra_slice"]), int(it["sign_hiding"]))
-            rec = reconstruct(pred, resi2, clp)
+            rec = kit.reconstruct(pred, resi2, clp)
             co, lo = int(it["cand_off"]) + k * w * h, int(it["level_off"]) + k * w * h
             resi_b[co:co + w * h] = resi2.reshape(-1)
             level_b[lo:lo + w * h] = level.reshape(-1)
             if flags & WRITE_REC:
                 rec_b[co:co + w * h] = rec.reshape(-1)
-            out["abs_sum"][i, k], out["dist_resi"][i, k], out["dist_rec"][i, k] = abs_sum, sse(org_resi, resi2), sse(org, rec)
+            out["abs_sum"][i, k], out["dist_resi"][i, k], out["dist_rec"][i, k] = abs_sum, kit.sse(org_resi, resi2), kit.sse(org, rec)
             out["clip_bites"][i, k] = not np.array_equal(rec.astype(np.int32), pred.astype(np.int32) + resi2)
     return out
 

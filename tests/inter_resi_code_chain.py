@@ -3,15 +3,19 @@ alter: vvcgpu_pelop_batch (subtract) -> vvcgpu_tr_fwd_batch -> vvcgpu_quant_batc
 (orgResi against resi', orgResi against a zero block) -> vvcgpu_pelop_batch (reconstruct) -> vvcgpu_dist_batch kind 2 (org against rec): eight launches, the
 residual, the coefficients and the de-quantised residual through device memory between them.  Served for items with a given prediction (no list items) and
 slots the entry serves.  Used by the consistency test of tests/test_gpu_inter_resi_code.py and by tools/inter_resi_code_time.py; Device.run_entry is the one
-call of the entry both use."""
+call of the entry both use.  Device also carries what the tests of the entry and of its DepQuant sibling (tests/inter_resi_dq_chain.py subclasses it) do
+alike: run / collect, the hand-over from vvcgpu_merge_cand_batch and the stored-zeros check."""
 import numpy as np
 import torch
 
+import inter_resi_code_cases as irc
+import merge_cand_chain
+import rd_pass_kit as kit
+from rd_pass_kit import dev
 from vvcsoftware_vtm_amd import abi, ops
 
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+KEYS = ("abs_sum", "zero_dist", "dist_resi", "dist_rec", "level", "resi", "rec")          # of kit.same: whole buffers, the canaries are part of the comparison
+FILLS = (irc.RESI_CANARY, irc.REC_CANARY, irc.LEVEL_CANARY)
 
 
 class Device:
@@ -21,6 +25,27 @@ class Device:
         self.org, self.pred, self.items_dev = dev(org), dev(pred), ops.struct_to_device(items)
         self.cand_size, self.level_size, self.fills = int(cand_size), int(level_size), fills
 
+    @staticmethod
+    def collect(resi, rec, level, outs):
+        """the three buffers and the entry's four outputs -> the dict the restatement returns"""
+        return kit.download((resi, rec, level) + tuple(outs), ("resi", "rec", "level", "abs_sum", "dist_resi", "dist_rec", "zero_dist"))
+
+    def run(self, flags=0, rd_list=None, with_rec=None):
+        """the entry on fresh buffers -> the dict the restatement returns (rec_base is NULL without WRITE_REC unless with_rec)"""
+        resi, rec, level = self.fresh()
+        give_rec = bool(flags & irc.WRITE_REC) if with_rec is None else with_rec
+        return self.collect(resi, rec, level, self.run_entry(resi, rec if give_rec else None, level, flags, rd_list))
+
+    def handover(self, M, pred_len):
+        """vvcgpu_merge_cand_batch (M: its merge_cand_chain.Device), then the entry under WRITE_REC with list items on the same stream, no download in
+        between; self holds the frame's original, the merge buffer of pred_len samples (with the room make() left behind it) becomes its prediction
+        -> (the dict the restatement returns, rd_list, the merge buffer) on the host"""
+        self.pred = torch.full((pred_len,), irc.PRED_GUARD, dtype=torch.int16, device="cuda")
+        resi, rec, level = self.fresh()
+        _, _, _, rd = merge_cand_chain.run_entry(M, self.pred, irc.HANDOVER_MAX_NUM, 1, irc.HANDOVER_LAM)
+        got = self.collect(resi, rec, level, self.run_entry(resi, rec, level, irc.WRITE_REC, rd))
+        return got, rd.cpu().numpy(), self.pred.cpu().numpy()
+
     def fresh(self):
         """-> (resi, rec, level) buffers painted with self.fills"""
         return (torch.full((self.cand_size,), self.fills[0], dtype=torch.int16, device="cuda"), torch.full((self.cand_size,), self.fills[1], dtype=torch.int16, device="cuda"),
@@ -29,6 +54,17 @@ class Device:
     def run_entry(self, resi, rec, level, flags=0, rd_list=None, clp=None):
         clp = clp or (0, (1 << self.bd) - 1)
         return ops.inter_resi_code_batch(self.org, self.pred, self.items_dev, self.n, resi, level, rec, rd_list, flags, self.bd, clp)
+
+
+def check_all_zero_slots(items, got):
+    """every served slot of `got` is an all-zero one: abs_sum 0, dist_resi == zero_dist, and resi' stored as zeros"""
+    served = got["abs_sum"] != irc.U32_MAX
+    assert (got["abs_sum"][served] == 0).all() and (got["dist_resi"] == got["zero_dist"][:, None])[served].all()
+    for i, it in enumerate(items):
+        for k in np.flatnonzero(served[i]):
+            sz = int(it["w"]) * int(it["h"])
+            co = int(it["cand_off"]) + int(k) * sz
+            assert not got["resi"][co:co + sz].any()
 
 
 class Chain:

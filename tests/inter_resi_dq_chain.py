@@ -9,7 +9,7 @@ import torch
 import inter_resi_code_chain as base
 from vvcsoftware_vtm_amd import abi, ops
 
-dev = base.dev
+dev, KEYS, FILLS, check_all_zero_slots = base.dev, base.KEYS, base.FILLS, base.check_all_zero_slots
 
 
 class Device(base.Device):

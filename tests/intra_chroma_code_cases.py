@@ -2,7 +2,7 @@
 mode) restated for the tests of vvcgpu_intra_chroma_code_batch from oracle steps that are each pinned to the compiled reference: orc_intra_fill_refs
 (tests/golden/intra_fill.npz), orc_intra_pred -- the restated predIntraAng, which runs 2-sample sides through the same code; tests/golden/gen_intra_chroma_code.py
 proves those against the reference's own predIntraAng --, orc_cclm_pred (tests/golden/cclm.npz) with the chroma neighbours taken from row 0 / column 0 of the
-references, the chain steps of intra_tu_code_cases.code_block, and SSE.  The contract (which PU is served, which slot) is written here from include/vvcgpu.h.
+references, and the chain steps of tests/rd_pass_kit.py as intra_tu_code_cases.code_block composes them.  The contract (which PU is served, which slot) is written here from include/vvcgpu.h.
 Also the case builders: a luma reconstruction, a chroma reconstruction and a chroma original of one 4:2:0 picture, PUs grouped by shape with candidate buffers
 of their own and canaries between them.  numpy only: the generator and the CPU tests load this file without torch."""
 import ctypes as C
@@ -13,6 +13,7 @@ import numpy as np
 import intra_mode_cand_cases as imc
 import intra_tu_code_cases as itc
 import pu_search_kit as kit
+import rd_pass_kit as rd
 from oraclelib import oracle, p
 from vvcsoftware_vtm_amd import abi
 
@@ -20,8 +21,8 @@ LM, WRITE_PRED = abi.INTRA_CHROMA_LM, abi.INTRA_CHROMA_WRITE_PRED
 SLOTS = 6
 CW, CH = 104, 88                    # the chroma planes; the luma plane is twice that
 UNIT = 2                            # pcv.minCUWidth / Height (4) shifted by the chroma scale
-U32_MAX, U64_MAX = itc.U32_MAX, itc.U64_MAX
-PRED_CANARY, REC_CANARY, LEVEL_CANARY, REFS_CANARY = itc.PRED_CANARY, itc.REC_CANARY, itc.LEVEL_CANARY, 0x3C3C
+U32_MAX, U64_MAX = rd.U32_MAX, rd.U64_MAX
+PRED_CANARY, REC_CANARY, LEVEL_CANARY, REFS_CANARY = rd.PRED_CANARY, rd.REC_CANARY, rd.LEVEL_CANARY, rd.REFS_CANARY
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "intra_chroma_code.npz")
 SHAPES = [(2, 2), (2, 8), (8, 2), (4, 4), (8, 8), (4, 16), (16, 16), (32, 8), (32, 32), (64, 64), (64, 16)]
 ref_lengths, ilog2, wide_angle = imc.ref_lengths, imc.ilog2, imc.wide_angle
@@ -35,10 +36,6 @@ def cand_modes(dm, lm=True):
 
 def n_units(w, h, unit=UNIT):
     return imc.n_units(w, h, unit)
-
-
-def side_ok(v):
-    return 2 <= v <= 64 and (v & (v - 1)) == 0
 
 
 def planes(rng, bd):
@@ -124,7 +121,7 @@ def pu_ok(case, q, have_luma=True, gather=True):
     u = case.pus[q]
     w, h = int(u["w"]), int(u["h"])
     rw, rh = (int(v) for v in case.run_shapes()[q])
-    if not (side_ok(w) and side_ok(h) and w == rw and h == rh and u["cand_off"] % 4 == 0 and u["level_off"] % 4 == 0):
+    if not (rd.side_ok(w, 2) and rd.side_ok(h, 2) and w == rw and h == rh and u["cand_off"] % 4 == 0 and u["level_off"] % 4 == 0):
         return False
     if not all(-1 <= int(m) <= LM for m in u["mode"]) or (not have_luma and LM in [int(m) for m in u["mode"]]):
         return False

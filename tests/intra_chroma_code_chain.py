@@ -3,15 +3,9 @@ tools/intra_chroma_code_time.py: vvcgpu_intra_fill_refs_batch for Cb and for Cr,
 neighbours into vvcgpu_cclm_pred_batch's nb_base layout ("w above, then h left"), vvcgpu_cclm_pred_batch for the LM slots, and
 vvcgpu_intra_tu_code_batch with PRED_GIVEN items -- every prediction goes through device memory.  The last entry takes sides 4..64 only."""
 import numpy as np
-import torch
 
+from rd_pass_kit import U32_MAX, U64_MAX, dev
 from vvcsoftware_vtm_amd import abi, ops
-
-U32_MAX, U64_MAX = 0xFFFFFFFF, 0xFFFFFFFFFFFFFFFF
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def ref_lengths(w, h):

@@ -1,23 +1,22 @@
 """The pixel pass of the intra RD loop (IntraSearch::xIntraCodingTUBlock, IntraSearch.cpp:1147-1316) restated for the tests of vvcgpu_intra_tu_code_batch from
-oracle steps that are each pinned to the compiled reference: orc_intra_filter_refs / orc_intra_pred, orc_pelop_batch (subtract), orc_tr_fwd_batch,
-orc_quant_batch, orc_dequant_tr_inv_batch, orc_pelop_batch (reconstruct), orc_dist_batch kind 2; num_sig is counted in numpy; the luma filter rule, the
+oracle steps that are each pinned to the compiled reference: orc_intra_filter_refs / orc_intra_pred, then the chain steps of tests/rd_pass_kit.py (subtract,
+forward transform, quantise, de-quantise with inverse transform, reconstruct, SSE); num_sig is counted in numpy; the luma filter rule, the
 list look-up and the planes come from intra_mode_cand_cases.  Also the case builders: items (a PU of an intra_mode_cand_cases.Case + a mode + the TU's
 transform and quantiser parameters) with candidate buffers of their own for prediction, reconstruction and levels, canaries between them.
 numpy only: the generator and the CPU tests load this file without torch."""
-import ctypes as C
 import os
 
 import numpy as np
 
 import intra_mode_cand_cases as imc
+import rd_pass_kit as kit
 from oraclelib import oracle, p
 from vvcsoftware_vtm_amd import abi
-from vvcsoftware_vtm_amd.abi import DIST_DESC, DQTR_DESC, PELOP_DESC, QUANT_DESC, TR_DESC, PelopCfg
 
 PRED_GIVEN, FROM_LIST = abi.INTRA_TU_PRED_GIVEN, abi.INTRA_TU_FROM_LIST
 WRITE_PRED, NO_SMOOTHING = abi.INTRA_TU_WRITE_PRED, abi.INTRA_TU_NO_SMOOTHING
-U32_MAX, U64_MAX = 0xFFFFFFFF, imc.U64_MAX
-PRED_CANARY, REC_CANARY, LEVEL_CANARY = 0x5A5A, -21846, 0x5A5A5A5A
+U32_MAX, U64_MAX, max_qp, block = kit.U32_MAX, kit.U64_MAX, kit.max_qp, kit.block
+PRED_CANARY, REC_CANARY, LEVEL_CANARY = kit.PRED_CANARY, kit.REC_CANARY, kit.LEVEL_CANARY
 EMT_SIG_NUM_THR = 2                                                         # g_EmtSigNumThr (Rom.cpp)
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "intra_tu_code.npz")
 
@@ -25,11 +24,6 @@ GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "int
 ITEM = np.dtype([("pu", "<i4"), ("mode", "<i4"), ("filt", "<i4"), ("w", "<i4"), ("h", "<i4"), ("tr_hor", "<i4"), ("tr_ver", "<i4"), ("qp", "<i4"),
                  ("intra", "<i4"), ("sbh", "<i4"), ("row", "<i4"), ("slot", "<i4"), ("pred_off", "<i8"), ("pred_stride", "<i4"), ("rec_off", "<i8"),
                  ("rec_stride", "<i4"), ("level_off", "<i8")])
-
-
-def max_qp(bd):
-    """the largest QpParam::Qp of the component: 63 (JVET_K0251) plus the bit-depth offset"""
-    return 63 + 6 * (bd - 8)
 
 
 def plain_case(bd, rec, org, blocks, rng=None):
@@ -83,16 +77,12 @@ class TuCase:
         return self.pred0.copy(), np.full(self.rec_size, REC_CANARY, np.int16), np.full(self.level_size, LEVEL_CANARY, np.int32)
 
 
-def side_ok(v):
-    return 4 <= v <= 64 and (v & (v - 1)) == 0
-
-
 def resolve(tc, i, flags, mode_list, have_pred=True):
     """-> (mode, filter) of item i, mode PRED_GIVEN included, or None: skipped"""
     it = tc.items[i]
     u = tc.base.pus[int(it["pu"])]
     w, h, mode = int(it["w"]), int(it["h"]), int(it["mode"])
-    if not (side_ok(w) and side_ok(h) and w == int(u["w"]) and h == int(u["h"]) and FROM_LIST <= mode <= 66):
+    if not (kit.side_ok(w, 4) and kit.side_ok(h, 4) and w == int(u["w"]) and h == int(u["h"]) and FROM_LIST <= mode <= 66):
         return None
     if not (0 <= it["tr_hor"] <= 2 and 0 <= it["tr_ver"] <= 2 and (w <= 32 or it["tr_hor"] == 0) and (h <= 32 or it["tr_ver"] == 0)):
         return None
@@ -109,31 +99,12 @@ def resolve(tc, i, flags, mode_list, have_pred=True):
     return mode, int(it["filt"] != 0)
 
 
-def block(buf, off, stride, w, h):
-    """the h x w view of a flat buffer"""
-    return np.lib.stride_tricks.as_strided(buf[off:], (h, w), (stride * buf.itemsize, buf.itemsize))
-
-
 def code_block(org, pred, bd, tr_hor, tr_ver, qp, intra, sbh, clp):
     """one TU from contiguous h x w original and prediction -> (levels [h][w] int32, abs_sum, rec [h][w] int16, dist) by the oracle's separate steps"""
-    h, w = org.shape
-    o = oracle()
     org, pred = np.ascontiguousarray(org, np.int16), np.ascontiguousarray(pred, np.int16)
-    band = np.zeros(1, PELOP_DESC); band[0] = (0, 0, 0, w, w, w, w, h)
-    tr = np.zeros(1, TR_DESC); tr[0] = (0, 0, w, w, h, tr_hor, tr_ver, 0, 0)
-    qd = np.zeros(1, QUANT_DESC); qd[0] = (0, 0, w, h, intra, sbh, 0, qp, 0)
-    dq = np.zeros(1, DQTR_DESC); dq[0] = (0, 0, w, w, h, tr_hor, tr_ver, 0, 0, qp)
-    dd = np.zeros(1, DIST_DESC); dd[0] = (0, 0, w, w, w, h, 0, 0)
-    resi, resi2, rec = np.zeros((h, w), np.int16), np.zeros((h, w), np.int16), np.zeros((h, w), np.int16)
-    coef, level, dqc = np.zeros(w * h, np.int32), np.zeros(w * h, np.int32), np.zeros(w * h, np.int32)
-    abs_sum, dist = np.zeros(1, np.uint32), np.zeros(1, np.uint64)
-    o.orc_pelop_batch(3, p(org), p(pred), p(resi), p(band), 1, C.byref(PelopCfg(0, 0, 0, 0, 0, (1 << bd) - 1)))
-    o.orc_tr_fwd_batch(p(resi), p(coef), p(tr), 1, bd)
-    o.orc_quant_batch(p(coef), p(level), p(qd), 1, bd, p(abs_sum))
-    o.orc_dequant_tr_inv_batch(p(level), p(resi2), p(dq), 1, bd, p(dqc))
-    o.orc_pelop_batch(1, p(pred), p(resi2), p(rec), p(band), 1, C.byref(PelopCfg(0, 0, 0, 1, clp[0], clp[1])))
-    o.orc_dist_batch(2, p(org), p(rec), p(dd), 1, p(dist))
-    return level.reshape(h, w), int(abs_sum[0]), rec, int(dist[0])
+    level, abs_sum, resi2 = kit.code_resi(kit.subtract(org, pred, bd), bd, tr_hor, tr_ver, qp, intra, sbh)
+    rec = kit.reconstruct(pred, resi2, clp)
+    return level.reshape(org.shape), abs_sum, rec, kit.sse(org, rec)
 
 
 def predict(refs, w, h, mode, filt, clp):

@@ -1,0 +1,224 @@
+"""What the tests, generators and timing tools of the RD pass entries (vvcgpu_intra_mode_cand_batch, vvcgpu_intra_tu_code_batch,
+vvcgpu_intra_chroma_code_batch, vvcgpu_inter_resi_code_batch, vvcgpu_inter_resi_code_dq_batch) share, each stated once: the skip markers, the canary values
+and the small helpers; the chain steps on one contiguous block -- subtract, forward transform, quantise, de-quantise with inverse transform, reconstruct,
+SSE -- through the CPU oracle or, given the handle R of reference(), through the compiled reference; the frame of the generators; the device harness of
+the tests/test_gpu_*.py files; the CPU-side checks of the golden files and of the argument-error tables; the lists and the row of the tools/*_time.py
+files.  numpy only at import time (torch is imported where it is used, so that the CPU tests and the generators load this file without it).
+The restatement of each pass -- restate, the item and slot rules, the list look-ups --, the case builders and the Case classes stay in the *_cases.py file
+of their entry; the inter pair's device harness is beside Device in tests/inter_resi_code_chain.py.
+
+The order of the rng draws in timing_lists is part of its contract: docs/MEASUREMENTS.md and profiles/*.txt were measured on these lists."""
+import ctypes as C
+import functools
+import os
+
+import numpy as np
+
+from oraclelib import oracle, p
+from pu_search_kit import U64_MAX, dev, events, times_of_alternating  # noqa: F401  (the device and timing helpers of the PU search kit, not copied)
+from vvcsoftware_vtm_amd.abi import DIST_DESC, DQTR_DESC, PELOP_DESC, QUANT_DESC, TR_DESC, PelopCfg
+
+# ---- markers and small helpers -------------------------------------------------------------------------------------------------------------------
+U32_MAX = 0xFFFFFFFF                                                        # abs_sum / num_sig of a skipped item or slot; U64_MAX: its distortions
+PRED_CANARY = RESI_CANARY = 0x5A5A                                          # what the candidate buffers hold before a call
+REC_CANARY, LEVEL_CANARY, REFS_CANARY = -21846, 0x5A5A5A5A, 0x3C3C
+GOLDEN_CAP = 400 * 1024                                                     # bytes a golden file of these entries may take
+
+
+def max_qp(bd):
+    """the largest QpParam::Qp of the component: 63 (JVET_K0251) plus the bit-depth offset"""
+    return 63 + 6 * (bd - 8)
+
+
+def side_ok(v, lo):
+    """a block side the entry serves: a power of two in lo..64"""
+    return lo <= v <= 64 and (v & (v - 1)) == 0
+
+
+def block(buf, off, stride, w, h):
+    """the h x w view of a flat buffer"""
+    return np.lib.stride_tricks.as_strided(buf[off:], (h, w), (stride * buf.itemsize, buf.itemsize))
+
+
+# ---- the chain steps on one contiguous h x w block: R None -> the CPU oracle, R = reference() -> the compiled reference ---------------------------
+def reference():
+    """the handle of the compiled reference (oracle/_ref/libvtmref.so) with the return types of its value-returning wrappers set"""
+    from oraclelib import ref
+    R = ref()
+    R.vtmref_dist.restype = C.c_uint64
+    R.vtmref_depquant.restype = C.c_uint32
+    return R
+
+
+def _step(R, name, *args):
+    """orc_<name> or, with R, vtmref_<name> (which reports success): the two take the same descriptors"""
+    if R is None:
+        getattr(oracle(), "orc_" + name)(*args)
+    else:
+        assert getattr(R, "vtmref_" + name)(*args) == 0, name
+
+
+def subtract(org, pred, bd, R=None):
+    """AreaBuf::subtract -> the residual [h][w] int16"""
+    h, w = org.shape
+    resi = np.zeros((h, w), np.int16)
+    if R is None:
+        band = np.zeros(1, PELOP_DESC); band[0] = (0, 0, 0, w, w, w, w, h)
+        oracle().orc_pelop_batch(3, p(org), p(pred), p(resi), p(band), 1, C.byref(PelopCfg(0, 0, 0, 0, 0, (1 << bd) - 1)))
+    else:
+        R.vtmref_pelop_area(3, p(org), w, p(pred), w, p(resi), w, w, h, 0, bd, 0, (1 << bd) - 1)
+    return resi
+
+
+def forward(resi, bd, tr_hor=0, tr_ver=0, R=None):
+    """the forward transform (tr_hor = 3: transform skip) -> the coefficients [w h] int32"""
+    h, w = resi.shape
+    tr = np.zeros(1, TR_DESC); tr[0] = (0, 0, w, w, h, tr_hor, tr_ver, 0, 0)
+    resi, coef = np.ascontiguousarray(resi), np.zeros(w * h, np.int32)
+    _step(R, "tr_fwd_batch", p(resi), p(coef), p(tr), 1, bd)
+    return coef
+
+
+def quantise(coef, w, h, bd, qp, intra, sbh, R=None):
+    """Quant::quant, the scalar quantiser -> (levels [w h] int32, abs_sum)"""
+    qd = np.zeros(1, QUANT_DESC); qd[0] = (0, 0, w, h, intra, sbh, 0, qp, 0)
+    level, abs_sum = np.zeros(w * h, np.int32), np.zeros(1, np.uint32)
+    _step(R, "quant_batch", p(coef), p(level), p(qd), 1, bd, p(abs_sum))
+    return level, int(abs_sum[0])
+
+
+def dequant_inverse(level, w, h, bd, tr_hor, tr_ver, qp, dep_quant=0, R=None):
+    """the de-quantiser (dep_quant 1: DQIntern::Quantizer::dequantBlock) and the inverse transform -> resi' [h][w] int16"""
+    dq = np.zeros(1, DQTR_DESC); dq[0] = (0, 0, w, w, h, tr_hor, tr_ver, dep_quant, 0, qp)
+    resi2, coef = np.zeros((h, w), np.int16), np.zeros(w * h, np.int32)
+    _step(R, "dequant_tr_inv_batch", p(level), p(resi2), p(dq), 1, bd, p(coef))
+    return resi2
+
+
+def code_resi(resi, bd, tr_hor, tr_ver, qp, intra, sbh, R=None):
+    """transformNxN + invTransformNxN of one residual under the scalar quantiser -> (levels [w h] int32, abs_sum, resi' [h][w] int16)"""
+    h, w = resi.shape
+    level, abs_sum = quantise(forward(resi, bd, tr_hor, tr_ver, R), w, h, bd, qp, intra, sbh, R)
+    return level, abs_sum, dequant_inverse(level, w, h, bd, tr_hor, tr_ver, qp, 0, R)
+
+
+def reconstruct(pred, resi, clp, bd=0, R=None):
+    """clip(pred + resi) -> the reconstruction [h][w] int16 (the reference's wrapper takes the bit depth too)"""
+    h, w = pred.shape
+    rec = np.zeros((h, w), np.int16)
+    if R is None:
+        band = np.zeros(1, PELOP_DESC); band[0] = (0, 0, 0, w, w, w, w, h)
+        oracle().orc_pelop_batch(1, p(pred), p(resi), p(rec), p(band), 1, C.byref(PelopCfg(0, 0, 0, 1, clp[0], clp[1])))
+    else:
+        R.vtmref_pelop(1, 1, p(pred), w, p(resi), w, p(rec), w, w, h, 0, 0, 0, 1, bd, clp[0], clp[1])
+    return rec
+
+
+def sse(a, b, bd=0, R=None):
+    """RdCost::xGetSSE of two int16 blocks (the reference's wrapper takes the bit depth too)"""
+    h, w = a.shape
+    if R is not None:
+        return int(R.vtmref_dist(2, 1, p(a), w, p(b), w, w, h, bd, 0))
+    dd = np.zeros(1, DIST_DESC); dd[0] = (0, 0, w, w, w, h, 0, 0)
+    out = np.zeros(1, np.uint64)
+    oracle().orc_dist_batch(2, p(a), p(b), p(dd), 1, p(out))
+    return int(out[0])
+
+
+# ---- the generators' frame ------------------------------------------------------------------------------------------------------------------------
+def check_restatement(want, stored, label):
+    """the restatement reproduces every stored value (stored: {name: the array the compiled reference gave})"""
+    for k, v in stored.items():
+        assert np.array_equal(want[k], v), (label, k)
+
+
+def save_golden(path, arrays):
+    np.savez_compressed(path, **arrays)
+    print("wrote", path, os.path.getsize(path), "bytes")
+    assert os.path.getsize(path) <= GOLDEN_CAP
+
+
+# ---- the device harness of tests/test_gpu_*.py ------------------------------------------------------------------------------------------------------
+VIEWS = dict(abs_sum=np.uint32, num_sig=np.uint32, dist=np.uint64, dist_resi=np.uint64, dist_rec=np.uint64, zero_dist=np.uint64)
+
+
+def download(tensors, names, views=VIEWS):
+    """synchronise, then the device tensors as host arrays by name; the counters and distortions, which torch holds signed, as what they are"""
+    import torch
+    torch.cuda.synchronize()
+    out = {}
+    for name, t in zip(names, tensors):
+        a = t.cpu().numpy()
+        out[name] = a.view(views[name]) if name in views else a
+    return out
+
+
+def same(got, want, keys):
+    """bit for bit over whole buffers (the canaries are part of the comparison); reports the first differing indices"""
+    for k in keys:
+        g, w = got[k], want[k]
+        assert np.array_equal(g, w), (k, np.flatnonzero(np.asarray(g).reshape(-1) != np.asarray(w).reshape(-1))[:8])
+
+
+@functools.lru_cache(maxsize=None)
+def cached(builder, *args):
+    """builder(*args), computed once per test session: the restatements are the slow part, and nothing writes to what they return"""
+    return builder(*args)
+
+
+# ---- the CPU-side checks ---------------------------------------------------------------------------------------------------------------------------
+def check_golden_file(path):
+    """a golden file holds integer data only and stays under the cap"""
+    assert os.path.getsize(path) <= GOLDEN_CAP
+    g = np.load(path, allow_pickle=False)
+    assert all(g[k].dtype.kind in "iu" for k in g.files)
+
+
+def check_argument_errors(call, cases, name, empty=({},), bad_depths=(7, 11, 12)):
+    """call(**kw): the entry with arguments that pass every check, changed by kw.  Every entry of `cases` is refused (VVCGPU_E_ARG) with the entry's name
+    in vvcgpu_last_error(), the unsupported bit depths return VVCGPU_E_UNSUPPORTED, and n == 0 succeeds with each of the `empty` argument sets -- all
+    before any device work"""
+    from vvcsoftware_vtm_amd import capi
+    lib = capi.lib()
+    for kw in cases:
+        assert call(**dict(kw)) == -1, kw
+        assert name in lib.vvcgpu_last_error(), kw
+    for bd in bad_depths:
+        assert call(bd=bd) == -3, bd
+        assert name in lib.vvcgpu_last_error(), bd
+    for kw in empty:
+        assert call(n=0, **kw) == 0, kw
+
+
+# ---- the lists and the row of tools/*_time.py --------------------------------------------------------------------------------------------------------
+def trace_shapes(rng, sides, count=8000):
+    """`count` shapes [count][2] drawn (one rng.choice) from the pelop calls of the committed call trace whose sides are both in `sides`, by their weight"""
+    from vvcsoftware_vtm_amd import shape_mix
+    hist, _ = shape_mix.load_trace()
+    sig = shape_mix.signatures(hist, "pelop", lambda w, h, a, b, c: a == 0 and w in sides and h in sides)
+    return np.array([(int(w), int(h)) for w, h in sig[rng.choice(len(sig), count, p=sig[:, 5] / sig[:, 5].sum()), :2]])
+
+
+def timing_lists(rng, W, H, sides, chroma=False):
+    """-> [(name, w, h, px, py)]: "4K", the interior 16x16 grid of a W x H luma plane, and "trace mix", trace_shapes(rng, sides) at random positions on the
+    4-sample grid (rng.choice, then rng.integers for x, then for y).  chroma: W x H is the chroma plane of a 4:2:0 picture -- the same luma blocks,
+    shapes, grid and position bounds halved"""
+    s = 1 if chroma else 0
+    mix = trace_shapes(rng, sides) >> s
+    bx, by = np.meshgrid(np.arange(1, (W << s) // 16 - 2), np.arange(1, (H << s) // 16 - 2))
+    b, u = 16 >> s, 4 >> s
+    g = np.stack([bx.ravel() * b, by.ravel() * b], 1)
+    return [("4K %dx%d" % (b, b), np.full(len(g), b), np.full(len(g), b), g[:, 0], g[:, 1]),
+            ("trace mix", mix[:, 0], mix[:, 1], rng.integers(1, (W - 160) // u, len(mix)) * u, rng.integers(1, (H - 160) // u, len(mix)) * u)]
+
+
+def time_row(head, chained, entry, check, warmup, runs):
+    """compare, then alternate, then print the row: check(what chained() returned, what entry() returned) asserts their equality and returns the row's
+    last column (the all-zero count); the comparison is the first warm-up run; `head` is the row's own first columns"""
+    import torch
+    oc, oe = chained(), entry()
+    torch.cuda.synchronize()
+    last = check(oc, oe)
+    ta, tb = times_of_alternating((chained, entry), warmup - 1, runs)
+    ma, mb = float(np.median(ta)), float(np.median(tb))
+    print("%s   %8.3f (%.3f..%.3f)   %8.3f (%.3f..%.3f)   %13.2f   %d" % (head, ma, min(ta), max(ta), mb, min(tb), max(tb), ma / mb, last))

@@ -58,8 +58,9 @@ SIZED = {31: ("WP_PARAM", 16), 32: ("WP_SAD_CAND", 16), 33: ("TILE_STATS", 24),
          48: ("AFFINE_BIPRED_STEP", 56),
          50: ("UNIPRED_ME_REF", 40), 51: ("UNIPRED_ME_ITEM", 360), 52: ("UnipredMeCfg", 304), 53: ("UNIPRED_ME_SEARCH", 48), 54: ("UNIPRED_ME_RESULT", 472),
          56: ("AFFINE_UNIPRED_REF", 80), 57: ("AFFINE_UNIPRED_ITEM", 688), 58: ("AffineUnipredCfg", 264), 59: ("AFFINE_UNIPRED_SEARCH", 88),
-         60: ("AFFINE_UNIPRED_RESULT", 840)}
-UNUSED_IDS = (43, 49, 55, 61)
+         60: ("AFFINE_UNIPRED_RESULT", 840),
+         62: ("INTRA_CHROMA_PU", 96), 63: ("INTER_RESI_ITEM", 80), 65: ("INTER_RESI_DQ", 16)}
+UNUSED_IDS = (43, 49, 55, 61, 64)
 
 
 def test_struct_layouts_match_python_bindings():
@@ -76,15 +77,16 @@ def test_struct_layouts_match_python_bindings():
         assert lib.vvcgpu_sizeof(k) == v, (k, lib.vvcgpu_sizeof(k), v)
     for k, (name, size) in SIZED.items():
         assert lib.vvcgpu_sizeof(k) == size == _mirror_size(getattr(abi, name)), (k, name, lib.vvcgpu_sizeof(k), size)
-    assert sorted(want) + sorted(SIZED) == [k for k in range(61) if k not in UNUSED_IDS]
+    assert sorted(want) + sorted(SIZED) == [k for k in range(66) if k not in UNUSED_IDS]
     for k in UNUSED_IDS + (99,):
         assert lib.vvcgpu_sizeof(k) == -1, k
     assert all(size % 8 == 0 for k, (_, size) in SIZED.items() if 56 <= k <= 60)             # the affine uni-predictive records pack into arrays of 8-byte members
     assert abi.AFFINE_BIPRED_ITEM.itemsize == 784                                              # the out-items of the affine uni-predictive entry
+    assert SIZED[62][1] % 16 == 0 and SIZED[63][1] % 16 == 0                                   # the RD pass items: 16-byte loads of a whole record
 
 
 def test_header_constants_match_python_bindings():
-    """the array bounds, flag values and stated sizes of the PU search entries in include/vvcgpu.h == abi's"""
+    """the array bounds, flag values and stated sizes of the PU search entries and of the RD pass entries in include/vvcgpu.h == abi's"""
     hdr = " ".join(open(capi.HEADER).read().split())
     for name in ("AFFINE_ME_MAX_STEPS", "BIPRED_ME_MAX_STEPS", "BIPRED_ME_MAX_REFS", "BIPRED_ME_MAX_PLANES", "AFFINE_BIPRED_MAX_STEPS", "AFFINE_BIPRED_MAX_REFS",
                  "UNIPRED_ME_MAX_REFS", "UNIPRED_ME_MAX_PLANES", "AFFINE_UNIPRED_MAX_REFS"):
@@ -95,6 +97,10 @@ def test_header_constants_match_python_bindings():
     # the out-items of the uni-predictive entries are the bi-predictive entries' items
     assert abi.BIPRED_ME_MAX_REFS == abi.UNIPRED_ME_MAX_REFS and abi.BIPRED_ME_MAX_PLANES == abi.UNIPRED_ME_MAX_PLANES
     assert abi.AFFINE_BIPRED_MAX_REFS == abi.AFFINE_UNIPRED_MAX_REFS
+    rd_pass = dict(INTER_RESI_SLOTS=6, INTER_RESI_TS=9, INTER_RESI_WRITE_REC=1, INTER_RESI_Q_DEPQUANT=1, INTRA_CHROMA_LM=67, INTRA_CHROMA_WRITE_PRED=1)
+    for name, value in rd_pass.items():
+        assert int(re.search(r"#define VVCGPU_%s \(?(-?\d+)\)?" % name, hdr).group(1)) == getattr(abi, name) == value, name
+    assert abi.INTER_RESI_ITEM.fields["tr"][0].shape == (abi.INTER_RESI_SLOTS,)
 
 
 # every typedef struct of include/vvcgpu.h -> its mirrors in vvcsoftware_vtm_amd.abi
@@ -120,6 +126,7 @@ MIRRORS = {
     "vvcgpu_unipred_me_search": ["UNIPRED_ME_SEARCH"], "vvcgpu_unipred_me_result": ["UNIPRED_ME_RESULT"],
     "vvcgpu_affine_unipred_ref": ["AFFINE_UNIPRED_REF"], "vvcgpu_affine_unipred_item": ["AFFINE_UNIPRED_ITEM"], "vvcgpu_affine_unipred_cfg": ["AffineUnipredCfg"],
     "vvcgpu_affine_unipred_search": ["AFFINE_UNIPRED_SEARCH"], "vvcgpu_affine_unipred_result": ["AFFINE_UNIPRED_RESULT"],
+    "vvcgpu_intra_chroma_pu": ["INTRA_CHROMA_PU"], "vvcgpu_inter_resi_item": ["INTER_RESI_ITEM"], "vvcgpu_inter_resi_dq": ["INTER_RESI_DQ"],
 }
 # mirror fields named differently from their C member
 RENAMED = {("MvCost", "lambda_"): "lambda", ("TZ_CFG", "reserved"): "uniform_pu"}
@@ -150,7 +157,7 @@ def test_struct_mirrors_match_header_field_by_field(tmp_path):
     """the C compiler's sizeof / offsetof of include/vvcgpu.h == every mirror in abi, per struct and per field"""
     hdr = re.sub(r"/\*.*?\*/", "", open(capi.HEADER).read(), flags=re.S)
     names = re.findall(r"typedef\s+struct\s*(?:vvcgpu_\w+)?\s*\{[^{}]*\}\s*(vvcgpu_\w+)\s*;", hdr)          # tagged or anonymous: the closing name
-    assert sorted(names) == sorted(MIRRORS) and len(names) >= 62
+    assert sorted(names) == sorted(MIRRORS) and len(names) >= 65
     mirrors = {(cname, name): getattr(abi, name) for cname, names in MIRRORS.items() for name in names}
     fields = {key: _mirror_fields(m) for key, m in mirrors.items()}
     seen = {(name, f) for (_, name), fs in fields.items() for f, _, _ in fs}
@@ -204,6 +211,8 @@ def test_every_declared_function_has_a_signature(tmp_path, monkeypatch):
     assert protos["vvcgpu_malloc"][1] == (C.c_void_p, C.c_size_t)                                           # void**
     assert protos["vvcgpu_me_hier_search"][1][6:8] == (C.c_void_p, C.c_void_p)                             # vvcgpu_search_best* const*
     assert protos["vvcgpu_imv_refine_batch"][1][7:9] == (C.c_int, C.c_double)
+    assert len(protos["vvcgpu_inter_resi_code_batch"][1]) == 17 and len(protos["vvcgpu_inter_resi_code_dq_batch"][1]) == 24
+    assert protos["vvcgpu_inter_resi_code_dq_workspace_bytes"] == (C.c_size_t, (C.c_size_t, C.c_int))
     # a value of the wrong type or a wrong argument count is refused before the call
     with pytest.raises(C.ArgumentError):
         lib.vvcgpu_sizeof(1.5)

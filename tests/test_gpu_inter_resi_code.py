@@ -1,9 +1,7 @@
 """vvcgpu_inter_resi_code_batch on the device, bit for bit through the C ABI with the canaries intact: against the compiled reference's values
 (tests/golden/inter_resi_code.npz), and against the restatement of the pass (tests/inter_resi_code_cases.py) on every shape, a random list, the hand-over
 from vvcgpu_merge_cand_batch on one stream, all-zero slots, the bounds and predictions at the clip bounds; as a supplement the chain of the existing
-entries (tests/inter_resi_code_chain.py)."""
-import functools
-
+entries (tests/inter_resi_code_chain.py, which also holds the harness this file shares with tests/test_gpu_inter_resi_dq.py)."""
 import numpy as np
 import pytest
 import torch
@@ -11,36 +9,25 @@ import torch
 import inter_resi_code_cases as irc
 import inter_resi_code_chain as chain
 import merge_cand_chain
-from vvcsoftware_vtm_amd import ops
+import rd_pass_kit as kit
 
 pytestmark = pytest.mark.gpu
 
-FILLS = (irc.RESI_CANARY, irc.REC_CANARY, irc.LEVEL_CANARY)
-
 
 def device_of(case):
-    return chain.Device(case.bd, case.org, case.pred, case.items, case.cand_size, case.level_size, FILLS)
+    return chain.Device(case.bd, case.org, case.pred, case.items, case.cand_size, case.level_size, chain.FILLS)
 
 
 def run(case, flags=0, rd_list=None, D=None, with_rec=None):
-    """the entry on the case -> the dict the restatement returns (rec_base is NULL without WRITE_REC unless with_rec)"""
-    D = D or device_of(case)
-    resi, rec, level = D.fresh()
-    give_rec = bool(flags & irc.WRITE_REC) if with_rec is None else with_rec
-    a, dr, dc, zd = D.run_entry(resi, rec if give_rec else None, level, flags, rd_list)
-    torch.cuda.synchronize()
-    return dict(resi=resi.cpu().numpy(), rec=rec.cpu().numpy(), level=level.cpu().numpy(), abs_sum=a.cpu().numpy().view(np.uint32),
-                dist_resi=dr.cpu().numpy().view(np.uint64), dist_rec=dc.cpu().numpy().view(np.uint64), zero_dist=zd.cpu().numpy().view(np.uint64))
+    return (D or device_of(case)).run(flags, rd_list, with_rec)
 
 
 def same(got, want):
-    for name in ("abs_sum", "zero_dist", "dist_resi", "dist_rec", "level", "resi", "rec"):          # whole buffers: the canaries are part of the comparison
-        assert np.array_equal(got[name], want[name]), name
+    kit.same(got, want, chain.KEYS)
 
 
-@functools.lru_cache(maxsize=None)
-def cached(name, bd):
-    return getattr(irc, name)(bd)
+def cached(name, *args):
+    return kit.cached(getattr(irc, name), *args)
 
 
 @pytest.mark.parametrize("bd", [8, 10])
@@ -79,17 +66,10 @@ def test_handover_from_merge_cand_batch(bd):
     """vvcgpu_merge_cand_batch, then the entry with list items for slots 0 .. 3 on the same stream, no download in between"""
     fr, L, mwant, case, want = cached("handover_case", bd)
     M = merge_cand_chain.Device(fr, L)
-    D = chain.Device(bd, fr.org, np.zeros(1, np.int16), case.items, case.cand_size, case.level_size, FILLS)
-    pred = torch.full((len(case.pred),), irc.PRED_GUARD, dtype=torch.int16, device="cuda")     # the merge buffer, with the room make() left behind it
-    D.pred = pred
-    resi, rec, level = D.fresh()
-    _, _, _, rd = merge_cand_chain.run_entry(M, pred, irc.HANDOVER_MAX_NUM, 1, irc.HANDOVER_LAM)
-    a, dr, dc, zd = D.run_entry(resi, rec, level, irc.WRITE_REC, rd)
-    torch.cuda.synchronize()
-    assert np.array_equal(rd.cpu().numpy(), mwant["rd_list"])
-    assert np.array_equal(pred.cpu().numpy()[:len(mwant["pred"])], mwant["pred"])
-    got = dict(resi=resi.cpu().numpy(), rec=rec.cpu().numpy(), level=level.cpu().numpy(), abs_sum=a.cpu().numpy().view(np.uint32),
-               dist_resi=dr.cpu().numpy().view(np.uint64), dist_rec=dc.cpu().numpy().view(np.uint64), zero_dist=zd.cpu().numpy().view(np.uint64))
+    D = chain.Device(bd, fr.org, np.zeros(1, np.int16), case.items, case.cand_size, case.level_size, chain.FILLS)
+    got, rd, pred = D.handover(M, len(case.pred))
+    assert np.array_equal(rd, mwant["rd_list"])
+    assert np.array_equal(pred[:len(mwant["pred"])], mwant["pred"])
     same(got, irc.restate(case, irc.WRITE_REC, rd_list=mwant["rd_list"]))
     assert np.array_equal(got["abs_sum"], want["abs_sum"])
 
@@ -99,13 +79,7 @@ def test_all_zero_slots(bd):
     case, want = cached("zero_case", bd)
     got = run(case, irc.WRITE_REC)
     same(got, irc.restate(case, irc.WRITE_REC))
-    served = got["abs_sum"] != irc.U32_MAX
-    assert (got["abs_sum"][served] == 0).all() and (got["dist_resi"] == got["zero_dist"][:, None])[served].all()
-    for i, it in enumerate(case.items):                                      # stored zeros
-        for k in np.flatnonzero(served[i]):
-            sz = int(it["w"]) * int(it["h"])
-            co = int(it["cand_off"]) + int(k) * sz
-            assert not got["resi"][co:co + sz].any()
+    chain.check_all_zero_slots(case.items, got)
 
 
 @pytest.mark.parametrize("bd", [8, 10])

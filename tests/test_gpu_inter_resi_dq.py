@@ -1,9 +1,8 @@
 """vvcgpu_inter_resi_code_dq_batch on the device, bit for bit through the C ABI with the canaries intact: against the compiled reference's values
 (tests/golden/inter_resi_dq.npz), and against the restatement of the pass (tests/inter_resi_dq_cases.py) on every shape, a random list with skipped items,
 record counts around the trellis' packing, the hand-over from vvcgpu_merge_cand_batch on one stream, a workspace that is dirty and reused, all-zero slots,
-predictions at the clip bounds; as a supplement the chain of the existing entries (tests/inter_resi_dq_chain.py); the contract of the argument checks."""
-import functools
-
+predictions at the clip bounds; as a supplement the chain of the existing entries (tests/inter_resi_dq_chain.py); the contract of the argument checks.  The harness this file shares
+with tests/test_gpu_inter_resi_code.py is beside Device in tests/inter_resi_code_chain.py."""
 import numpy as np
 import pytest
 import torch
@@ -12,41 +11,28 @@ import inter_resi_code_cases as irc
 import inter_resi_dq_cases as dqc
 import inter_resi_dq_chain as chain
 import merge_cand_chain
-from vvcsoftware_vtm_amd import capi, ops
+import rd_pass_kit as kit
+from vvcsoftware_vtm_amd import capi
 
 pytestmark = pytest.mark.gpu
 
-FILLS = (irc.RESI_CANARY, irc.REC_CANARY, irc.LEVEL_CANARY)
 WS_FILL = 0xA7                                                               # the workspace holds anything on entry
 
 
 def device_of(case):
-    return chain.Device(case.bd, case.org, case.pred, case.items, case.dq, case.rates, case.cand_size, case.level_size, FILLS, WS_FILL)
-
-
-def collect(resi, rec, level, outs):
-    a, dr, dc, zd = outs
-    torch.cuda.synchronize()
-    return dict(resi=resi.cpu().numpy(), rec=rec.cpu().numpy(), level=level.cpu().numpy(), abs_sum=a.cpu().numpy().view(np.uint32),
-                dist_resi=dr.cpu().numpy().view(np.uint64), dist_rec=dc.cpu().numpy().view(np.uint64), zero_dist=zd.cpu().numpy().view(np.uint64))
+    return chain.Device(case.bd, case.org, case.pred, case.items, case.dq, case.rates, case.cand_size, case.level_size, chain.FILLS, WS_FILL)
 
 
 def run(case, flags=0, rd_list=None, D=None, with_rec=None):
-    """the entry on the case -> the dict the restatement returns (rec_base is NULL without WRITE_REC unless with_rec)"""
-    D = D or device_of(case)
-    resi, rec, level = D.fresh()
-    give_rec = bool(flags & dqc.WRITE_REC) if with_rec is None else with_rec
-    return collect(resi, rec, level, D.run_entry(resi, rec if give_rec else None, level, flags, rd_list))
+    return (D or device_of(case)).run(flags, rd_list, with_rec)
 
 
 def same(got, want):
-    for name in ("abs_sum", "zero_dist", "dist_resi", "dist_rec", "level", "resi", "rec"):          # whole buffers: the canaries are part of the comparison
-        assert np.array_equal(got[name], want[name]), name
+    kit.same(got, want, chain.KEYS)
 
 
-@functools.lru_cache(maxsize=None)
 def cached(name, *args):
-    return getattr(dqc, name)(*args)
+    return kit.cached(getattr(dqc, name), *args)
 
 
 @pytest.mark.parametrize("bd", [8, 10])
@@ -97,13 +83,9 @@ def test_handover_from_merge_cand_batch(bd):
     """vvcgpu_merge_cand_batch, then the entry with list items for slots 0 .. 3 on the same stream, no download in between"""
     fr, L, mwant, case, want = cached("handover_case", bd)
     M = merge_cand_chain.Device(fr, L)
-    D = chain.Device(bd, fr.org, np.zeros(1, np.int16), case.items, case.dq, case.rates, case.cand_size, case.level_size, FILLS, WS_FILL)
-    pred = torch.full((len(case.pred),), irc.PRED_GUARD, dtype=torch.int16, device="cuda")     # the merge buffer, with the room make() left behind it
-    D.pred = pred
-    resi, rec, level = D.fresh()
-    _, _, _, rd = merge_cand_chain.run_entry(M, pred, irc.HANDOVER_MAX_NUM, 1, irc.HANDOVER_LAM)
-    got = collect(resi, rec, level, D.run_entry(resi, rec, level, dqc.WRITE_REC, rd))
-    assert np.array_equal(rd.cpu().numpy(), mwant["rd_list"])
+    D = chain.Device(bd, fr.org, np.zeros(1, np.int16), case.items, case.dq, case.rates, case.cand_size, case.level_size, chain.FILLS, WS_FILL)
+    got, rd, _ = D.handover(M, len(case.pred))
+    assert np.array_equal(rd, mwant["rd_list"])
     same(got, want)
 
 
@@ -116,7 +98,7 @@ def test_workspace_dirty_and_reused():
     ws = torch.full((n_ws,), WS_FILL, dtype=torch.uint8, device="cuda")
     for D, want in ((D1, w1), (D2, w2), (D1, w1)):
         resi, rec, level = D.fresh()
-        same(collect(resi, rec, level, D.run_entry(resi, None, level, 0, None, ws=ws)), want)
+        same(D.collect(resi, rec, level, D.run_entry(resi, None, level, 0, None, ws=ws)), want)
 
 
 @pytest.mark.parametrize("bd", [8, 10])
@@ -125,13 +107,7 @@ def test_all_zero_slots(bd):
     case, want = cached("zero_case", bd)
     got = run(case, dqc.WRITE_REC)
     same(got, want)
-    served = got["abs_sum"] != dqc.U32_MAX
-    assert (got["abs_sum"][served] == 0).all() and (got["dist_resi"] == got["zero_dist"][:, None])[served].all()
-    for i, it in enumerate(case.items):
-        for k in np.flatnonzero(served[i]):
-            sz = int(it["w"]) * int(it["h"])
-            co = int(it["cand_off"]) + int(k) * sz
-            assert not got["resi"][co:co + sz].any()
+    chain.check_all_zero_slots(case.items, got)
 
 
 @pytest.mark.parametrize("bd", [8, 10])

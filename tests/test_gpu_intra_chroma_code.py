@@ -3,9 +3,6 @@
 references gathered and given, the stored prediction, the skip markers, the argument errors, the hand-over of the luma reconstruction from
 vvcgpu_intra_tu_code_batch on one stream, and the bound item.  Every comparison is bit for bit and covers the whole of the four output buffers, i.e. the
 canaries around every region and the untouched regions of skipped slots too."""
-import ctypes as C
-import functools
-
 import numpy as np
 import pytest
 import torch
@@ -13,13 +10,14 @@ import torch
 import intra_chroma_code_cases as icc
 import intra_chroma_code_chain as chain
 import intra_tu_code_cases as itc
+import rd_pass_kit as kit
+from rd_pass_kit import dev
 from test_intra_chroma_code_cpu import E_ARG_CASES
 from vvcsoftware_vtm_amd import capi, ops
 
 pytestmark = pytest.mark.gpu
 
 KEYS = ("refs", "pred", "rec", "level", "abs_sum", "dist")
-dev = chain.dev
 
 
 def launch(case, flags=0, clp=None, gather=True, refs=None, luma=True, use_pred=True, write_refs=True):
@@ -37,15 +35,11 @@ def launch(case, flags=0, clp=None, gather=True, refs=None, luma=True, use_pred=
 
 
 def download(out):
-    torch.cuda.synchronize()
-    refs, pred, rec, level, abs_sum, dist = [t.cpu().numpy() for t in out]
-    return dict(refs=refs, pred=pred, rec=rec, level=level, abs_sum=abs_sum.view(np.uint32), dist=dist.view(np.uint64))
+    return kit.download(out, KEYS)
 
 
-def same(got, want, keys=KEYS):
-    for k in keys:
-        g, w = got[k], want[k]
-        assert np.array_equal(g, w), (k, np.flatnonzero(np.asarray(g).reshape(-1) != np.asarray(w).reshape(-1))[:8])
+def same(got, want):
+    kit.same(got, want, KEYS)
 
 
 @pytest.mark.parametrize("bd", [8, 10])
@@ -57,12 +51,15 @@ def test_against_golden(bd):
         assert np.array_equal(got[name], g["bd%d_want_%s" % (bd, name)]), name
 
 
-@functools.lru_cache(maxsize=None)
-def mixed(bd):
+def mixed_case(bd):
     """a few dozen PUs with sides 4..64 (the chain's last entry takes no 2-sample side) -> (case, restatement under WRITE_PRED)"""
     rng = np.random.default_rng(9100 + bd)
     case = icc.make(rng, bd, [s for s in icc.mixed_specs(rng, bd, 56) if min(s["w"], s["h"]) >= 4][:40])
     return case, icc.restate(case, icc.WRITE_PRED)
+
+
+def mixed(bd):
+    return kit.cached(mixed_case, bd)
 
 
 @pytest.mark.parametrize("bd", [8, 10])
@@ -152,11 +149,7 @@ def test_skip_markers_between_valid_neighbours():
 
 def test_argument_errors_and_the_empty_list():
     import test_intra_chroma_code_cpu as cpu
-    lib = capi.lib()
-    for kw in E_ARG_CASES:
-        assert cpu.call(**dict(kw)) == -1 and b"intra_chroma_code_batch" in lib.vvcgpu_last_error(), kw
-    for bd in (7, 11):
-        assert cpu.call(bd=bd) == -3, bd
+    kit.check_argument_errors(cpu.call, E_ARG_CASES, b"intra_chroma_code_batch")
     case, _ = mixed(10)
     refs0, pred0, rec0, level0 = case.initial()
     rec, level = dev(rec0), dev(level0)

@@ -2,8 +2,6 @@
 (tests/intra_tu_code_cases.py): every shape, the hand-over of the mode lists of vvcgpu_intra_mode_cand_batch on one stream, given predictions, the stored
 prediction, short and shuffled lists, candidates of one PU, odd offsets and strides, invalid items, a narrowed clip range and the bound items.  Every
 comparison is bit for bit and covers the whole of the three output buffers, i.e. the canaries around every region too."""
-import functools
-
 import numpy as np
 import pytest
 import torch
@@ -11,15 +9,13 @@ import torch
 import intra_mode_cand_cases as imc
 import intra_mode_cand_chain as chain
 import intra_tu_code_cases as itc
+import rd_pass_kit as kit
+from rd_pass_kit import dev
 from vvcsoftware_vtm_amd import ops
 
 pytestmark = pytest.mark.gpu
 
 KEYS = ("pred", "rec", "level", "abs_sum", "num_sig", "dist", "mode_out")
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def launch(tc, flags=0, clp=None, mode_list=None, refs=None, org=None, use_pred=True, n=None):
@@ -36,15 +32,11 @@ def launch(tc, flags=0, clp=None, mode_list=None, refs=None, org=None, use_pred=
 
 
 def download(out):
-    torch.cuda.synchronize()
-    pred, rec, level, abs_sum, num_sig, dist, mode_out = [t.cpu().numpy() for t in out]
-    return dict(pred=pred, rec=rec, level=level, abs_sum=abs_sum.view(np.uint32), num_sig=num_sig.view(np.uint32), dist=dist.view(np.uint64), mode_out=mode_out)
+    return kit.download(out, KEYS)
 
 
 def same(got, want):
-    for k in KEYS:
-        g, w = got[k], want[k]
-        assert np.array_equal(g, w), (k, np.flatnonzero(np.asarray(g).reshape(-1) != np.asarray(w).reshape(-1))[:8])
+    kit.same(got, want, KEYS)
 
 
 @pytest.mark.parametrize("bd", [8, 10])
@@ -58,9 +50,8 @@ def test_against_golden(bd):
     same(got, itc.restate(tc, flags))
 
 
-@functools.lru_cache(maxsize=None)
 def shapes(bd):
-    return itc.shapes_case(bd)
+    return kit.cached(itc.shapes_case, bd)
 
 
 @pytest.mark.parametrize("bd", [8, 10])

@@ -1,17 +1,15 @@
 """vvcgpu_inter_resi_code_batch without a GPU: the restatement of the pass (tests/inter_resi_code_cases.py) reproduces the compiled reference's values
-(tests/golden/inter_resi_code.npz), every list the GPU tests use meets the conditions it is chosen by, the restatement keeps the contract, the struct
-mirror has the C compiler's layout, and the argument checks that come before any device work answer as the header says."""
+(tests/golden/inter_resi_code.npz), every list the GPU tests use meets the conditions it is chosen by, the restatement keeps the contract, and
+the argument checks that come before any device work answer as the header says (tests/test_abi.py checks the struct mirror, the constants, the prototype and
+the vvcgpu_sizeof ids)."""
 import ctypes as C
-import os
-import re
-import shlex
-import subprocess
 
 import numpy as np
 import pytest
 
 import inter_resi_code_cases as irc
-from vvcsoftware_vtm_amd import abi, capi
+import rd_pass_kit as kit
+from vvcsoftware_vtm_amd import capi
 
 
 @pytest.mark.parametrize("bd", [8, 10])
@@ -42,9 +40,7 @@ def test_restatement_reproduces_the_golden_file(bd):
 
 
 def test_golden_file_holds_data_only_and_stays_small():
-    assert os.path.getsize(irc.GOLDEN) <= 400 * 1024
-    g = np.load(irc.GOLDEN, allow_pickle=False)
-    assert all(g[k].dtype.kind in "iu" for k in g.files)
+    kit.check_golden_file(irc.GOLDEN)
 
 
 @pytest.mark.parametrize("bd", [8, 10])
@@ -106,42 +102,6 @@ def test_contract_of_the_restatement():
     assert (none["abs_sum"][9:] == irc.U32_MAX).all() and (none["zero_dist"][9:] == irc.U64_MAX).all() and np.array_equal(none["abs_sum"][:9], want["abs_sum"][:9])
 
 
-def test_struct_mirror_matches_the_header(tmp_path):
-    """sizeof / offsetof of vvcgpu_inter_resi_item by the C compiler == abi.INTER_RESI_ITEM, field by field; the constants; the library reports the same size"""
-    m = abi.INTER_RESI_ITEM
-    src = tmp_path / "layout.c"
-    src.write_text("#include <stddef.h>\n#include <stdio.h>\n#include \"vvcgpu.h\"\nint main(void)\n{\n"
-                   '  printf("%zu\\n", sizeof(vvcgpu_inter_resi_item));\n'
-                   + "".join('  printf("%%s %%zu %%zu\\n", "%s", offsetof(vvcgpu_inter_resi_item, %s), sizeof(((vvcgpu_inter_resi_item*)0)->%s));\n' % (f, f, f) for f in m.names)
-                   + '  printf("%d %d %d\\n", VVCGPU_INTER_RESI_SLOTS, VVCGPU_INTER_RESI_TS, VVCGPU_INTER_RESI_WRITE_REC);\n  return 0;\n}\n')
-    exe = tmp_path / "layout"
-    cc = shlex.split(os.environ.get("CC", "cc"))
-    r = subprocess.run(cc + ["-I", os.path.dirname(capi.HEADER), str(src), "-o", str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    lines = subprocess.check_output([str(exe)], text=True).splitlines()
-    assert int(lines[0]) == m.itemsize == 80 and m.itemsize % 16 == 0
-    for line, name in zip(lines[1:-1], m.names):
-        f, off, size = line.split()
-        assert (f, int(off), int(size)) == (name, m.fields[name][1], m.fields[name][0].itemsize), line
-    assert lines[-1].split() == [str(abi.INTER_RESI_SLOTS), str(abi.INTER_RESI_TS), str(abi.INTER_RESI_WRITE_REC)]
-
-
-def test_sizeof_ids():
-    lib = capi.lib()
-    assert lib.vvcgpu_sizeof(63) == 80
-    for i in (43, 49, 55, 61, 64, 99):
-        assert lib.vvcgpu_sizeof(i) == -1, i
-
-
-def test_header_constants_equal_the_mirror():
-    txt = open(capi.HEADER).read()
-    val = lambda name: int(re.search(r"#define\s+%s\s+\(?(-?\d+)\)?" % name, txt).group(1))
-    assert (val("VVCGPU_INTER_RESI_SLOTS"), val("VVCGPU_INTER_RESI_TS"), val("VVCGPU_INTER_RESI_WRITE_REC")) == (abi.INTER_RESI_SLOTS, abi.INTER_RESI_TS,
-                                                                                                                  abi.INTER_RESI_WRITE_REC) == (6, 9, 1)
-    assert abi.INTER_RESI_ITEM.fields["tr"][0].shape == (abi.INTER_RESI_SLOTS,)
-    assert "vvcgpu_inter_resi_code_batch" in capi.prototypes() and len(capi.prototypes()["vvcgpu_inter_resi_code_batch"][1]) == 17
-
-
 def call(**kw):
     """the entry with arguments that pass every check (dummy non-null pointers: no check dereferences one), changed by kw"""
     a = dict(org=C.c_void_p(64), pred=C.c_void_p(64), items=C.c_void_p(64), n=3, rd_list=None, resi=C.c_void_p(64), rec=None, level=C.c_void_p(64), flags=0, bd=10,
@@ -157,11 +117,4 @@ E_ARG_CASES = [dict(n=-1), dict(org=None), dict(pred=None), dict(items=None), di
 
 
 def test_argument_errors_come_before_any_device_work():
-    lib = capi.lib()
-    for kw in E_ARG_CASES:
-        assert call(**dict(kw)) == -1, kw
-        assert b"inter_resi_code_batch" in lib.vvcgpu_last_error(), kw
-    for bd in (7, 11, 12):
-        assert call(bd=bd) == -3, bd
-        assert b"inter_resi_code_batch" in lib.vvcgpu_last_error(), bd
-    assert call(n=0) == 0 and call(n=0, org=None, pred=None, items=None, resi=None, level=None, abs_sum=None) == 0
+    kit.check_argument_errors(call, E_ARG_CASES, b"inter_resi_code_batch", empty=({}, dict(org=None, pred=None, items=None, resi=None, level=None, abs_sum=None)))

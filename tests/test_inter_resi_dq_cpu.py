@@ -1,17 +1,14 @@
 """vvcgpu_inter_resi_code_dq_batch without a GPU: the restatement of the pass (tests/inter_resi_dq_cases.py) reproduces the compiled reference's values
-(tests/golden/inter_resi_dq.npz), the file covers what it is meant to cover, the struct mirror has the C compiler's layout, and the argument checks that come
-before any device work answer as the header says."""
+(tests/golden/inter_resi_dq.npz), the file covers what it is meant to cover, and the argument checks that come before any device work answer as the header says
+(tests/test_abi.py checks the struct mirror, the constant, the prototypes and the vvcgpu_sizeof id)."""
 import ctypes as C
-import os
-import re
-import shlex
-import subprocess
 
 import numpy as np
 import pytest
 
 import inter_resi_dq_cases as dqc
-from vvcsoftware_vtm_amd import abi, capi
+import rd_pass_kit as kit
+from vvcsoftware_vtm_amd import capi
 
 
 @pytest.mark.parametrize("bd", [8, 10])
@@ -41,9 +38,7 @@ def test_restatement_reproduces_the_golden_file(bd):
 
 
 def test_golden_file_holds_data_only_and_stays_small():
-    assert os.path.getsize(dqc.GOLDEN) <= 400 * 1024
-    g = np.load(dqc.GOLDEN, allow_pickle=False)
-    assert all(g[k].dtype.kind in "iu" for k in g.files)
+    kit.check_golden_file(dqc.GOLDEN)
 
 
 def test_contract_of_the_restatement():
@@ -59,39 +54,6 @@ def test_contract_of_the_restatement():
     assert served[0].tolist() == [True, False, True, False, False, False]
     assert served[1].tolist() == [True, False, True, False, False, False]      # DCT-II on the 64-point side, any type on the 16-point side
     assert (want["zero_dist"] != dqc.U64_MAX).tolist() == [True, True] + [False] * 6 + [True] and not served[2:].any()
-
-
-def test_struct_mirror_matches_the_header(tmp_path):
-    """sizeof / offsetof of vvcgpu_inter_resi_dq by the C compiler == abi.INTER_RESI_DQ, field by field; the constant; the library reports the same size"""
-    m = abi.INTER_RESI_DQ
-    src = tmp_path / "layout.c"
-    src.write_text("#include <stddef.h>\n#include <stdio.h>\n#include \"vvcgpu.h\"\nint main(void)\n{\n"
-                   '  printf("%zu\\n", sizeof(vvcgpu_inter_resi_dq));\n'
-                   + "".join('  printf("%%s %%zu %%zu\\n", "%s", offsetof(vvcgpu_inter_resi_dq, %s), sizeof(((vvcgpu_inter_resi_dq*)0)->%s));\n' % (f, f, f) for f in m.names)
-                   + '  printf("%d\\n", VVCGPU_INTER_RESI_Q_DEPQUANT);\n  return 0;\n}\n')
-    exe = tmp_path / "layout"
-    cc = shlex.split(os.environ.get("CC", "cc"))
-    r = subprocess.run(cc + ["-I", os.path.dirname(capi.HEADER), str(src), "-o", str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    lines = subprocess.check_output([str(exe)], text=True).splitlines()
-    assert int(lines[0]) == m.itemsize == 16
-    for line, name in zip(lines[1:-1], m.names):
-        f, off, size = line.split()
-        assert (f, int(off), int(size)) == (name, m.fields[name][1], m.fields[name][0].itemsize), line
-    assert int(lines[-1]) == abi.INTER_RESI_Q_DEPQUANT == 1
-    assert capi.lib().vvcgpu_sizeof(65) == 16
-
-
-def test_header_and_exports_agree():
-    txt = open(capi.HEADER).read()
-    assert int(re.search(r"#define\s+VVCGPU_INTER_RESI_Q_DEPQUANT\s+(\d+)", txt).group(1)) == abi.INTER_RESI_Q_DEPQUANT
-    protos = capi.prototypes()
-    assert len(protos["vvcgpu_inter_resi_code_dq_batch"][1]) == 24
-    assert protos["vvcgpu_inter_resi_code_dq_workspace_bytes"] == (C.c_size_t, (C.c_size_t, C.c_int))
-    lib = capi.lib()
-    # the workspace: coefficients, decisions and histories by the level extent (4 + 16 + 8 bytes each, the extent rounded up to 16), a record and a work-list entry per slot
-    f = lib.vvcgpu_inter_resi_code_dq_workspace_bytes
-    assert f(160, 0) - f(16, 0) == 144 * 28 and f(17, 3) == f(32, 3) and f(32, 4) - f(32, 3) == 6 * (40 + 4)
 
 
 WS = 1 << 20
@@ -116,13 +78,12 @@ E_ARG_CASES = [dict(n=-1), dict(org=None), dict(pred=None), dict(items=None), di
 
 def test_argument_errors_come_before_any_device_work():
     lib = capi.lib()
-    for kw in E_ARG_CASES:
-        assert call(**dict(kw)) == -1, kw
-        assert b"inter_resi_code_dq_batch" in lib.vvcgpu_last_error(), kw
-    assert call(ws_bytes=lib.vvcgpu_inter_resi_code_dq_workspace_bytes(1024, 3) - 1) == -1
+    kit.check_argument_errors(call, E_ARG_CASES, b"inter_resi_code_dq_batch",
+                              empty=({}, dict(org=None, pred=None, items=None, dq=None, rates=None, ws=None, ws_bytes=0, quantiser=7)))
+    # the workspace: coefficients, decisions and histories by the level extent (4 + 16 + 8 bytes each, the extent rounded up to 16), a record and a work-list entry per slot
+    f = lib.vvcgpu_inter_resi_code_dq_workspace_bytes
+    assert f(160, 0) - f(16, 0) == 144 * 28 and f(17, 3) == f(32, 3) and f(32, 4) - f(32, 3) == 6 * (40 + 4)
+    assert call(ws_bytes=f(1024, 3) - 1) == -1
     for q in (0, 2, -1):                                                     # a quantiser other than the served one
         assert call(quantiser=q) == -3, q
         assert b"quantiser" in lib.vvcgpu_last_error(), q
-    for bd in (7, 11, 12):
-        assert call(bd=bd) == -3, bd
-    assert call(n=0) == 0 and call(n=0, org=None, pred=None, items=None, dq=None, rates=None, ws=None, ws_bytes=0, quantiser=7) == 0

@@ -1,16 +1,15 @@
 """vvcgpu_intra_chroma_code_batch without a GPU: the restatement of the pass (tests/intra_chroma_code_cases.py) reproduces the compiled reference's values
 (tests/golden/intra_chroma_code.npz), the golden list meets the conditions its cases are chosen by, the restatement keeps the contract, the bound case is
-beyond a signed 32-bit sum, the struct mirror has the C compiler's layout, and the argument checks that come before any device work answer as the header says."""
+beyond a signed 32-bit sum, and the argument checks that come before any device work answer as the header says (tests/test_abi.py checks the struct
+mirror, the constants and the vvcgpu_sizeof id)."""
 import ctypes as C
-import os
-import shlex
-import subprocess
 
 import numpy as np
 import pytest
 
 import intra_chroma_code_cases as icc
-from vvcsoftware_vtm_amd import abi, capi
+import rd_pass_kit as kit
+from vvcsoftware_vtm_amd import capi
 
 
 @pytest.mark.parametrize("bd", [8, 10])
@@ -31,9 +30,7 @@ def test_restatement_reproduces_the_golden_file(bd):
 
 
 def test_golden_file_holds_data_only_and_stays_small():
-    assert os.path.getsize(icc.GOLDEN) <= 400 * 1024
-    g = np.load(icc.GOLDEN, allow_pickle=False)
-    assert all(g[k].dtype.kind in "iu" for k in g.files)
+    kit.check_golden_file(icc.GOLDEN)
 
 
 def test_contract_of_the_restatement():
@@ -62,27 +59,6 @@ def test_bound_case_exceeds_a_signed_32_bit_sum():
     assert (want["abs_sum"][0, [1, 2, 3, 5]] == icc.U32_MAX).all()
 
 
-def test_struct_mirror_matches_the_header(tmp_path):
-    """sizeof / offsetof of vvcgpu_intra_chroma_pu by the C compiler == abi.INTRA_CHROMA_PU, field by field; the library reports the same size"""
-    m = abi.INTRA_CHROMA_PU
-    src = tmp_path / "layout.c"
-    src.write_text("#include <stddef.h>\n#include <stdio.h>\n#include \"vvcgpu.h\"\nint main(void)\n{\n"
-                   '  printf("%zu\\n", sizeof(vvcgpu_intra_chroma_pu));\n'
-                   + "".join('  printf("%%s %%zu %%zu\\n", "%s", offsetof(vvcgpu_intra_chroma_pu, %s), sizeof(((vvcgpu_intra_chroma_pu*)0)->%s));\n' % (f, f, f) for f in m.names)
-                   + '  printf("%d %d\\n", VVCGPU_INTRA_CHROMA_LM, VVCGPU_INTRA_CHROMA_WRITE_PRED);\n  return 0;\n}\n')
-    exe = tmp_path / "layout"
-    cc = shlex.split(os.environ.get("CC", "cc"))
-    r = subprocess.run(cc + ["-I", os.path.dirname(capi.HEADER), str(src), "-o", str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    lines = subprocess.check_output([str(exe)], text=True).splitlines()
-    assert int(lines[0]) == m.itemsize == 96 and m.itemsize % 16 == 0
-    for line, name in zip(lines[1:-1], m.names):
-        f, off, size = line.split()
-        assert (f, int(off), int(size)) == (name, m.fields[name][1], m.fields[name][0].itemsize), line
-    assert lines[-1].split() == [str(abi.INTRA_CHROMA_LM), str(abi.INTRA_CHROMA_WRITE_PRED)]
-    assert capi.lib().vvcgpu_sizeof(62) == 96
-
-
 def call(**kw):
     """the entry with arguments that pass every check (dummy non-null pointers: no check dereferences one), changed by kw"""
     runs = np.array(kw.pop("runs", [[8, 8, 3]]), np.int32)
@@ -101,10 +77,4 @@ E_ARG_CASES = [dict(n=-1), dict(org=None), dict(pus=None), dict(cand_rec=None), 
 
 
 def test_argument_errors_come_before_any_device_work():
-    lib = capi.lib()
-    for kw in E_ARG_CASES:
-        assert call(**dict(kw)) == -1, kw
-        assert b"intra_chroma_code_batch" in lib.vvcgpu_last_error(), kw
-    for bd in (7, 11, 12):
-        assert call(bd=bd) == -3, bd
-    assert call(n=0) == 0 and call(n=0, org=None, pus=None, runs_ptr=None) == 0
+    kit.check_argument_errors(call, E_ARG_CASES, b"intra_chroma_code_batch", empty=({}, dict(org=None, pus=None, runs_ptr=None)))

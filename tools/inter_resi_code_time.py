@@ -11,7 +11,7 @@ original moved by (1, -2) plus noise, QP 32, sign hiding on.
       uploaded outside the timed part;
   (b) vvcgpu_inter_resi_code_batch with WRITE_REC off: one launch.
 The results of (a) and (b) are compared before anything is timed.  Times: device events around a whole run on the stream, 3 warm-up runs, then the median
-and the spread of 9 runs, (a) and (b) alternating in one process."""
+and the spread of 9 runs, (a) and (b) alternating in one process.  The two lists and the row come from tests/rd_pass_kit.py."""
 import os
 import sys
 
@@ -22,8 +22,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import inter_resi_code_chain as chain  # noqa: E402
-import pu_search_kit as kit  # noqa: E402
-from vvcsoftware_vtm_amd import abi, shape_mix  # noqa: E402
+import pu_search_kit  # noqa: E402
+import rd_pass_kit as kit  # noqa: E402
+from vvcsoftware_vtm_amd import abi  # noqa: E402
 
 W, H, BD = 3840, 2160, 10
 QP = 32 + 12
@@ -56,41 +57,50 @@ def build(w, h, px, py, emt):
     return it, int((slots * area).sum())
 
 
-def main():
-    luma = kit.texture(rng, H, W, BD, 0.0)
-    planes = [luma, np.ascontiguousarray(luma[0::2, 0::2]), np.ascontiguousarray(luma[1::2, 1::2])]
-    org = np.concatenate([p.reshape(-1) for p in planes])
-    pred = np.concatenate([np.clip(np.roll(p, (1, -2), axis=(0, 1)).astype(np.int32) + rng.integers(-4, 5, p.shape), 0, 1023).astype(np.int16).reshape(-1) for p in planes])
-    hist, _ = shape_mix.load_trace()
-    sides = (4, 8, 16, 32, 64)
-    sig = shape_mix.signatures(hist, "pelop", lambda w, h, a, b, c: a == 0 and w in sides and h in sides)
-    mix = np.array([(int(w), int(h)) for w, h in sig[rng.choice(len(sig), 8000, p=sig[:, 5] / sig[:, 5].sum()), :2]])
-    bx, by = np.meshgrid(np.arange(1, W // 16 - 2), np.arange(1, H // 16 - 2))
-    g = np.stack([bx.ravel() * 16, by.ravel() * 16], 1)
-    cus = [("4K 16x16", np.full(len(g), 16), np.full(len(g), 16), g[:, 0], g[:, 1]),
-           ("trace mix", mix[:, 0], mix[:, 1], rng.integers(1, (W - 160) // 4, len(mix)) * 4, rng.integers(1, (H - 160) // 4, len(mix)) * 4)]
-    print("list             items   slots   chain ms (min..max)   entry ms (min..max)   chain / entry   all-zero slots")
+def planes(rng):
+    """-> (org, pred): the three planes of the picture one after another; the prediction is the original moved by (1, -2) plus noise"""
+    luma = pu_search_kit.texture(rng, H, W, BD, 0.0)
+    yuv = [luma, np.ascontiguousarray(luma[0::2, 0::2]), np.ascontiguousarray(luma[1::2, 1::2])]
+    org = np.concatenate([p.reshape(-1) for p in yuv])
+    pred = np.concatenate([np.clip(np.roll(p, (1, -2), axis=(0, 1)).astype(np.int32) + rng.integers(-4, 5, p.shape), 0, 1023).astype(np.int16).reshape(-1) for p in yuv])
+    return org, pred
+
+
+def time_lists(cus, device_of, chain_of, profile=False):
+    """every list without and with the EMT slots: the chain and the entry compared, then timed, one row each (profile: five runs of the entry instead)"""
+    if not profile:
+        print("list             items   slots   chain ms (min..max)   entry ms (min..max)   chain / entry   all-zero slots")
     for emt in (False, True):
         for name, w, h, px, py in cus:
             it, size = build(w, h, px, py, emt)
-            D = chain.Device(BD, org, pred, it, size, size)
-            C = chain.Chain(D)
-            ra, ca, la = D.fresh()
+            D = device_of(it, size)
             rb, _, lb = D.fresh()
-
-            def chained():
-                return C.run(ra, ca, la)
 
             def entry():
                 return D.run_entry(rb, None, lb, 0)
 
-            oc, oe = chained(), entry()
-            torch.cuda.synchronize()
-            assert C.same(oc, oe) and torch.equal(ra, rb) and torch.equal(la, lb), name
-            ta, tb = kit.times_of_alternating((chained, entry), WARMUP - 1, RUNS)   # the comparison above was the first warm-up run
-            ma, mb = float(np.median(ta)), float(np.median(tb))
-            print("%-14s %7d %7d   %8.3f (%.3f..%.3f)   %8.3f (%.3f..%.3f)   %13.2f   %d" %
-                  (name + (" +EMT" if emt else ""), len(it), C.m, ma, min(ta), max(ta), mb, min(tb), max(tb), ma / mb, int((oc[0] == 0).sum())))
+            if profile:
+                for _ in range(5):
+                    entry()
+                torch.cuda.synchronize()
+                continue
+            C = chain_of(D)
+            ra, ca, la = D.fresh()
+
+            def chained():
+                return C.run(ra, ca, la)
+
+            def check(oc, oe):
+                assert C.same(oc, oe) and torch.equal(ra, rb) and torch.equal(la, lb), name
+                return int((oc[0] == 0).sum())
+
+            kit.time_row("%-14s %7d %7d" % (name + (" +EMT" if emt else ""), len(it), C.m), chained, entry, check, WARMUP, RUNS)
+
+
+def main():
+    org, pred = planes(rng)
+    cus = kit.timing_lists(rng, W, H, (4, 8, 16, 32, 64))
+    time_lists(cus, lambda it, size: chain.Device(BD, org, pred, it, size, size), chain.Chain)
 
 
 if __name__ == "__main__":

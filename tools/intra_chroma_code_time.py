@@ -11,7 +11,7 @@ QP 32, sign hiding on, every neighbour available.
       descriptors uploaded and the neighbours repacked into nb_base outside the timed part;
   (b) vvcgpu_intra_chroma_code_batch: references gathered inside, not written; no prediction written.
 The results of (a) and (b) are compared before anything is timed.  Times: device events around a whole run on the stream, 3 warm-up runs, then the median
-and the spread of 9 runs, (a) and (b) alternating in one process."""
+and the spread of 9 runs, (a) and (b) alternating in one process.  The two lists and the row come from tests/rd_pass_kit.py."""
 import os
 import sys
 
@@ -22,15 +22,16 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import intra_chroma_code_chain as chain  # noqa: E402
-import pu_search_kit as kit  # noqa: E402
-from vvcsoftware_vtm_amd import abi, ops, shape_mix  # noqa: E402
+import pu_search_kit  # noqa: E402
+import rd_pass_kit as kit  # noqa: E402
+from rd_pass_kit import dev  # noqa: E402
+from vvcsoftware_vtm_amd import abi, ops  # noqa: E402
 
 W, H, BD = 3840, 2160, 10
 CW, CH = W // 2, H // 2
 QP = 32 + 12
 WARMUP, RUNS = 3, 9
 rng = np.random.default_rng(47)
-dev = chain.dev
 
 
 def build(w, h, px, py):
@@ -66,17 +67,11 @@ def build(w, h, px, py):
 
 
 def main():
-    luma = kit.texture(rng, H, W, BD, 0.0)
+    luma = pu_search_kit.texture(rng, H, W, BD, 0.0)
     ds = luma[::2, ::2].astype(np.float64)
     rec = np.stack([np.clip(np.rint(205 + 0.55 * ds + rng.normal(0, 7, ds.shape)), 0, 1023), np.clip(np.rint(818 - 0.45 * ds + rng.normal(0, 7, ds.shape)), 0, 1023)]).astype(np.int16)
     org = np.clip(np.roll(rec, (1, -1), axis=(1, 2)).astype(np.int32) + rng.integers(-12, 13, rec.shape), 0, 1023).astype(np.int16)
-    hist, _ = shape_mix.load_trace()
-    sig = shape_mix.signatures(hist, "pelop", lambda w, h, a, b, c: a == 0 and w in (8, 16, 32, 64) and h in (8, 16, 32, 64))
-    mix = np.array([(int(w) // 2, int(h) // 2) for w, h in sig[rng.choice(len(sig), 8000, p=sig[:, 5] / sig[:, 5].sum()), :2]])
-    bx, by = np.meshgrid(np.arange(1, W // 16 - 2), np.arange(1, H // 16 - 2))
-    g = np.stack([bx.ravel() * 8, by.ravel() * 8], 1)
-    lists = [("4K 8x8", np.full(len(g), 8), np.full(len(g), 8), g[:, 0], g[:, 1]),
-             ("trace mix", mix[:, 0], mix[:, 1], rng.integers(1, (CW - 160) // 2, len(mix)) * 2, rng.integers(1, (CH - 160) // 2, len(mix)) * 2)]
+    lists = kit.timing_lists(rng, CW, CH, (8, 16, 32, 64), chroma=True)
     drec, dorg, dluma, avail = dev(rec.reshape(-1)), dev(org.reshape(-1)), dev(luma.reshape(-1)), dev(np.ones(192, np.uint8))
     clp = (0, 1023)
     print("list        PUs    items   chain ms (min..max)   entry ms (min..max)   chain / entry   all-zero items")
@@ -95,14 +90,13 @@ def main():
         def entry():
             return ops.intra_chroma_code_batch(dorg, dpus, n, runs, rec_b, lev_b, None, (drec, avail, dfill), dluma, None, 0, BD, clp)
 
-        (sa, da), (sb, db) = ch.run(), entry()
-        torch.cuda.synchronize()
-        assert torch.equal(rec_a, rec_b) and torch.equal(lev_a, lev_b), name
-        assert torch.equal(sa, sb.reshape(-1)) and torch.equal(da, db.reshape(-1)), name     # six slots in use: the items are the entry's, in its order
-        ta, tb = kit.times_of_alternating((ch.run, entry), WARMUP - 1, RUNS)    # the comparison above was the first warm-up run
-        ma, mb = float(np.median(ta)), float(np.median(tb))
-        print("%-10s %6d %7d   %8.3f (%.3f..%.3f)   %8.3f (%.3f..%.3f)   %13.2f   %d" %
-              (name, n, 12 * n, ma, min(ta), max(ta), mb, min(tb), max(tb), ma / mb, int((sb == 0).sum())))
+        def check(oc, oe):
+            (sa, da), (sb, db) = oc, oe
+            assert torch.equal(rec_a, rec_b) and torch.equal(lev_a, lev_b), name
+            assert torch.equal(sa, sb.reshape(-1)) and torch.equal(da, db.reshape(-1)), name     # six slots in use: the items are the entry's, in its order
+            return int((sb == 0).sum())
+
+        kit.time_row("%-10s %6d %7d" % (name, n, 12 * n), ch.run, entry, check, WARMUP, RUNS)
 
 
 if __name__ == "__main__":

@@ -22,7 +22,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import intra_mode_cand_cases as imc  # noqa: E402
 import intra_mode_cand_chain as chain  # noqa: E402
 import pu_search_kit as kit  # noqa: E402
-from vvcsoftware_vtm_amd import shape_mix  # noqa: E402
+import rd_pass_kit  # noqa: E402
 
 W, H, BD = 3840, 2160, 10
 SQRT_LAMBDA = 27.375
@@ -55,13 +55,7 @@ def build(rec, org, w, h, px, py):
 def main():
     rec = kit.texture(rng, H, W, BD, 0.0)
     org = np.clip(np.roll(rec, (1, -2), axis=(0, 1)).astype(np.int32) + rng.integers(-4, 5, (H, W)), 0, 1023).astype(np.int16)
-    hist, _ = shape_mix.load_trace()
-    sig = shape_mix.signatures(hist, "pelop", lambda w, h, a, b, c: a == 0 and w in imc.SIDES and h in imc.SIDES)
-    mix = np.array([(int(w), int(h)) for w, h in sig[rng.choice(len(sig), 8000, p=sig[:, 5] / sig[:, 5].sum()), :2]])
-    bx, by = np.meshgrid(np.arange(1, W // 16 - 2), np.arange(1, H // 16 - 2))
-    g = np.stack([bx.ravel() * 16, by.ravel() * 16], 1)
-    lists = [("4K 16x16", np.full(len(g), 16), np.full(len(g), 16), g[:, 0], g[:, 1]),
-             ("trace mix", mix[:, 0], mix[:, 1], rng.integers(1, (W - 160) // 4, len(mix)) * 4, rng.integers(1, (H - 160) // 4, len(mix)) * 4)]
+    lists = rd_pass_kit.timing_lists(rng, W, H, imc.SIDES)                   # (the row has columns of its own: the launches alone, the final list sizes)
     print("list          PUs   chain ms (min..max)   its launches ms   entry ms (min..max)   its launch ms   chain / entry   launches / launch   final sizes 0 1 2 3+")
     for name, w, h, px, py in lists:
         D = chain.Device(build(rec, org, w, h, px, py))

@@ -9,7 +9,7 @@ Random modes with the luma filter rule's decision, DCT-II, QP 32, sign hiding on
       are grouped by shape), vvcgpu_dist_batch kind 2 -- three launches back to back, no host work between, descriptors uploaded outside the timed part;
   (b) vvcgpu_intra_tu_code_batch: one launch, the prediction never written.
 The results of (a) and (b) are compared before anything is timed.  Times: device events around a whole run on the stream, 3 warm-up runs, then the median
-and the spread of 9 runs, (a) and (b) alternating in one process."""
+and the spread of 9 runs, (a) and (b) alternating in one process.  The two lists and the row come from tests/rd_pass_kit.py."""
 import os
 import sys
 
@@ -20,17 +20,15 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import intra_mode_cand_cases as imc  # noqa: E402
-import pu_search_kit as kit  # noqa: E402
-from vvcsoftware_vtm_amd import abi, ops, shape_mix  # noqa: E402
+import pu_search_kit  # noqa: E402
+import rd_pass_kit as kit  # noqa: E402
+from rd_pass_kit import dev  # noqa: E402
+from vvcsoftware_vtm_amd import abi, ops  # noqa: E402
 
 W, H, BD = 3840, 2160, 10
 CANDS, QP = 3, 32 + 12
 WARMUP, RUNS = 3, 9
 rng = np.random.default_rng(43)
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def build(w, h, px, py):
@@ -67,15 +65,9 @@ def build(w, h, px, py):
 
 
 def main():
-    rec = kit.texture(rng, H, W, BD, 0.0)
+    rec = pu_search_kit.texture(rng, H, W, BD, 0.0)
     org = np.clip(np.roll(rec, (1, -2), axis=(0, 1)).astype(np.int32) + rng.integers(-4, 5, (H, W)), 0, 1023).astype(np.int16)
-    hist, _ = shape_mix.load_trace()
-    sig = shape_mix.signatures(hist, "pelop", lambda w, h, a, b, c: a == 0 and w in imc.SIDES and h in imc.SIDES)
-    mix = np.array([(int(w), int(h)) for w, h in sig[rng.choice(len(sig), 8000, p=sig[:, 5] / sig[:, 5].sum()), :2]])
-    bx, by = np.meshgrid(np.arange(1, W // 16 - 2), np.arange(1, H // 16 - 2))
-    g = np.stack([bx.ravel() * 16, by.ravel() * 16], 1)
-    lists = [("4K 16x16", np.full(len(g), 16), np.full(len(g), 16), g[:, 0], g[:, 1]),
-             ("trace mix", mix[:, 0], mix[:, 1], rng.integers(1, (W - 160) // 4, len(mix)) * 4, rng.integers(1, (H - 160) // 4, len(mix)) * 4)]
+    lists = kit.timing_lists(rng, W, H, imc.SIDES)
     drec, dorg, avail = dev(rec.reshape(-1)), dev(org.reshape(-1)), dev(np.ones(192, np.uint8))
     clp = (0, 1023)
     print("list        items   chain ms (min..max)   entry ms (min..max)   chain / entry   all-zero items")
@@ -97,16 +89,15 @@ def main():
         def entry():
             return ops.intra_tu_code_batch(refs, dd_, dorg, None, rec_b, lev_b, dt, m, None, 0, BD, clp)
 
-        (sa, da), (sb, nb, db, mb) = chained(), entry()
-        torch.cuda.synchronize()
-        assert torch.equal(rec_a, rec_b) and torch.equal(lev_a, lev_b) and torch.equal(sa, sb) and torch.equal(da, db), name
-        nz = torch.cat([torch.zeros(1, dtype=torch.int64, device="cuda"), (lev_b != 0).to(torch.int64).cumsum(0)])     # non-zero levels in front of each position
-        ends = dev(t["level_off"] + t["w"].astype(np.int64) * t["h"])
-        assert torch.equal(mb, dev(d["mode"].astype(np.int32))) and torch.equal(nb.to(torch.int64), nz[ends] - nz[dev(t["level_off"])]), name
-        ta, tb = kit.times_of_alternating((chained, entry), WARMUP - 1, RUNS)   # the comparison above was the first warm-up run
-        ma, mb_ = float(np.median(ta)), float(np.median(tb))
-        print("%-10s %6d   %8.3f (%.3f..%.3f)   %8.3f (%.3f..%.3f)   %13.2f   %d" %
-              (name, m, ma, min(ta), max(ta), mb_, min(tb), max(tb), ma / mb_, int((nb == 0).sum())))
+        def check(oc, oe):
+            (sa, da), (sb, nb, db, mb) = oc, oe
+            assert torch.equal(rec_a, rec_b) and torch.equal(lev_a, lev_b) and torch.equal(sa, sb) and torch.equal(da, db), name
+            nz = torch.cat([torch.zeros(1, dtype=torch.int64, device="cuda"), (lev_b != 0).to(torch.int64).cumsum(0)])     # non-zero levels in front of each position
+            ends = dev(t["level_off"] + t["w"].astype(np.int64) * t["h"])
+            assert torch.equal(mb, dev(d["mode"].astype(np.int32))) and torch.equal(nb.to(torch.int64), nz[ends] - nz[dev(t["level_off"])]), name
+            return int((nb == 0).sum())
+
+        kit.time_row("%-10s %6d" % (name, m), chained, entry, check, WARMUP, RUNS)
 
 
 if __name__ == "__main__":

@@ -24,7 +24,8 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import merge_cand_cases as mcc  # noqa: E402
 import merge_cand_chain as chain  # noqa: E402
 import pu_search_kit as kit  # noqa: E402
-from vvcsoftware_vtm_amd import abi, shape_mix  # noqa: E402
+import rd_pass_kit  # noqa: E402
+from vvcsoftware_vtm_amd import abi  # noqa: E402
 
 W, H, BD = 3840, 2160, 10
 SQRT_LAMBDA, MAX_NUM, N_CAND, ATMVP_AT, SUB = 27.375, 7, 7, 2, 4
@@ -121,9 +122,7 @@ def main():
     l0, l1 = kit.texture(rng, H, W, BD, 0.0), kit.texture(rng, H, W, BD, 1.5)
     org = np.clip(np.roll(l0, (2, -3), axis=(0, 1)).astype(np.int32) + rng.integers(-5, 6, (H, W)), 0, 1023).astype(np.int16)
     fr = mcc.derived_frame(l0, l1, org, BD)
-    hist, _ = shape_mix.load_trace()
-    sig = shape_mix.signatures(hist, "pelop", lambda w, h, a, b, c: a == 0 and w in mcc.SIDES and h in mcc.SIDES)
-    mix = np.array([(int(w), int(h)) for w, h in sig[rng.choice(len(sig), 8000, p=sig[:, 5] / sig[:, 5].sum()), :2]])
+    mix = rd_pass_kit.trace_shapes(rng, mcc.SIDES)                           # (the whole picture's grid and positions by the PU's own size: this tool's own)
     g = np.array([(x, y) for y in range(0, H, 16) for x in range(0, W, 16)])
     lists = [("4K 16x16", np.full(len(g), 16), np.full(len(g), 16), g[:, 0], g[:, 1]),
              ("trace mix", mix[:, 0], mix[:, 1], rng.integers(0, (W - mix[:, 0]) // 4 + 1) * 4, rng.integers(0, (H - mix[:, 1]) // 4 + 1) * 4)]
