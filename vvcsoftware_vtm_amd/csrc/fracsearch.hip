@@ -431,14 +431,21 @@ constexpr int FM_FB_MAX = 32;                                // PUs a wave of fr
 //           as a real number.  v_cvt_pkrtz_f16_f32 truncates: in [1024, 2048) f16 has unit spacing, so that IS the floor; values outside land
 //           outside and the packed clamp to [1024 + clpMin, 1024 + clpMax] takes them.  All partial sums stay below 2^24 in units of 2^-shift2
 //           whatever the order (largest positive part 88 x 128 x 1279 + 88 x 1151 = 14.5 M on a start value of about -8 M): exact in f32.
+//           The split stays at bit 7 at every bit depth.  Limbs at bit 8 would be byte picks of u's float (top byte 0x4C at bit depth 10, 0x4B at
+//           8 and 9: f16 values (1024 + b) / 64 and (1792 + b) / 128, one v_perm_b32 per register instead of mask, shift and OR), but the high
+//           limb then weighs 256 and keeps its bias: the positive taps alone give 88 x 256 x 1024 = 23.1 M (0x4B: 88 x 256 x 1792 = 40.4 M), beyond
+//           2^24 = 16.8 M before any sample is added and at every bit depth (u spans 2054 .. 30698 at bit depth 10, 2072 .. 30632 at 8), and the low
+//           limb's products are arbitrary integers of the same unit -- a partial sum of that size is no longer exact.  The bound needs 88 w B < 2^24:
+//           (w the high limb's weight, B its bias) w B <= 190 650, which w = 128, B = 1024 meets and no byte-aligned split does (a byte in an f16 mantissa has B >= 1024).
 //   residual d = (1024 + org) - (1024 + pred), |d| <= 1023 (PUs with other originals -- bi-predictive 2 org - otherPred -- take the vector form)
 //   Hadamard (RdCost.cpp:2205-2853, xCalcHADs8x8): over y one butterfly before the product (lane ^ 8, packed f16, |.| <= 2046 still exact),
 //           over x as a product with blockdiag(H8, H8) (the residual as A operand: y moves into registers), the remaining two y stages in
 //           registers on f32, the last of them as |a + b| + |a - b| = 2 max(|a|, |b|).
-//   tile sums: p = the lane's part of sum |coefficient| / 2; R1[x'][slot] += p x selector (slot = candidate + 8 (tile row)), one product per
-//           candidate into ONE accumulator for the eight candidates of a stage; at the end of the stage four registers are added, a second
-//           product adds the lane groups of a tile column, SATD tile = (P + 1) >> 1 (= (2 P + 2) >> 2), and a row_ror:8 adds the tile rows:
-//           lane i then holds the distortion of candidate i, which is where the arg-min wants it.
+//   tile sums: p = the lane's part of sum |coefficient| / 2 (below 2^16), as two byte limbs picked out of p + 2^23 (fm_limbs);
+//           R1[x'][slot] += limbs x selector (slot = candidate + 8 (tile row)), one f16 product per FOUR candidates into ONE accumulator for the
+//           eight candidates of a stage; at the end of the stage four registers and the lane groups of a tile column are added, the limbs' biases
+//           taken out, SATD tile = (P + 1) >> 1 (= (2 P + 2) >> 2), and a row_ror:8 adds the tile rows: lane i then holds the distortion of
+//           candidate i, which is where the arg-min wants it.
 constexpr int FM_MAT = 512;                                  // halves per lane-indexed operand image (64 lanes x 8)
 constexpr int FM_NA = 7, FM_NB = 14;                         // TA: (fx, ix) in {(0,0), (1,-1), (1,0), (2,-1), (2,0), (3,-1), (3,0)}; TB: the same seven (fy, iy) x two row chunks
 constexpr int FM_TAB_HALVES = (FM_NA + FM_NB) * FM_MAT;
@@ -502,7 +509,7 @@ struct FmPu                                                 // per-PU operands t
 struct FmK                                                  // wave constants (lane-varying ones in vector registers: v_and_or_b32 takes them as they are)
 {
   float magicA;
-  unsigned sp0;                                             // selector of slot 0 as the f16 pair (1, 2048): the weights of a sum's two limbs
+  unsigned sp0;                                             // selector of slot 0 as the f16 pair (128, 32768): the weights of a sum's two limbs (fm_limbs)
   fh2 pmin, pmax, sg;
   h4 hx;
   unsigned m7[2], m8[2], orX[2], orR[2];                    // limb masks / f16 exponent patterns per row chunk: chunk 1 has no rows 24..31, its lanes g >= 2 carry constants
@@ -574,23 +581,29 @@ __device__ __forceinline__ void fm_cands(const _Float16* __restrict__ tabS, cons
   }
 }
 
-// The lane's part P (an integer below 2^17 in f32) as two f16 limbs (P mod 2048, P div 2048) in one register
+// The lane's part P as two f16 limbs in one register, by two instructions.  P is an integer below 2^16: |d| <= 1023, one butterfly over y (2046), the
+// H8 product over x (8 x 2046 = 16368), sm / df (32736), and P = max + max <= 65472.  P + 2^23 is exact and has the bit pattern 0x4B000000 | P, so the
+// bytes b0 = P & 255 and b1 = P >> 8 lie in the mantissa and the top byte is the constant 0x4B.  As the high byte of an f16, 0x4B makes 0x4B00 | b the
+// value (1792 + b) / 128: one byte pick builds ((1792 + b0) / 128, (1792 + b1) / 128).  The selector carries the weights (128, 32768), so a lane's two
+// products are (1792 + b0) + 256 (1792 + b1) = P + FM_LIMB_BIAS, integers below 2^20 whose sums stay exact in f32 in any order; fm_finalize takes the
+// biases out again.
+constexpr float FM_LIMB_BIAS = 1792.f * 257.f;               // 460544
 __device__ __forceinline__ unsigned fm_limbs(float P)
 {
-  const float hi = floorf(P * (1.f / 2048.f));
-  const float lo = __builtin_fmaf(hi, -2048.f, P);
-  return __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(lo, hi));
+  const unsigned x = __builtin_bit_cast(unsigned, P + 8388608.f);
+  return __builtin_amdgcn_perm(x, x, 0x03010300u);           // (byte 3, byte 1), (byte 3, byte 0)
 }
-// R1[x'][slot] += sum over the lane groups of up to three candidates' parts, slot = T + 8 (tile row): ONE f16 product (the f32-input MFMA this
-// replaces holds the SIMD's vector pipe for its whole 32 cycles -- measured: 9 us of 72 per picture for 20 of them per PU)
-template <int T0, int T1, int T2>
-__device__ __forceinline__ f4 fm_acc(f4 R, float P0, float P1, float P2, const FmK& K)
+// R1[x'][slot] += sum over the lane groups of up to four candidates' parts (as fm_limbs registers), slot = T + 8 (tile row): ONE f16 product (the
+// f32-input MFMA this replaces holds the SIMD's vector pipe for its whole 32 cycles -- measured: 9 us of 72 per picture for 20 of them per PU).  Four
+// candidates fill the product's 32 inner positions: no register of either operand has to be cleared, and a stage needs two or three products
+template <int T0, int T1, int T2, int T3>
+__device__ __forceinline__ f4 fm_acc(f4 R, unsigned L0, unsigned L1, unsigned L2, unsigned L3, const FmK& K)
 {
   uint4 a, b;
-  a.x = fm_limbs(P0); b.x = fm_sel<T0 & 7>(K.sp0);
-  a.y = T1 >= 0 ? fm_limbs(P1) : 0u; b.y = T1 >= 0 ? fm_sel<T1 & 7>(K.sp0) : 0u;
-  a.z = T2 >= 0 ? fm_limbs(P2) : 0u; b.z = T2 >= 0 ? fm_sel<T2 & 7>(K.sp0) : 0u;
-  a.w = 0u; b.w = 0u;
+  a.x = L0; b.x = fm_sel<T0 & 7>(K.sp0);
+  a.y = T1 >= 0 ? L1 : 0u; b.y = T1 >= 0 ? fm_sel<T1 & 7>(K.sp0) : 0u;
+  a.z = T2 >= 0 ? L2 : 0u; b.z = T2 >= 0 ? fm_sel<T2 & 7>(K.sp0) : 0u;
+  a.w = T3 >= 0 ? L3 : 0u; b.w = T3 >= 0 ? fm_sel<T3 & 7>(K.sp0) : 0u;
   return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, a), __builtin_bit_cast(h8, b), R, 0, 0, 0);
 }
 
@@ -598,24 +611,26 @@ __device__ __forceinline__ f4 fm_acc(f4 R, float P0, float P1, float P2, const F
 // the lane groups of a tile column meet through the LDS crossbar (no memory: ds_swizzle / ds_bpermute), SATD tile = (P + 1) >> 1, tile rows by row_ror:8
 __device__ __forceinline__ float fm_finalize(const f4& R1, int lane)
 {
-  const float rr = (R1[0] + R1[1]) + (R1[2] + R1[3]);
+  const float rr = ((R1[0] + R1[1]) + R1[2]) + R1[3];       // (integers below 2^24: any order gives the same; a chain is not turned into packed adds that need copies)
   const float col = rr + __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, rr), 0x401F));       // lane ^ 16: the other half of the tile column
-  const float sat = floorf((col + 1.f) * 0.5f);
+  // col holds 16 parts of its slot (4 registers x 2 lanes x the 2 lane groups each product adds), each with FM_LIMB_BIAS: at most 16 x (460544 + 65472)
+  // = 8416256 < 2^24, exact; a slot no candidate was written to holds 0 and leaves a negative number here, in a lane nobody reads
+  const float sat = floorf((col + (1.f - 16.f * FM_LIMB_BIAS)) * 0.5f);
   float s = sat + __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute((lane ^ 32) << 2, __builtin_bit_cast(int, sat)));  // lane ^ 32: the other tile column
   s += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, s), DPP_ROR8, 0xF, 0xF, true));           // the other tile row
   return s;
 }
 
-// exp-Golomb length of xGetExpGolombNumberOfBits (RdCost.h:172-199) without its loop: every pass of `while (t > 128) { len += 14; t >>= 7; }` is one of
-// four monotone tests
-__device__ __forceinline__ unsigned fm_eg_bits(int v)
+// exp-Golomb length of xGetExpGolombNumberOfBits (RdCost.h:172-199) without its loop.  k passes of `while (t > 128) { len += 14; t >>= 7; }` leave
+// len = 1 + 14 k and t >> 7 k, which is at least 1 (the pass before saw more than 128), so floorLog2(t >> 7 k) = floorLog2(t) - 7 k and the result
+// 1 + 14 k + 2 (floorLog2(t) - 7 k) = 1 + 2 floorLog2(t) = 63 - 2 clz(t) does not depend on k.  fm_eg_clz returns clz(t); t >= 1 for every v.
+__device__ __forceinline__ unsigned fm_eg_clz(int v)
 {
-  const unsigned t = (v <= 0) ? ((unsigned)(-v) << 1) + 1 : (unsigned)(v << 1);
-  const unsigned k = (unsigned)(t > 128u) + (unsigned)((t >> 7) > 128u) + (unsigned)((t >> 14) > 128u) + (unsigned)((t >> 21) > 128u);
-  const unsigned tf = t >> (7 * k);
-  return 1 + 14 * k + ((31 - __clz((int)tf)) << 1);
+  const unsigned w = (unsigned)v << 1;
+  const unsigned t = (v <= 0) ? 1u - w : w;                  // (-v << 1) + 1 : v << 1, modulo 2^32 as there
+  return (unsigned)__builtin_clz(t);
 }
-constexpr int FM_COST_N = 160;                               // two lengths of at most 71 bits each
+constexpr int FM_COST_N = 160;                               // two lengths of at most 63 bits each: 126 is the largest count
 // the candidate offsets of s_acMvRefineH / s_acMvRefineQ as 2-bit fields (offset + 1), index i at bits 2 i
 constexpr unsigned FM_HX = 1u | 1u << 2 | 1u << 4 | 0u << 6 | 2u << 8 | 0u << 10 | 2u << 12 | 0u << 14 | 2u << 16;
 constexpr unsigned FM_HY = 1u | 0u << 2 | 2u << 4 | 1u << 6 | 1u << 8 | 0u << 10 | 0u << 12 | 2u << 14 | 2u << 16;
@@ -629,11 +644,11 @@ __device__ __forceinline__ void fm_best(unsigned dl, bool quarter, const unsigne
 {
   const int li = lane < 9 ? lane : 0;
   const int dx = (int)(((quarter ? FM_QX : FM_HX) >> (2 * li)) & 3u) - 1, dy = (int)(((quarter ? FM_QY : FM_HY) >> (2 * li)) & 3u) - 1;
-  const unsigned bits = fm_eg_bits(((baseX + dx) << scale) - predH) + fm_eg_bits(((baseY + dy) << scale) - predV);
+  const unsigned bits = 126u - ((fm_eg_clz(((baseX + dx) << scale) - predH) + fm_eg_clz(((baseY + dy) << scale) - predV)) << 1);   // two lengths 63 - 2 clz
   const unsigned long long mc = bits < (unsigned)FM_COST_N ? costS[bits] : (unsigned long long)(lambda * (double)bits);
-  unsigned long long c = lane < 9 ? (unsigned long long)dl + mc : ~0ull;
+  unsigned long long c = lane < 9 ? (unsigned long long)dl + mc : 0xFFFFFFFFull;   // lanes 9..63: a zero high word, so that the vote needs no lane mask
   int bi;
-  if (__ballot(lane < 9 && (c >> 32) != 0) == 0ull)
+  if (__builtin_amdgcn_ballot_w64((unsigned)(c >> 32) != 0u) == 0ull)
   {
     unsigned m = (unsigned)c;                                // lanes 9..63: all ones
     m = min(m, (unsigned)__builtin_amdgcn_mov_dpp((int)m, DPP_XOR1, 0xF, 0xF, true));
@@ -641,11 +656,12 @@ __device__ __forceinline__ void fm_best(unsigned dl, bool quarter, const unsigne
     m = min(m, (unsigned)__builtin_amdgcn_mov_dpp((int)m, DPP_HALF_MIRROR, 0xF, 0xF, true));
     m = min(m, (unsigned)__builtin_amdgcn_mov_dpp((int)m, 0x140, 0xF, 0xF, true));          // row_mirror: the minimum of the 16 lanes in each of them
     const unsigned m0 = (unsigned)__builtin_amdgcn_readfirstlane((int)m);
-    bi = __builtin_ctzll(__ballot((unsigned)c == m0 && lane < 9));
+    bi = __builtin_ctzll(__builtin_amdgcn_ballot_w64((unsigned)c == m0 && lane < 9));
     bcost = m0;
   }
   else
   {
+    if (lane >= 9) c = ~0ull;
     bi = lane;
 #pragma unroll
     for (int o = 1; o < 16; o <<= 1)
@@ -686,7 +702,7 @@ __global__ __launch_bounds__(64 * WV, WV == 16 ? 1 : WPS) void frac16m_kernel(co
   const int headRoom = max(2, 14 - bd), shift1 = 6 - headRoom, S = 1 << shift1;
   FmK K;
   K.magicA = 8388608.f * (float)S;
-  K.sp0 = c16 == 8 * (g & 1) ? 0x68003C00u : 0u;             // (1.0, 2048.0)
+  K.sp0 = c16 == 8 * (g & 1) ? 0x78005800u : 0u;             // (128.0, 32768.0): fm_limbs
   K.pmin = fh2{ (_Float16)(short)(1024 + cmin), (_Float16)(short)(1024 + cmin) };
   K.pmax = fh2{ (_Float16)(short)(1024 + cmax), (_Float16)(short)(1024 + cmax) };
   K.sg = (c16 & 8) ? fh2{ (_Float16)-1.f, (_Float16)-1.f } : fh2{ (_Float16)1.f, (_Float16)1.f };
@@ -701,7 +717,8 @@ __global__ __launch_bounds__(64 * WV, WV == 16 ? 1 : WPS) void frac16m_kernel(co
   K.orR[0] = K.orX[0];
   K.m7[1] = g < 2 ? 0x007F007Fu : 0u; K.m8[1] = g < 2 ? 0x00FF00FFu : 0u;
   K.orX[1] = g < 2 ? 0x64006400u : g == 2 ? 0x3C003C00u : 0u; K.orR[1] = g < 2 ? 0x64006400u : 0u;
-  const unsigned winAnd = g == 3 ? 0u : 0xFFFFFFFFu, winOrX = g == 3 ? 0x3C003C00u : 0x64006400u, winOrR = g == 3 ? 0u : 0x64006400u;   // columns 24..31: 1.0, 1.0, 0 ..
+  unsigned winAnd = g == 3 ? 0u : 0xFFFFFFFFu, winOrX = g == 3 ? 0x3C003C00u : 0x64006400u, winOrR = g == 3 ? 0u : 0x64006400u;   // columns 24..31: 1.0, 1.0, 0 ..
+  asm("" : "+v"(winAnd), "+v"(winOrX), "+v"(winOrR));        // as opaque lane constants: one v_and_or_b32 per register (seen through, they become an OR and a select on g == 3)
   const unsigned rangeMask = (unsigned)((1 << bd) - 1) * 0x10001u;
   const int orgLo = max(cmax - 1023, -1024), orgHi = min(cmin + 1023, 1023);   // |org - pred| <= 1023 for every clipped prediction, and 1024 + org exact in f16
   const int yrow = fm_ymap(c16);
@@ -763,7 +780,7 @@ __global__ __launch_bounds__(64 * WV, WV == 16 ? 1 : WPS) void frac16m_kernel(co
     blkN.ref_x = __builtin_amdgcn_readfirstlane((int)bv1.x); blkN.ref_y = __builtin_amdgcn_readfirstlane((int)bv1.y);
     blkN.mv_x = __builtin_amdgcn_readfirstlane((int)bv2.x); blkN.mv_y = __builtin_amdgcn_readfirstlane((int)bv2.y);
     predHN = __builtin_amdgcn_readfirstlane(pv.x); predVN = __builtin_amdgcn_readfirstlane(pv.y);
-    const bool fallBack = __ballot(bad != 0) != 0ull;        // reference samples outside the bit depth, or an original that is not a picture:
+    const bool fallBack = __builtin_amdgcn_ballot_w64(bad != 0) != 0ull;   // reference samples outside the bit depth, or an original that is not a picture:
     if (fallBack)                                            // set aside for the vector-pipe form
     {
       fetch(blkN, rawN);
@@ -777,17 +794,20 @@ __global__ __launch_bounds__(64 * WV, WV == 16 ? 1 : WPS) void frac16m_kernel(co
       f4 Ra = { 0.f, 0.f, 0.f, 0.f }, Rb = { 0.f, 0.f, 0.f, 0.f };
       const int cbH[3] = { fm_combo(0, 0), fm_combo(2, -1), fm_combo(2, 0) };      // dy = 0, -1, +1
       float P[3];
+      unsigned L[9];                                         // the candidates' parts as limb registers, by candidate index: four to a product
       fm_plane(tabS, fm_combo(0, 0), pu, K, lane, pl);
       fm_cands<3>(tabS, cbH, pl, pu, K, lane, P);
-      Ra = fm_acc<fm_idx(0, 0, false), fm_idx(0, -1, false), fm_idx(0, 1, false)>(Ra, P[0], P[1], P[2], K);
+      L[fm_idx(0, 0, false)] = fm_limbs(P[0]); L[fm_idx(0, -1, false)] = fm_limbs(P[1]); L[fm_idx(0, 1, false)] = fm_limbs(P[2]);
       fm_plane(tabS, fm_combo(2, -1), pu, K, lane, pl);
       fm_cands<3>(tabS, cbH, pl, pu, K, lane, P);
-      Ra = fm_acc<fm_idx(-1, 0, false), fm_idx(-1, -1, false), fm_idx(-1, 1, false)>(Ra, P[0], P[1], P[2], K);
+      L[fm_idx(-1, 0, false)] = fm_limbs(P[0]); L[fm_idx(-1, -1, false)] = fm_limbs(P[1]); L[fm_idx(-1, 1, false)] = fm_limbs(P[2]);
+      Ra = fm_acc<0, 1, 2, 3>(Ra, L[0], L[1], L[2], L[3], K);
       fetch(blkN, rawN);                                     // the next PU's samples travel behind the rest of this one
       fm_plane(tabS, fm_combo(2, 0), pu, K, lane, pl);
       fm_cands<3>(tabS, cbH, pl, pu, K, lane, P);
-      Ra = fm_acc<fm_idx(1, 0, false), fm_idx(1, -1, false), -1>(Ra, P[0], P[1], 0.f, K);
-      Rb = fm_acc<fm_idx(1, 1, false), -1, -1>(Rb, P[2], 0.f, 0.f, K);                       // candidate 8: slot 0 of its own accumulator
+      L[fm_idx(1, 0, false)] = fm_limbs(P[0]); L[fm_idx(1, -1, false)] = fm_limbs(P[1]); L[fm_idx(1, 1, false)] = fm_limbs(P[2]);
+      Ra = fm_acc<4, 5, 6, 7>(Ra, L[4], L[5], L[6], L[7], K);
+      Rb = fm_acc<8, -1, -1, -1>(Rb, L[8], 0u, 0u, 0u, K);                                   // candidate 8: slot 0 of its own accumulator
       const float da = fm_finalize(Ra, lane), db = fm_finalize(Rb, lane);
       int hx, hy;
       unsigned long long costH;
@@ -803,20 +823,22 @@ __global__ __launch_bounds__(64 * WV, WV == 16 ? 1 : WPS) void frac16m_kernel(co
         const int qx = 2 * hx - 1;
         fm_plane(tabS, fm_combo(qx & 3, (qx & 3) ? qx >> 2 : 0), pu, K, lane, pl);
         fm_cands<3>(tabS, cbQ, pl, pu, K, lane, P);
-        Rq = fm_acc<fm_idx(-1, -1, true), fm_idx(-1, 0, true), fm_idx(-1, 1, true)>(Rq, P[0], P[1], P[2], K);
+        L[fm_idx(-1, -1, true)] = fm_limbs(P[0]); L[fm_idx(-1, 0, true)] = fm_limbs(P[1]); L[fm_idx(-1, 1, true)] = fm_limbs(P[2]);
       }
       {
         const int qx = 2 * hx;
         float P2[2];
         fm_plane(tabS, fm_combo(qx & 3, (qx & 3) ? qx >> 2 : 0), pu, K, lane, pl);
         fm_cands<2>(tabS, cbQ2, pl, pu, K, lane, P2);
-        Rq = fm_acc<fm_idx(0, -1, true), fm_idx(0, 1, true), -1>(Rq, P2[0], P2[1], 0.f, K);
+        L[fm_idx(0, -1, true)] = fm_limbs(P2[0]); L[fm_idx(0, 1, true)] = fm_limbs(P2[1]);
+        Rq = fm_acc<1, 2, 3, 5>(Rq, L[1], L[2], L[3], L[5], K);
       }
       {
         const int qx = 2 * hx + 1;
         fm_plane(tabS, fm_combo(qx & 3, (qx & 3) ? qx >> 2 : 0), pu, K, lane, pl);
         fm_cands<3>(tabS, cbQ, pl, pu, K, lane, P);
-        Rq = fm_acc<fm_idx(1, -1, true), fm_idx(1, 0, true), fm_idx(1, 1, true)>(Rq, P[0], P[1], P[2], K);
+        L[fm_idx(1, -1, true)] = fm_limbs(P[0]); L[fm_idx(1, 0, true)] = fm_limbs(P[1]); L[fm_idx(1, 1, true)] = fm_limbs(P[2]);
+        Rq = fm_acc<4, 6, 7, 8>(Rq, L[4], L[6], L[7], L[8], K);
       }
       const float dq = fm_finalize(Rq, lane);                   // lane i (1..7) = candidate i, lane 8 = candidate 8 (slot 0 once more), lane 0 := the centre
       int qdx, qdy;
