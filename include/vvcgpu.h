@@ -1422,8 +1422,8 @@ int vvcgpu_intra_mode_cand_batch(
  * region its own pred region.  Samples must lie within the bit depth.  Offsets cannot be validated.
  * VVCGPU_E_ARG before any device work: a null required pointer (pred_base may be NULL when no item is PRED_GIVEN and WRITE_PRED is off; mode_list may
  * be NULL), negative n, unknown flag bits, a bad clip range, a descriptor array that is not 16-byte aligned.  n == 0 is a no-op.
- * Not served: transform skip and RDPCM (their own entries), RDOQ and the DepQuant trellis (vvcgpu_rdoq_batch / vvcgpu_depquant_batch; this is the
- * Quant::quant chain), cross-component prediction, TUs split below the PU (the 64x64 TUs of a 128-sample CU depend on each other's reconstruction),
+ * Not served: transform skip and RDPCM (their own entries), RDOQ (vvcgpu_rdoq_batch; this is the Quant::quant chain; the DepQuant trellis is
+ * vvcgpu_intra_tu_code_dq_batch's, below), cross-component prediction, TUs split below the PU (the 64x64 TUs of a 128-sample CU depend on each other's reconstruction),
  * chroma and CCLM prediction (they come in through PRED_GIVEN; whole chroma PUs: vvcgpu_intra_chroma_code_batch), the rate and the cost.          */
 #define VVCGPU_INTRA_TU_PRED_GIVEN  (-1)   /* preds[i].mode: the prediction is read from pred_base */
 #define VVCGPU_INTRA_TU_FROM_LIST   (-2)   /* preds[i].mode: taken from mode_list */
@@ -1436,6 +1436,55 @@ int vvcgpu_intra_tu_code_batch(
     const int32_t* mode_list,
     int flags, int bit_depth, int clp_min, int clp_max,
     uint32_t* abs_sum, uint32_t* num_sig, uint64_t* dist, int32_t* mode_out, void* stream);
+
+/* ---- the pixel pass of the intra RD loop with the quantiser of the shipped cfgs (DepQuant 1) ----
+ * vvcgpu_intra_tu_code_batch as above -- the same items (preds[i] + tus[i]), the same three mode kinds (0..66 as given, VVCGPU_INTRA_TU_FROM_LIST from
+ * mode_list with the device's filter decision, VVCGPU_INTRA_TU_PRED_GIVEN), the same flags, the same outputs at the same indices, the same skip
+ * markers -- with what transformNxN (IntraSearch.cpp:1253, called with the estimator's contexts) and invTransformNxN (:1289) of
+ * IntraSearch::xIntraCodingTUBlock (EncoderLib/IntraSearch.cpp:1147-1316) do under slice->getDepQuantEnabledFlag():
+ *   the quantiser is DQIntern::DepQuant::quant (CommonLib/DepQuant.cpp:1323-1387), the trellis of vvcgpu_depquant_batch over all w h coefficients (the
+ *               zeroed region of a 64-point side holds zeros), its early return when no coefficient exceeds getLastThreshold() included (abs_sum 0, all
+ *               levels zero);
+ *   the de-quantiser is DQIntern::Quantizer::dequantBlock (:708-785), the dep_quant = 1 path of vvcgpu_dequant_tr_inv_batch.
+ * Transform, trellis, de-quantiser and inverse transform are those of vvcgpu_inter_resi_code_dq_batch.  intra_slice and sign_hiding of tus[i] are
+ * IGNORED: the trellis has no rounding offset, and sign bit hiding is off with dependent quantisation (JVET_K0072).
+ * The trellis of an intra CU differs from an inter CU's only in RateEstimator::xSetLastCoeffOffset (DepQuant.cpp:379-396): an intra luma TU takes the
+ * QtCbf bits where a depth-0 inter luma TU takes QtRootCbf.  That lives in the rate table: AN INTRA CALLER FILLS vvcgpu_dq_rates.cbf FROM QtCbf
+ * (shim/vtm_rates.h branches on CU::isIntra).
+ * Per served item: the prediction is formed in LDS and stored at tus[i].pred_off only under WRITE_PRED; org - pred goes through the forward transform
+ * of tr_hor / tr_ver; the levels go to level_off; num_sig[i] is the number of non-zero stored levels, uncapped (the compare with g_EmtSigNumThr and
+ * the early return of :1276 stay with the caller, the entry always finishes the item); with abs_sum == 0 the reconstruction is clip(pred) (the
+ * piResi.fill(0) branch of :1293); dist[i] = xGetSSE(org, rec) from the reconstruction just formed; mode_out[i] as above.
+ * At most three launches on the caller's stream (prediction + forward transforms, trellis, de-quantiser + inverse transforms + reconstruction +
+ * distortion), no host synchronisation inside; validity and the list look-up are decided on the device, so the call can be submitted behind
+ * vvcgpu_intra_mode_cand_batch without a download.
+ *
+ * dq[i]        parallel to the items, 8-byte aligned: lambda = Quant::m_dLambda of the component (> 0), rates_idx and luma as in vvcgpu_depquant_desc.
+ * rates        n_rates tables (vvcgpu_dq_rates), in device memory.
+ * quantiser    VVCGPU_INTRA_TU_Q_DEPQUANT, the one served value; any other returns VVCGPU_E_UNSUPPORTED before any device work.
+ * level_extent the extent of level_base, in levels, that the items address (at least 16).
+ * ws           device workspace of vvcgpu_intra_tu_code_dq_workspace_bytes(level_extent, n) bytes, 16-byte aligned: the coefficients, the trellis
+ *              decisions and level histories, the predictions between the first and the last launch -- all indexed by the item's level offset -- and
+ *              per item a trellis record and a work-list entry.  It may hold anything on entry; nothing in it survives the call by contract.
+ * An item is skipped, beside the rules of vvcgpu_intra_tu_code_batch, when level_off is negative or not a multiple of 16 (the trellis workspace is
+ * indexed by it), when its w h levels do not lie inside level_extent, when rates_idx is outside [0, n_rates) or lambda is not above zero.  An item
+ * outside the contract is never a fault.
+ * VVCGPU_E_ARG before any device work: the cases of vvcgpu_intra_tu_code_batch, a null dq, rates or ws, n_rates < 1, level_extent < 16, a workspace
+ * that is too small or not 16-byte aligned, a dq array that is not 8-byte aligned.  n == 0 is a no-op.
+ * With the caller: as for vvcgpu_intra_tu_code_batch, and the rate tables (one per component and TU size class, refreshed when the CABAC contexts move).
+ * Not served: RDOQ, transform skip and RDPCM, cross-component prediction, TUs split below the PU, the chroma mode pass under DepQuant
+ * (vvcgpu_intra_chroma_code_batch is the Quant::quant chain; chroma reaches this entry through PRED_GIVEN).                                        */
+#define VVCGPU_INTRA_TU_Q_DEPQUANT 1       /* quantiser: DQIntern::DepQuant::quant */
+size_t vvcgpu_intra_tu_code_dq_workspace_bytes(size_t level_extent, int n);
+int vvcgpu_intra_tu_code_dq_batch(
+    const vvc_pel* refs_base, const vvcgpu_intra_desc* preds,
+    const vvc_pel* org_base, vvc_pel* pred_base, vvc_pel* rec_base, vvc_coef* level_base, size_t level_extent,
+    const vvcgpu_resi_chain_desc* tus, const vvcgpu_inter_resi_dq* dq, int n,
+    const int32_t* mode_list,
+    const struct vvcgpu_dq_rates* rates, int n_rates, int quantiser,
+    int flags, int bit_depth, int clp_min, int clp_max,
+    uint32_t* abs_sum, uint32_t* num_sig, uint64_t* dist, int32_t* mode_out,
+    void* ws, size_t ws_bytes, void* stream);
 
 /* N4, the intra chroma mode pass: what the mode loop of IntraSearch::estIntraPredChromaQT (EncoderLib/IntraSearch.cpp:704-852) does in pixels for n
  * independent chroma PUs of mixed sizes, each one TU per component, 4:2:0, with no host synchronisation inside: per PU up to six candidate modes

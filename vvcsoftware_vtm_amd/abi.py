@@ -77,6 +77,7 @@ INTRA_FILL_DESC = np.dtype([("rec_off", "<i8"), ("flags_off", "<i8"), ("ref_off"
 # vvcgpu_intra_tu_code_batch: INTRA_DESC.mode values beside 0..66, and the flags
 INTRA_TU_PRED_GIVEN, INTRA_TU_FROM_LIST = -1, -2
 INTRA_TU_WRITE_PRED, INTRA_TU_NO_SMOOTHING = 1, 2
+INTRA_TU_Q_DEPQUANT = 1                                                     # vvcgpu_intra_tu_code_dq_batch: the served quantiser
 # vvcgpu_intra_chroma_code_batch: one chroma PU (vvcgpu_intra_chroma_pu), the mode value of LM_CHROMA_IDX and the flag
 INTRA_CHROMA_PU = np.dtype([("org_off", "<i8", (2,)), ("ref_off", "<i8", (2,)), ("luma_off", "<i8"), ("cand_off", "<i8"), ("level_off", "<i8"),
                             ("org_stride", "<i4"), ("luma_stride", "<i4"), ("qp", "<i4", (2,)), ("w", "<i2"), ("h", "<i2"), ("above_avail", "i1"),

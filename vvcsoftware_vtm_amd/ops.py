@@ -9,7 +9,7 @@ import torch
 from . import capi
 # the struct mirrors live in abi; bench.py, the tests and the tools read them as ops.<NAME>
 from .abi import (AFE_DESC, AFFINE_ITER, AFFINE_ME_ITEM, AFFINE_ME_MAX_STEPS, AFFINE_ME_RESULT, AFFINE_ME_STEP, AFFINE_PU, AFG_DESC, CCLM_DESC, DEPQUANT_DESC, DIST_DESC, DQ_RATES, DQTR_DESC, FRAC_BLK,  # noqa: F401
-                  FRAC_RESULT, IF_DESC, IMV_PU, IMV_RESULT, INTER_RESI_DQ, INTER_RESI_ITEM, INTER_RESI_Q_DEPQUANT, INTER_RESI_SLOTS, INTER_RESI_TS, INTER_RESI_WRITE_REC, INTRA_DESC, INTRA_FILL_DESC, INTRA_SATD_DESC, INTRA_CHROMA_LM, INTRA_CHROMA_PU, INTRA_CHROMA_WRITE_PRED, INTRA_TU_FROM_LIST, INTRA_TU_NO_SMOOTHING, INTRA_TU_PRED_GIVEN, INTRA_TU_WRITE_PRED, MC_DESC, PELOP_DESC, QUANT_DESC, RC_DESC,
+                  FRAC_RESULT, IF_DESC, IMV_PU, IMV_RESULT, INTER_RESI_DQ, INTER_RESI_ITEM, INTER_RESI_Q_DEPQUANT, INTER_RESI_SLOTS, INTER_RESI_TS, INTER_RESI_WRITE_REC, INTRA_DESC, INTRA_FILL_DESC, INTRA_SATD_DESC, INTRA_CHROMA_LM, INTRA_CHROMA_PU, INTRA_CHROMA_WRITE_PRED, INTRA_TU_FROM_LIST, INTRA_TU_NO_SMOOTHING, INTRA_TU_PRED_GIVEN, INTRA_TU_Q_DEPQUANT, INTRA_TU_WRITE_PRED, MC_DESC, PELOP_DESC, QUANT_DESC, RC_DESC,
                   RDOQ_DESC, RDOQ_RATES, RDPCM_DESC, SAO_DTYPE, SEARCH_BEST, SEARCH_BLK, TR_DESC, TZ_CFG, TZ_PU, DeblockCfg, MeHierCfg, MvCost,
                   PelopCfg, Planes, AffineMeCfg, BipredMeCfg, BIPRED_ME_ITEM, BIPRED_ME_MAX_PLANES, BIPRED_ME_MAX_REFS, BIPRED_ME_MAX_STEPS, BIPRED_ME_REF,
                   BIPRED_ME_RESULT, BIPRED_ME_STEP, AffineBipredCfg, AFFINE_BIPRED_ITEM, AFFINE_BIPRED_MAX_REFS, AFFINE_BIPRED_MAX_STEPS,
@@ -279,6 +279,32 @@ def intra_tu_code_batch(refs_base, preds_dev, org_base, pred_base, rec_base, lev
     capi.call("vvcgpu_intra_tu_code_batch", capi.ptr(refs_base), capi.ptr(preds_dev), capi.ptr(org_base), capi.ptr(pred_base), capi.ptr(rec_base),
               capi.ptr(level_base), capi.ptr(tus_dev), n, capi.ptr(mode_list), flags, bit_depth, clp[0], clp[1], capi.ptr(abs_sum), capi.ptr(num_sig),
               capi.ptr(dist), capi.ptr(mode_out), _stream())
+    return abs_sum, num_sig, dist, mode_out
+
+
+def intra_tu_code_dq_workspace(level_extent, n, device="cuda"):
+    """a workspace for intra_tu_code_dq_batch (vvcgpu_intra_tu_code_dq_workspace_bytes); its contents never matter"""
+    return torch.empty(capi.lib().vvcgpu_intra_tu_code_dq_workspace_bytes(level_extent, n), dtype=torch.uint8, device=device)
+
+
+def intra_tu_code_dq_batch(refs_base, preds_dev, org_base, pred_base, rec_base, level_base, tus_dev, dq_dev, n, rates_dev, n_rates, mode_list=None, flags=0,
+                           bit_depth=10, clp=(0, 1023), ws=None, quantiser=INTRA_TU_Q_DEPQUANT):
+    """the pixel pass of the intra RD loop with the DepQuant trellis (vvcgpu_intra_tu_code_dq_batch): as intra_tu_code_batch, with dq_dev a device copy of
+    an INTER_RESI_DQ array parallel to the items, rates_dev one of a DQ_RATES array of n_rates tables (cbf from QtCbf), ws a workspace of
+    intra_tu_code_dq_workspace for level_base's extent (allocated here when None).
+    -> (abs_sum int32 [n] (bits as uint32), num_sig int32 [n] (bits as uint32), dist int64 [n] (bits as uint64), mode_out int32 [n])"""
+    dv = org_base.device
+    extent = int(level_base.numel())
+    if ws is None:
+        ws = intra_tu_code_dq_workspace(extent, n, dv)
+    abs_sum = torch.empty(n, dtype=torch.int32, device=dv)                 # every entry is written by the library
+    num_sig = torch.empty(n, dtype=torch.int32, device=dv)
+    dist = torch.empty(n, dtype=torch.int64, device=dv)
+    mode_out = torch.empty(n, dtype=torch.int32, device=dv)
+    capi.call("vvcgpu_intra_tu_code_dq_batch", capi.ptr(refs_base), capi.ptr(preds_dev), capi.ptr(org_base), capi.ptr(pred_base), capi.ptr(rec_base),
+              capi.ptr(level_base), C.c_size_t(extent), capi.ptr(tus_dev), capi.ptr(dq_dev), n, capi.ptr(mode_list), capi.ptr(rates_dev), n_rates, quantiser,
+              flags, bit_depth, clp[0], clp[1], capi.ptr(abs_sum), capi.ptr(num_sig), capi.ptr(dist), capi.ptr(mode_out), capi.ptr(ws), C.c_size_t(ws.numel()),
+              _stream())
     return abs_sum, num_sig, dist, mode_out
 
 
