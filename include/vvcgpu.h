@@ -241,7 +241,10 @@ int vvcgpu_sad_search(const vvc_pel* org, int org_stride, const vvc_pel* ref, in
  * sum of the SADs of its 16x16 sub-blocks at that displacement (same rows under row sub-sampling), so each 16x16 SAD is computed ONCE and the
  * larger blocks are sums.  Per block the result equals vvcgpu_sad_search on that block with
  *   raster: dx0 = dy0 = -5 (raster_range / 5), nx = ny = 2 (raster_range / 5) + 1, sx = sy = 5;   dense: dx0 = dy0 = -dense_range, nx = ny = 2 dense_range + 1,
- * the same sub_shift and mvcost (cost, arg-min in visiting order, strict '<').
+ * the same sub_shift and mvcost (cost, arg-min in visiting order, strict '<').  Sample range: org samples may be any int16, as for
+ * vvcgpu_sad_search (2 org - otherPred of a bi-predictive search and beyond); reference samples are picture samples of at most 10 bits; with these the SAD
+ * of a 64x64 block is at most 4096 * 33791 < 2^28 and SAD + lambda * bits stays below the 0x30000000 the raster key is built on (tested at
+ * exactly these ends: tests/test_gpu_search_bounds.py).
  * Grid: 16x16 block (i, j), i < n16x, j < n16y, has its origin at (org_x + 16 i, org_y + 16 j) in the original and its zero-vector position at
  * (ref_x + 16 i, ref_y + 16 j) in the reference plane; 32x32 block (i, j) covers 16x16 blocks (2i .. 2i+1, 2j .. 2j+1), i < n16x / 2, j < n16y / 2
  * (whole blocks only), 64x64 likewise with 4.  Results: raster_best[0 / 1 / 2] = arrays of n16x n16y / (n16x/2)(n16y/2) / (n16x/4)(n16y/4) records

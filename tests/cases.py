@@ -404,3 +404,65 @@ def alf_worst_planes(kind, w, h, bd):
     rec = np.full((h, w), v, np.int16)
     org = np.full((h, w), 0 if v > mx // 2 else mx, np.int16)
     return org, rec
+
+
+# ---- inputs at the bounds of the integer searches' packed keys and of the block distortions' sums -------------------------
+# kind -> (org, the two reference levels; the second one gives the larger |org - ref|)
+SEARCH_BOUND_KINDS = {"bipred_hi": (2046, (1, 0)), "bipred_lo": (-1023, (1022, 1023)), "int16_hi": (32767, (1, 0)), "int16_lo": (-32768, (1022, 1023))}
+# 64 x 64 samples of the larger |d|: what every position of a 64x64 block of a tie=True plane costs (the searches' `<< sub_shift` gives it back)
+SEARCH_BOUND_SAD64 = {"bipred_hi": 8380416, "bipred_lo": 8380416, "int16_hi": 134213632, "int16_lo": 138407936}
+
+
+def search_bound_planes(kind, tie, W, H, m):
+    """(org H x W, ref (H + 2 m) x (W + 2 m)): a constant original at an end of the bi-predictive (2 org - otherPred at bit depth 10) or of the int16
+    range, and a reference inside bit depth 10 at the opposite end: two adjacent levels drawn per 40 x 40 patch (SADs differ between positions by
+    less than one part in a thousand), or with tie=True the one level of the larger |d| (every position of every block has the same SAD)"""
+    o, (near, far) = SEARCH_BOUND_KINDS[kind]
+    PW, PH = W + 2 * m, H + 2 * m
+    org = np.full((H, W), o, np.int16)
+    if tie:
+        return org, np.full((PH, PW), far, np.int16)
+    rng = np.random.default_rng(4000 + sorted(SEARCH_BOUND_KINDS).index(kind))
+    pick = rng.integers(0, 2, (PH // 40 + 1, PW // 40 + 1)).repeat(40, 0).repeat(40, 1)[:PH, :PW]
+    return org, np.ascontiguousarray(np.where(pick, far, near).astype(np.int16))
+
+
+# (lambda, pred_hor, pred_ver) at cost_scale 2: every cost equal; the realistic top; a near predictor (the bits vary over the grid: differences in
+# bits 16..22 of the cost); a far predictor (59 or 61 bits per component: lambda * bits in [2^28, 2^29) at every position, the top of the 32-bit keys)
+SEARCH_BOUND_MVCOSTS = [(0.0, 0, 0), (1000.0, 37, -22), (65536.5, -58, 41), (3999999.5, -(1 << 29), 1 << 29)]
+# vvcgpu_tz_search_batch takes lambda < 2^20
+SEARCH_BOUND_MVCOSTS_TZ = SEARCH_BOUND_MVCOSTS[:3] + [(1048575.5,) + SEARCH_BOUND_MVCOSTS[3][1:]]
+
+DIST_BOUND_KINDS = ("const", "checker", "half")
+
+
+def dist_bound_planes(kind, W, H, bd):
+    """(org, cur) of one W x H block with |org - cur| = max in every sample: 'const' org = max, cur = 0 (the largest DC Hadamard coefficient);
+    'checker' cur a checkerboard of {0, max}, org its inverse (the highest-frequency coefficient); 'half' +max in the left half of every row and
+    -max in the right half (the mean-removed kinds subtract a zero mean from maximal differences)"""
+    mx = (1 << bd) - 1
+    yy, xx = np.mgrid[0:H, 0:W]
+    if kind == "const":
+        cur = np.zeros((H, W), np.int16)
+    elif kind == "checker":
+        cur = (((xx + yy) & 1) * mx).astype(np.int16)
+    elif kind == "half":
+        cur = ((xx >= W // 2) * mx).astype(np.int16)
+    else:
+        raise ValueError(kind)
+    return (mx - cur).astype(np.int16), cur
+
+
+SEARCH_BIT31_MV = (-5, 10)
+
+
+def search_bit31_planes(o, W, H, m, x0, y0, bw, bh):
+    """(org = o everywhere, ref = 0 but 1 where the bw x bh block at (x0, y0) lies when displaced by SEARCH_BIT31_MV): the block's SAD is at most bw bh o
+    and lowest, bw bh less, at that displacement; its neighbours overlap the patch of ones partly and lie between.  With bw bh o = 61 440 000 (64 x 64 x 15000, 16 x 128 x 30000) and the fourth entry of
+    SEARCH_BOUND_MVCOSTS the winner's raster key (cost << 2 | candidate, 118 bits) is just below 2^31 and the key of (0, 10) -- 120 bits, the last of
+    the four candidates a lane folds together with the winner -- just above: a signed 32-bit minimum inside the lane would prefer it"""
+    org = np.full((H, W), o, np.int16)
+    ref = np.zeros((H + 2 * m, W + 2 * m), np.int16)
+    dx, dy = SEARCH_BIT31_MV
+    ref[m + y0 + dy:m + y0 + dy + bh, m + x0 + dx:m + x0 + dx + bw] = 1
+    return org, ref

@@ -154,9 +154,15 @@ def test_me_hier_sliding_window_runs(monkeypatch, n16x, n16y, rr, dr, org_xy, re
 def test_me_hier_unsupported_shapes_are_refused():
     from vvcsoftware_vtm_amd import capi, ops
     org, refp = dev(np.zeros((64, 64), np.int16)), dev(np.zeros((400, 400), np.int16))
-    mv = ops.MvCost(4.0, 0, 0, 2, 0)
-    for kw in (dict(raster_range=128), dict(dense_range=5), dict(sub_shift=2)):
-        a = dict(sub_shift=1, raster_range=96, dense_range=4)
+    for kw in (dict(raster_range=128), dict(dense_range=5), dict(sub_shift=2),
+               dict(raster_range=100),                        # 41 x 41 positions
+               dict(raster_range=15),                         # R < D + 15: the +-4 grid's spans would leave the window
+               dict(lam=4.0e6)):                              # lambda * bits no longer below 2^29: the 32-bit raster key
+        a = dict(sub_shift=1, raster_range=96, dense_range=4, lam=4.0)
         a.update(kw)
         with pytest.raises(capi.VvcGpuError, match="-3"):
-            ops.me_hier_search(org, refp, (0, 0), (150, 150), 4, 4, a["sub_shift"], a["raster_range"], a["dense_range"], mv)
+            ops.me_hier_search(org, refp, (0, 0), (150, 150), 4, 4, a["sub_shift"], a["raster_range"], a["dense_range"], ops.MvCost(a["lam"], 0, 0, 2, 0))
+    # the last lambda below the limit is served
+    raster, dense = ops.me_hier_search(org, refp, (0, 0), (150, 150), 4, 4, 1, 96, 4, ops.MvCost(3999999.5, 0, 0, 2, 0))
+    torch.cuda.synchronize()
+    assert raster[2] is not None and dense[2] is not None

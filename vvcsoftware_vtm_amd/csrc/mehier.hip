@@ -47,7 +47,10 @@ constexpr int MH_MAXN = 39;                            // raster positions per a
 constexpr int MH_MAXSLOTS = 448;                       // 7 slot waves
 constexpr int MH_MAXSLIDE = 7;                         // slides of the window between two full fills (1 KB of slack behind the window)
 constexpr int MH_MAXDL = 96;                           // lanes of the +-D grid (9 rows x at most 9 spans)
-constexpr unsigned MH_INVALID = 0x30000000u;           // above every valid cost (SAD << 1 < 2^23, lambda * bits < 2^29), below 2^30
+// above every valid cost: SAD + cost < 0x30000000 = 2^28 + 2^29 (SAD of a 64x64 block of any two int16 planes <= 4096 * 65535 < 2^28; cost = lambda * bits
+// < 2^29, the host checks lambda < 4e6 and bits <= 131), and below 2^30: (cost << 2 | candidate) fits 32 bits.  An invalid lane's key is (MH_INVALID + its SAD)
+// << 2, inside 32 bits by the same SAD < 2^28.  tests/test_search_bounds_cpu.py puts inputs on these bounds (SAD 138 407 936, cost 487 999 939)
+constexpr unsigned MH_INVALID = 0x30000000u;
 
 struct MhGeom
 {

@@ -703,7 +703,10 @@ __global__ __launch_bounds__(MAXT, MINW) void sad_raster5q_kernel(const unsigned
 // v_sad_u16; the first group form (pair columns, sub-runs of four blocks, cost << 1 | candidate) needed 813 and is gone: its numbers are in
 // docs/OPTIMISATION_LOG.md.  A lambda too large for the 32-bit key goes to the per-block quad form.
 constexpr int R5G_MAXNB = 8;                            // blocks per group
-constexpr unsigned R5GQ_INVALID = 0x30000000u;         // above every valid cost (SAD << 1 < 2^20, lambda * bits < 2^29), below 2^30
+// above every valid cost: SAD + cost < 0x30000000 = 2^28 + 2^29 (SAD of a 16-wide block of any two int16 planes <= 16 * 128 * 65535 < 2^28; cost = lambda * bits
+// < 2^29: the host checks lambda < 4e6, bits <= 131), and below 2^30, so (cost << 2 | candidate) fits 32 bits, an invalid lane's (R5GQ_INVALID + SAD) << 2
+// included.  tests/test_search_bounds_cpu.py puts inputs on these bounds
+constexpr unsigned R5GQ_INVALID = 0x30000000u;
 
 __global__ __launch_bounds__(1024, 6) void sad_raster5gq_kernel(const unsigned* __restrict__ orgPacked, const Pel* __restrict__ ref, int rs,
                                                                 const vvcgpu_search_blk* __restrict__ blocks, int nblocks, int nbg, int h, int subShift,
@@ -1299,7 +1302,7 @@ int launch_r5q(const SadCall& c, const R5Plan& p, VvcScratch* sc, unsigned* pack
 int try_raster_group(const SadCall& c, VvcScratch& sc, bool& taken)
 {
   R5Plan p;
-  // 16-wide blocks, best candidate only; the 32-bit key cost << 2 | candidate needs lambda * bits < 2^29 (SAD << 1 < 2^20)
+  // 16-wide blocks, best candidate only; the 32-bit key cost << 2 | candidate needs SAD + lambda * bits < 0x30000000 (R5GQ_INVALID: SAD < 2^28, lambda * bits < 2^29)
   taken = c.raster5() && c.w == 16 && c.best && !c.out && c.nx <= 40 && c.mvHost->lambda >= 0.0 && c.mvHost->lambda < 4.0e6 &&
           r5gq_plan(c.nblocks, c.h, c.subShift, c.nx, c.ny, p);
   if (!taken) return VVCGPU_OK;
