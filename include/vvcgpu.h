@@ -1475,8 +1475,8 @@ int vvcgpu_intra_tu_code_batch(
  * VVCGPU_E_ARG before any device work: the cases of vvcgpu_intra_tu_code_batch, a null dq, rates or ws, n_rates < 1, level_extent < 16, a workspace
  * that is too small or not 16-byte aligned, a dq array that is not 8-byte aligned.  n == 0 is a no-op.
  * With the caller: as for vvcgpu_intra_tu_code_batch, and the rate tables (one per component and TU size class, refreshed when the CABAC contexts move).
- * Not served: RDOQ, transform skip and RDPCM, cross-component prediction, TUs split below the PU, the chroma mode pass under DepQuant
- * (vvcgpu_intra_chroma_code_batch is the Quant::quant chain; chroma reaches this entry through PRED_GIVEN).                                        */
+ * Not served: RDOQ, transform skip and RDPCM, cross-component prediction, TUs split below the PU.  The chroma mode pass under DepQuant is
+ * vvcgpu_intra_chroma_code_dq_batch (below); single chroma blocks also reach this entry through PRED_GIVEN.                                       */
 #define VVCGPU_INTRA_TU_Q_DEPQUANT 1       /* quantiser: DQIntern::DepQuant::quant */
 size_t vvcgpu_intra_tu_code_dq_workspace_bytes(size_t level_extent, int n);
 int vvcgpu_intra_tu_code_dq_batch(
@@ -1526,8 +1526,8 @@ int vvcgpu_intra_tu_code_dq_batch(
  * negative count, counts not summing to n, unknown flag bits, a bad clip range, a descriptor array that is not 16-byte aligned.  n == 0 is a no-op.
  * With the caller: getIntraChromaCandModes and the resolution of DM through getFinalIntraMode, isLMCModeEnabled, the rate (xGetIntraFracBitsQT), the cost
  * compare, the chroma distortion weight and DF_SSE_WTD, the copy of the winner.
- * Not served: transform-skip candidates (checkTransformSkip: their own entries), cross-component prediction, RDOQ and the DepQuant trellis, 4:2:2 and
- * 4:4:4, TUs split below the PU.                                                                                                                      */
+ * Not served: transform-skip candidates (checkTransformSkip: their own entries), cross-component prediction, RDOQ, 4:2:2 and 4:4:4, TUs split below
+ * the PU.  The DepQuant trellis is vvcgpu_intra_chroma_code_dq_batch's (below).                                                                      */
 #define VVCGPU_INTRA_CHROMA_LM          67   /* mode[k]: LM_CHROMA_IDX */
 #define VVCGPU_INTRA_CHROMA_WRITE_PRED   1   /* flags: every served item also stores its prediction in pred_base */
 typedef struct vvcgpu_intra_chroma_pu {
@@ -1549,6 +1549,55 @@ int vvcgpu_intra_chroma_code_batch(
     vvc_pel* pred_base, vvc_pel* cand_rec_base, vvc_coef* level_base,
     int flags, int bit_depth, int clp_min, int clp_max,
     uint32_t* abs_sum, uint64_t* dist, void* stream);
+
+/* ---- the intra chroma mode pass with the quantiser of the shipped cfgs (DepQuant 1) ----
+ * vvcgpu_intra_chroma_code_batch as above -- the same PUs grouped by shape, the same fill / refs_base / luma_base, the same six slots and mode values,
+ * VVCGPU_INTRA_CHROMA_WRITE_PRED, the same outputs at index 12 p + 2 k + c, the same candidate buffer layout, the same markers of unused slots and of
+ * PUs outside the contract -- with what transformNxN and invTransformNxN of xIntraCodingTUBlock do under slice->getDepQuantEnabledFlag(), exactly as
+ * in vvcgpu_intra_tu_code_dq_batch:
+ *   the quantiser is DQIntern::DepQuant::quant (CommonLib/DepQuant.cpp:1323-1387) over all w h coefficients (the zeroed region of a 64-point side holds
+ *               zeros), its early return when no coefficient exceeds getLastThreshold() included (abs_sum 0, all levels zero);
+ *   the de-quantiser is DQIntern::Quantizer::dequantBlock (:708-785); the transform is DCT-II both ways;
+ *   abs_sum == 0 gives rec = clip(pred) (the piResi.fill(0) branch); intra_slice and sign_hiding of the PU are IGNORED.
+ * THE RATE TABLE OF A Cr BLOCK DEPENDS ON THE Cb BLOCK OF THE SAME CANDIDATE MODE.  RateEstimator::xSetLastCoeffOffset (CommonLib/DepQuant.cpp:379-396)
+ * takes the cbf bits of a chroma TU from Ctx::QtCbf[compID](DeriveCtx::CtxQtCbf(compID, tu.depth, tu.cbf[COMPONENT_Cb])); DeriveCtx::CtxQtCbf
+ * (CommonLib/ContextModelling.cpp:519-549) returns prevCbCbf ? 1 : 0 for Cr; xRecurIntraChromaCodingQT (EncoderLib/IntraSearch.cpp:1722-1843) codes Cb
+ * first, and xIntraCodingTUBlock sets tu.cbf[Cb] from Cb's uiAbsSum before Cr's transformNxN runs.  The choice is made here on the device, per slot,
+ * from the Cb result of that slot in the same call:
+ * dq[3 p + 0]  the record of the PU's Cb blocks;
+ * dq[3 p + 1]  the record of Cr in a slot whose Cb block has abs_sum == 0: THE CALLER FILLS ITS TABLE'S cbf FROM Ctx::QtCbf[Cr](0);
+ * dq[3 p + 2]  the record of Cr in a slot whose Cb block has abs_sum > 0: its table's cbf from Ctx::QtCbf[Cr](1).
+ *              Each record has its own lambda (selectLambda(compID), > 0) and rates_idx; luma must be 0.  The array is 8-byte aligned.
+ * rates        n_rates tables (vvcgpu_dq_rates), in device memory.
+ * quantiser    VVCGPU_INTRA_CHROMA_Q_DEPQUANT, the one served value; any other returns VVCGPU_E_UNSUPPORTED before any device work.
+ * level_extent the extent of level_base, in levels, that the PUs address (at least 16).
+ * ws           device workspace of vvcgpu_intra_chroma_code_dq_workspace_bytes(level_extent, n) bytes, 16-byte aligned: the coefficients, the trellis
+ *              decisions and level histories, the predictions between the first and the last launch -- all indexed by the item's level offset -- and
+ *              per item (twelve per PU) a trellis record and a work-list entry.  It may hold anything on entry; nothing in it survives the call by
+ *              contract.
+ * Five launches on the caller's stream, for every list (one kernel design serves all shapes): staging + prediction + forward transforms; the trellis of
+ * the Cb blocks; the choice of the Cr records; the trellis of the Cr blocks; de-quantiser + inverse transforms + reconstruction + distortion.  No host
+ * synchronisation inside: the call can be submitted behind the luma passes.
+ * Contract differences from vvcgpu_intra_chroma_code_batch, all decided on the device and never a fault: sides are 4..64 (vvcgpu_depquant_batch serves
+ * no 2-sample side); a RUN with a 2-sample side is accepted, so that the sibling's list can be handed over, and every PU of it gets the markers;
+ * level_off must be a non-negative multiple of 16 (the trellis workspace is indexed by level offsets; w h >= 16 keeps every item of a PU on that grid);
+ * all twelve blocks of the PU must lie inside level_extent; all three records must have rates_idx in [0, n_rates), lambda > 0 and luma == 0.  Any
+ * violation skips the whole PU: markers for all twelve items, buffers untouched.
+ * VVCGPU_E_ARG before any device work: the cases of vvcgpu_intra_chroma_code_batch, a null dq, rates or ws, n_rates < 1, level_extent < 16, a dq array
+ * that is not 8-byte aligned, a workspace that is too small or not 16-byte aligned, n above (2^31 - 1) / 12, level_extent of 2^40 or more.  A bit depth outside 8..10 returns
+ * VVCGPU_E_UNSUPPORTED.  n == 0 is a no-op.
+ * With the caller: as for vvcgpu_intra_chroma_code_batch, and the three tables and lambdas per PU (shim/vtm_rates.h fills either Cr table from tu.cbf[Cb]).
+ * Not served: transform-skip candidates, cross-component prediction, RDOQ, 4:2:2 and 4:4:4, TUs split below the PU, 2-sample sides, the rate and the cost. */
+#define VVCGPU_INTRA_CHROMA_Q_DEPQUANT 1   /* quantiser: DQIntern::DepQuant::quant */
+size_t vvcgpu_intra_chroma_code_dq_workspace_bytes(size_t level_extent, int n);
+int vvcgpu_intra_chroma_code_dq_batch(
+    const vvc_pel* rec_base, const uint8_t* flags_base, const vvcgpu_intra_fill_desc* fill, vvc_pel* refs_base,
+    const vvc_pel* luma_base, const vvc_pel* org_base, const vvcgpu_intra_chroma_pu* pus, const vvcgpu_inter_resi_dq* dq, int n,
+    const int32_t* runs_host, int n_runs,
+    const struct vvcgpu_dq_rates* rates, int n_rates, int quantiser,
+    vvc_pel* pred_base, vvc_pel* cand_rec_base, vvc_coef* level_base, size_t level_extent,
+    int flags, int bit_depth, int clp_min, int clp_max,
+    uint32_t* abs_sum, uint64_t* dist, void* ws, size_t ws_bytes, void* stream);
 
 /* N4, CCLM: cross-component linear model prediction of a chroma block  (IntraPrediction::xGetLumaRecPixels :1283-1581, the
  * JVET_K0190 branch, + xGetLMParameters :1597-1857 + predIntraChromaLM :390-403).  4:2:0 only.  luma_off: the co-located luma

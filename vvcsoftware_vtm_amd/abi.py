@@ -84,6 +84,7 @@ INTRA_CHROMA_PU = np.dtype([("org_off", "<i8", (2,)), ("ref_off", "<i8", (2,)), 
                             ("left_avail", "i1"), ("intra_slice", "i1"), ("sign_hiding", "i1"), ("mode", "i1", (6,)), ("reserved", "<i2"),
                             ("reserved2", "<i4", (2,))])
 INTRA_CHROMA_LM, INTRA_CHROMA_WRITE_PRED = 67, 1
+INTRA_CHROMA_Q_DEPQUANT = 1                                                 # vvcgpu_intra_chroma_code_dq_batch: the served quantiser
 
 # ---- quantisers ---------------------------------------------------------------------------------------------------------------
 QUANT_DESC = np.dtype([("coeff_off", "<i8"), ("level_off", "<i8"), ("w", "<i2"), ("h", "<i2"), ("intra_slice", "i1"), ("sign_hiding", "i1"),

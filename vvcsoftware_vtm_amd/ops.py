@@ -9,7 +9,7 @@ import torch
 from . import capi
 # the struct mirrors live in abi; bench.py, the tests and the tools read them as ops.<NAME>
 from .abi import (AFE_DESC, AFFINE_ITER, AFFINE_ME_ITEM, AFFINE_ME_MAX_STEPS, AFFINE_ME_RESULT, AFFINE_ME_STEP, AFFINE_PU, AFG_DESC, CCLM_DESC, DEPQUANT_DESC, DIST_DESC, DQ_RATES, DQTR_DESC, FRAC_BLK,  # noqa: F401
-                  FRAC_RESULT, IF_DESC, IMV_PU, IMV_RESULT, INTER_RESI_DQ, INTER_RESI_ITEM, INTER_RESI_Q_DEPQUANT, INTER_RESI_SLOTS, INTER_RESI_TS, INTER_RESI_WRITE_REC, INTRA_DESC, INTRA_FILL_DESC, INTRA_SATD_DESC, INTRA_CHROMA_LM, INTRA_CHROMA_PU, INTRA_CHROMA_WRITE_PRED, INTRA_TU_FROM_LIST, INTRA_TU_NO_SMOOTHING, INTRA_TU_PRED_GIVEN, INTRA_TU_Q_DEPQUANT, INTRA_TU_WRITE_PRED, MC_DESC, PELOP_DESC, QUANT_DESC, RC_DESC,
+                  FRAC_RESULT, IF_DESC, IMV_PU, IMV_RESULT, INTER_RESI_DQ, INTER_RESI_ITEM, INTER_RESI_Q_DEPQUANT, INTER_RESI_SLOTS, INTER_RESI_TS, INTER_RESI_WRITE_REC, INTRA_DESC, INTRA_FILL_DESC, INTRA_SATD_DESC, INTRA_CHROMA_LM, INTRA_CHROMA_PU, INTRA_CHROMA_Q_DEPQUANT, INTRA_CHROMA_WRITE_PRED, INTRA_TU_FROM_LIST, INTRA_TU_NO_SMOOTHING, INTRA_TU_PRED_GIVEN, INTRA_TU_Q_DEPQUANT, INTRA_TU_WRITE_PRED, MC_DESC, PELOP_DESC, QUANT_DESC, RC_DESC,
                   RDOQ_DESC, RDOQ_RATES, RDPCM_DESC, SAO_DTYPE, SEARCH_BEST, SEARCH_BLK, TR_DESC, TZ_CFG, TZ_PU, DeblockCfg, MeHierCfg, MvCost,
                   PelopCfg, Planes, AffineMeCfg, BipredMeCfg, BIPRED_ME_ITEM, BIPRED_ME_MAX_PLANES, BIPRED_ME_MAX_REFS, BIPRED_ME_MAX_STEPS, BIPRED_ME_REF,
                   BIPRED_ME_RESULT, BIPRED_ME_STEP, AffineBipredCfg, AFFINE_BIPRED_ITEM, AFFINE_BIPRED_MAX_REFS, AFFINE_BIPRED_MAX_STEPS,
@@ -322,6 +322,32 @@ def intra_chroma_code_batch(org_base, pus_dev, n, runs, cand_rec_base, level_bas
     capi.call("vvcgpu_intra_chroma_code_batch", capi.ptr(rec), capi.ptr(flg), capi.ptr(fd), capi.ptr(refs_base), capi.ptr(luma_base), capi.ptr(org_base),
               capi.ptr(pus_dev), n, r.ctypes.data_as(C.c_void_p), len(r), capi.ptr(pred_base), capi.ptr(cand_rec_base), capi.ptr(level_base), flags,
               bit_depth, clp[0], clp[1], capi.ptr(abs_sum), capi.ptr(dist), _stream())
+    return abs_sum, dist
+
+
+def intra_chroma_code_dq_workspace(level_extent, n, device="cuda"):
+    """a workspace for intra_chroma_code_dq_batch (vvcgpu_intra_chroma_code_dq_workspace_bytes); its contents never matter"""
+    return torch.empty(capi.lib().vvcgpu_intra_chroma_code_dq_workspace_bytes(level_extent, n), dtype=torch.uint8, device=device)
+
+
+def intra_chroma_code_dq_batch(org_base, pus_dev, dq_dev, n, runs, rates_dev, n_rates, cand_rec_base, level_base, refs_base=None, fill=None, luma_base=None,
+                               pred_base=None, flags=0, bit_depth=10, clp=(0, 1023), ws=None, quantiser=INTRA_CHROMA_Q_DEPQUANT):
+    """the intra chroma mode pass with the DepQuant trellis (vvcgpu_intra_chroma_code_dq_batch): as intra_chroma_code_batch, with dq_dev a device copy of an
+    INTER_RESI_DQ array, three per PU (Cb; Cr behind a Cb block without a level; Cr behind one with a level), rates_dev one of a DQ_RATES array of n_rates
+    tables, ws a workspace of intra_chroma_code_dq_workspace for level_base's extent (allocated here when None).
+    -> (abs_sum int32 [n][6][2] (bits as uint32), dist int64 [n][6][2] (bits as uint64))"""
+    dv = org_base.device
+    extent = int(level_base.numel())
+    if ws is None:
+        ws = intra_chroma_code_dq_workspace(extent, n, dv)
+    abs_sum = torch.empty((n, 6, 2), dtype=torch.int32, device=dv)         # every entry is written by the library
+    dist = torch.empty((n, 6, 2), dtype=torch.int64, device=dv)
+    r = np.ascontiguousarray(np.asarray(runs, np.int32).reshape(-1, 3))
+    rec, flg, fd = fill if fill is not None else (None, None, None)
+    capi.call("vvcgpu_intra_chroma_code_dq_batch", capi.ptr(rec), capi.ptr(flg), capi.ptr(fd), capi.ptr(refs_base), capi.ptr(luma_base), capi.ptr(org_base),
+              capi.ptr(pus_dev), capi.ptr(dq_dev), n, r.ctypes.data_as(C.c_void_p), len(r), capi.ptr(rates_dev), n_rates, quantiser, capi.ptr(pred_base),
+              capi.ptr(cand_rec_base), capi.ptr(level_base), C.c_size_t(extent), flags, bit_depth, clp[0], clp[1], capi.ptr(abs_sum), capi.ptr(dist),
+              capi.ptr(ws), C.c_size_t(ws.numel()), _stream())
     return abs_sum, dist
 
 
