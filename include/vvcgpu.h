@@ -1236,6 +1236,95 @@ int vvcgpu_inter_resi_code_dq_batch(const vvc_pel* org_base, const vvc_pel* pred
                                     uint32_t* abs_sum, uint64_t* dist_resi, uint64_t* dist_rec, uint64_t* zero_dist,
                                     void* ws, size_t ws_bytes, void* stream);
 
+/* ---- the rate half of the RD loops: CABACWriter::residual_coding under the bit estimator, for n level blocks in one launch ----
+ * What getEstFracBits() returns after `getCtx() = ctxStart; resetBits(); residual_coding(tu, compID)` (InterSearch.cpp:4380-4381, :4490-4492;
+ * IntraSearch.cpp xGetIntraFracBitsQT) on a BitEstimator_Std, for every level block that the RD pass entries above leave in level_base:
+ *   residual_coding EncoderLib/CABACWriter.cpp:1970-2087 (HEVC_TOOLS 0, JVET_K0072, JVET_K1000_SIMPLIFIED_EMT, ENABLE_BMS: one scan, diagonal in 4x4
+ *               groups, 2x2 groups when a side is 2), transform_skip_flag :2090-2103, emt_tu_index :2106-2133, last_sig_coeff :2202-2255,
+ *               residual_coding_subblock :2260-2383 (group flag; sig / par / gt1; gt2; Go-Rice remainders; signs with hideSign, SBH_THRESHOLD 4);
+ *   the context of every bin: CoeffCodingContext CommonLib/ContextModelling.cpp:217-393 (rectCUs: the luma prefix_ctx table, the chroma
+ *               Clip3(0, 2, side >> 3) shifts), sigCtxIdAbs / ctxOffsetAbs / GoRiceParAbs ContextModelling.h:135-220 -- the offset of an inferred
+ *               significance is the one ctxOffsetAbs finds left over from the position coded before it, as in the reference;
+ *   the estimator: b += m_EstFracBits[state ^ bin]; state = m_NextState[state][bin] per context (Contexts.h:91-96, BinEncoder.h:300), whole bits
+ *               for bypass bins (BinEncoder.h:266-267), encodeRemAbsEP with useLimitedPrefixLength false (BinEncoder.cpp:452-503).
+ * The bins and their contexts depend on the levels alone, the fractional bits are a sum, and only bins of ONE context are ordered: one wavefront
+ * takes an item, lays the levels into LDS, finds every position's bins and context offsets with its lanes as scan positions, and walks them with
+ * its lanes as contexts.  One launch, no host synchronisation; behind an RD pass on the same stream with gate = that pass' abs_sum, nothing is
+ * downloaded between the two.
+ *
+ * items[i]     level_off: the w h levels of the block in level_base, row-major with pitch w -- what the RD passes write at level_off + k w h.
+ *              ctx_idx: the row of ctx.  w, h: powers of two 2..64.  luma: channel type.  dep_quant: stateTab 32040 or 0 (:2034).  sign_hiding:
+ *              cctx.hideSign.  ts_flag: -1 no transform_skip_flag bin, 0 / 1 the bin of that value (the host decides presence, :2093).
+ *              emt_idx: -1 none, 0..3 the emt_tu_index; emt_inter: context pair 2, 3 instead of 0, 1; emt_thr: 1 codes the two bins only when
+ *              numSig > g_EmtSigNumThr (the intra rule :2070-2079), 0 always (the inter rule).  reserved: 0.
+ * gate         may be NULL; gate[i] == 0xFFFFFFFF (the skip marker of the RD passes' abs_sum) skips item i.
+ * ctx          n_ctx rows of VVCGPU_RESI_RATE_CTX_BYTES bytes, device: the BinProbModel_Std states (getState()) of one (snapshot, channel type) at
+ *              the offsets below, a chroma row from the shorter chroma sets; shim/vtm_rates.h (vtmref_resi_ctx_row) fills one.
+ * est_bits     128 words, device: ProbModelTables::m_EstFracBits.  next_state: 256 bytes, device: m_NextState[s][bin] at 2 s + bin.  They are the
+ *              reference's data, handed in as the quantisers' rate tables are (shim/vtm_rates.h: vtmref_cabac_model).
+ * Outputs per item: frac_bits[i] as above; num_sig[i], the count of non-zero levels (numSig of :2056); ctx_out (may be NULL), row i: the item's
+ * row after its block, for the copy of the winner (the re-walk of InterSearch.cpp:4607-4624).  A block without a level returns 0 and 0 and its row
+ * unchanged: the reference never codes one, and the cbf bin is the caller's (vvcgpu_inter_resi_choose_batch takes its bits).
+ * A skipped item has frac_bits = ~0, num_sig = 0xFFFFFFFF and its ctx_out row untouched: gate[i] == 0xFFFFFFFF, a side outside 2..64 or not a power
+ * of two, ctx_idx outside [0, n_ctx), a negative level_off, a flag field out of range or a reserved byte that is not 0.  |level| <= 32767 (larger
+ * values are outside the contract and are clamped).  Offsets cannot be validated; an item outside the contract is never a fault.
+ * VVCGPU_E_ARG before any device work: a null required pointer (gate and ctx_out may be NULL), negative n, n_ctx < 1, an item array that is not
+ * 8-byte aligned.  n == 0 is a no-op.
+ * With the caller: the cbf and header bins, the context snapshot (one row per channel type), the copy of the winner's row.                        */
+#define VVCGPU_RESI_RATE_CTX_BYTES   192
+#define VVCGPU_RESI_RATE_LAST_X      0     /* 25: Ctx::LastX[chType] */
+#define VVCGPU_RESI_RATE_LAST_Y      25    /* 25: Ctx::LastY[chType] */
+#define VVCGPU_RESI_RATE_SIG_GROUP   50    /* 2: Ctx::SigCoeffGroup[chType] */
+#define VVCGPU_RESI_RATE_SIG         52    /* 3 x 20: Ctx::SigFlag[chType + 0 / 2 / 4] */
+#define VVCGPU_RESI_RATE_PAR         112   /* 21: Ctx::ParFlag[chType] */
+#define VVCGPU_RESI_RATE_GT2         133   /* 21: Ctx::GtxFlag[chType] */
+#define VVCGPU_RESI_RATE_GT1         154   /* 21: Ctx::GtxFlag[chType + 2] */
+#define VVCGPU_RESI_RATE_TS          175   /* 1: Ctx::TransformSkipFlag(chType) */
+#define VVCGPU_RESI_RATE_EMT         176   /* 4: Ctx::EMTTuIndex */
+#define VVCGPU_RESI_RATE_CTX_USED    180   /* zero padding from here */
+struct vvcgpu_resi_rate_item {
+  int64_t level_off;                       /* levels from level_base */
+  int32_t ctx_idx;                         /* row of ctx */
+  int16_t w, h;
+  int8_t  luma, dep_quant, sign_hiding;
+  int8_t  ts_flag;                         /* -1 none, 0 / 1 */
+  int8_t  emt_idx;                         /* -1 none, 0..3 */
+  int8_t  emt_inter, emt_thr;
+  int8_t  reserved[9];                     /* sizeof == 32 */
+};
+int vvcgpu_resi_rate_batch(const vvc_coef* level_base, const struct vvcgpu_resi_rate_item* items, int n,
+                           const uint32_t* gate,                         /* may be NULL */
+                           const uint8_t* ctx, int n_ctx, const uint32_t* est_bits, const uint8_t* next_state,
+                           uint64_t* frac_bits, uint32_t* num_sig,
+                           uint8_t* ctx_out,                             /* may be NULL */
+                           void* stream);
+
+/* ---- the compare of xEstimateInterResidualQT (InterSearch.cpp:4395-4568) over the outputs of the two calls before it ----
+ * Third call of the chain vvcgpu_inter_resi_code_batch / _dq_batch -> vvcgpu_resi_rate_batch (items 6 i + k on the levels at level_off + k w h,
+ * gate = abs_sum) -> this one: every input is a device array, so nothing is downloaded before the winner is known.  For item i, with
+ * D(x) = (uint64_t)(dist_weight[i] * (double)x) (RdCost::getDistPart :406-409; 1.0 for luma), cost(d, b) = dist_scale * (double)d + (double)b
+ * (RdCost::calcRdCost, a multiply then an add) and p the cbf of the Cb item of a Cr item (prev[i], else 0):
+ *   nonCoeffDist = D(zero_dist[i]), nonCoeffBits = cbf_bits[4 i + 2 p], nonCoeffCost = cost(nonCoeffDist, nonCoeffBits)             :4424-4455
+ *   the slots in ascending order: abs_sum > 0: bits = cbf_bits[4 i + 2 p + 1] + frac_bits[6 i + k], dist = D(dist_resi[6 i + k]), cbf 1  :4463-4509;
+ *               abs_sum == 0 on the transform-skip slot: cost DBL_MAX, bits and dist 0 (:4517-4520); else the non-coefficient triple, cbf 0;
+ *   a slot is taken when cost < min, or when it is the transform-skip slot and cost == min (:4531);
+ *   on slot 0 the forced null when nonCoeffCost < cost or abs_sum == 0: abs_sum 0, cbf 0, the non-coefficient triple (:4534-4544).
+ * A slot is a candidate when tr[k] is not -1, abs_sum[6 i + k] is not 0xFFFFFFFF and, with abs_sum > 0, frac_bits[6 i + k] is not ~0; other
+ * slots are passed over.  prev[i]: the index of the Cb item of a Cr item, else -1; the thread of a Cr item re-derives the Cb decision itself (with
+ * p = 0), so items need no order.
+ * Outputs per item: slot (the winner), cbf (0 after a forced null), abs_sum_out, dist, bits, min_cost.  An item comes back as slot -1 (cbf 0,
+ * abs_sum_out 0xFFFFFFFF, dist and bits ~0, min_cost DBL_MAX) when slot 0 is no candidate, when a transform-skip code is not the last code of tr[]
+ * that is not -1, when zero_dist[i] is ~0, when prev[i] is outside [-1, n) or the item it names comes back as slot -1.
+ * VVCGPU_E_ARG before any device work: a null pointer, negative n, an item array that is not 16-byte aligned.  n == 0 is a no-op.
+ * Not served: lossless (nonCoeffCost = MAX_DOUBLE, :4512) and cross-component prediction.
+ * With the caller: the cbf bins' bits (two contexts' estFracBits per item), the copy of the winner, the root-cbf decision (:4853).               */
+int vvcgpu_inter_resi_choose_batch(const vvcgpu_inter_resi_item* items, int n,
+                                   const uint32_t* abs_sum, const uint64_t* dist_resi, const uint64_t* zero_dist,
+                                   const uint64_t* frac_bits, const uint64_t* cbf_bits, const int32_t* prev,
+                                   const double* dist_weight, double dist_scale,
+                                   int32_t* slot, int32_t* cbf, uint32_t* abs_sum_out, uint64_t* dist, uint64_t* bits, double* min_cost,
+                                   void* stream);
+
 /* ---- N2 ("next" row): integer-sample TZ search of whole PUs, on the device  (InterSearch::xTZSearch,
  *          EncoderLib/InterSearch.cpp:1971-2252, with xTZSearchHelp :249-343, xTZ2PointSearch :349-374,
  *          xTZ8PointDiamondSearch :431-632, xSetSearchRange :1820-1883, clipMv CommonLib/Mv.cpp:64-80) -----------------

@@ -137,6 +137,12 @@ INTER_RESI_SLOTS, INTER_RESI_TS, INTER_RESI_WRITE_REC = 6, 9, 1
 # vvcgpu_inter_resi_code_dq_batch: the record beside an item (vvcgpu_inter_resi_dq) and the served value of `quantiser`
 INTER_RESI_DQ = np.dtype([("lambda", "<f8"), ("rates_idx", "<i4"), ("luma", "i1"), ("reserved", "i1", (3,))])
 INTER_RESI_Q_DEPQUANT = 1
+# vvcgpu_resi_rate_batch: one level block (struct vvcgpu_resi_rate_item), the bytes of a context row and the offsets of its regions
+RESI_RATE_ITEM = np.dtype([("level_off", "<i8"), ("ctx_idx", "<i4"), ("w", "<i2"), ("h", "<i2"), ("luma", "i1"), ("dep_quant", "i1"),
+                           ("sign_hiding", "i1"), ("ts_flag", "i1"), ("emt_idx", "i1"), ("emt_inter", "i1"), ("emt_thr", "i1"), ("reserved", "i1", (9,))])
+RESI_RATE_CTX_BYTES, RESI_RATE_CTX_USED = 192, 180
+RESI_RATE_LAST_X, RESI_RATE_LAST_Y, RESI_RATE_SIG_GROUP, RESI_RATE_SIG, RESI_RATE_PAR = 0, 25, 50, 52, 112
+RESI_RATE_GT2, RESI_RATE_GT1, RESI_RATE_TS, RESI_RATE_EMT = 133, 154, 175, 176
 
 # ---- affine motion --------------------------------------------------------------------------------------------------------------
 AFG_DESC = np.dtype([("pred_off", "<i8"), ("deriv_off", "<i8"), ("pred_stride", "<i4"), ("deriv_stride", "<i4"), ("w", "<i2"), ("h", "<i2"),

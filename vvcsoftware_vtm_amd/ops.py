@@ -9,7 +9,7 @@ import torch
 from . import capi
 # the struct mirrors live in abi; bench.py, the tests and the tools read them as ops.<NAME>
 from .abi import (AFE_DESC, AFFINE_ITER, AFFINE_ME_ITEM, AFFINE_ME_MAX_STEPS, AFFINE_ME_RESULT, AFFINE_ME_STEP, AFFINE_PU, AFG_DESC, CCLM_DESC, DEPQUANT_DESC, DIST_DESC, DQ_RATES, DQTR_DESC, FRAC_BLK,  # noqa: F401
-                  FRAC_RESULT, IF_DESC, IMV_PU, IMV_RESULT, INTER_RESI_DQ, INTER_RESI_ITEM, INTER_RESI_Q_DEPQUANT, INTER_RESI_SLOTS, INTER_RESI_TS, INTER_RESI_WRITE_REC, INTRA_DESC, INTRA_FILL_DESC, INTRA_SATD_DESC, INTRA_CHROMA_LM, INTRA_CHROMA_PU, INTRA_CHROMA_Q_DEPQUANT, INTRA_CHROMA_WRITE_PRED, INTRA_TU_FROM_LIST, INTRA_TU_NO_SMOOTHING, INTRA_TU_PRED_GIVEN, INTRA_TU_Q_DEPQUANT, INTRA_TU_WRITE_PRED, MC_DESC, PELOP_DESC, QUANT_DESC, RC_DESC,
+                  FRAC_RESULT, IF_DESC, IMV_PU, IMV_RESULT, INTER_RESI_DQ, INTER_RESI_ITEM, INTER_RESI_Q_DEPQUANT, INTER_RESI_SLOTS, INTER_RESI_TS, INTER_RESI_WRITE_REC, INTRA_DESC, INTRA_FILL_DESC, INTRA_SATD_DESC, INTRA_CHROMA_LM, INTRA_CHROMA_PU, INTRA_CHROMA_Q_DEPQUANT, INTRA_CHROMA_WRITE_PRED, INTRA_TU_FROM_LIST, INTRA_TU_NO_SMOOTHING, INTRA_TU_PRED_GIVEN, INTRA_TU_Q_DEPQUANT, INTRA_TU_WRITE_PRED, MC_DESC, PELOP_DESC, QUANT_DESC, RC_DESC, RESI_RATE_CTX_BYTES, RESI_RATE_ITEM,
                   RDOQ_DESC, RDOQ_RATES, RDPCM_DESC, SAO_DTYPE, SEARCH_BEST, SEARCH_BLK, TR_DESC, TZ_CFG, TZ_PU, DeblockCfg, MeHierCfg, MvCost,
                   PelopCfg, Planes, AffineMeCfg, BipredMeCfg, BIPRED_ME_ITEM, BIPRED_ME_MAX_PLANES, BIPRED_ME_MAX_REFS, BIPRED_ME_MAX_STEPS, BIPRED_ME_REF,
                   BIPRED_ME_RESULT, BIPRED_ME_STEP, AffineBipredCfg, AFFINE_BIPRED_ITEM, AFFINE_BIPRED_MAX_REFS, AFFINE_BIPRED_MAX_STEPS,
@@ -389,6 +389,36 @@ def inter_resi_code_dq_batch(org_base, pred_base, items_dev, dq_dev, n, rates_de
               capi.ptr(rates_dev), n_rates, quantiser, capi.ptr(resi_base), capi.ptr(rec_base), capi.ptr(level_base), C.c_size_t(extent), flags, bit_depth,
               clp[0], clp[1], capi.ptr(abs_sum), capi.ptr(dist_resi), capi.ptr(dist_rec), capi.ptr(zero_dist), capi.ptr(ws), C.c_size_t(ws.numel()), _stream())
     return abs_sum, dist_resi, dist_rec, zero_dist
+
+
+def resi_rate_batch(level_base, items_dev, n, ctx, est_bits, next_state, gate=None, ctx_out=None):
+    """the CABAC rate of residual_coding for n level blocks (vvcgpu_resi_rate_batch): items_dev a device copy of a RESI_RATE_ITEM array, ctx a uint8
+    [n_ctx][RESI_RATE_CTX_BYTES] tensor of context rows, est_bits int32 [128] and next_state uint8 [256] the reference's two model tables, gate the
+    abs_sum tensor of an RD pass (0xFFFFFFFF skips the item) or None, ctx_out a uint8 [n][RESI_RATE_CTX_BYTES] tensor for the rows after the blocks (the
+    rows of skipped items stay as they are) or None.
+    -> (frac_bits int64 [n] (bits as uint64), num_sig int32 [n] (bits as uint32))"""
+    dv = level_base.device
+    assert ctx.dtype == torch.uint8 and ctx.dim() == 2 and ctx.shape[1] == RESI_RATE_CTX_BYTES and ctx.is_contiguous()
+    frac_bits = torch.empty(n, dtype=torch.int64, device=dv)                # every entry is written by the library
+    num_sig = torch.empty(n, dtype=torch.int32, device=dv)
+    assert ctx_out is None or (ctx_out.dtype == torch.uint8 and ctx_out.numel() == n * RESI_RATE_CTX_BYTES and ctx_out.is_contiguous())
+    capi.call("vvcgpu_resi_rate_batch", capi.ptr(level_base), capi.ptr(items_dev), n, capi.ptr(gate), capi.ptr(ctx), int(ctx.shape[0]), capi.ptr(est_bits),
+              capi.ptr(next_state), capi.ptr(frac_bits), capi.ptr(num_sig), capi.ptr(ctx_out), _stream())
+    return frac_bits, num_sig
+
+
+def inter_resi_choose_batch(items_dev, n, abs_sum, dist_resi, zero_dist, frac_bits, cbf_bits, prev, dist_weight, dist_scale):
+    """the compare of xEstimateInterResidualQT (vvcgpu_inter_resi_choose_batch) over the outputs of inter_resi_code_batch / _dq_batch (items_dev, abs_sum,
+    dist_resi, zero_dist) and of resi_rate_batch (frac_bits [6 n]); cbf_bits int64 [n][4], prev int32 [n], dist_weight float64 [n], all on the device.
+    -> (slot, cbf int32 [n], abs_sum int32 [n] (bits as uint32), dist, bits int64 [n] (bits as uint64), min_cost float64 [n])"""
+    dv = abs_sum.device
+    slot, cbf, abs_out = (torch.empty(n, dtype=torch.int32, device=dv) for _ in range(3))
+    dist, bits = (torch.empty(n, dtype=torch.int64, device=dv) for _ in range(2))
+    min_cost = torch.empty(n, dtype=torch.float64, device=dv)
+    capi.call("vvcgpu_inter_resi_choose_batch", capi.ptr(items_dev), n, capi.ptr(abs_sum), capi.ptr(dist_resi), capi.ptr(zero_dist), capi.ptr(frac_bits),
+              capi.ptr(cbf_bits), capi.ptr(prev), capi.ptr(dist_weight), C.c_double(dist_scale), capi.ptr(slot), capi.ptr(cbf), capi.ptr(abs_out),
+              capi.ptr(dist), capi.ptr(bits), capi.ptr(min_cost), _stream())
+    return slot, cbf, abs_out, dist, bits, min_cost
 
 
 def imv_refine_batch(org, ref, pus_dev, n, cfg, use_hadamard=True, weight=1.0):

@@ -91,3 +91,41 @@ inline void vtmref_rdoq_rates_from_ctx(const TransformUnit& tu, ComponentID comp
     o[id] = bits;
   }
 }
+
+// ---------------------------------------------------------------------------------------------
+// vvcgpu_resi_rate_batch: one context row -- the BinProbModel_Std states (getState()) of the contexts CABACWriter::residual_coding touches for one
+// channel type, at the VVCGPU_RESI_RATE_* offsets; a chroma row is filled from the (shorter) chroma sets, the rest of a region stays zero.
+inline void vtmref_resi_ctx_row(const Ctx& ctx, ChannelType chType, uint8_t row[VVCGPU_RESI_RATE_CTX_BYTES])
+{
+  const CtxStore<BinProbModel_Std>& store = static_cast<const CtxStore<BinProbModel_Std>&>(ctx);
+  memset(row, 0, VVCGPU_RESI_RATE_CTX_BYTES);
+  auto put = [&](int at, const CtxSet& set) { for (unsigned c = 0; c < set.Size; c++) row[at + c] = (uint8_t)store[set(c)].getState(); };
+  put(VVCGPU_RESI_RATE_LAST_X, Ctx::LastX[chType]);
+  put(VVCGPU_RESI_RATE_LAST_Y, Ctx::LastY[chType]);
+  put(VVCGPU_RESI_RATE_SIG_GROUP, Ctx::SigCoeffGroup[chType]);
+  for (int s = 0; s < 3; s++) put(VVCGPU_RESI_RATE_SIG + 20 * s, Ctx::SigFlag[chType + 2 * s]);
+  put(VVCGPU_RESI_RATE_PAR, Ctx::ParFlag[chType]);
+  put(VVCGPU_RESI_RATE_GT2, Ctx::GtxFlag[chType]);
+  put(VVCGPU_RESI_RATE_GT1, Ctx::GtxFlag[chType + 2]);
+  row[VVCGPU_RESI_RATE_TS] = (uint8_t)store[Ctx::TransformSkipFlag(chType)].getState();
+  put(VVCGPU_RESI_RATE_EMT, Ctx::EMTTuIndex);
+}
+
+// the two tables of the estimator's probability model, m_EstFracBits[128] and m_NextState[s][bin] at 2 s + bin, through the public interface of
+// BinProbModel_Std (the tables themselves are protected)
+inline void vtmref_cabac_model(uint32_t est[128], uint8_t next[256])
+{
+  for (unsigned s = 0; s < 128; s++)
+  {
+    BinProbModel_Std m;
+    m.setState((uint16_t)s);
+    est[s] = m.estFracBits(0);                                                       // m_EstFracBits[s ^ 0]
+    for (unsigned bin = 0; bin < 2; bin++)
+    {
+      BinProbModel_Std u;
+      u.setState((uint16_t)s);
+      u.update(bin);
+      next[2 * s + bin] = (uint8_t)u.getState();
+    }
+  }
+}
