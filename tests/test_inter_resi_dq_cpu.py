@@ -83,6 +83,9 @@ def test_argument_errors_come_before_any_device_work():
     # the workspace: coefficients, decisions and histories by the level extent (4 + 16 + 8 bytes each, the extent rounded up to 16), a record and a work-list entry per slot
     f = lib.vvcgpu_inter_resi_code_dq_workspace_bytes
     assert f(160, 0) - f(16, 0) == 144 * 28 and f(17, 3) == f(32, 3) and f(32, 4) - f(32, 3) == 6 * (40 + 4)
+    # absolutely: 16 * 28 and the slack of 4096 * 4 + 256; further pairs as the library gave them before the layout was stated once (dqpass_dev.h)
+    assert f(16, 0) == 16 * 28 + 16640 == 17088
+    assert [f(e, n) for e, n in ((17, 3), (33, -2), (1000, 5), (4096, 3), (65551, 7), (100000, 1000))] == [18328, 17984, 46184, 132120, 1853944, 3080640]
     assert call(ws_bytes=f(1024, 3) - 1) == -1
     for q in (0, 2, -1):                                                     # a quantiser other than the served one
         assert call(quantiser=q) == -3, q

@@ -79,6 +79,9 @@ def test_argument_errors_come_before_any_device_work():
         assert call(quantiser=q) == -3 and b"intra_chroma_code_dq_batch" in lib.vvcgpu_last_error()
     f = lib.vvcgpu_intra_chroma_code_dq_workspace_bytes
     assert f(160, 0) - f(16, 0) == 144 * 30 and f(17, 3) == f(32, 3) and f(32, 4) - f(32, 3) == 12 * (40 + 4) and f(16, -1) == f(16, 0)
+    # absolutely: 16 * 30 and the slack of 4096 * 4 + 256; further pairs as the library gave them before the layout was stated once (dqpass_dev.h)
+    assert f(16, 0) == 16 * 30 + 16640 == 17120
+    assert [f(e, n) for e, n in ((17, 3), (33, -2), (1000, 5), (4096, 3), (65551, 7), (100000, 1000))] == [19184, 18080, 49520, 141104, 1986896, 3544640]
     assert call(ws_bytes=f(4096, 3) - 1) == -1 and call(extent=4097, ws_bytes=f(4096, 3)) == -1
 
 

@@ -135,6 +135,9 @@ def test_argument_errors_come_before_any_device_work():
     # and a work-list entry per item
     f = lib.vvcgpu_intra_tu_code_dq_workspace_bytes
     assert f(160, 0) - f(16, 0) == 144 * 30 and f(17, 3) == f(32, 3) and f(32, 4) - f(32, 3) == 40 + 4
+    # absolutely: 16 * 30 and the slack of 4096 * 4 + 256; further pairs as the library gave them before the layout was stated once (dqpass_dev.h)
+    assert f(16, 0) == 16 * 30 + 16640 == 17120
+    assert [f(e, n) for e, n in ((17, 3), (33, -2), (1000, 5), (4096, 3), (65551, 7), (100000, 1000))] == [17732, 18080, 47100, 139652, 1983508, 3060640]
     assert call(ws_bytes=f(1024, 3) - 1) == -1
     for q in (0, 2, -1):                                                     # a quantiser other than the served one
         assert call(quantiser=q) == -3, q

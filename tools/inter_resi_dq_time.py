@@ -9,7 +9,7 @@ tables of tests/golden/depquant.npz, one per item in turn.
 The results of (a) and (b) are compared before anything is timed.  Times: device events around a whole run on the stream, 3 warm-up runs, then the median
 and the spread of 9 runs, (a) and (b) alternating in one process.
 --profile: no timing, five runs of (b) per list -- the run to put under `rocprofv3 --kernel-trace --stats` for the split into inter_resi_dq_front_kernel,
-inter_resi_dq_trellis_kernel and inter_resi_dq_back_kernel.
+depquant_listed_kernel (the trellis launch that the DepQuant entries share, depquant.hip) and inter_resi_dq_back_kernel.
 The planes, build and the loop over the lists are the sibling's; the lists and the row come from tests/rd_pass_kit.py."""
 import os
 import sys

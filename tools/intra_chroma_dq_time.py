@@ -7,7 +7,9 @@ records per PU: lambdas 60 / 90 / 700 and tables of tests/golden/depquant.npz in
       Cr -- the download and the host work are inside the timed part: that is what the entry replaces;
   (b) vvcgpu_intra_chroma_code_dq_batch: references gathered inside, not written; no prediction written; its workspace allocated outside the timed part.
 The results of (a) and (b) are compared before anything is timed.  Times: device events around a whole run on the stream, 3 warm-up runs, then the median and
-the spread of 9 runs, (a) and (b) alternating in one process.  --profile: three runs of (b) per list and nothing else, for a kernel trace."""
+the spread of 9 runs, (a) and (b) alternating in one process.  --profile: three runs of (b) per list and nothing else, for a kernel trace
+(chroma_dq_front_kernel, depquant_listed_kernel twice -- the trellis launch that the DepQuant entries share, depquant.hip --, chroma_dq_select_kernel between
+them, chroma_dq_back_kernel)."""
 import os
 import sys
 

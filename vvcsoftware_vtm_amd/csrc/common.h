@@ -72,6 +72,13 @@ int vvcgpu_raster_per_block_launch(const vvc_pel* org, int org_stride, const vvc
 // code is compiled per source, so the kernels of every other source (resichain.hip, quant.hip, depquant.hip, rdoq.hip) take this struct as an argument.
 struct VvcTrTables { const int* tr32; const int* tr32t; const unsigned short* scan; const unsigned short* dqInv; const int* scanOff; const uint4* dqPosSel; const uint2* dqPosMisc; };
 int vvcgpu_tr_tables(VvcTrTables* out);
+// The dependent-quantisation trellis over a work list (depquant.hip, for the RD pass entries under DepQuant 1): work item ti is record list[ti], and
+// *count, on the device, is the list's length -- a front kernel of the caller has counted it on a counter set of vvcgpu_counters.  The grid is sized for
+// max_records; workgroups behind the list's end leave at once.  dec, ctx: the trellis' decisions and level histories, indexed as coef is.  Returns
+// VVCGPU_OK or an error code with the text set; a failed launch has reported the caller's counter set itself (vvcgpu_counters_failed).
+int vvcgpu_depquant_listed_launch(const vvc_coef* coef, vvc_coef* level, const vvcgpu_depquant_desc* recs, const int* list, const int* count, int max_records,
+                                  const vvcgpu_dq_rates* rates, int bit_depth, uint32_t* abs_sum, unsigned* dec, unsigned char* ctx, const VvcTrTables& tb,
+                                  hipStream_t stream);
 
 #define VVC_CHECK_ARG(cond, ...)                                   \
   do { if (!(cond)) { vvcgpu_set_error(__VA_ARGS__); return VVCGPU_E_ARG; } } while (0)
@@ -132,6 +139,18 @@ static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 __device__ __forceinline__ int clip3(int lo, int hi, int v) { return min(max(v, lo), hi); }
 __device__ __forceinline__ int sgn(int v) { return (v > 0) - (v < 0); }
 __device__ __forceinline__ int ilog2(int v) { return 31 - __clz(v); }
+// a block side that the RD pass entries serve: a power of two from lo (2 or 4) to 64
+inline __host__ __device__ bool side_ok(int v, int lo) { return v >= lo && v <= 64 && (v & (v - 1)) == 0; }
+
+// A wavefront that owns its work orders its own lanes without a workgroup barrier: wave_sync for what they exchange through LDS, wave_global_sync for
+// stores of the wavefront to global memory that other lanes of it read back.
+__device__ __forceinline__ void wave_sync() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }
+__device__ __forceinline__ void wave_global_sync()
+{
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+}
 
 // 8 Pels = 16 bytes, the coalescing sweet spot for int16 planes (guide G13)
 typedef short pel8 __attribute__((ext_vector_type(8)));

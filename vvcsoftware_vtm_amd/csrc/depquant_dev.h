@@ -1,7 +1,7 @@
 // depquant_dev.h -- the dependent-quantisation trellis, DQIntern::DepQuant::quant (DepQuant.cpp:1323-1391), stated once for its two kernels:
-// depquant_kernel (depquant.hip, vvcgpu_depquant_batch: work item ti is descriptor ti) and inter_resi_dq_trellis_kernel (interresidq.hip,
-// vvcgpu_inter_resi_code_dq_batch: work item ti is descriptor list[ti]).  Here are the types, helpers and constants and the workspace layout; the
-// kernels' body is depquant_body.inc, which each kernel includes under its own signature.
+// depquant_kernel (vvcgpu_depquant_batch: work item ti is descriptor ti) and depquant_listed_kernel (vvcgpu_depquant_listed_launch, the trellis launch of
+// the RD pass entries under DepQuant 1: work item ti is descriptor list[ti]), both in depquant.hip.  Here are the types, helpers and constants and the
+// workspace layout; the kernels' body is depquant_body.inc, which each kernel includes under its own signature.
 // The trellis is a sequential walk down the scan with four states; TUs are independent.  FOUR LANES own one TU, lane k carries
 // trellis state k (its previous-position state and its skip state live in the lane's registers), sixteen TUs share a wavefront.
 // Per scan position: every lane prices the transitions LEAVING its state (two quantisation candidates + zero), the three 64-bit

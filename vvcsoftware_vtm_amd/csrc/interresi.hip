@@ -37,8 +37,6 @@ struct IrArgs
   int n, writeRec, bd, cmin, cmax;
 };
 
-inline __host__ __device__ bool ir_side_ok(int v) { return v >= 2 && v <= 64 && (v & (v - 1)) == 0; }
-
 // the matrix-core body of one shape as a real call (the descriptor and the residual tile are the wavefront's, in LDS)
 template <int W, int H>
 __device__ __noinline__ bool ir_tu_mfma_call(const RcDesc* dS, const Pel* tile, Pel* __restrict__ resiBase, TCoeff* __restrict__ levelBase,
@@ -64,6 +62,7 @@ __global__ __launch_bounds__(IR_THREADS, 1) void inter_resi_code_kernel(const Ir
   _Float16* const tab = reinterpret_cast<_Float16*>(smem);
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   {
+    // (rc_load_image in words: as a call of it the kernel's first instructions come out in another order, docs/MEASUREMENTS.md)
     constexpr int NW4 = IR_TAB_BYTES / 16;                                // (the image holds both table sets back to back)
     const uint4* src = reinterpret_cast<const uint4*>(a.image);
     for (int i = tid; i < NW4; i += IR_THREADS) reinterpret_cast<uint4*>(tab)[i] = src[i];
@@ -84,7 +83,7 @@ __global__ __launch_bounds__(IR_THREADS, 1) void inter_resi_code_kernel(const Ir
     if (item + step < a.n) tNext = a.items[item + step];                  // the next record is on its way while this item runs
     const int w = t.w, h = t.h;
     long long predOff = t.pred_off;
-    bool ok = ir_side_ok(w) && ir_side_ok(h) && (t.cand_off & 3) == 0 && (t.level_off & 3) == 0;
+    bool ok = side_ok(w, 2) && side_ok(h, 2) && (t.cand_off & 3) == 0 && (t.level_off & 3) == 0;
     // (the guard is ir_list_pred's own, repeated: without it the kernel compiles to other code, 520 instructions less -- docs/MEASUREMENTS.md)
     if (ok && t.list_row >= 0) ok = ir_list_pred(ok, a.rdList, t, predOff);
     if (!ok)                                                              // skipped: the markers, nothing else
@@ -140,7 +139,7 @@ __global__ __launch_bounds__(IR_THREADS, 1) void inter_resi_code_kernel(const Ir
       servedMask |= 1u << k;
       if (inGroup) groupMask |= 1u << k;
     }
-    ir_wave_sync();
+    wave_sync();
 
     // the closing loop of slot k of this item, resi' in backK (null: in the slot's candidate buffer)
     auto finish = [&](int k, const short* backK) { ir_finish(a, t, item, k, resiT, predT, predG, backK, lane); };
@@ -156,7 +155,7 @@ __global__ __launch_bounds__(IR_THREADS, 1) void inter_resi_code_kernel(const Ir
       else if (w == 4 && h == 4) rc_small_group<4, RC_RESI>(dS, lst, cnt, 0, resiT, resiT, outBase, a.level, absSumItem, a.bd, 0, 0, *tabs, tmpL, lane);
       else if (w == 8)           rc_rect_group<8, 4, RC_RESI>(dS, lst, cnt, 0, resiT, resiT, outBase, a.level, absSumItem, a.bd, 0, 0, *tabs, tmpL, lane);
       else                       rc_rect_group<4, 8, RC_RESI>(dS, lst, cnt, 0, resiT, resiT, outBase, a.level, absSumItem, a.bd, 0, 0, *tabs, tmpL, lane);
-      ir_wave_sync();
+      wave_sync();
       for (int k = 0; k < IR_SLOTS; k++)
         if ((groupMask >> k) & 1u) finish(k, backT + k * samples);
     }
@@ -177,11 +176,11 @@ __global__ __launch_bounds__(IR_THREADS, 1) void inter_resi_code_kernel(const Ir
 #undef IR_MF
       if (!done)                                                          // samples outside the bit depth (out of contract): exact all the same
         ir_tu_generic_call(dS + k, resiT, outBase, a.level, absSumItem + k, a.bd, tb.tr32, tb.dqInv, tb.scanOff, fbScr, fbScr + 4096, lane);
-      if (backT) ir_wave_sync(); else ir_global_sync();
+      if (backT) wave_sync(); else wave_global_sync();
       finish(k, backT);
-      ir_wave_sync();                                                     // `back` is free again
+      wave_sync();                                                     // `back` is free again
     }
-    ir_wave_sync();                                                       // the tile and the descriptors are free again
+    wave_sync();                                                       // the tile and the descriptors are free again
   }
 }
 

@@ -1,7 +1,7 @@
 // interresi_dev.h -- the item walk of the inter residual passes, InterSearch::encodeResAndCalcRdInterCU (EncoderLib/InterSearch.cpp:4752-4909), stated
 // once for interresi.hip (vvcgpu_inter_resi_code_batch) and interresidq.hip (vvcgpu_inter_resi_code_dq_batch): a wavefront owns an item, stages
 // orgResi = org - pred in its LDS tile, runs the item's slots through transform and quantiser -- that part is each file's own -- and closes every slot
-// with both distortions, resi' and the reconstruction.  Here are the constants of that frame, its two synchronisations, the rd_list look-up, the staging
+// with both distortions, resi' and the reconstruction.  Here are the constants of that frame, the rd_list look-up, the staging
 // loop, the tile layout, the closing loop and the host side the two entries share.  The closing loop takes the kernel's argument struct as a template
 // parameter: the two structs (IrArgs, IqArgs) name the fields it reads alike.
 #pragma once
@@ -17,15 +17,6 @@ constexpr int IR_WAVES = 8, IR_THREADS = 64 * IR_WAVES;
 constexpr int IR_TILE = 64 * 64;                                          // samples of a wavefront's tile: orgResi, the prediction, resi' (ir_tile)
 constexpr int IR_LIST_INTS = 8, IR_LIST_MAX = 7;                          // a row of rd_list_out of vvcgpu_merge_cand_batch: [0] count, [1 .. 7] RdModeList
 constexpr int IR_FB_INTS = 2 * 4096;                                      // global scratch per wavefront: the integer body's two buffers for an item outside the matrix-core range
-
-__device__ __forceinline__ void ir_wave_sync() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }
-// stores of the wavefront to global memory, read back by other lanes of it
-__device__ __forceinline__ void ir_global_sync()
-{
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-}
 
 // The rd_list look-up of an item that has passed the entry's own checks so far (ok): with list_row >= 0 it takes its prediction from the candidate
 // that row list_row of rd_list names at list_slot, and predOff moves on by that candidate's pitch.  -> ok; false also: no list, or the slot or the

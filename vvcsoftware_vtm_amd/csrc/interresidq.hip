@@ -12,7 +12,7 @@
 //            -- the zeroed region of a 64-point side written as zeros: the trellis reads all w h coefficients -- and the slot's trellis record, whose
 //            index 6 i + k it appends to the work list (one atomic add per wavefront on a counter of vvcgpu_counters).  A skipped item or slot gets its
 //            markers here and no list entry.
-//   trellis  the trellis of depquant_dev.h (depquant_body.inc, the body it shares with depquant_kernel, here with the work list in front of the
+//   trellis  the trellis of depquant_dev.h (vvcgpu_depquant_listed_launch of depquant.hip: depquant_kernel's body with the work list in front of the
 //            descriptors) over the listed records: four lanes per TU, sixteen TUs per wavefront; levels and abs_sum of the served slots.  The grid is sized for 6 n records; workgroups behind the list's end leave at once.
 //   back     the same wavefront-per-item walk: orgResi and the prediction re-formed in the tile; per served slot the dependent de-quantiser (the
 //            GF(2)-linear state replay, as dq_group of transform.hip) into the coefficient workspace, the inverse transform (RC_INV bodies), resi'
@@ -25,27 +25,24 @@ static_assert(sizeof(vvcgpu_inter_resi_item) == 80 && sizeof(vvcgpu_inter_resi_d
 
 namespace {
 
-typedef vvcgpu_inter_resi_dq IrDq;
 constexpr int IQ_WAVE_BYTES = IR_TILE * 2 + IR_SLOTS * (int)sizeof(vvcgpu_resi_chain_desc);      // the tile, a chain descriptor per slot
 constexpr int IQ_LDS_BYTES = IQ_TAB_BYTES + IR_WAVES * IQ_WAVE_BYTES;
-static_assert(IQ_TAB_BYTES % 16 == 0 && IQ_WAVE_BYTES % 16 == 0 && IQ_LDS_BYTES <= 160 * 1024, "LDS budget");
+static_assert(IQ_TAB_BYTES % 16 == 0 && IQ_WAVE_BYTES % 16 == 0 && IQ_LDS_BYTES <= 160 * 1024 && IR_FB_INTS == IQ_FB_INTS, "LDS budget");
 
 struct IqArgs
 {
-  const Pel* org; const Pel* pred; const IrItem* items; const IrDq* dq; const int* rdList; Pel* resi; Pel* rec; TCoeff* level;
+  const Pel* org; const Pel* pred; const IrItem* items; const IqDq* dq; const int* rdList; Pel* resi; Pel* rec; TCoeff* level;
   unsigned* absSum; unsigned long long* distResi; unsigned long long* distRec; unsigned long long* zeroDist; int* fbScratch; const _Float16* image;
   TCoeff* coef; vvcgpu_depquant_desc* recs; int* list; int* count; int* nextCounters; long long levelExtent;
   int n, nRates, writeRec, bd, cmin, cmax;
 };
 
-inline __host__ __device__ bool iq_side_ok(int v) { return v >= 4 && v <= 64 && (v & (v - 1)) == 0; }
-
 // is the item served, and where is its prediction?  (the rules of interresi.hip; here also: no side of 2, level_off a multiple of 16 -- the trellis
 // workspace is indexed by it --, a rate table inside the array, a lambda above zero)
-__device__ __forceinline__ bool iq_item_ok(const IqArgs& a, const IrItem& t, const IrDq& q, long long& predOff)
+__device__ __forceinline__ bool iq_item_ok(const IqArgs& a, const IrItem& t, const IqDq& q, long long& predOff)
 {
   predOff = t.pred_off;
-  bool ok = iq_side_ok(t.w) && iq_side_ok(t.h) && (t.cand_off & 3) == 0 && (t.level_off & 15) == 0 && t.level_off >= 0
+  bool ok = side_ok(t.w, 4) && side_ok(t.h, 4) && (t.cand_off & 3) == 0 && (t.level_off & 15) == 0 && t.level_off >= 0
             && q.rates_idx >= 0 && q.rates_idx < a.nRates && q.lambda > 0.0;
   return ir_list_pred(ok, a.rdList, t, predOff);
 }
@@ -84,48 +81,33 @@ __device__ __forceinline__ RcDesc iq_desc(const IrItem& t, int k, long long recO
   return u;
 }
 
-__device__ __forceinline__ _Float16* iq_load_tables(unsigned char* smem, const _Float16* image, int tid)
-{
-  _Float16* const tab = reinterpret_cast<_Float16*>(smem);
-  const uint4* src = reinterpret_cast<const uint4*>(image);
-  for (int i = tid; i < IQ_TAB_BYTES / 16; i += IR_THREADS) reinterpret_cast<uint4*>(tab)[i] = src[i];
-  __syncthreads();                                                        // the only workgroup barrier: below every wavefront walks its own items
-  return tab;
-}
-
 // ---------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(IR_THREADS, 1) void inter_resi_dq_front_kernel(const IqArgs a, const VvcTrTables tb)
 {
   extern __shared__ __align__(16) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const _Float16* const tab = iq_load_tables(smem, a.image, tid);
+  const _Float16* const tab = rc_load_image<IR_THREADS>(smem, a.image, tid);   // below every wavefront walks its own items
   unsigned char* const mine = smem + IQ_TAB_BYTES + (size_t)wave * IQ_WAVE_BYTES;
   short* const resiT = reinterpret_cast<short*>(mine);
   RcDesc* const dS = reinterpret_cast<RcDesc*>(resiT + IR_TILE);
   int* const fbScr = a.fbScratch + ((size_t)blockIdx.x * IR_WAVES + wave) * IR_FB_INTS;
   if (blockIdx.x == 0 && tid < VVC_CTR_INTS) a.nextCounters[tid] = 0;    // the counter set of the NEXT call on this stream (vvcgpu_counters)
 
-  // the wavefront's run in the trellis' work list: its served slots are counted first, a lane per item, so that the counter sees one atomic add per
-  // wavefront (one per item, 94 000 on one address for the 4K list, took 0.9 ms)
+  // the wavefront's run in the trellis' work list: its served slots are counted first, a lane per item
   const int first = (int)blockIdx.x * IR_WAVES + wave, step = (int)gridDim.x * IR_WAVES;
-  int listAt = 0;
+  int cnt = 0;
+  for (int item = first + lane * step; item < a.n; item += 64 * step)
   {
-    int cnt = 0;
-    for (int item = first + lane * step; item < a.n; item += 64 * step)
-    {
-      const IrItem t = a.items[item];
-      long long predOff;
-      if (iq_item_ok(a, t, a.dq[item], predOff)) cnt += __popc(iq_served_mask(a, t));
-    }
-    cnt = wave_sum_i32(cnt);
-    if (cnt && lane == 0) listAt = atomicAdd(a.count, cnt);
-    listAt = __builtin_amdgcn_readfirstlane(listAt);
+    const IrItem t = a.items[item];
+    long long predOff;
+    if (iq_item_ok(a, t, a.dq[item], predOff)) cnt += __popc(iq_served_mask(a, t));
   }
+  int listAt = iq_reserve(a.count, cnt, lane);
 
   for (int item = first; item < a.n; item += step)
   {
     const IrItem t = a.items[item];
-    const IrDq q = a.dq[item];
+    const IqDq q = a.dq[item];
     long long predOff;
     const bool ok = iq_item_ok(a, t, q, predOff);
     const unsigned servedMask = ok ? iq_served_mask(a, t) : 0u;
@@ -134,11 +116,7 @@ __global__ __launch_bounds__(IR_THREADS, 1) void inter_resi_dq_front_kernel(cons
       const size_t out = IR_SLOTS * (size_t)item + lane;
       if ((servedMask >> lane) & 1u)
       {
-        vvcgpu_depquant_desc r;
-        r.coeff_off = r.level_off = t.level_off + (long long)lane * t.w * t.h;
-        r.lambda = q.lambda; r.qp = t.qp; r.rates_idx = q.rates_idx; r.w = t.w; r.h = t.h; r.luma = q.luma;
-        r.reserved[0] = r.reserved[1] = r.reserved[2] = 0;
-        a.recs[out] = r;
+        a.recs[out] = iq_record(t.level_off + (long long)lane * t.w * t.h, t.qp, t.w, t.h, q, q.luma);
         a.list[listAt + __popc(servedMask & ((1u << lane) - 1u))] = (int)out;
       }
       else { a.absSum[out] = 0xFFFFFFFFu; a.distResi[out] = ~0ull; a.distRec[out] = ~0ull; }
@@ -152,34 +130,22 @@ __global__ __launch_bounds__(IR_THREADS, 1) void inter_resi_dq_front_kernel(cons
     const unsigned long long zd = ir_stage(t, a.org + t.org_off, a.pred + predOff, resiT, nullptr, lane);
     if (lane == 0) a.zeroDist[item] = zd;
     if (lane < IR_SLOTS && ((servedMask >> lane) & 1u)) dS[lane] = iq_desc(t, lane, 0);
-    ir_wave_sync();
+    wave_sync();
     for (int k = 0; k < IR_SLOTS; k++)
     {
       if (!((servedMask >> k) & 1u)) continue;
       iq_transform<RC_FWD>(dS + k, resiT, nullptr, a.coef, a.bd, tab, tb, fbScr, lane);
-      ir_wave_sync();
+      wave_sync();
     }
-    ir_wave_sync();                                                       // the tile and the descriptors are free again
+    wave_sync();                                                       // the tile and the descriptors are free again
   }
-}
-
-// the trellis over the work list (iq_trellis of dqpass_dev.h): work item ti is descriptor list[ti]
-__global__ __launch_bounds__(256) void inter_resi_dq_trellis_kernel(const TCoeff* __restrict__ coeffBase, TCoeff* __restrict__ levelBase,
-                                                                    const vvcgpu_depquant_desc* __restrict__ descs, const int* __restrict__ list,
-                                                                    const int* __restrict__ count,
-                                                                    const vvcgpu_dq_rates* __restrict__ ratesBase, int bd, unsigned* __restrict__ absSumOut,
-                                                                    unsigned* __restrict__ wsDec, unsigned char* __restrict__ wsCtx, VvcTrTables tb)
-{
-  const int n = *count;                                                   // the served slots of the call, counted by the front
-  if ((int)blockIdx.x * 64 >= n) return;
-  iq_trellis<true>(coeffBase, levelBase, descs, list, n, ratesBase, bd, absSumOut, wsDec, wsCtx, tb);
 }
 
 __global__ __launch_bounds__(IR_THREADS, 1) void inter_resi_dq_back_kernel(const IqArgs a, const VvcTrTables tb)
 {
   extern __shared__ __align__(16) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const _Float16* const tab = iq_load_tables(smem, a.image, tid);
+  const _Float16* const tab = rc_load_image<IR_THREADS>(smem, a.image, tid);   // below every wavefront walks its own items
   unsigned char* const mine = smem + IQ_TAB_BYTES + (size_t)wave * IQ_WAVE_BYTES;
   short* const resiT = reinterpret_cast<short*>(mine);
   RcDesc* const dS = reinterpret_cast<RcDesc*>(resiT + IR_TILE);
@@ -188,7 +154,7 @@ __global__ __launch_bounds__(IR_THREADS, 1) void inter_resi_dq_back_kernel(const
   for (int item = (int)blockIdx.x * IR_WAVES + wave; item < a.n; item += (int)gridDim.x * IR_WAVES)
   {
     const IrItem t = a.items[item];
-    const IrDq q = a.dq[item];
+    const IqDq q = a.dq[item];
     long long predOff;
     if (!iq_item_ok(a, t, q, predOff)) continue;                          // (the front wrote the markers)
     const unsigned servedMask = iq_served_mask(a, t);
@@ -200,7 +166,7 @@ __global__ __launch_bounds__(IR_THREADS, 1) void inter_resi_dq_back_kernel(const
     const Pel* const predG = a.pred + predOff;
     ir_stage(t, a.org + t.org_off, predG, resiT, predT, lane);
     if (lane < IR_SLOTS && ((servedMask >> lane) & 1u)) dS[lane] = iq_desc(t, lane, backT ? 0 : t.cand_off + (long long)lane * samples);
-    ir_wave_sync();
+    wave_sync();
 
     const unsigned short* const scan = tb.scan + tb.scanOff[(lw - 1) * 6 + (ilog2(h) - 1)];
     Pel* const outBase = backT ? backT : a.resi;
@@ -219,14 +185,14 @@ __global__ __launch_bounds__(IR_THREADS, 1) void inter_resi_dq_back_kernel(const
       else
       {
         iq_dequant(a.level + levelOff, a.coef + levelOff, w, h, t.qp, a.bd, scan, lane);
-        ir_global_sync();
+        wave_global_sync();
         iq_transform<RC_INV>(dS + k, resiT, outBase, a.coef, a.bd, tab, tb, fbScr, lane);
       }
-      if (backT) ir_wave_sync(); else ir_global_sync();
+      if (backT) wave_sync(); else wave_global_sync();
       finish(k, backT);
-      ir_wave_sync();                                                     // `back` and the integer body's buffers are free again
+      wave_sync();                                                     // `back` and the integer body's buffers are free again
     }
-    ir_wave_sync();                                                       // the tile and the descriptors are free again
+    wave_sync();                                                       // the tile and the descriptors are free again
   }
 }
 
@@ -236,9 +202,7 @@ extern "C" {
 
 size_t vvcgpu_inter_resi_code_dq_workspace_bytes(size_t level_extent, int n)
 {
-  const size_t c = iq_extent16(level_extent);
-  // the coefficients, the trellis decisions and level histories (all indexed by the slot's level offset), per slot a trellis record and a list entry
-  return c * sizeof(TCoeff) + tq_dec_bytes(c) + tq_ctx_bytes(c) + (size_t)(n > 0 ? n : 0) * IR_SLOTS * (sizeof(vvcgpu_depquant_desc) + sizeof(int)) + IQ_WS_SLACK;
+  return iq_layout(level_extent, n, IR_SLOTS, false).bytes;               // nothing parked; per slot a trellis record and a list entry
 }
 
 int vvcgpu_inter_resi_code_dq_batch(const vvc_pel* org_base, const vvc_pel* pred_base, const vvcgpu_inter_resi_item* items, const vvcgpu_inter_resi_dq* dq,
@@ -252,47 +216,28 @@ int vvcgpu_inter_resi_code_dq_batch(const vvc_pel* org_base, const vvc_pel* pred
   if (const int rc = ir_check_frame(name, n, pointers, flags, rec_base, clp_min, clp_max)) return rc;
   if (n == 0) return VVCGPU_OK;
   VVC_CHECK_ARG(((uintptr_t)items & 15) == 0 && ((uintptr_t)dq & 7) == 0, "%s: item array must be 16-byte, dq array 8-byte aligned", name);
-  VVC_CHECK_ARG(n_rates > 0, "%s: n_rates %d", name, n_rates);
-  VVC_CHECK_ARG(level_extent >= 16 && level_extent < ((size_t)1 << 40), "%s: level_extent %zu", name, level_extent);
-  VVC_CHECK_ARG(ws_bytes >= vvcgpu_inter_resi_code_dq_workspace_bytes(level_extent, n) && ((uintptr_t)ws & 15) == 0,
-                "%s: workspace of %zu bytes for a level extent of %zu and %d items is too small (need %zu) or unaligned", name, ws_bytes, level_extent, n,
-                vvcgpu_inter_resi_code_dq_workspace_bytes(level_extent, n));
-  if (quantiser != VVCGPU_INTER_RESI_Q_DEPQUANT) { vvcgpu_set_error("%s: quantiser %d is not served", name, quantiser); return VVCGPU_E_UNSUPPORTED; }
-  if (const int rc = ir_check_bit_depth(name, bit_depth)) return rc;
+  const IqLayout lay = iq_layout(level_extent, n, IR_SLOTS, false);
+  if (const int rc = iq_check_frame(name, n, "items", n_rates, level_extent, ws, ws_bytes, lay.bytes, quantiser, quantiser == VVCGPU_INTER_RESI_Q_DEPQUANT, bit_depth))
+    return rc;
   hipStream_t st = (hipStream_t)stream;
-  VvcTrTables tb; const _Float16* image = nullptr;
-  const int rt = vvcgpu_tr_images(&tb, &image);
-  if (rt) return rt;
   const int wgs = ir_workgroups(n);
   VVC_HIP(vvc_allow_lds(inter_resi_dq_front_kernel, IQ_LDS_BYTES));
   VVC_HIP(vvc_allow_lds(inter_resi_dq_back_kernel, IQ_LDS_BYTES));
-  VVC_HIP(vvc_allow_lds(inter_resi_dq_trellis_kernel, TQ_LDS_BYTES));
-  int cur = 0;
-  int* counters = vvcgpu_counters(st, &cur);                              // the list's length: zero on entry, the front clears the other set
-  if (!counters) return VVCGPU_E_DEVICE;
   VvcScratch sc(st);
-  int* fbScratch = ir_fb_scratch(sc, wgs);
-  if (!fbScratch) { vvcgpu_counters_failed(st); return VVCGPU_E_DEVICE; }
-  // the workspace as vvcgpu_inter_resi_code_dq_workspace_bytes lays it out
-  const size_t c = iq_extent16(level_extent);
-  unsigned char* const w8 = static_cast<unsigned char*>(ws);
-  TCoeff* coef = reinterpret_cast<TCoeff*>(w8);
-  unsigned* dec = reinterpret_cast<unsigned*>(w8 + c * sizeof(TCoeff));
-  unsigned char* ctx = w8 + c * sizeof(TCoeff) + tq_dec_bytes(c);
-  vvcgpu_depquant_desc* recs = reinterpret_cast<vvcgpu_depquant_desc*>(w8 + c * sizeof(TCoeff) + tq_dec_bytes(c) + tq_ctx_bytes(c));
+  IqSetup s;
+  if (const int rc = iq_setup(st, sc, (size_t)wgs * IR_WAVES, s)) return rc;
   IqArgs a;
   a.org = org_base; a.pred = pred_base; a.items = items; a.dq = dq; a.rdList = rd_list; a.resi = resi_base; a.rec = rec_base; a.level = level_base;
   a.absSum = abs_sum; a.distResi = reinterpret_cast<unsigned long long*>(dist_resi); a.distRec = reinterpret_cast<unsigned long long*>(dist_rec);
-  a.zeroDist = reinterpret_cast<unsigned long long*>(zero_dist); a.fbScratch = fbScratch; a.image = image;
-  a.coef = coef; a.recs = recs; a.list = reinterpret_cast<int*>(recs + (size_t)n * IR_SLOTS);
-  a.count = counters + VVC_CTR_INTS * cur; a.nextCounters = counters + VVC_CTR_INTS * (cur ^ 1); a.levelExtent = (long long)level_extent;
+  a.zeroDist = reinterpret_cast<unsigned long long*>(zero_dist); a.fbScratch = s.fbScratch; a.image = s.image;
+  a.coef = iq_at<TCoeff>(ws, 0); a.recs = iq_at<vvcgpu_depquant_desc>(ws, lay.recs); a.list = iq_at<int>(ws, lay.list);
+  a.count = s.count; a.nextCounters = s.nextCounters; a.levelExtent = (long long)level_extent;
   a.n = n; a.nRates = n_rates; a.writeRec = (flags & VVCGPU_INTER_RESI_WRITE_REC) ? 1 : 0; a.bd = bit_depth; a.cmin = clp_min; a.cmax = clp_max;
-  hipLaunchKernelGGL(inter_resi_dq_front_kernel, dim3(wgs), dim3(IR_THREADS), IQ_LDS_BYTES, st, a, tb);
+  hipLaunchKernelGGL(inter_resi_dq_front_kernel, dim3(wgs), dim3(IR_THREADS), IQ_LDS_BYTES, st, a, s.tb);
   VVC_LAUNCH_CHECK_COUNTERS(st);
-  hipLaunchKernelGGL(inter_resi_dq_trellis_kernel, dim3(cdiv(n * IR_SLOTS, 64)), dim3(256), TQ_LDS_BYTES, st, coef, level_base, recs, a.list, a.count, rates, bit_depth,
-                     abs_sum, dec, ctx, tb);
-  VVC_LAUNCH_CHECK_COUNTERS(st);
-  hipLaunchKernelGGL(inter_resi_dq_back_kernel, dim3(wgs), dim3(IR_THREADS), IQ_LDS_BYTES, st, a, tb);
+  if (const int rc = vvcgpu_depquant_listed_launch(a.coef, level_base, a.recs, a.list, a.count, n * IR_SLOTS, rates, bit_depth, abs_sum,
+                                                   iq_at<unsigned>(ws, lay.dec), iq_at<unsigned char>(ws, lay.ctx), s.tb, st)) return rc;
+  hipLaunchKernelGGL(inter_resi_dq_back_kernel, dim3(wgs), dim3(IR_THREADS), IQ_LDS_BYTES, st, a, s.tb);
   VVC_LAUNCH_CHECK();
   return VVCGPU_OK;
 }

@@ -16,8 +16,6 @@ enum { PLANAR = 0, DC = 1, HOR = 18, DIA = 34, VER = 50, VDIA = 66 };
 constexpr int REF_MAX = 160;            // >= longest side reference + 2 (2 * 64 + 22 + 1)
 constexpr int NEG_MAX = 64;             // projected samples left of the main reference
 
-__device__ __forceinline__ void wave_sync() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }
-
 // m_topRefLength / m_leftRefLength of setReferenceArrayLengths :233-249
 __device__ __forceinline__ void intra_ref_lengths(int w, int h, int& T, int& L)
 {

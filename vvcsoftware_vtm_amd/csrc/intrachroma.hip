@@ -151,6 +151,7 @@ __global__ __launch_bounds__(256, 1) void chroma_large_kernel(const ChArgs a, co
   _Float16* const tab = reinterpret_cast<_Float16*>(smem);
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   {
+    // (rc_load_image in words: as a call of it the kernel's first instructions come out in another order, docs/MEASUREMENTS.md)
     constexpr int NW4 = RC_TAB_HALVES / 8;
     const uint4* src = reinterpret_cast<const uint4*>(a.image);
     for (int i = tid; i < NW4; i += 256) reinterpret_cast<uint4*>(tab)[i] = src[i];
@@ -222,9 +223,7 @@ __global__ __launch_bounds__(256, 1) void chroma_large_kernel(const ChArgs a, co
           ch_tu_generic_call(dS, orgS, tile, a.candRec, a.level, a.absSum + item, a.bd, a.cmin, a.cmax, tb.tr32, tb.dqInv, tb.scanOff, fbScr, fbScr + 4096, lane);
 
         // ---- the reconstruction the wavefront has just written, read back against the staged original: xGetSSE(org, rec)
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-        __builtin_amdgcn_wave_barrier();
+        wave_global_sync();
         {
           const Pel* rec = a.candRec + u.cand_off + off;
           unsigned long long sse = 0ull;                                  // 64 x 64 x 1023^2 is beyond 2^31
@@ -264,7 +263,7 @@ extern "C" int vvcgpu_intra_chroma_code_batch(const vvc_pel* rec_base, const uin
   for (int r = 0; r < n_runs; r++)
   {
     const int w = runs_host[3 * r], h = runs_host[3 * r + 1], count = runs_host[3 * r + 2];
-    VVC_CHECK_ARG(count >= 0 && ch_side_ok(w) && ch_side_ok(h), "%s: run %d (%d x %d, %d PUs)", name, r, w, h, count);
+    VVC_CHECK_ARG(count >= 0 && side_ok(w, 2) && side_ok(h, 2), "%s: run %d (%d x %d, %d PUs)", name, r, w, h, count);
     VVC_CHECK_ARG(sum + count <= n, "%s: the runs hold more than n = %d PUs", name, n);
     if (count == 0) continue;
     int lw = 0, lh = 0; while ((1 << lw) < w) lw++; while ((1 << lh) < h) lh++;

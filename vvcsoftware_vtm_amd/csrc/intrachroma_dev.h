@@ -20,8 +20,6 @@ struct ChArgs
   ChSeg seg[CH_MAX_RUNS];
 };
 
-inline __host__ __device__ bool ch_side_ok(int v) { return v >= 2 && v <= 64 && (v & (v - 1)) == 0; }
-
 // the PU behind work index q (wave-uniform, < a.total) of a launch and the shape of its run.  Unrolled, with constant indices: the runs stay kernel
 // arguments read by scalar loads
 __device__ __forceinline__ int ch_locate(const ChArgs& a, int q, int& rw, int& rh)
@@ -45,7 +43,7 @@ __device__ __forceinline__ int ch_locate(const ChArgs& a, int q, int& rw, int& r
 __device__ __forceinline__ bool ch_pu_ok(const ChArgs& a, const ChPu& u, int p, int rw, int rh, bool& anyLm)
 {
   const int w = u.w, h = u.h;
-  bool ok = ch_side_ok(w) && ch_side_ok(h) && w == rw && h == rh && (u.cand_off & 3) == 0 && (u.level_off & 3) == 0;
+  bool ok = side_ok(w, 2) && side_ok(h, 2) && w == rw && h == rh && (u.cand_off & 3) == 0 && (u.level_off & 3) == 0;
   anyLm = false;
 #pragma unroll
   for (int k = 0; k < CH_SLOTS; k++) { const int m = u.mode[k]; ok = ok && m >= -1 && m <= CH_LM; anyLm = anyLm || m == CH_LM; }

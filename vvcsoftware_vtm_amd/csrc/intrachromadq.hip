@@ -13,11 +13,11 @@
 //              PU, then per component and slot the prediction into the wavefront's LDS tile (stored under WRITE_PRED, parked in the workspace at the
 //              item's level offset), org - pred over it in place, the forward transform (dqpass_dev.h) into the coefficient workspace, the item's
 //              trellis record and its entry in the Cb or the Cr work list.  The two lists have one length: one atomic add per wavefront on one counter.
-//   trellis Cb iq_trellis<true> over the Cb list.
+//   trellis Cb vvcgpu_depquant_listed_launch (depquant.hip) over the Cb list.
 //   select     per entry of the Cr list: rates_idx and lambda of the record from dq[3 p + 1] or dq[3 p + 2] by abs_sum of the slot's Cb item.  A launch
 //              of its own: the trellis reads its records through const __restrict__ pointers, and another compute unit's abs_sum is only guaranteed
 //              visible across a kernel boundary.
-//   trellis Cr iq_trellis<true> over the Cr list.
+//   trellis Cr the same launch over the Cr list.
 //   back       persistent workgroups of twelve wavefronts, a wavefront per item (PU, slot, component): the dependent de-quantiser and the inverse
 //              transform when abs_sum != 0, clip(parked pred + resi') to cand_rec_base, xGetSSE(org, rec).
 #include "common.h"
@@ -31,9 +31,7 @@ static_assert(sizeof(vvcgpu_intra_chroma_pu) == 96 && sizeof(vvcgpu_intra_fill_d
 
 namespace {
 
-typedef vvcgpu_inter_resi_dq ChqDq;
 constexpr int CQ_TILE = 64 * 64;
-constexpr int CQ_FB_INTS = 2 * 4096;                                      // global scratch per wavefront: the integer body's two buffers for an item outside the matrix-core range
 // front: per wavefront the tile (also the packed references of the gathering), the luma block, top / left, the main reference buffer (also the unit
 // table of the gathering), the luma neighbours and the item's chain descriptor
 constexpr int CQF_WAVES = 6, CQF_THREADS = 64 * CQF_WAVES;
@@ -49,7 +47,7 @@ static_assert(IQ_TAB_BYTES % 16 == 0 && CQF_WAVE_BYTES % 16 == 0 && CQB_WAVE_BYT
 struct ChqArgs
 {
   ChArgs ch;                                                              // one class: every run of the list, so work index q is PU q
-  const ChqDq* dq; TCoeff* coef; Pel* park; vvcgpu_depquant_desc* recs; int* listCb; int* listCr; int* count; int* nextCounters;
+  const IqDq* dq; TCoeff* coef; Pel* park; vvcgpu_depquant_desc* recs; int* listCb; int* listCr; int* count; int* nextCounters;
   long long levelExtent; int nRates;
 };
 
@@ -62,7 +60,7 @@ __device__ __forceinline__ bool chq_pu_ok(const ChqArgs& a, const ChPu& u, int p
 #pragma unroll
   for (int j = 0; j < 3; j++)
   {
-    const ChqDq q = a.dq[3 * (size_t)p + j];
+    const IqDq q = a.dq[3 * (size_t)p + j];
     ok = ok && q.rates_idx >= 0 && q.rates_idx < a.nRates && q.lambda > 0.0 && q.luma == 0;
   }
   return ok;
@@ -73,14 +71,6 @@ __device__ __forceinline__ int chq_slots(const ChPu& u)
 #pragma unroll
   for (int k = 0; k < CH_SLOTS; k++) s += u.mode[k] >= 0 ? 1 : 0;
   return s;
-}
-__device__ __forceinline__ const _Float16* chq_load_tables(unsigned char* smem, const _Float16* image, int tid, int threads)
-{
-  _Float16* const tab = reinterpret_cast<_Float16*>(smem);
-  const uint4* src = reinterpret_cast<const uint4*>(image);
-  for (int i = tid; i < IQ_TAB_BYTES / 16; i += threads) reinterpret_cast<uint4*>(tab)[i] = src[i];
-  __syncthreads();                                                        // the only workgroup barrier: below every wavefront walks its own work
-  return tab;
 }
 // the chain descriptor of an item for the transform bodies: the residual (forward) or resi' (inverse) contiguous in the tile; the coefficients at the
 // item's place in the workspace
@@ -99,7 +89,7 @@ __global__ __launch_bounds__(CQF_THREADS, 1) void chroma_dq_front_kernel(const C
 {
   extern __shared__ __align__(16) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const _Float16* const tab = chq_load_tables(smem, a.ch.image, tid, CQF_THREADS);
+  const _Float16* const tab = rc_load_image<CQF_THREADS>(smem, a.ch.image, tid);   // below every wavefront walks its own work
   unsigned char* const mine = smem + IQ_TAB_BYTES + (size_t)wave * CQF_WAVE_BYTES;
   short* const tile = reinterpret_cast<short*>(mine);
   short* const lumaS = tile + CQ_TILE;
@@ -109,36 +99,30 @@ __global__ __launch_bounds__(CQF_THREADS, 1) void chroma_dq_front_kernel(const C
   short* const lumaTop = mainS + NEG_MAX + REF_MAX;
   short* const lumaLeft = lumaTop + 64;
   RcDesc* const dS = reinterpret_cast<RcDesc*>(mine + CQF_WAVE_BYTES - sizeof(RcDesc));
-  int* const fbScr = a.ch.fbScratch + ((size_t)blockIdx.x * CQF_WAVES + wave) * CQ_FB_INTS;
+  int* const fbScr = a.ch.fbScratch + ((size_t)blockIdx.x * CQF_WAVES + wave) * IQ_FB_INTS;
   if (blockIdx.x == 0 && tid < VVC_CTR_INTS) a.nextCounters[tid] = 0;    // the counter set of the NEXT call on this stream (vvcgpu_counters)
 
-  // the wavefront's run in the two work lists (they have one length: a served slot is one Cb and one Cr item): its served slots are counted first, so
-  // that the counter sees one atomic add per wavefront
+  // the wavefront's run in the two work lists (they have one length: a served slot is one Cb and one Cr item): its served slots are counted first
   const int first = (int)blockIdx.x + (int)gridDim.x * wave, step = (int)gridDim.x * CQF_WAVES;
-  int listAt = 0;
+  // a lane per PU.  Its run is found by a ROLLED walk over the runs, not by ch_locate: ch_locate is unrolled over its 36 runs for a wave-uniform index,
+  // and inside a loop as small as this one the compiler's loop unswitching takes up its 36 loop-invariant conditions (s < nSeg) one after the other
+  // -- hipcc -O3 did not finish this file in 40 minutes with ch_locate here, and finishes it in 4 s with this walk.  Do not "restore" ch_locate.
+  int cnt = 0;
+  for (long long q = first + (long long)lane * step; q < a.ch.total; q += 64ll * step)
   {
-    // a lane per PU.  Its run is found by a ROLLED walk over the runs, not by ch_locate: ch_locate is unrolled over its 36 runs for a wave-uniform index,
-    // and inside a loop as small as this one the compiler's loop unswitching takes up its 36 loop-invariant conditions (s < nSeg) one after the other
-    // -- hipcc -O3 did not finish this file in 40 minutes with ch_locate here, and finishes it in 4 s with this walk.  Do not "restore" ch_locate.
-    int cnt = 0;
-    for (long long q = first + (long long)lane * step; q < a.ch.total; q += 64ll * step)
-    {
-      const int p = (int)q;                                               // one class: work index q is PU q
-      int rw = 0, rh = 0;
+    const int p = (int)q;                                                 // one class: work index q is PU q
+    int rw = 0, rh = 0;
 #pragma nounroll
-      for (int s = 0; s < a.ch.nSeg; s++)
-      {
-        const ChSeg g = a.ch.seg[s];
-        if (p >= g.first && p - g.first < g.count) { rw = g.w; rh = g.h; }
-      }
-      const ChPu u = a.ch.pus[p];
-      bool anyLm;
-      if (chq_pu_ok(a, u, p, rw, rh, anyLm)) cnt += chq_slots(u);
+    for (int s = 0; s < a.ch.nSeg; s++)
+    {
+      const ChSeg g = a.ch.seg[s];
+      if (p >= g.first && p - g.first < g.count) { rw = g.w; rh = g.h; }
     }
-    cnt = wave_sum_i32(cnt);
-    if (cnt && lane == 0) listAt = atomicAdd(a.count, cnt);
-    listAt = __builtin_amdgcn_readfirstlane(listAt);
+    const ChPu u = a.ch.pus[p];
+    bool anyLm;
+    if (chq_pu_ok(a, u, p, rw, rh, anyLm)) cnt += chq_slots(u);
   }
+  int listAt = iq_reserve(a.count, cnt, lane);
 
   for (int q = first; q < a.ch.total; q += step)
   {
@@ -163,7 +147,7 @@ __global__ __launch_bounds__(CQF_THREADS, 1) void chroma_dq_front_kernel(const C
         cclm_params(w, h, aboveAvail, leftAvail, [&](int i) { return (int)lumaTop[i]; }, [&](int i) { return (int)lumaLeft[i]; }, topS + 1, leftS + 1,
                     a.ch.bd, a.ch.bd, lane, lmA, lmB, lmShift);
       const Pel* org = a.ch.org + CH_SEL(org_off, c);
-      const ChqDq dq = a.dq[3 * (size_t)p + c];                           // Cr: the record of a Cb block without a level, until the select step has looked
+      const IqDq dq = a.dq[3 * (size_t)p + c];                           // Cr: the record of a Cb block without a level, until the select step has looked
       int* const list = c ? a.listCr : a.listCb;
       int at = listAt;
 #pragma nounroll
@@ -182,11 +166,7 @@ __global__ __launch_bounds__(CQF_THREADS, 1) void chroma_dq_front_kernel(const C
         if (lane == 0)                                                    // the chain descriptor, the trellis record and its list entry
         {
           *dS = chq_desc(w, h, CH_SEL(qp, c), u.level_off + off);
-          vvcgpu_depquant_desc r;
-          r.coeff_off = r.level_off = u.level_off + off;
-          r.lambda = dq.lambda; r.qp = CH_SEL(qp, c); r.rates_idx = dq.rates_idx; r.w = (int16_t)w; r.h = (int16_t)h; r.luma = 0;
-          r.reserved[0] = r.reserved[1] = r.reserved[2] = 0;
-          a.recs[item] = r;
+          a.recs[item] = iq_record(u.level_off + off, CH_SEL(qp, c), w, h, dq, 0);
           list[at] = item;
         }
         at++;
@@ -202,36 +182,25 @@ __global__ __launch_bounds__(CQF_THREADS, 1) void chroma_dq_front_kernel(const C
 
 // the Cr records take the table and the lambda that Cb's result of the same slot asks for
 __global__ __launch_bounds__(256) void chroma_dq_select_kernel(vvcgpu_depquant_desc* __restrict__ recs, const int* __restrict__ listCr, const int* __restrict__ count,
-                                                               const unsigned* __restrict__ absSum, const ChqDq* __restrict__ dq)
+                                                               const unsigned* __restrict__ absSum, const IqDq* __restrict__ dq)
 {
   const int t = (int)blockIdx.x * 256 + (int)threadIdx.x;
   if (t >= *count) return;
   const int item = listCr[t], p = item / 12;
-  const ChqDq q = dq[3 * (size_t)p + (absSum[item - 1] != 0u ? 2 : 1)];
+  const IqDq q = dq[3 * (size_t)p + (absSum[item - 1] != 0u ? 2 : 1)];
   recs[item].lambda = q.lambda;
   recs[item].rates_idx = q.rates_idx;
-}
-
-__global__ __launch_bounds__(256) void chroma_dq_trellis_kernel(const TCoeff* __restrict__ coeffBase, TCoeff* __restrict__ levelBase,
-                                                                const vvcgpu_depquant_desc* __restrict__ descs, const int* __restrict__ list,
-                                                                const int* __restrict__ count,
-                                                                const vvcgpu_dq_rates* __restrict__ ratesBase, int bd, unsigned* __restrict__ absSumOut,
-                                                                unsigned* __restrict__ wsDec, unsigned char* __restrict__ wsCtx, VvcTrTables tb)
-{
-  const int n = *count;                                                   // the served slots of the call, counted by the front
-  if ((int)blockIdx.x * 64 >= n) return;
-  iq_trellis<true>(coeffBase, levelBase, descs, list, n, ratesBase, bd, absSumOut, wsDec, wsCtx, tb);
 }
 
 __global__ __launch_bounds__(CQB_THREADS, 1) void chroma_dq_back_kernel(const ChqArgs a, const VvcTrTables tb)
 {
   extern __shared__ __align__(16) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const _Float16* const tab = chq_load_tables(smem, a.ch.image, tid, CQB_THREADS);
+  const _Float16* const tab = rc_load_image<CQB_THREADS>(smem, a.ch.image, tid);   // below every wavefront walks its own work
   unsigned char* const mine = smem + IQ_TAB_BYTES + (size_t)wave * CQB_WAVE_BYTES;
   short* const tile = reinterpret_cast<short*>(mine);
   RcDesc* const dS = reinterpret_cast<RcDesc*>(mine + CQB_WAVE_BYTES - sizeof(RcDesc));
-  int* const fbScr = a.ch.fbScratch + ((size_t)blockIdx.x * CQB_WAVES + wave) * CQ_FB_INTS;
+  int* const fbScr = a.ch.fbScratch + ((size_t)blockIdx.x * CQB_WAVES + wave) * IQ_FB_INTS;
 
   const long long items = 12ll * a.ch.total;
   for (long long item = (long long)blockIdx.x + (long long)gridDim.x * wave; item < items; item += (long long)gridDim.x * CQB_WAVES)
@@ -242,36 +211,14 @@ __global__ __launch_bounds__(CQB_THREADS, 1) void chroma_dq_back_kernel(const Ch
     const ChPu u = a.ch.pus[p];
     bool anyLm;
     if (!chq_pu_ok(a, u, p, rw, rh, anyLm) || ch_mode(u, k) < 0) continue;   // (the front wrote the markers)
-    const int w = u.w, h = u.h, samples = w * h, lw = ilog2(w);
+    const int w = u.w, h = u.h, samples = w * h;
     const int64_t off = (int64_t)s * samples;
-    // the tile is where the body leaves resi': at 0, or -- a shape with a side of at most 8 (at most 512 samples) has the integer body's two buffers
-    // at 1024 and 2048 -- at 3072
-    short* const backT = (w <= 8 || h <= 8) ? tile + 3072 : tile;
+    short* const backT = iq_back_tile(tile, w, h);
     const bool coded = a.ch.absSum[item] != 0u;                           // all levels zero: resi' is zero (piResi.fill(0))
-    if (coded)
-    {
-      if (lane == 0) *dS = chq_desc(w, h, CH_SEL(qp, c), u.level_off + off);
-      const unsigned short* const scan = tb.scan + tb.scanOff[(lw - 1) * 6 + (ilog2(h) - 1)];
-      iq_dequant(a.ch.level + u.level_off + off, a.coef + u.level_off + off, w, h, CH_SEL(qp, c), a.ch.bd, scan, lane);
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");              // stores of the wavefront to global memory, read back by other lanes of it
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-      __builtin_amdgcn_wave_barrier();
-      iq_transform<RC_INV>(dS, tile, backT, a.coef, a.ch.bd, tab, tb, fbScr, lane);
-      wave_sync();
-    }
-    // clip(pred + resi') to cand_rec_base, xGetSSE(org, rec)
-    const Pel* org = a.ch.org + CH_SEL(org_off, c);
-    const Pel* pred = a.park + u.level_off + off;                         // as the front formed it
-    Pel* rec = a.ch.candRec + u.cand_off + off;
-    unsigned long long sse = 0ull;                                        // 64 x 64 x 1023^2 is beyond 2^31
-    for (int e = lane; e < samples; e += 64)
-    {
-      const int rc = clip3(a.ch.cmin, a.ch.cmax, (int)pred[e] + (coded ? (int)backT[e] : 0));
-      const unsigned df = (unsigned)abs((int)org[(ptrdiff_t)(e >> lw) * u.org_stride + (e & (w - 1))] - rc);
-      sse += (unsigned long long)(df * df);
-      rec[e] = (short)rc;
-    }
-    sse = group_sum_u64<64>(sse);
+    if (coded) iq_decode(chq_desc(w, h, CH_SEL(qp, c), u.level_off + off), dS, tile, backT, a.ch.level, a.coef, a.ch.bd, tab, tb, fbScr, lane);
+    // clip(pred + resi') with the prediction as the front formed it to cand_rec_base (rows w apart), xGetSSE(org, rec)
+    const unsigned long long sse = iq_close(a.ch.org + CH_SEL(org_off, c), u.org_stride, a.park + u.level_off + off, backT, coded,
+                                            a.ch.candRec + u.cand_off + off, w, nullptr, w, samples, a.ch.cmin, a.ch.cmax, lane, nullptr);
     if (lane == 0) a.ch.dist[item] = sse;
     wave_sync();                                                          // the tile and the descriptor are free again
   }
@@ -283,11 +230,8 @@ extern "C" {
 
 size_t vvcgpu_intra_chroma_code_dq_workspace_bytes(size_t level_extent, int n)
 {
-  const size_t c = iq_extent16(level_extent);
-  // the coefficients, the trellis decisions and level histories, the parked predictions (all indexed by the item's level offset), per item (twelve per
-  // PU) a trellis record and an entry of the Cb or the Cr work list
-  return c * sizeof(TCoeff) + tq_dec_bytes(c) + tq_ctx_bytes(c) + c * sizeof(Pel) +
-         (size_t)(n > 0 ? n : 0) * 2 * CH_SLOTS * (sizeof(vvcgpu_depquant_desc) + sizeof(int)) + IQ_WS_SLACK;
+  // parked predictions; per item (twelve per PU) a trellis record and an entry of the Cb or the Cr work list
+  return iq_layout(level_extent, n, 2 * CH_SLOTS, true).bytes;
 }
 
 int vvcgpu_intra_chroma_code_dq_batch(const vvc_pel* rec_base, const uint8_t* flags_base, const vvcgpu_intra_fill_desc* fill, vvc_pel* refs_base,
@@ -317,7 +261,7 @@ int vvcgpu_intra_chroma_code_dq_batch(const vvc_pel* rec_base, const uint8_t* fl
   for (int r = 0; r < n_runs; r++)
   {
     const int w = runs_host[3 * r], h = runs_host[3 * r + 1], count = runs_host[3 * r + 2];
-    VVC_CHECK_ARG(count >= 0 && ch_side_ok(w) && ch_side_ok(h), "%s: run %d (%d x %d, %d PUs)", name, r, w, h, count);
+    VVC_CHECK_ARG(count >= 0 && side_ok(w, 2) && side_ok(h, 2), "%s: run %d (%d x %d, %d PUs)", name, r, w, h, count);
     VVC_CHECK_ARG(sum + count <= n, "%s: the runs hold more than n = %d PUs", name, n);
     if (count == 0) continue;
     int lw = 0, lh = 0; while ((1 << lw) < w) lw++; while ((1 << lh) < h) lh++;
@@ -330,54 +274,34 @@ int vvcgpu_intra_chroma_code_dq_batch(const vvc_pel* rec_base, const uint8_t* fl
     sum += count;
   }
   VVC_CHECK_ARG(sum == n, "%s: the run counts sum to %lld, n is %d", name, sum, n);
-  VVC_CHECK_ARG(n_rates > 0, "%s: n_rates %d", name, n_rates);
-  VVC_CHECK_ARG(level_extent >= 16 && level_extent < ((size_t)1 << 40), "%s: level_extent %zu", name, level_extent);
-  VVC_CHECK_ARG(ws_bytes >= vvcgpu_intra_chroma_code_dq_workspace_bytes(level_extent, n) && ((uintptr_t)ws & 15) == 0,
-                "%s: workspace of %zu bytes for a level extent of %zu and %d PUs is too small (need %zu) or unaligned", name, ws_bytes, level_extent, n,
-                vvcgpu_intra_chroma_code_dq_workspace_bytes(level_extent, n));
-  if (quantiser != VVCGPU_INTRA_CHROMA_Q_DEPQUANT) { vvcgpu_set_error("%s: quantiser %d is not served", name, quantiser); return VVCGPU_E_UNSUPPORTED; }
-  if (bit_depth > 10 || bit_depth < 8) { vvcgpu_set_error("%s: bit depth %d outside 8..10", name, bit_depth); return VVCGPU_E_UNSUPPORTED; }
+  const IqLayout lay = iq_layout(level_extent, n, 2 * CH_SLOTS, true);
+  if (const int rc = iq_check_frame(name, n, "PUs", n_rates, level_extent, ws, ws_bytes, lay.bytes, quantiser, quantiser == VVCGPU_INTRA_CHROMA_Q_DEPQUANT, bit_depth))
+    return rc;
   hipStream_t st = (hipStream_t)stream;
-  VvcTrTables tb; const _Float16* image = nullptr;
-  const int rt = vvcgpu_tr_images(&tb, &image);
-  if (rt) return rt;
   const int cap = vvcgpu_cu_count(), wgsF = n < cap ? n : cap, wgsB = 12ll * n < cap ? 12 * n : cap;
   VVC_HIP(vvc_allow_lds(chroma_dq_front_kernel, CQF_LDS_BYTES));
   VVC_HIP(vvc_allow_lds(chroma_dq_back_kernel, CQB_LDS_BYTES));
-  VVC_HIP(vvc_allow_lds(chroma_dq_trellis_kernel, TQ_LDS_BYTES));
-  int cur = 0;
-  int* counters = vvcgpu_counters(st, &cur);                              // the lists' length: zero on entry, the front clears the other set
-  if (!counters) return VVCGPU_E_DEVICE;
   VvcScratch sc(st);
+  IqSetup s;
   const size_t fbWaves = (size_t)wgsF * CQF_WAVES > (size_t)wgsB * CQB_WAVES ? (size_t)wgsF * CQF_WAVES : (size_t)wgsB * CQB_WAVES;
-  int* fbScratch = sc.take<int>(fbWaves * CQ_FB_INTS);                    // touched only for an item outside the matrix-core range
-  if (!fbScratch) { vvcgpu_counters_failed(st); return VVCGPU_E_DEVICE; }
-  // the workspace as vvcgpu_intra_chroma_code_dq_workspace_bytes lays it out
-  const size_t c = iq_extent16(level_extent), items = (size_t)n * 2 * CH_SLOTS;
-  unsigned char* const w8 = static_cast<unsigned char*>(ws);
-  TCoeff* coef = reinterpret_cast<TCoeff*>(w8);
-  unsigned* dec = reinterpret_cast<unsigned*>(w8 + c * sizeof(TCoeff));
-  unsigned char* ctx = w8 + c * sizeof(TCoeff) + tq_dec_bytes(c);
-  Pel* park = reinterpret_cast<Pel*>(w8 + c * sizeof(TCoeff) + tq_dec_bytes(c) + tq_ctx_bytes(c));
-  vvcgpu_depquant_desc* recs = reinterpret_cast<vvcgpu_depquant_desc*>(w8 + c * sizeof(TCoeff) + tq_dec_bytes(c) + tq_ctx_bytes(c) + c * sizeof(Pel));
+  if (const int rc = iq_setup(st, sc, fbWaves, s)) return rc;
   a.ch.rec = rec_base; a.ch.flags = flags_base; a.ch.fill = fill; a.ch.refs = refs_base; a.ch.luma = luma_base; a.ch.org = org_base; a.ch.pus = pus;
   a.ch.pred = pred_base; a.ch.candRec = cand_rec_base; a.ch.level = level_base; a.ch.absSum = abs_sum; a.ch.dist = reinterpret_cast<unsigned long long*>(dist);
-  a.ch.fbScratch = fbScratch; a.ch.image = image; a.ch.writePred = (flags & VVCGPU_INTRA_CHROMA_WRITE_PRED) ? 1 : 0;
+  a.ch.fbScratch = s.fbScratch; a.ch.image = s.image; a.ch.writePred = (flags & VVCGPU_INTRA_CHROMA_WRITE_PRED) ? 1 : 0;
   a.ch.bd = bit_depth; a.ch.cmin = clp_min; a.ch.cmax = clp_max;
-  a.dq = dq; a.coef = coef; a.park = park; a.recs = recs; a.listCb = reinterpret_cast<int*>(recs + items); a.listCr = a.listCb + items / 2;
-  a.count = counters + VVC_CTR_INTS * cur; a.nextCounters = counters + VVC_CTR_INTS * (cur ^ 1); a.levelExtent = (long long)level_extent; a.nRates = n_rates;
-  const int slots = n * CH_SLOTS;                                         // the longest a list can be
-  hipLaunchKernelGGL(chroma_dq_front_kernel, dim3(wgsF), dim3(CQF_THREADS), CQF_LDS_BYTES, st, a, tb);
+  const int slots = n * CH_SLOTS;                                         // the longest a list can be: the Cb list, and behind it the Cr list
+  a.dq = dq; a.coef = iq_at<TCoeff>(ws, 0); a.park = iq_at<Pel>(ws, lay.park); a.recs = iq_at<vvcgpu_depquant_desc>(ws, lay.recs);
+  a.listCb = iq_at<int>(ws, lay.list); a.listCr = a.listCb + slots;
+  a.count = s.count; a.nextCounters = s.nextCounters; a.levelExtent = (long long)level_extent; a.nRates = n_rates;
+  unsigned* const dec = iq_at<unsigned>(ws, lay.dec);
+  unsigned char* const ctx = iq_at<unsigned char>(ws, lay.ctx);
+  hipLaunchKernelGGL(chroma_dq_front_kernel, dim3(wgsF), dim3(CQF_THREADS), CQF_LDS_BYTES, st, a, s.tb);
   VVC_LAUNCH_CHECK_COUNTERS(st);
-  hipLaunchKernelGGL(chroma_dq_trellis_kernel, dim3(cdiv(slots, 64)), dim3(256), TQ_LDS_BYTES, st, coef, level_base, recs, a.listCb, a.count, rates, bit_depth,
-                     abs_sum, dec, ctx, tb);
+  if (const int rc = vvcgpu_depquant_listed_launch(a.coef, level_base, a.recs, a.listCb, a.count, slots, rates, bit_depth, abs_sum, dec, ctx, s.tb, st)) return rc;
+  hipLaunchKernelGGL(chroma_dq_select_kernel, dim3(cdiv(slots, 256)), dim3(256), 0, st, a.recs, a.listCr, a.count, abs_sum, dq);
   VVC_LAUNCH_CHECK_COUNTERS(st);
-  hipLaunchKernelGGL(chroma_dq_select_kernel, dim3(cdiv(slots, 256)), dim3(256), 0, st, recs, a.listCr, a.count, abs_sum, dq);
-  VVC_LAUNCH_CHECK_COUNTERS(st);
-  hipLaunchKernelGGL(chroma_dq_trellis_kernel, dim3(cdiv(slots, 64)), dim3(256), TQ_LDS_BYTES, st, coef, level_base, recs, a.listCr, a.count, rates, bit_depth,
-                     abs_sum, dec, ctx, tb);
-  VVC_LAUNCH_CHECK_COUNTERS(st);
-  hipLaunchKernelGGL(chroma_dq_back_kernel, dim3(wgsB), dim3(CQB_THREADS), CQB_LDS_BYTES, st, a, tb);
+  if (const int rc = vvcgpu_depquant_listed_launch(a.coef, level_base, a.recs, a.listCr, a.count, slots, rates, bit_depth, abs_sum, dec, ctx, s.tb, st)) return rc;
+  hipLaunchKernelGGL(chroma_dq_back_kernel, dim3(wgsB), dim3(CQB_THREADS), CQB_LDS_BYTES, st, a, s.tb);
   VVC_LAUNCH_CHECK();
   return VVCGPU_OK;
 }

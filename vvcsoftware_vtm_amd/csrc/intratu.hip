@@ -16,6 +16,7 @@
 #include "common.h"
 #include "dist_dev.h"
 #include "intra_dev.h"
+#include "intratu_dev.h"
 #include "mfma_tr.h"
 #include "quant_dev.h"
 #include "resichain_dev.h"
@@ -24,13 +25,9 @@ static_assert(sizeof(vvcgpu_intra_desc) == 32 && sizeof(vvcgpu_resi_chain_desc) 
 
 namespace {
 
-constexpr int IT_TILE = 64 * 64;                                          // samples of a wavefront's prediction tile
 constexpr int IT_WGS_PER_CU = 2;
-constexpr int IT_TAB_BYTES = RC_TAB_HALVES * 2;
-constexpr int IT_WAVE_BYTES = (IT_TILE + 4 * REF_MAX + NEG_MAX + REF_MAX) * 2 + (int)sizeof(vvcgpu_resi_chain_desc);
 constexpr int IT_LDS_BYTES = IT_TAB_BYTES + 4 * IT_WAVE_BYTES;            // 79 296 bytes: two workgroups per compute unit
-static_assert(IT_TAB_BYTES % 16 == 0 && IT_WAVE_BYTES % 16 == 0 && IT_WGS_PER_CU * IT_LDS_BYTES <= 160 * 1024, "LDS budget");
-constexpr int IT_LIST_INTS = 16, IT_LIST_FIRST = 5, IT_LIST_MAX = 11;     // a row of list_out of vvcgpu_intra_mode_cand_batch: [0] size, [5 .. 15] uiRdModeList
+static_assert(IT_WGS_PER_CU * IT_LDS_BYTES <= 160 * 1024, "LDS budget");
 
 struct ItArgs
 {
@@ -38,8 +35,6 @@ struct ItArgs
   unsigned* absSum; unsigned* numSig; unsigned long long* dist; int* modeOut; int* fbScratch; const _Float16* image;
   int n, writePred, noSmoothing, bd, cmin, cmax;
 };
-
-inline __host__ __device__ bool it_side_ok(int v) { return v >= 4 && v <= 64 && (v & (v - 1)) == 0; }
 
 // the matrix-core body of one shape as a real call (the descriptor and the tile are the wavefront's, in LDS)
 template <int W, int H>
@@ -65,63 +60,25 @@ __global__ __launch_bounds__(256, IT_WGS_PER_CU) void intra_tu_code_kernel(const
   _Float16* const tab = reinterpret_cast<_Float16*>(smem);
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   {
-    // the f16 matrices as one run of 16-byte loads (as the chain kernel's)
+    // (rc_load_image in words: as a call of it the kernel's first instructions come out in another order, docs/MEASUREMENTS.md)
     constexpr int NW4 = RC_TAB_HALVES / 8;
     const uint4* src = reinterpret_cast<const uint4*>(a.image);
     for (int i = tid; i < NW4; i += 256) reinterpret_cast<uint4*>(tab)[i] = src[i];
   }
   __syncthreads();                                                        // the only workgroup barrier: below every wavefront walks its own items
-  unsigned char* const mine = smem + IT_TAB_BYTES + (size_t)wave * IT_WAVE_BYTES;
-  short* const tile = reinterpret_cast<short*>(mine);
-  short* const topS = tile + IT_TILE;                                     // top, left: REF_MAX each; tmp: 2 REF_MAX; main: NEG_MAX + REF_MAX
-  short* const leftS = topS + REF_MAX;
-  short* const tmpS = leftS + REF_MAX;
-  short* const mainS = tmpS + 2 * REF_MAX;
-  RcDesc* const dS = reinterpret_cast<RcDesc*>(mine + IT_WAVE_BYTES - sizeof(RcDesc));
-  int* const fbScr = a.fbScratch + ((size_t)blockIdx.x * 4 + wave) * 8192;
+  const ItLds l = it_lds(smem, wave);
+  short* const tile = l.tile;
+  RcDesc* const dS = l.dS;
+  int* const fbScr = a.fbScratch + ((size_t)blockIdx.x * 4 + wave) * IT_FB_INTS;
 
   for (int item = (int)blockIdx.x * 4 + wave; item < a.n; item += (int)gridDim.x * 4)
   {
     const vvcgpu_intra_desc p = a.preds[item];
-    RcDesc t = a.tus[item];
-    const int w = t.w, h = t.h;
-    int mode = p.mode;
-    bool filt = p.filter_refs != 0;
-    bool ok = it_side_ok(w) && it_side_ok(h) && p.w == w && p.h == h && mode >= VVCGPU_INTRA_TU_FROM_LIST && mode <= VDIA &&
-              (mode != VVCGPU_INTRA_TU_PRED_GIVEN || a.pred != nullptr) &&
-              t.tr_hor >= 0 && t.tr_hor <= 2 && t.tr_ver >= 0 && t.tr_ver <= 2 && (w <= 32 || t.tr_hor == 0) && (h <= 32 || t.tr_ver == 0);
-    if (ok && mode == VVCGPU_INTRA_TU_FROM_LIST)
-    {
-      const int row = t.reserved[0], slot = t.reserved[1];
-      ok = a.modeList != nullptr && row >= 0 && slot >= 0 && slot < IT_LIST_MAX;
-      if (ok) ok = slot < a.modeList[IT_LIST_INTS * (size_t)row];
-      if (ok)
-      {
-        mode = a.modeList[IT_LIST_INTS * (size_t)row + IT_LIST_FIRST + slot];
-        ok = mode >= PLANAR && mode <= VDIA;
-        if (ok) filt = intra_use_filtered(w, h, mode, a.noSmoothing);
-      }
-    }
-    if (!ok)                                                              // skipped: the markers, nothing else
-    {
-      if (lane == 0) { a.absSum[item] = 0xFFFFFFFFu; a.numSig[item] = 0xFFFFFFFFu; a.dist[item] = ~0ull; a.modeOut[item] = -1; }
-      continue;
-    }
-    const int lw = ilog2(w), samples = w * h;
-
-    // ---- the prediction into the tile
-    if (mode == VVCGPU_INTRA_TU_PRED_GIVEN)
-    {
-      const Pel* src = a.pred + t.pred_off;
-      for (int e = lane; e < samples; e += 64) tile[e] = src[(ptrdiff_t)(e >> lw) * t.pred_stride + (e & (w - 1))];
-    }
-    else
-    {
-      vvcgpu_intra_desc d = p;
-      d.mode = (int8_t)mode; d.filter_refs = filt ? 1 : 0;
-      intra_pred_block(d, a.refs, tile, w, a.cmin, a.cmax, lane, topS, leftS, tmpS, mainS);
-    }
-    wave_sync();
+    const RcDesc t = a.tus[item];
+    int mode; bool filt;
+    if (!it_resolve(a, p, t, [] { return true; }, mode, filt)) { it_mark(a, item, lane); continue; }
+    const int w = t.w, h = t.h, lw = ilog2(w), samples = w * h;
+    it_predict(a, p, t, mode, filt, l, lane);
     if (a.writePred && mode >= 0)
     {
       Pel* dst = a.pred + t.pred_off;
@@ -153,9 +110,7 @@ __global__ __launch_bounds__(256, IT_WGS_PER_CU) void intra_tu_code_kernel(const
       it_tu_generic_call(dS, a.org, tile, a.rec, a.level, a.absSum + item, a.bd, a.cmin, a.cmax, tb.tr32, tb.dqInv, tb.scanOff, fbScr, fbScr + 4096, lane);
 
     // ---- what the wavefront has just written, read back: xGetSSE(org, rec) and the non-zero levels of the kept region
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
+    wave_global_sync();
     {
       const Pel* org = a.org + t.org_off;
       const Pel* rec = a.rec + t.rec_off;
@@ -199,7 +154,7 @@ extern "C" int vvcgpu_intra_tu_code_batch(const vvc_pel* refs_base, const vvcgpu
   if (rt) return rt;
   const int cap = IT_WGS_PER_CU * vvcgpu_cu_count(), wgs = cdiv(n, 4) < cap ? cdiv(n, 4) : cap;
   VvcScratch sc(st);
-  int* fbScratch = sc.take<int>((size_t)wgs * 4 * 8192);                  // per wavefront two 4096-int buffers, touched only for an item outside the matrix-core range
+  int* fbScratch = sc.take<int>((size_t)wgs * 4 * IT_FB_INTS);            // touched only for an item outside the matrix-core range
   if (!fbScratch) return VVCGPU_E_DEVICE;
   ItArgs a;
   a.refs = refs_base; a.preds = preds; a.org = org_base; a.pred = pred_base; a.rec = rec_base; a.level = level_base; a.tus = tus; a.modeList = mode_list;

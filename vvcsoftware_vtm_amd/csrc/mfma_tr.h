@@ -78,6 +78,18 @@ __device__ __forceinline__ void rc_load_all_tables(_Float16* tab, const _Float16
   rc_load_tables<32>(tab, image, tid);
   rc_load_tables<64>(tab, image, tid);
 }
+// the first BYTES of the image (all f16 matrices; a caller with the lane-group bodies takes their matrices behind them too) into the head of the
+// dynamic LDS of a workgroup of THREADS threads as one run of 16-byte loads, and the workgroup barrier behind it -- the only one of a kernel whose
+// wavefronts then walk their own work
+template <int THREADS, int BYTES = RC_TAB_HALVES * 2>
+__device__ __forceinline__ _Float16* rc_load_image(unsigned char* smem, const _Float16* image, int tid)
+{
+  static_assert(BYTES % 16 == 0, "16-byte loads");
+  const uint4* src = reinterpret_cast<const uint4*>(image);
+  for (int i = tid; i < BYTES / 16; i += THREADS) reinterpret_cast<uint4*>(smem)[i] = src[i];
+  __syncthreads();
+  return reinterpret_cast<_Float16*>(smem);
+}
 
 // matrix operand of a product whose OTHER operand is a result tile: row `row` of the LDS matrix, the eight k values of k-step s in result-tile
 // order -- k = 32 s + 4 g + j (j < 4, tile 2 s) and 32 s + 16 + 4 g + (j - 4) (tile 2 s + 1)
