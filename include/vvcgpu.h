@@ -1688,6 +1688,124 @@ int vvcgpu_intra_chroma_code_dq_batch(
     int flags, int bit_depth, int clp_min, int clp_max,
     uint32_t* abs_sum, uint64_t* dist, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- the compares of the intra RD loops and the commit of the winner ----
+ * vvcgpu_intra_luma_choose_batch: the transform loop of IntraSearch::xRecurIntraCodingLumaQT (EncoderLib/IntraSearch.cpp:1429-1588) inside the mode loop
+ * of estIntraPredLumaQT (:637-697) for n_pu PUs coded as one TU, over the outputs of ONE vvcgpu_intra_tu_code_batch / _dq_batch call (the same tus
+ * array; abs_sum, num_sig, dist, mode_out) and of a vvcgpu_resi_rate_batch call whose items are parallel to it (gate = abs_sum; frac_bits and,
+ * optionally, ctx_out).  One launch, a wavefront per PU, no host synchronisation: behind those calls on one stream nothing is downloaded before the
+ * winner's reconstruction lies in the picture plane, where vvcgpu_intra_chroma_code_batch (luma_base) and the next CU's vvcgpu_intra_fill_refs_batch
+ * read it.
+ *
+ * pus[p]       cand_first, n_modes (1..16), n_tr (1..5): candidate (mode slot m, transform index t) is item j = cand_first + m n_tr + t.
+ *              mpm[3], mode_bits[4]: the fractional bits of everything xEncIntraHeader codes (:1047-1063, the CU header bins included) for a mode equal
+ *              to mpm[0] / mpm[1] / mpm[2] / none of them, the four-value scheme of vvcgpu_intra_mode_cand_batch.  cbf_bits[2]: the cbf_comp bin 0 / 1
+ *              under QtCbf luma.  emt_cu_bits: emt_cu_flag as coded at :1049, 0 where it is not coded.  flags VVCGPU_INTRA_CHOOSE_*: EMT_FLAG =
+ *              cu.emtFlag; TS_LAST = checkTransformSkip, index n_tr - 1 is the transform-skip candidate; FAST_EMT = getFastIntraEMT() && isAllIntra.
+ *              rec_dst_off / rec_dst_stride: the PU's block in rec_dst_base; level_dst_off: its w h levels, pitch w, in level_dst_base.  reserved: 0.
+ * Per candidate j, every context involved being distinct and every candidate starting from ctxStart (:646, :1465):
+ *   valid       abs_sum[j] != 0xFFFFFFFF and, with abs_sum[j] > 0, frac_bits[j] != ~0.  A mode slot whose t = 0 candidate is not valid is passed over
+ *               whole (the FROM_LIST slots beyond the list); an invalid candidate at t > 0 is passed over alone.
+ *   bits        cbf = abs_sum[j] > 0; mode_bits[class of mode_out[j]] + cbf_bits[cbf] + (cbf ? emt_cu_bits + frac_bits[j] : 0): xGetIntraFracBitsQT(.., true,
+ *               false) (:1109-1128, :1047-1063, :1102).
+ *   cost        dist_scale * (double)dist[j] + (double)bits (RdCost::calcRdCost: a multiply, then an add), or MAX_DOUBLE by the rule of :1501-1502: the
+ *               transform-skip candidate with cbf 0; EMT_FLAG and t > 0 and not the transform-skip candidate and num_sig[j] <= 2 (g_EmtSigNumThr).
+ * Within a mode slot the candidates run in ascending t and are taken on cost < dSingleCost (:1524, start MAX_DOUBLE) with cbfBestMode tracked; under
+ * FAST_EMT a candidate with t > 0 that is not the transform-skip one is passed over while !cbfBestMode (:1449).  The slots run in ascending m and are
+ * taken on cost < csBest->cost (:664, start MAX_DOUBLE): of equal costs the earlier stays, and a slot whose candidates all cost MAX_DOUBLE never wins.
+ * cand_cost[j] the cost of every candidate that was evaluated (MAX_DOUBLE included); VVCGPU_INTRA_CHOOSE_PASSED, a NaN pattern to be compared as 64
+ *              bits, for a candidate that was passed over or is invalid.  m_modeCostStore[m] is the minimum over t.  Entries outside the range of
+ *              every PU inside the contract are not written.
+ * result[p]    best_cand (the winner's j, or -1), best_mode (its mode_out), best_tr (its t), cbf, dist, bits, cost.  Without a winner: -1, -1, -1, 0,
+ *              ~0, ~0, MAX_DOUBLE and nothing committed (the early return).
+ * Commit, for a PU with a winner j*: the w x h reconstruction at tus[j*].rec_off / rec_stride of rec_base goes to rec_dst_base (:1650, the copy into the
+ * picture), the w h levels at tus[j*].level_off of level_base to level_dst_base, and -- when ctx_out and ctx_best are given -- row j* of ctx_out
+ * (VVCGPU_RESI_RATE_CTX_BYTES bytes) to row p of ctx_best (ctxBest of :1555).  Nothing else in the destinations is touched.  Rows are moved in 8-byte
+ * words where source and destination row are both 8-byte aligned (luma blocks lie at multiples of 4 samples), else in 4-byte or 2-byte ones.
+ * A PU outside the contract comes back without a winner and is never a fault: n_modes / n_tr out of range, a candidate range leaving [0, n), candidates
+ * disagreeing on w / h, a side outside 4..64 or not a power of two, unknown flag bits, a reserved word that is not 0.  Offsets cannot be validated.
+ * The destination blocks of different PUs must not overlap, nor the destinations the candidate buffers.
+ * VVCGPU_E_ARG before any device work: a null required pointer (ctx_out and ctx_best may be NULL, both or none), negative n_pu or n, pus / tus / result
+ * not 16-byte aligned, a 64-bit array not 8-byte aligned.  n_pu == 0 is a no-op.
+ * With the caller: the header and cbf bits (estFracBits of the contexts at ctxStart), the context snapshot, reading result[].
+ * Not served: TUs split below the PU, checkInitTrDepthTransformSkipWinner, lossless, DF_SSE_WTD.                                                   */
+#define VVCGPU_INTRA_CHOOSE_EMT_FLAG  1
+#define VVCGPU_INTRA_CHOOSE_TS_LAST   2
+#define VVCGPU_INTRA_CHOOSE_FAST_EMT  4
+#define VVCGPU_INTRA_CHOOSE_PASSED    0x7FF8000000564356ull   /* cand_cost / slot_cost of a candidate that was not evaluated */
+struct vvcgpu_intra_choose_pu {
+  int64_t  rec_dst_off, level_dst_off;
+  uint64_t mode_bits[4], cbf_bits[2], emt_cu_bits;
+  int32_t  cand_first, rec_dst_stride;
+  int16_t  n_modes, n_tr;
+  int8_t   mpm[3], flags;
+  int32_t  reserved[2];                    /* sizeof == 96 */
+};
+struct vvcgpu_intra_choose_result {
+  int32_t  best_cand, best_mode, best_tr, cbf;
+  uint64_t dist, bits;
+  double   cost;
+  int64_t  reserved;                       /* 0; sizeof == 48 */
+};
+int vvcgpu_intra_luma_choose_batch(
+    const struct vvcgpu_intra_choose_pu* pus, int n_pu,
+    const vvcgpu_resi_chain_desc* tus, int n,
+    const uint32_t* abs_sum, const uint32_t* num_sig, const uint64_t* dist, const int32_t* mode_out, const uint64_t* frac_bits, double dist_scale,
+    const vvc_pel* rec_base, const vvc_coef* level_base,
+    const uint8_t* ctx_out,                    /* may be NULL */
+    vvc_pel* rec_dst_base, vvc_coef* level_dst_base,
+    uint8_t* ctx_best,                         /* may be NULL */
+    double* cand_cost, struct vvcgpu_intra_choose_result* result, void* stream);
+
+/* vvcgpu_intra_chroma_choose_batch: the mode loop of IntraSearch::estIntraPredChromaQT (EncoderLib/IntraSearch.cpp:773-847) over the outputs of ONE
+ * vvcgpu_intra_chroma_code_batch / _dq_batch call -- the same pus array, abs_sum / dist at 12 p + 2 k + c -- and of the rate of its level blocks at the
+ * same index.  The Cr block of a slot is coded behind its Cb block (:1122-1123), so its contexts start from Cb's.  Two vvcgpu_resi_rate_batch calls
+ * over 12 n items each (gate = abs_sum) do it: the first serves the Cb items from the ctxStart row with ctx_out (its Cr items carry w = 0 and are
+ * skipped) and gives frac_bits_cb; the second serves the Cr items with ctx = that ctx_out and ctx_idx = 12 p + 2 k, the Cb item's index (its Cb
+ * items are skipped) and gives frac_bits_cr and, on request, the ctx_out this entry takes.  A Cb block without a level leaves its row as it was, so
+ * the Cr block behind it starts from ctxStart, as in the reference.  One launch, a wavefront per PU, no host synchronisation.
+ *
+ * cpus[p]      mode_bits[6]: intra_chroma_pred_mode of each slot.  cbf_cb_bits[2]: the cbf_comp bin 0 / 1 of Cb.  cbf_cr_bits[4]: index 2 cbf_cb + cbf_cr,
+ *              the context CtxQtCbf selects from Cb's cbf (:1003).  dist_weight[2]: the chroma distortion weight of Cb / Cr.  rec_dst_off[c] /
+ *              rec_dst_stride: the component's block in rec_dst_base; level_dst_off[c]: its w h levels in level_dst_base.  reserved: 0.
+ * pus[p]       what the pixel pass took: w, h (powers of two 2..64), mode[6], cand_off, level_off -- item (k, c) owns the w x h block at
+ *              cand_off + (2 k + c) w h of cand_rec_base and at level_off + (2 k + c) w h of level_base.
+ * A slot k is a candidate when mode[k] != -1, neither abs_sum is 0xFFFFFFFF and a component with levels has frac_bits != ~0.  With cbf_c = abs_sum > 0:
+ *   bits = mode_bits[k] + cbf_cb_bits[cbf_cb] + cbf_cr_bits[2 cbf_cb + cbf_cr] + the frac_bits of the components with levels   (xGetIntraFracBitsQT(.., false, true) :798)
+ *   dist = D_cb + D_cr, D_c = (uint64_t)(dist_weight[c] * (double)dist[..])                                             (RdCost::getDistPart :408)
+ *   cost = dist_scale * (double)dist + (double)bits                                                                     (:800, uiDist - baseDist)
+ * The slots run in ascending k and are taken on cost < dBestCost (:803, start MAX_DOUBLE).
+ * slot_cost[6 p + k] the cost of a candidate slot, VVCGPU_INTRA_CHOOSE_PASSED otherwise.
+ * result[p]    best_slot, best_mode (mode[best_slot]), cbf[2], dist, bits, cost; without a winner -1, -1, 0, 0, ~0, ~0, MAX_DOUBLE, nothing committed.
+ * Commit (:828-838): both components' reconstruction (rows of the candidate block are w apart) to rec_dst_base and levels to level_dst_base, and with
+ * ctx_out and ctx_best row 12 p + 2 k* + 1 of ctx_out, the contexts behind the Cr block, to row p of ctx_best.  Chroma blocks lie at multiples of 2
+ * samples: rows move in 8-byte words where both rows allow it, else in 4-byte or 2-byte ones.
+ * A PU outside the contract -- a side outside 2..64 or not a power of two, a reserved word that is not 0 -- comes back without a winner, never a fault.
+ * VVCGPU_E_ARG before any device work: a null required pointer (ctx_out and ctx_best may be NULL, both or none), negative n, n above (2^31 - 1) / 12,
+ * cpus / pus / result not 16-byte aligned, a 64-bit array not 8-byte aligned.  n == 0 is a no-op.
+ * With the caller: the mode and cbf bits, the weights, the context snapshot, reading result[].  4:2:0.
+ * Not served: transform-skip and cross-component candidates (the loop of :1751-1819).                                                              */
+struct vvcgpu_intra_chroma_choose_pu {
+  uint64_t mode_bits[6], cbf_cb_bits[2], cbf_cr_bits[4];
+  double   dist_weight[2];
+  int64_t  rec_dst_off[2], level_dst_off[2];
+  int32_t  rec_dst_stride;
+  int32_t  reserved[3];                    /* sizeof == 160 */
+};
+struct vvcgpu_intra_chroma_choose_result {
+  int32_t  best_slot, best_mode, cbf[2];
+  uint64_t dist, bits;
+  double   cost;
+  int64_t  reserved;                       /* 0; sizeof == 48 */
+};
+int vvcgpu_intra_chroma_choose_batch(
+    const struct vvcgpu_intra_chroma_choose_pu* cpus, const vvcgpu_intra_chroma_pu* pus, int n,
+    const uint32_t* abs_sum, const uint64_t* dist, const uint64_t* frac_bits_cb, const uint64_t* frac_bits_cr, double dist_scale,
+    const vvc_pel* cand_rec_base, const vvc_coef* level_base,
+    const uint8_t* ctx_out,                    /* may be NULL */
+    vvc_pel* rec_dst_base, vvc_coef* level_dst_base,
+    uint8_t* ctx_best,                         /* may be NULL */
+    double* slot_cost, struct vvcgpu_intra_chroma_choose_result* result, void* stream);
+
 /* N4, CCLM: cross-component linear model prediction of a chroma block  (IntraPrediction::xGetLumaRecPixels :1283-1581, the
  * JVET_K0190 branch, + xGetLMParameters :1597-1857 + predIntraChromaLM :390-403).  4:2:0 only.  luma_off: the co-located luma
  * block's top-left sample in the luma RECONSTRUCTION plane (rows -2, -1 are read when above_avail, columns -3 .. -1 when left_avail);

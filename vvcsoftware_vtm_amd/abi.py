@@ -143,6 +143,19 @@ RESI_RATE_ITEM = np.dtype([("level_off", "<i8"), ("ctx_idx", "<i4"), ("w", "<i2"
 RESI_RATE_CTX_BYTES, RESI_RATE_CTX_USED = 192, 180
 RESI_RATE_LAST_X, RESI_RATE_LAST_Y, RESI_RATE_SIG_GROUP, RESI_RATE_SIG, RESI_RATE_PAR = 0, 25, 50, 52, 112
 RESI_RATE_GT2, RESI_RATE_GT1, RESI_RATE_TS, RESI_RATE_EMT = 133, 154, 175, 176
+# vvcgpu_intra_luma_choose_batch / vvcgpu_intra_chroma_choose_batch: one PU and its result (struct vvcgpu_intra_choose_pu, _result, struct
+# vvcgpu_intra_chroma_choose_pu, _result), the flags, and the 64 bits of a cost that was not formed
+INTRA_CHOOSE_PU = np.dtype([("rec_dst_off", "<i8"), ("level_dst_off", "<i8"), ("mode_bits", "<u8", (4,)), ("cbf_bits", "<u8", (2,)), ("emt_cu_bits", "<u8"),
+                            ("cand_first", "<i4"), ("rec_dst_stride", "<i4"), ("n_modes", "<i2"), ("n_tr", "<i2"), ("mpm", "i1", (3,)), ("flags", "i1"),
+                            ("reserved", "<i4", (2,))])
+INTRA_CHOOSE_RESULT = np.dtype([("best_cand", "<i4"), ("best_mode", "<i4"), ("best_tr", "<i4"), ("cbf", "<i4"), ("dist", "<u8"), ("bits", "<u8"),
+                                ("cost", "<f8"), ("reserved", "<i8")])
+INTRA_CHROMA_CHOOSE_PU = np.dtype([("mode_bits", "<u8", (6,)), ("cbf_cb_bits", "<u8", (2,)), ("cbf_cr_bits", "<u8", (4,)), ("dist_weight", "<f8", (2,)),
+                                   ("rec_dst_off", "<i8", (2,)), ("level_dst_off", "<i8", (2,)), ("rec_dst_stride", "<i4"), ("reserved", "<i4", (3,))])
+INTRA_CHROMA_CHOOSE_RESULT = np.dtype([("best_slot", "<i4"), ("best_mode", "<i4"), ("cbf", "<i4", (2,)), ("dist", "<u8"), ("bits", "<u8"), ("cost", "<f8"),
+                                       ("reserved", "<i8")])
+INTRA_CHOOSE_EMT_FLAG, INTRA_CHOOSE_TS_LAST, INTRA_CHOOSE_FAST_EMT = 1, 2, 4
+INTRA_CHOOSE_PASSED = 0x7FF8000000564356
 
 # ---- affine motion --------------------------------------------------------------------------------------------------------------
 AFG_DESC = np.dtype([("pred_off", "<i8"), ("deriv_off", "<i8"), ("pred_stride", "<i4"), ("deriv_stride", "<i4"), ("w", "<i2"), ("h", "<i2"),

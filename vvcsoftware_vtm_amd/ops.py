@@ -9,7 +9,7 @@ import torch
 from . import capi
 # the struct mirrors live in abi; bench.py, the tests and the tools read them as ops.<NAME>
 from .abi import (AFE_DESC, AFFINE_ITER, AFFINE_ME_ITEM, AFFINE_ME_MAX_STEPS, AFFINE_ME_RESULT, AFFINE_ME_STEP, AFFINE_PU, AFG_DESC, CCLM_DESC, DEPQUANT_DESC, DIST_DESC, DQ_RATES, DQTR_DESC, FRAC_BLK,  # noqa: F401
-                  FRAC_RESULT, IF_DESC, IMV_PU, IMV_RESULT, INTER_RESI_DQ, INTER_RESI_ITEM, INTER_RESI_Q_DEPQUANT, INTER_RESI_SLOTS, INTER_RESI_TS, INTER_RESI_WRITE_REC, INTRA_DESC, INTRA_FILL_DESC, INTRA_SATD_DESC, INTRA_CHROMA_LM, INTRA_CHROMA_PU, INTRA_CHROMA_Q_DEPQUANT, INTRA_CHROMA_WRITE_PRED, INTRA_TU_FROM_LIST, INTRA_TU_NO_SMOOTHING, INTRA_TU_PRED_GIVEN, INTRA_TU_Q_DEPQUANT, INTRA_TU_WRITE_PRED, MC_DESC, PELOP_DESC, QUANT_DESC, RC_DESC, RESI_RATE_CTX_BYTES, RESI_RATE_ITEM,
+                  FRAC_RESULT, IF_DESC, IMV_PU, IMV_RESULT, INTER_RESI_DQ, INTER_RESI_ITEM, INTER_RESI_Q_DEPQUANT, INTER_RESI_SLOTS, INTER_RESI_TS, INTER_RESI_WRITE_REC, INTRA_DESC, INTRA_FILL_DESC, INTRA_SATD_DESC, INTRA_CHROMA_LM, INTRA_CHROMA_PU, INTRA_CHROMA_Q_DEPQUANT, INTRA_CHROMA_WRITE_PRED, INTRA_CHOOSE_PU, INTRA_CHOOSE_RESULT, INTRA_CHROMA_CHOOSE_PU, INTRA_CHROMA_CHOOSE_RESULT, INTRA_CHOOSE_PASSED, INTRA_TU_FROM_LIST, INTRA_TU_NO_SMOOTHING, INTRA_TU_PRED_GIVEN, INTRA_TU_Q_DEPQUANT, INTRA_TU_WRITE_PRED, MC_DESC, PELOP_DESC, QUANT_DESC, RC_DESC, RESI_RATE_CTX_BYTES, RESI_RATE_ITEM,
                   RDOQ_DESC, RDOQ_RATES, RDPCM_DESC, SAO_DTYPE, SEARCH_BEST, SEARCH_BLK, TR_DESC, TZ_CFG, TZ_PU, DeblockCfg, MeHierCfg, MvCost,
                   PelopCfg, Planes, AffineMeCfg, BipredMeCfg, BIPRED_ME_ITEM, BIPRED_ME_MAX_PLANES, BIPRED_ME_MAX_REFS, BIPRED_ME_MAX_STEPS, BIPRED_ME_REF,
                   BIPRED_ME_RESULT, BIPRED_ME_STEP, AffineBipredCfg, AFFINE_BIPRED_ITEM, AFFINE_BIPRED_MAX_REFS, AFFINE_BIPRED_MAX_STEPS,
@@ -419,6 +419,42 @@ def inter_resi_choose_batch(items_dev, n, abs_sum, dist_resi, zero_dist, frac_bi
               capi.ptr(cbf_bits), capi.ptr(prev), capi.ptr(dist_weight), C.c_double(dist_scale), capi.ptr(slot), capi.ptr(cbf), capi.ptr(abs_out),
               capi.ptr(dist), capi.ptr(bits), capi.ptr(min_cost), _stream())
     return slot, cbf, abs_out, dist, bits, min_cost
+
+
+def intra_luma_choose_batch(pus_dev, n_pu, tus_dev, n, abs_sum, num_sig, dist, mode_out, frac_bits, dist_scale, rec_base, level_base, rec_dst_base,
+                            level_dst_base, ctx_out=None, ctx_best=None, cand_cost=None):
+    """the compare of the intra luma RD loops and the commit of the winner (vvcgpu_intra_luma_choose_batch) over the outputs of intra_tu_code_batch /
+    _dq_batch (tus_dev, abs_sum, num_sig, dist, mode_out, rec_base, level_base) and of resi_rate_batch (frac_bits [n]; ctx_out, its rows, with ctx_best
+    uint8 [n_pu][RESI_RATE_CTX_BYTES]): pus_dev a device copy of an INTRA_CHOOSE_PU array; the winners go to rec_dst_base / level_dst_base / ctx_best.
+    -> (cand_cost float64 [n] (INTRA_CHOOSE_PASSED where no cost was formed; entries outside the range of every PU inside the contract are not written:
+    they keep what a given cand_cost tensor holds), result: uint8 tensor of n_pu INTRA_CHOOSE_RESULT records)"""
+    dv = abs_sum.device
+    if cand_cost is None:
+        cand_cost = torch.empty(n, dtype=torch.float64, device=dv)
+    assert cand_cost.dtype == torch.float64 and cand_cost.numel() == n and cand_cost.is_contiguous()
+    result = torch.empty(n_pu * INTRA_CHOOSE_RESULT.itemsize, dtype=torch.uint8, device=dv)
+    capi.call("vvcgpu_intra_luma_choose_batch", capi.ptr(pus_dev), n_pu, capi.ptr(tus_dev), n, capi.ptr(abs_sum), capi.ptr(num_sig), capi.ptr(dist),
+              capi.ptr(mode_out), capi.ptr(frac_bits), C.c_double(dist_scale), capi.ptr(rec_base), capi.ptr(level_base), capi.ptr(ctx_out),
+              capi.ptr(rec_dst_base), capi.ptr(level_dst_base), capi.ptr(ctx_best), capi.ptr(cand_cost), capi.ptr(result), _stream())
+    return cand_cost, result
+
+
+def intra_chroma_choose_batch(cpus_dev, pus_dev, n, abs_sum, dist, frac_bits_cb, frac_bits_cr, dist_scale, cand_rec_base, level_base, rec_dst_base,
+                              level_dst_base, ctx_out=None, ctx_best=None, slot_cost=None):
+    """the compare of the intra chroma mode loop and the commit of the winner (vvcgpu_intra_chroma_choose_batch) over the outputs of
+    intra_chroma_code_batch / _dq_batch (pus_dev, abs_sum, dist [n][6][2], cand_rec_base, level_base) and of the two resi_rate_batch calls over its 12 n
+    level blocks (frac_bits_cb, frac_bits_cr [12 n]; ctx_out, the rows of the second, with ctx_best uint8 [n][RESI_RATE_CTX_BYTES]): cpus_dev a device copy
+    of an INTRA_CHROMA_CHOOSE_PU array.
+    -> (slot_cost float64 [n][6] (INTRA_CHOOSE_PASSED where the slot is no candidate), result: uint8 tensor of n INTRA_CHROMA_CHOOSE_RESULT records)"""
+    dv = abs_sum.device
+    if slot_cost is None:
+        slot_cost = torch.empty((n, 6), dtype=torch.float64, device=dv)
+    assert slot_cost.dtype == torch.float64 and slot_cost.numel() == 6 * n and slot_cost.is_contiguous()
+    result = torch.empty(n * INTRA_CHROMA_CHOOSE_RESULT.itemsize, dtype=torch.uint8, device=dv)
+    capi.call("vvcgpu_intra_chroma_choose_batch", capi.ptr(cpus_dev), capi.ptr(pus_dev), n, capi.ptr(abs_sum), capi.ptr(dist), capi.ptr(frac_bits_cb),
+              capi.ptr(frac_bits_cr), C.c_double(dist_scale), capi.ptr(cand_rec_base), capi.ptr(level_base), capi.ptr(ctx_out), capi.ptr(rec_dst_base),
+              capi.ptr(level_dst_base), capi.ptr(ctx_best), capi.ptr(slot_cost), capi.ptr(result), _stream())
+    return slot_cost, result
 
 
 def imv_refine_batch(org, ref, pus_dev, n, cfg, use_hadamard=True, weight=1.0):
