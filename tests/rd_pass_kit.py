@@ -35,6 +35,16 @@ def side_ok(v, lo):
     return lo <= v <= 64 and (v & (v - 1)) == 0
 
 
+def cost_of(scale, dist, bits):
+    """RdCost::calcRdCost: a multiply, then an add, in doubles"""
+    return float(np.float64(scale) * np.float64(int(dist)) + np.float64(int(bits)))
+
+
+def weighted(weight, x):
+    """RdCost::getDistPart :408"""
+    return int(np.float64(weight) * np.float64(int(x)))
+
+
 def block(buf, off, stride, w, h):
     """the h x w view of a flat buffer"""
     return np.lib.stride_tricks.as_strided(buf[off:], (h, w), (stride * buf.itemsize, buf.itemsize))
@@ -153,11 +163,16 @@ def download(tensors, names, views=VIEWS):
     return out
 
 
-def same(got, want, keys):
-    """bit for bit over whole buffers (the canaries are part of the comparison); reports the first differing indices"""
+def same(got, want, keys, bytewise=False):
+    """bit for bit over whole buffers (the canaries are part of the comparison); reports the first differing indices.  bytewise: as bytes, for outputs that
+    hold costs (compared as 64 bits: the marker of an untouched one is a NaN)"""
     for k in keys:
         g, w = got[k], want[k]
-        assert np.array_equal(g, w), (k, np.flatnonzero(np.asarray(g).reshape(-1) != np.asarray(w).reshape(-1))[:8])
+        if bytewise:
+            g, w = np.ascontiguousarray(g), np.ascontiguousarray(w)
+            assert g.tobytes() == w.tobytes(), (k, np.flatnonzero(g.view(np.uint8).reshape(-1) != w.view(np.uint8).reshape(-1))[:8])
+        else:
+            assert np.array_equal(g, w), (k, np.flatnonzero(np.asarray(g).reshape(-1) != np.asarray(w).reshape(-1))[:8])
 
 
 @functools.lru_cache(maxsize=None)

@@ -6,7 +6,7 @@
 //
 // Design: one wavefront per PU.  Sobel: every output sample is the 3x3 response at the nearest INTERIOR position (that is what
 // the reference's ring-copy rules amount to), so the ring needs no second pass.  Equal coefficients: every lane walks its
-// share of the block with the <= 6 x 7 sums in 64-bit registers, then one transposed wave reduction (63 shuffles for all sums).
+// share of the block with the <= 6 x 7 sums in 64-bit registers, then one transposed wave reduction (at most 49 shuffles for all sums).
 #include "common.h"
 #include "dist_dev.h"
 #include "afi_dev.h"
@@ -38,6 +38,10 @@ template <int P>
 __device__ __forceinline__ void eq_accumulate(const Pel* __restrict__ resi, const int* __restrict__ gx, const int* __restrict__ gy, int stride,
                                               int w, int h, int tid, long long (&acc)[P][P + 1])
 {
+#pragma unroll
+  for (int c = 0; c < P; c++)
+#pragma unroll
+    for (int r = 0; r <= P; r++) acc[c][r] = 0;
   for (int i = tid; i < w * h; i += 64)
   {
     const int j = i / w, k = i - j * w;
@@ -57,31 +61,13 @@ __device__ __forceinline__ void eq_accumulate(const Pel* __restrict__ resi, cons
   }
 }
 
-// one wavefront per PU: every lane accumulates its samples, one transposed reduction, lanes 0 .. P (P + 1) - 1 hold the sums
+// one wavefront per PU: every lane accumulates its samples, then the transposed reduction and out[row7][col7] of afi_dev.h (rows 1..P hold the
+// equations, everything else is zero)
 template <int P>
 __device__ __forceinline__ void eq_block(const vvcgpu_afe_desc& d, const Pel* resiBase, const int* gxBase, const int* gyBase, long long* out, int lane)
 {
-  long long acc[P][P + 1];
-#pragma unroll
-  for (int c = 0; c < P; c++)
-#pragma unroll
-    for (int r = 0; r <= P; r++) acc[c][r] = 0;
-  eq_accumulate<P>(resiBase + d.resi_off, gxBase + d.deriv_off, gyBase + d.deriv_off, d.deriv_stride, d.w, d.h, lane, acc);
-  constexpr int M = P == 6 ? 64 : 32;
-  long long v[M];
-#pragma unroll
-  for (int i = 0; i < M; i++) v[i] = i < P * (P + 1) ? acc[i / (P + 1)][i % (P + 1)] : 0;
-  const long long total = wave_transpose_sum<M>(v, lane);       // lane L: sum of value L = acc[L / (P + 1)][L % (P + 1)]
-  // out[row7][col7]; rows 1..P hold the equations, everything else is zero
-  if (lane < 49)
-  {
-    const int row7 = lane / 7, col7 = lane - row7 * 7;
-    const bool used = row7 >= 1 && row7 <= P && col7 <= P;
-    const int src = used ? (row7 - 1) * (P + 1) + col7 : 0;
-    long long val = __shfl(total, src);
-    out[lane] = used ? val : 0;
-  }
-  else (void)__shfl(total, 0);
+  afi_reduce_publish<P, 64>([&](long long (&acc)[P][P + 1])
+  { eq_accumulate<P>(resiBase + d.resi_off, gxBase + d.deriv_off, gyBase + d.deriv_off, d.deriv_stride, d.w, d.h, lane, acc); }, out, nullptr, lane);
 }
 
 __global__ __launch_bounds__(256) void affine_equal_coeff_kernel(const Pel* __restrict__ resiBase, const int* __restrict__ gxBase,

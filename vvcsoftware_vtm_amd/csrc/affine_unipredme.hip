@@ -100,7 +100,7 @@ __device__ __forceinline__ void aup_search(const vvcgpu_affine_unipred_item* __r
     for (int k = 0; k < 3; k++)
 #pragma unroll
       for (int d = 0; d < 2; d++) tv[k][d] = t < 2 ? a.mv_cand[t][k][d] : t == 2 ? a.hevc_mv[d] : four[k][d];
-    const unsigned long long v = aup_template_sad<NT>(u, org, tv, L, tid) + pu_getcost(c.lambda, c.mvp_idx_cost[t < 2 ? t : mvpIdx]);
+    const unsigned long long v = aup_template_sad<NT>(u, org, tv, L, tid) + rd_getcost(c.lambda, c.mvp_idx_cost[t < 2 ? t : mvpIdx]);
     if (t < 2)
     {
       if (t == 0) tm0 = v; else tm1 = v;
@@ -208,9 +208,9 @@ __global__ __launch_bounds__(256) void affine_unipred_decide_kernel(const vvcgpu
 #pragma unroll
         for (int k = 0; k < 3; k++) { pred[k][0] = a.mv_cand[mvpIdx][k][0]; pred[k][1] = a.mv_cand[mvpIdx][k][1]; mv[k][0] = s0.mv[k][0]; mv[k][1] = s0.mv[k][1]; }
         unsigned long long cost = s0.cost;
-        cost -= pu_getcost(c.lambda, s0.bits);
+        cost -= rd_getcost(c.lambda, s0.bits);
         unsigned bits = afm_bits(s.bits, pred, nmv, mv);
-        cost += pu_getcost(c.lambda, bits);
+        cost += rd_getcost(c.lambda, bits);
         afm_check_best_mvp(a.mv_cand, a.num_cand, c.mvp_idx_cost, c.lambda, nmv, mv, pred, mvpIdx, bits, cost);
 #pragma unroll
         for (int k = 0; k < 3; k++) { s.mv[k][0] = mv[k][0]; s.mv[k][1] = mv[k][1]; }

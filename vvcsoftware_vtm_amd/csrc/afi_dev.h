@@ -1,30 +1,9 @@
 // afi_dev.h -- device functions of the affine gradient search shared by the per-iteration entry (affine.hip) and the whole-PU search
-// (affine_me.hip): the transposed wave reduction, the error / Sobel / normal-equation pass and the distortion over a prediction held in LDS.
+// (affine_me.hip, afm_dev.h): the transposed wave reduction, the error / Sobel / normal-equation pass and the distortion over a prediction held in LDS.
 // Reference behaviour: AffineGradientSearch.cpp:66-174, InterSearch.cpp:3446-3534 (see affine.hip).
 #pragma once
 #include "common.h"
 #include "dist_dev.h"
-
-// Sum M = 64 (or 32) per-lane values over the wavefront with a halving butterfly: at every step a lane keeps one half of its
-// values and hands the other half to its partner, so 63 (31 + 1) shuffles replace 6 per value; lane L ends with the total of value L.
-template <int M>
-__device__ __forceinline__ long long wave_transpose_sum(long long (&v)[M], int lane)
-{
-  static_assert(M == 64 || M == 32, "M");
-#pragma unroll
-  for (int s = M / 2, len = M; s > 0; s >>= 1, len >>= 1)
-  {
-    const bool up = (lane & s) != 0;
-#pragma unroll
-    for (int i = 0; i < len / 2; i++)
-    {
-      const long long keep = up ? v[i + len / 2] : v[i], send = up ? v[i] : v[i + len / 2];
-      v[i] = keep + __shfl_xor(send, s);
-    }
-  }
-  if (M == 32) v[0] += __shfl_xor(v[0], 32);
-  return v[0];
-}
 
 constexpr int AFI_MAX = 128, AFI_WAVE_MAX = 1024;          // PUs of up to AFI_WAVE_MAX samples are served by one wavefront each, larger ones by a workgroup
 typedef const __attribute__((address_space(3))) Pel* AfiLdsPel;
@@ -81,23 +60,9 @@ __device__ __forceinline__ void afi_publish(long long total, long long* out, lon
   }
 }
 
-template <int P, int NT>
-__device__ __forceinline__ void afi_equations(const vvcgpu_affine_iter& d, const Pel* __restrict__ org, const Pel* predL, int w, int h, long long* out,
-                                              long long (*red)[64], int tid)
-{
-  long long acc[P][P + 1];
-  afi_accumulate<P, NT>(d, org, predL, w, h, acc, tid);
-  constexpr int M = P == 6 ? 64 : 32;
-  long long v[M];
-#pragma unroll
-  for (int i = 0; i < M; i++) v[i] = i < P * (P + 1) ? acc[i / (P + 1)][i % (P + 1)] : 0;
-  const long long total = wave_transpose_sum<M>(v, tid & 63);   // lane L: this wave's sum of value L
-  afi_publish<P, NT>(total, out, red, tid);
-}
-
-// The halving butterfly of wave_transpose_sum, one stage per instantiation: every index is a constant, so v stays in registers (the loops of
-// wave_transpose_sum are not unrolled by the compiler and its v[] lives in scratch memory).  v[0] of lane L ends as the sum of value L % LEN over
-// the LEN lanes that share L / LEN.
+// The transposed wave reduction: sums of per-lane values over the wavefront with a halving butterfly.  At every stage a lane keeps one half of its
+// values and hands the other half to its partner, so LEN - 1 shuffles replace 6 per value.  One stage per instantiation: every index is a constant, so
+// v stays in registers.  v[0] of lane L ends as the sum of value L % LEN over the LEN lanes that share L / LEN.
 template <int LEN>
 __device__ __forceinline__ void afi_fold(long long (&v)[LEN], int lane)
 {
@@ -117,15 +82,15 @@ __device__ __forceinline__ void afi_fold(long long (&v)[LEN], int lane)
   }
 }
 
-// afi_equations with the reduction in registers only, 32 values at a time (at most 32 + 16 for the 42 sums of the 6-parameter model: 64 registers
-// instead of 128, 49 shuffles instead of 63); integer sums, so the result is the same whatever the order
-template <int P, int NT, class OrgPtr = const Pel*>
-__device__ __forceinline__ void afi_equations_regs(const vvcgpu_affine_iter& d, OrgPtr __restrict__ org, const Pel* predL, int w, int h,
-                                                   long long* out, long long (*red)[64], int tid)
+// accumulate(acc) fills acc[P][P + 1], this lane's share of the sums (a callable, so that acc lives here: handing the array in changes the instruction
+// streams of the whole-PU searches); then over the wavefront and into out[7][7], 32 values at a time (at most 32 + 16 for the 42 sums of the
+// 6-parameter model: 64 registers, 49 shuffles); integer sums, so the result is the same whatever the order
+template <int P, int NT, class Accumulate>
+__device__ __forceinline__ void afi_reduce_publish(Accumulate accumulate, long long* out, long long (*red)[64], int tid)
 {
   const int lane = tid & 63;
   long long acc[P][P + 1];
-  afi_accumulate<P, NT, OrgPtr>(d, org, predL, w, h, acc, tid);
+  accumulate(acc);
   long long a[32];
 #pragma unroll
   for (int i = 0; i < 32; i++) a[i] = i < P * (P + 1) ? acc[i / (P + 1)][i % (P + 1)] : 0;
@@ -144,6 +109,14 @@ __device__ __forceinline__ void afi_equations_regs(const vvcgpu_affine_iter& d, 
   afi_publish<P, NT>(total, out, red, tid);
 }
 
+// the normal equations of one iteration: the error / Sobel pass over the PU, then the sums into out[7][7]
+template <int P, int NT, class OrgPtr = const Pel*>
+__device__ __forceinline__ void afi_equations(const vvcgpu_affine_iter& d, OrgPtr __restrict__ org, const Pel* predL, int w, int h, long long* out,
+                                              long long (*red)[64], int tid)
+{
+  afi_reduce_publish<P, NT>([&](long long (&acc)[P][P + 1]) { afi_accumulate<P, NT, OrgPtr>(d, org, predL, w, h, acc, tid); }, out, red, tid);
+}
+
 // distortion of rows [r0, r1) x 16 of the PU against the prediction in LDS, by one wavefront
 template <class OrgPtr = const Pel*>
 __device__ __forceinline__ unsigned long long afi_dist(const vvcgpu_affine_iter& d, OrgPtr __restrict__ org, const Pel* predL, int w, int h,
@@ -160,7 +133,7 @@ __device__ __forceinline__ unsigned long long afi_dist(const vvcgpu_affine_iter&
     {
       unsigned s = 0;
       for (int i = lane; i < 16 * w; i += 64) { const int j = i / w, k = i - j * w; s += (unsigned)abs((int)o[(size_t)j * d.org_stride + k] - (int)c[j * w + k]); }
-      sum += wave_sum_u64(s);
+      sum += wave_sum((unsigned long long)s);
     }
   }
   return sum;

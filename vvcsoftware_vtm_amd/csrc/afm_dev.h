@@ -258,7 +258,7 @@ __device__ __forceinline__ void afm_check_best_mvp(const int32_t (&cand)[2][3][2
     mvpIdx = bestIdx;
     const unsigned orgB = bits;
     bits = orgB - (unsigned)orgBits + (unsigned)bestBits;
-    cost = (cost - pu_getcost(lambda, orgB)) + pu_getcost(lambda, bits);
+    cost = (cost - rd_getcost(lambda, orgB)) + rd_getcost(lambda, bits);
   }
 }
 
@@ -349,8 +349,8 @@ __device__ __forceinline__ void afm_search_body(const AfmPu& u, OrgPtr org, doub
   d.org_stride = u.os;
   for (int iter = 0; iter < iterTime; iter++)
   {
-    if (u.six) afi_equations_regs<6, NT, OrgPtr>(d, org, L.predL, u.w, u.h, L.eq, L.red, tid);
-    else       afi_equations_regs<4, NT, OrgPtr>(d, org, L.predL, u.w, u.h, L.eq, L.red, tid);
+    if (u.six) afi_equations<6, NT, OrgPtr>(d, org, L.predL, u.w, u.h, L.eq, L.red, tid);
+    else       afi_equations<4, NT, OrgPtr>(d, org, L.predL, u.w, u.h, L.eq, L.red, tid);
     owner_sync<NT>();
     int delta[3][2];
     if (u.six) afm_deltas<6>(L.eq, u.w, u.h, delta);

@@ -17,22 +17,11 @@
 // Per-lane partials are 32 bit only over a band (<= 64 samples a lane, see the bounds at each kernel), 64 bit from the wave reduction on.
 #include <math.h>
 #include "common.h"
+#include "wave_dev.h"
 
 namespace {
 
 typedef unsigned long long u64;
-
-__device__ __forceinline__ u64 shfl_xor64(u64 v, int m)
-{
-  const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)v, m), hi = (unsigned)__shfl_xor((int)(unsigned)(v >> 32), m);
-  return (u64)hi << 32 | lo;
-}
-__device__ __forceinline__ u64 wave_sum64(u64 v)
-{
-#pragma unroll
-  for (int m = 1; m < 64; m <<= 1) v += shfl_xor64(v, m);
-  return v;
-}
 
 // SPL samples of a row from column x on: one vector load when the chunk lies inside the row and the plane is aligned for it, else sample by
 // sample; columns from w on read as 0 (the callers mask them)
@@ -204,7 +193,7 @@ __global__ __launch_bounds__(256) void tile_stats_kernel(Ts3 p)
   {
 #pragma unroll
     for (int m = 1; m < 64; m <<= 1)
-      if (m < lpt) { s0 += shfl_xor64(s0, m); s1 += shfl_xor64(s1, m); s2 += shfl_xor64(s2, m); }
+      if (m < lpt) { s0 += __shfl_xor(s0, m); s1 += __shfl_xor(s1, m); s2 += __shfl_xor(s2, m); }
   }
   if (x < a.w && (!pow2 || (lane & (lpt - 1)) == 0))
   {
@@ -236,7 +225,7 @@ __global__ __launch_bounds__(256) void picture_sse_kernel(Ts3 p)
 #pragma unroll
   for (int c = 0; c < 3; c++)
   {
-    const u64 t = wave_sum64(s[c]);
+    const u64 t = wave_sum(s[c]);
     if (lane == 0) part[wave][c] = t;
   }
   __syncthreads();
@@ -369,7 +358,7 @@ __global__ __launch_bounds__(256) void wp_sad_kernel(WsArgs p, int nReal)
 #pragma unroll
   for (int k = 0; k < NC; k++)
   {
-    const u64 t = wave_sum64(acc[k]);
+    const u64 t = wave_sum(acc[k]);
     if (lane == 0) part[wave][k] = t;
   }
   __syncthreads();
@@ -419,8 +408,7 @@ __global__ void intra_cost_kernel(const Pel* __restrict__ org, int stride, int w
     }
     sum += (s + 2) >> 2;
   }
-#pragma unroll
-  for (int m = 1; m < 64; m <<= 1) sum += __shfl_xor(sum, m);
+  sum = wave_sum(sum);
   if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = sum;
   __syncthreads();
   if (threadIdx.x == 0)

@@ -85,7 +85,7 @@ __device__ __forceinline__ void bp_int_search(const MePu& u, const BpLds& L, con
     for (int o = 1; o < S; o <<= 1) sum += __shfl_xor(sum, o);
     if (act)
     {
-      const unsigned long long cost = (unsigned long long)(sum << u.subShift) + pu_getcost(lambda, me_mvbits_imv(predH, predV, 2, sh, left + i, top + j));
+      const unsigned long long cost = (unsigned long long)(sum << u.subShift) + rd_getcost(lambda, me_mvbits_imv(predH, predV, 2, sh, left + i, top + j));
       if (cost < bestC) { bestC = cost; bestP = (unsigned)p; }
     }
   }
@@ -199,7 +199,7 @@ __device__ __forceinline__ void bp_search(const vvcgpu_bipred_me_item* __restric
         mvX = (ix << 2) + (L.fres->half_x << 1) + L.fres->qter_x; mvY = (iy << 2) + (L.fres->half_y << 1) + L.fres->qter_y;
         const unsigned mvBits = me_mvbits(predX, predY, 0, mvX, mvY);
         bitsT += mvBits;
-        costT = (unsigned long long)(floor(0.5 * ((double)L.fres->cost - (double)pu_getcost(c.lambda, mvBits))) + (double)pu_getcost(c.lambda, bitsT));
+        costT = (unsigned long long)(floor(0.5 * ((double)L.fres->cost - (double)rd_getcost(c.lambda, mvBits))) + (double)rd_getcost(c.lambda, bitsT));
         me_check_best_mvp(a.mv_cand, a.num_cand, c.mvp_idx_cost, c.lambda, mvX, mvY, predX, predY, mvpIdx, bitsT, costT);
       }
       owner_sync<NT>();                                                   // every lane has read st and fres

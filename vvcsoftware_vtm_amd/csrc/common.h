@@ -135,6 +135,13 @@ __device__ __forceinline__ int vvc_xcd_index2(int bid, int nA, int total, int on
 #endif
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
+// the grid of a launch that gives every item a wavefront, `waves` to a workgroup (1: a workgroup), and walks the items with at most per_cu workgroups per
+// compute unit
+static inline int vvc_grid_cap(long long items, int waves, int per_cu)
+{
+  const long long cap = (long long)per_cu * vvcgpu_cu_count(), wgs = (items + waves - 1) / waves;
+  return (int)(wgs < cap ? wgs : cap);
+}
 
 __device__ __forceinline__ int clip3(int lo, int hi, int v) { return min(max(v, lo), hi); }
 __device__ __forceinline__ int sgn(int v) { return (v > 0) - (v < 0); }

@@ -50,7 +50,7 @@ __device__ __forceinline__ unsigned long long dist_one(int kind, const vvcgpu_di
       const int r = idx / w, x = idx - r * w;
       acc += (int)org[(size_t)(r << ssSad) * os + x] - (int)cur[(size_t)(r << ssSad) * cs + x];
     }
-    acc = (long long)group_sum_u64<G>((unsigned long long)acc);
+    acc = (long long)group_sum<G>((unsigned long long)acc);
     offset = act ? (int)(Pel)(kind == 3 ? (int)acc / (w * rows) : (int)(acc / (long long)(w * h))) : 0;
   }
   if (kind == 1 || kind == 4)
@@ -84,7 +84,7 @@ __device__ __forceinline__ unsigned long long dist_one(int kind, const vvcgpu_di
         acc += kind == 2 ? (unsigned)(df * df) : (unsigned)abs(df);
       }
     }
-    res = group_sum_u64<G>(acc) << ss;
+    res = group_sum<G>(acc) << ss;
   }
   return res;
 }
@@ -177,23 +177,14 @@ __global__ __launch_bounds__(256) void dist_heavy_kernel(int kind, const Pel* __
 // by the whole wavefront with the SATD / SAD code of vvcgpu_dist_batch.
 __device__ __forceinline__ unsigned long long block_dist(bool had, const Pel* org, int os, const Pel* cur, int cs, int w, int h, int lane)
 {
-  if (had)
-  {
-    if (w > h && (h & 7) == 0 && (w & 15) == 0)      return satd_tiles<16, 8>(org, os, cur, cs, w, h, lane);
-    else if (w < h && (w & 7) == 0 && (h & 15) == 0) return satd_tiles<8, 16>(org, os, cur, cs, w, h, lane);
-    else if (w > h && (h & 3) == 0 && (w & 7) == 0)  return satd_tiles<8, 4>(org, os, cur, cs, w, h, lane);
-    else if (w < h && (w & 3) == 0 && (h & 7) == 0)  return satd_tiles<4, 8>(org, os, cur, cs, w, h, lane);
-    else if ((h & 7) == 0 && (w & 7) == 0)           return satd_tiles<8, 8>(org, os, cur, cs, w, h, lane);
-    else if ((h & 3) == 0 && (w & 3) == 0)           return satd_tiles<4, 4>(org, os, cur, cs, w, h, lane);
-    return satd_tiles<2, 2>(org, os, cur, cs, w, h, lane);
-  }
+  if (had) return satd_block<64>(org, os, cur, cs, w, h, lane);
   unsigned long long acc = 0;
   for (int idx = lane; idx < h * w; idx += 64)
   {
     const int r = idx / w, x = idx - r * w;
     acc += (unsigned)abs((int)org[(size_t)r * os + x] - (int)cur[(size_t)r * cs + x]);
   }
-  return wave_sum_u64(acc);
+  return wave_sum(acc);
 }
 
 __global__ __launch_bounds__(256) void imv_refine_kernel(const Pel* __restrict__ org, int os, const Pel* __restrict__ ref, int rs,

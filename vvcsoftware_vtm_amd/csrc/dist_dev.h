@@ -1,36 +1,43 @@
-// dist_dev.h -- device functions of the block distortions shared by dist.hip and the fused "predict -> distortion" entries (intra.hip).
-// Reference behaviour: RdCost::xGetHADs CommonLib/RdCost.cpp:2855-2974, xCalcHADs* :2205-2853 (see dist.hip).
+// dist_dev.h -- RdCost on the device: the bits of a motion vector component, the cost of a bit count, calcRdCost and the weighted distortion, and the
+// Hadamard block distortion shared by dist.hip, the fused "predict -> distortion" entries (intra.hip) and the searches.
+// Reference behaviour: RdCost.h:172-199 (getBitsOfVectorWithPredictor, getCost), RdCost::calcRdCost, RdCost::getDistPart; RdCost::xGetHADs
+// CommonLib/RdCost.cpp:2855-2974, xCalcHADs* :2205-2853 (see dist.hip).
 #pragma once
 #include "common.h"
+#include "wave_dev.h"
 
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
+constexpr double RD_MAX_DOUBLE = 1.7976931348623157e308;                  // MAX_DOUBLE
+
+__device__ __forceinline__ unsigned expgolomb_bits(int v)        // RdCost.h:172-184
 {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
+  unsigned len = 1, t = (v <= 0) ? ((unsigned)(-v) << 1) + 1 : (unsigned)(v << 1);
+  while (t > 128u) { len += 14; t >>= 7; }
+  return len + ((31 - __clz((int)t)) << 1);
 }
-
-// sum over an aligned group of G lanes (G = 16: four descriptors side by side in a wave; G = 64: the wave)
-template <int G>
-__device__ __forceinline__ unsigned long long group_sum_u64(unsigned long long v)
+// getCost (RdCost.h:186-199): the cost of a bit count under lambda
+__device__ __forceinline__ unsigned long long rd_getcost(double lambda, unsigned bits) { return (unsigned long long)(lambda * (double)bits); }
+// getDistPart's weighted distortion, and calcRdCost: a multiply, then an add (-ffp-contract=off)
+__device__ __forceinline__ unsigned long long rd_weighted(double weight, unsigned long long x) { return (unsigned long long)(weight * (double)x); }
+__device__ __forceinline__ double rd_cost(double scale, unsigned long long dist, unsigned long long bits)
 {
-#pragma unroll
-  for (int o = G >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
+  const double scaled = scale * (double)dist;
+  return scaled + (double)bits;
 }
 
 // ---------------------------------------------------------------------------------------------------
 // Hadamard tile: TW columns in registers, TH rows across TH consecutive lanes.  `lane` = lane index inside a group of G lanes that share the block.
 // CurPtr, OrgPtr: the types of the two blocks' pointers (plain, or address-space qualified when the caller keeps the block in LDS: a plain pointer
-// to LDS costs flat loads).
+// to LDS costs flat loads).  A group takes every step-th round of the tile walk from round `first` on (wavefronts that share a block: first = the
+// wavefront, step = their number); the sum is over the group's own tiles, in every lane of it.
 template <int TW, int TH, int G = 64, class CurPtr = const Pel*, class OrgPtr = const Pel*>
-__device__ __forceinline__ unsigned long long satd_tiles(OrgPtr org, int os, CurPtr cur, int cs, int w, int h, int lane, int offset = 0)
+__device__ __forceinline__ unsigned long long satd_tiles(OrgPtr org, int os, CurPtr cur, int cs, int w, int h, int lane, int offset = 0, int first = 0,
+                                                         int step = 1)
 {
   constexpr int GROUPS = G / TH;
   const int row = lane % TH, grp = lane / TH;
   const int tilesX = w / TW, nTiles = tilesX * (h / TH);
   unsigned long long total = 0;
-  for (int t0 = 0; t0 < nTiles; t0 += GROUPS)
+  for (int t0 = first * GROUPS; t0 < nTiles; t0 += step * GROUPS)
   {
     const int t = t0 + grp;
     const bool active = t < nTiles;
@@ -83,20 +90,21 @@ __device__ __forceinline__ unsigned long long satd_tiles(OrgPtr org, int os, Cur
       total += n;
     }
   }
-  return group_sum_u64<G>(total);
+  return group_sum<G>(total);
 }
 
 // Hadamard SATD of a w x h block with the reference's tile choice (xGetHADs :2855-2974); lane = index inside a group of G lanes.  hSel (default h):
 // the height the tile choice is made for, when [org, cur] is a band of h rows of a taller block (h a multiple of the chosen tile height).
 template <int G, class CurPtr = const Pel*, class OrgPtr = const Pel*>
-__device__ __forceinline__ unsigned long long satd_block(OrgPtr org, int os, CurPtr cur, int cs, int w, int h, int lane, int offset = 0, int hSel = 0)
+__device__ __forceinline__ unsigned long long satd_block(OrgPtr org, int os, CurPtr cur, int cs, int w, int h, int lane, int offset = 0, int hSel = 0,
+                                                         int first = 0, int step = 1)
 {
   const int hs = hSel ? hSel : h;
-  if (w > hs && (hs & 7) == 0 && (w & 15) == 0)      return satd_tiles<16, 8, G, CurPtr, OrgPtr>(org, os, cur, cs, w, h, lane, offset);
-  else if (w < hs && (w & 7) == 0 && (hs & 15) == 0) return satd_tiles<8, 16, G, CurPtr, OrgPtr>(org, os, cur, cs, w, h, lane, offset);
-  else if (w > hs && (hs & 3) == 0 && (w & 7) == 0)  return satd_tiles<8, 4, G, CurPtr, OrgPtr>(org, os, cur, cs, w, h, lane, offset);
-  else if (w < hs && (w & 3) == 0 && (hs & 7) == 0)  return satd_tiles<4, 8, G, CurPtr, OrgPtr>(org, os, cur, cs, w, h, lane, offset);
-  else if ((hs & 7) == 0 && (w & 7) == 0)            return satd_tiles<8, 8, G, CurPtr, OrgPtr>(org, os, cur, cs, w, h, lane, offset);
-  else if ((hs & 3) == 0 && (w & 3) == 0)            return satd_tiles<4, 4, G, CurPtr, OrgPtr>(org, os, cur, cs, w, h, lane, offset);
-  return satd_tiles<2, 2, G, CurPtr, OrgPtr>(org, os, cur, cs, w, h, lane, offset);
+  if (w > hs && (hs & 7) == 0 && (w & 15) == 0)      return satd_tiles<16, 8, G, CurPtr, OrgPtr>(org, os, cur, cs, w, h, lane, offset, first, step);
+  else if (w < hs && (w & 7) == 0 && (hs & 15) == 0) return satd_tiles<8, 16, G, CurPtr, OrgPtr>(org, os, cur, cs, w, h, lane, offset, first, step);
+  else if (w > hs && (hs & 3) == 0 && (w & 7) == 0)  return satd_tiles<8, 4, G, CurPtr, OrgPtr>(org, os, cur, cs, w, h, lane, offset, first, step);
+  else if (w < hs && (w & 3) == 0 && (hs & 7) == 0)  return satd_tiles<4, 8, G, CurPtr, OrgPtr>(org, os, cur, cs, w, h, lane, offset, first, step);
+  else if ((hs & 7) == 0 && (w & 7) == 0)            return satd_tiles<8, 8, G, CurPtr, OrgPtr>(org, os, cur, cs, w, h, lane, offset, first, step);
+  else if ((hs & 3) == 0 && (w & 3) == 0)            return satd_tiles<4, 4, G, CurPtr, OrgPtr>(org, os, cur, cs, w, h, lane, offset, first, step);
+  return satd_tiles<2, 2, G, CurPtr, OrgPtr>(org, os, cur, cs, w, h, lane, offset, first, step);
 }

@@ -92,7 +92,7 @@ __device__ __forceinline__ vvcgpu_depquant_desc iq_record(int64_t off, int qp, i
 __device__ __forceinline__ int iq_reserve(int* count, int cnt, int lane)
 {
   int listAt = 0;
-  cnt = wave_sum_i32(cnt);
+  cnt = wave_sum(cnt);
   if (cnt && lane == 0) listAt = atomicAdd(count, cnt);
   return __builtin_amdgcn_readfirstlane(listAt);
 }
@@ -166,8 +166,8 @@ __device__ __forceinline__ unsigned long long iq_close(const Pel* org, ptrdiff_t
     if (level) nz += level[e] != 0;
     rec[r * recStride + x] = (short)rc;
   }
-  if (level) *numSig = wave_sum_i32(nz);
-  return group_sum_u64<64>(sse);
+  if (level) *numSig = wave_sum(nz);
+  return group_sum<64>(sse);
 }
 
 // ---- host side of the three entries.  `name` is the entry's name as the error text starts with it; a check returns VVCGPU_OK or the error code with the

@@ -8,6 +8,7 @@
 // any int16 block (a bi-predictive search key 2 org - otherPred): the Hadamards run in 32-bit registers.
 #pragma once
 #include "common.h"
+#include "dist_dev.h"
 
 namespace {
 
@@ -23,95 +24,23 @@ __constant__ signed char c_refQ[9][2] = { {0,0},{0,-1},{0,1},{-1,-1},{1,-1},{-1,
 
 constexpr int OFFS = 1 << 13;
 
-__device__ __forceinline__ unsigned eg_bits(int v)
-{
-  unsigned len = 1, t = (v <= 0) ? ((unsigned)(-v) << 1) + 1 : (unsigned)(v << 1);
-  while (t > 128u) { len += 14; t >>= 7; }
-  return len + ((31 - __clz((int)t)) << 1);
-}
 __device__ __forceinline__ unsigned long long mv_cost(double lambda, int predH, int predV, int scale, int x, int y)
 {
-  const unsigned bits = eg_bits((x << scale) - predH) + eg_bits((y << scale) - predV);
-  return (unsigned long long)(lambda * (double)bits);
+  const unsigned bits = expgolomb_bits((x << scale) - predH) + expgolomb_bits((y << scale) - predV);
+  return rd_getcost(lambda, bits);
 }
 
-// Hadamard SATD of (org - pred), both in LDS with pitch w; tiles spread over the lanes of `nw` waves; returns the
-// partial sum of THIS wave's tiles in every lane (caller combines the waves).
-template <int TW, int TH>
-__device__ __forceinline__ unsigned long long satd_lds(const short* org, const short* pred, int w, int h, int lane, int wave, int nw)
-{
-  constexpr int GROUPS = 64 / TH;
-  const int row = lane % TH, grp = lane / TH;
-  const int tilesX = w / TW, nTiles = tilesX * (h / TH);
-  unsigned long long total = 0;
-  for (int t0 = wave * GROUPS; t0 < nTiles; t0 += nw * GROUPS)
-  {
-    const int t = t0 + grp;
-    const bool act = t < nTiles;
-    int v[TW];
-    if (act)
-    {
-      const int ty = t / tilesX, tx = t - ty * tilesX;
-      const int o = (ty * TH + row) * w + tx * TW;
-#pragma unroll
-      for (int x = 0; x < TW; x++) v[x] = (int)org[o + x] - (int)pred[o + x];
-    }
-    else
-    {
-#pragma unroll
-      for (int x = 0; x < TW; x++) v[x] = 0;
-    }
-#pragma unroll
-    for (int len = 1; len < TW; len <<= 1)
-#pragma unroll
-      for (int i = 0; i < TW; i += 2 * len)
-#pragma unroll
-        for (int j = i; j < i + len; j++) { const int a = v[j], b = v[j + len]; v[j] = a + b; v[j + len] = a - b; }
-#pragma unroll
-    for (int len = 1; len < TH; len <<= 1)
-    {
-      const bool upper = row & len;
-#pragma unroll
-      for (int x = 0; x < TW; x++) { const int p = __shfl_xor(v[x], len); v[x] = upper ? p - v[x] : v[x] + p; }
-    }
-    int s = 0;
-#pragma unroll
-    for (int x = 0; x < TW; x++) s += abs(v[x]);
-#pragma unroll
-    for (int len = 1; len < TH; len <<= 1) s += __shfl_xor(s, len);
-    if (act && row == 0)
-    {
-      unsigned long long n;
-      if (TW == 2) n = (unsigned long long)s;
-      else if (TW == 4 && TH == 4) n = (unsigned long long)((s + 1) >> 1);
-      else if (TW == 8 && TH == 8) n = (unsigned long long)((s + 2) >> 2);
-      else if (TW * TH == 128) n = (unsigned long long)(int)((double)s / sqrt(16.0 * 8) * 2);
-      else n = (unsigned long long)(int)((double)s / sqrt(4.0 * 8) * 2);
-      total += n;
-    }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) total += __shfl_xor(total, o);
-  return total;
-}
-
+// distortion of (org - pred), both in LDS with pitch w, spread over the lanes of `nw` waves; returns the partial sum of THIS wave in every lane
+// (caller combines the waves)
 __device__ __forceinline__ unsigned long long dist_lds(const short* org, const short* pred, int w, int h, int useHad, int lane, int wave, int nw)
 {
   if (!useHad)
   {
     unsigned long long acc = 0;
     for (int i = wave * 64 + lane; i < w * h; i += nw * 64) acc += (unsigned)abs((int)org[i] - (int)pred[i]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
-    return acc;
+    return wave_sum(acc);
   }
-  if (w > h && (h & 7) == 0 && (w & 15) == 0)      return satd_lds<16, 8>(org, pred, w, h, lane, wave, nw);
-  else if (w < h && (w & 7) == 0 && (h & 15) == 0) return satd_lds<8, 16>(org, pred, w, h, lane, wave, nw);
-  else if (w > h && (h & 3) == 0 && (w & 7) == 0)  return satd_lds<8, 4>(org, pred, w, h, lane, wave, nw);
-  else if (w < h && (w & 3) == 0 && (h & 7) == 0)  return satd_lds<4, 8>(org, pred, w, h, lane, wave, nw);
-  else if ((h & 7) == 0 && (w & 7) == 0)           return satd_lds<8, 8>(org, pred, w, h, lane, wave, nw);
-  else if ((h & 3) == 0 && (w & 3) == 0)           return satd_lds<4, 4>(org, pred, w, h, lane, wave, nw);
-  return satd_lds<2, 2>(org, pred, w, h, lane, wave, nw);
+  return satd_block<64>(org, w, pred, w, w, h, lane, 0, 0, wave, nw);
 }
 
 // one wave per PU needs no workgroup barrier: LDS operations of a wave execute in order; the fence keeps the compiler from

@@ -645,7 +645,7 @@ __device__ __forceinline__ void fm_best(unsigned dl, bool quarter, const unsigne
   const int li = lane < 9 ? lane : 0;
   const int dx = (int)(((quarter ? FM_QX : FM_HX) >> (2 * li)) & 3u) - 1, dy = (int)(((quarter ? FM_QY : FM_HY) >> (2 * li)) & 3u) - 1;
   const unsigned bits = 126u - ((fm_eg_clz(((baseX + dx) << scale) - predH) + fm_eg_clz(((baseY + dy) << scale) - predV)) << 1);   // two lengths 63 - 2 clz
-  const unsigned long long mc = bits < (unsigned)FM_COST_N ? costS[bits] : (unsigned long long)(lambda * (double)bits);
+  const unsigned long long mc = bits < (unsigned)FM_COST_N ? costS[bits] : rd_getcost(lambda, bits);
   unsigned long long c = lane < 9 ? (unsigned long long)dl + mc : 0xFFFFFFFFull;   // lanes 9..63: a zero high word, so that the vote needs no lane mask
   int bi;
   if (__builtin_amdgcn_ballot_w64((unsigned)(c >> 32) != 0u) == 0ull)

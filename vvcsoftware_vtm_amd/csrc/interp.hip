@@ -811,7 +811,7 @@ __global__ __launch_bounds__(64) void mc_batch_kernel(const Pel* __restrict__ re
         const int df = (int)org[(size_t)(r << ss) * os + x] - (int)predT[(r << ss) * w + x];
         acc += distKind == 2 ? (unsigned)(df * df) : (unsigned)abs(df);
       }
-      res = wave_sum_u64(acc) << ss;
+      res = wave_sum(acc) << ss;
     }
     if (lane == 0) out[li] = res;
     __syncthreads();                                   // before the next descriptor overwrites the tile

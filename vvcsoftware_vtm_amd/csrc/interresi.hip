@@ -201,7 +201,7 @@ extern "C" int vvcgpu_inter_resi_code_batch(const vvc_pel* org_base, const vvc_p
   VvcTrTables tb; const _Float16* image = nullptr;
   const int rt = vvcgpu_tr_images(&tb, &image);
   if (rt) return rt;
-  const int wgs = ir_workgroups(n);
+  const int wgs = vvc_grid_cap(n, IR_WAVES, 1);
   VvcScratch sc(st);
   int* fbScratch = ir_fb_scratch(sc, wgs);
   if (!fbScratch) return VVCGPU_E_DEVICE;

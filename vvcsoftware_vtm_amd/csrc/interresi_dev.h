@@ -74,7 +74,7 @@ __device__ __forceinline__ unsigned long long ir_stage(const IrItem& t, const Pe
       zd += (unsigned long long)(ad * ad);
     }
   }
-  return group_sum_u64<64>(zd);
+  return group_sum<64>(zd);
 }
 
 // The closing loop of slot k: xGetSSE(orgResi, resi') and xGetSSE(org, clip(pred + resi')) from resi' where the body left it -- backK in the tile, or the
@@ -103,8 +103,8 @@ __device__ __forceinline__ void ir_finish(const Args& a, const IrItem& t, int it
     dc += (unsigned long long)(d2 * d2);
     if (rec) rec[e] = (short)rc;
   }
-  dr = group_sum_u64<64>(dr);
-  dc = group_sum_u64<64>(dc);
+  dr = group_sum<64>(dr);
+  dc = group_sum<64>(dc);
   if (lane == 0) { a.distResi[out] = dr; a.distRec[out] = dc; }
 }
 
@@ -126,8 +126,7 @@ inline int ir_check_bit_depth(const char* name, int bit_depth)
   if (bit_depth > 10 || bit_depth < 8) { vvcgpu_set_error("%s: bit depth %d outside 8..10", name, bit_depth); return VVCGPU_E_UNSUPPORTED; }
   return VVCGPU_OK;
 }
-// persistent workgroups of IR_WAVES wavefronts, at most one per compute unit; IR_FB_INTS of global scratch for each of their wavefronts
-inline int ir_workgroups(int n) { const int cap = vvcgpu_cu_count(), wgs = cdiv(n, IR_WAVES); return wgs < cap ? wgs : cap; }
+// IR_FB_INTS of global scratch for each wavefront of the persistent workgroups
 inline int* ir_fb_scratch(VvcScratch& sc, int wgs) { return sc.take<int>((size_t)wgs * IR_WAVES * IR_FB_INTS); }
 
 }  // namespace

@@ -220,7 +220,7 @@ int vvcgpu_inter_resi_code_dq_batch(const vvc_pel* org_base, const vvc_pel* pred
   if (const int rc = iq_check_frame(name, n, "items", n_rates, level_extent, ws, ws_bytes, lay.bytes, quantiser, quantiser == VVCGPU_INTER_RESI_Q_DEPQUANT, bit_depth))
     return rc;
   hipStream_t st = (hipStream_t)stream;
-  const int wgs = ir_workgroups(n);
+  const int wgs = vvc_grid_cap(n, IR_WAVES, 1);
   VVC_HIP(vvc_allow_lds(inter_resi_dq_front_kernel, IQ_LDS_BYTES));
   VVC_HIP(vvc_allow_lds(inter_resi_dq_back_kernel, IQ_LDS_BYTES));
   VvcScratch sc(st);

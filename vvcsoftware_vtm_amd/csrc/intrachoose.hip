@@ -66,7 +66,7 @@ __global__ __launch_bounds__(IC_THREADS) void intra_luma_choose_kernel(const LcA
         const int cls = mode == u.mpm[0] ? 0 : mode == u.mpm[1] ? 1 : mode == u.mpm[2] ? 2 : 3;
         const unsigned long long bits = up->mode_bits[cls] + up->cbf_bits[cbf ? 1 : 0] + (cbf ? u.emt_cu_bits + fb : 0ull);
         const bool forbidden = (ts && !cbf) || (emtFlag && t > 0 && !ts && a.numSig[j] <= IC_EMT_SIG_NUM_THR);    // :1501-1502
-        cost[c] = forbidden ? IC_MAX_DOUBLE : ic_cost(a.scale, a.dist[j], bits);
+        cost[c] = forbidden ? RD_MAX_DOUBLE : rd_cost(a.scale, a.dist[j], bits);
         code[c] = (unsigned char)((valid ? IC_VALID : 0) | (cbf ? IC_CBF : 0) | (ts ? IC_TS : 0));
       }
       wave_sync();
@@ -74,12 +74,12 @@ __global__ __launch_bounds__(IC_THREADS) void intra_luma_choose_kernel(const LcA
       if (lane == 0)
       {
         const bool fastEmt = u.flags & VVCGPU_INTRA_CHOOSE_FAST_EMT;
-        double bestCost = IC_MAX_DOUBLE;
+        double bestCost = RD_MAX_DOUBLE;
         for (int m = 0; m < nm; m++)
         {
           const int c0 = m * nt;
           if (!(code[c0] & IC_VALID)) { for (int t = 0; t < nt; t++) code[c0 + t] |= IC_PASSED; continue; }
-          double single = IC_MAX_DOUBLE;
+          double single = RD_MAX_DOUBLE;
           int bt = -1;
           bool cbfBest = false;
           for (int t = 0; t < nt; t++)
@@ -100,7 +100,7 @@ __global__ __launch_bounds__(IC_THREADS) void intra_luma_choose_kernel(const LcA
     }
     // ---- the result and the commit
     vvcgpu_intra_choose_result r;
-    r.best_cand = -1; r.best_mode = -1; r.best_tr = -1; r.cbf = 0; r.dist = ~0ull; r.bits = ~0ull; r.cost = IC_MAX_DOUBLE; r.reserved = 0;
+    r.best_cand = -1; r.best_mode = -1; r.best_tr = -1; r.cbf = 0; r.dist = ~0ull; r.bits = ~0ull; r.cost = RD_MAX_DOUBLE; r.reserved = 0;
     if (best >= 0)
     {
       const int j = u.cand_first + best;
@@ -147,20 +147,20 @@ __global__ __launch_bounds__(IC_THREADS) void intra_chroma_choose_kernel(const C
     const bool cand = ok && lane < 6 && qp->mode[k] != -1 && sCb != 0xFFFFFFFFu && sCr != 0xFFFFFFFFu && (!cbfCb || fCb != ~0ull) && (!cbfCr || fCr != ~0ull);
     const unsigned long long bits = up->mode_bits[k] + up->cbf_cb_bits[cbfCb ? 1 : 0] + up->cbf_cr_bits[2 * (cbfCb ? 1 : 0) + (cbfCr ? 1 : 0)]
                                     + (cbfCb ? fCb : 0ull) + (cbfCr ? fCr : 0ull);
-    const unsigned long long dist = ic_weighted(u.dist_weight[0], a.dist[o]) + ic_weighted(u.dist_weight[1], a.dist[o + 1]);
-    const double cost = ic_cost(a.scale, dist, bits);
+    const unsigned long long dist = rd_weighted(u.dist_weight[0], a.dist[o]) + rd_weighted(u.dist_weight[1], a.dist[o + 1]);
+    const double cost = rd_cost(a.scale, dist, bits);
     if (lane < 6) a.slotCost[6 * (size_t)p + k] = cand ? (unsigned long long)__double_as_longlong(cost) : VVCGPU_INTRA_CHOOSE_PASSED;
     // ---- the ordered loop of :773-826 over the six lanes' values
     const unsigned long long cands = __ballot(cand);
     int best = -1;
-    double bestCost = IC_MAX_DOUBLE;
+    double bestCost = RD_MAX_DOUBLE;
     for (int s = 0; s < 6; s++)
     {
       const double cs = __shfl(cost, s);
       if (((cands >> s) & 1ull) && cs < bestCost) { bestCost = cs; best = s; }                                          // :803
     }
     vvcgpu_intra_chroma_choose_result r;
-    r.best_slot = -1; r.best_mode = -1; r.cbf[0] = 0; r.cbf[1] = 0; r.dist = ~0ull; r.bits = ~0ull; r.cost = IC_MAX_DOUBLE; r.reserved = 0;
+    r.best_slot = -1; r.best_mode = -1; r.cbf[0] = 0; r.cbf[1] = 0; r.dist = ~0ull; r.bits = ~0ull; r.cost = RD_MAX_DOUBLE; r.reserved = 0;
     if (best >= 0)
     {
       r.best_slot = best; r.best_mode = qp->mode[best]; r.cbf[0] = __shfl((int)cbfCb, best); r.cbf[1] = __shfl((int)cbfCr, best);
@@ -180,7 +180,6 @@ __global__ __launch_bounds__(IC_THREADS) void intra_chroma_choose_kernel(const C
   }
 }
 
-inline int ic_workgroups(int n) { const int cap = 8 * vvcgpu_cu_count(), wgs = cdiv(n, IC_WAVES); return wgs < cap ? wgs : cap; }
 inline bool ic_aligned(const void* p, unsigned mask) { return ((uintptr_t)p & mask) == 0; }
 
 }  // namespace
@@ -205,7 +204,7 @@ extern "C" int vvcgpu_intra_luma_choose_batch(const struct vvcgpu_intra_choose_p
   a.frac = reinterpret_cast<const unsigned long long*>(frac_bits); a.scale = dist_scale; a.rec = rec_base; a.level = level_base; a.ctxOut = ctx_out;
   a.recDst = rec_dst_base; a.levelDst = level_dst_base; a.ctxBest = ctx_best; a.candCost = reinterpret_cast<unsigned long long*>(cand_cost);
   a.result = result; a.nPu = n_pu; a.n = n;
-  hipLaunchKernelGGL(intra_luma_choose_kernel, dim3(ic_workgroups(n_pu)), dim3(IC_THREADS), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(intra_luma_choose_kernel, dim3(vvc_grid_cap(n_pu, IC_WAVES, 8)), dim3(IC_THREADS), 0, (hipStream_t)stream, a);
   VVC_LAUNCH_CHECK();
   return VVCGPU_OK;
 }
@@ -230,7 +229,7 @@ extern "C" int vvcgpu_intra_chroma_choose_batch(const struct vvcgpu_intra_chroma
   a.fracCb = reinterpret_cast<const unsigned long long*>(frac_bits_cb); a.fracCr = reinterpret_cast<const unsigned long long*>(frac_bits_cr);
   a.scale = dist_scale; a.rec = cand_rec_base; a.level = level_base; a.ctxOut = ctx_out; a.recDst = rec_dst_base; a.levelDst = level_dst_base;
   a.ctxBest = ctx_best; a.slotCost = reinterpret_cast<unsigned long long*>(slot_cost); a.result = result; a.n = n;
-  hipLaunchKernelGGL(intra_chroma_choose_kernel, dim3(ic_workgroups(n)), dim3(IC_THREADS), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(intra_chroma_choose_kernel, dim3(vvc_grid_cap(n, IC_WAVES, 8)), dim3(IC_THREADS), 0, (hipStream_t)stream, a);
   VVC_LAUNCH_CHECK();
   return VVCGPU_OK;
 }

@@ -1,22 +1,15 @@
-// intrachoose_dev.h -- what the two kernels of intrachoose.hip share: the candidate codes, the host's cost arithmetic and the wavefront's copies of
+// intrachoose_dev.h -- what the two kernels of intrachoose.hip share: the candidate codes and the wavefront's copies of
 // the winner (a sample block, a level block, a context row).
 #pragma once
 #include "common.h"
+#include "dist_dev.h"
 
 namespace {
 
 constexpr int IC_WAVES = 4, IC_THREADS = 64 * IC_WAVES;                   // a wavefront per PU
 constexpr int IC_MAX_CAND = 16 * 5;                                       // n_modes x n_tr
 constexpr unsigned IC_EMT_SIG_NUM_THR = 2;                                // g_EmtSigNumThr (Rom.cpp:504)
-constexpr double IC_MAX_DOUBLE = 1.7976931348623157e308;                  // MAX_DOUBLE
 constexpr unsigned IC_VALID = 1, IC_CBF = 2, IC_TS = 4, IC_PASSED = 8;
-
-__device__ __forceinline__ unsigned long long ic_weighted(double weight, unsigned long long x) { return (unsigned long long)(weight * (double)x); }
-__device__ __forceinline__ double ic_cost(double scale, unsigned long long dist, unsigned long long bits)
-{
-  const double scaled = scale * (double)dist;                             // RdCost::calcRdCost: a multiply, then an add (-ffp-contract=off)
-  return scaled + (double)bits;
-}
 
 __device__ __forceinline__ unsigned ic_align_of(const void* a, const void* b) { return (unsigned)((uintptr_t)a | (uintptr_t)b); }
 

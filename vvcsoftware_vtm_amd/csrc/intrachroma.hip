@@ -111,7 +111,7 @@ __global__ __launch_bounds__(256) void chroma_small_kernel(const ChArgs a, const
         rec[e] = (Pel)r;
         sse += (unsigned)(df * df);
       }
-      const unsigned long long total = group_sum_u64<64>((unsigned long long)sse);
+      const unsigned long long total = group_sum<64>((unsigned long long)sse);
       if (lane == 0) a.dist[item] = total;
       wave_sync();                                                        // the tile, the buffers and the reconstruction are free again
     }
@@ -228,7 +228,7 @@ __global__ __launch_bounds__(256, 1) void chroma_large_kernel(const ChArgs a, co
           const Pel* rec = a.candRec + u.cand_off + off;
           unsigned long long sse = 0ull;                                  // 64 x 64 x 1023^2 is beyond 2^31
           for (int e = lane; e < samples; e += 64) { const int df = (int)orgS[e] - (int)rec[e]; sse += (unsigned long long)(unsigned)(df * df); }
-          sse = group_sum_u64<64>(sse);
+          sse = group_sum<64>(sse);
           if (lane == 0) a.dist[item] = sse;
         }
         wave_sync();                                                      // the tile and the descriptor are free again
@@ -282,7 +282,7 @@ extern "C" int vvcgpu_intra_chroma_code_batch(const vvc_pel* rec_base, const uin
   VvcTrTables tb; const _Float16* image = nullptr;
   const int rt = vvcgpu_tr_images(&tb, &image);
   if (rt) return rt;
-  const int cap = vvcgpu_cu_count(), wgsL = cdiv(cls[1].total, 4) < cap ? cdiv(cls[1].total, 4) : cap;
+  const int wgsL = vvc_grid_cap(cls[1].total, 4, 1);
   VvcScratch sc(st);
   int* fbScratch = nullptr;
   if (wgsL)

@@ -278,7 +278,7 @@ int vvcgpu_intra_chroma_code_dq_batch(const vvc_pel* rec_base, const uint8_t* fl
   if (const int rc = iq_check_frame(name, n, "PUs", n_rates, level_extent, ws, ws_bytes, lay.bytes, quantiser, quantiser == VVCGPU_INTRA_CHROMA_Q_DEPQUANT, bit_depth))
     return rc;
   hipStream_t st = (hipStream_t)stream;
-  const int cap = vvcgpu_cu_count(), wgsF = n < cap ? n : cap, wgsB = 12ll * n < cap ? 12 * n : cap;
+  const int wgsF = vvc_grid_cap(n, 1, 1), wgsB = vvc_grid_cap(12ll * n, 1, 1);
   VVC_HIP(vvc_allow_lds(chroma_dq_front_kernel, CQF_LDS_BYTES));
   VVC_HIP(vvc_allow_lds(chroma_dq_back_kernel, CQB_LDS_BYTES));
   VvcScratch sc(st);

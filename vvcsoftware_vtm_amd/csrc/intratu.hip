@@ -125,8 +125,8 @@ __global__ __launch_bounds__(256, IT_WGS_PER_CU) void intra_tu_code_kernel(const
       const int wj = min(w, 32), hj = min(h, 32), lwj = ilog2(wj);
       int nz = 0;
       for (int e = lane; e < wj * hj; e += 64) nz += level[(e >> lwj) * w + (e & (wj - 1))] != 0;
-      sse = group_sum_u64<64>(sse);
-      nz = wave_sum_i32(nz);
+      sse = group_sum<64>(sse);
+      nz = wave_sum(nz);
       if (lane == 0) { a.dist[item] = sse; a.numSig[item] = (unsigned)nz; }
     }
     wave_sync();                                                          // the tile and the descriptor are free again
@@ -152,7 +152,7 @@ extern "C" int vvcgpu_intra_tu_code_batch(const vvc_pel* refs_base, const vvcgpu
   VvcTrTables tb; const _Float16* image = nullptr;
   const int rt = vvcgpu_tr_images(&tb, &image);
   if (rt) return rt;
-  const int cap = IT_WGS_PER_CU * vvcgpu_cu_count(), wgs = cdiv(n, 4) < cap ? cdiv(n, 4) : cap;
+  const int wgs = vvc_grid_cap(n, 4, IT_WGS_PER_CU);
   VvcScratch sc(st);
   int* fbScratch = sc.take<int>((size_t)wgs * 4 * IT_FB_INTS);            // touched only for an item outside the matrix-core range
   if (!fbScratch) return VVCGPU_E_DEVICE;

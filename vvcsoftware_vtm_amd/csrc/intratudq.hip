@@ -181,7 +181,7 @@ int vvcgpu_intra_tu_code_dq_batch(const vvc_pel* refs_base, const vvcgpu_intra_d
   if (const int rc = iq_check_frame(name, n, "items", n_rates, level_extent, ws, ws_bytes, lay.bytes, quantiser, quantiser == VVCGPU_INTRA_TU_Q_DEPQUANT, bit_depth))
     return rc;
   hipStream_t st = (hipStream_t)stream;
-  const int cap = vvcgpu_cu_count(), wgs = n < cap ? n : cap;             // (the items are dealt to the workgroups first, then to their wavefronts: a short list spreads over the compute units)
+  const int wgs = vvc_grid_cap(n, 1, 1);                                  // (the items are dealt to the workgroups first, then to their wavefronts: a short list spreads over the compute units)
   VVC_HIP(vvc_allow_lds(intra_tu_dq_front_kernel, ITQ_LDS_BYTES));
   VVC_HIP(vvc_allow_lds(intra_tu_dq_back_kernel, ITQ_LDS_BYTES));
   VvcScratch sc(st);

@@ -21,11 +21,11 @@ struct MePu
   int horMin, horMax, verMin, verMax;          // clipMv, quarter units
 };
 
-__device__ __forceinline__ unsigned me_mvbits(int predH, int predV, int scale, int x, int y) { return eg_bits((x << scale) - predH) + eg_bits((y << scale) - predV); }
+__device__ __forceinline__ unsigned me_mvbits(int predH, int predV, int scale, int x, int y) { return expgolomb_bits((x << scale) - predH) + expgolomb_bits((y << scale) - predV); }
 // getBitsOfVectorWithPredictor(x, y, imvShift) (RdCost.h:189)
 __device__ __forceinline__ unsigned me_mvbits_imv(int predH, int predV, int scale, int sh, int x, int y)
 {
-  return eg_bits(((x << scale) - predH) >> sh) + eg_bits(((y << scale) - predV) >> sh);
+  return expgolomb_bits(((x << scale) - predH) >> sh) + expgolomb_bits(((y << scale) - predV) >> sh);
 }
 
 // motionCompensation (luma, uni, rounded and clipped) of the quarter-unit vector (mvX, mvY), clipMv applied, against `ref` (sample (0, 0) of the
@@ -110,7 +110,7 @@ __device__ __forceinline__ void me_check_best_mvp(const int32_t (*cand)[2], int 
     mvpIdx = bestIdx;
     const unsigned orgB = bits;
     bits = orgB - (unsigned)orgBits + (unsigned)bestBits;
-    cost = (cost - pu_getcost(lambda, orgB)) + pu_getcost(lambda, bits);
+    cost = (cost - rd_getcost(lambda, orgB)) + rd_getcost(lambda, bits);
   }
 }
 
@@ -151,7 +151,7 @@ __device__ __forceinline__ void me_imv_refine(const MePu& u, const short* key, c
     {
       unsigned acc = 0;
       for (int k = lane; k < w * h; k += 64) acc += (unsigned)abs((int)key[k] - (int)cur[(ptrdiff_t)(k >> u.lgW) * rs + (k & (w - 1))]);
-      d = wave_sum_u64(acc);
+      d = wave_sum(acc);
     }
     if (lane == 0) dl[e] = d;
   }
@@ -166,16 +166,16 @@ __device__ __forceinline__ void me_imv_refine(const MePu& u, const short* key, c
       if (i >= numCand) break;
       const int tx = dx * step + (i ? b1x : b0x), ty = dy * step + (i ? b1y : b0y);
       unsigned long long dist = (unsigned long long)((double)dl[same ? pos : 2 * pos + i] * weight);      // :2456; candidate 1 at candidate 0's position takes its distortion
-      const unsigned vb = eg_bits((tx - (i ? c1x : c0x)) >> sh) + eg_bits((ty - (i ? c1y : c0y)) >> sh);
-      dist += pu_getcost(lambda, vb);
+      const unsigned vb = expgolomb_bits((tx - (i ? c1x : c0x)) >> sh) + expgolomb_bits((ty - (i ? c1y : c0y)) >> sh);
+      dist += rd_getcost(lambda, vb);
       if (dist < bestDist) { bestDist = dist; bestX = tx; bestY = ty; bestIdx = i; bestBits = (int)(mvpIdxCost[i] + vb); }
     }
   }
   bits -= mvpIdxCost[mvpIdx];
   bits += (unsigned)bestBits;
-  cost = bestDist - pu_getcost(lambda, (unsigned)bestBits) + pu_getcost(lambda, bits);
+  cost = bestDist - rd_getcost(lambda, (unsigned)bestBits) + rd_getcost(lambda, bits);
   mvX = bestX; mvY = bestY; mvpIdx = bestIdx; predX = bestIdx ? c1x : c0x; predY = bestIdx ? c1y : c0y;
-  bits += eg_bits((bestX - predX) >> sh) + eg_bits((bestY - predY) >> sh);                                 // :2496: the vector bits a second time
+  bits += expgolomb_bits((bestX - predX) >> sh) + expgolomb_bits((bestY - predY) >> sh);                                 // :2496: the vector bits a second time
   owner_sync<NT>();                                                                                          // dl lies in the work area, which is written again
 }
 

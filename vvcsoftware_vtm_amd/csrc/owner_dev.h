@@ -1,8 +1,9 @@
 // owner_dev.h -- what the whole-PU search entries (affine_me.hip, bipredme.hip, affine_bipredme.hip, unipredme.hip, affine_unipredme.hip) share that is
-// neither translational nor affine: the owner split of the grid, the owner's barrier and 64-bit sum, the reference-index bits and getCost, the served
+// neither translational nor affine: the owner split of the grid, the owner's barrier and 64-bit sum, the reference-index bits, the served
 // PU sides, and what an item outside the contract gets.  docs/KERNELS.md, "Owners of the whole-PU entries", describes the model.
 #pragma once
 #include "common.h"
+#include "dist_dev.h"
 
 namespace {
 
@@ -28,9 +29,7 @@ template <int NT> __device__ __forceinline__ unsigned long long owner_sum_waves(
 // Sum of every lane's v over the owner, in every lane
 template <int NT> __device__ __forceinline__ unsigned long long owner_sum(unsigned long long v, unsigned long long* slots, int tid)
 {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return owner_sum_waves<NT>(v, slots, tid);
+  return owner_sum_waves<NT>(wave_sum(v), slots, tid);
 }
 
 // The owner split.  A launch over `units` (items, or searches) has cdiv(units, 4) workgroups of four wavefront owners, then up to `units` workgroup
@@ -46,9 +45,8 @@ __device__ __forceinline__ OwnerSlot owner_slot(int units, int wave)
   return s;
 }
 
-// the bits of reference index r of a list of nRef (truncated unary), and getCost (RdCost.h:172-199)
+// the bits of reference index r of a list of nRef (truncated unary)
 __device__ __forceinline__ unsigned pu_ref_bits(int nRef, int r) { return nRef > 1 ? (unsigned)(r + 1 - (r == nRef - 1 ? 1 : 0)) : 0u; }
-__device__ __forceinline__ unsigned long long pu_getcost(double lambda, unsigned bits) { return (unsigned long long)(lambda * (double)bits); }
 
 // the served sides of a PU (and of cfg.max_pu): translational 4, 8, .. 128; affine 16, 32, 64, 128
 inline __host__ __device__ bool pu_side_pow2_ok(int v) { return v >= 4 && v <= 128 && (v & (v - 1)) == 0; }

@@ -1,39 +1,11 @@
 // raster_dev.h -- device pieces shared by the step-5 raster search kernels of sadsearch.hip and the hierarchical search of mehier.hip:
-// wave minima, the LDS window fill, and the QUAD SAD loop (a lane owns four consecutive raster columns; the org rows are wave-uniform scalar
+// the LDS window fill, and the QUAD SAD loop (a lane owns four consecutive raster columns; the org rows are wave-uniform scalar
 // operands from a packed copy of the block).  See the kernel comments in sadsearch.hip for the measurements behind these forms.
 #pragma once
 #include "common.h"
+#include "dist_dev.h"
 
 namespace {
-
-__device__ __forceinline__ unsigned expgolomb_bits(int v)        // RdCost.h:172-184
-{
-  unsigned len = 1, t = (v <= 0) ? ((unsigned)(-v) << 1) + 1 : (unsigned)(v << 1);
-  while (t > 128u) { len += 14; t >>= 7; }
-  return len + ((31 - __clz((int)t)) << 1);
-}
-
-// minimum of a 32-bit value over the wavefront with DPP row operations (no LDS traffic, 6 VALU); the result is wave-uniform
-__device__ __forceinline__ unsigned wave_min_u32(unsigned v)
-{
-#define WMIN_STEP(CTRL, ROWMASK) v = min(v, (unsigned)__builtin_amdgcn_update_dpp(-1, (int)v, CTRL, ROWMASK, 0xF, false))
-  WMIN_STEP(0xB1, 0xF);      // quad_perm [1,0,3,2]
-  WMIN_STEP(0x4E, 0xF);      // quad_perm [2,3,0,1]
-  WMIN_STEP(0x141, 0xF);     // row_half_mirror
-  WMIN_STEP(0x140, 0xF);     // row_mirror: every lane of a 16-lane row holds the row's minimum
-  WMIN_STEP(0x142, 0xA);     // row_bcast15 into rows 1 and 3
-  WMIN_STEP(0x143, 0xC);     // row_bcast31 into rows 2 and 3: lane 63 holds the minimum of all four rows
-#undef WMIN_STEP
-  return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
-}
-// 64-bit minimum as two 32-bit passes: the high words first, then the low words of the lanes that hold the minimal high word
-__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long k)
-{
-  const unsigned hi = (unsigned)(k >> 32), lo = (unsigned)k;
-  const unsigned hmin = wave_min_u32(hi);
-  const unsigned lmin = wave_min_u32(hi == hmin ? lo : 0xFFFFFFFFu);
-  return ((unsigned long long)hmin << 32) | lmin;
-}
 
 #define R5C_COST_N 132                                            /* expgolomb_bits <= 65 per component */
 #define R5C_WAIT_LGKM0() __builtin_amdgcn_s_waitcnt(0xC07F)       /* lgkmcnt(0), vmcnt/expcnt untouched */

@@ -7,6 +7,7 @@
 // All double arithmetic is written in the reference's order with contraction off.
 // The scan tables are those of transform.hip (vvcgpu_tr_tables); their addresses arrive as a kernel argument.
 #include "common.h"
+#include "dist_dev.h"
 #include "quant_dev.h"
 
 namespace {
@@ -128,7 +129,7 @@ __global__ __launch_bounds__(256) void rdoq_kernel(const TCoeff* __restrict__ co
           codedCost = cost0 + costSig;
           done = maxAbs == 0;
         }
-        else codedCost = 1.7976931348623157e308;
+        else codedCost = RD_MAX_DOUBLE;
         if (!done)
         {
           const double currSig = isLast ? 0.0 : lambda * sig1;

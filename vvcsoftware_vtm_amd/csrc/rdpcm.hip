@@ -5,6 +5,7 @@
 // The forward form is a closed loop: every sample's delta is taken against the RECONSTRUCTED running sum, so a line (a column for vertical, a row
 // for horizontal DPCM) is a serial chain; the lines of a TU and the TUs of a batch are independent: one wave per TU, one lane per line.
 #include "common.h"
+#include "wave_dev.h"
 #include "quant_dev.h"
 
 namespace {
@@ -71,8 +72,7 @@ __global__ __launch_bounds__(256) void rdpcm_fwd_kernel(const Pel* __restrict__ 
       if (mode != 0) acc += rec;
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+  sum = wave_sum(sum);
   if (lane == 0) absSum[ti] = sum;
 }
 

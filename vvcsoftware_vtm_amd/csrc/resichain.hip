@@ -317,8 +317,8 @@ __device__ __forceinline__ bool rc_tu_coop(const RcDesc& d, const Pel* __restric
       for (int r = 0; r < 4; r++) { int mag; lv[r] = rc_quant_one(q, cf[r], du[r], mag); sum += mag; }
       const int cgIdx = (int)inv[(16 * it + 4 * g) * W + 16 * jt + (c & ~3)] >> 4;
       int lastCg = rc_cg_nonzero(lv) ? cgIdx : -1;
-      lastCg = wave_max_i32(lastCg);
-      sum = wave_sum_i32(sum);
+      lastCg = wave_max(lastCg);
+      sum = wave_sum(sum);
       if (lane == 0) { atomicAdd(&red[0], sum); atomicMax(&red[1], lastCg); }
       __syncthreads();                                      // (every wave has read its E1 operands: E2 may be written)
       lastCg = red[1];

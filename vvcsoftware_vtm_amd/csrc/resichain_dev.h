@@ -7,6 +7,7 @@
 // Quant::dequant (Quant.cpp:277-428), the reconstruction clip (Buffer.cpp:66-79) -- see resichain.hip.
 #pragma once
 #include "common.h"
+#include "wave_dev.h"
 #include "mfma_tr.h"
 #include "quant_dev.h"
 
@@ -72,19 +73,6 @@ __device__ __forceinline__ int quad_min(int v)
   v = min(v, __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xF, 0xF, false));
   return v;
 }
-__device__ __forceinline__ int wave_max_i32(int v)
-{
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o));
-  return v;
-}
-__device__ __forceinline__ int wave_sum_i32(int v)
-{
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
 // scan position (diagonal 4x4 scan: 0 4 1 8 5 2 12 9 6 3 13 10 7 14 11 15 in raster terms) of (row r, column x) inside a coefficient group
 __device__ __forceinline__ int rc_kpos(int r, int x)
 {
@@ -252,8 +240,8 @@ __device__ __forceinline__ bool rc_tu_mfma(const RcDesc& d, const Pel* __restric
           cgIdx[it][jt] = (int)inv[(16 * it + 4 * g) * W + 16 * jt + (c & ~3)] >> 4;
           if (rc_cg_nonzero(lv[it][jt])) lastCg = max(lastCg, cgIdx[it][jt]);
         }
-      lastCg = wave_max_i32(lastCg);
-      sum = wave_sum_i32(sum);
+      lastCg = wave_max(lastCg);
+      sum = wave_sum(sum);
       if (lane == 0) absSumOut[ti] = (unsigned)sum;
 #pragma unroll
       for (int it = 0; it < S::IT; it++)
@@ -449,7 +437,7 @@ __device__ void rc_tu_generic(const RcDesc& d, const Pel* __restrict__ orgBase, 
       const bool nz = rc_cg_nonzero(lv);
       if (on && nz) lastCg = max(lastCg, (int)inv[row * w + (col & ~3)] >> 4);
     }
-    lastCg = wave_max_i32(lastCg);
+    lastCg = wave_max(lastCg);
     for (int r0 = 0; r0 < h; r0 += rowsPerPass)
     {
       const int row = r0 + rsub;
@@ -466,7 +454,7 @@ __device__ void rc_tu_generic(const RcDesc& d, const Pel* __restrict__ orgBase, 
       }
     }
   }
-  sum = wave_sum_i32(sum);
+  sum = wave_sum(sum);
   if (lane == 0) absSumOut[ti] = (unsigned)sum;
   }
   else

@@ -78,7 +78,7 @@ __global__ __launch_bounds__(RR_THREADS) void resi_rate_kernel(const RrArgs a)
 
     // ---- the levels into LDS; scanPosLast, numSig and the significant groups
     reinterpret_cast<unsigned*>(cg)[lane] = 0u;
-    rr_wave_sync();
+    wave_sync();
     int last = -1;
     unsigned numSig = 0;
     {
@@ -95,9 +95,9 @@ __global__ __launch_bounds__(RR_THREADS) void resi_rate_kernel(const RrArgs a)
         numSig += (unsigned)__popcll(__ballot(v != 0));
       }
     }
-    last = rr_wave_max(last);
+    last = __builtin_amdgcn_readfirstlane(wave_max(last));
     numSig = (unsigned)__builtin_amdgcn_readfirstlane((int)numSig);
-    rr_wave_sync();
+    wave_sync();
 
     if (last >= 0)
     {
@@ -219,14 +219,14 @@ __global__ __launch_bounds__(RR_THREADS) void resi_rate_kernel(const RrArgs a)
 
     // ---- the sums and the row
     acc += (unsigned long long)ep << RR_SCALE_BITS;
-    acc = rr_wave_sum(acc);
+    acc = wave_sum(acc);
     if (lane == 0) { a.frac[item] = acc; a.numSig[item] = numSig; }
     if (a.ctxOut)
     {
       unsigned char* const out = a.ctxOut + (size_t)item * VVCGPU_RESI_RATE_CTX_BYTES;
       out[b0] = (unsigned char)s0; out[b1] = (unsigned char)s1; out[b2] = (unsigned char)s2;
     }
-    rr_wave_sync();                                                       // the levels and the group flags are free again
+    wave_sync();                                                       // the levels and the group flags are free again
   }
 }
 
@@ -238,13 +238,6 @@ struct RcArgs
   int* slot; int* cbf; unsigned* absOut; unsigned long long* dist; unsigned long long* bits; double* minCost; int n;
 };
 struct RcPick { int slot, cbf; unsigned absSum; unsigned long long dist, bits; double cost; };
-
-__device__ __forceinline__ unsigned long long rc_weighted(double weight, unsigned long long x) { return (unsigned long long)(weight * (double)x); }
-__device__ __forceinline__ double rc_cost(double scale, unsigned long long dist, unsigned long long bits)
-{
-  const double scaled = scale * (double)dist;                             // RdCost::calcRdCost: a multiply, then an add (-ffp-contract=off)
-  return scaled + (double)bits;
-}
 
 // :4395-4568 for item i with the previous component's cbf p; false: the item is skipped
 __device__ bool rc_choose_one(const RcArgs& a, int i, int p, RcPick& best)
@@ -270,9 +263,9 @@ __device__ bool rc_choose_one(const RcArgs& a, int i, int p, RcPick& best)
   };
   if (!cand(0) || zd == ~0ull || tsEarly) return false;
   const double weight = a.weight[i];
-  const unsigned long long nonDist = rc_weighted(weight, zd), nonBits = a.cbfBits[4 * (size_t)i + 2 * p];
-  const double nonCost = rc_cost(a.scale, nonDist, nonBits);
-  double minCost = 1.7976931348623157e308;                                // MAX_DOUBLE
+  const unsigned long long nonDist = rd_weighted(weight, zd), nonBits = a.cbfBits[4 * (size_t)i + 2 * p];
+  const double nonCost = rd_cost(a.scale, nonDist, nonBits);
+  double minCost = RD_MAX_DOUBLE;
   best.slot = -1;
   for (int k = 0; k < VVCGPU_INTER_RESI_SLOTS; k++)
   {
@@ -282,10 +275,10 @@ __device__ bool rc_choose_one(const RcArgs& a, int i, int p, RcPick& best)
     unsigned long long bits, dist; double cost; int cbf;
     if (s > 0u)
     {
-      bits = a.cbfBits[4 * (size_t)i + 2 * p + 1] + a.frac[o + k]; dist = rc_weighted(weight, a.distResi[o + k]); cbf = 1;
-      cost = rc_cost(a.scale, dist, bits);
+      bits = a.cbfBits[4 * (size_t)i + 2 * p + 1] + a.frac[o + k]; dist = rd_weighted(weight, a.distResi[o + k]); cbf = 1;
+      cost = rd_cost(a.scale, dist, bits);
     }
-    else if (ts) { bits = 0; dist = 0; cbf = 0; cost = 1.7976931348623157e308; }
+    else if (ts) { bits = 0; dist = 0; cbf = 0; cost = RD_MAX_DOUBLE; }
     else { bits = nonBits; dist = nonDist; cbf = 0; cost = nonCost; }
     if (cost < minCost || (ts && cost == minCost))
     {
@@ -312,7 +305,7 @@ __global__ __launch_bounds__(256) void inter_resi_choose_kernel(const RcArgs a)
     if (ok) p = best.cbf;
   }
   if (ok) ok = rc_choose_one(a, i, p, best);
-  if (!ok) { best.slot = -1; best.cbf = 0; best.absSum = 0xFFFFFFFFu; best.dist = ~0ull; best.bits = ~0ull; best.cost = 1.7976931348623157e308; }
+  if (!ok) { best.slot = -1; best.cbf = 0; best.absSum = 0xFFFFFFFFu; best.dist = ~0ull; best.bits = ~0ull; best.cost = RD_MAX_DOUBLE; }
   a.slot[i] = best.slot; a.cbf[i] = best.cbf; a.absOut[i] = best.absSum; a.dist[i] = best.dist; a.bits[i] = best.bits; a.minCost[i] = best.cost;
 }
 
@@ -335,7 +328,7 @@ extern "C" int vvcgpu_resi_rate_batch(const vvc_coef* level_base, const struct v
   a.level = level_base; a.items = items; a.gate = gate; a.ctx = ctx; a.est = est_bits; a.nxt = next_state;
   a.frac = reinterpret_cast<unsigned long long*>(frac_bits); a.numSig = num_sig; a.ctxOut = ctx_out;
   a.scan = tb.scan; a.inv = tb.dqInv; a.scanOff = tb.scanOff; a.n = n; a.nCtx = n_ctx;
-  hipLaunchKernelGGL(resi_rate_kernel, dim3(rr_workgroups(n)), dim3(RR_THREADS), 0, st, a);
+  hipLaunchKernelGGL(resi_rate_kernel, dim3(vvc_grid_cap(n, RR_WAVES, 8)), dim3(RR_THREADS), 0, st, a);
   VVC_LAUNCH_CHECK();
   return VVCGPU_OK;
 }

@@ -1,7 +1,8 @@
-// resirate_dev.h -- what the kernel of vvcgpu_resi_rate_batch (resirate.hip) takes from the reference's tables, stated once as arithmetic, the lane
-// layout of a context row and the wavefront helpers.
+// resirate_dev.h -- what the kernel of vvcgpu_resi_rate_batch (resirate.hip) takes from the reference's tables, stated once as arithmetic, and the lane
+// layout of a context row.
 #pragma once
 #include "common.h"
+#include "dist_dev.h"
 
 namespace {
 
@@ -45,20 +46,5 @@ __device__ __forceinline__ int rr_row_byte(int set, int lane)
                        : lane < 63 ? VVCGPU_RESI_RATE_GT2 + lane - 42 : VVCGPU_RESI_RATE_TS;
   return lane < 50 ? lane : lane < 54 ? VVCGPU_RESI_RATE_EMT + lane - 50 : VVCGPU_RESI_RATE_CTX_USED + lane - 54;
 }
-
-__device__ __forceinline__ void rr_wave_sync() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }
-__device__ __forceinline__ int rr_wave_max(int v)
-{
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) v = max(v, __shfl_xor(v, d));
-  return __builtin_amdgcn_readfirstlane(v);
-}
-__device__ __forceinline__ unsigned long long rr_wave_sum(unsigned long long v)
-{
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
-  return v;
-}
-inline int rr_workgroups(int n) { const int cap = 8 * vvcgpu_cu_count(), wgs = cdiv(n, RR_WAVES); return wgs < cap ? wgs : cap; }
 
 }  // namespace

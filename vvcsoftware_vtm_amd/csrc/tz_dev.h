@@ -2,15 +2,9 @@
 // uni-predictive stage (unipredme.hip).  Reference lines and the design are described at the top of tzsearch.hip.
 #pragma once
 #include "common.h"
+#include "dist_dev.h"
 
 namespace {
-
-__device__ __forceinline__ unsigned tz_expgolomb_bits(int v)   // RdCost.h:172-184
-{
-  unsigned len = 1, t = (v <= 0) ? ((unsigned)(-v) << 1) + 1 : (unsigned)(v << 1);
-  while (t > 128u) { len += 14; t >>= 7; }
-  return len + ((31 - __clz((int)t)) << 1);
-}
 
 // small signed tables packed into immediates: entry i holds v[i] + bias in `bits` bits
 template <int N> constexpr unsigned pack_tab(const int (&v)[N], int bits, int bias)
@@ -67,8 +61,8 @@ struct TzTeam
   }
   __device__ __forceinline__ unsigned long long mvcost(int x, int y) const
   {
-    const unsigned bits = tz_expgolomb_bits(((x << costScale) - predHor) >> imvShift) + tz_expgolomb_bits(((y << costScale) - predVer) >> imvShift);
-    return (unsigned long long)(lambda * (double)bits);
+    const unsigned bits = expgolomb_bits(((x << costScale) - predHor) >> imvShift) + expgolomb_bits(((y << costScale) - predVer) >> imvShift);
+    return rd_getcost(lambda, bits);
   }
 
   // candidate c of the round: position, point number, distance; false = not visited (the nested range tests of :431-632, :349-374)
@@ -368,7 +362,7 @@ struct TzTeam
       cur = nxt;
     }
     // fold the lanes of this wavefront (the tail of round() folds across groups of G lanes only)
-    for (int m = 1; m < 64; m <<= 1) { const unsigned long long ok = __shfl_xor(key, m); key = min(key, ok); }
+    key = wave_min(key);
     return true;
   }
 

@@ -101,7 +101,7 @@ __device__ __forceinline__ void up_search(const vvcgpu_unipred_me_item* __restri
     unsigned sad = 0;
     me_pred_uni<NT>(u, plane, c.ref_stride, c.bit_depth, c.clp_min, c.clp_max, a.mv_cand[i][0], a.mv_cand[i][1], L.work, tid,
                     [&](int k, int, int, int v) { sad += (unsigned)abs((int)L.F.org[k] - v); });
-    tmpl[i] = owner_sum<NT>(sad, L.part, tid) + pu_getcost(c.lambda, c.mvp_idx_cost[i]);
+    tmpl[i] = owner_sum<NT>(sad, L.part, tid) + rd_getcost(c.lambda, c.mvp_idx_cost[i]);
     if (bestTmpl > tmpl[i]) { bestTmpl = tmpl[i]; mvpIdx = i; }
   }
   int predX = a.mv_cand[mvpIdx][0], predY = a.mv_cand[mvpIdx][1];
@@ -162,7 +162,7 @@ __device__ __forceinline__ void up_search(const vvcgpu_unipred_me_item* __restri
     mvX = (ix << 2) + (L.fres->half_x << 1) + L.fres->qter_x; mvY = (iy << 2) + (L.fres->half_y << 1) + L.fres->qter_y;
     const unsigned mvBits = me_mvbits(predX, predY, 0, mvX, mvY);
     bits += mvBits;
-    cost = (unsigned long long)(floor(1.0 * ((double)L.fres->cost - (double)pu_getcost(c.lambda, mvBits))) + (double)pu_getcost(c.lambda, bits));
+    cost = (unsigned long long)(floor(1.0 * ((double)L.fres->cost - (double)rd_getcost(c.lambda, mvBits))) + (double)rd_getcost(c.lambda, bits));
     me_check_best_mvp(a.mv_cand, a.num_cand, c.mvp_idx_cost, c.lambda, mvX, mvY, predX, predY, mvpIdx, bits, cost);
   }
   if (tid == 0)
@@ -227,9 +227,9 @@ __global__ __launch_bounds__(256) void unipred_decide_kernel(const vvcgpu_unipre
         int mvpIdx = s.mvp_idx, predX = a.mv_cand[mvpIdx][0], predY = a.mv_cand[mvpIdx][1];
         s.mv[0] = R->s[0][k].mv[0]; s.mv[1] = R->s[0][k].mv[1];
         unsigned long long cost = costL0[k];
-        cost -= pu_getcost(c.lambda, bitsL0[k]);
+        cost -= rd_getcost(c.lambda, bitsL0[k]);
         unsigned bits = s.bits + me_mvbits_imv(predX, predY, 0, c.imv << 1, s.mv[0], s.mv[1]);
-        cost += pu_getcost(c.lambda, bits);
+        cost += rd_getcost(c.lambda, bits);
         if (c.imv == 0) me_check_best_mvp(a.mv_cand, a.num_cand, c.mvp_idx_cost, c.lambda, s.mv[0], s.mv[1], predX, predY, mvpIdx, bits, cost);
         s.mvp_idx = mvpIdx; s.bits = bits; s.cost = cost;
         R->s[list][r] = s;
