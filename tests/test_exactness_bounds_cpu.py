@@ -1,5 +1,5 @@
 """CPU: the worst-case inputs of tests/cases.py really sit on the bounds the device kernels' exactness arguments name (csrc/mfma_tr.h, csrc/resichain.hip,
-csrc/stats.hip).  The device tests at those bounds (test_tr_fwd_inv_at_the_exactness_bound, test_resi_chain_at_the_exactness_bound,
+csrc/saostats.hip, csrc/alfstats.hip).  The device tests at those bounds (test_tr_fwd_inv_at_the_exactness_bound, test_resi_chain_at_the_exactness_bound,
 test_sao_stats_one_category_full_ctu, ...) use the same builders and rely on what is asserted here."""
 import numpy as np
 

@@ -8,6 +8,7 @@ what their metadata notes say: VGPR, AGPR, spilled VGPR, static LDS, scratch.
 
 usage: python tools/kernel_streams.py PARENT_TREE THIS_TREE source [source ..] [--same here=parent ..] [--all]
   source      a file name under vvcsoftware_vtm_amd/csrc, with or without .hip
+              HERE=PARENT where the source has another name in the parent, e.g. after a split: saostats=stats alfstats=stats
   --same      a function of this tree that is to be compared with a function of another name in the parent (readable names, as the table prints them)
   --all       list the identical non-kernel functions too (default: their number)
 """
@@ -96,15 +97,27 @@ def main():
     if len(pos) < 3:
         sys.exit(__doc__)
     parent, here = os.path.abspath(pos[0]), os.path.abspath(pos[1])
-    srcs = [s[:-4] if s.endswith(".hip") else s for s in pos[2:]]
+    srcs = []                                                              # (here, parent)
+    for a in pos[2:]:
+        sh, _, sp = a.partition("=")
+        srcs.append(tuple(s[:-4] if s.endswith(".hip") else s for s in (sh, sp or sh)))
     with tempfile.TemporaryDirectory() as tmp:
         with ThreadPoolExecutor(max_workers=8) as ex:
-            jobs = [(ex.submit(compile_s, parent, s, os.path.join(tmp, "p_" + s + ".s")), ex.submit(compile_s, here, s, os.path.join(tmp, "h_" + s + ".s")))
-                    for s in srcs]
+            done = {}                                                      # a parent source that several sources of this tree came from is compiled once
+
+            def asm(tree, tag, s):
+                if (tag, s) not in done:
+                    done[tag, s] = ex.submit(compile_s, tree, s, os.path.join(tmp, tag + s + ".s"))
+                return done[tag, s]
+
+            jobs = [(asm(parent, "p_", sp), asm(here, "h_", sh)) for sh, sp in srcs]
             A, B = {}, {}
-            for s, (p, h) in zip(srcs, jobs):                              # a kernel by its name alone (it may move), a called body by source and name
-                A.update({n if f[1] else s + ": " + n: f for n, f in parse(p.result(), same).items()})   # the parent's under this tree's names
+            for (s, _), (_, h) in zip(srcs, jobs):                         # a kernel by its name alone (it may move), a called body by source and name
                 B.update({n if f[1] else s + ": " + n: f for n, f in parse(h.result(), {}).items()})
+            for sp in dict.fromkeys(sp for _, sp in srcs):                 # the parent's under this tree's names: a called body under the source of
+                heirs = [sh for sh, p in srcs if p == sp]                  # this tree that has it now, or the first that came from its source
+                for n, f in parse(done["p_", sp].result(), same).items():
+                    A[n if f[1] else next((sh for sh in heirs if sh + ": " + n in B), heirs[0]) + ": " + n] = f
     key = lambda r: "/".join(r.get(k, "?") for k in ("vgpr_count", "agpr_count", "vgpr_spill_count", "group_segment_fixed_size", "private_segment_fixed_size"))
     print("%-44s %13s  %-9s  %s" % ("function", "parent / here", "stream", "VGPR/AGPR/spilled/LDS/scratch   parent -> here"))
     quiet = 0

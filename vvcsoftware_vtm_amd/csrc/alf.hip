@@ -15,6 +15,7 @@
 //   * filtering: one thread per 4x4 block (the granularity at which coefficients change), 10 input rows
 //     streamed through registers into 16 accumulators; the class's coefficients are permuted once per block.
 #include "common.h"
+#include "alf_dev.h"
 #include <cstddef>
 
 namespace {
@@ -23,40 +24,6 @@ constexpr int CT = 64;            // classify tile (pixels)
 constexpr int CP = 72;            // LDS pitch (samples): x origin = tile_x - 4, 72 = 64 + 8
 constexpr int CR = CT + 6;        // rows: y origin = tile_y - 3
 constexpr int QN = CT / 4 + 1;    // 17 quads per dimension
-
-// Loads rows [y0, y0+rows) x cols [x0, x0+pitch) of the plane into LDS (int16), replicating the
-// picture border (== extendBorderPel).  x0 is a multiple of 4 samples, pitch a multiple of 4.
-template <int PITCH>
-__device__ __forceinline__ void load_tile_clamped(short* __restrict__ lds, const Pel* __restrict__ src,
-                                                  int stride, int w, int h, int x0, int y0, int rows,
-                                                  int tid, int nthreads)
-{
-  constexpr int VPR = PITCH / 4;                      // 8-byte vectors per row
-  const int nvec = rows * VPR;
-  const bool vec_ok = ((stride & 3) == 0) && ((reinterpret_cast<uintptr_t>(src) & 7) == 0);
-  for (int v = tid; v < nvec; v += nthreads)
-  {
-    const int r = v / VPR, c = (v - r * VPR) * 4;
-    int y = y0 + r;
-    y = y < 0 ? 0 : (y >= h ? h - 1 : y);
-    const int x = x0 + c;
-    const Pel* row = src + (size_t)y * stride;
-    pel4 val;
-    if (vec_ok && x >= 0 && x + 3 < w)
-      val = *reinterpret_cast<const pel4*>(row + x);
-    else
-    {
-#pragma unroll
-      for (int k = 0; k < 4; k++)
-      {
-        int xx = x + k;
-        xx = xx < 0 ? 0 : (xx >= w ? w - 1 : xx);
-        val[k] = row[xx];
-      }
-    }
-    *reinterpret_cast<pel4*>(lds + r * PITCH + c) = val;
-  }
-}
 
 __global__ __launch_bounds__(320) void alf_classify_kernel(const Pel* __restrict__ src, int stride, int w, int h,
                                                            int shift, uint16_t* __restrict__ cls, int gx, int total, int xcd)
@@ -75,35 +42,9 @@ __global__ __launch_bounds__(320) void alf_classify_kernel(const Pel* __restrict
   {
     const int qi = tid / QN, qj = tid - qi * QN;
     // quad region: picture rows ty0 + 4qi - 2 .. +3, cols tx0 + 4qj - 2 .. +3  ->  LDS row 4qi+1, col 4qj+2
-    // Two samples per instruction: a row of the 6x6 neighbourhood (columns 4qj+1 .. 4qj+6) is four aligned dwords, its five sample pairs
-    // P0..P4 = (s0,s1) .. (s4,s5) are two of the dwords and three v_alignbit; |2c - a - b| of a pair of samples is ONE v_sad_u16 of the
-    // doubled centre pair against the packed sum of the two neighbour pairs (samples are non-negative, <= 15 bits: nothing wraps), which also
-    // accumulates.  18 instructions per row of four samples instead of 64.
     const unsigned* base = reinterpret_cast<const unsigned*>(tile + (4 * qi) * CP + 4 * qj);
-    unsigned sv = 0, sh = 0, sd0 = 0, sd1 = 0;
-    unsigned A[5], B[5], C[5];                        // pairs of the rows above / at / below the centre row
-    auto loadRow = [&](int r, unsigned (&P)[5])
-    {
-      const uint2 lo = *reinterpret_cast<const uint2*>(base + r * (CP / 2)), hi = *reinterpret_cast<const uint2*>(base + r * (CP / 2) + 2);
-      P[0] = __builtin_amdgcn_alignbit(lo.y, lo.x, 16); P[1] = lo.y; P[2] = __builtin_amdgcn_alignbit(hi.x, lo.y, 16); P[3] = hi.x;
-      P[4] = __builtin_amdgcn_alignbit(hi.y, hi.x, 16);
-    };
-    typedef unsigned short us2v __attribute__((ext_vector_type(2)));
-    auto padd = [](unsigned a, unsigned b) { return __builtin_bit_cast(unsigned, __builtin_bit_cast(us2v, a) + __builtin_bit_cast(us2v, b)); };
-    loadRow(0, A); loadRow(1, B);
-#pragma unroll
-    for (int y = 0; y < 4; y++)
-    {
-      loadRow(y + 2, C);
-      // centre row = B: centres (s1,s2) = B[1], (s3,s4) = B[3]
-      const unsigned c01 = padd(B[1], B[1]), c23 = padd(B[3], B[3]);
-      sv  = __builtin_amdgcn_sad_u16(c01, padd(A[1], C[1]), sv);   sv  = __builtin_amdgcn_sad_u16(c23, padd(A[3], C[3]), sv);
-      sh  = __builtin_amdgcn_sad_u16(c01, padd(B[0], B[2]), sh);   sh  = __builtin_amdgcn_sad_u16(c23, padd(B[2], B[4]), sh);
-      sd0 = __builtin_amdgcn_sad_u16(c01, padd(A[0], C[2]), sd0);  sd0 = __builtin_amdgcn_sad_u16(c23, padd(A[2], C[4]), sd0);
-      sd1 = __builtin_amdgcn_sad_u16(c01, padd(C[0], A[2]), sd1);  sd1 = __builtin_amdgcn_sad_u16(c23, padd(C[2], A[4]), sd1);
-#pragma unroll
-      for (int k = 0; k < 5; k++) { A[k] = B[k]; B[k] = C[k]; }
-    }
+    constexpr int quadPitch = CP;
+#include "alf_quad_sums.inc"
     int* q = quad + tid * 4;
     q[0] = (int)sv; q[1] = (int)sh; q[2] = (int)sd0; q[3] = (int)sd1;
   }
@@ -123,25 +64,8 @@ __global__ __launch_bounds__(320) void alf_classify_kernel(const Pel* __restrict
       const int sumH = q00[1] + q01[1] + q10[1] + q11[1];
       const int sumD0 = q00[2] + q01[2] + q10[2] + q11[2];
       const int sumD1 = q00[3] + q01[3] + q10[3] + q11[3];
-      // th[] of AdaptiveLoopFilter.cpp:294 packed 4 bits per entry
-      const unsigned long long th = 0x4333333332222210ull;
-      const int activity = (short)clip3(0, 15, ((sumV + sumH) * 32) >> shift);
-      int classIdx = (int)((th >> (4 * activity)) & 15);
-      int hv1, hv0, d1, d0, dirHV, dirD;
-      if (sumV > sumH) { hv1 = sumV; hv0 = sumH; dirHV = 1; } else { hv1 = sumH; hv0 = sumV; dirHV = 3; }
-      if (sumD0 > sumD1) { d1 = sumD0; d0 = sumD1; dirD = 0; } else { d1 = sumD1; d0 = sumD0; dirD = 2; }
-      int hvd1, hvd0, mainDir, secDir;
-      // products wrap modulo 2^32 exactly like the reference's int arithmetic
-      if ((int)((unsigned)d1 * (unsigned)hv0) > (int)((unsigned)hv1 * (unsigned)d0))
-      { hvd1 = d1; hvd0 = d0; mainDir = dirD; secDir = dirHV; }
-      else
-      { hvd1 = hv1; hvd0 = hv0; mainDir = dirHV; secDir = dirD; }
-      int strength = 0;
-      if (hvd1 > 2 * hvd0) strength = 1;
-      if (hvd1 * 2 > 9 * hvd0) strength = 2;
-      if (strength) classIdx += (((mainDir & 1) << 1) + strength) * 5;
-      // transposeTable {0,1,0,2,2,3,1,3} packed 2 bits per entry (:447)
-      const int transposeIdx = (0xDE84u >> (2 * (mainDir * 2 + (secDir >> 1)))) & 3;
+      const int& keyShift = shift;
+#include "alf_class_key.inc"
       cls[(size_t)(by >> 2) * (w >> 2) + (bx >> 2)] = (uint16_t)(classIdx | (transposeIdx << 8));
     }
   }
@@ -154,27 +78,6 @@ constexpr int FP = FW + 8;          // LDS pitch, x origin = tile_x - 4
 constexpr int FR = FH + 6;          // rows, y origin = tile_y - 3
 
 struct AlfCoeffs { int16_t c[25 * 13]; };   // passed by value in the kernel argument block
-
-// coefficient index K(dy,dx) of the point-symmetric diamonds (AdaptiveLoopFilter.cpp:600-636)
-template <bool IS7>
-__device__ __forceinline__ constexpr int tapIndex(int dy, int dx)
-{
-  if (dy < 0 || (dy == 0 && dx < 0)) { dy = -dy; dx = -dx; }
-  if (IS7)
-  {
-    if (dy == 3) return dx == 0 ? 0 : -1;
-    if (dy == 2) return dx == 1 ? 1 : dx == 0 ? 2 : dx == -1 ? 3 : -1;
-    if (dy == 1) return (dx >= -2 && dx <= 2) ? 6 - dx : -1;
-    return dx <= 3 ? 12 - dx : -1;
-  }
-  else
-  {
-    if (dy == 2) return dx == 0 ? 0 : -1;
-    if (dy == 1) return (dx >= -1 && dx <= 1) ? 2 - dx : -1;
-    if (dy == 0) return dx <= 2 ? 6 - dx : -1;
-    return -1;
-  }
-}
 
 template <bool IS7, bool LUMA>
 __device__ __forceinline__ void alf_filter_body(const int bidx, const int bidy, short* tile, short* scoef, const Pel* __restrict__ src, int sstride,
