@@ -1209,16 +1209,29 @@ int vvcgpu_inter_resi_code_batch(const vvc_pel* org_base, const vvc_pel* pred_ba
  * ws           device workspace of vvcgpu_inter_resi_code_dq_workspace_bytes(level_extent, n) bytes, 16-byte aligned: the coefficients, the trellis
  *              decisions and level histories -- all indexed by the slot's level offset -- and per slot a trellis record and a work-list entry.  It may hold anything on
  *              entry; nothing in it survives the call by contract.
- * Served: sides 4..64, DCT-II and the four inter-EMT pairs (DCT-II only on a 64-point side), bit depth 8..10.
+ * flags        VVCGPU_INTER_RESI_WRITE_REC as above, and VVCGPU_INTER_RESI_DQ_TS (this entry's alone; vvcgpu_inter_resi_code_batch refuses it): a slot
+ *              with code VVCGPU_INTER_RESI_TS on an item with w == 4 && h == 4 -- the transform-skip candidate the reference tests on every 4x4 block it
+ *              codes under TransformSkip 1 (InterSearch.cpp:4340-4386: luma without cu.emtFlag, chroma 4x4) -- is served like any other slot.  In this
+ *              reference TrQuant::transformNxN (TrQuant.cpp:966-977) hands the output of xTransformSkip to the same DepQuant::quant, and DepQuant.cpp
+ *              reads tu.transformSkip for extended precision only (:663, :755; off), so with shift = 15 - bit_depth - 2 (getTransformShift of 4x4):
+ *                coefficients = orgResi << shift (xTransformSkip :1140-1148), the trellis and dequantBlock unchanged,
+ *                resi' = (coef' + (1 << (shift - 1))) >> shift (xITransformSkip :823-833), unclipped;
+ *              levels, abs_sum, both distortions, the reconstruction and the all-zero rule as for every slot.  The kernels of a call with the flag
+ *              are instantiations of their own: a call without it runs what it ran before the flag existed.
+ * Served: sides 4..64, DCT-II and the four inter-EMT pairs (DCT-II only on a 64-point side), with VVCGPU_INTER_RESI_DQ_TS transform skip on 4x4 (on no
+ * other size: TU::hasTransformSkipFlag with Log2MaxTransformSkipBlockSize 2 allows an area of at most 16, and sides of 2 are not served here), bit depth 8..10.
  * An ITEM is skipped, beside the rules above, when a side is 2, when level_off is negative or not a multiple of 16 (the trellis workspace is indexed by
  * it), when rates_idx is outside [0, n_rates) or lambda is not above zero.  A SLOT is skipped, beside the rules above, when it is a transform-skip slot
- * or its levels do not lie inside level_extent.
+ * and the call does not carry VVCGPU_INTER_RESI_DQ_TS or the block is not 4x4, or when its levels do not lie inside level_extent.
  * VVCGPU_E_ARG before any device work: the cases of vvcgpu_inter_resi_code_batch, a null dq, rates or ws, n_rates < 1, level_extent < 16, a workspace
  * that is too small or not 16-byte aligned, a dq array that is not 8-byte aligned.  n == 0 is a no-op.
  * With the caller: as for vvcgpu_inter_resi_code_batch, and the rate tables (one per component and TU size class, refreshed when the CABAC contexts move).
- * Not served: blocks with a side of 2 and transform skip (vvcgpu_depquant_batch serves neither: the binding keeps them on the host), RDOQ,
- * cross-component prediction, RDPCM and lossless.                                                                                                  */
+ * Not served: blocks with a side of 2 (vvcgpu_depquant_batch does not serve them either: the binding keeps them on the host), transform skip with
+ * rotation or RDPCM (range extensions, off), RDOQ, cross-component prediction, RDPCM and lossless.  Transform skip itself is no limit of
+ * vvcgpu_depquant_batch: it takes the scaled residual as coefficients like any others, and the stand-alone chain is vvcgpu_tr_fwd_batch with tr_hor = 3,
+ * vvcgpu_depquant_batch, vvcgpu_dequant_tr_inv_batch with tr_hor = 3 and dep_quant = 1 (sides of 4 and up).                                        */
 #define VVCGPU_INTER_RESI_Q_DEPQUANT 1     /* quantiser: DQIntern::DepQuant::quant */
+#define VVCGPU_INTER_RESI_DQ_TS      8     /* flags of vvcgpu_inter_resi_code_dq_batch: a VVCGPU_INTER_RESI_TS slot of a 4x4 item is served */
 typedef struct vvcgpu_inter_resi_dq {
   double  lambda;                          /* Quant::m_dLambda of the component */
   int32_t rates_idx;                       /* index into the rates array */
@@ -1558,15 +1571,26 @@ int vvcgpu_intra_tu_code_batch(
  * ws           device workspace of vvcgpu_intra_tu_code_dq_workspace_bytes(level_extent, n) bytes, 16-byte aligned: the coefficients, the trellis
  *              decisions and level histories, the predictions between the first and the last launch -- all indexed by the item's level offset -- and
  *              per item a trellis record and a work-list entry.  It may hold anything on entry; nothing in it survives the call by contract.
+ * flags        VVCGPU_INTRA_TU_WRITE_PRED and VVCGPU_INTRA_TU_NO_SMOOTHING as above, and VVCGPU_INTRA_TU_DQ_TS (this entry's alone;
+ *              vvcgpu_intra_tu_code_batch refuses it): an item with tus[i].tr_hor == 3 and w == h == 4 is the checkTransformSkip candidate of
+ *              xRecurIntraCodingLumaQT (IntraSearch.cpp:1347-1412: intra luma 4x4 without cu.emtFlag); tr_ver is ignored, as in vvcgpu_tr_desc.  All
+ *              three mode kinds are served: the reference reloads the prediction it saved (default0Save1Load2, :1182-1217), the same prediction the
+ *              item forms or is given.  The arithmetic is that of VVCGPU_INTER_RESI_DQ_TS: coefficients = (org - pred) << shift with
+ *              shift = 15 - bit_depth - 2, the trellis and dequantBlock unchanged, resi' = (coef' + (1 << (shift - 1))) >> shift.  num_sig, dist,
+ *              mode_out, WRITE_PRED and the abs_sum == 0 branch work as for every item.  The kernels of a call with the flag are instantiations of
+ *              their own: a call without it runs what it ran before the flag existed.
  * An item is skipped, beside the rules of vvcgpu_intra_tu_code_batch, when level_off is negative or not a multiple of 16 (the trellis workspace is
- * indexed by it), when its w h levels do not lie inside level_extent, when rates_idx is outside [0, n_rates) or lambda is not above zero.  An item
- * outside the contract is never a fault.
+ * indexed by it), when its w h levels do not lie inside level_extent, when rates_idx is outside [0, n_rates) or lambda is not above zero.  An item with
+ * tr_hor == 3 is skipped (the rule of vvcgpu_intra_tu_code_batch: tr_hor outside 0..2) unless the call carries VVCGPU_INTRA_TU_DQ_TS and the block is
+ * 4x4.  An item outside the contract is never a fault.
  * VVCGPU_E_ARG before any device work: the cases of vvcgpu_intra_tu_code_batch, a null dq, rates or ws, n_rates < 1, level_extent < 16, a workspace
  * that is too small or not 16-byte aligned, a dq array that is not 8-byte aligned.  n == 0 is a no-op.
  * With the caller: as for vvcgpu_intra_tu_code_batch, and the rate tables (one per component and TU size class, refreshed when the CABAC contexts move).
- * Not served: RDOQ, transform skip and RDPCM, cross-component prediction, TUs split below the PU.  The chroma mode pass under DepQuant is
- * vvcgpu_intra_chroma_code_dq_batch (below); single chroma blocks also reach this entry through PRED_GIVEN.                                       */
+ * Not served: RDOQ, transform skip on any block but 4x4 (Log2MaxTransformSkipBlockSize 2) or with rotation, RDPCM, cross-component prediction, TUs
+ * split below the PU.  The chroma mode pass under DepQuant is vvcgpu_intra_chroma_code_dq_batch (below; the chroma transform-skip loop of
+ * xRecurIntraChromaCodingQT :1751-1819 is not served); single chroma blocks also reach this entry through PRED_GIVEN.                           */
 #define VVCGPU_INTRA_TU_Q_DEPQUANT 1       /* quantiser: DQIntern::DepQuant::quant */
+#define VVCGPU_INTRA_TU_DQ_TS      8       /* flags of vvcgpu_intra_tu_code_dq_batch: a 4x4 item with tr_hor == 3 is the transform-skip candidate */
 size_t vvcgpu_intra_tu_code_dq_workspace_bytes(size_t level_extent, int n);
 int vvcgpu_intra_tu_code_dq_batch(
     const vvc_pel* refs_base, const vvcgpu_intra_desc* preds,

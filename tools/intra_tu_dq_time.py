@@ -9,6 +9,9 @@ gathered on the device beforehand.
   (b) vvcgpu_intra_tu_code_dq_batch with WRITE_PRED off: three launches, the workspace allocated outside the timed part.
 The results of (a) and (b) are compared before anything is timed.  Times: device events around a whole run on the stream, 3 warm-up runs, then the median
 and the spread of 9 runs, (a) and (b) alternating in one process.
+--ts: the transform-skip candidate instead (VVCGPU_INTRA_TU_DQ_TS): at every PU position of the 4K list a 4x4 PU, per candidate mode a DCT-II item and the
+skip item behind it (tr_hor = 3) -- checkTransformSkip of xRecurIntraCodingLumaQT.  (a) is the same chain (vvcgpu_tr_fwd_batch and
+vvcgpu_dequant_tr_inv_batch serve tr_hor = 3; the prediction is formed for both items), (b) the entry with the flag.
 --profile: no timing, five runs of (b) per list -- the run to put under `rocprofv3 --kernel-trace --stats` for the split into intra_tu_dq_front_kernel,
 depquant_listed_kernel (the trellis launch that the DepQuant entries share, depquant.hip) and intra_tu_dq_back_kernel.
 The planes and build are the sibling's; the lists and the row come from tests/rd_pass_kit.py."""
@@ -37,10 +40,13 @@ rng = np.random.default_rng(49)
 
 
 def main():
-    profile = "--profile" in sys.argv
+    profile, ts = "--profile" in sys.argv, "--ts" in sys.argv
     rec = pu_search_kit.texture(rng, H, W, BD, 0.0)
     org = np.clip(np.roll(rec, (1, -2), axis=(0, 1)).astype(np.int32) + rng.integers(-4, 5, (H, W)), 0, 1023).astype(np.int16)
     lists = kit.timing_lists(rng, W, H, imc.SIDES)
+    if ts:                                                                   # the 4K list's positions as 4x4 PUs
+        _, w, _, px, py = lists[0]
+        lists = [("4K 4x4 +TS", np.full_like(w, 4), np.full_like(w, 4), px, py)]
     drec, dorg, avail = dev(rec.reshape(-1)), dev(org.reshape(-1)), dev(np.ones(192, np.uint8))
     rates = tdq.shared_rates(8)
     drates = ops.struct_to_device(rates)
@@ -49,6 +55,11 @@ def main():
         print("list        items   chain ms (min..max)   entry ms (min..max)   chain / entry   all-zero items")
     for name, w, h, px, py in lists:
         fill, nrefs, d, t, _, _, samples = sibling.build(w, h, px, py)
+        if ts:                                                               # every item twice, buffers of its own each: DCT-II, then the skip item
+            d, t = np.repeat(d, 2), np.repeat(t, 2)
+            off = 16 * np.arange(len(d))
+            d["dst_off"], t["pred_off"], t["rec_off"], t["level_off"], samples = off, off, off, off, 16 * len(d)
+            t["tr_hor"][1::2] = abi.TSKIP
         m = len(d)
         assert (t["level_off"] % 16 == 0).all()
         dq = np.zeros(m, abi.INTER_RESI_DQ)
@@ -62,7 +73,7 @@ def main():
         ws = ops.intra_tu_code_dq_workspace(samples, m)
 
         def entry():
-            return chain.run_entry(refs, dd_, dorg, None, rec_b, lev_b, dt, ddq, m, drates, len(rates), None, 0, BD, clp, ws)
+            return chain.run_entry(refs, dd_, dorg, None, rec_b, lev_b, dt, ddq, m, drates, len(rates), None, abi.INTRA_TU_DQ_TS if ts else 0, BD, clp, ws)
 
         if profile:
             for _ in range(5):

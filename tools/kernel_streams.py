@@ -24,13 +24,27 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-fno-fast-math"
 
 
 def readable(sym):
-    """_ZN12_GLOBAL__N_123intra_tu_dq_back_kernelE.. -> intra_tu_dq_back_kernel; integer and bool template arguments are kept"""
-    m = re.match(r"_ZN12_GLOBAL__N_1(\d+)", sym) or re.match(r"_Z(\d+)", sym)
+    """_ZN12_GLOBAL__N_123intra_tu_dq_back_kernelE.. -> intra_tu_dq_back_kernel; integer and bool template arguments are kept, and so is the class of a
+    static member: _ZN12_GLOBAL__N_17ItqPassILb0EE4backE.. -> ItqPass<0>::back"""
+    m = re.match(r"_ZN12_GLOBAL__N_1(?=\d)", sym) or re.match(r"_Z(?=\d)", sym)
     if not m:
         return sym
-    end = m.end() + int(m.group(1))
-    args = re.match(r"I((?:L[ib]\d+E)+)E", sym[end:])
-    return sym[m.end():end] + ("<%s>" % ", ".join(re.findall(r"L[ib](\d+)E", args.group(1))) if args else "")
+    pos, parts = m.end(), []
+    while True:
+        n = re.match(r"\d+", sym[pos:])
+        if not n:
+            break
+        pos += n.end()
+        name = sym[pos:pos + int(n.group(0))]
+        pos += len(name)
+        args = re.match(r"I((?:L[ib]\d+E)+)E", sym[pos:])
+        if args:
+            name += "<%s>" % ", ".join(re.findall(r"L[ib](\d+)E", args.group(1)))
+            pos += args.end()
+        parts.append(name)
+        if not sym.startswith("_ZN"):
+            break
+    return "::".join(parts)
 
 
 def compile_s(tree, src, out):

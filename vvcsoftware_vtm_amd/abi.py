@@ -78,6 +78,7 @@ INTRA_FILL_DESC = np.dtype([("rec_off", "<i8"), ("flags_off", "<i8"), ("ref_off"
 INTRA_TU_PRED_GIVEN, INTRA_TU_FROM_LIST = -1, -2
 INTRA_TU_WRITE_PRED, INTRA_TU_NO_SMOOTHING = 1, 2
 INTRA_TU_Q_DEPQUANT = 1                                                     # vvcgpu_intra_tu_code_dq_batch: the served quantiser
+INTRA_TU_DQ_TS = 8                                                          # its flag: a 4x4 item with tr_hor == TSKIP is the transform-skip candidate
 # vvcgpu_intra_chroma_code_batch: one chroma PU (vvcgpu_intra_chroma_pu), the mode value of LM_CHROMA_IDX and the flag
 INTRA_CHROMA_PU = np.dtype([("org_off", "<i8", (2,)), ("ref_off", "<i8", (2,)), ("luma_off", "<i8"), ("cand_off", "<i8"), ("level_off", "<i8"),
                             ("org_stride", "<i4"), ("luma_stride", "<i4"), ("qp", "<i4", (2,)), ("w", "<i2"), ("h", "<i2"), ("above_avail", "i1"),
@@ -137,6 +138,7 @@ INTER_RESI_SLOTS, INTER_RESI_TS, INTER_RESI_WRITE_REC = 6, 9, 1
 # vvcgpu_inter_resi_code_dq_batch: the record beside an item (vvcgpu_inter_resi_dq) and the served value of `quantiser`
 INTER_RESI_DQ = np.dtype([("lambda", "<f8"), ("rates_idx", "<i4"), ("luma", "i1"), ("reserved", "i1", (3,))])
 INTER_RESI_Q_DEPQUANT = 1
+INTER_RESI_DQ_TS = 8                                                        # its flag: an INTER_RESI_TS slot of a 4x4 item is served
 # vvcgpu_resi_rate_batch: one level block (struct vvcgpu_resi_rate_item), the bytes of a context row and the offsets of its regions
 RESI_RATE_ITEM = np.dtype([("level_off", "<i8"), ("ctx_idx", "<i4"), ("w", "<i2"), ("h", "<i2"), ("luma", "i1"), ("dep_quant", "i1"),
                            ("sign_hiding", "i1"), ("ts_flag", "i1"), ("emt_idx", "i1"), ("emt_inter", "i1"), ("emt_thr", "i1"), ("reserved", "i1", (9,))])

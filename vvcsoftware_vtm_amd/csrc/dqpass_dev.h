@@ -5,7 +5,7 @@
 // item's levels back to resi', and the closing loop over a parked prediction.  Host side: the workspace's layout, the checks of the arguments that the
 // three entries have alike, and their set-up.  A front kernel stages the residual in the tile and runs iq_transform<RC_FWD>, the trellis is
 // vvcgpu_depquant_listed_launch (depquant.hip), a back kernel runs iq_decode (iq_dequant, iq_transform<RC_INV>); the item walk around them is each
-// file's own.
+// file's own.  The transform-skip candidate of a 4x4 block takes iq_ts_forward / iq_ts_inverse in the transforms' place.
 #pragma once
 #include "common.h"
 #include "depquant_dev.h"
@@ -134,19 +134,38 @@ __device__ __forceinline__ void iq_dequant(const TCoeff* __restrict__ level, TCo
   }
 }
 
+// The transform-skip candidate of a 4x4 block (TU::hasTransformSkipFlag with Log2MaxTransformSkipBlockSize 2; rotation and RDPCM are range extensions,
+// off): TrQuant::transformNxN hands the scaled residual to the same DepQuant::quant, and dequantBlock does not look at tu.transformSkip without extended
+// precision, so only the scaling around the trellis differs.  The shift is getTransformShift of the shape, 15 - bd - 2 (3 at 10 bits, 5 at 8); 4x4 needs
+// no needsBlockSizeTrafoScale.  Sixteen lanes, an element each.
+__device__ __forceinline__ int iq_ts_shift(int bd) { return 15 - bd - 2; }
+// xTransformSkip (TrQuant.cpp:1140-1148): the residual, contiguous in the tile -> the sixteen coefficients
+__device__ __forceinline__ void iq_ts_forward(const short* resiT, TCoeff* __restrict__ coef, int bd, int lane)
+{
+  if (lane < 16) coef[lane] = (int)resiT[lane] * (1 << iq_ts_shift(bd));
+}
+// xITransformSkip (TrQuant.cpp:823-833): the sixteen de-quantised coefficients -> resi' in backT
+__device__ __forceinline__ void iq_ts_inverse(const TCoeff* __restrict__ coef, short* backT, int bd, int lane)
+{
+  const int shift = iq_ts_shift(bd);
+  if (lane < 16) backT[lane] = (short)((coef[lane] + (1 << (shift - 1))) >> shift);
+}
+
 // Where the inverse body leaves resi' of a wavefront that keeps nothing else in its tile: at 0, or -- a shape with a side of at most 8 (at most 512
 // samples) has the integer body's two buffers at 1024 and 2048 -- at 3072
 __device__ __forceinline__ short* iq_back_tile(short* tile, int w, int h) { return (w <= 8 || h <= 8) ? tile + 3072 : tile; }
 // The levels of a coded item (abs_sum != 0) back to resi' in backT: the dependent de-quantiser into the coefficient workspace, then the inverse
-// transform.  d: the item's chain descriptor, put into the wavefront's dS (LDS) for the bodies
+// transform.  d: the item's chain descriptor, put into the wavefront's dS (LDS) for the bodies.  tskip: the item is the transform-skip candidate of a
+// 4x4 block -- the same de-quantiser, then the scaling back in place of the inverse transform
 __device__ __forceinline__ void iq_decode(const RcDesc& d, RcDesc* dS, short* tile, short* backT, const TCoeff* level, TCoeff* coef, int bd, const _Float16* tab,
-                                          const VvcTrTables& tb, int* fbScr, int lane)
+                                          const VvcTrTables& tb, int* fbScr, int lane, bool tskip = false)
 {
   if (lane == 0) *dS = d;
   const unsigned short* const scan = tb.scan + tb.scanOff[(ilog2(d.w) - 1) * 6 + (ilog2(d.h) - 1)];
   iq_dequant(level + d.level_off, coef + d.level_off, d.w, d.h, d.qp, bd, scan, lane);
   wave_global_sync();
-  iq_transform<RC_INV>(dS, tile, backT, coef, bd, tab, tb, fbScr, lane);
+  if (tskip) iq_ts_inverse(coef + d.level_off, backT, bd, lane);
+  else iq_transform<RC_INV>(dS, tile, backT, coef, bd, tab, tb, fbScr, lane);
   wave_sync();
 }
 // The closing loop of an intra item: clip(parked pred + resi') to rec (rows recStride apart), with resi' in backT if the item is coded and zero if not

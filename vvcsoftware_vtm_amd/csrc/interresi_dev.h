@@ -111,12 +111,13 @@ __device__ __forceinline__ void ir_finish(const Args& a, const IrItem& t, int it
 // ---- host side of the two entries.  `name` is the entry's name as the error text starts with it; a check returns VVCGPU_OK or the error code with the
 // text set.  An entry calls ir_check_frame, returns for n == 0, makes its own checks, then ir_check_bit_depth: the order in which a call with several
 // faults reports them.
-inline int ir_check_frame(const char* name, int n, bool pointers, int flags, const void* rec_base, int clp_min, int clp_max)
+// (known: the flag bits the entry knows -- VVCGPU_INTER_RESI_DQ_TS is the DepQuant entry's alone)
+inline int ir_check_frame(const char* name, int n, bool pointers, int flags, const void* rec_base, int clp_min, int clp_max, int known = VVCGPU_INTER_RESI_WRITE_REC)
 {
   VVC_CHECK_ARG(n >= 0, "%s: n %d", name, n);
   if (n == 0) return VVCGPU_OK;                                           // (nothing else is looked at)
   VVC_CHECK_ARG(pointers, "%s: null pointer", name);
-  VVC_CHECK_ARG((flags & ~VVCGPU_INTER_RESI_WRITE_REC) == 0, "%s: unknown flags 0x%x", name, flags);
+  VVC_CHECK_ARG((flags & ~known) == 0, "%s: unknown flags 0x%x", name, flags);
   VVC_CHECK_ARG(rec_base || !(flags & VVCGPU_INTER_RESI_WRITE_REC), "%s: null pointer (rec_base with VVCGPU_INTER_RESI_WRITE_REC)", name);
   VVC_CHECK_ARG(clp_min <= clp_max && clp_min >= -32768 && clp_max <= 32767, "%s: clip range %d..%d", name, clp_min, clp_max);
   return VVCGPU_OK;

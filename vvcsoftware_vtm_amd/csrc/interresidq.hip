@@ -17,6 +17,9 @@
 //   back     the same wavefront-per-item walk: orgResi and the prediction re-formed in the tile; per served slot the dependent de-quantiser (the
 //            GF(2)-linear state replay, as dq_group of transform.hip) into the coefficient workspace, the inverse transform (RC_INV bodies), resi'
 //            unclipped to the candidate buffer, both distortions and the reconstruction as interresi.hip's.  A slot with abs_sum == 0 stores zeros.
+//   VVCGPU_INTER_RESI_DQ_TS  the transform-skip slot of a 4x4 item (InterSearch.cpp:4340-4386) in the same two walks: xTransformSkip (TrQuant.cpp:1140-1148)
+//            in place of the forward transform, xITransformSkip (:823-833) in place of the inverse one, sixteen lanes each (dqpass_dev.h); record, list
+//            entry, trellis and de-quantiser as for every slot.  The flag selects the kernels, IqPass<true>'s.
 #include "common.h"
 #include "dqpass_dev.h"
 #include "interresi_dev.h"
@@ -46,7 +49,9 @@ __device__ __forceinline__ bool iq_item_ok(const IqArgs& a, const IrItem& t, con
             && q.rates_idx >= 0 && q.rates_idx < a.nRates && q.lambda > 0.0;
   return ir_list_pred(ok, a.rdList, t, predOff);
 }
-// the served slots of a served item: DCT-II and the DCT-VIII / DST-VII pairs on sides up to 32, the slot's levels inside level_extent
+// the served slots of a served item: DCT-II and the DCT-VIII / DST-VII pairs on sides up to 32 and -- TS: the call carries VVCGPU_INTER_RESI_DQ_TS --
+// the transform-skip slot of a 4x4 block; the slot's levels inside level_extent
+template <bool TS>
 __device__ __forceinline__ unsigned iq_served_mask(const IqArgs& a, const IrItem& t)
 {
   const int w = t.w, h = t.h, samples = w * h;
@@ -58,7 +63,9 @@ __device__ __forceinline__ unsigned iq_served_mask(const IqArgs& a, const IrItem
   {
     const int code = (int)(signed char)(trBits >> (8 * k));
     const int th = code % 3, tv = code / 3;
-    if (code >= 0 && code < 9 && (th == 0 || w <= 32) && (tv == 0 || h <= 32) && t.level_off + (long long)(k + 1) * samples <= a.levelExtent) mask |= 1u << k;
+    bool served = code >= 0 && code < 9 && (th == 0 || w <= 32) && (tv == 0 || h <= 32);
+    if constexpr (TS) served = served || (code == VVCGPU_INTER_RESI_TS && w == 4 && h == 4);
+    if (served && t.level_off + (long long)(k + 1) * samples <= a.levelExtent) mask |= 1u << k;
   }
   return mask;
 }
@@ -82,119 +89,133 @@ __device__ __forceinline__ RcDesc iq_desc(const IrItem& t, int k, long long recO
 }
 
 // ---------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(IR_THREADS, 1) void inter_resi_dq_front_kernel(const IqArgs a, const VvcTrTables tb)
+// The two kernels are static members of a class template over TS (the call carries VVCGPU_INTER_RESI_DQ_TS), not function templates: the compiler
+// numbers the kernels of a code object by their symbol names for the look-up of the dynamic LDS in the bodies they call, and only with the template
+// argument in front of "front" / "back" do IqPass<false>'s keep the numbers, and with them every instruction, of the kernels before the flag existed
+// (inter_resi_dq_front_kernel, inter_resi_dq_back_kernel; tools/kernel_streams.py, docs/MEASUREMENTS.md).
+template <bool TS>
+struct IqPass
 {
-  extern __shared__ __align__(16) unsigned char smem[];
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const _Float16* const tab = rc_load_image<IR_THREADS>(smem, a.image, tid);   // below every wavefront walks its own items
-  unsigned char* const mine = smem + IQ_TAB_BYTES + (size_t)wave * IQ_WAVE_BYTES;
-  short* const resiT = reinterpret_cast<short*>(mine);
-  RcDesc* const dS = reinterpret_cast<RcDesc*>(resiT + IR_TILE);
-  int* const fbScr = a.fbScratch + ((size_t)blockIdx.x * IR_WAVES + wave) * IR_FB_INTS;
-  if (blockIdx.x == 0 && tid < VVC_CTR_INTS) a.nextCounters[tid] = 0;    // the counter set of the NEXT call on this stream (vvcgpu_counters)
-
-  // the wavefront's run in the trellis' work list: its served slots are counted first, a lane per item
-  const int first = (int)blockIdx.x * IR_WAVES + wave, step = (int)gridDim.x * IR_WAVES;
-  int cnt = 0;
-  for (int item = first + lane * step; item < a.n; item += 64 * step)
+  static __global__ __launch_bounds__(IR_THREADS, 1) void front(const IqArgs a, const VvcTrTables tb)
   {
-    const IrItem t = a.items[item];
-    long long predOff;
-    if (iq_item_ok(a, t, a.dq[item], predOff)) cnt += __popc(iq_served_mask(a, t));
-  }
-  int listAt = iq_reserve(a.count, cnt, lane);
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const _Float16* const tab = rc_load_image<IR_THREADS>(smem, a.image, tid);   // below every wavefront walks its own items
+    unsigned char* const mine = smem + IQ_TAB_BYTES + (size_t)wave * IQ_WAVE_BYTES;
+    short* const resiT = reinterpret_cast<short*>(mine);
+    RcDesc* const dS = reinterpret_cast<RcDesc*>(resiT + IR_TILE);
+    int* const fbScr = a.fbScratch + ((size_t)blockIdx.x * IR_WAVES + wave) * IR_FB_INTS;
+    if (blockIdx.x == 0 && tid < VVC_CTR_INTS) a.nextCounters[tid] = 0;    // the counter set of the NEXT call on this stream (vvcgpu_counters)
 
-  for (int item = first; item < a.n; item += step)
-  {
-    const IrItem t = a.items[item];
-    const IqDq q = a.dq[item];
-    long long predOff;
-    const bool ok = iq_item_ok(a, t, q, predOff);
-    const unsigned servedMask = ok ? iq_served_mask(a, t) : 0u;
-    if (lane < IR_SLOTS)                                                  // the slot's trellis record and list entry; the markers of a skipped slot
+    // the wavefront's run in the trellis' work list: its served slots are counted first, a lane per item
+    const int first = (int)blockIdx.x * IR_WAVES + wave, step = (int)gridDim.x * IR_WAVES;
+    int cnt = 0;
+    for (int item = first + lane * step; item < a.n; item += 64 * step)
     {
-      const size_t out = IR_SLOTS * (size_t)item + lane;
-      if ((servedMask >> lane) & 1u)
+      const IrItem t = a.items[item];
+      long long predOff;
+      if (iq_item_ok(a, t, a.dq[item], predOff)) cnt += __popc(iq_served_mask<TS>(a, t));
+    }
+    int listAt = iq_reserve(a.count, cnt, lane);
+
+    for (int item = first; item < a.n; item += step)
+    {
+      const IrItem t = a.items[item];
+      const IqDq q = a.dq[item];
+      long long predOff;
+      const bool ok = iq_item_ok(a, t, q, predOff);
+      const unsigned servedMask = ok ? iq_served_mask<TS>(a, t) : 0u;
+      if (lane < IR_SLOTS)                                                  // the slot's trellis record and list entry; the markers of a skipped slot
       {
-        a.recs[out] = iq_record(t.level_off + (long long)lane * t.w * t.h, t.qp, t.w, t.h, q, q.luma);
-        a.list[listAt + __popc(servedMask & ((1u << lane) - 1u))] = (int)out;
+        const size_t out = IR_SLOTS * (size_t)item + lane;
+        if ((servedMask >> lane) & 1u)
+        {
+          a.recs[out] = iq_record(t.level_off + (long long)lane * t.w * t.h, t.qp, t.w, t.h, q, q.luma);
+          a.list[listAt + __popc(servedMask & ((1u << lane) - 1u))] = (int)out;
+        }
+        else { a.absSum[out] = 0xFFFFFFFFu; a.distResi[out] = ~0ull; a.distRec[out] = ~0ull; }
       }
-      else { a.absSum[out] = 0xFFFFFFFFu; a.distResi[out] = ~0ull; a.distRec[out] = ~0ull; }
-    }
-    listAt += __popc(servedMask);
-    if (!ok)
-    {
-      if (lane == 0) a.zeroDist[item] = ~0ull;
-      continue;
-    }
-    const unsigned long long zd = ir_stage(t, a.org + t.org_off, a.pred + predOff, resiT, nullptr, lane);
-    if (lane == 0) a.zeroDist[item] = zd;
-    if (lane < IR_SLOTS && ((servedMask >> lane) & 1u)) dS[lane] = iq_desc(t, lane, 0);
-    wave_sync();
-    for (int k = 0; k < IR_SLOTS; k++)
-    {
-      if (!((servedMask >> k) & 1u)) continue;
-      iq_transform<RC_FWD>(dS + k, resiT, nullptr, a.coef, a.bd, tab, tb, fbScr, lane);
+      listAt += __popc(servedMask);
+      if (!ok)
+      {
+        if (lane == 0) a.zeroDist[item] = ~0ull;
+        continue;
+      }
+      const unsigned long long zd = ir_stage(t, a.org + t.org_off, a.pred + predOff, resiT, nullptr, lane);
+      if (lane == 0) a.zeroDist[item] = zd;
+      if (lane < IR_SLOTS && ((servedMask >> lane) & 1u)) dS[lane] = iq_desc(t, lane, 0);
       wave_sync();
+      for (int k = 0; k < IR_SLOTS; k++)
+      {
+        if (!((servedMask >> k) & 1u)) continue;
+        if (TS && iq_code(t, k) == VVCGPU_INTER_RESI_TS)                     // (a 4x4 block: iq_served_mask) the scaled residual is the coefficient block
+        {
+          iq_ts_forward(resiT, a.coef + t.level_off + (long long)k * t.w * t.h, a.bd, lane);
+          continue;
+        }
+        iq_transform<RC_FWD>(dS + k, resiT, nullptr, a.coef, a.bd, tab, tb, fbScr, lane);
+        wave_sync();
+      }
+      wave_sync();                                                       // the tile and the descriptors are free again
     }
-    wave_sync();                                                       // the tile and the descriptors are free again
   }
-}
 
-__global__ __launch_bounds__(IR_THREADS, 1) void inter_resi_dq_back_kernel(const IqArgs a, const VvcTrTables tb)
-{
-  extern __shared__ __align__(16) unsigned char smem[];
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const _Float16* const tab = rc_load_image<IR_THREADS>(smem, a.image, tid);   // below every wavefront walks its own items
-  unsigned char* const mine = smem + IQ_TAB_BYTES + (size_t)wave * IQ_WAVE_BYTES;
-  short* const resiT = reinterpret_cast<short*>(mine);
-  RcDesc* const dS = reinterpret_cast<RcDesc*>(resiT + IR_TILE);
-  int* const fbScr = a.fbScratch + ((size_t)blockIdx.x * IR_WAVES + wave) * IR_FB_INTS;
-
-  for (int item = (int)blockIdx.x * IR_WAVES + wave; item < a.n; item += (int)gridDim.x * IR_WAVES)
+  static __global__ __launch_bounds__(IR_THREADS, 1) void back(const IqArgs a, const VvcTrTables tb)
   {
-    const IrItem t = a.items[item];
-    const IqDq q = a.dq[item];
-    long long predOff;
-    if (!iq_item_ok(a, t, q, predOff)) continue;                          // (the front wrote the markers)
-    const unsigned servedMask = iq_served_mask(a, t);
-    if (!servedMask) continue;
-    const int w = t.w, h = t.h, lw = ilog2(w), samples = w * h;
-    const bool narrow = w <= 8 || h <= 8;
-    short* const predT = ir_tile_pred(resiT, narrow, samples);
-    short* const backT = ir_tile_back(resiT, narrow, samples);
-    const Pel* const predG = a.pred + predOff;
-    ir_stage(t, a.org + t.org_off, predG, resiT, predT, lane);
-    if (lane < IR_SLOTS && ((servedMask >> lane) & 1u)) dS[lane] = iq_desc(t, lane, backT ? 0 : t.cand_off + (long long)lane * samples);
-    wave_sync();
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const _Float16* const tab = rc_load_image<IR_THREADS>(smem, a.image, tid);   // below every wavefront walks its own items
+    unsigned char* const mine = smem + IQ_TAB_BYTES + (size_t)wave * IQ_WAVE_BYTES;
+    short* const resiT = reinterpret_cast<short*>(mine);
+    RcDesc* const dS = reinterpret_cast<RcDesc*>(resiT + IR_TILE);
+    int* const fbScr = a.fbScratch + ((size_t)blockIdx.x * IR_WAVES + wave) * IR_FB_INTS;
 
-    const unsigned short* const scan = tb.scan + tb.scanOff[(lw - 1) * 6 + (ilog2(h) - 1)];
-    Pel* const outBase = backT ? backT : a.resi;
-    // the closing loop of slot k of this item, as in inter_resi_code_kernel
-    auto finish = [&](int k, const short* backK) { ir_finish(a, t, item, k, resiT, predT, predG, backK, lane); };
-    for (int k = 0; k < IR_SLOTS; k++)
+    for (int item = (int)blockIdx.x * IR_WAVES + wave; item < a.n; item += (int)gridDim.x * IR_WAVES)
     {
-      if (!((servedMask >> k) & 1u)) continue;
-      const size_t out = IR_SLOTS * (size_t)item + k;
-      const long long candOff = t.cand_off + (long long)k * samples, levelOff = t.level_off + (long long)k * samples;
-      Pel* const rs = a.resi + candOff;
-      if (a.absSum[out] == 0u)                                            // all levels zero: resi' is stored as zeros
+      const IrItem t = a.items[item];
+      const IqDq q = a.dq[item];
+      long long predOff;
+      if (!iq_item_ok(a, t, q, predOff)) continue;                          // (the front wrote the markers)
+      const unsigned servedMask = iq_served_mask<TS>(a, t);
+      if (!servedMask) continue;
+      const int w = t.w, h = t.h, lw = ilog2(w), samples = w * h;
+      const bool narrow = w <= 8 || h <= 8;
+      short* const predT = ir_tile_pred(resiT, narrow, samples);
+      short* const backT = ir_tile_back(resiT, narrow, samples);
+      const Pel* const predG = a.pred + predOff;
+      ir_stage(t, a.org + t.org_off, predG, resiT, predT, lane);
+      if (lane < IR_SLOTS && ((servedMask >> lane) & 1u)) dS[lane] = iq_desc(t, lane, backT ? 0 : t.cand_off + (long long)lane * samples);
+      wave_sync();
+
+      const unsigned short* const scan = tb.scan + tb.scanOff[(lw - 1) * 6 + (ilog2(h) - 1)];
+      Pel* const outBase = backT ? backT : a.resi;
+      // the closing loop of slot k of this item, as in inter_resi_code_kernel
+      auto finish = [&](int k, const short* backK) { ir_finish(a, t, item, k, resiT, predT, predG, backK, lane); };
+      for (int k = 0; k < IR_SLOTS; k++)
       {
-        for (int e = lane; e < samples; e += 64) { if (backT) backT[e] = 0; else rs[e] = 0; }
+        if (!((servedMask >> k) & 1u)) continue;
+        const size_t out = IR_SLOTS * (size_t)item + k;
+        const long long candOff = t.cand_off + (long long)k * samples, levelOff = t.level_off + (long long)k * samples;
+        Pel* const rs = a.resi + candOff;
+        if (a.absSum[out] == 0u)                                            // all levels zero: resi' is stored as zeros
+        {
+          for (int e = lane; e < samples; e += 64) { if (backT) backT[e] = 0; else rs[e] = 0; }
+        }
+        else
+        {
+          iq_dequant(a.level + levelOff, a.coef + levelOff, w, h, t.qp, a.bd, scan, lane);
+          wave_global_sync();
+          if (TS && iq_code(t, k) == VVCGPU_INTER_RESI_TS) iq_ts_inverse(a.coef + levelOff, backT, a.bd, lane);     // (a 4x4 block: resi' returns through the tile)
+          else iq_transform<RC_INV>(dS + k, resiT, outBase, a.coef, a.bd, tab, tb, fbScr, lane);
+        }
+        if (backT) wave_sync(); else wave_global_sync();
+        finish(k, backT);
+        wave_sync();                                                     // `back` and the integer body's buffers are free again
       }
-      else
-      {
-        iq_dequant(a.level + levelOff, a.coef + levelOff, w, h, t.qp, a.bd, scan, lane);
-        wave_global_sync();
-        iq_transform<RC_INV>(dS + k, resiT, outBase, a.coef, a.bd, tab, tb, fbScr, lane);
-      }
-      if (backT) wave_sync(); else wave_global_sync();
-      finish(k, backT);
-      wave_sync();                                                     // `back` and the integer body's buffers are free again
+      wave_sync();                                                       // the tile and the descriptors are free again
     }
-    wave_sync();                                                       // the tile and the descriptors are free again
   }
-}
+};
 
 }  // namespace
 
@@ -213,7 +234,7 @@ int vvcgpu_inter_resi_code_dq_batch(const vvc_pel* org_base, const vvc_pel* pred
 {
   const char* name = "inter_resi_code_dq_batch";
   const bool pointers = org_base && pred_base && items && dq && rates && resi_base && level_base && abs_sum && dist_resi && dist_rec && zero_dist && ws;
-  if (const int rc = ir_check_frame(name, n, pointers, flags, rec_base, clp_min, clp_max)) return rc;
+  if (const int rc = ir_check_frame(name, n, pointers, flags, rec_base, clp_min, clp_max, VVCGPU_INTER_RESI_WRITE_REC | VVCGPU_INTER_RESI_DQ_TS)) return rc;
   if (n == 0) return VVCGPU_OK;
   VVC_CHECK_ARG(((uintptr_t)items & 15) == 0 && ((uintptr_t)dq & 7) == 0, "%s: item array must be 16-byte, dq array 8-byte aligned", name);
   const IqLayout lay = iq_layout(level_extent, n, IR_SLOTS, false);
@@ -221,8 +242,12 @@ int vvcgpu_inter_resi_code_dq_batch(const vvc_pel* org_base, const vvc_pel* pred
     return rc;
   hipStream_t st = (hipStream_t)stream;
   const int wgs = vvc_grid_cap(n, IR_WAVES, 1);
-  VVC_HIP(vvc_allow_lds(inter_resi_dq_front_kernel, IQ_LDS_BYTES));
-  VVC_HIP(vvc_allow_lds(inter_resi_dq_back_kernel, IQ_LDS_BYTES));
+  // the flag selects the kernels: without it the front and the back are the ones that know no transform-skip slot
+  const bool ts = (flags & VVCGPU_INTER_RESI_DQ_TS) != 0;
+  const auto front = ts ? IqPass<true>::front : IqPass<false>::front;
+  const auto back = ts ? IqPass<true>::back : IqPass<false>::back;
+  VVC_HIP(vvc_allow_lds(front, IQ_LDS_BYTES));
+  VVC_HIP(vvc_allow_lds(back, IQ_LDS_BYTES));
   VvcScratch sc(st);
   IqSetup s;
   if (const int rc = iq_setup(st, sc, (size_t)wgs * IR_WAVES, s)) return rc;
@@ -233,11 +258,11 @@ int vvcgpu_inter_resi_code_dq_batch(const vvc_pel* org_base, const vvc_pel* pred
   a.coef = iq_at<TCoeff>(ws, 0); a.recs = iq_at<vvcgpu_depquant_desc>(ws, lay.recs); a.list = iq_at<int>(ws, lay.list);
   a.count = s.count; a.nextCounters = s.nextCounters; a.levelExtent = (long long)level_extent;
   a.n = n; a.nRates = n_rates; a.writeRec = (flags & VVCGPU_INTER_RESI_WRITE_REC) ? 1 : 0; a.bd = bit_depth; a.cmin = clp_min; a.cmax = clp_max;
-  hipLaunchKernelGGL(inter_resi_dq_front_kernel, dim3(wgs), dim3(IR_THREADS), IQ_LDS_BYTES, st, a, s.tb);
+  hipLaunchKernelGGL(front, dim3(wgs), dim3(IR_THREADS), IQ_LDS_BYTES, st, a, s.tb);
   VVC_LAUNCH_CHECK_COUNTERS(st);
   if (const int rc = vvcgpu_depquant_listed_launch(a.coef, level_base, a.recs, a.list, a.count, n * IR_SLOTS, rates, bit_depth, abs_sum,
                                                    iq_at<unsigned>(ws, lay.dec), iq_at<unsigned char>(ws, lay.ctx), s.tb, st)) return rc;
-  hipLaunchKernelGGL(inter_resi_dq_back_kernel, dim3(wgs), dim3(IR_THREADS), IQ_LDS_BYTES, st, a, s.tb);
+  hipLaunchKernelGGL(back, dim3(wgs), dim3(IR_THREADS), IQ_LDS_BYTES, st, a, s.tb);
   VVC_LAUNCH_CHECK();
   return VVCGPU_OK;
 }

@@ -18,6 +18,9 @@
 //   back     the same wavefront-per-item walk: the dependent de-quantiser into the coefficient workspace, the inverse transform (RC_INV bodies) with
 //            resi' left in the tile, then clip(pred + resi') with the parked prediction to rec_base, xGetSSE(org, rec) and the count of the non-zero
 //            levels.  An item with abs_sum == 0 has resi' = 0.
+//   VVCGPU_INTRA_TU_DQ_TS  a 4x4 item with tr_hor == 3, the checkTransformSkip candidate of xRecurIntraCodingLumaQT (IntraSearch.cpp:1347-1412), in the
+//            same two walks: the scaling of dqpass_dev.h in place of the two transforms, everything else every item's.  The flag selects the kernels,
+//            ItqPass<true>'s.
 #include "common.h"
 #include "dist_dev.h"
 #include "dqpass_dev.h"
@@ -43,11 +46,23 @@ struct ItqArgs
 };
 
 // is the item served, and with which mode and filter decision?  The rule of intratu_dev.h; here also: level_off a multiple of 16 and not negative -- the
-// trellis workspace is indexed by it --, the levels inside level_extent, a rate table inside the array, a lambda above zero
+// trellis workspace is indexed by it --, the levels inside level_extent, a rate table inside the array, a lambda above zero.  TS (the call carries
+// VVCGPU_INTRA_TU_DQ_TS): tr_hor == 3 on a 4x4 block is the checkTransformSkip candidate (itq_is_ts), tr_ver ignored; every other rule holds for it
+template <bool TS>
+__device__ __forceinline__ bool itq_is_ts(const RcDesc& t) { return TS && t.tr_hor == 3 && t.w == 4 && t.h == 4; }
+template <bool TS>
 __device__ __forceinline__ bool itq_resolve(const ItqArgs& a, const vvcgpu_intra_desc& p, const RcDesc& t, const IqDq& q, int& mode, bool& filt)
 {
   auto also = [&] { return t.level_off >= 0 && (t.level_off & 15) == 0 && t.level_off <= a.levelExtent - (long long)t.w * t.h &&
                            q.rates_idx >= 0 && q.rates_idx < a.nRates && q.lambda > 0.0; };
+  if constexpr (TS)
+  {
+    // (the shared rule knows the transform types alone: DCT-II in its eyes.  A copy of the descriptor, not another argument of it_resolve: with one,
+    // intra_tu_code_kernel and the kernels of a call without the flag compile to other code, docs/MEASUREMENTS.md)
+    RcDesc u = t;
+    if (itq_is_ts<TS>(t)) { u.tr_hor = 0; u.tr_ver = 0; }
+    return it_resolve(a, p, u, also, mode, filt);
+  }
   return it_resolve(a, p, t, also, mode, filt);
 }
 // the chain descriptor of the item for the transform bodies: the residual (forward) or resi' (inverse) contiguous in the tile; the coefficients at the
@@ -61,97 +76,104 @@ __device__ __forceinline__ RcDesc itq_desc(const RcDesc& t)
 }
 
 // ---------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(ITQ_THREADS, 1) void intra_tu_dq_front_kernel(const ItqArgs a, const VvcTrTables tb)
+// The two kernels are static members of a class template over TS (the call carries VVCGPU_INTRA_TU_DQ_TS), not function templates, for the reason
+// given at IqPass in interresidq.hip: ItqPass<false>'s are, to the instruction, intra_tu_dq_front_kernel and intra_tu_dq_back_kernel of before the flag.
+template <bool TS>
+struct ItqPass
 {
-  extern __shared__ __align__(16) unsigned char smem[];
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const _Float16* const tab = rc_load_image<ITQ_THREADS>(smem, a.image, tid);   // below every wavefront walks its own items
-  const ItLds l = it_lds(smem, wave);
-  int* const fbScr = a.fbScratch + ((size_t)blockIdx.x * ITQ_WAVES + wave) * IQ_FB_INTS;
-  if (blockIdx.x == 0 && tid < VVC_CTR_INTS) a.nextCounters[tid] = 0;    // the counter set of the NEXT call on this stream (vvcgpu_counters)
-
-  // the wavefront's run in the trellis' work list: its served items are counted first, a lane per item
-  const int first = (int)blockIdx.x + (int)gridDim.x * wave, step = (int)gridDim.x * ITQ_WAVES;
-  int cnt = 0;
-  for (int item = first + lane * step; item < a.n; item += 64 * step)
+  static __global__ __launch_bounds__(ITQ_THREADS, 1) void front(const ItqArgs a, const VvcTrTables tb)
   {
-    int mode; bool filt;
-    cnt += itq_resolve(a, a.preds[item], a.tus[item], a.dq[item], mode, filt) ? 1 : 0;
-  }
-  int listAt = iq_reserve(a.count, cnt, lane);
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const _Float16* const tab = rc_load_image<ITQ_THREADS>(smem, a.image, tid);   // below every wavefront walks its own items
+    const ItLds l = it_lds(smem, wave);
+    int* const fbScr = a.fbScratch + ((size_t)blockIdx.x * ITQ_WAVES + wave) * IQ_FB_INTS;
+    if (blockIdx.x == 0 && tid < VVC_CTR_INTS) a.nextCounters[tid] = 0;    // the counter set of the NEXT call on this stream (vvcgpu_counters)
 
-  for (int item = first; item < a.n; item += step)
-  {
-    const vvcgpu_intra_desc p = a.preds[item];
-    const RcDesc t = a.tus[item];
-    const IqDq q = a.dq[item];
-    int mode; bool filt;
-    if (!itq_resolve(a, p, t, q, mode, filt)) { it_mark(a, item, lane); continue; }
-    const int w = t.w, h = t.h, lw = ilog2(w), samples = w * h;
-    it_predict(a, p, t, mode, filt, l, lane);
-    if (a.writePred && mode >= 0)
+    // the wavefront's run in the trellis' work list: its served items are counted first, a lane per item
+    const int first = (int)blockIdx.x + (int)gridDim.x * wave, step = (int)gridDim.x * ITQ_WAVES;
+    int cnt = 0;
+    for (int item = first + lane * step; item < a.n; item += 64 * step)
     {
-      Pel* dst = a.pred + t.pred_off;
-      for (int e = lane; e < samples; e += 64) dst[(ptrdiff_t)(e >> lw) * t.pred_stride + (e & (w - 1))] = l.tile[e];
+      int mode; bool filt;
+      cnt += itq_resolve<TS>(a, a.preds[item], a.tus[item], a.dq[item], mode, filt) ? 1 : 0;
     }
-    for (int e = lane; e < samples; e += 64) a.park[t.level_off + e] = l.tile[e];      // for the back (re-forming it there measured slower)
-    if (lane == 0)                                                        // the chain descriptor, the trellis record and its list entry
+    int listAt = iq_reserve(a.count, cnt, lane);
+
+    for (int item = first; item < a.n; item += step)
     {
-      *l.dS = itq_desc(t);
-      a.modeOut[item] = mode < 0 ? -1 : mode;
-      a.recs[item] = iq_record(t.level_off, t.qp, w, h, q, q.luma);
-      a.list[listAt] = item;
-    }
-    listAt++;
-    // org - pred over the prediction (four loads in flight: the item waits for one round trip per 256 samples)
-    const Pel* org = a.org + t.org_off;
-    for (int e0 = lane; e0 < samples; e0 += 256)
-    {
-      int ov[4];
-#pragma unroll
-      for (int u = 0; u < 4; u++)
+      const vvcgpu_intra_desc p = a.preds[item];
+      const RcDesc t = a.tus[item];
+      const IqDq q = a.dq[item];
+      int mode; bool filt;
+      if (!itq_resolve<TS>(a, p, t, q, mode, filt)) { it_mark(a, item, lane); continue; }
+      const int w = t.w, h = t.h, lw = ilog2(w), samples = w * h;
+      it_predict(a, p, t, mode, filt, l, lane);
+      if (a.writePred && mode >= 0)
       {
-        const int e = e0 + 64 * u;
-        ov[u] = e < samples ? (int)org[(ptrdiff_t)(e >> lw) * t.org_stride + (e & (w - 1))] : 0;
+        Pel* dst = a.pred + t.pred_off;
+        for (int e = lane; e < samples; e += 64) dst[(ptrdiff_t)(e >> lw) * t.pred_stride + (e & (w - 1))] = l.tile[e];
       }
-#pragma unroll
-      for (int u = 0; u < 4; u++)
+      for (int e = lane; e < samples; e += 64) a.park[t.level_off + e] = l.tile[e];      // for the back (re-forming it there measured slower)
+      if (lane == 0)                                                        // the chain descriptor, the trellis record and its list entry
       {
-        const int e = e0 + 64 * u;
-        if (e < samples) l.tile[e] = (short)(ov[u] - (int)l.tile[e]);
+        *l.dS = itq_desc(t);
+        a.modeOut[item] = mode < 0 ? -1 : mode;
+        a.recs[item] = iq_record(t.level_off, t.qp, w, h, q, q.luma);
+        a.list[listAt] = item;
       }
+      listAt++;
+      // org - pred over the prediction (four loads in flight: the item waits for one round trip per 256 samples)
+      const Pel* org = a.org + t.org_off;
+      for (int e0 = lane; e0 < samples; e0 += 256)
+      {
+        int ov[4];
+  #pragma unroll
+        for (int u = 0; u < 4; u++)
+        {
+          const int e = e0 + 64 * u;
+          ov[u] = e < samples ? (int)org[(ptrdiff_t)(e >> lw) * t.org_stride + (e & (w - 1))] : 0;
+        }
+  #pragma unroll
+        for (int u = 0; u < 4; u++)
+        {
+          const int e = e0 + 64 * u;
+          if (e < samples) l.tile[e] = (short)(ov[u] - (int)l.tile[e]);
+        }
+      }
+      wave_sync();
+      if (itq_is_ts<TS>(t)) iq_ts_forward(l.tile, a.coef + t.level_off, a.bd, lane);      // the scaled residual is the coefficient block
+      else iq_transform<RC_FWD>(l.dS, l.tile, nullptr, a.coef, a.bd, tab, tb, fbScr, lane);
+      wave_sync();                                                          // the tile and the descriptor are free again
     }
-    wave_sync();
-    iq_transform<RC_FWD>(l.dS, l.tile, nullptr, a.coef, a.bd, tab, tb, fbScr, lane);
-    wave_sync();                                                          // the tile and the descriptor are free again
   }
-}
 
-__global__ __launch_bounds__(ITQ_THREADS, 1) void intra_tu_dq_back_kernel(const ItqArgs a, const VvcTrTables tb)
-{
-  extern __shared__ __align__(16) unsigned char smem[];
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const _Float16* const tab = rc_load_image<ITQ_THREADS>(smem, a.image, tid);   // below every wavefront walks its own items
-  const ItLds l = it_lds(smem, wave);
-  int* const fbScr = a.fbScratch + ((size_t)blockIdx.x * ITQ_WAVES + wave) * IQ_FB_INTS;
-
-  for (int item = (int)blockIdx.x + (int)gridDim.x * wave; item < a.n; item += (int)gridDim.x * ITQ_WAVES)
+  static __global__ __launch_bounds__(ITQ_THREADS, 1) void back(const ItqArgs a, const VvcTrTables tb)
   {
-    const vvcgpu_intra_desc p = a.preds[item];
-    const RcDesc t = a.tus[item];
-    int mode; bool filt;
-    if (!itq_resolve(a, p, t, a.dq[item], mode, filt)) continue;          // (the front wrote the markers)
-    short* const backT = iq_back_tile(l.tile, t.w, t.h);
-    const bool coded = a.absSum[item] != 0u;                              // all levels zero: resi' is zero (piResi.fill(0), :1293)
-    if (coded) iq_decode(itq_desc(t), l.dS, l.tile, backT, a.level, a.coef, a.bd, tab, tb, fbScr, lane);
-    // clip(pred + resi') with the prediction as the front formed it to rec_base, xGetSSE(org, rec), the non-zero levels
-    int nz = 0;
-    const unsigned long long sse = iq_close(a.org + t.org_off, t.org_stride, a.park + t.level_off, backT, coded, a.rec + t.rec_off, t.rec_stride,
-                                            a.level + t.level_off, t.w, t.w * t.h, a.cmin, a.cmax, lane, &nz);
-    if (lane == 0) { a.dist[item] = sse; a.numSig[item] = (unsigned)nz; }
-    wave_sync();                                                          // the tile and the descriptor are free again
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const _Float16* const tab = rc_load_image<ITQ_THREADS>(smem, a.image, tid);   // below every wavefront walks its own items
+    const ItLds l = it_lds(smem, wave);
+    int* const fbScr = a.fbScratch + ((size_t)blockIdx.x * ITQ_WAVES + wave) * IQ_FB_INTS;
+
+    for (int item = (int)blockIdx.x + (int)gridDim.x * wave; item < a.n; item += (int)gridDim.x * ITQ_WAVES)
+    {
+      const vvcgpu_intra_desc p = a.preds[item];
+      const RcDesc t = a.tus[item];
+      int mode; bool filt;
+      if (!itq_resolve<TS>(a, p, t, a.dq[item], mode, filt)) continue;          // (the front wrote the markers)
+      short* const backT = iq_back_tile(l.tile, t.w, t.h);
+      const bool coded = a.absSum[item] != 0u;                              // all levels zero: resi' is zero (piResi.fill(0), :1293)
+      if (coded) iq_decode(itq_desc(t), l.dS, l.tile, backT, a.level, a.coef, a.bd, tab, tb, fbScr, lane, itq_is_ts<TS>(t));
+      // clip(pred + resi') with the prediction as the front formed it to rec_base, xGetSSE(org, rec), the non-zero levels
+      int nz = 0;
+      const unsigned long long sse = iq_close(a.org + t.org_off, t.org_stride, a.park + t.level_off, backT, coded, a.rec + t.rec_off, t.rec_stride,
+                                              a.level + t.level_off, t.w, t.w * t.h, a.cmin, a.cmax, lane, &nz);
+      if (lane == 0) { a.dist[item] = sse; a.numSig[item] = (unsigned)nz; }
+      wave_sync();                                                          // the tile and the descriptor are free again
+    }
   }
-}
+};
 
 }  // namespace
 
@@ -172,7 +194,7 @@ int vvcgpu_intra_tu_code_dq_batch(const vvc_pel* refs_base, const vvcgpu_intra_d
   VVC_CHECK_ARG(n >= 0, "%s: n %d", name, n);
   if (n == 0) return VVCGPU_OK;
   VVC_CHECK_ARG(refs_base && preds && org_base && rec_base && level_base && tus && dq && rates && abs_sum && num_sig && dist && mode_out && ws, "%s: null pointer", name);
-  VVC_CHECK_ARG((flags & ~(VVCGPU_INTRA_TU_WRITE_PRED | VVCGPU_INTRA_TU_NO_SMOOTHING)) == 0, "%s: unknown flags 0x%x", name, flags);
+  VVC_CHECK_ARG((flags & ~(VVCGPU_INTRA_TU_WRITE_PRED | VVCGPU_INTRA_TU_NO_SMOOTHING | VVCGPU_INTRA_TU_DQ_TS)) == 0, "%s: unknown flags 0x%x", name, flags);
   VVC_CHECK_ARG(pred_base || !(flags & VVCGPU_INTRA_TU_WRITE_PRED), "%s: null pointer (pred_base with VVCGPU_INTRA_TU_WRITE_PRED)", name);
   VVC_CHECK_ARG(clp_min <= clp_max && clp_min >= -32768 && clp_max <= 32767, "%s: clip range %d..%d", name, clp_min, clp_max);
   VVC_CHECK_ARG(((uintptr_t)preds & 15) == 0 && ((uintptr_t)tus & 15) == 0 && ((uintptr_t)dq & 7) == 0,
@@ -182,8 +204,12 @@ int vvcgpu_intra_tu_code_dq_batch(const vvc_pel* refs_base, const vvcgpu_intra_d
     return rc;
   hipStream_t st = (hipStream_t)stream;
   const int wgs = vvc_grid_cap(n, 1, 1);                                  // (the items are dealt to the workgroups first, then to their wavefronts: a short list spreads over the compute units)
-  VVC_HIP(vvc_allow_lds(intra_tu_dq_front_kernel, ITQ_LDS_BYTES));
-  VVC_HIP(vvc_allow_lds(intra_tu_dq_back_kernel, ITQ_LDS_BYTES));
+  // the flag selects the kernels: without it the front and the back are the ones that know no transform-skip item
+  const bool ts = (flags & VVCGPU_INTRA_TU_DQ_TS) != 0;
+  const auto front = ts ? ItqPass<true>::front : ItqPass<false>::front;
+  const auto back = ts ? ItqPass<true>::back : ItqPass<false>::back;
+  VVC_HIP(vvc_allow_lds(front, ITQ_LDS_BYTES));
+  VVC_HIP(vvc_allow_lds(back, ITQ_LDS_BYTES));
   VvcScratch sc(st);
   IqSetup s;
   if (const int rc = iq_setup(st, sc, (size_t)wgs * ITQ_WAVES, s)) return rc;
@@ -194,11 +220,11 @@ int vvcgpu_intra_tu_code_dq_batch(const vvc_pel* refs_base, const vvcgpu_intra_d
   a.count = s.count; a.nextCounters = s.nextCounters; a.levelExtent = (long long)level_extent;
   a.n = n; a.nRates = n_rates; a.writePred = (flags & VVCGPU_INTRA_TU_WRITE_PRED) ? 1 : 0; a.noSmoothing = (flags & VVCGPU_INTRA_TU_NO_SMOOTHING) ? 1 : 0;
   a.bd = bit_depth; a.cmin = clp_min; a.cmax = clp_max;
-  hipLaunchKernelGGL(intra_tu_dq_front_kernel, dim3(wgs), dim3(ITQ_THREADS), ITQ_LDS_BYTES, st, a, s.tb);
+  hipLaunchKernelGGL(front, dim3(wgs), dim3(ITQ_THREADS), ITQ_LDS_BYTES, st, a, s.tb);
   VVC_LAUNCH_CHECK_COUNTERS(st);
   if (const int rc = vvcgpu_depquant_listed_launch(a.coef, level_base, a.recs, a.list, a.count, n, rates, bit_depth, abs_sum, iq_at<unsigned>(ws, lay.dec),
                                                    iq_at<unsigned char>(ws, lay.ctx), s.tb, st)) return rc;
-  hipLaunchKernelGGL(intra_tu_dq_back_kernel, dim3(wgs), dim3(ITQ_THREADS), ITQ_LDS_BYTES, st, a, s.tb);
+  hipLaunchKernelGGL(back, dim3(wgs), dim3(ITQ_THREADS), ITQ_LDS_BYTES, st, a, s.tb);
   VVC_LAUNCH_CHECK();
   return VVCGPU_OK;
 }
