@@ -466,3 +466,272 @@ def search_bit31_planes(o, W, H, m, x0, y0, bw, bh):
     dx, dy = SEARCH_BIT31_MV
     ref[m + y0 + dy:m + y0 + dy + bh, m + x0 + dx:m + x0 + dx + bw] = 1
     return org, ref
+
+
+# ---- deblocking: inputs that take every filter decision at its threshold (tests/test_deblock_census_cpu.py counts them) ------------
+DBK_TC = np.array([0] * 18 + [1] * 9 + [2] * 4 + [3] * 4 + [4] * 3 + [5, 5, 6, 6, 7, 8, 9, 10, 11, 13, 14, 16, 18, 20, 22, 24, 26, 28, 30, 32, 34, 36, 38, 40,
+                                                                    42, 44, 46, 48])
+DBK_BETA = np.array([0] * 16 + list(range(6, 19)) + list(range(20, 90, 2)))
+DBK_QP_KINDS = ("uniform", "mid", "low", "high", "ends")
+
+
+def deblock_qp_map(rng, shape, kind):
+    """CU QPs of [-12, 63] (the reference's range at bit depth 10): 'uniform' over all of it; 'mid' 20..49 where tc and beta are both at work, one unit in five
+    uniform; 'low' -12..8 and 'high' 50..63 (the clamps of the table indices, chroma QPs beyond the mapping table); 'ends' a third of each"""
+    uni = rng.integers(-12, 64, shape)
+    if kind == "uniform":
+        q = uni
+    elif kind == "mid":
+        q = np.where(rng.random(shape) < 0.8, rng.integers(20, 50, shape), uni)
+    elif kind == "low":
+        q = rng.integers(-12, 9, shape)
+    elif kind == "high":
+        q = rng.integers(50, 64, shape)
+    elif kind == "ends":
+        q = np.choose(rng.integers(0, 3, shape), [rng.integers(-12, 9, shape), rng.integers(50, 64, shape), uni])
+    else:
+        raise ValueError(kind)
+    return q.astype(np.int8)
+
+
+def deblock_maps_wide(rng, w, h, qp_kind, keep_ver=1.0, keep_hor=1.0, all_set=False):
+    """deblock_maps(..., 'random') -- every BS / flag combination it allows -- with the QP maps of deblock_qp_map; keep_*: the share of edge bytes that
+    stay (a horizontal decision then sees samples that no vertical pass has touched); all_set: no byte is zero"""
+    ev, eh, _, _ = deblock_maps(rng, w, h, "random")
+    for m, keep in ((ev, keep_ver), (eh, keep_hor)):
+        if all_set:
+            m[(m & 3) == 0] |= 1
+            m[((m >> 2) & 3) < 2] = (m[((m >> 2) & 3) < 2] & 0xF3) | 8
+        m[rng.random(m.shape) >= keep] = 0
+    return ev, eh, deblock_qp_map(rng, ev.shape, qp_kind), deblock_qp_map(rng, ev.shape, qp_kind)
+
+
+def deblock_lattice_plane(rng, h, w, bd, step, spread, lattice=True):
+    """flat in 8 x 8 blocks: a level per 32 x 32 region anywhere in 0 .. 2^bd - 1 (the margins of a narrowed clip range included), the blocks of a region
+    within +-step of it.  Only lines 0 and 3 of a 4-line segment enter the luma decisions, so the samples at x % 4 in {1, 2} and y % 4 in {1, 2} -- m1, m2, m5, m6
+    of lines 1 and 2, in both directions -- vary freely by +-spread: segments that pass d < beta and the strong test on their smooth lines filter rough ones.
+    lattice=False (chroma, which takes no decision): every sample varies"""
+    mx = (1 << bd) - 1
+    by, bx = (h + 7) // 8, (w + 7) // 8
+    coarse = rng.integers(0, mx + 1, ((h + 31) // 32, (w + 31) // 32)).repeat(4, 0).repeat(4, 1)[:by, :bx]
+    a = np.clip(coarse + rng.integers(-step, step + 1, (by, bx)), 0, mx).repeat(8, 0).repeat(8, 1)[:h, :w]
+    yy, xx = np.mgrid[0:h, 0:w]
+    free = ((xx % 4 == 1) | (xx % 4 == 2)) & ((yy % 4 == 1) | (yy % 4 == 2)) if lattice else np.ones((h, w), bool)
+    a = np.where(free, np.clip(a + rng.integers(-spread, spread + 1, (h, w)), 0, mx), a)
+    return np.ascontiguousarray(a.astype(np.int16))
+
+
+def _dbk_weak_delta(s):
+    return (6 * s + 8) >> 4                 # delta of the weak filter across a step s between two flat sides
+
+
+def _dbk_step_for(t):
+    """the smallest |s| whose weak-filter delta is t (t may be negative)"""
+    s = np.arange(0, 6000) * (1 if t >= 0 else -1)
+    hit = np.nonzero(_dbk_weak_delta(s) == t)[0]
+    return int(s[hit[0]]) if hit.size else None
+
+
+DBK_TARGETS = ("d_beta", "d_beta_m1", "ds_thr", "ds_thr_m1", "dd_thr", "dd_thr_m1", "dm_thr", "dm_thr_m1", "side", "side_m1", "delta")
+
+
+def _dbk_solve_segment(rng, target, tc, beta, mx):
+    """4 lines x 8 samples (m0 .. m7) across one edge, relative to an arbitrary level, that put `target` on its threshold; None where tc / beta leave no room.
+    The sides are flat (m1 = m2 = m3 = P, m4 = m5 = m6 = Q), then: m1 = P + k gives dp = k, m6 = Q + k gives dq = k, m0 / m7 give the ds term, Q - P the
+    dm term and the weak filter's delta"""
+    r = np.zeros((4, 8), np.int64)
+    sg = lambda: int(rng.choice((-1, 1)))
+    dmThr = (5 * tc + 1) >> 1
+
+    def step(s, lines=range(4)):
+        for i in lines:
+            r[i, 4:] += s
+
+    def split(v, n):
+        cut = np.sort(rng.integers(0, v + 1, n - 1))
+        return np.diff(np.concatenate(([0], cut, [v])))
+
+    small = int(rng.integers(0, dmThr)) * sg() if dmThr > 0 else 0              # a step that passes the dm term
+    a, b = (0, 3) if rng.random() < 0.5 else (3, 0)                             # the line that carries the event, and the other decision line
+    if target in ("d_beta", "d_beta_m1"):
+        v = beta - (target == "d_beta_m1")
+        if v < 0:
+            return None
+        k = split(v, 4)
+        r[0, 1] += k[0] * sg(); r[0, 6] += k[1] * sg(); r[3, 1] += k[2] * sg(); r[3, 6] += k[3] * sg()
+        step(int(rng.integers(2, 3 + 2 * tc)) * sg())
+    elif target in ("ds_thr", "ds_thr_m1"):
+        v = (beta >> 3) - (target == "ds_thr_m1")
+        if v < 0 or (beta >> 3) < 1 or dmThr < 1:
+            return None
+        k = split(v, 2)
+        r[a, 0] += k[0] * sg(); r[a, 7] += k[1] * sg()
+        k = split(int(rng.integers(0, beta >> 3)), 2)
+        r[b, 0] += k[0] * sg(); r[b, 7] += k[1] * sg()
+        step(small)
+    elif target in ("dd_thr", "dd_thr_m1"):
+        v = (beta >> 2) - (target == "dd_thr_m1")
+        if v < 0 or v & 1 or (beta >> 3) < 1 or dmThr < 1:
+            return None
+        k = split(v >> 1, 2)
+        r[a, 1] += k[0] * sg(); r[a, 6] += k[1] * sg()
+        k = split(int(rng.integers(0, ((beta >> 2) + 1) >> 1)), 2)
+        r[b, 1] += k[0] * sg(); r[b, 6] += k[1] * sg()
+        step(small)
+    elif target in ("dm_thr", "dm_thr_m1"):
+        v = dmThr - (target == "dm_thr_m1")
+        if v < 0 or dmThr < 1 or (beta >> 3) < 1:
+            return None
+        step(v * sg())
+        if rng.random() < 0.5:                                                  # the other decision line well inside
+            step(-int(np.sign(r[0, 4])) * int(rng.integers(0, v + 1)), [b])
+    elif target in ("side", "side_m1"):
+        side = (beta + (beta >> 1)) >> 3
+        v = side - (target == "side_m1")
+        if v < 0 or tc < 1:
+            return None
+        k = split(v, 2)
+        j = 1 if rng.random() < 0.5 else 6
+        r[0, j] += k[0] * sg(); r[3, j] += k[1] * sg()
+        r[a, 0 if rng.random() < 0.5 else 7] += ((beta >> 3) + 1 + int(rng.integers(0, 4))) * sg()      # ds fails: the weak filter
+        step(int(rng.integers(2, 3 + 2 * tc)) * sg())
+    elif target == "delta":
+        if beta < 1:
+            return None
+        r[a, 0 if rng.random() < 0.5 else 7] += ((beta >> 3) + 1 + int(rng.integers(0, 4))) * sg()
+        for i in range(4):                                                      # every line its own step: |delta| at 10 tc - 1, 10 tc, 10 tc + 1, tc, tc + 1
+            t = int(rng.choice((10 * tc - 1, 10 * tc, 10 * tc + 1, tc, tc + 1))) * sg()
+            s = _dbk_step_for(t)
+            if s is None or abs(s) > mx:
+                s = _dbk_step_for((tc + 1) * sg())
+            step(s, [i])
+            r[i] -= int(rng.integers(0, 2)) * s                                 # P or Q stays at the common level
+    else:
+        raise ValueError(target)
+    if rng.random() < 0.5:                                                      # rough lines 1 and 2 behind smooth decision lines
+        spread = int(rng.choice((2, 8, 40, 200)))
+        r[1:3, [1, 2, 5, 6]] += rng.integers(-spread, spread + 1, (2, 4))
+    return r if r.max() - r.min() <= mx else None
+
+
+def deblock_threshold_plane(rng, h, w, ev, qpl, cfg):
+    """luma plane for VERTICAL edges alone (the caller zeroes edge_hor, or transposes everything): each 4-row segment of each edge of the 8-sample grid owns
+    samples x - 4 .. x + 3, draws one of DBK_TARGETS and gets the samples that put it there for the tc and beta its map bytes and cfg give (the tables
+    above restate LoopFilter.cpp:66-80)"""
+    bd = cfg["bd_luma"]
+    mx, scale = (1 << bd) - 1, 1 << (bd - 8)
+    Y = deblock_lattice_plane(rng, h, w, bd, 2 * scale, 4 * scale).astype(np.int64)
+    for x in range(8, w, 8):
+        for uy in range(h // 4):
+            e = int(ev[uy, x // 4])
+            bs = e & 3
+            if not bs:
+                continue
+            qp = (int(qpl[uy, x // 4 - 1]) + int(qpl[uy, x // 4]) + 1) >> 1
+            tc = int(DBK_TC[min(max(qp + 2 * (bs - 1) + 2 * cfg["tc_off"], 0), 65)]) * scale
+            beta = int(DBK_BETA[min(max(qp + 2 * cfg["beta_off"], 0), 63)]) * scale
+            r = _dbk_solve_segment(rng, DBK_TARGETS[int(rng.integers(0, len(DBK_TARGETS)))], tc, beta, mx)
+            if r is None:
+                continue
+            Y[4 * uy:4 * uy + 4, x - 4:x + 4] = r + int(rng.integers(-r.min(), mx - r.max() + 1))
+    return np.ascontiguousarray(Y.astype(np.int16))
+
+
+def deblock_transpose(c):
+    """the case mirrored at the diagonal: vertical edges become horizontal ones"""
+    t = dict(c, w=c["h"], h=c["w"], name=c["name"] + "-T")
+    for k in ("Y", "Cb", "Cr", "qpl", "qpc"):
+        t[k] = np.ascontiguousarray(c[k].T)
+    t["ev"], t["eh"] = np.ascontiguousarray(c["eh"].T), np.ascontiguousarray(c["ev"].T)
+    return t
+
+
+# bit depths (luma, chroma), beta / tc offsets (div 2), Cb / Cr QP offsets, narrowed clip range: 8, 9, 10 bit, one mixed pair, the offsets' corners
+DBK_CFGS = [(10, 10, 0, 0, 0, 0, False), (8, 8, 6, -6, 12, -12, True), (9, 9, -6, 6, -12, 12, False), (10, 8, 2, -1, 12, 12, True),
+            (8, 8, -6, -6, -12, -12, False), (10, 10, 6, 6, 3, -5, True), (9, 9, 0, 3, 12, 12, True), (10, 10, -3, 1, -12, -12, False)]
+# a narrowed clip range, different per component, in units of 2^(bd - 8)
+DBK_NARROW = ((16, 235), (9, 247), (27, 224))
+
+
+def deblock_cfg_dict(bdl, bdc, beta_off, tc_off, cb_off, cr_off, narrow):
+    bds = (bdl, bdc, bdc)
+    lo = [DBK_NARROW[i][0] << (bds[i] - 8) if narrow else 0 for i in range(3)]
+    hi = [(DBK_NARROW[i][1] << (bds[i] - 8)) + (3 if bds[i] > 8 else 0) if narrow else (1 << bds[i]) - 1 for i in range(3)]
+    return dict(bd_luma=bdl, bd_chroma=bdc, beta_off=beta_off, tc_off=tc_off, cb_off=cb_off, cr_off=cr_off, clp_min=lo, clp_max=hi)
+
+
+def deblock_cfg_struct(cfg):
+    import ctypes as C
+    from vvcsoftware_vtm_amd.abi import DeblockCfg
+    return DeblockCfg(cfg["bd_luma"], cfg["bd_chroma"], cfg["beta_off"], cfg["tc_off"], cfg["cb_off"], cfg["cr_off"],
+                      (C.c_int32 * 3)(*cfg["clp_min"]), (C.c_int32 * 3)(*cfg["clp_max"]))
+
+
+def _dbk_chroma(rng, c, spread):
+    bd, sc = c["cfg"]["bd_chroma"], 1 << (c["cfg"]["bd_chroma"] - 8)
+    for k in ("Cb", "Cr"):
+        c[k] = deblock_lattice_plane(rng, c["h"] // 2, c["w"] // 2, bd, 3 * sc, spread * sc, lattice=False)
+
+
+def deblock_lattice_case(seed, w, h, cfg, qp_kind, step, spread, keep_ver=1.0, all_set=False, wild=False):
+    """step / spread in units of 2^(bd - 8).  wild: one sample in 30 outside the bit depth, up to +-32767: among the free samples of the lattice (they reach
+    the filters of segments whose decision lines stay smooth) and anywhere"""
+    rng = np.random.default_rng(seed)
+    c = dict(name="lattice-%d-%dx%d" % (seed, w, h), w=w, h=h, cfg=cfg)
+    sc = 1 << (cfg["bd_luma"] - 8)
+    c["Y"] = deblock_lattice_plane(rng, h, w, cfg["bd_luma"], step * sc, spread * sc)
+    _dbk_chroma(rng, c, min(spread, 40))
+    if wild:
+        c["name"] = "wild-" + c["name"]
+        for k in ("Y", "Cb", "Cr"):
+            a = c[k]
+            yy, xx = np.mgrid[0:a.shape[0], 0:a.shape[1]]
+            free = ((xx % 4 == 1) | (xx % 4 == 2)) & ((yy % 4 == 1) | (yy % 4 == 2))
+            m = (rng.random(a.shape) < 0.12) & free | (rng.random(a.shape) < 0.004)
+            a[m] = rng.choice(np.array([-32767, -32768, -4000, -37, -1, (1 << cfg["bd_luma"]), 3000, 20000, 32767], np.int16), int(m.sum()))
+    c["ev"], c["eh"], c["qpl"], c["qpc"] = deblock_maps_wide(rng, w, h, qp_kind, keep_ver=keep_ver, all_set=all_set)
+    return c
+
+
+def deblock_threshold_case(seed, w, h, cfg, qp_kind, transposed):
+    """vertical-only form (edge_hor all zero), or built at h x w and transposed: a horizontal decision then never depends on an earlier vertical pass"""
+    rng = np.random.default_rng(seed)
+    if transposed:
+        w, h = h, w
+    c = dict(name="threshold-%d-%dx%d" % (seed, w, h), w=w, h=h, cfg=cfg)
+    c["ev"], c["eh"], c["qpl"], c["qpc"] = deblock_maps_wide(rng, w, h, qp_kind, keep_hor=0.0)
+    c["Y"] = deblock_threshold_plane(rng, h, w, c["ev"], c["qpl"], cfg)
+    _dbk_chroma(rng, c, 12)
+    return deblock_transpose(c) if transposed else c
+
+
+DBK_CONTENT_SIZES = ((136, 72), (200, 120))
+DBK_SPREADS = (3, 12, 48, 255)              # of the lattice's free samples, in units of 2^(bd - 8): a few units .. the whole range
+_dbk_cases = None
+
+
+def deblock_census_cases():
+    """the input set of tests/test_deblock_census_cpu.py and of the device tests that share it -> list of dicts (name, w, h, Y, Cb, Cr, ev, eh, qpl, qpc, cfg).
+    Built once; the tests copy what they filter"""
+    global _dbk_cases
+    if _dbk_cases is not None:
+        return _dbk_cases
+    out = []
+    n = 0
+    for (w, h) in DBK_CONTENT_SIZES:
+        for i, row in enumerate(DBK_CFGS):
+            cfg = deblock_cfg_dict(*row)
+            for j in range(2):
+                out.append(deblock_lattice_case(7000 + n, w, h, cfg, DBK_QP_KINDS[(n + (n // 5)) % 5], step=(1, 2, 4, 9)[(i + j) % 4], spread=DBK_SPREADS[(n // 2 + j) % 4],
+                                                keep_ver=(1.0, 0.3)[j]))
+                n += 1
+            for transposed in (False, True):
+                out.append(deblock_threshold_case(7000 + n, w, h, cfg, ("mid", "uniform", "mid", "high", "mid")[n % 5], transposed))
+                n += 1
+    # 8 x 8 has no interior edge; 16 x 8 / 8 x 16 one; 520 x 24: 66 blocks per block row, two wavefronts, the second one with two lanes
+    for k, (w, h) in enumerate(((8, 8), (16, 8), (8, 16), (520, 24), (520, 24))):
+        out.append(deblock_lattice_case(7900 + k, w, h, deblock_cfg_dict(*DBK_CFGS[(0, 3, 1, 5, 2)[k]]), "mid", 2, 48, all_set=w < 100))
+    out.append(deblock_lattice_case(7950, 136, 72, deblock_cfg_dict(*DBK_CFGS[0]), "mid", 2, 12, wild=True))
+    out.append(deblock_lattice_case(7951, 200, 120, deblock_cfg_dict(*DBK_CFGS[3]), "mid", 3, 48, wild=True))
+    _dbk_cases = out
+    return out
